@@ -13,9 +13,11 @@ Prints ONE JSON line on rank 0 (see the task contract): metric / value / rooflin
 already running under a launcher; after the timed regions rank 0 compares one complete output set with the CPU oracle
 ("checked": true -- outside every timed region).
 
-`value` is the median of the timed regions, each of exactly --steps steps, back to back (five by default, nine when --steps is
-below 100); `spread` carries min / max / the first region and all of them in order.  The roofline of the dominant kernel is the VALU one:
-these kernels are bound by vector-instruction issue, not by HBM.
+The --steps timed steps run as back-to-back regions (--regions, five by default, each of at least 100 steps: fewer regions when
+--steps is small); `value` and `ms_per_step` come from the median region's time per step, and `spread` carries min / max / the
+first region and all of them in order.  --dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs).
+The roofline of the dominant kernel is the VALU one: these kernels are bound by vector-instruction issue,
+not by HBM.
 """
 import argparse
 import glob
@@ -185,6 +187,51 @@ def oracle_check(frames, got, cores):
                        "the CPU oracle" % (B, B // 2) if not bad else "MISMATCH: " + ", ".join(sorted(bad)[:8]))
 
 
+MIN_REGION_STEPS = 100
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20240611
+
+
+def region_steps(steps, regions):
+    """The `steps` timed steps split into back-to-back regions: at most `regions`, each of at least MIN_REGION_STEPS steps (one
+    region when there are fewer), as even as they can be.  The sum is exactly `steps`."""
+    n = max(1, min(max(regions, 1), steps // MIN_REGION_STEPS))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+def dump_outputs(out_dir, got, B, cap=1000, limit=DUMP_LIMIT_BYTES):
+    """Writes the output set of one batch -- what a caller of orbx_extract_match_batch_device_async receives: keypoints,
+    descriptors and counts per frame, matches12 and nmatches per consecutive pair -- as float32 / float64 .npy files under
+    `out_dir`.  Slots past a frame's count (keypoints, descriptors, matches12) hold no result and are written as zeros (-1 for
+    matches12), so that two builds compare output for output.  When the whole batch exceeds `limit` bytes, a fixed seeded sample
+    of its pairs is written (both frames of each); frame_index / pair_index name the frames and pairs written."""
+    from orb_slam_tracking_amd import KEYPOINT_DTYPE
+    P = B // 2
+    per_pair = 2 * (cap * 7 * 4 + cap * 32 * 4 + 8 + 8) + cap * 4 + 8 + 8
+    if P * per_pair <= limit:
+        pairs = np.arange(P)
+    else:
+        pairs = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=max(1, limit // per_pair), replace=False))
+    fr = np.stack([2 * pairs, 2 * pairs + 1], 1).ravel()
+    n = np.asarray(got["n"], np.int32)[:B]
+    kp = np.frombuffer(np.ascontiguousarray(got["k"]).tobytes()[:B * cap * 28], KEYPOINT_DTYPE).reshape(B, cap)[fr]
+    keypoints = np.stack([kp[f].astype(np.float32) for f in KEYPOINT_DTYPE.names], -1)  # x y size angle response octave class_id
+    desc = np.asarray(got["d"], np.uint8)[:B * cap * 32].reshape(B, cap, 32)[fr].astype(np.float32)
+    m12 = np.asarray(got["m"], np.int32)[:P * cap].reshape(P, cap)[pairs].astype(np.float32)
+    valid = np.arange(cap)[None, :] < n[fr][:, None]
+    keypoints[~valid] = 0
+    desc[~valid] = 0
+    m12[~(np.arange(cap)[None, :] < n[2 * pairs][:, None])] = -1
+    arrays = {"keypoints": keypoints, "descriptors": desc, "n_keypoints": n[fr].astype(np.float64), "matches12": m12,
+              "nmatches": np.asarray(got["nm"], np.int32)[:P][pairs].astype(np.float64),
+              "frame_index": fr.astype(np.float64), "pair_index": pairs.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= limit
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def cpu_share():
     """Host cores this process may really use: cgroup quota if set, else the affinity mask; capped at 64."""
     n = len(os.sched_getaffinity(0))
@@ -312,11 +359,11 @@ def main():
     exit_code = 0
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps in all, split over the timed regions")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="frames per GPU per step")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of exactly --steps steps, back to back; `value` is their median "
-                    "(at least nine regions when --steps is below 100)")
+    ap.add_argument("--regions", type=int, default=5, help="back-to-back timed regions the --steps steps are split into (fewer when a "
+                    "region would hold less than %d steps); `value` is the median region's rate" % MIN_REGION_STEPS)
     ap.add_argument("--depth", type=int, default=4, help="pipeline depth of the stream-ordered call (orbx_set_pipeline_depth): whole "
                     "batches on this many lanes; 0 = the two-half-batches mode")
     ap.add_argument("--prime", type=int, default=16, help="untimed batches right after the context is created (initialisation of "
@@ -334,7 +381,12 @@ def main():
     ap.add_argument("--no-host-pipeline", action="store_true", help="skip the host-frame pipeline figure (orbx_extract_match_batch_host_async)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE configurations 3 and 5 and the 2000 x 2000 "
                     "brute-force match that follow the headline (N = 1, outside its timed regions)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(rank 0's batch: keypoints, descriptors, counts, matches12, nmatches) as DIR/<name>.npy, float32 / float64, at "
+                    "most 64 MB (a fixed seeded sample of pairs beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # before torch is imported or anything touches the GPU: start the ranks as fresh child processes (never an exec)
         raise SystemExit(self_launch(args.gpus))
@@ -423,20 +475,17 @@ def main():
         ext.profile_stages([dom])  # timed steps: events around the dominant kernel only (each pair costs stream time)
     ext.profile_reset()
 
-    def timed_region():
-        return run.timed_region(args.steps, cdev)
-
-    dt_first = timed_region()           # the contract's region: exactly --steps steps
-    prof = ext.profile_get()
-    # More regions of exactly --steps steps follow back to back; `value` is their MEDIAN.  On this pool the GPU pauses for ~10 ms
-    # about every 100 ms whatever runs on it (tools/hiccup.py; a plain torch matmul loop shows the same), so one short region --
-    # the driver's 20 steps are 17 ms -- is hit with probability ~1/4 and then reads 35 % low; short regions get more repeats.
-    nreg = max(args.regions, 1) if args.steps >= 100 else max(args.regions, 9)
-    region_dts = [dt_first] + [timed_region() for _ in range(nreg - 1)]
-    dt = sorted(region_dts)[len(region_dts) // 2]
+    # exactly --steps timed steps, as back-to-back regions; `value` is the MEDIAN region's rate.  On this pool the GPU pauses for
+    # ~10 ms about every 100 ms whatever runs on it (tools/hiccup.py; a plain torch matmul loop shows the same), so one short
+    # region is hit with probability ~1/4 and then reads 35 % low; the median of several regions is not.
+    reg_steps = region_steps(args.steps, args.regions)
+    dt_first = run.timed_region(reg_steps[0], cdev)
+    prof = ext.profile_get()             # (events of the first region)
+    region_dts = [dt_first] + [run.timed_region(n_, cdev) for n_ in reg_steps[1:]]
+    step_s = float(np.median([t / n_ for t, n_ in zip(region_dts, reg_steps)]))  # seconds per step, median region
     ext.profile_enable(False)
     if stage_prof is None:
-        stage_prof, stage_steps = prof, args.steps
+        stage_prof, stage_steps = prof, reg_steps[0]
     last = run.nstep - 1
     d_n, d_nm = run.outs[last % nout]["n"], run.outs[last % nout]["nm"]
     gathered_ok = None
@@ -446,9 +495,13 @@ def main():
 
     # not timed: the last batch's complete output set against the CPU oracle -- every rank its own shard, the
     # verdict reduced to rank 0; a mismatch makes the process exit non-zero behind the JSON line
+    got = None
+    if args.dump_outputs and rank == 0:  # (not timed) what the last timed step computed, before anything else runs on the outputs
+        got = {k_: v.cpu().numpy() for k_, v in run.outs[last % nout].items()}
+        dumped = dump_outputs(args.dump_outputs, got, B, cap)
     check_ok, check_what = None, "skipped (--no-check)"
     if not args.no_check:
-        got = {k_: v.cpu().numpy() for k_, v in run.outs[last % nout].items()}
+        got = got if got is not None else {k_: v.cpu().numpy() for k_, v in run.outs[last % nout].items()}
         try:  # (a rank whose checker cannot run must still reach the all_reduce below: ADVICE r04)
             check_ok, check_what = oracle_check(host_sets[last % nsets], got, max(1, cpu_share() // max(world, 1)))
         except Exception as ex:
@@ -494,7 +547,7 @@ def main():
         kern = max(("pyramid", "fast", "describe"), key=lambda s: dev_ms[s])
         launches = max(prof[kern][1], 1)
         avg_launch_ms = prof[kern][0] / launches
-        frames_per_launch = B * args.steps / launches
+        frames_per_launch = B * reg_steps[0] / launches
         kname = KERNEL_OF[kern]
         pmc, pmc_file = load_pmc()
         pk = (pmc or {}).get("per_frame", {}).get(kname)
@@ -517,7 +570,7 @@ def main():
                                          "frac": pk.get("valu_frac_single_stream")}
             # the whole step: VALU issue cycles of every kernel of the path per frame x frames / step time / peak
             tot_cycles = sum(v["valu_issue_cycles"] for v in pmc["per_frame"].values())
-            roof["step_valu_frac"] = tot_cycles * B * args.steps / dt / VALU_PEAK_SIMD_CYCLES
+            roof["step_valu_frac"] = tot_cycles * B / step_s / VALU_PEAK_SIMD_CYCLES
         else:
             roof["achieved"] = roof["frac"] = roof["traffic"] = None
         # secondary: the HBM view of the same launch (algorithmic bytes of SURVEY 8(d) and counter bytes against 8 TB/s)
@@ -527,7 +580,7 @@ def main():
                        "counter_GBs": roof["traffic"] / secs / 1e9 if roof.get("traffic") and secs > 0 else None,
                        "counter_frac": roof["traffic"] / secs / 1e9 / HBM_PEAK_GBS if roof.get("traffic") and secs > 0 else None,
                        "peak_GBs": HBM_PEAK_GBS,
-                       "whole_path_algorithmic_GBs": ab["total"] * B * world * args.steps / dt / 1e9}
+                       "whole_path_algorithmic_GBs": ab["total"] * B * world / step_s / 1e9}
         # the other extraction kernels, from the warmup steps' events (same formulas), for comparison
         others = {}
         for s2 in ("pyramid", "fast", "describe"):
@@ -542,13 +595,13 @@ def main():
                 ent["valu_frac"] = p2["valu_issue_cycles"] * fpl / (ms2 * 1e-3) / VALU_PEAK_SIMD_CYCLES
                 ent["hbm_counter_frac"] = (p2["fetch_bytes"] + p2["write_bytes"]) * fpl / (ms2 * 1e-3) / 1e9 / HBM_PEAK_GBS
             others[KERNEL_OF[s2]] = ent
-        rates = sorted(B * world * args.steps / t for t in region_dts)
+        rates = sorted(B * world * n_ / t for t, n_ in zip(region_dts, reg_steps))
         out = {
             "metric": "frames/sec (extract+match, 1000 feat, 640x480)",
-            "value": B * world * args.steps / dt,
+            "value": B * world / step_s,
             "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
+            "ms_per_step": step_s * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
             "config": {"workload": "640x480 gray frames, 1000 features, 8 levels, FAST 20/7; %d frames per GPU per step resident in "
@@ -560,17 +613,19 @@ def main():
                        "collective": ({"backend": args.backend, "world_size": dist.get_world_size(), "all_gathers": run.ngather_calls,
                                        "gathered_counts_ok": gathered_ok} if coll else None),
                        "parallelism": "frames sharded per GPU (%d ranks), RCCL all_gather of keypoint counts" % world},
-            "spread": {"regions": len(region_dts), "steps_per_region": args.steps, "median": rates[len(rates) // 2],
-                       "min": rates[0], "max": rates[-1], "first_region": B * world * args.steps / dt_first,
-                       "note": "`value` is the median region (each region is exactly --steps steps, back to back); the GPUs of this "
-                               "pool pause ~10 ms every ~100 ms, which a single short region either catches or not",
-                       "in_order": [round(B * world * args.steps / t) for t in region_dts]},
+            "spread": {"regions": len(region_dts), "steps_per_region": reg_steps, "median": float(np.median(rates)),
+                       "min": rates[0], "max": rates[-1], "first_region": B * world * reg_steps[0] / dt_first,
+                       "note": "`value` is the median region (the --steps timed steps split into back-to-back regions); the GPUs of "
+                               "this pool pause ~10 ms every ~100 ms, which a single short region either catches or not",
+                       "in_order": [round(B * world * n_ / t) for t, n_ in zip(region_dts, reg_steps)]},
             "roofline": roof,
             "roofline_other_kernels": others,
             "stage_ms_per_step": {s: stage_prof[s][0] / stage_steps for s in stage_prof},
             "stage_ms_source": "warmup steps, every stage bracketed by HIP events (sums over the lanes / half-batch streams); the "
                                "timed steps bracket only the dominant kernel",
         }
+        if args.dump_outputs:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         out["checked"] = bool(check_ok) if check_ok is not None else False
         out["check"] = check_what
         if c4w is not None:

@@ -9,6 +9,9 @@ image files; nothing at test time reads /root/reference).
                SearchForInitialization results for the `canonical` (1000,1.2,8,20,7) and `as_shipped` (2000,1.2,8,0,0)
                presets.  The reference itself cannot run here (no OpenCV), so these pin the ORACLE against regressions;
                parity with an OpenCV-linked build of the reference stays unpinned.
+  init_rgb_sample.npz  a fixed, seeded sample of 4096 pixels of each RGB init image (init<i>/yx: row, column;
+               init<i>/rgb: the three channels): lets tests/test_oracle.py::test_to_gray check that the gray init
+               fixtures are the conversion of the RGB originals.
 """
 import glob
 import os
@@ -30,6 +33,18 @@ def rgb2gray(a):
     return ((a[..., 0] * 4899 + a[..., 1] * 9617 + a[..., 2] * 1868 + 8192) >> 14).astype(np.uint8)
 
 
+def write_init_rgb_sample(n=4096, seed=2024):
+    rng = np.random.default_rng(seed)
+    out = {}
+    for i, f in enumerate(sorted(glob.glob(REF + "/demo/initImages/*.png"))):
+        rgb = np.array(Image.open(f).convert("RGB"))
+        flat = np.sort(rng.choice(rgb.shape[0] * rgb.shape[1], size=n, replace=False))
+        yx = np.stack([flat // rgb.shape[1], flat % rgb.shape[1]], 1).astype(np.int32)
+        out["init%d/yx" % i] = yx
+        out["init%d/rgb" % i] = rgb[yx[:, 0], yx[:, 1]]
+    np.savez_compressed(os.path.join(HERE, "init_rgb_sample.npz"), **out)
+
+
 def main():
     imgs = {}
     for i in range(4):
@@ -39,6 +54,7 @@ def main():
     for k, v in imgs.items():
         assert v.dtype == np.uint8 and v.ndim == 2, (k, v.shape, v.dtype)
     np.savez_compressed(os.path.join(HERE, "images.npz"), **imgs)
+    write_init_rgb_sample()
 
     gold = {}
     for pname, p in PRESETS.items():

@@ -268,7 +268,7 @@ def test_bench_gpus_n_launches_its_ranks():
     assert "bench.py needs a GPU" in p.stdout and "launch with torch.distributed.run" not in p.stdout, p.stdout[-2000:]
 
 
-def test_libm_overload_probe():
+def test_libm_overload_probe(tmp_path):
     """which libm function the reference's unqualified cos(angle) / pow(factor, float) call is decided by the
     headers in the translation unit.  tools/pin_opencv/libm_probe.cpp lets the compiler say it (the type of cos(1.0f)); with a real
     OpenCV it names the orbx_set_libm_variant to use.  Here, on this image's libstdc++: the reference's standard headers + <cmath>
@@ -276,23 +276,24 @@ def test_libm_overload_probe():
     import subprocess
     src = os.path.join(ROOT, "tools", "pin_opencv", "libm_probe.cpp")
     for flag, want in (("-DORBX_PROBE_CMATH", "ORBX_LIBM_DOUBLE"), ("-DORBX_PROBE_MATH_H", "ORBX_LIBM_FLOAT")):
-        exe = "/tmp/orbx_libm_probe%s" % flag[-6:]
+        exe = str(tmp_path / ("orbx_libm_probe%s" % flag[-6:]))
         p = subprocess.run(["g++", "-std=c++17", "-DORBX_PROBE_NO_OPENCV", flag, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         assert p.returncode == 0, p.stdout
         out = subprocess.run([exe], stdout=subprocess.PIPE, text=True).stdout
         assert out.strip().splitlines()[-1] == "orbx_set_libm_variant: " + want, out
 
 
-def test_pin_kit_compiles():
+def test_pin_kit_compiles(tmp_path):
     """tools/pin_opencv (the one-command diff of the oracle against a real OpenCV, for whoever has one) at least compiles: its only
     possible check in this image is the compile-check mock of the cv:: declarations it uses (tests/cpp/mock_opencv pins nothing)."""
     import subprocess
     p = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "tests", "cpp", "mock_opencv"),
                         os.path.join(ROOT, "tools", "pin_opencv", "pin_opencv.cpp")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert p.returncode == 0, p.stdout
-    p = subprocess.run([os.sys.executable, os.path.join(ROOT, "tools", "pin_opencv", "export_fixtures.py"), "/tmp/orbx_pin_fixtures"],
+    fixtures = tmp_path / "pin_fixtures"
+    p = subprocess.run([os.sys.executable, os.path.join(ROOT, "tools", "pin_opencv", "export_fixtures.py"), str(fixtures)],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert p.returncode == 0 and os.path.exists("/tmp/orbx_pin_fixtures/manifest.txt"), p.stdout
+    assert p.returncode == 0 and (fixtures / "manifest.txt").exists(), p.stdout
 
 
 def test_one_hip_runtime_whatever_the_import_order():
@@ -367,3 +368,56 @@ def test_binding_refuses_short_buffers(orbx):
     with pytest.raises(ValueError, match="matches12"):
         _need_batch(imgs, 16, W, H, W, W * H, k, d, n, cap, first[:8], first[:8] + 1, m[:10], nm, None)
     _need_batch(123456, 64, W, H, W, W * H, 1, 2, 3, cap)  # raw pointers: sizes are the caller's business
+
+
+def test_bench_regions_sum_to_steps():
+    """`--steps K` is the number of timed steps: the regions bench.py splits them into add up to exactly K."""
+    import importlib
+    bench = importlib.import_module("bench")
+    for steps in (1, 5, 19, 20, 39, 40, 99, 100, 101, 200, 1000, 1003):
+        for regions in (0, 1, 3, 5, 9):
+            r = bench.region_steps(steps, regions)
+            assert sum(r) == steps and 1 <= len(r) <= max(regions, 1) and max(r) - min(r) <= 1, (steps, regions, r)
+            assert len(r) == 1 or min(r) >= bench.MIN_REGION_STEPS, (steps, regions, r)
+    assert bench.region_steps(1000, 5) == [200] * 5 and bench.region_steps(200, 5) == [100, 100] and bench.region_steps(20, 5) == [20]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the output set of a batch as float32 / float64 .npy files, values exact, the slots past each count zeroed
+    (-1 in matches12); a batch beyond the size limit is written as a fixed seeded sample of whole pairs."""
+    import importlib
+    from orb_slam_tracking_amd import KEYPOINT_DTYPE
+    bench = importlib.import_module("bench")
+    B, cap = 8, 16
+    rng = np.random.default_rng(5)
+    kp = np.zeros(B * cap, KEYPOINT_DTYPE)
+    for f in ("x", "y", "size", "angle", "response"):
+        kp[f] = rng.random(B * cap).astype(np.float32) * 640
+    kp["octave"], kp["class_id"] = rng.integers(0, 8, B * cap), -1
+    got = {"k": kp.view(np.uint8).copy(), "d": rng.integers(0, 256, B * cap * 32).astype(np.uint8),
+           "n": rng.integers(0, cap + 1, B).astype(np.int32), "m": rng.integers(-1, cap, B // 2 * cap).astype(np.int32),
+           "nm": rng.integers(0, cap, B // 2).astype(np.int32)}
+    names = bench.dump_outputs(str(tmp_path / "all"), got, B, cap)
+    z = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in z.values())
+    assert np.array_equal(z["frame_index"], np.arange(B)) and np.array_equal(z["pair_index"], np.arange(B // 2))
+    assert np.array_equal(z["n_keypoints"], got["n"]) and np.array_equal(z["nmatches"], got["nm"])
+    for f in range(B):
+        n = got["n"][f]
+        for j, name in enumerate(KEYPOINT_DTYPE.names):
+            assert np.array_equal(z["keypoints"][f, :n, j], kp[f * cap:f * cap + n][name].astype(np.float32))
+        assert np.array_equal(z["descriptors"][f, :n], got["d"].reshape(B, cap, 32)[f, :n])
+        assert not z["keypoints"][f, n:].any() and not z["descriptors"][f, n:].any()
+    for p in range(B // 2):
+        n = got["n"][2 * p]
+        assert np.array_equal(z["matches12"][p, :n], got["m"].reshape(-1, cap)[p, :n]) and (z["matches12"][p, n:] == -1).all()
+    # over the limit: whole pairs, the same sample every time, within the limit
+    small = 3 * (2 * (cap * 7 * 4 + cap * 32 * 4 + 16) + cap * 4 + 16)
+    bench.dump_outputs(str(tmp_path / "a"), got, B, cap, limit=small)
+    bench.dump_outputs(str(tmp_path / "b"), got, B, cap, limit=small)
+    pa, pb = np.load(str(tmp_path / "a" / "pair_index.npy")), np.load(str(tmp_path / "b" / "pair_index.npy"))
+    assert len(pa) == 3 and np.array_equal(pa, pb)
+    fa = np.load(str(tmp_path / "a" / "frame_index.npy"))
+    assert np.array_equal(fa, np.stack([2 * pa, 2 * pa + 1], 1).ravel())
+    assert sum(os.path.getsize(str(tmp_path / "a" / (n + ".npy"))) - 128 for n in names) <= small
+    assert np.array_equal(np.load(str(tmp_path / "a" / "descriptors.npy")), z["descriptors"][fa.astype(int)])
