@@ -12,6 +12,7 @@ built and a HIP device is usable.  (The C++ drop-in classes live in include/orbx
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional, Sequence, Tuple
@@ -56,7 +57,7 @@ class _Stats(ctypes.Structure):
 
 
 def lib_path() -> str:
-    # ORBX_LIB (diagnostics): an instrumented build of the same sources, e.g. `make -C csrc VARIANT=octstamps EXTRA=-DORBX_OCT_STAMPS`
+    # ORBX_LIB (diagnostics): another build of the same sources, e.g. `make -C csrc VARIANT=name EXTRA=...` for an A/B comparison
     return os.environ.get("ORBX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liborbx.so")
 
 
@@ -183,19 +184,12 @@ def lib() -> ctypes.CDLL:
     return L
 
 
-KNOBS = ("no_bands", "no_tiles", "tiles_max_frames", "tiles_max_pixels", "pyr_bands", "pyr_gmax", "pyr_strips", "bands_min_frames", "desc_no_staged",
-         "desc_staged_max", "no_split", "lat_trace", "no_direct_out", "fast_wg", "fast_wg_max_cells", "fast_lds_pad", "fast_debug",
-         "desc_lds_pad", "match_no_general", "match_no_mfma", "oct_no_small", "oct_key64", "oct_split_min", "oct_no_big", "oct_big_depth", "oct_big_no_fallback", "octb_no_512", "oct_inst",
-         "oct_lds_pad", "multi_force_rccl")
+KNOBS = ("no_bands", "pyr_bands", "pyr_strips", "bands_min_frames", "no_split", "lat_trace", "fast_wg_max_cells", "match_no_general",
+         "match_no_mfma", "oct_big_depth", "oct_big_no_fallback", "multi_force_rccl")
 KNOB_UNSET = -(1 << 63)
 
 
 def _knob_value(name: str, text: str) -> int:
-    if name == "oct_inst":  # "2048,2048,1024,512,..." -> one hex digit per level, lowest digit = level 0
-        v = 0
-        for l, t in enumerate(text.split(",")[:16]):
-            v |= {"512": 1, "1024": 2, "2048": 3}.get(t.strip(), 0) << (4 * l)
-        return v
     try:
         return int(text)
     except ValueError:
@@ -207,6 +201,18 @@ def debug_set(name: str, value: Optional[int]) -> None:
     r = lib().orbx_debug_set(name.encode(), KNOB_UNSET if value is None else int(value))
     if r != 0:
         raise OrbxError(r, "orbx_debug_set(%r)" % name)
+
+
+@contextlib.contextmanager
+def knobs(**values: Optional[int]):
+    """Sets diagnostic knobs (`debug_set`) for the body of a `with` statement and unsets them afterwards, also when the body raises."""
+    try:
+        for name, value in values.items():
+            debug_set(name, value)
+        yield
+    finally:
+        for name in values:
+            debug_set(name, None)
 
 
 def _ptr(a) -> ctypes.c_void_p:

@@ -1082,23 +1082,22 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
   // whole pyramid in one launch (k_pyramid_bands) when every level meets the dword path's preconditions and the batch
   // is large enough to fill the device with (bands x frames) workgroups; otherwise one launch per level
   const bool noBands = knobOn(KNOB_NO_BANDS);  // diagnostics (orbx_debug_set)
-  const bool noTiles = knobOn(KNOB_NO_TILES);  // diagnostics: small batches launch the levels one by one
   // k_pyramid_tiles up to this many frames per launch: measured at 640x480 (tools/batch_sweep.py), one frame 0.108 against 0.117 ms
   // per synchronous call and 22.1 k against 18.3 k frames/s on four lanes, 8 frames level, 16 frames 133 k against 147 k on lanes
-  // (and up to eight VGA frames' worth of pixels: 8 frames of 3840x2160 take 0.81 ms in tiles, 0.41 ms level by level)
-  const int tilesMax = (int)knob(KNOB_TILES_MAX_FRAMES, 8);
-  const long long tilesMaxPx = std::min(knob(KNOB_TILES_MAX_PIXELS, kPyrTilesMaxPixels), kPyrTilesMaxPixels);
+  // (and up to eight VGA frames' worth of pixels, kPyrTilesMaxPixels: 8 frames of 3840x2160 take 0.81 ms in tiles, 0.41 ms level by
+  // level)
+  const int tilesMax = 8;
   const int bandsEnv = (int)knob(KNOB_PYR_BANDS, 0);  // diagnostics
   const int bandsMin = (int)knob(KNOB_BANDS_MIN_FRAMES, 0);  // diagnostics
   const int stripsEnv = (int)knob(KNOB_PYR_STRIPS, 0);       // diagnostics
   // rounds 2 - 5: from 32 frames per stream, or from 8 when the frames are large (16 frames 1080p: 0.43 -> 0.30 ms; 16 frames 640x480
   // were better off with the per-level launches then: 0.252 vs 0.263 ms per 32-frame call)
   // (round 5: with column strips also few large frames -- the four-frame halves of a 3840x2160 batch in 32 bands x 4 strips: 0.227 ms
-  // per batch against 0.352 level by level and 0.456 in 32 bands without strips; tools/exp_pyr_strips.sh)
+  // per batch against 0.352 level by level and 0.456 in 32 bands without strips; docs/history.md)
   // (round 6, with round 5's kernel -- row pairs, one group per thread, strips: from 9 frames, i.e. wherever the levels used to be
   // launched one by one.  Per synchronous call of 32 frames 640x480 = two halves of 16: pyramid stage 0.096 -> 0.068 ms, 136.5 k ->
   // 162.4 k frames/s; 24 frames: 107.6 k -> 128.9 k; 12 frames on one stream: 66.3 k -> 69.8 k, on four lanes 143 k -> 154 k;
-  // up to 8 frames k_pyramid_tiles stays (8: 53.0 k against 53.8 k, level; tools/exp_c4_small.py))
+  // up to 8 frames k_pyramid_tiles stays (8: 53.0 k against 53.8 k, level; docs/history.md))
   const bool enough = bandsMin > 0 ? n >= bandsMin : (n >= 9 || (n >= 2 && (long long)n * g.L[0].w * g.L[0].h >= (16ll << 20)));
   bool banded = nl > 1 && ctx->pyrInfo.ok && a.aligned0 && enough && !noBands;  // (dword loads: level 0 rows 4-byte aligned)
   PyrBands pb{};
@@ -1116,7 +1115,7 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
       while (S < ORBX_PYR_STRIPS_MAX && n * K * S < 384) S *= 2;
     // rows of more than 256 groups (frames wider than 1228 pixels): strips of 100 .. 200 groups take the one-group-per-thread
     // instance (56 VGPRs, four workgroups per CU), 768 workgroups for up to four frames, 512 or more otherwise.  With the round's
-    // final kernel, bands x strips (tools/exp_pyr_strips2.sh): 3840x2160 four-frame halves 32 x 4 0.203 ms, 16 x 8 0.194, 24 x 8
+    // final kernel, bands x strips (docs/history.md): 3840x2160 four-frame halves 32 x 4 0.203 ms, 16 x 8 0.194, 24 x 8
     // 0.180; eight frames on a lane 32 x 1 16.5 k frames/s, 16 x 4 17.3 k; 1920x1080 sixteen-frame halves 16 x 1 0.244 ms / 46.3 k
     // frames/s, 16 x 2 0.200 / 47.7 k, 8 x 4 0.195 / 48.4 k
     const int ng1 = (g.L[1].w + 3) / 4;
@@ -1136,7 +1135,7 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
     tm.stop(1);
     ctx->lastLaunch[0] = 1;
     ctx->lastLaunch[1] = pb.nBands * pb.nStrips;
-  } else if (nl > 1 && ctx->nPyrTiles > 0 && !noTiles && n <= tilesMax && (long long)n * g.L[0].w * g.L[0].h <= tilesMaxPx) {
+  } else if (nl > 1 && ctx->nPyrTiles > 0 && n <= tilesMax && (long long)n * g.L[0].w * g.L[0].h <= kPyrTilesMaxPixels) {
     // small batches: one launch, a workgroup per tile of a frame, the level chain through LDS
     StageTimer tm(ctx, ORBX_STAGE_PYRAMID, si, st);
     HIPCHK(launch_pyramid_tiles(st, n, a.dImg0, a.frameStride0, ctx->dPyr, g, ctx->dPyrTiles, ctx->dPyrTaps, ctx->nPyrTiles,
@@ -1179,9 +1178,7 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
                          ctx->candHintL, 0, &ctx->lastLaunch[3]));
     // small launches (the one-frame call): the descriptor kernel indexes the staging lists itself and does the bookkeeping
     // (DescStage) -- one kernel less on the call's critical path
-    const bool noStaged = knobOn(KNOB_DESC_NO_STAGED);  // diagnostics
-    const int stagedMax = (int)knob(KNOB_DESC_STAGED_MAX, ORBX_DESC_STAGED_MAX_UNITS);  // (experiments)
-    staged = !noStaged && n * g.nlevels <= stagedMax;
+    staged = n * g.nlevels <= ORBX_DESC_STAGED_MAX_UNITS;
     if (!staged)
       HIPCHK(launch_sel_compact(st, n, ctx->dSelStage, ctx->dNselLevel, oct, ctx->dSel, ctx->dNsel, a.dNuser, ctx->hNselDev, g.selCap,
                                 ctx->hFlagsDev + ctx->parity, dMax, ctx->hMaxNDev + si * ORBX_MAX_LEVELS));
@@ -1675,8 +1672,7 @@ int orbx_extract_batch(orbx_ctx* ctx, int n_frames, const uint8_t* imgs, int wid
                                 hipMemcpyHostToDevice, ctx->st));
     }
     if (latTrace) tt[1] = nowUs();
-    const bool noDirect = knobOn(KNOB_NO_DIRECT_OUT);  // diagnostics
-    const bool direct = B <= ctx->pinFrames && !noDirect;
+    const bool direct = B <= ctx->pinFrames;
     int r = extractCore(ctx, B, ctx->dIn, width, height, dstride, (long long)dfs, direct ? ctx->hKpsPinDev : ctx->dKps,
                         direct ? ctx->hDescPinDev : ctx->dDesc, cap, nullptr, nullptr);
     if (r != ORBX_OK) return r;

@@ -12,15 +12,6 @@
 #define ORBX_GRID_COLS 64     // FRAME_GRID_COLS, SlamTypes/Frame.hpp:16
 #define ORBX_GRID_ROWS 48     // FRAME_GRID_ROWS, SlamTypes/Frame.hpp:15
 
-// Wave priority of the latency-bound kernels (quadtree selection, Jacobi matcher, banded pyramid): their ~90 barrier-separated
-// phases issue a few instructions each and then wait; on the lanes they share every SIMD with the issue-bound FAST / descriptor
-// waves of other batches, behind which their few instructions queue.  ORBX_PRIO=n (build flag, experiment of round 4) raises them.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ORBX_PRIO)
-#define ORBX_SETPRIO() __builtin_amdgcn_s_setprio(ORBX_PRIO)
-#else
-#define ORBX_SETPRIO() do {} while (0)
-#endif
-
 namespace orbx {
 
 // geometry of one pyramid level for the current frame size

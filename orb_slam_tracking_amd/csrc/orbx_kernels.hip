@@ -269,35 +269,8 @@ __device__ __forceinline__ uint32_t dot2u16(uint32_t a, uint32_t b, uint32_t c) 
 __device__ __forceinline__ uint32_t mulHiU24(uint32_t a, uint32_t b) {  // v_mul_hi_u32_u24: bits 47:32 of the 24 x 24 bit product
   return (uint32_t)(((unsigned long long)(a & 0xffffffu) * (unsigned long long)(b & 0xffffffu)) >> 32);
 }
-// Diagnostic build only (-DORBX_PYR_STAMPS): per workgroup, s_memtime at the start, after the first barrier, and per level after
-// the rows and after the barrier; s_memrealtime at start and end; tools/pyr_stamps.py prints where a workgroup's time goes.
-#ifdef ORBX_PYR_STAMPS
-#define PYR_STAMP_WGS (1 << 14)
-__device__ uint32_t g_pyrStamps[PYR_STAMP_WGS * 40];
-#define PYR_STAMP(k)                                                                                          \
-  do {                                                                                                        \
-    if (threadIdx.x == 0 && stampWg_ < PYR_STAMP_WGS) g_pyrStamps[stampWg_ * 40 + (k)] = (uint32_t)__builtin_amdgcn_s_memtime(); \
-  } while (0)
-#define PYR_STAMP_RT(k)                                                                                       \
-  do {                                                                                                        \
-    if (threadIdx.x == 0 && stampWg_ < PYR_STAMP_WGS) g_pyrStamps[stampWg_ * 40 + (k)] = (uint32_t)__builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-extern "C" int orbx_diag_pyr_stamps(uint32_t* out, int nWgs) {  // out: nWgs x 40 dwords; nWgs < 0: clear the buffer
-  if (nWgs < 0) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_pyrStamps)) != hipSuccess) return -1;
-    return (int)hipMemset(p, 0, sizeof(uint32_t) * 40 * PYR_STAMP_WGS);
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pyrStamps), sizeof(uint32_t) * 40 * (size_t)nWgs);
-}
-#else
-#define PYR_STAMP(k) do { } while (0)
-#define PYR_STAMP_RT(k) do { } while (0)
-#endif
-#ifndef PYR_T
 #define PYR_T 512   // threads per workgroup: 512 fill their lanes with whole rows better than 256 (level 1 of 640x480: 469 of 512
                     // against 201 of 256) and take three fat bands per frame (3.5 % shared rows instead of 11 % with seven)
-#endif
 #define PYR_R 2   // output rows in flight per thread and step
 // GMAX = groups of 4 pixels a thread may own: 2 in general; 1 (round 5) when no level (strip) is wider than PYR_T groups -- every
 // frame up to 2457 pixels wide, and the strips of larger ones -- which keeps one set of column constants and row registers
@@ -307,15 +280,9 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
                                                        const uint4* __restrict__ ptab, const PyrBands pb) {
   // the band's PyrYRow entries of the current level (and, filled meanwhile, of the next one): a step's row constants then
   // cost an LDS read instead of a global load in front of the source loads that depend on them
-  ORBX_SETPRIO();
   extern __shared__ uint4 yrows[];  // [2][pb.maxRows]
   const int f = blockIdx.y + g.frame0, strip = (int)blockIdx.x / pb.nBands, band = (int)blockIdx.x - strip * pb.nBands, tid = threadIdx.x;
   const int nl = g.nlevels;
-#ifdef ORBX_PYR_STAMPS
-  const unsigned stampWg_ = blockIdx.y * gridDim.x + blockIdx.x;
-#endif
-  PYR_STAMP(0);
-  PYR_STAMP_RT(36);
   // column constants of this thread for level l
   struct Cols {
     uint32_t o[GMAX], sel[GMAX][6], cf[GMAX][4];
@@ -358,7 +325,6 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     if (tid < n) yrows[pb.maxRows + tid] = (ptab + pb.yoff[1])[r0 + tid];
   }
   __syncthreads();
-  PYR_STAMP(1);
   for (int l = 1; l < nl; l++) {
     const LevelGeom& S = g.L[l - 1];
     const LevelGeom& D = g.L[l];
@@ -460,22 +426,13 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     };
     if (l == 1 && f >= pb.safeFrom) rows(std::true_type{});
     else rows(std::false_type{});
-    PYR_STAMP(2 * l);
     if (tid < nextN) yrows[((l + 1) & 1) * pb.maxRows + tid] = nextY;
     if (l + 1 < nl) loadCols(l + 1, C);
     // this band of level l is the source of the band of level l + 1 in the same workgroup: the barrier's workgroup-scope
     // release/acquire is all that is needed (the CU's vector L1 is coherent for its own workgroup; an agent-scope
     // fence would write back / invalidate L2 once per level and workgroup and was measured 7x slower)
     __syncthreads();
-    PYR_STAMP(2 * l + 1);
   }
-  PYR_STAMP_RT(37);
-#ifdef ORBX_PYR_STAMPS
-  if (threadIdx.x == 0 && stampWg_ < PYR_STAMP_WGS) {
-    g_pyrStamps[stampWg_ * 40 + 38] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
-    g_pyrStamps[stampWg_ * 40 + 39] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // XCC_ID
-  }
-#endif
 }
 
 // =================================================================================================
@@ -722,15 +679,8 @@ __global__ __launch_bounds__(FAST_T) void k_fast(const uint8_t* __restrict__ img
                       // (LDS is granted in pieces of 1280 bytes on gfx950: at 640x480 the kernel's 6208 bytes are five of them, 25
                       // waves per CU; with a stack of 320 entries it took six and ran 21)
 #define FW_CORN 256   // corner list, entries
-#ifndef FW_CPW
 #define FW_CPW 1      // consecutive cells per wave (measured per 256 frames: 1: 0.275 ms, 2: 0.288, 4: 0.316, 8: 0.361: the tail grows)
-#endif
-#ifndef ORBX_FAST_FLATSKIP
-#define ORBX_FAST_FLATSKIP 1  // 0 = comparison build: every cell without a survivor is swept again at minThFAST (tools/bench_real_images.py)
-#endif
-#ifndef FW_XK
 #define FW_XK 16      // groups of FW_CPW cells per run of the XCD-aware order (8 .. 64 measured equal)
-#endif
 
 __device__ __forceinline__ int fwMbcnt(unsigned long long m) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -803,41 +753,6 @@ __device__ __forceinline__ int fwStrength(const uint32_t e) {
 
 typedef short short2v __attribute__((ext_vector_type(2)));
 
-// Diagnostic build only (-DORBX_FAST_STAMPS): per wave, s_memtime deltas of k_fast_wave's phases, HW_ID / XCC_ID and start /
-// end in s_memtime and s_memrealtime ticks, stored to a buffer nothing else reads (cdna_hip_programming.md section 7,
-// in-kernel stamps); tools/fast_stamps.py prints phase shares, residency per CU and the chip-wide occupancy timeline.  The
-// production build contains no stamp.
-#ifdef ORBX_FAST_STAMPS
-#define FW_STAMP_WAVES (1 << 18)
-__device__ uint32_t g_fastStamps[FW_STAMP_WAVES * 12];
-#define FW_STAMP(k)                                                                        \
-  do {                                                                                     \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();                          \
-    stampAcc_[k] += (uint32_t)(now_ - tPrev_);                                             \
-    tPrev_ = now_;                                                                         \
-  } while (0)
-#define FW_STAMP_INIT()                                                  \
-  unsigned long long tPrev_ = __builtin_amdgcn_s_memtime();              \
-  const uint32_t tStart_ = (uint32_t)tPrev_;                             \
-  const uint32_t rStart_ = (uint32_t)__builtin_amdgcn_s_memrealtime();   \
-  uint32_t stampAcc_[4] = {0u, 0u, 0u, 0u}
-#define FW_STAMP_FLUSH()                                                                                                  \
-  do {                                                                                                                    \
-    const unsigned wid_ = (blockIdx.y * gridDim.x + blockIdx.x) & (FW_STAMP_WAVES - 1);                                   \
-    if (lane == 0) {                                                                                                     \
-      *reinterpret_cast<uint4*>(&g_fastStamps[wid_ * 12]) = make_uint4(stampAcc_[0], stampAcc_[1], stampAcc_[2], stampAcc_[3]); \
-      *reinterpret_cast<uint4*>(&g_fastStamps[wid_ * 12 + 4]) =                                                          \
-          make_uint4(__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)),                                        \
-                     __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)), tStart_, (uint32_t)__builtin_amdgcn_s_memtime()); \
-      *reinterpret_cast<uint4*>(&g_fastStamps[wid_ * 12 + 8]) = make_uint4(rStart_, (uint32_t)__builtin_amdgcn_s_memrealtime(), 0u, 0u); \
-    }                                                                                                                    \
-  } while (0)
-#else
-#define FW_STAMP(k) do {} while (0)
-#define FW_STAMP_INIT() do {} while (0)
-#define FW_STAMP_FLUSH() do {} while (0)
-#endif
-
 // TS = bytes per LDS tile row and per strength-map row: 48 when every cell image of the geometry is at most 12 dwords
 // wide (cells of ~36 px: every frame size from VGA up), else 64.
 // One wave = one workgroup = FW_CPW consecutive cells: single-wave workgroups retire on their own (a 4-wave workgroup holds
@@ -876,7 +791,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   // cells, about one cell row of the lowest level): horizontally adjacent cells, which overlap by 6 px and share cache lines,
   // are fetched through one L2 (HBM reads 1.89 -> 0.5 MB per frame), while every XCD still gets cells of all levels -- a
   // contiguous eighth of the cell list per XCD left the XCD with the small, corner-dense upper levels working twice as long
-  // as the others (measured: tools/fast_stamps.py).  The run -> XCD assignment rotates with the frame.
+  // as the others (measured: docs/history.md).  The run -> XCD assignment rotates with the frame.
   const int nGroups = (g.nCellsTotal + FW_CPW - 1) / FW_CPW;
   const int xq = (int)((blockIdx.x + blockIdx.y) & 7u), xi = (int)(blockIdx.x >> 3);
   const int grp = ((xi / FW_XK) * 8 + xq) * FW_XK + (xi % FW_XK);
@@ -886,7 +801,6 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   // the workgroups dispatched last are the launch's tail -- with the light level-0 cells there, 0.202 - 0.203 against 0.206 - 0.207 ms
   // alone per 256 frames, round 6)
   const int cid0 = (nGroups - 1 - grp) * FW_CPW, cid1 = min(cid0 + FW_CPW, g.nCellsTotal);
-  FW_STAMP_INIT();
   for (int cid = cid0; cid < cid1; cid++) {
   const FastCell c = cells[cid];  // wave-uniform: one s_load_dwordx8
   int* const myCount = cellCount + (long long)f * g.nCellsTotal + cid;
@@ -925,10 +839,6 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
     for (int i = lane; i < (ih + 2) * (TS / 16); i += 64) s128[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   __builtin_amdgcn_wave_barrier();  // (LDS operations of one wave execute in order; this only pins the compiler's order)
-#ifdef ORBX_FAST_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);  // charge the staging phase with its loads
-#endif
-  FW_STAMP(0);
 
   constexpr int RS = TS;
   // a pixel's tile offset is o = (py + 3) * TS + xoff + px + 3; it is carried as e = tileAddr + o - (3 * TS + 3), the LDS address
@@ -975,7 +885,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
     // passes the quick reject at minThFAST iff e < iniTh - minTh, so a cell whose sweep ends `flat` with every minimum at or above
     // that difference could not list a single pixel at minThFAST and is not swept again.  Pixels beyond a row's end and idle lanes
     // are not masked out of the minimum: a false "some pixel passes" only costs the second sweep, which then decides as before.
-    bool flat = pass == 0 && ORBX_FAST_FLATSKIP;
+    bool flat = pass == 0;
     short2v looseMin = {0x7fff, 0x7fff};
     // evaluates the `cnt` newest entries of the survivor stack (64, or what is left at the end): exact strength; corners
     // (s > th) enter the strength map and the corner list
@@ -1062,11 +972,9 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
         pos += dPos;
         pos = min(pos, pos + wrapK);
       }
-      FW_STAMP(1);
       if (nList > 0) flush(nList);
     }
     __builtin_amdgcn_wave_barrier();
-    FW_STAMP(2);
     // ---- in-cell NMS on the strength map; survivors are the cell's keypoints ----
     auto nms = [&](const uint32_t eIn, const bool act) {
       const uint32_t e = act ? eIn : eIdle;
@@ -1106,7 +1014,6 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
         if (px >= iw) { px -= iw; e += (uint32_t)(TS - iw); }
       }
     }
-    FW_STAMP(3);
     // cpp:1109-1123: the cell is retried at minThFAST only if it yielded nothing at iniThFAST
     if (nOut > 0 || pass == 1 || g.minTh >= g.iniTh) break;
     {  // no pixel was listed and none passes the quick reject at minThFAST either
@@ -1117,18 +1024,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   if (lane == 0) *myCount = min(nOut, segCap);  // nOut <= segCap: NMS survivors are never 8-neighbours
   __builtin_amdgcn_wave_barrier();  // the next cell's staging stores come after this cell's last LDS reads
   }  // cells of this wave
-  FW_STAMP_FLUSH();
 }
-#ifdef ORBX_FAST_STAMPS
-extern "C" int orbx_diag_fast_stamps(uint32_t* out, int nWaves) {  // out: nWaves x 12 dwords; nWaves < 0: clear the buffer
-  if (nWaves < 0) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_fastStamps)) != hipSuccess) return -1;
-    return (int)hipMemset(p, 0, sizeof(uint32_t) * 12 * FW_STAMP_WAVES);
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fastStamps), sizeof(uint32_t) * 12 * (size_t)nWaves);
-}
-#endif
 
 // =================================================================================================
 // K4+K5+K6  orientation + patch-local Gaussian + steered BRIEF per keypoint.
@@ -1154,38 +1050,15 @@ __device__ __forceinline__ int reflect101(int p, int n) {
   return p;
 }
 
-// cos / sin of x in [0, 2 pi + eps] (a keypoint angle in radians) in f64, ~1 ulp: quadrant reduction with a two-term pi/2
-// and the fdlibm kernel polynomials, fused multiply-adds written out.  The general-range sincos of the device library costs
-// ~110 f64 instructions per call (it also carries the huge-argument path); this one ~35.  What the descriptor needs is the
-// value rounded to f32, cpp:173-174; tests/test_gpu_parity.py::test_sincos_matches_libm sweeps 3 M angles against libm.
-__device__ __forceinline__ void sincosSmall(double x, double* sn, double* cs) {
-  const double k = rint(x * 6.36619772367581382433e-01);                   // nearest multiple of pi/2: 0 .. 4
-  double r = fma(-k, 1.57079632679489655800e+00, x);                       // pi/2 high part: exact product for k <= 4
-  r = fma(-k, 6.12323399573676603587e-17, r);                              // pi/2 low part
-  const double z = r * r;
-  // __kernel_sin / __kernel_cos (fdlibm), |r| <= pi/4
-  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
-               S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
-               C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-  const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, S6, S5), S4), S3), S2), S1);
-  const double sr = fma(z * r, ps, r);
-  const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, C6, C5), C4), C3), C2), C1);
-  const double hz = 0.5 * z;
-  const double w = 1.0 - hz;
-  const double cr = w + (((1.0 - w) - hz) + fma(z * z, pc, 0.0));
-  const int q = (int)k & 3;
-  const double s0 = (q & 1) ? cr : sr, c0 = (q & 1) ? sr : cr;
-  *sn = (q & 2) ? -s0 : s0;
-  *cs = ((q + 1) & 2) ? -c0 : c0;
-}
-
-// The same values from a 256-entry table (round 4): x = k pi / 128 + r with |r| <= pi / 256, sin / cos of k pi / 128 as correctly
-// rounded doubles (orbx_sincos_tab.inc), three-term Taylor polynomials for sin r and cos r - 1 (next terms r^9 / 9! and
-// r^8 / 8!: below 2^-80) and the addition theorems -- ~17 f64 instructions instead of ~33 (no 6-term kernels, no quadrant
-// selects).  In k_describe_patch the angle is the same in all 64 lanes (one keypoint per wave), so the table entry comes through
-// one scalar load (UNIFORM).  What matters is the value ROUNDED TO F32: tools/sincos_exhaustive.py compares it with the
-// oracle's (float)cos((double)a) / (float)sin((double)a) for EVERY f32 angle in [0, 360] (1.13e9 values).
+// cos / sin of x in [0, 2 pi + eps] (a keypoint angle in radians) in f64 from a 256-entry table (round 4): x = k pi / 128 + r
+// with |r| <= pi / 256, sin / cos of k pi / 128 as correctly rounded doubles (orbx_sincos_tab.inc), three-term Taylor polynomials
+// for sin r and cos r - 1 (next terms r^9 / 9! and r^8 / 8!: below 2^-80) and the addition theorems -- ~17 f64 instructions,
+// against ~110 for the general-range sincos of the device library (it also carries the huge-argument path) and ~33 for the
+// quadrant reduction with the fdlibm kernel polynomials that rounds 2 and 3 used.  In k_describe_patch the angle is the same in
+// all 64 lanes (one keypoint per wave), so the table entry comes through one scalar load (UNIFORM).  What matters is the value
+// ROUNDED TO F32 (cpp:173-174): tools/sincos_exhaustive.py compares it with the oracle's (float)cos((double)a) /
+// (float)sin((double)a) for EVERY f32 angle in [0, 360] (1.13e9 values); tests/test_gpu_parity.py::test_sincos_matches_libm
+// sweeps 3 M angles against libm.
 #include "orbx_sincos_tab.inc"
 template <bool UNIFORM>
 __device__ __forceinline__ void sincosTable(double x, double* sn, double* cs) {
@@ -1202,11 +1075,6 @@ __device__ __forceinline__ void sincosTable(double x, double* sn, double* cs) {
   *sn = fma(ck, sr, fma(sk, cm1, sk));
   *cs = fma(-sk, sr, fma(ck, cm1, ck));
 }
-#ifdef ORBX_SINCOS_POLY  // (build flag: the round-2 / 3 evaluation, for comparison)
-#define ORBX_SINCOS(x, sn, cs, uniform) sincosSmall(x, sn, cs)
-#else
-#define ORBX_SINCOS(x, sn, cs, uniform) sincosTable<uniform>(x, sn, cs)
-#endif
 
 // ORBX_LIBM_FLOAT (orbx_set_libm_variant): cos(angle) / sin(angle) of cpp:174 read as cosf / sinf -- glibc >= 2.28's f64-polynomial
 // algorithm (sysdeps/ieee754/flt-32/s_sincosf.h, s_sinf.c, s_cosf.c; constants of s_sincosf_data.c), which is not correctly
@@ -1306,40 +1174,12 @@ constexpr IcTables makeIcTables() {
 }
 __device__ const IcTables d_ic = makeIcTables();
 
-#ifndef ORBX_DESC_EXP
-#define ORBX_DESC_EXP 0      // 3 = diagnostic build without the window fetch (timing only: the kernel's issue bound; tools/exp_desc_fetch.sh)
-#endif
-#ifndef ORBX_DESC_LOADMAP
-#define ORBX_DESC_LOADMAP 0  // window staging: 0 = lane is a window row (three 16-byte loads per lane), 1 = lane is a (row, 16-byte piece) slot
-#endif
-#ifndef DESC_WAVES
 #define DESC_WAVES 3   // keypoints (= waves) per workgroup: consecutive keypoints of a frame's list are spatially close, so
                        // putting them on one CU lets their overlapping windows hit in that CU's L1 (1: 0.44 ms, 2: 0.38,
                        // 3: 0.365, 4: 0.39, 8: 0.44, 16: 0.63 per 256 frames; 3 slices of 5.8 KB keep 27 waves per CU)
-#endif
 // GV = Gaussian Q8 tap set (orbx_set_opencv_variant): 0 = [18,34,48,56,48,34,18] (error diffusion, sum 256: OpenCV >= 4.1.1 /
 // 3.4.7), 1 = [18,34,49,55,49,34,18] (every tap rounded, sum 257: the bit-exact path of 3.4.1 .. 4.1.0 and the integer filter
 // before it; a sum of 2^24 or more saturates to 255)
-// Diagnostic build only (-DORBX_DESC_STAMPS): per wave, s_memtime at the start, when the window loads have landed, after
-// IC_Angle, after the horizontal / vertical blur passes and at the end; tools/desc_stamps.py prints the shares.
-#ifdef ORBX_DESC_STAMPS
-#define DS_STAMP_WAVES (1 << 18)
-__device__ uint32_t g_descStamps[DS_STAMP_WAVES * 8];
-#define DS_STAMP(k)                                                                                     \
-  do {                                                                                                  \
-    if (lane == 0 && dsWave_ < DS_STAMP_WAVES) g_descStamps[dsWave_ * 8 + (k)] = (uint32_t)__builtin_amdgcn_s_memtime(); \
-  } while (0)
-extern "C" int orbx_diag_desc_stamps(uint32_t* out, int nWaves) {  // out: nWaves x 8 dwords; nWaves < 0: clear the buffer
-  if (nWaves < 0) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_descStamps)) != hipSuccess) return -1;
-    return (int)hipMemset(p, 0, sizeof(uint32_t) * 8 * DS_STAMP_WAVES);
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_descStamps), sizeof(uint32_t) * 8 * (size_t)nWaves);
-}
-#else
-#define DS_STAMP(k) do { } while (0)
-#endif
 
 // The 512 rotated sample points lie in the disc r^2 + c^2 <= 365 around the keypoint ((13, 13) is the farthest pattern point:
 // 18.38, and rounding moves a point by at most 0.71), not in the whole 37 x 37 square.  A (row pair, 4-column) item of the
@@ -1406,7 +1246,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
   // (the wave's index as a scalar: the keypoint record then comes through a scalar load, beside the count's)
   const int i = grp * DESC_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // (the keypoint record is fetched together with the frame's count, not behind it: count, record and window were three
-  // dependent global loads and, by tools/desc_stamps.py, 63 % of a wave's lifetime)
+  // dependent global loads and, by the cycle stamps of docs/history.md, 63 % of a wave's lifetime)
   SelKp k;
   if constexpr (STAGED) {
     // keypoint i of the level-major order = entry i - (keypoints of the levels below) of its level's staging list; the counts of
@@ -1426,7 +1266,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
     k = ds.selStage[(long long)f * ds.selStride + ds.selOff[kl] + (i - off)];
   } else {
     // (both loads are issued before either is waited for: the compiler sinks the record's load behind the count's branch otherwise,
-    // and the wave's chain of dependent loads is what its lifetime is made of -- tools/desc_stamps.py)
+    // and the wave's chain of dependent loads is what its lifetime is made of -- docs/history.md)
     const unsigned long long kraw = *reinterpret_cast<const unsigned long long*>(&sel[(long long)f * g.selCap + min(i, g.selCap - 1)]);
     const int cnt = nsel[f];
     unsigned long long kuse = kraw;
@@ -1435,10 +1275,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
     k.x = (uint16_t)(kuse & 0xffff); k.y = (uint16_t)((kuse >> 16) & 0xffff); k.level = (uint8_t)((kuse >> 32) & 0xff);
     k.response = (uint8_t)((kuse >> 40) & 0xff); k.pad = 0;
   }
-#ifdef ORBX_DESC_STAMPS
-  const unsigned dsWave_ = (unsigned)((blockIdx.y * gridDim.x + blockIdx.x) * DESC_WAVES + (threadIdx.x >> 6));
-#endif
-  DS_STAMP(0);
   // Loads that do not depend on the keypoint are issued first, so that their latency runs under the window fetch: the
   // disc-row weights of IC_Angle (lane = disc row) and this lane's four point pairs of the BRIEF pattern.
   const int icRow = min(lane, 30), icAv = icRow < 15 ? 15 - icRow : icRow - 15;
@@ -1474,12 +1310,8 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
   {
     if (lane == 0) { msum[0] = 0; msum[1] = 0; }
     const bool rowsInside = aligned && ax >= 0 && ax + 48 <= w;  // (uniform) no staged dword crosses the level's left / right side
-#if ORBX_DESC_EXP == 3  // TIMING ONLY: no window fetch at all (the kernel's issue bound)
-    if (false)
-#endif
     if (rowsInside) {
       typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-#if ORBX_DESC_LOADMAP == 0
       if (lane < PW_ROWS) {
         int yy = ky - 21 + lane;
         yy = yy < 0 ? -yy : yy; yy = yy >= h ? 2 * h - 2 - yy : yy;  // REFLECT_101 (a keypoint is at least 19 px from the border)
@@ -1491,19 +1323,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
         dst[0] = q0.x; dst[1] = q0.y; dst[2] = q0.z; dst[3] = q0.w; dst[4] = q1.x; dst[5] = q1.y; dst[6] = q1.z; dst[7] = q1.w;
         dst[8] = q2.x; dst[9] = q2.y; dst[10] = q2.z; dst[11] = q2.w;
       }
-#else  // (experiment: slot = (row, 16-byte piece), 129 slots over the lanes of three instructions)
-#pragma unroll
-      for (int t = 0; t < 3; t++) {
-        const int idx = t * 64 + lane, r = idx / 3, c = idx - 3 * r;
-        if (idx < 3 * PW_ROWS) {
-          int yy = ky - 21 + r;
-          yy = yy < 0 ? -yy : yy; yy = yy >= h ? 2 * h - 2 - yy : yy;
-          const u32x4_a4 q = *reinterpret_cast<const u32x4_a4*>(img + (uint32_t)(yy * stride + ax + 16 * c));
-          uint32_t* dst = raw + r * PW_WORDS + 4 * c;
-          dst[0] = q.x; dst[1] = q.y; dst[2] = q.z; dst[3] = q.w;
-        }
-      }
-#endif
     } else {
       // the window crosses the level's left / right side (or level 0 is not dword-aligned): lanes 0..51 = 4 rows x 13 dwords per
       // step; dwords inside the level by dword loads, the others byte by byte with REFLECT_101
@@ -1537,10 +1356,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
       }
     }
   }
-#ifdef ORBX_DESC_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);  // charge the staging phase with its loads
-#endif
-  DS_STAMP(1);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- IC_Angle (cpp:103-159) on the un-blurred window: pixel (u, v) is row 21+v, byte s+21+u.  Lane = disc row v;
@@ -1568,7 +1383,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
   __builtin_amdgcn_wave_barrier();
   const int m10 = msum[0], m01 = msum[1];
   const float angle = fast_atan2_deg((float)m01, (float)m10);
-  DS_STAMP(2);
   // ---- horizontal pass: blurred column c (x = kx-18+c) uses window bytes s+c .. s+c+6 of the staged row.
   //      Item = (row pair, group of 4 columns): 4 dwords per row cover the 10 bytes the 4 columns need; the 190 items of
   //      the sampling disc (d_descHItems) in 3 steps.
@@ -1612,7 +1426,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
       default: hpass(std::integral_constant<int, 3>{}); break;
     }
   }
-  DS_STAMP(3);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- vertical pass + rounding with v_dot2_u32_u16 on row pairs: blurred rows 2q and 2q+1 both use pairs q..q+3,
@@ -1650,7 +1463,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
       if (gq >= 10) { gq -= 10; q++; }
     }
   }
-  DS_STAMP(4);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // ---- steered BRIEF (cpp:169-228).  cos/sin of the f32 argument are evaluated in f64 and rounded to f32 ----
@@ -1661,7 +1473,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
     sincosfGlibc(angle * factorPI, &sn, &cs);
   } else {
     double sd, cd;
-    ORBX_SINCOS((double)(angle * factorPI), &sd, &cd, true);
+    sincosTable<true>((double)(angle * factorPI), &sd, &cd);
     cs = (float)cd; sn = (float)sd;
   }
   unsigned long long words[4];
@@ -1694,7 +1506,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
     kp.class_id = -1;
     kps[o] = kp;
   }
-  DS_STAMP(5);
 }
 
 // =================================================================================================
@@ -1888,22 +1699,6 @@ __device__ void matchWidePrep(const int pair, const int* __restrict__ pairFirst,
 }
 
 
-// Diagnostic build only (-DORBX_MJ_STAMPS): per workgroup of k_match_jacobi, s_memtime behind each phase (a barrier first);
-// tools/mj_stamps.py prints the shares.
-#ifdef ORBX_MJ_STAMPS
-__device__ unsigned long long g_mjStamps[1024 * 16];
-#define MJ_STAMP(k)                                                                                      \
-  do {                                                                                                   \
-    __syncthreads();                                                                                     \
-    if (threadIdx.x == 0 && blockIdx.x < 1024) g_mjStamps[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-extern "C" int orbx_diag_mj_stamps(unsigned long long* out, int nWgs) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mjStamps), sizeof(unsigned long long) * 16 * (size_t)nWgs);
-}
-#else
-#define MJ_STAMP(k) do { } while (0)
-#endif
-
 // -------------------------------------------------------------------------------------------------
 // k_match_jacobi: one workgroup per frame pair, ONE THREAD PER QUERY.
 // The reference's query loop is sequential only through vMatchedDistance: query q sees, for every train t, the smallest
@@ -1933,7 +1728,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
                                                                int* __restrict__ scratch, long long scratchStride, int capl,
                                                                int* __restrict__ hostWide) {
   constexpr int MJ_T = MJ_CAP * MJ_P;
-  ORBX_SETPRIO();
   __shared__ float2 tXY[MJ_CAP];
   __shared__ float tAng[MJ_CAP];
   __shared__ uint4 tDesc[MJ_CAP][2];  // a train's 256 bits: two 16-byte reads per distance
@@ -1967,7 +1761,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
   const float wInv = (float)ORBX_GRID_COLS / (float)(mp.b.max_x - mp.b.min_x);  // Frame.cpp:46-47
   const float hInv = (float)ORBX_GRID_ROWS / (float)(mp.b.max_y - mp.b.min_y);
   const float fminX = (float)mp.b.min_x, fminY = (float)mp.b.min_y;
-  MJ_STAMP(0);
   if (t == 0) { sNT = 0; sBase = 0; sOverflow = n2 > 65535 ? 1 : 0; sNm = 0; sBadDist = 0; sBadRatio = 0; sBadOri = 0; sTooMany[0] = 0; sTooMany[1] = 0; }
   if (t < 3) { sKeep[t] = -1; sKeepV[t] = 0; }
   if (t < MJ_SWEEPS) sChangedSw[t] = 0;
@@ -2015,7 +1808,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     matchWidePrep<MJ_T>(pair, pairFirst, pairSecond, kps, nkp, mp, matches12, scratch, scratchStride, capl);
     return;
   }
-  MJ_STAMP(1);
   // ---- the q-th octave-0 keypoint of F1 in index order is query q ----
   float qx = 0, qy = 0, qang = 0;
   int qi = -1;
@@ -2062,7 +1854,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     }
     __syncthreads();
   }
-  MJ_STAMP(2);
   const int nQ = sBase, nT = sNT;
   if (nQ > MJ_CAP || nT > MJ_CAP || sOverflow) {  // block-uniform: the pair goes to the wide path
     if (t == 0) { nmatchesOut[pair] = MATCH_PENDING; *hostWide = 1; }  // (mapped host memory: the batch needs the wide path)
@@ -2078,7 +1869,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
   __syncthreads();
   if (t < MJ_CAP) clCount[t] = 0;
   __syncthreads();
-  MJ_STAMP(3);
   // cell window of my query, Frame.cpp:167-177
   const float r = (float)mp.window;
   const int minCX = max(0, (int)floorf((qx - fminX - r) * wInv));
@@ -2114,7 +1904,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     }
   }
   bool anyIn = false;
-  MJ_STAMP(7);
   while (win) {
     const int e = part + MJ_P * __builtin_ctzll(win);
     win &= win - 1ull;
@@ -2137,7 +1926,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     matchWidePrep<MJ_T>(pair, pairFirst, pairSecond, kps, nkp, mp, matches12, scratch, scratchStride, capl);
     return;
   }
-  MJ_STAMP(4);
   // a query has a candidate in its window iff some part listed one (vIndices2.empty() -> continue, ORBmatcher.cpp:46-47)
   bool hasCand = false;
 #pragma unroll
@@ -2146,13 +1934,7 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
   // (kept by the part-0 thread of the query)
   int outcome = 0, bestT = -1, bestD = 0;
   bool converged = false;
-#ifdef ORBX_MJ_STAMPS
-  int sweepsDone_ = 0;
-#endif
   for (int sweep = 0; sweep < MJ_SWEEPS; sweep++) {
-#ifdef ORBX_MJ_STAMPS
-    sweepsDone_ = sweep + 1;
-#endif
     // ---- every part scans its share of the query's candidates ----
     unsigned long long best = MATCH_NONE;  // dist << 32 | cell << 20 | train index
     int second = INF_DIST, bt = 0;
@@ -2236,10 +2018,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     matchWidePrep<MJ_T>(pair, pairFirst, pairSecond, kps, nkp, mp, matches12, scratch, scratchStride, capl);
     return;
   }
-  MJ_STAMP(5);
-#ifdef ORBX_MJ_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 1024) g_mjStamps[blockIdx.x * 16 + 8] = (unsigned long long)sweepsDone_;
-#endif
   // ---- final bookkeeping from the converged outcomes (part-0 threads hold them; the others have outcome 0) ----
   if (t < MJ_CAP) lastQ[t] = -1;
   __syncthreads();
@@ -2290,7 +2068,6 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     nmatchesOut[pair] = sNm;
     if (statsOut) { statsOut[pair * 3] = sBadDist; statsOut[pair * 3 + 1] = sBadRatio; statsOut[pair * 3 + 2] = sBadOri; }
   }
-  MJ_STAMP(6);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -2486,7 +2263,6 @@ __global__ __launch_bounds__(MW_T) void k_match_wide_prep(const int* __restrict_
                                                          const MatchParams mp, int* __restrict__ matches12,
                                                          const int* __restrict__ nmatchesOut, int* __restrict__ scratch,
                                                          long long scratchStride, int capl) {
-  ORBX_SETPRIO();
   const int pair = blockIdx.x + mp.pair0;
   if (nmatchesOut[pair] != MATCH_PENDING) return;
   matchWidePrep<MW_T>(pair, pairFirst, pairSecond, kps, nkp, mp, matches12, scratch, scratchStride, capl);
@@ -2681,12 +2457,13 @@ __global__ __launch_bounds__(64 * NW) void k_match_wide_lists(const int* __restr
 // block covers every train (BASELINE config 5's 2000 x 2000 match, config 3's all-pairs match), the work is all pairs of
 // 256-bit Hamming distances and one compare -- a dense contraction over the bits: with the bits as +-1 bytes (pm1Bytes16) the
 // dot product of two descriptors is 256 - 2 x distance, so "distance < dmax" is "accumulator > 256 - 2 dmax", one threshold.
-//   * workgroup = 256 queries, eight waves of 32 (one 32-row fragment x 8 k-steps = 32 registers, built once; BF_NT = 2: four waves
-//     of 64 -- half the waves per SIMD, 2.50 against 2.30 us per 2000 x 2000: the kernel is bound by a wave's own chain of LDS reads,
+//   * workgroup = 256 queries, eight waves of 32 (one 32-row fragment x 8 k-steps = 32 registers, built once; four waves of 64
+//     -- half the waves per SIMD -- took 2.50 against 2.30 us per 2000 x 2000: the kernel is bound by a wave's own chain of LDS reads,
 //     MFMAs, reduction, appends and barrier, ~2800 cycles per tile, so more and lighter waves are what helps);
-//   * the trains go by in tiles of 32: thread (train t >> 3, dword t & 7) loads one dword of a train's descriptor (the record two
-//     tiles ahead, the dword one tile ahead) and expands it into the tile's LDS image (two 16-byte stores), laid out so that a
-//     wave reads the B fragment of k-step c as 64 consecutive 16-byte pieces; two images, one LDS-only barrier per tile;
+//   * the trains go by in tiles of 32: thread (train t >> 4, dword (t >> 1) & 7, bit half t & 1) loads one dword of a train's
+//     descriptor (the record two tiles ahead, the dword one tile ahead) and expands its half into the tile's LDS image (one
+//     16-byte store), laid out so that a wave reads the B fragment of k-step c as 64 consecutive 16-byte pieces; two images,
+//     one LDS-only barrier per tile;
 //   * per tile and wave 8 v_mfma_i32_32x32x32_i8 (32 x 32 distances), then the maxima of four consecutive query rows, their
 //     maximum and one compare;
 //   * a candidate -- about one per wave and tile in the synthetic sets, one in thousands of pairs -- is appended from the lane that
@@ -2695,9 +2472,9 @@ __global__ __launch_bounds__(64 * NW) void k_match_wide_lists(const int* __restr
 //   * both operands take their k order from the same function of (lane >> 5, byte), so the instruction's own k map is irrelevant.
 // The vector form costs 16 xor / bcnt per 64 pairs (1.1 cycles of a SIMD per pair), the matrix form 0.25 (16 MFMAs of 32 cycles
 // per 2048 pairs).  Measured per 64 sets of 2000 x 2000: 81 us (with 64 queries per wave: 96) against 160 for the vector form; the
-// MFMAs with their LDS reads and the barrier alone would take 31.5 us -- the int8 rate (tools/exp_bf_parts.sh: timing-only builds
+// MFMAs with their LDS reads and the barrier alone would take 31.5 us -- the int8 rate (docs/history.md: timing-only builds
 // without one part; with the reduction 55, the staging 65, the appends 100 at 64 queries per wave).  Cycle stamps
-// (tools/bf_stamps.py) show why the parts add up: a wave needs ~2800 cycles per tile whatever shares its CU -- LDS reads + MFMA
+// (docs/history.md) show why the parts add up: a wave needs ~2800 cycles per tile whatever shares its CU -- LDS reads + MFMA
 // issue 800, drain + reduction 290, appends 750 (a hit every second tile, 1400 cycles of compare -> scalar test -> branch round
 // trips), staging 420, barrier 670 (the wave that took the append path is waited for) -- so the kernel is bound by the number of
 // waves in flight: hence the light waves.  Tried against the chain itself, none faster (docs/history.md): the MFMAs of tile
@@ -2710,45 +2487,12 @@ __global__ __launch_bounds__(64 * NW) void k_match_wide_lists(const int* __restr
 // frames repeat their corners: every ninth pair is nearer than dmax) the appends dominate and the vector form is faster -- 64 such
 // pairs of 1080p frames in one launch (measured with four waves of 64 queries and the rule at 128 blocks): 0.47 against 0.32 ms for the
 // matching stage, 54.7 k against 56.2 k frames/s
-// (tools/exp_c3_dense.py; config 3 as benchmarked, 16 pairs per call, stays below the 256 blocks).  Giving such blocks back was tried
+// (docs/history.md; config 3 as benchmarked, 16 pairs per call, stays below the 256 blocks).  Giving such blocks back was tried
 // (a wave counting its first tiles' candidates: the first tile says nothing, those frames' candidates sit further down the train
 // list; counting while listing cost the sparse case 7 %) and left out.
 // -------------------------------------------------------------------------------------------------
-#ifndef ORBX_BF_EXP
-#define ORBX_BF_EXP 0  // diagnostic builds of k_match_bf_mfma without one of its parts (timing only; tools/exp_bf_parts.sh)
-#endif
-// Diagnostic build only (-DORBX_BF_STAMPS): per wave of k_match_bf_mfma, s_memtime deltas of a tile's phases summed over its tiles
-// (tools/bf_stamps.py prints the shares): 0 LDS reads + MFMA issue, 1 drain + reduction, 2 appends, 3 staging, 4 barrier.
-#ifdef ORBX_BF_STAMPS
-__device__ uint32_t g_bfStamps[4096 * 8];
-#define BF_STAMP(k)                                                        \
-  do {                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
-    bfAcc_[k] += (uint32_t)(now_ - bfPrev_);                               \
-    bfPrev_ = now_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-  } while (0)
-extern "C" int orbx_diag_bf_stamps(uint32_t* out, int nWaves) {
-  if (nWaves < 0) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_bfStamps)) != hipSuccess) return -1;
-    return (int)hipMemset(p, 0, sizeof(uint32_t) * 8 * 4096);
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bfStamps), sizeof(uint32_t) * 8 * (size_t)nWaves);
-}
-#else
-#define BF_STAMP(k) do { } while (0)
-#endif
-#ifndef BF_NT
-#define BF_NT 1  // 32-row query fragments per wave: 1 = 32 queries per wave, eight waves per workgroup; 2 = 64 queries, four waves
-#endif
-#ifndef BF_WAVES
-#define BF_WAVES (8 / BF_NT)  // waves per workgroup
-#endif
-#define BF_T (64 * BF_WAVES)
-#define BF_QWG (32 * BF_NT * BF_WAVES)  // queries per workgroup (a multiple of 64)
-static_assert(BF_T == 256 || BF_T == 512, "k_match_bf_mfma: the staging maps 512 half dwords of a tile onto 256 or 512 threads");
+#define BF_T 512    // threads per workgroup: eight waves, a thread stages one of the 512 half dwords of a tile
+#define BF_QWG 256  // queries per workgroup: 32 per wave (a multiple of 64)
 __global__ __launch_bounds__(BF_T) void k_match_bf_mfma(const int* __restrict__ pairFirst, const int* __restrict__ pairSecond,
                                                       const orbx_keypoint* __restrict__ kps,
                                                       const uint8_t* __restrict__ desc, const int* __restrict__ nkp,
@@ -2821,34 +2565,23 @@ __global__ __launch_bounds__(BF_T) void k_match_bf_mfma(const int* __restrict__ 
     if (!sAll) return;  // (uniform) k_match_wide_lists takes the block
   }
   if (t == 0 && diag) atomicAdd(diag, 1u);  // orbx_debug_match_counters: blocks of 256 queries this kernel has listed
-  // ---- the queries' fragments: rows = query 64 wv + 32 T + (lane & 31), k = the 16 bits (lane >> 5) of dword c ----
+  // ---- the queries' fragments: rows = query 32 wv + (lane & 31), k = the 16 bits (lane >> 5) of dword c ----
   const int h = lane >> 5, n = lane & 31;
-  const int qw = 32 * BF_NT * wv;  // the wave's first query of the block
+  const int qw = 32 * wv;  // the wave's first query of the block
   const bool waveLive = Q0 + qw < nQ;  // (uniform) a wave without a query only helps to stage the trains
-  v4i_t aq[BF_NT][8];
+  v4i_t aq[8];
 #pragma unroll
-  for (int T = 0; T < BF_NT; T++)
-#pragma unroll
-    for (int c = 0; c < 8; c++) aq[T][c] = pm1Bytes16(qdS[qw + 32 * T + n][c] >> (16 * h));
+  for (int c = 0; c < 8; c++) aq[c] = pm1Bytes16(qdS[qw + n][c] >> (16 * h));
   const int thr = 256 - 2 * mp.dmax;
   // ---- staging: thread = (train j of the tile, dword c).  A loaded value is first TOUCHED a tile later (the record word is masked
   //      where it is used, not where it is loaded) and both loads are unconditional (a slot beyond the last train reads the last
   //      train again; the appends mask it): a wait right behind a load, or the register copy a conditional load ends in, costs
   //      every tile a memory round trip ----
-#if BF_T == 256
-  const int sj = t >> 3, sc = t & 7;
-#else  // (eight waves: a thread expands one half of a dword)
   const int sj = t >> 4, sc = (t >> 1) & 7, sh = t & 1;
-#endif
   auto loadIdx = [&](const int tile) -> uint32_t { return reinterpret_cast<const uint32_t*>(trec + min(32 * tile + sj, nT - 1))[3]; };
   auto loadDw = [&](const uint32_t rec) -> uint32_t { return d2[(long long)(rec & 0xfffffu) * 8 + sc]; };
   auto expand = [&](const int img, const uint32_t w) {
-#if BF_T == 256
-    tileB[img][sc][0][sj] = pm1Bytes16(w);
-    tileB[img][sc][1][sj] = pm1Bytes16(w >> 16);
-#else
     tileB[img][sc][sh][sj] = pm1Bytes16(w >> (16 * sh));
-#endif
   };
   auto ldsBarrier = [&]() {  // (over the LDS images only: __syncthreads() would also wait for the global loads in flight)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -2863,85 +2596,42 @@ __global__ __launch_bounds__(BF_T) void k_match_bf_mfma(const int* __restrict__ 
   wN = loadDw(idxN);
   idxN = loadIdx(2);
   ldsBarrier();
-#ifdef ORBX_BF_STAMPS
-  unsigned long long bfPrev_ = __builtin_amdgcn_s_memtime();
-  uint32_t bfAcc_[5] = {0u, 0u, 0u, 0u, 0u};
-#endif
   for (int i = 0; i < nTl; i++) {
     const int img = i & 1;
     if (waveLive) {
-      v16i_t acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
+      v16i_t acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int c = 0; c < 8; c++) {
-#if !(ORBX_BF_EXP & 2)  // (2: TIMING ONLY, no matrix instructions)
-        const v4i_t bt = tileB[img][c][h][n];
-        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aq[0][c], bt, acc0, 0, 0, 0);
-#if BF_NT == 2
-        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aq[1][c], bt, acc1, 0, 0, 0);
-#endif
-#endif
-      }
-      BF_STAMP(0);
-#if !(ORBX_BF_EXP & 8)  // (8: TIMING ONLY, no reduction)
-      int gm[2][4];
+      for (int c = 0; c < 8; c++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(aq[c], tileB[img][c][h][n], acc, 0, 0, 0);
+      int gm[4];
 #pragma unroll
-      for (int T = 0; T < 2; T++)
-#pragma unroll
-        for (int gq = 0; gq < 4; gq++) {
-          const v16i_t& A = T ? acc1 : acc0;
-          gm[T][gq] = T < BF_NT ? max(max(A[4 * gq], A[4 * gq + 1]), max(A[4 * gq + 2], A[4 * gq + 3])) : (int)0x80000000;
-        }
-      const int m = max(max(max(gm[0][0], gm[0][1]), max(gm[0][2], gm[0][3])), max(max(gm[1][0], gm[1][1]), max(gm[1][2], gm[1][3])));
+      for (int gq = 0; gq < 4; gq++) gm[gq] = max(max(acc[4 * gq], acc[4 * gq + 1]), max(acc[4 * gq + 2], acc[4 * gq + 3]));
+      const int m = max(max(gm[0], gm[1]), max(gm[2], gm[3]));
       const int e = 32 * i + n;
       const bool tOk = e < nT;
       asm volatile("" :: "v"(m));
-      BF_STAMP(1);
-#if ORBX_BF_EXP & 1  // (1: TIMING ONLY, no appends)
-      if (m == 0x7fffffff)
-#endif
       if (__ballot(tOk && m > thr) != 0ull) {  // (wave-uniform) some pair of the tile is nearer than dmax
 #pragma unroll
-        for (int T = 0; T < BF_NT; T++)
+        for (int gq = 0; gq < 4; gq++) {
+          if (__ballot(tOk && gm[gq] > thr) == 0ull) continue;  // (wave-uniform)
 #pragma unroll
-          for (int gq = 0; gq < 4; gq++) {
-            if (__ballot(tOk && gm[T][gq] > thr) == 0ull) continue;  // (wave-uniform)
-            const v16i_t& A = T ? acc1 : acc0;
-#pragma unroll
-            for (int r = 4 * gq; r < 4 * gq + 4; r++) {
-              const int a = A[r];
-              const int ql = qw + 32 * T + (r & 3) + 8 * (r >> 2) + 4 * h;
-              if (tOk && a > thr && Q0 + ql < nQ) {
-                const int slot = atomicAdd(&cnt[ql], 1);
-                if (slot < MW_CP) lists[(size_t)slot * capl + Q0 + ql] = ((uint32_t)((256 - a) >> 1) << 16) | (uint32_t)e;
-              }
+          for (int r = 4 * gq; r < 4 * gq + 4; r++) {
+            const int a = acc[r];
+            const int ql = qw + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (tOk && a > thr && Q0 + ql < nQ) {
+              const int slot = atomicAdd(&cnt[ql], 1);
+              if (slot < MW_CP) lists[(size_t)slot * capl + Q0 + ql] = ((uint32_t)((256 - a) >> 1) << 16) | (uint32_t)e;
             }
           }
+        }
       }
-#else
-      if (acc0[0] == 0x7fffffff) cnt[0] = 1;
-#endif
-      BF_STAMP(2);
     }
-#if !(ORBX_BF_EXP & 4)  // (4: TIMING ONLY, no staging)
     if (i + 1 < nTl) {  // (uniform) the next tile into the other image: its last readers passed the barrier of the previous step
       expand(img ^ 1, wN);
       wN = loadDw(idxN);
       idxN = loadIdx(i + 3);
     }
-#endif
-    BF_STAMP(3);
     ldsBarrier();
-    BF_STAMP(4);
   }
-#ifdef ORBX_BF_STAMPS
-  {
-    const unsigned wid_ = ((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wv) & 4095u;
-    if (lane == 0) {
-      for (int j = 0; j < 5; j++) g_bfStamps[wid_ * 8 + j] = bfAcc_[j];
-      g_bfStamps[wid_ * 8 + 5] = (uint32_t)nTl;
-    }
-  }
-#endif
   __syncthreads();
   if (valid) {
     const int c = cnt[t];
@@ -2963,7 +2653,6 @@ __global__ __launch_bounds__(BF_T) void k_match_bf_mfma(const int* __restrict__ 
 static_assert(MW_CP == 128, "k_match_wide_sort: two list entries per lane");
 __global__ __launch_bounds__(256) void k_match_wide_sort(const MatchParams mp, const int* __restrict__ nmatchesOut, int* __restrict__ scratch,
                                                         long long scratchStride, int capl, int qpw) {
-  ORBX_SETPRIO();
   const int lane = threadIdx.x & 63;
   const int pair = blockIdx.y + mp.pair0;
   if (nmatchesOut[pair] != MATCH_PENDING) return;
@@ -3028,7 +2717,6 @@ __global__ __launch_bounds__(MW_T) void k_match_wide_resolve(const int* __restri
                                                             const MatchParams mp, int* __restrict__ matches12,
                                                             int* __restrict__ nmatchesOut, int* __restrict__ statsOut,
                                                             int* scratch, long long scratchStride, int capl) {
-  ORBX_SETPRIO();
   extern __shared__ __align__(16) unsigned char mwLds[];
   // claims of a sweep = one linked list per train through its claimant queries (any number of claimants)
   int* head = reinterpret_cast<int*>(mwLds);                              // [capl] a claimant of the train, -1 = none; lastQ at the end
@@ -3074,15 +2762,7 @@ __global__ __launch_bounds__(MW_T) void k_match_wide_resolve(const int* __restri
   __syncthreads();
   // outcome of a query: 0 = no candidate in the window, 1 = invalid by distance, 2 = invalid by ratio, 3 = accepted
   bool converged = false;
-  MJ_STAMP(0);
-#ifdef ORBX_MJ_STAMPS
-  int sweepsDone_ = 0;
-#endif
   for (int sweep = 0; sweep < MW_SWEEPS; sweep++) {
-#ifdef ORBX_MJ_STAMPS
-    sweepsDone_ = sweep + 1;
-    if (sweep == 1) MJ_STAMP(1);
-#endif
     bool changed = false;
 #pragma unroll
     for (int rr = 0; rr < MW_R; rr++) {
@@ -3145,10 +2825,6 @@ __global__ __launch_bounds__(MW_T) void k_match_wide_resolve(const int* __restri
       matchGeneral<MW_T>(pair, pairFirst, pairSecond, kps, desc, nkp, mp, matches12, nmatchesOut, statsOut, scratch, scratchStride);
     return;
   }
-  MJ_STAMP(2);
-#ifdef ORBX_MJ_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 1024) g_mjStamps[blockIdx.x * 16 + 8] = (unsigned long long)sweepsDone_;
-#endif
   // ---- final bookkeeping from the converged outcomes: a train belongs to its LAST claimant ----
   int* lastQ = head;
   for (int e = t; e < nT; e += MW_T) lastQ[e] = -1;
@@ -3213,7 +2889,6 @@ __global__ __launch_bounds__(MW_T) void k_match_wide_resolve(const int* __restri
     nmatchesOut[pair] = sNm;
     if (statsOut) { statsOut[pair * 3] = sBadDist; statsOut[pair * 3 + 1] = sBadRatio; statsOut[pair * 3 + 2] = sBadOri; }
   }
-  MJ_STAMP(3);
 }
 
 // =================================================================================================
@@ -3425,7 +3100,7 @@ __global__ __launch_bounds__(256) void k_debug_sincos(const float* __restrict__ 
     return;
   }
   double sd, cd;
-  ORBX_SINCOS((double)(angle[i] * factorPI), &sd, &cd, false);
+  sincosTable<false>((double)(angle[i] * factorPI), &sd, &cd);
   c[i] = (float)cd;
   s[i] = (float)sd;
 }
@@ -3486,13 +3161,6 @@ hipError_t launch_pyramid_bands(hipStream_t st, int nFrames, const uint8_t* img0
   // against 0.285 ms per batch; 640x480 and the strips of 3840x2160 the other way round: 425.2 k against 416.8 k frames/s,
   // 0.206 against 0.243 ms)
   one = one && g.nlevels > 1 && pb.g1[0][1] - pb.g0[0][1] <= PYR_T / 2;
-  const int gmaxKnob = (int)knob(KNOB_PYR_GMAX, 0);  // diagnostics
-  if (gmaxKnob == 2) one = false;
-  if (gmaxKnob == 1) {
-    one = true;
-    for (int l = 1; l < g.nlevels; l++)
-      for (int s2 = 0; s2 < pb.nStrips; s2++) one = one && pb.g1[s2][l] - pb.g0[s2][l] <= PYR_T;
-  }
   const size_t lds = 2 * (size_t)pb.maxRows * sizeof(uint4);
   const uint4* tab4 = reinterpret_cast<const uint4*>(tab);
   if (pb.dual2 && one) hipLaunchKernelGGL((k_pyramid_bands<1, 1>), grid, block, lds, st, img0, img0FrameStride, pyr, g, tab4, pb);
@@ -3510,28 +3178,19 @@ hipError_t launch_fast(hipStream_t st, int nFrames, const uint8_t* img0, long lo
     cw = std::max(cw, std::min(g.L[l].wCell + 6, ORBX_CELL_MAX));
     ch = std::max(ch, std::min(g.L[l].hCell + 6, ORBX_CELL_MAX));
   }
-  const bool forceOld = knobOn(KNOB_FAST_WG);  // diagnostics (orbx_debug_set): the workgroup-per-cell kernel
   // a lone wave needs 17 us for its cell; the four waves of k_fast's workgroup 8.8 us: the latter for the one-frame call, whose
-  // cells cannot fill the chip either way (measured up to eight 640x480 frames = 4616 cells per launch: tools/exp_fast_small.sh)
+  // cells cannot fill the chip either way (measured up to eight 640x480 frames = 4616 cells per launch: docs/history.md)
   // (the parity tests run their small batches through both kernels: knob fast_wg_max_cells = 0)
   const int wgMaxCells = (int)knob(KNOB_FAST_WG_MAX_CELLS, 5000);
   const bool small = (long long)nFrames * g.nCellsTotal <= wgMaxCells;
-  if (usedWave) *usedWave = (waveOk && img0Aligned && cells && !forceOld && !small) ? 1 : 0;
-  if (waveOk && img0Aligned && cells && !forceOld && !small) {
+  if (usedWave) *usedWave = (waveOk && img0Aligned && cells && !small) ? 1 : 0;
+  if (waveOk && img0Aligned && cells && !small) {
     // one wave per workgroup, FW_CPW cells per wave; x size padded to whole rounds of 8 runs (XCD-aware order)
     const int groups = ((g.nCellsTotal + FW_CPW - 1) / FW_CPW + 8 * FW_XK - 1) / (8 * FW_XK) * (8 * FW_XK);
     const int ts = waveOk == 2 ? 48 : 64;  // tile / strength-map row stride: 48 when every cell image is <= 12 dwords wide
     // (+ 16: the quick reject's dword reads reach a few bytes beyond the last tile row)
     const int tileBytes = ch * ts + 16, smapBytes = (ch - 6 + 2) * ts;
-    const int fastPad = (int)knob(KNOB_FAST_LDS_PAD, 0);  // diagnostics: fewer waves per CU
-    const size_t lds = (size_t)(16 + tileBytes + smapBytes + FW_RING * 2 + FW_CORN * 2) + fastPad;  // k_fast_wave's layout
-    const bool dbg = knobOn(KNOB_FAST_DEBUG);
-    if (dbg) {
-      int nb48 = -1, nb64 = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb48, k_fast_wave<48>, 64, lds);
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb64, k_fast_wave<64>, 64, lds);
-      fprintf(stderr, "k_fast_wave: ts %d lds %zu B, occupancy API: %d / %d workgroups per CU\n", ts, lds, nb48, nb64);
-    }
+    const size_t lds = (size_t)(16 + tileBytes + smapBytes + FW_RING * 2 + FW_CORN * 2);  // k_fast_wave's layout
     if (ts == 48)
       hipLaunchKernelGGL(k_fast_wave<48>, dim3(groups, nFrames, 1), dim3(64, 1, 1), lds, st, img0, img0FrameStride, pyr, g, cells,
                          cand, cellCount, tileBytes, smapBytes);
@@ -3559,20 +3218,19 @@ hipError_t launch_describe_patch(hipStream_t st, int nFrames, int maxSel, const 
   // launched no k_sel_compact; see DescStage)
   if (maxSel <= 0 && !staged) return hipSuccess;
   dim3 block(64 * DESC_WAVES, 1, 1), grid(((maxSel + DESC_WAVES - 1) / DESC_WAVES + 7) / 8 * 8, nFrames, 1);  // x: multiple of 8
-  const int descPad = (int)knob(KNOB_DESC_LDS_PAD, 0);  // diagnostics: fewer waves per CU
   const DescStage none = {};
   if (staged) {
     if (gaussVariant)
-      hipLaunchKernelGGL((k_describe_patch<1, true>), grid, block, descPad, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+      hipLaunchKernelGGL((k_describe_patch<1, true>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                          desc, capacity, *staged, libmFloat);
     else
-      hipLaunchKernelGGL((k_describe_patch<0, true>), grid, block, descPad, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+      hipLaunchKernelGGL((k_describe_patch<0, true>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                          desc, capacity, *staged, libmFloat);
   } else if (gaussVariant)
-    hipLaunchKernelGGL((k_describe_patch<1, false>), grid, block, descPad, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+    hipLaunchKernelGGL((k_describe_patch<1, false>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                        desc, capacity, none, libmFloat);
   else
-    hipLaunchKernelGGL((k_describe_patch<0, false>), grid, block, descPad, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+    hipLaunchKernelGGL((k_describe_patch<0, false>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                        desc, capacity, none, libmFloat);
   return hipGetLastError();
 }

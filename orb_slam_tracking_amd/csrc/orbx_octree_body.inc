@@ -102,20 +102,7 @@ __device__ __forceinline__ uint32_t laneXorT(uint32_t v) {
   if constexpr (LM == 1) return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xf, 0xf, false);
   else if constexpr (LM == 2) return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xf, 0xf, false);
   else if constexpr (LM == 8) return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x128, 0xf, 0xf, false);
-#ifdef ORBX_LANEXOR_VALU
-  else if constexpr (LM == 4) {
-    const int r = __builtin_amdgcn_update_dpp((int)v, (int)v, 0x104, 0xf, 0x5, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(r, (int)v, 0x114, 0xf, 0xa, false);
-  } else if constexpr (LM == 16) {
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return (__lane_id() & 16) ? r[0] : r[1];
-  } else {
-    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return (__lane_id() & 32) ? r[0] : r[1];
-  }
-#else
   else return __shfl_xor(v, LM);
-#endif
 }
 template <int LM>
 __device__ __forceinline__ u64 laneXorT(u64 v) {
@@ -648,15 +635,12 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
   bool inTask[2] = {false, false};
   MemKeys A{p};
   int depth = 2 * (31 - __builtin_clz((unsigned)n));
-  OCT_REPLAY_INIT();
   for (;;) {
-    OCT_REPLAY_COUNT(7);
     bool act[2];
 #pragma unroll
     for (int j = 0; j < 2; j++) act[j] = (2 * tid + j) < n && (l[j] - f[j] > 16);
     // Once no range is longer than 128 keys the recursion goes on wave by wave: every range still to be partitioned becomes a
     // task of one wave (stdSortPartitionWaveTask), which runs all of its remaining levels without a workgroup barrier.
-#ifndef ORBX_NO_WAVE_TASKS  // (experiment switch: the workgroup runs every level)
     if (!__syncthreads_or((act[0] && l[0] - f[0] > 128) || (act[1] && l[1] - f[1] > 128))) {
 #pragma unroll
       for (int j = 0; j < 2; j++) {
@@ -673,7 +657,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
         }
       break;
     }
-#endif
     const bool wAct = __ballot(act[0] || act[1]) != 0ull;  // (wave-uniform)
     if (depth == 0) {  // __introsort_loop: heapsort of what is left of the ranges
       // (a range of more than 16 keys starts at one of a thread's two positions at most)
@@ -698,7 +681,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
         }
     }
     __syncthreads();
-    OCT_REPLAY_ACC(0);
     // ---- every position inside a range: its stop flags ----
     int gl[2] = {0, 0}, ll[2] = {0, 0};
     if (wAct) {
@@ -715,7 +697,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
     // one workgroup scan for both flag sets: the counts (<= 2 x OCT_T <= 2048) ride in the two halves of one word
     int totLR;
     const int exLR = blockScanExcl((gl[0] + gl[1]) | ((ll[0] + ll[1]) << 16), tid, ws, &totLR, false);  // (barrier after the owners' phase)
-    OCT_REPLAY_ACC(1);
     if (totLR == 0) break;  // no range left to partition (every range has a stop: its pivot's neighbours by the median of three)
     if (2 * tid < capN) {  // (flags beyond n are 0: the prefix stays at the total there; every position's entry is read as some range's end)
       const uint32_t e0 = (uint32_t)exLR, e1 = (uint32_t)(exLR + (gl[0] | (ll[0] << 16)));
@@ -723,7 +704,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
     }
     if (tid == 0) SLR[capN] = (uint32_t)totLR;
     __syncthreads();
-    OCT_REPLAY_ACC(2);
     // ---- scatter the stop positions by rank: upward stops ascending, downward stops descending ----
     int nL[2] = {0, 0}, nR[2] = {0, 0};
     if (wAct) {
@@ -741,7 +721,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
       }
     }
     __syncthreads();
-    OCT_REPLAY_ACC(3);
     // ---- the swaps: pair k of a range lives at index first + 1 + k; the thread of pair K - 1 (pair 0 when K = 0) reports
     //      cut = min(L[K], R[K - 1]) at LR[first] (low half), which is never a rank slot ----
     if (wAct) {
@@ -771,7 +750,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
       }
     }
     __syncthreads();
-    OCT_REPLAY_ACC(4);
     // ---- every position of a partitioned range moves to the child that holds it ----
     if (act[0]) {
       const int c = (int)(LR[f[0]] & 0xffff);
@@ -784,7 +762,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
   }
   if (rankedOut) {
     __syncthreads();  // (the last swaps / a heapsort have been written)
-    OCT_REPLAY_ACC(5);
 #pragma unroll
     for (int j = 0; j < 2; j++)
       if (inTask[j]) {  // the position's final range, left behind by the wave that partitioned it
@@ -793,7 +770,6 @@ __device__ __forceinline__ void stdSortPartitionPhasePar(u64* p, int n, int tid,
         l[j] = (int)(fl >> 16);
       }
     rankOut();
-    OCT_REPLAY_ACC(6);
   }
 }
 
@@ -901,7 +877,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
   int nPad = 1;
   while (nPad < n) nPad <<= 1;
   if (nPad < OCT_T) nPad = OCT_T;  // the register sort works on at least OCT_T (padded) keys
-  OCT_STAMP(0);
 
   // ---- 1. path codes -----------------------------------------------------------------------------------------
   constexpr int RC = SCR::kRegCand;
@@ -962,7 +937,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
   }
   if (tid < OCT_DEPTH + 2) { cntDiv[tid] = 0; cntAlone[tid] = 0; }
   __syncthreads();
-  OCT_STAMP(1);
   if constexpr (sizeof(*S.keys) == 4) {
     bitonicSort(S.keys, nPad, tid, (uint32_t*)nullptr, 0);  // 32-bit keys exist in the LDS kernel only
   } else {
@@ -977,7 +951,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
       bitonicSort(S.keys, nPad, tid, S.xchg, S.xchgCap);
     }
   }
-  OCT_STAMP(2);
 
   // ---- 2. divergence depths, S_d (distinct depth-d prefixes), singles_d -----------------------------------------
   for (int i = tid; i <= n; i += OCT_T) {
@@ -991,7 +964,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
   __syncthreads();
   for (int i = tid; i < n; i += OCT_T) atomicAdd(&cntAlone[octAlone(S.div, i)], 1);
   __syncthreads();
-  OCT_STAMP(3);
   // ---- 3. replay the pass loop on sizes only (cpp:781-895) ------------------------------------------------------
   if (tid == 0) {
     int Sd[OCT_DEPTH + 2], sg[OCT_DEPTH + 2];
@@ -1024,7 +996,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
     if (tid == 0) *nOut = -2;
     return;
   }
-  OCT_STAMP(4);
   // ---- 4. node list in std::list order ---------------------------------------------------------------------------
   // node starts: a leaf key (alone < k) or the first key of a depth-k group
   {
@@ -1065,9 +1036,7 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
   __syncthreads();
   for (int m = M + tid; m < mPad; m += OCT_T) S.nodes[m] = ~0ull;
   __syncthreads();
-  OCT_STAMP(5);
   bitonicSort(S.nodes, mPad, tid, S.xchg, S.xchgCap);
-  OCT_STAMP(6);
   for (int m = tid; m < M; m += OCT_T) {
     const u64 v = S.nodes[m];
     const int lo = (int)(v & 0x7ffff);
@@ -1077,11 +1046,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
   }
   __syncthreads();
 
-  OCT_STAMP(7);
-#ifdef ORBX_OCT_STAMPS
-  unsigned long long tAcc = __builtin_amdgcn_s_memtime();
-  if (tid == 0) for (int k_ = 8; k_ < 14; k_++) g_octStamps[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * OCT_NSTAMP + k_] = 0;
-#endif
   // ---- 5. partial pass(es), cpp:897-965 ---------------------------------------------------------------------------
   if (sPhase2) {
     int* pendA = S.pending;
@@ -1130,7 +1094,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         sizedA[j] = ((u64)(S.nodeHi[nd] - lo) << 40) | ((u64)(ulx & 0xfffff) << 20) | (u64)nd;
       }
       __syncthreads();
-      OCT_STAMP_ACC(8, tAcc);
       // (b) std::sort (cpp:912): partition phase replayed, final insertion sort as a parallel stable rank sort
       constexpr bool ldsUnit = sizeof(*S.nodeLo) == 2;  // the LDS kernel: at most 256 pending nodes, everything in LDS
       if (nPend <= S.parCap && S.parScr) {
@@ -1152,7 +1115,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         stdSortPartitionPhase(sizedA, nPend, tid);
       }
       __syncthreads();
-      OCT_STAMP_ACC(9, tAcc);
       if constexpr (ldsUnit) {
         // the insertion sort is stable on the partition phase's output: rank by (count, UL.x, position) -- 12 + 12 + 8 bits here
         // (a node holds at most 2048 candidates, UL.x < 4096, at most 256 pending nodes), read four at a time
@@ -1194,7 +1156,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         }
       }
       __syncthreads();
-      OCT_STAMP_ACC(10, tAcc);
       // (c) children of every pending node (in sorted order)
       uint32_t* childB = S.parScr;  // (LDS kernels) [2 nPend]: the children's boundaries h1 | h2 << 16, h3 -- (e) creates from them
       for (int j = tid; j < nPend; j += OCT_T) {
@@ -1232,7 +1193,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         S.childCnt[j] = nch | (nmulti << 8);
       }
       __syncthreads();
-      OCT_STAMP_ACC(11, tAcc);
       // (d) cut point: nodes are split from the back of the sorted array until the list holds N nodes
       {
         // growth of the list when the last t+1 sorted nodes are split: inclusive prefix over t = nPend-1-j
@@ -1254,7 +1214,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
       }
       __syncthreads();
       const int cut = sCut, finish = sFinish;
-      OCT_STAMP_ACC(12, tAcc);
       // (e) create the children: processing order t = nPend-1-j; children are push_front'ed in quadrant order
       {
         const int nProc = nPend - cut;
@@ -1325,14 +1284,12 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         nPend = totM;
       }
       __syncthreads();
-      OCT_STAMP_ACC(13, tAcc);
       if (finish) break;
       { int* t = pendA; pendA = pendB; pendB = t; }
     }
     if (tid == 0) sFront = nFront;
     __syncthreads();
   }
-  OCT_STAMP(14);
   // ---- 6. output positions: reverse(front alive) ++ list alive; keep the first `quota` ------------------------------
   const int nFront = sFront;
   const int total = nFront + M;  // virtual sequence: pushed nodes in reverse push order, then the list
@@ -1414,7 +1371,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
         out[p++] = kp;
       }
       if (tid == 0) *nOut = min(alive, N);
-      OCT_STAMP(15);
       return;
     }
     auto ceAt = [&](int i) -> uint32_t { return S.ceBuf[i]; };  // candidate word of sorted key i
@@ -1453,7 +1409,6 @@ __device__ __forceinline__ void octreeSelect(const SCR S, int n, const OctLevel 
     }
     if (tid == 0) *nOut = min(alive, N);
   }
-  OCT_STAMP(15);
 }
 
 // The unit's arrays inside its global scratch area (layout = octScratchBytes(nMax, qMax) on the host); candBuf = the position
@@ -1527,7 +1482,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
   if (tid < OCT_DEPTH + 2) { cntDiv[tid] = 0; cntAlone[tid] = 0; }
   if (tid == 0) { sBad = 0; sMaxB = 0; }
   __syncthreads();
-  OCT_STAMP(0);
   // ---- 0. the buckets' records: counts, histograms, and what only the neighbours in key order can tell -------------------
   // (the records come from other XCDs' workgroups, i.e. from the fabric: one bulk load per thread, everything in flight at once)
   int rec[ORBX_OCTB_INFO];
@@ -1555,7 +1509,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
   if (tid < nB) bPre[tid] = chunkPre;
   if (tid == 0) bPre[nB] = nChunks;
   __syncthreads();
-  OCT_STAMP(1);
   if (sBad || nNE == 0 || N <= 0) {
     // (an overfull bucket: the count reported for the next batch's choice of bucket depth asks for the deepest one)
     if (tid == 0) { *nOut = (sBad ? -2 : 0); if (nKeysOut) *nKeysOut = sBad ? ORBX_OCT_FEEDBACK(ORBX_OCT_MAX_CAND, ORBX_OCTB_CAP, d0) : 0; }
@@ -1594,9 +1547,7 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
       }
     }
   }
-  OCT_STAMP(2);
   __syncthreads();
-  OCT_STAMP(3);
   // ---- 3. replay the pass loop on sizes only (cpp:781-895) ------------------------------------------------------
   if (tid == 0) {
     int Sd[OCT_DEPTH + 2], sg[OCT_DEPTH + 2];
@@ -1632,7 +1583,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
     if (tid == 0) *nOut = -2;
     return;
   }
-  OCT_STAMP(4);
   // ---- 4. node list in std::list order ---------------------------------------------------------------------------
   // node starts = keys whose divergence from their left neighbour lies at depth <= k (a leaf key's does: its first lonely depth is
   // the larger of its two divergences).  A thread owns consecutive chunks of 16 keys; starts are counted, scanned and then listed
@@ -1767,7 +1717,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
     }
   }
   __syncthreads();
-  OCT_STAMP(5);
   {
     const int e = mPad / OCT_T;
     if (use32) {
@@ -1781,7 +1730,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
       else bitonicSortRegs<4>(S.xchg, tid);
     }
   }
-  OCT_STAMP(6);
   // node records in list order (global: the partial pass appends to them); the pending nodes of the partial pass -- the
   // multi-key depth-k nodes in creation order = reverse list order -- get their records in LDS, where the sorted order reads them
   int nPend = 0;
@@ -1821,11 +1769,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
   if (tid == 0) { sSize = M; sFinish = 0; }
   __syncthreads();
 
-  OCT_STAMP(7);
-#ifdef ORBX_OCT_STAMPS
-  unsigned long long tAcc = __builtin_amdgcn_s_memtime();
-  if (tid == 0) for (int k_ = 8; k_ < 14; k_++) g_octStamps[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * OCT_NSTAMP + k_] = 0;
-#endif
   // ---- 5. partial pass(es), cpp:897-965 ---------------------------------------------------------------------------
   if (sPhase2) {
     int* pendB = S.pending + qCap;     // the multi-key children of a round, for the next one
@@ -1842,14 +1785,11 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
       for (int j = tid; j < nPend; j += OCT_T)
         S.xchg[j] = ((u64)((S.pHiD[j] >> 5) - S.pLo[j]) << 40) | ((u64)S.pUlx[j] << 20) | (u64)j;
       __syncthreads();
-      OCT_STAMP_ACC(8, tAcc);
       // (b) std::sort (cpp:912): partition phase replayed; the final insertion sort is a stable sort, and the partition phase
       // leaves ranges of at most 16 keys that are ordered among themselves (every key of a range <= every key of the next), so a
       // key's place is its range's start plus its stable rank inside the range
       stdSortPartitionPhasePar(S.xchg, nPend, tid, S.parScr, ws, S.parCap, sizedB);
       __syncthreads();
-      OCT_STAMP_ACC(9, tAcc);
-      OCT_STAMP_ACC(10, tAcc);
       // (c) children of every pending node (in sorted order): a child starts where the divergence depth equals the node's depth
       // + 1 (at most three places).  The bytes of a node are scanned 64 at a time, all loads of a step in flight
       for (int j = tid; j < nPend; j += OCT_T) {
@@ -1917,7 +1857,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
         bnd[3 * j] = b1; bnd[3 * j + 1] = b2; bnd[3 * j + 2] = b3;
       }
       __syncthreads();
-      OCT_STAMP_ACC(11, tAcc);
       // (d) cut point: nodes are split from the back of the sorted array until the list holds N nodes
       {
         // growth of the list when the last t+1 sorted nodes are split: inclusive prefix over t = nPend-1-j
@@ -1939,7 +1878,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
       }
       __syncthreads();
       const int cut = sCut, finish = sFinish;
-      OCT_STAMP_ACC(12, tAcc);
       // (e) create the children: processing order t = nPend-1-j; children are push_front'ed in quadrant order
       int totM;
       {
@@ -1992,7 +1930,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
         nFront += totC;
       }
       __syncthreads();
-      OCT_STAMP_ACC(13, tAcc);
       if (finish) break;
       // another round (rare: the first one did not reach N): the new pending nodes' records, from the global tables
       nPend = totM;
@@ -2014,7 +1951,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
     if (tid == 0) sFront = nFront;
     __syncthreads();
   }
-  OCT_STAMP(14);
   // ---- 6. output: reverse(front alive) ++ list alive, the first `quota` of them -- as a list of key ranges: k_octree_emit finds
   //         every range's first key with the highest response (many workgroups: one CU's L1 takes ~4 cycles per scattered line,
   //         45 k cycles for the 1737 nodes of a 4K level 0) -------------------------------------------------------------------
@@ -2038,7 +1974,6 @@ __device__ __forceinline__ void octreeSelectBig(OctScratch S, const u64* __restr
     }
     if (tid == 0) *nOut = min(alive, N);
   }
-  OCT_STAMP(15);
 }
 #endif  // OCT_T >= 1024
 

@@ -31,69 +31,6 @@ namespace orbx {
 
 #define OCT_DEPTH 16
 
-// Diagnostic build only (-DORBX_OCT_STAMPS): s_memtime stamps of the selection kernel's phases, per workgroup, into a
-// buffer nothing else reads (cdna_hip_programming.md section 7).  The production build contains no stamp.
-#ifdef ORBX_OCT_STAMPS
-#define OCT_NSTAMP 16
-__device__ unsigned long long g_octStamps[4096 * OCT_NSTAMP];
-#define OCT_STAMP(k)                                                                                         \
-  do {                                                                                                       \
-    __syncthreads();                                                                                         \
-    if (threadIdx.x == 0) {                                                                                  \
-      const int b_ = (blockIdx.y * gridDim.x + blockIdx.x) & 4095;                                           \
-      g_octStamps[b_ * OCT_NSTAMP + (k)] = __builtin_amdgcn_s_memtime();                                     \
-    }                                                                                                        \
-  } while (0)
-#define OCT_STAMP_ACC(k, t0)                                                                                 \
-  do {                                                                                                       \
-    __syncthreads();                                                                                         \
-    if (threadIdx.x == 0) {                                                                                  \
-      const int b_ = (blockIdx.y * gridDim.x + blockIdx.x) & 4095;                                           \
-      const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                          \
-      g_octStamps[b_ * OCT_NSTAMP + (k)] += now_ - (t0);                                                     \
-      (t0) = now_;                                                                                           \
-    }                                                                                                        \
-  } while (0)
-// ... the std::sort replay's phases, summed over its recursion levels (slot 7 = levels), per workgroup
-__device__ unsigned long long g_octReplay[4096 * 8];
-#define OCT_REPLAY_INIT() unsigned long long tRep_ = __builtin_amdgcn_s_memtime(); \
-  if (threadIdx.x == 0) for (int k_ = 0; k_ < 8; k_++) g_octReplay[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * 8 + k_] = 0
-#define OCT_REPLAY_ACC(k)                                                                                   \
-  do {                                                                                                      \
-    if (threadIdx.x == 0) {                                                                                 \
-      const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                         \
-      g_octReplay[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * 8 + (k)] += now_ - tRep_;                \
-      tRep_ = now_;                                                                                         \
-    }                                                                                                       \
-  } while (0)
-#define OCT_REPLAY_COUNT(k) do { if (threadIdx.x == 0) g_octReplay[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * 8 + (k)] += 1; } while (0)
-extern "C" int orbx_diag_oct_replay(unsigned long long* out, int nBlocks) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_octReplay), sizeof(unsigned long long) * 8 * nBlocks);
-}
-// ... and which XCD the bucket waves / the unit's workgroup of the many-workgroup selection ran on (placement check)
-__device__ unsigned int g_octXcc[4096 * 9];
-#define OCT_XCC_B1(u) atomicAdd(&g_octXcc[((u) & 4095) * 9 + (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 7)], 1u)
-#define OCT_XCC_B2(u) g_octXcc[((u) & 4095) * 9 + 8] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 7
-// ... and per bucket wave of k_octree_buckets: s_memtime behind its phases, the bucket's key count (tools/octb_stamps.py)
-#define OCTB_NSTAMP 8
-__device__ unsigned long long g_octbStamps[65536 * OCTB_NSTAMP];
-#define OCTB_STAMP(k) do { if (lane == 0) g_octbStamps[((blockIdx.x * OCTB_WAVES + wv) & 65535) * OCTB_NSTAMP + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define OCTB_STAMP_V(k, v) do { if (lane == 0) g_octbStamps[((blockIdx.x * OCTB_WAVES + wv) & 65535) * OCTB_NSTAMP + (k)] = (unsigned long long)(v); } while (0)
-extern "C" int orbx_diag_octb_stamps(unsigned long long* out, int nWaves) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_octbStamps), sizeof(unsigned long long) * 8 * (size_t)nWaves);
-}
-#else
-#define OCT_REPLAY_INIT() do {} while (0)
-#define OCT_REPLAY_ACC(k) do {} while (0)
-#define OCT_REPLAY_COUNT(k) do {} while (0)
-#define OCTB_STAMP(k) do {} while (0)
-#define OCTB_STAMP_V(k, v) do {} while (0)
-#define OCT_XCC_B1(u) do {} while (0)
-#define OCT_XCC_B2(u) do {} while (0)
-#define OCT_STAMP(k) do {} while (0)
-#define OCT_STAMP_ACC(k, t0) do {} while (0)
-#endif
-
 typedef unsigned long long u64;
 
 // sizes shared by both instances of the device code
@@ -140,7 +77,6 @@ __global__ __launch_bounds__(OCT_T) void k_octree_lds(const uint32_t* __restrict
                                                      const OctLaunch P, SelKp* __restrict__ selStage,
                                                      int* __restrict__ nselLevel, uint8_t* __restrict__ scratch,
                                                      int* __restrict__ maxN, int deferBig, int level0) {
-  ORBX_SETPRIO();
   constexpr int MCAP = 4 * QMAX, FCAP = 2 * QMAX;
   static_assert((NMAX & (NMAX - 1)) == 0 && (MCAP & (MCAP - 1)) == 0, "sort buffers must be powers of two");
   // LDS budget (QMAX 256): NMAX 2048: 16 + 8 + 4 + 6 + 2 + 3 KB = 39 KB -> FOUR workgroups per CU (it was 51 KB and three
@@ -225,7 +161,6 @@ static_assert(OCT_SORT_LDS >= 1024, "the register sort of the 1024-thread instan
 __global__ __launch_bounds__(1024) void k_octree_global(const uint32_t* __restrict__ cand, const int* __restrict__ cellCount,
                                                        const OctLaunch P, SelKp* __restrict__ selStage,
                                                        int* __restrict__ nselLevel, uint8_t* __restrict__ scratch, int all, int level0) {
-  ORBX_SETPRIO();
   // exchange buffer: 2048 keys for the register sorts, and 512 x 16 digit counters (9-bit digits) for the radix sort
   __shared__ u64 xchg[OCT_GLOBAL_XCHG];
   // scratch of the workgroup-parallel std::sort replay for up to 2048 pending nodes (the level-0 quota of 1080p / 4000 features is
@@ -302,8 +237,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
                                                           const OctLaunch P, uint8_t* __restrict__ scratch, int level0, int level1,
                                                           int nFrames) {
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  OCTB_STAMP(0);
-  OCTB_STAMP_V(6, 0);
   int level, f, b;
   {
     const int nUnits = (level1 - level0) * nFrames;
@@ -322,7 +255,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
       k -= nb;
     }
     level = level0 + u / nFrames; f = P.frame0 + u % nFrames; b = k;
-    if (lane == 0) OCT_XCC_B1(u);
   }
   const OctLevel& L = P.lev[level];
   static_assert(CAP <= ORBX_OCTB_CAP && CAP >= 64, "bucket slots in LDS");
@@ -383,7 +315,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
     if (lane == 0) cpre[nc] = nRaw;
   }
   OCTB_WAVE_SYNC();
-  OCTB_STAMP(1);
   const uint32_t* segBase = cand + P.candOff[level] + (int64_t)f * P.candCap[level];
   const uint2* __restrict__ tabX = reinterpret_cast<const uint2*>(P.codeTab + L.tabOff);
   const uint32_t* __restrict__ tabY = P.codeTab + L.tabOff + 2 * L.tabW;
@@ -437,9 +368,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
     return;
   }
   static_assert(ORBX_OCTB_CAP <= 1024, "ten slot bits in a sort key");
-  OCTB_STAMP(2);
-  OCTB_STAMP_V(6, n + 1);
-  OCTB_STAMP_V(7, nRaw);
   static_assert(ORBX_OCTB_CAP <= 16 * 64, "register sort: at most sixteen keys per lane");
   int nPad = 64;
   while (nPad < n) nPad <<= 1;
@@ -454,7 +382,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
     else waveSort32<16>(keysL, lane);
   }
   OCTB_WAVE_SYNC();
-  OCTB_STAMP(3);
   // the 16-level path code of sorted key i: root | the bucket's digits | the sorted digits | zeros
   const u64 codeTop = ((u64)root << 32) | (d0 > 0 ? (u64)((uint32_t)(b & ((1 << (2 * d0)) - 1)) << (32 - 2 * d0)) : 0ull);
   auto codeAt = [&](int i) { return codeTop | ((u64)(keysL[i] >> 10) << rshift); };
@@ -504,7 +431,6 @@ __global__ __launch_bounds__(OCTB_T) void k_octree_buckets(const uint32_t* __res
     info[0] = n; info[3] = 0;
     if (n < 2) { info[1] = 255; info[2] = 255; }
   }
-  OCTB_STAMP(4);
 }
 static_assert(ORBX_OCTB_INFO >= 4 + 2 * (OCT_DEPTH + 2), "a bucket's record holds both histograms");
 
@@ -514,7 +440,6 @@ static_assert(ORBX_OCTB_INFO >= 4 + 2 * (OCT_DEPTH + 2), "a bucket's record hold
 __global__ __launch_bounds__(1024) void k_octree_big(const uint32_t* __restrict__ cand, const int* __restrict__ cellCount, const OctLaunch P,
                                                     SelKp* __restrict__ selStage, int* __restrict__ nselLevel,
                                                     uint8_t* __restrict__ scratch, int* __restrict__ maxN, int level0, int fallback) {
-  ORBX_SETPRIO();
   __shared__ __attribute__((aligned(16))) u64 xchg[OCTBIG_XCHG];
   __shared__ __attribute__((aligned(16))) uint32_t parScr[OCT_PAR_SCR_FOR(OCT_PAR_BIG)];
   __shared__ __attribute__((aligned(16))) uint32_t nodeLH[OCTBIG_NODES];
@@ -530,7 +455,6 @@ __global__ __launch_bounds__(1024) void k_octree_big(const uint32_t* __restrict_
   S.xchg = xchg; S.xchgCap = OCTBIG_XCHG;
   S.parScr = parScr; S.parCap = OCT_PAR_BIG;
   S.nodeLH = nodeLH; S.nodeUlx = nodeUlx; S.pNd = pNd; S.pLo = pLo; S.pHiD = pHiD; S.pUlx = pUlx;
-  if (threadIdx.x == 0) OCT_XCC_B2(blockIdx.y * gridDim.x + blockIdx.x);
   __shared__ int handedOn, redoneCount;
   if (threadIdx.x == 0) handedOn = 1;
   __syncthreads();
@@ -558,12 +482,9 @@ __global__ __launch_bounds__(1024) void k_octree_big(const uint32_t* __restrict_
 // range's first key with the highest response (cpp:984-1007) is the key with the largest score.  One thread per range, 256 per
 // workgroup (many workgroups: one CU's L1 takes ~4 cycles per scattered line, 45 k cycles for the 1737 ranges of a 4K level 0),
 // every range's scores in flight sixteen at a time.
-#ifndef ORBX_TAIL_T
 #define ORBX_TAIL_T 64  // threads per workgroup of k_octree_emit / k_sel_compact: ONE wave (see k_sel_compact)
-#endif
 __global__ __launch_bounds__(ORBX_TAIL_T) void k_octree_emit(const OctLaunch P, SelKp* __restrict__ selStage, const int* __restrict__ nselLevel,
                                                     uint8_t* __restrict__ scratch, int level0) {
-  ORBX_SETPRIO();
   const int level = blockIdx.y + level0, f = blockIdx.x + P.frame0;
   const int nOutNodes = nselLevel[f * P.nlevels + level];
   const int p = blockIdx.z * ORBX_TAIL_T + threadIdx.x;
@@ -614,7 +535,6 @@ __global__ __launch_bounds__(ORBX_TAIL_T) void k_sel_compact(const SelKp* __rest
                                                      int* __restrict__ nselUser, int* __restrict__ hostNsel, int selCap,
                                                      int* __restrict__ hostErr, int* __restrict__ maxN,
                                                      int* __restrict__ hostMaxN) {
-  ORBX_SETPRIO();
   // grid (frames, parts): the workgroups (frame, 0 .. parts - 1) share the frame's copy; (frame, 0) writes its totals
   constexpr int T = ORBX_TAIL_T;
   const int f = blockIdx.x + P.frame0, part = blockIdx.y, parts = gridDim.y;
@@ -685,23 +605,14 @@ hipError_t launch_octree(hipStream_t st, int nFrames, const uint32_t* cand, cons
   // scratch: when a level expects them (a quota above 256, or more than 2048 candidates in a unit of the previous
   // batch) they are deferred to k_octree_global, which gives each of them 1024 threads; otherwise the LDS kernel's own
   // workgroup handles the rare outlier and no second kernel is launched.
-  // force: 0 = choose per level from hintL (nullptr = unknown); 2048 / 1024 / 512 = that LDS instance for every level (test
-  // hook, diagnostics); -1 = every unit on global scratch (test hook).
-  const bool noSmall = knobOn(KNOB_OCT_NO_SMALL);  // diagnostics (orbx_debug_set): always the 2048-candidate instance
-  const bool key64Env = knobOn(KNOB_OCT_KEY64);    // diagnostics: always 64-bit sort keys
-  const bool key64 = key64Env || (force & 0x10000) != 0;               // (test hook: force | 0x10000)
+  // force: 0 = choose from hintL (nullptr = unknown); 2048 / 1024 / 512 = that LDS instance for every level (test hook);
+  // -1 = every unit on global scratch (test hook); | 0x10000 = 64-bit sort keys (test hook).
+  const bool key64 = (force & 0x10000) != 0;
   force = force < 0 ? force : (force & 0xffff);
-  // knob oct_split_min (diagnostics) = batch size from which every group of consecutive levels with the same instance gets its
-  // own launch.  Off by default: measured on the bench workload (256 frames, four lanes) 2048 | 1024 x 2 | 512 x 5 gives 295.9 k
-  // frames/s, 2048 x 3 | 512 x 5 300.2 k, 2048 | 1024 x 7 302.3 k against 306.6 k with ONE launch on the largest instance --
-  // consecutive launches of a stream do not overlap (hipExtAnyOrderLaunch is ignored on gfx9: tools/microbench/any_order.hip),
-  // so every group adds its own tail, and that costs more than the smaller units' LDS gives back to the other lanes.
-  const int splitMin = (int)knob(KNOB_OCT_SPLIT_MIN, 1 << 30);
   if (usedInstance) *usedInstance = 0;
   // Large units (levels that expect them): k_octree_buckets sorts every unit's keys bucket by bucket on many workgroups,
   // k_octree_big does the tree arithmetic with one workgroup per unit (and redoes a unit it cannot take with the one-workgroup
-  // code of k_octree_global, the round-1..3 path), k_octree_emit picks the keypoints.  knob oct_no_big (diagnostics): the old path.
-  const bool noBig = knobOn(KNOB_OCT_NO_BIG);
+  // code of k_octree_global, the round-1..3 path), k_octree_emit picks the keypoints.
   OctLaunch Q = P;  // the launch's bucket depths: from the candidate counts of the previous batch (octBigChoose)
   // (hintL: ORBX_OCT_FEEDBACK values -- the previous batch's largest candidate count and fullest bucket per level)
   auto hintOf = [&](int l) { return hintL ? ORBX_OCT_FB_COUNT(hintL[l]) : 0; };
@@ -739,9 +650,8 @@ hipError_t launch_octree(hipStream_t st, int nFrames, const uint32_t* cand, cons
           known = known && fl > 0;
           fillMost = std::max(fillMost, fl);
         }
-      const bool noSmallSlots = knobOn(KNOB_OCTB_NO_512);  // diagnostics
       const dim3 bgrid((unsigned)(8 * ((most + OCTB_WAVES - 1) / OCTB_WAVES)), 1, 1);
-      if (known && !noSmallSlots && fillMost * 4 <= 512 * 3)
+      if (known && fillMost * 4 <= 512 * 3)
         hipLaunchKernelGGL(k_octree_buckets<512>, bgrid, dim3(OCTB_T), 0, st, cand, cellCount, Q, scratch, l0, l1, nFrames);
       else
         hipLaunchKernelGGL(k_octree_buckets<ORBX_OCTB_CAP>, bgrid, dim3(OCTB_T), 0, st, cand, cellCount, Q, scratch, l0, l1, nFrames);
@@ -763,73 +673,54 @@ hipError_t launch_octree(hipStream_t st, int nFrames, const uint32_t* cand, cons
                        1, 0);
     return hipGetLastError();
   }
-  int inst[ORBX_MAX_LEVELS];
-  int largest = 512;
-  bool anyBig = false;
+  // One launch for every level, on the largest instance any level needs (the levels of the reference's own 640x480 images stay
+  // below 960 candidates -> 30 KB units; sparse scenes with small quotas -> 17 KB units).  A launch per group of consecutive levels
+  // with the same instance was measured slower on the bench workload (256 frames, four lanes): 2048 | 1024 x 2 | 512 x 5 gives
+  // 295.9 k frames/s, 2048 x 3 | 512 x 5 300.2 k, 2048 | 1024 x 7 302.3 k against 306.6 k with one launch -- consecutive launches
+  // of a stream do not overlap (hipExtAnyOrderLaunch is ignored on gfx9: tools/microbench/any_order.hip), so every group adds its
+  // own tail, and that costs more than the smaller units' LDS gives back to the other lanes (docs/history.md).
+  int inst = force;
+  if (force == 0) {
+    inst = 512;
+    for (int l = 0; l < P.nlevels && inst != 0; l++) {
+      const int i = octInstanceFor(P.lev[l].quota, hintOf(l));
+      inst = i == 0 ? 0 : std::max(inst, i);  // (0: some level goes to k_octree_global)
+    }
+  }
+  if (usedInstance) *usedInstance = inst;
+  const dim3 grid(nFrames, P.nlevels, 1), block(OCT_T, 1, 1);
+  // 32-bit sort keys when the path codes of every level fit 21 bits (frames up to ~1024 px per root and side: VGA, 752x480,
+  // 1080p; not 4K)
+  bool k32 = !key64;
   for (int l = 0; l < P.nlevels; l++) {
-    inst[l] = force > 0 ? force : octInstanceFor(P.lev[l].quota, hintOf(l));
-    if (noSmall && inst[l] != 0 && force == 0) inst[l] = 2048;
-    if (inst[l] == 0) anyBig = true;
-    largest = std::max(largest, inst[l] == 0 ? 2048 : inst[l]);
+    const int rootBits = P.lev[l].nIni > 1 ? 32 - __builtin_clz((unsigned)(P.lev[l].nIni - 1)) : 0;
+    k32 = k32 && P.lev[l].depthBits >= 1 && rootBits + 2 * P.lev[l].depthBits <= 21;
   }
-  // One launch on the largest instance any level needs (the levels of the reference's own 640x480 images stay below 960
-  // candidates -> 30 KB units; sparse scenes with small quotas -> 17 KB units).
-  if (nFrames < splitMin && force == 0)
-    for (int l = 0; l < P.nlevels; l++) inst[l] = anyBig ? 0 : largest;
-  const long long instKnob = knob(KNOB_OCT_INST, 0);  // diagnostics: one hex digit per level, 1 = 512, 2 = 1024, 3 = 2048
-  if (instKnob && force == 0 && !anyBig && hintL && hintOf(0) > 0) {
-    for (int l = 0; l < P.nlevels && l < 16; l++) {
-      const int dgt = (int)((instKnob >> (4 * l)) & 15);
-      const int v = dgt == 1 ? 512 : dgt == 2 ? 1024 : dgt == 3 ? 2048 : 0;
-      if (v) inst[l] = std::max(inst[l] == largest ? octInstanceFor(P.lev[l].quota, hintOf(l)) : inst[l], v);
-    }
-  }
-  if (usedInstance) {  // the smallest instance any level runs on (0: some level goes to k_octree_global)
-    int m = 1 << 30;
-    for (int l = 0; l < P.nlevels; l++) m = std::min(m, inst[l]);
-    *usedInstance = m;
-  }
-  for (int l0 = 0; l0 < P.nlevels;) {
-    int l1 = l0 + 1;
-    while (l1 < P.nlevels && inst[l1] == inst[l0]) l1++;
-    const dim3 grid(nFrames, l1 - l0, 1), block(OCT_T, 1, 1);
-    // 32-bit sort keys when the path codes of every level of the launch fit 21 bits (frames up to ~1024 px per root and
-    // side: VGA, 752x480, 1080p; not 4K)
-    bool k32 = !key64;
-    for (int l = l0; l < l1; l++) {
-      const int rootBits = P.lev[l].nIni > 1 ? 32 - __builtin_clz((unsigned)(P.lev[l].nIni - 1)) : 0;
-      k32 = k32 && P.lev[l].depthBits >= 1 && rootBits + 2 * P.lev[l].depthBits <= 21;
-    }
-    const int ldsPad = (int)knob(KNOB_OCT_LDS_PAD, 0);  // diagnostics: fewer units per CU
-#define ORBX_OCT_LAUNCH(N_, Q_, DEFER_)                                                                                             \
-  do {                                                                                                                              \
-    if (k32)                                                                                                                        \
-      hipLaunchKernelGGL((k_octree_lds<N_, Q_, true>), grid, block, ldsPad, st, cand, cellCount, P, selStage, nselLevel, scratch, maxN, DEFER_, l0);  \
-    else                                                                                                                            \
-      hipLaunchKernelGGL((k_octree_lds<N_, Q_, false>), grid, block, ldsPad, st, cand, cellCount, P, selStage, nselLevel, scratch, maxN, DEFER_, l0); \
+#define ORBX_OCT_LAUNCH(N_, Q_, DEFER_)                                                                                          \
+  do {                                                                                                                           \
+    if (k32)                                                                                                                     \
+      hipLaunchKernelGGL((k_octree_lds<N_, Q_, true>), grid, block, 0, st, cand, cellCount, P, selStage, nselLevel, scratch, maxN, DEFER_, 0);  \
+    else                                                                                                                         \
+      hipLaunchKernelGGL((k_octree_lds<N_, Q_, false>), grid, block, 0, st, cand, cellCount, P, selStage, nselLevel, scratch, maxN, DEFER_, 0); \
   } while (0)
-    switch (inst[l0]) {
-      case 512: ORBX_OCT_LAUNCH(512, 128, 0); break;
-      case 1024: ORBX_OCT_LAUNCH(1024, 256, 0); break;
-      case 2048: ORBX_OCT_LAUNCH(2048, 256, 0); break;
-      default: {  // the level expects large units
-        bool planned = !noBig;
-        for (int l = l0; l < l1; l++) planned = planned && Q.lev[l].bigBuckets > 0;
-        if (planned) {
-          launchBig(l0, l1, !knobOn(KNOB_OCT_BIG_NO_FALLBACK));
-        } else {  // what fits the LDS layout is done there, the rest is deferred to the one-workgroup kernel
-          ORBX_OCT_LAUNCH(2048, 256, 1);
-          hipLaunchKernelGGL(k_octree_global, grid, dim3(1024), 0, st, cand, cellCount, P, selStage, nselLevel, scratch, 0, l0);
-        }
-        break;
+  switch (inst) {
+    case 512: ORBX_OCT_LAUNCH(512, 128, 0); break;
+    case 1024: ORBX_OCT_LAUNCH(1024, 256, 0); break;
+    case 2048: ORBX_OCT_LAUNCH(2048, 256, 0); break;
+    default: {  // some level expects large units
+      bool planned = true;
+      for (int l = 0; l < P.nlevels; l++) planned = planned && Q.lev[l].bigBuckets > 0;
+      if (planned) {
+        launchBig(0, P.nlevels, !knobOn(KNOB_OCT_BIG_NO_FALLBACK));
+      } else {  // what fits the LDS layout is done there, the rest is deferred to the one-workgroup kernel
+        ORBX_OCT_LAUNCH(2048, 256, 1);
+        hipLaunchKernelGGL(k_octree_global, grid, dim3(1024), 0, st, cand, cellCount, P, selStage, nselLevel, scratch, 0, 0);
       }
+      break;
     }
-#undef ORBX_OCT_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    l0 = l1;
   }
-  return hipSuccess;
+#undef ORBX_OCT_LAUNCH
+  return hipGetLastError();
 }
 
 hipError_t launch_sel_compact(hipStream_t st, int nFrames, const SelKp* selStage, const int* nselLevel, const OctLaunch& P,
@@ -840,14 +731,6 @@ hipError_t launch_sel_compact(hipStream_t st, int nFrames, const SelKp* selStage
   return hipGetLastError();
 }
 
-#ifdef ORBX_OCT_STAMPS
-extern "C" int orbx_diag_oct_stamps(unsigned long long* out, int nBlocks) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_octStamps), sizeof(unsigned long long) * OCT_NSTAMP * nBlocks);
-}
-extern "C" int orbx_diag_oct_xcc(unsigned int* out, int nUnits) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_octXcc), sizeof(unsigned int) * 9 * nUnits);
-}
-#endif
 
 // ---- test hook: the std::sort replay alone (partition phase on one lane + parallel stable rank sort) ---------------
 __global__ __launch_bounds__(OCT_T) void k_debug_sort(int* triples, int n, u64* a, u64* b) {

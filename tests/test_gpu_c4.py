@@ -321,14 +321,11 @@ def test_multi_c_abi_forced_rccl_one_device(orbx, c4_oracle, monkeypatch):
     import torch
     torch.cuda.init()
     monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    orbx.debug_set("multi_force_rccl", 1)
-    try:
+    with orbx.knobs(multi_force_rccl=1):
         _multi_run(orbx, [0], 64, c4_oracle)
         assert "librccl" in open("/proc/self/maps").read(), "RCCL was not loaded: the forced path did not run"
         _multi_async_run(orbx, [0], c4_oracle, 3, nbatch=4, n_frames=64)
         _multi_async_run(orbx, [0], c4_oracle, 0, nbatch=3, n_frames=64)
-    finally:
-        orbx.debug_set("multi_force_rccl", None)
 
 
 def test_bench_force_collective_one_rank(orbx):

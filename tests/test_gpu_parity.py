@@ -340,22 +340,21 @@ def test_brute_force_on_the_matrix_cores(orbx, oracle):
         NP = len(first)
         out = []
         for knob in (None, 1):
-            orbx.debug_set("match_no_mfma", knob)
-            d_m = torch.full((NP * cap,), -7, dtype=torch.int32, device=dev)
-            d_nm = torch.zeros(NP, dtype=torch.int32, device=dev)
-            d_st = torch.zeros(3 * NP, dtype=torch.int32, device=dev)
-            before = ext.debug_match_counters()["bf_mfma_blocks"]
-            ext.match_pairs_device(first, first + 1, d_k, d_d, d_n, (0, W, 0, H), d_m, d_nm, d_st, window, ratio, ori, cap)
-            torch.cuda.synchronize()
-            took = ext.debug_match_counters()["bf_mfma_blocks"] - before
-            # the matrix kernel really listed blocks of this launch (a changed launch rule must not leave the
-            # test green on the vector form alone) -- and under the knob it listed none
-            if knob is None:
-                assert took >= min_mfma_blocks, (took, min_mfma_blocks)
-            else:
-                assert took == 0, took
-            out.append((d_m.cpu().numpy().reshape(NP, cap), d_nm.cpu().numpy(), d_st.cpu().numpy().reshape(NP, 3)))
-        orbx.debug_set("match_no_mfma", None)
+            with orbx.knobs(match_no_mfma=knob):
+                d_m = torch.full((NP * cap,), -7, dtype=torch.int32, device=dev)
+                d_nm = torch.zeros(NP, dtype=torch.int32, device=dev)
+                d_st = torch.zeros(3 * NP, dtype=torch.int32, device=dev)
+                before = ext.debug_match_counters()["bf_mfma_blocks"]
+                ext.match_pairs_device(first, first + 1, d_k, d_d, d_n, (0, W, 0, H), d_m, d_nm, d_st, window, ratio, ori, cap)
+                torch.cuda.synchronize()
+                took = ext.debug_match_counters()["bf_mfma_blocks"] - before
+                # the matrix kernel really listed blocks of this launch (a changed launch rule must not leave the
+                # test green on the vector form alone) -- and under the knob it listed none
+                if knob is None:
+                    assert took >= min_mfma_blocks, (took, min_mfma_blocks)
+                else:
+                    assert took == 0, took
+                out.append((d_m.cpu().numpy().reshape(NP, cap), d_nm.cpu().numpy(), d_st.cpu().numpy().reshape(NP, 3)))
         for i, (k1, d1, k2, d2) in enumerate(sets):
             onm, om12, ost = oracle.match_init(k1, d1, k2, d2, (0, W, 0, H), window, ratio, ori)
             for (m, nm, st) in out:
@@ -388,7 +387,6 @@ def test_brute_force_on_the_matrix_cores(orbx, oracle):
         sets3 = [(k1, d1[:len(k1)], k2, d2) for (k1, d1, k2, d2) in sets3] + sets[48:]
         run(sets3, 8192, 0.9, True, reps=5)
     finally:
-        orbx.debug_set("match_no_mfma", None)
         ext.close()
 
 
@@ -451,11 +449,8 @@ def test_wide_matcher_contention(orbx, ext640, oracle):
         assert nm == onm and np.array_equal(m12, om12) and list(m.last_stats) == ost.tolist(), (n, npro, win)
         if must:
             assert onm > 50
-            orbx.debug_set("match_no_general", 1)
-            try:
+            with orbx.knobs(match_no_general=1):
                 nm2, m12b = m.SearchForInitialization(fa, fb, win)
-            finally:
-                orbx.debug_set("match_no_general", None)
             assert nm2 == onm and np.array_equal(m12b, om12), "the wide path handed the pair on: %r" % ((n, npro, win),)
 
 
@@ -808,32 +803,28 @@ def test_redone_and_failed_units_through_both_bookkeepers(orbx, oracle, B):
     d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
     d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
     try:
-        orbx.debug_set("no_split", 1)  # (one launch of B frames: B * 8 units)
-        orbx.debug_set("oct_big_depth", 0)
-        for it in range(2):
-            e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
-            info = e.debug_last_launch()
-            assert info["staged_lists"] == (1 if B * 8 <= 256 else 0) and info["octree_instance"] == 0, info
-            assert e.debug_selection_units(0)[1][0] == 1 and e.debug_selection_units(B - 1)[1][0] == 1  # level 0 was redone
+        with orbx.knobs(no_split=1):  # (one launch of B frames: B * 8 units)
+            with orbx.knobs(oct_big_depth=0):
+                for it in range(2):
+                    e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
+                    info = e.debug_last_launch()
+                    assert info["staged_lists"] == (1 if B * 8 <= 256 else 0) and info["octree_instance"] == 0, info
+                    assert e.debug_selection_units(0)[1][0] == 1 and e.debug_selection_units(B - 1)[1][0] == 1  # level 0 was redone
+                    n = d_n.cpu().numpy()
+                    kk = d_k.cpu().numpy().view(orbx.KEYPOINT_DTYPE).reshape(B, cap)
+                    dd = d_d.cpu().numpy().reshape(B, cap, 32)
+                    for f, (_, ko, do) in zip((0, B - 1), ora):
+                        assert n[f] == len(ko)
+                        _same(kk[f, :n[f]], dd[f, :n[f]], ko, do)
+                with orbx.knobs(oct_big_no_fallback=1):
+                    with pytest.raises(orbx.OrbxError) as ex:
+                        e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
+                    assert ex.value.code == orbx.E_CAPACITY
+                    assert e.debug_selection_units(0)[0][0] < 0
+            e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)  # the context works on
             n = d_n.cpu().numpy()
-            kk = d_k.cpu().numpy().view(orbx.KEYPOINT_DTYPE).reshape(B, cap)
-            dd = d_d.cpu().numpy().reshape(B, cap, 32)
-            for f, (_, ko, do) in zip((0, B - 1), ora):
-                assert n[f] == len(ko)
-                _same(kk[f, :n[f]], dd[f, :n[f]], ko, do)
-        orbx.debug_set("oct_big_no_fallback", 1)
-        with pytest.raises(orbx.OrbxError) as ex:
-            e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
-        assert ex.value.code == orbx.E_CAPACITY
-        assert e.debug_selection_units(0)[0][0] < 0
-        orbx.debug_set("oct_big_no_fallback", None)
-        orbx.debug_set("oct_big_depth", None)
-        e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)  # the context works on
-        n = d_n.cpu().numpy()
-        assert n[0] == len(ora[0][1])
+            assert n[0] == len(ora[0][1])
     finally:
-        for k in ("no_split", "oct_big_depth", "oct_big_no_fallback"):
-            orbx.debug_set(k, None)
         e.close()
 
 
@@ -1664,20 +1655,19 @@ def test_tiled_pyramid_small_batches(orbx, oracle, params):
             continue
         level_by_level = pad < 0  # (the last case: the per-level launches, which no default batch size takes any more)
         pad = max(pad, 0)
-        orbx.debug_set("no_bands", 1 if level_by_level else None)
-        frames = synth.synth_frames(B, w, h, 6100 + w)
-        stride = w + pad
-        buf = np.zeros((B, h, stride), np.uint8)
-        buf[:, :, :w] = frames
-        oe = oracle.Extractor(*params)
-        e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
-        d_img = torch.from_numpy(buf).cuda()
-        d_k = torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda")
-        d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
-        d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
-        e.extract_batch_device(d_img, B, w, h, stride, stride * h, d_k, d_d, d_n, cap)
-        info = e.debug_last_launch()
-        orbx.debug_set("no_bands", None)
+        with orbx.knobs(no_bands=1 if level_by_level else None):
+            frames = synth.synth_frames(B, w, h, 6100 + w)
+            stride = w + pad
+            buf = np.zeros((B, h, stride), np.uint8)
+            buf[:, :, :w] = frames
+            oe = oracle.Extractor(*params)
+            e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
+            d_img = torch.from_numpy(buf).cuda()
+            d_k = torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda")
+            d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
+            d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
+            e.extract_batch_device(d_img, B, w, h, stride, stride * h, d_k, d_d, d_n, cap)
+            info = e.debug_last_launch()
         assert (info["pyramid_banded"] == 2) if B <= 8 else (info["pyramid_banded"] == 0 if level_by_level else info["pyramid_banded"] in (0, 1)), (w, h, B, info)
         if B > 8 and not level_by_level and params[1] == 1.2:
             assert info["pyramid_banded"] == 1, info  # (scale 1.2 on aligned 640x480 frames: nothing keeps the banded kernel away)
@@ -1702,37 +1692,32 @@ def test_banded_pyramid_column_strips(orbx, oracle):
     library's own choice for the four-frame halves of a 3840x2160 batch (24 bands x 8 strips), whole extraction against the oracle."""
     import torch
     from orb_slam_tracking_amd import synth
-    try:
-        orbx.debug_set("bands_min_frames", 1)
+    with orbx.knobs(bands_min_frames=1):
         for (w, h, B, params, K, S) in ((1280, 720, 3, (1500, 1.2, 8, 20, 7), 8, 2), (1284, 723, 2, (1500, 1.2, 8, 20, 7), 6, 4),
                                         (2044, 600, 2, (1500, 1.2, 6, 20, 7), 4, 8), (1600, 900, 2, (1000, 1.5, 5, 20, 7), 5, 3),
                                         (900, 500, 2, (1000, 1.2, 8, 20, 7), 3, 8)):  # (the last: fewer strips than asked, a level is too narrow)
-            orbx.debug_set("pyr_bands", K)
-            orbx.debug_set("pyr_strips", S)
-            frames = synth.synth_frames(B, w, h, 8100 + w)
-            oe = oracle.Extractor(*params)
-            e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
-            cap = params[0]
-            d_img = torch.from_numpy(frames).cuda()
-            d_k = torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda")
-            d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
-            d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
-            e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
-            info = e.debug_last_launch()
-            assert info["pyramid_banded"] == 1 and info["pyramid_bands"] % K == 0 and (info["pyramid_bands"] == K * S or w == 900), info
-            n = d_n.cpu().numpy()
-            kk = d_k.cpu().numpy().view(orbx.KEYPOINT_DTYPE).reshape(B, cap)
-            dd = d_d.cpu().numpy().reshape(B, cap, 32)
-            for f in range(B):
-                _, ko, do = oe(frames[f], cap=cap)
-                for l in range(1, params[2]):
-                    assert np.array_equal(e.image_pyramid(l, f), oe.level_image(l)), (w, h, K, S, f, l)
-                assert n[f] == len(ko)
-                _same(kk[f, :n[f]], dd[f, :n[f]], ko, do)
-            e.close()
-    finally:
-        for k in ("bands_min_frames", "pyr_bands", "pyr_strips"):
-            orbx.debug_set(k, None)
+            with orbx.knobs(pyr_bands=K, pyr_strips=S):
+                frames = synth.synth_frames(B, w, h, 8100 + w)
+                oe = oracle.Extractor(*params)
+                e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
+                cap = params[0]
+                d_img = torch.from_numpy(frames).cuda()
+                d_k = torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda")
+                d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
+                d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
+                e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
+                info = e.debug_last_launch()
+                assert info["pyramid_banded"] == 1 and info["pyramid_bands"] % K == 0 and (info["pyramid_bands"] == K * S or w == 900), info
+                n = d_n.cpu().numpy()
+                kk = d_k.cpu().numpy().view(orbx.KEYPOINT_DTYPE).reshape(B, cap)
+                dd = d_d.cpu().numpy().reshape(B, cap, 32)
+                for f in range(B):
+                    _, ko, do = oe(frames[f], cap=cap)
+                    for l in range(1, params[2]):
+                        assert np.array_equal(e.image_pyramid(l, f), oe.level_image(l)), (w, h, K, S, f, l)
+                    assert n[f] == len(ko)
+                    _same(kk[f, :n[f]], dd[f, :n[f]], ko, do)
+                e.close()
     w, h, B, cap = 3840, 2160, 8, 8000
     params = (8000, 1.2, 8, 20, 7)
     frames = synth.synth_frames(B, w, h, 7400)

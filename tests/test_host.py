@@ -29,9 +29,15 @@ def test_abi_exports_every_declared_symbol(orbx):
         assert hasattr(L, n), "liborbx.so does not export %s" % n
 
 
-def test_library_reads_no_environment(orbx):
+# every knob the library accepts: the ones the tests, the kept tools and bench.py set (docs/history.md lists the retired ones)
+KNOBS_KEPT = ("no_bands", "pyr_bands", "pyr_strips", "bands_min_frames", "no_split", "lat_trace", "fast_wg_max_cells", "match_no_general",
+              "match_no_mfma", "oct_big_depth", "oct_big_no_fallback", "multi_force_rccl")
+
+
+def test_library_reads_no_environment_only_named_knobs(orbx):
     """The shipped library holds no getenv and no ORBX_* variable name: kernel choices are the library's own, and what the tests
-    and tools want to steer goes through orbx_debug_set's named knobs (csrc/orbx_knobs.h), which the Python loader mirrors."""
+    and tools want to steer goes through orbx_debug_set's named knobs (csrc/orbx_knobs.h), which the Python loader mirrors --
+    exactly the knobs of KNOBS_KEPT, no more and no fewer."""
     src = os.path.join(ROOT, "orb_slam_tracking_amd", "csrc")
     for fn in os.listdir(src):
         if fn.endswith((".cpp", ".hip", ".inc", ".h")):
@@ -39,7 +45,7 @@ def test_library_reads_no_environment(orbx):
     blob = open(orbx.lib_path(), "rb").read()
     assert not re.findall(rb"\x00ORBX_[A-Z0-9_]+\x00", blob)
     names = re.findall(r'X\(KNOB_[A-Z0-9_]+, "([a-z0-9_]+)"\)', open(os.path.join(src, "orbx_knobs.h")).read())
-    assert tuple(names) == orbx.KNOBS and len(names) >= 20
+    assert tuple(names) == orbx.KNOBS == KNOBS_KEPT
     L = ctypes.CDLL(orbx.lib_path())
     L.orbx_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     for n in names:

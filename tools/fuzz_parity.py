@@ -194,66 +194,66 @@ for t in range(trials):
         w, h = w // 2, h // 2
     params = (nf, sf, nlev, ini, mn)
     # small launches take k_fast (a workgroup per cell), large ones k_fast_wave; every other trial forces the latter (diagnostic knob)
-    orbx.debug_set("fast_wg_max_cells", 0 if t & 1 else None)
-    libm = 0 if t % 3 == 0 else 1  # every third trial with the DOUBLE libm reading (round 5), the oracle set to the same
-    O.set_libm_variant(libm)
-    tag = "trial %d: %dx%d B=%d %s params=%r%s%s" % (t, w, h, B, kind, params, " wave-per-cell" if t & 1 else "", " libm-double" if libm == 0 else "")
-    try:
-        e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
-        e.set_libm_variant(libm)
-    except orbx.OrbxError as err:
-        if err.code in (orbx.E_TOOSMALL, orbx.E_BADARG):
-            skipped += 1
-            print(tag, "-> skipped (%s)" % err)
-            continue
-        raise
-    oe = O.Extractor(*params)
-    fr = images(kind, B, w, h, 5000 + t)
-    cap = nf + 64
-    try:
-        res = e.extract_batch(fr)
-    except orbx.OrbxError as err:
-        if err.code == orbx.E_TOOSMALL:
-            skipped += 1
-            print(tag, "-> skipped (%s)" % err)
-            e.close()
-            continue
-        raise
-    ora = [oe(f, cap=cap) for f in fr]
-    ok = all(r[0] == o[0] and same(r[1], r[2], o[1], o[2]) for r, o in zip(res, ora))
-    # device-resident fused call (sync and stream-ordered) incl. matching of consecutive pairs
-    win = int(rng.choice([30, 100, 100, 400, 4096]))
-    ratio = float(rng.choice([0.9, 0.9, 0.6, 0.75, 1.0]))
-    ori = bool(rng.integers(0, 2))
-    if B >= 2:
-        d_img = torch.from_numpy(fr).cuda()
-        first = np.arange(0, B - 1, 2, dtype=np.int32)
-        npairs = len(first)
-        sets = []
-        for use_async in range(2):
-            o = dict(k=torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda"), d=torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda"),
-                     n=torch.zeros(B, dtype=torch.int32, device="cuda"), m=torch.zeros(npairs * cap, dtype=torch.int32, device="cuda"),
-                     nm=torch.zeros(npairs, dtype=torch.int32, device="cuda"), st=torch.zeros(npairs * 3, dtype=torch.int32, device="cuda"))
-            f = e.extract_match_batch_device_async if use_async else e.extract_match_batch_device
-            f(d_img, B, w, h, w, w * h, o["k"], o["d"], o["n"], first, first + 1, (0, w, 0, h), o["m"], o["nm"], o["st"], win, ratio, ori, cap)
-            sets.append(o)
-        e.wait()
-        for o in sets:
-            n = o["n"].cpu().numpy()
-            kk = o["k"].cpu().numpy().view(KP).reshape(B, cap)
-            dd = o["d"].cpu().numpy().reshape(B, cap, 32)
-            mm = o["m"].cpu().numpy().reshape(npairs, cap)
-            nm = o["nm"].cpu().numpy()
-            st = o["st"].cpu().numpy().reshape(npairs, 3)
-            for f_ in range(B):
-                ok &= n[f_] == len(ora[f_][1]) and same(kk[f_, :n[f_]], dd[f_, :n[f_]], ora[f_][1], ora[f_][2])
-            for p in range(npairs):
-                a, b = ora[2 * p], ora[2 * p + 1]
-                onm, om12, ost = O.match_init(a[1], a[2], b[1], b[2], (0, w, 0, h), win, ratio, ori)
-                ok &= nm[p] == onm and np.array_equal(mm[p, :len(om12)], om12) and st[p].tolist() == ost.tolist()
-    nk = [len(o[1]) for o in ora]
-    print(tag, "win=%d ratio=%.2f ori=%d keypoints=%d..%d ->" % (win, ratio, ori, min(nk), max(nk)), "ok" if ok else "MISMATCH", flush=True)
-    bad += not ok
-    e.close()
+    with orbx.knobs(fast_wg_max_cells=0 if t & 1 else None):
+        libm = 0 if t % 3 == 0 else 1  # every third trial with the DOUBLE libm reading (round 5), the oracle set to the same
+        O.set_libm_variant(libm)
+        tag = "trial %d: %dx%d B=%d %s params=%r%s%s" % (t, w, h, B, kind, params, " wave-per-cell" if t & 1 else "", " libm-double" if libm == 0 else "")
+        try:
+            e = orbx.ORBextractor(*params, max_width=w, max_height=h, max_batch=B)
+            e.set_libm_variant(libm)
+        except orbx.OrbxError as err:
+            if err.code in (orbx.E_TOOSMALL, orbx.E_BADARG):
+                skipped += 1
+                print(tag, "-> skipped (%s)" % err)
+                continue
+            raise
+        oe = O.Extractor(*params)
+        fr = images(kind, B, w, h, 5000 + t)
+        cap = nf + 64
+        try:
+            res = e.extract_batch(fr)
+        except orbx.OrbxError as err:
+            if err.code == orbx.E_TOOSMALL:
+                skipped += 1
+                print(tag, "-> skipped (%s)" % err)
+                e.close()
+                continue
+            raise
+        ora = [oe(f, cap=cap) for f in fr]
+        ok = all(r[0] == o[0] and same(r[1], r[2], o[1], o[2]) for r, o in zip(res, ora))
+        # device-resident fused call (sync and stream-ordered) incl. matching of consecutive pairs
+        win = int(rng.choice([30, 100, 100, 400, 4096]))
+        ratio = float(rng.choice([0.9, 0.9, 0.6, 0.75, 1.0]))
+        ori = bool(rng.integers(0, 2))
+        if B >= 2:
+            d_img = torch.from_numpy(fr).cuda()
+            first = np.arange(0, B - 1, 2, dtype=np.int32)
+            npairs = len(first)
+            sets = []
+            for use_async in range(2):
+                o = dict(k=torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda"), d=torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda"),
+                         n=torch.zeros(B, dtype=torch.int32, device="cuda"), m=torch.zeros(npairs * cap, dtype=torch.int32, device="cuda"),
+                         nm=torch.zeros(npairs, dtype=torch.int32, device="cuda"), st=torch.zeros(npairs * 3, dtype=torch.int32, device="cuda"))
+                f = e.extract_match_batch_device_async if use_async else e.extract_match_batch_device
+                f(d_img, B, w, h, w, w * h, o["k"], o["d"], o["n"], first, first + 1, (0, w, 0, h), o["m"], o["nm"], o["st"], win, ratio, ori, cap)
+                sets.append(o)
+            e.wait()
+            for o in sets:
+                n = o["n"].cpu().numpy()
+                kk = o["k"].cpu().numpy().view(KP).reshape(B, cap)
+                dd = o["d"].cpu().numpy().reshape(B, cap, 32)
+                mm = o["m"].cpu().numpy().reshape(npairs, cap)
+                nm = o["nm"].cpu().numpy()
+                st = o["st"].cpu().numpy().reshape(npairs, 3)
+                for f_ in range(B):
+                    ok &= n[f_] == len(ora[f_][1]) and same(kk[f_, :n[f_]], dd[f_, :n[f_]], ora[f_][1], ora[f_][2])
+                for p in range(npairs):
+                    a, b = ora[2 * p], ora[2 * p + 1]
+                    onm, om12, ost = O.match_init(a[1], a[2], b[1], b[2], (0, w, 0, h), win, ratio, ori)
+                    ok &= nm[p] == onm and np.array_equal(mm[p, :len(om12)], om12) and st[p].tolist() == ost.tolist()
+        nk = [len(o[1]) for o in ora]
+        print(tag, "win=%d ratio=%.2f ori=%d keypoints=%d..%d ->" % (win, ratio, ori, min(nk), max(nk)), "ok" if ok else "MISMATCH", flush=True)
+        bad += not ok
+        e.close()
 print("FUZZ %s: %d trials, %d skipped (too small), %d mismatching, %.0f s" % ("OK" if bad == 0 else "FAILED", trials, skipped, bad, time.time() - t_start))
 sys.exit(1 if bad else 0)
