@@ -330,6 +330,106 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
                   const orbx_keypoint* k2, int n2, const int32_t* matches12, const uint8_t* matches_inliers, float th2,
                   int32_t* n_good, uint8_t* tri_good, float* p3d, float* parallax);
 
+/* ---- behind the matcher: the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ---------- */
+/* For each pair: mvMatches12 (:24-33), then for every iteration `it` the 8-point hypotheses of the loops FindHomography
+ * (:169-211) and FindFundamental (:213-265) on the caller's mvSets[it], scored with CheckHomography / CheckFundamental,
+ * the first maximum of each loop (`currentScore > score`, score starting at 0), SH, SF, RH = SH / (SH + SF) (:89-90), the
+ * inlier counts nH / nF (:95-100) and the model choice RH > 0.50 (:111).  The decomposition of the chosen model and
+ * ReconstructHF (:440-566) are not part of this call: orbx_check_rt is their CheckRT.
+ *
+ * The solvers are restated [from-knowledge] from OpenCV (the reference calls cv::findHomography(src, dst, 0) and
+ * cv::findFundamentalMat(src, dst, FM_8POINT)), in f64, then Converter::toMatrix3f (f32); H12 is Eigen's 3x3 inverse() in
+ * f32.  PARITY UNPINNED, like every OpenCV-facing stage, and with these documented deviations:
+ *  - findHomography's Levenberg-Marquardt refinement of the closed form is left out;
+ *  - the 9x9 eigenproblems use a fixed-sweep cyclic Jacobi (not OpenCV's eigen), F's rank-2 step removes the component along
+ *    the smallest right singular vector of the 3x3 (same matrix as OpenCV's SVD step, other operations);
+ *  - a degenerate sample (OpenCV returns an empty Mat and the reference then reads it in toMatrix3f: UB) gets score 0 and is
+ *    never kept; so is a hypothesis with a non-finite entry;
+ *  - Initialize as committed upstream spawns FindHomographyCV / FindFundamentalCV (OpenCV's own RANSAC and RNG, which no
+ *    library can reproduce) and leaves the mvSets it draws unused; this call runs the 8-point loops over mvSets that the same
+ *    file keeps (FindHomography / FindFundamental), as ORB-SLAM does.
+ * The sets come from the caller: the library reads no RNG state (the Python package's sample_sets restates the draw of
+ * :50-63 for a given rand()). */
+typedef struct orbx_hf_result {
+  int32_t status;                /* 0, or a bitmask of ORBX_INIT_* reasons; the other fields are written either way */
+  int32_t model;                 /* 0 = H (RH > 0.50), 1 = F; -1 when SH + SF == 0 */
+  int32_t n_matches;             /* N = |mvMatches12| */
+  int32_t best_it_h, best_it_f;  /* the iteration each loop kept, -1 if no score was > 0 */
+  int32_t n_inliers_h, n_inliers_f;
+  int32_t reserved;
+  float score_h, score_f, rh;    /* SH, SF, RH (0 when SH + SF == 0) */
+  float H21[9], H12[9], F21[9];  /* the kept hypotheses, row-major (zeros when none was kept) */
+} orbx_hf_result;
+
+#define ORBX_INIT_TOO_FEW_MATCHES 1 /* N < 8: the sampler of :50-63 cannot run (rand() % 0 upstream) */
+#define ORBX_INIT_BAD_SETS 2        /* a set index outside [0, N) or repeated within its set: that hypothesis is skipped */
+#define ORBX_INIT_NO_SCORE 4        /* SH + SF == 0 (:89, Initialize returns false) */
+#define ORBX_INIT_BAD_MATCHES 128   /* a matches12 entry >= n2, or a frame's keypoint count outside [0, capacity]: nothing is
+                                     * scored for the pair */
+
+#define ORBX_INIT_AMBIGUOUS 8         /* secondBestGood > 0.7 * bestGood (:509) */
+#define ORBX_INIT_LOW_PARALLAX 16      /* the best solution's parallax < min_parallax (:515) */
+#define ORBX_INIT_FEW_TRIANGULATED 32  /* bestGood < min_triangulated (:521) */
+#define ORBX_INIT_FEW_INLIERS 64       /* bestGood < 0.9 * the inliers of the chosen model (:527) */
+
+/* ---- Initializer::Initialize end to end (Initialization/Initializer.cpp:19-125): the stage above, then ReconstructHF
+ * (:440-566): the chosen model decomposed -- F: E = K^T F K (Eigen, f32) and cv::decomposeEssentialMat, four candidates in the
+ * order of :458-466; H: cv::decomposeHomographyMat (the analytical Malis-Vargas decomposition, 1 or 4 solutions in OpenCV's
+ * order) --, CheckRT of every candidate (orbx_check_rt's kernel, th2 = 4 sigma^2), the best / second-best choice (:490-507) and
+ * the four acceptance rules (:509-545).  Initialize's `false` is status != 0 here, with ORBX_OK.  [from-knowledge], PARITY
+ * UNPINNED; further deviations: both decompositions compute their SVD / eigen-decompositions in f64 with a fixed-sweep Jacobi
+ * (decomposeEssentialMat runs on the CV_32F E upstream), so the sign of t and hence the order among the candidates may differ
+ * from OpenCV's; square roots of rounding-negative minors in the homography decomposition are taken at 0 (OpenCV yields NaNs);
+ * the reconstruction runs only behind a status-0 model stage (otherwise the reference has returned or is UB). */
+typedef struct orbx_init_result {
+  int32_t status;                /* 0 = reconstructed; else a bitmask of ORBX_INIT_* reasons; every field is written either way */
+  int32_t model;                 /* 0 = H (RH > 0.50), 1 = F, -1 when SH + SF == 0 */
+  int32_t n_matches;             /* N = |mvMatches12| */
+  int32_t best_it_h, best_it_f;  /* the iteration each RANSAC loop kept (-1 if no score > 0) */
+  int32_t n_inliers_h, n_inliers_f;
+  int32_t n_solutions, best_solution, best_good, second_good;  /* ReconstructHF's candidates and CheckRT counts (-1: none) */
+  int32_t reserved;
+  float score_h, score_f, rh, parallax;  /* parallax of the best solution in degrees (-1 if none) */
+  float R21[9], t21[3];          /* the chosen (R, t), row-major (zeros if none) */
+  float H21[9], F21[9];          /* the kept hypotheses */
+} orbx_init_result;
+
+/* Batched, device-resident, stream-ordered on the context stream (the call returns once everything is queued; results are
+ * valid after a device synchronisation, hipDeviceSynchronize): the layout of orbx_find_models_batch_device, K row-major 3x3 (host, f32),
+ * min_parallax in degrees, min_triangulated (the reference passes 1 and 50, :103-111).  Outputs: d_res [n_pairs];
+ * d_p3d (nullable) float [n_pairs][capacity][3] = vP3D, d_triangulated (nullable) uint8 [n_pairs][capacity] = vbTriangulated
+ * of the best solution (zeros when there is none; entries beyond the pair's first-frame count are 0). */
+int orbx_initialize_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
+                                 const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
+                                 int n_iter, const int32_t* d_sets, const float* K, float sigma, float min_parallax,
+                                 int min_triangulated, orbx_init_result* d_res, float* d_p3d, uint8_t* d_triangulated);
+/* The same for one pair in host memory (what Tracking::Initialize holds), run through the batched path; p3d [n1][3] and
+ * triangulated [n1] nullable.  Synchronous. */
+int orbx_initialize(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
+                    int n_iter, const int32_t* sets, const float* K, float sigma, float min_parallax, int min_triangulated,
+                    orbx_init_result* res, float* p3d, uint8_t* triangulated);
+
+/* Batched, device-resident, stream-ordered on the context stream (results valid after a device synchronisation, hipDeviceSynchronize): pair p = frame
+ * h_first[p] vs h_second[p] (host arrays, in [0, n_frames)) of the extract / undistort layout (d_kps_un [frames][capacity],
+ * d_n [frames]) and the matcher's d_matches12 [n_pairs][capacity] (entries beyond d_n[h_first[p]] are not read).
+ * d_sets int32 [n_pairs][n_iter][8] = mvSets (indices into mvMatches12).  Device data is checked before it is read: bad
+ * values are reported in status, never followed.  Outputs: d_res [n_pairs]; d_inliers (nullable) uint8 [n_pairs][2][capacity]
+ * = vbMatchesInliersH, then vbMatchesInliersF, of the kept hypotheses (first N entries; zeros when none was kept); d_models
+ * (nullable) float [3][n_pairs][n_iter][9] = every hypothesis's H21, H12, F21; d_scores (nullable) float [2][n_pairs][n_iter]
+ * = every hypothesis's CheckHomography / CheckFundamental score (that of a degenerate or skipped hypothesis is unspecified).
+ * ORBX_E_BADARG: null pointers, n_pairs / n_frames / n_iter <= 0, capacity outside [1, 2^20), a pair index outside
+ * [0, n_frames); nothing is launched then. */
+int orbx_find_models_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
+                                  const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
+                                  int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res, uint8_t* d_inliers,
+                                  float* d_models, float* d_scores);
+/* The same for one pair in host memory (k1 = mvKeys1, k2 = mvKeys2, matches12 = the n1 entries of vnMatches12, sets
+ * [n_iter][8]), run through the batched path; inliers [2][n1], models [3][n_iter][9] and scores [2][n_iter] nullable.
+ * Synchronous. */
+int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
+                     int n_iter, const int32_t* sets, float sigma, orbx_hf_result* res, uint8_t* inliers, float* models,
+                     float* scores);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

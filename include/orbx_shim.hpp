@@ -23,6 +23,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -370,6 +371,113 @@ class ORBmatcher {
   float mfNNratio;
   bool mbCheckOrientation;
   ORBextractor* ext_;
+};
+
+// ---- Initializer (Initialization/Initializer.hpp / .cpp:9-125) ------------------------------------------------------------
+// PoseT of the reference: a POD stand-in for its Eigen::Affine3d (4x4, row-major); vP3D: cv::Point3f with OpenCV, Point3T without.
+struct PoseT {
+  double m[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  double& operator()(int r, int c) { return m[r * 4 + c]; }
+  double operator()(int r, int c) const { return m[r * 4 + c]; }
+};
+// (Initialize takes the point type as a template parameter: std::vector<cv::Point3f> with OpenCV, of Point3T without)
+struct Point3T { float x = 0, y = 0, z = 0; };
+inline float frameK(const float (&K)[9], int r, int c) { return K[r * 3 + c]; }
+inline float frameK(const std::vector<float>& K, int r, int c) { return K[r * 3 + c]; }
+template <class MatT>  // the reference's mK: cv::Mat CV_32F (Settings.hpp:28-32)
+auto frameK(const MatT& K, int r, int c) -> decltype((float)K.template at<float>(r, c)) { return K.template at<float>(r, c); }
+
+// The reference's constructor (mK and mvKeysUn of the reference frame, sigma, iterations) and Initialize(currentFrame,
+// vMatches12, Tcw, vP3D, vbTriangulated): mvSets drawn with the host's rand() exactly as :50-63, then orbx_initialize on the
+// device of the frames' extractor (mpORBextractor, as ORBmatcher reads it); the reference's lines under orbx::verbose().
+// Returns false where the reference does (status != 0); argument / HIP errors throw orbx::Error.
+class Initializer {
+ public:
+  template <class FrameT>
+  Initializer(const FrameT& ReferenceFrame, float sigma = 1.0, int iterations = 200)
+      : mvKeys1(ReferenceFrame.mvKeysUn), mSigma(sigma), mMaxIterations(iterations), mpORBextractor(ReferenceFrame.mpORBextractor) {
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) mK[r * 3 + c] = frameK(ReferenceFrame.mK, r, c);
+  }
+
+  template <class FrameT, class Point3>
+  bool Initialize(const FrameT& CurrentFrame, const std::vector<int>& vMatches12, PoseT& Tcw, std::vector<Point3>& vP3D,
+                  std::vector<bool>& vbTriangulated) {
+    const auto& k2 = CurrentFrame.mvKeysUn;
+    ORBextractor* e = CurrentFrame.mpORBextractor ? CurrentFrame.mpORBextractor : mpORBextractor;
+    if (!e) throw orbx::Error(ORBX_E_BADARG, "Initializer: the frames carry no extractor");
+    int N = 0;
+    for (int m : vMatches12) N += m >= 0;
+    // :50-63, with the reference's own rand() calls (an N below 8 draws nothing: rand() % 0 upstream)
+    std::vector<int32_t> sets((size_t)mMaxIterations * 8, 0);
+    if (N >= 8) {
+      std::vector<size_t> vAllIndices;
+      vAllIndices.reserve(N);
+      std::vector<size_t> vAvailableIndices;
+      for (int i = 0; i < N; i++) vAllIndices.push_back(i);
+      for (int it = 0; it < mMaxIterations; it++) {
+        vAvailableIndices = vAllIndices;
+        for (size_t j = 0; j < 8; j++) {
+          int randi = rand() % vAvailableIndices.size();
+          int idx = vAvailableIndices[randi];
+          vAvailableIndices[randi] = vAvailableIndices.back();
+          vAvailableIndices.pop_back();
+          sets[(size_t)it * 8 + j] = idx;
+        }
+      }
+    }
+    orbx_init_result res;
+    std::vector<float> p3d(3 * (mvKeys1.size() ? mvKeys1.size() : 1));
+    std::vector<uint8_t> tri(mvKeys1.size() ? mvKeys1.size() : 1);
+    const int r = orbx_initialize(e->context(), reinterpret_cast<const orbx_keypoint*>(mvKeys1.data()), (int)mvKeys1.size(),
+                                  reinterpret_cast<const orbx_keypoint*>(k2.data()), (int)k2.size(), vMatches12.data(), mMaxIterations,
+                                  sets.data(), mK, mSigma, 1.0f, 50, &res, p3d.data(), tri.data());
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+    if (orbx::verbose() && !(res.status & (ORBX_INIT_TOO_FEW_MATCHES | ORBX_INIT_NO_SCORE | ORBX_INIT_BAD_MATCHES))) {
+      std::cout << "Score of H: " << res.score_h << std::endl;  // :91-92
+      std::cout << "Score of F: " << res.score_f << std::endl;
+      std::cout << "inliers of H: " << res.n_inliers_h << std::endl;  // :101-102
+      std::cout << "inliers of F: " << res.n_inliers_f << std::endl;
+      const int n = res.model == 0 ? res.n_inliers_h : res.n_inliers_f;
+      if (res.status & ORBX_INIT_AMBIGUOUS)
+        std::cout << "Failed: Second best solution = " << res.second_good << " is too close to best solution = " << res.best_good
+                  << std::endl;
+      if (res.status & ORBX_INIT_LOW_PARALLAX)
+        std::cout << "Failed: Parallax = " << res.parallax << " is below the minimum threshold (" << 1 << ")" << std::endl;
+      if (res.status & ORBX_INIT_FEW_TRIANGULATED)
+        std::cout << "Failed: Number of triangulated points = " << res.best_good << " is below the minimum threshold (" << 50 << ")"
+                  << std::endl;
+      if (res.status & ORBX_INIT_FEW_INLIERS)
+        std::cout << "Failed: Number of inliers = " << res.best_good << " is less than 90% of total matches = " << n << std::endl;
+      if (res.status) std::cout << "Failed: Failed to recover pose and triangulate points." << std::endl;
+    }
+    if (res.status) {  // :119-121: after a failed ReconstructHF
+      if (orbx::verbose() && (res.status & (ORBX_INIT_AMBIGUOUS | ORBX_INIT_LOW_PARALLAX | ORBX_INIT_FEW_TRIANGULATED | ORBX_INIT_FEW_INLIERS)))
+        std::cerr << "Initialization failed!" << std::endl;
+      return false;
+    }
+    Tcw = PoseT();  // :557-563: linear() = R, translation() = t
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Tcw(i, j) = res.R21[i * 3 + j];
+      Tcw(i, 3) = res.t21[i];
+    }
+    vP3D.resize(mvKeys1.size());
+    vbTriangulated.resize(mvKeys1.size());
+    for (size_t i = 0; i < mvKeys1.size(); i++) {
+      vP3D[i].x = p3d[3 * i];
+      vP3D[i].y = p3d[3 * i + 1];
+      vP3D[i].z = p3d[3 * i + 2];
+      vbTriangulated[i] = tri[i] != 0;
+    }
+    return true;
+  }
+
+ private:
+  std::vector<KeyPointT> mvKeys1;
+  float mK[9];
+  float mSigma;
+  int mMaxIterations;
+  ORBextractor* mpORBextractor;
 };
 
 }  // namespace ORB_SLAM_Tracking

@@ -20,6 +20,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
+           "HFResult", "HF_RESULT_DTYPE", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -49,6 +50,68 @@ class _Bounds(ctypes.Structure):
 
 class _Camera(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
+
+
+class HFResult(ctypes.Structure):
+    """orbx_hf_result: what Initializer::Initialize knows after its two RANSAC loops (Initializer.cpp:78-111)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h",
+                                              "n_inliers_f", "reserved")] + \
+               [(n, ctypes.c_float) for n in ("score_h", "score_f", "rh")] + \
+               [(n, ctypes.c_float * 9) for n in ("H21", "H12", "F21")]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        for n in ("H21", "H12", "F21"):
+            d[n] = np.array(d[n][:], np.float32).reshape(3, 3)
+        return d
+
+
+assert ctypes.sizeof(HFResult) == 4 * (8 + 3 + 27)
+HF_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h",
+                                                 "n_inliers_f", "reserved")] +
+                           [(n, "<f4") for n in ("score_h", "score_f", "rh")] + [(n, "<f4", (3, 3)) for n in ("H21", "H12", "F21")])
+assert HF_RESULT_DTYPE.itemsize == ctypes.sizeof(HFResult)
+INIT_TOO_FEW_MATCHES, INIT_BAD_SETS, INIT_NO_SCORE, INIT_BAD_MATCHES = 1, 2, 4, 128
+INIT_AMBIGUOUS, INIT_LOW_PARALLAX, INIT_FEW_TRIANGULATED, INIT_FEW_INLIERS = 8, 16, 32, 64
+_INIT_INTS = ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h", "n_inliers_f", "n_solutions", "best_solution",
+              "best_good", "second_good", "reserved")
+
+
+class InitResult(ctypes.Structure):
+    """orbx_init_result: Initializer::Initialize's outcome (status 0 = reconstructed) and the chosen (R21, t21)."""
+    _fields_ = [(n, ctypes.c_int32) for n in _INIT_INTS] + [(n, ctypes.c_float) for n in ("score_h", "score_f", "rh", "parallax")] + \
+               [("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3), ("H21", ctypes.c_float * 9), ("F21", ctypes.c_float * 9)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        for n in ("R21", "H21", "F21"):
+            d[n] = np.array(d[n][:], np.float32).reshape(3, 3)
+        d["t21"] = np.array(d["t21"][:], np.float32)
+        return d
+
+
+INIT_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _INIT_INTS] + [(n, "<f4") for n in ("score_h", "score_f", "rh", "parallax")] +
+                             [("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3))])
+assert INIT_RESULT_DTYPE.itemsize == ctypes.sizeof(InitResult) == 184
+
+
+def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
+    """mvSets as Initializer::Initialize draws them (Initializer.cpp:50-63): per iteration 8 distinct indices into
+    mvMatches12, each `rand() % available` with swap-with-last removal.  `rand` is a callable returning the host's next rand()
+    value (tests pass glibc's through ctypes), so the caller's random stream advances exactly as the reference's would.
+    n_matches < 8 raises ValueError (the reference computes rand() % 0 there)."""
+    n_matches, n_iter = int(n_matches), int(n_iter)
+    if n_matches < 8:
+        raise ValueError("sample_sets needs at least 8 matches (rand() %% 0 upstream), got %d" % n_matches)
+    out = np.zeros((n_iter, 8), np.int32)
+    for it in range(n_iter):
+        avail = list(range(n_matches))
+        for j in range(8):
+            randi = int(rand()) % len(avail)
+            out[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return out
 
 
 class _Stats(ctypes.Structure):
@@ -147,6 +210,10 @@ def lib() -> ctypes.CDLL:
     L.orbx_check_homography.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp]
     L.orbx_check_fundamental.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp]
     L.orbx_check_rt.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, f32, vp, vp, vp, vp]
+    L.orbx_find_models_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp]
+    L.orbx_find_models.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, f32, ctypes.POINTER(HFResult), vp, vp, vp]
+    L.orbx_initialize_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, f32, f32, i32, vp, vp, vp]
+    L.orbx_initialize.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, f32, f32, i32, ctypes.POINTER(InitResult), vp, vp]
     L.orbx_multi_create.argtypes = [ctypes.POINTER(_Params), i32, vp, i32, i32, i32, ctypes.POINTER(vp)]
     L.orbx_multi_destroy.argtypes = [vp]
     L.orbx_multi_destroy.restype = None
@@ -616,6 +683,127 @@ class ORBextractor:
         self._check(self._L.orbx_check_rt(self._h, nm, _ptr(R21), _ptr(t21), _ptr(K), _ptr(k1), len(k1), _ptr(k2), len(k2), _ptr(m12),
                                           _ptr(inl), float(th2), _ptr(ngood), _ptr(good), _ptr(p3d), _ptr(par)), "orbx_check_rt")
         return ngood[:nm], good[:nm, :len(k1)].astype(bool), p3d[:nm, :len(k1)], par[:nm]
+
+    # -- the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ---------
+    def find_models(self, keys1, keys2, matches12, sets, sigma: float = 1.0, debug: bool = False):
+        """One pair from host memory: mvKeys1 / mvKeys2 (mvKeysUn), vnMatches12 (one entry per keypoint of frame 1), mvSets
+        [n_iter, 8] (sample_sets).  Returns (HFResult, inliers [2, N] bool: the kept H's, then F's, vbMatchesInliers); with
+        debug=True also every hypothesis (models [3, n_iter, 3, 3] = H21, H12, F21) and its score (scores [2, n_iter])."""
+        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        sets = np.ascontiguousarray(sets, np.int32)
+        if len(m12) != len(k1):
+            raise OrbxError(E_BADARG, "matches12 must have one entry per keypoint of frame 1")
+        if sets.ndim != 2 or sets.shape[1] != 8:
+            raise OrbxError(E_BADARG, "sets must be [n_iter, 8]")
+        n_iter = len(sets)
+        res = HFResult()
+        inl = np.zeros((2, max(len(k1), 1)), np.uint8)
+        models = np.zeros((3, max(n_iter, 1), 3, 3), np.float32) if debug else None
+        scores = np.zeros((2, max(n_iter, 1)), np.float32) if debug else None
+        self._check(self._L.orbx_find_models(self._h, _ptr(k1), len(k1), _ptr(k2), len(k2), _ptr(m12), n_iter, _ptr(sets),
+                                             float(sigma), ctypes.byref(res), _ptr(inl), _ptr(models), _ptr(scores)),
+                    "orbx_find_models")
+        inliers = inl[:, :res.n_matches].astype(bool)
+        if debug:
+            return res, inliers, models, scores
+        return res, inliers
+
+    def find_models_batch_device(self, n_frames: int, first: np.ndarray, second: np.ndarray, d_kps_un, d_n, d_matches12, d_sets,
+                                 d_res, d_inliers=None, d_models=None, d_scores=None, sigma: float = 1.0,
+                                 capacity: Optional[int] = None, n_iter: Optional[int] = None) -> None:
+        """Batched and device-resident (device pointers or torch tensors): pair p = frame first[p] vs second[p] of the
+        extract / undistort layout; d_sets int32 [n_pairs, n_iter, 8]; d_res [n_pairs] HF_RESULT_DTYPE-sized records (152 bytes);
+        d_inliers uint8 [n_pairs, 2, capacity], d_models float32 [3, n_pairs, n_iter, 9], d_scores float32 [2, n_pairs, n_iter]
+        are optional.  n_iter: from d_sets' shape when it is a [n_pairs, n_iter, 8] tensor, else required.  Stream-ordered on the
+        context's stream: the outputs are valid after a device synchronisation (torch.cuda.synchronize())."""
+        first = np.ascontiguousarray(first, np.int32)
+        second = np.ascontiguousarray(second, np.int32)
+        cap = int(capacity or self.capacity)
+        P = len(first)
+        if len(second) != P:
+            raise OrbxError(E_BADARG, "first and second must have the same length")
+        n_iter = self._n_iter(d_sets, P, n_iter)
+        n_frames = int(n_frames)
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        _need("matches12", d_matches12, P * cap * 4)
+        _need("the sets", d_sets, P * n_iter * 32)
+        _need("the result array", d_res, P * HF_RESULT_DTYPE.itemsize)
+        if d_inliers is not None:
+            _need("the inlier array", d_inliers, P * 2 * cap)
+        if d_models is not None:
+            _need("the model array", d_models, 3 * P * n_iter * 36)
+        if d_scores is not None:
+            _need("the score array", d_scores, 2 * P * n_iter * 4)
+        self._order_torch(d_kps_un, d_n, d_matches12, d_sets, d_res, d_inliers, d_models, d_scores)
+        self._check(self._L.orbx_find_models_batch_device(self._h, n_frames, P, _ptr(first), _ptr(second), _ptr(d_kps_un), _ptr(d_n), cap,
+                                                          _ptr(d_matches12), n_iter, _ptr(d_sets), float(sigma), _ptr(d_res),
+                                                          _ptr(d_inliers), _ptr(d_models), _ptr(d_scores)),
+                    "orbx_find_models_batch_device")
+
+    @staticmethod
+    def _n_iter(d_sets, n_pairs: int, n_iter: Optional[int]) -> int:
+        shape = getattr(d_sets, "shape", None)
+        if shape is not None and len(shape) == 3:
+            if int(shape[0]) != n_pairs or int(shape[2]) != 8 or (n_iter is not None and int(n_iter) != int(shape[1])):
+                raise OrbxError(E_BADARG, "d_sets must be [n_pairs, n_iter, 8]")
+            return int(shape[1])
+        if n_iter is None:
+            raise OrbxError(E_BADARG, "n_iter is required when d_sets is not a [n_pairs, n_iter, 8] tensor")
+        return int(n_iter)
+
+    # -- Initializer::Initialize end to end (Initialization/Initializer.cpp:19-125) ------------------
+    def initialize(self, keys1, keys2, matches12, sets, K, sigma: float = 1.0, min_parallax: float = 1.0, min_triangulated: int = 50):
+        """One pair from host memory: mvKeys1 / mvKeys2 (mvKeysUn), vnMatches12, mvSets [n_iter, 8] (sample_sets), K 3x3.  Returns
+        (InitResult, vP3D [n1, 3] float32, vbTriangulated [n1] bool); result.status == 0 is Initialize's `true`."""
+        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        sets = np.ascontiguousarray(sets, np.int32)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        if len(m12) != len(k1):
+            raise OrbxError(E_BADARG, "matches12 must have one entry per keypoint of frame 1")
+        if sets.ndim != 2 or sets.shape[1] != 8:
+            raise OrbxError(E_BADARG, "sets must be [n_iter, 8]")
+        res = InitResult()
+        p3d = np.zeros((max(len(k1), 1), 3), np.float32)
+        tri = np.zeros(max(len(k1), 1), np.uint8)
+        self._check(self._L.orbx_initialize(self._h, _ptr(k1), len(k1), _ptr(k2), len(k2), _ptr(m12), len(sets), _ptr(sets), _ptr(Kf),
+                                            float(sigma), float(min_parallax), int(min_triangulated), ctypes.byref(res), _ptr(p3d),
+                                            _ptr(tri)), "orbx_initialize")
+        return res, p3d[:len(k1)], tri[:len(k1)].astype(bool)
+
+    def initialize_batch_device(self, n_frames: int, first: np.ndarray, second: np.ndarray, d_kps_un, d_n, d_matches12, d_sets, K,
+                                d_res, d_p3d=None, d_triangulated=None, sigma: float = 1.0, min_parallax: float = 1.0,
+                                min_triangulated: int = 50, capacity: Optional[int] = None, n_iter: Optional[int] = None) -> None:
+        """Batched and device-resident (device pointers or torch tensors), the layout of find_models_batch_device; d_res
+        [n_pairs] INIT_RESULT_DTYPE records (184 bytes), d_p3d float32 [n_pairs, capacity, 3] and d_triangulated uint8
+        [n_pairs, capacity] optional.  Stream-ordered: the outputs are valid after a device synchronisation."""
+        first = np.ascontiguousarray(first, np.int32)
+        second = np.ascontiguousarray(second, np.int32)
+        cap = int(capacity or self.capacity)
+        P = len(first)
+        if len(second) != P:
+            raise OrbxError(E_BADARG, "first and second must have the same length")
+        n_iter = self._n_iter(d_sets, P, n_iter)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        n_frames = int(n_frames)
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        _need("matches12", d_matches12, P * cap * 4)
+        _need("the sets", d_sets, P * n_iter * 32)
+        _need("the result array", d_res, P * INIT_RESULT_DTYPE.itemsize)
+        if d_p3d is not None:
+            _need("the point array", d_p3d, P * cap * 12)
+        if d_triangulated is not None:
+            _need("the triangulated array", d_triangulated, P * cap)
+        self._order_torch(d_kps_un, d_n, d_matches12, d_sets, d_res, d_p3d, d_triangulated)
+        self._check(self._L.orbx_initialize_batch_device(self._h, n_frames, P, _ptr(first), _ptr(second), _ptr(d_kps_un), _ptr(d_n), cap,
+                                                         _ptr(d_matches12), n_iter, _ptr(d_sets), _ptr(Kf), float(sigma),
+                                                         float(min_parallax), int(min_triangulated), _ptr(d_res), _ptr(d_p3d),
+                                                         _ptr(d_triangulated)), "orbx_initialize_batch_device")
 
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:

@@ -59,6 +59,10 @@ hipError_t launch_to_gray(hipStream_t st, int nFrames, const uint8_t* src, long 
 hipError_t launch_check_model(hipStream_t st, int nModels, const ScoreArgs& a);
 hipError_t launch_copy_out(hipStream_t st, const CopyOut& c, int nseg, int maxRows);
 hipError_t launch_check_rt(hipStream_t st, int nModels, const CheckRtArgs& a);
+hipError_t launch_init_prep(hipStream_t st, const InitArgs& a);
+hipError_t launch_init_solve(hipStream_t st, const InitArgs& a);
+hipError_t launch_init_select(hipStream_t st, const InitArgs& a);
+hipError_t launch_init_finish(hipStream_t st, const InitArgs& a);
 hipError_t launch_debug_sincos(hipStream_t st, const float* angle, int n, float* c, float* s, int libmFloat);
 hipError_t launch_undistort(hipStream_t st, int nFrames, const orbx_keypoint* in, const int* nkp, int capacity, const CamD& c,
                             orbx_keypoint* out);
@@ -163,6 +167,7 @@ struct orbx_ctx {
     int32_t* dNmatches = nullptr;
     int32_t* dStats = nullptr;
   } late[2];
+  std::vector<int32_t> initPairs;  // the pair list of the last orbx_find_models* call (source of its copy)
   std::vector<int32_t> lastPairs;  // the pair list dPairs holds (first[], second[]): an unchanged list is not copied again
   uint8_t* dIn = nullptr;
   size_t inBytes = 0;
@@ -197,6 +202,10 @@ struct orbx_ctx {
   size_t mCap = 0;
   uint8_t* dScore = nullptr;  // staging of orbx_check_homography / _fundamental
   size_t scoreBytes = 0;
+  uint8_t* dInit = nullptr;   // arena of orbx_find_models* / orbx_initialize* (grown on demand)
+  size_t initBytes = 0;
+  int32_t* dInitPairs = nullptr;  // their pair list (first[], second[]) as ctx->initPairs holds it
+  size_t initPairsCap = 0;
   uint8_t* dColor = nullptr;  // staging of orbx_to_gray (host API): colour frame followed by its gray image
   size_t colorBytes = 0;
 
@@ -1554,7 +1563,7 @@ void orbx_destroy(orbx_ctx* ctx) {
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
   if (ctx->st2) (void)hipStreamSynchronize(ctx->st2);
   freeAll(ctx);
-  void* dev[] = {ctx->dMatchScratch, ctx->dMatchDiag, ctx->dPairs, ctx->dMblk, ctx->dMi, ctx->dColor, ctx->dScore};
+  void* dev[] = {ctx->dMatchScratch, ctx->dMatchDiag, ctx->dPairs, ctx->dMblk, ctx->dMi, ctx->dColor, ctx->dScore, ctx->dInit, ctx->dInitPairs};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (ctx->hMblk) (void)hipHostFree(ctx->hMblk);
@@ -2442,6 +2451,264 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
   }
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
+}
+
+// ---- the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ----------------------------------
+namespace {
+size_t al256(size_t v) { return (v + 255) / 256 * 256; }
+// bytes of the batched stage's work area
+size_t findModelsWorkBytes(int nPairs, int nIter, int cap) {
+  const size_t P = nPairs, H = (size_t)nPairs * nIter, C = cap;
+  return 3 * al256(P * 4) + 2 * al256(P * C * 4) + 3 * al256(H * 36) + al256(2 * H) + 2 * al256(H * 4) + 2 * al256(H * C) +
+         al256(P * sizeof(orbx_hf_result)) + al256(P * 2 * C);
+}
+// the reconstruction's part: candidates, counts, CheckRT inputs and outputs
+size_t reconWorkBytes(int nPairs, int cap) {
+  const size_t P = nPairs, C = cap, M = 4 * P;
+  return al256(M * 36) + al256(M * 12) + 2 * al256(P * 4) + al256(P * C * 16) + al256(P * C * 4) + al256(M * 4) * 2 +
+         al256(M * C) + al256(M * C * 12) + al256(M * C * 4);
+}
+// the pair list through the context's own copy; a changed list waits for the work that may still read the previous one
+int uploadInitPairs(orbx_ctx* ctx, int n_pairs, const int32_t* h_first, const int32_t* h_second) {
+  std::vector<int32_t>& lp = ctx->initPairs;
+  if ((int)lp.size() == 2 * n_pairs && std::memcmp(lp.data(), h_first, 4 * (size_t)n_pairs) == 0 &&
+      std::memcmp(lp.data() + n_pairs, h_second, 4 * (size_t)n_pairs) == 0)
+    return ORBX_OK;
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  if (ctx->initPairsCap < (size_t)2 * n_pairs) {
+    if (ctx->dInitPairs) (void)hipFree(ctx->dInitPairs);
+    ctx->dInitPairs = nullptr; ctx->initPairsCap = 0;
+    HIPCHK(hipMalloc((void**)&ctx->dInitPairs, (size_t)8 * n_pairs));
+    ctx->initPairsCap = (size_t)2 * n_pairs;
+  }
+  lp.assign(h_first, h_first + n_pairs);
+  lp.insert(lp.end(), h_second, h_second + n_pairs);
+  if (hipMemcpyAsync(ctx->dInitPairs, lp.data(), (size_t)8 * n_pairs, hipMemcpyHostToDevice, ctx->st) != hipSuccess) {
+    lp.clear();
+    ctx->err = "hipMemcpyAsync (initializer pair list)";
+    return ORBX_E_HIP;
+  }
+  return ORBX_OK;
+}
+struct ReconParams {
+  const float* K;
+  float minParallax;
+  int minTriangulated;
+  orbx_init_result* res;
+  float* p3d;
+  uint8_t* tri;
+};
+int ensureInitArena(orbx_ctx* ctx, size_t need) {
+  if (need <= ctx->initBytes) return ORBX_OK;
+  if (ctx->dInit) {
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    (void)hipFree(ctx->dInit);
+  }
+  ctx->dInit = nullptr; ctx->initBytes = 0;
+  HIPCHK(hipMalloc((void**)&ctx->dInit, need));
+  ctx->initBytes = need;
+  return ORBX_OK;
+}
+// prep -> solve -> score H -> score F -> select, all on the context stream; `work` holds findModelsWorkBytes; d_models /
+// d_scores (nullable) take the hypotheses and their scores in place of the work area's arrays
+int findModels(orbx_ctx* ctx, uint8_t* work, int n_pairs, const int32_t* h_first, const int32_t* h_second, const orbx_keypoint* d_kps,
+               const int32_t* d_n, int cap, const int32_t* d_m12, int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res,
+               uint8_t* d_inliers, float* d_models, float* d_scores, const ReconParams* rc) {
+  hipStream_t st = ctx->st;
+  const size_t P = n_pairs, H = (size_t)n_pairs * n_iter, C = cap;
+  int r = uploadInitPairs(ctx, n_pairs, h_first, h_second);
+  if (r != ORBX_OK) return r;
+  uint8_t* p = work;
+  InitArgs a{};
+  int32_t* frames = ctx->dInitPairs;
+  a.N = (int32_t*)p; p += al256(P * 4);
+  a.scoreN = (int32_t*)p; p += al256(P * 4);
+  a.pstat = (int32_t*)p; p += al256(P * 4);
+  a.first = (int32_t*)p; p += al256(P * C * 4);
+  a.second = (int32_t*)p; p += al256(P * C * 4);
+  float* models = (float*)p; p += 3 * al256(H * 36);
+  if (d_models) models = d_models;
+  a.H21 = models; a.H12 = models + H * 9; a.F21 = models + 2 * H * 9;
+  a.flags = p; p += al256(2 * H);
+  float* scores = (float*)p; p += 2 * al256(H * 4);
+  if (d_scores) scores = d_scores;
+  a.scoresH = scores; a.scoresF = scores + H;
+  uint8_t* inlH = p; p += al256(H * C);
+  uint8_t* inlF = p; p += al256(H * C);
+  a.inlH = inlH; a.inlF = inlF;
+  a.kps = d_kps; a.nKps = d_n; a.m12 = d_m12; a.sets = d_sets; a.frames = frames;
+  a.nPairs = n_pairs; a.nIter = n_iter; a.cap = cap;
+  orbx_hf_result* hf = (orbx_hf_result*)p; p += al256(P * sizeof(orbx_hf_result));
+  uint8_t* inlKept = p; p += al256(P * 2 * C);
+  a.res = d_res ? d_res : hf;
+  a.inlOut = d_inliers ? d_inliers : inlKept;
+  CheckRtArgs c{};
+  if (rc) {
+    a.reconstruct = 1;
+    for (int i = 0; i < 9; i++) a.K[i] = rc->K[i];
+    a.minParallax = rc->minParallax; a.minTriangulated = rc->minTriangulated;
+    const size_t M = 4 * P;
+    a.R4 = (float*)p; p += al256(M * 36);
+    a.t4 = (float*)p; p += al256(M * 12);
+    a.nSol = (int32_t*)p; p += al256(P * 4);
+    a.nInl = (int32_t*)p; p += al256(P * 4);
+    a.pts = (float*)p; p += al256(P * C * 16);
+    a.book = (int32_t*)p; p += al256(P * C * 4);
+    int32_t* nGood = (int32_t*)p; p += al256(M * 4);
+    float* par = (float*)p; p += al256(M * 4);
+    uint8_t* good = p; p += al256(M * C);
+    float* p3d = (float*)p; p += al256(M * C * 12);
+    float* cosBuf = (float*)p;
+    a.nGood = nGood; a.parallax = par; a.good = good; a.p3d4 = p3d;
+    a.ires = rc->res; a.p3dOut = rc->p3d; a.triOut = rc->tri;
+    c.R21 = a.R4; c.t21 = a.t4; c.pts = a.pts; c.book = a.book;
+    for (int i = 0; i < 9; i++) c.K[i] = rc->K[i];
+    c.th2 = (float)(4.0 * (double)(sigma * sigma));  // `4.0 * mSigma2` (:499), mSigma2 = sigma * sigma (f32)
+    c.nInl = 0; c.n1 = cap;
+    c.good = good; c.p3d = p3d; c.cosBuf = cosBuf; c.nGood = nGood; c.parallax = par;
+    c.pairNInl = a.nInl; c.pairNSol = a.nSol; c.perPair = 4; c.stride = cap;
+  }
+  HIPCHK(launch_init_prep(st, a));
+  HIPCHK(launch_init_solve(st, a));
+  ScoreArgs s{};
+  s.k1 = d_kps; s.k2 = d_kps; s.first = a.first; s.second = a.second;
+  s.invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
+  s.pairN = a.scoreN; s.frames = frames; s.perPair = n_iter; s.stride = cap; s.nPairs = n_pairs;
+  s.kind = 0; s.M21 = a.H21; s.M12 = a.H12; s.scores = scores; s.inliers = inlH;
+  HIPCHK(launch_check_model(st, (int)H, s));
+  s.kind = 1; s.M21 = a.F21; s.M12 = nullptr; s.scores = scores + H; s.inliers = inlF;
+  HIPCHK(launch_check_model(st, (int)H, s));
+  HIPCHK(launch_init_select(st, a));
+  if (rc) {
+    HIPCHK(launch_check_rt(st, 4 * n_pairs, c));
+    HIPCHK(launch_init_finish(st, a));
+  }
+  return ORBX_OK;
+}
+int checkBatchArgs(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second, const void* d_kps_un,
+                   const void* d_n, int capacity, const void* d_matches12, int n_iter, const void* d_sets, float sigma, const void* d_res) {
+  if (!ctx || n_frames <= 0 || n_pairs <= 0 || !h_first || !h_second || !d_kps_un || !d_n || !d_matches12 || !d_sets || !d_res ||
+      n_iter <= 0 || capacity < 1 || capacity >= (1 << 20) || !(sigma > 0.f))
+    return ORBX_E_BADARG;
+  if ((long long)n_pairs * n_iter >= (1LL << 26)) return ORBX_E_BADARG;
+  for (int p = 0; p < n_pairs; p++)
+    if (h_first[p] < 0 || h_first[p] >= n_frames || h_second[p] < 0 || h_second[p] >= n_frames) {
+      ctx->err = "pair index outside [0, n_frames)";
+      return ORBX_E_BADARG;
+    }
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbx_find_models_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
+                                  const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
+                                  int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res, uint8_t* d_inliers,
+                                  float* d_models, float* d_scores) {
+  int r = checkBatchArgs(ctx, n_frames, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res);
+  if (r != ORBX_OK) return r;
+  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
+  r = waitAll(ctx);  // batches issued with the _async calls may still be writing the inputs
+  if (r != ORBX_OK) return r;
+  r = ensureInitArena(ctx, findModelsWorkBytes(n_pairs, n_iter, capacity));
+  if (r != ORBX_OK) return r;
+  return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res,
+                    d_inliers, d_models, d_scores, nullptr);
+}
+
+int orbx_initialize_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
+                                 const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
+                                 int n_iter, const int32_t* d_sets, const float* K, float sigma, float min_parallax,
+                                 int min_triangulated, orbx_init_result* d_res, float* d_p3d, uint8_t* d_triangulated) {
+  int r = checkBatchArgs(ctx, n_frames, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res);
+  if (r != ORBX_OK) return r;
+  if (!K) return ORBX_E_BADARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
+  r = waitAll(ctx);
+  if (r != ORBX_OK) return r;
+  r = ensureInitArena(ctx, findModelsWorkBytes(n_pairs, n_iter, capacity) + reconWorkBytes(n_pairs, capacity));
+  if (r != ORBX_OK) return r;
+  const ReconParams rc{K, min_parallax, min_triangulated, d_res, d_p3d, d_triangulated};
+  return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, nullptr,
+                    nullptr, nullptr, nullptr, &rc);
+}
+
+namespace {
+// one pair from host memory = frames 0 and 1 of a two-frame batch through the batched path; inputs and outputs live behind the
+// batched stage's work area; synchronous
+int singlePair(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12, int n_iter,
+               const int32_t* sets, float sigma, orbx_hf_result* hres, uint8_t* inliers, float* models, float* scores, const float* K,
+               float min_parallax, int min_triangulated, orbx_init_result* ires, float* p3d, uint8_t* tri) {
+  if (!ctx || n1 < 0 || n2 < 0 || (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2) || n_iter <= 0 || !sets || !(sigma > 0.f) ||
+      n1 >= (1 << 20) || n2 >= (1 << 20) || n_iter >= (1 << 26) || (!hres && !ires) || (ires && !K))
+    return ORBX_E_BADARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
+  int r = waitAll(ctx);
+  if (r != ORBX_OK) return r;
+  const int cap = std::max(std::max(n1, n2), 1);
+  const size_t work = findModelsWorkBytes(1, n_iter, cap) + (ires ? reconWorkBytes(1, cap) : 0);
+  const size_t bK = al256((size_t)2 * cap * sizeof(orbx_keypoint)), bN = al256(8), bM = al256((size_t)cap * 4),
+               bS = al256((size_t)n_iter * 32), bR = al256(sizeof(orbx_hf_result) + sizeof(orbx_init_result)), bI = al256((size_t)2 * cap),
+               bMo = al256((size_t)3 * n_iter * 36), bSo = al256((size_t)2 * n_iter * 4), bP = al256((size_t)cap * 12), bT = al256(cap);
+  r = ensureInitArena(ctx, work + bK + bN + bM + bS + bR + bI + bMo + bSo + bP + bT);
+  if (r != ORBX_OK) return r;
+  uint8_t* p = ctx->dInit + work;
+  orbx_keypoint* dK = (orbx_keypoint*)p; p += bK;
+  int32_t* dN = (int32_t*)p; p += bN;
+  int32_t* dM = (int32_t*)p; p += bM;
+  int32_t* dS = (int32_t*)p; p += bS;
+  orbx_hf_result* dR = (orbx_hf_result*)p;
+  orbx_init_result* dIR = (orbx_init_result*)(p + sizeof(orbx_hf_result)); p += bR;
+  uint8_t* dI = p; p += bI;
+  float* dMo = (float*)p; p += bMo;
+  float* dSo = (float*)p; p += bSo;
+  float* dP = (float*)p; p += bP;
+  uint8_t* dT = p;
+  hipStream_t st = ctx->st;
+  const int32_t hn[2] = {n1, n2};
+  if (n1) HIPCHK(hipMemcpyAsync(dK, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  if (n2) HIPCHK(hipMemcpyAsync(dK + cap, k2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dN, hn, sizeof hn, hipMemcpyHostToDevice, st));
+  if (n1) HIPCHK(hipMemcpyAsync(dM, matches12, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dS, sets, (size_t)n_iter * 32, hipMemcpyHostToDevice, st));
+  const int32_t f0 = 0, f1 = 1;
+  if (ires) {
+    const ReconParams rc{K, min_parallax, min_triangulated, dIR, dP, dT};
+    r = findModels(ctx, ctx->dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, nullptr, nullptr, nullptr, nullptr, &rc);
+  } else {
+    r = findModels(ctx, ctx->dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, dR, dI, dMo, dSo, nullptr);
+  }
+  if (r != ORBX_OK) return r;
+  if (ires) {
+    HIPCHK(hipMemcpyAsync(ires, dIR, sizeof(orbx_init_result), hipMemcpyDeviceToHost, st));
+    if (p3d && n1) HIPCHK(hipMemcpyAsync(p3d, dP, (size_t)n1 * 12, hipMemcpyDeviceToHost, st));
+    if (tri && n1) HIPCHK(hipMemcpyAsync(tri, dT, (size_t)n1, hipMemcpyDeviceToHost, st));
+  } else {
+    HIPCHK(hipMemcpyAsync(hres, dR, sizeof(orbx_hf_result), hipMemcpyDeviceToHost, st));
+    if (inliers && n1) {  // [2][n1] from [2][cap]
+      HIPCHK(hipMemcpyAsync(inliers, dI, (size_t)n1, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(inliers + n1, dI + cap, (size_t)n1, hipMemcpyDeviceToHost, st));
+    }
+    if (models) HIPCHK(hipMemcpyAsync(models, dMo, (size_t)3 * n_iter * 36, hipMemcpyDeviceToHost, st));
+    if (scores) HIPCHK(hipMemcpyAsync(scores, dSo, (size_t)2 * n_iter * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
+                     int n_iter, const int32_t* sets, float sigma, orbx_hf_result* res, uint8_t* inliers, float* models, float* scores) {
+  if (!res) return ORBX_E_BADARG;
+  return singlePair(ctx, k1, n1, k2, n2, matches12, n_iter, sets, sigma, res, inliers, models, scores, nullptr, 0.f, 0, nullptr,
+                    nullptr, nullptr);
+}
+
+int orbx_initialize(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
+                    int n_iter, const int32_t* sets, const float* K, float sigma, float min_parallax, int min_triangulated,
+                    orbx_init_result* res, float* p3d, uint8_t* triangulated) {
+  if (!res || !K) return ORBX_E_BADARG;
+  return singlePair(ctx, k1, n1, k2, n2, matches12, n_iter, sets, sigma, nullptr, nullptr, nullptr, nullptr, K, min_parallax,
+                    min_triangulated, res, p3d, triangulated);
 }
 
 // ---- Converter::toGray (Utils/Converter.cpp:5-19) ------------------------------------------------

@@ -86,6 +86,22 @@ __global__ __launch_bounds__(64) void k_check_rt(const CheckRtArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const float* R = a.R21 + 9 * m;
   const float* t = a.t21 + 3 * m;
+  int nInl = a.nInl, n1 = a.n1;
+  const float* ptsIn = a.pts;
+  const int32_t* bookIn = a.book;
+  uint8_t* good = a.good + (long long)m * a.n1;
+  float* p3d = a.p3d + (long long)m * a.n1 * 3;
+  float* cosBuf = a.cosBuf + (long long)m * a.nInl;
+  if (a.pairNInl) {  // batched form (CheckRtArgs)
+    const int p = m / a.perPair;
+    nInl = m % a.perPair < a.pairNSol[p] ? a.pairNInl[p] : 0;
+    n1 = a.stride;
+    ptsIn = a.pts + (long long)p * a.stride * 4;
+    bookIn = a.book + (long long)p * a.stride;
+    good = a.good + (long long)m * a.stride;
+    p3d = a.p3d + (long long)m * a.stride * 3;
+    cosBuf = a.cosBuf + (long long)m * a.stride;
+  }
   // 1. P1 = [K | 0], P2 = K [R | t] (gemm on CV_32F: double accumulation, one rounding), O2 = -R^T t
   float P2[12], O2[3], Rl[9], tl[3];
 #pragma unroll
@@ -108,18 +124,15 @@ __global__ __launch_bounds__(64) void k_check_rt(const CheckRtArgs a) {
     for (int k = 0; k < 3; k++) sd += (double)Rl[k * 3 + r] * (double)tl[k];
     O2[r] = (float)(-1.0 * sd);
   }
-  uint8_t* good = a.good + (long long)m * a.n1;
-  float* p3d = a.p3d + (long long)m * a.n1 * 3;
-  float* cosBuf = a.cosBuf + (long long)m * a.nInl;
-  for (int i = lane; i < a.n1; i += 64) { good[i] = 0; p3d[3 * i] = 0.f; p3d[3 * i + 1] = 0.f; p3d[3 * i + 2] = 0.f; }
+  for (int i = lane; i < n1; i += 64) { good[i] = 0; p3d[3 * i] = 0.f; p3d[3 * i + 1] = 0.f; p3d[3 * i + 2] = 0.f; }
   __syncthreads();  // (one wave: orders the zeroing before the bookings below)
   int nGood = 0;
-  for (int i0 = 0; i0 < a.nInl; i0 += 64) {
+  for (int i0 = 0; i0 < nInl; i0 += 64) {
     const int i = i0 + lane;
     bool counted = false;
     float cosParallax = 0.f;
-    if (i < a.nInl) {
-      const float4 p = reinterpret_cast<const float4*>(a.pts)[i];
+    if (i < nInl) {
+      const float4 p = reinterpret_cast<const float4*>(ptsIn)[i];
       const float u1 = p.x, v1 = p.y, u2 = p.z, v2 = p.w;
       double A[16];
 #pragma unroll
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(64) void k_check_rt(const CheckRtArgs a) {
       double xd[4];
       smallestRightSingularVector4(A, xd);
       const float X0 = (float)xd[0], X1 = (float)xd[1], X2 = (float)xd[2], X3 = (float)xd[3];
-      const int book = a.book[i];
+      const int book = bookIn[i];
       const float invW = (float)(1.0 / (double)X3);
       const float xn0 = X0 * invW, xn1 = X1 * invW, xn2 = X2 * invW;
       const bool finite3 = isfinite(X0) && isfinite(X1) && isfinite(X2);

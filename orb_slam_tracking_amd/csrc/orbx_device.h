@@ -296,6 +296,12 @@ struct ScoreArgs {
   float invSigmaSquare;
   float* scores;      // [nModels]
   uint8_t* inliers;   // [nModels][N]
+  // batched form (orbx_find_models_batch_device; pairN == nullptr: the single-pair form above): hypothesis m belongs to pair
+  // p = m / perPair, whose N is pairN[p], whose matches are first / second + p * stride, whose keypoints are k1 / k2 +
+  // frames[p] * stride / frames[nPairs + p] * stride, and whose inlier flags go to inliers + m * stride
+  const int32_t* pairN;
+  const int32_t* frames;  // [2][nPairs]
+  int32_t perPair, stride, nPairs;
 };
 
 // k_check_rt: CheckRT (Initializer.cpp:569-713) over nModels (R21, t21) hypotheses
@@ -312,8 +318,58 @@ struct CheckRtArgs {
   float* cosBuf;         // [nModels][nInl] scratch: cosines of the counted points
   int32_t* nGood;        // [nModels]
   float* parallax;       // [nModels]
+  // batched form (orbx_initialize_batch_device; pairNInl == nullptr: the single-pair form above): model m is candidate m % perPair
+  // of pair p = m / perPair, with pairNInl[p] points at pts / book + p * stride (none when m % perPair >= pairNSol[p]); good /
+  // p3d / cosBuf of model m at m * stride, n1 = stride
+  const int32_t* pairNInl;
+  const int32_t* pairNSol;
+  int32_t perPair, stride;
 };
 
+
+// k_init_*: the RANSAC stage of Initializer::Initialize (Initializer.cpp:19-111) over nPairs pairs x nIter hypotheses
+struct InitArgs {
+  const orbx_keypoint* kps;  // [frames][cap] mvKeysUn
+  const int32_t* nKps;       // [frames]
+  const int32_t* m12;        // [nPairs][cap] the matcher's vnMatches12
+  const int32_t* sets;       // [nPairs][nIter][8] mvSets
+  const int32_t* frames;     // [2][nPairs] first frames, then second frames
+  int32_t nPairs, nIter, cap;
+  int32_t* N;                // [nPairs] |mvMatches12|
+  int32_t* scoreN;           // [nPairs] N, or 0 for a pair whose matches cannot be used (nothing is scored)
+  int32_t* pstat;            // [nPairs] ORBX_INIT_* bits found by k_init_prep
+  int32_t* first;            // [nPairs][cap] mvMatches12 (first, second)
+  int32_t* second;
+  float* H21;                // [nPairs * nIter][9]
+  float* H12;
+  float* F21;
+  uint8_t* flags;            // [2][nPairs * nIter] INIT_FLAG_* of the H, then the F hypotheses
+  const float* scoresH;      // [nPairs * nIter] (k_check_model)
+  const float* scoresF;
+  const uint8_t* inlH;       // [nPairs * nIter][cap]
+  const uint8_t* inlF;
+  orbx_hf_result* res;       // [nPairs]
+  uint8_t* inlOut;           // nullable [nPairs][2][cap]: the kept hypotheses' inlier flags (H, then F)
+  // reconstruction (orbx_initialize*): k_init_select also decomposes the chosen model and lists its inliers for CheckRT
+  int32_t reconstruct;
+  float K[9];
+  float minParallax;
+  int32_t minTriangulated;
+  float* R4;                 // [nPairs * 4][9] candidates
+  float* t4;                 // [nPairs * 4][3]
+  int32_t* nSol;             // [nPairs]
+  int32_t* nInl;             // [nPairs]
+  float* pts;                // [nPairs][cap][4] (u1, v1, u2, v2) of the chosen model's inliers, in match order
+  int32_t* book;             // [nPairs][cap] the i-th inlier's keypoint of frame 1 = mvMatches12[i].first (CheckRT's quirk)
+  const int32_t* nGood;      // [nPairs * 4] (k_check_rt)
+  const float* parallax;
+  const uint8_t* good;       // [nPairs * 4][cap]
+  const float* p3d4;         // [nPairs * 4][cap][3]
+  orbx_init_result* ires;    // [nPairs]
+  float* p3dOut;             // nullable [nPairs][cap][3]
+  uint8_t* triOut;           // nullable [nPairs][cap]
+};
+constexpr int INIT_FLAG_H_DEGENERATE = 1, INIT_FLAG_F_DEGENERATE = 2, INIT_FLAG_BAD_SET = 4;
 
 // camera of cv::undistortPoints in the doubles OpenCV converts mK / mDistCoef (CV_32F, Settings.hpp:32,39) to
 struct CamD {

@@ -2944,6 +2944,19 @@ __global__ __launch_bounds__(256) void k_undistort(const orbx_keypoint* __restri
 __global__ __launch_bounds__(64) void k_check_model(const ScoreArgs a) {
   __shared__ __attribute__((aligned(16))) float add[128];
   const int hyp = blockIdx.x, lane = threadIdx.x;
+  int N = a.N;
+  const orbx_keypoint *k1 = a.k1, *k2 = a.k2;
+  const int32_t *first = a.first, *second = a.second;
+  uint8_t* inliers = a.inliers + (size_t)hyp * a.N;
+  if (a.pairN) {  // batched form (ScoreArgs)
+    const int p = hyp / a.perPair;
+    N = a.pairN[p];
+    k1 += (size_t)a.frames[p] * a.stride;
+    k2 += (size_t)a.frames[a.nPairs + p] * a.stride;
+    first += (size_t)p * a.stride;
+    second += (size_t)p * a.stride;
+    inliers = a.inliers + (size_t)hyp * a.stride;
+  }
   float m[9], mi[9];
 #pragma unroll
   for (int q = 0; q < 9; q++) {
@@ -2953,12 +2966,12 @@ __global__ __launch_bounds__(64) void k_check_model(const ScoreArgs a) {
   const float th = a.kind == 0 ? 5.991f : 3.841f, thScore = 5.991f;
   const float invSigmaSquare = a.invSigmaSquare;
   float score = 0;
-  for (int i0 = 0; i0 < a.N; i0 += 64) {
+  for (int i0 = 0; i0 < N; i0 += 64) {
     const int i = i0 + lane;
     float c1 = 0.f, c2 = 0.f;
-    if (i < a.N) {
+    if (i < N) {
       bool bIn = true;
-      const orbx_keypoint kp1 = a.k1[a.first[i]], kp2 = a.k2[a.second[i]];
+      const orbx_keypoint kp1 = k1[first[i]], kp2 = k2[second[i]];
       const float u1 = kp1.x, v1 = kp1.y, u2 = kp2.x, v2 = kp2.y;
       float chiSquare1, chiSquare2;
       if (a.kind == 0) {  // CheckHomography :300-343
@@ -2990,7 +3003,7 @@ __global__ __launch_bounds__(64) void k_check_model(const ScoreArgs a) {
       else c1 = thScore - chiSquare1;
       if (chiSquare2 > th) bIn = false;
       else c2 = thScore - chiSquare2;
-      a.inliers[(size_t)hyp * a.N + i] = bIn ? 1 : 0;
+      inliers[i] = bIn ? 1 : 0;
     }
     add[2 * lane] = c1;
     add[2 * lane + 1] = c2;

@@ -1,0 +1,357 @@
+// init_ref.cpp — CPU restatement of the RANSAC stage of Initializer::Initialize as orbx_init_kernel.hip computes it (test
+// infrastructure, built by tests/init_ref_lib.py with g++ -O2 -ffp-contract=off and loaded with ctypes).  The 8-point solvers
+// (cv::findHomography(src, dst, 0) without its LM refinement, cv::findFundamentalMat(FM_8POINT)), the fixed-sweep cyclic Jacobi
+// they use, Converter::toMatrix3f and Eigen's 3x3 inverse(), operation for operation, so the device's hypotheses can be compared
+// bit for bit.  Scoring and the choice between H and F are composed in Python from the oracle's CheckHomography /
+// CheckFundamental (tests/init_ref_lib.py).
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace {
+
+const int kSweeps = 12;
+const double kDblEps = 2.2204460492503131e-16, kFltEps = 1.1920928955078125e-07;
+
+inline int sidx(int n, int i, int j) {
+  if (i > j) { const int t = i; i = j; j = t; }
+  return i * n - i * (i - 1) / 2 + (j - i);
+}
+
+// smallest-eigenvalue eigenvector of a packed symmetric n x n matrix (n <= 9); returns the number of |eigenvalues| < DBL_EPSILON
+int jacobiSmallest(int n, double* A, double* v) {
+  double V[9][9];
+  for (int i = 0; i < n; i++)
+    for (int k = 0; k < n; k++) V[i][k] = i == k ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kSweeps; sweep++)
+    for (int p = 0; p < n - 1; p++)
+      for (int q = p + 1; q < n; q++) {
+        const double apq = A[sidx(n, p, q)];
+        if (apq == 0.0) continue;
+        const double app = A[sidx(n, p, p)], aqq = A[sidx(n, q, q)];
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        A[sidx(n, p, p)] = app - t * apq;
+        A[sidx(n, q, q)] = aqq + t * apq;
+        A[sidx(n, p, q)] = 0.0;
+        for (int k = 0; k < n; k++) {
+          if (k == p || k == q) continue;
+          const double akp = A[sidx(n, k, p)], akq = A[sidx(n, k, q)];
+          A[sidx(n, k, p)] = c * akp - s * akq;
+          A[sidx(n, k, q)] = s * akp + c * akq;
+        }
+        for (int k = 0; k < n; k++) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  int best = 0, tiny = 0;
+  for (int i = 0; i < n; i++) {
+    if (std::fabs(A[sidx(n, i, i)]) < kDblEps) tiny++;
+    if (A[sidx(n, i, i)] < A[sidx(n, best, best)]) best = i;
+  }
+  for (int k = 0; k < n; k++) v[k] = V[k][best];
+  return tiny;
+}
+
+void mul3(const double* a, const double* b, double* c) {
+  for (int r = 0; r < 3; r++)
+    for (int q = 0; q < 3; q++) c[r * 3 + q] = a[r * 3] * b[q] + a[r * 3 + 1] * b[3 + q] + a[r * 3 + 2] * b[6 + q];
+}
+
+float cof3(const float* m, int i, int j) {
+  const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+  return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
+}
+
+}  // namespace
+
+extern "C" {
+
+// Eigen's Matrix3f::inverse(): cofactors of column 0, det = c0*m00 + (c1*m10 + c2*m20), r(i, j) = cofactor(j, i) / det
+void ir_eigen_inverse(const float* m, float* r) {
+  const float c0 = cof3(m, 0, 0), c1 = cof3(m, 1, 0), c2 = cof3(m, 2, 0);
+  const float det = c0 * m[0] + (c1 * m[3] + c2 * m[6]);
+  const float invdet = 1.0f / det;
+  r[0] = c0 * invdet; r[1] = c1 * invdet; r[2] = c2 * invdet;
+  for (int i = 1; i < 3; i++)
+    for (int j = 0; j < 3; j++) r[i * 3 + j] = cof3(m, j, i) * invdet;
+}
+
+// smallest-eigenvalue eigenvector of a full symmetric n x n (row-major) matrix, for the tests of the Jacobi itself
+int ir_jacobi_smallest(int n, const double* full, double* v) {
+  double A[45];
+  for (int i = 0; i < n; i++)
+    for (int j = i; j < n; j++) A[sidx(n, i, j)] = full[i * n + j];
+  return jacobiSmallest(n, A, v);
+}
+
+// cv::findHomography(src, dst, 0) on 8 points (xy pairs, f32) without the LM step: Md = the f64 model scaled to H22 = 1,
+// H21 = toMatrix3f, H12 = Eigen's inverse.  Returns 0 for a degenerate sample (H21 = H12 = 0), 1 otherwise.
+int ir_solve_h(const float* src, const float* dst, double* Md, float* H21, float* H12) {
+  double cMx = 0, cMy = 0, cmx = 0, cmy = 0;
+  for (int j = 0; j < 8; j++) { cmx += dst[2 * j]; cmy += dst[2 * j + 1]; cMx += src[2 * j]; cMy += src[2 * j + 1]; }
+  const double t8 = 1.0 / 8;
+  cmx *= t8; cmy *= t8; cMx *= t8; cMy *= t8;
+  double smx = 0, smy = 0, sMx = 0, sMy = 0;
+  for (int j = 0; j < 8; j++) {
+    smx += std::fabs(dst[2 * j] - cmx); smy += std::fabs(dst[2 * j + 1] - cmy);
+    sMx += std::fabs(src[2 * j] - cMx); sMy += std::fabs(src[2 * j + 1] - cMy);
+  }
+  bool degenerate = std::fabs(smx) < kDblEps || std::fabs(smy) < kDblEps || std::fabs(sMx) < kDblEps || std::fabs(sMy) < kDblEps;
+  smx = 8 / smx; smy = 8 / smy; sMx = 8 / sMx; sMy = 8 / sMy;
+  double A[45] = {0};
+  for (int j = 0; j < 8; j++) {
+    const double x = (dst[2 * j] - cmx) * smx, y = (dst[2 * j + 1] - cmy) * smy;
+    const double X = (src[2 * j] - cMx) * sMx, Y = (src[2 * j + 1] - cMy) * sMy;
+    const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
+    const double Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
+    for (int r = 0; r < 9; r++)
+      for (int q = r; q < 9; q++) A[sidx(9, r, q)] += Lx[r] * Lx[q] + Ly[r] * Ly[q];
+  }
+  double h[9];
+  jacobiSmallest(9, A, h);
+  const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+  const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+  double T[9], M[9];
+  mul3(invHnorm, h, T);
+  mul3(T, Hnorm2, M);
+  const double s22 = 1. / M[8];
+  for (int q = 0; q < 9; q++) M[q] *= s22;
+  float Mf[9];
+  for (int q = 0; q < 9; q++) {
+    Md[q] = M[q];
+    Mf[q] = (float)M[q];
+    degenerate = degenerate || !std::isfinite(Mf[q]);
+  }
+  float Mi[9];
+  ir_eigen_inverse(Mf, Mi);
+  for (int q = 0; q < 9; q++) { H21[q] = degenerate ? 0.f : Mf[q]; H12[q] = degenerate ? 0.f : Mi[q]; }
+  return degenerate ? 0 : 1;
+}
+
+// cv::findFundamentalMat(src, dst, FM_8POINT) on 8 points: Md = the f64 model (scaled to F22 = 1 when |F22| > FLT_EPSILON),
+// F21 = toMatrix3f.  Returns 0 for a degenerate sample (F21 = 0), 1 otherwise.
+int ir_solve_f(const float* src, const float* dst, double* Md, float* F21) {
+  double m1x = 0, m1y = 0, m2x = 0, m2y = 0;
+  for (int j = 0; j < 8; j++) { m1x += src[2 * j]; m1y += src[2 * j + 1]; m2x += dst[2 * j]; m2y += dst[2 * j + 1]; }
+  const double t8 = 1.0 / 8;
+  m1x *= t8; m1y *= t8; m2x *= t8; m2y *= t8;
+  double s1 = 0, s2 = 0;
+  for (int j = 0; j < 8; j++) {
+    const double ax = src[2 * j] - m1x, ay = src[2 * j + 1] - m1y, bx = dst[2 * j] - m2x, by = dst[2 * j + 1] - m2y;
+    s1 += std::sqrt(ax * ax + ay * ay);
+    s2 += std::sqrt(bx * bx + by * by);
+  }
+  s1 *= t8; s2 *= t8;
+  bool degenerate = s1 < kFltEps || s2 < kFltEps;
+  s1 = 1.4142135623730951 / s1; s2 = 1.4142135623730951 / s2;
+  double A[45] = {0};
+  for (int j = 0; j < 8; j++) {
+    const double x1 = (src[2 * j] - m1x) * s1, y1 = (src[2 * j + 1] - m1y) * s1;
+    const double x2 = (dst[2 * j] - m2x) * s2, y2 = (dst[2 * j + 1] - m2y) * s2;
+    const double r[9] = {x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, 1};
+    for (int i = 0; i < 9; i++)
+      for (int q = i; q < 9; q++) A[sidx(9, i, q)] += r[i] * r[q];
+  }
+  double f[9];
+  degenerate = jacobiSmallest(9, A, f) >= 2 || degenerate;
+  double G[6];
+  for (int i = 0; i < 3; i++)
+    for (int q = i; q < 3; q++) G[sidx(3, i, q)] = f[i] * f[q] + f[3 + i] * f[3 + q] + f[6 + i] * f[6 + q];
+  double w[3];
+  jacobiSmallest(3, G, w);
+  double F0[9];
+  for (int r = 0; r < 3; r++) {
+    const double fw = f[r * 3] * w[0] + f[r * 3 + 1] * w[1] + f[r * 3 + 2] * w[2];
+    for (int q = 0; q < 3; q++) F0[r * 3 + q] = f[r * 3 + q] - fw * w[q];
+  }
+  const double T1[9] = {s1, 0, -s1 * m1x, 0, s1, -s1 * m1y, 0, 0, 1};
+  const double T2t[9] = {s2, 0, 0, 0, s2, 0, -s2 * m2x, -s2 * m2y, 1};
+  double T[9], M[9];
+  mul3(T2t, F0, T);
+  mul3(T, T1, M);
+  if (std::fabs(M[8]) > kFltEps) {
+    const double s22 = 1. / M[8];
+    for (int q = 0; q < 9; q++) M[q] *= s22;
+  }
+  float Mf[9];
+  for (int q = 0; q < 9; q++) {
+    Md[q] = M[q];
+    Mf[q] = (float)M[q];
+    degenerate = degenerate || !std::isfinite(Mf[q]);
+  }
+  for (int q = 0; q < 9; q++) F21[q] = degenerate ? 0.f : Mf[q];
+  return degenerate ? 0 : 1;
+}
+
+// The whole stage for one pair (orbx_find_models): mvMatches12, every hypothesis, scored by the ORACLE's CheckHomography /
+// CheckFundamental (passed in: oracle/liborbx_oracle.so's orbo_check_*), the first maximum of each loop, SH, SF, RH, model.
+// ri = {status, model, N, best_it_h, best_it_f, nH, nF, 0}, rf = {SH, SF, RH, H21[9], H12[9], F21[9]}; inl [2][n1] (first N),
+// models [3][n_iter][9], scores [2][n_iter] (0 for a degenerate or skipped hypothesis).
+struct IrKp { float x, y, size, angle, response; int32_t octave, class_id; };
+typedef float (*ChkH)(const float*, const float*, const IrKp*, const IrKp*, const int32_t*, const int32_t*, int, float, uint8_t*);
+typedef float (*ChkF)(const float*, const IrKp*, const IrKp*, const int32_t*, const int32_t*, int, float, uint8_t*);
+void ir_find_models(const IrKp* k1, int n1, const IrKp* k2, int n2, const int32_t* m12, int n_iter, const int32_t* sets, float sigma,
+                    ChkH chkH, ChkF chkF, int32_t* ri, float* rf, uint8_t* inl, float* models, float* scores) {
+  std::vector<int32_t> first, second;
+  int status = 0;
+  for (int i = 0; i < n1; i++)
+    if (m12[i] >= 0) {
+      if (m12[i] >= n2) status |= 128;
+      first.push_back(i);
+      second.push_back(m12[i]);
+    }
+  const int N = (int)first.size();
+  if (N < 8) status |= 1;
+  const int sN = (status & 128) ? 0 : N;
+  std::vector<uint8_t> cur(N + 1), bestH(N + 1, 0), bestF(N + 1, 0);
+  float SH = 0, SF = 0, keptH[9] = {0}, keptH12[9] = {0}, keptF[9] = {0};
+  int itH = -1, itF = -1;
+  float* H21 = models;
+  float* H12 = models + (size_t)n_iter * 9;
+  float* F21 = models + (size_t)2 * n_iter * 9;
+  for (int it = 0; it < n_iter; it++) {
+    const int32_t* set = sets + (size_t)it * 8;
+    bool ok = sN >= 8;
+    for (int j = 0; j < 8; j++) ok = ok && set[j] >= 0 && set[j] < sN;
+    for (int j = 1; j < 8; j++)
+      for (int k = 0; k < j; k++) ok = ok && set[j] != set[k];
+    scores[it] = 0; scores[n_iter + it] = 0;
+    for (int q = 0; q < 9; q++) H21[it * 9 + q] = H12[it * 9 + q] = F21[it * 9 + q] = 0.f;
+    if (!ok) {
+      if (sN >= 8) status |= 2;
+      continue;
+    }
+    float src[16], dst[16];
+    for (int j = 0; j < 8; j++) {
+      src[2 * j] = k1[first[set[j]]].x; src[2 * j + 1] = k1[first[set[j]]].y;
+      dst[2 * j] = k2[second[set[j]]].x; dst[2 * j + 1] = k2[second[set[j]]].y;
+    }
+    double Md[9];
+    if (ir_solve_h(src, dst, Md, H21 + it * 9, H12 + it * 9)) {
+      const float sc = chkH(H21 + it * 9, H12 + it * 9, k1, k2, first.data(), second.data(), N, sigma, cur.data());
+      scores[it] = sc;
+      if (sc > SH) {
+        SH = sc; itH = it; bestH = cur;
+        for (int q = 0; q < 9; q++) { keptH[q] = H21[it * 9 + q]; keptH12[q] = H12[it * 9 + q]; }
+      }
+    }
+    if (ir_solve_f(src, dst, Md, F21 + it * 9)) {
+      const float sc = chkF(F21 + it * 9, k1, k2, first.data(), second.data(), N, sigma, cur.data());
+      scores[n_iter + it] = sc;
+      if (sc > SF) { SF = sc; itF = it; bestF = cur; for (int q = 0; q < 9; q++) keptF[q] = F21[it * 9 + q]; }
+    }
+  }
+  int nH = 0, nF = 0;
+  for (int i = 0; i < N; i++) {
+    const uint8_t h = itH >= 0 && i < sN ? bestH[i] : 0, f = itF >= 0 && i < sN ? bestF[i] : 0;
+    nH += h; nF += f;
+    inl[i] = h; inl[n1 + i] = f;
+  }
+  const float sum = SH + SF;
+  if (sum == 0.f) status |= 4;
+  const float RH = sum == 0.f ? 0.f : SH / sum;
+  ri[0] = status; ri[1] = sum == 0.f ? -1 : (RH > 0.50 ? 0 : 1); ri[2] = N; ri[3] = itH; ri[4] = itF; ri[5] = nH; ri[6] = nF; ri[7] = 0;
+  rf[0] = SH; rf[1] = SF; rf[2] = RH;
+  for (int q = 0; q < 9; q++) { rf[3 + q] = keptH[q]; rf[12 + q] = keptH12[q]; rf[21 + q] = keptF[q]; }
+}
+
+}  // extern "C"
+
+#include <cstdlib>
+extern "C" {
+// Initializer::Initialize's draw of mvSets (Initializer.cpp:50-63) after srand(seed), as the reference writes it
+void ir_sample_sets(unsigned seed, int N, int n_iter, int32_t* out) {
+  srand(seed);
+  std::vector<size_t> vAllIndices;
+  vAllIndices.reserve(N);
+  std::vector<size_t> vAvailableIndices;
+  for (int i = 0; i < N; i++) vAllIndices.push_back(i);
+  for (int it = 0; it < n_iter; it++) {
+    vAvailableIndices = vAllIndices;
+    for (size_t j = 0; j < 8; j++) {
+      int randi = rand() % vAvailableIndices.size();
+      int idx = vAvailableIndices[randi];
+      vAvailableIndices[randi] = vAvailableIndices.back();
+      vAvailableIndices.pop_back();
+      out[it * 8 + j] = idx;
+    }
+  }
+}
+}  // extern "C"
+
+#include <cmath>
+using std::fabs;
+using std::sqrt;
+#include "../../orb_slam_tracking_amd/csrc/orbx_init_decomp.inc"
+extern "C" {
+// cv::decomposeEssentialMat(K^T F K) / cv::decomposeHomographyMat(H, K) as the device computes them (orbx_init_decomp.inc)
+int ir_decompose_essential(const float* F, const float* K, float* R, float* t) {
+  float E[9];
+  orbx_decomp::essentialFromF(F, K, E);
+  return orbx_decomp::decomposeEssential(E, (float(*)[9])R, (float(*)[3])t);
+}
+int ir_decompose_homography(const float* H, const float* K, float* R, float* t, float* n) {
+  return orbx_decomp::decomposeHomography(H, K, (float(*)[9])R, (float(*)[3])t, (float(*)[3])n);
+}
+}  // extern "C"
+
+extern "C" {
+// Initializer::Initialize end to end for one pair (orbx_initialize): ir_find_models, then the chosen model decomposed, every
+// candidate through the ORACLE's CheckRT (chkRT = oracle/liborbx_oracle.so's orbo_check_rt) with th2 = 4 sigma^2, and ReconstructHF's
+// rules.  ri = the 12 int fields of orbx_init_result, rf = {SH, SF, RH, parallax, R21[9], t21[3], H21[9], F21[9]}; p3d [n1][3],
+// tri [n1] of the best solution (zeros if none).
+typedef int (*ChkRT)(const float*, const float*, const float*, const IrKp*, int, const IrKp*, const int32_t*, const int32_t*, int,
+                     const uint8_t*, float, uint8_t*, float*, float*);
+void ir_initialize(const IrKp* k1, int n1, const IrKp* k2, int n2, const int32_t* m12, int n_iter, const int32_t* sets, const float* K,
+                   float sigma, float min_parallax, int min_triangulated, ChkH chkH, ChkF chkF, ChkRT chkRT, int32_t* ri, float* rf,
+                   float* p3d, uint8_t* tri) {
+  int32_t hi[8];
+  float hf[30];
+  std::vector<uint8_t> inl(2 * (size_t)(n1 > 0 ? n1 : 1));
+  std::vector<float> models((size_t)27 * n_iter), scores((size_t)2 * n_iter);
+  ir_find_models(k1, n1, k2, n2, m12, n_iter, sets, sigma, chkH, chkF, hi, hf, inl.data(), models.data(), scores.data());
+  for (int i = 0; i < 7; i++) ri[i] = hi[i];
+  for (int i = 7; i < 12; i++) ri[i] = 0;
+  int st = hi[0], nSol = 0, bi = -1, bg = 0, sg = 0;
+  float bp = -1.f, R[4][9], t[4][3], nrm[4][3];
+  const int N = hi[2];
+  std::vector<int32_t> first, second;
+  for (int i = 0; i < n1; i++)
+    if (m12[i] >= 0) { first.push_back(i); second.push_back(m12[i]); }
+  std::vector<uint8_t> good[4];
+  std::vector<float> pts[4];
+  int ng[4] = {0, 0, 0, 0};
+  float par[4] = {0, 0, 0, 0};
+  if (st == 0) {
+    const bool isF = hi[1] == 1;
+    const float* M = isF ? hf + 21 : hf + 3;
+    if (isF) {
+      float E[9];
+      orbx_decomp::essentialFromF(M, K, E);
+      nSol = orbx_decomp::decomposeEssential(E, R, t);
+    } else {
+      nSol = orbx_decomp::decomposeHomography(M, K, R, t, nrm);
+    }
+    const uint8_t* ic = inl.data() + (isF ? n1 : 0);
+    const float th2 = (float)(4.0 * (double)(sigma * sigma));
+    for (int k = 0; k < nSol; k++) {
+      good[k].assign(n1 > 0 ? n1 : 1, 0);
+      pts[k].assign(3 * (size_t)(n1 > 0 ? n1 : 1), 0.f);
+      ng[k] = chkRT(R[k], t[k], K, k1, n1, k2, first.data(), second.data(), N, ic, th2, good[k].data(), pts[k].data(), &par[k]);
+    }
+    st |= orbx_decomp::reconstructRules(nSol, ng, par, isF ? hi[6] : hi[5], min_parallax, min_triangulated, &bi, &bg, &sg, &bp);
+  }
+  ri[0] = st; ri[7] = nSol; ri[8] = bi; ri[9] = bg; ri[10] = sg;
+  rf[0] = hf[0]; rf[1] = hf[1]; rf[2] = hf[2]; rf[3] = bp;
+  for (int q = 0; q < 9; q++) { rf[4 + q] = bi >= 0 ? R[bi][q] : 0.f; rf[16 + q] = hf[3 + q]; rf[25 + q] = hf[21 + q]; }
+  for (int q = 0; q < 3; q++) rf[13 + q] = bi >= 0 ? t[bi][q] : 0.f;
+  for (int i = 0; i < n1; i++) {
+    tri[i] = bi >= 0 ? good[bi][i] : 0;
+    for (int c = 0; c < 3; c++) p3d[3 * i + c] = bi >= 0 ? pts[bi][3 * i + c] : 0.f;
+  }
+}
+}  // extern "C"
