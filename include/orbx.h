@@ -5,6 +5,7 @@
  *   ORBextractor getters + mvImagePyramid              (Features/ORBextractor.hpp:87-111)
  *   ORBmatcher::SearchForInitialization                (Features/ORBmatcher.hpp:36, .cpp:11-150)
  *   Frame grid rules the matcher depends on            (SlamTypes/Frame.cpp:70-99, 163-206)
+ *   DBoW2 TemplatedVocabulary<FORB>::transform / score (Thirdparty/DBoW2; Frame::mBowVec / mFeatVec, "bag of words" below)
  * Plain pointers and sizes only; no C++ or torch types cross this boundary.  The C++ classes with the
  * reference's own signatures live in include/orbx_shim.hpp and call only the functions below.
  *
@@ -429,6 +430,92 @@ int orbx_find_models_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, cons
 int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
                      int n_iter, const int32_t* sets, float sigma, orbx_hf_result* res, uint8_t* inliers, float* models,
                      float* scores);
+
+/* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
+ * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
+ * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)
+ * Bit-identical to a CPU restatement of those lines: word ids, node ids, feature indices and the bytes of every f64.
+ *   node ids      the loader's (:1542-1620): root 0, the file's node lines 1, 2, ... in order; children in file order; word ids in
+ *                 file order to the lines whose leaf flag is > 0
+ *   descent       at each level the child with the smallest Hamming distance, the first child on a tie; it ends at a node WITHOUT
+ *                 CHILDREN (isLeaf()), whatever its flag: a childless node flagged non-leaf gives word id 0 and its own weight,
+ *                 a flagged leaf with children is descended through.  The FeatureVector's node is the one at depth L - levelsup
+ *                 (the root, 0, when that is <= 0)
+ *   BowVector     a feature whose weight is <= 0 is stopped; TF / TF_IDF: repeated f64 additions of the weight, divided by the
+ *                 number of distinct WORDS when the scoring does not normalise (DOT_PRODUCT, the reference's quirk); IDF / BINARY:
+ *                 the first value; scoring L2_NORM: L2 norm, every other scoring but DOT_PRODUCT: L1 norm, a sequential f64 sum in
+ *                 ascending word order (nothing divided when it is 0)
+ *   FeatureVector node ids ascending, each with its feature indices ascending; stopped features absent
+ *   empty         a vocabulary without words, or a frame without keypoints: both vectors empty
+ * Documented deviations from the reference:
+ *   1. Trailing empty line: the reference loader turns an empty last line (every file saveToTextFile writes ends in one) into an
+ *      extra child of the root with weight 0, word id 0 and an UNINITIALISED descriptor, whose effect is indeterminate; here
+ *      empty and whitespace-only lines are skipped.
+ *   2. Shallow leaf: a leaf reached above depth L - levelsup leaves the reference's nid uninitialised (UB); here it is the
+ *      leaf's own node id.
+ *   3. Refused inputs (ORBX_E_BADARG; the reference accepts them with UB, or prints a message and keeps an empty vocabulary): a
+ *      parent id outside [0, the line's own id); a node with more than k children; a node deeper than L; a header outside
+ *      k 0..20, L 1..10, scoring 0..5, weighting 0..3; a node line with fewer than 35 numbers.
+ *   4. Scores: only L1Scoring::score (scoring L1_NORM) is offered; the score entry point returns ORBX_E_BADARG for the other five
+ *      scoring types.  transform supports all four weightings and both norms.
+ * Descriptor elements are parsed as int and cast to uint8, weights as double (strtod, the rounding of istream >> double).
+ * A frame may hold up to ORBX_BOW_MAX_FEATURES keypoints: a larger capacity returns ORBX_E_CAPACITY. */
+#define ORBX_BOW_MAX_FEATURES 16384
+#define ORBX_BOW_TF_IDF 0 /* WeightingType */
+#define ORBX_BOW_TF 1
+#define ORBX_BOW_IDF 2
+#define ORBX_BOW_BINARY 3
+#define ORBX_BOW_L1_NORM 0 /* ScoringType */
+#define ORBX_BOW_L2_NORM 1
+#define ORBX_BOW_CHI_SQUARE 2
+#define ORBX_BOW_KL 3
+#define ORBX_BOW_BHATTACHARYYA 4
+#define ORBX_BOW_DOT_PRODUCT 5
+typedef struct orbx_vocabulary orbx_vocabulary;
+
+/* Host only, no context: the text format of saveToTextFile (:1626-1645; ORB-SLAM's ORBvoc.txt), a header "k L scoring
+ * weighting" and one line "parent leaf_flag d0 .. d31 weight" per node.  header = {k, L, scoring, weighting}; for node i + 1
+ * (i in [0, n)): parent[i], is_leaf[i] (the flag as read), desc32[i * 32 .. +32], weight[i].  With NULL arrays only *n_nodes
+ * is set; with arrays, capacity < n returns ORBX_E_CAPACITY.  Returns the node count, or ORBX_E_BADARG for an unreadable
+ * file, a bad header or line, or a refused tree (deviation 3).  This is the parser of orbx_vocabulary_load_text. */
+int orbx_vocabulary_parse_text(const char* path, int32_t* header, int32_t* n_nodes, int32_t* parent, int32_t* is_leaf,
+                               uint8_t* desc32, double* weight, int32_t capacity);
+/* A vocabulary on the context's device from host arrays for nodes 1..n_nodes in file order (the layout above).  The tree is
+ * checked first (ORBX_E_BADARG, deviation 3), then laid out breadth-first on the device.  ctx == NULL (no device: orbx_create
+ * returned ORBX_E_HIP) returns ORBX_E_HIP for a well-formed tree.  Destroy vocabularies before their context. */
+int orbx_vocabulary_create(orbx_ctx* ctx, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
+                           const int32_t* is_leaf, const uint8_t* desc32, const double* weight, orbx_vocabulary** out);
+int orbx_vocabulary_load_text(orbx_ctx* ctx, const char* path, orbx_vocabulary** out);
+void orbx_vocabulary_destroy(orbx_vocabulary* voc);
+/* info = {k, L, scoring, weighting, nodes (without the root), words} */
+int orbx_vocabulary_info(const orbx_vocabulary* voc, int32_t* info6);
+
+/* transform(features, BowVector&, FeatureVector&, levelsup) for a batch of frames, device-resident, stream-ordered on the
+ * context stream (the call returns once queued; results are valid after a device synchronisation): frame f's descriptors at
+ * d_desc32 + f * capacity * 32, its count d_n[f] (clamped to [0, capacity]; the layout of orbx_extract_batch_device).
+ * Outputs, [n_frames][capacity] entries each: d_bow_word uint32 / d_bow_value f64 (the BowVector in ascending word order,
+ * d_bow_n[f] entries); d_fv_node / d_fv_feat uint32 (the FeatureVector as (node, feature) pairs in ascending order, d_fv_n[f]
+ * entries); d_feat_word uint32 (each feature's word id from the descent, stopped or not, first d_n[f] entries).  d_fv_* (all
+ * three or none) and d_feat_word may be NULL: without d_fv_* it is the two-argument transform.  ORBX_E_BADARG: a vocabulary of
+ * another context, null required pointers, n_frames < 0, capacity < 1; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES. */
+int orbx_bow_transform_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n_frames, const uint8_t* d_desc32,
+                                    const int32_t* d_n, int capacity, int levelsup, uint32_t* d_bow_word, double* d_bow_value,
+                                    int32_t* d_bow_n, uint32_t* d_fv_node, uint32_t* d_fv_feat, int32_t* d_fv_n,
+                                    uint32_t* d_feat_word);
+/* The same for one frame in host memory (desc32 [n][32]), through the batched path; outputs host arrays of n entries (bow_*,
+ * fv_*, feat_word; fv_* and feat_word nullable).  Synchronous. */
+int orbx_bow_transform(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint8_t* desc32, int n, int levelsup, uint32_t* bow_word,
+                       double* bow_value, int32_t* bow_n, uint32_t* fv_node, uint32_t* fv_feat, int32_t* fv_n, uint32_t* feat_word);
+/* L1Scoring::score(v1, v2) for pair p = frames h_first[p], h_second[p] (host arrays, each in [0, n_frames), checked before any
+ * launch: ORBX_E_BADARG) of the BowVectors transform wrote (d_bow_* with the same capacity); d_score_f64 [n_pairs].
+ * Stream-ordered like the transform.  ORBX_E_BADARG for a vocabulary whose scoring is not L1_NORM (deviation 4). */
+int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n_frames, int n_pairs, const int32_t* h_first,
+                                const int32_t* h_second, const uint32_t* d_bow_word, const double* d_bow_value,
+                                const int32_t* d_bow_n, int capacity, double* d_score_f64);
+/* The same for two BowVectors in host memory (ascending words w1 [n1] / w2 [n2] with their values), through the batched path.
+ * Synchronous. */
+int orbx_bow_score(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint32_t* w1, const double* v1, int n1, const uint32_t* w2,
+                   const double* v2, int n2, double* score);
 
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0

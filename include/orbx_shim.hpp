@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <cstdlib>
@@ -478,6 +479,93 @@ class Initializer {
   float mSigma;
   int mMaxIterations;
   ORBextractor* mpORBextractor;
+};
+
+}  // namespace ORB_SLAM_Tracking
+
+// DBoW2's vector types (Thirdparty/DBoW2/include/DBoW2/BowVector.h, FeatureVector.h): the same names and key / value types
+namespace DBoW2 {
+typedef unsigned int WordId;
+typedef double WordValue;
+typedef unsigned int NodeId;
+class BowVector : public std::map<WordId, WordValue> {};
+class FeatureVector : public std::map<NodeId, std::vector<unsigned int> > {};
+}  // namespace DBoW2
+
+namespace ORB_SLAM_Tracking {
+
+// Features/ORBVocabulary.hpp: TemplatedVocabulary<FORB> with the members ORB-SLAM calls -- loadFromTextFile, transform (BowVector +
+// FeatureVector), score (L1Scoring) -- on the device of an ORBextractor's context (orbx.h, "bag of words", with its documented
+// deviations).  Descriptors are N x 32 contiguous bytes (a Frame's mDescriptors), or a vector of 1 x 32 cv::Mat rows.
+class ORBVocabulary {
+ public:
+  explicit ORBVocabulary(ORBextractor* extractor) : e_(extractor) {}
+  ~ORBVocabulary() { orbx_vocabulary_destroy(voc_); }
+  ORBVocabulary(const ORBVocabulary&) = delete;
+  ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+
+  // TemplatedVocabulary.h:1542-1620; the reference prints and keeps an empty vocabulary on a bad header, this throws
+  void loadFromTextFile(const std::string& filename) {
+    orbx_vocabulary* v = nullptr;
+    const int r = orbx_vocabulary_load_text(e_->context(), filename.c_str(), &v);
+    if (r != ORBX_OK) throw orbx::Error(r, "loadFromTextFile(" + filename + ") failed");
+    orbx_vocabulary_destroy(voc_);
+    voc_ = v;
+  }
+
+  void transform(const uint8_t* descriptors, int n, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {
+    run(descriptors, n, levelsup, v, &fv);
+  }
+  void transform(const uint8_t* descriptors, int n, DBoW2::BowVector& v) const { run(descriptors, n, 0, v, nullptr); }
+  void transform(const std::vector<uint8_t>& descriptors, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {
+    run(descriptors.data(), (int)(descriptors.size() / 32), levelsup, v, &fv);
+  }
+#ifdef ORBX_WITH_OPENCV
+  // Frame::ComputeBoW: transform(Converter::toDescriptorVector(mDescriptors), mBowVec, mFeatVec, 4)
+  void transform(const std::vector<cv::Mat>& features, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {
+    std::vector<uint8_t> d(features.size() * 32);
+    for (size_t i = 0; i < features.size(); i++) std::memcpy(d.data() + 32 * i, features[i].data, 32);
+    run(d.data(), (int)features.size(), levelsup, v, &fv);
+  }
+#endif
+
+  // L1Scoring::score (src/ScoringObject.cpp:23-66); ORBX_E_BADARG for a vocabulary of another scoring type
+  double score(const DBoW2::BowVector& a, const DBoW2::BowVector& b) const {
+    std::vector<uint32_t> w1, w2;
+    std::vector<double> v1, v2;
+    for (const auto& e : a) { w1.push_back(e.first); v1.push_back(e.second); }
+    for (const auto& e : b) { w2.push_back(e.first); v2.push_back(e.second); }
+    double s = 0.0;
+    const int r = orbx_bow_score(e_->context(), voc_, w1.data(), v1.data(), (int)w1.size(), w2.data(), v2.data(), (int)w2.size(), &s);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+    return s;
+  }
+
+  bool empty() const { return words() == 0; }
+  unsigned int size() const { return (unsigned int)words(); }
+
+ private:
+  int words() const {
+    int32_t info[6] = {0, 0, 0, 0, 0, 0};
+    if (voc_) orbx_vocabulary_info(voc_, info);
+    return info[5];
+  }
+  void run(const uint8_t* d, int n, int levelsup, DBoW2::BowVector& v, DBoW2::FeatureVector* fv) const {
+    v.clear();
+    if (fv) fv->clear();
+    const size_t m = (size_t)std::max(n, 1);
+    std::vector<uint32_t> bw(m), fn(m), ff(m);
+    std::vector<double> bv(m);
+    int32_t bn = 0, fvn = 0;
+    const int r = orbx_bow_transform(e_->context(), voc_, d, n, levelsup, bw.data(), bv.data(), &bn, fv ? fn.data() : nullptr,
+                                     fv ? ff.data() : nullptr, fv ? &fvn : nullptr, nullptr);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+    for (int i = 0; i < bn; i++) v.emplace_hint(v.end(), bw[i], bv[i]);
+    if (fv)
+      for (int i = 0; i < fvn; i++) (*fv)[fn[i]].push_back(ff[i]);
+  }
+  ORBextractor* e_;
+  orbx_vocabulary* voc_ = nullptr;
 };
 
 }  // namespace ORB_SLAM_Tracking

@@ -5,13 +5,15 @@ C++ host pipeline).  The classes keep the names and argument meaning of the refe
 
 * ``ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST)`` / ``__call__``  -- Features/ORBextractor.hpp:68-85
 * ``ORBmatcher(nnratio=0.6, checkOri=True).SearchForInitialization(F1, F2, windowSize=100)`` -- Features/ORBmatcher.hpp:15,36
-* ``Frame`` -- the part of SlamTypes/Frame.{hpp,cpp} the matcher reads (mvKeys, mvKeysUn, mDescriptors, N, image bounds)
+* ``Frame`` -- the part of SlamTypes/Frame.{hpp,cpp} the matcher reads (mvKeys, mvKeysUn, mDescriptors, N, image bounds), and
+  ``ComputeBoW`` (mBowVec / mFeatVec) with a ``Vocabulary`` (Features/ORBVocabulary.hpp: DBoW2's TemplatedVocabulary<FORB>)
 
 There is NO CPU fallback: importing works anywhere, but every compute call raises ``OrbxError`` unless liborbx.so is
 built and a HIP device is usable.  (The C++ drop-in classes live in include/orbx_shim.hpp.)
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import os
@@ -20,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -214,6 +216,16 @@ def lib() -> ctypes.CDLL:
     L.orbx_find_models.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, f32, ctypes.POINTER(HFResult), vp, vp, vp]
     L.orbx_initialize_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, f32, f32, i32, vp, vp, vp]
     L.orbx_initialize.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, f32, f32, i32, ctypes.POINTER(InitResult), vp, vp]
+    L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
+    L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
+    L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.orbx_vocabulary_destroy.argtypes = [vp]
+    L.orbx_vocabulary_destroy.restype = None
+    L.orbx_vocabulary_info.argtypes = [vp, vp]
+    L.orbx_bow_transform_batch_device.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_bow_transform.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_bow_score_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.orbx_bow_score.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
     L.orbx_multi_create.argtypes = [ctypes.POINTER(_Params), i32, vp, i32, i32, i32, ctypes.POINTER(vp)]
     L.orbx_multi_destroy.argtypes = [vp]
     L.orbx_multi_destroy.restype = None
@@ -893,14 +905,162 @@ def camera_from(K, distCoef) -> Tuple[float, ...]:
     return (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), float(d[0]), float(d[1]), float(d[2]), float(d[3]))
 
 
+BOW_MAX_FEATURES = 16384  # ORBX_BOW_MAX_FEATURES: keypoints per frame of the bag-of-words calls
+BowResult = collections.namedtuple("BowResult", "bow_word bow_value fv_node fv_feat feat_word")
+BowResult.__doc__ = """One frame's transform: the BowVector as bow_word (uint32) / bow_value (float64) in ascending word order, the
+FeatureVector as (fv_node, fv_feat) uint32 pairs in ascending order, and feat_word, each feature's word id (None if not asked)."""
+
+
+class Vocabulary:
+    """Features/ORBVocabulary.hpp -- DBoW2's TemplatedVocabulary<FORB> -- on the device of an ORBextractor's context: transform
+    (BowVector, FeatureVector) and the L1 score (include/orbx.h, "bag of words", with its documented deviations).  The
+    vocabulary keeps its extractor alive; close() it (or drop it) before the extractor."""
+
+    TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
+    L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT = 0, 1, 2, 3, 4, 5
+
+    def __init__(self, extractor: ORBextractor, handle: ctypes.c_void_p):
+        self._ext, self._L, self._h = extractor, extractor._L, handle
+        info = np.zeros(6, np.int32)
+        self._ext._check(self._L.orbx_vocabulary_info(self._h, _ptr(info)), "orbx_vocabulary_info")
+        self.k, self.L, self.scoring, self.weighting, self.n_nodes, self.n_words = (int(v) for v in info)
+
+    @staticmethod
+    def parse_text(path: str):
+        """The host parser of the text format (orbx_vocabulary_parse_text): (header [k, L, scoring, weighting], parent, is_leaf,
+        desc [n, 32], weight) for nodes 1..n in file order."""
+        L = lib()
+        hdr, n = np.zeros(4, np.int32), ctypes.c_int32(0)
+        r = L.orbx_vocabulary_parse_text(os.fsencode(path), _ptr(hdr), ctypes.byref(n), None, None, None, None, 0)
+        if r < 0:
+            raise OrbxError(r, "orbx_vocabulary_parse_text(%s)" % path)
+        m = n.value
+        parent, leaf = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
+        desc, weight = np.zeros((max(m, 1), 32), np.uint8), np.zeros(max(m, 1), np.float64)
+        r = L.orbx_vocabulary_parse_text(os.fsencode(path), _ptr(hdr), ctypes.byref(n), _ptr(parent), _ptr(leaf), _ptr(desc),
+                                         _ptr(weight), len(parent))
+        if r < 0:
+            raise OrbxError(r, "orbx_vocabulary_parse_text(%s)" % path)
+        return hdr, parent[:m], leaf[:m], desc[:m], weight[:m]
+
+    @classmethod
+    def from_text(cls, extractor: ORBextractor, path: str) -> "Vocabulary":
+        """loadFromTextFile (saveToTextFile's format, ORB-SLAM's ORBvoc.txt)."""
+        h = ctypes.c_void_p(0)
+        extractor._check(extractor._L.orbx_vocabulary_load_text(extractor._h, os.fsencode(path), ctypes.byref(h)),
+                         "orbx_vocabulary_load_text(%s)" % path)
+        return cls(extractor, h)
+
+    @classmethod
+    def from_arrays(cls, extractor: ORBextractor, k: int, L: int, scoring: int, weighting: int, parent, is_leaf, desc,
+                    weight) -> "Vocabulary":
+        """Nodes 1..n in file order: parent [n] (node ids, root 0), is_leaf [n] (the file's flag), desc [n, 32], weight [n]."""
+        parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        n = len(parent)
+        is_leaf = np.ascontiguousarray(is_leaf, np.int32).reshape(-1)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        weight = np.ascontiguousarray(weight, np.float64).reshape(-1)
+        if len(is_leaf) != n or len(desc) != n or len(weight) != n:
+            raise OrbxError(E_BADARG, "parent, is_leaf, desc and weight must describe the same nodes")
+        h = ctypes.c_void_p(0)
+        extractor._check(extractor._L.orbx_vocabulary_create(extractor._h, int(k), int(L), int(scoring), int(weighting), n, _ptr(parent),
+                                                             _ptr(is_leaf), _ptr(desc), _ptr(weight), ctypes.byref(h)),
+                         "orbx_vocabulary_create")
+        return cls(extractor, h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbx_vocabulary_destroy(self._h)
+            self._h = ctypes.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def transform(self, descriptors, levelsup: int = 4, feature_vector: bool = True, feat_word: bool = False) -> BowResult:
+        """transform(features, BowVector&, FeatureVector&, levelsup) of one frame's descriptors [n, 32] from host memory
+        (feature_vector=False: the two-argument transform, fv_* None).  Synchronous."""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        n = len(d)
+        m = max(n, 1)
+        bw, bv, fn, ff, fw = np.zeros(m, np.uint32), np.zeros(m, np.float64), np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        bn, fvn = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._ext._check(self._L.orbx_bow_transform(self._ext._h, self._h, _ptr(d), n, int(levelsup), _ptr(bw), _ptr(bv), ctypes.byref(bn),
+                                                    _ptr(fn) if feature_vector else None, _ptr(ff) if feature_vector else None,
+                                                    ctypes.byref(fvn) if feature_vector else None, _ptr(fw) if feat_word else None),
+                         "orbx_bow_transform")
+        return BowResult(bw[:bn.value], bv[:bn.value], fn[:fvn.value] if feature_vector else None, ff[:fvn.value] if feature_vector else None,
+                         fw[:n] if feat_word else None)
+
+    def score(self, w1, v1, w2, v2) -> float:
+        """L1Scoring::score of two BowVectors in host memory (ascending word arrays and their values).  Synchronous."""
+        w1, w2 = np.ascontiguousarray(w1, np.uint32), np.ascontiguousarray(w2, np.uint32)
+        v1, v2 = np.ascontiguousarray(v1, np.float64), np.ascontiguousarray(v2, np.float64)
+        if len(w1) != len(v1) or len(w2) != len(v2):
+            raise OrbxError(E_BADARG, "a BowVector's words and values differ in length")
+        out = ctypes.c_double(0.0)
+        self._ext._check(self._L.orbx_bow_score(self._ext._h, self._h, _ptr(w1), _ptr(v1), len(w1), _ptr(w2), _ptr(v2), len(w2),
+                                                ctypes.byref(out)), "orbx_bow_score")
+        return out.value
+
+    def transform_batch_device(self, n_frames: int, d_desc, d_n, d_bow_word, d_bow_value, d_bow_n, d_fv_node=None, d_fv_feat=None,
+                               d_fv_n=None, d_feat_word=None, levelsup: int = 4, capacity: Optional[int] = None) -> None:
+        """Batched and device-resident (device pointers or torch tensors), the layout of extract_batch_device: d_desc uint8
+        [n_frames, capacity, 32], d_n int32 [n_frames]; outputs d_bow_word uint32 / d_bow_value float64 / d_fv_node, d_fv_feat
+        uint32 / d_feat_word uint32, all [n_frames, capacity], d_bow_n / d_fv_n int32 [n_frames]; d_fv_* (all three or none) and
+        d_feat_word optional.  Stream-ordered on the context's stream: the outputs are valid after a device synchronisation."""
+        cap, nf = int(capacity or self._ext.capacity), int(n_frames)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the word array", d_bow_word, nf * cap * 4)
+        _need("the value array", d_bow_value, nf * cap * 8)
+        _need("the BowVector count array", d_bow_n, nf * 4)
+        if (d_fv_node is None) != (d_fv_feat is None) or (d_fv_node is None) != (d_fv_n is None):
+            raise OrbxError(E_BADARG, "d_fv_node, d_fv_feat and d_fv_n go together")
+        if d_fv_node is not None:
+            _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
+            _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
+            _need("the FeatureVector count array", d_fv_n, nf * 4)
+        if d_feat_word is not None:
+            _need("the feature word array", d_feat_word, nf * cap * 4)
+        self._ext._order_torch(d_desc, d_n, d_bow_word, d_bow_value, d_bow_n, d_fv_node, d_fv_feat, d_fv_n, d_feat_word)
+        self._ext._check(self._L.orbx_bow_transform_batch_device(self._ext._h, self._h, nf, _ptr(d_desc), _ptr(d_n), cap, int(levelsup),
+                                                                 _ptr(d_bow_word), _ptr(d_bow_value), _ptr(d_bow_n), _ptr(d_fv_node),
+                                                                 _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_feat_word)),
+                         "orbx_bow_transform_batch_device")
+
+    def score_pairs_device(self, n_frames: int, first, second, d_bow_word, d_bow_value, d_bow_n, d_score,
+                           capacity: Optional[int] = None) -> None:
+        """L1Scoring::score of frame first[p] vs second[p] (host index arrays) of transform_batch_device's BowVectors (same
+        capacity) into d_score float64 [n_pairs].  Stream-ordered like the transform."""
+        first = np.ascontiguousarray(first, np.int32).reshape(-1)
+        second = np.ascontiguousarray(second, np.int32).reshape(-1)
+        if len(first) != len(second):
+            raise OrbxError(E_BADARG, "first and second must have the same length")
+        cap, nf, P = int(capacity or self._ext.capacity), int(n_frames), len(first)
+        _need("the word array", d_bow_word, nf * cap * 4)
+        _need("the value array", d_bow_value, nf * cap * 8)
+        _need("the BowVector count array", d_bow_n, nf * 4)
+        _need("the score array", d_score, P * 8)
+        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n, d_score)
+        self._ext._check(self._L.orbx_bow_score_batch_device(self._ext._h, self._h, nf, P, _ptr(first), _ptr(second), _ptr(d_bow_word),
+                                                             _ptr(d_bow_value), _ptr(d_bow_n), cap, _ptr(d_score)),
+                         "orbx_bow_score_batch_device")
+
+
 class Frame:
     """The slice of SlamTypes/Frame.{hpp,cpp} on this path: runs the extractor (Frame.cpp:58-60), undistorts the
     keypoints (Frame.cpp:136-161) and keeps mvKeys / mvKeysUn / mDescriptors / N and the image bounds
-    (Frame.cpp:101-134).  K / distCoef = None means no distortion (mvKeysUn = mvKeys, bounds = the image)."""
+    (Frame.cpp:101-134).  K / distCoef = None means no distortion (mvKeysUn = mvKeys, bounds = the image).  voc
+    (mpORBvocabulary) is what ComputeBoW transforms with."""
 
-    def __init__(self, im: np.ndarray, timestamp: float, extractor: ORBextractor, K=None, distCoef=None):
+    def __init__(self, im: np.ndarray, timestamp: float, extractor: ORBextractor, K=None, distCoef=None, voc: Optional[Vocabulary] = None):
         self.mTimestamp = timestamp
         self.mpORBextractor = extractor
+        self.mpORBvocabulary = voc
+        self.mBowVec, self.mFeatVec = {}, {}
         h, w = im.shape
         self.camera = camera_from(K, distCoef) if K is not None and distCoef is not None else None
         if self.camera is not None:
@@ -915,14 +1075,30 @@ class Frame:
         self.N = len(self.mvKeysUn)
 
     @classmethod
-    def from_arrays(cls, keys: np.ndarray, descriptors: np.ndarray, bounds: Tuple[int, int, int, int]) -> "Frame":
+    def from_arrays(cls, keys: np.ndarray, descriptors: np.ndarray, bounds: Tuple[int, int, int, int],
+                    voc: Optional[Vocabulary] = None) -> "Frame":
         f = cls.__new__(cls)
         f.mTimestamp, f.mpORBextractor = 0.0, None
+        f.mpORBvocabulary, f.mBowVec, f.mFeatVec = voc, {}, {}
         f.mvKeys = f.mvKeysUn = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
         f.mDescriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
         f.N = len(f.mvKeysUn)
         f.bounds = tuple(int(v) for v in bounds)
         return f
+
+    def ComputeBoW(self, levelsup: int = 4) -> None:
+        """Frame::ComputeBoW: once, mBowVec {word id: value} and mFeatVec {node id: [feature indices]}, both in ascending key
+        order, from mDescriptors with mpORBvocabulary (transform(..., mBowVec, mFeatVec, 4))."""
+        if self.mBowVec:
+            return
+        if self.mpORBvocabulary is None:
+            raise OrbxError(E_BADARG, "Frame.ComputeBoW needs a vocabulary (Frame(..., voc=))")
+        r = self.mpORBvocabulary.transform(self.mDescriptors, levelsup)
+        self.mBowVec = {int(w): float(v) for w, v in zip(r.bow_word, r.bow_value)}
+        fv = {}
+        for node, feat in zip(r.fv_node.tolist(), r.fv_feat.tolist()):
+            fv.setdefault(node, []).append(feat)
+        self.mFeatVec = fv
 
 
 class ORBmatcher:

@@ -3042,3 +3042,15 @@ int orbx_debug_std_sort(orbx_ctx* ctx, int32_t* triples, int n) {
 }
 
 }  // extern "C"
+
+// ---- what orbx_bow.cpp needs of a context (orbx_ctx is private to this file) ----------------------
+namespace orbx {
+int ctxDevice(const orbx_ctx* c) { return c->device; }
+hipStream_t ctxStream(const orbx_ctx* c) { return c->st; }
+// the context's device made current and every batch issued with the _async calls waited for (they may still be writing the inputs)
+int ctxDrain(orbx_ctx* c) {
+  if (hipSetDevice(c->device) != hipSuccess) return ORBX_E_HIP;
+  return waitAll(c);
+}
+void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
+}  // namespace orbx

@@ -395,4 +395,49 @@ inline long long matchScratchStride(int capacity) {
   return (s + 3) & ~3LL;  // the train records are uint4
 }
 
+// ---- DBoW2 TemplatedVocabulary::transform / L1Scoring::score (orbx_bow_kernel.hip) ----
+// One vocabulary node in breadth-first order: a node's children are the contiguous range [first, first + nChild).
+struct BowNode {
+  int32_t first;   // breadth-first index of the first child (0 when nChild == 0)
+  int32_t nChild;  // 0 = isLeaf() (DBoW2: "has no children", not the file's leaf flag)
+  uint32_t word;   // word id (0 for a node the file does not flag as a leaf, as the reference's Node())
+  uint32_t id;     // the loader's node id (root 0, then the file's lines 1, 2, ...)
+  double weight;
+};
+static_assert(sizeof(BowNode) == 24, "BowNode layout");
+constexpr int BOW_MAX_FEATURES = 16384;  // keypoints per frame (ORBX_E_CAPACITY above)
+constexpr int BOW_LDS_NODES = 1152;      // breadth-first prefix of descriptors k_bow_descend stages in LDS (36 KB: levels 0-3 at k = 10)
+constexpr int BOW_DESCEND_THREADS = 512;
+constexpr int BOW_ASSEMBLE_THREADS = 1024;
+constexpr int BOW_SCORE_WAVES = 4;  // pairs (one wave each) per k_bow_score_l1 workgroup
+struct BowArgs {
+  const BowNode* nodes;   // [nNodes + 1] breadth-first
+  const uint32_t* desc;   // [nNodes + 1][8] breadth-first, 32-byte aligned
+  int32_t nStaged;        // breadth-first nodes whose descriptors k_bow_descend stages in LDS
+  int32_t nidLevel;       // L - levelsup
+  const uint8_t* fdesc;   // [nFrames][cap][32]
+  const int32_t* n;       // [nFrames] (clamped to [0, cap])
+  int32_t cap, nFrames;
+  uint32_t* fin;          // scratch [nFrames][cap]: breadth-first index of the node the descent ended at
+  uint32_t* nid;          // scratch [nFrames][cap]: node id at depth nidLevel (FeatureVector)
+  int32_t weighting;      // 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY
+  int32_t norm;           // 0 none (DOT_PRODUCT), 1 L1, 2 L2
+  int32_t hasWords;       // 0: the vocabulary is empty(), both vectors are empty
+  uint32_t* bowWord;      // [nFrames][cap]
+  double* bowValue;       // [nFrames][cap]
+  int32_t* bowN;          // [nFrames]
+  uint32_t* fvNode;       // nullable [nFrames][cap]
+  uint32_t* fvFeat;       // nullable [nFrames][cap]
+  int32_t* fvN;           // nullable [nFrames]
+  uint32_t* featWord;     // nullable [nFrames][cap]
+};
+struct BowScoreArgs {
+  const uint32_t* word;   // [frames][cap]
+  const double* value;    // [frames][cap]
+  const int32_t* n;       // [frames] (clamped to [0, cap])
+  int32_t cap, nPairs;
+  const int32_t* pairs;   // [2][nPairs] first frames, then second frames
+  double* score;          // [nPairs]
+};
+
 }  // namespace orbx

@@ -1,0 +1,267 @@
+"""DBoW2's transform (BowVector, FeatureVector) and L1 score on the device (orbx_bow_*): every case equals the CPU restatement
+(tests/cpp/bow_ref.cpp) bit for bit -- word ids, node ids, feature indices and the bytes of every f64."""
+import numpy as np
+import pytest
+
+import bow_ref_lib as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ext(orbx):
+    e = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def golden_desc(golden):
+    return [golden["canonical/%s/desc" % k] for k in ("dbow0", "dbow1", "dbow2", "dbow3", "init0", "init1")] + \
+           [golden["as_shipped/init0/desc"], golden["as_shipped/init1/desc"]]
+
+
+@pytest.fixture(scope="module")
+def full(golden_desc):
+    """The full k = 10, L = 6 vocabulary (1,111,110 nodes) grown from the golden frames' descriptors."""
+    return R.full_vocabulary(np.concatenate(golden_desc), k=10, L=6, seed=7)
+
+
+@pytest.fixture(scope="module")
+def dev_full(orbx, ext, full):
+    v = orbx.Vocabulary.from_arrays(ext, *full.arrays())
+    yield v
+    v.close()
+
+
+def _same(dev, ref, fv=True, feat_word=False):
+    assert np.array_equal(dev.bow_word, ref["bow_word"]), "BowVector words differ"
+    assert dev.bow_value.tobytes() == ref["bow_value"].tobytes(), "BowVector values differ"
+    if fv:
+        assert np.array_equal(dev.fv_node, ref["fv_node"]), "FeatureVector nodes differ"
+        assert np.array_equal(dev.fv_feat, ref["fv_feat"]), "FeatureVector features differ"
+    if feat_word:
+        assert np.array_equal(dev.feat_word, ref["feat_word"])
+
+
+def test_full_vocabulary_golden_frames(dev_full, full, golden_desc):
+    assert (dev_full.k, dev_full.L, dev_full.n_nodes, dev_full.n_words) == (10, 6, 1111110, 10 ** 6)
+    for d in golden_desc:
+        ref = full.transform(d, 4)
+        assert len(ref["bow_word"]) > 0.5 * len(d)  # the descriptors spread over many words
+        _same(dev_full.transform(d, 4, feat_word=True), ref, feat_word=True)
+
+
+def test_full_vocabulary_types(orbx, ext, full, golden_desc):
+    d = golden_desc[0]
+    for scoring, weighting in ((1, 1), (5, 0), (5, 2), (3, 3)):
+        ref = full.with_types(scoring, weighting)
+        v = orbx.Vocabulary.from_arrays(ext, *ref.arrays())
+        _same(v.transform(d, 2), ref.transform(d, 2))
+        v.close()
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_irregular_trees_all_types_and_levelsup(orbx, ext, seed):
+    base = R.irregular_tree(seed, k=2 + seed % 5, L=3 + seed % 4, n_nodes=150 + 60 * seed)
+    feats = R.features_near(base, 500, seed + 100)
+    for scoring in range(6):
+        for weighting in range(4):
+            ref = base.with_types(scoring, weighting)
+            v = orbx.Vocabulary.from_arrays(ext, *ref.arrays())
+            for levelsup in range(0, ref.header[1] + 2):
+                _same(v.transform(feats, levelsup, feat_word=True), ref.transform(feats, levelsup), feat_word=True)
+            v.close()
+
+
+def test_text_file_equals_arrays(orbx, ext, tmp_path, full, dev_full, golden_desc):
+    small = R.irregular_tree(11, k=5, L=4, n_nodes=400, scoring=0, weighting=0)
+    for voc, name in ((small, "small"), (full, "full")):
+        path = str(tmp_path / ("%s.txt" % name))
+        R.write_text(path, voc, trailing_newline=True, exact=True)
+        vt = orbx.Vocabulary.from_text(ext, path)
+        va = dev_full if voc is full else orbx.Vocabulary.from_arrays(ext, *voc.arrays())
+        assert (vt.n_nodes, vt.n_words) == (va.n_nodes, va.n_words)
+        for d in golden_desc[:2]:
+            a, b = vt.transform(d, 3, feat_word=True), va.transform(d, 3, feat_word=True)
+            for x, y in zip(a, b):
+                assert x.tobytes() == y.tobytes()
+        vt.close()
+
+
+def test_empty_cases(orbx, ext, full, dev_full):
+    r = dev_full.transform(np.zeros((0, 32), np.uint8), 4, feat_word=True)
+    assert len(r.bow_word) == 0 and len(r.fv_node) == 0 and len(r.feat_word) == 0
+    nowords = R.irregular_tree(4, k=3, L=3, n_nodes=30)
+    nowords.is_leaf[:] = 0
+    ref = R.Voc(*nowords.arrays())
+    v = orbx.Vocabulary.from_arrays(ext, *ref.arrays())
+    assert v.n_words == 0
+    feats = R.features_near(ref, 50, 3)
+    r = v.transform(feats, 2, feat_word=True)
+    assert len(r.bow_word) == 0 and len(r.fv_node) == 0
+    _same(r, ref.transform(feats, 2), feat_word=True)
+    v.close()
+
+
+def test_largest_frame(dev_full, full, orbx):
+    d = R.features_near(full, orbx.BOW_MAX_FEATURES, 21, ands=4)
+    _same(dev_full.transform(d, 4), full.transform(d, 4))
+    with pytest.raises(orbx.OrbxError) as e:
+        dev_full.transform(np.zeros((orbx.BOW_MAX_FEATURES + 1, 32), np.uint8))
+    assert e.value.code == orbx.E_CAPACITY
+
+
+def _bow_buffers(torch, B, cap, fv=True, fw=True):
+    z = lambda dt: torch.zeros(B * cap, dtype=dt, device="cuda")  # noqa: E731
+    out = dict(d_bow_word=z(torch.int32), d_bow_value=z(torch.float64), d_bow_n=torch.zeros(B, dtype=torch.int32, device="cuda"))
+    if fv:
+        out.update(d_fv_node=z(torch.int32), d_fv_feat=z(torch.int32), d_fv_n=torch.zeros(B, dtype=torch.int32, device="cuda"))
+    if fw:
+        out["d_feat_word"] = z(torch.int32)
+    return out
+
+
+def _frame(buf, f, cap):
+    bn = int(buf["d_bow_n"][f])
+    w = buf["d_bow_word"].cpu().numpy().view(np.uint32).reshape(-1, cap)[f, :bn]
+    v = buf["d_bow_value"].cpu().numpy().reshape(-1, cap)[f, :bn]
+    out = dict(bow_word=w, bow_value=v)
+    if "d_fv_n" in buf:
+        fn = int(buf["d_fv_n"][f])
+        out["fv_node"] = buf["d_fv_node"].cpu().numpy().view(np.uint32).reshape(-1, cap)[f, :fn]
+        out["fv_feat"] = buf["d_fv_feat"].cpu().numpy().view(np.uint32).reshape(-1, cap)[f, :fn]
+    return out
+
+
+def test_batch_from_extractor_in_hbm(orbx, full, dev_full):
+    """256 synthetic frames: orbx_extract_batch_device, then the transform on the same device arrays, no host copy between;
+    every frame equals the restatement, and the batch equals single calls; NULL FeatureVector / word outputs change nothing."""
+    torch = pytest.importorskip("torch")
+    from orb_slam_tracking_amd import synth
+    B, w, h = 256, 640, 480
+    e = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=B)
+    voc = orbx.Vocabulary.from_arrays(e, *full.arrays())
+    cap = e.capacity
+    frames = synth.synth_frames(B, w, h, 4242)
+    d_img = torch.from_numpy(frames).cuda()
+    d_k = torch.zeros(B * cap * 28, dtype=torch.uint8, device="cuda")
+    d_d = torch.zeros(B * cap * 32, dtype=torch.uint8, device="cuda")
+    d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
+    e.extract_batch_device(d_img, B, w, h, w, w * h, d_k, d_d, d_n, cap)
+    buf = _bow_buffers(torch, B, cap)
+    voc.transform_batch_device(B, d_d, d_n, levelsup=4, capacity=cap, **buf)
+    bare = _bow_buffers(torch, B, cap, fv=False, fw=False)
+    voc.transform_batch_device(B, d_d, d_n, levelsup=4, capacity=cap, **bare)
+    torch.cuda.synchronize()
+    n = d_n.cpu().numpy()
+    dd = d_d.cpu().numpy().reshape(B, cap, 32)
+    fw = buf["d_feat_word"].cpu().numpy().view(np.uint32).reshape(B, cap)
+    assert n.min() > 500
+    for f in range(B):
+        ref = full.transform(dd[f, :n[f]], 4)
+        got = _frame(buf, f, cap)
+        for key in ("bow_word", "fv_node", "fv_feat"):
+            assert np.array_equal(got[key], ref[key]), (f, key)
+        assert got["bow_value"].tobytes() == ref["bow_value"].tobytes(), f
+        assert np.array_equal(fw[f, :n[f]], ref["feat_word"]), f
+        g2 = _frame(bare, f, cap)
+        assert np.array_equal(g2["bow_word"], got["bow_word"]) and g2["bow_value"].tobytes() == got["bow_value"].tobytes()
+        assert int(bare["d_bow_n"][f]) == len(ref["bow_word"])
+    for f in (0, 77, 255):  # the batch against single calls
+        single = voc.transform(dd[f, :n[f]], 4, feat_word=True)
+        _same(single, full.transform(dd[f, :n[f]], 4), feat_word=True)
+    voc.close()
+    e.close()
+
+
+def test_counts_clamped(orbx, ext, torch_or_skip, full, dev_full):
+    """Counts above capacity read as capacity, negative ones as 0, zero-keypoint frames give empty vectors."""
+    torch = torch_or_skip
+    cap, B = 64, 4
+    d = R.features_near(full, B * cap, 5).reshape(B, cap, 32)
+    d_d = torch.from_numpy(np.ascontiguousarray(d)).cuda()
+    d_n = torch.tensor([cap, cap + 100, -3, 0], dtype=torch.int32, device="cuda")
+    buf = _bow_buffers(torch, B, cap)
+    dev_full.transform_batch_device(B, d_d, d_n, levelsup=4, capacity=cap, **buf)
+    torch.cuda.synchronize()
+    for f, m in ((0, cap), (1, cap), (2, 0), (3, 0)):
+        ref = full.transform(d[f, :m], 4)
+        got = _frame(buf, f, cap)
+        for key in ("bow_word", "fv_node", "fv_feat"):
+            assert np.array_equal(got[key], ref[key]), (f, key)
+        assert got["bow_value"].tobytes() == ref["bow_value"].tobytes()
+
+
+@pytest.fixture
+def torch_or_skip():
+    return pytest.importorskip("torch")
+
+
+def test_frame_compute_bow(orbx, ext, images, full, dev_full):
+    f = orbx.Frame(images["dbow0"], 0.0, ext, voc=dev_full)
+    f.ComputeBoW()
+    ref = full.transform(f.mDescriptors, 4)
+    assert list(f.mBowVec.keys()) == [int(w) for w in ref["bow_word"]]
+    assert np.array(list(f.mBowVec.values())).tobytes() == ref["bow_value"].tobytes()
+    flat = [(nd, i) for nd, idx in f.mFeatVec.items() for i in idx]
+    assert flat == list(zip(ref["fv_node"].tolist(), ref["fv_feat"].tolist()))
+    assert list(f.mFeatVec.keys()) == sorted(f.mFeatVec.keys())
+
+
+def test_l1_scores(orbx, ext, torch_or_skip, full, dev_full, golden_desc):
+    torch = torch_or_skip
+    cap, B = 2048, 16
+    rng = np.random.default_rng(9)
+    frames = [golden_desc[i % len(golden_desc)][: rng.integers(100, 1000)] for i in range(B - 2)]
+    frames.append(R.features_near(full, 300, 77))
+    frames.append(np.zeros((0, 32), np.uint8))
+    d = np.zeros((B, cap, 32), np.uint8)
+    n = np.zeros(B, np.int32)
+    for i, fr in enumerate(frames):
+        d[i, :len(fr)] = fr
+        n[i] = len(fr)
+    d_d, d_n = torch.from_numpy(d).cuda(), torch.from_numpy(n).cuda()
+    buf = _bow_buffers(torch, B, cap, fv=False, fw=False)
+    dev_full.transform_batch_device(B, d_d, d_n, levelsup=4, capacity=cap, **buf)
+    first = rng.integers(0, B, 128).astype(np.int32)
+    second = rng.integers(0, B, 128).astype(np.int32)
+    first[:3], second[:3] = (0, B - 1, 3), (0, 2, 3)  # a self-pair, a pair with an empty frame, another self-pair
+    d_s = torch.zeros(128, dtype=torch.float64, device="cuda")
+    dev_full.score_pairs_device(B, first, second, buf["d_bow_word"], buf["d_bow_value"], buf["d_bow_n"], d_s, capacity=cap)
+    torch.cuda.synchronize()
+    s = d_s.cpu().numpy()
+    vec = [_frame(buf, f, cap) for f in range(B)]
+    for p in range(128):
+        a, b = vec[first[p]], vec[second[p]]
+        ref = R.score_l1(a["bow_word"], a["bow_value"], b["bow_word"], b["bow_value"])
+        assert np.float64(s[p]).tobytes() == np.float64(ref).tobytes(), p
+    assert s[1] == 0.0
+    # no common word
+    w1, v1 = np.array([1, 5, 9], np.uint32), np.array([0.2, 0.3, 0.5])
+    w2, v2 = np.array([2, 6], np.uint32), np.array([0.5, 0.5])
+    assert dev_full.score(w1, v1, w2, v2) == R.score_l1(w1, v1, w2, v2) == 0.0
+    a = vec[0]
+    assert np.float64(dev_full.score(a["bow_word"], a["bow_value"], a["bow_word"], a["bow_value"])).tobytes() == \
+        np.float64(R.score_l1(a["bow_word"], a["bow_value"], a["bow_word"], a["bow_value"])).tobytes()
+
+
+def test_score_refusals(orbx, ext, torch_or_skip, dev_full):
+    """Pair indices outside [0, n_frames) and scorings other than L1 are refused before any launch."""
+    torch = torch_or_skip
+    cap, B = 16, 2
+    buf = _bow_buffers(torch, B, cap, fv=False, fw=False)
+    d_s = torch.full((2,), 7.0, dtype=torch.float64, device="cuda")
+    for first, second in (([0, 2], [1, 1]), ([0, 1], [-1, 0])):
+        with pytest.raises(orbx.OrbxError) as e:
+            dev_full.score_pairs_device(B, np.array(first), np.array(second), buf["d_bow_word"], buf["d_bow_value"], buf["d_bow_n"], d_s,
+                                        capacity=cap)
+        assert e.value.code == orbx.E_BADARG
+    torch.cuda.synchronize()
+    assert d_s.cpu().numpy().tolist() == [7.0, 7.0]
+    l2 = R.irregular_tree(1, k=3, L=3, n_nodes=20, scoring=1)
+    v = orbx.Vocabulary.from_arrays(ext, *l2.arrays())
+    with pytest.raises(orbx.OrbxError) as e:
+        v.score(np.array([1], np.uint32), np.array([1.0]), np.array([1], np.uint32), np.array([1.0]))
+    assert e.value.code == orbx.E_BADARG
+    v.close()
