@@ -180,7 +180,10 @@ int orbx_download_pyramid(orbx_ctx* ctx, int frame, int level, int border, uint8
  * the 64x48 grid of F2 is rebuilt inside with Frame::PosInGrid's rule (Frame.cpp:89-99), so callers
  * do not pass mGrid.  matches12 has n1 entries (-1 = none).  *nmatches receives the reference's return value
  * exactly as it computes it (its double-decrement quirk can make it differ from the number of non-negative
- * entries, even negative), which is why it is an out-parameter; the function returns ORBX_OK or an error. */
+ * entries, even negative), which is why it is an out-parameter; the function returns ORBX_OK or an error.
+ * A query keypoint with a NEGATIVE octave (ORBextractor never produces one) is matched against F2's keypoints of EVERY
+ * octave, as the reference's GetFeaturesInArea(.., octave, octave) skips its level check for a negative level (Frame.cpp:179);
+ * a query of octave 0 against F2's octave-0 keypoints.  Pinned to the reference's compiled matcher (tests/test_gpu_ref_pins.py). */
 int orbx_match_init(orbx_ctx* ctx, const orbx_keypoint* k1, const uint8_t* d1, int n1, const orbx_keypoint* k2,
                     const uint8_t* d2, int n2, const orbx_bounds* bounds, int window_size, float nnratio,
                     int check_orientation, int32_t* matches12, int32_t* nmatches, orbx_match_stats* stats);
@@ -434,7 +437,12 @@ int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)
- * Bit-identical to a CPU restatement of those lines: word ids, node ids, feature indices and the bytes of every f64.
+ * Bit-identical to a CPU restatement of those lines (tests/cpp/bow_ref.cpp): word ids, node ids, feature indices and the bytes
+ * of every f64.  PINNED to the reference's own compiled code: the restatement is compared bit for bit with DBoW2's own
+ * loadFromTextFile / transform / scoring objects (built unmodified into oracle/_ref/libref.so; tests/test_ref_pins.py), and the
+ * device directly with them (tests/test_gpu_ref_pins.py), for every weighting x scoring and levelsup 0 .. L + 1; so is this
+ * library's text parser (orbx_vocabulary_parse_text) against loadFromTextFile.  Not compared where the reference is undefined:
+ * deviations 1 and 2 below, k < 2, trees beyond the k^(L+1) nodes the loader reserves, and what deviation 3 refuses.
  *   node ids      the loader's (:1542-1620): root 0, the file's node lines 1, 2, ... in order; children in file order; word ids in
  *                 file order to the lines whose leaf flag is > 0
  *   descent       at each level the child with the smallest Hamming distance, the first child on a tie; it ends at a node WITHOUT
@@ -455,10 +463,17 @@ int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_
  *      leaf's own node id.
  *   3. Refused inputs (ORBX_E_BADARG; the reference accepts them with UB, or prints a message and keeps an empty vocabulary): a
  *      parent id outside [0, the line's own id); a node with more than k children; a node deeper than L; a header outside
- *      k 0..20, L 1..10, scoring 0..5, weighting 0..3; a node line with fewer than 35 numbers.
+ *      k 0..20, L 1..10, scoring 0..5, weighting 0..3; a node line with fewer than 35 numbers; a number followed directly
+ *      by other characters; an int outside int's range; a weight token that is not one complete finite decimal number
+ *      [+-]?(d+(.d*)?|.d+)([eE][+-]?d+)?, where the reference's `istream >> double` reads, without an error it checks: inf, nan
+ *      and other tokens without a number (0), a hexadecimal float such as 0x1p3 (its leading 0), a number with trailing
+ *      characters such as 1e5x (the number), an overflow such as 1e400 (+-DBL_MAX).
  *   4. Scores: only L1Scoring::score (scoring L1_NORM) is offered; the score entry point returns ORBX_E_BADARG for the other five
  *      scoring types.  transform supports all four weightings and both norms.
- * Descriptor elements are parsed as int and cast to uint8, weights as double (strtod, the rounding of istream >> double).
+ * Descriptor elements are parsed as int and cast to uint8 (an explicit sign, a leading zero and values outside a byte as the
+ * reference reads them: +7 -> 7, 07 -> 7, 300 -> 44, -1 -> 255), weights as double (strtod on the whole token, which is what
+ * istream >> double computes for the tokens accepted: underflow to 0 or a denormal, -0 and 6- or 17-digit forms included).
+ * CRLF line ends and tokens after the weight are accepted and ignored, as by the reference.
  * A frame may hold up to ORBX_BOW_MAX_FEATURES keypoints: a larger capacity returns ORBX_E_CAPACITY. */
 #define ORBX_BOW_MAX_FEATURES 16384
 #define ORBX_BOW_TF_IDF 0 /* WeightingType */

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -89,13 +90,35 @@ bool parseInt(const char** s, int* out) {
   return true;
 }
 
+// istream >> double on one whitespace-separated token that is a complete finite decimal number, [+-]? (d+ (.d*)? | .d+)
+// ([eE] [+-]? d+)?: for those, libstdc++'s num_get hands exactly the token to strtod, so the value is strtod's.  Refused
+// (deviation 3), because the reference reads them without a reported error into another value: no number (inf, nan, "1e": 0),
+// a hexadecimal float (its leading 0), trailing characters (the number before them) and an overflow (+-DBL_MAX).
 bool parseDouble(const char** s, double* out) {
   const char* p = *s;
   while (*p && isspace((unsigned char)*p)) p++;
-  if (!*p) return false;
+  const char* q = p;
+  if (*q == '+' || *q == '-') q++;
+  const char* mant = q;
+  while (isdigit((unsigned char)*q)) q++;
+  bool digits = q != mant;
+  if (*q == '.') {
+    const char* frac = ++q;
+    while (isdigit((unsigned char)*q)) q++;
+    digits = digits || q != frac;
+  }
+  if (!digits) return false;
+  if (*q == 'e' || *q == 'E') {
+    q++;
+    if (*q == '+' || *q == '-') q++;
+    const char* exp = q;
+    while (isdigit((unsigned char)*q)) q++;
+    if (q == exp) return false;
+  }
+  if (*q && !isspace((unsigned char)*q)) return false;
   char* end = nullptr;
   const double v = strtod(p, &end);
-  if (end == p || (*end && !isspace((unsigned char)*end))) return false;
+  if (end != q || std::isinf(v)) return false;
   *out = v;
   *s = end;
   return true;

@@ -1574,7 +1574,7 @@ __device__ void matchWidePrep(const int pair, const int* __restrict__ pairFirst,
                               const orbx_keypoint* __restrict__ kps, const int* __restrict__ nkp, const MatchParams& mp,
                               int* __restrict__ matches12, int* __restrict__ scratch, long long scratchStride, int capl) {
   __shared__ int wq[T / 64], wt[T / 64];
-  __shared__ int sBaseQ, sBaseT;
+  __shared__ int sBaseQ, sBaseT, sNegQ;
   __shared__ int colT[ORBX_GRID_COLS + 1], colQ[ORBX_GRID_COLS + 1];  // per grid column: count, then start / fill position
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fa = pairFirst[pair], fb = pairSecond[pair];
@@ -1599,7 +1599,7 @@ __device__ void matchWidePrep(const int pair, const int* __restrict__ pairFirst,
   const float wInv = (float)ORBX_GRID_COLS / (float)(mp.b.max_x - mp.b.min_x);  // Frame.cpp:46-47
   const float hInv = (float)ORBX_GRID_ROWS / (float)(mp.b.max_y - mp.b.min_y);
   const float fminX = (float)mp.b.min_x, fminY = (float)mp.b.min_y;
-  if (t == 0) { sBaseQ = 0; sBaseT = 0; }
+  if (t == 0) { sBaseQ = 0; sBaseT = 0; sNegQ = 0; }
   __syncthreads();
   const int n = max(n1, n2);
   // bounding box of the eligible trains (header [4..7]): lets k_match_wide_lists recognise the brute-force case -- a window that
@@ -1614,6 +1614,7 @@ __device__ void matchWidePrep(const int pair, const int* __restrict__ pairFirst,
     if (i < n1) {
       const orbx_keypoint kq = k1[i];
       okQ = !(kq.octave > 0);  // ORBmatcher.cpp:38-39
+      if (kq.octave < 0) sNegQ = 1;  // its candidates are not the staged octave-0 trains (see matchGeneral)
       qc = min(max((int)floorf((kq.x - fminX) * wInv), 0), ORBX_GRID_COLS - 1);  // the query's own column (an ordering aid only)
       m12[i] = -1;
     }
@@ -1668,7 +1669,7 @@ __device__ void matchWidePrep(const int pair, const int* __restrict__ pairFirst,
   }
   if (t == 0) {
     S[0] = sBaseQ; S[1] = sBaseT;
-    S[2] = (sBaseQ > capl || sBaseT > capl || n2 > 0xfffff) ? 1 : 0;
+    S[2] = (sBaseQ > capl || sBaseT > capl || n2 > 0xfffff || sNegQ) ? 1 : 0;
     S[3] = 0;
     S[8] = byCol ? 1 : 0;
     S[9] = 0; S[10] = 0;  // k_match_bf_mfma's mask of the 64-query blocks it has listed
@@ -1742,7 +1743,7 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
   __shared__ uint8_t pCnt[MJ_P][MJ_CAP];                 // per part: candidates listed for the query
   __shared__ int hist[HISTO_LENGTH];
   __shared__ int sChangedSw[MJ_SWEEPS];
-  __shared__ int sNT, sBase, sOverflow, sNm, sBadDist, sBadRatio, sBadOri, sKeep[3], sKeepV[3];
+  __shared__ int sNT, sBase, sOverflow, sNegQ, sNm, sBadDist, sBadRatio, sBadOri, sKeep[3], sKeepV[3];
   __shared__ int sTooMany[2];  // per parity of the train-staging chunk: more than MJ_CAP eligible trains so far
   __shared__ int wcnt[MJ_T / 64];
 
@@ -1761,7 +1762,7 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
   const float wInv = (float)ORBX_GRID_COLS / (float)(mp.b.max_x - mp.b.min_x);  // Frame.cpp:46-47
   const float hInv = (float)ORBX_GRID_ROWS / (float)(mp.b.max_y - mp.b.min_y);
   const float fminX = (float)mp.b.min_x, fminY = (float)mp.b.min_y;
-  if (t == 0) { sNT = 0; sBase = 0; sOverflow = n2 > 65535 ? 1 : 0; sNm = 0; sBadDist = 0; sBadRatio = 0; sBadOri = 0; sTooMany[0] = 0; sTooMany[1] = 0; }
+  if (t == 0) { sNT = 0; sBase = 0; sOverflow = n2 > 65535 ? 1 : 0; sNegQ = 0; sNm = 0; sBadDist = 0; sBadRatio = 0; sBadOri = 0; sTooMany[0] = 0; sTooMany[1] = 0; }
   if (t < 3) { sKeep[t] = -1; sKeepV[t] = 0; }
   if (t < MJ_SWEEPS) sChangedSw[t] = 0;
   if (t < HISTO_LENGTH) hist[t] = 0;
@@ -1832,6 +1833,7 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     }
     if (i < n1) {
       ok = !(kq.octave > 0);  // ORBmatcher.cpp:38-39
+      if (kq.octave < 0) sNegQ = 1;  // its candidates are not the staged octave-0 trains (see matchGeneral)
       m12[i] = -1;
     }
     const unsigned long long bm = __ballot(ok);
@@ -1855,7 +1857,8 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
     __syncthreads();
   }
   const int nQ = sBase, nT = sNT;
-  if (nQ > MJ_CAP || nT > MJ_CAP || sOverflow) {  // block-uniform: the pair goes to the wide path
+  if (nQ > MJ_CAP || nT > MJ_CAP || sOverflow || sNegQ) {  // block-uniform: the pair goes to the wide path (and from there, with
+    // a negative-octave query, to matchGeneral)
     if (t == 0) { nmatchesOut[pair] = MATCH_PENDING; *hostWide = 1; }  // (mapped host memory: the batch needs the wide path)
     matchWidePrep<MJ_T>(pair, pairFirst, pairSecond, kps, nkp, mp, matches12, scratch, scratchStride, capl);
     return;
@@ -2073,8 +2076,10 @@ __global__ __launch_bounds__(MJ_CAP * MJ_P) void k_match_jacobi(const int* __res
 // -------------------------------------------------------------------------------------------------
 // matchGeneral: the reference's loop as written - queries one after the other, the workgroup's threads share the trains
 // of one query (any size; vMatchedDistance, vnMatches21 and the rotation bins in the pair's global scratch).  Run by the
-// workgroup of k_match_wide_resolve for a pair the parallel paths cannot take.  Every thread must call it.
+// workgroup of k_match_wide_resolve for a pair the parallel paths cannot take, and for every pair with a query of negative
+// octave (its candidates are the trains of every octave, not the staged octave-0 ones).  Every thread must call it.
 // -------------------------------------------------------------------------------------------------
+#define NOT_OCT0 (1 << 30)  // matchGeneral's cell2: the train's octave is not 0
 template <int T>
 __device__ void matchGeneral(const int pair, const int* __restrict__ pairFirst, const int* __restrict__ pairSecond,
                              const orbx_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
@@ -2098,7 +2103,7 @@ __device__ void matchGeneral(const int pair, const int* __restrict__ pairFirst, 
   int* md = scratch + (long long)pair * scratchStride;  // vMatchedDistance (the pair's scratch holds >= 4 * cap ints)
   int* m21 = md + cap;                            // vnMatches21
   int* accBin = m21 + cap;                        // rotation bin of every accepted query (rotHist membership)
-  int* cell2 = accBin + cap;                      // F2 grid cell (cx*48+cy) of every eligible train, -1 otherwise
+  int* cell2 = accBin + cap;                      // F2 grid cell (cx*48+cy) of every train in the grid, -1 otherwise; | NOT_OCT0
 
   const float wInv = (float)ORBX_GRID_COLS / (float)(mp.b.max_x - mp.b.min_x);  // Frame.cpp:46-47
   const float hInv = (float)ORBX_GRID_ROWS / (float)(mp.b.max_y - mp.b.min_y);
@@ -2107,10 +2112,10 @@ __device__ void matchGeneral(const int pair, const int* __restrict__ pairFirst, 
     md[j] = INF_DIST;
     m21[j] = -1;
     const orbx_keypoint kp = k2[j];
-    // Frame::PosInGrid (Frame.cpp:89-99) + the octave filter of GetFeaturesInArea (Frame.cpp:179,191)
+    // Frame::PosInGrid (Frame.cpp:89-99); the octave filter of GetFeaturesInArea (Frame.cpp:179,191) is applied per query
     const int px = (int)roundf((kp.x - fminX) * wInv), py = (int)roundf((kp.y - fminY) * hInv);
-    const bool ok = kp.octave == 0 && px >= 0 && px < ORBX_GRID_COLS && py >= 0 && py < ORBX_GRID_ROWS;
-    cell2[j] = ok ? px * ORBX_GRID_ROWS + py : -1;
+    const bool ok = px >= 0 && px < ORBX_GRID_COLS && py >= 0 && py < ORBX_GRID_ROWS;
+    cell2[j] = ok ? ((px * ORBX_GRID_ROWS + py) | (kp.octave == 0 ? 0 : NOT_OCT0)) : -1;
   }
   for (int i = t; i < n1; i += T) {
     m12[i] = -1;
@@ -2125,6 +2130,9 @@ __device__ void matchGeneral(const int pair, const int* __restrict__ pairFirst, 
   for (int i1 = 0; i1 < n1; i1++) {
     const orbx_keypoint kp1 = k1[i1];
     if (kp1.octave > 0) continue;  // ORBmatcher.cpp:38-39
+    // GetFeaturesInArea(.., level1, level1) checks the octave only when level1 >= 0 (Frame.cpp:179): a query with a negative
+    // octave takes the trains of every octave, one with octave 0 those of octave 0
+    const int skipOct = kp1.octave < 0 ? 0 : NOT_OCT0;
     // cell window, Frame.cpp:167-177
     const int minCX = max(0, (int)floorf((kp1.x - fminX - r) * wInv));
     const int maxCX = min(ORBX_GRID_COLS - 1, (int)ceilf((kp1.x - fminX + r) * wInv));
@@ -2136,8 +2144,9 @@ __device__ void matchGeneral(const int pair, const int* __restrict__ pairFirst, 
     unsigned long long best = MATCH_NONE;  // (dist << 32) | (cell << 20 | index)  -- index < 2^20
     int second = INF_DIST, any = 0;
     for (int j = t; j < n2; j += T) {
-      const int c = cell2[j];
-      if (c < 0) continue;
+      const int cb = cell2[j];
+      if (cb < 0 || (cb & skipOct)) continue;
+      const int c = cb & ~NOT_OCT0;
       const int cx = c / ORBX_GRID_ROWS, cy = c - cx * ORBX_GRID_ROWS;
       if (cx < minCX || cx > maxCX || cy < minCY || cy > maxCY) continue;
       const float dx = k2[j].x - kp1.x, dy = k2[j].y - kp1.y;
