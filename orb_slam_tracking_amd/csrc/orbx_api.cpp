@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "orbx_buf.h"
 #include "orbx_device.h"
 #include "orbx_knobs.h"
 
@@ -71,7 +72,6 @@ namespace {
 
 inline int cvRoundF(float v) { return (int)lrintf(v); }  // round half to even
 inline int cvRoundD(double v) { return (int)lrint(v); }
-inline int alignUp(int v, int a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 }  // namespace orbx
@@ -83,6 +83,55 @@ using namespace orbx;
 struct PyrTabInfo {
   int32_t xoff[ORBX_MAX_LEVELS], yoff[ORBX_MAX_LEVELS];  // uint4 units from the table base
   int ok, dual2;
+};
+
+// Every buffer whose size follows from (maxW, maxH, maxB): allocated by allocAll at orbx_create, and released together and
+// allocated again by growTo when a call brings a larger frame or batch (ORBextractor::operator() takes any image,
+// cpp:1531-1545).  The mapped page-locked ones are written by kernels straight into host memory.
+struct SizedBufs {
+  DeviceBuf<uint8_t> dPyr;
+  DeviceBuf<uint32_t> dCand;
+  DeviceBuf<int> dCandCount;       // (nothing reads it)
+  DeviceBuf<int> dCellCount;       // [frame][cell of all levels]: candidates in the cell's segment
+  DeviceBuf<int> dMaxN;            // [frame][level] candidate count of the unit (k_octree_lds); reduced and reset by k_sel_compact
+  PinnedBuf<int> hMaxN;            // mapped mirror, written by k_sel_compact
+  DeviceBuf<ResizeTab> dTab;
+  DeviceBuf<FastCell> dCells;      // k_fast_wave's per-cell records of the current geometry (orbx_ctx::hCells)
+  DeviceBuf<SelKp> dSel;
+  DeviceBuf<int> dNsel;
+  DeviceBuf<SelKp> dSelStage;      // quadtree selection stage
+  DeviceBuf<int> dNselLevel;
+  DeviceBuf<uint8_t> dOctScratch;
+  DeviceBuf<uint32_t> dOctTab;     // path-code tables of the current geometry's levels (OctLaunch::codeTab)
+  DeviceBuf<PyrTileRect> dPyrTiles;  // k_pyramid_tiles' rectangles of the current geometry (buildPyrTiles); nPyrTiles == 0: not usable
+  DeviceBuf<PyrTileTap> dPyrTaps;    // ... and the tiles' tap blobs (ORBX_PYR_TILE_TAPS entries per tile)
+  DeviceBuf<uint8_t> dIn;
+  DeviceBuf<orbx_keypoint> dKps;
+  DeviceBuf<uint8_t> dDesc;
+  PinnedBuf<int> hNsel;            // mapped: k_sel_compact stores the per-frame counts straight to the host
+  PinnedBuf<int> hFlags;           // mapped [2], written by k_sel_compact: selection error of the batch in flight with that parity
+  PinnedBuf<int> hWide;            // mapped [2], raised by k_match_jacobi (orbx_ctx::wideExpected)
+  // results of a call on a few host frames are written by the descriptor kernel straight into mapped page-locked memory
+  // (no copy commands, no second synchronisation behind them): orbx_extract_batch with at most pinFrames frames
+  PinnedBuf<orbx_keypoint> hKpsPin;
+  PinnedBuf<uint8_t> hDescPin;
+};
+
+// the staging block of the host-array entry points (orbx_match_init, orbx_undistort_keypoints) over `base`: keypoints and
+// descriptors of two frames of `cap` entries, then their counts
+struct PairBlock {
+  orbx_keypoint* kps = nullptr;  // [2][cap]
+  uint8_t* desc = nullptr;       // [2][cap][32]
+  int32_t* n = nullptr;          // [2]
+  size_t bytes = 0;
+  PairBlock() = default;
+  PairBlock(void* base, size_t cap) {
+    Layout L(base);
+    kps = L.take<orbx_keypoint>(2 * cap);
+    desc = L.take<uint8_t>(2 * cap * 32);
+    n = L.take<int32_t>(2);
+    bytes = L.size();
+  }
 };
 
 struct orbx_ctx {
@@ -103,52 +152,29 @@ struct orbx_ctx {
   Geom g{};
   std::vector<ResizeTab> hTab;
 
-  // device buffers
-  uint8_t* dPyr = nullptr;
+  SizedBufs bufs;
   size_t pyrBytes = 0;
-  uint32_t* dCand = nullptr;
   size_t candEntries = 0;
-  int* dCandCount = nullptr;   // only its tail is used: the two error flags (dOverflow)
-  int* dCellCount = nullptr;   // [frame][cell of all levels]: candidates in the cell's segment
-  int* dMaxN = nullptr;        // [frame][level] candidate count of the unit (k_octree_lds); reduced and reset by k_sel_compact
-  int* hMaxN = nullptr;        // pinned mirror, written by k_sel_compact
-  int* hMaxNDev = nullptr;
   int candHintL[ORBX_MAX_LEVELS]{};  // per level: largest candidate count of a unit in the previous batch of this geometry (0 = unknown)
   int maxSlotsUsed = 0;
   size_t cellCountEntries = 0;
-  int* dOverflow = nullptr;
-  ResizeTab* dTab = nullptr;
   size_t tabEntries = 0;
   PyrTabInfo pyrInfo{};   // k_pyramid_bands' tables inside dTab, for the current geometry
   std::vector<FastCell> hCells;  // k_fast_wave's per-cell records of the current geometry (buildFastCells)
-  FastCell* dCells = nullptr;
   size_t cellEntries = 0;
   int fastWaveOk = 0;            // k_fast_wave usable for the current geometry: 0 no, 1 tiles of 16 dwords x 64 rows, 2 of 12 dwords
-  SelKp* dSel = nullptr;
-  int* dNsel = nullptr;
   // quadtree selection stage (device)
   OctLaunch oct{};
   int maxQuota = 0;
-  SelKp* dSelStage = nullptr;
-  int* dNselLevel = nullptr;
-  uint8_t* dOctScratch = nullptr;
-  PyrTileRect* dPyrTiles = nullptr;  // k_pyramid_tiles' rectangles of the current geometry (buildPyrTiles); nPyrTiles == 0: not usable
-  PyrTileTap* dPyrTaps = nullptr;    // ... and the tiles' tap blobs (ORBX_PYR_TILE_TAPS entries per tile)
   size_t pyrTileCap = 0;             // tiles the two buffers hold
   std::vector<PyrTileRect> hPyrTiles;
   std::vector<PyrTileTap> hPyrTaps;
   int nPyrTiles = 0, pyrTileBuf0 = 0, pyrTileBuf = 0;
-  uint32_t* dOctTab = nullptr;     // path-code tables of the current geometry's levels (OctLaunch::codeTab)
   size_t octTabEntries = 0;
   std::vector<uint32_t> hOctTab;
   size_t octScratchBytes = 0;
-  int* hFlags = nullptr;  // pinned [2], written by k_sel_compact through hFlagsDev: selection error of the batch in flight with that parity
-  int* hFlagsDev = nullptr;
-  int* hNselDev = nullptr;  // device view of hNsel: k_sel_compact stores the per-frame counts straight to the host
-  // The wide matcher kernels are issued with a batch only while batches need them (k_match_jacobi raises hWide[parity]
+  // The wide matcher kernels are issued with a batch only while batches need them (k_match_jacobi raises bufs.hWide[parity]
   // when it hands a pair on); a batch that needed them without having them gets them at its wait (late, prep included).
-  int* hWide = nullptr;     // pinned [2]
-  int* hWideDev = nullptr;
   bool wideExpected = false;  // a batch that needs the wide kernels without having them gets them at its wait, and its successors with them
   int wideIdle = 0;         // consecutive batches that had the wide kernels and did not need them
   bool wideLaunched[2]{};
@@ -169,45 +195,25 @@ struct orbx_ctx {
   } late[2];
   std::vector<int32_t> initPairs;  // the pair list of the last orbx_find_models* call (source of its copy)
   std::vector<int32_t> lastPairs;  // the pair list dPairs holds (first[], second[]): an unchanged list is not copied again
-  uint8_t* dIn = nullptr;
   size_t inBytes = 0;
-  orbx_keypoint* dKps = nullptr;
-  uint8_t* dDesc = nullptr;
-  // pinned host mirrors
-  int* hNsel = nullptr;
-  // results of a call on a few host frames are written by the descriptor kernel straight into mapped page-locked memory
-  // (no copy commands, no second synchronisation behind them): orbx_extract_batch with at most pinFrames frames
-  orbx_keypoint* hKpsPin = nullptr;
-  orbx_keypoint* hKpsPinDev = nullptr;
-  uint8_t* hDescPin = nullptr;
-  uint8_t* hDescPinDev = nullptr;
-  int pinFrames = 0;
+  int pinFrames = 0;  // frames bufs.hKpsPin / hDescPin hold
   // matcher
-  int* dMatchScratch = nullptr;
-  unsigned int* dMatchDiag = nullptr;  // orbx_debug_match_counters: [0] blocks of 256 queries listed by k_match_bf_mfma since orbx_create
-  size_t matchScratchInts = 0;
-  int* dPairs = nullptr;
-  size_t pairsCap = 0;
-  // host-array entry points (orbx_match_init, orbx_undistort_keypoints): ONE device block [2 mCap keypoints | 2 mCap
-  // descriptors | n[2]] with a page-locked mirror, so that a pair goes up with one copy command, and page-locked mapped
-  // result words the matcher kernels write straight into (no copy commands back)
-  uint8_t* dMblk = nullptr;
-  uint8_t* hMblk = nullptr;
-  size_t mBlkBytes = 0, mDescOff = 0, mCntOff = 0;
-  int* hMo = nullptr;     // [mCap + 8]: n/a[2], nmatches, stats[3], pad[2], matches12[mCap]
-  int* hMoDev = nullptr;
-  orbx_keypoint* dMk = nullptr;  // = dMblk
-  uint8_t* dMd = nullptr;        // = dMblk + mDescOff
-  int* dMi = nullptr;  // n[2] + matches12[cap] + nmatches + stats[3]  (device ints of orbx_undistort_keypoints)
+  DeviceBuf<int> dMatchScratch;
+  DeviceBuf<unsigned int> dMatchDiag;  // orbx_debug_match_counters: [0] blocks of 256 queries listed by k_match_bf_mfma since orbx_create
+  DeviceBuf<int32_t> dPairs;           // the pair list lastPairs holds
+  // host-array entry points (orbx_match_init, orbx_undistort_keypoints): ONE device block (PairBlock of mCap entries) with a
+  // page-locked mirror, so that a pair goes up with one copy command, and page-locked mapped result words the matcher kernels
+  // write straight into (no copy commands back)
+  DeviceBuf<uint8_t> dMblk;
+  PinnedBuf<uint8_t> hMblk;
+  PairBlock dM, hM;    // the block over dMblk / hMblk
+  PinnedBuf<int> hMo;  // mapped [mCap + 8]: n/a[2], nmatches, stats[3], pad[2], matches12[mCap]
+  DeviceBuf<int> dMi;  // n[2] + matches12[cap] + nmatches + stats[3]  (device ints of orbx_undistort_keypoints)
   size_t mCap = 0;
-  uint8_t* dScore = nullptr;  // staging of orbx_check_homography / _fundamental
-  size_t scoreBytes = 0;
-  uint8_t* dInit = nullptr;   // arena of orbx_find_models* / orbx_initialize* (grown on demand)
-  size_t initBytes = 0;
-  int32_t* dInitPairs = nullptr;  // their pair list (first[], second[]) as ctx->initPairs holds it
-  size_t initPairsCap = 0;
-  uint8_t* dColor = nullptr;  // staging of orbx_to_gray (host API): colour frame followed by its gray image
-  size_t colorBytes = 0;
+  DeviceBuf<uint8_t> dScore;      // staging of orbx_check_homography / _fundamental / orbx_check_rt
+  DeviceBuf<uint8_t> dInit;       // arena of orbx_find_models* / orbx_initialize*
+  DeviceBuf<int32_t> dInitPairs;  // their pair list (first[], second[]) as ctx->initPairs holds it
+  DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -233,8 +239,7 @@ struct orbx_ctx {
   bool noSplit = false;                  // (a lane) never cuts a batch into halves
   // orbx_extract_match_batch_host_async: the batch's frames go up into dIn and its results come down from these device
   // buffers behind its kernels, all stream-ordered; evOut = the copies back have landed (waited for by waitOldest)
-  uint8_t* dPipeOut = nullptr;           // [kps | desc | n | matches12 | nmatches | stats]
-  size_t pipeOutBytes = 0;
+  DeviceBuf<uint8_t> dPipeOut;           // [kps | desc | n | matches12 | nmatches | stats]
   hipEvent_t evOut[2]{};
   bool outUsed[2]{};
   bool hostInput = false;                // (while such a batch is issued) the second stream forks behind the upload
@@ -765,28 +770,17 @@ size_t buildOctLaunch(const orbx_ctx* c, const Geom& g, OctLaunch* out) {
   }
   P.nCellsTotal = g.nCellsTotal;
   octTabLayout(&P);
-  P.codeTab = c->dOctTab;
+  P.codeTab = c->bufs.dOctTab;
   *out = P;
   return (size_t)scr;
 }
 
-// Every buffer whose size follows from (maxW, maxH, maxB): allocated at orbx_create and again by growTo when a call brings
-// a larger frame or batch (ORBextractor::operator() takes any image, cpp:1531-1545).  Streams, events and the lazily sized
+// The size dependent buffers released (SizedBufs), and what refers to them forgotten.  Streams, events and the lazily sized
 // matcher / staging buffers are not touched.
 void freeAll(orbx_ctx* ctx) {
-  void* dev[] = {ctx->dPyr, ctx->dCand, ctx->dCandCount, ctx->dCellCount, ctx->dMaxN, ctx->dTab, ctx->dCells, ctx->dSel, ctx->dNsel,
-                 ctx->dSelStage, ctx->dNselLevel, ctx->dOctScratch, ctx->dOctTab, ctx->dPyrTiles, ctx->dPyrTaps, ctx->dIn, ctx->dKps, ctx->dDesc};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  void* host[] = {ctx->hNsel, ctx->hFlags, ctx->hMaxN, ctx->hWide, ctx->hKpsPin, ctx->hDescPin};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
-  ctx->dPyr = nullptr; ctx->dCand = nullptr; ctx->dCandCount = nullptr; ctx->dCellCount = nullptr; ctx->dMaxN = nullptr;
-  ctx->dTab = nullptr; ctx->dCells = nullptr; ctx->dSel = nullptr; ctx->dNsel = nullptr; ctx->dSelStage = nullptr; ctx->dNselLevel = nullptr;
-  ctx->dOctScratch = nullptr; ctx->dOctTab = nullptr; ctx->dPyrTiles = nullptr; ctx->dPyrTaps = nullptr; ctx->nPyrTiles = 0; ctx->dIn = nullptr; ctx->dKps = nullptr; ctx->dDesc = nullptr;
-  ctx->hNsel = nullptr; ctx->hFlags = nullptr; ctx->hMaxN = nullptr; ctx->hWide = nullptr;
-  ctx->hKpsPin = nullptr; ctx->hDescPin = nullptr; ctx->hKpsPinDev = nullptr; ctx->hDescPinDev = nullptr; ctx->pinFrames = 0;
-  ctx->hNselDev = nullptr; ctx->hFlagsDev = nullptr; ctx->hMaxNDev = nullptr; ctx->hWideDev = nullptr;
+  ctx->bufs = SizedBufs();
+  ctx->nPyrTiles = 0;
+  ctx->pinFrames = 0;
   ctx->curW = ctx->curH = ctx->curStride0 = 0;  // the tables on the device are gone with dTab
   ctx->lastB = 0;
   ctx->lastImg0 = nullptr;
@@ -824,27 +818,27 @@ int allocAll(orbx_ctx* ctx) {
   const size_t B = (size_t)max_batch, nl = (size_t)ctx->p.nlevels;
   const size_t cap = (size_t)std::max(ctx->selCap, 1);
   ctx->inBytes = (size_t)alignUp(max_width, 64) * max_height * B;
-#define ALLOC(ptr, bytes)                                                                         \
-  if (hipMalloc((void**)&(ptr), std::max<size_t>((bytes), 16)) != hipSuccess) {                  \
-    ctx->err = "hipMalloc failed for " #ptr " (context sizing: max_width x max_height x max_batch)"; \
+  SizedBufs& b = ctx->bufs;
+#define ALLOC(buf, bytes)                                                                         \
+  if (b.buf.grow(std::max<size_t>((bytes), 16)) != hipSuccess) {                                 \
+    ctx->err = "device allocation failed for " #buf " (context sizing: max_width x max_height x max_batch)"; \
     return ORBX_E_HIP;                                                                            \
   }
-#define ALLOCH(ptr, bytes)                                                                        \
-  if (hipHostMalloc((void**)&(ptr), std::max<size_t>((bytes), 16), hipHostMallocDefault) != hipSuccess) {  \
-    ctx->err = "hipHostMalloc failed for " #ptr;                                                  \
+#define ALLOCH(buf, bytes)                                                                        \
+  if (b.buf.grow(std::max<size_t>((bytes), 16), true) != hipSuccess) {                           \
+    ctx->err = "page-locked allocation failed for " #buf;                                         \
     return ORBX_E_HIP;                                                                            \
   }
-  ALLOC(ctx->dPyr, ctx->pyrBytes);
-  ALLOC(ctx->dCand, ctx->candEntries * 4);
-  ALLOC(ctx->dCandCount, (B * nl + 2) * sizeof(int));
-  ALLOC(ctx->dCellCount, ctx->cellCountEntries * sizeof(int));
-  ctx->dOverflow = ctx->dCandCount + B * nl;  // (unused tail kept for layout compatibility)
-  ALLOC(ctx->dTab, ctx->tabEntries * sizeof(ResizeTab));
-  ALLOC(ctx->dCells, ctx->cellEntries * sizeof(FastCell));
-  ALLOC(ctx->dSel, B * cap * sizeof(SelKp));
-  ALLOC(ctx->dNsel, B * sizeof(int));
-  ALLOC(ctx->dSelStage, B * cap * sizeof(SelKp));
-  ALLOC(ctx->dNselLevel, B * nl * sizeof(int));
+  ALLOC(dPyr, ctx->pyrBytes);
+  ALLOC(dCand, ctx->candEntries * 4);
+  ALLOC(dCandCount, (B * nl + 2) * sizeof(int));
+  ALLOC(dCellCount, ctx->cellCountEntries * sizeof(int));
+  ALLOC(dTab, ctx->tabEntries * sizeof(ResizeTab));
+  ALLOC(dCells, ctx->cellEntries * sizeof(FastCell));
+  ALLOC(dSel, B * cap * sizeof(SelKp));
+  ALLOC(dNsel, B * sizeof(int));
+  ALLOC(dSelStage, B * cap * sizeof(SelKp));
+  ALLOC(dNselLevel, B * nl * sizeof(int));
   {
     OctLaunch oct;
     ctx->octScratchBytes = buildOctLaunch(ctx, g, &oct) + 4096;
@@ -853,40 +847,34 @@ int allocAll(orbx_ctx* ctx) {
     ctx->maxQuota = 0;
     for (int q : ctx->quota) ctx->maxQuota = std::max(ctx->maxQuota, q);
   }
-  ALLOC(ctx->dOctScratch, ctx->octScratchBytes);
-  ALLOC(ctx->dOctTab, ctx->octTabEntries * 4);
+  ALLOC(dOctScratch, ctx->octScratchBytes);
+  ALLOC(dOctTab, ctx->octTabEntries * 4);
   {  // tiles of the largest geometry (no smaller frame has more) -- or of the largest frame k_pyramid_tiles is taken for at all
     int TX = 1, TY = 1;
     if (g.nlevels > 1) pyrTileGrid(g, &TX, &TY);
     ctx->pyrTileCap = std::min((size_t)TX * TY, (size_t)(kPyrTilesMaxPixels / (36 * 28) + 256));
   }
-  ALLOC(ctx->dPyrTiles, ctx->pyrTileCap * g.nlevels * sizeof(PyrTileRect));
-  ALLOC(ctx->dPyrTaps, ctx->pyrTileCap * ORBX_PYR_TILE_TAPS * sizeof(PyrTileTap));
-  ALLOC(ctx->dIn, ctx->inBytes);
-  ALLOC(ctx->dKps, B * cap * sizeof(orbx_keypoint));
-  ALLOC(ctx->dDesc, B * cap * 32);
-  ALLOCH(ctx->hNsel, B * sizeof(int))
-  ALLOCH(ctx->hFlags, 2 * sizeof(int))
-  ALLOC(ctx->dMaxN, (B * nl + 2) * sizeof(int));
-  if (hipMemset(ctx->dMaxN, 0, (B * nl + 2) * sizeof(int)) != hipSuccess) return ORBX_E_HIP;
-  ALLOCH(ctx->hMaxN, 2 * ORBX_MAX_LEVELS * sizeof(int))
-  if (hipHostGetDevicePointer((void**)&ctx->hMaxNDev, ctx->hMaxN, 0) != hipSuccess) return ORBX_E_HIP;
-  if (hipHostGetDevicePointer((void**)&ctx->hNselDev, ctx->hNsel, 0) != hipSuccess) return ORBX_E_HIP;
-  if (hipHostGetDevicePointer((void**)&ctx->hFlagsDev, ctx->hFlags, 0) != hipSuccess) return ORBX_E_HIP;
+  ALLOC(dPyrTiles, ctx->pyrTileCap * g.nlevels * sizeof(PyrTileRect));
+  ALLOC(dPyrTaps, ctx->pyrTileCap * ORBX_PYR_TILE_TAPS * sizeof(PyrTileTap));
+  ALLOC(dIn, ctx->inBytes);
+  ALLOC(dKps, B * cap * sizeof(orbx_keypoint));
+  ALLOC(dDesc, B * cap * 32);
+  ALLOCH(hNsel, B * sizeof(int))
+  ALLOCH(hFlags, 2 * sizeof(int))
+  ALLOC(dMaxN, (B * nl + 2) * sizeof(int));
+  if (hipMemset(b.dMaxN, 0, (B * nl + 2) * sizeof(int)) != hipSuccess) return ORBX_E_HIP;
+  ALLOCH(hMaxN, 2 * ORBX_MAX_LEVELS * sizeof(int))
   ctx->pinFrames = (int)std::min<size_t>(B, 4);
-  ALLOCH(ctx->hKpsPin, (size_t)ctx->pinFrames * cap * sizeof(orbx_keypoint))
-  ALLOCH(ctx->hDescPin, (size_t)ctx->pinFrames * cap * 32)
-  if (hipHostGetDevicePointer((void**)&ctx->hKpsPinDev, ctx->hKpsPin, 0) != hipSuccess) return ORBX_E_HIP;
-  if (hipHostGetDevicePointer((void**)&ctx->hDescPinDev, ctx->hDescPin, 0) != hipSuccess) return ORBX_E_HIP;
-  ALLOCH(ctx->hWide, 16)
-  ctx->hWide[0] = ctx->hWide[1] = 0;
-  if (hipHostGetDevicePointer((void**)&ctx->hWideDev, ctx->hWide, 0) != hipSuccess) return ORBX_E_HIP;
-  ctx->hFlags[0] = ctx->hFlags[1] = 0;
-  for (int i = 0; i < 2 * ORBX_MAX_LEVELS; i++) ctx->hMaxN[i] = 0;
-  for (int& v : ctx->candHintL) v = 0;
-  ctx->maxSlotsUsed = 0;
+  ALLOCH(hKpsPin, (size_t)ctx->pinFrames * cap * sizeof(orbx_keypoint))
+  ALLOCH(hDescPin, (size_t)ctx->pinFrames * cap * 32)
+  ALLOCH(hWide, 16)
 #undef ALLOC
 #undef ALLOCH
+  b.hWide[0] = b.hWide[1] = 0;
+  b.hFlags[0] = b.hFlags[1] = 0;
+  for (int i = 0; i < 2 * ORBX_MAX_LEVELS; i++) b.hMaxN[i] = 0;
+  for (int& v : ctx->candHintL) v = 0;
+  ctx->maxSlotsUsed = 0;
   return ORBX_OK;
 }
 
@@ -948,7 +936,7 @@ int ensureGeometry(orbx_ctx* ctx, int w, int h, int stride0) {
     ctx->err = "internal: geometry exceeds the buffers sized at orbx_create";
     return ORBX_E_BADARG;
   }
-  oct.codeTab = ctx->dOctTab;  // (growTo may have replaced the buffer since buildOctLaunch read the pointer: it did not, but keep one source)
+  oct.codeTab = ctx->bufs.dOctTab;  // (growTo may have replaced the buffer since buildOctLaunch read the pointer: it did not, but keep one source)
   octCodeTables(&oct, &ctx->hOctTab);
   if (ctx->hOctTab.size() > ctx->octTabEntries) {
     ctx->err = "internal: geometry exceeds the buffers sized at orbx_create";
@@ -956,21 +944,21 @@ int ensureGeometry(orbx_ctx* ctx, int w, int h, int stride0) {
   }
   ctx->g = g;
   ctx->oct = oct;
-  HIPCHK(hipMemcpyAsync(ctx->dOctTab, ctx->hOctTab.data(), ctx->hOctTab.size() * 4, hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(hipMemcpyAsync(ctx->bufs.dOctTab, ctx->hOctTab.data(), ctx->hOctTab.size() * 4, hipMemcpyHostToDevice, ctx->st));
   if ((long long)w * h > kPyrTilesMaxPixels ||  // (never taken for such a frame: no tables, no 6 KB of taps per tile)
       !buildPyrTiles(g, tab, &ctx->hPyrTiles, &ctx->hPyrTaps, &ctx->nPyrTiles, &ctx->pyrTileBuf0, &ctx->pyrTileBuf) ||
       (size_t)ctx->nPyrTiles > ctx->pyrTileCap) {
     ctx->nPyrTiles = 0;
   } else {
-    HIPCHK(hipMemcpyAsync(ctx->dPyrTiles, ctx->hPyrTiles.data(), ctx->hPyrTiles.size() * sizeof(PyrTileRect), hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(ctx->dPyrTaps, ctx->hPyrTaps.data(), ctx->hPyrTaps.size() * sizeof(PyrTileTap), hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(ctx->bufs.dPyrTiles, ctx->hPyrTiles.data(), ctx->hPyrTiles.size() * sizeof(PyrTileRect), hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(ctx->bufs.dPyrTaps, ctx->hPyrTaps.data(), ctx->hPyrTaps.size() * sizeof(PyrTileTap), hipMemcpyHostToDevice, ctx->st));
   }
   ctx->hTab = tab;
   ctx->pyrInfo = pyrInfo;
   ctx->fastWaveOk = buildFastCells(g, &ctx->hCells);
-  if (!tab.empty()) HIPCHK(hipMemcpyAsync(ctx->dTab, ctx->hTab.data(), tab.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, ctx->st));
+  if (!tab.empty()) HIPCHK(hipMemcpyAsync(ctx->bufs.dTab, ctx->hTab.data(), tab.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, ctx->st));
   if (!ctx->hCells.empty())
-    HIPCHK(hipMemcpyAsync(ctx->dCells, ctx->hCells.data(), ctx->hCells.size() * sizeof(FastCell), hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(ctx->bufs.dCells, ctx->hCells.data(), ctx->hCells.size() * sizeof(FastCell), hipMemcpyHostToDevice, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
   ctx->curW = w;
   ctx->curH = h;
@@ -1140,14 +1128,14 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
   }
   if (banded) {
     StageTimer tm(ctx, ORBX_STAGE_PYRAMID, si, st);
-    HIPCHK(launch_pyramid_bands(st, n, a.dImg0, a.frameStride0, ctx->dPyr, g, ctx->dTab, pb));
+    HIPCHK(launch_pyramid_bands(st, n, a.dImg0, a.frameStride0, ctx->bufs.dPyr, g, ctx->bufs.dTab, pb));
     tm.stop(1);
     ctx->lastLaunch[0] = 1;
     ctx->lastLaunch[1] = pb.nBands * pb.nStrips;
   } else if (nl > 1 && ctx->nPyrTiles > 0 && n <= tilesMax && (long long)n * g.L[0].w * g.L[0].h <= kPyrTilesMaxPixels) {
     // small batches: one launch, a workgroup per tile of a frame, the level chain through LDS
     StageTimer tm(ctx, ORBX_STAGE_PYRAMID, si, st);
-    HIPCHK(launch_pyramid_tiles(st, n, a.dImg0, a.frameStride0, ctx->dPyr, g, ctx->dPyrTiles, ctx->dPyrTaps, ctx->nPyrTiles,
+    HIPCHK(launch_pyramid_tiles(st, n, a.dImg0, a.frameStride0, ctx->bufs.dPyr, g, ctx->bufs.dPyrTiles, ctx->bufs.dPyrTaps, ctx->nPyrTiles,
                                 ctx->pyrTileBuf0, ctx->pyrTileBuf));
     tm.stop(1);
     ctx->lastLaunch[0] = 2;
@@ -1157,10 +1145,10 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
     for (int l = 1; l < nl; l++) {
       const LevelGeom& S = g.L[l - 1];
       const LevelGeom& D = g.L[l];
-      const uint8_t* src = l == 1 ? a.dImg0 : ctx->dPyr + S.imgOff;
+      const uint8_t* src = l == 1 ? a.dImg0 : ctx->bufs.dPyr + S.imgOff;
       const long long sfs = l == 1 ? a.frameStride0 : S.frameStride;
-      HIPCHK(launch_resize(st, n, src + (long long)f0 * sfs, sfs, S.w, S.h, S.stride, ctx->dPyr + D.imgOff + (long long)f0 * D.frameStride,
-                           D.frameStride, D.w, D.h, D.stride, ctx->dTab + D.xtabOff, ctx->dTab + D.ytabOff,
+      HIPCHK(launch_resize(st, n, src + (long long)f0 * sfs, sfs, S.w, S.h, S.stride, ctx->bufs.dPyr + D.imgOff + (long long)f0 * D.frameStride,
+                           D.frameStride, D.w, D.h, D.stride, ctx->bufs.dTab + D.xtabOff, ctx->bufs.dTab + D.ytabOff,
                            D.resizeSpanOk && (l > 1 || a.aligned0),
                            // (behind the pyramid buffer's levels there is slack; behind the caller's last frame nothing is known)
                            l > 1 ? n : std::min(std::max(a.safeFrom - f0, 0), n)));
@@ -1171,7 +1159,7 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
   }
   {
     StageTimer tm(ctx, ORBX_STAGE_FAST, si, st);
-    HIPCHK(launch_fast(st, n, a.dImg0, a.frameStride0, a.aligned0, ctx->dPyr, g, ctx->dCand, ctx->dCellCount, ctx->dCells,
+    HIPCHK(launch_fast(st, n, a.dImg0, a.frameStride0, a.aligned0, ctx->bufs.dPyr, g, ctx->bufs.dCand, ctx->bufs.dCellCount, ctx->bufs.dCells,
                        ctx->fastWaveOk, &ctx->lastLaunch[2]));
     tm.stop(1);
     ctx->lastLaunch[5] = n;
@@ -1182,15 +1170,15 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
   {  // selection stage: quadtree per (frame, level), then level-major compaction
     StageTimer tm(ctx, ORBX_STAGE_SELECT, si, st);
     // per-level candidate maxima of this stream slot: device accumulators + their pinned host mirror (read after the sync)
-    int* dMax = ctx->dMaxN;  // (indexed by frame: the two half batches do not meet)
-    HIPCHK(launch_octree(st, n, ctx->dCand, ctx->dCellCount, oct, ctx->dSelStage, ctx->dNselLevel, ctx->dOctScratch, dMax,
+    int* dMax = ctx->bufs.dMaxN;  // (indexed by frame: the two half batches do not meet)
+    HIPCHK(launch_octree(st, n, ctx->bufs.dCand, ctx->bufs.dCellCount, oct, ctx->bufs.dSelStage, ctx->bufs.dNselLevel, ctx->bufs.dOctScratch, dMax,
                          ctx->candHintL, 0, &ctx->lastLaunch[3]));
     // small launches (the one-frame call): the descriptor kernel indexes the staging lists itself and does the bookkeeping
     // (DescStage) -- one kernel less on the call's critical path
     staged = n * g.nlevels <= ORBX_DESC_STAGED_MAX_UNITS;
     if (!staged)
-      HIPCHK(launch_sel_compact(st, n, ctx->dSelStage, ctx->dNselLevel, oct, ctx->dSel, ctx->dNsel, a.dNuser, ctx->hNselDev, g.selCap,
-                                ctx->hFlagsDev + ctx->parity, dMax, ctx->hMaxNDev + si * ORBX_MAX_LEVELS));
+      HIPCHK(launch_sel_compact(st, n, ctx->bufs.dSelStage, ctx->bufs.dNselLevel, oct, ctx->bufs.dSel, ctx->bufs.dNsel, a.dNuser, ctx->bufs.hNsel.dev(), g.selCap,
+                                ctx->bufs.hFlags.dev() + ctx->parity, dMax, ctx->bufs.hMaxN.dev() + si * ORBX_MAX_LEVELS));
     ctx->maxSlotsUsed |= 1 << si;
     tm.stop(staged ? 1 : 2);
     ctx->lastLaunch[4] = (ctx->lastLaunch[4] & 1) | (staged ? 2 : 0);
@@ -1198,11 +1186,11 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
   {
     StageTimer tm(ctx, ORBX_STAGE_DESCRIBE, si, st);
     DescStage ds;
-    ds.selStage = ctx->dSelStage; ds.nselLevel = ctx->dNselLevel; ds.nsel = ctx->dNsel; ds.nselUser = a.dNuser; ds.hostNsel = ctx->hNselDev;
-    ds.hostErr = ctx->hFlagsDev + ctx->parity; ds.maxN = ctx->dMaxN; ds.hostMaxN = ctx->hMaxNDev + si * ORBX_MAX_LEVELS;
+    ds.selStage = ctx->bufs.dSelStage; ds.nselLevel = ctx->bufs.dNselLevel; ds.nsel = ctx->bufs.dNsel; ds.nselUser = a.dNuser; ds.hostNsel = ctx->bufs.hNsel.dev();
+    ds.hostErr = ctx->bufs.hFlags.dev() + ctx->parity; ds.maxN = ctx->bufs.dMaxN; ds.hostMaxN = ctx->bufs.hMaxN.dev() + si * ORBX_MAX_LEVELS;
     ds.selStride = oct.selStride;
     for (int l = 0; l < ORBX_MAX_LEVELS; l++) ds.selOff[l] = oct.selOff[l];
-    HIPCHK(launch_describe_patch(st, n, g.selCap, a.dImg0, a.frameStride0, a.aligned0, ctx->dPyr, g, ctx->dSel, ctx->dNsel,
+    HIPCHK(launch_describe_patch(st, n, g.selCap, a.dImg0, a.frameStride0, a.aligned0, ctx->bufs.dPyr, g, ctx->bufs.dSel, ctx->bufs.dNsel,
                                  a.dKps, a.dDesc, a.capacity, ctx->gaussVariant, ctx->libmVariant, staged ? &ds : nullptr));
     tm.stop(1);
   }
@@ -1230,7 +1218,7 @@ int issueMatch(orbx_ctx* ctx, int si, hipStream_t st, int pair0, int n, const Ma
   StageTimer tm(ctx, ORBX_STAGE_MATCH, si, st);
   const int wide = ctx->wideLaunched[ctx->parity] ? 1 : 0;
   HIPCHK(launch_match(st, n, ctx->dPairs, ctx->dPairs + m.nPairs, dKps, dDesc, dN, capacity, m.b, m.window, m.nnratio, m.checkOri,
-                      m.dMatches12, m.dNmatches, m.dStats, ctx->dMatchScratch, pair0, wide, ctx->hWideDev + ctx->parity, ctx->dMatchDiag));
+                      m.dMatches12, m.dNmatches, m.dStats, ctx->dMatchScratch, pair0, wide, ctx->bufs.hWide.dev() + ctx->parity, ctx->dMatchDiag));
   tm.stop(wide ? 3 : 1);  // k_match_jacobi (+ k_match_wide_lists + k_match_wide_resolve, for pending pairs only)
   return ORBX_OK;
 }
@@ -1239,7 +1227,7 @@ int issueMatch(orbx_ctx* ctx, int si, hipStream_t st, int pair0, int n, const Ma
 // a late launch would need.
 void armMatch(orbx_ctx* ctx, const MatchArgs& m, const orbx_keypoint* dKps, const uint8_t* dDesc, const int* dN, int capacity) {
   const int par = ctx->parity;
-  ctx->hWide[par] = 0;  // (the previous batch of this parity has been waited for)
+  ctx->bufs.hWide[par] = 0;  // (the previous batch of this parity has been waited for)
   ctx->wideLaunched[par] = ctx->wideExpected || ctx->eventOrdered;
   orbx_ctx::LateMatch& L = ctx->late[par];
   L.valid = true;
@@ -1254,12 +1242,12 @@ int settleMatch(orbx_ctx* ctx, int parity) {
   orbx_ctx::LateMatch& L = ctx->late[parity];
   if (!L.valid) return ORBX_OK;
   L.valid = false;
-  const bool needed = ctx->hWide[parity] != 0;
+  const bool needed = ctx->bufs.hWide[parity] != 0;
   if (needed && !ctx->wideLaunched[parity]) {
     HIPCHK(hipStreamSynchronize(ctx->st));
     if (ctx->st2) HIPCHK(hipStreamSynchronize(ctx->st2));
     HIPCHK(launch_match(ctx->st, L.nPairs, ctx->dPairs, ctx->dPairs + L.nPairs, L.dKps, L.dDesc, L.dN, L.capacity, L.b, L.window,
-                        L.nnratio, L.checkOri, L.dMatches12, L.dNmatches, L.dStats, ctx->dMatchScratch, 0, 2, ctx->hWideDev + parity, ctx->dMatchDiag));
+                        L.nnratio, L.checkOri, L.dMatches12, L.dNmatches, L.dStats, ctx->dMatchScratch, 0, 2, ctx->bufs.hWide.dev() + parity, ctx->dMatchDiag));
     HIPCHK(hipStreamSynchronize(ctx->st));
   }
   if (needed) {
@@ -1271,24 +1259,30 @@ int settleMatch(orbx_ctx* ctx, int parity) {
   return ORBX_OK;
 }
 
-// Pair list -> dPairs (first[], then second[]).  Trackers match the same pairs batch after batch, so an unchanged list
-// is not copied again (two copy commands less at the head of the stream).
+// Pair list (first[], then second[]) -> `dev`.  The copy reads `held`, the context's own copy of the list `dev` holds, which
+// stays put until the next change (the caller's arrays may be gone by the time a stream-ordered call's copy runs).  Trackers
+// match the same pairs batch after batch, so an unchanged list is not copied again.  A changed one first drains what may still
+// read the list `dev` holds: every batch in flight (`waitBatches`) or the context stream.  `*copied`: the copy was queued.
 int waitAll(orbx_ctx* ctx);
-int uploadPairs(orbx_ctx* ctx, int nPairs, const int32_t* hFirst, const int32_t* hSecond, hipStream_t st, bool* copied) {
-  *copied = false;
-  std::vector<int32_t>& lp = ctx->lastPairs;
-  if ((int)lp.size() == 2 * nPairs && std::memcmp(lp.data(), hFirst, sizeof(int32_t) * nPairs) == 0 &&
-      std::memcmp(lp.data() + nPairs, hSecond, sizeof(int32_t) * nPairs) == 0)
+int uploadPairs(orbx_ctx* ctx, std::vector<int32_t>& held, DeviceBuf<int32_t>& dev, int nPairs, const int32_t* hFirst,
+                const int32_t* hSecond, bool waitBatches, bool* copied = nullptr) {
+  if (copied) *copied = false;
+  if ((int)held.size() == 2 * nPairs && std::memcmp(held.data(), hFirst, sizeof(int32_t) * nPairs) == 0 &&
+      std::memcmp(held.data() + nPairs, hSecond, sizeof(int32_t) * nPairs) == 0)
     return ORBX_OK;
-  int r = waitAll(ctx);  // batches in flight (either stream) may still read the list dPairs holds
-  if (r != ORBX_OK) return r;
-  // the copy reads the context's own copy of the list, which stays put until the next change (the caller's arrays may be
-  // gone by the time a stream-ordered call's copy runs)
-  lp.assign(hFirst, hFirst + nPairs);
-  lp.insert(lp.end(), hSecond, hSecond + nPairs);
-  *copied = true;
-  if (hipMemcpyAsync(ctx->dPairs, lp.data(), sizeof(int) * 2 * nPairs, hipMemcpyHostToDevice, st) != hipSuccess) {
-    lp.clear();
+  if (waitBatches) {
+    const int r = waitAll(ctx);
+    if (r != ORBX_OK) return r;
+  } else {
+    HIPCHK(hipStreamSynchronize(ctx->st));
+  }
+  held.clear();  // (until the copy is queued, `dev` holds no list a later call may skip its copy for)
+  HIPCHK(dev.grow(sizeof(int32_t) * 2 * nPairs));
+  held.assign(hFirst, hFirst + nPairs);
+  held.insert(held.end(), hSecond, hSecond + nPairs);
+  if (copied) *copied = true;
+  if (hipMemcpyAsync(dev, held.data(), sizeof(int32_t) * 2 * nPairs, hipMemcpyHostToDevice, ctx->st) != hipSuccess) {
+    held.clear();
     ctx->err = "hipMemcpyAsync (pair list)";
     return ORBX_E_HIP;
   }
@@ -1316,13 +1310,13 @@ int waitOldest(orbx_ctx* ctx) {
     for (int l = 0; l < ctx->p.nlevels; l++) {
       int m = 0;
       for (int q = 0; q < 2; q++)
-        if (ctx->maxSlotsUsed & (1 << q)) { const int v = ctx->hMaxN[q * ORBX_MAX_LEVELS + l]; m = ORBX_OCT_FB_MAX(m, v); }
+        if (ctx->maxSlotsUsed & (1 << q)) { const int v = ctx->bufs.hMaxN[q * ORBX_MAX_LEVELS + l]; m = ORBX_OCT_FB_MAX(m, v); }
       ctx->candHintL[l] = m;
     }
     if (ctx->pending == 0) ctx->maxSlotsUsed = 0;
   }
-  if (ctx->hFlags[parity]) {  // raised by this batch's k_sel_compact through mapped host memory (one slot per parity: the
-    ctx->hFlags[parity] = 0;   // other batch in flight reports into its own)
+  if (ctx->bufs.hFlags[parity]) {  // raised by this batch's k_sel_compact through mapped host memory (one slot per parity: the
+    ctx->bufs.hFlags[parity] = 0;   // other batch in flight reports into its own)
     ctx->err = "selection stage: more candidates or nodes than its scratch can hold";
     return ORBX_E_CAPACITY;
   }
@@ -1387,7 +1381,7 @@ int extractCore(orbx_ctx* ctx, int B, const uint8_t* dImg0, int w, int h, int st
   a.dKps = dKps; a.dDesc = dDesc; a.capacity = capacity;
   // k_pyramid_bands may read a few bytes beyond a level-0 row: harmless while another frame follows in the caller's buffer
   a.safeFrom = frameStride0 >= (long long)stride0 * h ? B - 1 : 0;
-  int* dN = dNout ? dNout : ctx->dNsel;
+  int* dN = dNout ? dNout : ctx->bufs.dNsel;
   const int nPairs = match ? match->nPairs : 0;
   bool pairsCopied = false;
   if (nPairs > 0) {
@@ -1396,7 +1390,7 @@ int extractCore(orbx_ctx* ctx, int B, const uint8_t* dImg0, int w, int h, int st
       if (match->hFirst[p] < 0 || match->hFirst[p] >= B || match->hSecond[p] < 0 || match->hSecond[p] >= B) return ORBX_E_BADARG;
     r = ensureMatchScratch(ctx, nPairs, capacity);
     if (r != ORBX_OK) return r;
-    r = uploadPairs(ctx, nPairs, match->hFirst, match->hSecond, st, &pairsCopied);
+    r = uploadPairs(ctx, ctx->lastPairs, ctx->dPairs, nPairs, match->hFirst, match->hSecond, true, &pairsCopied);
     if (r != ORBX_OK) return r;
     ctx->parity = (int)(ctx->seqIssue & 1u);  // (uploadPairs may have waited)
   }
@@ -1468,8 +1462,8 @@ int extractCore(orbx_ctx* ctx, int B, const uint8_t* dImg0, int w, int h, int st
     (void)hipStreamSynchronize(st);
     if (ctx->st2) (void)hipStreamSynchronize(ctx->st2);
     ctx->late[ctx->parity].valid = false;
-    ctx->hWide[ctx->parity] = 0;
-    ctx->hFlags[ctx->parity] = 0;
+    ctx->bufs.hWide[ctx->parity] = 0;
+    ctx->bufs.hFlags[ctx->parity] = 0;
     for (int si = 0; si < 2; si++)
       for (int s2 = 0; s2 < ORBX_STAGE_COUNT; s2++) ctx->used[ctx->parity][si][s2] = false;
     if (pairsCopied) ctx->lastPairs.clear();
@@ -1562,12 +1556,6 @@ void orbx_destroy(orbx_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
   if (ctx->st2) (void)hipStreamSynchronize(ctx->st2);
-  freeAll(ctx);
-  void* dev[] = {ctx->dMatchScratch, ctx->dMatchDiag, ctx->dPairs, ctx->dMblk, ctx->dMi, ctx->dColor, ctx->dScore, ctx->dInit, ctx->dInitPairs};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (ctx->hMblk) (void)hipHostFree(ctx->hMblk);
-  if (ctx->hMo) (void)hipHostFree(ctx->hMo);
   for (int si = 0; si < 2; si++)
     for (int s = 0; s < ORBX_STAGE_COUNT; s++)
       for (int k = 0; k < 2; k++)
@@ -1582,10 +1570,9 @@ void orbx_destroy(orbx_ctx* ctx) {
   if (ctx->evOrder) (void)hipEventDestroy(ctx->evOrder);
   for (int par = 0; par < 2; par++)
     if (ctx->evOut[par]) (void)hipEventDestroy(ctx->evOut[par]);
-  if (ctx->dPipeOut) (void)hipFree(ctx->dPipeOut);
   if (ctx->st2) (void)hipStreamDestroy(ctx->st2);
   if (ctx->ownStream && ctx->st) (void)hipStreamDestroy(ctx->st);
-  delete ctx;
+  delete ctx;  // (frees the buffers)
 }
 
 int orbx_set_opencv_variant(orbx_ctx* ctx, int gaussian_variant, int gray_variant) {
@@ -1673,39 +1660,39 @@ int orbx_extract_batch(orbx_ctx* ctx, int n_frames, const uint8_t* imgs, int wid
     const int B = std::min(ctx->maxB, n_frames - f0);
     if (frame_stride_bytes == (size_t)stride * height || B == 1) {
       // frames stacked without gaps: the whole batch is one tall image -> one copy command instead of one per frame
-      HIPCHK(hipMemcpy2DAsync(ctx->dIn, dstride, imgs + (size_t)f0 * frame_stride_bytes, stride, width, (size_t)height * B,
+      HIPCHK(hipMemcpy2DAsync(ctx->bufs.dIn, dstride, imgs + (size_t)f0 * frame_stride_bytes, stride, width, (size_t)height * B,
                               hipMemcpyHostToDevice, ctx->st));
     } else {
       for (int f = 0; f < B; f++)
-        HIPCHK(hipMemcpy2DAsync(ctx->dIn + f * dfs, dstride, imgs + (size_t)(f0 + f) * frame_stride_bytes, stride, width, height,
+        HIPCHK(hipMemcpy2DAsync(ctx->bufs.dIn + f * dfs, dstride, imgs + (size_t)(f0 + f) * frame_stride_bytes, stride, width, height,
                                 hipMemcpyHostToDevice, ctx->st));
     }
     if (latTrace) tt[1] = nowUs();
     const bool direct = B <= ctx->pinFrames;
-    int r = extractCore(ctx, B, ctx->dIn, width, height, dstride, (long long)dfs, direct ? ctx->hKpsPinDev : ctx->dKps,
-                        direct ? ctx->hDescPinDev : ctx->dDesc, cap, nullptr, nullptr);
+    int r = extractCore(ctx, B, ctx->bufs.dIn, width, height, dstride, (long long)dfs, direct ? ctx->bufs.hKpsPin.dev() : ctx->bufs.dKps,
+                        direct ? ctx->bufs.hDescPin.dev() : ctx->bufs.dDesc, cap, nullptr, nullptr);
     if (r != ORBX_OK) return r;
     if (latTrace) tt[2] = nowUs();
     int maxN = 0;
     for (int f = 0; f < B; f++) {
-      n_out[f0 + f] = ctx->hNsel[f];
-      maxN = std::max(maxN, ctx->hNsel[f]);
+      n_out[f0 + f] = ctx->bufs.hNsel[f];
+      maxN = std::max(maxN, ctx->bufs.hNsel[f]);
     }
     if (direct) {  // the synchronous extractCore has waited for the descriptor kernel: the results are in host memory
       for (int f = 0; f < B; f++) {
-        const size_t nf = (size_t)ctx->hNsel[f];
-        memcpy(kps + (size_t)(f0 + f) * capacity, ctx->hKpsPin + (size_t)f * cap, nf * sizeof(orbx_keypoint));
-        memcpy(desc32 + (size_t)(f0 + f) * capacity * 32, ctx->hDescPin + (size_t)f * cap * 32, nf * 32);
+        const size_t nf = (size_t)ctx->bufs.hNsel[f];
+        memcpy(kps + (size_t)(f0 + f) * capacity, ctx->bufs.hKpsPin + (size_t)f * cap, nf * sizeof(orbx_keypoint));
+        memcpy(desc32 + (size_t)(f0 + f) * capacity * 32, ctx->bufs.hDescPin + (size_t)f * cap * 32, nf * 32);
       }
       maxN = 0;
     }
     if (maxN > 0) {
       // one strided copy per array: row f = the first maxN entries of frame f (entries between n_out[f] and maxN are
       // unspecified, like everything beyond n_out[f] in the caller's capacity-sized rows)
-      HIPCHK(hipMemcpy2DAsync(kps + (size_t)f0 * capacity, sizeof(orbx_keypoint) * (size_t)capacity, ctx->dKps,
+      HIPCHK(hipMemcpy2DAsync(kps + (size_t)f0 * capacity, sizeof(orbx_keypoint) * (size_t)capacity, ctx->bufs.dKps,
                               sizeof(orbx_keypoint) * (size_t)cap, sizeof(orbx_keypoint) * (size_t)maxN, B, hipMemcpyDeviceToHost,
                               ctx->st));
-      HIPCHK(hipMemcpy2DAsync(desc32 + (size_t)f0 * capacity * 32, (size_t)32 * capacity, ctx->dDesc, (size_t)32 * cap,
+      HIPCHK(hipMemcpy2DAsync(desc32 + (size_t)f0 * capacity * 32, (size_t)32 * capacity, ctx->bufs.dDesc, (size_t)32 * cap,
                               (size_t)32 * maxN, B, hipMemcpyDeviceToHost, ctx->st));
     }
     if (latTrace) tt[3] = nowUs();
@@ -1778,7 +1765,7 @@ int orbx_download_pyramid(orbx_ctx* ctx, int frame, int level, int border, uint8
   const LevelGeom& L = ctx->g.L[level];
   if (dst_stride < L.w + 2 * border) return ORBX_E_BADARG;
   const uint8_t* src = level == 0 ? ctx->lastImg0 + (long long)frame * ctx->lastFrameStride0
-                                  : ctx->dPyr + L.imgOff + (long long)frame * L.frameStride;
+                                  : ctx->bufs.dPyr + L.imgOff + (long long)frame * L.frameStride;
   HIPCHK(hipMemcpy2DAsync(dst + (size_t)border * dst_stride + border, dst_stride, src, L.stride, L.w, L.h, hipMemcpyDeviceToHost,
                           ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
@@ -1806,34 +1793,20 @@ int orbx_download_pyramid(orbx_ctx* ctx, int frame, int level, int border, uint8
 }  // extern "C"
 namespace {
 int ensureMatchScratch(orbx_ctx* ctx, int nPairs, int capacity) {
-  if (ctx->pending > 0 && ((size_t)nPairs * (size_t)matchScratchStride(capacity) > ctx->matchScratchInts || (size_t)nPairs > ctx->pairsCap)) {
-    const int w = waitAll(ctx);  // the buffers about to be replaced are in use
-    if (w != ORBX_OK) return w;
-  }
   // per pair: matchScratchStride(capacity) ints (orbx_device.h) -- the one function both this allocation and launch_match's
   // stride argument use; the kernels index a pair's area with [pair * stride, (pair + 1) * stride) and clamp their own
   // counts to the capacities the layout was computed from (queries / trains to matchWideCap(capacity), list entries per
   // query to MW_CP, per-frame counts to `capacity`)
+  const size_t bytes = sizeof(int) * nPairs * (size_t)matchScratchStride(capacity);
+  if (ctx->pending > 0 && bytes > ctx->dMatchScratch.bytes()) {
+    const int w = waitAll(ctx);  // the buffer about to be replaced is in use
+    if (w != ORBX_OK) return w;
+  }
   if (!ctx->dMatchDiag) {  // (diagnostic counters, orbx_debug_match_counters: 64 bytes, zero at first use)
-    HIPCHK(hipMalloc((void**)&ctx->dMatchDiag, 64));
+    HIPCHK(ctx->dMatchDiag.grow(64));
     HIPCHK(hipMemset(ctx->dMatchDiag, 0, 64));
   }
-  const size_t need = (size_t)nPairs * (size_t)matchScratchStride(capacity);
-  if (need > ctx->matchScratchInts) {
-    if (ctx->dMatchScratch) (void)hipFree(ctx->dMatchScratch);
-    ctx->dMatchScratch = nullptr;
-    ctx->matchScratchInts = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dMatchScratch, need * sizeof(int)));
-    ctx->matchScratchInts = need;
-  }
-  if ((size_t)nPairs > ctx->pairsCap) {
-    if (ctx->dPairs) (void)hipFree(ctx->dPairs);
-    ctx->dPairs = nullptr;
-    ctx->lastPairs.clear();
-    ctx->pairsCap = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dPairs, (size_t)nPairs * 2 * sizeof(int)));
-    ctx->pairsCap = nPairs;
-  }
+  HIPCHK(ctx->dMatchScratch.grow(bytes));
   return ORBX_OK;
 }
 
@@ -1841,23 +1814,15 @@ int ensureMatchScratch(orbx_ctx* ctx, int nPairs, int capacity) {
 // descriptor arrays of `cap` entries and a small int area
 int ensureHostPairBuffers(orbx_ctx* ctx, size_t cap) {
   if (cap <= ctx->mCap) return ORBX_OK;
-  if (ctx->dMblk) (void)hipFree(ctx->dMblk);
-  if (ctx->dMi) (void)hipFree(ctx->dMi);
-  if (ctx->hMblk) (void)hipHostFree(ctx->hMblk);
-  if (ctx->hMo) (void)hipHostFree(ctx->hMo);
-  ctx->dMblk = nullptr; ctx->hMblk = nullptr; ctx->hMo = nullptr; ctx->hMoDev = nullptr;
-  ctx->dMk = nullptr; ctx->dMd = nullptr; ctx->dMi = nullptr; ctx->mCap = 0;
-  const size_t descOff = (2 * cap * sizeof(orbx_keypoint) + 63) / 64 * 64, cntOff = descOff + 2 * cap * 32;
-  const size_t bytes = cntOff + 64;
-  HIPCHK(hipMalloc((void**)&ctx->dMblk, bytes));
-  HIPCHK(hipMalloc((void**)&ctx->dMi, (cap + 8) * sizeof(int)));
-  HIPCHK(hipHostMalloc((void**)&ctx->hMblk, bytes, hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&ctx->hMo, (cap + 8) * sizeof(int), hipHostMallocDefault));
-  HIPCHK(hipHostGetDevicePointer((void**)&ctx->hMoDev, ctx->hMo, 0));
+  ctx->mCap = 0;
+  const size_t bytes = PairBlock(nullptr, cap).bytes;
+  HIPCHK(ctx->dMblk.grow(bytes));
+  HIPCHK(ctx->dMi.grow((cap + 8) * sizeof(int)));
+  HIPCHK(ctx->hMblk.grow(bytes));
+  HIPCHK(ctx->hMo.grow((cap + 8) * sizeof(int), true));
   memset(ctx->hMblk, 0, bytes);
-  ctx->dMk = reinterpret_cast<orbx_keypoint*>(ctx->dMblk);
-  ctx->dMd = ctx->dMblk + descOff;
-  ctx->mBlkBytes = bytes; ctx->mDescOff = descOff; ctx->mCntOff = cntOff;
+  ctx->dM = PairBlock(ctx->dMblk, cap);
+  ctx->hM = PairBlock(ctx->hMblk, cap);
   ctx->mCap = cap;
   return ORBX_OK;
 }
@@ -1890,8 +1855,7 @@ int orbx_match_init_batch_device(orbx_ctx* ctx, int n_pairs, const int32_t* h_fi
   ctx->parity = (int)(ctx->seqIssue & 1u);
   r = ensureMatchScratch(ctx, n_pairs, capacity);
   if (r != ORBX_OK) return r;
-  bool copied = false;
-  r = uploadPairs(ctx, n_pairs, h_first, h_second, ctx->st, &copied);
+  r = uploadPairs(ctx, ctx->lastPairs, ctx->dPairs, n_pairs, h_first, h_second, true);
   if (r != ORBX_OK) return r;
   MatchArgs m;
   m.nPairs = n_pairs; m.b = *bounds; m.window = window_size; m.nnratio = nnratio; m.checkOri = check_orientation;
@@ -1987,18 +1951,22 @@ int hostBatchIssue(orbx_ctx* c, int n_frames, const uint8_t* h_imgs, int width, 
   }
   const int dstride = alignUp(width, 64);
   const size_t dfs = (size_t)dstride * height;
-  // the result block: [kps][desc][n][matches12][nmatches][stats], every part 256-byte aligned
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t oK = 0, oD = al(oK + sizeof(orbx_keypoint) * (size_t)capacity * n_frames), oN = al(oD + (size_t)32 * capacity * n_frames),
-               oM = al(oN + sizeof(int32_t) * (size_t)n_frames), oNm = al(oM + sizeof(int32_t) * (size_t)capacity * n_pairs),
-               oSt = al(oNm + sizeof(int32_t) * (size_t)n_pairs), total = al(oSt + sizeof(int32_t) * 3 * (size_t)n_pairs);
-  if (total > c->pipeOutBytes) {
-    if (c->dPipeOut) (void)hipFree(c->dPipeOut);
-    c->dPipeOut = nullptr;
-    c->pipeOutBytes = 0;
-    HIPCHK(hipMalloc((void**)&c->dPipeOut, total));
-    c->pipeOutBytes = total;
-  }
+  // the result block: [kps][desc][n][matches12][nmatches][stats]
+  orbx_keypoint* dK;
+  uint8_t* dD;
+  int32_t *dN, *dM, *dNm, *dSt;
+  auto results = [&](Layout L) {
+    dK = L.take<orbx_keypoint>((size_t)capacity * n_frames);
+    dD = L.take<uint8_t>((size_t)32 * capacity * n_frames);
+    dN = L.take<int32_t>(n_frames);
+    dM = L.take<int32_t>((size_t)capacity * n_pairs);
+    dNm = L.take<int32_t>(n_pairs);
+    dSt = L.take<int32_t>((size_t)3 * n_pairs);
+    return L.size();
+  };
+  HIPCHK(c->dPipeOut.grow(results(Layout())));
+  results(Layout(c->dPipeOut));
+  if (!h_stats) dSt = nullptr;
   for (int par = 0; par < 2; par++)
     // (release to SYSTEM scope: k_copy_out's stores into the caller's page-locked arrays must be visible to the host when the
     // event has completed, also for arrays allocated non-coherent -- ADVICE r05)
@@ -2009,22 +1977,16 @@ int hostBatchIssue(orbx_ctx* c, int n_frames, const uint8_t* h_imgs, int width, 
   // ---- upload (stream-ordered; asynchronous when the caller's memory is page-locked) ----
   if (frame_stride_bytes == (size_t)stride * height || n_frames == 1) {
     if (stride == dstride)
-      HIPCHK(hipMemcpyAsync(c->dIn, h_imgs, dfs * n_frames, hipMemcpyHostToDevice, c->st));
+      HIPCHK(hipMemcpyAsync(c->bufs.dIn, h_imgs, dfs * n_frames, hipMemcpyHostToDevice, c->st));
     else
-      HIPCHK(hipMemcpy2DAsync(c->dIn, dstride, h_imgs, stride, width, (size_t)height * n_frames, hipMemcpyHostToDevice, c->st));
+      HIPCHK(hipMemcpy2DAsync(c->bufs.dIn, dstride, h_imgs, stride, width, (size_t)height * n_frames, hipMemcpyHostToDevice, c->st));
   } else {
     for (int f = 0; f < n_frames; f++)
-      HIPCHK(hipMemcpy2DAsync(c->dIn + f * dfs, dstride, h_imgs + (size_t)f * frame_stride_bytes, stride, width, height,
+      HIPCHK(hipMemcpy2DAsync(c->bufs.dIn + f * dfs, dstride, h_imgs + (size_t)f * frame_stride_bytes, stride, width, height,
                               hipMemcpyHostToDevice, c->st));
   }
-  orbx_keypoint* dK = reinterpret_cast<orbx_keypoint*>(c->dPipeOut + oK);
-  uint8_t* dD = c->dPipeOut + oD;
-  int32_t* dN = reinterpret_cast<int32_t*>(c->dPipeOut + oN);
-  int32_t* dM = reinterpret_cast<int32_t*>(c->dPipeOut + oM);
-  int32_t* dNm = reinterpret_cast<int32_t*>(c->dPipeOut + oNm);
-  int32_t* dSt = h_stats ? reinterpret_cast<int32_t*>(c->dPipeOut + oSt) : nullptr;
   c->hostInput = true;
-  r = extractMatch(c, n_frames, c->dIn, width, height, dstride, dfs, dK, dD, capacity, dN, n_pairs, h_first, h_second, bounds,
+  r = extractMatch(c, n_frames, c->bufs.dIn, width, height, dstride, dfs, dK, dD, capacity, dN, n_pairs, h_first, h_second, bounds,
                    window_size, nnratio, check_orientation, dM, dNm, dSt, true);
   c->hostInput = false;
   if (r != ORBX_OK) return r;
@@ -2227,25 +2189,23 @@ int orbx_match_init(orbx_ctx* ctx, const orbx_keypoint* k1, const uint8_t* d1, i
   hipStream_t st = ctx->st;
   // the pair is packed into the page-locked mirror of the device block and goes up with one copy command; the matcher
   // kernels store matches, count and statistics straight into mapped page-locked words (0.13 -> 0.09 ms per call)
-  uint8_t* hb = ctx->hMblk;
+  const PairBlock& hb = ctx->hM;
   if (n1) {
-    memcpy(hb, k1, sizeof(orbx_keypoint) * n1);
-    memcpy(hb + ctx->mDescOff, d1, (size_t)32 * n1);
+    memcpy(hb.kps, k1, sizeof(orbx_keypoint) * n1);
+    memcpy(hb.desc, d1, (size_t)32 * n1);
   }
   if (n2) {
-    memcpy(hb + c * sizeof(orbx_keypoint), k2, sizeof(orbx_keypoint) * n2);
-    memcpy(hb + ctx->mDescOff + c * 32, d2, (size_t)32 * n2);
+    memcpy(hb.kps + c, k2, sizeof(orbx_keypoint) * n2);
+    memcpy(hb.desc + c * 32, d2, (size_t)32 * n2);
   }
-  int* hn = reinterpret_cast<int*>(hb + ctx->mCntOff);
-  hn[0] = n1; hn[1] = n2;
+  hb.n[0] = n1; hb.n[1] = n2;
   // (the block is private to the host-array entry points, which are synchronous: nothing in flight reads it)
-  HIPCHK(hipMemcpyAsync(ctx->dMblk, hb, ctx->mBlkBytes, hipMemcpyHostToDevice, st));
-  int* dN = reinterpret_cast<int*>(ctx->dMblk + ctx->mCntOff);  // [2]
-  int* oNm = ctx->hMoDev + 2;     // [1]
-  int* oSt = ctx->hMoDev + 3;     // [3]
-  int* oM12 = ctx->hMoDev + 8;    // [cap]
+  HIPCHK(hipMemcpyAsync(ctx->dMblk, ctx->hMblk, hb.bytes, hipMemcpyHostToDevice, st));
+  int* oNm = ctx->hMo.dev() + 2;     // [1]
+  int* oSt = ctx->hMo.dev() + 3;     // [3]
+  int* oM12 = ctx->hMo.dev() + 8;    // [cap]
   const int32_t first = 0, second = 1;
-  int r = orbx_match_init_batch_device(ctx, 1, &first, &second, ctx->dMk, ctx->dMd, dN, (int)c, bounds, window_size, nnratio,
+  int r = orbx_match_init_batch_device(ctx, 1, &first, &second, ctx->dM.kps, ctx->dM.desc, ctx->dM.n, (int)c, bounds, window_size, nnratio,
                                        check_orientation, oM12, oNm, oSt);
   if (r != ORBX_OK) return r;
   // (orbx_match_init_batch_device has synchronised the stream: the results are in host memory)
@@ -2276,10 +2236,11 @@ int orbx_undistort_keypoints(orbx_ctx* ctx, const orbx_keypoint* kps, int n, con
   if (er != ORBX_OK) return er;
   const size_t c = ctx->mCap;
   hipStream_t st = ctx->st;
-  HIPCHK(hipMemcpyAsync(ctx->dMk, kps, sizeof(orbx_keypoint) * n, hipMemcpyHostToDevice, st));
+  orbx_keypoint* dK = ctx->dM.kps;
+  HIPCHK(hipMemcpyAsync(dK, kps, sizeof(orbx_keypoint) * n, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->dMi, &n, sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(launch_undistort(st, 1, ctx->dMk, ctx->dMi, (int)c, makeCam(*cam), ctx->dMk + c));
-  HIPCHK(hipMemcpyAsync(out, ctx->dMk + c, sizeof(orbx_keypoint) * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(launch_undistort(st, 1, dK, ctx->dMi, (int)c, makeCam(*cam), dK + c));
+  HIPCHK(hipMemcpyAsync(out, dK + c, sizeof(orbx_keypoint) * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
@@ -2304,63 +2265,67 @@ int orbx_image_bounds(orbx_ctx* ctx, const orbx_camera* cam, int width, int heig
 
 // ---- Initializer scoring loops (Initialization/Initializer.cpp:268-438) ---------------------------
 namespace {
+// mvMatches12 (Initializer.cpp:24-33): the matched keypoints of frame 1 in order (first) and their partners (second); false
+// for a partner outside frame 2
+bool compactMatches(const int32_t* matches12, int n1, int n2, std::vector<int32_t>* first, std::vector<int32_t>* second) {
+  for (int i = 0; i < n1; i++)
+    if (matches12[i] >= 0) {
+      if (matches12[i] >= n2) return false;
+      first->push_back(i);
+      second->push_back(matches12[i]);
+    }
+  return true;
+}
+
 int checkModels(orbx_ctx* ctx, int kind, int n_models, const float* M21, const float* M12, const orbx_keypoint* k1, int n1,
                 const orbx_keypoint* k2, int n2, const int32_t* matches12, float sigma, float* scores, uint8_t* inliers,
                 int* n_matches_out, int* best) {
   if (!ctx || n_models < 0 || n1 < 0 || n2 < 0 || !n_matches_out || (n_models > 0 && (!M21 || (kind == 0 && !M12) || !scores)) ||
       (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2))
     return ORBX_E_BADARG;
-  // mvMatches12, Initializer.cpp:24-33
-  std::vector<int32_t> fs;
-  fs.reserve(2 * (size_t)n1);
-  for (int i = 0; i < n1; i++)
-    if (matches12[i] >= 0) {
-      if (matches12[i] >= n2) return ORBX_E_BADARG;
-      fs.push_back(i);
-    }
+  std::vector<int32_t> fs, sc;
+  if (!compactMatches(matches12, n1, n2, &fs, &sc)) return ORBX_E_BADARG;
   const int N = (int)fs.size();
-  for (int i = 0; i < N; i++) fs.push_back(matches12[fs[i]]);
   *n_matches_out = N;
   if (best) *best = -1;
   if (n_models == 0) return ORBX_OK;
   if (N > 0 && !inliers) return ORBX_E_BADARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  // one staging allocation: models | keypoints | pairs | scores | inliers
-  const size_t bM = (size_t)n_models * 9 * sizeof(float), bK1 = (size_t)n1 * sizeof(orbx_keypoint),
-               bK2 = (size_t)n2 * sizeof(orbx_keypoint), bP = (size_t)N * sizeof(int32_t), bS = (size_t)n_models * sizeof(float),
-               bI = (size_t)n_models * N;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t need = 2 * al(bM) + al(bK1) + al(bK2) + 2 * al(bP) + al(bS) + al(bI) + 256;
-  if (need > ctx->scoreBytes) {
-    if (ctx->dScore) (void)hipFree(ctx->dScore);
-    ctx->dScore = nullptr; ctx->scoreBytes = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dScore, need));
-    ctx->scoreBytes = need;
-  }
-  uint8_t* p = ctx->dScore;
+  // the batched form with one pair (frames {0, 0} of k1 / k2: the staged keypoint arrays) and the call's models as its
+  // hypotheses; one staging block: models | keypoints | matches | pair table | scores | inliers
   ScoreArgs a{};
+  int32_t* table;
+  auto staging = [&](Layout L) {
+    a.M21 = L.take<float>((size_t)n_models * 9);
+    a.M12 = L.take<float>((size_t)n_models * 9);
+    a.k1 = L.take<orbx_keypoint>(n1);
+    a.k2 = L.take<orbx_keypoint>(n2);
+    a.first = L.take<int32_t>(N);
+    a.second = L.take<int32_t>(N);
+    table = L.take<int32_t>(3);  // pairN[1], frames[2]
+    a.scores = L.take<float>(n_models);
+    a.inliers = L.take<uint8_t>((size_t)n_models * N);
+    return L.size();
+  };
+  HIPCHK(ctx->dScore.grow(staging(Layout())));
+  staging(Layout(ctx->dScore));
   hipStream_t st = ctx->st;
-  a.M21 = (const float*)p; p += al(bM);
-  a.M12 = (const float*)p; p += al(bM);
-  a.k1 = (const orbx_keypoint*)p; p += al(bK1);
-  a.k2 = (const orbx_keypoint*)p; p += al(bK2);
-  a.first = (const int32_t*)p; p += al(bP);
-  a.second = (const int32_t*)p; p += al(bP);
-  a.scores = (float*)p; p += al(bS);
-  a.inliers = p;
-  a.N = N; a.kind = kind;
+  const int32_t hTable[3] = {N, 0, 0};
+  a.pairN = table; a.frames = table + 1; a.perPair = n_models; a.stride = N; a.nPairs = 1; a.kind = kind;
   a.invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
+  const size_t bM = (size_t)n_models * 9 * sizeof(float);
   HIPCHK(hipMemcpyAsync((void*)a.M21, M21, bM, hipMemcpyHostToDevice, st));
   if (kind == 0) HIPCHK(hipMemcpyAsync((void*)a.M12, M12, bM, hipMemcpyHostToDevice, st));
-  if (n1) HIPCHK(hipMemcpyAsync((void*)a.k1, k1, bK1, hipMemcpyHostToDevice, st));
-  if (n2) HIPCHK(hipMemcpyAsync((void*)a.k2, k2, bK2, hipMemcpyHostToDevice, st));
+  if (n1) HIPCHK(hipMemcpyAsync((void*)a.k1, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  if (n2) HIPCHK(hipMemcpyAsync((void*)a.k2, k2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
   if (N) {
-    HIPCHK(hipMemcpyAsync((void*)a.first, fs.data(), bP, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((void*)a.second, fs.data() + N, bP, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)a.first, fs.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)a.second, sc.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
+  HIPCHK(hipMemcpyAsync(table, hTable, sizeof hTable, hipMemcpyHostToDevice, st));
   HIPCHK(launch_check_model(st, n_models, a));
-  HIPCHK(hipMemcpyAsync(scores, a.scores, bS, hipMemcpyDeviceToHost, st));
-  if (N) HIPCHK(hipMemcpyAsync(inliers, a.inliers, bI, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(scores, a.scores, (size_t)n_models * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (N) HIPCHK(hipMemcpyAsync(inliers, a.inliers, (size_t)n_models * N, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (best) {  // `if (currentScore > score)` with score starting at 0, Initializer.cpp:205-209 / 259-263
     float sc = 0;
@@ -2391,15 +2356,10 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
       (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2) || (n_models > 0 && n1 > 0 && (!tri_good || !p3d)))
     return ORBX_E_BADARG;
   if (n_models == 0) return ORBX_OK;
-  // mvMatches12 (Initializer.cpp:24-33), then the inliers in match order (:617-622); the i-th of them is booked under the
-  // i-th MATCH's first keypoint (:643, :700: the reference indexes vMatches12 with the compacted index)
+  // mvMatches12, then the inliers in match order (:617-622); the i-th of them is booked under the i-th MATCH's first keypoint
+  // (:643, :700: the reference indexes vMatches12 with the compacted index)
   std::vector<int32_t> fs, sc;
-  for (int i = 0; i < n1; i++)
-    if (matches12[i] >= 0) {
-      if (matches12[i] >= n2) return ORBX_E_BADARG;
-      fs.push_back(i);
-      sc.push_back(matches12[i]);
-    }
+  if (!compactMatches(matches12, n1, n2, &fs, &sc)) return ORBX_E_BADARG;
   const int N = (int)fs.size();
   if (N > 0 && !matches_inliers) return ORBX_E_BADARG;
   std::vector<float> pts;
@@ -2412,42 +2372,42 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
     }
   const int nInl = (int)book.size();
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t bR = (size_t)n_models * 9 * 4, bT = (size_t)n_models * 3 * 4, bP = (size_t)nInl * 16, bB = (size_t)nInl * 4,
-               bG = (size_t)n_models * n1, bX = (size_t)n_models * n1 * 12, bC = (size_t)n_models * nInl * 4, bN = (size_t)n_models * 4;
-  const size_t need = al(bR) + al(bT) + al(bP) + al(bB) + al(bG) + al(bX) + al(bC) + 2 * al(bN) + 256;
-  if (need > ctx->scoreBytes) {
-    if (ctx->dScore) (void)hipFree(ctx->dScore);
-    ctx->dScore = nullptr; ctx->scoreBytes = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dScore, need));
-    ctx->scoreBytes = need;
-  }
-  uint8_t* p = ctx->dScore;
+  // the batched form with one pair whose n_models candidates are all solutions (stride n1 >= nInl)
   CheckRtArgs a{};
+  int32_t* table;
+  auto staging = [&](Layout L) {
+    a.R21 = L.take<float>((size_t)n_models * 9);
+    a.t21 = L.take<float>((size_t)n_models * 3);
+    a.pts = L.take<float>((size_t)nInl * 4);
+    a.book = L.take<int32_t>(nInl);
+    table = L.take<int32_t>(2);  // pairNInl[1], pairNSol[1]
+    a.good = L.take<uint8_t>((size_t)n_models * n1);
+    a.p3d = L.take<float>((size_t)n_models * n1 * 3);
+    a.cosBuf = L.take<float>((size_t)n_models * n1);
+    a.nGood = L.take<int32_t>(n_models);
+    a.parallax = L.take<float>(n_models);
+    return L.size();
+  };
+  HIPCHK(ctx->dScore.grow(staging(Layout())));
+  staging(Layout(ctx->dScore));
   hipStream_t st = ctx->st;
-  a.R21 = (const float*)p; p += al(bR);
-  a.t21 = (const float*)p; p += al(bT);
-  a.pts = (const float*)p; p += al(bP);
-  a.book = (const int32_t*)p; p += al(bB);
-  a.good = p; p += al(bG);
-  a.p3d = (float*)p; p += al(bX);
-  a.cosBuf = (float*)p; p += al(bC);
-  a.nGood = (int32_t*)p; p += al(bN);
-  a.parallax = (float*)p;
+  const int32_t hTable[2] = {nInl, n_models};
   for (int i = 0; i < 9; i++) a.K[i] = K[i];
-  a.th2 = th2; a.nInl = nInl; a.n1 = n1;
-  HIPCHK(hipMemcpyAsync((void*)a.R21, R21, bR, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync((void*)a.t21, t21, bT, hipMemcpyHostToDevice, st));
+  a.th2 = th2;
+  a.pairNInl = table; a.pairNSol = table + 1; a.perPair = n_models; a.stride = n1;
+  HIPCHK(hipMemcpyAsync((void*)a.R21, R21, (size_t)n_models * 9 * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync((void*)a.t21, t21, (size_t)n_models * 3 * 4, hipMemcpyHostToDevice, st));
   if (nInl) {
-    HIPCHK(hipMemcpyAsync((void*)a.pts, pts.data(), bP, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((void*)a.book, book.data(), bB, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)a.pts, pts.data(), (size_t)nInl * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)a.book, book.data(), (size_t)nInl * 4, hipMemcpyHostToDevice, st));
   }
+  HIPCHK(hipMemcpyAsync(table, hTable, sizeof hTable, hipMemcpyHostToDevice, st));
   HIPCHK(launch_check_rt(st, n_models, a));
-  HIPCHK(hipMemcpyAsync(n_good, a.nGood, bN, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(parallax, a.parallax, bN, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(n_good, a.nGood, (size_t)n_models * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(parallax, a.parallax, (size_t)n_models * 4, hipMemcpyDeviceToHost, st));
   if (n1) {
-    HIPCHK(hipMemcpyAsync(tri_good, a.good, bG, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(p3d, a.p3d, bX, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(tri_good, a.good, (size_t)n_models * n1, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(p3d, a.p3d, (size_t)n_models * n1 * 12, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
@@ -2455,41 +2415,6 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
 
 // ---- the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ----------------------------------
 namespace {
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-// bytes of the batched stage's work area
-size_t findModelsWorkBytes(int nPairs, int nIter, int cap) {
-  const size_t P = nPairs, H = (size_t)nPairs * nIter, C = cap;
-  return 3 * al256(P * 4) + 2 * al256(P * C * 4) + 3 * al256(H * 36) + al256(2 * H) + 2 * al256(H * 4) + 2 * al256(H * C) +
-         al256(P * sizeof(orbx_hf_result)) + al256(P * 2 * C);
-}
-// the reconstruction's part: candidates, counts, CheckRT inputs and outputs
-size_t reconWorkBytes(int nPairs, int cap) {
-  const size_t P = nPairs, C = cap, M = 4 * P;
-  return al256(M * 36) + al256(M * 12) + 2 * al256(P * 4) + al256(P * C * 16) + al256(P * C * 4) + al256(M * 4) * 2 +
-         al256(M * C) + al256(M * C * 12) + al256(M * C * 4);
-}
-// the pair list through the context's own copy; a changed list waits for the work that may still read the previous one
-int uploadInitPairs(orbx_ctx* ctx, int n_pairs, const int32_t* h_first, const int32_t* h_second) {
-  std::vector<int32_t>& lp = ctx->initPairs;
-  if ((int)lp.size() == 2 * n_pairs && std::memcmp(lp.data(), h_first, 4 * (size_t)n_pairs) == 0 &&
-      std::memcmp(lp.data() + n_pairs, h_second, 4 * (size_t)n_pairs) == 0)
-    return ORBX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->st));
-  if (ctx->initPairsCap < (size_t)2 * n_pairs) {
-    if (ctx->dInitPairs) (void)hipFree(ctx->dInitPairs);
-    ctx->dInitPairs = nullptr; ctx->initPairsCap = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dInitPairs, (size_t)8 * n_pairs));
-    ctx->initPairsCap = (size_t)2 * n_pairs;
-  }
-  lp.assign(h_first, h_first + n_pairs);
-  lp.insert(lp.end(), h_second, h_second + n_pairs);
-  if (hipMemcpyAsync(ctx->dInitPairs, lp.data(), (size_t)8 * n_pairs, hipMemcpyHostToDevice, ctx->st) != hipSuccess) {
-    lp.clear();
-    ctx->err = "hipMemcpyAsync (initializer pair list)";
-    return ORBX_E_HIP;
-  }
-  return ORBX_OK;
-}
 struct ReconParams {
   const float* K;
   float minParallax;
@@ -2498,86 +2423,88 @@ struct ReconParams {
   float* p3d;
   uint8_t* tri;
 };
-int ensureInitArena(orbx_ctx* ctx, size_t need) {
-  if (need <= ctx->initBytes) return ORBX_OK;
-  if (ctx->dInit) {
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    (void)hipFree(ctx->dInit);
+// findModels' work area over `L`: its arrays into a (the H and F scores and inlier flags into sH / sF, CheckRT's into c) in
+// order; with `recon`, the reconstruction's part follows.  Returns the area's size.
+size_t initWork(Layout L, int nPairs, int nIter, int cap, bool recon, InitArgs& a, ScoreArgs& sH, ScoreArgs& sF, CheckRtArgs& c) {
+  const size_t P = nPairs, H = (size_t)nPairs * nIter, C = cap, M = 4 * P;
+  a.N = L.take<int32_t>(P);
+  a.scoreN = L.take<int32_t>(P);
+  a.pstat = L.take<int32_t>(P);
+  a.first = L.take<int32_t>(P * C);
+  a.second = L.take<int32_t>(P * C);
+  a.H21 = L.take<float>(H * 9);
+  a.H12 = L.take<float>(H * 9);
+  a.F21 = L.take<float>(H * 9);
+  a.flags = L.take<uint8_t>(2 * H);
+  sH.scores = L.take<float>(H);
+  sF.scores = L.take<float>(H);
+  sH.inliers = L.take<uint8_t>(H * C);
+  sF.inliers = L.take<uint8_t>(H * C);
+  a.res = L.take<orbx_hf_result>(P);
+  a.inlOut = L.take<uint8_t>(P * 2 * C);
+  if (recon) {
+    a.R4 = L.take<float>(M * 9);
+    a.t4 = L.take<float>(M * 3);
+    a.nSol = L.take<int32_t>(P);
+    a.nInl = L.take<int32_t>(P);
+    a.pts = L.take<float>(P * C * 4);
+    a.book = L.take<int32_t>(P * C);
+    c.nGood = L.take<int32_t>(M);
+    c.parallax = L.take<float>(M);
+    c.good = L.take<uint8_t>(M * C);
+    c.p3d = L.take<float>(M * C * 3);
+    c.cosBuf = L.take<float>(M * C);
   }
-  ctx->dInit = nullptr; ctx->initBytes = 0;
-  HIPCHK(hipMalloc((void**)&ctx->dInit, need));
-  ctx->initBytes = need;
-  return ORBX_OK;
+  return L.size();
 }
-// prep -> solve -> score H -> score F -> select, all on the context stream; `work` holds findModelsWorkBytes; d_models /
+size_t initWorkSize(int nPairs, int nIter, int cap, bool recon) {
+  InitArgs a{};
+  ScoreArgs sH{}, sF{};
+  CheckRtArgs c{};
+  return initWork(Layout(), nPairs, nIter, cap, recon, a, sH, sF, c);
+}
+// prep -> solve -> score H -> score F -> select, all on the context stream; `work` holds the work area (initWork); d_models /
 // d_scores (nullable) take the hypotheses and their scores in place of the work area's arrays
 int findModels(orbx_ctx* ctx, uint8_t* work, int n_pairs, const int32_t* h_first, const int32_t* h_second, const orbx_keypoint* d_kps,
                const int32_t* d_n, int cap, const int32_t* d_m12, int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res,
                uint8_t* d_inliers, float* d_models, float* d_scores, const ReconParams* rc) {
   hipStream_t st = ctx->st;
-  const size_t P = n_pairs, H = (size_t)n_pairs * n_iter, C = cap;
-  int r = uploadInitPairs(ctx, n_pairs, h_first, h_second);
+  const size_t H = (size_t)n_pairs * n_iter;
+  int r = uploadPairs(ctx, ctx->initPairs, ctx->dInitPairs, n_pairs, h_first, h_second, false);
   if (r != ORBX_OK) return r;
-  uint8_t* p = work;
   InitArgs a{};
-  int32_t* frames = ctx->dInitPairs;
-  a.N = (int32_t*)p; p += al256(P * 4);
-  a.scoreN = (int32_t*)p; p += al256(P * 4);
-  a.pstat = (int32_t*)p; p += al256(P * 4);
-  a.first = (int32_t*)p; p += al256(P * C * 4);
-  a.second = (int32_t*)p; p += al256(P * C * 4);
-  float* models = (float*)p; p += 3 * al256(H * 36);
-  if (d_models) models = d_models;
-  a.H21 = models; a.H12 = models + H * 9; a.F21 = models + 2 * H * 9;
-  a.flags = p; p += al256(2 * H);
-  float* scores = (float*)p; p += 2 * al256(H * 4);
-  if (d_scores) scores = d_scores;
-  a.scoresH = scores; a.scoresF = scores + H;
-  uint8_t* inlH = p; p += al256(H * C);
-  uint8_t* inlF = p; p += al256(H * C);
-  a.inlH = inlH; a.inlF = inlF;
-  a.kps = d_kps; a.nKps = d_n; a.m12 = d_m12; a.sets = d_sets; a.frames = frames;
-  a.nPairs = n_pairs; a.nIter = n_iter; a.cap = cap;
-  orbx_hf_result* hf = (orbx_hf_result*)p; p += al256(P * sizeof(orbx_hf_result));
-  uint8_t* inlKept = p; p += al256(P * 2 * C);
-  a.res = d_res ? d_res : hf;
-  a.inlOut = d_inliers ? d_inliers : inlKept;
+  ScoreArgs sH{}, sF{};
   CheckRtArgs c{};
+  initWork(Layout(work), n_pairs, n_iter, cap, rc != nullptr, a, sH, sF, c);
+  if (d_models) { a.H21 = d_models; a.H12 = d_models + H * 9; a.F21 = d_models + 2 * H * 9; }
+  if (d_scores) { sH.scores = d_scores; sF.scores = d_scores + H; }
+  if (d_res) a.res = d_res;
+  if (d_inliers) a.inlOut = d_inliers;
+  a.scoresH = sH.scores; a.scoresF = sF.scores; a.inlH = sH.inliers; a.inlF = sF.inliers;
+  a.kps = d_kps; a.nKps = d_n; a.m12 = d_m12; a.sets = d_sets; a.frames = ctx->dInitPairs;
+  a.nPairs = n_pairs; a.nIter = n_iter; a.cap = cap;
   if (rc) {
     a.reconstruct = 1;
     for (int i = 0; i < 9; i++) a.K[i] = rc->K[i];
     a.minParallax = rc->minParallax; a.minTriangulated = rc->minTriangulated;
-    const size_t M = 4 * P;
-    a.R4 = (float*)p; p += al256(M * 36);
-    a.t4 = (float*)p; p += al256(M * 12);
-    a.nSol = (int32_t*)p; p += al256(P * 4);
-    a.nInl = (int32_t*)p; p += al256(P * 4);
-    a.pts = (float*)p; p += al256(P * C * 16);
-    a.book = (int32_t*)p; p += al256(P * C * 4);
-    int32_t* nGood = (int32_t*)p; p += al256(M * 4);
-    float* par = (float*)p; p += al256(M * 4);
-    uint8_t* good = p; p += al256(M * C);
-    float* p3d = (float*)p; p += al256(M * C * 12);
-    float* cosBuf = (float*)p;
-    a.nGood = nGood; a.parallax = par; a.good = good; a.p3d4 = p3d;
+    a.nGood = c.nGood; a.parallax = c.parallax; a.good = c.good; a.p3d4 = c.p3d;
     a.ires = rc->res; a.p3dOut = rc->p3d; a.triOut = rc->tri;
     c.R21 = a.R4; c.t21 = a.t4; c.pts = a.pts; c.book = a.book;
     for (int i = 0; i < 9; i++) c.K[i] = rc->K[i];
     c.th2 = (float)(4.0 * (double)(sigma * sigma));  // `4.0 * mSigma2` (:499), mSigma2 = sigma * sigma (f32)
-    c.nInl = 0; c.n1 = cap;
-    c.good = good; c.p3d = p3d; c.cosBuf = cosBuf; c.nGood = nGood; c.parallax = par;
     c.pairNInl = a.nInl; c.pairNSol = a.nSol; c.perPair = 4; c.stride = cap;
   }
   HIPCHK(launch_init_prep(st, a));
   HIPCHK(launch_init_solve(st, a));
-  ScoreArgs s{};
-  s.k1 = d_kps; s.k2 = d_kps; s.first = a.first; s.second = a.second;
-  s.invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
-  s.pairN = a.scoreN; s.frames = frames; s.perPair = n_iter; s.stride = cap; s.nPairs = n_pairs;
-  s.kind = 0; s.M21 = a.H21; s.M12 = a.H12; s.scores = scores; s.inliers = inlH;
-  HIPCHK(launch_check_model(st, (int)H, s));
-  s.kind = 1; s.M21 = a.F21; s.M12 = nullptr; s.scores = scores + H; s.inliers = inlF;
-  HIPCHK(launch_check_model(st, (int)H, s));
+  for (ScoreArgs* s : {&sH, &sF}) {
+    s->k1 = d_kps; s->k2 = d_kps; s->first = a.first; s->second = a.second;
+    s->invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
+    s->pairN = a.scoreN; s->frames = a.frames; s->perPair = n_iter; s->stride = cap; s->nPairs = n_pairs;
+  }
+  sH.kind = 0; sH.M21 = a.H21; sH.M12 = a.H12;
+  sF.kind = 1; sF.M21 = a.F21; sF.M12 = nullptr;
+  HIPCHK(launch_check_model(st, (int)H, sH));
+  HIPCHK(launch_check_model(st, (int)H, sF));
   HIPCHK(launch_init_select(st, a));
   if (rc) {
     HIPCHK(launch_check_rt(st, 4 * n_pairs, c));
@@ -2609,8 +2536,7 @@ int orbx_find_models_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, cons
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
   r = waitAll(ctx);  // batches issued with the _async calls may still be writing the inputs
   if (r != ORBX_OK) return r;
-  r = ensureInitArena(ctx, findModelsWorkBytes(n_pairs, n_iter, capacity));
-  if (r != ORBX_OK) return r;
+  HIPCHK(ctx->dInit.grow(initWorkSize(n_pairs, n_iter, capacity, false), ctx->st));  // (behind the work that may still use it)
   return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res,
                     d_inliers, d_models, d_scores, nullptr);
 }
@@ -2625,8 +2551,7 @@ int orbx_initialize_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
   r = waitAll(ctx);
   if (r != ORBX_OK) return r;
-  r = ensureInitArena(ctx, findModelsWorkBytes(n_pairs, n_iter, capacity) + reconWorkBytes(n_pairs, capacity));
-  if (r != ORBX_OK) return r;
+  HIPCHK(ctx->dInit.grow(initWorkSize(n_pairs, n_iter, capacity, true), ctx->st));
   const ReconParams rc{K, min_parallax, min_triangulated, d_res, d_p3d, d_triangulated};
   return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, nullptr,
                     nullptr, nullptr, nullptr, &rc);
@@ -2645,24 +2570,29 @@ int singlePair(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoi
   int r = waitAll(ctx);
   if (r != ORBX_OK) return r;
   const int cap = std::max(std::max(n1, n2), 1);
-  const size_t work = findModelsWorkBytes(1, n_iter, cap) + (ires ? reconWorkBytes(1, cap) : 0);
-  const size_t bK = al256((size_t)2 * cap * sizeof(orbx_keypoint)), bN = al256(8), bM = al256((size_t)cap * 4),
-               bS = al256((size_t)n_iter * 32), bR = al256(sizeof(orbx_hf_result) + sizeof(orbx_init_result)), bI = al256((size_t)2 * cap),
-               bMo = al256((size_t)3 * n_iter * 36), bSo = al256((size_t)2 * n_iter * 4), bP = al256((size_t)cap * 12), bT = al256(cap);
-  r = ensureInitArena(ctx, work + bK + bN + bM + bS + bR + bI + bMo + bSo + bP + bT);
-  if (r != ORBX_OK) return r;
-  uint8_t* p = ctx->dInit + work;
-  orbx_keypoint* dK = (orbx_keypoint*)p; p += bK;
-  int32_t* dN = (int32_t*)p; p += bN;
-  int32_t* dM = (int32_t*)p; p += bM;
-  int32_t* dS = (int32_t*)p; p += bS;
-  orbx_hf_result* dR = (orbx_hf_result*)p;
-  orbx_init_result* dIR = (orbx_init_result*)(p + sizeof(orbx_hf_result)); p += bR;
-  uint8_t* dI = p; p += bI;
-  float* dMo = (float*)p; p += bMo;
-  float* dSo = (float*)p; p += bSo;
-  float* dP = (float*)p; p += bP;
-  uint8_t* dT = p;
+  const size_t work = initWorkSize(1, n_iter, cap, ires != nullptr);
+  orbx_keypoint* dK;  // [2][cap]
+  int32_t *dN, *dM, *dS;
+  orbx_hf_result* dR;
+  orbx_init_result* dIR;
+  uint8_t *dI, *dT;
+  float *dMo, *dSo, *dP;
+  auto staging = [&](Layout L) {  // behind the work area
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dS = L.take<int32_t>((size_t)n_iter * 8);
+    dR = L.take<orbx_hf_result>(1);
+    dIR = L.take<orbx_init_result>(1);
+    dI = L.take<uint8_t>((size_t)2 * cap);
+    dMo = L.take<float>((size_t)3 * n_iter * 9);
+    dSo = L.take<float>((size_t)2 * n_iter);
+    dP = L.take<float>((size_t)cap * 3);
+    dT = L.take<uint8_t>(cap);
+    return L.size();
+  };
+  HIPCHK(ctx->dInit.grow(work + staging(Layout()), ctx->st));
+  staging(Layout(ctx->dInit + work));
   hipStream_t st = ctx->st;
   const int32_t hn[2] = {n1, n2};
   if (n1) HIPCHK(hipMemcpyAsync(dK, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
@@ -2737,13 +2667,7 @@ int orbx_to_gray(orbx_ctx* ctx, const uint8_t* img, int width, int height, int s
   if (!gray || height > 65535 || (long long)stride < (long long)width * channels || gray_stride < width) return ORBX_E_BADARG;
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
   const int sstride = alignUp(width * channels, 64), gstride = alignUp(width, 64);
-  const size_t need = ((size_t)sstride + gstride) * height;
-  if (need > ctx->colorBytes) {
-    if (ctx->dColor) (void)hipFree(ctx->dColor);
-    ctx->dColor = nullptr; ctx->colorBytes = 0;
-    HIPCHK(hipMalloc((void**)&ctx->dColor, need));
-    ctx->colorBytes = need;
-  }
+  HIPCHK(ctx->dColor.grow(((size_t)sstride + gstride) * height));
   uint8_t* dG = ctx->dColor + (size_t)sstride * height;
   HIPCHK(hipMemcpy2DAsync(ctx->dColor, sstride, img, stride, (size_t)width * channels, height, hipMemcpyHostToDevice, ctx->st));
   HIPCHK(launch_to_gray(ctx->st, 1, ctx->dColor, 0, sstride, width, height, channels, rgb, dG, 0, gstride, ctx->grayVariant));
@@ -2796,10 +2720,10 @@ int orbx_debug_candidates(orbx_ctx* ctx, int frame, int level, float* xyr, int c
   // gather the cells' segments (k_fast writes every cell's survivors into the cell's own segment)
   const int nCells = L.nCols * L.nRows;
   std::vector<int> cc(std::max(nCells, 1));
-  HIPCHK(hipMemcpy(cc.data(), ctx->dCellCount + (size_t)frame * ctx->g.nCellsTotal + L.cellBase, sizeof(int) * (size_t)nCells,
+  HIPCHK(hipMemcpy(cc.data(), ctx->bufs.dCellCount + (size_t)frame * ctx->g.nCellsTotal + L.cellBase, sizeof(int) * (size_t)nCells,
                    hipMemcpyDeviceToHost));
   std::vector<uint32_t> seg((size_t)std::max(L.candCap, 1));
-  HIPCHK(hipMemcpy(seg.data(), ctx->dCand + L.candOff + (int64_t)frame * L.candCap, (size_t)L.candCap * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(seg.data(), ctx->bufs.dCand + L.candOff + (int64_t)frame * L.candCap, (size_t)L.candCap * 4, hipMemcpyDeviceToHost));
   std::vector<uint32_t> e;
   for (int c = 0; c < nCells; c++)
     for (int k = 0; k < cc[c]; k++) e.push_back(seg[(size_t)c * L.segCap + k]);
@@ -2824,7 +2748,7 @@ int orbx_debug_selection_units(orbx_ctx* ctx, int frame, int32_t* counts, int32_
   }
   const int nl = ctx->p.nlevels;
   std::vector<int32_t> raw((size_t)nl);
-  HIPCHK(hipMemcpy(raw.data(), ctx->dNselLevel + (size_t)frame * nl, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(raw.data(), ctx->bufs.dNselLevel + (size_t)frame * nl, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost));
   for (int l = 0; l < nl; l++) {
     counts[l] = raw[l] < 0 ? raw[l] : (raw[l] & ~ORBX_OCT_REDONE);
     if (redone) redone[l] = raw[l] >= 0 && (raw[l] & ORBX_OCT_REDONE) ? 1 : 0;
@@ -2886,40 +2810,29 @@ int orbx_debug_distribute_device(orbx_ctx* ctx, const float* xyr, int n, int min
   octTabLayout(&P);
   std::vector<uint32_t> codeTab;
   octCodeTables(&P, &codeTab);
-  uint32_t* dC = nullptr;
-  uint32_t* dT = nullptr;
-  int* dI = nullptr;
-  SelKp* dS = nullptr;
-  uint8_t* dScr = nullptr;
   std::vector<SelKp> sel(std::max(n_features, 1));
   int res[2] = {0, 0};
-  auto body = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&dC, packed.size() * 4));
-    HIPCHK(hipMalloc((void**)&dI, 2 * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&dS, sel.size() * sizeof(SelKp)));
-    HIPCHK(hipMalloc((void**)&dScr, (size_t)P.scrStride[0]));
-    HIPCHK(hipMalloc((void**)&dT, codeTab.size() * 4));
-    P.codeTab = dT;
-    HIPCHK(hipMemcpyAsync(dT, codeTab.data(), codeTab.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(dC, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    int hi[2] = {n, -7};
-    HIPCHK(hipMemcpyAsync(dI, hi, sizeof hi, hipMemcpyHostToDevice, ctx->st));
-    const int hintN[ORBX_MAX_LEVELS] = {n};  // (variant 5: the bucket depth from the candidate count, as in the pipeline; 6: from the area)
-    HIPCHK(launch_octree(ctx->st, 1, dC, dI, P, dS, dI + 1, dScr, nullptr, variant == 5 ? hintN : nullptr,
-                         variant == 1 ? -1 : variant == 2 ? 1024 : variant == 3 ? 512 : variant == 4 ? (2048 | 0x10000) : variant == 5 ? -2 :
-                         variant == 6 ? -3 : 0, nullptr));
-    HIPCHK(hipMemcpyAsync(res, dI, sizeof res, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(sel.data(), dS, sel.size() * sizeof(SelKp), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    return ORBX_OK;
-  };
-  const int rc = body();
-  if (dC) (void)hipFree(dC);
-  if (dI) (void)hipFree(dI);
-  if (dS) (void)hipFree(dS);
-  if (dScr) (void)hipFree(dScr);
-  if (dT) (void)hipFree(dT);
-  if (rc != ORBX_OK) return rc;
+  DeviceBuf<uint32_t> dC, dT;
+  DeviceBuf<int> dI;
+  DeviceBuf<SelKp> dS;
+  DeviceBuf<uint8_t> dScr;
+  HIPCHK(dC.grow(packed.size() * 4));
+  HIPCHK(dI.grow(2 * sizeof(int)));
+  HIPCHK(dS.grow(sel.size() * sizeof(SelKp)));
+  HIPCHK(dScr.grow((size_t)P.scrStride[0]));
+  HIPCHK(dT.grow(codeTab.size() * 4));
+  P.codeTab = dT;
+  HIPCHK(hipMemcpyAsync(dT, codeTab.data(), codeTab.size() * 4, hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(hipMemcpyAsync(dC, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, ctx->st));
+  int hi[2] = {n, -7};
+  HIPCHK(hipMemcpyAsync(dI, hi, sizeof hi, hipMemcpyHostToDevice, ctx->st));
+  const int hintN[ORBX_MAX_LEVELS] = {n};  // (variant 5: the bucket depth from the candidate count, as in the pipeline; 6: from the area)
+  HIPCHK(launch_octree(ctx->st, 1, dC, dI, P, dS, dI + 1, dScr, nullptr, variant == 5 ? hintN : nullptr,
+                       variant == 1 ? -1 : variant == 2 ? 1024 : variant == 3 ? 512 : variant == 4 ? (2048 | 0x10000) : variant == 5 ? -2 :
+                       variant == 6 ? -3 : 0, nullptr));
+  HIPCHK(hipMemcpyAsync(res, dI, sizeof res, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipMemcpyAsync(sel.data(), dS, sel.size() * sizeof(SelKp), hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
   if (res[1] < 0) return ORBX_E_CAPACITY;
   res[1] &= ~0x40000000;  // (ORBX_OCT_REDONE: the many-workgroup kernels handed the unit to the one-workgroup code)
   for (int i = 0; i < res[1] && i < cap; i++) {
@@ -3005,40 +2918,29 @@ int orbx_debug_sincos(orbx_ctx* ctx, const float* angle_deg, int n, float* cos_o
   if (!ctx || n < 0 || (n > 0 && (!angle_deg || !cos_out || !sin_out))) return ORBX_E_BADARG;
   if (n == 0) return ORBX_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  float* d = nullptr;
-  auto body = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&d, (size_t)n * 3 * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(d, angle_deg, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(launch_debug_sincos(ctx->st, d, n, d + n, d + 2 * (size_t)n, ctx->libmVariant));
-    HIPCHK(hipMemcpyAsync(cos_out, d + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(sin_out, d + 2 * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    return ORBX_OK;
-  };
-  const int rc = body();
-  if (d) (void)hipFree(d);
-  return rc;
+  DeviceBuf<float> d;
+  HIPCHK(d.grow((size_t)n * 3 * sizeof(float)));
+  HIPCHK(hipMemcpyAsync(d, angle_deg, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(launch_debug_sincos(ctx->st, d, n, d + n, d + 2 * (size_t)n, ctx->libmVariant));
+  HIPCHK(hipMemcpyAsync(cos_out, d + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipMemcpyAsync(sin_out, d + 2 * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  return ORBX_OK;
 }
 
 int orbx_debug_std_sort(orbx_ctx* ctx, int32_t* triples, int n) {
   if (!ctx || n < 0 || (n > 0 && !triples)) return ORBX_E_BADARG;
   if (n == 0) return ORBX_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  int* d = nullptr;
-  unsigned long long* w = nullptr;
-  auto body = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&d, (size_t)n * 3 * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&w, (size_t)n * 2 * sizeof(unsigned long long)));
-    HIPCHK(hipMemcpyAsync(d, triples, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(launch_debug_sort(ctx->st, d, n, w, w + n));
-    HIPCHK(hipMemcpyAsync(triples, d, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    return ORBX_OK;
-  };
-  const int rc = body();
-  if (d) (void)hipFree(d);
-  if (w) (void)hipFree(w);
-  return rc;
+  DeviceBuf<int> d;
+  DeviceBuf<unsigned long long> w;
+  HIPCHK(d.grow((size_t)n * 3 * sizeof(int)));
+  HIPCHK(w.grow((size_t)n * 2 * sizeof(unsigned long long)));
+  HIPCHK(hipMemcpyAsync(d, triples, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(launch_debug_sort(ctx->st, d, n, w, w + n));
+  HIPCHK(hipMemcpyAsync(triples, d, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  return ORBX_OK;
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "orbx_buf.h"
 #include "orbx_device.h"
 
 namespace orbx {
@@ -32,15 +33,12 @@ struct orbx_vocabulary {
   int device = 0;
   int k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;
   int nStaged = 0;            // breadth-first nodes k_bow_descend stages in LDS
-  BowNode* dNodes = nullptr;  // [nNodes + 1]
-  uint32_t* dDesc = nullptr;  // [nNodes + 1][8]
+  DeviceBuf<BowNode> dNodes;  // [nNodes + 1]
+  DeviceBuf<uint32_t> dDesc;  // [nNodes + 1][8]
   // scratch of the calls (grown on demand; the stream is drained before a buffer is replaced)
-  uint32_t* dScratch = nullptr;  // fin, nid: [2][frames * capacity]
-  size_t scratchEntries = 0;
-  uint8_t* dIo = nullptr;  // orbx_bow_transform's frame in device memory: descriptors, count, outputs
-  size_t ioBytes = 0;
-  int32_t* dPairs = nullptr;  // orbx_bow_score_batch_device's pair list [2][n_pairs]
-  size_t pairsCap = 0;
+  DeviceBuf<uint32_t> dScratch;  // fin, nid: [2][frames * capacity]
+  DeviceBuf<uint8_t> dIo;        // staging of orbx_bow_transform / orbx_bow_score
+  DeviceBuf<int32_t> dPairs;     // orbx_bow_score_batch_device's pair list [2][n_pairs]
   std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
 };
 
@@ -180,39 +178,16 @@ int parseFile(const char* path, ParsedVoc* v) {
   return ORBX_OK;
 }
 
+// (the buffers are freed on the vocabulary's device: when it cannot be made current, the vocabulary is left as it is)
 void freeVoc(orbx_vocabulary* v) {
-  if (hipSetDevice(v->device) == hipSuccess) {
-    if (v->dNodes) (void)hipFree(v->dNodes);
-    if (v->dDesc) (void)hipFree(v->dDesc);
-    if (v->dScratch) (void)hipFree(v->dScratch);
-    if (v->dIo) (void)hipFree(v->dIo);
-    if (v->dPairs) (void)hipFree(v->dPairs);
-  }
-  delete v;
+  if (hipSetDevice(v->device) == hipSuccess) delete v;
 }
-
-// the scratch of a batch of frames x capacity features
-int ensureScratch(orbx_ctx* ctx, orbx_vocabulary* v, size_t entries) {
-  if (entries <= v->scratchEntries) return ORBX_OK;
-  if (v->dScratch) {
-    BOWCHK(hipStreamSynchronize(ctxStream(ctx)));
-    (void)hipFree(v->dScratch);
-  }
-  v->dScratch = nullptr;
-  v->scratchEntries = 0;
-  BOWCHK(hipMalloc((void**)&v->dScratch, entries * 2 * sizeof(uint32_t)));
-  v->scratchEntries = entries;
-  return ORBX_OK;
-}
-
-size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 int transformIssue(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
                    int levelsup, uint32_t* d_bow_word, double* d_bow_value, int32_t* d_bow_n, uint32_t* d_fv_node,
                    uint32_t* d_fv_feat, int32_t* d_fv_n, uint32_t* d_feat_word) {
   const size_t entries = (size_t)n_frames * capacity;
-  int r = ensureScratch(ctx, v, entries);
-  if (r != ORBX_OK) return r;
+  BOWCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));  // fin, nid
   BowArgs a{};
   a.nodes = v->dNodes;
   a.desc = v->dDesc;
@@ -322,8 +297,8 @@ int orbx_vocabulary_create(orbx_ctx* ctx, int k, int L, int scoring, int weighti
   v->nNodes = n_nodes; v->nWords = nWords; v->nStaged = nStaged;
   auto body = [&]() -> int {
     BOWCHK(hipSetDevice(v->device));
-    BOWCHK(hipMalloc((void**)&v->dNodes, sizeof(BowNode) * N));
-    BOWCHK(hipMalloc((void**)&v->dDesc, (size_t)32 * N));
+    BOWCHK(v->dNodes.grow(sizeof(BowNode) * N));
+    BOWCHK(v->dDesc.grow((size_t)32 * N));
     BOWCHK(hipMemcpy(v->dNodes, nodes.data(), sizeof(BowNode) * N, hipMemcpyHostToDevice));
     BOWCHK(hipMemcpy(v->dDesc, desc.data(), (size_t)32 * N, hipMemcpyHostToDevice));
     return ORBX_OK;
@@ -395,24 +370,23 @@ int orbx_bow_transform(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint8_t*
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
   const int cap = n > 0 ? n : 1;
-  const size_t bD = al256((size_t)cap * 32), bN = al256(16), bW = al256((size_t)cap * 4), bV = al256((size_t)cap * 8);
-  const size_t need = bD + bN + 4 * bW + bV;  // descriptors, counts (n, bow_n, fv_n), bow words, fv nodes, fv features, feat words, values
   hipStream_t st = ctxStream(ctx);
-  if (need > v->ioBytes) {
-    if (v->dIo) (void)hipFree(v->dIo);
-    v->dIo = nullptr;
-    v->ioBytes = 0;
-    BOWCHK(hipMalloc((void**)&v->dIo, need));
-    v->ioBytes = need;
-  }
-  uint8_t* p = v->dIo;
-  uint8_t* dD = p; p += bD;
-  int32_t* dN = (int32_t*)p; p += bN;
-  uint32_t* dW = (uint32_t*)p; p += bW;
-  uint32_t* dFn = (uint32_t*)p; p += bW;
-  uint32_t* dFf = (uint32_t*)p; p += bW;
-  uint32_t* dFw = (uint32_t*)p; p += bW;
-  double* dV = (double*)p;
+  uint8_t* dD;
+  int32_t* dN;
+  uint32_t *dW, *dFn, *dFf, *dFw;
+  double* dV;
+  auto staging = [&](Layout L) {
+    dD = L.take<uint8_t>((size_t)cap * 32);  // descriptors
+    dN = L.take<int32_t>(4);                 // counts: n, bow_n, fv_n
+    dW = L.take<uint32_t>(cap);              // bow words
+    dFn = L.take<uint32_t>(cap);             // fv nodes
+    dFf = L.take<uint32_t>(cap);             // fv features
+    dFw = L.take<uint32_t>(cap);             // feat words
+    dV = L.take<double>(cap);                // bow values
+    return L.size();
+  };
+  BOWCHK(v->dIo.grow(staging(Layout())));
+  staging(Layout(v->dIo));
   if (n) BOWCHK(hipMemcpyAsync(dD, desc32, (size_t)n * 32, hipMemcpyHostToDevice, st));
   BOWCHK(hipMemcpyAsync(dN, &n, 4, hipMemcpyHostToDevice, st));
   r = transformIssue(ctx, v, 1, dD, dN, cap, levelsup, dW, dV, dN + 1, fv ? dFn : nullptr, fv ? dFf : nullptr, fv ? dN + 2 : nullptr,
@@ -460,16 +434,7 @@ int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
   hipStream_t st = ctxStream(ctx);
-  if ((size_t)n_pairs > v->pairsCap) {
-    if (v->dPairs) {
-      BOWCHK(hipStreamSynchronize(st));
-      (void)hipFree(v->dPairs);
-    }
-    v->dPairs = nullptr;
-    v->pairsCap = 0;
-    BOWCHK(hipMalloc((void**)&v->dPairs, (size_t)n_pairs * 8));
-    v->pairsCap = n_pairs;
-  }
+  BOWCHK(v->dPairs.grow((size_t)n_pairs * 8, st));
   v->hPairs.assign(h_first, h_first + n_pairs);
   v->hPairs.insert(v->hPairs.end(), h_second, h_second + n_pairs);
   BOWCHK(hipMemcpyAsync(v->dPairs, v->hPairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
@@ -495,19 +460,19 @@ int orbx_bow_score(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint32_t* w1
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
-  const size_t bW = al256((size_t)2 * cap * 4), bV = al256((size_t)2 * cap * 8), bN = al256(8), bS = al256(8);
   hipStream_t st = ctxStream(ctx);
-  if (bW + bV + bN + bS > v->ioBytes) {
-    if (v->dIo) (void)hipFree(v->dIo);
-    v->dIo = nullptr;
-    v->ioBytes = 0;
-    BOWCHK(hipMalloc((void**)&v->dIo, bW + bV + bN + bS));
-    v->ioBytes = bW + bV + bN + bS;
-  }
-  uint32_t* dW = (uint32_t*)v->dIo;
-  double* dV = (double*)(v->dIo + bW);
-  int32_t* dN = (int32_t*)(v->dIo + bW + bV);
-  double* dS = (double*)(v->dIo + bW + bV + bN);
+  uint32_t* dW;
+  double *dV, *dS;
+  int32_t* dN;
+  auto staging = [&](Layout L) {  // the two frames' words and values, their counts, the score
+    dW = L.take<uint32_t>((size_t)2 * cap);
+    dV = L.take<double>((size_t)2 * cap);
+    dN = L.take<int32_t>(2);
+    dS = L.take<double>(1);
+    return L.size();
+  };
+  BOWCHK(v->dIo.grow(staging(Layout())));
+  staging(Layout(v->dIo));
   const int32_t hn[2] = {n1, n2};
   if (n1) BOWCHK(hipMemcpyAsync(dW, w1, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
   if (n2) BOWCHK(hipMemcpyAsync(dW + cap, w2, (size_t)n2 * 4, hipMemcpyHostToDevice, st));

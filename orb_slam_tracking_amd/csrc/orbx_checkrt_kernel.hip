@@ -86,22 +86,14 @@ __global__ __launch_bounds__(64) void k_check_rt(const CheckRtArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const float* R = a.R21 + 9 * m;
   const float* t = a.t21 + 3 * m;
-  int nInl = a.nInl, n1 = a.n1;
-  const float* ptsIn = a.pts;
-  const int32_t* bookIn = a.book;
-  uint8_t* good = a.good + (long long)m * a.n1;
-  float* p3d = a.p3d + (long long)m * a.n1 * 3;
-  float* cosBuf = a.cosBuf + (long long)m * a.nInl;
-  if (a.pairNInl) {  // batched form (CheckRtArgs)
-    const int p = m / a.perPair;
-    nInl = m % a.perPair < a.pairNSol[p] ? a.pairNInl[p] : 0;
-    n1 = a.stride;
-    ptsIn = a.pts + (long long)p * a.stride * 4;
-    bookIn = a.book + (long long)p * a.stride;
-    good = a.good + (long long)m * a.stride;
-    p3d = a.p3d + (long long)m * a.stride * 3;
-    cosBuf = a.cosBuf + (long long)m * a.stride;
-  }
+  const int p = m / a.perPair;
+  const int nInl = m % a.perPair < a.pairNSol[p] ? a.pairNInl[p] : 0;
+  const int n1 = a.stride;
+  const float* ptsIn = a.pts + (long long)p * a.stride * 4;
+  const int32_t* bookIn = a.book + (long long)p * a.stride;
+  uint8_t* good = a.good + (long long)m * a.stride;
+  float* p3d = a.p3d + (long long)m * a.stride * 3;
+  float* cosBuf = a.cosBuf + (long long)m * a.stride;
   // 1. P1 = [K | 0], P2 = K [R | t] (gemm on CV_32F: double accumulation, one rounding), O2 = -R^T t
   float P2[12], O2[3], Rl[9], tl[3];
 #pragma unroll

@@ -285,6 +285,9 @@ struct PyrYRow {     // one output row: byte offsets of its two source rows (alr
 };
 
 // k_check_model: CheckHomography (kind 0) / CheckFundamental (kind 1) over nModels hypotheses
+// Hypothesis m belongs to pair p = m / perPair, whose N is pairN[p], whose matches are first / second + p * stride, whose
+// keypoints are k1 / k2 + frames[p] * stride / frames[nPairs + p] * stride, and whose inlier flags go to inliers + m * stride
+// (one pair from host arrays: nPairs = 1, frames {0, 0}, stride = N)
 struct ScoreArgs {
   const float* M21;   // [nModels][9] row-major H21 / F21
   const float* M12;   // [nModels][9] H12 (kind 0 only)
@@ -292,35 +295,30 @@ struct ScoreArgs {
   const orbx_keypoint* k2;
   const int32_t* first;   // mvMatches12[i].first / .second
   const int32_t* second;
-  int32_t N, kind;
+  int32_t kind;
   float invSigmaSquare;
   float* scores;      // [nModels]
-  uint8_t* inliers;   // [nModels][N]
-  // batched form (orbx_find_models_batch_device; pairN == nullptr: the single-pair form above): hypothesis m belongs to pair
-  // p = m / perPair, whose N is pairN[p], whose matches are first / second + p * stride, whose keypoints are k1 / k2 +
-  // frames[p] * stride / frames[nPairs + p] * stride, and whose inlier flags go to inliers + m * stride
+  uint8_t* inliers;   // [nModels][stride]
   const int32_t* pairN;
   const int32_t* frames;  // [2][nPairs]
   int32_t perPair, stride, nPairs;
 };
 
-// k_check_rt: CheckRT (Initializer.cpp:569-713) over nModels (R21, t21) hypotheses
+// k_check_rt: CheckRT (Initializer.cpp:569-713) over nModels (R21, t21) hypotheses.  Model m is candidate m % perPair of pair
+// p = m / perPair, with pairNInl[p] points at pts / book + p * stride (none when m % perPair >= pairNSol[p]); good / p3d / cosBuf
+// of model m at m * stride, n1 = stride (one pair from host arrays: perPair = pairNSol[0] = nModels, stride = n1)
 struct CheckRtArgs {
   const float* R21;      // [nModels][9]
   const float* t21;      // [nModels][3]
-  const float* pts;      // [nInl][4] (u1, v1, u2, v2) of the inlier matches, in match order
-  const int32_t* book;   // [nInl] keypoint of frame 1 the i-th triangulated point is booked under (the reference's quirk)
+  const float* pts;      // [nPairs][stride][4] (u1, v1, u2, v2) of the inlier matches, in match order
+  const int32_t* book;   // [nPairs][stride] keypoint of frame 1 the i-th triangulated point is booked under (the reference's quirk)
   float K[9];
   float th2;
-  int32_t nInl, n1;
-  uint8_t* good;         // [nModels][n1]
-  float* p3d;            // [nModels][n1][3]
-  float* cosBuf;         // [nModels][nInl] scratch: cosines of the counted points
+  uint8_t* good;         // [nModels][stride]
+  float* p3d;            // [nModels][stride][3]
+  float* cosBuf;         // [nModels][stride] scratch: cosines of the counted points
   int32_t* nGood;        // [nModels]
   float* parallax;       // [nModels]
-  // batched form (orbx_initialize_batch_device; pairNInl == nullptr: the single-pair form above): model m is candidate m % perPair
-  // of pair p = m / perPair, with pairNInl[p] points at pts / book + p * stride (none when m % perPair >= pairNSol[p]); good /
-  // p3d / cosBuf of model m at m * stride, n1 = stride
   const int32_t* pairNInl;
   const int32_t* pairNSol;
   int32_t perPair, stride;

@@ -2953,19 +2953,13 @@ __global__ __launch_bounds__(256) void k_undistort(const orbx_keypoint* __restri
 __global__ __launch_bounds__(64) void k_check_model(const ScoreArgs a) {
   __shared__ __attribute__((aligned(16))) float add[128];
   const int hyp = blockIdx.x, lane = threadIdx.x;
-  int N = a.N;
-  const orbx_keypoint *k1 = a.k1, *k2 = a.k2;
-  const int32_t *first = a.first, *second = a.second;
-  uint8_t* inliers = a.inliers + (size_t)hyp * a.N;
-  if (a.pairN) {  // batched form (ScoreArgs)
-    const int p = hyp / a.perPair;
-    N = a.pairN[p];
-    k1 += (size_t)a.frames[p] * a.stride;
-    k2 += (size_t)a.frames[a.nPairs + p] * a.stride;
-    first += (size_t)p * a.stride;
-    second += (size_t)p * a.stride;
-    inliers = a.inliers + (size_t)hyp * a.stride;
-  }
+  const int p = hyp / a.perPair;
+  const int N = a.pairN[p];
+  const orbx_keypoint* k1 = a.k1 + (size_t)a.frames[p] * a.stride;
+  const orbx_keypoint* k2 = a.k2 + (size_t)a.frames[a.nPairs + p] * a.stride;
+  const int32_t* first = a.first + (size_t)p * a.stride;
+  const int32_t* second = a.second + (size_t)p * a.stride;
+  uint8_t* inliers = a.inliers + (size_t)hyp * a.stride;
   float m[9], mi[9];
 #pragma unroll
   for (int q = 0; q < 9; q++) {

@@ -53,6 +53,17 @@ def test_library_reads_no_environment_only_named_knobs(orbx):
     assert L.orbx_debug_set(b"no_such_knob", 1) == orbx.E_BADARG and L.orbx_debug_set(None, 1) == orbx.E_BADARG
 
 
+def test_library_allocates_only_through_the_buffer_types():
+    """orbx_api.cpp and orbx_bow.cpp allocate and free device and page-locked memory only through csrc/orbx_buf.h's owning
+    types (DeviceBuf, PinnedBuf): no hand-written hipMalloc / hipFree pairs to keep in step.  (orbx_multi.cpp frees each
+    rank's buffers under that rank's device and is not covered.)"""
+    src = os.path.join(ROOT, "orb_slam_tracking_amd", "csrc")
+    for fn in ("orbx_api.cpp", "orbx_bow.cpp"):
+        calls = re.findall(r"\bhip(?:Host)?(?:Malloc|Free)\b", open(os.path.join(src, fn), errors="replace").read())
+        assert not calls, (fn, calls)
+    assert re.findall(r"\bhipMalloc\b", open(os.path.join(src, "orbx_buf.h")).read())
+
+
 def test_no_cpu_fallback(orbx):
     """Without a usable HIP device the product must refuse to compute (no CPU path exists)."""
     if _has_gpu():
