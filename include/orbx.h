@@ -504,6 +504,58 @@ int orbx_vocabulary_load_text(orbx_ctx* ctx, const char* path, orbx_vocabulary**
 void orbx_vocabulary_destroy(orbx_vocabulary* voc);
 /* info = {k, L, scoring, weighting, nodes (without the root), words} */
 int orbx_vocabulary_info(const orbx_vocabulary* voc, int32_t* info6);
+/* Nodes 1..n of any vocabulary, loaded, created or trained, in file order and in the layout of orbx_vocabulary_parse_text;
+ * is_leaf is the flag as it was given (trained vocabularies: 1 for the nodes without children).  With NULL arrays only the
+ * count is returned; with arrays, capacity < n returns ORBX_E_CAPACITY.  Returns the node count. */
+int orbx_vocabulary_get_nodes(const orbx_vocabulary* voc, int32_t* parent, int32_t* is_leaf, uint8_t* desc32, double* weight,
+                              int32_t capacity);
+/* saveToTextFile (:1626-1645).  exact == 0 writes every weight as an ostream writes a double (6 significant digits), as the
+ * reference does; exact != 0 writes 17 significant digits, so that loading the file returns the same bytes.  ORBX_E_BADARG:
+ * null pointers or a file that cannot be written. */
+int orbx_vocabulary_save_text(const orbx_vocabulary* voc, const char* path, int exact);
+
+/* ---- training: TemplatedVocabulary<FORB>::create (TemplatedVocabulary.h:569-1008, src/FORB.cpp:24-73) ----------------------
+ * Hierarchical k-means over the descriptors of n_docs documents, on the device, one tree level at a time.  It follows the
+ * reference: getFeatures' order (:633-649: documents in order, features in order; every group keeps its features in ascending
+ * original order); HKmeansStep (:654-831: the trivial case n <= k, the rounds until the association repeats, strict < so the
+ * first centre wins a tie, recursion only for level < L and groups of more than one feature); initiateClustersKMpp (:846-925:
+ * min_dist updated only where it is > 0, the exact distance sum, a seeding that stops with fewer than k centres when the sum is
+ * 0, the cut drawn again while it is 0, the first index whose running sum reaches the cut); FORB::meanValue (a copy for one
+ * member, otherwise bit i set iff its count >= n / 2 + n % 2); create's node numbering (a node's children together, then each
+ * child's subtree, depth first); createWords (:930-950: word ids in node-id order over the nodes without children);
+ * setNodeWeights (:955-1008: TF and BINARY weight 1; IDF and TF_IDF log((double)NDocs / (double)Ni), Ni the documents with a
+ * feature whose transform ends in word i, computed with the host's libm from the device's integer counts; 0 where Ni == 0 and
+ * for inner nodes).  Three deviations:
+ *   1. Draws.  The reference consumes rand() depth first, so every node's draws depend on all earlier subtrees.  Here draw j of
+ *      a node is r = mix(mix(seed ^ mix(key)) + j) >> 33 (31 bits, as rand()), mix the splitmix64 step (add 0x9E3779B97F4A7C15;
+ *      z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31); the root's key is 0, child i
+ *      (0-based) of the node with key K has key 21 K + i + 1.  The first centre is feature int((double)r / 2147483648.0 * n),
+ *      a cut is (double)r / 2147483647.0 * dist_sum.
+ *   2. Emptied cluster.  A cluster that loses all its members keeps its centre (the reference releases the cv::Mat and reads
+ *      through its null pointer at the next distance); one that is empty at the end is a node without children, a word with
+ *      Ni = 0.
+ *   3. Round limit.  A k-means run stops after max_rounds assignment rounds (<= 0: 100; a safety limit, the reference loops
+ *      for ever on a cycle) and keeps its last association.
+ * Documents in the layout of orbx_extract_batch_device: document f at d_desc32 + f * capacity * 32, d_n[f] features (clamped to
+ * [0, capacity]); n_docs is not bounded by the context's max_batch, n_docs * capacity by ORBX_VOC_TRAIN_MAX_SLOTS.  *out is an
+ * ordinary vocabulary, ready for transform and score.  stats8 (nullable) = {nodes, words, k-means runs, most rounds of one run,
+ * runs stopped by max_rounds, emptied-cluster events (centre updates that met an empty group), seedings that stopped short,
+ * trivial nodes}.  d_feat_word (nullable, [n_docs][capacity]): the word every training feature descends to.  Synchronous.
+ * ORBX_E_BADARG: k outside [2, 20], L outside [1, 10], a scoring or weighting type out of range, n_docs < 0, capacity < 1, null
+ * pointers; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES or too many slots; ORBX_E_HIP: ctx == NULL with otherwise
+ * well-formed arguments.  Without any feature the vocabulary is empty, as create leaves it. */
+#define ORBX_VOC_TRAIN_MAX_SLOTS (1 << 30)
+int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int weighting, uint64_t seed, int max_rounds, int n_docs,
+                                 const uint8_t* d_desc32, const int32_t* d_n, int capacity, orbx_vocabulary** out, int32_t* stats8,
+                                 uint32_t* d_feat_word);
+/* The same for host memory: the documents' descriptors concatenated in desc32, doc_n[n_docs] of them each (a negative count:
+ * ORBX_E_BADARG; more than ORBX_BOW_MAX_FEATURES in one document: ORBX_E_CAPACITY); feat_word (nullable) concatenated likewise.
+ * Runs through the device path. */
+int orbx_vocabulary_train(orbx_ctx* ctx, int k, int L, int scoring, int weighting, uint64_t seed, int max_rounds, int n_docs,
+                          const uint8_t* desc32, const int32_t* doc_n, orbx_vocabulary** out, int32_t* stats8, uint32_t* feat_word);
+/* Diagnostic: nodes with more than n features are seeded by the grid-wide kernels instead of one workgroup (n < 0: the default,
+ * which is also the largest value taken).  Both forms give the same result; tests drive the grid-wide form on small inputs. */
+int orbx_debug_voc_train_seed_grid_min(long long n);
 
 /* transform(features, BowVector&, FeatureVector&, levelsup) for a batch of frames, device-resident, stream-ordered on the
  * context stream (the call returns once queued; results are valid after a device synchronisation): frame f's descriptors at

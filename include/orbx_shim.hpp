@@ -490,12 +490,14 @@ typedef double WordValue;
 typedef unsigned int NodeId;
 class BowVector : public std::map<WordId, WordValue> {};
 class FeatureVector : public std::map<NodeId, std::vector<unsigned int> > {};
+enum WeightingType { TF_IDF, TF, IDF, BINARY };                                          // BowVector.h:27-34
+enum ScoringType { L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT };  // BowVector.h:37-45
 }  // namespace DBoW2
 
 namespace ORB_SLAM_Tracking {
 
 // Features/ORBVocabulary.hpp: TemplatedVocabulary<FORB> with the members ORB-SLAM calls -- loadFromTextFile, transform (BowVector +
-// FeatureVector), score (L1Scoring) -- on the device of an ORBextractor's context (orbx.h, "bag of words", with its documented
+// FeatureVector), score (L1Scoring) -- and create / saveToTextFile, on the device of an ORBextractor's context (orbx.h, "bag of words", with its documented
 // deviations).  Descriptors are N x 32 contiguous bytes (a Frame's mDescriptors), or a vector of 1 x 32 cv::Mat rows.
 class ORBVocabulary {
  public:
@@ -511,6 +513,38 @@ class ORBVocabulary {
     if (r != ORBX_OK) throw orbx::Error(r, "loadFromTextFile(" + filename + ") failed");
     orbx_vocabulary_destroy(voc_);
     voc_ = v;
+  }
+
+  // TemplatedVocabulary.h:617-628, create(training_features, k, L, weighting, scoring), on the device (orbx.h, "training", with
+  // its three deviations: the draws come from setSeed's seed and the node's path, not from rand()).  The documents'
+  // descriptors concatenated, doc_n[i] of them in document i.
+  void setSeed(uint64_t seed) { seed_ = seed; }
+  void create(const uint8_t* descriptors, const std::vector<int>& doc_n, int k, int L, DBoW2::WeightingType weighting = DBoW2::TF_IDF,
+              DBoW2::ScoringType scoring = DBoW2::L1_NORM) {
+    std::vector<int32_t> n(doc_n.begin(), doc_n.end());
+    orbx_vocabulary* v = nullptr;
+    const int r = orbx_vocabulary_train(e_->context(), k, L, (int)scoring, (int)weighting, seed_, 0, (int)n.size(), descriptors, n.data(),
+                                        &v, nullptr, nullptr);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+    orbx_vocabulary_destroy(voc_);
+    voc_ = v;
+  }
+#ifdef ORBX_WITH_OPENCV
+  void create(const std::vector<std::vector<cv::Mat> >& training_features, int k, int L, DBoW2::WeightingType weighting = DBoW2::TF_IDF,
+              DBoW2::ScoringType scoring = DBoW2::L1_NORM) {
+    std::vector<uint8_t> d;
+    std::vector<int> n;
+    for (const auto& doc : training_features) {
+      n.push_back((int)doc.size());
+      for (const cv::Mat& f : doc) d.insert(d.end(), f.data, f.data + 32);
+    }
+    create(d.data(), n, k, L, weighting, scoring);
+  }
+#endif
+  // TemplatedVocabulary.h:1626-1645 (the weights as the reference's ostream writes them, 6 significant digits)
+  void saveToTextFile(const std::string& filename) const {
+    const int r = orbx_vocabulary_save_text(voc_, filename.c_str(), 0);
+    if (r != ORBX_OK) throw orbx::Error(r, "saveToTextFile(" + filename + ") failed");
   }
 
   void transform(const uint8_t* descriptors, int n, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {
@@ -566,6 +600,7 @@ class ORBVocabulary {
   }
   ORBextractor* e_;
   orbx_vocabulary* voc_ = nullptr;
+  uint64_t seed_ = 0;
 };
 
 }  // namespace ORB_SLAM_Tracking

@@ -222,6 +222,11 @@ def lib() -> ctypes.CDLL:
     L.orbx_vocabulary_destroy.argtypes = [vp]
     L.orbx_vocabulary_destroy.restype = None
     L.orbx_vocabulary_info.argtypes = [vp, vp]
+    L.orbx_vocabulary_get_nodes.argtypes = [vp, vp, vp, vp, vp, i32]
+    L.orbx_vocabulary_save_text.argtypes = [vp, ctypes.c_char_p, i32]
+    L.orbx_vocabulary_train_device.argtypes = [vp, i32, i32, i32, i32, ctypes.c_uint64, i32, i32, vp, vp, i32, ctypes.POINTER(vp), vp, vp]
+    L.orbx_vocabulary_train.argtypes = [vp, i32, i32, i32, i32, ctypes.c_uint64, i32, i32, vp, vp, ctypes.POINTER(vp), vp, vp]
+    L.orbx_debug_voc_train_seed_grid_min.argtypes = [ctypes.c_longlong]
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_bow_transform.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_bow_score_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
@@ -967,6 +972,70 @@ class Vocabulary:
                                                              _ptr(is_leaf), _ptr(desc), _ptr(weight), ctypes.byref(h)),
                          "orbx_vocabulary_create")
         return cls(extractor, h)
+
+    TRAIN_STATS = ("nodes", "words", "kmeans_runs", "max_rounds_seen", "capped_runs", "emptied_clusters", "short_seedings",
+                   "trivial_nodes")
+
+    @classmethod
+    def train(cls, extractor: ORBextractor, docs=None, k: int = 10, L: int = 6, weighting: int = 0, scoring: int = 0, seed: int = 0,
+              max_rounds: int = 100, feat_word: bool = False, d_desc=None, d_n=None, n_docs: Optional[int] = None,
+              capacity: Optional[int] = None, d_feat_word=None) -> "Vocabulary":
+        """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the device (orbx_vocabulary_train, with the
+        deviations include/orbx.h lists: the draws are a function of `seed` and the node's path, an emptied cluster keeps its
+        centre, a run stops after `max_rounds` rounds).  Either `docs`, a sequence of descriptor arrays [n_i, 32] in host memory
+        (feat_word=True keeps each training feature's word in .train_feat_word, concatenated), or the device-resident layout of
+        extract_batch_device: d_desc uint8 [n_docs, capacity, 32] and d_n int32 [n_docs] (device pointers or torch tensors), with
+        d_feat_word uint32 [n_docs, capacity] optional.  The statistics are kept in .train_stats (a dict, TRAIN_STATS).
+        Synchronous."""
+        h, stats = ctypes.c_void_p(0), np.zeros(8, np.int32)
+        fw = None
+        if docs is not None:
+            if d_desc is not None or d_n is not None:
+                raise OrbxError(E_BADARG, "either docs or d_desc / d_n")
+            arrs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
+            doc_n = np.array([len(a) for a in arrs], np.int32)
+            cat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 32), np.uint8))
+            fw = np.zeros(max(len(cat), 1), np.uint32) if feat_word else None
+            extractor._check(extractor._L.orbx_vocabulary_train(extractor._h, int(k), int(L), int(scoring), int(weighting), int(seed),
+                                                                int(max_rounds), len(arrs), _ptr(cat) if len(cat) else None,
+                                                                _ptr(doc_n) if len(arrs) else None, ctypes.byref(h), _ptr(stats),
+                                                                _ptr(fw)), "orbx_vocabulary_train")
+            fw = fw[:len(cat)] if feat_word else None
+        else:
+            if d_desc is None or d_n is None or n_docs is None:
+                raise OrbxError(E_BADARG, "the device form needs d_desc, d_n and n_docs")
+            cap, nd = int(capacity or extractor.capacity), int(n_docs)
+            _need("the descriptor array", d_desc, nd * cap * 32)
+            _need("the count array", d_n, nd * 4)
+            if d_feat_word is not None:
+                _need("the feature word array", d_feat_word, nd * cap * 4)
+            extractor._order_torch(d_desc, d_n, d_feat_word)
+            extractor._check(extractor._L.orbx_vocabulary_train_device(extractor._h, int(k), int(L), int(scoring), int(weighting), int(seed),
+                                                                       int(max_rounds), nd, _ptr(d_desc), _ptr(d_n), cap, ctypes.byref(h),
+                                                                       _ptr(stats), _ptr(d_feat_word)), "orbx_vocabulary_train_device")
+        v = cls(extractor, h)
+        v.train_stats = dict(zip(cls.TRAIN_STATS, (int(x) for x in stats)))
+        v.train_feat_word = fw
+        return v
+
+    def nodes(self):
+        """(parent, is_leaf, desc [n, 32], weight) of nodes 1..n in file order (orbx_vocabulary_get_nodes), the layout from_arrays
+        takes, for any vocabulary however it was made."""
+        n = self.n_nodes
+        m = max(n, 1)
+        parent, leaf = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        desc, weight = np.zeros((m, 32), np.uint8), np.zeros(m, np.float64)
+        r = self._L.orbx_vocabulary_get_nodes(self._h, _ptr(parent), _ptr(leaf), _ptr(desc), _ptr(weight), m)
+        if r < 0:
+            raise OrbxError(r, "orbx_vocabulary_get_nodes")
+        return parent[:n], leaf[:n], desc[:n], weight[:n]
+
+    def save_text(self, path: str, exact: bool = True) -> None:
+        """saveToTextFile; exact=True writes the weights with 17 significant digits (a load returns the same bytes), exact=False
+        as the reference's ostream does (6 significant digits)."""
+        r = self._L.orbx_vocabulary_save_text(self._h, os.fsencode(path), 1 if exact else 0)
+        if r < 0:
+            raise OrbxError(r, "orbx_vocabulary_save_text(%s)" % path)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

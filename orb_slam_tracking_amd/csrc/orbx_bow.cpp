@@ -19,6 +19,7 @@
 namespace orbx {
 hipError_t launch_bow_transform(hipStream_t st, const BowArgs& a);
 hipError_t launch_bow_score_l1(hipStream_t st, const BowScoreArgs& s);
+hipError_t launch_bow_descend(hipStream_t st, const BowArgs& a);
 // orbx_api.cpp
 int ctxDevice(const orbx_ctx* c);
 hipStream_t ctxStream(const orbx_ctx* c);
@@ -40,6 +41,10 @@ struct orbx_vocabulary {
   DeviceBuf<uint8_t> dIo;        // staging of orbx_bow_transform / orbx_bow_score
   DeviceBuf<int32_t> dPairs;     // orbx_bow_score_batch_device's pair list [2][n_pairs]
   std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
+  // nodes 1..nNodes in file order as they were given (orbx_vocabulary_get_nodes, orbx_vocabulary_save_text)
+  std::vector<int32_t> hParent, hLeaf;
+  std::vector<uint8_t> hDesc;
+  std::vector<double> hWeight;
 };
 
 namespace {
@@ -224,6 +229,31 @@ int checkVoc(orbx_ctx* ctx, const orbx_vocabulary* voc) {
 
 }  // namespace
 
+namespace orbx {
+// orbx_voc_train.cpp: the descent alone over a batch; *nodes the vocabulary's breadth-first nodes, *fin [n_frames][capacity] the
+// breadth-first index each feature ends at (the vocabulary's scratch: valid until its next call)
+int vocDescend(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+               const BowNode** nodes, const uint32_t** fin) {
+  const size_t entries = (size_t)n_frames * capacity;
+  BOWCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));
+  BowArgs a{};
+  a.nodes = v->dNodes;
+  a.desc = v->dDesc;
+  a.nStaged = v->nStaged;
+  a.nidLevel = v->L;
+  a.fdesc = d_desc32;
+  a.n = d_n;
+  a.cap = capacity;
+  a.nFrames = n_frames;
+  a.fin = v->dScratch;
+  a.nid = v->dScratch + entries;
+  BOWCHK(launch_bow_descend(ctxStream(ctx), a));
+  *nodes = v->dNodes;
+  *fin = v->dScratch;
+  return ORBX_OK;
+}
+}  // namespace orbx
+
 extern "C" {
 
 int orbx_vocabulary_parse_text(const char* path, int32_t* header, int32_t* n_nodes, int32_t* parent, int32_t* is_leaf,
@@ -295,6 +325,12 @@ int orbx_vocabulary_create(orbx_ctx* ctx, int k, int L, int scoring, int weighti
   v->device = ctxDevice(ctx);
   v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting;
   v->nNodes = n_nodes; v->nWords = nWords; v->nStaged = nStaged;
+  if (n_nodes > 0) {
+    v->hParent.assign(parent, parent + n_nodes);
+    v->hLeaf.assign(is_leaf, is_leaf + n_nodes);
+    v->hDesc.assign(desc32, desc32 + (size_t)n_nodes * 32);
+    v->hWeight.assign(weight, weight + n_nodes);
+  }
   auto body = [&]() -> int {
     BOWCHK(hipSetDevice(v->device));
     BOWCHK(v->dNodes.grow(sizeof(BowNode) * N));
@@ -334,6 +370,35 @@ int orbx_vocabulary_info(const orbx_vocabulary* voc, int32_t* info6) {
   const int32_t v[6] = {voc->k, voc->L, voc->scoring, voc->weighting, voc->nNodes, voc->nWords};
   memcpy(info6, v, sizeof v);
   return ORBX_OK;
+}
+
+int orbx_vocabulary_get_nodes(const orbx_vocabulary* voc, int32_t* parent, int32_t* is_leaf, uint8_t* desc32, double* weight,
+                              int32_t capacity) {
+  if (!voc) return ORBX_E_BADARG;
+  const int n = voc->nNodes;
+  if (parent || is_leaf || desc32 || weight) {
+    if (capacity < n) return ORBX_E_CAPACITY;
+    if (parent && n) memcpy(parent, voc->hParent.data(), (size_t)n * 4);
+    if (is_leaf && n) memcpy(is_leaf, voc->hLeaf.data(), (size_t)n * 4);
+    if (desc32 && n) memcpy(desc32, voc->hDesc.data(), (size_t)n * 32);
+    if (weight && n) memcpy(weight, voc->hWeight.data(), (size_t)n * 8);
+  }
+  return n;
+}
+
+int orbx_vocabulary_save_text(const orbx_vocabulary* voc, const char* path, int exact) {
+  if (!voc || !path) return ORBX_E_BADARG;
+  FILE* fp = fopen(path, "wb");
+  if (!fp) return ORBX_E_BADARG;
+  // saveToTextFile (:1626-1645): "k L  scoring weighting", then per node "parent flag d0 .. d31 weight"
+  fprintf(fp, "%d %d  %d %d\n", voc->k, voc->L, voc->scoring, voc->weighting);
+  for (int i = 0; i < voc->nNodes; i++) {
+    fprintf(fp, "%d %d ", voc->hParent[i], voc->hLeaf[i]);
+    for (int j = 0; j < 32; j++) fprintf(fp, "%d ", (int)voc->hDesc[(size_t)i * 32 + j]);  // FORB::toString
+    fprintf(fp, exact ? "%.17g\n" : "%g\n", voc->hWeight[i]);  // (%g: an ostream's default, 6 significant digits)
+  }
+  const bool bad = ferror(fp) != 0;
+  return (fclose(fp) != 0 || bad) ? ORBX_E_BADARG : ORBX_OK;
 }
 
 int orbx_bow_transform_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n_frames, const uint8_t* d_desc32,

@@ -268,6 +268,14 @@ __global__ __launch_bounds__(64 * BOW_SCORE_WAVES) void k_bow_score_l1(BowScoreA
   if (lane == 0) s.score[p] = -acc / 2.0;
 }
 
+// the descent alone (vocabulary training: the word of every training feature)
+hipError_t launch_bow_descend(hipStream_t st, const BowArgs& a) {
+  const long long lanes = (long long)a.nFrames * a.cap;
+  hipLaunchKernelGGL(k_bow_descend, dim3((unsigned)((lanes + BOW_DESCEND_THREADS - 1) / BOW_DESCEND_THREADS)),
+                     dim3(BOW_DESCEND_THREADS), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_bow_transform(hipStream_t st, const BowArgs& a) {
   const long long lanes = (long long)a.nFrames * a.cap;
   hipLaunchKernelGGL(k_bow_descend, dim3((unsigned)((lanes + BOW_DESCEND_THREADS - 1) / BOW_DESCEND_THREADS)),

@@ -438,4 +438,46 @@ struct BowScoreArgs {
   double* score;          // [nPairs]
 };
 
+// ---- DBoW2 TemplatedVocabulary::create (orbx_voc_train_kernel.hip): one tree level at a time ----
+constexpr int VT_THREADS = 256;   // threads of the training kernels, and the features of one block of the level's block table
+constexpr int VT_CHUNK = 4096;    // features one workgroup of k_vt_count counts (a node with more has global counters)
+constexpr int VT_SEED_LDS = 4096; // the largest node the one-workgroup seeding takes (its distances live in LDS)
+constexpr int VT_KMAX = 20;
+constexpr int VT_DF_THREADS = 1024;
+enum { VT_RUNNING = 0, VT_CONVERGED = 1, VT_CAPPED = 2, VT_TRIVIAL = 3 };
+struct VtNode {      // a node being split at this level
+  uint64_t key;      // of the node's draws (root 0, child i of K: 21 K + i + 1)
+  int32_t start, n;  // its features: perm[start, start + n), ascending original order
+  int32_t nC;        // centres
+  int32_t state, rounds, changed;
+  int32_t form;      // 0: seeded by one workgroup (and the trivial case n <= k), 1: grid-wide seeding
+  int32_t blk0;      // the node's first block in the block table
+  int32_t multi;     // index of its global bit counters (more than one chunk of k_vt_count), -1: none
+  int32_t seedDone, draws, pad;
+};
+static_assert(sizeof(VtNode) == 56, "VtNode layout");
+struct VtArgs {
+  const uint32_t* feat;   // descriptors [slots][8]; a feature is named by its slot (document * capacity + index)
+  uint32_t* perm;         // [N] slots, every node's features contiguous
+  uint32_t* permOut;      // [N] the regrouped order
+  uint8_t* assoc;         // [N] cluster of the feature at a position
+  int32_t* minDist;       // [N] grid-wide seeding: distance to the nearest centre, by position
+  VtNode* nodes;          // [nNodes]
+  uint32_t* centres;      // [nNodes][k][8]
+  int32_t nNodes, k, maxRounds, nBlk;
+  uint64_t seed;
+  const int32_t* blkNode;   // [nBlk] block table: node and first position of blocks of VT_THREADS positions
+  const int32_t* blkStart;  // [nBlk]
+  uint32_t* blkSum;         // [nBlk] seeding: the block's distance sum
+  int32_t* blkHist;         // [nBlk][k] regrouping: members per cluster, then their exclusive prefix within the node
+  int32_t* nodeHist;        // [nNodes][k] members per cluster
+  int32_t* childBase;       // [nNodes][k] first position of each cluster's group
+  const int32_t* list;      // node indices a launch runs over (small nodes, large nodes, multi-chunk nodes)
+  int32_t nList, nChunk;
+  const int32_t* chNode;    // [nChunk] chunk table of k_vt_count: node, first position
+  const int32_t* chStart;
+  uint32_t* gCnt;           // [multi][k][256 + 1] global bit counters and the group size (zero between rounds)
+  int32_t* stats;           // [8] orbx_vocabulary_train's statistics; [8] nodes still running after this round
+};
+
 }  // namespace orbx
