@@ -584,6 +584,74 @@ int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n
 int orbx_bow_score(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint32_t* w1, const double* v1, int n1, const uint32_t* w2,
                    const double* v2, int n2, double* score);
 
+/* ---- database: DBoW2 TemplatedDatabase::add and query ------------------------------------------------------------------------
+ * (Thirdparty/DBoW2/include/DBoW2/TemplatedDatabase.h:433-464 add, :566-1113 query and the five query* it dispatches to.)
+ * The BowVectors of past frames in an inverted file on the device -- row_start [words + 1], and per posting an entry id (uint32)
+ * and a value (f64), every row in ascending entry id -- and, for a new BowVector, the best-scoring entries.  A database belongs
+ * to one context and takes its scoring and weighting types from the vocabulary it is created with (the vocabulary itself is
+ * not kept).  Bit-identical to a CPU restatement of those lines (tests/cpp/db_ref.cpp), which is itself compared with the
+ * reference's compiled scoring objects: every score a query returns equals ScoringObject::score(query, entry) byte for byte.
+ *   add     every vector gets the next entry id (m_nentries++), an empty one too; each (word, value) is appended to its word's row
+ *   query   entry e's sum is built from the words it shares with the query in ascending word id, one sequential f64 chain
+ *           that starts from the first term; entries with id < max_id take part (max_id == -1: all); the list is ordered,
+ *           cut to max_results, and the final score computed after the cut:
+ *             L1_NORM        term fabs(q - d) - fabs(q) - fabs(d)          listed with >= 1 common word   smallest sum first
+ *                            score -sum / 2.0
+ *             L2_NORM        term -q * d                                   >= 1                           smallest sum first
+ *                            score sum <= -1.0 ? 1.0 : 1.0 - sqrt(1.0 + sum)
+ *             CHI_SQUARE     term q + d != 0.0 ? -q * d / (q + d) : 0      >= 5 (MIN_COMMON_WORDS)        smallest sum first
+ *                            (the word counts either way); score -2. * sum
+ *             BHATTACHARYYA  term sqrt(q * d)                              >= 5                           largest sum first
+ *             DOT_PRODUCT    term q * d, or 1 under BINARY weighting       >= 1                           largest sum first
+ *           f64 divide and sqrt correctly rounded, nothing contracted.
+ * Documented deviations from the reference:
+ *   1. Equal sums are ordered by ascending entry id (the reference's std::sort leaves their order unspecified).
+ *   2. KL is not offered: orbx_database_create returns ORBX_E_BADARG for a KL vocabulary.
+ *   3. max_results must lie in [1, ORBX_DB_MAX_RESULTS]: the reference's "<= 0 means all", and a larger value, return
+ *      ORBX_E_CAPACITY.
+ *   4. The debug fields of Result (nWords, bhatScore, chiScore, sumCommonVi, sumCommonWi, expectedChiScore) are not produced.
+ *   5. Word ids: the host forms refuse (ORBX_E_BADARG) a word id >= the vocabulary's word count and words that are not strictly
+ *      ascending, where the reference indexes out of range; the device forms skip a posting whose word id is no word.
+ * Not offered: the direct index (m_dfile, retrieveFeatures), save / load, allocate.
+ * The batch forms read BowVectors in the layout orbx_bow_transform_batch_device writes ([n][capacity], d_bow_n clamped to
+ * [0, capacity]) and are stream-ordered on the context stream: adds and queries issued in order see each other in order.  An
+ * add rewrites the whole file (one pass over every posting) and reads the file's new length back once, so it returns with the
+ * stream idle up to its last three kernels; a query returns once queued.
+ * Common refusals: ORBX_E_BADARG for a vocabulary or database of another context, null pointers, negative counts, capacity < 1;
+ * ORBX_E_CAPACITY for capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP for ctx == NULL with otherwise well-formed arguments. */
+#define ORBX_DB_MAX_RESULTS 256
+typedef struct orbx_database orbx_database;
+int orbx_database_create(orbx_ctx* ctx, const orbx_vocabulary* voc, orbx_database** out);
+/* Destroy databases before their context. */
+void orbx_database_destroy(orbx_database* db);
+/* clear(): no entries; the next id is 0 again. */
+int orbx_database_clear(orbx_database* db);
+/* size(): the number of entries (ORBX_E_BADARG for NULL). */
+int orbx_database_size(const orbx_database* db);
+/* add(v) for a batch: frame f becomes entry *first_entry_id + f. */
+int orbx_database_add_batch_device(orbx_ctx* ctx, orbx_database* db, int n_frames, const uint32_t* d_bow_word,
+                                   const double* d_bow_value, const int32_t* d_bow_n, int capacity, int32_t* first_entry_id);
+/* query(vec, ret, max_results, max_id) for a batch: d_res_entry int32 / d_res_score f64, both [n_queries][max_results], best
+ * first; d_res_n[q] entries are written for query q and nothing beyond them. */
+int orbx_database_query_batch_device(orbx_ctx* ctx, orbx_database* db, int n_queries, const uint32_t* d_bow_word,
+                                     const double* d_bow_value, const int32_t* d_bow_n, int capacity, int max_results, int max_id,
+                                     int32_t* d_res_entry, double* d_res_score, int32_t* d_res_n);
+/* The same for one BowVector in host memory (ascending words word [n] with their values), through the batched path as a batch
+ * of one.  res_entry / res_score hold max_results entries.  More than ORBX_BOW_MAX_FEATURES words: ORBX_E_CAPACITY.
+ * Synchronous. */
+int orbx_database_add(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, const double* value, int n, int32_t* entry_id);
+int orbx_database_query(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, const double* value, int n, int max_results,
+                        int max_id, int32_t* res_entry, double* res_score, int32_t* res_n);
+/* Diagnostic readback, synchronous: row_start [words + 1], then the postings word by word (post_entry / post_value, capacity
+ * entries each; fewer than the file holds: ORBX_E_CAPACITY).  With NULL arrays only the posting count is returned.  Returns the
+ * posting count. */
+int64_t orbx_database_get_inverted_file(orbx_database* db, uint32_t* row_start, uint32_t* post_entry, double* post_value,
+                                        int64_t capacity);
+/* Diagnostic: the entries one accumulate workgroup takes (1 .. 2048) and the lists one merge workgroup takes (2 .. 8); negative
+ * arguments restore the defaults, which are also the largest values (other values: ORBX_E_BADARG).  Every shape gives the same
+ * result; tests drive several slices and merge rounds on small databases. */
+int orbx_debug_database_shape(int entries_per_slice, int lists_per_merge);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

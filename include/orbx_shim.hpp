@@ -492,6 +492,21 @@ class BowVector : public std::map<WordId, WordValue> {};
 class FeatureVector : public std::map<NodeId, std::vector<unsigned int> > {};
 enum WeightingType { TF_IDF, TF, IDF, BINARY };                                          // BowVector.h:27-34
 enum ScoringType { L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT };  // BowVector.h:37-45
+// QueryResults.h: a database query's answer, best first.  The debug fields of Result are not produced (orbx.h, "database",
+// deviation 4).
+typedef unsigned int EntryId;
+class Result {
+ public:
+  EntryId Id;
+  double Score;
+  Result() : Id(0), Score(0) {}
+  Result(EntryId _id, double _score) : Id(_id), Score(_score) {}
+  bool operator<(const Result& r) const { return Score < r.Score; }
+  bool operator>(const Result& r) const { return Score > r.Score; }
+  bool operator==(EntryId id) const { return Id == id; }
+  static bool gt(const Result& a, const Result& b) { return a.Score > b.Score; }
+};
+class QueryResults : public std::vector<Result> {};
 }  // namespace DBoW2
 
 namespace ORB_SLAM_Tracking {
@@ -577,6 +592,9 @@ class ORBVocabulary {
 
   bool empty() const { return words() == 0; }
   unsigned int size() const { return (unsigned int)words(); }
+  // what ORBDatabase is built from
+  orbx_vocabulary* handle() const { return voc_; }
+  ORBextractor* extractor() const { return e_; }
 
  private:
   int words() const {
@@ -601,6 +619,94 @@ class ORBVocabulary {
   ORBextractor* e_;
   orbx_vocabulary* voc_ = nullptr;
   uint64_t seed_ = 0;
+};
+
+// DBoW2's TemplatedDatabase<FORB::TDescriptor, FORB> (Thirdparty/DBoW2/include/DBoW2/TemplatedDatabase.h) with the members a SLAM
+// system calls -- add, query, size, clear -- over an inverted file on the device (orbx.h, "database", with its documented
+// deviations: max_results in [1, ORBX_DB_MAX_RESULTS], no KL, no direct index).  Built from a loaded or trained ORBVocabulary,
+// whose scoring and weighting types it takes; the vocabulary must outlive it for the members that take features.
+class ORBDatabase {
+ public:
+  explicit ORBDatabase(const ORBVocabulary& voc) : voc_(&voc), e_(voc.extractor()) {
+    const int r = orbx_database_create(e_->context(), voc.handle(), &db_);
+    if (r != ORBX_OK) throw orbx::Error(r, "ORBDatabase: the vocabulary is not loaded, or its scoring type is KL");
+  }
+  ~ORBDatabase() { orbx_database_destroy(db_); }
+  ORBDatabase(const ORBDatabase&) = delete;
+  ORBDatabase& operator=(const ORBDatabase&) = delete;
+
+  // TemplatedDatabase.h:433-464 (without the direct index)
+  DBoW2::EntryId add(const DBoW2::BowVector& vec) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    flatten(vec, w, v);
+    int32_t id = 0;
+    const int r = orbx_database_add(e_->context(), db_, w.data(), v.data(), (int)w.size(), &id);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+    return (DBoW2::EntryId)id;
+  }
+  // :403-428: transform, then add; *bowvec (nullable) receives the vector
+  DBoW2::EntryId add(const uint8_t* descriptors, int n, DBoW2::BowVector* bowvec = nullptr) {
+    DBoW2::BowVector v;
+    voc_->transform(descriptors, n, v);
+    if (bowvec) *bowvec = v;
+    return add(v);
+  }
+  DBoW2::EntryId add(const std::vector<uint8_t>& descriptors, DBoW2::BowVector* bowvec = nullptr) {
+    return add(descriptors.data(), (int)(descriptors.size() / 32), bowvec);
+  }
+
+  // :578-610
+  void query(const DBoW2::BowVector& vec, DBoW2::QueryResults& ret, int max_results = 1, int max_id = -1) const {
+    ret.resize(0);
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    flatten(vec, w, v);
+    const size_t m = (size_t)std::max(max_results, 1);
+    std::vector<int32_t> id(m);
+    std::vector<double> score(m);
+    int32_t got = 0;
+    const int r = orbx_database_query(e_->context(), db_, w.data(), v.data(), (int)w.size(), max_results, max_id, id.data(),
+                                      score.data(), &got);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+    for (int i = 0; i < got; i++) ret.push_back(DBoW2::Result((DBoW2::EntryId)id[i], score[i]));
+  }
+  // :566-573
+  void query(const uint8_t* descriptors, int n, DBoW2::QueryResults& ret, int max_results = 1, int max_id = -1) const {
+    DBoW2::BowVector v;
+    voc_->transform(descriptors, n, v);
+    query(v, ret, max_results, max_id);
+  }
+  void query(const std::vector<uint8_t>& descriptors, DBoW2::QueryResults& ret, int max_results = 1, int max_id = -1) const {
+    query(descriptors.data(), (int)(descriptors.size() / 32), ret, max_results, max_id);
+  }
+#ifdef ORBX_WITH_OPENCV
+  DBoW2::EntryId add(const std::vector<cv::Mat>& features, DBoW2::BowVector* bowvec = nullptr) { return add(rows(features), bowvec); }
+  void query(const std::vector<cv::Mat>& features, DBoW2::QueryResults& ret, int max_results = 1, int max_id = -1) const {
+    query(rows(features), ret, max_results, max_id);
+  }
+#endif
+
+  unsigned int size() const { return (unsigned int)std::max(orbx_database_size(db_), 0); }
+  void clear() {
+    const int r = orbx_database_clear(db_);
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e_->context()));
+  }
+
+ private:
+  static void flatten(const DBoW2::BowVector& vec, std::vector<uint32_t>& w, std::vector<double>& v) {
+    for (const auto& e : vec) { w.push_back(e.first); v.push_back(e.second); }
+  }
+#ifdef ORBX_WITH_OPENCV
+  static std::vector<uint8_t> rows(const std::vector<cv::Mat>& features) {
+    std::vector<uint8_t> d(features.size() * 32);
+    for (size_t i = 0; i < features.size(); i++) std::memcpy(d.data() + 32 * i, features[i].data, 32);
+    return d;
+  }
+#endif
+  const ORBVocabulary* voc_;
+  ORBextractor* e_;
+  orbx_database* db_ = nullptr;
 };
 
 }  // namespace ORB_SLAM_Tracking

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -231,6 +231,18 @@ def lib() -> ctypes.CDLL:
     L.orbx_bow_transform.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_bow_score_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.orbx_bow_score.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
+    L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    L.orbx_database_destroy.argtypes = [vp]
+    L.orbx_database_destroy.restype = None
+    L.orbx_database_clear.argtypes = [vp]
+    L.orbx_database_size.argtypes = [vp]
+    L.orbx_database_add_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp]
+    L.orbx_database_query_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.orbx_database_add.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.orbx_database_query.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.orbx_database_get_inverted_file.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
+    L.orbx_database_get_inverted_file.restype = ctypes.c_int64
+    L.orbx_debug_database_shape.argtypes = [i32, i32]
     L.orbx_multi_create.argtypes = [ctypes.POINTER(_Params), i32, vp, i32, i32, i32, ctypes.POINTER(vp)]
     L.orbx_multi_destroy.argtypes = [vp]
     L.orbx_multi_destroy.restype = None
@@ -1117,6 +1129,119 @@ class Vocabulary:
         self._ext._check(self._L.orbx_bow_score_batch_device(self._ext._h, self._h, nf, P, _ptr(first), _ptr(second), _ptr(d_bow_word),
                                                              _ptr(d_bow_value), _ptr(d_bow_n), cap, _ptr(d_score)),
                          "orbx_bow_score_batch_device")
+
+
+DB_MAX_RESULTS = 256  # ORBX_DB_MAX_RESULTS: the longest result list of a database query
+DB_ENTRIES_PER_SLICE, DB_LISTS_PER_MERGE = 2048, 8  # the defaults of orbx_debug_database_shape
+
+
+def debug_database_shape(entries_per_slice: int = -1, lists_per_merge: int = -1) -> None:
+    """Diagnostic (orbx_debug_database_shape): the entries one accumulate workgroup and the lists one merge workgroup of a
+    database query take; negative values restore the defaults.  Every shape gives the same result."""
+    r = lib().orbx_debug_database_shape(int(entries_per_slice), int(lists_per_merge))
+    if r != 0:
+        raise OrbxError(r, "orbx_debug_database_shape(%d, %d)" % (entries_per_slice, lists_per_merge))
+
+
+class Database:
+    """DBoW2's TemplatedDatabase on the device of a Vocabulary's context: the BowVectors of past frames in an inverted file, and
+    the best-scoring entries for a new one (include/orbx.h, "database", with its documented deviations).  The scoring and
+    weighting types are the vocabulary's; KL is not offered.  The database keeps its extractor alive; close() it (or drop it)
+    before the extractor."""
+
+    def __init__(self, vocabulary: Vocabulary):
+        self._ext, self._L = vocabulary._ext, vocabulary._L
+        self.n_words, self.scoring, self.weighting = vocabulary.n_words, vocabulary.scoring, vocabulary.weighting
+        self._h = ctypes.c_void_p(0)
+        self._ext._check(self._L.orbx_database_create(self._ext._h, vocabulary._h, ctypes.byref(self._h)), "orbx_database_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbx_database_destroy(self._h)
+            self._h = ctypes.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self) -> int:
+        """size(): the number of entries."""
+        return self._ext._check(self._L.orbx_database_size(self._h), "orbx_database_size")
+
+    def clear(self) -> None:
+        """clear(): no entries; the next entry id is 0 again."""
+        self._ext._check(self._L.orbx_database_clear(self._h), "orbx_database_clear")
+
+    @staticmethod
+    def _vector(word, value):
+        w, v = np.ascontiguousarray(word, np.uint32).reshape(-1), np.ascontiguousarray(value, np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise OrbxError(E_BADARG, "a BowVector's words and values differ in length")
+        return w, v
+
+    def add(self, word, value) -> int:
+        """add(v) of one BowVector in host memory (ascending word ids and their values) -> its entry id.  Synchronous."""
+        w, v = self._vector(word, value)
+        eid = ctypes.c_int32(0)
+        self._ext._check(self._L.orbx_database_add(self._ext._h, self._h, _ptr(w), _ptr(v), len(w), ctypes.byref(eid)),
+                         "orbx_database_add")
+        return eid.value
+
+    def query(self, word, value, max_results: int = 1, max_id: int = -1):
+        """query(vec, ret, max_results, max_id) of one BowVector in host memory -> (entry ids int32, scores float64), best first.
+        max_results in [1, DB_MAX_RESULTS].  Synchronous."""
+        w, v = self._vector(word, value)
+        m = max(int(max_results), 1)
+        e, s, n = np.zeros(m, np.int32), np.zeros(m, np.float64), ctypes.c_int32(0)
+        self._ext._check(self._L.orbx_database_query(self._ext._h, self._h, _ptr(w), _ptr(v), len(w), int(max_results), int(max_id),
+                                                     _ptr(e), _ptr(s), ctypes.byref(n)), "orbx_database_query")
+        return e[:n.value], s[:n.value]
+
+    def add_batch_device(self, n_frames: int, d_bow_word, d_bow_value, d_bow_n, capacity: Optional[int] = None) -> int:
+        """add for a batch of BowVectors in the layout transform_batch_device writes (device pointers or torch tensors): d_bow_word
+        uint32 / d_bow_value float64 [n_frames, capacity], d_bow_n int32 [n_frames] -> the first frame's entry id (frame f is
+        entry first + f).  Stream-ordered on the context's stream."""
+        cap, nf = int(capacity or self._ext.capacity), int(n_frames)
+        _need("the word array", d_bow_word, nf * cap * 4)
+        _need("the value array", d_bow_value, nf * cap * 8)
+        _need("the BowVector count array", d_bow_n, nf * 4)
+        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n)
+        first = ctypes.c_int32(0)
+        self._ext._check(self._L.orbx_database_add_batch_device(self._ext._h, self._h, nf, _ptr(d_bow_word), _ptr(d_bow_value),
+                                                                _ptr(d_bow_n), cap, ctypes.byref(first)),
+                         "orbx_database_add_batch_device")
+        return first.value
+
+    def query_batch_device(self, n_queries: int, d_bow_word, d_bow_value, d_bow_n, d_res_entry, d_res_score, d_res_n,
+                           max_results: int = 1, max_id: int = -1, capacity: Optional[int] = None) -> None:
+        """query for a batch of BowVectors (the layout of add_batch_device): d_res_entry int32 / d_res_score float64
+        [n_queries, max_results] best first, d_res_n int32 [n_queries] the entries written for each query; nothing beyond them is
+        written.  Stream-ordered on the context's stream: the results are valid after a device synchronisation."""
+        cap, nq, m = int(capacity or self._ext.capacity), int(n_queries), max(int(max_results), 0)
+        _need("the word array", d_bow_word, nq * cap * 4)
+        _need("the value array", d_bow_value, nq * cap * 8)
+        _need("the BowVector count array", d_bow_n, nq * 4)
+        _need("the result entry array", d_res_entry, nq * m * 4)
+        _need("the result score array", d_res_score, nq * m * 8)
+        _need("the result count array", d_res_n, nq * 4)
+        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n, d_res_entry, d_res_score, d_res_n)
+        self._ext._check(self._L.orbx_database_query_batch_device(self._ext._h, self._h, nq, _ptr(d_bow_word), _ptr(d_bow_value),
+                                                                  _ptr(d_bow_n), cap, int(max_results), int(max_id), _ptr(d_res_entry),
+                                                                  _ptr(d_res_score), _ptr(d_res_n)),
+                         "orbx_database_query_batch_device")
+
+    def inverted_file(self):
+        """Diagnostic readback (orbx_database_get_inverted_file): (row_start uint32 [words + 1], post_entry uint32, post_value
+        float64), the postings word by word, each row in ascending entry id.  Synchronous."""
+        n = self._ext._check(self._L.orbx_database_get_inverted_file(self._h, None, None, None, 0), "orbx_database_get_inverted_file")
+        rs = np.zeros(self.n_words + 1, np.uint32)
+        pe, pv = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float64)
+        self._ext._check(self._L.orbx_database_get_inverted_file(self._h, _ptr(rs), _ptr(pe), _ptr(pv), len(pe)),
+                         "orbx_database_get_inverted_file")
+        return rs, pe[:n], pv[:n]
 
 
 class Frame:

@@ -230,6 +230,9 @@ int checkVoc(orbx_ctx* ctx, const orbx_vocabulary* voc) {
 }  // namespace
 
 namespace orbx {
+// orbx_db.cpp: the context a vocabulary was made on
+orbx_ctx* vocCtx(const orbx_vocabulary* v) { return v->ctx; }
+
 // orbx_voc_train.cpp: the descent alone over a batch; *nodes the vocabulary's breadth-first nodes, *fin [n_frames][capacity] the
 // breadth-first index each feature ends at (the vocabulary's scratch: valid until its next call)
 int vocDescend(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_t* d_desc32, const int32_t* d_n, int capacity,

@@ -17,6 +17,7 @@
 
 #include <cstdint>
 
+#include "orbx_bow_terms.h"
 #include "orbx_device.h"
 
 namespace orbx {
@@ -28,18 +29,6 @@ constexpr int BOW_CHUNK = 10;  // children whose descriptors are loaded before t
 __device__ __forceinline__ uint32_t hamming32(const uint4& qa, const uint4& qb, const uint4& a, const uint4& b) {
   return __popc(qa.x ^ a.x) + __popc(qa.y ^ a.y) + __popc(qa.z ^ a.z) + __popc(qa.w ^ a.w) + __popc(qb.x ^ b.x) +
          __popc(qb.y ^ b.y) + __popc(qb.z ^ b.z) + __popc(qb.w ^ b.w);
-}
-
-__device__ __forceinline__ int clampN(const int32_t* n, int f, int cap) {
-  const int v = n[f];
-  return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-__device__ __forceinline__ double readlaneF64(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
-  return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
 }
 
 }  // namespace
@@ -258,7 +247,7 @@ __global__ __launch_bounds__(64 * BOW_SCORE_WAVES) void k_bow_score_l1(BowScoreA
       }
       if (lo < n2 && w2[lo] == w) {
         const double vi = v1[i], wi = v2[lo];
-        term = fabs(vi - wi) - fabs(vi) - fabs(wi);
+        term = bowTermL1(vi, wi);
         found = true;
       }
     }

@@ -438,6 +438,63 @@ struct BowScoreArgs {
   double* score;          // [nPairs]
 };
 
+// ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
+constexpr int DB_THREADS = 256;       // threads of the database kernels
+constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries
+constexpr int DB_SLICE_MAX = 2048;    // entries of one k_db_accumulate workgroup (the default), and the most keys sorted in LDS
+constexpr int DB_MAX_RESULTS = 256;   // ORBX_DB_MAX_RESULTS
+constexpr int DB_MERGE_MAX = 8;       // lists one k_db_merge workgroup merges (the default): DB_MERGE_MAX * DB_MAX_RESULTS keys
+static_assert(DB_MERGE_MAX * DB_MAX_RESULTS <= DB_SLICE_MAX, "a merge sorts its lists in the LDS of one slice");
+constexpr int DB_SCAN_THREADS = 1024;
+struct DbAddArgs {
+  const uint32_t* word;     // [nFrames][cap] the batch's BowVectors (orbx_bow_transform_batch_device's layout)
+  const double* value;      // [nFrames][cap]
+  const int32_t* n;         // [nFrames] (clamped to [0, cap])
+  int32_t cap, nFrames;
+  uint32_t nWords, firstId; // the vocabulary's words; the entry id of frame 0
+  uint32_t oldTotal;        // postings in the old file
+  uint32_t* cnt;            // [nWords] zero before k_db_count, zero again after k_db_scatter
+  const uint32_t* oldRow;   // [nWords + 1]
+  const uint32_t* oldEntry;
+  const double* oldValue;
+  uint32_t* newRow;         // [nWords + 1]
+  uint32_t* newEntry;
+  double* newValue;
+  uint32_t* tmpWord;        // the batch's postings grouped by word, in arrival order within a word
+  uint32_t* tmpFrame;
+  double* tmpValue;
+};
+struct DbQueryArgs {
+  const uint32_t* word;     // [nQueries][cap]
+  const double* value;
+  const int32_t* n;
+  int32_t cap, nQueries;
+  uint32_t nWords;
+  const uint32_t* row;      // the inverted file
+  const uint32_t* entry;
+  const double* pvalue;
+  int32_t scoring, binary;  // binary: DOT_PRODUCT's term is 1 (BINARY weighting)
+  int32_t minCommon;        // common words an entry needs to be listed (1, or MIN_COMMON_WORDS)
+  int32_t descending;       // best first = the largest sum (BHATTACHARYYA, DOT_PRODUCT)
+  int32_t limit;            // entries [0, limit) take part (max_id)
+  int32_t perSlice, nSlices, maxResults;
+  double* listRaw;          // [nQueries][nSlices][maxResults] every slice's best: the sums ...
+  uint32_t* listId;         // ... and the entry ids
+  int32_t* listN;           // [nQueries][nSlices]
+};
+struct DbMergeArgs {
+  int32_t nQueries, nIn, nOut, perMerge, maxResults, scoring, descending;
+  const double* inRaw;      // [nQueries][nIn][maxResults]
+  const uint32_t* inId;
+  const int32_t* inN;       // [nQueries][nIn]
+  double* outRaw;           // [nQueries][nOut][maxResults] (not the last round)
+  uint32_t* outId;
+  int32_t* outN;
+  int32_t* resEntry;        // the last round (nOut == 1): [nQueries][maxResults] entry ids, final scores, counts
+  double* resScore;
+  int32_t* resN;
+};
+
 // ---- DBoW2 TemplatedVocabulary::create (orbx_voc_train_kernel.hip): one tree level at a time ----
 constexpr int VT_THREADS = 256;   // threads of the training kernels, and the features of one block of the level's block table
 constexpr int VT_CHUNK = 4096;    // features one workgroup of k_vt_count counts (a node with more has global counters)
