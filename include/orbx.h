@@ -652,6 +652,54 @@ int64_t orbx_database_get_inverted_file(orbx_database* db, uint32_t* row_start, 
  * result; tests drive several slices and merge rounds on small databases. */
 int orbx_debug_database_shape(int entries_per_slice, int lists_per_merge);
 
+/* ---- matching through the FeatureVector: ORBmatcher::SearchByBoW -----------------------------------------------------------
+ * The step behind a database query: a keyframe KF (a candidate the database returned) is matched against a frame F, every KF
+ * feature only against the F features under the same vocabulary node (Frame::mFeatVec, SlamTypes/Frame.hpp:81; what TH_LOW is
+ * for, Features/ORBmatcher.hpp:56).  The reference ships no SearchByBoW; this is ORB-SLAM2's
+ * SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&), bit-identical to a CPU restatement of the rules below
+ * (tests/cpp/match_bow_ref.cpp):
+ *   1. every matches_f[j] = -1, the 30 rotation bins empty
+ *   2. the node ids present in both FeatureVectors in ascending order; a node's KF features i in ascending index, those with
+ *      kf_mask[i] == 0 skipped: over the node's F features j in ascending index that no earlier KF feature took,
+ *      d = popcount(desc_KF[i] ^ desc_F[j]); best1 = the smallest d, best2 = the second smallest counting duplicates (both start
+ *      at 256), bestIdx = the lowest j attaining best1
+ *   3. best1 <= 50 (TH_LOW) and (float)best1 < nnratio * (float)best2 (an f32 product, strict): matches_f[bestIdx] = i, and with
+ *      check_orientation the match joins bin (int)roundf(rot * (30 / 360.0f)), rot = angle_KF[i] - angle_F[bestIdx] (+ 360.0f
+ *      when negative), bin 30 = bin 0
+ *   4. with check_orientation, ComputeThreeMaxima (Features/ORBmatcher.cpp:152-183) on the bin sizes; the matches of every other
+ *      bin are set back to -1
+ *   nmatches = the entries of matches_f that are not -1.
+ * Documented deviations from ORB-SLAM2:
+ *   1. The bin factor is the reference's corrected HISTO_LENGTH / 360.0f (Features/ORBmatcher.cpp:21-23), not 1.0f / HISTO_LENGTH.
+ *   2. A match whose bin falls outside [0, 30) (an angle that is no angle) joins no bin and is kept, where the reference's
+ *      matcher asserts; orbx_match_init* does the same.
+ *   3. Map points are a mask (kf_mask, one byte per KF feature: 0 = no map point) and an index (matches_f holds the KF feature),
+ *      not MapPoint pointers.
+ * Malformed FeatureVectors: the device form skips a (node, feature) pair whose feature index is not below the frame's count, the
+ * host form refuses it (ORBX_E_BADARG); a FeatureVector that is not ascending by node and feature, or that names a feature
+ * twice, gives unspecified matches (and nothing worse).
+ *
+ * Batched and device-resident: pair p matches keyframe h_kf[p] against frame h_f[p] (host arrays, each in [0, n_frames); a frame
+ * may be in any number of pairs, on either side, also paired with itself) of the arrays orbx_extract_batch_device
+ * (d_kps: only angle is read; d_desc32, 16-byte aligned; d_n) and orbx_bow_transform_batch_device (d_fv_node / d_fv_feat /
+ * d_fv_n) filled, same capacity and layout, so that the three calls chain without a copy.  d_kf_mask (nullable)
+ * [n_frames][capacity].  d_matches_f int32 [n_pairs][capacity]: row p's first d_n[h_f[p]] entries, the rest is unspecified;
+ * d_nmatches int32 [n_pairs].  Stream-ordered on the context stream like the transform (the call returns once queued).
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, a pair index outside [0, n_frames) -- all checked
+ * before anything touches a device; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise
+ * well-formed arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_bow_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_f,
+                                const orbx_keypoint* d_kps, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                const uint32_t* d_fv_node, const uint32_t* d_fv_feat, const int32_t* d_fv_n, const uint8_t* d_kf_mask,
+                                float nnratio, int check_orientation, int32_t* d_matches_f, int32_t* d_nmatches);
+/* The same for one pair in host memory, through the batched path as a batch of one: the keyframe's keypoints / descriptors
+ * (kf_n of them), its FeatureVector (kf_fv_n pairs) and kf_mask (nullable, kf_n bytes), then the frame's; matches_f holds f_n
+ * entries.  More than ORBX_BOW_MAX_FEATURES features or pairs: ORBX_E_CAPACITY.  Synchronous. */
+int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf_desc32, int kf_n, const uint32_t* kf_fv_node,
+                   const uint32_t* kf_fv_feat, int kf_fv_n, const orbx_keypoint* f_kps, const uint8_t* f_desc32, int f_n,
+                   const uint32_t* f_fv_node, const uint32_t* f_fv_feat, int f_fv_n, const uint8_t* kf_mask, float nnratio,
+                   int check_orientation, int32_t* matches_f, int32_t* nmatches);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

@@ -301,13 +301,21 @@ class ORBextractor {
   std::vector<float> mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2;
 };
 
+}  // namespace ORB_SLAM_Tracking
+namespace DBoW2 {
+class FeatureVector;  // (below, with the other DBoW2 types)
+}
+namespace ORB_SLAM_Tracking {
+
 // What ORBmatcher reads from a Frame (Features/ORBmatcher.cpp:14,28,37,44,51,59,109; Frame.cpp:163-206): mvKeysUn,
-// mDescriptors (N x 32 contiguous bytes), N and the static image bounds.
+// mDescriptors (N x 32 contiguous bytes), N and the static image bounds; for SearchByBoW also mFeatVec (SlamTypes/Frame.hpp:81,
+// what ComputeBoW filled; null for a frame without one).
 struct FrameView {
   const KeyPointT* mvKeysUn = nullptr;
   const uint8_t* mDescriptors = nullptr;
   int N = 0;
   int mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;
+  const DBoW2::FeatureVector* mFeatVec = nullptr;
 };
 
 class ORBmatcher {
@@ -334,6 +342,7 @@ class ORBmatcher {
     v.mDescriptors = orbx::descriptorBytes(F.mDescriptors);
     v.N = F.N;
     v.mnMinX = FrameT::mnMinX; v.mnMaxX = FrameT::mnMaxX; v.mnMinY = FrameT::mnMinY; v.mnMaxY = FrameT::mnMaxY;
+    v.mFeatVec = featVecOf(F, 0);
     return v;
   }
 
@@ -343,6 +352,20 @@ class ORBmatcher {
     return search(ext_, F1, F2, vnMatches12, windowSize);
   }
 
+  // ORB-SLAM2's SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) over the two frames' mFeatVec (orbx.h, "matching through
+  // the FeatureVector", with its documented deviations; the reference declares TH_LOW for it, Features/ORBmatcher.hpp:56, and
+  // ships no implementation): every keyframe feature is matched against the frame features under the same vocabulary node.
+  // vnMatchesF[j] = the KF feature matched to F's feature j, or -1; returns the number of matches.  kfHasPoint (optional, KF.N
+  // entries): false = the keyframe's feature has no map point and is skipped.  Both frames' ComputeBoW must have run.
+  int SearchByBoW(const FrameView& KF, const FrameView& F, std::vector<int>& vnMatchesF, const std::vector<bool>* kfHasPoint = nullptr) {
+    return searchByBoW(ext_, KF, F, vnMatchesF, kfHasPoint);
+  }
+  template <class FrameT, class = typename std::enable_if<!std::is_same<typename std::decay<FrameT>::type, FrameView>::value>::type>
+  int SearchByBoW(FrameT& KF, FrameT& F, std::vector<int>& vnMatchesF, const std::vector<bool>* kfHasPoint = nullptr) {
+    ORBextractor* e = ext_ ? ext_ : (KF.mpORBextractor ? KF.mpORBextractor : F.mpORBextractor);
+    return searchByBoW(e, frameView(KF), frameView(F), vnMatchesF, kfHasPoint);
+  }
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -350,6 +373,14 @@ class ORBmatcher {
   inline static constexpr int TH_HIGH = 100;
 
  private:
+  // a Frame-like type's mFeatVec, or null for a type without one
+  template <class FrameT>
+  static auto featVecOf(const FrameT& F, int) -> decltype(&F.mFeatVec) { return &F.mFeatVec; }
+  template <class FrameT>
+  static const DBoW2::FeatureVector* featVecOf(const FrameT&, long) { return nullptr; }
+  inline int searchByBoW(ORBextractor* e, const FrameView& KF, const FrameView& F, std::vector<int>& vnMatchesF,
+                         const std::vector<bool>* kfHasPoint);  // (defined behind DBoW2::FeatureVector)
+
   int search(ORBextractor* e, const FrameView& F1, const FrameView& F2, std::vector<int>& vnMatches12, int windowSize) {
     if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
     vnMatches12.assign(F1.N, -1);  // cpp:14
@@ -510,6 +541,31 @@ class QueryResults : public std::vector<Result> {};
 }  // namespace DBoW2
 
 namespace ORB_SLAM_Tracking {
+
+inline int ORBmatcher::searchByBoW(ORBextractor* e, const FrameView& KF, const FrameView& F, std::vector<int>& vnMatchesF,
+                                   const std::vector<bool>* kfHasPoint) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
+  if (!KF.mFeatVec || !F.mFeatVec) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchByBoW: a frame has no mFeatVec (ComputeBoW has not run)");
+  if (kfHasPoint && (int)kfHasPoint->size() != KF.N) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchByBoW: kfHasPoint needs KF.N entries");
+  std::vector<uint32_t> node[2], feat[2];
+  const DBoW2::FeatureVector* fv[2] = {KF.mFeatVec, F.mFeatVec};
+  for (int s = 0; s < 2; s++)
+    for (const auto& kv : *fv[s])  // (a map: ascending node ids)
+      for (unsigned int i : kv.second) {
+        node[s].push_back(kv.first);
+        feat[s].push_back(i);
+      }
+  std::vector<uint8_t> mask;
+  if (kfHasPoint) mask.assign(kfHasPoint->begin(), kfHasPoint->end());
+  vnMatchesF.assign(F.N, -1);
+  int nmatches = 0;
+  const int r = orbx_match_bow(e->context(), reinterpret_cast<const orbx_keypoint*>(KF.mvKeysUn), KF.mDescriptors, KF.N, node[0].data(),
+                               feat[0].data(), (int)node[0].size(), reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn), F.mDescriptors,
+                               F.N, node[1].data(), feat[1].data(), (int)node[1].size(), kfHasPoint ? mask.data() : nullptr, mfNNratio,
+                               mbCheckOrientation ? 1 : 0, vnMatchesF.data(), &nmatches);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  return nmatches;
+}
 
 // Features/ORBVocabulary.hpp: TemplatedVocabulary<FORB> with the members ORB-SLAM calls -- loadFromTextFile, transform (BowVector +
 // FeatureVector), score (L1Scoring) -- and create / saveToTextFile, on the device of an ORBextractor's context (orbx.h, "bag of words", with its documented

@@ -231,6 +231,8 @@ def lib() -> ctypes.CDLL:
     L.orbx_bow_transform.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_bow_score_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.orbx_bow_score.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
+    L.orbx_match_bow_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, i32, vp, vp]
+    L.orbx_match_bow.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, f32, i32, vp, vp]
     L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.orbx_database_destroy.argtypes = [vp]
     L.orbx_database_destroy.restype = None
@@ -540,6 +542,56 @@ class ORBextractor:
                                                  float(nnratio), int(bool(checkOri)), _ptr(d_matches12), _ptr(d_nmatches),
                                                  _ptr(d_stats))
         self._check(r, "orbx_match_init_batch_device")
+
+    def match_bow_pairs_device(self, n_frames: int, kf: np.ndarray, f: np.ndarray, d_kps, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n,
+                               d_matches_f, d_nmatches, d_kf_mask=None, nnratio: float = 0.6, checkOri: bool = True,
+                               capacity: Optional[int] = None) -> None:
+        """ORBmatcher::SearchByBoW for pairs (keyframe kf[p], frame f[p]; host index arrays) of the arrays extract_batch_device
+        and Vocabulary.transform_batch_device filled (same capacity): d_matches_f int32 [n_pairs, capacity] (row p: the keyframe
+        feature matched to each of frame f[p]'s features, or -1), d_nmatches int32 [n_pairs]; d_kf_mask (optional) uint8
+        [n_frames, capacity], 0 = the keyframe's feature has no map point.  Stream-ordered on the context's stream."""
+        kf = np.ascontiguousarray(kf, np.int32).reshape(-1)
+        f = np.ascontiguousarray(f, np.int32).reshape(-1)
+        if len(kf) != len(f):
+            raise OrbxError(E_BADARG, "kf and f must have the same length")
+        cap, nf, P = int(capacity or self.capacity), int(n_frames), len(kf)
+        _need("the keypoint array", d_kps, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
+        _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
+        _need("the FeatureVector count array", d_fv_n, nf * 4)
+        if d_kf_mask is not None:
+            _need("the keyframe mask", d_kf_mask, nf * cap)
+        _need("matches_f", d_matches_f, P * cap * 4)
+        _need("nmatches", d_nmatches, P * 4)
+        self._order_torch(d_kps, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n, d_kf_mask, d_matches_f, d_nmatches)
+        r = self._L.orbx_match_bow_batch_device(self._h, nf, P, _ptr(kf), _ptr(f), _ptr(d_kps), _ptr(d_desc), _ptr(d_n), cap,
+                                                _ptr(d_fv_node), _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_kf_mask), float(nnratio),
+                                                int(bool(checkOri)), _ptr(d_matches_f), _ptr(d_nmatches))
+        self._check(r, "orbx_match_bow_batch_device")
+
+    def match_bow(self, kf_keys, kf_desc, kf_fv_node, kf_fv_feat, f_keys, f_desc, f_fv_node, f_fv_feat, kf_mask=None,
+                  nnratio: float = 0.6, checkOri: bool = True):
+        """SearchByBoW for one pair in host memory (orbx_match_bow) -> (matches_f int32 [len(f_keys)], nmatches).  Synchronous."""
+        kk, fk = np.ascontiguousarray(kf_keys, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(f_keys, KEYPOINT_DTYPE).reshape(-1)
+        kd, fd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(f_desc, np.uint8).reshape(-1, 32)
+        kn, kft = np.ascontiguousarray(kf_fv_node, np.uint32).reshape(-1), np.ascontiguousarray(kf_fv_feat, np.uint32).reshape(-1)
+        fn, fft = np.ascontiguousarray(f_fv_node, np.uint32).reshape(-1), np.ascontiguousarray(f_fv_feat, np.uint32).reshape(-1)
+        if len(kk) != len(kd) or len(fk) != len(fd) or len(kn) != len(kft) or len(fn) != len(fft):
+            raise OrbxError(E_BADARG, "keypoints / descriptors or FeatureVector nodes / features differ in length")
+        mask = None
+        if kf_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(kf_mask) != 0, np.uint8).reshape(-1)
+            if len(mask) != len(kk):
+                raise OrbxError(E_BADARG, "the mask needs one entry per keyframe feature")
+        m = np.full(max(len(fk), 1), -1, np.int32)
+        nm = ctypes.c_int32(0)
+        r = self._L.orbx_match_bow(self._h, _ptr(kk), _ptr(kd), len(kk), _ptr(kn), _ptr(kft), len(kn), _ptr(fk), _ptr(fd), len(fk),
+                                   _ptr(fn), _ptr(fft), len(fn), _ptr(mask), float(nnratio), int(bool(checkOri)), _ptr(m),
+                                   ctypes.byref(nm))
+        self._check(r, "orbx_match_bow")
+        return m[:len(fk)].copy(), int(nm.value)
 
     def extract_match_batch_device(self, d_imgs, n_frames: int, width: int, height: int, stride: int, frame_stride: int,
                                    d_kps, d_desc, d_n, first: np.ndarray, second: np.ndarray,
@@ -1293,6 +1345,7 @@ class Frame:
         for node, feat in zip(r.fv_node.tolist(), r.fv_feat.tolist()):
             fv.setdefault(node, []).append(feat)
         self.mFeatVec = fv
+        self._bow_computed = True  # (both vectors may be empty: ORBmatcher.SearchByBoW asks whether this has run)
 
 
 class ORBmatcher:
@@ -1325,3 +1378,23 @@ class ORBmatcher:
         ext._check(r, "orbx_match_init")
         self.last_stats = (st.invalid_by_distance, st.invalid_by_ratio, st.invalid_by_orientation)
         return int(nm.value), m12[:len(k1)].copy()
+
+    def SearchByBoW(self, KF: Frame, F: Frame, mask=None):
+        """ORB-SLAM2's SearchByBoW(KeyFrame*, Frame&, ...) over the frames' mFeatVec (include/orbx.h, "matching through the
+        FeatureVector") -> (matches_f, nmatches): matches_f[j] = the KF feature matched to F's feature j, or -1.  mask
+        (optional): one entry per KF feature, false = it has no map point.  Both frames' ComputeBoW must have run."""
+        ext = self._ext or KF.mpORBextractor or F.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        for name, fr in (("KF", KF), ("F", F)):
+            if not (getattr(fr, "_bow_computed", False) or fr.mBowVec or fr.mFeatVec):
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchByBoW: %s has no FeatureVector; call its ComputeBoW() first" % name)
+
+        def flat(fv):
+            node = [n for n in sorted(fv) for _ in fv[n]]
+            feat = [j for n in sorted(fv) for j in fv[n]]
+            return np.asarray(node, np.uint32), np.asarray(feat, np.uint32)
+        kn, kf = flat(KF.mFeatVec)
+        fn, ff = flat(F.mFeatVec)
+        return ext.match_bow(KF.mvKeysUn, KF.mDescriptors, kn, kf, F.mvKeysUn, F.mDescriptors, fn, ff, mask, self.mfNNratio,
+                             self.mbCheckOrientation)

@@ -214,6 +214,7 @@ struct orbx_ctx {
   DeviceBuf<uint8_t> dInit;       // arena of orbx_find_models* / orbx_initialize*
   DeviceBuf<int32_t> dInitPairs;  // their pair list (first[], second[]) as ctx->initPairs holds it
   DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
+  MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -2955,4 +2956,5 @@ int ctxDrain(orbx_ctx* c) {
   return waitAll(c);
 }
 void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
+MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 }  // namespace orbx

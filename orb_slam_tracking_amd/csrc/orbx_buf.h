@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
 namespace orbx {
 
@@ -125,6 +126,13 @@ class Layout {
  private:
   uintptr_t base_ = 0;
   size_t off_ = 0;
+};
+
+// What a context keeps for orbx_match_bow* (orbx_match_bow.cpp; the context owns it, orbx_api.cpp).
+struct MatchBowScratch {
+  DeviceBuf<int32_t> dPairs;    // the pair list [2][n_pairs] of the last call
+  std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_match_bow
 };
 
 }  // namespace orbx

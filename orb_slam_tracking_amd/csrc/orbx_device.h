@@ -438,6 +438,24 @@ struct BowScoreArgs {
   double* score;          // [nPairs]
 };
 
+// ---- ORBmatcher::SearchByBoW (orbx_match_bow_kernel.hip): one workgroup per (keyframe, frame) pair ----
+constexpr int MB_WAVES = 4;  // waves of k_match_bow: the pair's common nodes go to them in turn
+constexpr int MB_THREADS = 64 * MB_WAVES;
+struct MatchBowArgs {
+  const orbx_keypoint* kps;  // [nFrames][cap] (only angle is read)
+  const uint8_t* desc;       // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;          // [nFrames] (clamped to [0, cap])
+  const uint32_t* fvNode;    // [nFrames][cap] the FeatureVectors as orbx_bow_transform_batch_device writes them
+  const uint32_t* fvFeat;    // [nFrames][cap]
+  const int32_t* fvN;        // [nFrames] (clamped to [0, cap])
+  const uint8_t* mask;       // nullable [nFrames][cap]: 0 = the keyframe's feature has no map point
+  const int32_t* pairs;      // [2][nPairs] keyframes, then frames
+  int32_t cap, nPairs, checkOri;
+  float nnratio;
+  int32_t* matchesF;         // [nPairs][cap]
+  int32_t* nmatches;         // [nPairs]
+};
+
 // ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
 constexpr int DB_THREADS = 256;       // threads of the database kernels
 constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries
