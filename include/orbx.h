@@ -434,6 +434,101 @@ int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_
                      int n_iter, const int32_t* sets, float sigma, orbx_hf_result* res, uint8_t* inliers, float* models,
                      float* scores);
 
+/* ---- behind the Initializer: two-view bundle adjustment (g2o, as Tracking::CreateInitialMapMonocular uses it) -----------------
+ * Optimizer::GlobalBundleAdjustemnt(map, 20) of the ORB-SLAM design on the two initial keyframes and their points, the median-
+ * depth normalisation and the "Wrong initialization, reseting" test behind it, for a batch of pairs, read from the arrays
+ * orbx_initialize_batch_device left on the device.  The reference vendors the g2o types and solver (Thirdparty/g2o) but nothing
+ * in it calls them: every rule below restates the g2o lines it cites, [from-knowledge] where Eigen is involved, PARITY UNPINNED
+ * (no Eigen exists to compile g2o against).  The device equals the CPU restatement tests/cpp/ba_ref.cpp bit for bit.
+ *
+ * Graph.  Frame 1 is the identity pose, fixed.  Frame 2 starts at the Initializer's (R21, t21), f32 -> f64, as SE3Quat(R, t)
+ * builds it (types/se3quat.h:58-60, :280-285): rotation matrix -> quaternion, w made non-negative, normalised.  One
+ * VertexSBAPointXYZ (types/types_sba.h) per i with matches12[i] >= 0 && triangulated[i], ascending i, from vP3D[i] f32 -> f64.
+ * Each point has two EdgeSE3ProjectXYZ (types/types_six_dof_expmap.h): obs = the keypoint's pt in its frame, information =
+ * inv_sigma2[octave] * I, RobustKernelHuber with delta = (float)sqrt(5.99), fx fy cx cy from K.
+ *
+ * Per iteration (core/optimization_algorithm_levenberg.cpp:61-164):
+ *  1. computeActiveErrors and activeRobustChi2 (rho[0] of every edge; core/robust_kernel_impl.cpp:78-91).
+ *  2. linearizeOplus: the expressions of types/types_six_dof_expmap.cpp:98-134.
+ *  3. constructQuadraticForm's robust branch (core/base_binary_edge.hpp:91-113): weightedOmega = rho[1] * omega, omega_r =
+ *     -omega e rho[1]; robustInformation's commented-out second-order term stays out.
+ *  4. At iteration 0 computeLambdaInit (:166-180): 1e-5 times the largest |diagonal entry| of the pose's and every point's block.
+ *  5. Up to 10 trials (:102-149): setLambda on every diagonal; the Schur solve of core/block_solver.hpp:354-486 (Dinv = (Hll +
+ *     lambda I)^-1 per point, Hschur = Hpp - sum Hpl Dinv Hpl^T, bschur = bp - sum Hpl Dinv bl, the 6x6 solve, xl = Dinv (bl -
+ *     Hpl^T xp)); oplus: the pose by SE3Quat::exp(update) * estimate (se3quat.h:223-257, with its theta < 1e-5 branch and the
+ *     normalisation of :104-110), the points by addition; the new errors, tempChi (DBL_MAX when the solve failed), computeScale
+ *     (:182-189) + 1e-3, rho; accept (alpha = 1 - (2 rho - 1)^3 clamped to [1/3, 2/3], _ni = 2) or reject (lambda *= _ni,
+ *     _ni *= 2, the state restored); another trial while rho < 0.
+ *  6. Terminate when qmax == 10 || rho == 0 (:151); Raul Mur-Artal's rule (:155-161): _nBad counts the iterations in a row with
+ *     (iniChi - currentChi) * 1e3 < iniChi, Terminate at 3.
+ *  7. SparseOptimizer::optimize's loop (core/sparse_optimizer.cpp:376-414) ends on the first result that is not OK.
+ * Behind the optimisation: the points go back to f32; ComputeSceneMedianDepth(2) in frame 1 = the z of the f32 points, sorted,
+ * at element (n - 1) / 2; with normalize != 0 and no status bit set (and a median > 0), t21 and every refined point are
+ * multiplied by 1.0f / median in f32, as CreateInitialMapMonocular does.
+ *
+ * Documented deviations:
+ *  1. Sums.  Every sum over points (chi2, Hpp, bp, the Schur terms, computeScale) is f64 in this order: the workgroup has 256
+ *     lanes; lane l adds the terms of points l, l + 256, l + 512, ... one after the other, a point's frame-1 edge before its
+ *     frame-2 edge; in each wave of 64 lanes, lane l then adds lane l + 32's sum to its own, then lane l + 16's, + 8, + 4, + 2,
+ *     + 1; the four waves' sums are added in wave order, starting from wave 0's.  computeScale adds the pose's six terms first,
+ *     then the points' sum, then 1e-3.  g2o adds edge by edge.
+ *  2. Small dense algebra.  The 3x3 inverse is by cofactors and one reciprocal of the determinant; the 6x6 solve is an unblocked
+ *     lower Cholesky in which a pivot <= 0 or non-finite, or a non-finite solution, means the solve failed, and the whole step
+ *     is then zero (g2o applies whatever its solver left); matrix -> quaternion uses Eigen's four-branch rule; pow(x, 3) is
+ *     x * x * x.  The same mathematics as Eigen / libm, other rounding.
+ *  3. sin(theta) and cos(theta) in SE3Quat::exp come from one restated f64 routine (csrc/orbx_ba_math.inc: Cody-Waite reduction
+ *     by pi/2, fdlibm's polynomials), not from a libm; theta >= 2^19 gives NaN (and ORBX_BA_NONFINITE).
+ *  4. There are no Map / KeyFrame / MapPoint types and no pbStopFlag.
+ *  5. A pair whose orbx_init_result.status != 0 is skipped: the reference never reaches the adjustment for it.
+ *  6. Garbage inputs set flags and never lead to an out-of-range read.  A pair with a status bit other than FEW_POINTS /
+ *     NEGATIVE_DEPTH is not optimised: its points and (R21, t21) are the inputs, every other number is 0; a non-finite RESULT
+ *     keeps its counters.  Without any point no iteration runs.  With n_iterations == 0 (or no point) chi2_initial and
+ *     chi2_final are 0, the points and t21 come back bit for bit (f32 -> f64 -> f32), and R21 comes back as the rotation matrix
+ *     of the normalised quaternion SE3Quat(R, t) built from it: within a few f32 roundings of the input, not its bits. */
+#define ORBX_BA_SKIPPED 1        /* the pair's orbx_init_result.status != 0 */
+#define ORBX_BA_BAD_INPUT 2      /* a frame count outside [0, capacity], a matches12 entry >= n2, an octave outside [0, nlevels) */
+#define ORBX_BA_NONFINITE 4      /* a non-finite input point or pose, or a non-finite result */
+#define ORBX_BA_FEW_POINTS 8     /* n_points < min_points (the reference: TrackedMapPoints(1) < 100) */
+#define ORBX_BA_NEGATIVE_DEPTH 16 /* median depth < 0 */
+typedef struct orbx_ba_result {
+  int32_t status;           /* 0, or a bitmask of ORBX_BA_*; every field is written for every pair */
+  int32_t n_points;         /* point vertices */
+  int32_t iterations;       /* solve() calls made (g2o's cjIterations) */
+  int32_t lm_trials;        /* the sum of qmax */
+  int32_t rejected_trials;
+  int32_t solver_failures;
+  int32_t stop_reason;      /* 0 = all iterations ran, 1 = qmax == 10 || rho == 0, 2 = _nBad >= 3 */
+  int32_t reserved;
+  double chi2_initial, chi2_final, lambda;
+  double q[4], t[3];        /* the refined pose as g2o holds it: quaternion (x, y, z, w) and translation */
+  float R21[9], t21[3];     /* as Converter::toCvMat would store it (row-major), after the normalisation if it was applied */
+  float median_depth;
+  float reserved2;
+} orbx_ba_result;
+
+/* Batched, device-resident, stream-ordered on the context stream (results valid after a device synchronisation), in the layout
+ * of orbx_initialize_batch_device, whose d_res / d_p3d / d_triangulated are d_init_res / d_p3d / d_triangulated here.  K row-major
+ * 3x3 (host, f32); inv_sigma2: host, the context's nlevels floats (mvInvLevelSigma2), NULL = the context's own table;
+ * n_iterations >= 0 (the reference passes 20); min_points (100).  Outputs: d_res [n_pairs]; d_p3d_out float [n_pairs][capacity][3]
+ * = the refined points where a point vertex exists, d_p3d's entry elsewhere; it may equal d_p3d.  One workgroup per pair runs
+ * the whole optimisation in one launch.  The call returns once queued, with one exception: when the pair list or the table differs
+ * from the previous call's on this context, the call first waits for the context stream before it uploads them (the first call
+ * always does); a caller that adjusts the same pairs of every batch, as the extract + match calls are used, never waits again.
+ * ORBX_E_BADARG: null pointers, negative counts, n_frames < 1 with pairs, capacity < 1,
+ * a pair index outside [0, n_frames), n_iterations < 0; ORBX_E_CAPACITY: capacity >= 2^20; ORBX_E_HIP: ctx == NULL with otherwise
+ * well-formed arguments -- all checked before anything touches a device.  n_pairs == 0 is ORBX_OK. */
+int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
+                                    const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
+                                    const orbx_init_result* d_init_res, const float* d_p3d, const uint8_t* d_triangulated,
+                                    const float* K, const float* inv_sigma2, int n_iterations, int min_points, int normalize,
+                                    orbx_ba_result* d_res, float* d_p3d_out);
+/* The same for one pair in host memory, run through the batched path as a batch of one; p3d_out [n1][3] may equal p3d.
+ * Synchronous. */
+int orbx_bundle_adjust(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
+                       const orbx_init_result* init_res, const float* p3d, const uint8_t* triangulated, const float* K,
+                       const float* inv_sigma2, int n_iterations, int min_points, int normalize, orbx_ba_result* res,
+                       float* p3d_out);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

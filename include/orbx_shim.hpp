@@ -512,6 +512,60 @@ class Initializer {
   ORBextractor* mpORBextractor;
 };
 
+// ---- Optimizer: the two-view bundle adjustment of Tracking::CreateInitialMapMonocular (include/orbx.h, "behind the Initializer:
+// two-view bundle adjustment") ------------------------------------------------------------------------------------
+// BundleAdjustmentTwoView(F1, F2, vMatches12, Tcw, vP3D, vbTriangulated, nIterations): what Initialize() returned, refined in
+// place by orbx_bundle_adjust on the device of the frames' extractor: GlobalBundleAdjustemnt(map, 20) on the two initial
+// keyframes, then the median-depth normalisation and the "Wrong initialization, reseting" test (100 points, a positive median
+// depth).  Returns the status (0 = accepted; ORBX_BA_* bits otherwise, Tcw and vP3D then hold the refined but unnormalised
+// values, or the inputs if nothing was optimised); argument / HIP errors throw orbx::Error.
+class Optimizer {
+ public:
+  template <class FrameT, class Point3>
+  static int BundleAdjustmentTwoView(const FrameT& F1, const FrameT& F2, const std::vector<int>& vMatches12, PoseT& Tcw,
+                                     std::vector<Point3>& vP3D, std::vector<bool>& vbTriangulated, int nIterations = 20) {
+    ORBextractor* e = F2.mpORBextractor ? F2.mpORBextractor : F1.mpORBextractor;
+    if (!e) throw orbx::Error(ORBX_E_BADARG, "Optimizer: the frames carry no extractor");
+    const size_t n1 = F1.mvKeysUn.size();
+    if (vMatches12.size() != n1 || vP3D.size() != n1 || vbTriangulated.size() != n1)
+      throw orbx::Error(ORBX_E_BADARG, "Optimizer: vMatches12, vP3D and vbTriangulated must have one entry per keypoint of frame 1");
+    orbx_init_result ir = {};
+    float K[9];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) {
+        ir.R21[r * 3 + c] = (float)Tcw(r, c);
+        K[r * 3 + c] = frameK(F1.mK, r, c);
+      }
+      ir.t21[r] = (float)Tcw(r, 3);
+    }
+    std::vector<float> p3d(3 * (n1 ? n1 : 1));
+    std::vector<uint8_t> tri(n1 ? n1 : 1);
+    for (size_t i = 0; i < n1; i++) {
+      p3d[3 * i] = vP3D[i].x;
+      p3d[3 * i + 1] = vP3D[i].y;
+      p3d[3 * i + 2] = vP3D[i].z;
+      tri[i] = vbTriangulated[i] ? 1 : 0;
+    }
+    orbx_ba_result res;
+    const int r = orbx_bundle_adjust(e->context(), reinterpret_cast<const orbx_keypoint*>(F1.mvKeysUn.data()), (int)n1,
+                                     reinterpret_cast<const orbx_keypoint*>(F2.mvKeysUn.data()), (int)F2.mvKeysUn.size(),
+                                     vMatches12.data(), &ir, p3d.data(), tri.data(), K, nullptr, nIterations, 100, 1, &res, p3d.data());
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+    if (orbx::verbose() && (res.status & (ORBX_BA_FEW_POINTS | ORBX_BA_NEGATIVE_DEPTH)))
+      std::cout << "Wrong initialization, reseting..." << std::endl;
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Tcw(i, j) = res.R21[i * 3 + j];
+      Tcw(i, 3) = res.t21[i];
+    }
+    for (size_t i = 0; i < n1; i++) {
+      vP3D[i].x = p3d[3 * i];
+      vP3D[i].y = p3d[3 * i + 1];
+      vP3D[i].z = p3d[3 * i + 2];
+    }
+    return res.status;
+  }
+};
+
 }  // namespace ORB_SLAM_Tracking
 
 // DBoW2's vector types (Thirdparty/DBoW2/include/DBoW2/BowVector.h, FeatureVector.h): the same names and key / value types

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -95,6 +95,28 @@ class InitResult(ctypes.Structure):
 INIT_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _INIT_INTS] + [(n, "<f4") for n in ("score_h", "score_f", "rh", "parallax")] +
                              [("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3))])
 assert INIT_RESULT_DTYPE.itemsize == ctypes.sizeof(InitResult) == 184
+BA_SKIPPED, BA_BAD_INPUT, BA_NONFINITE, BA_FEW_POINTS, BA_NEGATIVE_DEPTH = 1, 2, 4, 8, 16
+_BA_INTS = ("status", "n_points", "iterations", "lm_trials", "rejected_trials", "solver_failures", "stop_reason", "reserved")
+
+
+class BAResult(ctypes.Structure):
+    """orbx_ba_result: the two-view bundle adjustment's outcome for one pair (status 0 = a usable initial map)."""
+    _fields_ = [(n, ctypes.c_int32) for n in _BA_INTS] + [(n, ctypes.c_double) for n in ("chi2_initial", "chi2_final", "lambda_")] + \
+               [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
+                ("median_depth", ctypes.c_float), ("reserved2", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
+        d["lambda"] = d.pop("lambda_")
+        d["q"], d["t"] = np.array(d["q"][:], np.float64), np.array(d["t"][:], np.float64)
+        d["R21"], d["t21"] = np.array(d["R21"][:], np.float32).reshape(3, 3), np.array(d["t21"][:], np.float32)
+        return d
+
+
+BA_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _BA_INTS] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
+                           [("q", "<f8", 4), ("t", "<f8", 3), ("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("median_depth", "<f4"),
+                            ("reserved2", "<f4")])
+assert BA_RESULT_DTYPE.itemsize == ctypes.sizeof(BAResult) == 168
 
 
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
@@ -216,6 +238,8 @@ def lib() -> ctypes.CDLL:
     L.orbx_find_models.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, f32, ctypes.POINTER(HFResult), vp, vp, vp]
     L.orbx_initialize_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, f32, f32, i32, vp, vp, vp]
     L.orbx_initialize.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, f32, f32, i32, ctypes.POINTER(InitResult), vp, vp]
+    L.orbx_bundle_adjust_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.orbx_bundle_adjust.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(BAResult), vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -341,7 +365,7 @@ def _need(what: str, a, nbytes: int) -> None:
 
 
 def _need_batch(imgs, n_frames, width, height, stride, frame_stride, kps, desc, n, capacity, first=None, second=None, matches12=None,
-                nmatches=None, stats=None) -> None:
+                nmatches=None, stats=None, init_res=None, p3d=None, triangulated=None, ba_res=None, p3d_out=None) -> None:
     if n_frames > 0 and imgs is not None:
         _need("the frames", imgs, (n_frames - 1) * frame_stride + (height - 1) * stride + width)
     _need("the keypoint array", kps, n_frames * capacity * 28)
@@ -357,6 +381,12 @@ def _need_batch(imgs, n_frames, width, height, stride, frame_stride, kps, desc, 
         _need("nmatches", nmatches, len(first) * 4)
         if stats is not None:
             _need("stats", stats, len(first) * 12)
+        # the arrays of the bundle adjustment (each per pair)
+        _need("the Initializer's results", init_res, len(first) * INIT_RESULT_DTYPE.itemsize)
+        _need("the point array", p3d, len(first) * capacity * 12)
+        _need("the triangulated array", triangulated, len(first) * capacity)
+        _need("the result array", ba_res, len(first) * BA_RESULT_DTYPE.itemsize)
+        _need("the refined point array", p3d_out, len(first) * capacity * 12)
 
 
 def _torch_stream(*arrays):
@@ -885,6 +915,60 @@ class ORBextractor:
                                                          _ptr(d_matches12), n_iter, _ptr(d_sets), _ptr(Kf), float(sigma),
                                                          float(min_parallax), int(min_triangulated), _ptr(d_res), _ptr(d_p3d),
                                                          _ptr(d_triangulated)), "orbx_initialize_batch_device")
+
+    # -- two-view bundle adjustment behind the Initializer (include/orbx.h) ------------------------------
+    def bundle_adjust(self, keys1, keys2, matches12, init_res, p3d, triangulated, K, inv_sigma2=None, n_iterations: int = 20,
+                      min_points: int = 100, normalize: bool = True):
+        """One pair from host memory: what initialize() took and returned (its InitResult, vP3D, vbTriangulated).  Returns
+        (BAResult, refined vP3D [n1, 3] float32); result.status == 0 is an accepted initial map."""
+        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        pts = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+        tri = np.ascontiguousarray(np.asarray(triangulated) != 0, np.uint8)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        if len(m12) != len(k1) or len(pts) != len(k1) or len(tri) != len(k1):
+            raise OrbxError(E_BADARG, "matches12, p3d and triangulated must have one entry per keypoint of frame 1")
+        if isinstance(init_res, InitResult):
+            ir = init_res
+        else:
+            ir = InitResult.from_buffer_copy(np.ascontiguousarray(init_res, INIT_RESULT_DTYPE).tobytes())
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        res = BAResult()
+        out = np.zeros((max(len(k1), 1), 3), np.float32)
+        self._check(self._L.orbx_bundle_adjust(self._h, _ptr(k1), len(k1), _ptr(k2), len(k2), _ptr(m12), ctypes.byref(ir), _ptr(pts),
+                                               _ptr(tri), _ptr(Kf), _ptr(sig), int(n_iterations), int(min_points), int(bool(normalize)),
+                                               ctypes.byref(res), _ptr(out)), "orbx_bundle_adjust")
+        return res, out[:len(k1)]
+
+    def bundle_adjust_batch_device(self, n_frames: int, first: np.ndarray, second: np.ndarray, d_kps_un, d_n, d_matches12, d_init_res,
+                                   d_p3d, d_triangulated, K, d_res, d_p3d_out=None, inv_sigma2=None, n_iterations: int = 20,
+                                   min_points: int = 100, normalize: bool = True, capacity: Optional[int] = None) -> None:
+        """Batched and device-resident, chained behind initialize_batch_device on the same arrays (its d_res, d_p3d,
+        d_triangulated); d_res [n_pairs] BA_RESULT_DTYPE records (168 bytes); d_p3d_out float32 [n_pairs, capacity, 3], None =
+        in place (d_p3d).  Stream-ordered: the outputs are valid after a device synchronisation."""
+        first = np.ascontiguousarray(first, np.int32)
+        second = np.ascontiguousarray(second, np.int32)
+        cap = int(capacity or self.capacity)
+        if len(second) != len(first):
+            raise OrbxError(E_BADARG, "first and second must have the same length")
+        if d_p3d_out is None:
+            d_p3d_out = d_p3d
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        n_frames = int(n_frames)
+        _need_batch(None, n_frames, 0, 0, 0, 0, d_kps_un, None, d_n, cap, first, second, d_matches12, None, None, init_res=d_init_res,
+                    p3d=d_p3d, triangulated=d_triangulated, ba_res=d_res, p3d_out=d_p3d_out)
+        self._order_torch(d_kps_un, d_n, d_matches12, d_init_res, d_p3d, d_triangulated, d_res, d_p3d_out)
+        self._check(self._L.orbx_bundle_adjust_batch_device(self._h, n_frames, len(first), _ptr(first), _ptr(second), _ptr(d_kps_un),
+                                                            _ptr(d_n), cap, _ptr(d_matches12), _ptr(d_init_res), _ptr(d_p3d),
+                                                            _ptr(d_triangulated), _ptr(Kf), _ptr(sig), int(n_iterations),
+                                                            int(min_points), int(bool(normalize)), _ptr(d_res), _ptr(d_p3d_out)),
+                    "orbx_bundle_adjust_batch_device")
 
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:

@@ -215,6 +215,7 @@ struct orbx_ctx {
   DeviceBuf<int32_t> dInitPairs;  // their pair list (first[], second[]) as ctx->initPairs holds it
   DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
   MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
+  BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -2957,4 +2958,9 @@ int ctxDrain(orbx_ctx* c) {
 }
 void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
 MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
+BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
+const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
+  *nlevels = c->p.nlevels;
+  return c->invSigma2.data();
+}
 }  // namespace orbx

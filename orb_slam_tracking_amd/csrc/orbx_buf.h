@@ -1,5 +1,5 @@
 // orbx_buf.h — owners of the library's device and page-locked host memory, and the one description of a staging block.
-// orbx_api.cpp and orbx_bow.cpp allocate and free through these types only.
+// orbx_api.cpp, orbx_bow.cpp and orbx_ba.cpp allocate and free through these types only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,6 +133,16 @@ struct MatchBowScratch {
   DeviceBuf<int32_t> dPairs;    // the pair list [2][n_pairs] of the last call
   std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
   DeviceBuf<uint8_t> dIo;       // staging of orbx_match_bow
+};
+
+// What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp; the context owns it, orbx_api.cpp).
+struct BaScratch {
+  DeviceBuf<uint8_t> dWork;     // the per-point blocks of every pair: sized from n_pairs x capacity
+  DeviceBuf<int32_t> dPairs;    // the pair list [2][n_pairs] of the last call
+  std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
+  DeviceBuf<float> dSigma;      // inv_sigma2 of the last call
+  std::vector<float> hSigma;
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_bundle_adjust
 };
 
 }  // namespace orbx

@@ -555,4 +555,25 @@ struct VtArgs {
   int32_t* stats;           // [8] orbx_vocabulary_train's statistics; [8] nodes still running after this round
 };
 
+// k_ba: the two-view bundle adjustment (include/orbx.h, "behind the Initializer: two-view bundle adjustment"), a workgroup per pair
+constexpr int BA_THREADS = 256;     // lanes of the workgroup = the stride of the points over the lanes
+constexpr int BA_WS_DOUBLES = 33;   // per point: estimate 3, its backup 3, Hll 6, bl 3, Hpl 18
+constexpr int BA_WS_FLOATS = 6;     // per point: u1 v1 u2 v2, inv_sigma2 of the two keypoints' octaves
+struct BaArgs {
+  const orbx_keypoint* kps;      // [frames][cap] mvKeysUn
+  const int32_t* nKps;           // [frames]
+  const int32_t* m12;            // [nPairs][cap]
+  const int32_t* frames;         // [2][nPairs] first frames, then second frames
+  const orbx_init_result* ires;  // [nPairs]
+  const float* p3d;              // [nPairs][cap][3]
+  const uint8_t* tri;            // [nPairs][cap]
+  const float* invSigma2;        // [nLevels] (device)
+  orbx_ba_result* res;           // [nPairs]
+  float* p3dOut;                 // [nPairs][cap][3], may be p3d
+  double* ws;                    // [nPairs][BA_WS_DOUBLES][cap]
+  float* wf;                     // [nPairs][BA_WS_FLOATS][cap]
+  int32_t* widx;                 // [nPairs][cap] the point vertex's keypoint of frame 1
+  double fx, fy, cx, cy, delta;
+  int32_t nPairs, cap, nLevels, nIterations, minPoints, normalize;
+};
 }  // namespace orbx
