@@ -297,6 +297,17 @@ int ir_decompose_essential(const float* F, const float* K, float* R, float* t) {
 int ir_decompose_homography(const float* H, const float* K, float* R, float* t, float* n) {
   return orbx_decomp::decomposeHomography(H, K, (float(*)[9])R, (float(*)[3])t, (float(*)[3])n);
 }
+// ReconstructHF's choice and acceptance rules as both sides compile them (orbx_init_decomp.inc), for the comparison with a
+// statement of Initializer.cpp:490-545 that shares no source with it.  io = {bestIdx, bestGood, secondGood}; returns the rule bits.
+int ir_reconstruct_rules(int nSol, const int32_t* nGood, const float* parallax, int nInliers, float minParallax, int minTriangulated,
+                         int32_t* io, float* bestParallax) {
+  int ng[4] = {0, 0, 0, 0}, bi, bg, sg;
+  float par[4] = {0, 0, 0, 0};
+  for (int i = 0; i < nSol && i < 4; i++) { ng[i] = nGood[i]; par[i] = parallax[i]; }
+  const int st = orbx_decomp::reconstructRules(nSol, ng, par, nInliers, minParallax, minTriangulated, &bi, &bg, &sg, bestParallax);
+  io[0] = bi; io[1] = bg; io[2] = sg;
+  return st;
+}
 }  // extern "C"
 
 extern "C" {

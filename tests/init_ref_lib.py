@@ -42,6 +42,7 @@ def lib() -> ctypes.CDLL:
     L.ir_find_models.restype = None
     L.ir_sample_sets.argtypes = [ctypes.c_uint, i32, i32, vp]
     L.ir_sample_sets.restype = None
+    L.ir_reconstruct_rules.argtypes = [i32, vp, vp, i32, f32, i32, vp, vp]
     _L = L
     return L
 
@@ -208,3 +209,116 @@ def planar_case(seed=0, n=400, noise=0.3, outliers=0.1):
     wrong = rng.random(n) < outliers
     m12[wrong] = rng.integers(0, n, wrong.sum())
     return K, R, t, nrm, d, k1, k2, m12, X
+
+
+def reconstruct_rules(n_good, parallax, n_inliers, min_parallax=1.0, min_triangulated=50):
+    """orbx_init_decomp.inc's reconstructRules as compiled into the restatement -> (status bits, bestIdx, bestGood, secondGood,
+    bestParallax f32); one entry of n_good / parallax per candidate (0, 1 or 4 of them)."""
+    ng, par = np.ascontiguousarray(n_good, np.int32), np.ascontiguousarray(parallax, np.float32)
+    io, bp = np.zeros(3, np.int32), np.zeros(1, np.float32)
+    st = lib().ir_reconstruct_rules(len(ng), _p(ng), _p(par), int(n_inliers), float(min_parallax), int(min_triangulated), _p(io), _p(bp))
+    return int(st), int(io[0]), int(io[1]), int(io[2]), bp[0]
+
+
+def rotation_case(seed=3, n=500):
+    """A pure rotation: frame 1 of oracle_lib.two_view_case(seed, n), frame 2 its exact image under K R K^-1 (rounded to f32), every
+    keypoint matched.  -> (K, R, k1, k2, matches12)."""
+    K, Rm, _, k1, *_ = oracle_lib.two_view_case(seed=seed, n=n)
+    H = K @ Rm @ np.linalg.inv(K)
+    p = np.c_[k1["x"], k1["y"], np.ones(len(k1))] @ H.T
+    k2 = k1.copy()
+    k2["x"], k2["y"] = (p[:, 0] / p[:, 2]).astype(np.float32), (p[:, 1] / p[:, 2]).astype(np.float32)
+    return K, Rm, k1, k2, np.arange(len(k1), dtype=np.int32)
+
+
+def doubled(k1, k2, m12, seed, n_iter=200):
+    """Every keypoint twice: frames k1 ++ k1 and k2 ++ k2, matches m12 ++ (m12 + len(k2)) with holes kept, so that position c of
+    mvMatches12 (N/2 of them) has a copy at c + N/2.  mvSets are built, not drawn: four distinct positions and their copies, the eight
+    indices permuted (seeded numpy generator).  Eight distinct indices over four distinct points: the homography solver is exact on
+    them, the 8-point F sees a rank-4 system -- degenerate (two eigenvalues under DBL_EPSILON) or an arbitrary null vector that fits
+    little else -- so SH > SF and the pair takes ReconstructHF's homography route.  -> (k1d, k2d, m12d, sets [n_iter, 8])."""
+    m12 = np.asarray(m12, np.int32)
+    k1d, k2d = np.concatenate([k1, k1]), np.concatenate([k2, k2])
+    m12d = np.concatenate([m12, np.where(m12 >= 0, m12 + len(k2), -1)]).astype(np.int32)
+    half = int((m12 >= 0).sum())
+    rng = np.random.default_rng(seed)
+    sets = np.zeros((n_iter, 8), np.int32)
+    for it in range(n_iter):
+        c = rng.choice(half, 4, replace=False)
+        sets[it] = rng.permutation(np.concatenate([c, c + half]))
+    return k1d, k2d, m12d, sets
+
+
+# ---- the worlds of the Initializer's tests ---------------------------------------------------------------------------------------
+# (name, generator, its arguments, doubled, seed, keep, n_iter).  generator: "planar" = planar_case, "two_view" =
+# oracle_lib.two_view_case, "rotation" = rotation_case.  doubled: the pair goes through doubled() with `seed` for its numpy generator
+# (ReconstructHF's homography route); otherwise mvSets are drawn as the reference draws them after srand(seed).  keep: only the first
+# `keep` matches of the generator's matches12 stay (before doubling), which sets N = |mvMatches12| around the wave of 64.
+# Every world has at most 250 positions (500 keypoints per frame once doubled) but f_rotation: it is the scene of
+# test_pure_rotation_is_low_parallax unchanged, 500 positions, not doubled, so 500 keypoints per frame as well.
+# tests/test_initializer_host.py::test_init_worlds_reach_every_branch asserts on the CPU what each of them reaches.
+INIT_WORLDS = (
+    # the homography route
+    ("h_accept_i0", "planar", dict(seed=11, n=60, noise=0.3, outliers=0.0), True, 11, None, 200),
+    ("h_accept_i1", "planar", dict(seed=3, n=30, noise=0.3, outliers=0.0), True, 3, None, 200),
+    ("h_ambiguous_i2", "planar", dict(seed=1, n=30, noise=0.3, outliers=0.0), True, 1, None, 200),
+    ("h_low_parallax", "planar", dict(seed=0, n=30, noise=0.3, outliers=0.0), True, 0, None, 200),
+    ("h_few_triangulated", "planar", dict(seed=11, n=30, noise=1.0, outliers=0.0), True, 11, None, 200),
+    ("h_few_inliers", "planar", dict(seed=11, n=30, noise=2.0, outliers=0.5), True, 11, None, 200),
+    ("h_40", "planar", dict(seed=3, n=30, noise=1.0, outliers=0.3), True, 3, None, 200),
+    ("h_56", "planar", dict(seed=6, n=30, noise=0.3, outliers=0.3), True, 6, None, 200),
+    ("h_n128", "planar", dict(seed=11, n=64, noise=0.3, outliers=0.0), True, 11, None, 200),
+    ("h_rotation", "rotation", dict(seed=0, n=30), True, 0, None, 200),
+    ("tiny", "planar", dict(seed=11, n=60, noise=0.3, outliers=0.0), True, 5, 4, 3),
+    # the fundamental route
+    ("f_accept_n63", "two_view", dict(seed=3, n=70, outliers=0.0, noise=0.3), False, 0, None, 200),
+    ("f_accept_200", "two_view", dict(seed=3, n=200, outliers=0.0, noise=0.3), False, 0, None, 200),
+    ("f_n64", "two_view", dict(seed=3, n=200, outliers=0.0, noise=0.3), False, 0, 64, 200),
+    ("f_n65", "two_view", dict(seed=3, n=200, outliers=0.0, noise=0.3), False, 0, 65, 200),
+    ("f_ambiguous", "two_view", dict(seed=1, n=130, outliers=0.0, noise=0.3), False, 0, None, 200),
+    ("f_low_parallax", "two_view", dict(seed=7, n=60, outliers=0.0, noise=0.3), False, 0, None, 200),
+    ("f_few_triangulated", "two_view", dict(seed=3, n=60, outliers=0.2, noise=0.5), False, 0, None, 200),
+    ("f_few_inliers", "two_view", dict(seed=3, n=250, outliers=0.2, noise=0.5), False, 0, None, 200),
+    ("f_no_good_point", "planar", dict(seed=3, n=130, noise=0.3, outliers=0.0), False, 0, None, 200),
+    ("f_104", "planar", dict(seed=0, n=60, noise=0.3, outliers=0.0), False, 0, None, 200),
+    ("f_120", "planar", dict(seed=0, n=60, noise=0.3, outliers=0.3), False, 0, None, 200),
+    ("f_rotation", "rotation", dict(seed=3, n=500), False, 0, None, 200),
+)
+_WORLDS = {}
+
+
+def init_world(name):
+    """The world `name` of INIT_WORLDS -> dict(K f32 [3, 3], k1, k2, m12, sets, doubled, truth); truth = (R, t, plane normal, plane
+    distance) with None where the generator has none.  Built once and shared: do not write into it."""
+    if name in _WORLDS:
+        return _WORLDS[name]
+    _, gen, args, dbl, seed, keep, n_iter = next(w for w in INIT_WORLDS if w[0] == name)
+    if gen == "planar":
+        K, Rm, t, nrm, d, k1, k2, m12, _ = planar_case(**args)
+    elif gen == "two_view":
+        K, Rm, t, k1, k2, m12, _ = oracle_lib.two_view_case(**args)
+        nrm = d = None
+    else:
+        K, Rm, k1, k2, m12 = rotation_case(**args)
+        t = nrm = d = None
+    m12 = m12.astype(np.int32).copy()
+    if keep is not None:
+        m12[np.nonzero(m12 >= 0)[0][keep:]] = -1
+    if dbl:
+        k1, k2, m12, sets = doubled(k1, k2, m12, seed, n_iter)
+    else:
+        sets = sample_sets_cpp(seed, int((m12 >= 0).sum()), n_iter)
+    w = dict(name=name, K=np.ascontiguousarray(K, np.float32), k1=k1, k2=k2, m12=m12, sets=sets, doubled=dbl, truth=(Rm, t, nrm, d))
+    _WORLDS[name] = w
+    return w
+
+
+_REFS = {}
+
+
+def init_reference(name):
+    """The restatement's answer for the world `name` -> (result dict, p3d, tri), computed once and shared: do not write into it."""
+    if name not in _REFS:
+        w = init_world(name)
+        _REFS[name] = initialize(w["k1"], w["k2"], w["m12"], w["sets"], w["K"])
+    return _REFS[name]

@@ -245,3 +245,218 @@ def build_shim_initializer(orbx, out_dir):
 
 def test_shim_initializer_compiles(orbx, tmp_path):
     build_shim_initializer(orbx, tmp_path)
+
+
+# ---- the worlds of tests/test_gpu_initialize.py: what they reach, the rules against numpy, the homography route against truth ----
+AMBIGUOUS, LOW_PARALLAX, FEW_TRIANGULATED, FEW_INLIERS = 8, 16, 32, 64
+
+
+def _indx(H21, K):
+    """decomposeHomography's row choice restated in numpy: Hn = K^-1 H21 K / sigma_2, S = Hn^T Hn - I, the largest |S_ii| in the
+    kernel's tie order (0 unless |S00| < |S11|; then 1 unless |S11| < |S22|; from 0 to 2 only if |S00| < |S22|)."""
+    K = np.asarray(K, np.float32).astype(np.float64)
+    Hn = np.linalg.inv(K) @ np.asarray(H21, np.float32).astype(np.float64) @ K
+    Hn /= np.linalg.svd(Hn, compute_uv=False)[1]
+    a = np.abs(np.diag(Hn.T @ Hn - np.eye(3)))
+    if a[0] < a[1]:
+        return 2 if a[1] < a[2] else 1
+    return 2 if a[0] < a[2] else 0
+
+
+def test_init_worlds_reach_every_branch():
+    """The proof that tests/test_gpu_initialize.py's worlds run what they claim to run: the restatement over INIT_WORLDS, and from its
+    result fields every item of the coverage.  If a numpy release moves a random stream, this fails here, by name."""
+    names = [w[0] for w in R.INIT_WORLDS]
+    assert len(set(names)) == len(names) and 20 <= len(names) <= 24
+    res, world = {n: R.init_reference(n)[0] for n in names}, {n: R.init_world(n) for n in names}
+    for w in R.INIT_WORLDS:
+        W, r = world[w[0]], res[w[0]]
+        assert len(W["k1"]) <= 500 and len(W["k2"]) <= 500 and len(W["sets"]) == (3 if w[0] == "tiny" else 200), w[0]
+        # at most 250 positions; f_rotation alone has 500, being test_pure_rotation_is_low_parallax's scene as it stands
+        assert len(W["k1"]) <= (500 if W["doubled"] or w[0] == "f_rotation" else 250), w[0]
+        assert not r["status"] & 0x87, w[0]                          # every world passes the model stage
+        assert r["model"] == (0 if W["doubled"] else 1), w[0]        # doubled: the homography route; drawn sets: the fundamental one
+        assert (r["rh"] > 0.5) == W["doubled"], w[0]
+    H = {n: r for n, r in res.items() if r["model"] == 0}
+    F = {n: r for n, r in res.items() if r["model"] == 1}
+    indx = {n: _indx(r["H21"], world[n]["K"]) for n, r in H.items()}
+
+    # the homography route
+    accepted = {n: indx[n] for n, r in H.items() if r["status"] == 0}
+    assert len(accepted) >= 2 and len(set(accepted.values())) >= 2, accepted
+    assert {indx[n] for n, r in H.items() if r["n_solutions"] == 4} == {0, 1, 2}, indx
+    for bit in (AMBIGUOUS, LOW_PARALLAX, FEW_TRIANGULATED, FEW_INLIERS):
+        assert any(r["status"] & bit and r["n_solutions"] == 4 for r in H.values()), bit
+    r = res["h_rotation"]
+    assert r["model"] == 0 and r["n_solutions"] == 1 and r["best_solution"] == -1 and r["parallax"] == -1 and r["status"] == 112
+    assert res["h_accept_i0"]["status"] == 0 and indx["h_accept_i0"] == 0 and res["h_accept_i1"]["status"] == 0 and indx["h_accept_i1"] == 1
+    assert indx["h_ambiguous_i2"] == 2 and res["h_ambiguous_i2"]["status"] == AMBIGUOUS
+    assert res["h_low_parallax"]["status"] & LOW_PARALLAX and res["h_few_triangulated"]["status"] == FEW_TRIANGULATED
+    assert res["h_few_inliers"]["status"] & FEW_INLIERS
+    assert len({r["best_solution"] for r in H.values() if r["n_solutions"] == 4}) >= 3   # the winner is not always the same candidate
+
+    # the fundamental route
+    assert all(r["n_solutions"] == 4 for r in F.values())
+    assert sum(r["status"] == 0 for r in F.values()) >= 2
+    for bit in (AMBIGUOUS, LOW_PARALLAX, FEW_TRIANGULATED, FEW_INLIERS):
+        assert any(r["status"] & bit for r in F.values()), bit
+    assert res["f_ambiguous"]["status"] == AMBIGUOUS and res["f_low_parallax"]["status"] & LOW_PARALLAX
+    assert res["f_few_triangulated"]["status"] == FEW_TRIANGULATED and res["f_few_inliers"]["status"] & FEW_INLIERS
+    assert res["f_120"]["status"] == 120 and res["f_104"]["status"] == 104                # the combinations
+    r = res["f_no_good_point"]
+    assert r["best_solution"] == -1 and r["parallax"] == -1 and r["best_good"] == 0 and r["status"] == 112
+    r = res["f_rotation"]                                             # test_pure_rotation_is_low_parallax's scene: through F
+    assert r["model"] == 1 and r["rh"] == 0.5 and r["status"] & LOW_PARALLAX and r["best_solution"] >= 0
+
+    # the wave of 64: matched counts and the chosen model's inlier counts
+    N = {n: r["n_matches"] for n, r in res.items()}
+    for rem in (0, 1, 63):
+        assert any(v % 64 == rem for v in N.values()), (rem, N)
+    inl = {n: r["n_inliers_h"] if r["model"] == 0 else r["n_inliers_f"] for n, r in res.items()}
+    assert any(v >= 63 and min(v % 64, 64 - v % 64) <= 1 for v in inl.values()), inl
+    assert N["tiny"] == 8 and len(world["tiny"]["sets"]) == 3 and N["f_accept_n63"] == 63 and N["f_n64"] == 64 and N["f_n65"] == 65
+
+    # the threshold case: on a doubled world the F loop holds zeroed (two eigenvalues under DBL_EPSILON) and non-zero hypotheses
+    mixed = 0
+    for n in H:
+        W = world[n]
+        _, _, models, scores = R.find_models(W["k1"], W["k2"], W["m12"], W["sets"])
+        zeroed = ~models[2].reshape(len(W["sets"]), 9).any(1)
+        assert models[0].reshape(len(W["sets"]), 9).any(1).all(), n    # the homography solver is exact on every doubled set
+        assert not scores[1][zeroed].any()
+        mixed += bool(zeroed.any() and not zeroed.all())
+    assert mixed >= 1
+
+
+def _rules(n_good, parallax, n_inliers, min_parallax, min_triangulated):
+    """ReconstructHF's choice (the first strict maximum of nGood keeps the index, the runner-up is tracked beside it) and its four
+    rules, as include/orbx.h states them (Initializer.cpp:490-545); doubles for 0.7 * bestGood and 0.9 * nInliers, f32 parallax."""
+    bg, sg, bi, bp = 0, 0, -1, np.float32(-1)
+    for i, g in enumerate(n_good):
+        if g > bg:
+            sg, bg, bi, bp = bg, g, i, np.float32(parallax[i])
+        elif g > sg:
+            sg = g
+    st = (AMBIGUOUS if sg > 0.7 * bg else 0) | (LOW_PARALLAX if bp < np.float32(min_parallax) else 0)
+    st |= (FEW_TRIANGULATED if bg < min_triangulated else 0) | (FEW_INLIERS if bg < 0.9 * n_inliers else 0)
+    return st, bi, bg, sg, bp
+
+
+def test_reconstruct_rules_against_numpy():
+    """reconstructRules is one source compiled into the device and into the restatement, so the restatement cannot catch an error
+    in it: here it meets a statement that shares no source with it."""
+    rng = np.random.default_rng(5)
+    cases = []
+    for _ in range(4000):
+        n = int(rng.choice([0, 1, 4]))
+        top = int(rng.choice([3, 60, 300]))
+        ng = rng.integers(0, top + 1, n)
+        if n == 4 and rng.random() < 0.3:
+            ng[rng.integers(0, 4)] = ng[rng.integers(0, 4)]           # equal counts
+        par = rng.choice([0.0, 0.5, 0.99999994, 1.0, 1.0000001, 3.0, 120.0], n).astype(np.float32)
+        cases.append((ng, par, int(rng.integers(0, top + 30)), 1.0, 50))
+    f = np.float32
+    cases += [
+        ([10, 7, 0, 0], f([2, 2, 2, 2]), 10, 1.0, 5),                 # sg == 0.7 bg (in doubles: 0.7 * 10 rounds to 7)
+        ([100, 70, 3, 0], f([2, 2, 2, 2]), 100, 1.0, 50), ([100, 71, 3, 0], f([2, 2, 2, 2]), 100, 1.0, 50),
+        ([20, 14, 14, 1], f([2, 2, 2, 2]), 20, 1.0, 5),
+        ([9, 1, 0, 0], f([2, 2, 2, 2]), 10, 1.0, 5), ([90, 0, 0, 0], f([2, 2, 2, 2]), 100, 1.0, 50),   # bg == 0.9 nInliers
+        ([89, 0, 0, 0], f([2, 2, 2, 2]), 100, 1.0, 50), ([63, 0, 0, 0], f([2, 2, 2, 2]), 70, 1.0, 50),
+        ([60, 1, 0, 0], f([1, 0, 0, 0]), 60, 1.0, 50), ([60, 1, 0, 0], f([0.99999994, 5, 5, 5]), 60, 1.0, 50),   # parallax == min
+        ([60, 1, 0, 0], f([2.5, 0, 0, 0]), 60, 2.5, 50),
+        ([50, 0, 0, 0], f([2, 0, 0, 0]), 50, 1.0, 50), ([49, 0, 0, 0], f([2, 0, 0, 0]), 49, 1.0, 50),  # bg == minTriangulated
+        ([30, 30, 30, 30], f([1, 2, 3, 4]), 30, 1.0, 5), ([5, 30, 30, 7], f([1, 2, 3, 4]), 30, 1.0, 5),  # equal: the first keeps
+        ([0, 0, 0, 0], f([0, 0, 0, 0]), 0, 1.0, 50), ([0, 0, 0, 0], f([9, 9, 9, 9]), 40, 1.0, 50), ([0], f([0]), 0, 1.0, 50),
+        ([], f([]), 0, 1.0, 50), ([], f([]), 100, 1.0, 0), ([0, 0, 0, 0], f([0, 0, 0, 0]), 0, -1.0, 0),
+    ]
+    seen = set()
+    for ng, par, n_inl, mp, mt in cases:
+        got = R.reconstruct_rules(ng, par, n_inl, mp, mt)
+        want = _rules(list(ng), par, n_inl, mp, mt)
+        assert got[:4] == tuple(int(v) for v in want[:4]) and np.float32(got[4]).tobytes() == np.float32(want[4]).tobytes(), \
+            (ng, par, n_inl, mp, mt, got, want)
+        seen.add(got[0])
+    assert seen >= {0, 8, 16, 32, 64, 112, 120}
+    assert R.reconstruct_rules([10, 7, 0, 0], f([2, 2, 2, 2]), 10, 1.0, 5)[0] == 0          # the ties do not raise their bits
+    assert R.reconstruct_rules([90, 0, 0, 0], f([2, 2, 2, 2]), 100, 1.0, 50)[0] == 0
+    assert R.reconstruct_rules([60, 1, 0, 0], f([1, 0, 0, 0]), 60, 1.0, 50)[0] == 0
+    assert R.reconstruct_rules([30, 30, 30, 30], f([1, 2, 3, 4]), 30, 1.0, 5)[:4] == (AMBIGUOUS, 0, 30, 30)
+    assert R.reconstruct_rules([0, 0, 0, 0], f([9, 9, 9, 9]), 40, 1.0, 50) == (112, -1, 0, 0, np.float32(-1))
+
+
+def test_restated_initialize_on_planes():
+    """The restatement's homography route against the scene's truth, on the accepted (status 0) doubled planes: (R21, t21 / |t21|)
+    is the true motion, sign of t included, |t21| is 1 / d (the decomposition's t is the translation over the plane's distance) and
+    the triangulated points lie on the true plane n.X = -1 in those units.  Observed here: rotation 0.100 / 0.148 / 0.092 degrees,
+    translation direction 0.279 / 1.373 / 0.341 degrees, |n.X + 1| at most 0.0223 / 0.0138 / 0.0145 (h_accept_i0, h_accept_i1,
+    h_n128; 0.3 px of noise on a plane 8 units away); the bounds are twice the largest of each."""
+    for name in ("h_accept_i0", "h_accept_i1", "h_n128"):
+        w, (r, p3d, tri) = R.init_world(name), R.init_reference(name)
+        Rm, t, nrm, d = w["truth"]
+        assert r["status"] == 0 and r["model"] == 0 and tri.sum() == r["best_good"] >= 50
+        Re, te = r["R21"].astype(np.float64), r["t21"].astype(np.float64)
+        rot = np.degrees(np.arccos(np.clip((np.trace(Re.T @ Rm) - 1) / 2, -1, 1)))
+        trans = np.degrees(np.arccos(np.clip(te @ t / (np.linalg.norm(te) * np.linalg.norm(t)), -1, 1)))
+        plane = np.abs(p3d[tri].astype(np.float64) @ nrm + 1).max()
+        print("%s: rotation %.3f deg, translation %.3f deg, plane %.4f, |t| d %.4f" % (name, rot, trans, plane, np.linalg.norm(te) * d))
+        assert rot < 0.296 and trans < 2.75 and plane < 0.045
+        assert abs(np.linalg.norm(te) * d - 1) < 0.0246   # observed 0.0060 / 0.0074 / 0.0123
+        assert not p3d[~tri].any()
+
+
+def _decompose_h_numpy(H21, K):
+    """The analytical homography decomposition of Malis & Vargas (INRIA RR-6303) in numpy f64, written from the paper's formulas in
+    OpenCV's order of solutions -- (Ra, ta, na), (Ra, -ta, -na), (Rb, tb, nb), (Rb, -tb, -nb) -- and sharing no source with
+    orbx_init_decomp.inc.  -> (R [4, 3, 3], t [4, 3], n [4, 3])."""
+    K = np.asarray(K, np.float32).astype(np.float64)
+    Hn = np.linalg.inv(K) @ np.asarray(H21, np.float32).astype(np.float64) @ K
+    Hn /= np.linalg.svd(Hn, compute_uv=False)[1]
+    S = Hn.T @ Hn - np.eye(3)
+
+    def minor(r, c):  # the opposite of the minor of S without row r and column c
+        m = np.delete(np.delete(S, r, 0), c, 1)
+        return -(m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0])
+    rt = lambda v: np.sqrt(max(v, 0.0))  # noqa: E731
+    sgn = lambda v: 1.0 if v >= 0 else -1.0  # noqa: E731
+    M00, M11, M22 = minor(0, 0), minor(1, 1), minor(2, 2)
+    e12, e02, e01 = sgn(minor(1, 2)), sgn(minor(0, 2)), sgn(minor(0, 1))
+    i = _indx(H21, K)
+    if i == 0:
+        npa = np.array([S[0, 0], S[0, 1] + rt(M22), S[0, 2] + e12 * rt(M11)])
+        npb = np.array([S[0, 0], S[0, 1] - rt(M22), S[0, 2] - e12 * rt(M11)])
+    elif i == 1:
+        npa = np.array([S[0, 1] + rt(M22), S[1, 1], S[1, 2] - e02 * rt(M00)])
+        npb = np.array([S[0, 1] - rt(M22), S[1, 1], S[1, 2] + e02 * rt(M00)])
+    else:
+        npa = np.array([S[0, 2] + e01 * rt(M11), S[1, 2] + rt(M00), S[2, 2]])
+        npb = np.array([S[0, 2] - e01 * rt(M11), S[1, 2] - rt(M00), S[2, 2]])
+    na, nb = npa / np.linalg.norm(npa), npb / np.linalg.norm(npb)
+    tr = np.trace(S)
+    v = 2 * rt(1 + tr - M00 - M11 - M22)
+    rho, nt, es = rt(2 + tr + v), rt(2 + tr - v), sgn(S[i, i])
+    out = []
+    for n, m in ((na, nb), (nb, na)):
+        ts = nt / 2 * (es * rho * m - nt * n)
+        Rm = Hn @ (np.eye(3) - 2 / v * np.outer(ts, n))
+        out += [(Rm, Rm @ ts, n), (Rm, -(Rm @ ts), -n)]
+    return tuple(np.stack(c) for c in zip(*out))
+
+
+def test_homography_candidates_against_numpy():
+    """The four candidates of decomposeHomography, in their order, on the kept homography of every world that takes the route (all
+    three rows of the decomposition): against the numpy statement above, to one ulp of the f32 outputs.  The order matters: it decides
+    best_solution and which of two equal candidates wins."""
+    seen = set()
+    for w in R.INIT_WORLDS:
+        r, W = R.init_reference(w[0])[0], R.init_world(w[0])
+        if r["model"] != 0 or r["n_solutions"] != 4:
+            continue
+        Rs, ts, ns = R.decompose_homography(r["H21"], W["K"])
+        Rn, tn, nn = _decompose_h_numpy(r["H21"], W["K"])
+        seen.add(_indx(r["H21"], W["K"]))
+        assert len(Rs) == 4
+        for got, want in ((Rs, Rn), (ts, tn), (ns, nn)):   # one f32 ulp: the outputs' own rounding is half of one, the f64 paths differ by far less
+            assert (np.abs(got - want) <= 2.0 ** -23 * np.maximum(1.0, np.abs(want))).all(), w[0]
+        # and the candidates differ by far more than that, so a swap cannot hide in the tolerance
+        assert np.abs(tn[0] - tn[1]).max() > 1e-2 and np.abs(Rn[0] - Rn[2]).max() > 1e-3, w[0]
+    assert seen == {0, 1, 2}
