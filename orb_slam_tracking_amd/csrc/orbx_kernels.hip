@@ -5,7 +5,7 @@
 //                                                    (ORBextractor::ComputePyramid, cpp:1660-1713 -> cv::resize)
 //   k_fast            per-cell FAST-9-16 + in-cell NMS + threshold fallback, survivors into per-cell segments
 //                                                    (ComputeKeyPointsOctTree cell loops, cpp:1078-1141 -> cv::FAST)
-//   k_describe_patch  IC-angle + 7x7 Gaussian (patch-local, v_dot4/v_dot2 fixed point) + steered BRIEF, one wave per
+//   k_describe_patch  IC-angle + 7x7 Gaussian (patch-local, exact int8 matrix products) + steered BRIEF, one wave per
 //                     keypoint                       (IC_Angle cpp:103-159, GaussianBlur cpp:1598-1606,
 //                                                     computeOrbDescriptor cpp:169-228, assembly cpp:1557-1652)
 //   k_match_jacobi / k_match_wide_lists / k_match_wide_resolve   SearchForInitialization: parallel fixpoint sweeps (one
@@ -18,8 +18,9 @@
 //   (the quadtree selection lives in orbx_octree_kernel.hip)
 //
 // All arithmetic is integer or uncontracted IEEE f32/f64 (compile with -ffp-contract=off) so the results are
-// bit-identical to the CPU restatement in oracle/.  The matrix cores serve k_match_bf_mfma only (exact int8 / int32 arithmetic): the
-// all-pairs distances of a brute-force match are the path's one dense contraction; everything else is byte and integer work.
+// bit-identical to the CPU restatement in oracle/.  The matrix cores serve the path's two dense linear maps, both in exact int8 /
+// int32 arithmetic: the all-pairs distances of a brute-force match (k_match_bf_mfma) and the 7x7 Gaussian of a keypoint's patch
+// (k_describe_patch); everything else is byte and integer work.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1137,16 +1138,16 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 // -------------------------------------------------------------------------------------------------
 // K4+K5+K6 fused, patch-local: one wave per keypoint.  The 43x43 raw window (REFLECT_101 at the level's edges) is
 // staged in LDS with dword loads; the 7x7 Gaussian is evaluated only on the 37x37 neighbourhood the 512 rotated
-// sample points can reach, with the same exact fixed-point arithmetic as the whole-level blur (v_dot4_u32_u8 for the
-// horizontal pass, v_dot2_u32_u16 on row pairs for the vertical pass), so no blurred pyramid is written or re-read.
+// sample points can reach, with the same exact fixed-point arithmetic as the whole-level blur, as two banded matrix
+// products on the matrix cores (v_mfma_i32_16x16x64_i8; BlurFrags below), so no blurred pyramid is written or re-read.
 // -------------------------------------------------------------------------------------------------
 #define PW_ROWS 43
 #define PW_WORDS 13    // 52 bytes per staged row: window columns kx-21 .. kx+21 start at byte (kx-21)&3
-#define PW_PAIRS 22    // row pairs of horizontal sums (rows 0..43, the last one is a dummy)
-#define PW_COLS 40     // 37 blurred columns padded to 10 groups of 4
-#define BL_ROWS_PAD 38
-#define PW_RAW_WORDS 560  // PW_ROWS * PW_WORDS = 559, padded so that the row-pair sums behind it are 16-byte aligned
-#define PW_WAVE_WORDS (PW_RAW_WORDS + PW_PAIRS * PW_COLS + 4)  // the blurred bytes reuse the raw window's space; + 2 moment sums
+#define PW_ROWS_PAD 48 // three 16-row tiles of the horizontal product; rows 43..47 are never written and only ever meet zero taps
+#define BL_STRIDE 48   // the blurred bytes are stored column-major: byte (column c, row r) at c * 48 + r, three 16-row tiles
+#define BL_COLS 48     // 37 blurred columns padded to three 16-column tiles
+#define PW_RAW_WORDS (PW_ROWS_PAD * PW_WORDS)
+#define PW_WAVE_WORDS (PW_RAW_WORDS + 4)  // the blurred bytes reuse the raw window's space; + 2 moment sums
 
 // IC_Angle disc as dot4 weights: row |v| of the 31x31 disc covers u = -umax[|v|] .. umax[|v|]; the row's 32 bytes
 // u = -15 .. 16 are 8 dwords j, and for each the weights are w1 = (1 per valid byte) and wu = (u + 15 per valid byte), so
@@ -1176,60 +1177,79 @@ __device__ const IcTables d_ic = makeIcTables();
 
 #define DESC_WAVES 3   // keypoints (= waves) per workgroup: consecutive keypoints of a frame's list are spatially close, so
                        // putting them on one CU lets their overlapping windows hit in that CU's L1 (1: 0.44 ms, 2: 0.38,
-                       // 3: 0.365, 4: 0.39, 8: 0.44, 16: 0.63 per 256 frames; 3 slices of 5.8 KB keep 27 waves per CU)
+                       // 3: 0.365, 4: 0.39, 8: 0.44, 16: 0.63 per 256 frames, measured with the vector-ALU blur of rounds 2-6)
 // GV = Gaussian Q8 tap set (orbx_set_opencv_variant): 0 = [18,34,48,56,48,34,18] (error diffusion, sum 256: OpenCV >= 4.1.1 /
 // 3.4.7), 1 = [18,34,49,55,49,34,18] (every tap rounded, sum 257: the bit-exact path of 3.4.1 .. 4.1.0 and the integer filter
 // before it; a sum of 2^24 or more saturates to 255)
 
 // The 512 rotated sample points lie in the disc r^2 + c^2 <= 365 around the keypoint ((13, 13) is the farthest pattern point:
-// 18.38, and rounding moves a point by at most 0.71), not in the whole 37 x 37 square.  A (row pair, 4-column) item of the
-// horizontal pass is needed only if one of the four vertical items it feeds holds a point of the disc: 190 of 220, i.e. three
-// steps of 64 lanes instead of four of 60.  Entry = row pair << 4 | column group, 0xffff = idle.
-struct DescHItems {
-  uint16_t v[192];
+// 18.38, and rounding moves a point by at most 0.71), not in the whole 37 x 37 square.
+// The 7x7 Gaussian as two integer matrix products on the matrix cores (v_mfma_i32_16x16x64_i8), exact:
+//   H   = (W - 128) G_s + 128      W = the staged window, 48 rows x 48 bytes; G_s[k][c] = T[k - s - c]: the wave's byte shift s
+//                                  lives in the tap matrix, column c of H is blurred column c (x = kx - 18 + c)
+//   Out = V (W G_s) + 32768        V[r][k] = T[k - r]; the blurred byte is bits 16..23 of Out (saturated for the taps that sum to 257)
+// H = 256 hi + u is split into two int8 operands, hi = (signed) byte 1 and lo = u - 128 (so (W - 128) G_s = 256 hi + lo; the 128 in
+// the accumulator is what keeps hi inside int8 for both tap sets), and with S = the taps' sum
+//   Out = 256 (V hi) + (V lo) + 128 S S + 32768.
+// The instruction sums over all (lane group q, byte j) slots of its two operands, so WHICH k a slot holds is ours to choose as
+// long as both operands agree.  Both products use  k(q, j) = 16 (j >> 2) + 4 q + (j & 3):  that is how a 16x16 accumulator tile
+// lies in the registers (lane = column + 16 q, register b = row 4 q + b), so the three row tiles of one column of H, packed to
+// bytes, ARE the vertical product's B operand (dword t = rows 16 t + 4 q .. + 3) -- H never goes through LDS.  With this k order
+// a banded Toeplitz operand needs two dwords per lane, not a table per tile: dword d of the fragment of tile t holds
+// T[16 (d - t) + 4 q - (lane & 15) - s + b], b = 0 .. 3, which is zero unless d == t (-> W0) or d == t + 1 (-> W1, 16 taps further).
+// V is the same matrix as G_0.  Entry [s][lane] = (W0, W1); a wave reads V's pair and G_s's pair: two 8-byte loads.
+struct BlurFrags {
+  uint32_t w[4][64][2];
 };
-constexpr DescHItems makeDescHItems() {
-  DescHItems t{};
-  bool vneed[19 + 3][10] = {};
-  for (int q = 0; q < 19; q++)
-    for (int g = 0; g < 10; g++)
-      for (int r = 2 * q; r < 2 * q + 2; r++)
-        for (int c = 4 * g; c < 4 * g + 4; c++)
-          if (r <= 36 && c <= 36 && (r - 18) * (r - 18) + (c - 18) * (c - 18) <= 365) vneed[q][g] = true;
-  int n = 0;
-  for (int rp = 0; rp < 22; rp++)
-    for (int g = 0; g < 10; g++) {
-      bool need = false;
-      for (int q = rp - 3; q <= rp; q++)
-        if (q >= 0 && q < 19 && vneed[q][g]) need = true;
-      if (need && n < 192) t.v[n++] = (uint16_t)(rp << 4 | g);
-    }
-  for (; n < 192; n++) t.v[n] = 0xffff;
+template <int GV>
+constexpr int blurTap(int j) {
+  const int T[7] = {18, 34, GV ? 49 : 48, GV ? 55 : 56, GV ? 49 : 48, 34, 18};
+  return j >= 0 && j < 7 ? T[j] : 0;
+}
+template <int GV>
+constexpr BlurFrags makeBlurFrags() {
+  BlurFrags t{};
+  for (int s = 0; s < 4; s++)
+    for (int lane = 0; lane < 64; lane++)
+      for (int e = 0; e < 2; e++)
+        for (int b = 0; b < 4; b++)
+          t.w[s][lane][e] |= (uint32_t)blurTap<GV>(16 * e + 4 * (lane >> 4) - (lane & 15) - s + b) << (8 * b);
   return t;
 }
-__device__ const DescHItems d_descHItems = makeDescHItems();
-constexpr int descHItemCount() {
-  const DescHItems t = makeDescHItems();
-  int n = 0;
-  for (int i = 0; i < 192; i++) n += t.v[i] != 0xffff;
-  return n;
+// the operand of tile t, lane, slot (dword d, byte b), rebuilt the way the kernel builds it
+constexpr int blurFragByte(const BlurFrags& t, int s, int tile, int lane, int d, int b) {
+  return d == tile ? (int)(t.w[s][lane][0] >> (8 * b) & 0xff) : d == tile + 1 ? (int)(t.w[s][lane][1] >> (8 * b) & 0xff) : 0;
 }
-static_assert(descHItemCount() == 190, "horizontal items of the sampling disc (all of them must fit the three steps)");
-
-// horizontal Gaussian taps as v_dot4 weights: the 7 taps applied to window bytes t .. t + 6 (t = byte shift + column, 0 .. 6),
-// restricted to dword m of the 16 staged bytes
+// invariants: every entry fits int8, and the fragments ARE the banded matrix -- slot (q, 4 d + b) of column c holds T[k - s - c]
+// for every k < 64 (so columns 0 .. 36, whose 7 taps end at k = s + 42, sum to 256 / 257)
 template <int GV>
-__host__ __device__ constexpr uint32_t descHTap(int t, int m) {
-  const uint32_t T[7] = {18u, 34u, GV ? 49u : 48u, GV ? 55u : 56u, GV ? 49u : 48u, 34u, 18u};
-  uint32_t k = 0;
-  for (int i = 0; i < 4; i++) {
-    const int j = 4 * m + i - t;
-    if (j >= 0 && j < 7) k |= T[j] << (8 * i);
-  }
-  return k;
+constexpr bool blurFragsOk() {
+  const BlurFrags t = makeBlurFrags<GV>();
+  for (int s = 0; s < 4; s++)
+    for (int c = 0; c < BL_COLS; c++) {
+      int sum = 0;
+      for (int q = 0; q < 4; q++)
+        for (int d = 0; d < 4; d++)
+          for (int b = 0; b < 4; b++) {
+            const int v = blurFragByte(t, s, c >> 4, (c & 15) + 16 * q, d, b);
+            if (v > 127 || v != blurTap<GV>(16 * d + 4 * q + b - s - c)) return false;
+            sum += v;
+          }
+      if (c < 37 && sum != (GV ? 257 : 256)) return false;
+    }
+  return true;
 }
+static_assert(blurFragsOk<0>() && blurFragsOk<1>(), "tap fragments of the matrix-core blur");
+__device__ const BlurFrags d_blurFrags0 = makeBlurFrags<0>();
+__device__ const BlurFrags d_blurFrags1 = makeBlurFrags<1>();
+// the corner tile (rows 32.., columns 32..) of the blurred patch holds no point of the sampling disc and is not computed
+static_assert((32 - 18) * (32 - 18) * 2 > 365, "sampling disc against the corner tile");
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+
+// (second launch bound = 7 waves per SIMD, i.e. at most 72 registers: without it the scheduler spreads the three column tiles'
+// accumulators over 82-92 registers and the kernel drops to 5 waves per SIMD; with it 64-67 registers, no spill)
 template <int GV, bool STAGED = false>
-__global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_t* __restrict__ img0, long long img0FrameStride,
+__global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uint8_t* __restrict__ img0, long long img0FrameStride,
                                                        int img0Aligned, const uint8_t* __restrict__ pyr, const Geom g,
                                                        const SelKp* __restrict__ sel, const int* __restrict__ nsel,
                                                        orbx_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
@@ -1276,22 +1296,18 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
     k.response = (uint8_t)((kuse >> 40) & 0xff); k.pad = 0;
   }
   // Loads that do not depend on the keypoint are issued first, so that their latency runs under the window fetch: the
-  // disc-row weights of IC_Angle (lane = disc row) and this lane's four point pairs of the BRIEF pattern.
+  // disc-row weights of IC_Angle (lane = disc row) and the vertical tap fragment.
   const int icRow = min(lane, 30), icAv = icRow < 15 ? 15 - icRow : icRow - 15;
   const uint4 w1a = reinterpret_cast<const uint4*>(d_ic.w1 + icAv * 8)[0], w1b = reinterpret_cast<const uint4*>(d_ic.w1 + icAv * 8)[1];
   const uint4 wua = reinterpret_cast<const uint4*>(d_ic.wu + icAv * 8)[0], wub = reinterpret_cast<const uint4*>(d_ic.wu + icAv * 8)[1];
-  float4 pat[4];
-#pragma unroll
-  for (int wq = 0; wq < 4; wq++) pat[wq] = reinterpret_cast<const float4*>(d_patternf.v)[wq * 64 + lane];
-  uint32_t hitem[3];  // this lane's items of the horizontal pass
-#pragma unroll
-  for (int it = 0; it < 3; it++) hitem[it] = d_descHItems.v[it * 64 + lane];
-  uint32_t* raw = lds;                               // [43][13] dwords
-  uint32_t* hz2 = raw + PW_RAW_WORDS;                // [22][40] row-pair packed horizontal sums (16-byte aligned rows)
-  uint32_t* bl32 = raw;                              // [38][10] dwords = blurred bytes, row stride 40 (raw is dead by then)
-  int* msum = reinterpret_cast<int*>(hz2 + PW_PAIRS * PW_COLS);  // [2] moment sums of IC_Angle
-  static_assert(BL_ROWS_PAD * (PW_COLS / 4) <= PW_ROWS * PW_WORDS, "blurred bytes must fit in the raw window");
-  static_assert(PW_ROWS * PW_WORDS <= PW_RAW_WORDS && PW_RAW_WORDS % 4 == 0, "raw window padding");
+  // the vertical tap fragment (V = G_0: it does not depend on the keypoint)
+  const BlurFrags& bf = GV ? d_blurFrags1 : d_blurFrags0;
+  const uint2 fv = *reinterpret_cast<const uint2*>(bf.w[0][lane]);
+  uint32_t* raw = lds;                               // [48][13] dwords (rows 43..47: padding of the third row tile, never written)
+  uint32_t* bl32 = raw;                              // [48][12] dwords = blurred bytes, column-major (raw is dead by then)
+  int* msum = reinterpret_cast<int*>(raw + PW_RAW_WORDS);  // [2] moment sums of IC_Angle
+  static_assert(BL_COLS * (BL_STRIDE / 4) <= PW_RAW_WORDS, "blurred bytes must fit in the raw window");
+  static_assert((PW_ROWS_PAD - 1) * PW_WORDS + 8 + 3 < PW_RAW_WORDS, "the padded row tiles stay inside the wave's own slice");
   // the keypoint is wave-uniform: keep its fields in SGPRs so that the level geometry comes through scalar loads
   const int level = __builtin_amdgcn_readfirstlane((int)k.level);
   const int kx = __builtin_amdgcn_readfirstlane((int)k.x), ky = __builtin_amdgcn_readfirstlane((int)k.y);
@@ -1383,89 +1399,72 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
   __builtin_amdgcn_wave_barrier();
   const int m10 = msum[0], m01 = msum[1];
   const float angle = fast_atan2_deg((float)m01, (float)m10);
-  // ---- horizontal pass: blurred column c (x = kx-18+c) uses window bytes s+c .. s+c+6 of the staged row.
-  //      Item = (row pair, group of 4 columns): 4 dwords per row cover the 10 bytes the 4 columns need; the 190 items of
-  //      the sampling disc (d_descHItems) in 3 steps.
-  //      The byte shift s of the window inside its dwords is the same for the whole wave, so instead of shifting the data
-  //      (9 v_alignbyte per row) the TAPS are shifted: for each s the weights of the four dwords are compile-time
-  //      constants (descHTap), zero ones are skipped, and every s costs exactly 10 v_dot4_u32_u8 per row ----
+  // ---- 7x7 Gaussian on the matrix cores (the comment at BlurFrags has the arithmetic and the k order).
+  //      A operand of the horizontal product: row (lane & 15) + 16 t of the window, dwords q, q + 4, q + 8 (q = lane >> 4), as
+  //      signed bytes (pixel - 128); the fourth dword (k = 48 ..) is zero.  They are read before anything overwrites the window. ----
+  const uint2 fg = *reinterpret_cast<const uint2*>(bf.w[s][lane]);
+  v4i_t aw[3];
   {
-    auto hpass = [&](auto sTag) {
-      constexpr int SH = decltype(sTag)::value;
+    const uint32_t* ap = raw + (lane & 15) * PW_WORDS + (lane >> 4);
 #pragma unroll
-      for (int it = 0; it < 3; it++) {
-        const int rp = (int)(hitem[it] >> 4), gq = (int)(hitem[it] & 15u);
-        if (hitem[it] != 0xffffu) {
-          uint32_t hs[2][4];
-#pragma unroll
-          for (int h2 = 0; h2 < 2; h2++) {
-            const int row = h2 ? min(2 * rp + 1, PW_ROWS - 1) : 2 * rp;
-            const uint32_t* p = raw + row * PW_WORDS + gq;
-            const uint32_t dd[4] = {p[0], p[1], p[2], p[3]};
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-              uint32_t acc = 0;
-#pragma unroll
-              for (int m = 0; m < 4; m++)
-                if (descHTap<GV>(SH + c, m) != 0u) acc = __builtin_amdgcn_udot4(dd[m], descHTap<GV>(SH + c, m), acc, false);
-              hs[h2][c] = acc;
-            }
-          }
-          uint4 o4;
-          // (both sums are < 2^16: one v_perm_b32 packs the pair instead of a shift and an or)
-          o4.x = __builtin_amdgcn_perm(hs[1][0], hs[0][0], 0x05040100u); o4.y = __builtin_amdgcn_perm(hs[1][1], hs[0][1], 0x05040100u);
-          o4.z = __builtin_amdgcn_perm(hs[1][2], hs[0][2], 0x05040100u); o4.w = __builtin_amdgcn_perm(hs[1][3], hs[0][3], 0x05040100u);
-          *reinterpret_cast<uint4*>(&hz2[rp * PW_COLS + 4 * gq]) = o4;
-        }
-      }
-    };
-    switch (s) {  // wave-uniform
-      case 0: hpass(std::integral_constant<int, 0>{}); break;
-      case 1: hpass(std::integral_constant<int, 1>{}); break;
-      case 2: hpass(std::integral_constant<int, 2>{}); break;
-      default: hpass(std::integral_constant<int, 3>{}); break;
+    for (int t = 0; t < 3; t++) {
+      aw[t][0] = (int)(ap[16 * t * PW_WORDS] ^ 0x80808080u);
+      aw[t][1] = (int)(ap[16 * t * PW_WORDS + 4] ^ 0x80808080u);
+      aw[t][2] = (int)(ap[16 * t * PW_WORDS + 8] ^ 0x80808080u);
+      aw[t][3] = 0;
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  // ---- vertical pass + rounding with v_dot2_u32_u16 on row pairs: blurred rows 2q and 2q+1 both use pairs q..q+3,
-  //      even row taps (18,34)(48,56)(48,34)(18,0), odd row taps (0,18)(34,48)(56,48)(34,18).  Item = (q, group of 4
-  //      columns), 190 items over 3 steps; the blurred bytes overwrite the raw window (no longer needed) ----
   {
-    constexpr uint32_t T0 = 18u, T1 = 34u, T2 = GV ? 49u : 48u, T3 = GV ? 55u : 56u;
-    constexpr uint32_t E0 = T0 | (T1 << 16), E1 = T2 | (T3 << 16), E2 = T2 | (T1 << 16), E3 = T0;
-    constexpr uint32_t O0 = T0 << 16, O1 = T1 | (T2 << 16), O2 = T3 | (T2 << 16), O3 = T1 | (T0 << 16);
-    int q = lane / 10, gq = lane - q * 10;
+    constexpr int S = GV ? 257 : 256, CLO = 128 * S * S + 32768;
+    const int col = lane & 15, q4 = lane >> 4;
 #pragma unroll
-    for (int it = 0; it < 3; it++) {
-      if (q < BL_ROWS_PAD / 2) {
-        const uint4 P0 = *reinterpret_cast<const uint4*>(&hz2[(q + 0) * PW_COLS + 4 * gq]);
-        const uint4 P1 = *reinterpret_cast<const uint4*>(&hz2[(q + 1) * PW_COLS + 4 * gq]);
-        const uint4 P2 = *reinterpret_cast<const uint4*>(&hz2[(q + 2) * PW_COLS + 4 * gq]);
-        const uint4 P3 = *reinterpret_cast<const uint4*>(&hz2[(q + 3) * PW_COLS + 4 * gq]);
-#define ORBX_VE(c) dot2u16(P0.c, E0, dot2u16(P1.c, E1, dot2u16(P2.c, E2, dot2u16(P3.c, E3, 32768u))))
-#define ORBX_VO(c) dot2u16(P0.c, O0, dot2u16(P1.c, O1, dot2u16(P2.c, O2, dot2u16(P3.c, O3, 32768u))))
-        uint32_t e0 = ORBX_VE(x), e1 = ORBX_VE(y), e2 = ORBX_VE(z), e3 = ORBX_VE(w);
-        uint32_t o0 = ORBX_VO(x), o1 = ORBX_VO(y), o2 = ORBX_VO(z), o3 = ORBX_VO(w);
-        if (GV) {  // taps that sum to 257: saturate_cast<uchar>
-          e0 = min(e0, 0xffffffu); e1 = min(e1, 0xffffffu); e2 = min(e2, 0xffffffu); e3 = min(e3, 0xffffffu);
-          o0 = min(o0, 0xffffffu); o1 = min(o1, 0xffffffu); o2 = min(o2, 0xffffffu); o3 = min(o3, 0xffffffu);
+    for (int tn = 0; tn < 3; tn++) {
+      // H, columns 16 tn .. + 15: three row tiles; this lane ends up with rows 16 t + 4 q4 + b of column 16 tn + col
+      v4i_t bg = {0, 0, 0, 0};
+      bg[tn] = (int)fg.x; bg[tn + 1] = (int)fg.y;
+      v4i_t hh[3];
+#pragma unroll
+      for (int t = 0; t < 3; t++) hh[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[t], bg, v4i_t{128, 128, 128, 128}, 0, 0, 0);
+      // hi = byte 1, lo = byte 0 ^ 0x80 of the four rows of a tile: one operand dword each (4 v_perm_b32 + 1 xor per tile)
+      v4i_t bhi = {0, 0, 0, 0}, blo = {0, 0, 0, 0};
+#pragma unroll
+      for (int t = 0; t < 3; t++) {
+        const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)hh[t][1], (uint32_t)hh[t][0], 0x04000501u);
+        const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)hh[t][3], (uint32_t)hh[t][2], 0x04000501u);
+        bhi[t] = (int)__builtin_amdgcn_perm(x23, x01, 0x05040100u);
+        blo[t] = (int)(__builtin_amdgcn_perm(x23, x01, 0x07060302u) ^ 0x80808080u);
+      }
+      // Out, rows 16 to .. + 15 of these columns; the four rows a lane holds are one dword of the column-major blurred patch
+#pragma unroll
+      for (int to = 0; to < 3; to++) {
+        if (tn == 2 && to == 2) continue;
+        v4i_t av = {0, 0, 0, 0};
+        av[to] = (int)fv.x;
+        if (to < 2) av[to + 1] = (int)fv.y;   // (to == 2: rows 48 .. do not exist, bhi[3] == blo[3] == 0)
+        const v4i_t oh = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bhi, v4i_t{0, 0, 0, 0}, 0, 0, 0);
+        const v4i_t ol = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, blo, v4i_t{CLO, CLO, CLO, CLO}, 0, 0, 0);
+        uint32_t o[4];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          o[b] = (uint32_t)((oh[b] << 8) + ol[b]);
+          if (GV) o[b] = min(o[b], 0xffffffu);  // taps that sum to 257: saturate_cast<uchar>
         }
-#undef ORBX_VE
-#undef ORBX_VO
         // each sum is < 2^24: its blurred byte is bits 16..23; v_perm_b32 gathers byte 2 of four sums into one dword
-        bl32[(2 * q) * (PW_COLS / 4) + gq] =
-            __builtin_amdgcn_perm(e1, e0, 0x0c0c0602u) | __builtin_amdgcn_perm(e3, e2, 0x06020c0cu);
-        bl32[(2 * q + 1) * (PW_COLS / 4) + gq] =
-            __builtin_amdgcn_perm(o1, o0, 0x0c0c0602u) | __builtin_amdgcn_perm(o3, o2, 0x06020c0cu);
+        bl32[(16 * tn + col) * (BL_STRIDE / 4) + 4 * to + q4] =
+            __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0602u) | __builtin_amdgcn_perm(o[3], o[2], 0x06020c0cu);
       }
-      q += 6; gq += 4;  // item + 64
-      if (gq >= 10) { gq -= 10; q++; }
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  // ---- steered BRIEF (cpp:169-228).  cos/sin of the f32 argument are evaluated in f64 and rounded to f32 ----
+  // ---- steered BRIEF (cpp:169-228).  cos/sin of the f32 argument are evaluated in f64 and rounded to f32.  This lane's four point
+  //      pairs of the pattern are loaded here, not with the other tables: 16 registers that the blur's accumulators need, and
+  //      the sin / cos evaluation covers the load ----
+  float4 pat[4];
+#pragma unroll
+  for (int wq = 0; wq < 4; wq++) pat[wq] = reinterpret_cast<const float4*>(d_patternf.v)[wq * 64 + lane];
   const uint8_t* bl = reinterpret_cast<const uint8_t*>(bl32);
   const float factorPI = (float)(3.14159265358979323846 / 180.f);
   float cs, sn;
@@ -1481,15 +1480,15 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe_patch(const uint8_
   for (int wq = 0; wq < 4; wq++) {
     const float4 pt = pat[wq];
     const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
-    // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + r) * 40 + 18 + c in one go: v + 1.5 * 2^23
-    // rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits; the low 24 bits
-    // (0x400000 + r) go through v_mad_u32_u24, the constants are taken off at the end
+    // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + c) * 48 + 18 + r (column-major) in one go:
+    // v + 1.5 * 2^23 rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits; the low
+    // 24 bits (0x400000 + c) go through v_mad_u32_u24, the constants are taken off at the end
     constexpr float MAGIC = 12582912.f;
-    constexpr uint32_t OFF = 40u * 0x400000u + 0x4B400000u - (18u * PW_COLS + 18u);
+    constexpr uint32_t OFF = (uint32_t)BL_STRIDE * 0x400000u + 0x4B400000u - (18u * BL_STRIDE + 18u);
     const uint32_t ir0 = __float_as_uint((x0 * sn + y0 * cs) + MAGIC), ic0 = __float_as_uint((x0 * cs - y0 * sn) + MAGIC);
     const uint32_t ir1 = __float_as_uint((x1 * sn + y1 * cs) + MAGIC), ic1 = __float_as_uint((x1 * cs - y1 * sn) + MAGIC);
-    const int t0 = bl[(ir0 & 0xffffffu) * (uint32_t)PW_COLS + ic0 - OFF];
-    const int t1 = bl[(ir1 & 0xffffffu) * (uint32_t)PW_COLS + ic1 - OFF];
+    const int t0 = bl[(ic0 & 0xffffffu) * (uint32_t)BL_STRIDE + ir0 - OFF];
+    const int t1 = bl[(ic1 & 0xffffffu) * (uint32_t)BL_STRIDE + ir1 - OFF];
     words[wq] = __ballot(t0 < t1);
   }
   const long long o = (long long)f * capacity + i;
@@ -1539,7 +1538,6 @@ struct MatchParams {
 // v_mfma_i32_32x32x32_i8 in which the dot product of two 256-bit descriptors is 256 - 2 x their Hamming distance.
 // nibble * 0x00204081 has bit j of the nibble at bit 8 j (its other copies are masked off); the 0 / 1 bytes then select byte 0
 // (0x01) or byte 1 (0xff) of a constant through v_perm_b32: four instructions per four bytes.
-typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ v4i_t pm1Bytes16(const uint32_t w) {
   v4i_t r;
