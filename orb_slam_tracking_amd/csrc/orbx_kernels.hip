@@ -475,6 +475,46 @@ __device__ __forceinline__ bool arc9(uint32_t m) {  // 16-bit circular mask has 
   return (r & 0xFFFFu) != 0;
 }
 
+// Arc strength of a pixel v with ring pixels p[0..15] (zero-extended bytes), both signs in ONE network of packed f16 (round 8).
+//   strength = max(smn, -smx), smn = max over the 16 arcs of 9 of min(d_k), smx = min over the arcs of max(d_k), d_k = v - p_k,
+// and -smx is the same max-of-arc-minima network applied to -d.  So a register carries d in its low half and -d in its high
+// half, each biased by B = 0x6500:  e_k = (B + v - p_k, B - v + p_k).  Both halves lie in 0x6401 .. 0x65ff; read as f16 these are
+// the integers 1025 .. 1535, the binade whose ulp is 1: the f16 order IS the integer order, no denormal, no NaN, nothing rounds
+// (minimum / maximum only select).  gfx950's v_pk_minimum3_f16 / v_pk_maximum3_f16 take three operands at the issue cost of one
+// packed instruction (4 cycles, tools/microbench/valu_rate.hip), so the network is
+//   K   = v * (+1, -1) + (B, B)                          1  v_pk_mad_i16, both halves reading v's low half (op_sel_hi:[0,1,1])
+//   e_k = p_k * (-1, +1) + K                            16  v_pk_mad_i16, the same
+//   mn3_k = minimum3(e_k, e_k+1, e_k+2)                 16
+//   arc_k = minimum3(mn3_k, mn3_k+3, mn3_k+6)           16  (the minimum of e_k .. e_k+8)
+//   R = maximum3 accumulation of the 16 arcs             8
+// 57 instructions where the two i32 networks took 17 v_sub + 88 v_min3 / v_max3 / v_min / v_max.  R = (B + smn, B - smx); the
+// function returns B + strength = max of R's halves (B's low byte is 0: the low byte of the result is the strength of a corner).
+#define FAST_PK_BIAS 0x6500u
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t fastPkMad(const uint32_t a, const uint32_t mul, const uint32_t add) {
+  uint32_t r;  // (a.lo * mul.lo + add.lo, a.lo * mul.hi + add.hi)
+  asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(a), "s"(mul), "v"(add));
+  return r;
+}
+__device__ __forceinline__ uint32_t fastStrengthBiased(const uint32_t v, const uint32_t (&p)[16]) {
+  const uint32_t K = fastPkMad(v, 0xFFFF0001u, FAST_PK_BIAS * 0x00010001u);
+  half2v e[16], mn3[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) e[k] = __builtin_bit_cast(half2v, fastPkMad(p[k], 0x0001FFFFu, K));
+#pragma unroll
+  for (int k = 0; k < 16; k++)
+    mn3[k] = __builtin_elementwise_minimum(__builtin_elementwise_minimum(e[k], e[(k + 1) & 15]), e[(k + 2) & 15]);
+  half2v R = {};
+#pragma unroll
+  for (int k = 0; k < 16; k += 2) {
+    const half2v a0 = __builtin_elementwise_minimum(__builtin_elementwise_minimum(mn3[k], mn3[(k + 3) & 15]), mn3[(k + 6) & 15]);
+    const half2v a1 = __builtin_elementwise_minimum(__builtin_elementwise_minimum(mn3[k + 1], mn3[(k + 4) & 15]), mn3[(k + 7) & 15]);
+    R = k == 0 ? __builtin_elementwise_maximum(a0, a1) : __builtin_elementwise_maximum(__builtin_elementwise_maximum(R, a0), a1);
+  }
+  const uint32_t r = __builtin_bit_cast(uint32_t, R);
+  return max(r & 0xffffu, r >> 16);
+}
+
 __global__ __launch_bounds__(FAST_T) void k_fast(const uint8_t* __restrict__ img0, long long img0FrameStride, int img0Aligned,
                                               const uint8_t* __restrict__ pyr, const Geom g,
                                               uint32_t* __restrict__ cand, int* __restrict__ cellCount,
@@ -597,23 +637,10 @@ __global__ __launch_bounds__(FAST_T) void k_fast(const uint8_t* __restrict__ img
     for (int e = t; e < nl; e += FAST_T) {
       const int off = list[e];
       const uint8_t* p = &tile[off];
-      const int v = p[0];
-      int d[16];
+      uint32_t q[16];
 #pragma unroll
-      for (int k = 0; k < 16; k++) d[k] = v - (int)p[ro[k]];
-      int mn3[16], mx3[16];
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        mn3[k] = min(min(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-        mx3[k] = max(max(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-      }
-      int smn = -256, smx = 256;
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        smn = max(smn, min(min(mn3[k], mn3[(k + 3) & 15]), mn3[(k + 6) & 15]));
-        smx = min(smx, max(max(mx3[k], mx3[(k + 3) & 15]), mx3[(k + 6) & 15]));
-      }
-      const int s = max(smn, -smx);
+      for (int k = 0; k < 16; k++) q[k] = p[ro[k]];
+      const int s = (int)fastStrengthBiased(p[0], q) - (int)FAST_PK_BIAS;
       if (s > th) {
         const int row = (off * 3121) >> 18;  // off / TILE_STRIDE (84): exact for off < 6500
         smap[(row - 2) * SMAP_STRIDE + (off - row * TILE_STRIDE - xoff - 2)] = (uint8_t)s;  // [(py + 1)][px + 1]
@@ -725,31 +752,18 @@ __device__ __forceinline__ unsigned long long fwNegHi(const uint32_t x) {
   return m;
 }
 
-// arc strength of the pixel whose 7 x 7 block starts at LDS address e (tile row stride TS): max over the 16 arcs of 9
-// contiguous ring pixels of the smallest |difference| with one sign, as in k_fast
+// B + arc strength (fastStrengthBiased, B = FAST_PK_BIAS) of the pixel whose 7 x 7 block starts at LDS address e (tile row stride
+// TS): the 17 byte reads are immediate offsets from e, zero-extended as they come
 template <int TS>
-__device__ __forceinline__ int fwStrength(const uint32_t e) {
+__device__ __forceinline__ uint32_t fwStrength(const uint32_t e) {
   constexpr int C = 3 * TS + 3;
   constexpr int ro[16] = {C + 3 * TS,  C + 3 * TS + 1, C + 2 * TS + 2, C + TS + 3, C + 3,  C - TS + 3, C - 2 * TS + 2, C - 3 * TS + 1,
                           C - 3 * TS,  C - 3 * TS - 1, C - 2 * TS - 2, C - TS - 3, C - 3,  C + TS - 3, C + 2 * TS - 2, C + 3 * TS - 1};
   const fw_lds_u8* const p = fwLds8(e);
-  const int v = p[C];
-  int d[16];
+  uint32_t q[16];
 #pragma unroll
-  for (int k = 0; k < 16; k++) d[k] = v - (int)p[ro[k]];
-  int mn3[16], mx3[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    mn3[k] = min(min(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-    mx3[k] = max(max(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-  }
-  int smn = -256, smx = 256;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    smn = max(smn, min(min(mn3[k], mn3[(k + 3) & 15]), mn3[(k + 6) & 15]));
-    smx = min(smx, max(max(mx3[k], mx3[(k + 3) & 15]), mx3[(k + 6) & 15]));
-  }
-  return max(smn, -smx);
+  for (int k = 0; k < 16; k++) q[k] = p[ro[k]];
+  return fastStrengthBiased(p[C], q);
 }
 
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -772,6 +786,9 @@ typedef short short2v __attribute__((ext_vector_type(2)));
 //   * survivors are appended by exec-masked stores (exec = the ballot: fwStoreB16) to a STACK of LDS addresses -- no ring index
 //     to wrap, no per-lane slot select -- and evaluated 64 from the top as soon as 64 are waiting, twice per step;
 //   * corners enter the strength map and the corner list the same way.
+// Round 8: an evaluation's arc strength is one packed f16 network for both signs (fastStrengthBiased): 64 - 67 vector instructions
+// per evaluation of 64 survivors instead of 111 - 114, 38 VGPRs instead of 59.  The evaluation compares B + strength with B + th and
+// stores the low byte, so the bias is never taken off.
 template <int TS>
 __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ img0, long long img0FrameStride,
                                                   const uint8_t* __restrict__ pyr, const Geom g,
@@ -879,6 +896,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   for (int pass = 0; pass < 2; pass++) {
     const int th = pass == 0 ? g.iniTh : g.minTh;
     const uint32_t th2 = (uint32_t)th * 0x00010001u;
+    const int thB = th + (int)FAST_PK_BIAS;
     int nList = 0, nCorn = 0;  // wave-uniform (SGPRs)
     // A cell without a survivor at iniThFAST is swept again at minThFAST (cpp:1117-1123) -- on real images that is every second
     // cell, and in a flat region the second sweep lists nothing either.  While the first sweep has not listed a pixel yet (`flat`,
@@ -900,10 +918,10 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
         act = (1ull << cnt) - 1ull;
         e = lane < cnt ? e : eIdle;
       }
-      const int sv = fwStrength<TS>(e);
-      const unsigned long long mc = __ballot(sv > th) & act;
+      const uint32_t sv = fwStrength<TS>(e);  // B + strength
+      const unsigned long long mc = __ballot((int)sv > thB) & act;
       if (mc != 0ull) {
-        fwStoreB8(e + kS, (uint32_t)sv, mc);
+        fwStoreB8(e + kS, sv, mc);  // (the low byte: B's is 0 and a corner's strength is 1 .. 255)
         const int nc = (int)__popcll(mc);
         if (nCorn + nc <= FW_CORN) fwStoreB16((cornAddr + 2u * (uint32_t)nCorn) + 2u * (uint32_t)fwMbcnt(mc), e, mc);
         nCorn += nc;

@@ -15,6 +15,8 @@
 // eight copies of one instruction on eight different destination registers
 #define OP8_2(ins) asm volatile(ins " %0, %0, %8\n" ins " %1, %1, %8\n" ins " %2, %2, %8\n" ins " %3, %3, %8\n" ins " %4, %4, %8\n" ins " %5, %5, %8\n" ins " %6, %6, %8\n" ins " %7, %7, %8" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2))
 #define OP8_3(ins) asm volatile(ins " %0, %0, %8, %9\n" ins " %1, %1, %8, %9\n" ins " %2, %2, %8, %9\n" ins " %3, %3, %8, %9\n" ins " %4, %4, %8, %9\n" ins " %5, %5, %8, %9\n" ins " %6, %6, %8, %9\n" ins " %7, %7, %8, %9" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2))
+// three operands with a modifier suffix (op_sel_hi of the packed 16-bit forms)
+#define OP8_3S(ins, suf) asm volatile(ins " %0, %0, %8, %9 " suf "\n" ins " %1, %1, %8, %9 " suf "\n" ins " %2, %2, %8, %9 " suf "\n" ins " %3, %3, %8, %9 " suf "\n" ins " %4, %4, %8, %9 " suf "\n" ins " %5, %5, %8, %9 " suf "\n" ins " %6, %6, %8, %9 " suf "\n" ins " %7, %7, %8, %9 " suf : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2))
 #define OP8_1(ins) asm volatile(ins " %0, %0\n" ins " %1, %1\n" ins " %2, %2\n" ins " %3, %3\n" ins " %4, %4\n" ins " %5, %5\n" ins " %6, %6\n" ins " %7, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2))
 // compares write an SGPR pair each
 #define OP8_C(ins) asm volatile(ins " s[20:21], %0, %8\n" ins " s[22:23], %1, %8\n" ins " s[24:25], %2, %8\n" ins " s[26:27], %3, %8\n" ins " s[28:29], %4, %8\n" ins " s[30:31], %5, %8\n" ins " s[32:33], %6, %8\n" ins " s[34:35], %7, %8" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2) : "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s32", "s33", "s34", "s35")
@@ -99,6 +101,12 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, unsigned long long* cyc,
       if (OP == 64) OP8_2("v_min_f32");
       if (OP == 65) OP8_2("v_mul_i32_i24");
       if (OP == 66) OP8_3("v_fma_f32");
+      if (OP == 67) OP8_3("v_pk_minimum3_f16");
+      if (OP == 68) OP8_3("v_pk_maximum3_f16");
+      if (OP == 69) OP8_3S("v_pk_mad_i16", "op_sel_hi:[0,1,1]");
+      if (OP == 70) OP8_2("v_pk_min_f16");
+      if (OP == 71) OP8_2("v_pk_max_f16");
+      if (OP == 72) OP8_3("v_pk_mad_i16");
       if (OP == 100) asm volatile("v_mov_b32_dpp %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %2, %2 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %3, %3 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %5, %5 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %6, %6 row_shr:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %7, %7 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2));
       if (OP == 101) asm volatile("v_add_u32_dpp %0, %0, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %1, %1, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %2, %2, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %3, %3, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %4, %4, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %5, %5, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %6, %6, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n v_add_u32_dpp %7, %7, %8 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(k1), "v"(k2));
     }
@@ -145,6 +153,11 @@ int main() {
   run<1>("v_min3_i32"); run<26>("v_max3_u32"); run<27>("v_med3_i32"); run<2>("v_perm_b32"); run<11>("v_bfe_u32"); run<12>("v_alignbyte_b32");
   run<13>("v_lshl_add_u32"); run<14>("v_add3_u32"); run<24>("v_or3_b32"); run<15>("v_mad_u32_u24"); run<25>("v_sad_u8"); run<6>("v_mul_lo_u32");
   run<3>("v_pk_max_u16"); run<21>("v_pk_add_u16"); run<22>("v_pk_sub_i16"); run<5>("v_dot4_u32_u8"); run<23>("v_dot2_u32_u16");
+  // the packed 16-bit classes of k_fast_wave's arc strength (round 8): VALU_RATE_PK16=1
+  if (getenv("VALU_RATE_PK16")) {
+    run<67>("v_pk_minimum3_f16"); run<68>("v_pk_maximum3_f16"); run<69>("v_pk_mad_i16 opsel"); run<72>("v_pk_mad_i16"); run<70>("v_pk_min_f16");
+    run<71>("v_pk_max_f16"); run<3>("v_pk_max_u16"); run<1>("v_min3_i32"); run<30>("v_sub_u32");
+  }
   if (getenv("VALU_RATE_MORE")) {
     run<32>("v_mul_f32"); run<33>("v_add_f32"); run<34>("v_floor_f32"); run<35>("v_cvt_u32_f32"); run<36>("v_cvt_f32_ubyte0"); run<37>("v_cvt_f32_ubyte2");
     run<38>("v_mul_hi_u32_u24"); run<39>("v_lshl_or_b32"); run<40>("v_and_or_b32"); run<41>("v_cvt_pk_u8_f32"); run<42>("v_rndne_f32"); run<43>("v_max_f32");
