@@ -529,6 +529,106 @@ int orbx_bundle_adjust(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orb
                        const float* inv_sigma2, int n_iterations, int min_points, int normalize, orbx_ba_result* res,
                        float* p3d_out);
 
+/* ---- behind SearchByBoW: pose optimisation (Optimizer::PoseOptimization, motion-only bundle adjustment) ----------------------
+ * What a tracker calls behind SearchByBoW in TrackReferenceKeyFrame and Relocalization: one free 6-dof pose, the matched map
+ * points held fixed, four rounds of Levenberg-Marquardt with an outlier classification behind each, for a batch of independent
+ * problems.  The reference vendors the g2o types and solver but has no Optimizer and no EdgeSE3ProjectXYZOnlyPose: the rules
+ * below restate the monocular Optimizer::PoseOptimization of the ORB-SLAM2 design, built from the vendored VertexSE3Expmap, FIXED
+ * VertexSBAPointXYZ and EdgeSE3ProjectXYZ (for the pose block the same arithmetic as the only-pose edge), [from-knowledge],
+ * PARITY UNPINNED, as the two-view bundle adjustment above.  The device equals the CPU restatement tests/cpp/pose_ref.cpp bit for
+ * bit.
+ *
+ * Graph.  One pose vertex, its start SE3Quat(R, t) of the caller's f32 Tcw (types/se3quat.h:58-60, :280-285, as above).  One
+ * EdgeSE3ProjectXYZ per feature j of the frame that has a map point, ascending j: obs = the undistorted keypoint's pt,
+ * information = inv_sigma2[octave] * I, RobustKernelHuber with delta = (float)sqrt(5.991) (`const float deltaMono`), fx fy cx
+ * cy from K; the point vertex is fixed, so the edge adds a block to the pose only (core/base_binary_edge.hpp:65-113).  Every
+ * feature's outlier flag starts false.  n_correspondences = the edges; below 3 the status is ORBX_POSE_FEW_POINTS, the pose is
+ * returned as given and nothing runs (`if (nInitialCorrespondences < 3) return 0`).
+ *
+ * Four rounds, it = 0 .. 3 (`for (size_t it = 0; it < 4; it++)`):
+ *  a. The pose is set back to the INITIAL estimate (`vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw))`).
+ *  b. initializeOptimization(0): the active edges are those of level 0 = the features not flagged.
+ *  c. optimize(n_iterations) (the reference design passes 10 in every round): the loop of core/sparse_optimizer.cpp:376-414 over
+ *     OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:61-164), steps 1 to 7 of the bundle
+ *     adjustment above without points: no Schur complement, computeLambdaInit over the pose's six diagonal entries,
+ *     computeScale over the pose's six terms; _ni, _nBad and lambda start again at iteration 0 of every round (:93-97).  A round
+ *     without an active edge runs no iteration (optimize returns at its empty index mapping).
+ *  d. Classification.  For every edge `const float chi2 = e->chi2()` = e . (information e), not robustified, f64 -> f32;
+ *     chi2 > 5.991f: the feature is flagged and its edge leaves the active set (level 1); otherwise it is not flagged (level 0).
+ *     g2o's stale errors are kept: the design recomputes the error only of the edges that were flagged during the round.  An
+ *     edge that was active keeps the _error of the last computeActiveErrors, which is that of the round's last TRIAL, accepted or
+ *     not (:123, and pop() at :146 restores estimates, not errors).  So: edges flagged during the round are evaluated at the
+ *     round's final pose, edges active during the round at the pose of its last trial (a trial whose solve failed applies a
+ *     zero step: the pose before it); a round that ran no iteration uses the initial pose for both.  Behind round 2 the robust
+ *     kernel is removed (`if (it == 2) e->setRobustKernel(0)`): round 3 runs with rho[0] = chi2, rho[1] = 1.
+ *  e. `if (optimizer.edges().size() < 10) break`: the count is of ALL edges = n_correspondences, so with fewer than 10 only round
+ *     0 runs.
+ * Result: the pose behind the last round that ran, the flags, n_bad of that round, n_inliers = n_correspondences - n_bad (the
+ * design's return value).
+ *
+ * Documented deviations:
+ *  1. Sums.  Every sum over edges (chi2, Hpp, bp) is f64 in this order: a problem has 64 lanes; lane l adds the terms of the
+ *     active features l, l + 64, l + 128, ... one after the other (features without an edge or flagged are passed over: feature j
+ *     always belongs to lane j % 64); lane l then adds lane l + 32's sum to its own, then lane l + 16's, + 8, + 4, + 2, + 1; the
+ *     result is lane 0's.  (The device adds lane l ^ 32's, l ^ 16's, ... so that every lane ends with lane 0's bits: f64 addition
+ *     is commutative.)  g2o adds edge by edge.
+ *  2. The small dense algebra and the sin / cos of deviations 2 and 3 above, through the shared csrc/orbx_ba_math.inc; a failed
+ *     6x6 solve applies a zero step.
+ *  3. There are no Frame / MapPoint types and no pbStopFlag: map points are coordinates plus a mask.
+ *  4. Garbage inputs set flags and are never followed: a frame count outside [0, capacity], a match index >= capacity, an octave
+ *     outside the table on a feature with a point (ORBX_POSE_BAD_INPUT), a non-finite point or pose, a non-finite resulting
+ *     pose, chi2 or lambda (ORBX_POSE_NONFINITE).  Such a problem returns its inputs: R and tcw are d_pose0's bits, every flag
+ *     is 0 and every other number of the result is 0.  So does a problem with ORBX_POSE_FEW_POINTS, except that
+ *     n_correspondences and n_inliers are reported.
+ *  5. n_iterations == 0 is accepted: nothing is optimised, the rounds only classify at the initial pose, and chi2_initial,
+ *     chi2_final and lambda are 0.  Like every optimised pose, R comes back as the rotation matrix of the normalised quaternion
+ *     built from it. */
+#define ORBX_POSE_BAD_INPUT 2    /* a frame count outside [0, capacity], a match index >= capacity, an octave outside [0, nlevels) */
+#define ORBX_POSE_NONFINITE 4    /* a non-finite input point or pose, or a non-finite result */
+#define ORBX_POSE_FEW_POINTS 8   /* n_correspondences < 3 */
+typedef struct orbx_pose_result {
+  int32_t status;            /* 0, or a bitmask of ORBX_POSE_*; every field is written for every problem */
+  int32_t n_correspondences; /* edges (nInitialCorrespondences) */
+  int32_t n_bad;             /* flagged features behind the last round that ran */
+  int32_t n_inliers;         /* n_correspondences - n_bad */
+  int32_t rounds;            /* rounds that ran: 4, 1 with fewer than 10 correspondences, 0 when nothing ran */
+  int32_t iterations[4];     /* solve() calls of each round */
+  int32_t lm_trials;         /* over all rounds: the sum of qmax */
+  int32_t rejected_trials;
+  int32_t solver_failures;
+  int32_t stop_reason[4];    /* per round: 0 = all iterations ran, 1 = qmax == 10 || rho == 0, 2 = _nBad >= 3 */
+  double chi2_initial;       /* activeRobustChi2 at the initial pose in round 0 */
+  double chi2_final, lambda; /* of the last round that ran an iteration */
+  double q[4], t[3];         /* the pose as g2o holds it: quaternion (x, y, z, w) and translation */
+  float R[9], tcw[3];        /* as Converter::toCvMat would store it (row-major) */
+} orbx_pose_result;
+
+/* Batched, device-resident, stream-ordered on the context stream (results valid after a device synchronisation).  Problem p
+ * optimises frame h_frame[p] (its d_kps_un / d_n rows, the layout of the extract calls) against point set h_point_set[p] of
+ * d_points float [n_point_sets][capacity][3] and d_point_mask uint8 [n_point_sets][capacity] (NULL = every entry is a point),
+ * from d_pose0 float [n_problems][12] (R row-major, then t).  With d_match == NULL feature j's point is entry j of the set, where
+ * the mask is set.  With d_match int32 [n_problems][capacity], it is entry i = d_match[p][j] >= 0, where the mask at i is set:
+ * the layout of orbx_match_bow_batch_device's d_matches_f with the keyframe's map points as the point set, so SearchByBoW ->
+ * PoseOptimization chains on the device without a gather or a copy.  A frame and a point set may appear in any number of
+ * problems.  K row-major 3x3 (host, f32); inv_sigma2: host, the context's nlevels floats, NULL = the context's own table;
+ * n_iterations >= 0 (10).  Outputs: d_res [n_problems]; d_outlier uint8 [n_problems][capacity]: 1 = feature j is flagged; every
+ * entry is written.  One wave of 64 lanes runs a problem's whole optimisation, four problems per workgroup, in one launch.  The
+ * call returns once queued, with the exception of orbx_bundle_adjust_batch_device: when the problem list or the table differs from
+ * the previous call's on this context, the call first waits for the context stream before it uploads them.
+ * ORBX_E_BADARG: null pointers, negative counts, capacity < 1, n_iterations < 0, a frame index outside [0, n_frames), a point set
+ * outside [0, n_point_sets); ORBX_E_CAPACITY: capacity >= 2^20; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments -- all
+ * checked before anything touches a device.  n_problems == 0 is ORBX_OK. */
+int orbx_pose_optimize_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_frame, const int32_t* h_point_set,
+                                    const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_match,
+                                    int n_point_sets, const float* d_points, const uint8_t* d_point_mask, const float* d_pose0,
+                                    const float* K, const float* inv_sigma2, int n_iterations, orbx_pose_result* d_res,
+                                    uint8_t* d_outlier);
+/* The same for one problem in host memory (the direct form: points [n][3], mask [n] nullable, pose0 [12], outlier [n]), run
+ * through the batched path as a batch of one.  Synchronous. */
+int orbx_pose_optimize(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const float* points, const uint8_t* mask,
+                       const float* pose0, const float* K, const float* inv_sigma2, int n_iterations, orbx_pose_result* res,
+                       uint8_t* outlier);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

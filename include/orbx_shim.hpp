@@ -513,7 +513,7 @@ class Initializer {
 };
 
 // ---- Optimizer: the two-view bundle adjustment of Tracking::CreateInitialMapMonocular (include/orbx.h, "behind the Initializer:
-// two-view bundle adjustment") ------------------------------------------------------------------------------------
+// two-view bundle adjustment") and the pose optimisation of TrackReferenceKeyFrame / Relocalization ------------------------------------------------------------------------------------
 // BundleAdjustmentTwoView(F1, F2, vMatches12, Tcw, vP3D, vbTriangulated, nIterations): what Initialize() returned, refined in
 // place by orbx_bundle_adjust on the device of the frames' extractor: GlobalBundleAdjustemnt(map, 20) on the two initial
 // keyframes, then the median-depth normalisation and the "Wrong initialization, reseting" test (100 points, a positive median
@@ -563,6 +563,51 @@ class Optimizer {
       vP3D[i].z = p3d[3 * i + 2];
     }
     return res.status;
+  }
+
+  // PoseOptimization(F, vP3D, vbHasPoint, Tcw, vbOutlier): ORB-SLAM2's Optimizer::PoseOptimization(&F) (include/orbx.h, "behind
+  // SearchByBoW: pose optimisation") for a frame whose map points are given as coordinates (vP3D[j], where vbHasPoint[j]):
+  // motion-only bundle adjustment from Tcw by orbx_pose_optimize on the device of the frame's extractor.  Tcw is replaced by
+  // the refined pose and vbOutlier by the features' flags (mvbOutlier); returns nInitialCorrespondences - nBad.  With fewer
+  // than 3 correspondences (or inputs the library refuses: res.status, see orbx.h) Tcw is left as it is.  Argument / HIP
+  // errors throw orbx::Error.
+  template <class FrameT, class Point3>
+  static int PoseOptimization(FrameT& F, const std::vector<Point3>& vP3D, const std::vector<bool>& vbHasPoint, PoseT& Tcw,
+                              std::vector<bool>& vbOutlier, int nIterations = 10, orbx_pose_result* result = nullptr) {
+    ORBextractor* e = F.mpORBextractor;
+    if (!e) throw orbx::Error(ORBX_E_BADARG, "Optimizer: the frame carries no extractor");
+    const size_t n = F.mvKeysUn.size();
+    if (vP3D.size() != n || vbHasPoint.size() != n)
+      throw orbx::Error(ORBX_E_BADARG, "Optimizer: vP3D and vbHasPoint must have one entry per keypoint of the frame");
+    float pose0[12], K[9];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) {
+        pose0[r * 3 + c] = (float)Tcw(r, c);
+        K[r * 3 + c] = frameK(F.mK, r, c);
+      }
+      pose0[9 + r] = (float)Tcw(r, 3);
+    }
+    std::vector<float> p3d(3 * (n ? n : 1));
+    std::vector<uint8_t> has(n ? n : 1), out(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+      p3d[3 * i] = vP3D[i].x;
+      p3d[3 * i + 1] = vP3D[i].y;
+      p3d[3 * i + 2] = vP3D[i].z;
+      has[i] = vbHasPoint[i] ? 1 : 0;
+    }
+    orbx_pose_result res;
+    const int r = orbx_pose_optimize(e->context(), reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn.data()), (int)n, p3d.data(),
+                                     has.data(), pose0, K, nullptr, nIterations, &res, out.data());
+    if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+    if (res.status == 0)
+      for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Tcw(i, j) = res.R[i * 3 + j];
+        Tcw(i, 3) = res.tcw[i];
+      }
+    vbOutlier.assign(n, false);
+    for (size_t i = 0; i < n; i++) vbOutlier[i] = out[i] != 0;
+    if (result) *result = res;
+    return res.n_inliers;
   }
 };
 

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -117,6 +117,30 @@ BA_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _BA_INTS] + [(n, "<f8") for n in
                            [("q", "<f8", 4), ("t", "<f8", 3), ("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("median_depth", "<f4"),
                             ("reserved2", "<f4")])
 assert BA_RESULT_DTYPE.itemsize == ctypes.sizeof(BAResult) == 168
+POSE_BAD_INPUT, POSE_NONFINITE, POSE_FEW_POINTS = 2, 4, 8
+
+
+class PoseResult(ctypes.Structure):
+    """orbx_pose_result: Optimizer::PoseOptimization's outcome for one problem (n_inliers is the reference design's return value)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")] + \
+               [("iterations", ctypes.c_int32 * 4)] + [(n, ctypes.c_int32) for n in ("lm_trials", "rejected_trials", "solver_failures")] + \
+               [("stop_reason", ctypes.c_int32 * 4)] + [(n, ctypes.c_double) for n in ("chi2_initial", "chi2_final", "lambda_")] + \
+               [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("R", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["lambda"] = d.pop("lambda_")
+        d["iterations"], d["stop_reason"] = np.array(d["iterations"][:], np.int32), np.array(d["stop_reason"][:], np.int32)
+        d["q"], d["t"] = np.array(d["q"][:], np.float64), np.array(d["t"][:], np.float64)
+        d["R"], d["tcw"] = np.array(d["R"][:], np.float32).reshape(3, 3), np.array(d["tcw"][:], np.float32)
+        return d
+
+
+POSE_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")] +
+                             [("iterations", "<i4", 4)] + [(n, "<i4") for n in ("lm_trials", "rejected_trials", "solver_failures")] +
+                             [("stop_reason", "<i4", 4)] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
+                             [("q", "<f8", 4), ("t", "<f8", 3), ("R", "<f4", (3, 3)), ("tcw", "<f4", 3)])
+assert POSE_RESULT_DTYPE.itemsize == ctypes.sizeof(PoseResult) == 192
 
 
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
@@ -240,6 +264,8 @@ def lib() -> ctypes.CDLL:
     L.orbx_initialize.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, f32, f32, i32, ctypes.POINTER(InitResult), vp, vp]
     L.orbx_bundle_adjust_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.orbx_bundle_adjust.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(BAResult), vp]
+    L.orbx_pose_optimize_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.orbx_pose_optimize.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, ctypes.POINTER(PoseResult), vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -970,6 +996,61 @@ class ORBextractor:
                                                             int(min_points), int(bool(normalize)), _ptr(d_res), _ptr(d_p3d_out)),
                     "orbx_bundle_adjust_batch_device")
 
+    # -- Optimizer::PoseOptimization behind SearchByBoW (include/orbx.h) -------------------------------------
+    def pose_optimize(self, keys_un, points, mask, Tcw, K, inv_sigma2=None, n_iterations: int = 10):
+        """One problem from host memory: the frame's mvKeysUn, one map point per feature (points [n, 3], mask [n] or None = every
+        feature has one), the start pose Tcw (3x4 or 4x4) and K.  Returns (PoseResult, vbOutlier [n] bool); result.n_inliers is
+        the reference design's return value."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        if len(pts) != len(k) or (m is not None and len(m) != len(k)):
+            raise OrbxError(E_BADARG, "points and mask must have one entry per keypoint of the frame")
+        T = np.asarray(Tcw, np.float32)
+        pose0 = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        res = PoseResult()
+        out = np.zeros(max(len(k), 1), np.uint8)
+        self._check(self._L.orbx_pose_optimize(self._h, _ptr(k), len(k), _ptr(pts), _ptr(m), _ptr(pose0), _ptr(Kf), _ptr(sig),
+                                               int(n_iterations), ctypes.byref(res), _ptr(out)), "orbx_pose_optimize")
+        return res, out[:len(k)].astype(bool)
+
+    def pose_optimize_batch_device(self, n_frames: int, frame: np.ndarray, point_set: np.ndarray, d_kps_un, d_n, d_match, n_point_sets: int,
+                                   d_points, d_point_mask, d_pose0, K, d_res, d_outlier, inv_sigma2=None, n_iterations: int = 10,
+                                   capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: problem p optimises frame frame[p] against point set point_set[p] (d_points float32
+        [n_point_sets, capacity, 3], d_point_mask uint8 [n_point_sets, capacity] or None) from d_pose0 float32 [n_problems, 12].
+        d_match int32 [n_problems, capacity] is match_bow_batch_device's d_matches_f (the point sets are then the keyframes' map
+        points), or None = feature j's point is entry j.  d_res [n_problems] POSE_RESULT_DTYPE records (192 bytes), d_outlier
+        uint8 [n_problems, capacity].  Stream-ordered: the outputs are valid after a device synchronisation."""
+        frame = np.ascontiguousarray(frame, np.int32)
+        point_set = np.ascontiguousarray(point_set, np.int32)
+        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
+        if len(point_set) != P:
+            raise OrbxError(E_BADARG, "frame and point_set must have the same length")
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        if d_match is not None:
+            _need("the match array", d_match, P * cap * 4)
+        _need("the point array", d_points, n_point_sets * cap * 12)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, n_point_sets * cap)
+        _need("the pose array", d_pose0, P * 48)
+        _need("the result array", d_res, P * POSE_RESULT_DTYPE.itemsize)
+        _need("the outlier array", d_outlier, P * cap)
+        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_pose0, d_res, d_outlier)
+        self._check(self._L.orbx_pose_optimize_batch_device(self._h, n_frames, P, _ptr(frame), _ptr(point_set), _ptr(d_kps_un), _ptr(d_n),
+                                                            cap, _ptr(d_match), n_point_sets, _ptr(d_points), _ptr(d_point_mask),
+                                                            _ptr(d_pose0), _ptr(Kf), _ptr(sig), int(n_iterations), _ptr(d_res),
+                                                            _ptr(d_outlier)), "orbx_pose_optimize_batch_device")
+
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:
         w, h = ctypes.c_int(0), ctypes.c_int(0)
@@ -1482,3 +1563,25 @@ class ORBmatcher:
         fn, ff = flat(F.mFeatVec)
         return ext.match_bow(KF.mvKeysUn, KF.mDescriptors, kn, kf, F.mvKeysUn, F.mDescriptors, fn, ff, mask, self.mfNNratio,
                              self.mbCheckOrientation)
+
+
+class Optimizer:
+    """The part of ORB-SLAM2's Optimizer a tracker calls on every frame (include/orbx.h, "behind SearchByBoW: pose optimisation")."""
+
+    @staticmethod
+    def PoseOptimization(frame: Frame, points, mask, Tcw, K=None, extractor: Optional[ORBextractor] = None, n_iterations: int = 10):
+        """Optimizer::PoseOptimization(&frame): frame.mvKeysUn against one map point per feature (points [N, 3], mask [N] = the
+        feature has one: mvpMapPoints), from the pose Tcw (3x4 or 4x4).  K: 3x3, default the frame's camera.  Returns (the inlier
+        count, the refined Tcw 4x4 float32, vbOutlier [N] bool, the PoseResult)."""
+        ext = extractor or frame.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "Optimizer needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(frame, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "Optimizer.PoseOptimization needs K (the frame carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        res, outlier = ext.pose_optimize(frame.mvKeysUn, points, mask, Tcw, K, None, n_iterations)
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3], T[:3, 3] = np.array(res.R[:], np.float32).reshape(3, 3), np.array(res.tcw[:], np.float32)
+        return int(res.n_inliers), T, outlier, res

@@ -216,6 +216,7 @@ struct orbx_ctx {
   DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
   MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
+  PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -2959,6 +2960,7 @@ int ctxDrain(orbx_ctx* c) {
 void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
 MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
+PoseScratch* ctxPose(orbx_ctx* c) { return &c->pose; }
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;
   return c->invSigma2.data();

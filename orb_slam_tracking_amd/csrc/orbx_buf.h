@@ -1,5 +1,5 @@
 // orbx_buf.h — owners of the library's device and page-locked host memory, and the one description of a staging block.
-// orbx_api.cpp, orbx_bow.cpp and orbx_ba.cpp allocate and free through these types only.
+// orbx_api.cpp, orbx_bow.cpp, orbx_ba.cpp and orbx_pose.cpp allocate and free through these types only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -143,6 +143,15 @@ struct BaScratch {
   DeviceBuf<float> dSigma;      // inv_sigma2 of the last call
   std::vector<float> hSigma;
   DeviceBuf<uint8_t> dIo;       // staging of orbx_bundle_adjust
+};
+
+// What a context keeps for orbx_pose_optimize* (orbx_pose.cpp; the context owns it, orbx_api.cpp).
+struct PoseScratch {
+  DeviceBuf<int32_t> dProblems;    // the problem list [2][n_problems] of the last call
+  std::vector<int32_t> hProblems;  // (kept alive behind the asynchronous upload)
+  DeviceBuf<float> dSigma;         // inv_sigma2 of the last call
+  std::vector<float> hSigma;
+  DeviceBuf<uint8_t> dIo;          // staging of orbx_pose_optimize
 };
 
 }  // namespace orbx

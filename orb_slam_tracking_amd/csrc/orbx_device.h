@@ -576,4 +576,23 @@ struct BaArgs {
   double fx, fy, cx, cy, delta;
   int32_t nPairs, cap, nLevels, nIterations, minPoints, normalize;
 };
+
+// k_pose: Optimizer::PoseOptimization (include/orbx.h, "behind SearchByBoW: pose optimisation"), a wave per problem
+constexpr int POSE_WAVES = 4;  // problems per workgroup; the waves share nothing
+constexpr int POSE_THREADS = 64 * POSE_WAVES;
+constexpr int POSE_CACHE = 6;  // edges per lane a wave keeps in LDS (384 per problem when they are spread evenly); 12 KB per wave
+struct PoseArgs {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const int32_t* nKps;        // [frames]
+  const int32_t* problems;    // [2][nProblems] frames, then point sets
+  const int32_t* match;       // nullable [nProblems][cap]
+  const float* points;        // [sets][cap][3]
+  const uint8_t* mask;        // nullable [sets][cap]
+  const float* pose0;         // [nProblems][12]
+  const float* invSigma2;     // [nLevels] (device)
+  orbx_pose_result* res;      // [nProblems]
+  uint8_t* outlier;           // [nProblems][cap]
+  double fx, fy, cx, cy, delta;
+  int32_t nProblems, cap, nLevels, nIterations;
+};
 }  // namespace orbx
