@@ -289,6 +289,24 @@ def init_scene(seed, n=500, n_iter=200):
     return K.astype(np.float32), k1, len(a), k2, len(b), m12, sets
 
 
+def zero_table():
+    return np.zeros(NLEVELS, np.float32)
+
+
+def top_level_off_table():
+    """The usual table with the weight of the last level set to 0: the table world("no_weight") is meant for."""
+    t = inv_sigma2_table()
+    t[NLEVELS - 1] = 0
+    return t
+
+
+def one_level_table(level=3):
+    """Weight 1 at one level, 0 elsewhere."""
+    t = zero_table()
+    t[level] = 1
+    return t
+
+
 _worlds = {}
 
 
@@ -296,7 +314,9 @@ def world(name: str) -> Pair:
     """Named pairs, made once.  general: converges; rejecting: the input translation 30 times too long and gross
     mismatches (rejected trials); huber:
     gross mismatches; converged: general's result fed back (the small-theta branch); mirrored: negative depths; few: 40 points; truth: little pixel noise, an input pose
-    1.5 degrees and 11 degrees (translation direction) off."""
+    1.5 degrees and 11 degrees (translation direction) off; no_weight: general with every keypoint at the last level, for
+    top_level_off_table() -- every edge weighs nothing, as under a table of zeros, in a call whose other pairs keep their weights
+    (a call has one table)."""
     if name not in _worlds:
         if name == "general":
             w = make_pair(300, 1)
@@ -314,6 +334,10 @@ def world(name: str) -> Pair:
             w = make_pair(40, 5)
         elif name == "truth":
             w = make_pair(300, 11, noise=0.2, twist=(0.02, -0.015, 0.01, 0.05, -0.04, 0.03))
+        elif name == "no_weight":
+            g = world("general")
+            w = g.padded(g.cap)
+            w.k1["octave"][:], w.k2["octave"][:] = NLEVELS - 1, NLEVELS - 1
         else:
             raise KeyError(name)
         _worlds[name] = w

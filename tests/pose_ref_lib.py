@@ -284,6 +284,89 @@ def feed_back(w: World, res) -> World:
     return q
 
 
+WAVE, LANE_CACHE = 64, 6  # k_pose: feature j is lane j % 64's, and a lane keeps its first six edges in LDS
+BIG_CAP = 1024            # the capacity of the worlds that leave that cache
+
+
+def lane_layout(w: World):
+    """From the edges alone: (features of the edges behind their lane's cache [ascending], edges per lane [64], lanes with a
+    feature without an edge in front of their sixth edge, lanes with one behind their seventh edge)."""
+    j, _ = w.edges()
+    behind, per_lane, hole_front, hole_behind = [], np.zeros(WAVE, np.int64), [], []
+    for lane in range(WAVE):
+        mine = j[j % WAVE == lane]
+        per_lane[lane] = len(mine)
+        behind.extend(mine[LANE_CACHE:])
+        holes = np.setdiff1d(np.arange(lane, w.n, WAVE), mine)
+        if len(mine) >= LANE_CACHE and (holes < mine[LANE_CACHE - 1]).any():
+            hole_front.append(lane)
+        if len(mine) > LANE_CACHE and (holes > mine[LANE_CACHE]).any():
+            hole_behind.append(lane)
+    return np.sort(np.array(behind, np.int64)), per_lane, hole_front, hole_behind
+
+
+def scattered(dense: World, at, nf, seed, cap=BIG_CAP, dead=()):
+    """A dense world (make_world(..., extra=0): feature j's point is entry j) as a match-row world of nf features: edge k sits
+    on feature at[k] (ascending) and names a permuted entry of a masked point set; the features `dead` are matched to entries
+    with mask == 0; every other feature has match -1."""
+    rng = np.random.default_rng(7000 + seed)
+    at, dead = np.asarray(at, np.int64), np.asarray(dead, np.int64)
+    m = len(at)
+    assert dense.match is None and dense.n == m and (np.diff(at) > 0).all() and at[-1] < nf <= cap and not np.intersect1d(at, dead).size
+    kps = np.zeros(cap, KEYPOINT_DTYPE)
+    kps["x"][:nf], kps["y"][:nf], kps["octave"][:nf] = rng.uniform(0, 640, nf), rng.uniform(0, 480, nf), rng.integers(0, NLEVELS, nf)
+    kps[at] = dense.kps[:m]
+    entries = rng.permutation(cap)
+    where, off = entries[:m], entries[m:m + len(dead)]
+    points = rng.normal(0, 1, (cap, 3)).astype(np.float32)  # (entries that are no point hold leftovers)
+    points[where] = dense.points[:m]
+    mask = np.zeros(cap, np.uint8)
+    mask[where] = 1
+    match = np.full(cap, -1, np.int32)
+    match[at], match[dead] = where, off
+    t = dense.truth
+    truth = dict(R=t["R"], t=t["t"], slots=at, bad=at[t["bad"]], clean=at[t["clean"]])
+    return World(kps, nf, match, points, mask, dense.pose0.copy(), dense.K, truth)
+
+
+def weight_lost_world(n_gross, n_exact, seed, cap=None):
+    """n_gross correspondences at octave 0 that are all gross mismatches (20 to 40 px off in both coordinates) and n_exact
+    without noise at octave 1, for the table level0_table(): 1 at level 0 and 0 elsewhere.  Round 0 optimises over the weighted
+    edges and flags them; the exact edges weigh nothing, so their chi2 is 0 and they stay active for ever.  From the round in
+    which no weighted edge is active any more Hpp = 0, lambda re-initialises to 1e-5 * 0 = 0 and every 6x6 solve fails at its
+    first pivot."""
+    n = n_gross + n_exact
+    w = make_world(n, seed, cap=cap, noise=0.0)
+    rng = np.random.default_rng(9000 + seed)
+    slots = w.truth["slots"]
+    gross = np.sort(rng.choice(n, n_gross, replace=False))
+    w.kps["octave"][slots] = 1
+    w.kps["octave"][slots[gross]] = 0
+    off = rng.choice([-1.0, 1.0], (n_gross, 2)) * rng.uniform(20, 40, (n_gross, 2))
+    w.kps["x"][slots[gross]] += off[:, 0].astype(np.float32)
+    w.kps["y"][slots[gross]] += off[:, 1].astype(np.float32)
+    w.truth = dict(w.truth, bad=slots[gross], clean=np.setdiff1d(slots, slots[gross]))
+    return w
+
+
+def zero_table():
+    return np.zeros(NLEVELS, np.float32)
+
+
+def level0_table():
+    t = np.zeros(NLEVELS, np.float32)
+    t[0] = 1
+    return t
+
+
+# the inv_sigma2 table a named world is meant for (every other world: the default table)
+TABLES = {"no_weight": zero_table, "no_weight_big": zero_table, "weight_lost": level0_table, "weight_lost_big": level0_table}
+
+
+def table_of(name):
+    return TABLES[name]() if name in TABLES else None
+
+
 _worlds = {}
 
 
@@ -291,7 +374,20 @@ def world(name: str) -> World:
     """Named worlds, made once.  clean: 200 correspondences, 20 mismatches; matched: the same kind through a match row; far: a
     start 25 degrees and 60 % off with a third mismatches (rejected trials); noisy: 1.2 sigma of pixel noise (features that
     change sides between rounds); converged: clean's result fed back; nine: 9 correspondences (one round); three: 3; two: 2
-    (FEW_POINTS); truth: little noise."""
+    (FEW_POINTS); truth: little noise.
+
+    Worlds of capacity 1024 in which lanes hold more than the six edges k_pose caches (lane_layout): cache_edge: 385
+    correspondences in 390 features, so a few lanes hold a seventh edge; cache_full: 700 correspondences with 1.2 sigma of
+    noise, 90 mismatches and a start 4 degrees off (flags behind the cache that change sides between rounds); cache_skewed: a
+    match-row world of 1000 features whose 24 correspondences all sit on the features of two lanes, 16 on lane 5's and 8 on every
+    other one of lane 37's, so that 62 lanes hold none (a lane has at most 16 features at this capacity); cache_holes: a
+    match-row world of 640 features of which about a quarter have no point -- match -1, or a match to an entry with mask == 0 --
+    in front of, between and behind the edges.
+
+    Worlds whose 6x6 solves fail, each for the table table_of(name): no_weight: clean under a table of zeros (Hpp = 0, lambda =
+    0: every solve fails); no_weight_big: the same with 700 correspondences; weight_lost (weight_lost_world: 100 gross mismatches
+    at level 0, 20 exact correspondences at level 1) and weight_lost_big (420 and 40): failures behind accepted trials, with flags
+    set."""
     if name not in _worlds:
         if name == "clean":
             w = make_world(200, 1, outliers=20)
@@ -312,6 +408,26 @@ def world(name: str) -> World:
             w = make_world(2, 7)
         elif name == "truth":
             w = make_world(300, 8, noise=0.2, outliers=30)
+        elif name == "cache_edge":
+            w = make_world(385, 74, cap=BIG_CAP, outliers=40)  # (three mismatches behind the cache)
+        elif name == "cache_full":
+            w = make_world(700, 770, cap=BIG_CAP, outliers=90, noise=1.2, angle_deg=4.0)
+        elif name == "cache_skewed":
+            at = np.sort(np.r_[np.arange(5, 1000, WAVE), np.arange(37, 1000, 2 * WAVE)])
+            w = scattered(make_world(len(at), 71, outliers=6, extra=0), at, 1000, 71)
+        elif name == "cache_holes":
+            rng = np.random.default_rng(72)
+            kind = rng.choice(3, 640, p=[0.74, 0.13, 0.13])  # an edge, match -1, a match to an entry with mask == 0
+            at = np.flatnonzero(kind == 0)
+            w = scattered(make_world(len(at), 72, outliers=50, extra=0), at, 640, 72, dead=np.flatnonzero(kind == 2))
+        elif name == "no_weight":
+            w = world("clean")
+        elif name == "no_weight_big":
+            w = make_world(700, 73, cap=BIG_CAP, outliers=70)
+        elif name == "weight_lost":
+            w = weight_lost_world(100, 20, 74)
+        elif name == "weight_lost_big":
+            w = weight_lost_world(420, 40, 75, cap=BIG_CAP)
         else:
             raise KeyError(name)
         _worlds[name] = w

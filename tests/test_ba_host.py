@@ -130,8 +130,52 @@ def test_general_scene_moves_towards_the_truth():
     assert r["chi2_final"] < truth_chi2
 
 
+def test_a_table_of_zeros_fails_every_solve():
+    """general under a table of zeros: Hpp = 0 and lambda = 1e-5 * 0 = 0, every point's 3x3 block is 0 and the first of them has
+    no inverse, so each of the ten trials of the only iteration is a failed solve (stop reason 1).  Status 0, a finite result,
+    and the refined points are the input points times the normalisation only.  world("no_weight") under top_level_off_table()
+    is the same problem (every edge at a level that weighs nothing) and gives the same bytes."""
+    g, idx = B.world("general"), B.pair_graph(B.world("general"))[0]
+    rest = np.setdiff1d(np.arange(g.cap), idx)
+    for normalize in (False, True):
+        r, p, c = B.bundle_adjust(g, 20, 100, normalize, inv_sigma2=B.zero_table())
+        assert r["status"] == 0 and r["n_points"] == 300
+        assert r["solver_failures"] == r["lm_trials"] == r["rejected_trials"] == 10 and r["iterations"] == 1 and r["stop_reason"] == 1
+        assert r["chi2_initial"] == 0 and r["chi2_final"] == 0 and r["lambda"] == 0
+        assert c == dict(accepted=0, rejected=10, huber_outliers=0, small_theta=0)
+        assert all(np.isfinite(r[f]).all() for f in ("q", "t", "R21", "t21", "median_depth")) and np.isfinite(p).all()
+        assert r["median_depth"] == np.sort(g.p3d[idx, 2])[(len(idx) - 1) // 2]
+        scale = np.float32(1.0) / r["median_depth"] if normalize else np.float32(1.0)
+        assert np.array_equal(p[idx], g.p3d[idx] * scale) and p[rest].tobytes() == g.p3d[rest].tobytes()
+        assert np.array_equal(r["t21"], g.init["t21"][0] * scale) and np.abs(r["R21"] - g.init["R21"][0]).max() <= 4 * 2.0 ** -24
+        r2, p2, c2 = B.bundle_adjust(B.world("no_weight"), 20, 100, normalize, inv_sigma2=B.top_level_off_table())
+        assert r2.tobytes() == r.tobytes() and p2.tobytes() == p.tobytes() and c2 == c
+    # the other pairs of tests/test_gpu_ba.py's call keep weighted edges under that table and solve
+    for name in ("rejecting", "general"):
+        r = B.bundle_adjust(B.world(name), inv_sigma2=B.top_level_off_table())[0]
+        assert r["status"] == 0 and r["solver_failures"] == 0 and r["iterations"] > 1, name
+
+
+def test_a_table_with_one_weight_keeps_every_solve():
+    """A mixed pair: weight 1 at level 3, 0 elsewhere, so three quarters of the points have two edges that weigh nothing and a
+    3x3 block of zeros.  Found on the restatement: neither NONFINITE nor a failed solve.  Some edge weighs, so lambda = 1e-5 *
+    max |diag H| > 0, and the damping makes such a point's block lambda * I with the determinant lambda^3: pointDinv never divides
+    by 0.  Status 0, solver_failures == 0, the weightless points get a zero step (their b and their Hpl are 0) and come back bit
+    for bit; every point with a weighted edge moves."""
+    g, table = B.world("general"), B.one_level_table(3)
+    r, p, c = B.bundle_adjust(g, 20, 100, False, inv_sigma2=table)
+    assert r["status"] == 0 and r["solver_failures"] == 0 and c["accepted"] > 0 and r["lambda"] > 0
+    assert r["chi2_final"] < r["chi2_initial"] and np.isfinite(p).all()
+    idx = B.pair_graph(g)[0]
+    weighs = (g.k1["octave"][idx] == 3) | (g.k2["octave"][g.m12[idx]] == 3)
+    assert 50 <= weighs.sum() <= len(idx) - 150
+    assert p[idx[~weighs]].tobytes() == g.p3d[idx[~weighs]].tobytes()
+    assert (p[idx[weighs]] != g.p3d[idx[weighs]]).any(axis=1).all()
+
+
 def test_the_worlds_run_every_branch(results):
-    """What the GPU comparison relies on: each branch of the optimisation is taken by at least one of the shared worlds."""
+    """What the GPU comparison relies on: each branch of the optimisation is taken by at least one of the shared worlds.  None
+    of them has a failed solve; that branch is test_a_table_of_zeros_fails_every_solve's."""
     cnt = {k: v[2] for k, v in results.items()}
     res = {k: v[0] for k, v in results.items()}
     assert cnt["rejecting", 20]["rejected"] > 0 and res["rejecting", 20]["rejected_trials"] == cnt["rejecting", 20]["rejected"]
@@ -142,6 +186,7 @@ def test_the_worlds_run_every_branch(results):
     assert res["general", 3]["stop_reason"] == 0 and res["general", 3]["iterations"] == 3   # all iterations used
     assert res["huber", 20]["stop_reason"] == 0 and res["huber", 20]["iterations"] == 20
     assert res["rejecting", 20]["lm_trials"] == cnt["rejecting", 20]["accepted"] + cnt["rejecting", 20]["rejected"]
+    assert all(r["solver_failures"] == 0 for r in res.values())
 
 
 def test_few_points_and_negative_depth_on_and_off():

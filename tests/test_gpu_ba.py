@@ -98,6 +98,23 @@ def test_three_pairs_mixed_in_place_and_reversed_frames(orbx, ext, sized):
     check(orbx, ext, [sized[257], B.skipped(sized[65]), sized[520]], in_place=True, reverse=True)
 
 
+@pytest.mark.parametrize("in_place", [False, True])
+def test_failed_solves_between_pairs_that_solve(orbx, ext, sized, in_place):
+    """no_weight (every edge at a level that weighs nothing under this table: ten failed solves, decided by thread 0 and taken by
+    the whole workgroup, the points passed through) as pair 1 of 3 between a pair that rejects trials and the largest one."""
+    pairs = [B.world("rejecting").padded(CAP), B.world("no_weight").padded(CAP), sized[520]]
+    res = check(orbx, ext, pairs, inv_sigma2=B.top_level_off_table(), in_place=in_place)
+    assert list(res["status"]) == [0, 0, 0] and list(res["solver_failures"]) == [0, 10, 0]
+    assert res[1]["lm_trials"] == 10 and res[1]["iterations"] == 1 and res[1]["stop_reason"] == 1 and res[1]["lambda"] == 0
+    assert res[0]["rejected_trials"] > 0 and res[2]["iterations"] == 20
+
+
+def test_every_pair_fails_every_solve_under_a_table_of_zeros(orbx, ext, sized):
+    res = check(orbx, ext, [sized[65], B.world("general").padded(CAP), sized[520]], inv_sigma2=B.zero_table(), min_points=60)
+    assert list(res["status"]) == [0, 0, 0] and list(res["solver_failures"]) == list(res["lm_trials"]) == [10, 10, 10]
+    assert list(res["iterations"]) == [1, 1, 1] and list(res["stop_reason"]) == [1, 1, 1]
+
+
 def test_five_pairs_diverging_workgroups(orbx, ext, sized):
     """Skipped and refused pairs leave early next to pairs that reject trials, run into Huber's outlier branch, stop by the
     _nBad rule or use every iteration."""

@@ -206,6 +206,142 @@ def test_host_form_equals_a_batch_of_one(orbx, ext, sized):
     assert n == ref["n_inliers"] and T[:3, :3].tobytes() == ref["R"].tobytes() and T[:3, 3].tobytes() == ref["tcw"].tobytes()
 
 
+# ---- behind the LDS cache: a lane's edges from the seventh on are read from the problem's rows, their flags from its outlier row
+# (tests/test_pose_host.py, test_the_cache_worlds_leave_the_cache, shows which worlds hold what there).  Capacity 1024, in a
+# context of their own ----
+
+BIG = P.BIG_CAP
+CACHE_WORLDS = ("cache_edge", "cache_full", "cache_skewed", "cache_holes")
+
+
+@pytest.fixture(scope="module")
+def big(orbx):
+    e = orbx.ORBextractor(1000, 1.2, P.NLEVELS, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+def _as_given(res, flags, w, status):
+    assert res["status"] == status and not flags.any()
+    assert res["R"].tobytes() == w.pose0[:9].tobytes() and res["tcw"].tobytes() == w.pose0[9:].tobytes()
+
+
+@pytest.mark.parametrize("name", CACHE_WORLDS)
+def test_one_world_behind_the_cache(orbx, big, name):
+    w = P.world(name)
+    res = check(orbx, big, [w])
+    assert w.cap == BIG and res[0]["status"] == 0 and res[0]["rounds"] == 4 and res[0]["n_correspondences"] == len(w.edges()[0])
+    assert res[0]["n_bad"] >= len(w.truth["bad"]) > 0
+
+
+def test_nine_problems_that_leave_the_cache_or_do_not(orbx, big, sized):
+    """Two full workgroups and one wave, the waves of a workgroup ending at very different times: worlds with a few edges, with
+    hundreds and with none behind the cache, a few-point problem and two refused ones -- a NaN point, and a match index >= cap
+    on a feature behind its lane's cache."""
+    full = P.world("cache_full")
+    late = with_match(full)
+    behind = P.lane_layout(full)[0]
+    late.match[behind[len(behind) // 2]] = BIG
+    worlds = [full, sized[2].padded(BIG), P.world("cache_skewed"), P.world("clean").padded(BIG), P.world("cache_holes"),
+              bad(full, "nan"), P.world("cache_edge"), P.world("far").padded(BIG), late]
+    res, flags = run_batch(orbx, big, [with_match(w) for w in worlds])
+    for p, w in enumerate(worlds):
+        r, rf, _, _ = P.pose_optimize(w)
+        same(res[p], flags[p], r, rf, "problem %d" % p)
+    assert list(res["status"]) == [0, P.FEW_POINTS, 0, 0, 0, P.NONFINITE, 0, 0, P.BAD_INPUT]
+    for p in (1, 5, 8):
+        _as_given(res[p], flags[p], worlds[p], res[p]["status"])
+    assert res[0]["n_correspondences"] == 700 and res[2]["n_correspondences"] == 24 and res[7]["rejected_trials"] > 0
+
+
+def test_a_point_in_the_plane_behind_the_cache(orbx, big):
+    """NONFINITE with the in-plane point on an edge behind the cache: every flag that the rounds set (test_pose_host shows that
+    they set some behind the cache) is cleared again."""
+    from test_pose_host import plane_world
+    w = plane_world(BIG, 450, True)
+    res, flags = run_batch(orbx, big, [w])
+    r, rf, per_round, _ = P.pose_optimize(w)
+    same(res[0], flags[0], r, rf)
+    assert per_round[:, P.lane_layout(w)[0]].any()
+    _as_given(res[0], flags[0], w, P.NONFINITE)
+
+
+@pytest.mark.parametrize("n_iterations", [0, 3])
+def test_few_and_no_iterations_behind_the_cache(orbx, big, n_iterations):
+    """With no iteration the classification alone walks the edges behind the cache."""
+    res = check(orbx, big, [P.world("cache_full")], n_iterations=n_iterations)
+    assert res[0]["status"] == 0 and list(res[0]["iterations"]) == [n_iterations] * 4 and res[0]["n_bad"] > 0
+
+
+def test_host_forms_behind_the_cache(orbx, big):
+    """orbx_pose_optimize, ORBextractor.pose_optimize and Optimizer.PoseOptimization at n = 705 (the capacity is then n, no
+    multiple of 64) against a batch of one at capacity 1024."""
+    w = P.world("cache_full")
+    assert w.n == 705
+    res, flags = run_batch(orbx, big, [w])
+    T = np.c_[w.pose0[:9].reshape(3, 3), w.pose0[9:]]
+    one, out = big.pose_optimize(w.kps[:w.n], w.points[:w.n], w.mask[:w.n], T, w.K)
+    assert bytes(one) == res[0].tobytes() and one.status == 0
+    assert np.array_equal(out, flags[0, :w.n] != 0) and not flags[0, w.n:].any()
+    frame = orbx.Frame.from_arrays(w.kps[:w.n], np.zeros((w.n, 32), np.uint8), (0, 640, 0, 480))
+    n, T2, out2, r2 = orbx.Optimizer.PoseOptimization(frame, w.points[:w.n], w.mask[:w.n], T, K=w.K, extractor=big)
+    ref, rf, _, _ = P.pose_optimize(w)
+    assert bytes(r2) == ref.tobytes() == res[0].tobytes() and np.array_equal(out2, rf[:w.n] != 0)
+    assert n == ref["n_inliers"] and T2[:3, :3].tobytes() == ref["R"].tobytes() and T2[:3, 3].tobytes() == ref["tcw"].tobytes()
+
+
+def test_one_frame_in_several_problems_behind_the_cache(orbx, big):
+    """test_one_frame_in_several_problems with a frame of 450 correspondences."""
+    a, b = P.make_world(450, 90, cap=BIG, outliers=50), P.world("cache_full")
+    moved = a.points.copy()
+    moved[:, 0] += np.float32(0.05)
+    frames, sets = [(b.kps, b.n), (a.kps, a.n)], [(a.points, a.mask), (b.points, b.mask), (moved, a.mask)]
+    worlds = []
+    for point_set, pose0 in ((0, a.pose0), (1, b.pose0), (2, a.pose0), (0, b.pose0)):
+        w = P.World(a.kps, a.n, None, sets[point_set][0], sets[point_set][1], pose0, a.K)
+        w.frame, w.point_set = 1, point_set
+        worlds.append(w)
+    assert all(len(P.lane_layout(w)[0]) >= 60 for w in worlds)
+    res = check(orbx, big, worlds, frames=frames, sets=sets)
+    assert res[0]["status"] == 0 and res[0]["n_correspondences"] == 450 and res[0]["n_bad"] == 50
+    assert res[0].tobytes() != res[2].tobytes() and res[0].tobytes() != res[3].tobytes()
+
+
+# ---- failed 6x6 solves (tests/test_pose_host.py: test_a_table_of_zeros_fails_every_solve,
+# test_solves_fail_once_every_weighted_edge_is_flagged).  A call has one table, so each table has a call of its own ----
+
+def test_every_solve_fails_under_a_table_of_zeros(orbx, big, sized):
+    """Hpp = 0, lambda = 0: forty failed solves per problem, next to a problem of one round.  Two of the problems walk edges
+    behind the cache with ok == 0, but a weightless edge adds 0 to every sum: this test cannot tell whether that loop ran
+    (test_solves_fail_behind_accepted_trials can)."""
+    worlds = [P.world("far").padded(BIG), P.world("no_weight").padded(BIG), P.world("no_weight_big"), sized[9].padded(BIG),
+              P.world("cache_full")]
+    res = check(orbx, big, worlds, inv_sigma2=P.zero_table())
+    assert list(res["status"]) == [0] * 5 and list(res["solver_failures"]) == [40, 40, 40, 10, 40]
+    assert list(res["lm_trials"]) == list(res["rejected_trials"]) == [40, 40, 40, 10, 40]
+    assert not res["n_bad"].any() and not res["chi2_initial"].any() and not res["lambda"].any()
+    for p in range(5):
+        assert list(res[p]["iterations"]) == ([1, 0, 0, 0] if p == 3 else [1, 1, 1, 1])
+        assert res[p]["tcw"].tobytes() == worlds[p].pose0[9:].tobytes()
+
+
+def test_solves_fail_behind_accepted_trials(orbx, big, sized):
+    """weight_lost and weight_lost_big between clean and far, all under the table that weighs level 0 alone: in the two the
+    solves fail from round 1 on, with flags set (behind the cache too); the other three keep weighted edges and solve."""
+    names = ("clean", "weight_lost", "cache_edge", "weight_lost_big", "far")
+    worlds = [P.world(name).padded(BIG) for name in names]
+    res = check(orbx, big, worlds, inv_sigma2=P.level0_table())
+    assert list(res["status"]) == [0] * 5 and list(res["solver_failures"]) == [0, 30, 0, 30, 0]
+    for p, gross in ((1, 100), (3, 420)):
+        assert res[p]["n_bad"] == gross and res[p]["lm_trials"] > res[p]["solver_failures"]
+        assert res[p]["iterations"][0] > 1 and list(res[p]["iterations"][1:]) == [1, 1, 1]
+
+
+# Whether test_chained_from_images' two problems hold an edge behind the cache: what the image pair happens to give, recorded here
+# so that the test says what it covers (the worlds above are what covers the cache on purpose).
+CHAINED_LEAVES_THE_CACHE = [True, True]
+
+
 def test_chained_from_images(orbx, images, golden):
     """extract -> bow transform -> SearchByBoW -> PoseOptimization from two images, every stage reading what the stage before left
     on the device: a keyframe and a frame that is its copy shifted by (5, 3) pixels.  The keyframe's map points lie on the plane
@@ -247,6 +383,7 @@ def test_chained_from_images(orbx, images, golden):
     match, pts = m.cpu().numpy().reshape(2, cap), d_pts.cpu().numpy()
     res, flags = d_res.cpu().numpy().view(orbx.POSE_RESULT_DTYPE), d_out.cpu().numpy().reshape(2, cap)
     table = e.GetInverseScaleSigmaSquares()
+    leaves_the_cache = []
     for p in range(2):
         w = P.World(kps[fr[p]].copy(), n[fr[p]], match[p].copy(), pts[kf[p]].copy(), None, pose0[p], K.reshape(9))
         r, rf, _, _ = P.pose_optimize(w, inv_sigma2=table)
@@ -257,6 +394,11 @@ def test_chained_from_images(orbx, images, golden):
         assert res[p]["status"] == 0 and res[p]["n_correspondences"] == (match[p, :n[fr[p]]] >= 0).sum() >= 50
         assert res[p]["n_inliers"] * 2 > res[p]["n_correspondences"]
         assert np.linalg.norm(res[p]["tcw"] - true_t) < np.linalg.norm(pose0[p, 9:] - true_t)
+        behind, per_lane, _, _ = P.lane_layout(w)
+        print("chained: problem %d has %d lanes with more than six correspondences, %d edges behind the cache" %
+              (p, (per_lane > P.LANE_CACHE).sum(), len(behind)))
+        leaves_the_cache.append(len(behind) > 0)
+    assert leaves_the_cache == CHAINED_LEAVES_THE_CACHE
     voc.close()
     e.close()
 

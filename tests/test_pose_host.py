@@ -15,6 +15,11 @@ import pose_ref_lib as P
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP_WORLDS = ("clean", "matched", "far", "noisy", "truth")
 ALL_WORLDS = STEP_WORLDS + ("converged", "nine", "three", "two")
+# worlds of capacity 1024 with lanes that hold more edges than k_pose caches; the two that are also checked against numpy
+CACHE_WORLDS = ("cache_edge", "cache_full", "cache_skewed", "cache_holes")
+CACHE_STEP_WORLDS = ("cache_full", "cache_skewed")
+# worlds whose 6x6 solves fail, each under its own table (pose_ref_lib.table_of)
+FAILING_WORLDS = ("no_weight", "no_weight_big", "weight_lost", "weight_lost_big")
 
 # Measured on the development machine (x86-64): the largest relative difference (max |a - b| / max |b| per vector) between the
 # restatement's first step and the numpy statement's over STEP_WORLDS, in xp, chi2_initial and lambda.  The numerical derivatives
@@ -25,16 +30,25 @@ STEP_MEASURED = 8.5e-6
 # (the features not flagged behind round 2).  The restatement stops by g2o's rules (three iterations in a row that gain less than
 # a thousandth), the numpy side differentiates numerically; the test asserts 100 times this value.
 GN_MEASURED = 1.4e-11
+# The same measurement over CACHE_STEP_WORLDS (cache_full, 700 edges: 1.95e-11; cache_skewed, 24 edges: 1.7e-11), likewise
+# against the numpy statement; their first steps stay below STEP_MEASURED (cache_full 2.3e-6, cache_skewed 6.1e-7).
+GN_MEASURED_CACHE = 2.0e-11
 
 
 @pytest.fixture(scope="module")
 def results():
     """{(world, n_iterations): (result, flags, flags per round, counters)} of the restatement, computed once and left unchanged."""
     out = {}
-    for name in ALL_WORLDS:
+    for name in ALL_WORLDS + CACHE_WORLDS:
         for it in (10, 3):
             out[name, it] = P.pose_optimize(P.world(name), it)
     return out
+
+
+@pytest.fixture(scope="module")
+def failing():
+    """{world: (result, flags, flags per round, counters)} of the worlds whose solves fail, each under its table."""
+    return {name: P.pose_optimize(P.world(name), 10, P.table_of(name)) for name in FAILING_WORLDS}
 
 
 def _rel(a, b):
@@ -45,7 +59,7 @@ def test_first_step_agrees_with_the_numpy_statement():
     """The pose Jacobian, Huber's weights, the 6x6 system, lambda and the solve against numerically differentiated residuals
     and numpy.linalg.solve of the damped normal equations."""
     worst = 0.0
-    for name in STEP_WORLDS:
+    for name in STEP_WORLDS + CACHE_STEP_WORLDS:
         w = P.world(name)
         a, b = P.first_step(w), P.first_step_numpy(w)
         assert a is not None and a["n"] == len(w.edges()[0]), name
@@ -57,16 +71,17 @@ def test_first_step_agrees_with_the_numpy_statement():
 
 def test_round_three_ends_where_gauss_newton_converges(results):
     """Round 3 has no Huber: its pose against an independent Gauss-Newton over the same edges."""
-    worst = 0.0
-    for name in STEP_WORLDS:
-        w = P.world(name)
-        r, _, per_round, _ = results[name, 10]
-        assert r["rounds"] == 4 and r["iterations"][3] > 0
-        R, t = P.gauss_newton_numpy(w, per_round[2] == 0)
-        d = max(_rel(P.quat_to_matrix(r["q"]), R), _rel(r["t"], t))
-        print(name, "largest relative difference:", d)
-        worst = max(worst, d)
-    assert worst <= 100 * GN_MEASURED
+    for worlds, measured in ((STEP_WORLDS, GN_MEASURED), (CACHE_STEP_WORLDS, GN_MEASURED_CACHE)):
+        worst = 0.0
+        for name in worlds:
+            w = P.world(name)
+            r, _, per_round, _ = results[name, 10]
+            assert r["rounds"] == 4 and r["iterations"][3] > 0
+            R, t = P.gauss_newton_numpy(w, per_round[2] == 0)
+            d = max(_rel(P.quat_to_matrix(r["q"]), R), _rel(r["t"], t))
+            print(name, "largest relative difference:", d)
+            worst = max(worst, d)
+        assert worst <= 100 * measured
 
 
 def test_properties_without_a_tolerance(results):
@@ -85,7 +100,7 @@ def test_properties_without_a_tolerance(results):
 
 
 def test_planted_mismatches_are_flagged_and_nothing_else(results):
-    for name in ("clean", "matched", "far", "truth", "converged", "nine"):
+    for name in ("clean", "matched", "far", "truth", "converged", "nine", "cache_edge", "cache_skewed", "cache_holes"):
         w = P.world(name)
         _, flags, _, _ = results[name, 10]
         assert flags[w.truth["bad"]].all(), name
@@ -97,7 +112,7 @@ def _angle(Ra, Rb):
 
 
 def test_the_pose_moves_towards_the_truth(results):
-    for name in ("clean", "matched", "far", "truth"):
+    for name in ("clean", "matched", "far", "truth") + CACHE_WORLDS:
         w = P.world(name)
         r = results[name, 10][0]
         R0, t0 = w.pose0[:9].reshape(3, 3).astype(np.float64), w.pose0[9:].astype(np.float64)
@@ -159,7 +174,10 @@ def test_the_worlds_run_every_branch(results):
     and by construction hardly reachable: a flag that the stale-error rule decides differently from a recomputation at the
     round's final pose.  A round's last trial is rejected only behind ten rejections in a row or with rho == 0, when lambda has
     grown so far that the rejected step no longer moves an edge's chi2 across 5.991f; the rule is implemented and counted
-    (stale_differs) all the same.  Nor is a failed 6x6 solve reached (solver_failures)."""
+    (stale_differs) all the same.  None of these worlds has a failed 6x6 solve (solver_failures == 0 is asserted over them):
+    that branch is the business of no_weight and weight_lost (test_a_table_of_zeros_fails_every_solve,
+    test_solves_fail_once_every_weighted_edge_is_flagged), and the edges behind k_pose's cache that of the cache_* worlds
+    (test_the_cache_worlds_leave_the_cache), which run here as well."""
     cnt = {k: v[3] for k, v in results.items()}
     res = {k: v[0] for k, v in results.items()}
     assert cnt["clean", 10]["rejected"] > 0 and res["clean", 10]["rejected_trials"] == cnt["clean", 10]["rejected"]
@@ -215,11 +233,111 @@ def test_bad_inputs_are_reported_and_not_followed():
     _returned_as_given(*P.pose_optimize(w)[:2], w, P.NONFINITE)
 
 
-def plane_world(cap=None):
-    w = P.make_world(80, 13, cap=cap, outliers=5, identity_start=True)
-    _, i = _first_edge(w)
+def plane_world(cap=None, n=80, behind_the_cache=False):
+    """A world with one point in the camera's plane: the first edge's, or that of the first edge behind its lane's cache."""
+    w = P.make_world(n, 13, cap=cap, outliers=max(n // 16, 1), identity_start=True)
+    if behind_the_cache:
+        j, i = w.edges()
+        i = int(i[j == P.lane_layout(w)[0][0]][0])
+    else:
+        _, i = _first_edge(w)
     w.points[i, 2] = -w.pose0[11]
     return w
+
+
+def test_a_point_in_the_plane_behind_the_cache_clears_flags_that_were_set():
+    """The NONFINITE end at more than 384 correspondences, its in-plane point on an edge behind the cache: that edge's error is
+    infinite and the sums are NaN from the first linearisation on, so no trial is accepted (a NaN rho ends each iteration behind
+    one trial) and the pose stays at the start, the identity rotation, where round 0's classification flags the edges, those
+    behind the cache included, before the end clears the row."""
+    w = plane_world(P.BIG_CAP, 450, True)
+    behind = P.lane_layout(w)[0]
+    assert len(w.edges()[0]) == 450 and len(behind) >= 450 - 384
+    r, flags, per_round, c = P.pose_optimize(w)
+    _returned_as_given(r, flags, w, P.NONFINITE)
+    assert per_round[:, behind].any(axis=1).all() and per_round[:, behind[0]].all()  # (the in-plane edge: inf > 5.991f)
+    assert c["accepted"] == 0 and c["rejected"] == 10 and c["ended_on_rejected"] == 1
+
+
+def test_the_cache_worlds_leave_the_cache(results):
+    """What the GPU comparison relies on behind k_pose's LDS cache of six edges per lane, from World.edges() alone (feature j is
+    lane j % 64's, in ascending order): which lanes hold more, which edges lie behind the cache, where features without a point
+    sit, and what became of the flags behind the cache."""
+    layout = {name: P.lane_layout(P.world(name)) for name in CACHE_WORLDS}
+    for name in CACHE_WORLDS:
+        w = P.world(name)
+        behind, per_lane, _, _ = layout[name]
+        r = results[name, 10][0]
+        assert w.cap == P.BIG_CAP and per_lane.sum() == len(w.edges()[0]) == r["n_correspondences"]
+        assert (per_lane > P.LANE_CACHE).any() and len(behind) == np.maximum(per_lane - P.LANE_CACHE, 0).sum() > 0, name
+        assert r["status"] == 0 and r["rounds"] == 4 and (r["iterations"] > 0).all(), name
+        assert results[name, 3][0]["status"] == 0 and results[name, 3][0]["rounds"] == 4, name
+    per_lane = layout["cache_edge"][1]
+    assert (per_lane == 6).any() and (per_lane == 7).any() and per_lane.max() == 7
+    assert len(np.intersect1d(layout["cache_edge"][0], P.world("cache_edge").truth["bad"])) > 0
+    per_lane = layout["cache_skewed"][1]
+    assert (per_lane == 0).sum() >= 60 and sorted(per_lane[per_lane > 0]) == [8, 16]
+    assert len(layout["cache_full"][0]) >= 300
+    for name in ("cache_full", "cache_skewed"):
+        flags = results[name, 10][1]
+        assert flags[layout[name][0]].any() and not flags[layout[name][0]].all(), name
+    # behind the cache: flagged behind one round and unflagged behind a later one
+    per_round = results["cache_full", 10][2]
+    back = [int(j) for j in layout["cache_full"][0] if any(per_round[a, j] and not per_round[b, j] for a in range(4) for b in range(a + 1, 4))]
+    print("flagged, then unflagged, behind the cache:", back)
+    assert back
+    assert results["cache_full", 10][3]["ended_on_rejected"] > 0
+    # features without a point in front of a lane's sixth edge and behind its seventh: of each kind
+    w = P.world("cache_holes")
+    _, _, front, rear = layout["cache_holes"]
+    assert front and rear
+    no_point = np.setdiff1d(np.arange(w.n), w.edges()[0])
+    kinds = {lane: set("none" if w.match[j] < 0 else "masked" for j in no_point[no_point % P.WAVE == lane]) for lane in range(P.WAVE)}
+    assert any(kinds[l] == {"none", "masked"} for l in front) and any(kinds[l] == {"none", "masked"} for l in rear)
+    assert len(np.intersect1d(layout["cache_holes"][0], w.truth["bad"])) > 0
+    # the world matched=True plants its unmatched entry the same way: a match to an entry that is no map point
+    m = P.world("matched")
+    assert any(m.match[j] >= 0 and m.mask[m.match[j]] == 0 for j in range(m.n))
+
+
+def test_a_table_of_zeros_fails_every_solve(failing):
+    """Hpp = 0 and lambda = 1e-5 * 0 = 0: the first pivot of every 6x6 solve is not > 0.  Each trial is a failed solve and
+    counts as rejected, ten of them end the round's only iteration (stop reason 1), no feature is flagged and the start pose comes
+    back through its quaternion.  no_weight_big: the same with edges behind the cache."""
+    for name, n in (("no_weight", 200), ("no_weight_big", 700)):
+        w = P.world(name)
+        r, flags, per_round, c = failing[name]
+        assert r["status"] == 0 and r["n_correspondences"] == n and r["rounds"] == 4
+        assert r["solver_failures"] == r["lm_trials"] == r["rejected_trials"] == 40
+        assert list(r["iterations"]) == [1, 1, 1, 1] and list(r["stop_reason"]) == [1, 1, 1, 1]
+        assert r["chi2_initial"] == 0 and r["chi2_final"] == 0 and r["lambda"] == 0 and r["n_bad"] == 0 and r["n_inliers"] == n
+        assert not flags.any() and not per_round.any()
+        assert c == dict(accepted=0, rejected=40, huber_outliers=0, small_theta=0, ended_on_rejected=4, stale_differs=0)
+        assert np.isfinite(r["q"]).all() and np.isfinite(r["t"]).all() and np.isfinite(r["R"]).all()
+        assert r["tcw"].tobytes() == w.pose0[9:].tobytes() and np.abs(r["R"] - w.pose0[:9].reshape(3, 3)).max() <= 4 * 2.0 ** -24
+    assert (P.lane_layout(P.world("no_weight_big"))[1] > P.LANE_CACHE).all()
+
+
+def test_solves_fail_once_every_weighted_edge_is_flagged(failing):
+    """pose_ref_lib.weight_lost_world: round 0 optimises over the level-0 mismatches (accepted trials, Huber's outlier branch)
+    and flags them all; in rounds 1 to 3 only the weightless exact edges are active, so every solve fails -- behind accepted
+    trials and with flags set.  weight_lost_big: the same with edges and flags behind the cache."""
+    for name, gross, exact in (("weight_lost", 100, 20), ("weight_lost_big", 420, 40)):
+        w = P.world(name)
+        r, flags, per_round, c = failing[name]
+        assert r["status"] == 0 and r["n_correspondences"] == gross + exact and r["rounds"] == 4
+        assert 0 < r["solver_failures"] < r["lm_trials"] and c["accepted"] > 0 and r["n_bad"] == gross > 0
+        # where the solves fail: ten in each of rounds 1, 2 and 3, none in round 0
+        assert r["iterations"][0] > 1 and list(r["iterations"][1:]) == [1, 1, 1] and list(r["stop_reason"][1:]) == [1, 1, 1]
+        assert r["solver_failures"] == 30 and r["lm_trials"] == c["accepted"] + c["rejected"] and c["rejected"] >= 30
+        assert c["ended_on_rejected"] >= 3 and c["huber_outliers"] > 0
+        assert flags[w.truth["bad"]].all() and not flags[w.truth["clean"]].any()
+        assert all(np.array_equal(per_round[k], flags) for k in range(4))
+        assert r["chi2_initial"] > 0 and r["chi2_final"] == 0 and r["lambda"] == 0
+        assert all(np.isfinite(r[f]).all() for f in ("q", "t", "R", "tcw", "chi2_initial", "chi2_final", "lambda"))
+        assert abs(float(np.sqrt((r["q"] ** 2).sum())) - 1.0) <= 2.0 ** -52
+    behind = P.lane_layout(P.world("weight_lost_big"))[0]
+    assert len(behind) >= 460 - 384 and failing["weight_lost_big"][1][behind].any() and not failing["weight_lost_big"][1][behind].all()
 
 
 def test_refusals_without_a_context(orbx):
