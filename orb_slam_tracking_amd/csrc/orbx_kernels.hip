@@ -1157,7 +1157,7 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 // K4+K5+K6 fused, patch-local: one wave per keypoint.  The 43x43 raw window (REFLECT_101 at the level's edges) is
 // staged in LDS with dword loads; the 7x7 Gaussian is evaluated only on the 37x37 neighbourhood the 512 rotated
 // sample points can reach, with the same exact fixed-point arithmetic as the whole-level blur, as two banded matrix
-// products on the matrix cores (v_mfma_i32_16x16x64_i8; BlurFrags below), so no blurred pyramid is written or re-read.
+// products on the matrix cores (v_mfma_i32_16x16x32_i8; BlurFrags below), so no blurred pyramid is written or re-read.
 // -------------------------------------------------------------------------------------------------
 #define PW_ROWS 43
 #define PW_WORDS 13    // 52 bytes per staged row: window columns kx-21 .. kx+21 start at byte (kx-21)&3
@@ -1202,7 +1202,7 @@ __device__ const IcTables d_ic = makeIcTables();
 
 // The 512 rotated sample points lie in the disc r^2 + c^2 <= 365 around the keypoint ((13, 13) is the farthest pattern point:
 // 18.38, and rounding moves a point by at most 0.71), not in the whole 37 x 37 square.
-// The 7x7 Gaussian as two integer matrix products on the matrix cores (v_mfma_i32_16x16x64_i8), exact:
+// The 7x7 Gaussian as two integer matrix products on the matrix cores (v_mfma_i32_16x16x32_i8), exact:
 //   H   = (W - 128) G_s + 128      W = the staged window, 48 rows x 48 bytes; G_s[k][c] = T[k - s - c]: the wave's byte shift s
 //                                  lives in the tap matrix, column c of H is blurred column c (x = kx - 18 + c)
 //   Out = V (W G_s) + 32768        V[r][k] = T[k - r]; the blurred byte is bits 16..23 of Out (saturated for the taps that sum to 257)
@@ -1216,6 +1216,14 @@ __device__ const IcTables d_ic = makeIcTables();
 // a banded Toeplitz operand needs two dwords per lane, not a table per tile: dword d of the fragment of tile t holds
 // T[16 (d - t) + 4 q - (lane & 15) - s + b], b = 0 .. 3, which is zero unless d == t (-> W0) or d == t + 1 (-> W1, 16 taps further).
 // V is the same matrix as G_0.  Entry [s][lane] = (W0, W1); a wave reads V's pair and G_s's pair: two 8-byte loads.
+// Round 9: the pair IS the operand.  A product of tile t only needs the k of dwords t and t + 1, so it runs as the K = 32 shape on
+// (dword t, dword t + 1) of the data against (W0, W1) -- the accumulator layout is the same, and no four-dword tuple with two zero
+// dwords is built per tile.  A 64-bit operand is an even-aligned register pair, and the middle dword belongs to the pairs (0, 1)
+// and (1, 2): it is made twice (blurTwin), the pairs are (d0, d1) and (d1', d2).  Tile 2's own pair would be (d2, 0); it runs on
+// (d1', d2) against the SWAPPED taps (W1, W0) instead: d2 meets W0 as it must, and d1' meets W1, which in tile 2 is zero in every
+// lane of the columns (rows, in the vertical product) below 39 -- W1 there holds T[16 + 4 q - (lane & 15) - s + b], non-zero only
+// for lane & 15 >= 10 - s >= 7.  Columns and rows from 37 on are never sampled (the patch is 37 x 37): what d1' adds is not read.
+static_assert(32 + (10 - 3) > 36, "tile 2's swapped-tap product only touches columns / rows past the 37 x 37 patch");
 struct BlurFrags {
   uint32_t w[4][64][2];
 };
@@ -1263,9 +1271,21 @@ __device__ const BlurFrags d_blurFrags1 = makeBlurFrags<1>();
 // the corner tile (rows 32.., columns 32..) of the blurred patch holds no point of the sampling disc and is not computed
 static_assert((32 - 18) * (32 - 18) * 2 > 365, "sampling disc against the corner tile");
 typedef int v4i_t __attribute__((ext_vector_type(4)));
+typedef int v2i_t __attribute__((ext_vector_type(2)));
+// One product of the blur: a 16x16 tile += the operands' two live dwords (v_mfma_i32_16x16x32_i8).
+__device__ __forceinline__ v4i_t blurMfma(const v2i_t a, const v2i_t b, const v4i_t c) {
+  return __builtin_amdgcn_mfma_i32_16x16x32_i8(__builtin_bit_cast(long, a), __builtin_bit_cast(long, b), c, 0, 0, 0);
+}
+// The middle dword of a banded operand belongs to two register pairs (tiles (0, 1) and (1, 2)), and a 64-bit operand is an
+// even-aligned pair, so it exists twice.  Its second instance is made by the instruction that makes the first one, from a source
+// the compiler cannot recognise as the same value: otherwise it folds the two and copies the result (a v_mov per instance).
+__device__ __forceinline__ uint32_t blurTwin(uint32_t v) {
+  asm("" : "+v"(v));
+  return v;
+}
 
 // (second launch bound = 7 waves per SIMD, i.e. at most 72 registers: without it the scheduler spreads the three column tiles'
-// accumulators over 82-92 registers and the kernel drops to 5 waves per SIMD; with it 64-67 registers, no spill)
+// accumulators over 82-92 registers and the kernel drops to 5 waves per SIMD; with it 52-62 registers, no spill)
 template <int GV, bool STAGED = false>
 __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uint8_t* __restrict__ img0, long long img0FrameStride,
                                                        int img0Aligned, const uint8_t* __restrict__ pyr, const Geom g,
@@ -1419,17 +1439,21 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
   const float angle = fast_atan2_deg((float)m01, (float)m10);
   // ---- 7x7 Gaussian on the matrix cores (the comment at BlurFrags has the arithmetic and the k order).
   //      A operand of the horizontal product: row (lane & 15) + 16 t of the window, dwords q, q + 4, q + 8 (q = lane >> 4), as
-  //      signed bytes (pixel - 128); the fourth dword (k = 48 ..) is zero.  They are read before anything overwrites the window. ----
+  //      signed bytes (pixel - 128), in the pairs (q, q + 4) and (q + 4, q + 8).  They are read before anything overwrites the
+  //      window. ----
   const uint2 fg = *reinterpret_cast<const uint2*>(bf.w[s][lane]);
-  v4i_t aw[3];
+  const v2i_t fgP = {(int)fg.x, (int)fg.y}, fgX = {(int)fg.y, (int)fg.x};
+  const v2i_t fvP = {(int)fv.x, (int)fv.y}, fvX = {(int)fv.y, (int)fv.x};
+  v2i_t a01[3], a12[3];
   {
     const uint32_t* ap = raw + (lane & 15) * PW_WORDS + (lane >> 4);
 #pragma unroll
     for (int t = 0; t < 3; t++) {
-      aw[t][0] = (int)(ap[16 * t * PW_WORDS] ^ 0x80808080u);
-      aw[t][1] = (int)(ap[16 * t * PW_WORDS + 4] ^ 0x80808080u);
-      aw[t][2] = (int)(ap[16 * t * PW_WORDS + 8] ^ 0x80808080u);
-      aw[t][3] = 0;
+      const uint32_t m = ap[16 * t * PW_WORDS + 4];
+      a01[t][0] = (int)(ap[16 * t * PW_WORDS] ^ 0x80808080u);
+      a01[t][1] = (int)(m ^ 0x80808080u);
+      a12[t][0] = (int)(blurTwin(m) ^ 0x80808080u);
+      a12[t][1] = (int)(ap[16 * t * PW_WORDS + 8] ^ 0x80808080u);
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1440,29 +1464,33 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
 #pragma unroll
     for (int tn = 0; tn < 3; tn++) {
       // H, columns 16 tn .. + 15: three row tiles; this lane ends up with rows 16 t + 4 q4 + b of column 16 tn + col
-      v4i_t bg = {0, 0, 0, 0};
-      bg[tn] = (int)fg.x; bg[tn + 1] = (int)fg.y;
       v4i_t hh[3];
 #pragma unroll
-      for (int t = 0; t < 3; t++) hh[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[t], bg, v4i_t{128, 128, 128, 128}, 0, 0, 0);
-      // hi = byte 1, lo = byte 0 ^ 0x80 of the four rows of a tile: one operand dword each (4 v_perm_b32 + 1 xor per tile)
-      v4i_t bhi = {0, 0, 0, 0}, blo = {0, 0, 0, 0};
+      for (int t = 0; t < 3; t++)
+        hh[t] = blurMfma(tn == 0 ? a01[t] : a12[t], tn == 2 ? fgX : fgP, v4i_t{128, 128, 128, 128});
+      // hi = byte 1, lo = byte 0 ^ 0x80 of the four rows of a tile: one operand dword each (4 v_perm_b32 + 1 xor per tile; the
+      // middle tile's pair is made twice, once for each operand pair it belongs to)
+      v2i_t h01, h12, l01, l12;
 #pragma unroll
       for (int t = 0; t < 3; t++) {
         const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)hh[t][1], (uint32_t)hh[t][0], 0x04000501u);
         const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)hh[t][3], (uint32_t)hh[t][2], 0x04000501u);
-        bhi[t] = (int)__builtin_amdgcn_perm(x23, x01, 0x05040100u);
-        blo[t] = (int)(__builtin_amdgcn_perm(x23, x01, 0x07060302u) ^ 0x80808080u);
+        const int hi = (int)__builtin_amdgcn_perm(x23, x01, 0x05040100u);
+        const uint32_t lo = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
+        if (t == 0) { h01[0] = hi; l01[0] = (int)(lo ^ 0x80808080u); }
+        if (t == 1) {
+          h01[1] = hi; l01[1] = (int)(lo ^ 0x80808080u);
+          h12[0] = (int)__builtin_amdgcn_perm(blurTwin(x23), x01, 0x05040100u); l12[0] = (int)(blurTwin(lo) ^ 0x80808080u);
+        }
+        if (t == 2) { h12[1] = hi; l12[1] = (int)(lo ^ 0x80808080u); }
       }
       // Out, rows 16 to .. + 15 of these columns; the four rows a lane holds are one dword of the column-major blurred patch
 #pragma unroll
       for (int to = 0; to < 3; to++) {
         if (tn == 2 && to == 2) continue;
-        v4i_t av = {0, 0, 0, 0};
-        av[to] = (int)fv.x;
-        if (to < 2) av[to + 1] = (int)fv.y;   // (to == 2: rows 48 .. do not exist, bhi[3] == blo[3] == 0)
-        const v4i_t oh = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bhi, v4i_t{0, 0, 0, 0}, 0, 0, 0);
-        const v4i_t ol = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, blo, v4i_t{CLO, CLO, CLO, CLO}, 0, 0, 0);
+        const v2i_t av = to == 2 ? fvX : fvP;
+        const v4i_t oh = blurMfma(av, to == 0 ? h01 : h12, v4i_t{0, 0, 0, 0});
+        const v4i_t ol = blurMfma(av, to == 0 ? l01 : l12, v4i_t{CLO, CLO, CLO, CLO});
         uint32_t o[4];
 #pragma unroll
         for (int b = 0; b < 4; b++) {
