@@ -613,8 +613,8 @@ typedef struct orbx_pose_result {
  * problems.  K row-major 3x3 (host, f32); inv_sigma2: host, the context's nlevels floats, NULL = the context's own table;
  * n_iterations >= 0 (10).  Outputs: d_res [n_problems]; d_outlier uint8 [n_problems][capacity]: 1 = feature j is flagged; every
  * entry is written.  One wave of 64 lanes runs a problem's whole optimisation, four problems per workgroup, in one launch.  The
- * call returns once queued, with the exception of orbx_bundle_adjust_batch_device: when the problem list or the table differs from
- * the previous call's on this context, the call first waits for the context stream before it uploads them.
+ * call returns once queued, with the one exception orbx_bundle_adjust_batch_device has: when the problem list or the table differs
+ * from the previous call's on this context, the call first waits for the context stream before it uploads them.
  * ORBX_E_BADARG: null pointers, negative counts, capacity < 1, n_iterations < 0, a frame index outside [0, n_frames), a point set
  * outside [0, n_point_sets); ORBX_E_CAPACITY: capacity >= 2^20; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments -- all
  * checked before anything touches a device.  n_problems == 0 is ORBX_OK. */
@@ -770,7 +770,10 @@ int orbx_bow_transform(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint8_t*
                        double* bow_value, int32_t* bow_n, uint32_t* fv_node, uint32_t* fv_feat, int32_t* fv_n, uint32_t* feat_word);
 /* L1Scoring::score(v1, v2) for pair p = frames h_first[p], h_second[p] (host arrays, each in [0, n_frames), checked before any
  * launch: ORBX_E_BADARG) of the BowVectors transform wrote (d_bow_* with the same capacity); d_score_f64 [n_pairs].
- * Stream-ordered like the transform.  ORBX_E_BADARG for a vocabulary whose scoring is not L1_NORM (deviation 4). */
+ * Stream-ordered like the transform: the call returns once queued, with one exception: when the pair list differs from the previous
+ * call's on this vocabulary, the call first waits for the context stream before it uploads the list (the first call always does); a
+ * caller that scores the same pairs of every batch never waits again.
+ * ORBX_E_BADARG for a vocabulary whose scoring is not L1_NORM (deviation 4). */
 int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n_frames, int n_pairs, const int32_t* h_first,
                                 const int32_t* h_second, const uint32_t* d_bow_word, const double* d_bow_value,
                                 const int32_t* d_bow_n, int capacity, double* d_score_f64);
@@ -879,7 +882,9 @@ int orbx_debug_database_shape(int entries_per_slice, int lists_per_merge);
  * (d_kps: only angle is read; d_desc32, 16-byte aligned; d_n) and orbx_bow_transform_batch_device (d_fv_node / d_fv_feat /
  * d_fv_n) filled, same capacity and layout, so that the three calls chain without a copy.  d_kf_mask (nullable)
  * [n_frames][capacity].  d_matches_f int32 [n_pairs][capacity]: row p's first d_n[h_f[p]] entries, the rest is unspecified;
- * d_nmatches int32 [n_pairs].  Stream-ordered on the context stream like the transform (the call returns once queued).
+ * d_nmatches int32 [n_pairs].  Stream-ordered on the context stream like the transform.  The call returns once queued, with one
+ * exception: when the pair list differs from the previous call's on this context, the call first waits for the context stream
+ * before it uploads the list (the first call always does); a caller that matches the same pairs of every batch never waits again.
  * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, a pair index outside [0, n_frames) -- all checked
  * before anything touches a device; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise
  * well-formed arguments.  n_pairs == 0 is ORBX_OK. */

@@ -17,8 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
+#include "orbx_host.h"
 #include "orbx_knobs.h"
 
 namespace orbx {
@@ -29,44 +28,6 @@ std::atomic<long long> g_knob[KNOB_COUNT] = {
     ORBX_KNOB_LIST(ORBX_KNOB_INIT)
 #undef ORBX_KNOB_INIT
 };
-
-hipError_t launch_resize(hipStream_t st, int nFrames, const uint8_t* src, long long srcFrameStride, int sw, int sh, int sstride,
-                         uint8_t* dst, long long dstFrameStride, int dw, int dh, int dstride, const ResizeTab* xtab,
-                         const ResizeTab* ytab, int dwordPath, int wideFrames);
-hipError_t launch_fast(hipStream_t st, int nFrames, const uint8_t* img0, long long img0FrameStride, int img0Aligned,
-                       const uint8_t* pyr, const Geom& g, uint32_t* cand, int* cellCount, const FastCell* cells, int waveOk,
-                       int* usedWave);
-hipError_t launch_pyramid_tiles(hipStream_t st, int nFrames, const uint8_t* img0, long long img0FrameStride, uint8_t* pyr,
-                                const Geom& g, const PyrTileRect* rects, const PyrTileTap* taps, int nTiles, int buf0Bytes,
-                                int bufBytes);
-hipError_t launch_pyramid_bands(hipStream_t st, int nFrames, const uint8_t* img0, long long img0FrameStride, uint8_t* pyr,
-                                const Geom& g, const ResizeTab* tab, const PyrBands& pb);
-hipError_t launch_describe_patch(hipStream_t st, int nFrames, int maxSel, const uint8_t* img0, long long img0FrameStride,
-                                 int img0Aligned, const uint8_t* pyr, const Geom& g, const SelKp* sel, const int* nsel,
-                                 orbx_keypoint* kps, uint8_t* desc, int capacity, int gaussVariant, int libmFloat,
-                                 const DescStage* staged);
-hipError_t launch_match(hipStream_t st, int nPairs, const int* dFirst, const int* dSecond, const orbx_keypoint* kps,
-                        const uint8_t* desc, const int* nkp, int capacity, orbx_bounds b, int window, float nnratio, int checkOri,
-                        int* matches12, int* nmatches, int* stats, int* scratch, int pair0, int wideMode, int* hostWide,
-                        unsigned int* diag);
-hipError_t launch_octree(hipStream_t st, int nFrames, const uint32_t* cand, const int* cellCount, const OctLaunch& P,
-                         SelKp* selStage, int* nselLevel, uint8_t* scratch, int* maxN, const int* hintL, int force, int* usedInstance);
-hipError_t launch_sel_compact(hipStream_t st, int nFrames, const SelKp* selStage, const int* nselLevel, const OctLaunch& P,
-                              SelKp* sel, int* nsel, int* nselUser, int* hostNsel, int selCap, int* hostErr, int* maxN,
-                              int* hostMaxN);
-size_t octScratchBytes(int nMax, int qMax);
-hipError_t launch_to_gray(hipStream_t st, int nFrames, const uint8_t* src, long long srcFrameStride, int sstride, int w, int h,
-                          int channels, int rgb, uint8_t* dst, long long dstFrameStride, int dstride, int grayVariant);
-hipError_t launch_check_model(hipStream_t st, int nModels, const ScoreArgs& a);
-hipError_t launch_copy_out(hipStream_t st, const CopyOut& c, int nseg, int maxRows);
-hipError_t launch_check_rt(hipStream_t st, int nModels, const CheckRtArgs& a);
-hipError_t launch_init_prep(hipStream_t st, const InitArgs& a);
-hipError_t launch_init_solve(hipStream_t st, const InitArgs& a);
-hipError_t launch_init_select(hipStream_t st, const InitArgs& a);
-hipError_t launch_init_finish(hipStream_t st, const InitArgs& a);
-hipError_t launch_debug_sincos(hipStream_t st, const float* angle, int n, float* c, float* s, int libmFloat);
-hipError_t launch_undistort(hipStream_t st, int nFrames, const orbx_keypoint* in, const int* nkp, int capacity, const CamD& c,
-                            orbx_keypoint* out);
 
 namespace {
 
@@ -193,14 +154,12 @@ struct orbx_ctx {
     int32_t* dNmatches = nullptr;
     int32_t* dStats = nullptr;
   } late[2];
-  std::vector<int32_t> initPairs;  // the pair list of the last orbx_find_models* call (source of its copy)
-  std::vector<int32_t> lastPairs;  // the pair list dPairs holds (first[], second[]): an unchanged list is not copied again
   size_t inBytes = 0;
   int pinFrames = 0;  // frames bufs.hKpsPin / hDescPin hold
   // matcher
   DeviceBuf<int> dMatchScratch;
   DeviceBuf<unsigned int> dMatchDiag;  // orbx_debug_match_counters: [0] blocks of 256 queries listed by k_match_bf_mfma since orbx_create
-  DeviceBuf<int32_t> dPairs;           // the pair list lastPairs holds
+  HeldArray<int32_t> pairs;            // the matcher's pair list (first[], second[]): an unchanged list is not copied again
   // host-array entry points (orbx_match_init, orbx_undistort_keypoints): ONE device block (PairBlock of mCap entries) with a
   // page-locked mirror, so that a pair goes up with one copy command, and page-locked mapped result words the matcher kernels
   // write straight into (no copy commands back)
@@ -210,9 +169,7 @@ struct orbx_ctx {
   PinnedBuf<int> hMo;  // mapped [mCap + 8]: n/a[2], nmatches, stats[3], pad[2], matches12[mCap]
   DeviceBuf<int> dMi;  // n[2] + matches12[cap] + nmatches + stats[3]  (device ints of orbx_undistort_keypoints)
   size_t mCap = 0;
-  DeviceBuf<uint8_t> dScore;      // staging of orbx_check_homography / _fundamental / orbx_check_rt
-  DeviceBuf<uint8_t> dInit;       // arena of orbx_find_models* / orbx_initialize*
-  DeviceBuf<int32_t> dInitPairs;  // their pair list (first[], second[]) as ctx->initPairs holds it
+  InitScratch init;               // the Initializer (orbx_init.cpp)
   DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
   MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
@@ -256,17 +213,6 @@ struct orbx_ctx {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) {                                                                              \
-      char buf_[512];                                                                                    \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      ctx->err = buf_;                                                                                   \
-      return ORBX_E_HIP;                                                                                 \
-    }                                                                                                    \
-  } while (0)
 
 // ORBextractor ctor arithmetic, Features/ORBextractor.cpp:508-594
 void computeTables(orbx_ctx* c) {
@@ -1220,7 +1166,7 @@ int issueMatch(orbx_ctx* ctx, int si, hipStream_t st, int pair0, int n, const Ma
   if (n <= 0) return ORBX_OK;
   StageTimer tm(ctx, ORBX_STAGE_MATCH, si, st);
   const int wide = ctx->wideLaunched[ctx->parity] ? 1 : 0;
-  HIPCHK(launch_match(st, n, ctx->dPairs, ctx->dPairs + m.nPairs, dKps, dDesc, dN, capacity, m.b, m.window, m.nnratio, m.checkOri,
+  HIPCHK(launch_match(st, n, ctx->pairs, ctx->pairs + m.nPairs, dKps, dDesc, dN, capacity, m.b, m.window, m.nnratio, m.checkOri,
                       m.dMatches12, m.dNmatches, m.dStats, ctx->dMatchScratch, pair0, wide, ctx->bufs.hWide.dev() + ctx->parity, ctx->dMatchDiag));
   tm.stop(wide ? 3 : 1);  // k_match_jacobi (+ k_match_wide_lists + k_match_wide_resolve, for pending pairs only)
   return ORBX_OK;
@@ -1249,7 +1195,7 @@ int settleMatch(orbx_ctx* ctx, int parity) {
   if (needed && !ctx->wideLaunched[parity]) {
     HIPCHK(hipStreamSynchronize(ctx->st));
     if (ctx->st2) HIPCHK(hipStreamSynchronize(ctx->st2));
-    HIPCHK(launch_match(ctx->st, L.nPairs, ctx->dPairs, ctx->dPairs + L.nPairs, L.dKps, L.dDesc, L.dN, L.capacity, L.b, L.window,
+    HIPCHK(launch_match(ctx->st, L.nPairs, ctx->pairs, ctx->pairs + L.nPairs, L.dKps, L.dDesc, L.dN, L.capacity, L.b, L.window,
                         L.nnratio, L.checkOri, L.dMatches12, L.dNmatches, L.dStats, ctx->dMatchScratch, 0, 2, ctx->bufs.hWide.dev() + parity, ctx->dMatchDiag));
     HIPCHK(hipStreamSynchronize(ctx->st));
   }
@@ -1262,33 +1208,18 @@ int settleMatch(orbx_ctx* ctx, int parity) {
   return ORBX_OK;
 }
 
-// Pair list (first[], then second[]) -> `dev`.  The copy reads `held`, the context's own copy of the list `dev` holds, which
-// stays put until the next change (the caller's arrays may be gone by the time a stream-ordered call's copy runs).  Trackers
-// match the same pairs batch after batch, so an unchanged list is not copied again.  A changed one first drains what may still
-// read the list `dev` holds: every batch in flight (`waitBatches`) or the context stream.  `*copied`: the copy was queued.
+// The matcher's pair list (first[], then second[]) -> ctx->pairs.  The copy reads the context's own copy of the list, which stays
+// put until the next change (the caller's arrays may be gone by the time a stream-ordered call's copy runs).  Trackers match the
+// same pairs batch after batch, so an unchanged list is not copied again.  A changed one first waits for every batch in flight:
+// they may still read the list the device holds.  `*copied`: the copy was queued.
 int waitAll(orbx_ctx* ctx);
-int uploadPairs(orbx_ctx* ctx, std::vector<int32_t>& held, DeviceBuf<int32_t>& dev, int nPairs, const int32_t* hFirst,
-                const int32_t* hSecond, bool waitBatches, bool* copied = nullptr) {
+int uploadPairs(orbx_ctx* ctx, int nPairs, const int32_t* hFirst, const int32_t* hSecond, bool* copied = nullptr) {
   if (copied) *copied = false;
-  if ((int)held.size() == 2 * nPairs && std::memcmp(held.data(), hFirst, sizeof(int32_t) * nPairs) == 0 &&
-      std::memcmp(held.data() + nPairs, hSecond, sizeof(int32_t) * nPairs) == 0)
-    return ORBX_OK;
-  if (waitBatches) {
-    const int r = waitAll(ctx);
-    if (r != ORBX_OK) return r;
-  } else {
-    HIPCHK(hipStreamSynchronize(ctx->st));
-  }
-  held.clear();  // (until the copy is queued, `dev` holds no list a later call may skip its copy for)
-  HIPCHK(dev.grow(sizeof(int32_t) * 2 * nPairs));
-  held.assign(hFirst, hFirst + nPairs);
-  held.insert(held.end(), hSecond, hSecond + nPairs);
+  if (ctx->pairs.holds(hFirst, nPairs, hSecond, nPairs)) return ORBX_OK;
+  const int r = waitAll(ctx);
+  if (r != ORBX_OK) return r;
   if (copied) *copied = true;
-  if (hipMemcpyAsync(dev, held.data(), sizeof(int32_t) * 2 * nPairs, hipMemcpyHostToDevice, ctx->st) != hipSuccess) {
-    held.clear();
-    ctx->err = "hipMemcpyAsync (pair list)";
-    return ORBX_E_HIP;
-  }
+  HIPCHK(ctx->pairs.replace(ctx->st, hFirst, nPairs, hSecond, nPairs));
   return ORBX_OK;
 }
 
@@ -1389,11 +1320,10 @@ int extractCore(orbx_ctx* ctx, int B, const uint8_t* dImg0, int w, int h, int st
   bool pairsCopied = false;
   if (nPairs > 0) {
     if (capacity >= (1 << 20)) return ORBX_E_BADARG;
-    for (int p = 0; p < nPairs; p++)
-      if (match->hFirst[p] < 0 || match->hFirst[p] >= B || match->hSecond[p] < 0 || match->hSecond[p] >= B) return ORBX_E_BADARG;
+    if (!pairsInRange(match->hFirst, match->hSecond, nPairs, B)) return ORBX_E_BADARG;
     r = ensureMatchScratch(ctx, nPairs, capacity);
     if (r != ORBX_OK) return r;
-    r = uploadPairs(ctx, ctx->lastPairs, ctx->dPairs, nPairs, match->hFirst, match->hSecond, true, &pairsCopied);
+    r = uploadPairs(ctx, nPairs, match->hFirst, match->hSecond, &pairsCopied);
     if (r != ORBX_OK) return r;
     ctx->parity = (int)(ctx->seqIssue & 1u);  // (uploadPairs may have waited)
   }
@@ -1469,7 +1399,7 @@ int extractCore(orbx_ctx* ctx, int B, const uint8_t* dImg0, int w, int h, int st
     ctx->bufs.hFlags[ctx->parity] = 0;
     for (int si = 0; si < 2; si++)
       for (int s2 = 0; s2 < ORBX_STAGE_COUNT; s2++) ctx->used[ctx->parity][si][s2] = false;
-    if (pairsCopied) ctx->lastPairs.clear();
+    if (pairsCopied) ctx->pairs.forget();
     ctx->err = why;
     return r;
   }
@@ -1858,7 +1788,7 @@ int orbx_match_init_batch_device(orbx_ctx* ctx, int n_pairs, const int32_t* h_fi
   ctx->parity = (int)(ctx->seqIssue & 1u);
   r = ensureMatchScratch(ctx, n_pairs, capacity);
   if (r != ORBX_OK) return r;
-  r = uploadPairs(ctx, ctx->lastPairs, ctx->dPairs, n_pairs, h_first, h_second, true);
+  r = uploadPairs(ctx, n_pairs, h_first, h_second);
   if (r != ORBX_OK) return r;
   MatchArgs m;
   m.nPairs = n_pairs; m.b = *bounds; m.window = window_size; m.nnratio = nnratio; m.checkOri = check_orientation;
@@ -2266,384 +2196,6 @@ int orbx_image_bounds(orbx_ctx* ctx, const orbx_camera* cam, int width, int heig
   return ORBX_OK;
 }
 
-// ---- Initializer scoring loops (Initialization/Initializer.cpp:268-438) ---------------------------
-namespace {
-// mvMatches12 (Initializer.cpp:24-33): the matched keypoints of frame 1 in order (first) and their partners (second); false
-// for a partner outside frame 2
-bool compactMatches(const int32_t* matches12, int n1, int n2, std::vector<int32_t>* first, std::vector<int32_t>* second) {
-  for (int i = 0; i < n1; i++)
-    if (matches12[i] >= 0) {
-      if (matches12[i] >= n2) return false;
-      first->push_back(i);
-      second->push_back(matches12[i]);
-    }
-  return true;
-}
-
-int checkModels(orbx_ctx* ctx, int kind, int n_models, const float* M21, const float* M12, const orbx_keypoint* k1, int n1,
-                const orbx_keypoint* k2, int n2, const int32_t* matches12, float sigma, float* scores, uint8_t* inliers,
-                int* n_matches_out, int* best) {
-  if (!ctx || n_models < 0 || n1 < 0 || n2 < 0 || !n_matches_out || (n_models > 0 && (!M21 || (kind == 0 && !M12) || !scores)) ||
-      (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2))
-    return ORBX_E_BADARG;
-  std::vector<int32_t> fs, sc;
-  if (!compactMatches(matches12, n1, n2, &fs, &sc)) return ORBX_E_BADARG;
-  const int N = (int)fs.size();
-  *n_matches_out = N;
-  if (best) *best = -1;
-  if (n_models == 0) return ORBX_OK;
-  if (N > 0 && !inliers) return ORBX_E_BADARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  // the batched form with one pair (frames {0, 0} of k1 / k2: the staged keypoint arrays) and the call's models as its
-  // hypotheses; one staging block: models | keypoints | matches | pair table | scores | inliers
-  ScoreArgs a{};
-  int32_t* table;
-  auto staging = [&](Layout L) {
-    a.M21 = L.take<float>((size_t)n_models * 9);
-    a.M12 = L.take<float>((size_t)n_models * 9);
-    a.k1 = L.take<orbx_keypoint>(n1);
-    a.k2 = L.take<orbx_keypoint>(n2);
-    a.first = L.take<int32_t>(N);
-    a.second = L.take<int32_t>(N);
-    table = L.take<int32_t>(3);  // pairN[1], frames[2]
-    a.scores = L.take<float>(n_models);
-    a.inliers = L.take<uint8_t>((size_t)n_models * N);
-    return L.size();
-  };
-  HIPCHK(ctx->dScore.grow(staging(Layout())));
-  staging(Layout(ctx->dScore));
-  hipStream_t st = ctx->st;
-  const int32_t hTable[3] = {N, 0, 0};
-  a.pairN = table; a.frames = table + 1; a.perPair = n_models; a.stride = N; a.nPairs = 1; a.kind = kind;
-  a.invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
-  const size_t bM = (size_t)n_models * 9 * sizeof(float);
-  HIPCHK(hipMemcpyAsync((void*)a.M21, M21, bM, hipMemcpyHostToDevice, st));
-  if (kind == 0) HIPCHK(hipMemcpyAsync((void*)a.M12, M12, bM, hipMemcpyHostToDevice, st));
-  if (n1) HIPCHK(hipMemcpyAsync((void*)a.k1, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  if (n2) HIPCHK(hipMemcpyAsync((void*)a.k2, k2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  if (N) {
-    HIPCHK(hipMemcpyAsync((void*)a.first, fs.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((void*)a.second, sc.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(hipMemcpyAsync(table, hTable, sizeof hTable, hipMemcpyHostToDevice, st));
-  HIPCHK(launch_check_model(st, n_models, a));
-  HIPCHK(hipMemcpyAsync(scores, a.scores, (size_t)n_models * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (N) HIPCHK(hipMemcpyAsync(inliers, a.inliers, (size_t)n_models * N, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (best) {  // `if (currentScore > score)` with score starting at 0, Initializer.cpp:205-209 / 259-263
-    float sc = 0;
-    for (int m = 0; m < n_models; m++)
-      if (scores[m] > sc) { sc = scores[m]; *best = m; }
-  }
-  return ORBX_OK;
-}
-}  // namespace
-
-int orbx_check_homography(orbx_ctx* ctx, int n_models, const float* H21, const float* H12, const orbx_keypoint* k1, int n1,
-                          const orbx_keypoint* k2, int n2, const int32_t* matches12, float sigma, float* scores, uint8_t* inliers,
-                          int* n_matches_out, int* best) {
-  return checkModels(ctx, 0, n_models, H21, H12, k1, n1, k2, n2, matches12, sigma, scores, inliers, n_matches_out, best);
-}
-
-int orbx_check_fundamental(orbx_ctx* ctx, int n_models, const float* F21, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2,
-                           int n2, const int32_t* matches12, float sigma, float* scores, uint8_t* inliers, int* n_matches_out,
-                           int* best) {
-  return checkModels(ctx, 1, n_models, F21, nullptr, k1, n1, k2, n2, matches12, sigma, scores, inliers, n_matches_out, best);
-}
-
-// ---- Initializer::CheckRT (Initialization/Initializer.cpp:569-713) -------------------------------------
-int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t21, const float* K, const orbx_keypoint* k1, int n1,
-                  const orbx_keypoint* k2, int n2, const int32_t* matches12, const uint8_t* matches_inliers, float th2, int32_t* n_good,
-                  uint8_t* tri_good, float* p3d, float* parallax) {
-  if (!ctx || n_models < 0 || n1 < 0 || n2 < 0 || !K || (n_models > 0 && (!R21 || !t21 || !n_good || !parallax)) ||
-      (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2) || (n_models > 0 && n1 > 0 && (!tri_good || !p3d)))
-    return ORBX_E_BADARG;
-  if (n_models == 0) return ORBX_OK;
-  // mvMatches12, then the inliers in match order (:617-622); the i-th of them is booked under the i-th MATCH's first keypoint
-  // (:643, :700: the reference indexes vMatches12 with the compacted index)
-  std::vector<int32_t> fs, sc;
-  if (!compactMatches(matches12, n1, n2, &fs, &sc)) return ORBX_E_BADARG;
-  const int N = (int)fs.size();
-  if (N > 0 && !matches_inliers) return ORBX_E_BADARG;
-  std::vector<float> pts;
-  std::vector<int32_t> book;
-  for (int m = 0; m < N; m++)
-    if (matches_inliers[m]) {
-      const int i = (int)book.size();
-      book.push_back(fs[i]);
-      pts.push_back(k1[fs[m]].x); pts.push_back(k1[fs[m]].y); pts.push_back(k2[sc[m]].x); pts.push_back(k2[sc[m]].y);
-    }
-  const int nInl = (int)book.size();
-  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  // the batched form with one pair whose n_models candidates are all solutions (stride n1 >= nInl)
-  CheckRtArgs a{};
-  int32_t* table;
-  auto staging = [&](Layout L) {
-    a.R21 = L.take<float>((size_t)n_models * 9);
-    a.t21 = L.take<float>((size_t)n_models * 3);
-    a.pts = L.take<float>((size_t)nInl * 4);
-    a.book = L.take<int32_t>(nInl);
-    table = L.take<int32_t>(2);  // pairNInl[1], pairNSol[1]
-    a.good = L.take<uint8_t>((size_t)n_models * n1);
-    a.p3d = L.take<float>((size_t)n_models * n1 * 3);
-    a.cosBuf = L.take<float>((size_t)n_models * n1);
-    a.nGood = L.take<int32_t>(n_models);
-    a.parallax = L.take<float>(n_models);
-    return L.size();
-  };
-  HIPCHK(ctx->dScore.grow(staging(Layout())));
-  staging(Layout(ctx->dScore));
-  hipStream_t st = ctx->st;
-  const int32_t hTable[2] = {nInl, n_models};
-  for (int i = 0; i < 9; i++) a.K[i] = K[i];
-  a.th2 = th2;
-  a.pairNInl = table; a.pairNSol = table + 1; a.perPair = n_models; a.stride = n1;
-  HIPCHK(hipMemcpyAsync((void*)a.R21, R21, (size_t)n_models * 9 * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync((void*)a.t21, t21, (size_t)n_models * 3 * 4, hipMemcpyHostToDevice, st));
-  if (nInl) {
-    HIPCHK(hipMemcpyAsync((void*)a.pts, pts.data(), (size_t)nInl * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((void*)a.book, book.data(), (size_t)nInl * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(hipMemcpyAsync(table, hTable, sizeof hTable, hipMemcpyHostToDevice, st));
-  HIPCHK(launch_check_rt(st, n_models, a));
-  HIPCHK(hipMemcpyAsync(n_good, a.nGood, (size_t)n_models * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(parallax, a.parallax, (size_t)n_models * 4, hipMemcpyDeviceToHost, st));
-  if (n1) {
-    HIPCHK(hipMemcpyAsync(tri_good, a.good, (size_t)n_models * n1, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(p3d, a.p3d, (size_t)n_models * n1 * 12, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
-}
-
-// ---- the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ----------------------------------
-namespace {
-struct ReconParams {
-  const float* K;
-  float minParallax;
-  int minTriangulated;
-  orbx_init_result* res;
-  float* p3d;
-  uint8_t* tri;
-};
-// findModels' work area over `L`: its arrays into a (the H and F scores and inlier flags into sH / sF, CheckRT's into c) in
-// order; with `recon`, the reconstruction's part follows.  Returns the area's size.
-size_t initWork(Layout L, int nPairs, int nIter, int cap, bool recon, InitArgs& a, ScoreArgs& sH, ScoreArgs& sF, CheckRtArgs& c) {
-  const size_t P = nPairs, H = (size_t)nPairs * nIter, C = cap, M = 4 * P;
-  a.N = L.take<int32_t>(P);
-  a.scoreN = L.take<int32_t>(P);
-  a.pstat = L.take<int32_t>(P);
-  a.first = L.take<int32_t>(P * C);
-  a.second = L.take<int32_t>(P * C);
-  a.H21 = L.take<float>(H * 9);
-  a.H12 = L.take<float>(H * 9);
-  a.F21 = L.take<float>(H * 9);
-  a.flags = L.take<uint8_t>(2 * H);
-  sH.scores = L.take<float>(H);
-  sF.scores = L.take<float>(H);
-  sH.inliers = L.take<uint8_t>(H * C);
-  sF.inliers = L.take<uint8_t>(H * C);
-  a.res = L.take<orbx_hf_result>(P);
-  a.inlOut = L.take<uint8_t>(P * 2 * C);
-  if (recon) {
-    a.R4 = L.take<float>(M * 9);
-    a.t4 = L.take<float>(M * 3);
-    a.nSol = L.take<int32_t>(P);
-    a.nInl = L.take<int32_t>(P);
-    a.pts = L.take<float>(P * C * 4);
-    a.book = L.take<int32_t>(P * C);
-    c.nGood = L.take<int32_t>(M);
-    c.parallax = L.take<float>(M);
-    c.good = L.take<uint8_t>(M * C);
-    c.p3d = L.take<float>(M * C * 3);
-    c.cosBuf = L.take<float>(M * C);
-  }
-  return L.size();
-}
-size_t initWorkSize(int nPairs, int nIter, int cap, bool recon) {
-  InitArgs a{};
-  ScoreArgs sH{}, sF{};
-  CheckRtArgs c{};
-  return initWork(Layout(), nPairs, nIter, cap, recon, a, sH, sF, c);
-}
-// prep -> solve -> score H -> score F -> select, all on the context stream; `work` holds the work area (initWork); d_models /
-// d_scores (nullable) take the hypotheses and their scores in place of the work area's arrays
-int findModels(orbx_ctx* ctx, uint8_t* work, int n_pairs, const int32_t* h_first, const int32_t* h_second, const orbx_keypoint* d_kps,
-               const int32_t* d_n, int cap, const int32_t* d_m12, int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res,
-               uint8_t* d_inliers, float* d_models, float* d_scores, const ReconParams* rc) {
-  hipStream_t st = ctx->st;
-  const size_t H = (size_t)n_pairs * n_iter;
-  int r = uploadPairs(ctx, ctx->initPairs, ctx->dInitPairs, n_pairs, h_first, h_second, false);
-  if (r != ORBX_OK) return r;
-  InitArgs a{};
-  ScoreArgs sH{}, sF{};
-  CheckRtArgs c{};
-  initWork(Layout(work), n_pairs, n_iter, cap, rc != nullptr, a, sH, sF, c);
-  if (d_models) { a.H21 = d_models; a.H12 = d_models + H * 9; a.F21 = d_models + 2 * H * 9; }
-  if (d_scores) { sH.scores = d_scores; sF.scores = d_scores + H; }
-  if (d_res) a.res = d_res;
-  if (d_inliers) a.inlOut = d_inliers;
-  a.scoresH = sH.scores; a.scoresF = sF.scores; a.inlH = sH.inliers; a.inlF = sF.inliers;
-  a.kps = d_kps; a.nKps = d_n; a.m12 = d_m12; a.sets = d_sets; a.frames = ctx->dInitPairs;
-  a.nPairs = n_pairs; a.nIter = n_iter; a.cap = cap;
-  if (rc) {
-    a.reconstruct = 1;
-    for (int i = 0; i < 9; i++) a.K[i] = rc->K[i];
-    a.minParallax = rc->minParallax; a.minTriangulated = rc->minTriangulated;
-    a.nGood = c.nGood; a.parallax = c.parallax; a.good = c.good; a.p3d4 = c.p3d;
-    a.ires = rc->res; a.p3dOut = rc->p3d; a.triOut = rc->tri;
-    c.R21 = a.R4; c.t21 = a.t4; c.pts = a.pts; c.book = a.book;
-    for (int i = 0; i < 9; i++) c.K[i] = rc->K[i];
-    c.th2 = (float)(4.0 * (double)(sigma * sigma));  // `4.0 * mSigma2` (:499), mSigma2 = sigma * sigma (f32)
-    c.pairNInl = a.nInl; c.pairNSol = a.nSol; c.perPair = 4; c.stride = cap;
-  }
-  HIPCHK(launch_init_prep(st, a));
-  HIPCHK(launch_init_solve(st, a));
-  for (ScoreArgs* s : {&sH, &sF}) {
-    s->k1 = d_kps; s->k2 = d_kps; s->first = a.first; s->second = a.second;
-    s->invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
-    s->pairN = a.scoreN; s->frames = a.frames; s->perPair = n_iter; s->stride = cap; s->nPairs = n_pairs;
-  }
-  sH.kind = 0; sH.M21 = a.H21; sH.M12 = a.H12;
-  sF.kind = 1; sF.M21 = a.F21; sF.M12 = nullptr;
-  HIPCHK(launch_check_model(st, (int)H, sH));
-  HIPCHK(launch_check_model(st, (int)H, sF));
-  HIPCHK(launch_init_select(st, a));
-  if (rc) {
-    HIPCHK(launch_check_rt(st, 4 * n_pairs, c));
-    HIPCHK(launch_init_finish(st, a));
-  }
-  return ORBX_OK;
-}
-int checkBatchArgs(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second, const void* d_kps_un,
-                   const void* d_n, int capacity, const void* d_matches12, int n_iter, const void* d_sets, float sigma, const void* d_res) {
-  if (!ctx || n_frames <= 0 || n_pairs <= 0 || !h_first || !h_second || !d_kps_un || !d_n || !d_matches12 || !d_sets || !d_res ||
-      n_iter <= 0 || capacity < 1 || capacity >= (1 << 20) || !(sigma > 0.f))
-    return ORBX_E_BADARG;
-  if ((long long)n_pairs * n_iter >= (1LL << 26)) return ORBX_E_BADARG;
-  for (int p = 0; p < n_pairs; p++)
-    if (h_first[p] < 0 || h_first[p] >= n_frames || h_second[p] < 0 || h_second[p] >= n_frames) {
-      ctx->err = "pair index outside [0, n_frames)";
-      return ORBX_E_BADARG;
-    }
-  return ORBX_OK;
-}
-}  // namespace
-
-int orbx_find_models_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
-                                  const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
-                                  int n_iter, const int32_t* d_sets, float sigma, orbx_hf_result* d_res, uint8_t* d_inliers,
-                                  float* d_models, float* d_scores) {
-  int r = checkBatchArgs(ctx, n_frames, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res);
-  if (r != ORBX_OK) return r;
-  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  r = waitAll(ctx);  // batches issued with the _async calls may still be writing the inputs
-  if (r != ORBX_OK) return r;
-  HIPCHK(ctx->dInit.grow(initWorkSize(n_pairs, n_iter, capacity, false), ctx->st));  // (behind the work that may still use it)
-  return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res,
-                    d_inliers, d_models, d_scores, nullptr);
-}
-
-int orbx_initialize_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_first, const int32_t* h_second,
-                                 const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_matches12,
-                                 int n_iter, const int32_t* d_sets, const float* K, float sigma, float min_parallax,
-                                 int min_triangulated, orbx_init_result* d_res, float* d_p3d, uint8_t* d_triangulated) {
-  int r = checkBatchArgs(ctx, n_frames, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, d_res);
-  if (r != ORBX_OK) return r;
-  if (!K) return ORBX_E_BADARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  r = waitAll(ctx);
-  if (r != ORBX_OK) return r;
-  HIPCHK(ctx->dInit.grow(initWorkSize(n_pairs, n_iter, capacity, true), ctx->st));
-  const ReconParams rc{K, min_parallax, min_triangulated, d_res, d_p3d, d_triangulated};
-  return findModels(ctx, ctx->dInit, n_pairs, h_first, h_second, d_kps_un, d_n, capacity, d_matches12, n_iter, d_sets, sigma, nullptr,
-                    nullptr, nullptr, nullptr, &rc);
-}
-
-namespace {
-// one pair from host memory = frames 0 and 1 of a two-frame batch through the batched path; inputs and outputs live behind the
-// batched stage's work area; synchronous
-int singlePair(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12, int n_iter,
-               const int32_t* sets, float sigma, orbx_hf_result* hres, uint8_t* inliers, float* models, float* scores, const float* K,
-               float min_parallax, int min_triangulated, orbx_init_result* ires, float* p3d, uint8_t* tri) {
-  if (!ctx || n1 < 0 || n2 < 0 || (n1 > 0 && (!k1 || !matches12)) || (n2 > 0 && !k2) || n_iter <= 0 || !sets || !(sigma > 0.f) ||
-      n1 >= (1 << 20) || n2 >= (1 << 20) || n_iter >= (1 << 26) || (!hres && !ires) || (ires && !K))
-    return ORBX_E_BADARG;
-  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
-  int r = waitAll(ctx);
-  if (r != ORBX_OK) return r;
-  const int cap = std::max(std::max(n1, n2), 1);
-  const size_t work = initWorkSize(1, n_iter, cap, ires != nullptr);
-  orbx_keypoint* dK;  // [2][cap]
-  int32_t *dN, *dM, *dS;
-  orbx_hf_result* dR;
-  orbx_init_result* dIR;
-  uint8_t *dI, *dT;
-  float *dMo, *dSo, *dP;
-  auto staging = [&](Layout L) {  // behind the work area
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dS = L.take<int32_t>((size_t)n_iter * 8);
-    dR = L.take<orbx_hf_result>(1);
-    dIR = L.take<orbx_init_result>(1);
-    dI = L.take<uint8_t>((size_t)2 * cap);
-    dMo = L.take<float>((size_t)3 * n_iter * 9);
-    dSo = L.take<float>((size_t)2 * n_iter);
-    dP = L.take<float>((size_t)cap * 3);
-    dT = L.take<uint8_t>(cap);
-    return L.size();
-  };
-  HIPCHK(ctx->dInit.grow(work + staging(Layout()), ctx->st));
-  staging(Layout(ctx->dInit + work));
-  hipStream_t st = ctx->st;
-  const int32_t hn[2] = {n1, n2};
-  if (n1) HIPCHK(hipMemcpyAsync(dK, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  if (n2) HIPCHK(hipMemcpyAsync(dK + cap, k2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dN, hn, sizeof hn, hipMemcpyHostToDevice, st));
-  if (n1) HIPCHK(hipMemcpyAsync(dM, matches12, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dS, sets, (size_t)n_iter * 32, hipMemcpyHostToDevice, st));
-  const int32_t f0 = 0, f1 = 1;
-  if (ires) {
-    const ReconParams rc{K, min_parallax, min_triangulated, dIR, dP, dT};
-    r = findModels(ctx, ctx->dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, nullptr, nullptr, nullptr, nullptr, &rc);
-  } else {
-    r = findModels(ctx, ctx->dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, dR, dI, dMo, dSo, nullptr);
-  }
-  if (r != ORBX_OK) return r;
-  if (ires) {
-    HIPCHK(hipMemcpyAsync(ires, dIR, sizeof(orbx_init_result), hipMemcpyDeviceToHost, st));
-    if (p3d && n1) HIPCHK(hipMemcpyAsync(p3d, dP, (size_t)n1 * 12, hipMemcpyDeviceToHost, st));
-    if (tri && n1) HIPCHK(hipMemcpyAsync(tri, dT, (size_t)n1, hipMemcpyDeviceToHost, st));
-  } else {
-    HIPCHK(hipMemcpyAsync(hres, dR, sizeof(orbx_hf_result), hipMemcpyDeviceToHost, st));
-    if (inliers && n1) {  // [2][n1] from [2][cap]
-      HIPCHK(hipMemcpyAsync(inliers, dI, (size_t)n1, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(inliers + n1, dI + cap, (size_t)n1, hipMemcpyDeviceToHost, st));
-    }
-    if (models) HIPCHK(hipMemcpyAsync(models, dMo, (size_t)3 * n_iter * 36, hipMemcpyDeviceToHost, st));
-    if (scores) HIPCHK(hipMemcpyAsync(scores, dSo, (size_t)2 * n_iter * 4, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
-}
-}  // namespace
-
-int orbx_find_models(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
-                     int n_iter, const int32_t* sets, float sigma, orbx_hf_result* res, uint8_t* inliers, float* models, float* scores) {
-  if (!res) return ORBX_E_BADARG;
-  return singlePair(ctx, k1, n1, k2, n2, matches12, n_iter, sets, sigma, res, inliers, models, scores, nullptr, 0.f, 0, nullptr,
-                    nullptr, nullptr);
-}
-
-int orbx_initialize(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoint* k2, int n2, const int32_t* matches12,
-                    int n_iter, const int32_t* sets, const float* K, float sigma, float min_parallax, int min_triangulated,
-                    orbx_init_result* res, float* p3d, uint8_t* triangulated) {
-  if (!res || !K) return ORBX_E_BADARG;
-  return singlePair(ctx, k1, n1, k2, n2, matches12, n_iter, sets, sigma, nullptr, nullptr, nullptr, nullptr, K, min_parallax,
-                    min_triangulated, res, p3d, triangulated);
-}
-
 // ---- Converter::toGray (Utils/Converter.cpp:5-19) ------------------------------------------------
 int orbx_to_gray_batch_device(orbx_ctx* ctx, int n_frames, const uint8_t* d_src, int width, int height, int stride,
                               size_t frame_stride_bytes, int channels, int rgb, uint8_t* d_gray, int gray_stride,
@@ -2762,10 +2314,6 @@ int orbx_debug_selection_units(orbx_ctx* ctx, int frame, int32_t* counts, int32_
 }  // extern "C"
 
 // ---- device-side test hooks for the selection stage ------------------------------------------------------------
-namespace orbx {
-hipError_t launch_debug_sort(hipStream_t st, int* triples, int n, unsigned long long* a, unsigned long long* b);
-}
-
 extern "C" {
 
 // DistributeOctTree on the device for caller-supplied candidates given in row-major (y, x) order, integer coordinates
@@ -2948,16 +2496,17 @@ int orbx_debug_std_sort(orbx_ctx* ctx, int32_t* triples, int n) {
 
 }  // extern "C"
 
-// ---- what orbx_bow.cpp needs of a context (orbx_ctx is private to this file) ----------------------
+// ---- what the modules in their own files need of a context (orbx_host.h; orbx_ctx is private to this file): orbx_init.cpp,
+// orbx_bow.cpp, orbx_db.cpp, orbx_voc_train.cpp, orbx_match_bow.cpp, orbx_ba.cpp and orbx_pose.cpp ----------------------------
 namespace orbx {
 int ctxDevice(const orbx_ctx* c) { return c->device; }
 hipStream_t ctxStream(const orbx_ctx* c) { return c->st; }
-// the context's device made current and every batch issued with the _async calls waited for (they may still be writing the inputs)
 int ctxDrain(orbx_ctx* c) {
   if (hipSetDevice(c->device) != hipSuccess) return ORBX_E_HIP;
   return waitAll(c);
 }
 void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
+InitScratch* ctxInit(orbx_ctx* c) { return &c->init; }
 MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
 PoseScratch* ctxPose(orbx_ctx* c) { return &c->pose; }

@@ -4,36 +4,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-hipError_t launch_ba(hipStream_t st, const BaArgs& a);
-// orbx_api.cpp
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-BaScratch* ctxBa(orbx_ctx* c);
-const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
 namespace {
-
-#define BACHK(expr)                                                                                    \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      ctxSetError(ctx, buf_);                                                                          \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 constexpr int BA_MAX_CAPACITY = 1 << 20;
 
@@ -49,11 +25,10 @@ int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, co
   if (n_frames < 0 || n_pairs < 0 || capacity < 1 || n_iterations < 0 || (n_pairs > 0 && (!h_first || !h_second)) || !d_kps_un ||
       !d_n || !d_matches12 || !d_init_res || !d_p3d || !d_triangulated || !K || !d_res || !d_p3d_out)
     return ORBX_E_BADARG;
-  for (int p = 0; p < n_pairs; p++)
-    if (h_first[p] < 0 || h_first[p] >= n_frames || h_second[p] < 0 || h_second[p] >= n_frames) {
-      if (ctx) ctxSetError(ctx, "bundle adjust: pair index outside [0, n_frames)");
-      return ORBX_E_BADARG;
-    }
+  if (!pairsInRange(h_first, h_second, n_pairs, n_frames)) {
+    if (ctx) ctxSetError(ctx, "bundle adjust: pair index outside [0, n_frames)");
+    return ORBX_E_BADARG;
+  }
   if (capacity >= BA_MAX_CAPACITY) {
     if (ctx) ctxSetError(ctx, "bundle adjust: capacity of 2^20 or more");
     return ORBX_E_CAPACITY;
@@ -70,26 +45,10 @@ int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, co
   // -- the host copies an earlier upload may still be reading are replaced -- and is the documented exception to "returns once
   // queued" (include/orbx.h); a pipeline that adjusts the same pairs of every batch uploads once
   const float* sig = inv_sigma2 ? inv_sigma2 : table;
-  const bool samePairs = (int)s->hPairs.size() == 2 * n_pairs && std::memcmp(s->hPairs.data(), h_first, (size_t)n_pairs * 4) == 0 &&
-                         std::memcmp(s->hPairs.data() + n_pairs, h_second, (size_t)n_pairs * 4) == 0;
-  const bool sameSigma = (int)s->hSigma.size() == nLevels && std::memcmp(s->hSigma.data(), sig, (size_t)nLevels * 4) == 0;
-  if (!samePairs || !sameSigma) {
-    BACHK(hipStreamSynchronize(st));
-    s->hSigma.clear();
-    s->hPairs.clear();
-    BACHK(s->dSigma.grow((size_t)nLevels * sizeof(float)));
-    BACHK(s->dPairs.grow((size_t)n_pairs * 8));
-    s->hSigma.assign(sig, sig + nLevels);
-    s->hPairs.assign(h_first, h_first + n_pairs);
-    s->hPairs.insert(s->hPairs.end(), h_second, h_second + n_pairs);
-    if (hipMemcpyAsync(s->dSigma, s->hSigma.data(), (size_t)nLevels * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(s->dPairs, s->hPairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
-      s->hSigma.clear();
-      s->hPairs.clear();
-      ctxSetError(ctx, "bundle adjust: hipMemcpyAsync (pair list)");
-      return ORBX_E_HIP;
-    }
-  }
+  const bool samePairs = s->pairs.holds(h_first, n_pairs, h_second, n_pairs), sameSigma = s->sigma.holds(sig, nLevels);
+  if (!samePairs || !sameSigma) HIPCHK(hipStreamSynchronize(st));
+  if (!samePairs) HIPCHK(s->pairs.replace(st, h_first, n_pairs, h_second, n_pairs));
+  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
   BaArgs a{};
   const size_t points = (size_t)n_pairs * (size_t)capacity;
   auto work = [&](Layout L) {
@@ -98,22 +57,19 @@ int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, co
     a.widx = L.take<int32_t>(points);
     return L.size();
   };
-  BACHK(s->dWork.grow(work(Layout()), st));
+  HIPCHK(s->dWork.grow(work(Layout()), st));
   work(Layout(s->dWork));
   a.kps = d_kps_un;
   a.nKps = d_n;
   a.m12 = d_matches12;
-  a.frames = s->dPairs;
+  a.frames = s->pairs;
   a.ires = d_init_res;
   a.p3d = d_p3d;
   a.tri = d_triangulated;
-  a.invSigma2 = s->dSigma;
+  a.invSigma2 = s->sigma;
   a.res = d_res;
   a.p3dOut = d_p3d_out;
-  a.fx = (double)K[0];
-  a.fy = (double)K[4];
-  a.cx = (double)K[2];
-  a.cy = (double)K[5];
+  intrinsics(K, &a.fx, &a.fy, &a.cx, &a.cy);
   a.delta = (double)(float)std::sqrt(5.99);  // `const float thHuber2D = sqrt(5.99)` of the ORB-SLAM design
   a.nPairs = n_pairs;
   a.cap = capacity;
@@ -121,7 +77,7 @@ int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, co
   a.nIterations = n_iterations;
   a.minPoints = min_points;
   a.normalize = normalize != 0;
-  BACHK(launch_ba(st, a));
+  HIPCHK(launch_ba(st, a));
   return ORBX_OK;
 }
 
@@ -159,19 +115,17 @@ int orbx_bundle_adjust(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orb
     return L.size();
   };
   const size_t bytes = staging(Layout());
-  BACHK(s->dIo.grow(bytes, st));
+  HIPCHK(s->dIo.grow(bytes, st));
   staging(Layout(s->dIo));
-  BACHK(hipMemsetAsync(s->dIo, 0, bytes, st));  // (entries beyond n1: no match, not triangulated)
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));  // (entries beyond n1: no match, not triangulated)
   const int32_t hn[2] = {n1, n2};
-  if (n1) {
-    BACHK(hipMemcpyAsync(dK, k1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-    BACHK(hipMemcpyAsync(dM, matches12, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-    BACHK(hipMemcpyAsync(dP, p3d, (size_t)n1 * 12, hipMemcpyHostToDevice, st));
-    BACHK(hipMemcpyAsync(dT, triangulated, (size_t)n1, hipMemcpyHostToDevice, st));
-  }
-  if (n2) BACHK(hipMemcpyAsync(dK + cap, k2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  BACHK(hipMemcpyAsync(dN, hn, sizeof hn, hipMemcpyHostToDevice, st));
-  BACHK(hipMemcpyAsync(dIR, init_res, sizeof(orbx_init_result), hipMemcpyHostToDevice, st));
+  HIPCHK(up(dK, k1, n1, st));
+  HIPCHK(up(dM, matches12, n1, st));
+  HIPCHK(up(dP, p3d, (size_t)n1 * 3, st));
+  HIPCHK(up(dT, triangulated, n1, st));
+  HIPCHK(up(dK + cap, k2, n2, st));
+  HIPCHK(up(dN, hn, 2, st));
+  HIPCHK(up(dIR, init_res, 1, st));
   const int32_t f0 = 0, f1 = 1;
   r = orbx_bundle_adjust_batch_device(ctx, 2, 1, &f0, &f1, dK, dN, cap, dM, dIR, dP, dT, K, inv_sigma2, n_iterations, min_points,
                                       normalize, dR, dP);
@@ -179,9 +133,9 @@ int orbx_bundle_adjust(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orb
     (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
     return r;
   }
-  BACHK(hipMemcpyAsync(res, dR, sizeof(orbx_ba_result), hipMemcpyDeviceToHost, st));
-  if (n1) BACHK(hipMemcpyAsync(p3d_out, dP, (size_t)n1 * 12, hipMemcpyDeviceToHost, st));
-  BACHK(hipStreamSynchronize(st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(down(p3d_out, dP, (size_t)n1 * 3, st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 

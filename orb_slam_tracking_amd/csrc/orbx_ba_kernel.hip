@@ -16,7 +16,7 @@
 #include <cstdint>
 
 #include "../../include/orbx.h"
-#include "orbx_device.h"
+#include "orbx_launch.h"
 
 #define ORBX_BA_FN __device__
 #include "orbx_ba_math.inc"

@@ -13,19 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-hipError_t launch_bow_transform(hipStream_t st, const BowArgs& a);
-hipError_t launch_bow_score_l1(hipStream_t st, const BowScoreArgs& s);
-hipError_t launch_bow_descend(hipStream_t st, const BowArgs& a);
-// orbx_api.cpp
-int ctxDevice(const orbx_ctx* c);
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
@@ -39,8 +27,7 @@ struct orbx_vocabulary {
   // scratch of the calls (grown on demand; the stream is drained before a buffer is replaced)
   DeviceBuf<uint32_t> dScratch;  // fin, nid: [2][frames * capacity]
   DeviceBuf<uint8_t> dIo;        // staging of orbx_bow_transform / orbx_bow_score
-  DeviceBuf<int32_t> dPairs;     // orbx_bow_score_batch_device's pair list [2][n_pairs]
-  std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
+  HeldArray<int32_t> pairs;      // orbx_bow_score_batch_device's pair list [2][n_pairs] of the last call
   // nodes 1..nNodes in file order as they were given (orbx_vocabulary_get_nodes, orbx_vocabulary_save_text)
   std::vector<int32_t> hParent, hLeaf;
   std::vector<uint8_t> hDesc;
@@ -48,17 +35,6 @@ struct orbx_vocabulary {
 };
 
 namespace {
-
-#define BOWCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      if (ctx) ctxSetError(ctx, buf_);                                                                 \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 // the reference's own ranges (:1561-1566)
 bool headerOk(int k, int L, int scoring, int weighting) {
@@ -192,7 +168,7 @@ int transformIssue(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_
                    int levelsup, uint32_t* d_bow_word, double* d_bow_value, int32_t* d_bow_n, uint32_t* d_fv_node,
                    uint32_t* d_fv_feat, int32_t* d_fv_n, uint32_t* d_feat_word) {
   const size_t entries = (size_t)n_frames * capacity;
-  BOWCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));  // fin, nid
+  HIPCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));  // fin, nid
   BowArgs a{};
   a.nodes = v->dNodes;
   a.desc = v->dDesc;
@@ -214,7 +190,7 @@ int transformIssue(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_
   a.fvFeat = d_fv_feat;
   a.fvN = d_fv_n;
   a.featWord = d_feat_word;
-  BOWCHK(launch_bow_transform(ctxStream(ctx), a));
+  HIPCHK(launch_bow_transform(ctxStream(ctx), a));
   return ORBX_OK;
 }
 
@@ -230,15 +206,13 @@ int checkVoc(orbx_ctx* ctx, const orbx_vocabulary* voc) {
 }  // namespace
 
 namespace orbx {
-// orbx_db.cpp: the context a vocabulary was made on
+// what orbx_db.cpp and orbx_voc_train.cpp need of a vocabulary (orbx_host.h)
 orbx_ctx* vocCtx(const orbx_vocabulary* v) { return v->ctx; }
 
-// orbx_voc_train.cpp: the descent alone over a batch; *nodes the vocabulary's breadth-first nodes, *fin [n_frames][capacity] the
-// breadth-first index each feature ends at (the vocabulary's scratch: valid until its next call)
 int vocDescend(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
                const BowNode** nodes, const uint32_t** fin) {
   const size_t entries = (size_t)n_frames * capacity;
-  BOWCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));
+  HIPCHK(v->dScratch.grow(entries * 2 * sizeof(uint32_t), ctxStream(ctx)));
   BowArgs a{};
   a.nodes = v->dNodes;
   a.desc = v->dDesc;
@@ -250,7 +224,7 @@ int vocDescend(orbx_ctx* ctx, orbx_vocabulary* v, int n_frames, const uint8_t* d
   a.nFrames = n_frames;
   a.fin = v->dScratch;
   a.nid = v->dScratch + entries;
-  BOWCHK(launch_bow_descend(ctxStream(ctx), a));
+  HIPCHK(launch_bow_descend(ctxStream(ctx), a));
   *nodes = v->dNodes;
   *fin = v->dScratch;
   return ORBX_OK;
@@ -335,11 +309,11 @@ int orbx_vocabulary_create(orbx_ctx* ctx, int k, int L, int scoring, int weighti
     v->hWeight.assign(weight, weight + n_nodes);
   }
   auto body = [&]() -> int {
-    BOWCHK(hipSetDevice(v->device));
-    BOWCHK(v->dNodes.grow(sizeof(BowNode) * N));
-    BOWCHK(v->dDesc.grow((size_t)32 * N));
-    BOWCHK(hipMemcpy(v->dNodes, nodes.data(), sizeof(BowNode) * N, hipMemcpyHostToDevice));
-    BOWCHK(hipMemcpy(v->dDesc, desc.data(), (size_t)32 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(v->dNodes.grow(sizeof(BowNode) * N));
+    HIPCHK(v->dDesc.grow((size_t)32 * N));
+    HIPCHK(hipMemcpy(v->dNodes, nodes.data(), sizeof(BowNode) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v->dDesc, desc.data(), (size_t)32 * N, hipMemcpyHostToDevice));
     return ORBX_OK;
   };
   const int r = body();
@@ -453,30 +427,26 @@ int orbx_bow_transform(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint8_t*
     dV = L.take<double>(cap);                // bow values
     return L.size();
   };
-  BOWCHK(v->dIo.grow(staging(Layout())));
+  HIPCHK(v->dIo.grow(staging(Layout())));
   staging(Layout(v->dIo));
-  if (n) BOWCHK(hipMemcpyAsync(dD, desc32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-  BOWCHK(hipMemcpyAsync(dN, &n, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dD, desc32, (size_t)n * 32, st));
+  HIPCHK(up(dN, &n, 1, st));
   r = transformIssue(ctx, v, 1, dD, dN, cap, levelsup, dW, dV, dN + 1, fv ? dFn : nullptr, fv ? dFf : nullptr, fv ? dN + 2 : nullptr,
                      feat_word ? dFw : nullptr);
   if (r != ORBX_OK) return r;
   int32_t counts[3] = {0, 0, 0};
-  BOWCHK(hipMemcpyAsync(counts, dN, 12, hipMemcpyDeviceToHost, st));
-  BOWCHK(hipStreamSynchronize(st));
+  HIPCHK(down(counts, dN, 3, st));
+  HIPCHK(hipStreamSynchronize(st));
   *bow_n = counts[1];
-  if (counts[1]) {
-    BOWCHK(hipMemcpyAsync(bow_word, dW, (size_t)counts[1] * 4, hipMemcpyDeviceToHost, st));
-    BOWCHK(hipMemcpyAsync(bow_value, dV, (size_t)counts[1] * 8, hipMemcpyDeviceToHost, st));
-  }
+  HIPCHK(down(bow_word, dW, counts[1], st));
+  HIPCHK(down(bow_value, dV, counts[1], st));
   if (fv) {
     *fv_n = counts[2];
-    if (counts[2]) {
-      BOWCHK(hipMemcpyAsync(fv_node, dFn, (size_t)counts[2] * 4, hipMemcpyDeviceToHost, st));
-      BOWCHK(hipMemcpyAsync(fv_feat, dFf, (size_t)counts[2] * 4, hipMemcpyDeviceToHost, st));
-    }
+    HIPCHK(down(fv_node, dFn, counts[2], st));
+    HIPCHK(down(fv_feat, dFf, counts[2], st));
   }
-  if (feat_word && n) BOWCHK(hipMemcpyAsync(feat_word, dFw, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  BOWCHK(hipStreamSynchronize(st));
+  if (feat_word) HIPCHK(down(feat_word, dFw, n, st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 
@@ -492,29 +462,30 @@ int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n
   if (n_frames < 1 || n_pairs < 0 || capacity < 1 || capacity > ORBX_BOW_MAX_FEATURES || (n_pairs > 0 && (!h_first || !h_second)) ||
       !d_bow_word || !d_bow_value || !d_bow_n || !d_score_f64)
     return ORBX_E_BADARG;
-  for (int p = 0; p < n_pairs; p++)
-    if (h_first[p] < 0 || h_first[p] >= n_frames || h_second[p] < 0 || h_second[p] >= n_frames) {
-      ctxSetError(ctx, "pair index outside [0, n_frames)");
-      return ORBX_E_BADARG;
-    }
+  if (!pairsInRange(h_first, h_second, n_pairs, n_frames)) {
+    ctxSetError(ctx, "pair index outside [0, n_frames)");
+    return ORBX_E_BADARG;
+  }
   if (n_pairs == 0) return ORBX_OK;
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
   hipStream_t st = ctxStream(ctx);
-  BOWCHK(v->dPairs.grow((size_t)n_pairs * 8, st));
-  v->hPairs.assign(h_first, h_first + n_pairs);
-  v->hPairs.insert(v->hPairs.end(), h_second, h_second + n_pairs);
-  BOWCHK(hipMemcpyAsync(v->dPairs, v->hPairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
+  // the pair list goes up only when it differs from the last call's.  Such a call first waits for the context stream -- the host
+  // copy an earlier upload may still be reading is replaced -- and is the documented exception to "returns once queued"
+  if (!v->pairs.holds(h_first, n_pairs, h_second, n_pairs)) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(v->pairs.replace(st, h_first, n_pairs, h_second, n_pairs));
+  }
   BowScoreArgs s{};
   s.word = d_bow_word;
   s.value = d_bow_value;
   s.n = d_bow_n;
   s.cap = capacity;
   s.nPairs = n_pairs;
-  s.pairs = v->dPairs;
+  s.pairs = v->pairs;
   s.score = d_score_f64;
-  BOWCHK(launch_bow_score_l1(st, s));
+  HIPCHK(launch_bow_score_l1(st, s));
   return ORBX_OK;
 }
 
@@ -539,19 +510,19 @@ int orbx_bow_score(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint32_t* w1
     dS = L.take<double>(1);
     return L.size();
   };
-  BOWCHK(v->dIo.grow(staging(Layout())));
+  HIPCHK(v->dIo.grow(staging(Layout())));
   staging(Layout(v->dIo));
   const int32_t hn[2] = {n1, n2};
-  if (n1) BOWCHK(hipMemcpyAsync(dW, w1, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-  if (n2) BOWCHK(hipMemcpyAsync(dW + cap, w2, (size_t)n2 * 4, hipMemcpyHostToDevice, st));
-  if (n1) BOWCHK(hipMemcpyAsync(dV, v1, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
-  if (n2) BOWCHK(hipMemcpyAsync(dV + cap, v2, (size_t)n2 * 8, hipMemcpyHostToDevice, st));
-  BOWCHK(hipMemcpyAsync(dN, hn, 8, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dW, w1, n1, st));
+  HIPCHK(up(dW + cap, w2, n2, st));
+  HIPCHK(up(dV, v1, n1, st));
+  HIPCHK(up(dV + cap, v2, n2, st));
+  HIPCHK(up(dN, hn, 2, st));
   const int32_t f0 = 0, f1 = 1;
   r = orbx_bow_score_batch_device(ctx, voc, 2, 1, &f0, &f1, dW, dV, dN, cap, dS);
   if (r != ORBX_OK) return r;
-  BOWCHK(hipMemcpyAsync(score, dS, 8, hipMemcpyDeviceToHost, st));
-  BOWCHK(hipStreamSynchronize(st));
+  HIPCHK(down(score, dS, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 

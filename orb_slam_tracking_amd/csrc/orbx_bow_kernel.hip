@@ -18,7 +18,7 @@
 #include <cstdint>
 
 #include "orbx_bow_terms.h"
-#include "orbx_device.h"
+#include "orbx_launch.h"
 
 namespace orbx {
 

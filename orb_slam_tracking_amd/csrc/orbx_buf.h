@@ -1,10 +1,13 @@
 // orbx_buf.h — owners of the library's device and page-locked host memory, and the one description of a staging block.
-// orbx_api.cpp, orbx_bow.cpp, orbx_ba.cpp and orbx_pose.cpp allocate and free through these types only.
+// Every host .cpp of the library except orbx_multi.cpp (orbx_api, orbx_init, orbx_bow, orbx_db, orbx_voc_train, orbx_match_bow,
+// orbx_ba, orbx_pose) allocates and frees through these types only.  The scratch structs at the end are what a context keeps for
+// the modules that live in their own .cpp; orbx_host.h declares the accessors.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -128,30 +131,64 @@ class Layout {
   size_t off_ = 0;
 };
 
-// What a context keeps for orbx_match_bow* (orbx_match_bow.cpp; the context owns it, orbx_api.cpp).
+// A device array and the host copy its last upload read.  The copy command reads the host copy when it runs, which may be after
+// the call that queued it has returned, so the copy stays put until the next replace(); and an array that holds() the values a
+// call brings is not uploaded again.  Between "holds() says no" and replace() the caller drains whatever may still read either
+// copy.  Reads as a T* (the device array) wherever one is expected.
+template <class T>
+class HeldArray {
+ public:
+  operator T*() const { return dev_; }
+  // exactly a[0, na) followed by b[0, nb)?  (A pair list is its two columns, one after the other.)
+  bool holds(const T* a, size_t na, const T* b = nullptr, size_t nb = 0) const {
+    return host_.size() == na + nb && (na == 0 || std::memcmp(host_.data(), a, na * sizeof(T)) == 0) &&
+           (nb == 0 || std::memcmp(host_.data() + na, b, nb * sizeof(T)) == 0);
+  }
+  // From the first step to the queued copy the array holds nothing, and again after a copy command that failed: no later call
+  // skips an upload the device never received.
+  hipError_t replace(hipStream_t st, const T* a, size_t na, const T* b = nullptr, size_t nb = 0) {
+    host_.clear();
+    hipError_t e = dev_.grow((na + nb) * sizeof(T));
+    if (e != hipSuccess) return e;
+    host_.assign(a, a + na);
+    host_.insert(host_.end(), b, b + nb);
+    e = hipMemcpyAsync(dev_, host_.data(), host_.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) host_.clear();
+    return e;
+  }
+  void forget() { host_.clear(); }  // (the work the upload was queued with has been abandoned)
+
+ private:
+  DeviceBuf<T> dev_;
+  std::vector<T> host_;
+};
+
+// What a context keeps for the Initializer (orbx_init.cpp).
+struct InitScratch {
+  DeviceBuf<uint8_t> dScore;  // staging of orbx_check_homography / _fundamental / orbx_check_rt
+  DeviceBuf<uint8_t> dInit;   // arena of orbx_find_models* / orbx_initialize*
+  HeldArray<int32_t> pairs;   // their pair list [2][n_pairs]
+};
+
+// What a context keeps for orbx_match_bow* (orbx_match_bow.cpp).
 struct MatchBowScratch {
-  DeviceBuf<int32_t> dPairs;    // the pair list [2][n_pairs] of the last call
-  std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_match_bow
+  HeldArray<int32_t> pairs;  // the pair list [2][n_pairs] of the last call
+  DeviceBuf<uint8_t> dIo;    // staging of orbx_match_bow
 };
 
-// What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp; the context owns it, orbx_api.cpp).
+// What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp).
 struct BaScratch {
-  DeviceBuf<uint8_t> dWork;     // the per-point blocks of every pair: sized from n_pairs x capacity
-  DeviceBuf<int32_t> dPairs;    // the pair list [2][n_pairs] of the last call
-  std::vector<int32_t> hPairs;  // (kept alive behind the asynchronous upload)
-  DeviceBuf<float> dSigma;      // inv_sigma2 of the last call
-  std::vector<float> hSigma;
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_bundle_adjust
+  DeviceBuf<uint8_t> dWork;  // the per-point blocks of every pair: sized from n_pairs x capacity
+  HeldArray<int32_t> pairs;  // the pair list [2][n_pairs] of the last call
+  HeldArray<float> sigma;    // inv_sigma2 of the last call
+  DeviceBuf<uint8_t> dIo;    // staging of orbx_bundle_adjust
 };
 
-// What a context keeps for orbx_pose_optimize* (orbx_pose.cpp; the context owns it, orbx_api.cpp).
+// What a context keeps for orbx_pose_optimize* (orbx_pose.cpp).
 struct PoseScratch {
-  DeviceBuf<int32_t> dProblems;    // the problem list [2][n_problems] of the last call
-  std::vector<int32_t> hProblems;  // (kept alive behind the asynchronous upload)
-  DeviceBuf<float> dSigma;         // inv_sigma2 of the last call
-  std::vector<float> hSigma;
-  DeviceBuf<uint8_t> dIo;          // staging of orbx_pose_optimize
+  HeldArray<int32_t> problems;  // the problem list [2][n_problems] of the last call
+  HeldArray<float> sigma;       // inv_sigma2 of the last call
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_pose_optimize
 };
 
 }  // namespace orbx

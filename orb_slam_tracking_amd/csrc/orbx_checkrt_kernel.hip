@@ -12,7 +12,7 @@
 #include <cstdint>
 
 #include "../../include/orbx.h"
-#include "orbx_device.h"
+#include "orbx_launch.h"
 
 namespace orbx {
 

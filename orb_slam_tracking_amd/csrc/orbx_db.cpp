@@ -8,22 +8,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-hipError_t launch_db_add_count(hipStream_t st, const DbAddArgs& a, uint32_t* tileSum);
-hipError_t launch_db_add_fill(hipStream_t st, const DbAddArgs& a, uint32_t nNew);
-hipError_t launch_db_accumulate(hipStream_t st, const DbQueryArgs& a);
-hipError_t launch_db_merge(hipStream_t st, const DbMergeArgs& a);
-// orbx_api.cpp
-int ctxDevice(const orbx_ctx* c);
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-// orbx_bow.cpp
-orbx_ctx* vocCtx(const orbx_vocabulary* v);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
@@ -48,17 +33,6 @@ struct orbx_database {
 };
 
 namespace {
-
-#define DBCHK(expr)                                                                                    \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      if (ctx) ctxSetError(ctx, buf_);                                                                 \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 // orbx_debug_database_shape
 std::atomic<int> g_perSlice{DB_SLICE_MAX}, g_perMerge{DB_MERGE_MAX};
@@ -137,10 +111,10 @@ int orbx_database_create(orbx_ctx* ctx, const orbx_vocabulary* voc, orbx_databas
   db->nWords = info[5];
   auto body = [&]() -> int {
     const size_t rows = ((size_t)db->nWords + 1) * 4;
-    for (int i = 0; i < 2; i++) DBCHK(db->dRow[i].grow(rows));
-    DBCHK(db->dCnt.grow(rows));
-    DBCHK(db->dTiles.grow(((size_t)db->nWords / DB_SCAN_THREADS + 1) * 4));
-    DBCHK(hipMemsetAsync(db->dRow[0], 0, rows, ctxStream(ctx)));
+    for (int i = 0; i < 2; i++) HIPCHK(db->dRow[i].grow(rows));
+    HIPCHK(db->dCnt.grow(rows));
+    HIPCHK(db->dTiles.grow(((size_t)db->nWords / DB_SCAN_THREADS + 1) * 4));
+    HIPCHK(hipMemsetAsync(db->dRow[0], 0, rows, ctxStream(ctx)));
     return ORBX_OK;
   };
   r = body();
@@ -163,7 +137,7 @@ int orbx_database_clear(orbx_database* db) {
   orbx_ctx* ctx = db->ctx;
   const int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  DBCHK(hipMemsetAsync(db->dRow[db->cur], 0, ((size_t)db->nWords + 1) * 4, ctxStream(ctx)));
+  HIPCHK(hipMemsetAsync(db->dRow[db->cur], 0, ((size_t)db->nWords + 1) * 4, ctxStream(ctx)));
   db->nEntries = 0;
   db->nPost = 0;
   return ORBX_OK;
@@ -203,29 +177,29 @@ int orbx_database_add_batch_device(orbx_ctx* ctx, orbx_database* db, int n_frame
   a.oldValue = db->dValue[cur];
   a.newRow = db->dRow[nxt];
   if (db->nWords > 0) {
-    DBCHK(hipMemsetAsync(db->dCnt, 0, (size_t)db->nWords * 4, st));
-    DBCHK(launch_db_add_count(st, a, db->dTiles));
+    HIPCHK(hipMemsetAsync(db->dCnt, 0, (size_t)db->nWords * 4, st));
+    HIPCHK(launch_db_add_count(st, a, db->dTiles));
     // the file's new length sizes its arrays: one small readback per add, behind which the stream is idle
     uint32_t total = 0;
-    DBCHK(hipMemcpyAsync(&total, db->dRow[nxt] + db->nWords, 4, hipMemcpyDeviceToHost, st));
-    DBCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&total, db->dRow[nxt] + db->nWords, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     const uint32_t nNew = total - db->nPost;
     if (total > 0) {
       const size_t have = db->dEntry[nxt].bytes() / 4;  // grown by half at least, so that a sequence of adds allocates rarely
       const size_t want = total <= have ? have : std::max<size_t>(total, have + have / 2);
-      DBCHK(db->dEntry[nxt].grow(want * 4));
-      DBCHK(db->dValue[nxt].grow(want * 8));
+      HIPCHK(db->dEntry[nxt].grow(want * 4));
+      HIPCHK(db->dValue[nxt].grow(want * 8));
     }
     if (nNew > 0) {
-      DBCHK(db->dTmp.grow((size_t)nNew * 8));
-      DBCHK(db->dTmpValue.grow((size_t)nNew * 8));
+      HIPCHK(db->dTmp.grow((size_t)nNew * 8));
+      HIPCHK(db->dTmpValue.grow((size_t)nNew * 8));
     }
     a.newEntry = db->dEntry[nxt];
     a.newValue = db->dValue[nxt];
     a.tmpWord = db->dTmp;
     a.tmpFrame = db->dTmp + nNew;
     a.tmpValue = db->dTmpValue;
-    DBCHK(launch_db_add_fill(st, a, nNew));
+    HIPCHK(launch_db_add_fill(st, a, nNew));
     db->cur = nxt;
     db->nPost = total;
   }
@@ -251,7 +225,7 @@ int orbx_database_query_batch_device(orbx_ctx* ctx, orbx_database* db, int n_que
   // (int)entry_id < max_id || max_id == -1
   const int limit = max_id == -1 ? db->nEntries : std::min(std::max(max_id, 0), db->nEntries);
   if (limit == 0 || db->nPost == 0) {
-    DBCHK(hipMemsetAsync(d_res_n, 0, (size_t)n_queries * 4, st));
+    HIPCHK(hipMemsetAsync(d_res_n, 0, (size_t)n_queries * 4, st));
     return ORBX_OK;
   }
   const int perSlice = g_perSlice.load(), perMerge = g_perMerge.load(), R = max_results;
@@ -270,7 +244,7 @@ int orbx_database_query_batch_device(orbx_ctx* ctx, orbx_database* db, int n_que
     nB = L.take<int32_t>(listsB);
     return L.size();
   };
-  DBCHK(db->dLists.grow(scratch(Layout()), st));
+  HIPCHK(db->dLists.grow(scratch(Layout()), st));
   scratch(Layout(db->dLists));
   const bool descending = db->scoring == ORBX_BOW_BHATTACHARYYA || db->scoring == ORBX_BOW_DOT_PRODUCT;
   DbQueryArgs a{};
@@ -294,7 +268,7 @@ int orbx_database_query_batch_device(orbx_ctx* ctx, orbx_database* db, int n_que
   a.listRaw = rawA;
   a.listId = idA;
   a.listN = nA;
-  DBCHK(launch_db_accumulate(st, a));
+  HIPCHK(launch_db_accumulate(st, a));
   for (int nIn = nSlices;;) {  // at least one round: the last one writes the results
     DbMergeArgs m{};
     m.nQueries = n_queries;
@@ -316,7 +290,7 @@ int orbx_database_query_batch_device(orbx_ctx* ctx, orbx_database* db, int n_que
       m.outId = idB;
       m.outN = nB;
     }
-    DBCHK(launch_db_merge(st, m));
+    HIPCHK(launch_db_merge(st, m));
     if (m.nOut == 1) break;
     std::swap(rawA, rawB);
     std::swap(idA, idB);
@@ -344,15 +318,15 @@ int orbx_database_add(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, co
     dN = L.take<int32_t>(1);
     return L.size();
   };
-  DBCHK(db->dIo.grow(staging(Layout()), st));
+  HIPCHK(db->dIo.grow(staging(Layout()), st));
   staging(Layout(db->dIo));
   const int32_t hn = n;
-  if (n) DBCHK(hipMemcpyAsync(dW, word, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  if (n) DBCHK(hipMemcpyAsync(dV, value, (size_t)n * 8, hipMemcpyHostToDevice, st));
-  DBCHK(hipMemcpyAsync(dN, &hn, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dW, word, n, st));
+  HIPCHK(up(dV, value, n, st));
+  HIPCHK(up(dN, &hn, 1, st));
   r = orbx_database_add_batch_device(ctx, db, 1, dW, dV, dN, cap, entry_id);
   if (r != ORBX_OK) return r;
-  DBCHK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 
@@ -381,22 +355,22 @@ int orbx_database_query(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, 
     dS = L.take<double>(max_results);
     return L.size();
   };
-  DBCHK(db->dIo.grow(staging(Layout()), st));
+  HIPCHK(db->dIo.grow(staging(Layout()), st));
   staging(Layout(db->dIo));
   const int32_t hn = n;
-  if (n) DBCHK(hipMemcpyAsync(dW, word, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  if (n) DBCHK(hipMemcpyAsync(dV, value, (size_t)n * 8, hipMemcpyHostToDevice, st));
-  DBCHK(hipMemcpyAsync(dN, &hn, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dW, word, n, st));
+  HIPCHK(up(dV, value, n, st));
+  HIPCHK(up(dN, &hn, 1, st));
   r = orbx_database_query_batch_device(ctx, db, 1, dW, dV, dN, cap, max_results, max_id, dE, dS, dN + 1);
   if (r != ORBX_OK) return r;
   int32_t got = 0;
-  DBCHK(hipMemcpyAsync(&got, dN + 1, 4, hipMemcpyDeviceToHost, st));
-  DBCHK(hipStreamSynchronize(st));
+  HIPCHK(down(&got, dN + 1, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
   *res_n = got;
   if (got) {
-    DBCHK(hipMemcpyAsync(res_entry, dE, (size_t)got * 4, hipMemcpyDeviceToHost, st));
-    DBCHK(hipMemcpyAsync(res_score, dS, (size_t)got * 8, hipMemcpyDeviceToHost, st));
-    DBCHK(hipStreamSynchronize(st));
+    HIPCHK(down(res_entry, dE, got, st));
+    HIPCHK(down(res_score, dS, got, st));
+    HIPCHK(hipStreamSynchronize(st));
   }
   return ORBX_OK;
 }
@@ -411,12 +385,12 @@ int64_t orbx_database_get_inverted_file(orbx_database* db, uint32_t* row_start, 
   const int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
   hipStream_t st = ctxStream(ctx);
-  DBCHK(hipMemcpyAsync(row_start, db->dRow[db->cur], ((size_t)db->nWords + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(row_start, db->dRow[db->cur], ((size_t)db->nWords + 1) * 4, hipMemcpyDeviceToHost, st));
   if (db->nPost) {
-    DBCHK(hipMemcpyAsync(post_entry, db->dEntry[db->cur], (size_t)db->nPost * 4, hipMemcpyDeviceToHost, st));
-    DBCHK(hipMemcpyAsync(post_value, db->dValue[db->cur], (size_t)db->nPost * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(post_entry, db->dEntry[db->cur], (size_t)db->nPost * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(post_value, db->dValue[db->cur], (size_t)db->nPost * 8, hipMemcpyDeviceToHost, st));
   }
-  DBCHK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   return (int64_t)db->nPost;
 }
 

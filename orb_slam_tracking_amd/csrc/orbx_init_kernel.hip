@@ -18,7 +18,7 @@
 #include <cstdint>
 
 #include "../../include/orbx.h"
-#include "orbx_device.h"
+#include "orbx_launch.h"
 
 #define ORBX_DECOMP_FN __device__
 #include "orbx_init_decomp.inc"

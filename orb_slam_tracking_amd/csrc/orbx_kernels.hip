@@ -30,7 +30,7 @@
 #include <type_traits>
 
 #include "../../include/orbx.h"
-#include "orbx_device.h"
+#include "orbx_launch.h"
 #include "orbx_knobs.h"
 
 namespace orbx {

@@ -3,35 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-hipError_t launch_match_bow(hipStream_t st, const MatchBowArgs& a);
-// orbx_api.cpp
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-MatchBowScratch* ctxMatchBow(orbx_ctx* c);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
 namespace {
-
-#define MBCHK(expr)                                                                                    \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      ctxSetError(ctx, buf_);                                                                          \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 // a FeatureVector in host memory: every feature index below the frame's count
 bool featuresOk(const uint32_t* feat, int fvN, int n) {
@@ -51,11 +28,10 @@ int orbx_match_bow_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   if (n_frames < 0 || n_pairs < 0 || capacity < 1 || (n_pairs > 0 && (!h_kf || !h_f)) || !d_kps || !d_desc32 || !d_n || !d_fv_node ||
       !d_fv_feat || !d_fv_n || !d_matches_f || !d_nmatches)
     return ORBX_E_BADARG;
-  for (int p = 0; p < n_pairs; p++)
-    if (h_kf[p] < 0 || h_kf[p] >= n_frames || h_f[p] < 0 || h_f[p] >= n_frames) {
-      if (ctx) ctxSetError(ctx, "match bow: pair index outside [0, n_frames)");
-      return ORBX_E_BADARG;
-    }
+  if (!pairsInRange(h_kf, h_f, n_pairs, n_frames)) {
+    if (ctx) ctxSetError(ctx, "match bow: pair index outside [0, n_frames)");
+    return ORBX_E_BADARG;
+  }
   if (capacity > ORBX_BOW_MAX_FEATURES) {
     if (ctx) ctxSetError(ctx, "match bow: capacity above ORBX_BOW_MAX_FEATURES");
     return ORBX_E_CAPACITY;
@@ -66,10 +42,12 @@ int orbx_match_bow_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   if (r != ORBX_OK) return r;
   MatchBowScratch* s = ctxMatchBow(ctx);
   hipStream_t st = ctxStream(ctx);
-  MBCHK(s->dPairs.grow((size_t)n_pairs * 8, st));
-  s->hPairs.assign(h_kf, h_kf + n_pairs);
-  s->hPairs.insert(s->hPairs.end(), h_f, h_f + n_pairs);
-  MBCHK(hipMemcpyAsync(s->dPairs, s->hPairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
+  // the pair list goes up only when it differs from the last call's.  Such a call first waits for the context stream -- the host
+  // copy an earlier upload may still be reading is replaced -- and is the documented exception to "returns once queued"
+  if (!s->pairs.holds(h_kf, n_pairs, h_f, n_pairs)) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(s->pairs.replace(st, h_kf, n_pairs, h_f, n_pairs));
+  }
   MatchBowArgs a{};
   a.kps = d_kps;
   a.desc = d_desc32;
@@ -78,14 +56,14 @@ int orbx_match_bow_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   a.fvFeat = d_fv_feat;
   a.fvN = d_fv_n;
   a.mask = d_kf_mask;
-  a.pairs = s->dPairs;
+  a.pairs = s->pairs;
   a.cap = capacity;
   a.nPairs = n_pairs;
   a.checkOri = check_orientation != 0;
   a.nnratio = nnratio;
   a.matchesF = d_matches_f;
   a.nmatches = d_nmatches;
-  MBCHK(launch_match_bow(st, a));
+  HIPCHK(launch_match_bow(st, a));
   return ORBX_OK;
 }
 
@@ -125,35 +103,27 @@ int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf
     dM = L.take<int32_t>(cap);
     return L.size();
   };
-  MBCHK(s->dIo.grow(staging(Layout()), st));
+  HIPCHK(s->dIo.grow(staging(Layout()), st));
   staging(Layout(s->dIo));
   const size_t c = (size_t)cap;
-  if (kf_n) {
-    MBCHK(hipMemcpyAsync(dK, kf_kps, (size_t)kf_n * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-    MBCHK(hipMemcpyAsync(dD, kf_desc32, (size_t)kf_n * 32, hipMemcpyHostToDevice, st));
-    if (kf_mask) MBCHK(hipMemcpyAsync(dMask, kf_mask, (size_t)kf_n, hipMemcpyHostToDevice, st));
-  }
-  if (f_n) {
-    MBCHK(hipMemcpyAsync(dK + c, f_kps, (size_t)f_n * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-    MBCHK(hipMemcpyAsync(dD + c * 32, f_desc32, (size_t)f_n * 32, hipMemcpyHostToDevice, st));
-  }
-  if (kf_fv_n) {
-    MBCHK(hipMemcpyAsync(dNode, kf_fv_node, (size_t)kf_fv_n * 4, hipMemcpyHostToDevice, st));
-    MBCHK(hipMemcpyAsync(dFeat, kf_fv_feat, (size_t)kf_fv_n * 4, hipMemcpyHostToDevice, st));
-  }
-  if (f_fv_n) {
-    MBCHK(hipMemcpyAsync(dNode + c, f_fv_node, (size_t)f_fv_n * 4, hipMemcpyHostToDevice, st));
-    MBCHK(hipMemcpyAsync(dFeat + c, f_fv_feat, (size_t)f_fv_n * 4, hipMemcpyHostToDevice, st));
-  }
+  HIPCHK(up(dK, kf_kps, kf_n, st));
+  HIPCHK(up(dD, kf_desc32, (size_t)kf_n * 32, st));
+  if (kf_mask) HIPCHK(up(dMask, kf_mask, kf_n, st));
+  HIPCHK(up(dK + c, f_kps, f_n, st));
+  HIPCHK(up(dD + c * 32, f_desc32, (size_t)f_n * 32, st));
+  HIPCHK(up(dNode, kf_fv_node, kf_fv_n, st));
+  HIPCHK(up(dFeat, kf_fv_feat, kf_fv_n, st));
+  HIPCHK(up(dNode + c, f_fv_node, f_fv_n, st));
+  HIPCHK(up(dFeat + c, f_fv_feat, f_fv_n, st));
   const int32_t hn[4] = {kf_n, f_n, kf_fv_n, f_fv_n};
-  MBCHK(hipMemcpyAsync(dN, hn, sizeof hn, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dN, hn, 4, st));
   const int32_t kf = 0, f = 1;
   r = orbx_match_bow_batch_device(ctx, 2, 1, &kf, &f, dK, dD, dN, cap, dNode, dFeat, dN + 2, kf_mask ? dMask : nullptr, nnratio,
                                   check_orientation, dM, dN + 4);
   if (r != ORBX_OK) return r;
-  if (f_n) MBCHK(hipMemcpyAsync(matches_f, dM, (size_t)f_n * 4, hipMemcpyDeviceToHost, st));
-  MBCHK(hipMemcpyAsync(nmatches, dN + 4, 4, hipMemcpyDeviceToHost, st));
-  MBCHK(hipStreamSynchronize(st));
+  HIPCHK(down(matches_f, dM, f_n, st));
+  HIPCHK(down(nmatches, dN + 4, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 

@@ -7,7 +7,7 @@
 // frame features over its lanes.  Integer arithmetic apart from the ratio test and the rotation bin; no float atomics.
 #include <hip/hip_runtime.h>
 
-#include "orbx_device.h"
+#include "orbx_launch.h"
 #include "orbx_match_hist.h"
 
 namespace orbx {

@@ -4,36 +4,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-hipError_t launch_pose(hipStream_t st, const PoseArgs& a);
-// orbx_api.cpp
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-PoseScratch* ctxPose(orbx_ctx* c);
-const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
 namespace {
-
-#define POSECHK(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      ctxSetError(ctx, buf_);                                                                          \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 constexpr int POSE_MAX_CAPACITY = 1 << 20;
 
@@ -49,11 +25,10 @@ int orbx_pose_optimize_batch_device(orbx_ctx* ctx, int n_frames, int n_problems,
   if (n_frames < 0 || n_problems < 0 || n_point_sets < 0 || capacity < 1 || n_iterations < 0 ||
       (n_problems > 0 && (!h_frame || !h_point_set)) || !d_kps_un || !d_n || !d_points || !d_pose0 || !K || !d_res || !d_outlier)
     return ORBX_E_BADARG;
-  for (int p = 0; p < n_problems; p++)
-    if (h_frame[p] < 0 || h_frame[p] >= n_frames || h_point_set[p] < 0 || h_point_set[p] >= n_point_sets) {
-      if (ctx) ctxSetError(ctx, "pose optimize: frame outside [0, n_frames) or point set outside [0, n_point_sets)");
-      return ORBX_E_BADARG;
-    }
+  if (!pairsInRange(h_frame, h_point_set, n_problems, n_frames, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "pose optimize: frame outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
   if (capacity >= POSE_MAX_CAPACITY) {
     if (ctx) ctxSetError(ctx, "pose optimize: capacity of 2^20 or more");
     return ORBX_E_CAPACITY;
@@ -70,48 +45,28 @@ int orbx_pose_optimize_batch_device(orbx_ctx* ctx, int n_frames, int n_problems,
   // stream -- the host copies an earlier upload may still be reading are replaced -- and is the documented exception to "returns
   // once queued" (include/orbx.h)
   const float* sig = inv_sigma2 ? inv_sigma2 : table;
-  const bool sameList = (int)s->hProblems.size() == 2 * n_problems &&
-                        std::memcmp(s->hProblems.data(), h_frame, (size_t)n_problems * 4) == 0 &&
-                        std::memcmp(s->hProblems.data() + n_problems, h_point_set, (size_t)n_problems * 4) == 0;
-  const bool sameSigma = (int)s->hSigma.size() == nLevels && std::memcmp(s->hSigma.data(), sig, (size_t)nLevels * 4) == 0;
-  if (!sameList || !sameSigma) {
-    POSECHK(hipStreamSynchronize(st));
-    s->hSigma.clear();
-    s->hProblems.clear();
-    POSECHK(s->dSigma.grow((size_t)nLevels * sizeof(float)));
-    POSECHK(s->dProblems.grow((size_t)n_problems * 8));
-    s->hSigma.assign(sig, sig + nLevels);
-    s->hProblems.assign(h_frame, h_frame + n_problems);
-    s->hProblems.insert(s->hProblems.end(), h_point_set, h_point_set + n_problems);
-    if (hipMemcpyAsync(s->dSigma, s->hSigma.data(), (size_t)nLevels * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(s->dProblems, s->hProblems.data(), (size_t)n_problems * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
-      s->hSigma.clear();
-      s->hProblems.clear();
-      ctxSetError(ctx, "pose optimize: hipMemcpyAsync (problem list)");
-      return ORBX_E_HIP;
-    }
-  }
+  const bool sameList = s->problems.holds(h_frame, n_problems, h_point_set, n_problems), sameSigma = s->sigma.holds(sig, nLevels);
+  if (!sameList || !sameSigma) HIPCHK(hipStreamSynchronize(st));
+  if (!sameList) HIPCHK(s->problems.replace(st, h_frame, n_problems, h_point_set, n_problems));
+  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
   PoseArgs a{};
   a.kps = d_kps_un;
   a.nKps = d_n;
-  a.problems = s->dProblems;
+  a.problems = s->problems;
   a.match = d_match;
   a.points = d_points;
   a.mask = d_point_mask;
   a.pose0 = d_pose0;
-  a.invSigma2 = s->dSigma;
+  a.invSigma2 = s->sigma;
   a.res = d_res;
   a.outlier = d_outlier;
-  a.fx = (double)K[0];
-  a.fy = (double)K[4];
-  a.cx = (double)K[2];
-  a.cy = (double)K[5];
+  intrinsics(K, &a.fx, &a.fy, &a.cx, &a.cy);
   a.delta = (double)(float)std::sqrt(5.991);  // `const float deltaMono = sqrt(5.991)` of the ORB-SLAM2 design
   a.nProblems = n_problems;
   a.cap = capacity;
   a.nLevels = nLevels;
   a.nIterations = n_iterations;
-  POSECHK(launch_pose(st, a));
+  HIPCHK(launch_pose(st, a));
   return ORBX_OK;
 }
 
@@ -145,26 +100,24 @@ int orbx_pose_optimize(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const 
     return L.size();
   };
   const size_t bytes = staging(Layout());
-  POSECHK(s->dIo.grow(bytes, st));
+  HIPCHK(s->dIo.grow(bytes, st));
   staging(Layout(s->dIo));
-  POSECHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
   const int32_t hn = n, zero = 0;
-  if (n) {
-    POSECHK(hipMemcpyAsync(dK, kps_un, (size_t)n * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-    POSECHK(hipMemcpyAsync(dP, points, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    if (mask) POSECHK(hipMemcpyAsync(dM, mask, (size_t)n, hipMemcpyHostToDevice, st));
-  }
-  POSECHK(hipMemcpyAsync(dN, &hn, sizeof hn, hipMemcpyHostToDevice, st));
-  POSECHK(hipMemcpyAsync(dPose, pose0, 48, hipMemcpyHostToDevice, st));
+  HIPCHK(up(dK, kps_un, n, st));
+  HIPCHK(up(dP, points, (size_t)n * 3, st));
+  if (mask) HIPCHK(up(dM, mask, n, st));
+  HIPCHK(up(dN, &hn, 1, st));
+  HIPCHK(up(dPose, pose0, 12, st));
   r = orbx_pose_optimize_batch_device(ctx, 1, 1, &zero, &zero, dK, dN, cap, nullptr, 1, dP, mask ? dM : nullptr, dPose, K, inv_sigma2,
                                       n_iterations, dR, dO);
   if (r != ORBX_OK) {
     (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
     return r;
   }
-  POSECHK(hipMemcpyAsync(res, dR, sizeof(orbx_pose_result), hipMemcpyDeviceToHost, st));
-  if (n) POSECHK(hipMemcpyAsync(outlier, dO, (size_t)n, hipMemcpyDeviceToHost, st));
-  POSECHK(hipStreamSynchronize(st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(down(outlier, dO, n, st));
+  HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
 

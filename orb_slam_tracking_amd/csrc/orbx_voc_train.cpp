@@ -12,34 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "orbx_buf.h"
-#include "orbx_device.h"
-
-namespace orbx {
-// orbx_voc_train_kernel.hip
-hipError_t vtLaunchPermInit(hipStream_t st, const int32_t* n, const int32_t* docOff, int cap, int nDocs, uint32_t* perm);
-hipError_t vtLaunchSeedSmall(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchSeedFirst(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchSeedUpdate(hipStream_t st, const VtArgs& a, int c);
-hipError_t vtLaunchSeedPick(hipStream_t st, const VtArgs& a, int c);
-hipError_t vtLaunchAssign(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchRound(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchCount(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchCentreFinal(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchHist(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchScan(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchScatter(hipStream_t st, const VtArgs& a);
-hipError_t vtLaunchDocFreq(hipStream_t st, const BowNode* nodes, const uint32_t* fin, const int32_t* n, int cap, int nDocs,
-                           uint32_t* featWord, uint32_t* Ni);
-// orbx_bow.cpp
-int vocDescend(orbx_ctx* ctx, orbx_vocabulary* voc, int n_frames, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
-               const BowNode** nodes, const uint32_t** fin);
-// orbx_api.cpp
-int ctxDevice(const orbx_ctx* c);
-hipStream_t ctxStream(const orbx_ctx* c);
-int ctxDrain(orbx_ctx* c);
-void ctxSetError(orbx_ctx* c, const char* msg);
-}  // namespace orbx
+#include "orbx_host.h"
 
 using namespace orbx;
 
@@ -47,17 +20,6 @@ namespace {
 
 // nodes with more features than this are seeded by the grid-wide kernels (orbx_debug_voc_train_seed_grid_min; at most VT_SEED_LDS)
 std::atomic<long long> g_seedGridMin{VT_SEED_LDS};
-
-#define VTCHK(expr)                                                                                    \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      char buf_[512];                                                                                  \
-      snprintf(buf_, sizeof buf_, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      ctxSetError(ctx, buf_);                                                                          \
-      return ORBX_E_HIP;                                                                               \
-    }                                                                                                  \
-  } while (0)
 
 int checkHeader(int k, int L, int scoring, int weighting) {
   return k >= 2 && k <= VT_KMAX && L >= 1 && L <= 10 && scoring >= 0 && scoring <= 5 && weighting >= 0 && weighting <= 3;
@@ -113,14 +75,14 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  VTCHK(hipSetDevice(ctxDevice(ctx)));
+  HIPCHK(hipSetDevice(ctxDevice(ctx)));
   hipStream_t st = ctxStream(ctx);
   int32_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 
   // getFeatures: the documents' features in order
   std::vector<int32_t> hn((size_t)n_docs), docOff((size_t)n_docs);
-  if (n_docs) VTCHK(hipMemcpyAsync(hn.data(), d_n, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st));
-  VTCHK(hipStreamSynchronize(st));
+  if (n_docs) HIPCHK(hipMemcpyAsync(hn.data(), d_n, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   long long total = 0;
   for (int f = 0; f < n_docs; f++) {
     docOff[f] = (int32_t)total;
@@ -135,14 +97,14 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
     DeviceBuf<uint32_t> dPermA, dPermB, dCentres, dBlkSum, dGCnt;
     DeviceBuf<uint8_t> dAssoc;
     DeviceBuf<VtNode> dNodes;
-    VTCHK(upload(dDocOff, docOff, st));
-    VTCHK(dPermA.grow((size_t)N * 4));
-    VTCHK(dPermB.grow((size_t)N * 4));
-    VTCHK(dAssoc.grow((size_t)N));
-    VTCHK(dMinDist.grow((size_t)N * 4));
-    VTCHK(dStats.grow(sizeof stats));
-    VTCHK(hipMemsetAsync(dStats, 0, sizeof stats, st));
-    VTCHK(vtLaunchPermInit(st, d_n, dDocOff, capacity, n_docs, dPermA));
+    HIPCHK(upload(dDocOff, docOff, st));
+    HIPCHK(dPermA.grow((size_t)N * 4));
+    HIPCHK(dPermB.grow((size_t)N * 4));
+    HIPCHK(dAssoc.grow((size_t)N));
+    HIPCHK(dMinDist.grow((size_t)N * 4));
+    HIPCHK(dStats.grow(sizeof stats));
+    HIPCHK(hipMemsetAsync(dStats, 0, sizeof stats, st));
+    HIPCHK(vtLaunchPermInit(st, d_n, dDocOff, capacity, n_docs, dPermA));
     uint32_t *perm = dPermA, *permOut = dPermB;
     const long long gridMin = g_seedGridMin.load();
 
@@ -192,23 +154,23 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
       lists.insert(lists.end(), large.begin(), large.end());
       lists.insert(lists.end(), multi.begin(), multi.end());
       const int nBlk = (int)blkNode.size();
-      VTCHK(upload(dNodes, hNodes, st));
-      VTCHK(upload(dBlkNode, blkNode, st));
-      VTCHK(upload(dBlkStart, blkStart, st));
-      VTCHK(upload(dChNode, chNode, st));
-      VTCHK(upload(dChStart, chStart, st));
-      VTCHK(upload(dList, lists, st));
-      VTCHK(dCentres.grow((size_t)nNodes * k * 32, st));
-      VTCHK(dBlkSum.grow((size_t)nBlk * 4, st));
-      VTCHK(dBlkHist.grow((size_t)nBlk * k * 4, st));
-      VTCHK(dNodeHist.grow((size_t)nNodes * k * 4, st));
-      VTCHK(dChildBase.grow((size_t)nNodes * k * 4, st));
+      HIPCHK(upload(dNodes, hNodes, st));
+      HIPCHK(upload(dBlkNode, blkNode, st));
+      HIPCHK(upload(dBlkStart, blkStart, st));
+      HIPCHK(upload(dChNode, chNode, st));
+      HIPCHK(upload(dChStart, chStart, st));
+      HIPCHK(upload(dList, lists, st));
+      HIPCHK(dCentres.grow((size_t)nNodes * k * 32, st));
+      HIPCHK(dBlkSum.grow((size_t)nBlk * 4, st));
+      HIPCHK(dBlkHist.grow((size_t)nBlk * k * 4, st));
+      HIPCHK(dNodeHist.grow((size_t)nNodes * k * 4, st));
+      HIPCHK(dChildBase.grow((size_t)nNodes * k * 4, st));
       if (nMulti) {
         const size_t bytes = (size_t)nMulti * k * (VT_THREADS + 1) * 4;
-        VTCHK(dGCnt.grow(bytes, st));
-        VTCHK(hipMemsetAsync(dGCnt, 0, bytes, st));
+        HIPCHK(dGCnt.grow(bytes, st));
+        HIPCHK(hipMemsetAsync(dGCnt, 0, bytes, st));
       }
-      VTCHK(hipMemsetAsync(dAssoc, 0xff, (size_t)N, st));
+      HIPCHK(hipMemsetAsync(dAssoc, 0xff, (size_t)N, st));
 
       VtArgs a{};
       a.feat = reinterpret_cast<const uint32_t*>(d_desc32);
@@ -243,37 +205,37 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
       aMulti.nList = nMulti;
 
       // seeding (and the trivial nodes)
-      VTCHK(vtLaunchSeedSmall(st, aSmall));
+      HIPCHK(vtLaunchSeedSmall(st, aSmall));
       if (nLarge) {
-        VTCHK(vtLaunchSeedFirst(st, aLarge));
+        HIPCHK(vtLaunchSeedFirst(st, aLarge));
         for (int c = 1; c < k; c++) {
-          VTCHK(vtLaunchSeedUpdate(st, aLarge, c));
-          VTCHK(vtLaunchSeedPick(st, aLarge, c));
+          HIPCHK(vtLaunchSeedUpdate(st, aLarge, c));
+          HIPCHK(vtLaunchSeedPick(st, aLarge, c));
         }
       }
       // rounds, until no node of the level is running
       for (int round = 0; nKmeans > 0; round++) {
-        VTCHK(hipMemsetAsync(dStats + 8, 0, 4, st));
-        VTCHK(vtLaunchAssign(st, a));
-        VTCHK(vtLaunchRound(st, a));
+        HIPCHK(hipMemsetAsync(dStats + 8, 0, 4, st));
+        HIPCHK(vtLaunchAssign(st, a));
+        HIPCHK(vtLaunchRound(st, a));
         int32_t running = 0;
-        VTCHK(hipMemcpyAsync(&running, dStats + 8, 4, hipMemcpyDeviceToHost, st));
-        VTCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&running, dStats + 8, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         if (running == 0 || round >= max_rounds) break;
-        VTCHK(vtLaunchCount(st, a));
-        VTCHK(vtLaunchCentreFinal(st, aMulti));
+        HIPCHK(vtLaunchCount(st, a));
+        HIPCHK(vtLaunchCentreFinal(st, aMulti));
       }
       // the next level's groups
-      VTCHK(vtLaunchHist(st, a));
-      VTCHK(vtLaunchScan(st, a));
-      VTCHK(vtLaunchScatter(st, a));
+      HIPCHK(vtLaunchHist(st, a));
+      HIPCHK(vtLaunchScan(st, a));
+      HIPCHK(vtLaunchScatter(st, a));
       std::swap(perm, permOut);
       std::vector<int32_t> hHist((size_t)nNodes * k);
       hCentres.resize((size_t)nNodes * k * 8);
-      VTCHK(hipMemcpyAsync(hNodes.data(), dNodes, (size_t)nNodes * sizeof(VtNode), hipMemcpyDeviceToHost, st));
-      VTCHK(hipMemcpyAsync(hHist.data(), dNodeHist, hHist.size() * 4, hipMemcpyDeviceToHost, st));
-      VTCHK(hipMemcpyAsync(hCentres.data(), dCentres, hCentres.size() * 4, hipMemcpyDeviceToHost, st));
-      VTCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(hNodes.data(), dNodes, (size_t)nNodes * sizeof(VtNode), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(hHist.data(), dNodeHist, hHist.size() * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(hCentres.data(), dCentres, hCentres.size() * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       std::vector<Active> next;
       for (int i = 0; i < nNodes; i++) {
         const int nC = hNodes[i].nC, tn = cur[i].tnode;
@@ -290,8 +252,8 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
       cur.swap(next);
     }
     int32_t dev[9];  // the kernels' counters: most rounds, capped runs, emptied clusters, short seedings
-    VTCHK(hipMemcpyAsync(dev, dStats, sizeof dev, hipMemcpyDeviceToHost, st));
-    VTCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(dev, dStats, sizeof dev, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     for (int i = 3; i <= 6; i++) stats[i] = dev[i];
   }
 
@@ -350,12 +312,12 @@ int orbx_vocabulary_train_device(orbx_ctx* ctx, int k, int L, int scoring, int w
       DeviceBuf<uint32_t> dNi;
       std::vector<uint32_t> Ni((size_t)nWords, 0);
       if (idf) {
-        VTCHK(dNi.grow((size_t)nWords * 4));
-        VTCHK(hipMemsetAsync(dNi, 0, (size_t)nWords * 4, st));
+        HIPCHK(dNi.grow((size_t)nWords * 4));
+        HIPCHK(hipMemsetAsync(dNi, 0, (size_t)nWords * 4, st));
       }
-      VTCHK(vtLaunchDocFreq(st, dBowNodes, dFin, d_n, capacity, n_docs, d_feat_word, idf ? (uint32_t*)dNi : nullptr));
-      if (idf) VTCHK(hipMemcpyAsync(Ni.data(), dNi, (size_t)nWords * 4, hipMemcpyDeviceToHost, st));
-      VTCHK(hipStreamSynchronize(st));
+      HIPCHK(vtLaunchDocFreq(st, dBowNodes, dFin, d_n, capacity, n_docs, d_feat_word, idf ? (uint32_t*)dNi : nullptr));
+      if (idf) HIPCHK(hipMemcpyAsync(Ni.data(), dNi, (size_t)nWords * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       if (idf)  // setNodeWeights (:997-1004): ln(NDocs / Ni) with the host's libm, 0 for a word no document reaches
         for (int w = 0; w < nWords; w++) weight[wordNode[w]] = Ni[w] > 0 ? log((double)n_docs / (double)Ni[w]) : 0.0;
       return ORBX_OK;
@@ -398,7 +360,7 @@ int orbx_vocabulary_train(orbx_ctx* ctx, int k, int L, int scoring, int weightin
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  VTCHK(hipSetDevice(ctxDevice(ctx)));
+  HIPCHK(hipSetDevice(ctxDevice(ctx)));
   hipStream_t st = ctxStream(ctx);
   // the extractor's batch layout: document f at f * cap
   const size_t slots = std::max<size_t>((size_t)n_docs * cap, 1);
@@ -411,19 +373,19 @@ int orbx_vocabulary_train(orbx_ctx* ctx, int k, int L, int scoring, int weightin
   DeviceBuf<uint8_t> dDesc;
   DeviceBuf<int32_t> dN;
   DeviceBuf<uint32_t> dFw;
-  VTCHK(dDesc.grow(slots * 32));
-  VTCHK(dN.grow(std::max<size_t>((size_t)n_docs, 1) * 4));
-  if (feat_word) VTCHK(dFw.grow(slots * 4));
-  VTCHK(hipMemcpyAsync(dDesc, padded.data(), slots * 32, hipMemcpyHostToDevice, st));
-  if (n_docs) VTCHK(hipMemcpyAsync(dN, doc_n, (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
-  VTCHK(hipStreamSynchronize(st));
+  HIPCHK(dDesc.grow(slots * 32));
+  HIPCHK(dN.grow(std::max<size_t>((size_t)n_docs, 1) * 4));
+  if (feat_word) HIPCHK(dFw.grow(slots * 4));
+  HIPCHK(hipMemcpyAsync(dDesc, padded.data(), slots * 32, hipMemcpyHostToDevice, st));
+  if (n_docs) HIPCHK(hipMemcpyAsync(dN, doc_n, (size_t)n_docs * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   r = orbx_vocabulary_train_device(ctx, k, L, scoring, weighting, seed, max_rounds, n_docs, dDesc, dN, cap, out, stats8,
                                    feat_word ? (uint32_t*)dFw : nullptr);
   if (r != ORBX_OK) return r;
   if (feat_word && total > 0) {
     std::vector<uint32_t> fw(slots);
-    VTCHK(hipMemcpyAsync(fw.data(), dFw, slots * 4, hipMemcpyDeviceToHost, st));
-    VTCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(fw.data(), dFw, slots * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     off = 0;
     for (int f = 0; f < n_docs; f++) {
       if (doc_n[f]) memcpy(feat_word + off, &fw[(size_t)f * cap], (size_t)doc_n[f] * 4);

@@ -23,7 +23,7 @@
 
 #include <cstdint>
 
-#include "orbx_device.h"
+#include "orbx_launch.h"
 
 namespace orbx {
 

@@ -153,6 +153,36 @@ def test_null_table_is_the_contexts(orbx, ext, sized):
     assert res2[0]["chi2_initial"] != res[0]["chi2_initial"]
 
 
+def test_pair_list_and_table_held_across_calls(orbx, sized):
+    """The pair list and the table live on the device between calls, each with the host copy its upload read: call after call on
+    one context of its own -- a first list, the same again (no upload), as many pairs in other frames (replaced in place), one
+    pair, three pairs (the device array grows), the first list again, and then the same two pairs under another table (the table
+    alone is replaced) and under the first one -- every call equals the restatement bit for bit."""
+    e = orbx.ORBextractor(1000, 1.2, B.NLEVELS, 20, 7, max_width=640, max_height=480, max_batch=2)
+    a, b, c = sized[63], sized[65], sized[257]
+    refs = {}
+
+    def step(what, pairs, table=None, **kw):
+        res, pts = run_batch(orbx, e, pairs, min_points=60, inv_sigma2=table, **kw)
+        for p, w in enumerate(pairs):
+            key = (id(w), table is not None)
+            if key not in refs:
+                refs[key] = B.bundle_adjust(w, min_points=60, inv_sigma2=table)[:2]
+            same(res[p], pts[p], *refs[key], what="%s, pair %d" % (what, p))
+
+    try:
+        step("two pairs", [a, b])
+        step("the same list", [a, b])
+        step("as many pairs, other frames", [a, b], reverse=True)
+        step("one pair", [c])
+        step("three pairs", [b, c, a])
+        step("the first list again", [a, b])
+        step("another table", [a, b], table=B.top_level_off_table())
+        step("the first table again", [a, b])
+    finally:
+        e.close()
+
+
 def test_host_form_equals_the_batch(orbx, ext, sized):
     for w in (sized[257], B.skipped(sized[64]), _bad(sized[65], "match")):
         res, pts = run_batch(orbx, ext, [w])

@@ -209,8 +209,11 @@ def test_frame_compute_bow(orbx, ext, images, full, dev_full):
     assert list(f.mFeatVec.keys()) == sorted(f.mFeatVec.keys())
 
 
-def test_l1_scores(orbx, ext, torch_or_skip, full, dev_full, golden_desc):
-    torch = torch_or_skip
+@pytest.fixture(scope="module")
+def l1_frames(full, golden_desc):
+    """(B, cap, descriptors [B, cap, 32], counts [B], the generator's state behind them): the golden frames cut to random
+    lengths, a frame of features near the vocabulary's nodes and an empty one.  A consumer that draws on restores the state into a
+    generator of its own, so that what it draws depends on no other consumer."""
     cap, B = 2048, 16
     rng = np.random.default_rng(9)
     frames = [golden_desc[i % len(golden_desc)][: rng.integers(100, 1000)] for i in range(B - 2)]
@@ -221,6 +224,14 @@ def test_l1_scores(orbx, ext, torch_or_skip, full, dev_full, golden_desc):
     for i, fr in enumerate(frames):
         d[i, :len(fr)] = fr
         n[i] = len(fr)
+    return B, cap, d, n, rng.bit_generator.state
+
+
+def test_l1_scores(orbx, ext, torch_or_skip, full, dev_full, l1_frames):
+    torch = torch_or_skip
+    B, cap, d, n, state = l1_frames
+    rng = np.random.default_rng()
+    rng.bit_generator.state = state
     d_d, d_n = torch.from_numpy(d).cuda(), torch.from_numpy(n).cuda()
     buf = _bow_buffers(torch, B, cap, fv=False, fw=False)
     dev_full.transform_batch_device(B, d_d, d_n, levelsup=4, capacity=cap, **buf)
@@ -244,6 +255,34 @@ def test_l1_scores(orbx, ext, torch_or_skip, full, dev_full, golden_desc):
     a = vec[0]
     assert np.float64(dev_full.score(a["bow_word"], a["bow_value"], a["bow_word"], a["bow_value"])).tobytes() == \
         np.float64(R.score_l1(a["bow_word"], a["bow_value"], a["bow_word"], a["bow_value"])).tobytes()
+
+
+def test_score_pair_list_held_across_calls(orbx, ext, torch_or_skip, full, l1_frames):
+    """The pair list lives on the device between calls with the host copy its upload read: call after call on one vocabulary of its
+    own -- a first list, the same again (no upload), as many other pairs (replaced in place), one pair, three (the device array
+    grows), the first list again -- every score equals the restatement's bit for bit."""
+    torch = torch_or_skip
+    B, cap, d, n, _ = l1_frames
+    v = orbx.Vocabulary.from_arrays(ext, *full.arrays())
+    try:
+        buf = _bow_buffers(torch, B, cap, fv=False, fw=False)
+        v.transform_batch_device(B, torch.from_numpy(d).cuda(), torch.from_numpy(n).cuda(), levelsup=4, capacity=cap, **buf)
+        torch.cuda.synchronize()
+        vec, refs = [_frame(buf, f, cap) for f in range(B)], {}
+        two = ([0, 3], [1, B - 1])
+        for what, (first, second) in (("two pairs", two), ("the same list", two), ("as many other pairs", ([2, B - 2], [5, 2])),
+                                      ("one pair", ([4], [4])), ("three pairs", ([6, 0, 7], [7, 9, 6])), ("the first list again", two)):
+            d_s = torch.full((len(first),), -1.0, dtype=torch.float64, device="cuda")
+            v.score_pairs_device(B, np.array(first, np.int32), np.array(second, np.int32), buf["d_bow_word"], buf["d_bow_value"],
+                                 buf["d_bow_n"], d_s, capacity=cap)
+            torch.cuda.synchronize()
+            s = d_s.cpu().numpy()
+            for p, (a, b) in enumerate(zip(first, second)):
+                if (a, b) not in refs:
+                    refs[(a, b)] = R.score_l1(vec[a]["bow_word"], vec[a]["bow_value"], vec[b]["bow_word"], vec[b]["bow_value"])
+                assert np.float64(s[p]).tobytes() == np.float64(refs[(a, b)]).tobytes(), (what, a, b)
+    finally:
+        v.close()
 
 
 def test_score_refusals(orbx, ext, torch_or_skip, dev_full):

@@ -146,20 +146,27 @@ def _mixed_pairs():
     return pairs
 
 
-def _run_mixed(orbx, ext, pairs, cap, K):
-    """The pairs as one initialize_batch_device call (pair p = frames 2p and 2p + 1, outputs pre-filled with 0xA5) ->
-    (results [P], vP3D [P, cap, 3], vbTriangulated [P, cap])."""
+def _upload(orbx, pairs, cap, reverse=False):
+    """The pairs in HBM, pair p = frames 2p and 2p + 1, or with `reverse` pair P - 1 - p -> (first, second, d_kps, d_n, d_m12, d_sets)."""
     import torch
     P = len(pairs)
     kps, n = np.zeros((2 * P, cap), orbx.KEYPOINT_DTYPE), np.zeros(2 * P, np.int32)
     m12 = np.zeros((P, cap), np.int32)  # beyond a frame's count: 0, which would be a match if it were read (orbx.h: it is not)
     sets = np.zeros((P, 200, 8), np.int32)
+    first = 2 * (np.arange(P, dtype=np.int32)[::-1] if reverse else np.arange(P, dtype=np.int32))
     for p, (_, k1, k2, m, s, _) in enumerate(pairs):
-        kps[2 * p, :len(k1)], kps[2 * p + 1, :len(k2)], n[2 * p], n[2 * p + 1] = k1, k2, len(k1), len(k2)
+        kps[first[p], :len(k1)], kps[first[p] + 1, :len(k2)], n[first[p]], n[first[p] + 1] = k1, k2, len(k1), len(k2)
         m12[p, :len(m)], sets[p] = m, s
-    first, second = np.arange(0, 2 * P, 2, dtype=np.int32), np.arange(1, 2 * P, 2, dtype=np.int32)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
-    d_k, d_n, d_m, d_sets = d(kps), d(n), d(m12), d(sets)
+    return np.ascontiguousarray(first), first + 1, d(kps), d(n), d(m12), d(sets)
+
+
+def _run_mixed(orbx, ext, pairs, cap, K, reverse=False):
+    """The pairs as one initialize_batch_device call (_upload; outputs pre-filled with 0xA5) ->
+    (results [P], vP3D [P, cap, 3], vbTriangulated [P, cap])."""
+    import torch
+    P = len(pairs)
+    first, second, d_k, d_n, d_m, d_sets = _upload(orbx, pairs, cap, reverse)
     d_res = torch.full((P * orbx.INIT_RESULT_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
     d_p = torch.full((P * cap * 12,), 0xA5, dtype=torch.uint8, device="cuda")
     d_t = torch.full((P * cap,), 0xA5, dtype=torch.uint8, device="cuda")
@@ -198,6 +205,64 @@ def test_mixed_batch_equals_the_restatement(orbx, ext):
         before = pairs[P - 1 - names.index(name)]
         assert before[5][0]["n_solutions"] == 4 and before[5][0]["best_solution"] >= 0, (name, before[0])
     assert st["h_rotation"]["n_solutions"] == 1
+
+
+_HELD = ("h_accept_i1", "f_n64", "f_n65")  # 60, 64 and 65 matches
+_HF_INTS = ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h", "n_inliers_f")
+_HF_FLOATS = ("score_h", "score_f", "rh", "H21", "H12", "F21")
+
+
+def _held_steps():
+    """One context, call after call: a first list, the same again (no upload), as many pairs in other frames (replaced in place),
+    one pair, three pairs (the device array grows), the first list again -> (what, world names, reverse)."""
+    a, b, c = _HELD
+    return (("two pairs", (a, b), False), ("the same list", (a, b), False), ("as many pairs, other frames", (a, b), True),
+            ("one pair", (c,), False), ("three pairs", (b, c, a), False), ("the first list again", (a, b), False))
+
+
+def test_initialize_pair_list_held_across_calls(orbx):
+    """The pair list lives on the device between calls with the host copy its upload read (_held_steps): every call of
+    orbx_initialize_batch_device equals the restatement bit for bit."""
+    worlds = {name: R.init_world(name) for name in _HELD}
+    cap = max(max(len(w["k1"]), len(w["k2"])) for w in worlds.values()) + 4
+    e = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=640, max_height=480, max_batch=2)
+    try:
+        for what, names, reverse in _held_steps():
+            pairs = [(nm, worlds[nm]["k1"], worlds[nm]["k2"], worlds[nm]["m12"], worlds[nm]["sets"], None) for nm in names]
+            res, p3d, tri = _run_mixed(orbx, e, pairs, cap, worlds[names[0]]["K"], reverse)
+            for p, nm in enumerate(names):
+                n1 = len(worlds[nm]["k1"])
+                _same(res[p], p3d[p, :n1], tri[p, :n1], *_ref(nm), what="%s, %s" % (what, nm))
+    finally:
+        e.close()
+
+
+def test_find_models_pair_list_held_across_calls(orbx):
+    """The same for orbx_find_models_batch_device: every field of the result and the inlier flags of both models."""
+    import torch
+    worlds = {name: R.init_world(name) for name in _HELD}
+    refs = {name: R.find_models(w["k1"], w["k2"], w["m12"], w["sets"])[:2] for name, w in worlds.items()}
+    cap = max(max(len(w["k1"]), len(w["k2"])) for w in worlds.values()) + 4
+    e = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=640, max_height=480, max_batch=2)
+    try:
+        for what, names, reverse in _held_steps():
+            P = len(names)
+            pairs = [(nm, worlds[nm]["k1"], worlds[nm]["k2"], worlds[nm]["m12"], worlds[nm]["sets"], None) for nm in names]
+            first, second, d_k, d_n, d_m, d_sets = _upload(orbx, pairs, cap, reverse)
+            d_res = torch.full((P * orbx.HF_RESULT_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
+            d_inl = torch.full((P * 2 * cap,), 0xA5, dtype=torch.uint8, device="cuda")
+            e.find_models_batch_device(2 * P, first, second, d_k, d_n, d_m, d_sets, d_res, d_inl, capacity=cap, n_iter=200)
+            torch.cuda.synchronize()
+            res, inl = d_res.cpu().numpy().view(orbx.HF_RESULT_DTYPE), d_inl.cpu().numpy().reshape(P, 2, cap)
+            for p, nm in enumerate(names):
+                ref, rinl = refs[nm]
+                for f in _HF_INTS:
+                    assert int(res[p][f]) == int(ref[f]), (what, nm, f, res[p][f], ref[f])
+                for f in _HF_FLOATS:
+                    assert np.asarray(res[p][f], np.float32).tobytes() == np.asarray(ref[f], np.float32).tobytes(), (what, nm, f)
+                assert np.array_equal(inl[p, :, :int(ref["n_matches"])].astype(bool), rinl), (what, nm)
+    finally:
+        e.close()
 
 
 def test_batch_equals_single_calls(orbx, oracle):

@@ -113,6 +113,32 @@ def test_single_pairs_and_host_form_equal_the_batch(torch, ext, worlds, name, li
         assert hnm == nm[p] and np.array_equal(hm, got[p, :nb]), M.PAIRS[p]
 
 
+def test_pair_list_held_across_calls(orbx, torch):
+    """The pair list lives on the device between calls with the host copy its upload read: call after call on one context of its
+    own -- a first list, the same again (no upload), as many other pairs (replaced in place), one pair, three (the device array
+    grows), the first list again -- every call equals the restatement.  Pairs of the small frames only."""
+    cfg = (1, 0.9, True)
+    e = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=640, max_height=480, max_batch=2, device=0)
+    d = DeviceWorld(orbx, torch, e, M.world("irregular", 0))
+    want = d.w.expected(cfg)
+    try:
+        two = [4, 5]  # (keyframe g, frame 12 + g) of 40 and of 150 features
+        steps = (("two pairs", two), ("the same list", two), ("as many other pairs", [10, 11]), ("one pair", [3]),
+                 ("three pairs", [5, 9, 10]), ("the first list again", two))
+        assert not set(M.BIG_PAIRS) & {p for _, idx in steps for p in idx}
+        # (a list left in place of its successor would be seen: the two lists of two expect different matches)
+        assert any(not np.array_equal(want[p][0], want[q][0]) for p, q in zip(two, [10, 11]))
+        for what, idx in steps:
+            got, nm = d.match(torch, e, KF_IDX[idx], F_IDX[idx], cfg)
+            for row, p in enumerate(idx):
+                nb = int(d.w.n[M.PAIRS[p][1]])
+                assert nm[row] == want[p][1] and np.array_equal(got[row, :nb], want[p][0]), (what, M.PAIRS[p])
+                assert np.all(got[row, nb:] == -7), (what, M.PAIRS[p])
+    finally:
+        d.voc.close()
+        e.close()
+
+
 def test_refusals_with_a_context(orbx, torch, ext, worlds):
     d = worlds("irregular", 0)
     m, nm = torch.zeros(CAP, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")

@@ -522,6 +522,40 @@ def test_device_resident_api(orbx, oracle):
         e.close()
 
 
+def test_match_pair_list_held_across_calls(orbx, oracle, golden):
+    """orbx_match_init_batch_device keeps its pair list on the device between calls with the host copy its upload read: call after
+    call on one context of its own over the six canonical golden frames -- a first list, the same again (no upload), as many other
+    pairs (replaced in place), one pair, three (the device array grows), the first list again -- every call equals the oracle."""
+    import torch
+    names = ("dbow0", "dbow1", "dbow2", "dbow3", "init0", "init1")
+    fr = [(golden["canonical/%s/kps" % k], golden["canonical/%s/desc" % k]) for k in names]
+    cap, bounds = 1000, (0, 752, 0, 480)
+    kps, desc = np.zeros((len(fr), cap), orbx.KEYPOINT_DTYPE), np.zeros((len(fr), cap, 32), np.uint8)
+    for f, (k, d) in enumerate(fr):
+        kps[f, :len(k)], desc[f, :len(k)] = k, d
+    d_k, d_d = torch.from_numpy(kps.view(np.uint8).reshape(-1)).cuda(), torch.from_numpy(desc.reshape(-1)).cuda()
+    d_n = torch.tensor([len(k) for k, _ in fr], dtype=torch.int32, device="cuda")
+    refs = {}
+    e = orbx.ORBextractor(cap, 1.2, 8, 20, 7, max_width=752, max_height=480, max_batch=2)
+    try:
+        two = ([4, 0], [5, 1])
+        for what, (first, second) in (("two pairs", two), ("the same list", two), ("as many other pairs", ([5, 2], [4, 3])),
+                                      ("one pair", ([1], [0])), ("three pairs", ([2, 4, 3], [3, 5, 1])), ("the first list again", two)):
+            P = len(first)
+            d_m = torch.full((P * cap,), -7, dtype=torch.int32, device="cuda")
+            d_nm, d_st = torch.zeros(P, dtype=torch.int32, device="cuda"), torch.zeros(3 * P, dtype=torch.int32, device="cuda")
+            e.match_pairs_device(np.array(first, np.int32), np.array(second, np.int32), d_k, d_d, d_n, bounds, d_m, d_nm, d_st, 100, 0.9,
+                                 True, cap)
+            mm, nm, st = d_m.cpu().numpy().reshape(P, cap), d_nm.cpu().numpy(), d_st.cpu().numpy().reshape(P, 3)
+            for p, (a, b) in enumerate(zip(first, second)):
+                if (a, b) not in refs:
+                    refs[(a, b)] = oracle.match_init(fr[a][0], fr[a][1], fr[b][0], fr[b][1], bounds, 100, 0.9, True)
+                onm, om12, ost = refs[(a, b)]
+                assert nm[p] == onm and np.array_equal(mm[p, :len(om12)], om12) and st[p].tolist() == ost.tolist(), (what, a, b)
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("cfg", [(1920, 1080, 4000), (3840, 2160, 8000)])
 def test_full_size_configs(orbx, oracle, cfg):
     """BASELINE configs 3 and 5 at full size: extraction equals the oracle; extract -> match of a shifted frame is

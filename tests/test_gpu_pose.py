@@ -185,6 +185,44 @@ def test_null_table_is_the_contexts(orbx, ext, sized):
     assert res2[0]["chi2_initial"] != res[0]["chi2_initial"]
 
 
+def test_problem_list_and_table_held_across_calls(orbx, sized):
+    """The problem list and the table live on the device between calls, each with the host copy its upload read: call after call
+    on one context of its own -- a first list, the same again (no upload), as many problems over other frames and point sets
+    (replaced in place), one problem, three (the device array grows), the first list again, and then the same two problems under
+    another table (the table alone is replaced) and under the first one -- every call equals the restatement bit for bit."""
+    e = orbx.ORBextractor(1000, 1.2, P.NLEVELS, 20, 7, max_width=640, max_height=480, max_batch=2)
+    a, b, c = sized[63], sized[64], sized[65]
+    off = P.inv_sigma2_table()
+    off[P.NLEVELS - 1] = 0  # the usual table with the weight of the last level set to 0
+    refs = {}
+
+    def step(what, worlds, table=None, swapped=False):
+        kw = {}
+        if swapped:  # problem p reads frame and point set 1 - p
+            worlds = [w.copy() for w in worlds]
+            for p, w in enumerate(worlds):
+                w.frame = w.point_set = 1 - p
+            kw = dict(frames=[(w.kps, w.n) for w in worlds[::-1]], sets=[(w.points, w.mask) for w in worlds[::-1]])
+        res, flags = run_batch(orbx, e, worlds, inv_sigma2=table, **kw)
+        for p, w in enumerate(worlds):
+            key = (w.n, table is not None)
+            if key not in refs:
+                refs[key] = P.pose_optimize(w, inv_sigma2=table)[:2]
+            same(res[p], flags[p], *refs[key], what="%s, problem %d" % (what, p))
+
+    try:
+        step("two problems", [a, b])
+        step("the same list", [a, b])
+        step("as many problems, other frames and sets", [a, b], swapped=True)
+        step("one problem", [c])
+        step("three problems", [b, c, a])
+        step("the first list again", [a, b])
+        step("another table", [a, b], table=off)
+        step("the first table again", [a, b])
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("n_iterations", [0, 3])
 def test_few_and_no_iterations(orbx, ext, sized, n_iterations):
     res = check(orbx, ext, [named("far"), sized[9], sized[65]], n_iterations=n_iterations)

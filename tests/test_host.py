@@ -54,11 +54,14 @@ def test_library_reads_no_environment_only_named_knobs(orbx):
 
 
 def test_library_allocates_only_through_the_buffer_types():
-    """orbx_api.cpp and orbx_bow.cpp allocate and free device and page-locked memory only through csrc/orbx_buf.h's owning
-    types (DeviceBuf, PinnedBuf): no hand-written hipMalloc / hipFree pairs to keep in step.  (orbx_multi.cpp frees each
-    rank's buffers under that rank's device and is not covered.)"""
+    """Every host .cpp except orbx_multi.cpp allocates and frees device and page-locked memory only through csrc/orbx_buf.h's
+    owning types (DeviceBuf, PinnedBuf, HeldArray): no hand-written hipMalloc / hipFree pairs to keep in step.  (orbx_multi.cpp
+    frees each rank's buffers under that rank's device and is not covered.)"""
     src = os.path.join(ROOT, "orb_slam_tracking_amd", "csrc")
-    for fn in ("orbx_api.cpp", "orbx_bow.cpp"):
+    covered = ("orbx_api.cpp", "orbx_init.cpp", "orbx_bow.cpp", "orbx_db.cpp", "orbx_voc_train.cpp", "orbx_match_bow.cpp",
+               "orbx_ba.cpp", "orbx_pose.cpp")
+    assert sorted(covered + ("orbx_multi.cpp",)) == sorted(f for f in os.listdir(src) if f.endswith(".cpp"))
+    for fn in covered:
         calls = re.findall(r"\bhip(?:Host)?(?:Malloc|Free)\b", open(os.path.join(src, fn), errors="replace").read())
         assert not calls, (fn, calls)
     assert re.findall(r"\bhipMalloc\b", open(os.path.join(src, "orbx_buf.h")).read())
