@@ -900,6 +900,93 @@ int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf
                    const uint32_t* f_fv_node, const uint32_t* f_fv_feat, int f_fv_n, const uint8_t* kf_mask, float nnratio,
                    int check_orientation, int32_t* matches_f, int32_t* nmatches);
 
+/* ---- matching by projection: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) ------------------------------
+ * The matcher of Tracking::TrackWithMotionModel: the last frame's map points are projected with the current frame's predicted
+ * pose, each one is matched inside a window of the current frame's grid around its projection, and the matches go to
+ * PoseOptimization.  The reference ships no SearchByProjection (it declares TH_HIGH for it, Features/ORBmatcher.hpp:57); this
+ * is ORB-SLAM2's SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono) with
+ * bMono = true, [from-knowledge], PARITY UNPINNED, bit-identical to a CPU restatement of the rules below
+ * (tests/cpp/match_proj_ref.cpp).  The window search alone is pinned: it is the reference's Frame::GetFeaturesInArea
+ * (SlamTypes/Frame.cpp:163-206) on the grid Frame::PosInGrid fills (:89-99), and the tests compare it with the reference's own
+ * compiled code.
+ *
+ * Pair p: the last frame L = h_last[p], the current frame C = h_cur[p], point set h_point_set[p] whose entry i is the map point
+ * of L's feature i (d_points / d_point_mask as orbx_pose_optimize_batch_device takes them), C's predicted pose d_pose_cur[p]
+ * (12 floats: R row-major, then t).
+ *   1. every matches_cur[j] = -1 (j over C's features), the 30 rotation bins empty
+ *   2. L's features i in ascending order.  Skipped: a feature whose mask byte is 0; one with d_last_outlier[p][i] != 0
+ *      (LastFrame.mvbOutlier; the array is nullable); one whose octave o is outside [0, nlevels) (sets ORBX_PROJ_BAD_INPUT)
+ *   3. projection, f32, no contraction: xc = ((R0*X + R1*Y) + R2*Z) + t0, yc and zc likewise from rows 1 and 2;
+ *      invz = 1.0f / zc correctly rounded; skipped when invz < 0; u = (fx*xc)*invz + cx, v = (fy*yc)*invz + cy; skipped when u or
+ *      v is not finite; skipped when u < min_x || u > max_x || v < min_y || v > max_y (a value on a bound stays)
+ *   4. r = th * scale[o] (an f32 product with the context's table, orbx_get_tables); the candidates are
+ *      GetFeaturesInArea(u, v, r, o - 1, o + 1) over C's undistorted keypoints: PosInGrid's rounding, the cells
+ *      floor((u - min_x - r) * inv) .. ceil((u - min_x + r) * inv) clamped to the grid, the level test and the strict
+ *      fabs(d) < r in both coordinates, in the order cell x outer, cell y inner, ascending index inside a cell.  No candidate:
+ *      skipped
+ *   5. over the candidates that no EARLIER feature of L took, in that order: d = popcount(desc_i ^ desc_C[j]); best = the first
+ *      candidate with the smallest d (`if (dist < bestDist)`, bestDist starting at 256).  desc_i is d_point_desc32[set][i] when
+ *      that array is given (the map point's own descriptor, pMP->GetDescriptor()), otherwise L's descriptor i
+ *   6. best <= 100 (TH_HIGH): matches_cur[bestIdx] = i, bestIdx is taken, and with check_orientation the match joins the bin of
+ *      angle_L[i] - angle_C[bestIdx] as in SearchByBoW above
+ *   7. with check_orientation, ComputeThreeMaxima and its 0.1 rule on the bin sizes; the matches of every other bin go back to -1
+ *   nmatches = the entries of matches_cur that are not -1.
+ * Documented deviations from ORB-SLAM2:
+ *   1. The bin factor and a bin outside [0, 30): deviations 1 and 2 of SearchByBoW.
+ *   2. "Taken" (matches_cur[j] >= 0) stands for `CurrentFrame.mvpMapPoints[i2]->Observations() > 0`: every map point counts as
+ *      observed.
+ *   3. No stereo branches: no bForward / bBackward scale windows and no mvuRight test.
+ *   4. Map points are coordinates plus a mask, matches are indices (matches_cur holds L's feature, whose map point it is).
+ *   5. Garbage is flagged and never followed.  u or v that is no number skips the feature (the design's comparisons would let a
+ *      NaN through); a non-finite pose, or a non-finite point of a feature that step 2 keeps, sets ORBX_PROJ_NONFINITE; a frame
+ *      count outside [0, capacity] is clamped and sets ORBX_PROJ_BAD_INPUT, as does an octave outside the table.  A keypoint of C
+ *      whose cell is no number is in no cell.  Window cells are clamped as floats, which equals the reference wherever its
+ *      float -> int conversion is defined.
+ * Worst case: features of L that all claim the same candidates resolve one per round (see the kernel); the common case is a
+ * handful of rounds. */
+#define ORBX_PROJ_BAD_INPUT 2 /* a frame count outside [0, capacity], an octave of L outside [0, nlevels) */
+#define ORBX_PROJ_NONFINITE 4 /* a non-finite pose, or a non-finite point of a feature that step 2 keeps */
+typedef struct orbx_proj_result {
+  int32_t status;            /* 0, or a bitmask of ORBX_PROJ_*; every field is written for every pair */
+  int32_t nmatches;
+  int32_t n_points;          /* features of L that survive step 2 */
+  int32_t n_in_image;        /* ... and step 3 */
+  int32_t n_with_candidates; /* ... and have a candidate in step 4 */
+  int32_t n_displaced;       /* features whose outcome (the candidate, or none) differs from what nothing taken would give */
+  int32_t n_rot_removed;     /* matches step 7 removed */
+  int32_t rounds;            /* the device's rounds of claims; not comparable with a sequential statement, which reports 0 */
+} orbx_proj_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  d_kps_un / d_desc32 (16-byte aligned) / d_n: the frames, in
+ * the layout of the extract calls ([n_frames][capacity]); a frame may be L in one pair and C in another, and in any number of
+ * pairs.  d_points float [n_point_sets][capacity][3], d_point_mask uint8 [n_point_sets][capacity] (NULL = every entry is a
+ * point), d_point_desc32 uint8 [n_point_sets][capacity][32] (NULL = L's descriptors; 16-byte aligned), d_last_outlier uint8
+ * [n_pairs][capacity] (NULL = none; the layout of orbx_pose_optimize_batch_device's d_outlier), d_pose_cur float [n_pairs][12].
+ * K row-major 3x3 (host, f32), bounds = C's image bounds (every C shares them, as Frame's statics), th > 0 (the design passes 15
+ * and 2 * 15), check_orientation.  d_matches_cur int32 [n_pairs][capacity]: row p's first d_n[h_cur[p]] entries hold L's feature
+ * index or -1, the rest is unspecified.  That is orbx_pose_optimize_batch_device's d_match: with h_frame = h_cur, the same point
+ * sets and d_pose0 = d_pose_cur the two calls chain without a copy.  d_res [n_pairs].  One workgroup per pair, one launch.  The
+ * call returns once queued, with the exception orbx_match_bow_batch_device has: when the pair lists differ from the previous
+ * call's on this context, the call first waits for the context stream before it uploads them.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, th not finite or <= 0, bounds with max <= min, a frame
+ * index outside [0, n_frames), a point set outside [0, n_point_sets) -- all checked before anything touches a device;
+ * ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments.
+ * n_pairs == 0 is ORBX_OK. */
+int orbx_match_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_last, const int32_t* h_cur,
+                                       const int32_t* h_point_set, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                       const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                       const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const uint8_t* d_last_outlier,
+                                       const float* d_pose_cur, const float* K, const orbx_bounds* bounds, float th,
+                                       int check_orientation, int32_t* d_matches_cur, orbx_proj_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: the last frame (last_n features; points
+ * [last_n][3]; mask, point_desc32 and last_outlier nullable, one entry per feature of L), then the current frame; pose_cur [12];
+ * matches_cur holds cur_n entries.  More than ORBX_BOW_MAX_FEATURES features: ORBX_E_CAPACITY.  Synchronous. */
+int orbx_match_projection(orbx_ctx* ctx, const orbx_keypoint* last_kps_un, const uint8_t* last_desc32, int last_n,
+                          const orbx_keypoint* cur_kps_un, const uint8_t* cur_desc32, int cur_n, const float* points,
+                          const uint8_t* mask, const uint8_t* point_desc32, const uint8_t* last_outlier, const float* pose_cur,
+                          const float* K, const orbx_bounds* bounds, float th, int check_orientation, int32_t* matches_cur,
+                          orbx_proj_result* res);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

@@ -318,6 +318,8 @@ struct FrameView {
   const DBoW2::FeatureVector* mFeatVec = nullptr;
 };
 
+struct PoseT;  // (below, with the Initializer)
+
 class ORBmatcher {
  public:
   // Features/ORBmatcher.hpp:15.  (The optional third argument pins the device context; without it the matcher uses the
@@ -366,6 +368,24 @@ class ORBmatcher {
     return searchByBoW(e, frameView(KF), frameView(F), vnMatchesF, kfHasPoint);
   }
 
+  // ORB-SLAM2's SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono) with bMono =
+  // true (orbx.h, "matching by projection", with its documented deviations; the reference declares TH_HIGH for it,
+  // Features/ORBmatcher.hpp:57, and ships no implementation): LastFrame's map points -- given as coordinates, vP3D[i] where
+  // vbHasPoint[i], one entry per feature of LastFrame -- are projected with CurrentFrame's predicted pose Tcw and matched
+  // inside a window of CurrentFrame's grid.  vnMatchesCur[j] = the LastFrame feature whose map point CurrentFrame's feature j
+  // got, or -1; returns the number of matches.  vbLastOutlier (optional): LastFrame.mvbOutlier.  K: 9 floats, row-major.
+  template <class Point3>
+  int SearchByProjection(const FrameView& CurrentFrame, const FrameView& LastFrame, float th, const std::vector<Point3>& vP3D,
+                         const std::vector<bool>& vbHasPoint, const PoseT& Tcw, const float* K, std::vector<int>& vnMatchesCur,
+                         const std::vector<bool>* vbLastOutlier = nullptr, orbx_proj_result* result = nullptr) {
+    return searchByProjection(ext_, CurrentFrame, LastFrame, th, vP3D, vbHasPoint, Tcw, K, vnMatchesCur, vbLastOutlier, result);
+  }
+  // ... for the reference's Frame or any Frame-like type (K from CurrentFrame.mK)
+  template <class FrameT, class Point3, class = typename std::enable_if<!std::is_same<typename std::decay<FrameT>::type, FrameView>::value>::type>
+  int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, float th, const std::vector<Point3>& vP3D,
+                         const std::vector<bool>& vbHasPoint, const PoseT& Tcw, std::vector<int>& vnMatchesCur,
+                         const std::vector<bool>* vbLastOutlier = nullptr, orbx_proj_result* result = nullptr);
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -380,6 +400,10 @@ class ORBmatcher {
   static const DBoW2::FeatureVector* featVecOf(const FrameT&, long) { return nullptr; }
   inline int searchByBoW(ORBextractor* e, const FrameView& KF, const FrameView& F, std::vector<int>& vnMatchesF,
                          const std::vector<bool>* kfHasPoint);  // (defined behind DBoW2::FeatureVector)
+  template <class Point3>
+  int searchByProjection(ORBextractor* e, const FrameView& C, const FrameView& L, float th, const std::vector<Point3>& vP3D,
+                         const std::vector<bool>& vbHasPoint, const PoseT& Tcw, const float* K, std::vector<int>& vnMatchesCur,
+                         const std::vector<bool>* vbLastOutlier, orbx_proj_result* result);  // (defined behind PoseT)
 
   int search(ORBextractor* e, const FrameView& F1, const FrameView& F2, std::vector<int>& vnMatches12, int windowSize) {
     if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
@@ -610,6 +634,52 @@ class Optimizer {
     return res.n_inliers;
   }
 };
+
+template <class Point3>
+int ORBmatcher::searchByProjection(ORBextractor* e, const FrameView& C, const FrameView& L, float th, const std::vector<Point3>& vP3D,
+                                   const std::vector<bool>& vbHasPoint, const PoseT& Tcw, const float* K, std::vector<int>& vnMatchesCur,
+                                   const std::vector<bool>* vbLastOutlier, orbx_proj_result* result) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
+  const size_t n = (size_t)L.N;
+  if (vP3D.size() != n || vbHasPoint.size() != n || (vbLastOutlier && vbLastOutlier->size() != n))
+    throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchByProjection: vP3D, vbHasPoint and vbLastOutlier need LastFrame.N entries");
+  float pose[12];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) pose[r * 3 + c] = (float)Tcw(r, c);
+    pose[9 + r] = (float)Tcw(r, 3);
+  }
+  std::vector<float> p3d(3 * (n ? n : 1));
+  std::vector<uint8_t> has(n ? n : 1), out(n ? n : 1);
+  for (size_t i = 0; i < n; i++) {
+    p3d[3 * i] = vP3D[i].x;
+    p3d[3 * i + 1] = vP3D[i].y;
+    p3d[3 * i + 2] = vP3D[i].z;
+    has[i] = vbHasPoint[i] ? 1 : 0;
+    out[i] = vbLastOutlier && (*vbLastOutlier)[i] ? 1 : 0;
+  }
+  vnMatchesCur.assign(C.N, -1);
+  const orbx_bounds b{C.mnMinX, C.mnMaxX, C.mnMinY, C.mnMaxY};
+  orbx_proj_result res;
+  const int r = orbx_match_projection(e->context(), reinterpret_cast<const orbx_keypoint*>(L.mvKeysUn), L.mDescriptors, L.N,
+                                      reinterpret_cast<const orbx_keypoint*>(C.mvKeysUn), C.mDescriptors, C.N, p3d.data(), has.data(),
+                                      nullptr, vbLastOutlier ? out.data() : nullptr, pose, K, &b, th, mbCheckOrientation ? 1 : 0,
+                                      vnMatchesCur.data(), &res);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  if (result) *result = res;
+  return res.nmatches;
+}
+
+template <class FrameT, class Point3, class>
+int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, float th, const std::vector<Point3>& vP3D,
+                                   const std::vector<bool>& vbHasPoint, const PoseT& Tcw, std::vector<int>& vnMatchesCur,
+                                   const std::vector<bool>* vbLastOutlier, orbx_proj_result* result) {
+  ORBextractor* e = ext_ ? ext_ : (CurrentFrame.mpORBextractor ? CurrentFrame.mpORBextractor : LastFrame.mpORBextractor);
+  float K[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) K[r * 3 + c] = frameK(CurrentFrame.mK, r, c);
+  return searchByProjection(e, frameView(CurrentFrame), frameView(LastFrame), th, vP3D, vbHasPoint, Tcw, K, vnMatchesCur, vbLastOutlier,
+                            result);
+}
 
 }  // namespace ORB_SLAM_Tracking
 

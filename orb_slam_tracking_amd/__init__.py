@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -141,6 +141,22 @@ POSE_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_correspondences"
                              [("stop_reason", "<i4", 4)] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
                              [("q", "<f8", 4), ("t", "<f8", 3), ("R", "<f4", (3, 3)), ("tcw", "<f4", 3)])
 assert POSE_RESULT_DTYPE.itemsize == ctypes.sizeof(PoseResult) == 192
+
+
+PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
+PROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_in_image", "n_with_candidates", "n_displaced", "n_rot_removed", "rounds")
+
+
+class ProjResult(ctypes.Structure):
+    """orbx_proj_result: ORBmatcher::SearchByProjection's counters for one pair (rounds is the device's own count)."""
+    _fields_ = [(n, ctypes.c_int32) for n in PROJ_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+PROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in PROJ_RESULT_FIELDS])
+assert PROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(ProjResult) == 32
 
 
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
@@ -283,6 +299,10 @@ def lib() -> ctypes.CDLL:
     L.orbx_bow_score.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
     L.orbx_match_bow_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, i32, vp, vp]
     L.orbx_match_bow.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, f32, i32, vp, vp]
+    L.orbx_match_projection_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                     ctypes.POINTER(_Bounds), f32, i32, vp, vp]
+    L.orbx_match_projection.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp,
+                                        ctypes.POINTER(ProjResult)]
     L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.orbx_database_destroy.argtypes = [vp]
     L.orbx_database_destroy.restype = None
@@ -648,6 +668,84 @@ class ORBextractor:
                                    ctypes.byref(nm))
         self._check(r, "orbx_match_bow")
         return m[:len(fk)].copy(), int(nm.value)
+
+    def match_projection_pairs_device(self, n_frames: int, last: np.ndarray, cur: np.ndarray, point_set: np.ndarray, d_kps_un, d_desc,
+                                      d_n, n_point_sets: int, d_points, d_point_mask, d_pose_cur, K, bounds: Tuple[int, int, int, int],
+                                      d_matches_cur, d_res, th: float = 15.0, checkOri: bool = True, d_point_desc=None,
+                                      d_last_outlier=None, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono=True) for pairs (last frame last[p], current frame
+        cur[p], the last frame's map points = point set point_set[p]; host index arrays) of the arrays extract_batch_device and
+        undistort_batch_device filled, with the point sets of pose_optimize_batch_device (d_points float32 [n_point_sets,
+        capacity, 3], d_point_mask uint8 [n_point_sets, capacity] or None) and the predicted poses d_pose_cur float32 [n_pairs,
+        12].  Optional: d_point_desc uint8 [n_point_sets, capacity, 32] (the map points' own descriptors; default the last
+        frame's), d_last_outlier uint8 [n_pairs, capacity].  d_matches_cur int32 [n_pairs, capacity] (row p: the last frame's
+        feature matched to each of frame cur[p]'s features, or -1: pose_optimize_batch_device's d_match), d_res [n_pairs]
+        PROJ_RESULT_DTYPE records (32 bytes).  Stream-ordered on the context's stream."""
+        last = np.ascontiguousarray(last, np.int32).reshape(-1)
+        cur = np.ascontiguousarray(cur, np.int32).reshape(-1)
+        point_set = np.ascontiguousarray(point_set, np.int32).reshape(-1)
+        if len(last) != len(cur) or len(last) != len(point_set):
+            raise OrbxError(E_BADARG, "last, cur and point_set must have the same length")
+        cap, nf, ns, P = int(capacity or self.capacity), int(n_frames), int(n_point_sets), len(last)
+        # (as unsigned, a negative index is a huge one)
+        if P and int(np.maximum(last.view(np.uint32), cur.view(np.uint32)).max()) >= nf:
+            raise ValueError("a pair names a frame outside the batch of %d" % nf)
+        if P and int(point_set.view(np.uint32).max()) >= ns:
+            raise ValueError("a pair names a point set outside the %d given" % ns)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the point array", d_points, ns * cap * 12)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, ns * cap)
+        if d_point_desc is not None:
+            _need("the point descriptor array", d_point_desc, ns * cap * 32)
+        if d_last_outlier is not None:
+            _need("the outlier array", d_last_outlier, P * cap)
+        _need("the pose array", d_pose_cur, P * 48)
+        _need("matches_cur", d_matches_cur, P * cap * 4)
+        _need("the result array", d_res, P * PROJ_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_last_outlier, d_pose_cur, d_matches_cur, d_res)
+        r = self._L.orbx_match_projection_batch_device(self._h, nf, P, _ptr(last), _ptr(cur), _ptr(point_set), _ptr(d_kps_un),
+                                                       _ptr(d_desc), _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask),
+                                                       _ptr(d_point_desc), _ptr(d_last_outlier), _ptr(d_pose_cur), _ptr(Kf),
+                                                       ctypes.byref(b), float(th), int(bool(checkOri)), _ptr(d_matches_cur), _ptr(d_res))
+        self._check(r, "orbx_match_projection_batch_device")
+
+    def match_projection(self, last_keys_un, last_desc, cur_keys_un, cur_desc, points, mask, Tcw, K, bounds: Tuple[int, int, int, int],
+                         th: float = 15.0, checkOri: bool = True, point_desc=None, last_outlier=None):
+        """SearchByProjection for one pair in host memory (orbx_match_projection) -> (matches_cur int32 [len(cur_keys_un)],
+        ProjResult).  points [n_last, 3] and mask [n_last] (or None) are the last frame's map points, Tcw (3x4 or 4x4) the
+        current frame's predicted pose.  Synchronous."""
+        lk, ck = np.ascontiguousarray(last_keys_un, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(cur_keys_un, KEYPOINT_DTYPE).reshape(-1)
+        ld, cd = np.ascontiguousarray(last_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, 32)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        if len(lk) != len(ld) or len(ck) != len(cd) or len(pts) != len(lk):
+            raise OrbxError(E_BADARG, "keypoints / descriptors / points differ in length")
+
+        def per_feature(a, what, width=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.uint8).reshape(-1) if width is None else np.ascontiguousarray(a, np.uint8).reshape(-1, width)
+            if len(a) != len(lk):
+                raise OrbxError(E_BADARG, "%s needs one entry per feature of the last frame" % what)
+            return a
+        m = per_feature(None if mask is None else np.asarray(mask) != 0, "the mask")
+        out = per_feature(None if last_outlier is None else np.asarray(last_outlier) != 0, "last_outlier")
+        pd = per_feature(point_desc, "point_desc", 32)
+        T = np.asarray(Tcw, np.float32)
+        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        mc = np.full(max(len(ck), 1), -1, np.int32)
+        res = ProjResult()
+        r = self._L.orbx_match_projection(self._h, _ptr(lk), _ptr(ld), len(lk), _ptr(ck), _ptr(cd), len(ck), _ptr(pts), _ptr(m), _ptr(pd),
+                                          _ptr(out), _ptr(pose), _ptr(Kf), ctypes.byref(b), float(th), int(bool(checkOri)), _ptr(mc),
+                                          ctypes.byref(res))
+        self._check(r, "orbx_match_projection")
+        return mc[:len(ck)].copy(), res
 
     def extract_match_batch_device(self, d_imgs, n_frames: int, width: int, height: int, stride: int, frame_stride: int,
                                    d_kps, d_desc, d_n, first: np.ndarray, second: np.ndarray,
@@ -1563,6 +1661,25 @@ class ORBmatcher:
         fn, ff = flat(F.mFeatVec)
         return ext.match_bow(KF.mvKeysUn, KF.mDescriptors, kn, kf, F.mvKeysUn, F.mDescriptors, fn, ff, mask, self.mfNNratio,
                              self.mbCheckOrientation)
+
+    def SearchByProjection(self, CurrentFrame: Frame, LastFrame: Frame, th: float, points, mask, Tcw, K=None, point_desc=None,
+                           last_outlier=None):
+        """ORB-SLAM2's SearchByProjection(CurrentFrame, LastFrame, th, bMono=True) (include/orbx.h, "matching by projection") ->
+        (nmatches, matches_cur, ProjResult): matches_cur[j] = the LastFrame feature whose map point CurrentFrame's feature j
+        got, or -1.  points [N_last, 3] / mask [N_last]: LastFrame's map points (mvpMapPoints); Tcw (3x4 or 4x4):
+        CurrentFrame's predicted pose; K: 3x3, default CurrentFrame's camera; point_desc (optional): the map points' own
+        descriptors; last_outlier (optional): LastFrame.mvbOutlier."""
+        ext = self._ext or CurrentFrame.mpORBextractor or LastFrame.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(CurrentFrame, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjection needs K (the frame carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        m, res = ext.match_projection(LastFrame.mvKeysUn, LastFrame.mDescriptors, CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors,
+                                      points, mask, Tcw, K, CurrentFrame.bounds, th, self.mbCheckOrientation, point_desc, last_outlier)
+        return int(res.nmatches), m, res
 
 
 class Optimizer:

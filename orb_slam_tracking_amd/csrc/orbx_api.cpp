@@ -2514,4 +2514,8 @@ const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;
   return c->invSigma2.data();
 }
+const float* ctxScale(const orbx_ctx* c, int* nlevels) {
+  *nlevels = c->p.nlevels;
+  return c->scale.data();
+}
 }  // namespace orbx

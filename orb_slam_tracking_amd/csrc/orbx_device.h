@@ -456,6 +456,26 @@ struct MatchBowArgs {
   int32_t* nmatches;         // [nPairs]
 };
 
+// ---- ORBmatcher::SearchByProjection (orbx_match_proj_kernel.hip): one workgroup per (last frame, current frame) pair ----
+constexpr int MP_THREADS = 512;
+struct MatchProjArgs {
+  const orbx_keypoint* kps;    // [nFrames][cap] undistorted
+  const uint8_t* desc;         // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;            // [nFrames] (clamped to [0, cap])
+  const float* points;         // [nSets][cap][3]
+  const uint8_t* pointMask;    // nullable [nSets][cap]
+  const uint8_t* pointDesc;    // nullable [nSets][cap][32], 16-byte aligned
+  const uint8_t* lastOutlier;  // nullable [nPairs][cap]
+  const float* pose;           // [nPairs][12]
+  const int32_t* pairs;        // [3][nPairs] last frames, current frames, point sets
+  int32_t cap, nPairs, nLevels, checkOri;
+  float fx, fy, cx, cy, th;
+  orbx_bounds b;
+  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t* matchesCur;         // [nPairs][cap]
+  orbx_proj_result* res;       // [nPairs]
+};
+
 // ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
 constexpr int DB_THREADS = 256;       // threads of the database kernels
 constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries

@@ -18,6 +18,7 @@ hipStream_t ctxStream(const orbx_ctx* c);
 int ctxDrain(orbx_ctx* c);
 void ctxSetError(orbx_ctx* c, const char* msg);
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels);
+const float* ctxScale(const orbx_ctx* c, int* nlevels);  // mvScaleFactor
 InitScratch* ctxInit(orbx_ctx* c);
 MatchBowScratch* ctxMatchBow(orbx_ctx* c);
 BaScratch* ctxBa(orbx_ctx* c);

@@ -1,8 +1,11 @@
-// orbx_match_bow.cpp — host side of ORBmatcher::SearchByBoW (include/orbx.h, "matching through the FeatureVector"): the
-// argument checks, the pair list and the C entry points.  The kernel is in orbx_match_bow_kernel.hip.
+// orbx_match_bow.cpp — host side of ORBmatcher::SearchByBoW (include/orbx.h, "matching through the FeatureVector") and of
+// ORBmatcher::SearchByProjection ("matching by projection"): the argument checks, the pair lists and the C entry points.  The
+// kernels are in orbx_match_bow_kernel.hip and orbx_match_proj_kernel.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "orbx_host.h"
 
@@ -123,6 +126,143 @@ int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf
   if (r != ORBX_OK) return r;
   HIPCHK(down(matches_f, dM, f_n, st));
   HIPCHK(down(nmatches, dN + 4, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+int orbx_match_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_last, const int32_t* h_cur,
+                                       const int32_t* h_point_set, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                       const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                       const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const uint8_t* d_last_outlier,
+                                       const float* d_pose_cur, const float* K, const orbx_bounds* bounds, float th,
+                                       int check_orientation, int32_t* d_matches_cur, orbx_proj_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || n_point_sets < 0 || capacity < 1 || (n_pairs > 0 && (!h_last || !h_cur || !h_point_set)) ||
+      !d_kps_un || !d_desc32 || !d_n || !d_points || !d_pose_cur || !K || !bounds || !d_matches_cur || !d_res)
+    return ORBX_E_BADARG;
+  if (!std::isfinite(th) || !(th > 0.0f)) {
+    if (ctx) ctxSetError(ctx, "match projection: th is not a positive number");
+    return ORBX_E_BADARG;
+  }
+  // (max - min is an int in Frame's grid: it has to be one)
+  if ((long long)bounds->max_x - bounds->min_x < 1 || (long long)bounds->max_x - bounds->min_x > INT32_MAX ||
+      (long long)bounds->max_y - bounds->min_y < 1 || (long long)bounds->max_y - bounds->min_y > INT32_MAX) {
+    if (ctx) ctxSetError(ctx, "match projection: bounds with max <= min");
+    return ORBX_E_BADARG;
+  }
+  if (!pairsInRange(h_last, h_cur, n_pairs, n_frames) || !pairsInRange(h_cur, h_point_set, n_pairs, n_frames, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "match projection: frame outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
+  if (capacity > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match projection: capacity above ORBX_BOW_MAX_FEATURES");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  // the three lists as one array, held as orbx_match_bow_batch_device holds its two: uploaded only when they differ from the
+  // last call's, behind a wait for the context stream
+  std::vector<int32_t> lists;
+  lists.reserve((size_t)3 * n_pairs);
+  lists.insert(lists.end(), h_last, h_last + n_pairs);
+  lists.insert(lists.end(), h_cur, h_cur + n_pairs);
+  lists.insert(lists.end(), h_point_set, h_point_set + n_pairs);
+  if (!s->projPairs.holds(lists.data(), lists.size())) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(s->projPairs.replace(st, lists.data(), lists.size()));
+  }
+  MatchProjArgs a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.points = d_points;
+  a.pointMask = d_point_mask;
+  a.pointDesc = d_point_desc32;
+  a.lastOutlier = d_last_outlier;
+  a.pose = d_pose_cur;
+  a.pairs = s->projPairs;
+  a.cap = capacity;
+  a.nPairs = n_pairs;
+  a.checkOri = check_orientation != 0;
+  a.fx = K[0];
+  a.fy = K[4];
+  a.cx = K[2];
+  a.cy = K[5];
+  a.th = th;
+  a.b = *bounds;
+  const float* scale = ctxScale(ctx, &a.nLevels);
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) a.scale[l] = l < a.nLevels ? scale[l] : 0.0f;
+  a.matchesCur = d_matches_cur;
+  a.res = d_res;
+  HIPCHK(launch_match_proj(st, a));
+  return ORBX_OK;
+}
+
+int orbx_match_projection(orbx_ctx* ctx, const orbx_keypoint* last_kps_un, const uint8_t* last_desc32, int last_n,
+                          const orbx_keypoint* cur_kps_un, const uint8_t* cur_desc32, int cur_n, const float* points,
+                          const uint8_t* mask, const uint8_t* point_desc32, const uint8_t* last_outlier, const float* pose_cur,
+                          const float* K, const orbx_bounds* bounds, float th, int check_orientation, int32_t* matches_cur,
+                          orbx_proj_result* res) {
+  if (last_n < 0 || cur_n < 0 || !pose_cur || !K || !bounds || !res || (last_n > 0 && (!last_kps_un || !last_desc32 || !points)) ||
+      (cur_n > 0 && (!cur_kps_un || !cur_desc32 || !matches_cur)))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(last_n, cur_n), 1);
+  if (cap > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match projection: more than ORBX_BOW_MAX_FEATURES features");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t *dD, *dPD, *dMask, *dOut;
+  float *dP, *dPose;
+  int32_t *dN, *dM;
+  orbx_proj_result* dR;
+  auto staging = [&](Layout L) {  // the two frames (last 0, current 1) and one point set in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dD = L.take<uint8_t>((size_t)2 * cap * 32);
+    dP = L.take<float>((size_t)cap * 3);
+    dPD = L.take<uint8_t>((size_t)cap * 32);
+    dMask = L.take<uint8_t>(cap);
+    dOut = L.take<uint8_t>(cap);
+    dPose = L.take<float>(12);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dR = L.take<orbx_proj_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dProjIo.grow(bytes, st));
+  staging(Layout(s->dProjIo));
+  HIPCHK(hipMemsetAsync(s->dProjIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
+  HIPCHK(up(dK, last_kps_un, last_n, st));
+  HIPCHK(up(dD, last_desc32, (size_t)last_n * 32, st));
+  HIPCHK(up(dK + c, cur_kps_un, cur_n, st));
+  HIPCHK(up(dD + c * 32, cur_desc32, (size_t)cur_n * 32, st));
+  HIPCHK(up(dP, points, (size_t)last_n * 3, st));
+  if (point_desc32) HIPCHK(up(dPD, point_desc32, (size_t)last_n * 32, st));
+  if (mask) HIPCHK(up(dMask, mask, last_n, st));
+  if (last_outlier) HIPCHK(up(dOut, last_outlier, last_n, st));
+  HIPCHK(up(dPose, pose_cur, 12, st));
+  const int32_t hn[2] = {last_n, cur_n};
+  HIPCHK(up(dN, hn, 2, st));
+  const int32_t last = 0, cur = 1, set = 0;
+  r = orbx_match_projection_batch_device(ctx, 2, 1, &last, &cur, &set, dK, dD, dN, cap, 1, dP, mask ? dMask : nullptr,
+                                         point_desc32 ? dPD : nullptr, last_outlier ? dOut : nullptr, dPose, K, bounds, th,
+                                         check_orientation, dM, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(matches_cur, dM, cur_n, st));
+  HIPCHK(down(res, dR, 1, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
