@@ -1080,7 +1080,8 @@ int orbx_debug_sincos(orbx_ctx* ctx, const float* angle_deg, int n, float* cos_o
  * (one launch, small batches), 0 = one resize launch per level; [1] row bands (tiles) per frame of that kernel; [2] FAST: 1 = k_fast_wave, 0 = k_fast; [3] selection: candidate
  * capacity of the smallest LDS instance a pyramid level of the batch ran on (2048 / 1024 / 512; 0 = a level expected units beyond
  * the LDS layout and went to the global-scratch kernel); [4] bit 0: the batch was cut into two
- * halves on two streams, bit 1: the descriptor kernel took the selection's staging lists itself (small launches: no k_sel_compact); [5] frames per kernel launch; [6] 1 = the wide matcher kernels went with the batch; [7] lane the batch
+ * halves on two streams, bit 1: the descriptor kernel took the selection's staging lists itself (small launches: no k_sel_compact),
+ * bit 2: the descriptor kernel ran its pair form, two keypoints per wave (the launches on k_sel_compact's list); [5] frames per kernel launch; [6] 1 = the wide matcher kernels went with the batch; [7] lane the batch
  * went to (1-based; 0 = the context itself) }. */
 int orbx_debug_last_launch(const orbx_ctx* ctx, int32_t* info8);
 /* Which matcher kernels did the work (cumulative since orbx_create, for the context itself -- a lane has its own): info4 = { [0] blocks

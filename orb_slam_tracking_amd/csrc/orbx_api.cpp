@@ -1130,7 +1130,8 @@ int issueExtract(orbx_ctx* ctx, int si, hipStream_t st, int f0, int n, const Ext
                                 ctx->bufs.hFlags.dev() + ctx->parity, dMax, ctx->bufs.hMaxN.dev() + si * ORBX_MAX_LEVELS));
     ctx->maxSlotsUsed |= 1 << si;
     tm.stop(staged ? 1 : 2);
-    ctx->lastLaunch[4] = (ctx->lastLaunch[4] & 1) | (staged ? 2 : 0);
+    // (bit 2: k_describe_patch's pair form, two keypoints per wave -- exactly the launches on k_sel_compact's list)
+    ctx->lastLaunch[4] = (ctx->lastLaunch[4] & 1) | (staged ? 2 : 4);
   }
   {
     StageTimer tm(ctx, ORBX_STAGE_DESCRIBE, si, st);

@@ -6,7 +6,7 @@
 //   k_fast            per-cell FAST-9-16 + in-cell NMS + threshold fallback, survivors into per-cell segments
 //                                                    (ComputeKeyPointsOctTree cell loops, cpp:1078-1141 -> cv::FAST)
 //   k_describe_patch  IC-angle + 7x7 Gaussian (patch-local, exact int8 matrix products) + steered BRIEF, one wave per
-//                     keypoint                       (IC_Angle cpp:103-159, GaussianBlur cpp:1598-1606,
+//                     two keypoints (per keypoint in small launches)  (IC_Angle cpp:103-159, GaussianBlur cpp:1598-1606,
 //                                                     computeOrbDescriptor cpp:169-228, assembly cpp:1557-1652)
 //   k_match_jacobi / k_match_wide_lists / k_match_wide_resolve   SearchForInitialization: parallel fixpoint sweeps (one
 //                     workgroup per pair up to 256 queries; wide path up to 4096), the sequential loop for the rest
@@ -1154,7 +1154,7 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 
 
 // -------------------------------------------------------------------------------------------------
-// K4+K5+K6 fused, patch-local: one wave per keypoint.  The 43x43 raw window (REFLECT_101 at the level's edges) is
+// K4+K5+K6 fused, patch-local: one wave per keypoint or per two (KPW below).  The 43x43 raw window (REFLECT_101 at the level's edges) is
 // staged in LDS with dword loads; the 7x7 Gaussian is evaluated only on the 37x37 neighbourhood the 512 rotated
 // sample points can reach, with the same exact fixed-point arithmetic as the whole-level blur, as two banded matrix
 // products on the matrix cores (v_mfma_i32_16x16x32_i8; BlurFrags below), so no blurred pyramid is written or re-read.
@@ -1196,6 +1196,12 @@ __device__ const IcTables d_ic = makeIcTables();
 #define DESC_WAVES 3   // keypoints (= waves) per workgroup: consecutive keypoints of a frame's list are spatially close, so
                        // putting them on one CU lets their overlapping windows hit in that CU's L1 (1: 0.44 ms, 2: 0.38,
                        // 3: 0.365, 4: 0.39, 8: 0.44, 16: 0.63 per 256 frames, measured with the vector-ALU blur of rounds 2-6)
+                       // one keypoint per wave: 50-60 VGPRs, 0 AGPRs, no scratch, 7,536 B of LDS = six 1,280-byte pieces, 28 waves per CU
+#define DESC_PAIR_WAVES 3  // waves per workgroup of the pair form (two keypoints per wave, six per workgroup): two 2,512-byte
+                           // slices per wave, 15,072 B = twelve pieces, ten workgroups' worth of LDS per CU -- the 28 waves per
+                           // CU of the register budget stand (nine workgroups).  60 VGPRs, 0 AGPRs, no scratch.  Two waves per workgroup
+                           // (10,048 B = eight pieces, fourteen workgroups) measured the same alone: docs/history.md, round 10
+constexpr int descWaves(const int kpw) { return kpw == 2 ? DESC_PAIR_WAVES : DESC_WAVES; }
 // GV = Gaussian Q8 tap set (orbx_set_opencv_variant): 0 = [18,34,48,56,48,34,18] (error diffusion, sum 256: OpenCV >= 4.1.1 /
 // 3.4.7), 1 = [18,34,49,55,49,34,18] (every tap rounded, sum 257: the bit-exact path of 3.4.1 .. 4.1.0 and the integer filter
 // before it; a sum of 2^24 or more saturates to 255)
@@ -1284,28 +1290,60 @@ __device__ __forceinline__ uint32_t blurTwin(uint32_t v) {
   return v;
 }
 
+// cv::fastAtan2 once more, for lanes that hold DIFFERENT moments (the pair form of k_describe_patch: lanes 0..31 one keypoint,
+// lanes 32..63 the other): the quotient's operands and the 90 - a of the steep side are selected per lane, so that lanes on both
+// sides of the |x| >= |y| split run one polynomial and one division -- operation for operation the values of fast_atan2_deg.
+__device__ __forceinline__ float fast_atan2_deg_sel(float y, float x) {
+  const float p1 = 0.9997878412794807f * (float)(180 / 3.14159265358979323846);
+  const float p3 = -0.3258083974640975f * (float)(180 / 3.14159265358979323846);
+  const float p5 = 0.1555786518463281f * (float)(180 / 3.14159265358979323846);
+  const float p7 = -0.04432655554792128f * (float)(180 / 3.14159265358979323846);
+  const float eps = (float)2.2204460492503131e-16;
+  const float ax = fabsf(x), ay = fabsf(y);
+  const bool flat = ax >= ay;
+  const float c = (flat ? ay : ax) / ((flat ? ax : ay) + eps);
+  const float c2 = c * c;
+  float a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  a = flat ? a : 90.f - a;
+  a = x < 0 ? 180.f - a : a;
+  a = y < 0 ? 360.f - a : a;
+  return a;
+}
+
 // (second launch bound = 7 waves per SIMD, i.e. at most 72 registers: without it the scheduler spreads the three column tiles'
-// accumulators over 82-92 registers and the kernel drops to 5 waves per SIMD; with it 52-62 registers, no spill)
-template <int GV, bool STAGED = false>
-__global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uint8_t* __restrict__ img0, long long img0FrameStride,
+// accumulators over 82-92 registers and the kernel drops to 5 waves per SIMD; with it 50-60 registers, no spill)
+// KPW = keypoints per wave.  1: one wave per keypoint (the staged small launches; every launch before round 10).  2 (round 10, the
+// launches on k_sel_compact's list): wave-item j owns keypoints 2 j and 2 j + 1 of the frame's level-major list, each with its own
+// LDS slice and its own scalars (level, position, byte shift, geometry, image base -- the two may lie on different levels).  What is
+// per WAVE is then paid once per PAIR: the work-item map and the table loads, IC_Angle (lanes 0..30 = disc rows of keypoint A, lanes
+// 32..62 of keypoint B: the same 9 LDS reads, 8 v_alignbyte, 16 v_dot4, 2 atomics), fastAtan2 and cos / sin (lane = keypoint, the
+// per-lane forms; the three values per keypoint go to SGPRs by v_readlane), the pattern loads and the stores.  Staging, the blur and
+// the steered-BRIEF loop run one after the other, A then B, on the same registers.  Nothing is handed over between waves.
+template <int GV, bool STAGED = false, int KPW = 1>
+__global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const uint8_t* __restrict__ img0, long long img0FrameStride,
                                                        int img0Aligned, const uint8_t* __restrict__ pyr, const Geom g,
                                                        const SelKp* __restrict__ sel, const int* __restrict__ nsel,
                                                        orbx_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
                                                        int capacity, const DescStage ds, const int libmFloat) {
-  __shared__ __attribute__((aligned(16))) uint32_t ldsAll[DESC_WAVES][PW_WAVE_WORDS];
-  static_assert(PW_WAVE_WORDS % 4 == 0, "every wave's LDS slice must stay 16-byte aligned");
+  static_assert(KPW == 1 || (KPW == 2 && !STAGED), "one keypoint per wave, or two on the compact list");
+  constexpr int WPG = descWaves(KPW);
+  __shared__ __attribute__((aligned(16))) uint32_t ldsAll[WPG][KPW][PW_WAVE_WORDS];
+  static_assert(PW_WAVE_WORDS % 4 == 0, "every keypoint's LDS slice must stay 16-byte aligned");
   const int f = blockIdx.y + g.frame0, lane = threadIdx.x & 63;
-  uint32_t* const lds = ldsAll[threadIdx.x >> 6];
+  uint32_t* const lds = ldsAll[threadIdx.x >> 6][0];
+  // the lane's half of the wave and its index in that half (pair form; 0 and the lane itself otherwise)
+  const int hl = KPW == 2 ? lane >> 5 : 0, rl = KPW == 2 ? lane & 31 : lane;
   // XCD-aware order: workgroups go round-robin to the 8 XCDs (the grid's x size is a multiple of 8); workgroup b takes
   // keypoint group (b % 8) * chunk + b / 8, so that one XCD works on a contiguous eighth of the frame's keypoint list
   // (mostly one pyramid level) and its L2 holds that part of the pyramid only.  Every keypoint costs the same, so the
   // XCDs stay balanced.
   const int grp = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   // (the wave's index as a scalar: the keypoint record then comes through a scalar load, beside the count's)
-  const int i = grp * DESC_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int i = (grp * WPG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * KPW;  // the wave's first keypoint
   // (the keypoint record is fetched together with the frame's count, not behind it: count, record and window were three
   // dependent global loads and, by the cycle stamps of docs/history.md, 63 % of a wave's lifetime)
-  SelKp k;
+  SelKp k[KPW];
+  bool liveB = false;  // (pair form) keypoint i + 1 exists: otherwise half B computes on A's record and stores nothing
   if constexpr (STAGED) {
     // keypoint i of the level-major order = entry i - (keypoints of the levels below) of its level's staging list; the counts of
     // the frame's levels come through scalar loads (a unit the selection redid carries a tag bit, a failed one a negative count)
@@ -1321,83 +1359,110 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
       if (blockIdx.y == 0 && ds.maxN) selReduceReports(lane, g.frame0, (int)gridDim.y, g.nlevels, ds.maxN, ds.hostMaxN);
     }
     if (i >= total) return;  // wave-uniform
-    k = ds.selStage[(long long)f * ds.selStride + ds.selOff[kl] + (i - off)];
+    k[0] = ds.selStage[(long long)f * ds.selStride + ds.selOff[kl] + (i - off)];
   } else {
-    // (both loads are issued before either is waited for: the compiler sinks the record's load behind the count's branch otherwise,
+    // (the loads are issued before any is waited for: the compiler sinks the record's load behind the count's branch otherwise,
     // and the wave's chain of dependent loads is what its lifetime is made of -- docs/history.md)
-    const unsigned long long kraw = *reinterpret_cast<const unsigned long long*>(&sel[(long long)f * g.selCap + min(i, g.selCap - 1)]);
+    unsigned long long kuse[KPW];
+#pragma unroll
+    for (int h = 0; h < KPW; h++)
+      kuse[h] = *reinterpret_cast<const unsigned long long*>(&sel[(long long)f * g.selCap + min(i + h, g.selCap - 1)]);
     const int cnt = nsel[f];
-    unsigned long long kuse = kraw;
-    asm volatile("" : "+s"(kuse));  // (the record is a value here, not a load to be moved)
+#pragma unroll
+    for (int h = 0; h < KPW; h++) asm volatile("" : "+s"(kuse[h]));  // (the record is a value here, not a load to be moved)
     if (i >= cnt) return;  // wave-uniform; the waves of a workgroup never synchronise with each other
-    k.x = (uint16_t)(kuse & 0xffff); k.y = (uint16_t)((kuse >> 16) & 0xffff); k.level = (uint8_t)((kuse >> 32) & 0xff);
-    k.response = (uint8_t)((kuse >> 40) & 0xff); k.pad = 0;
+    if constexpr (KPW == 2) {
+      liveB = i + 1 < cnt;
+      kuse[1] = liveB ? kuse[1] : kuse[0];  // (a slot past the count may hold anything: a level that does not exist, a window off the image)
+    }
+#pragma unroll
+    for (int h = 0; h < KPW; h++) {
+      k[h].x = (uint16_t)(kuse[h] & 0xffff); k[h].y = (uint16_t)((kuse[h] >> 16) & 0xffff); k[h].level = (uint8_t)((kuse[h] >> 32) & 0xff);
+      k[h].response = (uint8_t)((kuse[h] >> 40) & 0xff); k[h].pad = 0;
+    }
   }
   // Loads that do not depend on the keypoint are issued first, so that their latency runs under the window fetch: the
   // disc-row weights of IC_Angle (lane = disc row) and the vertical tap fragment.
-  const int icRow = min(lane, 30), icAv = icRow < 15 ? 15 - icRow : icRow - 15;
+  const int icRow = min(rl, 30), icAv = icRow < 15 ? 15 - icRow : icRow - 15;
   const uint4 w1a = reinterpret_cast<const uint4*>(d_ic.w1 + icAv * 8)[0], w1b = reinterpret_cast<const uint4*>(d_ic.w1 + icAv * 8)[1];
   const uint4 wua = reinterpret_cast<const uint4*>(d_ic.wu + icAv * 8)[0], wub = reinterpret_cast<const uint4*>(d_ic.wu + icAv * 8)[1];
   // the vertical tap fragment (V = G_0: it does not depend on the keypoint)
   const BlurFrags& bf = GV ? d_blurFrags1 : d_blurFrags0;
   const uint2 fv = *reinterpret_cast<const uint2*>(bf.w[0][lane]);
-  uint32_t* raw = lds;                               // [48][13] dwords (rows 43..47: padding of the third row tile, never written)
-  uint32_t* bl32 = raw;                              // [48][12] dwords = blurred bytes, column-major (raw is dead by then)
-  int* msum = reinterpret_cast<int*>(raw + PW_RAW_WORDS);  // [2] moment sums of IC_Angle
+  // a keypoint's slice (half h of the wave at lds + h * PW_WAVE_WORDS):
+  //   raw   [48][13] dwords (rows 43..47: padding of the third row tile, never written)
+  //   bl32  [48][12] dwords = blurred bytes, column-major, in the raw window's place (raw is dead by then)
+  //   msum  [2] moment sums of IC_Angle, behind them
   static_assert(BL_COLS * (BL_STRIDE / 4) <= PW_RAW_WORDS, "blurred bytes must fit in the raw window");
-  static_assert((PW_ROWS_PAD - 1) * PW_WORDS + 8 + 3 < PW_RAW_WORDS, "the padded row tiles stay inside the wave's own slice");
-  // the keypoint is wave-uniform: keep its fields in SGPRs so that the level geometry comes through scalar loads
-  const int level = __builtin_amdgcn_readfirstlane((int)k.level);
-  const int kx = __builtin_amdgcn_readfirstlane((int)k.x), ky = __builtin_amdgcn_readfirstlane((int)k.y);
-  const LevelGeom& L = g.L[level];
-  const uint8_t* img = level == 0 ? img0 + (long long)f * img0FrameStride : pyr + L.imgOff + (long long)f * L.frameStride;
-  const bool aligned = level > 0 || img0Aligned != 0;
-  const int w = L.w, h = L.h, stride = L.stride;
-  const int ax = (kx - 21) & ~3;          // may be -4
-  const int s = (kx - 21) - ax;           // byte offset of window column 0 inside a staged row, 0..3
+  static_assert((PW_ROWS_PAD - 1) * PW_WORDS + 8 + 3 < PW_RAW_WORDS, "the padded row tiles stay inside the keypoint's own slice");
+  int* const msumL = reinterpret_cast<int*>(lds + hl * PW_WAVE_WORDS + PW_RAW_WORDS);  // the moment sums of this lane's half
+  // a keypoint is wave-uniform: keep its fields in SGPRs so that the level geometry comes through scalar loads
+  int level[KPW], kx[KPW], ky[KPW], s[KPW];
+  const LevelGeom* Lg[KPW];
+#pragma unroll
+  for (int h = 0; h < KPW; h++) {
+    level[h] = __builtin_amdgcn_readfirstlane((int)k[h].level);
+    kx[h] = __builtin_amdgcn_readfirstlane((int)k[h].x); ky[h] = __builtin_amdgcn_readfirstlane((int)k[h].y);
+    Lg[h] = &g.L[level[h]];
+    s[h] = (kx[h] - 21) & 3;               // byte offset of window column 0 inside a staged row, 0..3
+  }
   // ---- stage the raw window.  Round 5: LANE = WINDOW ROW, the row as three 16-byte loads (4-byte aligned global_load_dwordx4):
   //      3 vector-memory instructions per keypoint instead of 11 single-dword ones over (4 rows x 13 dwords) -- the CU's address /
   //      return path charges per instruction and lane, and the window fetch was what kept the kernel off its issue bound (alone
   //      per 256 frames: 0.334 ms; without any fetch 0.231 = the issue bound; this form 0.265; docs/history.md, round 5).
   //      Columns kx-21 .. kx+21 end at byte s + 42 <= 45 of the staged row: 48 bytes hold them; dword 12 of a row only ever meets
-  //      zero taps (blurred columns 37..39, the padding of the last group of four, are never sampled) and is left as it is. ----
+  //      zero taps (blurred columns 37..39, the padding of the last group of four, are never sampled) and is left as it is.
+  //      Pair form: both windows' loads are issued before either is stored -- six 16-byte loads in flight. ----
   {
-    if (lane == 0) { msum[0] = 0; msum[1] = 0; }
-    const bool rowsInside = aligned && ax >= 0 && ax + 48 <= w;  // (uniform) no staged dword crosses the level's left / right side
-    if (rowsInside) {
-      typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-      if (lane < PW_ROWS) {
-        int yy = ky - 21 + lane;
-        yy = yy < 0 ? -yy : yy; yy = yy >= h ? 2 * h - 2 - yy : yy;  // REFLECT_101 (a keypoint is at least 19 px from the border)
-        // (uniform base + 32-bit lane offset: global_load with an SGPR address)
-        const uint8_t* p = img + (uint32_t)(yy * stride + ax);
-        const u32x4_a4 q0 = *reinterpret_cast<const u32x4_a4*>(p), q1 = *reinterpret_cast<const u32x4_a4*>(p + 16),
-                       q2 = *reinterpret_cast<const u32x4_a4*>(p + 32);
-        uint32_t* dst = raw + lane * PW_WORDS;
-        dst[0] = q0.x; dst[1] = q0.y; dst[2] = q0.z; dst[3] = q0.w; dst[4] = q1.x; dst[5] = q1.y; dst[6] = q1.z; dst[7] = q1.w;
-        dst[8] = q2.x; dst[9] = q2.y; dst[10] = q2.z; dst[11] = q2.w;
-      }
-    } else {
-      // the window crosses the level's left / right side (or level 0 is not dword-aligned): lanes 0..51 = 4 rows x 13 dwords per
-      // step; dwords inside the level by dword loads, the others byte by byte with REFLECT_101
+    if (rl == 0) { msumL[0] = 0; msumL[1] = 0; }
+    typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+    const uint8_t* img[KPW];
+    bool aligned[KPW], rowsInside[KPW];
+#pragma unroll
+    for (int h = 0; h < KPW; h++) {
+      img[h] = level[h] == 0 ? img0 + (long long)f * img0FrameStride : pyr + Lg[h]->imgOff + (long long)f * Lg[h]->frameStride;
+      aligned[h] = level[h] > 0 || img0Aligned != 0;
+      const int ax = (kx[h] - 21) & ~3;      // may be -4
+      rowsInside[h] = aligned[h] && ax >= 0 && ax + 48 <= Lg[h]->w;  // (uniform) no staged dword crosses the level's left / right side
+    }
+    // the three loads of this lane's window row of half h / their way into the half's slice
+    auto rowLoad = [&](const int h, u32x4_a4* q) {
+      const int hgt = Lg[h]->h;
+      int yy = ky[h] - 21 + lane;
+      yy = yy < 0 ? -yy : yy; yy = yy >= hgt ? 2 * hgt - 2 - yy : yy;  // REFLECT_101 (a keypoint is at least 19 px from the border)
+      // (uniform base + 32-bit lane offset: global_load with an SGPR address)
+      const uint8_t* p = img[h] + (uint32_t)(yy * Lg[h]->stride + ((kx[h] - 21) & ~3));
+      q[0] = *reinterpret_cast<const u32x4_a4*>(p); q[1] = *reinterpret_cast<const u32x4_a4*>(p + 16);
+      q[2] = *reinterpret_cast<const u32x4_a4*>(p + 32);
+    };
+    auto rowStore = [&](const int h, const u32x4_a4* q) {
+      uint32_t* dst = lds + h * PW_WAVE_WORDS + lane * PW_WORDS;
+      dst[0] = q[0].x; dst[1] = q[0].y; dst[2] = q[0].z; dst[3] = q[0].w; dst[4] = q[1].x; dst[5] = q[1].y; dst[6] = q[1].z; dst[7] = q[1].w;
+      dst[8] = q[2].x; dst[9] = q[2].y; dst[10] = q[2].z; dst[11] = q[2].w;
+    };
+    // the window crosses the level's left / right side (or level 0 is not dword-aligned): lanes 0..51 = 4 rows x 13 dwords per
+    // step; dwords inside the level by dword loads, the others byte by byte with REFLECT_101
+    auto sideStage = [&](const int h) {
+      uint32_t* raw = lds + h * PW_WAVE_WORDS;
+      const int w = Lg[h]->w, hgt = Lg[h]->h, stride = Lg[h]->stride;
       const int rsub = lane / PW_WORDS, d = lane - rsub * PW_WORDS;
-      const int xs = ax + 4 * d;
+      const int xs = ((kx[h] - 21) & ~3) + 4 * d;
       const bool active = lane < 4 * PW_WORDS;
-      const bool fastx = aligned && xs >= 0 && xs + 4 <= w;
+      const bool fastx = aligned[h] && xs >= 0 && xs + 4 <= w;
 #pragma unroll
       for (int it = 0; it < 11; it++) {
         const int r = it * 4 + rsub;
         if (active && fastx && r < PW_ROWS) {
-          int yy = ky - 21 + r;
-          yy = yy < 0 ? -yy : yy; yy = yy >= h ? 2 * h - 2 - yy : yy;
-          raw[it * (4 * PW_WORDS) + lane] = *reinterpret_cast<const uint32_t*>(img + (yy * stride + xs));
+          int yy = ky[h] - 21 + r;
+          yy = yy < 0 ? -yy : yy; yy = yy >= hgt ? 2 * hgt - 2 - yy : yy;
+          raw[it * (4 * PW_WORDS) + lane] = *reinterpret_cast<const uint32_t*>(img[h] + (yy * stride + xs));
         }
       }
       if (active && !fastx) {
         for (int r = rsub; r < PW_ROWS; r += 4) {
-          int yy = ky - 21 + r;
-          yy = yy < 0 ? -yy : yy; yy = yy >= h ? 2 * h - 2 - yy : yy;
-          const uint8_t* row = img + (long long)yy * stride;
+          int yy = ky[h] - 21 + r;
+          yy = yy < 0 ? -yy : yy; yy = yy >= hgt ? 2 * hgt - 2 - yy : yy;
+          const uint8_t* row = img[h] + (long long)yy * stride;
           uint32_t word = 0;
 #pragma unroll
           for (int b = 0; b < 4; b++) {
@@ -1408,18 +1473,39 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
           raw[r * PW_WORDS + d] = word;
         }
       }
+    };
+    if (KPW == 2 && rowsInside[0] && rowsInside[KPW - 1]) {
+      if (lane < PW_ROWS) {
+        u32x4_a4 qa[3], qb[3];
+        rowLoad(0, qa); rowLoad(KPW - 1, qb);
+        rowStore(0, qa); rowStore(KPW - 1, qb);
+      }
+    } else {
+#pragma unroll
+      for (int h = 0; h < KPW; h++) {
+        if (rowsInside[h]) {
+          if (lane < PW_ROWS) {
+            u32x4_a4 q[3];
+            rowLoad(h, q); rowStore(h, q);
+          }
+        } else {
+          sideStage(h);
+        }
+      }
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  // ---- IC_Angle (cpp:103-159) on the un-blurred window: pixel (u, v) is row 21+v, byte s+21+u.  Lane = disc row v;
-  //      the row's bytes u = -15..16 are 8 dwords, each weighted with v_dot4_u32_u8 (tables d_ic) ----
-  if (lane < 31) {
-    const int v = lane - 15;
+  // ---- IC_Angle (cpp:103-159) on the un-blurred window: pixel (u, v) is row 21+v, byte s+21+u.  Lane = disc row v (pair form:
+  //      lanes 0..30 keypoint A, lanes 32..62 keypoint B, each half on its own slice and its own two sums); the row's bytes
+  //      u = -15..16 are 8 dwords, each weighted with v_dot4_u32_u8 (tables d_ic) ----
+  if (rl < 31) {
+    const int v = rl - 15;
     const uint32_t w1[8] = {w1a.x, w1a.y, w1a.z, w1a.w, w1b.x, w1b.y, w1b.z, w1b.w};
     const uint32_t wu[8] = {wua.x, wua.y, wua.z, wua.w, wub.x, wub.y, wub.z, wub.w};
-    const uint32_t* rowp = raw + (6 + lane) * PW_WORDS + ((s + 6) >> 2);  // row 21 + v, first dword holding u = -15
-    const uint32_t sh = (uint32_t)(s + 6) & 3u;
+    const int sl = hl ? s[KPW - 1] : s[0];  // this half's byte shift
+    const uint32_t* rowp = lds + hl * PW_WAVE_WORDS + (6 + rl) * PW_WORDS + ((sl + 6) >> 2);  // row 21 + v, first dword holding u = -15
+    const uint32_t sh = (uint32_t)(sl + 6) & 3u;
     uint32_t src[9];
 #pragma unroll
     for (int j = 0; j < 9; j++) src[j] = rowp[j];
@@ -1430,76 +1516,86 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
       sumI = __builtin_amdgcn_udot4(B, w1[j], sumI, false);
       sumU = __builtin_amdgcn_udot4(B, wu[j], sumU, false);
     }
-    atomicAdd(&msum[0], (int)sumU - 15 * (int)sumI);  // m10 = sum u*I
-    atomicAdd(&msum[1], v * (int)sumI);                // m01 = sum v*I
+    atomicAdd(&msumL[0], (int)sumU - 15 * (int)sumI);  // m10 = sum u*I
+    atomicAdd(&msumL[1], v * (int)sumI);                // m01 = sum v*I
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  const int m10 = msum[0], m01 = msum[1];
-  const float angle = fast_atan2_deg((float)m01, (float)m10);
-  // ---- 7x7 Gaussian on the matrix cores (the comment at BlurFrags has the arithmetic and the k order).
+  // (pair form: every lane of a half reads its half's sums; lanes 0 and 32 are the ones read back)
+  const int m10 = msumL[0], m01 = msumL[1];
+  const float angleL = KPW == 2 ? fast_atan2_deg_sel((float)m01, (float)m10) : fast_atan2_deg((float)m01, (float)m10);
+  // ---- 7x7 Gaussian on the matrix cores (the comment at BlurFrags has the arithmetic and the k order), one keypoint after the
+  //      other on the same registers.
   //      A operand of the horizontal product: row (lane & 15) + 16 t of the window, dwords q, q + 4, q + 8 (q = lane >> 4), as
   //      signed bytes (pixel - 128), in the pairs (q, q + 4) and (q + 4, q + 8).  They are read before anything overwrites the
   //      window. ----
-  const uint2 fg = *reinterpret_cast<const uint2*>(bf.w[s][lane]);
-  const v2i_t fgP = {(int)fg.x, (int)fg.y}, fgX = {(int)fg.y, (int)fg.x};
   const v2i_t fvP = {(int)fv.x, (int)fv.y}, fvX = {(int)fv.y, (int)fv.x};
-  v2i_t a01[3], a12[3];
-  {
-    const uint32_t* ap = raw + (lane & 15) * PW_WORDS + (lane >> 4);
+  uint2 fgs[KPW];
 #pragma unroll
-    for (int t = 0; t < 3; t++) {
-      const uint32_t m = ap[16 * t * PW_WORDS + 4];
-      a01[t][0] = (int)(ap[16 * t * PW_WORDS] ^ 0x80808080u);
-      a01[t][1] = (int)(m ^ 0x80808080u);
-      a12[t][0] = (int)(blurTwin(m) ^ 0x80808080u);
-      a12[t][1] = (int)(ap[16 * t * PW_WORDS + 8] ^ 0x80808080u);
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  {
-    constexpr int S = GV ? 257 : 256, CLO = 128 * S * S + 32768;
-    const int col = lane & 15, q4 = lane >> 4;
+  for (int h = 0; h < KPW; h++) fgs[h] = *reinterpret_cast<const uint2*>(bf.w[s[h]][lane]);
 #pragma unroll
-    for (int tn = 0; tn < 3; tn++) {
-      // H, columns 16 tn .. + 15: three row tiles; this lane ends up with rows 16 t + 4 q4 + b of column 16 tn + col
-      v4i_t hh[3];
-#pragma unroll
-      for (int t = 0; t < 3; t++)
-        hh[t] = blurMfma(tn == 0 ? a01[t] : a12[t], tn == 2 ? fgX : fgP, v4i_t{128, 128, 128, 128});
-      // hi = byte 1, lo = byte 0 ^ 0x80 of the four rows of a tile: one operand dword each (4 v_perm_b32 + 1 xor per tile; the
-      // middle tile's pair is made twice, once for each operand pair it belongs to)
-      v2i_t h01, h12, l01, l12;
+  for (int h = 0; h < KPW; h++) {
+    uint32_t* const raw = lds + h * PW_WAVE_WORDS;
+    uint32_t* const bl32 = raw;
+    const uint2 fg = fgs[h];
+    const v2i_t fgP = {(int)fg.x, (int)fg.y}, fgX = {(int)fg.y, (int)fg.x};
+    v2i_t a01[3], a12[3];
+    {
+      const uint32_t* ap = raw + (lane & 15) * PW_WORDS + (lane >> 4);
 #pragma unroll
       for (int t = 0; t < 3; t++) {
-        const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)hh[t][1], (uint32_t)hh[t][0], 0x04000501u);
-        const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)hh[t][3], (uint32_t)hh[t][2], 0x04000501u);
-        const int hi = (int)__builtin_amdgcn_perm(x23, x01, 0x05040100u);
-        const uint32_t lo = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
-        if (t == 0) { h01[0] = hi; l01[0] = (int)(lo ^ 0x80808080u); }
-        if (t == 1) {
-          h01[1] = hi; l01[1] = (int)(lo ^ 0x80808080u);
-          h12[0] = (int)__builtin_amdgcn_perm(blurTwin(x23), x01, 0x05040100u); l12[0] = (int)(blurTwin(lo) ^ 0x80808080u);
-        }
-        if (t == 2) { h12[1] = hi; l12[1] = (int)(lo ^ 0x80808080u); }
+        const uint32_t m = ap[16 * t * PW_WORDS + 4];
+        a01[t][0] = (int)(ap[16 * t * PW_WORDS] ^ 0x80808080u);
+        a01[t][1] = (int)(m ^ 0x80808080u);
+        a12[t][0] = (int)(blurTwin(m) ^ 0x80808080u);
+        a12[t][1] = (int)(ap[16 * t * PW_WORDS + 8] ^ 0x80808080u);
       }
-      // Out, rows 16 to .. + 15 of these columns; the four rows a lane holds are one dword of the column-major blurred patch
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    {
+      constexpr int S = GV ? 257 : 256, CLO = 128 * S * S + 32768;
+      const int col = lane & 15, q4 = lane >> 4;
 #pragma unroll
-      for (int to = 0; to < 3; to++) {
-        if (tn == 2 && to == 2) continue;
-        const v2i_t av = to == 2 ? fvX : fvP;
-        const v4i_t oh = blurMfma(av, to == 0 ? h01 : h12, v4i_t{0, 0, 0, 0});
-        const v4i_t ol = blurMfma(av, to == 0 ? l01 : l12, v4i_t{CLO, CLO, CLO, CLO});
-        uint32_t o[4];
+      for (int tn = 0; tn < 3; tn++) {
+        // H, columns 16 tn .. + 15: three row tiles; this lane ends up with rows 16 t + 4 q4 + b of column 16 tn + col
+        v4i_t hh[3];
 #pragma unroll
-        for (int b = 0; b < 4; b++) {
-          o[b] = (uint32_t)((oh[b] << 8) + ol[b]);
-          if (GV) o[b] = min(o[b], 0xffffffu);  // taps that sum to 257: saturate_cast<uchar>
+        for (int t = 0; t < 3; t++)
+          hh[t] = blurMfma(tn == 0 ? a01[t] : a12[t], tn == 2 ? fgX : fgP, v4i_t{128, 128, 128, 128});
+        // hi = byte 1, lo = byte 0 ^ 0x80 of the four rows of a tile: one operand dword each (4 v_perm_b32 + 1 xor per tile; the
+        // middle tile's pair is made twice, once for each operand pair it belongs to)
+        v2i_t h01, h12, l01, l12;
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+          const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)hh[t][1], (uint32_t)hh[t][0], 0x04000501u);
+          const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)hh[t][3], (uint32_t)hh[t][2], 0x04000501u);
+          const int hi = (int)__builtin_amdgcn_perm(x23, x01, 0x05040100u);
+          const uint32_t lo = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
+          if (t == 0) { h01[0] = hi; l01[0] = (int)(lo ^ 0x80808080u); }
+          if (t == 1) {
+            h01[1] = hi; l01[1] = (int)(lo ^ 0x80808080u);
+            h12[0] = (int)__builtin_amdgcn_perm(blurTwin(x23), x01, 0x05040100u); l12[0] = (int)(blurTwin(lo) ^ 0x80808080u);
+          }
+          if (t == 2) { h12[1] = hi; l12[1] = (int)(lo ^ 0x80808080u); }
         }
-        // each sum is < 2^24: its blurred byte is bits 16..23; v_perm_b32 gathers byte 2 of four sums into one dword
-        bl32[(16 * tn + col) * (BL_STRIDE / 4) + 4 * to + q4] =
-            __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0602u) | __builtin_amdgcn_perm(o[3], o[2], 0x06020c0cu);
+        // Out, rows 16 to .. + 15 of these columns; the four rows a lane holds are one dword of the column-major blurred patch
+#pragma unroll
+        for (int to = 0; to < 3; to++) {
+          if (tn == 2 && to == 2) continue;
+          const v2i_t av = to == 2 ? fvX : fvP;
+          const v4i_t oh = blurMfma(av, to == 0 ? h01 : h12, v4i_t{0, 0, 0, 0});
+          const v4i_t ol = blurMfma(av, to == 0 ? l01 : l12, v4i_t{CLO, CLO, CLO, CLO});
+          uint32_t o[4];
+#pragma unroll
+          for (int b = 0; b < 4; b++) {
+            o[b] = (uint32_t)((oh[b] << 8) + ol[b]);
+            if (GV) o[b] = min(o[b], 0xffffffu);  // taps that sum to 257: saturate_cast<uchar>
+          }
+          // each sum is < 2^24: its blurred byte is bits 16..23; v_perm_b32 gathers byte 2 of four sums into one dword
+          bl32[(16 * tn + col) * (BL_STRIDE / 4) + 4 * to + q4] =
+              __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0602u) | __builtin_amdgcn_perm(o[3], o[2], 0x06020c0cu);
+        }
       }
     }
   }
@@ -1511,45 +1607,74 @@ __global__ __launch_bounds__(64 * DESC_WAVES, 7) void k_describe_patch(const uin
   float4 pat[4];
 #pragma unroll
   for (int wq = 0; wq < 4; wq++) pat[wq] = reinterpret_cast<const float4*>(d_patternf.v)[wq * 64 + lane];
-  const uint8_t* bl = reinterpret_cast<const uint8_t*>(bl32);
   const float factorPI = (float)(3.14159265358979323846 / 180.f);
-  float cs, sn;
+  float csL, snL;
   if (libmFloat) {  // (uniform) ORBX_LIBM_FLOAT
-    sincosfGlibc(angle * factorPI, &sn, &cs);
+    sincosfGlibc(angleL * factorPI, &snL, &csL);
   } else {
     double sd, cd;
-    sincosTable<true>((double)(angle * factorPI), &sd, &cd);
-    cs = (float)cd; sn = (float)sd;
+    sincosTable<KPW == 1>((double)(angleL * factorPI), &sd, &cd);  // (pair form: the table entry per lane)
+    csL = (float)cd; snL = (float)sd;
   }
-  unsigned long long words[4];
+  // pair form: the three values of a keypoint go from its half's first lane to SGPRs
+  float angle[KPW], cs[KPW], sn[KPW];
 #pragma unroll
-  for (int wq = 0; wq < 4; wq++) {
-    const float4 pt = pat[wq];
-    const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
-    // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + c) * 48 + 18 + r (column-major) in one go:
-    // v + 1.5 * 2^23 rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits; the low
-    // 24 bits (0x400000 + c) go through v_mad_u32_u24, the constants are taken off at the end
-    constexpr float MAGIC = 12582912.f;
-    constexpr uint32_t OFF = (uint32_t)BL_STRIDE * 0x400000u + 0x4B400000u - (18u * BL_STRIDE + 18u);
-    const uint32_t ir0 = __float_as_uint((x0 * sn + y0 * cs) + MAGIC), ic0 = __float_as_uint((x0 * cs - y0 * sn) + MAGIC);
-    const uint32_t ir1 = __float_as_uint((x1 * sn + y1 * cs) + MAGIC), ic1 = __float_as_uint((x1 * cs - y1 * sn) + MAGIC);
-    const int t0 = bl[(ic0 & 0xffffffu) * (uint32_t)BL_STRIDE + ir0 - OFF];
-    const int t1 = bl[(ic1 & 0xffffffu) * (uint32_t)BL_STRIDE + ir1 - OFF];
-    words[wq] = __ballot(t0 < t1);
+  for (int h = 0; h < KPW; h++) {
+    if constexpr (KPW == 2) {
+      angle[h] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(angleL), 32 * h));
+      cs[h] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(csL), 32 * h));
+      sn[h] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(snL), 32 * h));
+    } else {
+      angle[h] = angleL; cs[h] = csL; sn[h] = snL;
+    }
   }
+  unsigned long long words[KPW][4];
+#pragma unroll
+  for (int h = 0; h < KPW; h++) {
+    const uint8_t* bl = reinterpret_cast<const uint8_t*>(lds + h * PW_WAVE_WORDS);
+#pragma unroll
+    for (int wq = 0; wq < 4; wq++) {
+      const float4 pt = pat[wq];
+      const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
+      // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + c) * 48 + 18 + r (column-major) in one go:
+      // v + 1.5 * 2^23 rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits; the low
+      // 24 bits (0x400000 + c) go through v_mad_u32_u24, the constants are taken off at the end
+      constexpr float MAGIC = 12582912.f;
+      constexpr uint32_t OFF = (uint32_t)BL_STRIDE * 0x400000u + 0x4B400000u - (18u * BL_STRIDE + 18u);
+      const uint32_t ir0 = __float_as_uint((x0 * sn[h] + y0 * cs[h]) + MAGIC), ic0 = __float_as_uint((x0 * cs[h] - y0 * sn[h]) + MAGIC);
+      const uint32_t ir1 = __float_as_uint((x1 * sn[h] + y1 * cs[h]) + MAGIC), ic1 = __float_as_uint((x1 * cs[h] - y1 * sn[h]) + MAGIC);
+      const int t0 = bl[(ic0 & 0xffffffu) * (uint32_t)BL_STRIDE + ir0 - OFF];
+      const int t1 = bl[(ic1 & 0xffffffu) * (uint32_t)BL_STRIDE + ir1 - OFF];
+      words[h][wq] = __ballot(t0 < t1);
+    }
+  }
+  // lane 0 stores keypoint A's descriptor and record, lane 1 (pair form) keypoint B's: the words are SGPR pairs, a lane's 32 bytes
+  // are eight moves (and eight selects between A and B) and two 16-byte stores (8-byte aligned, as the u64 stores before them)
   const long long o = (long long)f * capacity + i;
-  if (lane < 4) reinterpret_cast<unsigned long long*>(desc + o * 32)[lane] = words[lane];
-  if (lane == 0) {
+  const int nLive = KPW == 2 && liveB ? 2 : 1;
+  if (lane < nLive) {
+    const bool hb = KPW == 2 && lane != 0;
+    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+    u32x4_a8 dq[2];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const unsigned long long wd = hb ? words[KPW - 1][j] : words[0][j];
+      dq[j >> 1][2 * (j & 1)] = (uint32_t)wd; dq[j >> 1][2 * (j & 1) + 1] = (uint32_t)(wd >> 32);
+    }
+    u32x4_a8* dp = reinterpret_cast<u32x4_a8*>(desc + (o + lane) * 32);
+    dp[0] = dq[0]; dp[1] = dq[1];
+    const int lv = hb ? level[KPW - 1] : level[0], kxl = hb ? kx[KPW - 1] : kx[0], kyl = hb ? ky[KPW - 1] : ky[0];
+    const float scale = hb ? Lg[KPW - 1]->scale : Lg[0]->scale;
     orbx_keypoint kp;
     // cpp:1631-1634: pt *= scale for level != 0 (scale[0] == 1 exactly)
-    kp.x = k.level ? (float)kx * L.scale : (float)kx;
-    kp.y = k.level ? (float)ky * L.scale : (float)ky;
-    kp.size = (float)L.patchSize;
-    kp.angle = angle;
-    kp.response = (float)k.response;
-    kp.octave = k.level;
+    kp.x = lv ? (float)kxl * scale : (float)kxl;
+    kp.y = lv ? (float)kyl * scale : (float)kyl;
+    kp.size = (float)(hb ? Lg[KPW - 1]->patchSize : Lg[0]->patchSize);
+    kp.angle = hb ? angle[KPW - 1] : angle[0];
+    kp.response = (float)(hb ? k[KPW - 1].response : k[0].response);
+    kp.octave = lv;
     kp.class_id = -1;
-    kps[o] = kp;
+    kps[o + lane] = kp;
   }
 }
 
@@ -3275,9 +3400,11 @@ hipError_t launch_describe_patch(hipStream_t st, int nFrames, int maxSel, const 
                                  orbx_keypoint* kps, uint8_t* desc, int capacity, int gaussVariant, int libmFloat,
                                  const DescStage* staged) {
   // staged (optional): the selection's staging lists -- the kernel indexes them itself and writes the frames' totals (the caller
-  // launched no k_sel_compact; see DescStage)
+  // launched no k_sel_compact; see DescStage), one keypoint per wave: such a launch cannot fill the chip, and a wave that lasts
+  // twice as long is pure latency there.  Otherwise (k_sel_compact's list) two keypoints per wave.
   if (maxSel <= 0 && !staged) return hipSuccess;
-  dim3 block(64 * DESC_WAVES, 1, 1), grid(((maxSel + DESC_WAVES - 1) / DESC_WAVES + 7) / 8 * 8, nFrames, 1);  // x: multiple of 8
+  const int perGroup = staged ? DESC_WAVES : 2 * DESC_PAIR_WAVES;  // keypoints per workgroup
+  dim3 block(64 * (staged ? DESC_WAVES : DESC_PAIR_WAVES), 1, 1), grid(((maxSel + perGroup - 1) / perGroup + 7) / 8 * 8, nFrames, 1);  // x: multiple of 8
   const DescStage none = {};
   if (staged) {
     if (gaussVariant)
@@ -3287,10 +3414,10 @@ hipError_t launch_describe_patch(hipStream_t st, int nFrames, int maxSel, const 
       hipLaunchKernelGGL((k_describe_patch<0, true>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                          desc, capacity, *staged, libmFloat);
   } else if (gaussVariant)
-    hipLaunchKernelGGL((k_describe_patch<1, false>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+    hipLaunchKernelGGL((k_describe_patch<1, false, 2>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                        desc, capacity, none, libmFloat);
   else
-    hipLaunchKernelGGL((k_describe_patch<0, false>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
+    hipLaunchKernelGGL((k_describe_patch<0, false, 2>), grid, block, 0, st, img0, img0FrameStride, img0Aligned, pyr, g, sel, nsel, kps,
                        desc, capacity, none, libmFloat);
   return hipGetLastError();
 }
