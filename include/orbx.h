@@ -987,6 +987,117 @@ int orbx_match_projection(orbx_ctx* ctx, const orbx_keypoint* last_kps_un, const
                           const float* K, const orbx_bounds* bounds, float th, int check_orientation, int32_t* matches_cur,
                           orbx_proj_result* res);
 
+/* ---- matching the local map by projection: ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) ---------------
+ * The second half of a tracked frame, Tracking::TrackLocalMap: SearchLocalPoints marks the map points the frame already has,
+ * tests every other point of the local map with Frame::isInFrustum(pMP, 0.5), predicts its scale (MapPoint::PredictScale) and
+ * matches the points in view inside a window of the frame's grid; PoseOptimization follows.  The reference ships neither
+ * isInFrustum nor this overload: this is ORB-SLAM2's code, [from-knowledge], PARITY UNPINNED, bit-identical to a CPU restatement
+ * of the rules below (tests/cpp/match_local_ref.cpp).  The window search alone is pinned: it is the reference's
+ * Frame::GetFeaturesInArea (SlamTypes/Frame.cpp:163-206), and the tests compare it with the reference's own compiled code.
+ *
+ * Pair p: frame F = h_frame[p], map set s = h_map_set[p] with n_s = d_map_n[s] points, F's pose d_pose[p] (12 floats: R
+ * row-major, then t), the row d_matches[p] (feature j's map point as an index into set s, or a negative value).
+ *   1. the points F already has (SearchLocalPoints' first loop, with TrackWithMotionModel's clean-up), over F's features j with
+ *      i = d_matches[p][j] >= 0: i >= n_s is never followed -- the entry stays, feature j counts as taken and
+ *      ORBX_LOCAL_BAD_INPUT is set.  Otherwise point i is "seen" and is not searched; with d_outlier[p][j] != 0 the entry
+ *      becomes -1 and feature j is free (the point stays seen: ORB-SLAM2 sets mnLastFrameSeen for a discarded outlier too),
+ *      without it feature j is taken.  A negative entry is left as it is.
+ *   2. isInFrustum(pMP, 0.5) for every point i that is not seen and whose mask byte is set, in ascending i; f32 without
+ *      contraction unless said otherwise.  Pc = R*P + t as xc = ((R0*X + R1*Y) + R2*Z) + t0, yc and zc likewise; PcZ < 0.0f:
+ *      out.  invz = 1.0f / PcZ correctly rounded; u = (fx*PcX)*invz + cx, v = (fy*PcY)*invz + cy; u or v not finite: out; u <
+ *      min_x || u > max_x || v < min_y || v > max_y: out (a value on a bound stays).  The camera centre Ow_k = -((R[0][k]*t0 +
+ *      R[1][k]*t1) + R[2][k]*t2); PO = P - Ow; dist = (float)sqrt((double)POx*POx + (double)POy*POy + (double)POz*POz), the
+ *      products and sums in f64 in that order (cv::norm of a CV_32F vector); dist < 0.8f*minDist || dist > 1.2f*maxDist: out;
+ *      viewCos = (float)(((double)POx*Nx + (double)POy*Ny + (double)POz*Nz) / (double)dist) with the normal as given;
+ *      viewCos < 0.5f: out
+ *   3. PredictScale: ratio = maxDist / dist (the raw mfMaxDistance; correctly rounded); a ratio that is no number sets
+ *      ORBX_LOCAL_NONFINITE and drops the point; level = the number of n in [0, nlevels - 1) with ratio > scale[n] (the
+ *      context's table, orbx_get_tables; scale[0] = 1).  The point is in view (mbTrackInView, nToMatch)
+ *   4. r = viewCos > 0.998f ? 2.5f : 4.0f; if th != 1.0f, r *= th; the candidates are GetFeaturesInArea(u, v, r*scale[level],
+ *      level - 1, level) over F's undistorted keypoints (the reference's function with its own bCheckLevels reading: PosInGrid's
+ *      rounding, the clamped cell range, octave in [level - 1, level], the strict fabs(d) < r in both coordinates), in the order
+ *      cell x outer, cell y inner, ascending index inside a cell.  No candidate: the point is skipped
+ *   5. over the candidates that are not taken on entry and not taken by an earlier point, in that order, with d =
+ *      popcount(d_map_desc32[s][i] ^ desc_F[j]): if (d < bestDist) { bestDist2 = bestDist; bestLevel2 = bestLevel; bestDist = d;
+ *      bestLevel = octave_j; bestIdx = j; } else if (d < bestDist2) { bestLevel2 = octave_j; bestDist2 = d; } -- both distances
+ *      start at 256, both levels at -1.  (That stream is "the two smallest under the key (d, position in the order of 4)".)
+ *   6. bestDist <= 100 (TH_HIGH) is required; the point is rejected when bestLevel == bestLevel2 && (float)bestDist >
+ *      nnratio*(float)bestDist2; otherwise d_matches[p][bestIdx] = i and bestIdx is taken.  This overload has no rotation
+ *      histogram.
+ * Documented deviations from ORB-SLAM2:
+ *   1. PredictScale in table form: ORB-SLAM2 takes ceil(log(ratio) / mfLogScaleFactor) clamped to [0, nlevels - 1].  The count
+ *      of table entries below the ratio is the same number except where the ratio lies within rounding of a table entry, and
+ *      needs no libm on either side.
+ *   2. "Taken" stands for `F.mvpMapPoints[idx]->Observations() > 0`: every map point counts as observed (deviation 2 of
+ *      matching by projection above).
+ *   3. No stereo branch: no mvuRight test.
+ *   4. Map points are arrays plus a mask (0 = isBad() or absent), matches are indices into the pair's map set.
+ *   5. Garbage is flagged and never followed.  Counts outside [0, capacity] / [0, map_capacity] are clamped and set
+ *      ORBX_LOCAL_BAD_INPUT, as does an entry of d_matches >= n_s.  A non-finite pose sets ORBX_LOCAL_NONFINITE and drops every
+ *      point of step 2; a point of step 2 whose position, normal or two distances hold a non-finite value sets it and is
+ *      dropped, as is one whose ratio is no number.  u or v that is no number is out of the image (the design's comparisons
+ *      would let a NaN through).  A keypoint whose cell is no number is in no cell; window cells are clamped as floats.
+ * Translating the last-frame feature indices that orbx_match_projection* writes into map-set indices is the caller's gather
+ * (map index of the last frame's feature), as is building the local map (UpdateLocalMap).
+ * Worst case: points whose windows all share candidates resolve one per round (see the kernel); the common case is a handful. */
+#define ORBX_LOCAL_BAD_INPUT 2 /* a count outside its capacity, an entry of d_matches beyond the map set's count */
+#define ORBX_LOCAL_NONFINITE 4 /* a non-finite pose, a non-finite point / normal / distance or ratio of a point of step 2 */
+#define ORBX_LOCAL_NOT_IN_VIEW 0xFF /* d_point_view */
+#define ORBX_LOCAL_SEEN 0xFE
+typedef struct orbx_local_result {
+  int32_t status;             /* 0, or a bitmask of ORBX_LOCAL_*; every field is written for every pair */
+  int32_t nmatches;           /* new matches only */
+  int32_t n_points;           /* points that reach step 2: mask set, not seen */
+  int32_t n_seen;             /* points some entry of d_matches names (whatever their mask) */
+  int32_t n_behind;           /* step 2: PcZ < 0 */
+  int32_t n_out_image;        /* ... u or v not finite or outside the bounds */
+  int32_t n_out_distance;
+  int32_t n_out_angle;
+  int32_t n_in_view;          /* the design's nToMatch */
+  int32_t n_with_candidates;  /* points in view whose window holds a feature (step 4) */
+  int32_t n_over_th;          /* ... whose bestDist is above TH_HIGH (256 when every candidate is taken) */
+  int32_t n_ratio_rejected;
+  int32_t n_displaced;        /* points in view whose outcome (the feature, or none) differs from what they would get with only
+                                 the entry's matches taken */
+  int32_t n_outliers_cleared; /* entries step 1 set to -1 */
+  int32_t rounds;             /* the device's rounds of claims; a sequential statement reports 0 */
+} orbx_local_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  d_kps_un / d_desc32 (16-byte aligned) / d_n: the frames, in
+ * the layout of the extract and undistort calls ([n_frames][capacity]).  Map set s holds d_map_n[s] points of
+ * [n_map_sets][map_capacity]: d_map_points float [3] (world position), d_map_normals float [3] (GetNormal(), used as given),
+ * d_map_dist float [2] (mfMinDistance, mfMaxDistance; the kernel applies the 0.8f and 1.2f), d_map_desc32 uint8 [32] (16-byte
+ * aligned), d_map_mask uint8 (NULL = every entry is a point; 0 = isBad() or absent).  A frame or a map set may be in any number
+ * of pairs.  d_pose float [n_pairs][12].  K row-major 3x3 (host, f32), bounds = the frames' image bounds, th > 0 (Tracking passes
+ * 1, or 5 just after a relocalisation), nnratio in (0, 1] (Tracking passes 0.8).  d_matches int32 [n_pairs][capacity], in and out
+ * and required (a fresh frame is a row of -1): on exit the entry's matches, without those step 1 cleared, plus the new ones;
+ * entries at and beyond the frame's count are not touched.  d_outlier uint8 [n_pairs][capacity] (NULL = none): read only,
+ * orbx_pose_optimize_batch_device's output.  d_point_view uint8 [n_pairs][map_capacity] (NULL = not wanted; Tracking's
+ * IncreaseVisible): for i < n_s ORBX_LOCAL_NOT_IN_VIEW, ORBX_LOCAL_SEEN, or the predicted level of a point in view.
+ * d_res [n_pairs].  With map_capacity == capacity the row is orbx_pose_optimize_batch_device's d_match: with the map set as the
+ * point set (d_points = d_map_points, d_point_mask = d_map_mask) and the same h_frame the two calls chain without a copy.
+ * One workgroup per pair, one launch.  The call returns once queued, with the exception orbx_match_bow_batch_device has: when the
+ * pair lists differ from the previous call's on this context, the call first waits for the context stream before it uploads
+ * them.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity or map_capacity < 1, th not finite or <= 0, nnratio not in
+ * (0, 1], bounds with max <= min, a frame index outside [0, n_frames), a map set outside [0, n_map_sets) -- all checked before
+ * anything touches a device; ORBX_E_CAPACITY: capacity or map_capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with
+ * otherwise well-formed arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_local_map_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_frame, const int32_t* h_map_set,
+                                      const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                      int n_map_sets, int map_capacity, const int32_t* d_map_n, const float* d_map_points,
+                                      const float* d_map_normals, const float* d_map_dist, const uint8_t* d_map_desc32,
+                                      const uint8_t* d_map_mask, const float* d_pose, const float* K, const orbx_bounds* bounds,
+                                      float th, float nnratio, int32_t* d_matches, const uint8_t* d_outlier, uint8_t* d_point_view,
+                                      orbx_local_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: the frame (n features), the map (map_n
+ * points; map_mask nullable), pose [12]; matches [n] in and out, outlier [n] nullable, point_view [map_n] nullable.  More than
+ * ORBX_BOW_MAX_FEATURES features or points: ORBX_E_CAPACITY.  Synchronous. */
+int orbx_match_local_map(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n,
+                         const float* map_points, const float* map_normals, const float* map_dist, const uint8_t* map_desc32,
+                         const uint8_t* map_mask, const float* pose, const float* K, const orbx_bounds* bounds, float th,
+                         float nnratio, int32_t* matches, const uint8_t* outlier, uint8_t* point_view, orbx_local_result* res);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

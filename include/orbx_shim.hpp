@@ -320,6 +320,18 @@ struct FrameView {
 
 struct PoseT;  // (below, with the Initializer)
 
+// The local map as ORBmatcher::SearchByProjection(F, map, th) reads it (orbx.h, "matching the local map by projection"): per map
+// point the world position (GetWorldPos), the normal (GetNormal), mfMinDistance and mfMaxDistance, the descriptor
+// (GetDescriptor) and a flag (null = every entry is a point; 0 = isBad() or absent).
+struct MapView {
+  int N = 0;
+  const float* mWorldPos = nullptr;       // [N][3]
+  const float* mNormalVector = nullptr;   // [N][3]
+  const float* mfMinMaxDistance = nullptr;  // [N][2]
+  const uint8_t* mDescriptors = nullptr;  // [N][32]
+  const uint8_t* mbGood = nullptr;        // [N] or null
+};
+
 class ORBmatcher {
  public:
   // Features/ORBmatcher.hpp:15.  (The optional third argument pins the device context; without it the matcher uses the
@@ -386,6 +398,24 @@ class ORBmatcher {
                          const std::vector<bool>& vbHasPoint, const PoseT& Tcw, std::vector<int>& vnMatchesCur,
                          const std::vector<bool>* vbLastOutlier = nullptr, orbx_proj_result* result = nullptr);
 
+  // Tracking::SearchLocalPoints around ORB-SLAM2's SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float
+  // th) (orbx.h, "matching the local map by projection", with its documented deviations; mfNNratio is this matcher's): the
+  // frustum test, the scale prediction and the window search for every point of `map` the frame does not have yet.
+  // vnMatches[j] = the index into `map` of feature j's map point, or -1 -- in and out: on entry the points F already has
+  // (F.mvpMapPoints; any other size than F.N stands for none), on exit those without the outliers' plus the new ones.  Returns
+  // the number of new matches.  vbOutlier (optional): F.mvbOutlier.  pointView (optional): per map point ORBX_LOCAL_NOT_IN_VIEW,
+  // ORBX_LOCAL_SEEN or the predicted level (what IncreaseVisible needs).  K: 9 floats, row-major.
+  int SearchByProjection(const FrameView& F, const MapView& map, float th, const PoseT& Tcw, const float* K, std::vector<int>& vnMatches,
+                         const std::vector<bool>* vbOutlier = nullptr, std::vector<uint8_t>* pointView = nullptr,
+                         orbx_local_result* result = nullptr) {
+    return searchLocalMap(ext_, F, map, th, Tcw, K, vnMatches, vbOutlier, pointView, result);
+  }
+  // ... for the reference's Frame or any Frame-like type (K from F.mK)
+  template <class FrameT, class = typename std::enable_if<!std::is_same<typename std::decay<FrameT>::type, FrameView>::value>::type>
+  int SearchByProjection(FrameT& F, const MapView& map, float th, const PoseT& Tcw, std::vector<int>& vnMatches,
+                         const std::vector<bool>* vbOutlier = nullptr, std::vector<uint8_t>* pointView = nullptr,
+                         orbx_local_result* result = nullptr);
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -404,6 +434,9 @@ class ORBmatcher {
   int searchByProjection(ORBextractor* e, const FrameView& C, const FrameView& L, float th, const std::vector<Point3>& vP3D,
                          const std::vector<bool>& vbHasPoint, const PoseT& Tcw, const float* K, std::vector<int>& vnMatchesCur,
                          const std::vector<bool>* vbLastOutlier, orbx_proj_result* result);  // (defined behind PoseT)
+  inline int searchLocalMap(ORBextractor* e, const FrameView& F, const MapView& map, float th, const PoseT& Tcw, const float* K,
+                            std::vector<int>& vnMatches, const std::vector<bool>* vbOutlier, std::vector<uint8_t>* pointView,
+                            orbx_local_result* result);  // (defined behind PoseT)
 
   int search(ORBextractor* e, const FrameView& F1, const FrameView& F2, std::vector<int>& vnMatches12, int windowSize) {
     if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
@@ -667,6 +700,40 @@ int ORBmatcher::searchByProjection(ORBextractor* e, const FrameView& C, const Fr
   if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
   if (result) *result = res;
   return res.nmatches;
+}
+
+inline int ORBmatcher::searchLocalMap(ORBextractor* e, const FrameView& F, const MapView& map, float th, const PoseT& Tcw, const float* K,
+                                      std::vector<int>& vnMatches, const std::vector<bool>* vbOutlier, std::vector<uint8_t>* pointView,
+                                      orbx_local_result* result) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frame carries none and none was set");
+  const size_t n = (size_t)F.N;
+  if (vbOutlier && vbOutlier->size() != n) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchByProjection: vbOutlier needs F.N entries");
+  float pose[12];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) pose[r * 3 + c] = (float)Tcw(r, c);
+    pose[9 + r] = (float)Tcw(r, 3);
+  }
+  if (vnMatches.size() != n) vnMatches.assign(n, -1);
+  std::vector<uint8_t> out(n ? n : 1), view((size_t)(map.N > 0 ? map.N : 1));
+  for (size_t j = 0; j < n; j++) out[j] = vbOutlier && (*vbOutlier)[j] ? 1 : 0;
+  const orbx_bounds b{F.mnMinX, F.mnMaxX, F.mnMinY, F.mnMaxY};
+  orbx_local_result res;
+  const int r = orbx_match_local_map(e->context(), reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn), F.mDescriptors, F.N, map.N,
+                                     map.mWorldPos, map.mNormalVector, map.mfMinMaxDistance, map.mDescriptors, map.mbGood, pose, K, &b,
+                                     th, mfNNratio, vnMatches.data(), vbOutlier ? out.data() : nullptr, view.data(), &res);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  if (pointView) pointView->assign(view.begin(), view.begin() + (map.N > 0 ? map.N : 0));
+  if (result) *result = res;
+  return res.nmatches;
+}
+
+template <class FrameT, class>
+int ORBmatcher::SearchByProjection(FrameT& F, const MapView& map, float th, const PoseT& Tcw, std::vector<int>& vnMatches,
+                                   const std::vector<bool>* vbOutlier, std::vector<uint8_t>* pointView, orbx_local_result* result) {
+  float K[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) K[r * 3 + c] = frameK(F.mK, r, c);
+  return searchLocalMap(ext_ ? ext_ : F.mpORBextractor, frameView(F), map, th, Tcw, K, vnMatches, vbOutlier, pointView, result);
 }
 
 template <class FrameT, class Point3, class>

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -157,6 +157,23 @@ class ProjResult(ctypes.Structure):
 
 PROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in PROJ_RESULT_FIELDS])
 assert PROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(ProjResult) == 32
+
+
+LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
+LOCAL_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_seen", "n_behind", "n_out_image", "n_out_distance", "n_out_angle", "n_in_view",
+                       "n_with_candidates", "n_over_th", "n_ratio_rejected", "n_displaced", "n_outliers_cleared", "rounds")
+
+
+class LocalResult(ctypes.Structure):
+    """orbx_local_result: SearchLocalPoints' counters for one (frame, map set) pair (rounds is the device's own count)."""
+    _fields_ = [(n, ctypes.c_int32) for n in LOCAL_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+LOCAL_RESULT_DTYPE = np.dtype([(n, "<i4") for n in LOCAL_RESULT_FIELDS])
+assert LOCAL_RESULT_DTYPE.itemsize == ctypes.sizeof(LocalResult) == 60
 
 
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
@@ -303,6 +320,10 @@ def lib() -> ctypes.CDLL:
                                                      ctypes.POINTER(_Bounds), f32, i32, vp, vp]
     L.orbx_match_projection.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp,
                                         ctypes.POINTER(ProjResult)]
+    L.orbx_match_local_map_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    ctypes.POINTER(_Bounds), f32, f32, vp, vp, vp, vp]
+    L.orbx_match_local_map.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, f32, vp, vp, vp,
+                                       ctypes.POINTER(LocalResult)]
     L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.orbx_database_destroy.argtypes = [vp]
     L.orbx_database_destroy.restype = None
@@ -746,6 +767,94 @@ class ORBextractor:
                                           ctypes.byref(res))
         self._check(r, "orbx_match_projection")
         return mc[:len(ck)].copy(), res
+
+    def match_local_map_pairs_device(self, n_frames: int, frame: np.ndarray, map_set: np.ndarray, d_kps_un, d_desc, d_n,
+                                     n_map_sets: int, map_capacity: int, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc,
+                                     d_map_mask, d_pose, K, bounds: Tuple[int, int, int, int], d_matches, d_res, th: float = 1.0,
+                                     nnratio: float = 0.8, d_outlier=None, d_point_view=None, capacity: Optional[int] = None) -> None:
+        """Tracking::SearchLocalPoints -- isInFrustum, PredictScale and ORBmatcher::SearchByProjection(Frame, local map points,
+        th) -- for pairs (frame frame[p], map set map_set[p]; host index arrays) of the arrays extract_batch_device and
+        undistort_batch_device filled and of map sets [n_map_sets, map_capacity]: d_map_n int32 counts, d_map_points and
+        d_map_normals float32 [.., 3], d_map_dist float32 [.., 2] (mfMinDistance, mfMaxDistance), d_map_desc uint8 [.., 32],
+        d_map_mask uint8 or None; d_pose float32 [n_pairs, 12].  d_matches int32 [n_pairs, capacity] is read and written: feature
+        j's index into the pair's map set, or -1 (with map_capacity == capacity: pose_optimize_batch_device's d_match).
+        Optional: d_outlier uint8 [n_pairs, capacity] (read only), d_point_view uint8 [n_pairs, map_capacity] (LOCAL_NOT_IN_VIEW,
+        LOCAL_SEEN or the predicted level).  d_res [n_pairs] LOCAL_RESULT_DTYPE records (60 bytes).  Stream-ordered on the
+        context's stream."""
+        frame = np.ascontiguousarray(frame, np.int32).reshape(-1)
+        map_set = np.ascontiguousarray(map_set, np.int32).reshape(-1)
+        if len(frame) != len(map_set):
+            raise OrbxError(E_BADARG, "frame and map_set must have the same length")
+        cap, mcap, nf, ns, P = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets), len(frame)
+        # (as unsigned, a negative index is a huge one)
+        if P and int(frame.view(np.uint32).max()) >= nf:
+            raise ValueError("a pair names a frame outside the batch of %d" % nf)
+        if P and int(map_set.view(np.uint32).max()) >= ns:
+            raise ValueError("a pair names a map set outside the %d given" % ns)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the map count array", d_map_n, ns * 4)
+        _need("the map point array", d_map_points, ns * mcap * 12)
+        _need("the map normal array", d_map_normals, ns * mcap * 12)
+        _need("the map distance array", d_map_dist, ns * mcap * 8)
+        _need("the map descriptor array", d_map_desc, ns * mcap * 32)
+        if d_map_mask is not None:
+            _need("the map mask", d_map_mask, ns * mcap)
+        if d_outlier is not None:
+            _need("the outlier array", d_outlier, P * cap)
+        if d_point_view is not None:
+            _need("point_view", d_point_view, P * mcap)
+        _need("the pose array", d_pose, P * 48)
+        _need("matches", d_matches, P * cap * 4)
+        _need("the result array", d_res, P * LOCAL_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_outlier,
+                          d_point_view, d_pose, d_matches, d_res)
+        r = self._L.orbx_match_local_map_batch_device(self._h, nf, P, _ptr(frame), _ptr(map_set), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n),
+                                                      cap, ns, mcap, _ptr(d_map_n), _ptr(d_map_points), _ptr(d_map_normals),
+                                                      _ptr(d_map_dist), _ptr(d_map_desc), _ptr(d_map_mask), _ptr(d_pose), _ptr(Kf),
+                                                      ctypes.byref(b), float(th), float(nnratio), _ptr(d_matches), _ptr(d_outlier),
+                                                      _ptr(d_point_view), _ptr(d_res))
+        self._check(r, "orbx_match_local_map_batch_device")
+
+    def match_local_map(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
+                        bounds: Tuple[int, int, int, int], matches=None, th: float = 1.0, nnratio: float = 0.8, outlier=None):
+        """SearchLocalPoints for one frame and one local map in host memory (orbx_match_local_map) -> (matches int32
+        [len(keys_un)], point_view uint8 [n_map], LocalResult).  matches (default all -1) holds the map points the frame already
+        has, as indices into the map arrays; Tcw is 3x4 or 4x4.  Synchronous."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        mp = np.ascontiguousarray(map_points, np.float32).reshape(-1, 3)
+        mn = np.ascontiguousarray(map_normals, np.float32).reshape(-1, 3)
+        md = np.ascontiguousarray(map_dist, np.float32).reshape(-1, 2)
+        mdesc = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, 32)
+        if len(k) != len(d) or not (len(mp) == len(mn) == len(md) == len(mdesc)):
+            raise OrbxError(E_BADARG, "keypoints / descriptors or the map arrays differ in length")
+        mm = None if map_mask is None else np.ascontiguousarray(np.asarray(map_mask) != 0, np.uint8).reshape(-1)
+        if mm is not None and len(mm) != len(mp):
+            raise OrbxError(E_BADARG, "the map mask needs one entry per map point")
+        out = None if outlier is None else np.ascontiguousarray(np.asarray(outlier) != 0, np.uint8).reshape(-1)
+        if out is not None and len(out) != len(k):
+            raise OrbxError(E_BADARG, "outlier needs one entry per feature")
+        m = np.full(max(len(k), 1), -1, np.int32)
+        if matches is not None:
+            given = np.asarray(matches, np.int32).reshape(-1)
+            if len(given) != len(k):
+                raise OrbxError(E_BADARG, "matches needs one entry per feature")
+            m[:len(k)] = given
+        T = np.asarray(Tcw, np.float32)
+        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        view = np.zeros(max(len(mp), 1), np.uint8)
+        res = LocalResult()
+        r = self._L.orbx_match_local_map(self._h, _ptr(k), _ptr(d), len(k), len(mp), _ptr(mp), _ptr(mn), _ptr(md), _ptr(mdesc), _ptr(mm),
+                                         _ptr(pose), _ptr(Kf), ctypes.byref(b), float(th), float(nnratio), _ptr(m), _ptr(out), _ptr(view),
+                                         ctypes.byref(res))
+        self._check(r, "orbx_match_local_map")
+        return m[:len(k)].copy(), view[:len(mp)].copy(), res
 
     def extract_match_batch_device(self, d_imgs, n_frames: int, width: int, height: int, stride: int, frame_stride: int,
                                    d_kps, d_desc, d_n, first: np.ndarray, second: np.ndarray,
@@ -1681,6 +1790,25 @@ class ORBmatcher:
         m, res = ext.match_projection(LastFrame.mvKeysUn, LastFrame.mDescriptors, CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors,
                                       points, mask, Tcw, K, CurrentFrame.bounds, th, self.mbCheckOrientation, point_desc, last_outlier)
         return int(res.nmatches), m, res
+
+
+    def SearchLocalPoints(self, F: Frame, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, th: float = 1.0, K=None,
+                          matches=None, outlier=None):
+        """Tracking::SearchLocalPoints on a frame and the local map as arrays (include/orbx.h, "matching the local map by
+        projection"): isInFrustum, PredictScale and ORB-SLAM2's SearchByProjection(F, vpMapPoints, th) with this matcher's
+        nnratio -> (nmatches, matches, point_view, LocalResult).  matches (optional): the map points F already has, as indices
+        into the map arrays (F.mvpMapPoints); outlier (optional): F.mvbOutlier; K: 3x3, default F's camera."""
+        ext = self._ext or F.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(F, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchLocalPoints needs K (the frame carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        m, view, res = ext.match_local_map(F.mvKeysUn, F.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
+                                           F.bounds, matches, th, self.mfNNratio, outlier)
+        return int(res.nmatches), m, view, res
 
 
 class Optimizer:

@@ -476,6 +476,30 @@ struct MatchProjArgs {
   orbx_proj_result* res;       // [nPairs]
 };
 
+// ---- ORBmatcher::SearchByProjection(Frame, local map points) (orbx_match_local_kernel.hip): one workgroup of MP_THREADS per
+// (frame, map set) pair ----
+struct MatchLocalArgs {
+  const orbx_keypoint* kps;   // [nFrames][cap] undistorted
+  const uint8_t* desc;        // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;           // [nFrames] (clamped to [0, cap])
+  const int32_t* mapN;        // [nSets] (clamped to [0, mapCap])
+  const float* mapPoints;     // [nSets][mapCap][3]
+  const float* mapNormals;    // [nSets][mapCap][3]
+  const float* mapDist;       // [nSets][mapCap][2] mfMinDistance, mfMaxDistance
+  const uint8_t* mapDesc;     // [nSets][mapCap][32], 16-byte aligned
+  const uint8_t* mapMask;     // nullable [nSets][mapCap]
+  const uint8_t* outlier;     // nullable [nPairs][cap]
+  const float* pose;          // [nPairs][12]
+  const int32_t* pairs;       // [2][nPairs] frames, map sets
+  int32_t cap, mapCap, nPairs, nLevels;
+  float fx, fy, cx, cy, th, nnratio;
+  orbx_bounds b;
+  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t* matches;           // [nPairs][cap] in and out
+  uint8_t* pointView;         // nullable [nPairs][mapCap]
+  orbx_local_result* res;     // [nPairs]
+};
+
 // ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
 constexpr int DB_THREADS = 256;       // threads of the database kernels
 constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries

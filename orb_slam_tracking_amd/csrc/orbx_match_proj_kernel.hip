@@ -1,7 +1,7 @@
 // orbx_match_proj_kernel.hip — ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono = true) for a batch of
 // (last frame L, current frame C) pairs (include/orbx.h, "matching by projection").  gfx950.
 //
-// One workgroup of MP_THREADS threads per pair, one launch per call.  The workgroup builds C's grid in LDS (the cells' start
+// One workgroup of MP_THREADS threads per pair, one launch per call.  The workgroup builds C's grid in LDS (orbx_match_grid.h: the cells' start
 // table and the features' indices by cell: Frame::PosInGrid, Frame.cpp:89-99) and then gives every feature of L a thread: the
 // thread projects the feature's map point and walks its window (Frame::GetFeaturesInArea, Frame.cpp:163-206) cell x outer, cell
 // y inner.  Inside a cell the indices lie in the order the fill's atomics left them, so a cell's best is taken as the smallest
@@ -37,16 +37,13 @@
 #include <hip/hip_runtime.h>
 
 #include "orbx_launch.h"
+#include "orbx_match_grid.h"
 #include "orbx_match_hist.h"
 
 namespace orbx {
 namespace {
 
 constexpr int MP_TH_HIGH = 100;  // ORBmatcher::TH_HIGH
-constexpr int MP_CELLS = ORBX_GRID_COLS * ORBX_GRID_ROWS;
-constexpr int MP_CELLS_PER_THREAD = MP_CELLS / MP_THREADS;
-static_assert(MP_CELLS_PER_THREAD * MP_THREADS == MP_CELLS, "the scan gives every thread the same number of cells");
-constexpr int MP_START_WORDS = (MP_CELLS + 1 + 3) & ~3;  // cell starts [MP_CELLS + 1], padded to 16 bytes
 constexpr int MP_FREE = 0x7fffffff;                      // claim[j]: nobody claims j
 constexpr uint32_t MP_NO_PICK = 0x7fffu;                 // pick[i]: low 15 bits the candidate (< 16384) ...
 constexpr uint32_t MP_DISPLACED = 0x8000u;               // ... bit 15: with nothing taken i would have taken another one
@@ -57,14 +54,6 @@ __host__ __device__ constexpr size_t mpLdsBytes(int cap) {
   return (size_t)4 * (MP_START_WORDS + cap + 2 * mpBitWords(cap)) + (size_t)2 * 2 * ((cap + 1) & ~1);
 }
 
-__device__ __forceinline__ int mpClamp(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-__device__ __forceinline__ bool mpFinite(float x) { return fabsf(x) <= 3.402823466e38f; }  // (false for a NaN)
-
-__device__ __forceinline__ int mpDistance(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-         __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // what the threads of a pair share about it
 struct MpPair {
   const orbx_keypoint* kpsL;
@@ -73,15 +62,8 @@ struct MpPair {
   const uint8_t* mask;
   const uint8_t* outl;
   float R[9], t[3];
-  float minX, maxX, minY, maxY, wInv, hInv;
+  MpGrid g;
 };
-
-// Frame::PosInGrid: the cell (x * ORBX_GRID_ROWS + y) of a keypoint of C, -1 outside the grid
-__device__ __forceinline__ int mpCell(const MpPair& P, float x, float y) {
-  const float px = roundf((x - P.minX) * P.wInv), py = roundf((y - P.minY) * P.hInv);
-  if (!(px >= 0.0f && px < (float)ORBX_GRID_COLS && py >= 0.0f && py < (float)ORBX_GRID_ROWS)) return -1;
-  return (int)px * ORBX_GRID_ROWS + (int)py;
-}
 
 // steps 2 and 3 for feature i of L: 0 = skipped by step 2, 1 = by step 3, 2 = (u, v), the radius and the octave are set
 __device__ __forceinline__ int mpProject(const MatchProjArgs& a, const MpPair& P, const float* __restrict__ scale, int i, float* u,
@@ -102,7 +84,7 @@ __device__ __forceinline__ int mpProject(const MatchProjArgs& a, const MpPair& P
   if (invz < 0.0f) return 1;
   const float pu = (a.fx * xc) * invz + a.cx, pv = (a.fy * yc) * invz + a.cy;
   if (!mpFinite(pu) || !mpFinite(pv)) return 1;
-  if (pu < P.minX || pu > P.maxX || pv < P.minY || pv > P.maxY) return 1;
+  if (pu < P.g.minX || pu > P.g.maxX || pv < P.g.minY || pv > P.g.maxY) return 1;
   *u = pu;
   *v = pv;
   *r = a.th * scale[oct];
@@ -118,7 +100,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   __shared__ int sWave[MP_THREADS / 64];
   __shared__ int sCnt[8];  // status, nmatches, n_points, n_in_image, n_with_candidates, n_displaced, n_rot_removed, rounds
   __shared__ int sAny;
-  const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int pair = blockIdx.x, t = threadIdx.x;
   const int cap = a.cap, words = mpBitWords(cap);
   int* const cellStart = (int*)mpLds;                       // [MP_CELLS + 1]: cell c holds cellIdx[cellStart[c] .. cellStart[c + 1])
   int* const claim = cellStart + MP_START_WORDS;            // [cap] per feature of C: the smallest claimant; of a taken one: its match
@@ -147,10 +129,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
     if (!ok) status |= ORBX_PROJ_NONFINITE;
   }
   if (t != 0) status = 0;  // (what all threads see alike is reported once)
-  P.minX = (float)a.b.min_x; P.maxX = (float)a.b.max_x;
-  P.minY = (float)a.b.min_y; P.maxY = (float)a.b.max_y;
-  P.wInv = (float)ORBX_GRID_COLS / (float)(a.b.max_x - a.b.min_x);  // Frame.cpp:46-47
-  P.hInv = (float)ORBX_GRID_ROWS / (float)(a.b.max_y - a.b.min_y);
+  P.g = mpGridOf(a.b);
   const uint4* __restrict__ descC = (const uint4*)a.desc + (size_t)fc * cap * 2;
   const uint4* __restrict__ descQ = a.pointDesc ? (const uint4*)a.pointDesc + (size_t)ps * cap * 2 : (const uint4*)a.desc + (size_t)fl * cap * 2;
   int* __restrict__ mC = a.matchesCur + (size_t)pair * cap;
@@ -164,34 +143,9 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   if (t < 8) sCnt[t] = 0;
   if (t == 0) sAny = 0;
   __syncthreads();
-  for (int j = t; j < nC; j += MP_THREADS) {
-    const int c = mpCell(P, P.kpsC[j].x, P.kpsC[j].y);
-    if (c >= 0) atomicAdd(&cellStart[c + 1], 1);
-  }
+  mpGridCount(P.g, P.kpsC, nC, cellStart);
   __syncthreads();
-  {  // exclusive scan of the counts in place: a thread owns MP_CELLS_PER_THREAD consecutive cells
-    int cnt[MP_CELLS_PER_THREAD], sum = 0;
-#pragma unroll
-    for (int k = 0; k < MP_CELLS_PER_THREAD; k++) { cnt[k] = cellStart[1 + t * MP_CELLS_PER_THREAD + k]; sum += cnt[k]; }
-    int incl = sum;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const int o = __shfl_up(incl, s);
-      if (lane >= s) incl += o;
-    }
-    if (lane == 63) sWave[w] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int k = 0; k < w; k++) run += sWave[k];
-#pragma unroll
-    for (int k = 0; k < MP_CELLS_PER_THREAD; k++) { cellStart[1 + t * MP_CELLS_PER_THREAD + k] = run; run += cnt[k]; }
-  }
-  __syncthreads();
-  // (cellStart[c + 1] is cell c's fill position; once every feature is placed it is the cell's end = the next cell's start)
-  for (int j = t; j < nC; j += MP_THREADS) {
-    const int c = mpCell(P, P.kpsC[j].x, P.kpsC[j].y);
-    if (c >= 0) cellIdx[atomicAdd(&cellStart[c + 1], 1)] = (uint16_t)j;
-  }
+  mpGridFill(P.g, P.kpsC, nC, cellStart, cellIdx, sWave);
   // ---- steps 2 and 3 for every feature of L: those with a window are the unresolved ones of the first round
   int nPoints = 0, nInImage = 0, nWithCand = 0, nDisplaced = 0, nm = 0;
   for (int i = t; i < nL; i += MP_THREADS) {
@@ -220,12 +174,8 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
       float u, v, r;
       int o, ignored = 0;
       mpProject(a, P, sScale, i, &u, &v, &r, &o, &ignored);  // (the same arithmetic as above: stage 2 again)
-      // GetFeaturesInArea's cell range, clamped as floats
-      const float lox = floorf(((u - P.minX) - r) * P.wInv), hix = ceilf(((u - P.minX) + r) * P.wInv);
-      const float loy = floorf(((v - P.minY) - r) * P.hInv), hiy = ceilf(((v - P.minY) + r) * P.hInv);
-      const bool none = lox >= (float)ORBX_GRID_COLS || hix < 0.0f || loy >= (float)ORBX_GRID_ROWS || hiy < 0.0f;
-      const int x0 = lox < 0.0f ? 0 : (int)lox, x1 = hix > (float)(ORBX_GRID_COLS - 1) ? ORBX_GRID_COLS - 1 : (int)hix;
-      const int y0 = loy < 0.0f ? 0 : (int)loy, y1 = hiy > (float)(ORBX_GRID_ROWS - 1) ? ORBX_GRID_ROWS - 1 : (int)hiy;
+      int x0, x1, y0, y1;
+      const bool none = !mpWindow(P.g, u, v, r, &x0, &x1, &y0, &y1);
       const uint4 q0 = descQ[(size_t)i * 2], q1 = descQ[(size_t)i * 2 + 1];
       int bestD = 256, bestJ = -1, bestCell = -1;  // among the untaken candidates
       int freeD = 256, freeJ = -1, freeCell = -1;  // among all of them
