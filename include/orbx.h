@@ -629,6 +629,125 @@ int orbx_pose_optimize(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const 
                        const float* pose0, const float* K, const float* inv_sigma2, int n_iterations, orbx_pose_result* res,
                        uint8_t* outlier);
 
+/* ---- behind SearchByBoW: PnP RANSAC (PnPsolver: EPnP inside RANSAC, what Relocalization calls before PoseOptimization) ---------
+ * A lost frame has no start pose for the call above.  ORB-SLAM2 gets one per candidate keyframe from PnPsolver: RANSAC over the
+ * 2D-3D matches of SearchByBoW, each hypothesis Lepetit / Moreno-Noguer's EPnP on four correspondences.  The reference tree ships
+ * no PnPsolver: the rules below restate ORB-SLAM2's PnPsolver.cc [from-knowledge], PARITY UNPINNED, as the two sections above.
+ * The device equals the CPU restatement tests/cpp/pnp_ref.cpp bit for bit.
+ *
+ * Rules.
+ *  1. Constructor.  For feature j of the frame in ascending j: it has a correspondence when it names a point (d_match == NULL:
+ *     entry j; else entry i = d_match[p][j] >= 0) and the point mask there is set, exactly as orbx_pose_optimize_batch_device
+ *     reads them.  mvP2D = the undistorted keypoint's pt, mvSigma2 = sigma2[octave], mvP3Dw = the point, mvKeyIndices = j.
+ *     N = their number (n_correspondences).
+ *  2. SetRansacParameters(probability, minInliers, maxIterations, minSet = 4, epsilon, th2) (the design passes 0.99, 10, 300, 4,
+ *     0.5, 5.991): nMinInliers = (int)(N * epsilon) with the product in f32, raised to minInliers and to minSet = 4; epsilon (f32)
+ *     raised to (float)nMinInliers / N; nIterations = 1 when nMinInliers == N, else (int)ceil(log(1 - probability) / log(1 -
+ *     pow(epsilon, 3))) in f64; mRansacMaxIts = max(1, min(nIterations, maxIterations)); mvMaxError[i] = sigma2 * th2 in f32.  N
+ *     is known only on the device and the device has no libm that equals the host's, so the host computes the table N ->
+ *     (mRansacMinInliers, mRansacMaxIts) for N in [0, capacity] with these expression types (orbx_pnp_ransac_table) and uploads it.
+ *     (nMinInliers grows with N beyond minInliers / epsilon, so the whole range is stored.)
+ *  3. Sampling.  d_draws int32 [n_problems][n_iter][4] holds the values rand() returned, each in [0, ORBX_PNP_RAND_MAX]; the
+ *     library reads no RNG state.  Draw i of a hypothesis picks entry randi = (int)(((double)r / ((double)RAND_MAX + 1.0)) * size)
+ *     of the available list (DUtils::Random::RandomInt(0, size - 1)), size = N - i; the entry is replaced by the list's last and the
+ *     list shrinks (vAvailableIndices' swap-and-pop).  The caller need not know N.  A negative draw skips the hypothesis (it counts
+ *     no inlier) and sets ORBX_PNP_BAD_DRAWS.
+ *  4. epnp compute_pose, all f64: choose_control_points (the centroid, then the eigenvectors of PW0^T PW0 scaled by
+ *     sqrt(lambda / n)), compute_barycentric_coordinates, fill_M and M^T M (12x12), the eigenvectors of its four smallest
+ *     eigenvalues, compute_L_6x10, compute_rho, find_betas_approx_1 / 2 / 3 over the columns {0,1,3,6}, {0,1,2}, {0,1,2,3,4},
+ *     five gauss_newton steps each, compute_R_and_t (compute_ccs, compute_pcs, solve_for_sign on the first point,
+ *     estimate_R_and_t with the det < 0 row flip), the mean reprojection error, and the choice N = 1; rep[2] < rep[1]: N = 2;
+ *     rep[3] < rep[N]: N = 3 (beta_choice).
+ *  5. CheckInliers keeps the reference's types: Xc, Yc, invZc, distX, distY and error2 are f32, ue and ve f64; the test is
+ *     error2 < mvMaxError[i].  A hypothesis with a non-finite entry in R or t counts no inlier (n_degenerate) and is never kept.
+ *  6. iterate.  Hypothesis `it` qualifies when inliers[it] >= mRansacMinInliers; best(it) is the first maximum of
+ *     inliers[0..it] under strict >.  Refine() at a qualifying `it` runs compute_pose over the inliers of best(it) -- the best so
+ *     far, not the current one -- and CheckInliers; it succeeds when the refined count is > mRansacMinInliers (strict) and the
+ *     refined pose is finite.  The result is the first qualifying `it` whose best refines (found_it, refined = 1: the refined
+ *     pose and the refined inliers).  Otherwise, with all min(n_iter, mRansacMaxIts) iterations run, it is the unrefined best
+ *     when mnBestInliers >= mRansacMinInliers (refined = 0), else there is no pose.  N < mRansacMinInliers is bNoMore at once
+ *     (ORBX_PNP_FEW_POINTS).
+ *
+ * Documented deviations:
+ *  1. Every eigen / SVD step of OpenCV is the project's cyclic Jacobi with 12 fixed sweeps and no convergence test: orbx_decomp's
+ *     eig3 for the 3x3s, its rotation on the packed 12x12 for M^T M; eigenvalues sorted descending and stable (of equal values
+ *     the lower column first), eigenvector signs as the Jacobi leaves them.  cvInvert(CC) is the adjugate inverse inv33.
+ *     The square roots of choose_control_points take a negative eigenvalue as 0.
+ *  2. The 3x3 SVD of ABt goes through eig3 of ABt^T ABt: V = its eigenvectors, u_i = ABt v_i / |ABt v_i| for the two largest,
+ *     u_2 = +-(u_0 x u_1) with the sign that gives det(U V^T) the sign of det(ABt) (a full SVD's, singular values >= 0).
+ *  3. The least-squares solves (6x4, 6x3, 6x5) and gauss_newton's qr_solve are one Householder QR with back substitution; a
+ *     singular system gives a non-finite result, which rule 5 drops (qr_solve returns with the betas unchanged there).
+ *  4. Sums over points are f64 in this order.  A hypothesis adds its four points in the order drawn.  Refine's sums (the
+ *     centroid, PW0^T PW0, the 78 entries of M^T M, for each beta set the camera-frame centroid, ABt and the reprojection
+ *     error) run over the correspondences c = 0 .. N-1 in the constructor's order: lane c % 64 adds the terms of its inliers one
+ *     after the other; lane l then adds lane l + 32's sum to its own, then l + 16's, + 8, + 4, + 2, + 1; the result is lane 0's
+ *     (the order of the pose call's deviation 1).  The barycentric coordinates are recomputed from the point in every pass; pw0
+ *     of estimate_R_and_t is the centroid of choose_control_points (the same sum and division).
+ *  5. iterate is resolved after the fact: all hypotheses are computed, then the rule 6 is applied in iteration order.  Refine
+ *     depends on best(it) alone, so it is evaluated once per distinct best (n_refines) -- a set that failed fails again.  The
+ *     answer equals the sequential loop's (tests/cpp/pnp_ref.cpp holds both).
+ *  6. One call is a solver's whole life.  ORB-SLAM2 calls iterate(5) in turns over the candidates to ration a CPU; the best state
+ *     carries over, so the answer does not depend on the chunking, and found_it tells which turn would have returned it.  The
+ *     design's loop condition (`mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`) is taken as the bound
+ *     min(n_iter, mRansacMaxIts) on the solver's total.  There is no state across calls.
+ *  7. Garbage is flagged and never followed: a frame count outside [0, capacity], a match index >= capacity, an octave outside
+ *     the table on a feature with a point (ORBX_PNP_BAD_INPUT); a non-finite point or keypoint (ORBX_PNP_NONFINITE).  A problem
+ *     that ends without a pose (these, ORBX_PNP_FEW_POINTS, or no qualifying hypothesis) carries ORBX_PNP_NO_POSE, zeros for
+ *     R, t, Tcw and d_pose, and an all -1 row; the pose call then finds zero correspondences and answers ORBX_POSE_FEW_POINTS. */
+#define ORBX_PNP_RAND_MAX 2147483647
+#define ORBX_PNP_BAD_INPUT 2   /* a frame count outside [0, capacity], a match index >= capacity, an octave outside [0, nlevels) */
+#define ORBX_PNP_NONFINITE 4   /* a non-finite input point or keypoint */
+#define ORBX_PNP_FEW_POINTS 8  /* N < mRansacMinInliers: bNoMore at once */
+#define ORBX_PNP_BAD_DRAWS 16  /* a draw outside [0, ORBX_PNP_RAND_MAX] among the iterations that ran */
+#define ORBX_PNP_NO_POSE 32    /* no pose is returned */
+typedef struct orbx_pnp_result {
+  int32_t status;            /* 0, or a bitmask of ORBX_PNP_*; every field is written for every problem */
+  int32_t n_correspondences; /* N (0 with BAD_INPUT / NONFINITE) */
+  int32_t min_inliers;       /* mRansacMinInliers of N */
+  int32_t max_its;           /* mRansacMaxIts of N */
+  int32_t its_run;           /* found_it + 1, or min(n_iter, max_its); 0 when nothing ran */
+  int32_t found_it;          /* the iteration whose Refine succeeded, or -1 */
+  int32_t best_it;           /* the iteration of the best hypothesis when the solver stopped, or -1 */
+  int32_t refined;           /* 1 = the pose is Refine's */
+  int32_t n_inliers;         /* of the returned pose (nInliers) */
+  int32_t n_best_inliers;    /* mnBestInliers when the solver stopped */
+  int32_t n_refines;         /* Refine evaluations (distinct bests) */
+  int32_t n_degenerate;      /* non-finite hypotheses among the iterations that ran */
+  int32_t beta_choice;       /* 1 .. 3 of the returned pose, 0 without one */
+  int32_t reserved;
+  double R[9], t[3];         /* mRi / mti of the returned pose (row-major) */
+  float Tcw[12];             /* R row-major, then t: d_pose0's layout */
+} orbx_pnp_result;
+
+/* The table of rule 2: out int32 [n_max + 1][2] = (mRansacMinInliers, mRansacMaxIts) for N = 0 .. n_max.  Host only.  For N <
+ * mRansacMinInliers the design takes the logarithm of a negative number (and divides by N = 0): those entries get max_iterations;
+ * such a solver is bNoMore before it iterates.  ORBX_E_BADARG for the parameter ranges below, n_max < 0 or NULL. */
+int orbx_pnp_ransac_table(double probability, int min_inliers, int max_iterations, float epsilon, int n_max, int32_t* out);
+
+/* Batched, device-resident, stream-ordered on the context stream.  Every argument up to d_point_mask means what it means in
+ * orbx_pose_optimize_batch_device.  K row-major 3x3 (host, f32); sigma2: host, the context's nlevels floats (mvLevelSigma2), NULL =
+ * the context's own; probability and epsilon in (0, 1), min_inliers >= 4, max_iterations >= 1, th2 > 0; d_draws int32
+ * [n_problems][n_iter][4], n_iter >= 1.  Outputs: d_res [n_problems]; d_pose float [n_problems][12] and d_match_inliers int32
+ * [n_problems][capacity] (= d_match[p][j], or j without d_match, for an inlier j and -1 otherwise; every entry is written): the
+ * pose call's d_pose0 and d_match for the same problem lists; d_inliers uint8 [n_problems][capacity] (NULL = not wanted):
+ * vbInliers.  Three launches: k_pnp_prep (a wave per problem), k_pnp_hypotheses (a lane per problem and iteration), k_pnp_refine
+ * (a wave per problem).  The call returns once queued, with the pose call's exception: when the problem list, sigma2 or the
+ * parameters' table differ from the previous call's on this context, or the workspace grows, it first waits for the context stream.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, n_iter < 1, a parameter outside its range, a frame index
+ * outside [0, n_frames), a point set outside [0, n_point_sets); ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx
+ * == NULL with otherwise well-formed arguments -- all checked before anything touches a device.  n_problems == 0 is ORBX_OK. */
+int orbx_pnp_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_frame, const int32_t* h_point_set,
+                                const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_match,
+                                int n_point_sets, const float* d_points, const uint8_t* d_point_mask, const float* K,
+                                const float* sigma2, double probability, int min_inliers, int max_iterations, float epsilon, float th2,
+                                int n_iter, const int32_t* d_draws, orbx_pnp_result* d_res, float* d_pose, int32_t* d_match_inliers,
+                                uint8_t* d_inliers);
+/* The same for one problem in host memory (the direct form: points [n][3], mask [n] nullable, draws [n_iter][4], inliers [n]), run
+ * through the batched path as a batch of one.  Synchronous. */
+int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const float* points, const uint8_t* mask, const float* K,
+                   const float* sigma2, double probability, int min_inliers, int max_iterations, float epsilon, float th2, int n_iter,
+                   const int32_t* draws, orbx_pnp_result* res, uint8_t* inliers);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

@@ -668,6 +668,133 @@ class Optimizer {
   }
 };
 
+// ---- PnPsolver (ORB-SLAM2's PnPsolver.h; include/orbx.h, "behind SearchByBoW: PnP RANSAC") ---------------------------------------
+// The design's constructor takes the frame and vpMapPointMatches; here the map points are coordinates plus a has-point flag per
+// feature, like PoseOptimization above.  SetRansacParameters, iterate and find keep their signatures; the pose comes back as the
+// design's 4x4 CV_32F cv::Mat with OpenCV (empty when there is none) and as PnPsolver::Mat without (m[16] row-major, empty()).
+// One orbx_pnp_solve call is the solver's whole life (orbx.h, deviation 6): the first iterate() or find() draws
+// 4 * maxIterations values from the host's rand(), as the design's iterations would one after the other, and runs them all on
+// the device of the frame's extractor; every iterate(n) then answers what the design's n-iteration turn would.  Argument / HIP
+// errors throw orbx::Error.
+class PnPsolver {
+ public:
+#ifdef ORBX_WITH_OPENCV
+  typedef cv::Mat Mat;
+#else
+  struct Mat {
+    float m[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bool has = false;
+    bool empty() const { return !has; }
+    float at(int r, int c) const { return m[r * 4 + c]; }
+  };
+#endif
+
+  template <class FrameT, class Point3>
+  PnPsolver(const FrameT& F, const std::vector<Point3>& vP3D, const std::vector<bool>& vbHasPoint)
+      : ext_(F.mpORBextractor), keys_(F.mvKeysUn.size()), p3d_(3 * (F.mvKeysUn.size() ? F.mvKeysUn.size() : 1)),
+        has_(F.mvKeysUn.size() ? F.mvKeysUn.size() : 1) {
+    if (!ext_) throw orbx::Error(ORBX_E_BADARG, "PnPsolver: the frame carries no extractor");
+    const size_t n = keys_.size();
+    if (vP3D.size() != n || vbHasPoint.size() != n)
+      throw orbx::Error(ORBX_E_BADARG, "PnPsolver: vP3D and vbHasPoint must have one entry per keypoint of the frame");
+    if (n) std::memcpy(keys_.data(), F.mvKeysUn.data(), n * sizeof(orbx_keypoint));
+    for (size_t i = 0; i < n; i++) {
+      p3d_[3 * i] = vP3D[i].x;
+      p3d_[3 * i + 1] = vP3D[i].y;
+      p3d_[3 * i + 2] = vP3D[i].z;
+      has_[i] = vbHasPoint[i] ? 1 : 0;
+    }
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) K_[r * 3 + c] = frameK(F.mK, r, c);
+    SetRansacParameters();
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4,
+                           float th2 = 5.991) {
+    if (minSet != 4) throw orbx::Error(ORBX_E_BADARG, "PnPsolver: minSet is 4 (EPnP's minimal set)");
+    probability_ = probability;
+    minInliers_ = minInliers;
+    maxIterations_ = maxIterations;
+    epsilon_ = epsilon;
+    th2_ = th2;
+    ran_ = false;
+    iterationsAsked_ = 0;
+  }
+
+  Mat find(std::vector<bool>& vbInliers, int& nInliers) {
+    bool bFlag;
+    return iterate(maxIterations_, bFlag, vbInliers, nInliers);
+  }
+
+  Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    run();
+    iterationsAsked_ += nIterations > 0 ? nIterations : 0;
+    bNoMore = false;
+    vbInliers.clear();
+    nInliers = 0;
+    if (res_.status & (ORBX_PNP_FEW_POINTS | ORBX_PNP_BAD_INPUT | ORBX_PNP_NONFINITE)) {
+      bNoMore = true;
+      return Mat();
+    }
+    if (res_.refined && res_.found_it < iterationsAsked_) return answer(vbInliers, nInliers);
+    if (!res_.refined && iterationsAsked_ >= res_.its_run) {
+      bNoMore = true;
+      if (!(res_.status & ORBX_PNP_NO_POSE)) return answer(vbInliers, nInliers);
+    }
+    return Mat();
+  }
+
+  const orbx_pnp_result& result() {
+    run();
+    return res_;
+  }
+
+ private:
+  void run() {
+    if (ran_) return;
+    std::vector<int32_t> draws(4 * (size_t)(maxIterations_ > 0 ? maxIterations_ : 1));
+    for (size_t i = 0; i < draws.size(); i++) draws[i] = rand();
+    inl_.assign(keys_.size() ? keys_.size() : 1, 0);
+    const int r = orbx_pnp_solve(ext_->context(), keys_.data(), (int)keys_.size(), p3d_.data(), has_.data(), K_, nullptr, probability_,
+                                 minInliers_, maxIterations_, epsilon_, th2_, (int)(draws.size() / 4), draws.data(), &res_, inl_.data());
+    if (r != ORBX_OK) throw orbx::Error(r, r == ORBX_E_BADARG ? "PnPsolver: a RANSAC parameter out of range" : orbx_last_error(ext_->context()));
+    ran_ = true;
+  }
+
+  Mat answer(std::vector<bool>& vbInliers, int& nInliers) const {
+    nInliers = res_.n_inliers;
+    vbInliers.assign(keys_.size(), false);
+    for (size_t i = 0; i < keys_.size(); i++) vbInliers[i] = inl_[i] != 0;
+#ifdef ORBX_WITH_OPENCV
+    Mat T(4, 4, CV_32F);
+    for (int r = 0; r < 4; r++) {
+      float* row = reinterpret_cast<float*>(T.data + (size_t)r * T.step);
+      for (int c = 0; c < 4; c++) row[c] = r == 3 ? (c == 3 ? 1.f : 0.f) : (c == 3 ? res_.Tcw[9 + r] : res_.Tcw[r * 3 + c]);
+    }
+#else
+    Mat T;
+    T.has = true;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) T.m[r * 4 + c] = res_.Tcw[r * 3 + c];
+      T.m[r * 4 + 3] = res_.Tcw[9 + r];
+    }
+#endif
+    return T;
+  }
+
+  ORBextractor* ext_;
+  std::vector<orbx_keypoint> keys_;
+  std::vector<float> p3d_;
+  std::vector<uint8_t> has_, inl_;
+  float K_[9];
+  double probability_ = 0.99;
+  int minInliers_ = 8, maxIterations_ = 300;
+  float epsilon_ = 0.4f, th2_ = 5.991f;
+  bool ran_ = false;
+  int iterationsAsked_ = 0;
+  orbx_pnp_result res_ = {};
+};
+
 template <class Point3>
 int ORBmatcher::searchByProjection(ORBextractor* e, const FrameView& C, const FrameView& L, float th, const std::vector<Point3>& vP3D,
                                    const std::vector<bool>& vbHasPoint, const PoseT& Tcw, const float* K, std::vector<int>& vnMatchesCur,

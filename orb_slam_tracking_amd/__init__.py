@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -141,6 +141,40 @@ POSE_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_correspondences"
                              [("stop_reason", "<i4", 4)] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
                              [("q", "<f8", 4), ("t", "<f8", 3), ("R", "<f4", (3, 3)), ("tcw", "<f4", 3)])
 assert POSE_RESULT_DTYPE.itemsize == ctypes.sizeof(PoseResult) == 192
+
+
+PNP_BAD_INPUT, PNP_NONFINITE, PNP_FEW_POINTS, PNP_BAD_DRAWS, PNP_NO_POSE = 2, 4, 8, 16, 32
+PNP_RAND_MAX = 2147483647
+_PNP_INTS = ("status", "n_correspondences", "min_inliers", "max_its", "its_run", "found_it", "best_it", "refined", "n_inliers",
+             "n_best_inliers", "n_refines", "n_degenerate", "beta_choice", "reserved")
+
+
+class PnpResult(ctypes.Structure):
+    """orbx_pnp_result: PnPsolver's outcome for one problem (found_it tells which iterate() turn would have returned it)."""
+    _fields_ = [(n, ctypes.c_int32) for n in _PNP_INTS] + [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3),
+                                                          ("Tcw", ctypes.c_float * 12)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n in _PNP_INTS if n != "reserved"}
+        d["R"], d["t"] = np.array(self.R[:], np.float64).reshape(3, 3), np.array(self.t[:], np.float64)
+        d["Tcw"] = np.array(self.Tcw[:], np.float32)
+        return d
+
+
+PNP_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _PNP_INTS] + [("R", "<f8", (3, 3)), ("t", "<f8", 3), ("Tcw", "<f4", 12)])
+assert PNP_RESULT_DTYPE.itemsize == ctypes.sizeof(PnpResult) == 200
+
+
+def sample_pnp_draws(rand, n_iter: int) -> np.ndarray:
+    """The draws of n_iter PnP RANSAC hypotheses, int32 [n_iter, 4]: the next 4 * n_iter values of `rand`, a callable returning
+    the host's next rand() value (as sample_sets takes it), in the order PnPsolver::iterate would draw them.  The device turns
+    them into indices itself (DUtils::Random::RandomInt and the swap-and-pop), so the caller need not know N."""
+    n_iter = int(n_iter)
+    out = np.zeros((n_iter, 4), np.int32)
+    for it in range(n_iter):
+        for j in range(4):
+            out[it, j] = int(rand())
+    return out
 
 
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
@@ -299,6 +333,11 @@ def lib() -> ctypes.CDLL:
     L.orbx_bundle_adjust.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(BAResult), vp]
     L.orbx_pose_optimize_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
     L.orbx_pose_optimize.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, ctypes.POINTER(PoseResult), vp]
+    f64 = ctypes.c_double
+    L.orbx_pnp_ransac_table.argtypes = [f64, i32, i32, f32, i32, vp]
+    L.orbx_pnp_solve_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, f64, i32, i32, f32, f32, i32,
+                                              vp, vp, vp, vp, vp]
+    L.orbx_pnp_solve.argtypes = [vp, vp, i32, vp, vp, vp, vp, f64, i32, i32, f32, f32, i32, vp, ctypes.POINTER(PnpResult), vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1258,6 +1297,72 @@ class ORBextractor:
                                                             _ptr(d_pose0), _ptr(Kf), _ptr(sig), int(n_iterations), _ptr(d_res),
                                                             _ptr(d_outlier)), "orbx_pose_optimize_batch_device")
 
+    # -- PnPsolver behind SearchByBoW (include/orbx.h, "behind SearchByBoW: PnP RANSAC") ------------------------
+    def pnp_solve(self, keys_un, points, mask, K, draws, sigma2=None, probability: float = 0.99, min_inliers: int = 10,
+                  max_iterations: int = 300, epsilon: float = 0.5, th2: float = 5.991):
+        """One problem from host memory: the frame's mvKeysUn, one map point per feature (points [n, 3], mask [n] or None = every
+        feature has one), K and the draws int32 [n_iter, 4] (sample_pnp_draws).  One call is the solver's whole life: up to
+        min(n_iter, mRansacMaxIts) iterations.  Returns (PnpResult, vbInliers [n] bool)."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        if len(pts) != len(k) or (m is not None and len(m) != len(k)):
+            raise OrbxError(E_BADARG, "points and mask must have one entry per keypoint of the frame")
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1, 4)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        res = PnpResult()
+        out = np.zeros(max(len(k), 1), np.uint8)
+        self._check(self._L.orbx_pnp_solve(self._h, _ptr(k), len(k), _ptr(pts), _ptr(m), _ptr(Kf), _ptr(sig), float(probability),
+                                           int(min_inliers), int(max_iterations), float(epsilon), float(th2), len(d), _ptr(d),
+                                           ctypes.byref(res), _ptr(out)), "orbx_pnp_solve")
+        return res, out[:len(k)].astype(bool)
+
+    def pnp_solve_batch_device(self, n_frames: int, frame: np.ndarray, point_set: np.ndarray, d_kps_un, d_n, d_match, n_point_sets: int,
+                               d_points, d_point_mask, K, d_draws, d_res, d_pose, d_match_inliers, d_inliers=None, sigma2=None,
+                               probability: float = 0.99, min_inliers: int = 10, max_iterations: int = 300, epsilon: float = 0.5,
+                               th2: float = 5.991, n_iter: Optional[int] = None, capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: problem p solves frame frame[p] against point set point_set[p]; every array up to
+        d_point_mask is pose_optimize_batch_device's.  d_draws int32 [n_problems, n_iter, 4] (n_iter: default from its size).
+        Outputs: d_res [n_problems] PNP_RESULT_DTYPE records (200 bytes), d_pose float32 [n_problems, 12] and d_match_inliers int32
+        [n_problems, capacity] -- pose_optimize_batch_device's d_pose0 and d_match for the same lists --, d_inliers uint8
+        [n_problems, capacity] or None.  Stream-ordered: the outputs are valid after a device synchronisation."""
+        frame = np.ascontiguousarray(frame, np.int32)
+        point_set = np.ascontiguousarray(point_set, np.int32)
+        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
+        if len(point_set) != P:
+            raise OrbxError(E_BADARG, "frame and point_set must have the same length")
+        if n_iter is None:
+            nbytes = _nbytes(d_draws)
+            n_iter = nbytes // (16 * P) if P and nbytes is not None else 0
+        n_iter = int(n_iter)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        if d_match is not None:
+            _need("the match array", d_match, P * cap * 4)
+        _need("the point array", d_points, n_point_sets * cap * 12)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, n_point_sets * cap)
+        _need("the draws", d_draws, P * max(n_iter, 0) * 16)
+        _need("the result array", d_res, P * PNP_RESULT_DTYPE.itemsize)
+        _need("the pose array", d_pose, P * 48)
+        _need("the inlier match array", d_match_inliers, P * cap * 4)
+        if d_inliers is not None:
+            _need("the inlier flags", d_inliers, P * cap)
+        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_draws, d_res, d_pose, d_match_inliers, d_inliers)
+        self._check(self._L.orbx_pnp_solve_batch_device(self._h, n_frames, P, _ptr(frame), _ptr(point_set), _ptr(d_kps_un), _ptr(d_n),
+                                                        cap, _ptr(d_match), n_point_sets, _ptr(d_points), _ptr(d_point_mask),
+                                                        _ptr(Kf), _ptr(sig), float(probability), int(min_inliers),
+                                                        int(max_iterations), float(epsilon), float(th2), n_iter, _ptr(d_draws),
+                                                        _ptr(d_res), _ptr(d_pose), _ptr(d_match_inliers), _ptr(d_inliers)),
+                    "orbx_pnp_solve_batch_device")
+
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:
         w, h = ctypes.c_int(0), ctypes.c_int(0)
@@ -1809,6 +1914,94 @@ class ORBmatcher:
         m, view, res = ext.match_local_map(F.mvKeysUn, F.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
                                            F.bounds, matches, th, self.mfNNratio, outlier)
         return int(res.nmatches), m, view, res
+
+
+class PnPsolver:
+    """ORB-SLAM2's PnPsolver for one frame and one candidate's map points (include/orbx.h, "behind SearchByBoW: PnP RANSAC"):
+    PnPsolver(frame, points, mask_or_match, K), SetRansacParameters, then iterate(nIterations) or find().  mask_or_match: bool /
+    uint8 [N] = feature j has the point points[j], or int32 [N] = feature j's point is points[match[j]] (-1: none), the row
+    SearchByBoW returns.  The device runs a solver's whole life in one call (deviation 6): the first iterate() or find() runs
+    every iteration on `rand`'s draws, and iterate(n) answers as the reference's n-at-a-time turns would."""
+
+    def __init__(self, frame: Frame, points, mask_or_match, K=None, extractor: Optional[ORBextractor] = None, rand=None):
+        self._ext = extractor or frame.mpORBextractor
+        if self._ext is None:
+            raise OrbxError(E_BADARG, "PnPsolver needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(frame, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "PnPsolver needs K (the frame carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        self._K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self._keys = np.ascontiguousarray(frame.mvKeysUn, KEYPOINT_DTYPE).reshape(-1)
+        n = len(self._keys)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        mm = np.asarray(mask_or_match).reshape(-1)
+        if len(mm) != n:
+            raise OrbxError(E_BADARG, "mask_or_match must have one entry per keypoint of the frame")
+        if mm.dtype.kind in "iu" and mm.dtype.itemsize >= 4:  # a match row: gather the points feature by feature
+            ok = (mm >= 0) & (mm < len(pts))
+            self._points = np.zeros((n, 3), np.float32)
+            self._points[ok] = pts[mm[ok]]
+            self._mask = ok.astype(np.uint8)
+        else:
+            if len(pts) != n:
+                raise OrbxError(E_BADARG, "points must have one entry per keypoint of the frame")
+            self._points, self._mask = pts, (mm != 0).astype(np.uint8)
+        if rand is None:
+            libc = ctypes.CDLL(None)
+            libc.rand.restype = ctypes.c_int
+            rand = libc.rand
+        self._rand = rand
+        self._params = dict(probability=0.99, min_inliers=8, max_iterations=300, epsilon=0.4, th2=5.991)  # the constructor's own
+        self._turns = 0
+        self._result = None
+
+    def SetRansacParameters(self, probability: float = 0.99, minInliers: int = 8, maxIterations: int = 300, minSet: int = 4,
+                            epsilon: float = 0.4, th2: float = 5.991) -> None:
+        if int(minSet) != 4:
+            raise OrbxError(E_BADARG, "PnPsolver: minSet is 4 (EPnP's minimal set)")
+        self._params = dict(probability=probability, min_inliers=minInliers, max_iterations=maxIterations, epsilon=epsilon, th2=th2)
+        self._result, self._turns = None, 0
+
+    def _run(self):
+        if self._result is None:
+            draws = sample_pnp_draws(self._rand, int(self._params["max_iterations"]))
+            self._result = self._ext.pnp_solve(self._keys, self._points, self._mask, self._K, draws, **self._params)
+        return self._result
+
+    def _answer(self):
+        res, inl = self._run()
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3], T[:3, 3] = np.array(res.Tcw[:9], np.float32).reshape(3, 3), np.array(res.Tcw[9:], np.float32)
+        return T, inl, int(res.n_inliers)
+
+    def iterate(self, nIterations: int):
+        """-> (Tcw 4x4 float32 or None, bNoMore, vbInliers [N] bool, nInliers, the PnpResult): what the reference's iterate
+        returns in this turn of nIterations iterations."""
+        res, _ = self._run()
+        self._turns += 1
+        done = self._turns * int(nIterations)
+        none = np.zeros(len(self._keys), bool)
+        if res.status & PNP_FEW_POINTS or res.status & (PNP_BAD_INPUT | PNP_NONFINITE):
+            return None, True, none, 0, res
+        if res.refined and res.found_it < done:
+            T, inl, n = self._answer()
+            return T, False, inl, n, res
+        if done >= res.its_run and not res.refined:
+            if res.status & PNP_NO_POSE:
+                return None, True, none, 0, res
+            T, inl, n = self._answer()
+            return T, True, inl, n, res
+        return None, False, none, 0, res
+
+    def find(self):
+        """-> (Tcw 4x4 float32 or None, vbInliers [N] bool, nInliers, the PnpResult): iterate until a pose or bNoMore."""
+        res, _ = self._run()
+        if res.status & PNP_NO_POSE:
+            return None, np.zeros(len(self._keys), bool), 0, res
+        T, inl, n = self._answer()
+        return T, inl, n, res
 
 
 class Optimizer:

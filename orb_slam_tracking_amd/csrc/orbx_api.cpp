@@ -174,6 +174,7 @@ struct orbx_ctx {
   MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
   PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
+  PnpScratch pnp;                 // orbx_pnp_solve* (orbx_pose.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -2511,9 +2512,14 @@ InitScratch* ctxInit(orbx_ctx* c) { return &c->init; }
 MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
 PoseScratch* ctxPose(orbx_ctx* c) { return &c->pose; }
+PnpScratch* ctxPnp(orbx_ctx* c) { return &c->pnp; }
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;
   return c->invSigma2.data();
+}
+const float* ctxSigma2(const orbx_ctx* c, int* nlevels) {
+  *nlevels = c->p.nlevels;
+  return c->sigma2.data();
 }
 const float* ctxScale(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;

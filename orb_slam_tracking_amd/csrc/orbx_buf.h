@@ -195,4 +195,17 @@ struct PoseScratch {
   DeviceBuf<uint8_t> dIo;       // staging of orbx_pose_optimize
 };
 
+// What a context keeps for orbx_pnp_solve* (orbx_pose.cpp).
+struct PnpScratch {
+  HeldArray<int32_t> problems;  // the problem list [2][n_problems] of the last call
+  HeldArray<float> sigma2;      // sigma2 of the last call
+  HeldArray<int32_t> table;     // N -> (mRansacMinInliers, mRansacMaxIts) for N in [0, capacity] of the last call
+  std::vector<int32_t> hTable;  // ... as computed on the host for `key`: the parameters it was computed from
+  double keyProbability = 0;
+  float keyEpsilon = 0;
+  int keyMinInliers = 0, keyMaxIterations = 0;
+  DeviceBuf<uint8_t> dWork;     // the correspondences, the hypotheses and the per-problem values of a call
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_pnp_solve
+};
+
 }  // namespace orbx

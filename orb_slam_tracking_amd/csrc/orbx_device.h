@@ -639,4 +639,32 @@ struct PoseArgs {
   double fx, fy, cx, cy, delta;
   int32_t nProblems, cap, nLevels, nIterations;
 };
+
+// k_pnp_*: PnPsolver (include/orbx.h, "behind SearchByBoW: PnP RANSAC"): prep and refine a wave per problem, the hypotheses a
+// lane per (problem, iteration)
+constexpr int PNP_CORR_BYTES = 32;   // orbx_pnp::Corr
+constexpr int PNP_HYP_BYTES = 112;   // orbx_pnp::Hyp
+constexpr int PNP_MAX_CAPACITY = 16384;  // ORBX_BOW_MAX_FEATURES: sizes the inlier bit sets in LDS
+struct PnpArgs {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const int32_t* nKps;        // [frames]
+  const int32_t* problems;    // [2][nProblems] frames, then point sets
+  const int32_t* match;       // nullable [nProblems][cap]
+  const float* points;        // [sets][cap][3]
+  const uint8_t* mask;        // nullable [sets][cap]
+  const float* sigma2;        // [nLevels] (device)
+  const int32_t* table;       // [cap + 1][2] (device): mRansacMinInliers, mRansacMaxIts of N
+  const int32_t* draws;       // [nProblems][nIter][4]
+  orbx_pnp_result* res;       // [nProblems]
+  float* pose;                // [nProblems][12]
+  int32_t* matchInliers;      // [nProblems][cap]
+  uint8_t* inliers;           // nullable [nProblems][cap]
+  uint8_t* corr;              // workspace [nProblems][cap] Corr: the correspondences, ascending feature
+  int32_t* corrOf;            // workspace [nProblems][cap]: feature j's correspondence, or -1
+  int32_t* meta;              // workspace [nProblems][4]: orbx_pnp::Meta
+  uint8_t* hyp;               // workspace [nProblems][nIter] Hyp
+  double fu, fv, uc, vc;
+  float th2;
+  int32_t nProblems, cap, nLevels, nIter;
+};
 }  // namespace orbx

@@ -19,10 +19,12 @@ int ctxDrain(orbx_ctx* c);
 void ctxSetError(orbx_ctx* c, const char* msg);
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels);
 const float* ctxScale(const orbx_ctx* c, int* nlevels);  // mvScaleFactor
+const float* ctxSigma2(const orbx_ctx* c, int* nlevels);  // mvLevelSigma2
 InitScratch* ctxInit(orbx_ctx* c);
 MatchBowScratch* ctxMatchBow(orbx_ctx* c);
 BaScratch* ctxBa(orbx_ctx* c);
 PoseScratch* ctxPose(orbx_ctx* c);
+PnpScratch* ctxPnp(orbx_ctx* c);
 
 // ... and of a vocabulary (orbx_vocabulary is private to orbx_bow.cpp): the context it was made on, and the descent alone over
 // a batch; *nodes the vocabulary's breadth-first nodes, *fin [n_frames][capacity] the breadth-first index each feature ends at

@@ -86,4 +86,9 @@ hipError_t launch_match_local(hipStream_t st, const MatchLocalArgs& a);
 hipError_t launch_ba(hipStream_t st, const BaArgs& a);
 hipError_t launch_pose(hipStream_t st, const PoseArgs& a);
 
+// orbx_pnp_kernel.hip
+hipError_t launch_pnp_prep(hipStream_t st, const PnpArgs& a);
+hipError_t launch_pnp_hypotheses(hipStream_t st, const PnpArgs& a);
+hipError_t launch_pnp_refine(hipStream_t st, const PnpArgs& a);
+
 }  // namespace orbx

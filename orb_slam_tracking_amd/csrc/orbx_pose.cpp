@@ -1,5 +1,7 @@
-// orbx_pose.cpp — host side of Optimizer::PoseOptimization (include/orbx.h, "behind SearchByBoW: pose optimisation"): the
-// argument checks, the problem list and the C entry points.  The kernel is in orbx_pose_kernel.hip.
+// orbx_pose.cpp — host side of what runs behind SearchByBoW: Optimizer::PoseOptimization (include/orbx.h, "behind SearchByBoW:
+// pose optimisation"; the kernel is in orbx_pose_kernel.hip) and, below it, PnPsolver, which gives a lost frame the start pose
+// ("behind SearchByBoW: PnP RANSAC"; orbx_pnp_kernel.hip).  For each: the argument checks, the problem list, the held tables and
+// the C entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -117,6 +119,183 @@ int orbx_pose_optimize(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const 
   }
   HIPCHK(down(res, dR, 1, st));
   HIPCHK(down(outlier, dO, n, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- PnPsolver: SetRansacParameters' table, the workspace of the three launches and the C entry points ---------------------------
+namespace {
+
+bool paramsOk(double probability, int minInliers, int maxIterations, float epsilon) {
+  return probability > 0.0 && probability < 1.0 && epsilon > 0.f && epsilon < 1.f && minInliers >= 4 && maxIterations >= 1;
+}
+
+// SetRansacParameters for one N, with the design's expression types (include/orbx.h, rule 2)
+void ransacEntry(int N, double mRansacProb, int minInliers, int mRansacMaxIts, float mRansacEpsilon, int32_t* out) {
+  const int minSet = 4;
+  int nMinInliers = (int)((float)N * mRansacEpsilon);
+  if (nMinInliers < minInliers) nMinInliers = minInliers;
+  if (nMinInliers < minSet) nMinInliers = minSet;
+  const int Nd = N > 0 ? N : 1;  // (the design divides by N = 0; such a solver is bNoMore before it iterates)
+  if (mRansacEpsilon < (float)nMinInliers / Nd) mRansacEpsilon = (float)nMinInliers / Nd;
+  int nIterations;
+  if (nMinInliers == Nd) {
+    nIterations = 1;
+  } else {
+    const double it = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)mRansacEpsilon, 3)));
+    // (epsilon >= 1 gives log(<= 0): no finite count; mRansacMaxIts bounds it either way)
+    nIterations = (it >= 1.0 && it < 2147483647.0) ? (int)it : (it < 1.0 ? 1 : mRansacMaxIts);
+  }
+  out[0] = nMinInliers;
+  out[1] = std::max(1, std::min(nIterations, mRansacMaxIts));
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_pnp_ransac_table(double probability, int min_inliers, int max_iterations, float epsilon, int n_max, int32_t* out) {
+  if (!paramsOk(probability, min_inliers, max_iterations, epsilon) || n_max < 0 || !out) return ORBX_E_BADARG;
+  for (int N = 0; N <= n_max; N++) ransacEntry(N, probability, min_inliers, max_iterations, epsilon, out + 2 * (size_t)N);
+  return ORBX_OK;
+}
+
+int orbx_pnp_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_frame, const int32_t* h_point_set,
+                                const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const int32_t* d_match,
+                                int n_point_sets, const float* d_points, const uint8_t* d_point_mask, const float* K,
+                                const float* sigma2, double probability, int min_inliers, int max_iterations, float epsilon, float th2,
+                                int n_iter, const int32_t* d_draws, orbx_pnp_result* d_res, float* d_pose, int32_t* d_match_inliers,
+                                uint8_t* d_inliers) {
+  if (n_frames < 0 || n_problems < 0 || n_point_sets < 0 || capacity < 1 || n_iter < 1 ||
+      (n_problems > 0 && (!h_frame || !h_point_set)) || !d_kps_un || !d_n || !d_points || !K || !d_draws || !d_res || !d_pose ||
+      !d_match_inliers || !paramsOk(probability, min_inliers, max_iterations, epsilon) || !(th2 > 0.f) || !std::isfinite(th2))
+    return ORBX_E_BADARG;
+  if (!pairsInRange(h_frame, h_point_set, n_problems, n_frames, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "pnp solve: frame outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
+  if (capacity > PNP_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "pnp solve: capacity above ORBX_BOW_MAX_FEATURES");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_problems == 0) return ORBX_OK;
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  PnpScratch* s = ctxPnp(ctx);
+  hipStream_t st = ctxStream(ctx);
+  int nLevels = 0;
+  const float* own = ctxSigma2(ctx, &nLevels);
+  const float* sig = sigma2 ? sigma2 : own;
+  // the table of these parameters up to this capacity (computed again only when they change)
+  const size_t tableLen = 2 * ((size_t)capacity + 1);
+  if (s->hTable.size() != tableLen || s->keyProbability != probability || s->keyEpsilon != epsilon ||
+      s->keyMinInliers != min_inliers || s->keyMaxIterations != max_iterations) {
+    s->hTable.resize(tableLen);
+    (void)orbx_pnp_ransac_table(probability, min_inliers, max_iterations, epsilon, capacity, s->hTable.data());
+    s->keyProbability = probability;
+    s->keyEpsilon = epsilon;
+    s->keyMinInliers = min_inliers;
+    s->keyMaxIterations = max_iterations;
+  }
+  // the workspace of the three launches
+  PnpArgs a{};
+  auto workspace = [&](Layout L) {
+    a.corr = L.take<uint8_t>((size_t)n_problems * capacity * PNP_CORR_BYTES);
+    a.corrOf = L.take<int32_t>((size_t)n_problems * capacity);
+    a.meta = L.take<int32_t>((size_t)n_problems * 4);
+    a.hyp = L.take<uint8_t>((size_t)n_problems * n_iter * PNP_HYP_BYTES);
+    return L.size();
+  };
+  const size_t bytes = workspace(Layout());
+  // the lists and the tables go up only when they differ from the last call's; such a call first waits for the context stream,
+  // as orbx_pose_optimize_batch_device does (include/orbx.h)
+  const bool sameList = s->problems.holds(h_frame, n_problems, h_point_set, n_problems), sameSigma = s->sigma2.holds(sig, nLevels),
+             sameTable = s->table.holds(s->hTable.data(), tableLen);
+  if (!sameList || !sameSigma || !sameTable) HIPCHK(hipStreamSynchronize(st));
+  if (!sameList) HIPCHK(s->problems.replace(st, h_frame, n_problems, h_point_set, n_problems));
+  if (!sameSigma) HIPCHK(s->sigma2.replace(st, sig, nLevels));
+  if (!sameTable) HIPCHK(s->table.replace(st, s->hTable.data(), tableLen));
+  HIPCHK(s->dWork.grow(bytes, st));
+  workspace(Layout(s->dWork));
+  a.kps = d_kps_un;
+  a.nKps = d_n;
+  a.problems = s->problems;
+  a.match = d_match;
+  a.points = d_points;
+  a.mask = d_point_mask;
+  a.sigma2 = s->sigma2;
+  a.table = s->table;
+  a.draws = d_draws;
+  a.res = d_res;
+  a.pose = d_pose;
+  a.matchInliers = d_match_inliers;
+  a.inliers = d_inliers;
+  intrinsics(K, &a.fu, &a.fv, &a.uc, &a.vc);
+  a.th2 = th2;
+  a.nProblems = n_problems;
+  a.cap = capacity;
+  a.nLevels = nLevels;
+  a.nIter = n_iter;
+  HIPCHK(launch_pnp_prep(st, a));
+  HIPCHK(launch_pnp_hypotheses(st, a));
+  HIPCHK(launch_pnp_refine(st, a));
+  return ORBX_OK;
+}
+
+int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const float* points, const uint8_t* mask, const float* K,
+                   const float* sigma2, double probability, int min_inliers, int max_iterations, float epsilon, float th2, int n_iter,
+                   const int32_t* draws, orbx_pnp_result* res, uint8_t* inliers) {
+  if (n < 0 || n_iter < 1 || !K || !draws || !res || (n > 0 && (!kps_un || !points || !inliers)) ||
+      !paramsOk(probability, min_inliers, max_iterations, epsilon) || !(th2 > 0.f) || !std::isfinite(th2))
+    return ORBX_E_BADARG;
+  const int cap = std::max(n, 1);
+  if (cap > PNP_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "pnp solve: more than ORBX_BOW_MAX_FEATURES keypoints");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  PnpScratch* s = ctxPnp(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  int32_t *dN, *dDraws, *dRow;
+  float *dP, *dPose;
+  uint8_t *dM, *dI;
+  orbx_pnp_result* dR;
+  auto staging = [&](Layout L) {  // one frame and one point set in the batch layout, then the results
+    dK = L.take<orbx_keypoint>(cap);
+    dN = L.take<int32_t>(1);
+    dP = L.take<float>((size_t)cap * 3);
+    dM = L.take<uint8_t>(cap);
+    dDraws = L.take<int32_t>((size_t)n_iter * 4);
+    dPose = L.take<float>(12);
+    dRow = L.take<int32_t>(cap);
+    dI = L.take<uint8_t>(cap);
+    dR = L.take<orbx_pnp_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dIo.grow(bytes, st));
+  staging(Layout(s->dIo));
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const int32_t hn = n, zero = 0;
+  HIPCHK(up(dK, kps_un, n, st));
+  HIPCHK(up(dP, points, (size_t)n * 3, st));
+  if (mask) HIPCHK(up(dM, mask, n, st));
+  HIPCHK(up(dN, &hn, 1, st));
+  HIPCHK(up(dDraws, draws, (size_t)n_iter * 4, st));
+  r = orbx_pnp_solve_batch_device(ctx, 1, 1, &zero, &zero, dK, dN, cap, nullptr, 1, dP, mask ? dM : nullptr, K, sigma2, probability,
+                                  min_inliers, max_iterations, epsilon, th2, n_iter, dDraws, dR, dPose, dRow, dI);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(down(inliers, dI, n, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
