@@ -1217,6 +1217,112 @@ int orbx_match_local_map(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8
                          const uint8_t* map_mask, const float* pose, const float* K, const orbx_bounds* bounds, float th,
                          float nnratio, int32_t* matches, const uint8_t* outlier, uint8_t* point_view, orbx_local_result* res);
 
+/* ---- matching a keyframe's points by projection: ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) --
+ * The tail of Tracking::Relocalization: behind SearchByBoW, PnPsolver and PoseOptimization a candidate keyframe with fewer than
+ * 50 inliers has its other map points projected into the lost frame with (th 10, ORBdist 100), the pose optimised again, and
+ * with 30 to 50 inliers once more with (th 3, ORBdist 64).  The reference ships no such function: this is ORB-SLAM2's code,
+ * [from-knowledge], PARITY UNPINNED, bit-identical to a CPU restatement of the rules below (tests/cpp/match_kfproj_ref.cpp).  The
+ * window search alone is pinned: it is the reference's Frame::GetFeaturesInArea (SlamTypes/Frame.cpp:163-206), and the tests
+ * compare it with the reference's own compiled code.
+ *
+ * Pair p: keyframe KF = h_kf[p] (n_K features), current frame C = h_cur[p], point set s = h_point_set[p] whose entry i is the map
+ * point of KF's feature i (the layout of matching by projection: d_points, d_point_mask), C's pose d_pose[p] (12 floats: R
+ * row-major, then t), the row d_matches[p] (C's feature j -> an index into set s, or a negative value; read and written).
+ *   1. what C already has (sAlreadyFound, and CurrentFrame.mvpMapPoints), over C's features j with i = d_matches[p][j] >= 0:
+ *      i >= n_K is never followed -- the entry stays, feature j counts as taken and ORBX_KFPROJ_BAD_INPUT is set.  Otherwise point
+ *      i is "found" and is not searched; with d_outlier[p][j] != 0 the entry becomes -1 and feature j is free (the point stays
+ *      found: Relocalization fills sFound from the PnP inliers before PoseOptimization and clears the outliers' mvpMapPoints
+ *      after it), without it feature j is taken.  d_outlier == NULL is Relocalization's second use: sFound is rebuilt from
+ *      mvpMapPoints, nothing is cleared.  A negative entry is left as it is.
+ *   2. the points searched: KF's features i in ascending order whose mask byte is set and whose point is not found; f32 without
+ *      contraction.  Pc = R*P + t as xc = ((R0*X + R1*Y) + R2*Z) + t0, yc and zc likewise; invz = 1.0f / zc correctly rounded;
+ *      u = (fx*xc)*invz + cx, v = (fy*yc)*invz + cy.  THERE IS NO DEPTH TEST, as in ORB-SLAM2's overload: a point behind the
+ *      camera (zc < 0.0f) whose (u, v) lands inside the bounds goes on (counted in n_behind_kept).  u or v not finite: skipped;
+ *      u < min_x || u > max_x || v < min_y || v > max_y: skipped (a value on a bound stays).
+ *   3. Ow_k = -((R[0][k]*t0 + R[1][k]*t1) + R[2][k]*t2); PO = P - Ow; dist3D = (float)sqrt((double)POx*POx + (double)POy*POy +
+ *      (double)POz*POz), the products and sums in f64 in that order (cv::norm of a CV_32F vector); dist3D < 0.8f*minDist ||
+ *      dist3D > 1.2f*maxDist: skipped (d_point_dist holds the raw mfMinDistance, mfMaxDistance).  No viewing-angle test, no
+ *      normals.  level = PredictScale in table form on ratio = maxDist / dist3D (correctly rounded): the number of n in
+ *      [0, nlevels - 1) with ratio > scale[n]; a ratio that is no number sets ORBX_KFPROJ_NONFINITE and drops the point.
+ *   4. r = th * scale[level]; the candidates are GetFeaturesInArea(u, v, r, level - 1, level + 1) over C's undistorted keypoints
+ *      (the reference's function: PosInGrid's rounding, the clamped cell range, octave in [level - 1, level + 1], the strict
+ *      fabs(d) < r in both coordinates), in the order cell x outer, cell y inner, ascending index inside a cell.  No candidate:
+ *      the point is skipped.
+ *   5. over the candidates that are not taken, neither on entry nor by an earlier point of this call, in that order, with d =
+ *      popcount(desc_i ^ desc_C[j]): the first smallest wins (dist < bestDist, starting from 256).  desc_i is
+ *      d_point_desc32[s][i] when that array is given (MapPoint::GetDescriptor), KF's descriptor i otherwise.  No second-best, no
+ *      ratio test.
+ *   6. bestDist <= orb_dist: d_matches[p][bestIdx] = i and bestIdx is taken.  With check_orientation the match joins the bin of
+ *      angle_KF[i] - angle_C[bestIdx] (the corrected factor and the kept out-of-range bin of matching through the
+ *      FeatureVector).
+ *   7. with check_orientation, ComputeThreeMaxima and its 0.1 rule over the NEW matches only; the new matches of the losing bins
+ *      go back to -1 (the entry's matches never vote and never go).  nmatches = the new matches that remain.
+ * Documented deviations from ORB-SLAM2:
+ *   1. PredictScale in table form (deviation 1 of matching the local map by projection).
+ *   2. "Taken" is CurrentFrame.mvpMapPoints[i2] != NULL as in ORB-SLAM2: this overload makes no Observations() test, so the
+ *      deviation that matching by projection and matching the local map state for it does not arise here.
+ *   3. Map points are arrays plus a mask (0 = NULL or isBad()), matches are indices into the pair's point set.
+ *   4. Garbage is flagged and never followed.  Counts outside [0, capacity] are clamped and set ORBX_KFPROJ_BAD_INPUT, as does an
+ *      entry of d_matches >= n_K.  A non-finite pose sets ORBX_KFPROJ_NONFINITE and drops every point of rule 2; a point of rule
+ *      2 whose position or two distances hold a non-finite value sets it and is dropped, as is one whose ratio is no number.  u
+ *      or v that is no number is out of the image.  A keypoint whose cell is no number is in no cell; window cells are clamped
+ *      as floats.
+ *   5. orb_dist is accepted in [0, 256] (0 accepts only an identical descriptor; 255 and 256 accept every candidate but one at
+ *      distance 256, which `dist < bestDist` never picks).
+ * Worst case: points whose windows all share candidates within orb_dist resolve one per round (see the kernel). */
+#define ORBX_KFPROJ_BAD_INPUT 2 /* a count outside its capacity, an entry of d_matches beyond the keyframe's count */
+#define ORBX_KFPROJ_NONFINITE 4 /* a non-finite pose, a non-finite point / distance or ratio of a point of rule 2 */
+typedef struct orbx_kfproj_result {
+  int32_t status;             /* 0, or a bitmask of ORBX_KFPROJ_*; every field is written for every pair */
+  int32_t nmatches;           /* new matches that remain behind rule 7 */
+  int32_t n_points;           /* points that reach rule 2: mask set, not found */
+  int32_t n_found;            /* points some entry of d_matches names (whatever their mask) */
+  int32_t n_behind_kept;      /* rule 2: zc < 0 with (u, v) inside the bounds -- the point goes on to rule 3 all the same */
+  int32_t n_out_image;        /* ... u or v not finite or outside the bounds */
+  int32_t n_out_distance;
+  int32_t n_with_candidates;  /* searched points whose window holds a feature (rule 4) */
+  int32_t n_over_dist;        /* ... whose bestDist is above orb_dist (256 when every candidate is taken) */
+  int32_t n_displaced;        /* searched points whose pick (the feature, or none) differs from what they would get with only
+                                 the entry's matches taken */
+  int32_t n_rot_removed;      /* rule 7 */
+  int32_t n_outliers_cleared; /* entries rule 1 set to -1 */
+  int32_t rounds;             /* the device's rounds of claims; a sequential statement reports 0 */
+} orbx_kfproj_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  d_kps_un / d_desc32 (16-byte aligned) / d_n: the frames, in
+ * the layout of the extract and undistort calls ([n_frames][capacity]); a frame may be a keyframe in one pair and a current frame
+ * in another.  Point set s of [n_point_sets][capacity]: d_points float [3], d_point_mask uint8 (NULL = every entry is a point),
+ * d_point_desc32 uint8 [32] (16-byte aligned; NULL = the keyframe's own descriptors), d_point_dist float [2] (mfMinDistance,
+ * mfMaxDistance; the kernel applies the 0.8f and 1.2f; required).  d_pose float [n_pairs][12].  K row-major 3x3 (host, f32),
+ * bounds = the frames' image bounds, th > 0 (Relocalization passes 10, then 3), orb_dist in [0, 256] (100, then 64).  d_matches
+ * int32 [n_pairs][capacity], in and out and required: it is matching through the FeatureVector's d_matches_f with the keyframe's
+ * map points as the point set -- the row orbx_match_bow_batch_device and orbx_pnp_solve_batch_device write and
+ * orbx_pose_optimize_batch_device reads as d_match -- so SearchByBoW -> PnP -> pose -> this call -> pose runs on one row without
+ * a gather.  Entries at and beyond C's count are not touched.  d_outlier uint8 [n_pairs][capacity] (NULL = none): read only,
+ * orbx_pose_optimize_batch_device's output.  d_res [n_pairs].
+ * One workgroup per pair, one launch.  The call returns once queued, with the exception orbx_match_bow_batch_device has: when the
+ * pair lists differ from the previous call's on this context, the call first waits for the context stream before it uploads
+ * them.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, th not finite or <= 0, orb_dist outside [0, 256], bounds
+ * with max <= min, a frame index outside [0, n_frames), a point set outside [0, n_point_sets) -- all checked before anything
+ * touches a device; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed
+ * arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_keyframe_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_cur,
+                                                const int32_t* h_point_set, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                                const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                                const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const float* d_point_dist,
+                                                const float* d_pose, const float* K, const orbx_bounds* bounds, float th, int orb_dist,
+                                                int check_orientation, int32_t* d_matches, const uint8_t* d_outlier,
+                                                orbx_kfproj_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: the keyframe (kf_n features; points, point_dist
+ * per feature; mask, point_desc32 nullable), the current frame (cur_n features), pose [12]; matches [cur_n] in and out, outlier
+ * [cur_n] nullable.  More than ORBX_BOW_MAX_FEATURES features: ORBX_E_CAPACITY.  Synchronous. */
+int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un, const uint8_t* kf_desc32, int kf_n,
+                                   const orbx_keypoint* cur_kps_un, const uint8_t* cur_desc32, int cur_n, const float* points,
+                                   const uint8_t* mask, const uint8_t* point_desc32, const float* point_dist, const float* pose,
+                                   const float* K, const orbx_bounds* bounds, float th, int orb_dist, int check_orientation,
+                                   int32_t* matches, const uint8_t* outlier, orbx_kfproj_result* res);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

@@ -332,6 +332,21 @@ struct MapView {
   const uint8_t* mbGood = nullptr;        // [N] or null
 };
 
+// A candidate keyframe as the relocalisation overload ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th,
+// ORBdist) reads it (orbx.h, "matching a keyframe's points by projection"): its undistorted keypoints (for their angles) and
+// descriptors, and per feature its map point (GetMapPointMatches): the world position, mfMinDistance and mfMaxDistance, a flag
+// (null = every feature has a point; 0 = NULL or isBad()) and, optionally, the point's own descriptor (GetDescriptor; null = the
+// keyframe's).
+struct KeyFrameView {
+  int N = 0;
+  const KeyPointT* mvKeysUn = nullptr;          // [N]
+  const uint8_t* mDescriptors = nullptr;        // [N][32]
+  const float* mWorldPos = nullptr;             // [N][3]
+  const float* mfMinMaxDistance = nullptr;      // [N][2]
+  const uint8_t* mbGood = nullptr;              // [N] or null
+  const uint8_t* mPointDescriptors = nullptr;   // [N][32] or null
+};
+
 class ORBmatcher {
  public:
   // Features/ORBmatcher.hpp:15.  (The optional third argument pins the device context; without it the matcher uses the
@@ -416,6 +431,22 @@ class ORBmatcher {
                          const std::vector<bool>* vbOutlier = nullptr, std::vector<uint8_t>* pointView = nullptr,
                          orbx_local_result* result = nullptr);
 
+  // ORB-SLAM2's relocalisation overload SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound,
+  // const float th, const int ORBdist) (orbx.h, "matching a keyframe's points by projection", with its documented deviations; the
+  // orientation check is this matcher's).  vnMatches[j] = the index of the keyframe's feature whose map point CurrentFrame's
+  // feature j has, or -1 -- in and out: on entry CurrentFrame.mvpMapPoints, which is also sAlreadyFound (any other size than
+  // CurrentFrame.N stands for none), on exit those without the outliers' plus the new ones.  Returns the number of new matches.
+  // vbOutlier (optional): CurrentFrame.mvbOutlier behind PoseOptimization.  K: 9 floats, row-major.
+  int SearchByProjection(const FrameView& CurrentFrame, const KeyFrameView& KF, std::vector<int>& vnMatches, float th, int ORBdist,
+                         const PoseT& Tcw, const float* K, const std::vector<bool>* vbOutlier = nullptr,
+                         orbx_kfproj_result* result = nullptr) {
+    return searchKeyFrame(ext_, CurrentFrame, KF, vnMatches, th, ORBdist, Tcw, K, vbOutlier, result);
+  }
+  // ... for the reference's Frame or any Frame-like type (K from CurrentFrame.mK)
+  template <class FrameT, class = typename std::enable_if<!std::is_same<typename std::decay<FrameT>::type, FrameView>::value>::type>
+  int SearchByProjection(FrameT& CurrentFrame, const KeyFrameView& KF, std::vector<int>& vnMatches, float th, int ORBdist,
+                         const PoseT& Tcw, const std::vector<bool>* vbOutlier = nullptr, orbx_kfproj_result* result = nullptr);
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -437,6 +468,9 @@ class ORBmatcher {
   inline int searchLocalMap(ORBextractor* e, const FrameView& F, const MapView& map, float th, const PoseT& Tcw, const float* K,
                             std::vector<int>& vnMatches, const std::vector<bool>* vbOutlier, std::vector<uint8_t>* pointView,
                             orbx_local_result* result);  // (defined behind PoseT)
+  inline int searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,
+                            int ORBdist, const PoseT& Tcw, const float* K, const std::vector<bool>* vbOutlier,
+                            orbx_kfproj_result* result);  // (defined behind PoseT)
 
   int search(ORBextractor* e, const FrameView& F1, const FrameView& F2, std::vector<int>& vnMatches12, int windowSize) {
     if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
@@ -861,6 +895,41 @@ int ORBmatcher::SearchByProjection(FrameT& F, const MapView& map, float th, cons
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) K[r * 3 + c] = frameK(F.mK, r, c);
   return searchLocalMap(ext_ ? ext_ : F.mpORBextractor, frameView(F), map, th, Tcw, K, vnMatches, vbOutlier, pointView, result);
+}
+
+inline int ORBmatcher::searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,
+                                      int ORBdist, const PoseT& Tcw, const float* K, const std::vector<bool>* vbOutlier,
+                                      orbx_kfproj_result* result) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frame carries none and none was set");
+  const size_t n = (size_t)C.N;
+  if (vbOutlier && vbOutlier->size() != n) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchByProjection: vbOutlier needs CurrentFrame.N entries");
+  float pose[12];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) pose[r * 3 + c] = (float)Tcw(r, c);
+    pose[9 + r] = (float)Tcw(r, 3);
+  }
+  if (vnMatches.size() != n) vnMatches.assign(n, -1);
+  std::vector<uint8_t> out(n ? n : 1);
+  for (size_t j = 0; j < n; j++) out[j] = vbOutlier && (*vbOutlier)[j] ? 1 : 0;
+  const orbx_bounds b{C.mnMinX, C.mnMaxX, C.mnMinY, C.mnMaxY};
+  orbx_kfproj_result res;
+  const int r = orbx_match_keyframe_projection(e->context(), reinterpret_cast<const orbx_keypoint*>(KF.mvKeysUn), KF.mDescriptors, KF.N,
+                                               reinterpret_cast<const orbx_keypoint*>(C.mvKeysUn), C.mDescriptors, C.N, KF.mWorldPos,
+                                               KF.mbGood, KF.mPointDescriptors, KF.mfMinMaxDistance, pose, K, &b, th, ORBdist,
+                                               mbCheckOrientation ? 1 : 0, vnMatches.data(), vbOutlier ? out.data() : nullptr, &res);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  if (result) *result = res;
+  return res.nmatches;
+}
+
+template <class FrameT, class>
+int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const KeyFrameView& KF, std::vector<int>& vnMatches, float th, int ORBdist,
+                                   const PoseT& Tcw, const std::vector<bool>* vbOutlier, orbx_kfproj_result* result) {
+  float K[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) K[r * 3 + c] = frameK(CurrentFrame.mK, r, c);
+  return searchKeyFrame(ext_ ? ext_ : CurrentFrame.mpORBextractor, frameView(CurrentFrame), KF, vnMatches, th, ORBdist, Tcw, K, vbOutlier,
+                        result);
 }
 
 template <class FrameT, class Point3, class>

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -210,6 +210,24 @@ LOCAL_RESULT_DTYPE = np.dtype([(n, "<i4") for n in LOCAL_RESULT_FIELDS])
 assert LOCAL_RESULT_DTYPE.itemsize == ctypes.sizeof(LocalResult) == 60
 
 
+KFPROJ_BAD_INPUT, KFPROJ_NONFINITE = 2, 4
+KFPROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_found", "n_behind_kept", "n_out_image", "n_out_distance", "n_with_candidates",
+                        "n_over_dist", "n_displaced", "n_rot_removed", "n_outliers_cleared", "rounds")
+
+
+class KfProjResult(ctypes.Structure):
+    """orbx_kfproj_result: the counters of the relocalisation SearchByProjection for one (keyframe, frame) pair (rounds is the
+    device's own count)."""
+    _fields_ = [(n, ctypes.c_int32) for n in KFPROJ_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+KFPROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in KFPROJ_RESULT_FIELDS])
+assert KFPROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(KfProjResult) == 52
+
+
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
     """mvSets as Initializer::Initialize draws them (Initializer.cpp:50-63): per iteration 8 distinct indices into
     mvMatches12, each `rand() % available` with swap-with-last removal.  `rand` is a callable returning the host's next rand()
@@ -363,6 +381,10 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.POINTER(_Bounds), f32, f32, vp, vp, vp, vp]
     L.orbx_match_local_map.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, f32, vp, vp, vp,
                                        ctypes.POINTER(LocalResult)]
+    L.orbx_match_keyframe_projection_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                              ctypes.POINTER(_Bounds), f32, i32, i32, vp, vp, vp]
+    L.orbx_match_keyframe_projection.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32,
+                                                 i32, i32, vp, vp, ctypes.POINTER(KfProjResult)]
     L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.orbx_database_destroy.argtypes = [vp]
     L.orbx_database_destroy.restype = None
@@ -894,6 +916,181 @@ class ORBextractor:
                                          ctypes.byref(res))
         self._check(r, "orbx_match_local_map")
         return m[:len(k)].copy(), view[:len(mp)].copy(), res
+
+    def match_keyframe_projection_pairs_device(self, n_frames: int, kf: np.ndarray, cur: np.ndarray, point_set: np.ndarray, d_kps_un,
+                                               d_desc, d_n, n_point_sets: int, d_points, d_point_mask, d_point_dist, d_pose, K,
+                                               bounds: Tuple[int, int, int, int], d_matches, d_res, th: float = 10.0, ORBdist: int = 100,
+                                               checkOri: bool = True, d_point_desc=None, d_outlier=None,
+                                               capacity: Optional[int] = None) -> None:
+        """The relocalisation overload ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) for pairs
+        (keyframe kf[p], current frame cur[p], the keyframe's map points = point set point_set[p]; host index arrays) of the
+        arrays extract_batch_device and undistort_batch_device filled, with the point sets of pose_optimize_batch_device
+        (d_points float32 [n_point_sets, capacity, 3], d_point_mask uint8 [n_point_sets, capacity] or None), d_point_dist float32
+        [n_point_sets, capacity, 2] (mfMinDistance, mfMaxDistance) and the poses d_pose float32 [n_pairs, 12].  d_matches int32
+        [n_pairs, capacity] is read and written: the current frame's feature j -> an index into the point set, or -1
+        (match_bow_pairs_device's d_matches_f, pose_optimize_batch_device's d_match).  Optional: d_point_desc uint8 [n_point_sets,
+        capacity, 32] (default the keyframe's descriptors), d_outlier uint8 [n_pairs, capacity] (read only).  d_res [n_pairs]
+        KFPROJ_RESULT_DTYPE records (52 bytes).  Stream-ordered on the context's stream."""
+        kf = np.ascontiguousarray(kf, np.int32).reshape(-1)
+        cur = np.ascontiguousarray(cur, np.int32).reshape(-1)
+        point_set = np.ascontiguousarray(point_set, np.int32).reshape(-1)
+        if len(kf) != len(cur) or len(kf) != len(point_set):
+            raise OrbxError(E_BADARG, "kf, cur and point_set must have the same length")
+        cap, nf, ns, P = int(capacity or self.capacity), int(n_frames), int(n_point_sets), len(kf)
+        # (as unsigned, a negative index is a huge one)
+        if P and int(np.maximum(kf.view(np.uint32), cur.view(np.uint32)).max()) >= nf:
+            raise ValueError("a pair names a frame outside the batch of %d" % nf)
+        if P and int(point_set.view(np.uint32).max()) >= ns:
+            raise ValueError("a pair names a point set outside the %d given" % ns)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the point array", d_points, ns * cap * 12)
+        _need("the point distance array", d_point_dist, ns * cap * 8)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, ns * cap)
+        if d_point_desc is not None:
+            _need("the point descriptor array", d_point_desc, ns * cap * 32)
+        if d_outlier is not None:
+            _need("the outlier array", d_outlier, P * cap)
+        _need("the pose array", d_pose, P * 48)
+        _need("matches", d_matches, P * cap * 4)
+        _need("the result array", d_res, P * KFPROJ_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_point_dist, d_outlier, d_pose, d_matches, d_res)
+        r = self._L.orbx_match_keyframe_projection_batch_device(self._h, nf, P, _ptr(kf), _ptr(cur), _ptr(point_set), _ptr(d_kps_un),
+                                                                _ptr(d_desc), _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask),
+                                                                _ptr(d_point_desc), _ptr(d_point_dist), _ptr(d_pose), _ptr(Kf),
+                                                                ctypes.byref(b), float(th), int(ORBdist), int(bool(checkOri)),
+                                                                _ptr(d_matches), _ptr(d_outlier), _ptr(d_res))
+        self._check(r, "orbx_match_keyframe_projection_batch_device")
+
+    def match_keyframe_projection(self, kf_keys_un, kf_desc, cur_keys_un, cur_desc, points, mask, point_dist, Tcw, K,
+                                  bounds: Tuple[int, int, int, int], matches=None, th: float = 10.0, ORBdist: int = 100,
+                                  checkOri: bool = True, point_desc=None, outlier=None):
+        """The relocalisation SearchByProjection for one pair in host memory (orbx_match_keyframe_projection) -> (matches int32
+        [len(cur_keys_un)], KfProjResult).  points [n_kf, 3], mask [n_kf] (or None) and point_dist [n_kf, 2] are the keyframe's
+        map points; matches (default all -1) holds the points the current frame already has, as indices into them; Tcw (3x4 or
+        4x4) is the current frame's pose.  Synchronous."""
+        kk, ck = np.ascontiguousarray(kf_keys_un, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(cur_keys_un, KEYPOINT_DTYPE).reshape(-1)
+        kd, cd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, 32)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        dst = np.ascontiguousarray(point_dist, np.float32).reshape(-1, 2)
+        if len(kk) != len(kd) or len(ck) != len(cd) or len(pts) != len(kk) or len(dst) != len(kk):
+            raise OrbxError(E_BADARG, "keypoints / descriptors / points / distances differ in length")
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        if m is not None and len(m) != len(kk):
+            raise OrbxError(E_BADARG, "the mask needs one entry per feature of the keyframe")
+        pd = None if point_desc is None else np.ascontiguousarray(point_desc, np.uint8).reshape(-1, 32)
+        if pd is not None and len(pd) != len(kk):
+            raise OrbxError(E_BADARG, "point_desc needs one entry per feature of the keyframe")
+        out = None if outlier is None else np.ascontiguousarray(np.asarray(outlier) != 0, np.uint8).reshape(-1)
+        if out is not None and len(out) != len(ck):
+            raise OrbxError(E_BADARG, "outlier needs one entry per feature of the current frame")
+        mc = np.full(max(len(ck), 1), -1, np.int32)
+        if matches is not None:
+            given = np.asarray(matches, np.int32).reshape(-1)
+            if len(given) != len(ck):
+                raise OrbxError(E_BADARG, "matches needs one entry per feature of the current frame")
+            mc[:len(ck)] = given
+        T = np.asarray(Tcw, np.float32)
+        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        res = KfProjResult()
+        r = self._L.orbx_match_keyframe_projection(self._h, _ptr(kk), _ptr(kd), len(kk), _ptr(ck), _ptr(cd), len(ck), _ptr(pts), _ptr(m),
+                                                   _ptr(pd), _ptr(dst), _ptr(pose), _ptr(Kf), ctypes.byref(b), float(th), int(ORBdist),
+                                                   int(bool(checkOri)), _ptr(mc), _ptr(out), ctypes.byref(res))
+        self._check(r, "orbx_match_keyframe_projection")
+        return mc[:len(ck)].copy(), res
+
+    def relocalize_refine_pairs_device(self, n_frames: int, kf: np.ndarray, cur: np.ndarray, point_set: np.ndarray, d_kps_un, d_desc,
+                                       d_n, n_point_sets: int, d_points, d_point_mask, d_point_dist, d_pose0, d_matches, K,
+                                       bounds: Tuple[int, int, int, int], d_point_desc=None, capacity: Optional[int] = None):
+        """The tail of Tracking::Relocalization behind PnPsolver for a batch of (lost frame cur[p], candidate keyframe kf[p]) pairs,
+        on torch tensors: d_pose0 float32 [n_pairs, 12] the start poses and d_matches int32 [n_pairs, capacity] the inlier rows as
+        PnP leaves them (updated in place).  Each stage is ONE batched call over the pairs still alive; between stages the host
+        reads the counts once (ORB-SLAM2's loop is host-driven there too):
+          1. PoseOptimization; nGood < 10: dropped
+          2. where nGood < 50: SearchByProjection(th 10, ORBdist 100) with that call's outlier flags
+          3. where nadditional + nGood >= 50: PoseOptimization
+          4. where 30 < nGood < 50: SearchByProjection(th 3, ORBdist 64), no outlier flags
+          5. where nGood + nadditional >= 50: PoseOptimization, then the outliers' entries are cleared
+        with ORBmatcher(0.9, true): the orientation check is on.  A pair that ends at stage 1 with nGood >= 10 has its outliers'
+        entries cleared as Relocalization clears them.  -> (stage int32 [n_pairs] the last stage the pair ran, nGood int32
+        [n_pairs], d_pose float32 [n_pairs, 12], d_matches)."""
+        import torch
+        kf, cur, point_set = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (kf, cur, point_set))
+        cap, P = int(capacity or self.capacity), len(kf)
+        if len(cur) != P or len(point_set) != P:
+            raise OrbxError(E_BADARG, "kf, cur and point_set must have the same length")
+        _need("the pose array", d_pose0, P * 48)
+        _need("matches", d_matches, P * cap * 4)
+        dev = d_matches.device
+        rows = d_matches.view(torch.int32).reshape(-1)[:P * cap].view(P, cap)
+        pose = d_pose0.view(torch.float32).reshape(-1)[:P * 12].view(P, 12).clone()
+        stage, n_good = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        mine = torch.cuda.current_stream(dev).cuda_stream
+
+        def optimise(idx, which):
+            """One PoseOptimization call over the pairs idx -> (nGood [len(idx)], their outlier flags [len(idx), cap], idx on the device)."""
+            sel = torch.from_numpy(idx.astype(np.int64)).to(dev)
+            r, p0 = rows[sel].contiguous(), pose[sel].contiguous()
+            res = torch.empty(len(idx) * POSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            out = torch.zeros(len(idx) * cap, dtype=torch.uint8, device=dev)
+            self.pose_optimize_batch_device(n_frames, cur[idx], point_set[idx], d_kps_un, d_n, r, n_point_sets, d_points, d_point_mask, p0, K,
+                                            res, out, capacity=cap)
+            self.order_before(mine)
+            rec = res.view(len(idx), POSE_RESULT_DTYPE.itemsize)
+            pose[sel] = rec[:, 144:192].contiguous().view(torch.float32)  # (the record ends with R [9] and tcw [3] as f32: a pose row)
+            good = rec[:, 12:16].contiguous().view(torch.int32).reshape(-1).cpu().numpy()  # n_inliers: the design's return value
+            stage[idx], n_good[idx] = which, good
+            return good, out.view(len(idx), cap), sel
+
+        def search(idx, th, orb_dist, outl):
+            """One SearchByProjection call over the pairs idx -> nadditional [len(idx)]."""
+            sel = torch.from_numpy(idx.astype(np.int64)).to(dev)
+            r, p = rows[sel].contiguous(), pose[sel].contiguous()
+            res = torch.empty(len(idx) * KFPROJ_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            self.match_keyframe_projection_pairs_device(n_frames, kf[idx], cur[idx], point_set[idx], d_kps_un, d_desc, d_n, n_point_sets,
+                                                        d_points, d_point_mask, d_point_dist, p, K, bounds, r, res, th=th, ORBdist=orb_dist,
+                                                        checkOri=True, d_point_desc=d_point_desc, d_outlier=outl, capacity=cap)
+            self.order_before(mine)
+            rows[sel] = r
+            return res.view(len(idx), KFPROJ_RESULT_DTYPE.itemsize)[:, 4:8].contiguous().view(torch.int32).reshape(-1).cpu().numpy()
+
+        def clear(sel, out):
+            r = rows[sel]
+            rows[sel] = torch.where(out != 0, torch.full_like(r, -1), r)
+
+        if P == 0:
+            return stage, n_good, pose, d_matches
+        every = np.arange(P)
+        good, out, sel = optimise(every, 1)                                             # 1
+        done = np.flatnonzero((good >= 10) & (good >= 50))
+        if len(done):
+            k = torch.from_numpy(done.astype(np.int64)).to(dev)
+            clear(sel[k], out[k])
+        k = np.flatnonzero((good >= 10) & (good < 50))
+        if len(k):
+            idx = every[k]
+            kk = torch.from_numpy(k.astype(np.int64)).to(dev)
+            extra = search(idx, 10.0, 100, out[kk].contiguous())                        # 2
+            stage[idx] = 2
+            idx = idx[extra + n_good[idx] >= 50]
+            if len(idx):
+                good, out, sel = optimise(idx, 3)                                       # 3
+                k = np.flatnonzero((good > 30) & (good < 50))
+                if len(k):
+                    idx = idx[k]
+                    extra = search(idx, 3.0, 64, None)                                  # 4
+                    stage[idx] = 4
+                    idx = idx[n_good[idx] + extra >= 50]
+                    if len(idx):
+                        good, out, sel = optimise(idx, 5)                               # 5
+                        clear(sel, out)
+        return stage, n_good, pose, d_matches
 
     def extract_match_batch_device(self, d_imgs, n_frames: int, width: int, height: int, stride: int, frame_stride: int,
                                    d_kps, d_desc, d_n, first: np.ndarray, second: np.ndarray,
@@ -1914,6 +2111,27 @@ class ORBmatcher:
         m, view, res = ext.match_local_map(F.mvKeysUn, F.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
                                            F.bounds, matches, th, self.mfNNratio, outlier)
         return int(res.nmatches), m, view, res
+
+    def SearchByProjectionKeyFrame(self, CurrentFrame: Frame, KF: Frame, points, mask, point_dist, Tcw, th: float = 10.0, ORBdist: int = 100,
+                                   K=None, matches=None, outlier=None, point_desc=None):
+        """ORB-SLAM2's relocalisation overload SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (include/orbx.h,
+        "matching a keyframe's points by projection") -> (nmatches, matches, KfProjResult).  points [N_kf, 3] / mask [N_kf] /
+        point_dist [N_kf, 2]: the keyframe's map points (GetMapPointMatches, mfMinDistance and mfMaxDistance); Tcw (3x4 or 4x4):
+        CurrentFrame's pose; matches (optional): the points CurrentFrame already has (mvpMapPoints = sAlreadyFound), as indices
+        into the keyframe's features; outlier (optional): CurrentFrame.mvbOutlier; point_desc (optional): the map points' own
+        descriptors; K: 3x3, default CurrentFrame's camera."""
+        ext = self._ext or CurrentFrame.mpORBextractor or KF.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(CurrentFrame, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjectionKeyFrame needs K (the frame carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        m, res = ext.match_keyframe_projection(KF.mvKeysUn, KF.mDescriptors, CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors, points, mask,
+                                               point_dist, Tcw, K, CurrentFrame.bounds, matches, th, ORBdist, self.mbCheckOrientation,
+                                               point_desc, outlier)
+        return int(res.nmatches), m, res
 
 
 class PnPsolver:

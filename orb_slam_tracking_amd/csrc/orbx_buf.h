@@ -170,7 +170,8 @@ struct InitScratch {
   HeldArray<int32_t> pairs;   // their pair list [2][n_pairs]
 };
 
-// What a context keeps for orbx_match_bow*, orbx_match_projection* and orbx_match_local_map* (orbx_match_bow.cpp).
+// What a context keeps for orbx_match_bow*, orbx_match_projection*, orbx_match_local_map* and orbx_match_keyframe_projection*
+// (orbx_match_bow.cpp).
 struct MatchBowScratch {
   HeldArray<int32_t> pairs;      // the pair list [2][n_pairs] of the last orbx_match_bow* call
   DeviceBuf<uint8_t> dIo;        // staging of orbx_match_bow
@@ -178,6 +179,8 @@ struct MatchBowScratch {
   DeviceBuf<uint8_t> dProjIo;    // staging of orbx_match_projection
   HeldArray<int32_t> localPairs; // the lists [2][n_pairs] (frame, map set) of the last orbx_match_local_map* call
   DeviceBuf<uint8_t> dLocalIo;   // staging of orbx_match_local_map
+  HeldArray<int32_t> kfProjPairs;  // the lists [3][n_pairs] (keyframe, current, point set) of the last orbx_match_keyframe_projection* call
+  DeviceBuf<uint8_t> dKfProjIo;  // staging of orbx_match_keyframe_projection
 };
 
 // What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp).

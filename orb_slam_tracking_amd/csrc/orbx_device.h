@@ -500,6 +500,27 @@ struct MatchLocalArgs {
   orbx_local_result* res;     // [nPairs]
 };
 
+// ---- ORBmatcher::SearchByProjection(Frame, KeyFrame, sAlreadyFound, th, ORBdist) (orbx_match_kfproj_kernel.hip): one workgroup of
+// MP_THREADS per (keyframe, current frame) pair ----
+struct MatchKfProjArgs {
+  const orbx_keypoint* kps;   // [nFrames][cap] undistorted
+  const uint8_t* desc;        // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;           // [nFrames] (clamped to [0, cap])
+  const float* points;        // [nSets][cap][3] the keyframe's map points, per feature
+  const uint8_t* pointMask;   // nullable [nSets][cap]
+  const uint8_t* pointDesc;   // nullable [nSets][cap][32], 16-byte aligned
+  const float* pointDist;     // [nSets][cap][2] mfMinDistance, mfMaxDistance
+  const uint8_t* outlier;     // nullable [nPairs][cap]
+  const float* pose;          // [nPairs][12]
+  const int32_t* pairs;       // [3][nPairs] keyframes, current frames, point sets
+  int32_t cap, nPairs, nLevels, orbDist, checkOri;
+  float fx, fy, cx, cy, th;
+  orbx_bounds b;
+  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t* matches;           // [nPairs][cap] in and out
+  orbx_kfproj_result* res;    // [nPairs]
+};
+
 // ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
 constexpr int DB_THREADS = 256;       // threads of the database kernels
 constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries

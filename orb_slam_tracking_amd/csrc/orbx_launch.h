@@ -79,10 +79,12 @@ hipError_t launch_db_add_fill(hipStream_t st, const DbAddArgs& a, uint32_t nNew)
 hipError_t launch_db_accumulate(hipStream_t st, const DbQueryArgs& a);
 hipError_t launch_db_merge(hipStream_t st, const DbMergeArgs& a);
 
-// orbx_match_bow_kernel.hip, orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip, orbx_ba_kernel.hip, orbx_pose_kernel.hip
+// orbx_match_bow_kernel.hip, orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip, orbx_match_kfproj_kernel.hip, orbx_ba_kernel.hip,
+// orbx_pose_kernel.hip
 hipError_t launch_match_bow(hipStream_t st, const MatchBowArgs& a);
 hipError_t launch_match_proj(hipStream_t st, const MatchProjArgs& a);
 hipError_t launch_match_local(hipStream_t st, const MatchLocalArgs& a);
+hipError_t launch_match_kfproj(hipStream_t st, const MatchKfProjArgs& a);
 hipError_t launch_ba(hipStream_t st, const BaArgs& a);
 hipError_t launch_pose(hipStream_t st, const PoseArgs& a);
 

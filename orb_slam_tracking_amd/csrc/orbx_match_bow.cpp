@@ -1,7 +1,8 @@
 // orbx_match_bow.cpp — host side of ORBmatcher::SearchByBoW (include/orbx.h, "matching through the FeatureVector"), of
-// ORBmatcher::SearchByProjection ("matching by projection") and of Tracking::SearchLocalPoints ("matching the local map by
-// projection"): the argument checks, the pair lists and the C entry points.  The kernels are in orbx_match_bow_kernel.hip,
-// orbx_match_proj_kernel.hip and orbx_match_local_kernel.hip.
+// ORBmatcher::SearchByProjection ("matching by projection"), of Tracking::SearchLocalPoints ("matching the local map by
+// projection") and of the relocalisation overload ("matching a keyframe's points by projection"): the argument checks, the pair
+// lists and the C entry points.  The kernels are in orbx_match_bow_kernel.hip, orbx_match_proj_kernel.hip,
+// orbx_match_local_kernel.hip and orbx_match_kfproj_kernel.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -412,6 +413,152 @@ int orbx_match_local_map(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8
   }
   HIPCHK(down(matches, dM, n, st));
   if (point_view) HIPCHK(down(point_view, dView, map_n, st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+int orbx_match_keyframe_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_cur,
+                                                const int32_t* h_point_set, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                                const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                                const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const float* d_point_dist,
+                                                const float* d_pose, const float* K, const orbx_bounds* bounds, float th, int orb_dist,
+                                                int check_orientation, int32_t* d_matches, const uint8_t* d_outlier,
+                                                orbx_kfproj_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || n_point_sets < 0 || capacity < 1 || (n_pairs > 0 && (!h_kf || !h_cur || !h_point_set)) ||
+      !d_kps_un || !d_desc32 || !d_n || !d_points || !d_point_dist || !d_pose || !K || !bounds || !d_matches || !d_res)
+    return ORBX_E_BADARG;
+  if (!std::isfinite(th) || !(th > 0.0f)) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: th is not a positive number");
+    return ORBX_E_BADARG;
+  }
+  if (orb_dist < 0 || orb_dist > 256) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: orb_dist outside [0, 256]");
+    return ORBX_E_BADARG;
+  }
+  // (max - min is an int in Frame's grid: it has to be one)
+  if ((long long)bounds->max_x - bounds->min_x < 1 || (long long)bounds->max_x - bounds->min_x > INT32_MAX ||
+      (long long)bounds->max_y - bounds->min_y < 1 || (long long)bounds->max_y - bounds->min_y > INT32_MAX) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: bounds with max <= min");
+    return ORBX_E_BADARG;
+  }
+  if (!pairsInRange(h_kf, h_cur, n_pairs, n_frames) || !pairsInRange(h_cur, h_point_set, n_pairs, n_frames, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: frame outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
+  if (capacity > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: capacity above ORBX_BOW_MAX_FEATURES");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  // the three lists as one array, held as orbx_match_projection_batch_device holds its three
+  std::vector<int32_t> lists;
+  lists.reserve((size_t)3 * n_pairs);
+  lists.insert(lists.end(), h_kf, h_kf + n_pairs);
+  lists.insert(lists.end(), h_cur, h_cur + n_pairs);
+  lists.insert(lists.end(), h_point_set, h_point_set + n_pairs);
+  if (!s->kfProjPairs.holds(lists.data(), lists.size())) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(s->kfProjPairs.replace(st, lists.data(), lists.size()));
+  }
+  MatchKfProjArgs a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.points = d_points;
+  a.pointMask = d_point_mask;
+  a.pointDesc = d_point_desc32;
+  a.pointDist = d_point_dist;
+  a.outlier = d_outlier;
+  a.pose = d_pose;
+  a.pairs = s->kfProjPairs;
+  a.cap = capacity;
+  a.nPairs = n_pairs;
+  a.orbDist = orb_dist;
+  a.checkOri = check_orientation != 0;
+  a.fx = K[0];
+  a.fy = K[4];
+  a.cx = K[2];
+  a.cy = K[5];
+  a.th = th;
+  a.b = *bounds;
+  const float* scale = ctxScale(ctx, &a.nLevels);
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) a.scale[l] = l < a.nLevels ? scale[l] : 0.0f;
+  a.matches = d_matches;
+  a.res = d_res;
+  HIPCHK(launch_match_kfproj(st, a));
+  return ORBX_OK;
+}
+
+int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un, const uint8_t* kf_desc32, int kf_n,
+                                   const orbx_keypoint* cur_kps_un, const uint8_t* cur_desc32, int cur_n, const float* points,
+                                   const uint8_t* mask, const uint8_t* point_desc32, const float* point_dist, const float* pose,
+                                   const float* K, const orbx_bounds* bounds, float th, int orb_dist, int check_orientation,
+                                   int32_t* matches, const uint8_t* outlier, orbx_kfproj_result* res) {
+  if (kf_n < 0 || cur_n < 0 || !pose || !K || !bounds || !res || (kf_n > 0 && (!kf_kps_un || !kf_desc32 || !points || !point_dist)) ||
+      (cur_n > 0 && (!cur_kps_un || !cur_desc32 || !matches)))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(kf_n, cur_n), 1);
+  if (cap > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match keyframe projection: more than ORBX_BOW_MAX_FEATURES features");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t *dD, *dPD, *dMask, *dOut;
+  float *dP, *dDist, *dPose;
+  int32_t *dN, *dM;
+  orbx_kfproj_result* dR;
+  auto staging = [&](Layout L) {  // the two frames (keyframe 0, current 1) and one point set in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dD = L.take<uint8_t>((size_t)2 * cap * 32);
+    dP = L.take<float>((size_t)cap * 3);
+    dDist = L.take<float>((size_t)cap * 2);
+    dPD = L.take<uint8_t>((size_t)cap * 32);
+    dMask = L.take<uint8_t>(cap);
+    dOut = L.take<uint8_t>(cap);
+    dPose = L.take<float>(12);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dR = L.take<orbx_kfproj_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dKfProjIo.grow(bytes, st));
+  staging(Layout(s->dKfProjIo));
+  HIPCHK(hipMemsetAsync(s->dKfProjIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
+  HIPCHK(up(dK, kf_kps_un, kf_n, st));
+  HIPCHK(up(dD, kf_desc32, (size_t)kf_n * 32, st));
+  HIPCHK(up(dK + c, cur_kps_un, cur_n, st));
+  HIPCHK(up(dD + c * 32, cur_desc32, (size_t)cur_n * 32, st));
+  HIPCHK(up(dP, points, (size_t)kf_n * 3, st));
+  HIPCHK(up(dDist, point_dist, (size_t)kf_n * 2, st));
+  if (point_desc32) HIPCHK(up(dPD, point_desc32, (size_t)kf_n * 32, st));
+  if (mask) HIPCHK(up(dMask, mask, kf_n, st));
+  if (outlier) HIPCHK(up(dOut, outlier, cur_n, st));
+  HIPCHK(up(dM, matches, cur_n, st));
+  HIPCHK(up(dPose, pose, 12, st));
+  const int32_t hn[2] = {kf_n, cur_n};
+  HIPCHK(up(dN, hn, 2, st));
+  const int32_t kf = 0, cur = 1, set = 0;
+  r = orbx_match_keyframe_projection_batch_device(ctx, 2, 1, &kf, &cur, &set, dK, dD, dN, cap, 1, dP, mask ? dMask : nullptr,
+                                                  point_desc32 ? dPD : nullptr, dDist, dPose, K, bounds, th, orb_dist,
+                                                  check_orientation, dM, outlier ? dOut : nullptr, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(matches, dM, cur_n, st));
   HIPCHK(down(res, dR, 1, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
