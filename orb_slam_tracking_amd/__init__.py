@@ -492,6 +492,33 @@ def _need(what: str, a, nbytes: int) -> None:
         raise ValueError("%s holds %d bytes, the call needs %d" % (what, have, nbytes))
 
 
+def _pair_lists(names, lists, n_frames: int, n_sets: int, set_what: str) -> np.ndarray:
+    """The host index lists of a match_*_pairs_device call as the rows of one int32 array [len(lists), n_pairs]: of one length, the
+    last one (the sets: `set_what` in the message) below n_sets, the others (frames) below n_frames."""
+    try:
+        m = np.ascontiguousarray(lists, np.int32)
+    except ValueError:  # (not of one shape)
+        m = None
+    if m is None or m.ndim != 2:  # each list flattened on its own: they may still be of one length
+        flat = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in lists]
+        if any(len(a) != len(flat[0]) for a in flat):
+            raise OrbxError(E_BADARG, "%s and %s must have the same length" % (", ".join(names[:-1]), names[-1]))
+        m = np.stack(flat)
+    if m.shape[1]:
+        u = m.view(np.uint32)  # (as unsigned, a negative index is a huge one)
+        if int(u[:-1].max()) >= n_frames:
+            raise ValueError("a pair names a frame outside the batch of %d" % n_frames)
+        if int(u[-1].max()) >= n_sets:
+            raise ValueError("a pair names a %s outside the %d given" % (set_what, n_sets))
+    return m
+
+
+def _pose12(Tcw) -> np.ndarray:
+    """Tcw (3x4 or 4x4) as the C ABI's pose: row-major R [9], then t [3]."""
+    T = np.asarray(Tcw, np.float32)
+    return np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+
+
 def _need_batch(imgs, n_frames, width, height, stride, frame_stride, kps, desc, n, capacity, first=None, second=None, matches12=None,
                 nmatches=None, stats=None, init_res=None, p3d=None, triangulated=None, ba_res=None, p3d_out=None) -> None:
     if n_frames > 0 and imgs is not None:
@@ -763,17 +790,9 @@ class ORBextractor:
         frame's), d_last_outlier uint8 [n_pairs, capacity].  d_matches_cur int32 [n_pairs, capacity] (row p: the last frame's
         feature matched to each of frame cur[p]'s features, or -1: pose_optimize_batch_device's d_match), d_res [n_pairs]
         PROJ_RESULT_DTYPE records (32 bytes).  Stream-ordered on the context's stream."""
-        last = np.ascontiguousarray(last, np.int32).reshape(-1)
-        cur = np.ascontiguousarray(cur, np.int32).reshape(-1)
-        point_set = np.ascontiguousarray(point_set, np.int32).reshape(-1)
-        if len(last) != len(cur) or len(last) != len(point_set):
-            raise OrbxError(E_BADARG, "last, cur and point_set must have the same length")
-        cap, nf, ns, P = int(capacity or self.capacity), int(n_frames), int(n_point_sets), len(last)
-        # (as unsigned, a negative index is a huge one)
-        if P and int(np.maximum(last.view(np.uint32), cur.view(np.uint32)).max()) >= nf:
-            raise ValueError("a pair names a frame outside the batch of %d" % nf)
-        if P and int(point_set.view(np.uint32).max()) >= ns:
-            raise ValueError("a pair names a point set outside the %d given" % ns)
+        cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
+        last, cur, point_set = _pair_lists(("last", "cur", "point_set"), (last, cur, point_set), nf, ns, "point set")
+        P = len(last)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         _need("the keypoint array", d_kps_un, nf * cap * 28)
@@ -817,8 +836,7 @@ class ORBextractor:
         m = per_feature(None if mask is None else np.asarray(mask) != 0, "the mask")
         out = per_feature(None if last_outlier is None else np.asarray(last_outlier) != 0, "last_outlier")
         pd = per_feature(point_desc, "point_desc", 32)
-        T = np.asarray(Tcw, np.float32)
-        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        pose = _pose12(Tcw)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         mc = np.full(max(len(ck), 1), -1, np.int32)
@@ -842,16 +860,9 @@ class ORBextractor:
         Optional: d_outlier uint8 [n_pairs, capacity] (read only), d_point_view uint8 [n_pairs, map_capacity] (LOCAL_NOT_IN_VIEW,
         LOCAL_SEEN or the predicted level).  d_res [n_pairs] LOCAL_RESULT_DTYPE records (60 bytes).  Stream-ordered on the
         context's stream."""
-        frame = np.ascontiguousarray(frame, np.int32).reshape(-1)
-        map_set = np.ascontiguousarray(map_set, np.int32).reshape(-1)
-        if len(frame) != len(map_set):
-            raise OrbxError(E_BADARG, "frame and map_set must have the same length")
-        cap, mcap, nf, ns, P = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets), len(frame)
-        # (as unsigned, a negative index is a huge one)
-        if P and int(frame.view(np.uint32).max()) >= nf:
-            raise ValueError("a pair names a frame outside the batch of %d" % nf)
-        if P and int(map_set.view(np.uint32).max()) >= ns:
-            raise ValueError("a pair names a map set outside the %d given" % ns)
+        cap, mcap, nf, ns = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets)
+        frame, map_set = _pair_lists(("frame", "map_set"), (frame, map_set), nf, ns, "map set")
+        P = len(frame)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         _need("the keypoint array", d_kps_un, nf * cap * 28)
@@ -905,8 +916,7 @@ class ORBextractor:
             if len(given) != len(k):
                 raise OrbxError(E_BADARG, "matches needs one entry per feature")
             m[:len(k)] = given
-        T = np.asarray(Tcw, np.float32)
-        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        pose = _pose12(Tcw)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         view = np.zeros(max(len(mp), 1), np.uint8)
@@ -931,17 +941,9 @@ class ORBextractor:
         (match_bow_pairs_device's d_matches_f, pose_optimize_batch_device's d_match).  Optional: d_point_desc uint8 [n_point_sets,
         capacity, 32] (default the keyframe's descriptors), d_outlier uint8 [n_pairs, capacity] (read only).  d_res [n_pairs]
         KFPROJ_RESULT_DTYPE records (52 bytes).  Stream-ordered on the context's stream."""
-        kf = np.ascontiguousarray(kf, np.int32).reshape(-1)
-        cur = np.ascontiguousarray(cur, np.int32).reshape(-1)
-        point_set = np.ascontiguousarray(point_set, np.int32).reshape(-1)
-        if len(kf) != len(cur) or len(kf) != len(point_set):
-            raise OrbxError(E_BADARG, "kf, cur and point_set must have the same length")
-        cap, nf, ns, P = int(capacity or self.capacity), int(n_frames), int(n_point_sets), len(kf)
-        # (as unsigned, a negative index is a huge one)
-        if P and int(np.maximum(kf.view(np.uint32), cur.view(np.uint32)).max()) >= nf:
-            raise ValueError("a pair names a frame outside the batch of %d" % nf)
-        if P and int(point_set.view(np.uint32).max()) >= ns:
-            raise ValueError("a pair names a point set outside the %d given" % ns)
+        cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
+        kf, cur, point_set = _pair_lists(("kf", "cur", "point_set"), (kf, cur, point_set), nf, ns, "point set")
+        P = len(kf)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         _need("the keypoint array", d_kps_un, nf * cap * 28)
@@ -994,8 +996,7 @@ class ORBextractor:
             if len(given) != len(ck):
                 raise OrbxError(E_BADARG, "matches needs one entry per feature of the current frame")
             mc[:len(ck)] = given
-        T = np.asarray(Tcw, np.float32)
-        pose = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        pose = _pose12(Tcw)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         b = _Bounds(*[int(v) for v in bounds])
         res = KfProjResult()
@@ -1449,8 +1450,7 @@ class ORBextractor:
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
         if len(pts) != len(k) or (m is not None and len(m) != len(k)):
             raise OrbxError(E_BADARG, "points and mask must have one entry per keypoint of the frame")
-        T = np.asarray(Tcw, np.float32)
-        pose0 = np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+        pose0 = _pose12(Tcw)
         Kf = np.ascontiguousarray(K, np.float32).reshape(9)
         sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
         if sig is not None and len(sig) != self.nlevels:

@@ -171,7 +171,7 @@ struct orbx_ctx {
   size_t mCap = 0;
   InitScratch init;               // the Initializer (orbx_init.cpp)
   DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
-  MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp)
+  MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp), the matchers by projection (orbx_match_proj.cpp)
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
   PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
   PnpScratch pnp;                 // orbx_pnp_solve* (orbx_pose.cpp)
@@ -2499,7 +2499,7 @@ int orbx_debug_std_sort(orbx_ctx* ctx, int32_t* triples, int n) {
 }  // extern "C"
 
 // ---- what the modules in their own files need of a context (orbx_host.h; orbx_ctx is private to this file): orbx_init.cpp,
-// orbx_bow.cpp, orbx_db.cpp, orbx_voc_train.cpp, orbx_match_bow.cpp, orbx_ba.cpp and orbx_pose.cpp ----------------------------
+// orbx_bow.cpp, orbx_db.cpp, orbx_voc_train.cpp, orbx_match_bow.cpp, orbx_match_proj.cpp, orbx_ba.cpp and orbx_pose.cpp -------
 namespace orbx {
 int ctxDevice(const orbx_ctx* c) { return c->device; }
 hipStream_t ctxStream(const orbx_ctx* c) { return c->st; }

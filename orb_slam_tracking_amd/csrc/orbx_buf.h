@@ -171,7 +171,7 @@ struct InitScratch {
 };
 
 // What a context keeps for orbx_match_bow*, orbx_match_projection*, orbx_match_local_map* and orbx_match_keyframe_projection*
-// (orbx_match_bow.cpp).
+// (orbx_match_bow.cpp, orbx_match_proj.cpp).
 struct MatchBowScratch {
   HeldArray<int32_t> pairs;      // the pair list [2][n_pairs] of the last orbx_match_bow* call
   DeviceBuf<uint8_t> dIo;        // staging of orbx_match_bow

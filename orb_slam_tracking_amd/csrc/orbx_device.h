@@ -458,6 +458,13 @@ struct MatchBowArgs {
 
 // ---- ORBmatcher::SearchByProjection (orbx_match_proj_kernel.hip): one workgroup per (last frame, current frame) pair ----
 constexpr int MP_THREADS = 512;
+// what the three projection matchers take alike: the camera, the search radius factor, the image bounds and the pyramid's scales
+struct MatchCamArgs {
+  float fx, fy, cx, cy, th;
+  orbx_bounds b;
+  int32_t nLevels;
+  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+};
 struct MatchProjArgs {
   const orbx_keypoint* kps;    // [nFrames][cap] undistorted
   const uint8_t* desc;         // [nFrames][cap][32], 16-byte aligned
@@ -468,10 +475,8 @@ struct MatchProjArgs {
   const uint8_t* lastOutlier;  // nullable [nPairs][cap]
   const float* pose;           // [nPairs][12]
   const int32_t* pairs;        // [3][nPairs] last frames, current frames, point sets
-  int32_t cap, nPairs, nLevels, checkOri;
-  float fx, fy, cx, cy, th;
-  orbx_bounds b;
-  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t cap, nPairs, checkOri;
+  MatchCamArgs cam;
   int32_t* matchesCur;         // [nPairs][cap]
   orbx_proj_result* res;       // [nPairs]
 };
@@ -491,10 +496,9 @@ struct MatchLocalArgs {
   const uint8_t* outlier;     // nullable [nPairs][cap]
   const float* pose;          // [nPairs][12]
   const int32_t* pairs;       // [2][nPairs] frames, map sets
-  int32_t cap, mapCap, nPairs, nLevels;
-  float fx, fy, cx, cy, th, nnratio;
-  orbx_bounds b;
-  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t cap, mapCap, nPairs;
+  float nnratio;
+  MatchCamArgs cam;
   int32_t* matches;           // [nPairs][cap] in and out
   uint8_t* pointView;         // nullable [nPairs][mapCap]
   orbx_local_result* res;     // [nPairs]
@@ -513,10 +517,8 @@ struct MatchKfProjArgs {
   const uint8_t* outlier;     // nullable [nPairs][cap]
   const float* pose;          // [nPairs][12]
   const int32_t* pairs;       // [3][nPairs] keyframes, current frames, point sets
-  int32_t cap, nPairs, nLevels, orbDist, checkOri;
-  float fx, fy, cx, cy, th;
-  orbx_bounds b;
-  float scale[ORBX_MAX_LEVELS];  // the context's mvScaleFactor
+  int32_t cap, nPairs, orbDist, checkOri;
+  MatchCamArgs cam;
   int32_t* matches;           // [nPairs][cap] in and out
   orbx_kfproj_result* res;    // [nPairs]
 };

@@ -1,7 +1,7 @@
 // orbx_match_grid.h — a frame's grid in LDS, for the kernels that search windows of it (orbx_match_proj_kernel.hip,
-// orbx_match_local_kernel.hip): Frame::PosInGrid (SlamTypes/Frame.cpp:89-99) as the cells' start table plus the features' indices
-// by cell, and the cell range of Frame::GetFeaturesInArea (:163-206).  Device code; every function is called by all MP_THREADS
-// threads of a workgroup.
+// orbx_match_local_kernel.hip, orbx_match_kfproj_kernel.hip, through orbx_match_rounds.h, which walks the windows):
+// Frame::PosInGrid (SlamTypes/Frame.cpp:89-99) as the cells' start table plus the features' indices by cell, and the cell range of
+// Frame::GetFeaturesInArea (:163-206).  Device code; every function is called by all MP_THREADS threads of a workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,13 +1,14 @@
 // orbx_match_proj_kernel.hip — ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono = true) for a batch of
 // (last frame L, current frame C) pairs (include/orbx.h, "matching by projection").  gfx950.
 //
-// One workgroup of MP_THREADS threads per pair, one launch per call.  The workgroup builds C's grid in LDS (orbx_match_grid.h: the cells' start
-// table and the features' indices by cell: Frame::PosInGrid, Frame.cpp:89-99) and then gives every feature of L a thread: the
-// thread projects the feature's map point and walks its window (Frame::GetFeaturesInArea, Frame.cpp:163-206) cell x outer, cell
-// y inner.  Inside a cell the indices lie in the order the fill's atomics left them, so a cell's best is taken as the smallest
-// (distance, index) of the cell, and cells are compared with the reference's strict `dist < bestDist`: the first candidate with
-// the smallest distance in the order (cell x, cell y, index), without a key that would have to hold all four (at 16384 features
-// distance, cell and index need 35 bits).
+// One workgroup of MP_THREADS threads per pair, one launch per call.  The workgroup builds C's grid in LDS (orbx_match_grid.h: the
+// cells' start table and the features' indices by cell: Frame::PosInGrid, Frame.cpp:89-99) and then gives every feature of L a
+// thread: the thread projects the feature's map point and walks its window (Frame::GetFeaturesInArea, Frame.cpp:163-206) cell x
+// outer, cell y inner.  The pose, the camera, the walk and the launcher are orbx_match_rounds.h's, shared with the other two
+// projection kernels.  Inside a cell the indices lie in the order the fill's atomics left them, so a cell's best is taken as the
+// smallest (distance, index) of the cell, and cells are compared with the reference's strict `dist < bestDist`: the first
+// candidate with the smallest distance in the order (cell x, cell y, index), without a key that would have to hold all four (at
+// 16384 features distance, cell and index need 35 bits).
 //
 // The sequential rule -- feature i does not see the candidates that features before it took -- is resolved in rounds, all
 // unresolved features of L in parallel:
@@ -37,8 +38,8 @@
 #include <hip/hip_runtime.h>
 
 #include "orbx_launch.h"
-#include "orbx_match_grid.h"
 #include "orbx_match_hist.h"
+#include "orbx_match_rounds.h"
 
 namespace orbx {
 namespace {
@@ -49,9 +50,8 @@ constexpr uint32_t MP_NO_PICK = 0x7fffu;                 // pick[i]: low 15 bits
 constexpr uint32_t MP_DISPLACED = 0x8000u;               // ... bit 15: with nothing taken i would have taken another one
 static_assert(BOW_MAX_FEATURES <= (int)MP_NO_PICK, "a pick is 15 bits");
 
-__host__ __device__ constexpr int mpBitWords(int cap) { return (cap + 31) >> 5; }
 __host__ __device__ constexpr size_t mpLdsBytes(int cap) {
-  return (size_t)4 * (MP_START_WORDS + cap + 2 * mpBitWords(cap)) + (size_t)2 * 2 * ((cap + 1) & ~1);
+  return (size_t)4 * (MP_START_WORDS + cap + 2 * mrBitWords(cap)) + (size_t)2 * 2 * ((cap + 1) & ~1);
 }
 
 // what the threads of a pair share about it
@@ -61,7 +61,7 @@ struct MpPair {
   const float* pts;
   const uint8_t* mask;
   const uint8_t* outl;
-  float R[9], t[3];
+  MrPose pose;
   MpGrid g;
 };
 
@@ -71,23 +71,18 @@ __device__ __forceinline__ int mpProject(const MatchProjArgs& a, const MpPair& P
   if (P.mask && P.mask[i] == 0) return 0;
   if (P.outl && P.outl[i] != 0) return 0;
   const int oct = P.kpsL[i].octave;
-  if (oct < 0 || oct >= a.nLevels) {
+  if (oct < 0 || oct >= a.cam.nLevels) {
     *status |= ORBX_PROJ_BAD_INPUT;
     return 0;
   }
   const float X = P.pts[3 * (size_t)i], Y = P.pts[3 * (size_t)i + 1], Z = P.pts[3 * (size_t)i + 2];
   if (!(mpFinite(X) && mpFinite(Y) && mpFinite(Z))) *status |= ORBX_PROJ_NONFINITE;
-  const float xc = ((P.R[0] * X + P.R[1] * Y) + P.R[2] * Z) + P.t[0];
-  const float yc = ((P.R[3] * X + P.R[4] * Y) + P.R[5] * Z) + P.t[1];
-  const float zc = ((P.R[6] * X + P.R[7] * Y) + P.R[8] * Z) + P.t[2];
+  float xc, yc, zc;
+  mrToCamera(P.pose, P.pts, i, &xc, &yc, &zc);
   const float invz = 1.0f / zc;
   if (invz < 0.0f) return 1;
-  const float pu = (a.fx * xc) * invz + a.cx, pv = (a.fy * yc) * invz + a.cy;
-  if (!mpFinite(pu) || !mpFinite(pv)) return 1;
-  if (pu < P.g.minX || pu > P.g.maxX || pv < P.g.minY || pv > P.g.maxY) return 1;
-  *u = pu;
-  *v = pv;
-  *r = a.th * scale[oct];
+  if (!mrToImage(a.cam, P.g, xc, yc, invz, u, v)) return 1;
+  *r = a.cam.th * scale[oct];
   *o = oct;
   return 2;
 }
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   __shared__ int sCnt[8];  // status, nmatches, n_points, n_in_image, n_with_candidates, n_displaced, n_rot_removed, rounds
   __shared__ int sAny;
   const int pair = blockIdx.x, t = threadIdx.x;
-  const int cap = a.cap, words = mpBitWords(cap);
+  const int cap = a.cap, words = mrBitWords(cap);
   int* const cellStart = (int*)mpLds;                       // [MP_CELLS + 1]: cell c holds cellIdx[cellStart[c] .. cellStart[c + 1])
   int* const claim = cellStart + MP_START_WORDS;            // [cap] per feature of C: the smallest claimant; of a taken one: its match
   uint32_t* const taken = (uint32_t*)(claim + cap);         // [words] bits over C's features
@@ -119,17 +114,9 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   P.mask = a.pointMask ? a.pointMask + (size_t)ps * cap : nullptr;
   P.outl = a.lastOutlier ? a.lastOutlier + (size_t)pair * cap : nullptr;
   int status = (rawL != nL || rawC != nC) ? ORBX_PROJ_BAD_INPUT : 0;
-  {
-    const float* pose = a.pose + (size_t)pair * 12;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) { P.R[k] = pose[k]; ok = ok && mpFinite(P.R[k]); }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { P.t[k] = pose[9 + k]; ok = ok && mpFinite(P.t[k]); }
-    if (!ok) status |= ORBX_PROJ_NONFINITE;
-  }
+  if (!mrLoadPose(a.pose, pair, &P.pose)) status |= ORBX_PROJ_NONFINITE;
   if (t != 0) status = 0;  // (what all threads see alike is reported once)
-  P.g = mpGridOf(a.b);
+  P.g = mpGridOf(a.cam.b);
   const uint4* __restrict__ descC = (const uint4*)a.desc + (size_t)fc * cap * 2;
   const uint4* __restrict__ descQ = a.pointDesc ? (const uint4*)a.pointDesc + (size_t)ps * cap * 2 : (const uint4*)a.desc + (size_t)fl * cap * 2;
   int* __restrict__ mC = a.matchesCur + (size_t)pair * cap;
@@ -137,7 +124,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   // ---- start state, and C's grid
   for (int c = t; c < MP_START_WORDS; c += MP_THREADS) cellStart[c] = 0;
   for (int k = t; k < 2 * words; k += MP_THREADS) taken[k] = 0;  // (taken and pending lie one behind the other)
-  if (t < ORBX_MAX_LEVELS) sScale[t] = a.scale[t];
+  if (t < ORBX_MAX_LEVELS) sScale[t] = a.cam.scale[t];
   if (t < MATCH_HISTO_LENGTH) hist[t] = 0;
   if (t < 3) { sKeep[t] = -1; sKeepV[t] = 0; }
   if (t < 8) sCnt[t] = 0;
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
     nPoints += stage >= 1;
     if (stage == 2) {
       nInImage++;
-      atomicOr(&pending[i >> 5], 1u << (i & 31));
+      mrSetBit(pending, i);
       sAny = 1;
     }
   }
@@ -165,45 +152,31 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   int rounds = 0;
   while (sAny) {  // (uniform: read behind a barrier, written again only behind the next one)
     for (int j = t; j < nC; j += MP_THREADS)
-      if (!((taken[j >> 5] >> (j & 31)) & 1u)) claim[j] = MP_FREE;
+      if (!mrBit(taken, j)) claim[j] = MP_FREE;
     __syncthreads();
     if (t == 0) sAny = 0;
     // A. picks and claims
     for (int i = t; i < nL; i += MP_THREADS) {
-      if (!((pending[i >> 5] >> (i & 31)) & 1u)) continue;
+      if (!mrBit(pending, i)) continue;
       float u, v, r;
       int o, ignored = 0;
       mpProject(a, P, sScale, i, &u, &v, &r, &o, &ignored);  // (the same arithmetic as above: stage 2 again)
-      int x0, x1, y0, y1;
-      const bool none = !mpWindow(P.g, u, v, r, &x0, &x1, &y0, &y1);
       const uint4 q0 = descQ[(size_t)i * 2], q1 = descQ[(size_t)i * 2 + 1];
       int bestD = 256, bestJ = -1, bestCell = -1;  // among the untaken candidates
       int freeD = 256, freeJ = -1, freeCell = -1;  // among all of them
       int nCand = 0;
-      if (!none)
-        for (int cx = x0; cx <= x1; cx++)
-          for (int cy = y0; cy <= y1; cy++) {
-            const int c = cx * ORBX_GRID_ROWS + cy;
-            const int k1 = cellStart[c + 1];
-            for (int k = cellStart[c]; k < k1; k++) {
-              const int j = cellIdx[k];
-              const orbx_keypoint* kp = P.kpsC + j;
-              const int lev = kp->octave;
-              if (!(lev >= o - 1 && lev <= o + 1)) continue;  // (bCheckLevels holds: maxLevel = o + 1 >= 0)
-              const float dx = kp->x - u, dy = kp->y - v;
-              if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-              nCand++;
-              const int d = mpDistance(q0, q1, descC[(size_t)j * 2], descC[(size_t)j * 2 + 1]);
-              if (d < freeD || (d == freeD && c == freeCell && j < freeJ)) { freeD = d; freeJ = j; freeCell = c; }
-              if ((taken[j >> 5] >> (j & 31)) & 1u) continue;
-              if (d < bestD || (d == bestD && c == bestCell && j < bestJ)) { bestD = d; bestJ = j; bestCell = c; }
-              if (d <= MP_TH_HIGH) atomicMin(&claim[j], i);
-            }
-          }
+      mrWalk(P.g, P.kpsC, cellStart, cellIdx, u, v, r, o - 1, o + 1, [&](int j, int c) {
+        nCand++;
+        const int d = mpDistance(q0, q1, descC[(size_t)j * 2], descC[(size_t)j * 2 + 1]);
+        if (d < freeD || (d == freeD && c == freeCell && j < freeJ)) { freeD = d; freeJ = j; freeCell = c; }
+        if (mrBit(taken, j)) return;
+        if (d < bestD || (d == bestD && c == bestCell && j < bestJ)) { bestD = d; bestJ = j; bestCell = c; }
+        if (d <= MP_TH_HIGH) atomicMin(&claim[j], i);
+      });
       if (rounds == 0) nWithCand += nCand > 0;
       const int got = bestD <= MP_TH_HIGH ? bestJ : -1, alone = freeD <= MP_TH_HIGH ? freeJ : -1;
       if (got < 0) {  // final without a match
-        atomicAnd(&pending[i >> 5], ~(1u << (i & 31)));
+        mrClearBit(pending, i);
         nDisplaced += alone >= 0;
       } else {
         pick[i] = (uint16_t)((uint32_t)got | (got != alone ? MP_DISPLACED : 0u));
@@ -212,12 +185,12 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
     __syncthreads();
     // B. a pick whose smallest claimant is its feature is final
     for (int i = t; i < nL; i += MP_THREADS) {
-      if (!((pending[i >> 5] >> (i & 31)) & 1u)) continue;
+      if (!mrBit(pending, i)) continue;
       const uint32_t pk = pick[i];
       const int j = (int)(pk & MP_NO_PICK);
       if (claim[j] == i) {
-        atomicOr(&taken[j >> 5], 1u << (j & 31));
-        atomicAnd(&pending[i >> 5], ~(1u << (i & 31)));
+        mrSetBit(taken, j);
+        mrClearBit(pending, i);
         nm++;
         nDisplaced += (pk & MP_DISPLACED) != 0;
       } else {
@@ -231,7 +204,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   // ---- steps 6 and 7: a taken feature's claim is its match
   if (a.checkOri) {  // (uniform)
     for (int j = t; j < nC; j += MP_THREADS)
-      if ((taken[j >> 5] >> (j & 31)) & 1u) {
+      if (mrBit(taken, j)) {
         const int bin = matchRotBin(P.kpsL[claim[j]].angle, P.kpsC[j].angle);
         if (bin >= 0) atomicAdd(&hist[bin], 1);
       }
@@ -248,7 +221,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
   int dropped = 0;
   for (int j = t; j < nC; j += MP_THREADS) {
     int m = -1;
-    if ((taken[j >> 5] >> (j & 31)) & 1u) {
+    if (mrBit(taken, j)) {
       m = claim[j];
       if (a.checkOri) {
         // a match's bin is a function of the match: recomputed here from the two angles instead of kept in a list per bin
@@ -277,13 +250,8 @@ __global__ __launch_bounds__(MP_THREADS) void k_match_proj(MatchProjArgs a) {
 hipError_t launch_match_proj(hipStream_t st, const MatchProjArgs& a) {
   static_assert(sizeof(orbx_proj_result) == 32, "eight int32");
   static_assert(mpLdsBytes(BOW_MAX_FEATURES) + 512 <= 160 * 1024, "a workgroup's LDS at the largest capacity");
-  const size_t lds = mpLdsBytes(a.cap);
-  if (lds > 48 * 1024) {  // (beyond the default limit of a launch's dynamic LDS)
-    const hipError_t e = hipFuncSetAttribute((const void*)k_match_proj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_match_proj, dim3((unsigned)a.nPairs), dim3(MP_THREADS), lds, st, a);
-  return hipGetLastError();
+  static_assert(mpLdsBytes(1024) == 20752, "capacity 1024: seven workgroups per CU by LDS");
+  return mrLaunch(k_match_proj, a.nPairs, mpLdsBytes(a.cap), st, a);
 }
 
 }  // namespace orbx

@@ -142,6 +142,51 @@ def test_rule_world_equals_restatement(torch, ext, name):
     check_pair(m[0], v[0], r[0], w, name)
 
 
+def _small_frame_large_map():
+    """16 features against a map of 1500 points of which a few dozen are in view (the others that were get their normal turned
+    away): twelve features lie on projections of points in view, eight of those points with an index >= 512; four features bring
+    entry matches that name points with an index >= 512, two of them as outliers."""
+    rng = np.random.default_rng(123)
+    K, pose = L.camera(), L.pose_of(52)
+    pts, normals, dists, mdesc, mask = L.make_map(1500, 53, pose, K)
+    none_k, none_d = L._none_frame()
+    proj = L.search_local_points(L.World(none_k, none_d, pts, normals, dists, mdesc, None, pose, K))["proj"]
+    in_view = np.flatnonzero((proj[:, 5] == 5.0) & (mask != 0))
+    low, high = in_view[in_view < 512][:12], in_view[in_view >= 512][:28]
+    assert len(low) == 12 and len(high) == 28
+    away = np.setdiff1d(np.flatnonzero(proj[:, 5] == 5.0), np.r_[low, high])
+    normals[away] = -normals[away]
+    shown = np.r_[high[:8], low[:4]]
+    k = np.zeros(16, KP)
+    k["x"], k["y"], k["octave"] = rng.uniform(50, 590, 16), rng.uniform(50, 430, 16), rng.integers(0, L.NLEVELS, 16)
+    k["x"][:12], k["y"][:12], k["octave"][:12] = proj[shown, 0], proj[shown, 1], proj[shown, 3]
+    k["angle"], k["size"], k["class_id"] = rng.uniform(0, 360, 16), 31.0, -1
+    desc = rng.integers(0, 256, (16, 32), dtype=np.uint8)
+    for f, i in enumerate(shown):
+        desc[f] = L._flip(mdesc[i], int(rng.integers(0, 30)), rng)
+    entry, outlier = np.full(16, -1, np.int32), np.zeros(16, np.uint8)
+    entry[[8, 13, 10, 11]] = [high[8], high[9], high[10], 1499]  # (features 10 and 11 lie on projections: cleared, they can match anew)
+    outlier[[10, 11]] = 1
+    return L.World(k, desc, pts, normals, dists, mdesc, mask, pose, K, matches=entry, outlier=outlier)
+
+
+def test_seen_bits_beyond_the_claims(torch, ext):
+    """capacity 16 against map_capacity 2048: the "seen" bits of the entry pass need 64 words where the claims that later lie in
+    the same LDS need 16, and the entry names points whose bits lie beyond claim[capacity]."""
+    cap, mcap = 16, 2048
+    w = _small_frame_large_map()
+    e = w.expected()
+    named, new = w.matches[w.matches >= 0], e["matches"][(e["matches"] >= 0) & (e["matches"] != w.matches)]
+    print("restatement", e["res"], "entry", w.matches.tolist(), "row", e["matches"].tolist())
+    assert (mcap + 31) // 32 > cap and w.n_f <= cap and 1400 <= w.n_m <= 1600
+    assert 24 <= e["res"]["n_in_view"] <= 60
+    assert e["res"]["n_seen"] > 0 and e["res"]["n_outliers_cleared"] > 0 and e["res"]["nmatches"] > 0
+    assert len(named) and named.min() >= 512 and w.matches[w.outlier != 0].min() >= 512
+    assert len(new) == e["res"]["nmatches"] and new.max() >= 512
+    m, v, r = batch_of(torch, w, cap, mcap).run(torch, ext, w.K, w.bounds, w.th, w.nnratio)
+    check_pair(m[0], v[0], r[0], w, "16 features, 1500 points")
+
+
 @pytest.mark.parametrize("caps", ("exact", "largest"))
 def test_capacities_and_counts(torch, orbx, ext, caps):
     """Capacities that are exactly the counts (nothing lies beyond the rows), and both at ORBX_BOW_MAX_FEATURES with counts far

@@ -59,7 +59,7 @@ def test_library_allocates_only_through_the_buffer_types():
     frees each rank's buffers under that rank's device and is not covered.)"""
     src = os.path.join(ROOT, "orb_slam_tracking_amd", "csrc")
     covered = ("orbx_api.cpp", "orbx_init.cpp", "orbx_bow.cpp", "orbx_db.cpp", "orbx_voc_train.cpp", "orbx_match_bow.cpp",
-               "orbx_ba.cpp", "orbx_pose.cpp")
+               "orbx_match_proj.cpp", "orbx_ba.cpp", "orbx_pose.cpp")
     assert sorted(covered + ("orbx_multi.cpp",)) == sorted(f for f in os.listdir(src) if f.endswith(".cpp"))
     for fn in covered:
         calls = re.findall(r"\bhip(?:Host)?(?:Malloc|Free)\b", open(os.path.join(src, fn), errors="replace").read())
