@@ -1323,6 +1323,138 @@ int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un
                                    const float* K, const orbx_bounds* bounds, float th, int orb_dist, int check_orientation,
                                    int32_t* matches, const uint8_t* outlier, orbx_kfproj_result* res);
 
+/* ---- growing the map: LocalMapping::CreateNewMapPoints ---------------------------------------------------------------------------
+ * The one step that makes map points after the Initializer's first pair: a new keyframe KF1 is matched against a covisible
+ * neighbour KF2 along the epipolar lines (ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false),
+ * monocular), and every match is triangulated and gated on parallax, depth, reprojection error and scale.  The reference ships
+ * neither function: this is ORB-SLAM2's code, [from-knowledge], PARITY UNPINNED, bit-identical to a CPU restatement of the rules
+ * below (tests/cpp/tri_ref.cpp; the arithmetic is csrc/orbx_tri_math.inc on both sides, the walk is written twice) and equal in
+ * every discrete outcome to an independent numpy statement away from the thresholds (tests/test_tri_host.py).
+ * f32 without contraction unless stated; a matrix product is "gemm on CV_32F" as in the Initializer: the products and their sum
+ * in f64 in ascending k, one rounding.  Poses are Tcw per FRAME: d_pose float [n_frames][12], R row-major, then t.
+ *
+ * orbx_match_triangulation*, pair p = (KF1 = h_kf1[p], KF2 = h_kf2[p]):
+ *   1. from the two poses and K: R12 = R1w * R2w^T; t12 = -R12 * t2w + t1w; F12 = K^-T * [t12]x * R12 * K^-1, the three products
+ *      left to right; Ow = -Rcw^T * tcw for both keyframes (KeyFrame::SetPose's association); C2 = R2w * Ow1 + t2w;
+ *      invz = 1.0f / C2z; ex = (fx * C2x) * invz + cx, ey likewise; baseline = (float)sqrt of the f64 sum of squares of Ow2 - Ow1.
+ *   2. every matches12[i] = -1, the 30 rotation bins empty.  The node ids present in both FeatureVectors in ascending order; a
+ *      node's KF1 features i in ascending index, those with mask[KF1][i] != 0 (the feature already has a map point) skipped.
+ *   3. for each remaining i (a "query"): a = (x1 * F00 + y1 * F10) + F20, b and c likewise from columns 1 and 2; bestDist = 50
+ *      (TH_LOW), bestIdx = -1.  Over the node's KF2 features j in ascending index that no earlier KF1 feature of this call took
+ *      and whose mask[KF2][j] == 0, d = popcount(desc1[i] ^ desc2[j]); d > 50 || d > bestDist: skipped -- the test is NOT strict,
+ *      so among equal distances the LAST passing candidate wins (the opposite of SearchByBoW).  Then
+ *        dx = ex - x2, dy = ey - y2; dx * dx + dy * dy < 100.0f * scale[octave2]: skipped (too close to the epipole);
+ *        CheckDistEpipolarLine: num = (a * x2 + b * y2) + c, den = a * a + b * b; den == 0: rejected; accepted iff
+ *        num * num / den < 3.84f * sigma2[octave2];
+ *      on accept bestIdx = j, bestDist = d.
+ *   4. bestIdx >= 0: matches12[i] = bestIdx, bestIdx is taken, and with check_orientation the match joins the bin of
+ *      angle1[i] - angle2[bestIdx] (the corrected factor and the kept out-of-range bin of SearchByBoW's deviations 1 and 2).
+ *   5. with check_orientation, ComputeThreeMaxima and its 0.1 rule; the losing bins' matches go back to -1.  nmatches = the
+ *      entries that remain.
+ * Optional gate (CreateNewMapPoints' ratioBaselineDepth): with d_median_depth (float [n_frames], ComputeSceneMedianDepth(2) of
+ * each keyframe; NULL = no gate), baseline / d_median_depth[KF2] < 0.01f refuses the pair: ORBX_TRI_LOW_BASELINE, rules 2-5 do
+ * not run, its row is all -1.  A median that is no positive finite number is garbage: ORBX_TRI_BAD_INPUT is set and the pair is
+ * matched without the gate.
+ * Documented deviations from ORB-SLAM2:
+ *   1. K^-1 is the closed form (1/fx, 0, -cx/fx; 0, 1/fy, -cy/fy; 0, 0, 1), f32; ORB-SLAM2 calls cv::Mat::inv.
+ *   2. The bin factor and the out-of-range bin: deviations 1 and 2 of SearchByBoW.
+ *   3. The counters n_with_candidates, n_epipole_rejected and n_epiline_rejected are taken over every free, unmasked candidate
+ *      with d <= 50, whatever bestDist was when the walk reached it: they do not depend on the order of the walk.
+ *   4. baseline == 0 (a keyframe paired with itself) is refused as ORBX_TRI_ZERO_BASELINE: the epipole and F12 of such a pair are
+ *      rounding noise; the record holds zeros in their place.
+ *   5. Garbage is flagged and never followed: counts outside [0, capacity] are clamped and set ORBX_TRI_BAD_INPUT; a FeatureVector
+ *      entry naming no feature is skipped; a non-finite pose sets ORBX_TRI_NONFINITE and matches nothing; a candidate with d <= 50
+ *      whose octave is outside [0, nlevels) sets ORBX_TRI_BAD_INPUT and is skipped.  A FeatureVector that is not ascending gives
+ *      unspecified matches (and nothing worse).
+ *   6. Pairs are independent.  In ORB-SLAM2 a point made with one neighbour takes KF1's feature out of the next neighbour's
+ *      search; here two pairs with the same KF1 may both triangulate feature i (SearchInNeighbors fuses such duplicates later;
+ *      not part of this library).  A caller that wants the reference's order issues the neighbours in successive calls and
+ *      updates the mask between them. */
+#define ORBX_TRI_BAD_INPUT 2
+#define ORBX_TRI_NONFINITE 4
+#define ORBX_TRI_LOW_BASELINE 8
+#define ORBX_TRI_ZERO_BASELINE 16
+typedef struct orbx_tri_match_result {
+  int32_t status;              /* 0, or a bitmask of ORBX_TRI_*; every field is written for every pair */
+  int32_t nmatches;            /* matches that remain behind rule 5 */
+  int32_t n_queries;           /* KF1 features of common nodes that have no map point (rule 3) */
+  int32_t n_with_candidates;   /* ... with a free, unmasked KF2 feature of the node at d <= 50 */
+  int32_t n_epipole_rejected;  /* such (i, j) the epipole test skipped */
+  int32_t n_epiline_rejected;  /* such (i, j) CheckDistEpipolarLine rejected */
+  int32_t n_rot_removed;       /* rule 5 */
+  float baseline, ex, ey;      /* rule 1 */
+  float F12[9];                /* row-major */
+} orbx_tri_match_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  d_kps_un / d_desc32 (16-byte aligned) / d_n and d_fv_node /
+ * d_fv_feat / d_fv_n: the frames as the extract, undistort and bag-of-words calls leave them ([n_frames][capacity]); a frame may
+ * be in any number of pairs, on either side.  d_mask uint8 [n_frames][capacity] (NULL = no feature has a map point): != 0 = the
+ * feature already has one.  K row-major 3x3 (host, f32; finite, fx and fy > 0).  The scale and sigma2 tables are the context's.
+ * d_matches12 int32 [n_pairs][capacity], indexed by KF1's feature -- the Initializer's and the bundle adjustment's matches12
+ * layout; the whole row is written.  d_res [n_pairs].
+ * One workgroup per pair, one launch.  The call returns once queued, with the exception orbx_match_bow_batch_device has: when the
+ * pair list differs from the previous call's on this context, the call first waits for the context stream.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, a pair index outside [0, n_frames), K not finite or
+ * without positive focal lengths -- all checked before anything touches a device; ORBX_E_CAPACITY: capacity >
+ * ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_triangulation_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                          const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                          const uint32_t* d_fv_node, const uint32_t* d_fv_feat, const int32_t* d_fv_n,
+                                          const uint8_t* d_mask, const float* d_pose, const float* K, const float* d_median_depth,
+                                          int check_orientation, int32_t* d_matches12, orbx_tri_match_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: KF1 (n1 features, fv_n1 FeatureVector pairs,
+ * mask1 nullable, pose1 [12]), then KF2; median_depth2 <= 0 or not a number = no gate asked for (+infinity is passed on and is
+ * flagged as the batch form flags it); matches12 holds n1 entries.  A
+ * FeatureVector that names a feature the keyframe does not have: ORBX_E_BADARG.  More than ORBX_BOW_MAX_FEATURES features or
+ * pairs: ORBX_E_CAPACITY.  Synchronous. */
+int orbx_match_triangulation(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* desc1, int n1, const uint32_t* fv_node1,
+                             const uint32_t* fv_feat1, int fv_n1, const uint8_t* mask1, const float* pose1,
+                             const orbx_keypoint* kps_un2, const uint8_t* desc2, int n2, const uint32_t* fv_node2,
+                             const uint32_t* fv_feat2, int fv_n2, const uint8_t* mask2, const float* pose2, const float* K,
+                             float median_depth2, int check_orientation, int32_t* matches12, orbx_tri_match_result* res);
+
+/* orbx_triangulate_matches*: the body of CreateNewMapPoints' loop behind the matcher, for each i with j = matches12[i] >= 0 (j
+ * not below KF2's count, or an octave outside [0, nlevels): ORBX_TRI_BAD_INPUT, the entry is not followed or counted):
+ *   1. xn = ((x - cx) * invfx, (y - cy) * invfy, 1) for both, invfx = 1.0f / fx; ray = Rwc * xn; cos = (float)(ray1 . ray2 /
+ *      (|ray1| * |ray2|)) in f64; kept iff cos > 0 && cos < 0.9998f (the monocular branch), else n_low_parallax.
+ *   2. A's four rows are xn.x * T.row(2) - T.row(0) and xn.y * T.row(2) - T.row(1) for both cameras (T = [R | t], f32); x3D = the
+ *      right singular vector of A's smallest singular value (the f64 one-sided Jacobi of orbx_check_rt), rounded to f32;
+ *      x3D[3] == 0 (or a value that is no number): n_w_zero; otherwise x3D = x3D[0..2] / x3D[3].
+ *   3. z = (float)(R.row(2) . x3D + tz) with the dot product in f64; z1 <= 0: n_behind_1; z2 <= 0: n_behind_2.
+ *   4. per view x, y like z; invz = 1.0f / z; u = (fx * x) * invz + cx, v likewise; errX * errX + errY * errY >
+ *      5.991f * sigma2[octave]: n_reproj_1, then n_reproj_2.
+ *   5. dist1 = |x3D - Ow1| (cv::norm: f64 inside), dist2 likewise; either 0: n_zero_dist.  ratioDist = dist2 / dist1, ratioOctave =
+ *      scale[octave1] / scale[octave2], ratioFactor = 1.5f * scaleFactor; ratioDist * ratioFactor < ratioOctave || ratioDist >
+ *      ratioOctave * ratioFactor: n_scale.
+ *   6. a kept match is a map point at KF1's feature i: d_points[i] = x3D, d_point_mask[i] = 1, d_point_normal[i] =
+ *      ((x3D - Ow1) / dist1 + (x3D - Ow2) / dist2) / 2.0f (UpdateNormalAndDepth with two observations), d_point_dist[i] =
+ *      (mfMinDistance, mfMaxDistance) = (max / scale[nlevels - 1], max = dist1 * scale[octave1]): KF1 is the reference keyframe.
+ *      Every other entry of the row: mask 0 and zeros.
+ * All four arrays are [n_pairs][capacity], indexed by KF1's feature, so pair p's row is a point set for
+ * orbx_match_keyframe_projection* / orbx_pose_optimize* with KF1 as the keyframe.  With two observations
+ * ComputeDistinctiveDescriptors picks KF1's descriptor: that is the consumers' d_point_desc32 == NULL convention, and no
+ * descriptor array is written.
+ * Documented deviations from ORB-SLAM2: cv::SVD on a CV_32F matrix is the project's f64 Jacobi, as in orbx_check_rt (no OpenCV
+ * to pin against); x3D / x3D[3] is an f32 division; the normal's mean is taken in f32 in the order above; deviation 6 above.
+ * A non-finite pose sets ORBX_TRI_NONFINITE and makes no point; a keyframe paired with itself has parallel rays and makes none. */
+typedef struct orbx_tri_result {
+  int32_t status;    /* 0, or a bitmask of ORBX_TRI_BAD_INPUT / ORBX_TRI_NONFINITE */
+  int32_t n_matches; /* entries of matches12 that are followed */
+  int32_t n_points;  /* ... that became map points */
+  int32_t n_low_parallax, n_w_zero, n_behind_1, n_behind_2, n_reproj_1, n_reproj_2, n_zero_dist, n_scale; /* one per gate */
+} orbx_tri_result;
+
+/* Batched, device-resident, stream-ordered on the context stream; d_matches12 is orbx_match_triangulation_batch_device's (or any
+ * matches12 in that layout).  The same refusals as that call.  Several workgroups per pair, one launch. */
+int orbx_triangulate_matches_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                          const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const float* d_pose,
+                                          const float* K, const int32_t* d_matches12, float* d_points, uint8_t* d_point_mask,
+                                          float* d_point_normal, float* d_point_dist, orbx_tri_result* d_res);
+/* The same for one pair in host memory: points [n1][3], point_mask [n1], point_normal [n1][3], point_dist [n1][2].  Synchronous. */
+int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* pose1, const orbx_keypoint* kps_un2,
+                             int n2, const float* pose2, const float* K, const int32_t* matches12, float* points, uint8_t* point_mask,
+                             float* point_normal, float* point_dist, orbx_tri_result* res);
+
 /* ---- measurement hooks (bench.py; HIP events on the ctx stream) ---------------------------- */
 #define ORBX_STAGE_PYRAMID 0
 #define ORBX_STAGE_FAST 1

@@ -345,6 +345,11 @@ struct KeyFrameView {
   const float* mfMinMaxDistance = nullptr;      // [N][2]
   const uint8_t* mbGood = nullptr;              // [N] or null
   const uint8_t* mPointDescriptors = nullptr;   // [N][32] or null
+  // ... and as ORBmatcher::SearchForTriangulation / CreateNewMapPoints read it (orbx.h, "growing the map"): mFeatVec (what
+  // ComputeBoW filled) and the pose Tcw, 12 floats: R row-major, then t.  There mbGood != 0 means "the feature already has a map
+  // point" (such a feature is not searched) and the point arrays are not read.
+  const DBoW2::FeatureVector* mFeatVec = nullptr;
+  const float* mTcw = nullptr;                  // [12]
 };
 
 class ORBmatcher {
@@ -447,6 +452,19 @@ class ORBmatcher {
   int SearchByProjection(FrameT& CurrentFrame, const KeyFrameView& KF, std::vector<int>& vnMatches, float th, int ORBdist,
                          const PoseT& Tcw, const std::vector<bool>* vbOutlier = nullptr, orbx_kfproj_result* result = nullptr);
 
+  // ORB-SLAM2's SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
+  // const bool bOnlyStereo = false), monocular (orbx.h, "growing the map", with its documented deviations; the orientation check
+  // is this matcher's): the features of KF1 without a map point are matched along their epipolar lines against KF2's features
+  // under the same vocabulary node.  F12 and the epipole come from the two views' mTcw and K (9 floats, row-major).
+  // vMatchedPairs = (KF1 feature, KF2 feature) in ascending KF1 index, as ORB-SLAM2 builds it; returns their number.
+  // medianDepth2 > 0: CreateNewMapPoints' baseline gate with KF2's ComputeSceneMedianDepth(2).  Needs the extractor given to the
+  // constructor or setExtractor.
+  int SearchForTriangulation(const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
+                             std::vector<std::pair<size_t, size_t> >& vMatchedPairs, float medianDepth2 = 0.0f,
+                             orbx_tri_match_result* result = nullptr) {
+    return searchForTriangulation(ext_, KF1, KF2, K, vMatchedPairs, medianDepth2, result);
+  }
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -471,6 +489,9 @@ class ORBmatcher {
   inline int searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,
                             int ORBdist, const PoseT& Tcw, const float* K, const std::vector<bool>* vbOutlier,
                             orbx_kfproj_result* result);  // (defined behind PoseT)
+  inline int searchForTriangulation(ORBextractor* e, const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
+                                    std::vector<std::pair<size_t, size_t> >& vMatchedPairs, float medianDepth2,
+                                    orbx_tri_match_result* result);  // (defined behind DBoW2::FeatureVector)
 
   int search(ORBextractor* e, const FrameView& F1, const FrameView& F2, std::vector<int>& vnMatches12, int windowSize) {
     if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): the frames carry none and none was set");
@@ -997,6 +1018,71 @@ inline int ORBmatcher::searchByBoW(ORBextractor* e, const FrameView& KF, const F
                                mbCheckOrientation ? 1 : 0, vnMatchesF.data(), &nmatches);
   if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
   return nmatches;
+}
+
+inline int ORBmatcher::searchForTriangulation(ORBextractor* e, const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
+                                              std::vector<std::pair<size_t, size_t> >& vMatchedPairs, float medianDepth2,
+                                              orbx_tri_match_result* result) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): none was set");
+  if (!KF1.mFeatVec || !KF2.mFeatVec)
+    throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchForTriangulation: a keyframe has no mFeatVec (ComputeBoW has not run)");
+  if (!KF1.mTcw || !KF2.mTcw) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchForTriangulation: a keyframe has no pose (mTcw)");
+  std::vector<uint32_t> node[2], feat[2];
+  const DBoW2::FeatureVector* fv[2] = {KF1.mFeatVec, KF2.mFeatVec};
+  for (int s = 0; s < 2; s++)
+    for (const auto& kv : *fv[s])  // (a map: ascending node ids)
+      for (unsigned int i : kv.second) {
+        node[s].push_back(kv.first);
+        feat[s].push_back(i);
+      }
+  std::vector<int32_t> m12((size_t)(KF1.N > 0 ? KF1.N : 1), -1);
+  orbx_tri_match_result res;
+  const int r = orbx_match_triangulation(e->context(), reinterpret_cast<const orbx_keypoint*>(KF1.mvKeysUn), KF1.mDescriptors, KF1.N,
+                                         node[0].data(), feat[0].data(), (int)node[0].size(), KF1.mbGood, KF1.mTcw,
+                                         reinterpret_cast<const orbx_keypoint*>(KF2.mvKeysUn), KF2.mDescriptors, KF2.N, node[1].data(),
+                                         feat[1].data(), (int)node[1].size(), KF2.mbGood, KF2.mTcw, K, medianDepth2,
+                                         mbCheckOrientation ? 1 : 0, m12.data(), &res);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  vMatchedPairs.clear();
+  for (int i = 0; i < KF1.N; i++)
+    if (m12[(size_t)i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[(size_t)i]));
+  if (result) *result = res;
+  return (int)vMatchedPairs.size();
+}
+
+// The new map points of LocalMapping::CreateNewMapPoints for one neighbour (orbx.h, "growing the map"), indexed by KF1's feature:
+// the layout KeyFrameView's point arrays have, so that KF1 with these arrays is a keyframe for the relocalisation overload of
+// SearchByProjection.
+struct NewMapPoints {
+  std::vector<float> mWorldPos;         // [N1][3]
+  std::vector<uint8_t> mbGood;          // [N1]: 1 = a point was made at this feature
+  std::vector<float> mNormalVector;     // [N1][3]
+  std::vector<float> mfMinMaxDistance;  // [N1][2]
+  orbx_tri_result result;
+};
+
+// The body of CreateNewMapPoints' loop over vMatchedPairs (SearchForTriangulation's): every pair is triangulated and gated on
+// parallax, depth, reprojection error and scale.  Returns the number of points made.
+inline int CreateNewMapPoints(ORBextractor* e, const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
+                              const std::vector<std::pair<size_t, size_t> >& vMatchedPairs, NewMapPoints& out) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "CreateNewMapPoints: no ORBextractor (device context)");
+  if (!KF1.mTcw || !KF2.mTcw) throw orbx::Error(ORBX_E_BADARG, "CreateNewMapPoints: a keyframe has no pose (mTcw)");
+  const size_t n = (size_t)(KF1.N > 0 ? KF1.N : 1);
+  std::vector<int32_t> m12(n, -1);
+  for (const auto& pr : vMatchedPairs) {
+    if (pr.first >= (size_t)KF1.N) throw orbx::Error(ORBX_E_BADARG, "CreateNewMapPoints: a pair names a feature KF1 does not have");
+    m12[pr.first] = (int32_t)pr.second;
+  }
+  out.mWorldPos.assign(n * 3, 0.0f);
+  out.mbGood.assign(n, 0);
+  out.mNormalVector.assign(n * 3, 0.0f);
+  out.mfMinMaxDistance.assign(n * 2, 0.0f);
+  const int r = orbx_triangulate_matches(e->context(), reinterpret_cast<const orbx_keypoint*>(KF1.mvKeysUn), KF1.N, KF1.mTcw,
+                                         reinterpret_cast<const orbx_keypoint*>(KF2.mvKeysUn), KF2.N, KF2.mTcw, K, m12.data(),
+                                         out.mWorldPos.data(), out.mbGood.data(), out.mNormalVector.data(),
+                                         out.mfMinMaxDistance.data(), &out.result);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  return out.result.n_points;
 }
 
 // Features/ORBVocabulary.hpp: TemplatedVocabulary<FORB> with the members ORB-SLAM calls -- loadFromTextFile, transform (BowVector +

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -228,6 +228,40 @@ KFPROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in KFPROJ_RESULT_FIELDS])
 assert KFPROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(KfProjResult) == 52
 
 
+TRI_BAD_INPUT, TRI_NONFINITE, TRI_LOW_BASELINE, TRI_ZERO_BASELINE = 2, 4, 8, 16
+TRI_MATCH_COUNTERS = ("status", "nmatches", "n_queries", "n_with_candidates", "n_epipole_rejected", "n_epiline_rejected", "n_rot_removed")
+TRI_RESULT_FIELDS = ("status", "n_matches", "n_points", "n_low_parallax", "n_w_zero", "n_behind_1", "n_behind_2", "n_reproj_1", "n_reproj_2",
+                     "n_zero_dist", "n_scale")
+
+
+class TriMatchResult(ctypes.Structure):
+    """orbx_tri_match_result: SearchForTriangulation's counters and the pair's geometry (baseline, epipole, F12 row-major)."""
+    _fields_ = [(n, ctypes.c_int32) for n in TRI_MATCH_COUNTERS] + [("baseline", ctypes.c_float), ("ex", ctypes.c_float),
+                                                                    ("ey", ctypes.c_float), ("F12", ctypes.c_float * 9)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n in TRI_MATCH_COUNTERS}
+        d.update(baseline=float(self.baseline), ex=float(self.ex), ey=float(self.ey), F12=np.array(list(self.F12), np.float32).reshape(3, 3))
+        return d
+
+
+TRI_MATCH_RESULT_DTYPE = np.dtype([(n, "<i4") for n in TRI_MATCH_COUNTERS] + [("baseline", "<f4"), ("ex", "<f4"), ("ey", "<f4"),
+                                                                               ("F12", "<f4", (9,))])
+assert TRI_MATCH_RESULT_DTYPE.itemsize == ctypes.sizeof(TriMatchResult) == 76
+
+
+class TriResult(ctypes.Structure):
+    """orbx_tri_result: CreateNewMapPoints' counters for one (KF1, KF2) pair, one per gate."""
+    _fields_ = [(n, ctypes.c_int32) for n in TRI_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+TRI_RESULT_DTYPE = np.dtype([(n, "<i4") for n in TRI_RESULT_FIELDS])
+assert TRI_RESULT_DTYPE.itemsize == ctypes.sizeof(TriResult) == 44
+
+
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
     """mvSets as Initializer::Initialize draws them (Initializer.cpp:50-63): per iteration 8 distinct indices into
     mvMatches12, each `rand() % available` with swap-with-last removal.  `rand` is a callable returning the host's next rand()
@@ -385,6 +419,11 @@ def lib() -> ctypes.CDLL:
                                                               ctypes.POINTER(_Bounds), f32, i32, i32, vp, vp, vp]
     L.orbx_match_keyframe_projection.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32,
                                                  i32, i32, vp, vp, ctypes.POINTER(KfProjResult)]
+    L.orbx_match_triangulation_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.orbx_match_triangulation.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, f32, i32, vp,
+                                           ctypes.POINTER(TriMatchResult)]
+    L.orbx_triangulate_matches_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_triangulate_matches.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(TriResult)]
     L.orbx_database_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.orbx_database_destroy.argtypes = [vp]
     L.orbx_database_destroy.restype = None
@@ -1005,6 +1044,130 @@ class ORBextractor:
                                                    int(bool(checkOri)), _ptr(mc), _ptr(out), ctypes.byref(res))
         self._check(r, "orbx_match_keyframe_projection")
         return mc[:len(ck)].copy(), res
+
+    def _tri_pairs(self, kf1, kf2, n_frames: int):
+        kf1 = np.ascontiguousarray(kf1, np.int32).reshape(-1)
+        kf2 = np.ascontiguousarray(kf2, np.int32).reshape(-1)
+        if len(kf1) != len(kf2):
+            raise OrbxError(E_BADARG, "kf1 and kf2 must have the same length")
+        if len(kf1) and int(np.maximum(kf1.view(np.uint32), kf2.view(np.uint32)).max()) >= n_frames:
+            raise ValueError("a pair names a frame outside the batch of %d" % n_frames)
+        return kf1, kf2
+
+    def match_triangulation_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_desc, d_n, d_fv_node,
+                                         d_fv_feat, d_fv_n, d_pose, K, d_matches12, d_res, d_mask=None, d_median_depth=None,
+                                         checkOri: bool = True, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::SearchForTriangulation for pairs (new keyframe kf1[p], neighbour kf2[p]; host index arrays) of the arrays
+        extract_batch_device, undistort_batch_device and Vocabulary.transform_batch_device filled (same capacity), with the
+        keyframes' poses d_pose float32 [n_frames, 12] (Tcw: R row-major, then t) and K 3x3: d_matches12 int32 [n_pairs, capacity]
+        (row p: the kf2 feature matched to each of kf1's features, or -1), d_res [n_pairs] TRI_MATCH_RESULT_DTYPE records (76
+        bytes).  Optional: d_mask uint8 [n_frames, capacity] (!= 0 = the feature already has a map point), d_median_depth float32
+        [n_frames] (the baseline gate).  Stream-ordered on the context's stream."""
+        cap, nf = int(capacity or self.capacity), int(n_frames)
+        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
+        P = len(kf1)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
+        _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
+        _need("the FeatureVector count array", d_fv_n, nf * 4)
+        _need("the pose array", d_pose, nf * 48)
+        if d_mask is not None:
+            _need("the mask", d_mask, nf * cap)
+        if d_median_depth is not None:
+            _need("the median depth array", d_median_depth, nf * 4)
+        _need("matches12", d_matches12, P * cap * 4)
+        _need("the result array", d_res, P * TRI_MATCH_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n, d_pose, d_mask, d_median_depth, d_matches12, d_res)
+        r = self._L.orbx_match_triangulation_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n),
+                                                          cap, _ptr(d_fv_node), _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_mask), _ptr(d_pose),
+                                                          _ptr(Kf), _ptr(d_median_depth), int(bool(checkOri)), _ptr(d_matches12),
+                                                          _ptr(d_res))
+        self._check(r, "orbx_match_triangulation_batch_device")
+
+    def triangulate_matches_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_n, d_pose, K, d_matches12,
+                                         d_points, d_point_mask, d_point_normal, d_point_dist, d_res,
+                                         capacity: Optional[int] = None) -> None:
+        """The body of LocalMapping::CreateNewMapPoints behind the matcher, for the same pairs: every match of d_matches12 int32
+        [n_pairs, capacity] is triangulated and gated; row p of d_points float32 [n_pairs, capacity, 3], d_point_mask uint8
+        [n_pairs, capacity], d_point_normal float32 [n_pairs, capacity, 3] and d_point_dist float32 [n_pairs, capacity, 2]
+        (mfMinDistance, mfMaxDistance) is a point set indexed by kf1's feature, as match_keyframe_projection_pairs_device and
+        pose_optimize_batch_device read one.  d_res [n_pairs] TRI_RESULT_DTYPE records (44 bytes).  Stream-ordered."""
+        cap, nf = int(capacity or self.capacity), int(n_frames)
+        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
+        P = len(kf1)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the count array", d_n, nf * 4)
+        _need("the pose array", d_pose, nf * 48)
+        _need("matches12", d_matches12, P * cap * 4)
+        _need("the point array", d_points, P * cap * 12)
+        _need("the point mask", d_point_mask, P * cap)
+        _need("the point normal array", d_point_normal, P * cap * 12)
+        _need("the point distance array", d_point_dist, P * cap * 8)
+        _need("the result array", d_res, P * TRI_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_n, d_pose, d_matches12, d_points, d_point_mask, d_point_normal, d_point_dist, d_res)
+        r = self._L.orbx_triangulate_matches_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(d_kps_un), _ptr(d_n), cap,
+                                                          _ptr(d_pose), _ptr(Kf), _ptr(d_matches12), _ptr(d_points), _ptr(d_point_mask),
+                                                          _ptr(d_point_normal), _ptr(d_point_dist), _ptr(d_res))
+        self._check(r, "orbx_triangulate_matches_batch_device")
+
+    def create_new_map_points_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_desc, d_n, d_fv_node,
+                                           d_fv_feat, d_fv_n, d_pose, K, d_matches12, d_match_res, d_points, d_point_mask,
+                                           d_point_normal, d_point_dist, d_res, d_mask=None, d_median_depth=None, checkOri: bool = True,
+                                           capacity: Optional[int] = None) -> None:
+        """LocalMapping::CreateNewMapPoints for pairs (kf1[p], kf2[p]): match_triangulation_pairs_device, then
+        triangulate_matches_pairs_device on its rows, queued one behind the other on the context's stream with no copy and no
+        wait between them (the pair list goes up once)."""
+        self.match_triangulation_pairs_device(n_frames, kf1, kf2, d_kps_un, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n, d_pose, K,
+                                              d_matches12, d_match_res, d_mask, d_median_depth, checkOri, capacity)
+        self.triangulate_matches_pairs_device(n_frames, kf1, kf2, d_kps_un, d_n, d_pose, K, d_matches12, d_points, d_point_mask,
+                                              d_point_normal, d_point_dist, d_res, capacity)
+
+    def match_triangulation(self, keys_un1, desc1, fv_node1, fv_feat1, Tcw1, keys_un2, desc2, fv_node2, fv_feat2, Tcw2, K, mask1=None,
+                            mask2=None, median_depth2: float = 0.0, checkOri: bool = True):
+        """SearchForTriangulation for one pair in host memory (orbx_match_triangulation) -> (matches12 int32 [len(keys_un1)],
+        TriMatchResult).  Synchronous."""
+        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        n1, t1 = np.ascontiguousarray(fv_node1, np.uint32).reshape(-1), np.ascontiguousarray(fv_feat1, np.uint32).reshape(-1)
+        n2, t2 = np.ascontiguousarray(fv_node2, np.uint32).reshape(-1), np.ascontiguousarray(fv_feat2, np.uint32).reshape(-1)
+        if len(k1) != len(d1) or len(k2) != len(d2) or len(n1) != len(t1) or len(n2) != len(t2):
+            raise OrbxError(E_BADARG, "keypoints / descriptors or FeatureVector nodes / features differ in length")
+        masks = []
+        for mk, k in ((mask1, k1), (mask2, k2)):
+            m = None if mk is None else np.ascontiguousarray(np.asarray(mk) != 0, np.uint8).reshape(-1)
+            if m is not None and len(m) != len(k):
+                raise OrbxError(E_BADARG, "a mask needs one entry per feature of its keyframe")
+            masks.append(m)
+        p1, p2 = _pose12(Tcw1), _pose12(Tcw2)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        m12 = np.full(max(len(k1), 1), -1, np.int32)
+        res = TriMatchResult()
+        r = self._L.orbx_match_triangulation(self._h, _ptr(k1), _ptr(d1), len(k1), _ptr(n1), _ptr(t1), len(n1), _ptr(masks[0]), _ptr(p1),
+                                             _ptr(k2), _ptr(d2), len(k2), _ptr(n2), _ptr(t2), len(n2), _ptr(masks[1]), _ptr(p2), _ptr(Kf),
+                                             float(median_depth2), int(bool(checkOri)), _ptr(m12), ctypes.byref(res))
+        self._check(r, "orbx_match_triangulation")
+        return m12[:len(k1)].copy(), res
+
+    def triangulate_matches(self, keys_un1, Tcw1, keys_un2, Tcw2, K, matches12):
+        """CreateNewMapPoints' triangulation for one pair in host memory (orbx_triangulate_matches) -> (points [n1, 3], mask [n1],
+        normals [n1, 3], dist [n1, 2], TriResult).  Synchronous."""
+        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        m12 = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        if len(m12) != len(k1):
+            raise OrbxError(E_BADARG, "matches12 needs one entry per feature of the first keyframe")
+        n = max(len(k1), 1)
+        pts, msk, nrm, dst = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
+        p1, p2 = _pose12(Tcw1), _pose12(Tcw2)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        res = TriResult()
+        r = self._L.orbx_triangulate_matches(self._h, _ptr(k1), len(k1), _ptr(p1), _ptr(k2), len(k2), _ptr(p2), _ptr(Kf), _ptr(m12),
+                                             _ptr(pts), _ptr(msk), _ptr(nrm), _ptr(dst), ctypes.byref(res))
+        self._check(r, "orbx_triangulate_matches")
+        return pts[:len(k1)], msk[:len(k1)], nrm[:len(k1)], dst[:len(k1)], res
 
     def relocalize_refine_pairs_device(self, n_frames: int, kf: np.ndarray, cur: np.ndarray, point_set: np.ndarray, d_kps_un, d_desc,
                                        d_n, n_point_sets: int, d_points, d_point_mask, d_point_dist, d_pose0, d_matches, K,
@@ -2073,6 +2236,35 @@ class ORBmatcher:
         fn, ff = flat(F.mFeatVec)
         return ext.match_bow(KF.mvKeysUn, KF.mDescriptors, kn, kf, F.mvKeysUn, F.mDescriptors, fn, ff, mask, self.mfNNratio,
                              self.mbCheckOrientation)
+
+    def SearchForTriangulation(self, KF1: Frame, KF2: Frame, Tcw1, Tcw2, K=None, mask1=None, mask2=None, median_depth2: float = 0.0):
+        """ORB-SLAM2's SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo=False) over the keyframes' mFeatVec
+        (include/orbx.h, "growing the map") -> (nmatches, vMatchedPairs, TriMatchResult): vMatchedPairs int32 [nmatches, 2] =
+        (KF1 feature, KF2 feature) in ascending KF1 index, as ORB-SLAM2 builds it.  F12 is computed from the two poses Tcw (3x4 or
+        4x4) and K (3x3, default KF1's camera); mask1 / mask2 (optional): true = the feature already has a map point.  Both
+        keyframes' ComputeBoW must have run."""
+        ext = self._ext or KF1.mpORBextractor or KF2.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        for name, fr in (("KF1", KF1), ("KF2", KF2)):
+            if not (getattr(fr, "_bow_computed", False) or fr.mBowVec or fr.mFeatVec):
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchForTriangulation: %s has no FeatureVector; call its ComputeBoW() first" % name)
+        if K is None:
+            cam = getattr(KF1, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchForTriangulation needs K (the keyframe carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+
+        def flat(fv):
+            node = [n for n in sorted(fv) for _ in fv[n]]
+            feat = [j for n in sorted(fv) for j in fv[n]]
+            return np.asarray(node, np.uint32), np.asarray(feat, np.uint32)
+        n1, f1 = flat(KF1.mFeatVec)
+        n2, f2 = flat(KF2.mFeatVec)
+        m12, res = ext.match_triangulation(KF1.mvKeysUn, KF1.mDescriptors, n1, f1, Tcw1, KF2.mvKeysUn, KF2.mDescriptors, n2, f2, Tcw2, K,
+                                           mask1, mask2, median_depth2, self.mbCheckOrientation)
+        i = np.flatnonzero(m12 >= 0)
+        return int(res.nmatches), np.stack([i, m12[i]], axis=1).astype(np.int32), res
 
     def SearchByProjection(self, CurrentFrame: Frame, LastFrame: Frame, th: float, points, mask, Tcw, K=None, point_desc=None,
                            last_outlier=None):

@@ -183,6 +183,12 @@ struct MatchBowScratch {
   DeviceBuf<uint8_t> dKfProjIo;  // staging of orbx_match_keyframe_projection
 };
 
+// What a context keeps for orbx_match_triangulation* and orbx_triangulate_matches* (orbx_match_bow.cpp).
+struct TriScratch {
+  HeldArray<int32_t> pairs;  // the pair list [2][n_pairs] (KF1s, KF2s) of the last call of either: the chain uploads it once
+  DeviceBuf<uint8_t> dIo;    // staging of orbx_match_triangulation / orbx_triangulate_matches
+};
+
 // What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp).
 struct BaScratch {
   DeviceBuf<uint8_t> dWork;  // the per-point blocks of every pair: sized from n_pairs x capacity

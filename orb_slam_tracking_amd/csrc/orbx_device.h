@@ -523,6 +523,46 @@ struct MatchKfProjArgs {
   orbx_kfproj_result* res;    // [nPairs]
 };
 
+// ---- LocalMapping::CreateNewMapPoints (orbx_match_tri_kernel.hip): SearchForTriangulation, one workgroup of MB_THREADS per
+// (KF1, KF2) pair as k_match_bow; then the triangulation, TT_THREADS features of a pair per workgroup ----
+constexpr int TT_THREADS = 256;
+struct TriCamArgs {
+  float fx, fy, cx, cy, scaleFactor;
+  int32_t nLevels;
+  float scale[ORBX_MAX_LEVELS];   // the context's mvScaleFactor
+  float sigma2[ORBX_MAX_LEVELS];  // the context's mvLevelSigma2
+};
+struct MatchTriArgs {
+  const orbx_keypoint* kps;  // [nFrames][cap] undistorted
+  const uint8_t* desc;       // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;          // [nFrames] (clamped to [0, cap])
+  const uint32_t* fvNode;    // [nFrames][cap]
+  const uint32_t* fvFeat;    // [nFrames][cap]
+  const int32_t* fvN;        // [nFrames] (clamped to [0, cap])
+  const uint8_t* mask;       // nullable [nFrames][cap]: != 0 = the feature has a map point
+  const float* pose;         // [nFrames][12]
+  const float* medianDepth;  // nullable [nFrames]
+  const int32_t* pairs;      // [2][nPairs] KF1s, then KF2s
+  int32_t cap, nPairs, checkOri;
+  TriCamArgs cam;
+  int32_t* matches12;          // [nPairs][cap]
+  orbx_tri_match_result* res;  // [nPairs]
+};
+struct TriangulateArgs {
+  const orbx_keypoint* kps;  // [nFrames][cap] undistorted
+  const int32_t* n;          // [nFrames] (clamped to [0, cap])
+  const float* pose;         // [nFrames][12]
+  const int32_t* pairs;      // [2][nPairs] KF1s, then KF2s
+  const int32_t* matches12;  // [nPairs][cap]
+  int32_t cap, nPairs;
+  TriCamArgs cam;
+  float* points;           // [nPairs][cap][3]
+  uint8_t* pointMask;      // [nPairs][cap]
+  float* pointNormal;      // [nPairs][cap][3]
+  float* pointDist;        // [nPairs][cap][2]
+  orbx_tri_result* res;    // [nPairs], zero on entry: the workgroups of a pair add to it
+};
+
 // ---- DBoW2 TemplatedDatabase (orbx_db_kernel.hip): a CSR inverted file, batched add and query ----
 constexpr int DB_THREADS = 256;       // threads of the database kernels
 constexpr int DB_WAVES = DB_THREADS / 64;  // waves of k_db_accumulate: each owns a sub-slice of the workgroup's entries

@@ -88,6 +88,10 @@ hipError_t launch_match_kfproj(hipStream_t st, const MatchKfProjArgs& a);
 hipError_t launch_ba(hipStream_t st, const BaArgs& a);
 hipError_t launch_pose(hipStream_t st, const PoseArgs& a);
 
+// orbx_match_tri_kernel.hip
+hipError_t launch_match_tri(hipStream_t st, const MatchTriArgs& a);
+hipError_t launch_triangulate(hipStream_t st, const TriangulateArgs& a);  // (zeroes a.res first)
+
 // orbx_pnp_kernel.hip
 hipError_t launch_pnp_prep(hipStream_t st, const PnpArgs& a);
 hipError_t launch_pnp_hypotheses(hipStream_t st, const PnpArgs& a);

@@ -1,6 +1,7 @@
-// orbx_match_bow.cpp — host side of ORBmatcher::SearchByBoW (include/orbx.h, "matching through the FeatureVector"): the argument
-// checks, the pair list and the C entry points.  The kernel is in orbx_match_bow_kernel.hip.  (The matchers by projection are in
-// orbx_match_proj.cpp.)
+// orbx_match_bow.cpp — host side of the matchers that walk the FeatureVector: ORBmatcher::SearchByBoW (include/orbx.h, "matching
+// through the FeatureVector") and LocalMapping::CreateNewMapPoints ("growing the map": ORBmatcher::SearchForTriangulation and the
+// triangulation behind it): the argument checks, the pair lists and the C entry points.  The kernels are in
+// orbx_match_bow_kernel.hip and orbx_match_tri_kernel.hip.  (The matchers by projection are in orbx_match_proj.cpp.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,52 @@ bool featuresOk(const uint32_t* feat, int fvN, int n) {
   for (int i = 0; i < fvN; i++)
     if (feat[i] >= (uint32_t)n) return false;
   return true;
+}
+
+// What the four calls of CreateNewMapPoints refuse alike, all of it before the context -> ORBX_OK or the code, with the complaint
+// left in the context when there is one.
+int triRefused(orbx_ctx* ctx, const char* name, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2, int capacity,
+               const float* K) {
+  const char* why = nullptr;
+  if (!pairsInRange(h_kf1, h_kf2, n_pairs, n_frames)) why = "pair index outside [0, n_frames)";
+  else if (!std::isfinite(K[0]) || !std::isfinite(K[4]) || !std::isfinite(K[2]) || !std::isfinite(K[5]) || !(K[0] > 0.0f) || !(K[4] > 0.0f))
+    why = "K is not finite or has no positive focal lengths";
+  const bool over = capacity > ORBX_BOW_MAX_FEATURES;
+  if (!why && !over) return ORBX_OK;
+  if (ctx) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", name, why ? why : "capacity above ORBX_BOW_MAX_FEATURES");
+    ctxSetError(ctx, msg);
+  }
+  return why ? ORBX_E_BADARG : ORBX_E_CAPACITY;
+}
+
+// the camera K[9] (row-major) and the context's pyramid tables as the two kernels take them
+TriCamArgs triCam(const orbx_ctx* ctx, const float* K) {
+  TriCamArgs c{};
+  c.fx = K[0];
+  c.fy = K[4];
+  c.cx = K[2];
+  c.cy = K[5];
+  c.scaleFactor = orbx_get_scale_factor(ctx);
+  int nl = 0;
+  const float* scale = ctxScale(ctx, &c.nLevels);
+  const float* sigma2 = ctxSigma2(ctx, &nl);
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
+    c.scale[l] = l < c.nLevels ? scale[l] : 0.0f;
+    c.sigma2[l] = l < nl ? sigma2[l] : 0.0f;
+  }
+  return c;
+}
+
+// the pair list [2][n_pairs] of the two calls, which take the same one: uploaded only when it differs from the last call's.  Such a
+// call first waits for the context stream -- the host copy an earlier upload may still be reading is replaced
+int triPairs(orbx_ctx* ctx, hipStream_t st, TriScratch* s, const int32_t* h_kf1, const int32_t* h_kf2, int n_pairs) {
+  if (!s->pairs.holds(h_kf1, n_pairs, h_kf2, n_pairs)) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(s->pairs.replace(st, h_kf1, n_pairs, h_kf2, n_pairs));
+  }
+  return ORBX_OK;
 }
 
 }  // namespace
@@ -126,6 +173,211 @@ int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf
   if (r != ORBX_OK) return r;
   HIPCHK(down(matches_f, dM, f_n, st));
   HIPCHK(down(nmatches, dN + 4, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+int orbx_match_triangulation_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                          const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                          const uint32_t* d_fv_node, const uint32_t* d_fv_feat, const int32_t* d_fv_n,
+                                          const uint8_t* d_mask, const float* d_pose, const float* K, const float* d_median_depth,
+                                          int check_orientation, int32_t* d_matches12, orbx_tri_match_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || capacity < 1 || (n_pairs > 0 && (!h_kf1 || !h_kf2)) || !d_kps_un || !d_desc32 || !d_n ||
+      !d_fv_node || !d_fv_feat || !d_fv_n || !d_pose || !K || !d_matches12 || !d_res)
+    return ORBX_E_BADARG;
+  int r = triRefused(ctx, "match triangulation", n_frames, n_pairs, h_kf1, h_kf2, capacity, K);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  TriScratch* s = ctxTri(ctx);
+  hipStream_t st = ctxStream(ctx);
+  r = triPairs(ctx, st, s, h_kf1, h_kf2, n_pairs);
+  if (r != ORBX_OK) return r;
+  MatchTriArgs a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.fvNode = d_fv_node;
+  a.fvFeat = d_fv_feat;
+  a.fvN = d_fv_n;
+  a.mask = d_mask;
+  a.pose = d_pose;
+  a.medianDepth = d_median_depth;
+  a.pairs = s->pairs;
+  a.cap = capacity;
+  a.nPairs = n_pairs;
+  a.checkOri = check_orientation != 0;
+  a.cam = triCam(ctx, K);
+  a.matches12 = d_matches12;
+  a.res = d_res;
+  HIPCHK(launch_match_tri(st, a));
+  return ORBX_OK;
+}
+
+int orbx_triangulate_matches_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                          const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const float* d_pose,
+                                          const float* K, const int32_t* d_matches12, float* d_points, uint8_t* d_point_mask,
+                                          float* d_point_normal, float* d_point_dist, orbx_tri_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || capacity < 1 || (n_pairs > 0 && (!h_kf1 || !h_kf2)) || !d_kps_un || !d_n || !d_pose || !K ||
+      !d_matches12 || !d_points || !d_point_mask || !d_point_normal || !d_point_dist || !d_res)
+    return ORBX_E_BADARG;
+  int r = triRefused(ctx, "triangulate matches", n_frames, n_pairs, h_kf1, h_kf2, capacity, K);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  TriScratch* s = ctxTri(ctx);
+  hipStream_t st = ctxStream(ctx);
+  r = triPairs(ctx, st, s, h_kf1, h_kf2, n_pairs);
+  if (r != ORBX_OK) return r;
+  TriangulateArgs a{};
+  a.kps = d_kps_un;
+  a.n = d_n;
+  a.pose = d_pose;
+  a.pairs = s->pairs;
+  a.matches12 = d_matches12;
+  a.cap = capacity;
+  a.nPairs = n_pairs;
+  a.cam = triCam(ctx, K);
+  a.points = d_points;
+  a.pointMask = d_point_mask;
+  a.pointNormal = d_point_normal;
+  a.pointDist = d_point_dist;
+  a.res = d_res;
+  HIPCHK(launch_triangulate(st, a));
+  return ORBX_OK;
+}
+
+int orbx_match_triangulation(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* desc1, int n1, const uint32_t* fv_node1,
+                             const uint32_t* fv_feat1, int fv_n1, const uint8_t* mask1, const float* pose1,
+                             const orbx_keypoint* kps_un2, const uint8_t* desc2, int n2, const uint32_t* fv_node2,
+                             const uint32_t* fv_feat2, int fv_n2, const uint8_t* mask2, const float* pose2, const float* K,
+                             float median_depth2, int check_orientation, int32_t* matches12, orbx_tri_match_result* res) {
+  if (n1 < 0 || n2 < 0 || fv_n1 < 0 || fv_n2 < 0 || !pose1 || !pose2 || !K || !res || (n1 > 0 && (!kps_un1 || !desc1 || !matches12)) ||
+      (n2 > 0 && (!kps_un2 || !desc2)) || (fv_n1 > 0 && (!fv_node1 || !fv_feat1)) || (fv_n2 > 0 && (!fv_node2 || !fv_feat2)))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(std::max(n1, n2), std::max(fv_n1, fv_n2)), 1);
+  const int32_t kf1 = 0, kf2 = 1;
+  int r = triRefused(ctx, "match triangulation", 2, 1, &kf1, &kf2, cap, K);
+  if (r != ORBX_OK) return r;
+  if (!featuresOk(fv_feat1, fv_n1, n1) || !featuresOk(fv_feat2, fv_n2, n2)) {
+    if (ctx) ctxSetError(ctx, "match triangulation: a FeatureVector names a feature the keyframe does not have");
+    return ORBX_E_BADARG;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  TriScratch* s = ctxTri(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t *dD, *dMask;
+  uint32_t *dNode, *dFeat;
+  float *dPose, *dMed;
+  int32_t *dN, *dM;
+  orbx_tri_match_result* dR;
+  auto staging = [&](Layout L) {  // the two keyframes (KF1 0, KF2 1) in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dD = L.take<uint8_t>((size_t)2 * cap * 32);
+    dNode = L.take<uint32_t>((size_t)2 * cap);
+    dFeat = L.take<uint32_t>((size_t)2 * cap);
+    dMask = L.take<uint8_t>((size_t)2 * cap);
+    dPose = L.take<float>(24);
+    dMed = L.take<float>(2);
+    dN = L.take<int32_t>(4);  // n[2], fv_n[2]
+    dM = L.take<int32_t>(cap);
+    dR = L.take<orbx_tri_match_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dIo.grow(bytes, st));
+  staging(Layout(s->dIo));
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));  // (the mask of a keyframe that brings none)
+  const size_t c = (size_t)cap;
+  HIPCHK(up(dK, kps_un1, n1, st));
+  HIPCHK(up(dD, desc1, (size_t)n1 * 32, st));
+  HIPCHK(up(dK + c, kps_un2, n2, st));
+  HIPCHK(up(dD + c * 32, desc2, (size_t)n2 * 32, st));
+  HIPCHK(up(dNode, fv_node1, fv_n1, st));
+  HIPCHK(up(dFeat, fv_feat1, fv_n1, st));
+  HIPCHK(up(dNode + c, fv_node2, fv_n2, st));
+  HIPCHK(up(dFeat + c, fv_feat2, fv_n2, st));
+  if (mask1) HIPCHK(up(dMask, mask1, n1, st));
+  if (mask2) HIPCHK(up(dMask + c, mask2, n2, st));
+  HIPCHK(up(dPose, pose1, 12, st));
+  HIPCHK(up(dPose + 12, pose2, 12, st));
+  const bool gate = median_depth2 > 0.0f;
+  const float hMed[2] = {0.0f, median_depth2};
+  if (gate) HIPCHK(up(dMed, hMed, 2, st));
+  const int32_t hn[4] = {n1, n2, fv_n1, fv_n2};
+  HIPCHK(up(dN, hn, 4, st));
+  r = orbx_match_triangulation_batch_device(ctx, 2, 1, &kf1, &kf2, dK, dD, dN, cap, dNode, dFeat, dN + 2,
+                                            mask1 || mask2 ? dMask : nullptr, dPose, K, gate ? dMed : nullptr, check_orientation, dM, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(matches12, dM, n1, st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* pose1, const orbx_keypoint* kps_un2,
+                             int n2, const float* pose2, const float* K, const int32_t* matches12, float* points, uint8_t* point_mask,
+                             float* point_normal, float* point_dist, orbx_tri_result* res) {
+  if (n1 < 0 || n2 < 0 || !pose1 || !pose2 || !K || !res ||
+      (n1 > 0 && (!kps_un1 || !matches12 || !points || !point_mask || !point_normal || !point_dist)) || (n2 > 0 && !kps_un2))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(n1, n2), 1);
+  const int32_t kf1 = 0, kf2 = 1;
+  int r = triRefused(ctx, "triangulate matches", 2, 1, &kf1, &kf2, cap, K);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  TriScratch* s = ctxTri(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t* dMask;
+  float *dPose, *dP, *dNrm, *dDist;
+  int32_t *dN, *dM;
+  orbx_tri_result* dR;
+  auto staging = [&](Layout L) {  // the two keyframes in the batch layout, the matches, then the point set and the record
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dPose = L.take<float>(24);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dP = L.take<float>((size_t)cap * 3);
+    dMask = L.take<uint8_t>(cap);
+    dNrm = L.take<float>((size_t)cap * 3);
+    dDist = L.take<float>((size_t)cap * 2);
+    dR = L.take<orbx_tri_result>(1);
+    return L.size();
+  };
+  HIPCHK(s->dIo.grow(staging(Layout()), st));
+  staging(Layout(s->dIo));
+  const size_t c = (size_t)cap;
+  HIPCHK(hipMemsetAsync(dM, 0xff, c * sizeof(int32_t), st));  // (entries at and beyond n1: no match)
+  HIPCHK(up(dK, kps_un1, n1, st));
+  HIPCHK(up(dK + c, kps_un2, n2, st));
+  HIPCHK(up(dPose, pose1, 12, st));
+  HIPCHK(up(dPose + 12, pose2, 12, st));
+  HIPCHK(up(dM, matches12, n1, st));
+  const int32_t hn[2] = {n1, n2};
+  HIPCHK(up(dN, hn, 2, st));
+  r = orbx_triangulate_matches_batch_device(ctx, 2, 1, &kf1, &kf2, dK, dN, cap, dPose, K, dM, dP, dMask, dNrm, dDist, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);
+    return r;
+  }
+  HIPCHK(down(points, dP, (size_t)n1 * 3, st));
+  HIPCHK(down(point_mask, dMask, n1, st));
+  HIPCHK(down(point_normal, dNrm, (size_t)n1 * 3, st));
+  HIPCHK(down(point_dist, dDist, (size_t)n1 * 2, st));
+  HIPCHK(down(res, dR, 1, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }

@@ -9,30 +9,13 @@
 
 #include "orbx_launch.h"
 #include "orbx_match_hist.h"
+#include "orbx_match_node.h"
 
 namespace orbx {
 namespace {
 
 constexpr uint32_t MB_NONE = (256u << 16) | 0xffffu;  // distance 256 (best1 = best2 = 256 at the start), no position
 constexpr int MB_TAKEN_WORDS = BOW_MAX_FEATURES / 32;  // a node holds at most a whole frame
-
-__device__ __forceinline__ int mbClamp(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-
-// first index in [lo, hi) whose node is >= (upper == false) or > (upper == true) `node`; any content keeps it inside [lo, hi]
-__device__ __forceinline__ int mbBound(const uint32_t* __restrict__ nodes, int lo, int hi, uint32_t node, bool upper) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    const uint32_t v = nodes[mid];
-    if (upper ? v <= node : v < node) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int mbDistance(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-         __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // One node by one wave: the keyframe's FeatureVector entries [a0, a1) against the frame's [b0, b1).  A frame feature is named
 // by its position p in [0, nb): positions ascend with the feature index, so the smallest (distance, position) is the lowest
