@@ -748,6 +748,128 @@ int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const floa
                    const float* sigma2, double probability, int min_inliers, int max_iterations, float epsilon, float th2, int n_iter,
                    const int32_t* draws, orbx_pnp_result* res, uint8_t* inliers);
 
+/* ---- loop closing: Sim3 RANSAC (Sim3Solver: Horn's closed-form similarity inside RANSAC, what LoopClosing::ComputeSim3 calls) ----
+ * A loop candidate found by the database and matched by SearchByBoW gives 3D-3D correspondences between the map points of the
+ * current keyframe (KF1) and of the candidate (KF2).  ORB-SLAM2's Sim3Solver finds the similarity T12 = [s12 R12 | t12] between
+ * the two camera frames by RANSAC, each hypothesis Horn's 1987 closed form on three correspondences.  The reference tree ships
+ * no Sim3Solver: the rules below restate ORB-SLAM2's Sim3Solver.cc [from-knowledge], PARITY UNPINNED, as the PnP section above.
+ * The device equals the CPU restatement tests/cpp/sim3_ref.cpp bit for bit.  (The guided matcher ORBmatcher::SearchBySim3 that
+ * follows it in ComputeSim3 is the section "loop closing: matching under a similarity" below and reads the row and the similarity
+ * written here as they are; OptimizeSim3 is not offered yet.)
+ *
+ * Rules.
+ *  1. Constructor.  For feature i1 of KF1 in ascending i1: a correspondence exists when i2 = d_match[p][i1] >= 0 and the point
+ *     mask of KF1's set at i1 and of KF2's set at i2 are set (no mask: every entry is a point).  mvX3Dc1 = Rcw1 * X1w + tcw1 and
+ *     mvX3Dc2 = Rcw2 * X2w + tcw2 in f32, each row's products added left to right, then the translation.  mvnMaxError1 = th2 *
+ *     sigma2[octave(kp1[i1])], mvnMaxError2 = th2 * sigma2[octave(kp2[i2])] (f32).  mvP1im1 / mvP2im2 = FromCameraToImage of
+ *     mvX3Dc1 / mvX3Dc2: invz = 1.0f / z, (fx * (x * invz) + cx, fy * (y * invz) + cy), f32, no sign test on z.  mvnIndices1 =
+ *     i1.  N = their number (n_correspondences).
+ *  2. SetRansacParameters(probability, minInliers, maxIterations) (LoopClosing passes 0.99, 20, 300): epsilon = (float)minInliers
+ *     / N (f32); nIterations = 1 when minInliers == N, else (int)ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in f64;
+ *     mRansacMaxIts = max(1, min(nIterations, maxIterations)).  minInliers is NOT raised with N (PnPsolver raises its own).  N is
+ *     known only on the device and the device has no libm that equals the host's, so the host computes the table N ->
+ *     mRansacMaxIts for N in [0, capacity] with these expression types (orbx_sim3_ransac_table) and uploads it.
+ *  3. Sampling.  d_draws int32 [n_problems][n_iter][3] holds the values rand() returned; the three draws of a hypothesis go
+ *     through PnP's rule 3 (RandomInt on the available list, swap-and-pop), the same code on three draws.  A negative draw skips
+ *     the hypothesis (it counts no inlier and is never kept) and sets ORBX_SIM3_BAD_DRAWS.
+ *  4. ComputeSim3 (Horn 1987) on the triple's mvX3Dc1 (P1) and mvX3Dc2 (P2): the centroids O1, O2 and the relative coordinates
+ *     Pr1, Pr2; M = Pr2 * Pr1^T; the symmetric traceless 4x4 N with N11 = M00+M11+M22, N12 = M12-M21, N13 = M20-M02, N14 =
+ *     M01-M10, N22 = M00-M11-M22, N23 = M01+M10, N24 = M20+M02, N33 = -M00+M11-M22, N34 = M12+M21, N44 = -M00-M11+M22; the
+ *     quaternion (w, x, y, z) = the eigenvector of N's largest signed eigenvalue, and R12 from it; P3 = R12 * Pr2; s12 =
+ *     dot(Pr1, P3) / sum(P3 .* P3), or 1 with fix_scale; t12 = O1 - s12 * R12 * O2.  T12 = [s12 R12 | t12], T21 = [(1 / s12)
+ *     R12^T | -(1 / s12) R12^T t12].
+ *  5. CheckInliers, f32: vP2im1 = mvX3Dc2 through T12 and K, vP1im2 = mvX3Dc1 through T21 and K (each row's products added left
+ *     to right, then the translation; the projection of rule 1); err1 = |mvP1im1 - vP2im1|^2, err2 = |vP1im2 - mvP2im2|^2 (dx *
+ *     dx + dy * dy); a correspondence is an inlier when err1 < mvnMaxError1 && err2 < mvnMaxError2, both strict.  A hypothesis
+ *     with a non-finite entry in s12, R12, t12, T12 or T21 counts no inlier (n_degenerate) and is never kept.
+ *  6. iterate.  N < minInliers is bNoMore at once (ORBX_SIM3_FEW_POINTS).  Otherwise, in iteration order with mnBestInliers = 0
+ *     at the start, a hypothesis becomes the best when its inliers >= mnBestInliers -- non-strict: of equals the LAST wins,
+ *     unlike PnPsolver -- and a hypothesis that becomes the best with inliers > minInliers (strict) ends the solver and is the
+ *     result (found_it).  Otherwise all min(n_iter, mRansacMaxIts) iterations run and there is no result
+ *     (ORBX_SIM3_NO_RESULT).  There is no Refine.
+ *
+ * Documented deviations:
+ *  1. Horn's algebra (rule 4) runs in f64 from the f32 camera-frame points, where the reference keeps f32 cv::Mat: centroids
+ *     p0 + ((p1 - p0) + (p2 - p0)) / 3.0 (three coincident points then give Pr = 0 and s12 = 0 / 0 exactly); M[i][j] summed over the triple's points in the order drawn; nom and den summed over the
+ *     coordinate (outer) and the point (inner).  s12, R12 and t12 are then rounded to f32 -- these are the values returned --
+ *     and rule 5's matrices are made from the rounded values: s12 * R12 an f32 product; (1.0 / s12) in f64, times R12^T, rounded
+ *     to f32; t21 = -(row . t12) in f32.
+ *  2. cv::eigen is a cyclic two-sided Jacobi on the symmetric 4x4 with 12 fixed sweeps over (0,1) (0,2) (0,3) (1,2) (1,3)
+ *     (2,3) and no convergence test (as PnP's deviation 1); the eigenvector is the column of the largest SIGNED eigenvalue, of
+ *     equal values the lowest column.  (N is indefinite: for degenerate triples |lambda_min| can exceed lambda_max, which is why
+ *     the one-sided routine of orbx_svd4.inc, ordered by singular value, is not used.)
+ *  3. R12 comes from the normalised quaternion directly; the reference's atan2 + Rodrigues round trip gives the same rotation
+ *     but divides 0 / 0 for the identity.
+ *  4. Map points are arrays plus a mask, indexed by their keyframe's feature.
+ *  5. iterate is resolved after the fact: all hypotheses are computed, then rule 6 is applied in iteration order; the answer
+ *     equals the sequential loop's (tests/cpp/sim3_ref.cpp holds both; DESIGN.md 4n has the argument).
+ *  6. One call is a solver's whole life, as PnP's deviation 6: found_it tells which iterate(5) turn would have returned it.
+ *  7. Garbage is flagged and never followed: a keyframe count outside [0, capacity], a match index >= KF2's count, an octave
+ *     outside the table on either feature of a correspondence (ORBX_SIM3_BAD_INPUT); a non-finite pose, or a non-finite point
+ *     or keypoint of a correspondence (ORBX_SIM3_NONFINITE).  A problem that ends without a result (these,
+ *     ORBX_SIM3_FEW_POINTS, or no hypothesis above minInliers) carries ORBX_SIM3_NO_RESULT, zeros for s12, R12, t12 and d_sim3,
+ *     and an all -1 row. */
+#define ORBX_SIM3_BAD_INPUT 2   /* a count outside [0, capacity], a match index >= KF2's count, an octave outside [0, nlevels) */
+#define ORBX_SIM3_NONFINITE 4   /* a non-finite pose, point or keypoint */
+#define ORBX_SIM3_FEW_POINTS 8  /* N < minInliers: bNoMore at once */
+#define ORBX_SIM3_BAD_DRAWS 16  /* a negative draw among the iterations that ran */
+#define ORBX_SIM3_NO_RESULT 32  /* no similarity is returned */
+typedef struct orbx_sim3_result {
+  int32_t status;            /* 0, or a bitmask of ORBX_SIM3_*; every field is written for every problem */
+  int32_t n_correspondences; /* N (0 with BAD_INPUT / NONFINITE) */
+  int32_t max_its;           /* mRansacMaxIts of N */
+  int32_t its_run;           /* found_it + 1, or min(n_iter, max_its); 0 when nothing ran */
+  int32_t found_it;          /* the iteration that ended the solver, or -1 */
+  int32_t best_it;           /* the iteration of the best hypothesis when the solver stopped, or -1 */
+  int32_t n_inliers;         /* of the returned similarity (0 without one) */
+  int32_t n_best_inliers;    /* mnBestInliers when the solver stopped */
+  int32_t n_degenerate;      /* non-finite hypotheses among the iterations that ran */
+  int32_t reserved[2];
+  float s12, R12[9], t12[3]; /* the returned similarity (R12 row-major), zeros without one */
+} orbx_sim3_result;
+
+/* The table of rule 2: out int32 [n_max + 1] = mRansacMaxIts for N = 0 .. n_max.  Host only.  For N < min_inliers the design
+ * takes the logarithm of a negative number (and divides by N = 0): those entries get max_iterations; such a solver is bNoMore
+ * before it iterates.  ORBX_E_BADARG for the parameter ranges below, n_max < 0 or NULL. */
+int orbx_sim3_ransac_table(double probability, int min_inliers, int max_iterations, int n_max, int32_t* out);
+
+/* Batched, device-resident, stream-ordered on the context stream.  Problem p: KF1 = h_kf1[p] (the current keyframe), KF2 =
+ * h_kf2[p] (the candidate), their point sets h_set1[p] and h_set2[p] (d_points float [n_point_sets][capacity][3], d_point_mask
+ * uint8 [n_point_sets][capacity] or NULL, each indexed by its own keyframe's feature); a keyframe or a set may be in any number
+ * of problems, on either side.  d_kps_un / d_n: the frames as the extract and undistort calls leave them.  d_match int32
+ * [n_problems][capacity]: the feature of KF2 matched to feature i1 of KF1, or -1 (orbx_match_bow_batch_device's d_matches_f
+ * with KF1 on the frame side).  d_pose float [n_frames][12]: Tcw per frame, R row-major, then t.  K row-major 3x3 (host, f32);
+ * sigma2: host, the context's nlevels floats, NULL = the context's own; fix_scale: 0 (monocular) or 1; probability in (0, 1),
+ * min_inliers >= 3, max_iterations >= 1, th2 > 0 (ORB-SLAM2's 9.210); d_draws int32 [n_problems][n_iter][3], n_iter >= 1.
+ * Outputs: d_res [n_problems]; d_sim3 float [n_problems][13]: R12 row-major, t12, s12; d_match_inliers int32
+ * [n_problems][capacity]: d_match[p][i1] where i1 is an inlier of the result and -1 elsewhere (every entry is written), the row
+ * LoopClosing builds from vbInliers; d_inliers uint8 [n_problems][capacity] (NULL = not wanted).  Three launches: k_sim3_prep (a
+ * wave per problem), k_sim3_hypotheses (a lane per problem and iteration), k_sim3_resolve (a wave per problem).  The call
+ * returns once queued, with the PnP call's exception: when the lists, sigma2 or the parameters' table differ from the previous
+ * call's on this context, or the workspace grows, it first waits for the context stream.  The workspace is sized from the
+ * capacity, not from the counts, which only the device knows: n_problems * capacity * 60 bytes of correspondence records plus
+ * n_problems * n_iter * 64 bytes of hypotheses, kept by the context and grown on demand (38 MB at 640 problems of capacity 1000
+ * and 300 iterations; 640 problems at capacity 16384 would take 630 MB: batch sparse keyframes at the capacity they need).
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, n_iter < 1, a parameter outside its range, fix_scale
+ * not 0 or 1, a keyframe index outside [0, n_frames), a point set outside [0, n_point_sets); ORBX_E_CAPACITY: capacity >
+ * ORBX_BOW_MAX_FEATURES, or n_problems * n_iter > 2^31 - 64 (a lane per hypothesis); ORBX_E_HIP: ctx == NULL with otherwise
+ * well-formed arguments -- all checked before anything touches a device.  n_problems == 0 is ORBX_OK. */
+int orbx_sim3_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_kf1, const int32_t* h_kf2,
+                                 const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const int32_t* d_n,
+                                 int capacity, const int32_t* d_match, int n_point_sets, const float* d_points,
+                                 const uint8_t* d_point_mask, const float* d_pose, const float* K, const float* sigma2, int fix_scale,
+                                 double probability, int min_inliers, int max_iterations, float th2, int n_iter,
+                                 const int32_t* d_draws, orbx_sim3_result* d_res, float* d_sim3, int32_t* d_match_inliers,
+                                 uint8_t* d_inliers);
+/* The same for one problem in host memory: KF1 (n1 features, points1 [n1][3], mask1 [n1] nullable, pose1 [12]), then KF2;
+ * match12 [n1]; draws [n_iter][3]; sim3 [13]; match_inliers [n1]; inliers [n1] nullable.  mask1 and mask2 are given together
+ * or not at all.  Run through the batched path as a batch of one.  Synchronous. */
+int orbx_sim3_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* points1, const uint8_t* mask1,
+                    const float* pose1, const orbx_keypoint* kps_un2, int n2, const float* points2, const uint8_t* mask2,
+                    const float* pose2, const int32_t* match12, const float* K, const float* sigma2, int fix_scale,
+                    double probability, int min_inliers, int max_iterations, float th2, int n_iter, const int32_t* draws,
+                    orbx_sim3_result* res, float* sim3, int32_t* match_inliers, uint8_t* inliers);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)
@@ -1322,6 +1444,82 @@ int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un
                                    const uint8_t* mask, const uint8_t* point_desc32, const float* point_dist, const float* pose,
                                    const float* K, const orbx_bounds* bounds, float th, int orb_dist, int check_orientation,
                                    int32_t* matches, const uint8_t* outlier, orbx_kfproj_result* res);
+
+/* ---- loop closing: matching under a similarity (ORBmatcher::SearchBySim3) ------------------------------------------------------
+ * Behind Sim3Solver ("loop closing: Sim3 RANSAC") LoopClosing::ComputeSim3 widens the inlier set: ORBmatcher::SearchBySim3(pKF1,
+ * pKF2, vpMatches12, s12, R12, t12, th = 7.5) projects KF1's unmatched map points into KF2 under T21 and KF2's into KF1 under
+ * T12, picks the nearest descriptor in a window each way, and keeps a pair where both directions agree.  The reference tree ships
+ * no SearchBySim3: the rules restate ORB-SLAM2's ORBmatcher.cc [from-knowledge], PARITY UNPINNED.  The device equals the CPU
+ * restatement in tests/cpp/sim3_ref.cpp byte for byte.
+ *
+ * Rules.
+ *  1. vbAlreadyMatched1[i1] = row[i1] >= 0; vbAlreadyMatched2[row[i1]] = true when that index is below KF2's count.
+ *  2. Direction 1 -> 2.  For every feature i1 of KF1 whose point mask is set (no mask: every feature) and that is not already
+ *     matched: p3Dc1 = R1w * X + t1w; p3Dc2 = sR21 * p3Dc1 + t21 with sR21 = (1 / s12) * R12^T and t21 = -sR21 * t12.  Skip when
+ *     z < 0 (z == 0 goes on and fails the next test).  invz = 1 / z, u = fx * (x * invz) + cx, v = fy * (y * invz) + cy; skip
+ *     unless IsInImage: u >= min_x, u < max_x, v >= min_y, v < max_y.  dist3D = |p3Dc2|; skip when dist3D < 0.8f * min or >
+ *     1.2f * max of the point's d_point_dist.  level = PredictScale in the table form of the local-map matcher (the number of
+ *     scale factors below max / dist3D, among the first nlevels - 1); radius = th * scaleFactor[level].
+ *     KeyFrame::GetFeaturesInArea(u, v, radius) in KF2 -- the pinned Frame::GetFeaturesInArea without level bounds; the
+ *     arithmetic is the same -- then the candidates with octave in [level - 1, level]; the first with the smallest descriptor
+ *     distance wins (dist < bestDist from INT_MAX: a distance of 256 can win); when bestDist <= orb_dist, vnMatch1[i1] = bestIdx.
+ *     No "taken" rule, no ratio test, no orientation histogram.
+ *  3. Direction 2 -> 1: the mirror image over KF2's points that are not already matched, with sR12 = s12 * R12 and t12,
+ *     searching KF1; it gives vnMatch2.
+ *  4. Agreement, i1 ascending: when vnMatch1[i1] = i2 >= 0 and vnMatch2[i2] == i1, row[i1] = i2 and it counts in n_found.
+ *     Entries already >= 0 are never changed.
+ * Expression types: f32 as the reference's cv::Mat, every three-term row sum ((a + b) + c) + t; sR12 an f32 product; 1.0 / s12
+ * taken in f64, times R12^T, rounded to f32; t21's sum in f32; dist3D the f32 of an f64 square root of f64 squares.
+ *
+ * Documented deviations: (1) PredictScale is the table walk, not ceil(log(ratio) / log(scaleFactor)); (2) map points are arrays
+ * plus a mask, indexed by their keyframe's feature (GetIndexInKeyFrame is the identity), their descriptors d_point_desc32 or,
+ * without it, the feature's own; (3) orb_dist in [0, 256]; (4) n_with_candidates counts points with a candidate inside the
+ * octave window (the reference tests the unfiltered list, which changes no match); (5) garbage is flagged and dropped: a count
+ * outside [0, capacity] (clamped) or an entry of the row >= KF2's count (ORBX_MSIM3_BAD_INPUT: the entry stays and is followed
+ * nowhere); a non-finite point, distance or ratio (ORBX_MSIM3_NONFINITE: the point is dropped); a non-finite pose or
+ * similarity, or s12 <= 0: ORBX_MSIM3_NONFINITE, every point is dropped and the row stays as it came. */
+#define ORBX_MSIM3_BAD_INPUT 2 /* a count outside its capacity, an entry of d_matches beyond KF2's count */
+#define ORBX_MSIM3_NONFINITE 4 /* a non-finite pose, similarity (or s12 <= 0), point, distance or ratio */
+typedef struct orbx_msim3_result {
+  int32_t status;             /* 0, or a bitmask of ORBX_MSIM3_*; every field is written for every pair */
+  int32_t n_found;            /* nFound: entries rule 4 wrote */
+  int32_t n_points_12;        /* direction 1 -> 2: points searched for (mask set, not already matched) */
+  int32_t n_behind_12;        /* ... z < 0 */
+  int32_t n_out_image_12;     /* ... not IsInImage */
+  int32_t n_out_distance_12;
+  int32_t n_with_candidates_12;
+  int32_t n_over_dist_12;     /* ... bestDist above orb_dist */
+  int32_t n_points_21, n_behind_21, n_out_image_21, n_out_distance_21, n_with_candidates_21, n_over_dist_21; /* direction 2 -> 1 */
+  int32_t n_one_sided;        /* vnMatch1 picks that vnMatch2 does not return */
+  int32_t reserved;
+} orbx_msim3_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  Pair p: KF1 = h_kf1[p], KF2 = h_kf2[p], their point sets
+ * h_set1[p], h_set2[p] (d_points float [n_point_sets][capacity][3], d_point_mask uint8 or NULL, d_point_desc32 uint8
+ * [n_point_sets][capacity][32] 16-byte aligned or NULL, d_point_dist float [n_point_sets][capacity][2] = mfMinDistance,
+ * mfMaxDistance: the kernel applies 0.8f and 1.2f), each indexed by its own keyframe's feature.  d_pose float [n_frames][12]
+ * (Tcw per frame) and d_sim3 float [n_pairs][13] (R12, t12, s12) as orbx_sim3_solve_batch_device takes and writes them.  K
+ * row-major 3x3 (host, f32), bounds = the keyframes' image bounds, th > 0 (LoopClosing passes 7.5), orb_dist in [0, 256]
+ * (TH_HIGH = 100).  d_matches int32 [n_pairs][capacity], in and out: the solver's d_match_inliers.  d_res [n_pairs].  One
+ * workgroup per pair, one launch; dynamic LDS sized from the capacity (110.0 KB at ORBX_BOW_MAX_FEATURES).  The call returns once
+ * queued, except that a pair list that differs from the previous call's first waits for the context stream.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, th not positive, orb_dist outside [0, 256], bounds with
+ * max <= min, an index outside its range; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with
+ * otherwise well-formed arguments -- all checked before anything touches a device.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                 const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                 const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                 const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const float* d_point_dist,
+                                 const float* d_pose, const float* d_sim3, const float* K, const orbx_bounds* bounds, float th,
+                                 int orb_dist, int32_t* d_matches, orbx_msim3_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: KF1 (n1 features; points1, point_dist1 per
+ * feature; mask1, point_desc1 nullable; pose1 [12]), then KF2; the masks are given together or not at all, and so are the point
+ * descriptors; sim3 [13]; matches12 [n1] in and out.  Synchronous. */
+int orbx_match_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* desc1, int n1, const float* points1,
+                    const uint8_t* mask1, const uint8_t* point_desc1, const float* point_dist1, const float* pose1,
+                    const orbx_keypoint* kps_un2, const uint8_t* desc2, int n2, const float* points2, const uint8_t* mask2,
+                    const uint8_t* point_desc2, const float* point_dist2, const float* pose2, const float* sim3, const float* K,
+                    const orbx_bounds* bounds, float th, int orb_dist, int32_t* matches12, orbx_msim3_result* res);
 
 /* ---- growing the map: LocalMapping::CreateNewMapPoints ---------------------------------------------------------------------------
  * The one step that makes map points after the Initializer's first pair: a new keyframe KF1 is matched against a covisible

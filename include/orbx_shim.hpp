@@ -465,6 +465,34 @@ class ORBmatcher {
     return searchForTriangulation(ext_, KF1, KF2, K, vMatchedPairs, medianDepth2, result);
   }
 
+  // ORB-SLAM2's SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (orbx.h, "loop closing: matching under a similarity"),
+  // what LoopClosing::ComputeSim3 runs behind Sim3Solver.  The keyframes as KeyFrameViews with their map points (mWorldPos,
+  // mfMinMaxDistance, mbGood, mPointDescriptors: given for both keyframes or for neither) and poses (mTcw); vpMatches12 holds
+  // KF2's feature per feature of KF1, or -1 (GetIndexInKeyFrame taken as the identity), and is widened in place; R12 [9]
+  // row-major, t12 [3]; K [9] and the keyframes' image bounds.  Returns nFound.  Needs the extractor given to the constructor or
+  // setExtractor.
+  int SearchBySim3(const KeyFrameView& KF1, const KeyFrameView& KF2, std::vector<int>& vpMatches12, const float& s12, const float* R12,
+                   const float* t12, const float th, const float* K, const orbx_bounds& bounds, orbx_msim3_result* result = nullptr) {
+    if (!ext_) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): none was set");
+    if (!KF1.mTcw || !KF2.mTcw) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchBySim3: a keyframe has no pose (mTcw)");
+    if (vpMatches12.size() != (size_t)KF1.N) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher::SearchBySim3: vpMatches12 needs KF1.N entries");
+    float sim[13];
+    for (int k = 0; k < 9; k++) sim[k] = R12[k];
+    for (int k = 0; k < 3; k++) sim[9 + k] = t12[k];
+    sim[12] = s12;
+    std::vector<int32_t> row(vpMatches12.begin(), vpMatches12.end());
+    if (row.empty()) row.push_back(-1);
+    orbx_msim3_result res;
+    const int r = orbx_match_sim3(ext_->context(), reinterpret_cast<const orbx_keypoint*>(KF1.mvKeysUn), KF1.mDescriptors, KF1.N,
+                                  KF1.mWorldPos, KF1.mbGood, KF1.mPointDescriptors, KF1.mfMinMaxDistance, KF1.mTcw,
+                                  reinterpret_cast<const orbx_keypoint*>(KF2.mvKeysUn), KF2.mDescriptors, KF2.N, KF2.mWorldPos, KF2.mbGood,
+                                  KF2.mPointDescriptors, KF2.mfMinMaxDistance, KF2.mTcw, sim, K, &bounds, th, TH_HIGH, row.data(), &res);
+    if (r != ORBX_OK) throw orbx::Error(r, r == ORBX_E_BADARG ? "ORBmatcher::SearchBySim3: an argument out of range" : orbx_last_error(ext_->context()));
+    for (int i = 0; i < KF1.N; i++) vpMatches12[(size_t)i] = row[(size_t)i];
+    if (result) *result = res;
+    return res.n_found;
+  }
+
   // Features/ORBmatcher.cpp:5-7 defines these out of class; `inline` gives the header-only shim a definition too, so that an
   // odr-use (std::min(ORBmatcher::TH_LOW, d)) links
   inline static constexpr int HISTO_LENGTH = 30;
@@ -848,6 +876,151 @@ class PnPsolver {
   bool ran_ = false;
   int iterationsAsked_ = 0;
   orbx_pnp_result res_ = {};
+};
+
+// ---- Sim3Solver (ORB-SLAM2's Sim3Solver.h; include/orbx.h, "loop closing: Sim3 RANSAC") -------------------------------------------
+// The design's constructor takes the two keyframes and vpMatched12; here a keyframe is a Frame-like object (mvKeysUn,
+// mpORBextractor, mK) with its map points as coordinates plus a has-point flag per feature and its pose Tcw, and the matches are
+// the row vnMatches12 (KF2's feature matched to KF1's, or -1: GetIndexInKeyFrame taken as the identity).  SetRansacParameters,
+// iterate, find and the GetEstimated* calls keep their signatures; T12 = [s12 R12 | t12] comes back as PnPsolver::Mat.  One
+// orbx_sim3_solve call is the solver's whole life: the first iterate() or find() draws 3 * maxIterations values from the host's
+// rand() and runs them all on the device of KF1's extractor; every iterate(n) then answers what the design's n-iteration turn
+// would.  Argument / HIP errors throw orbx::Error.
+class Sim3Solver {
+ public:
+  typedef PnPsolver::Mat Mat;
+
+  template <class KeyFrameT, class Point3>
+  Sim3Solver(const KeyFrameT& KF1, const std::vector<Point3>& vP3D1, const std::vector<bool>& vbHasPoint1, const PoseT& Tcw1,
+             const KeyFrameT& KF2, const std::vector<Point3>& vP3D2, const std::vector<bool>& vbHasPoint2, const PoseT& Tcw2,
+             const std::vector<int>& vnMatches12, bool bFixScale = true)
+      : ext_(KF1.mpORBextractor), fixScale_(bFixScale) {
+    if (!ext_) throw orbx::Error(ORBX_E_BADARG, "Sim3Solver: the keyframe carries no extractor");
+    if (vnMatches12.size() != KF1.mvKeysUn.size())
+      throw orbx::Error(ORBX_E_BADARG, "Sim3Solver: vnMatches12 must have one entry per keypoint of KF1");
+    side(KF1, vP3D1, vbHasPoint1, Tcw1, 0);
+    side(KF2, vP3D2, vbHasPoint2, Tcw2, 1);
+    match_.assign(vnMatches12.begin(), vnMatches12.end());
+    if (match_.empty()) match_.push_back(-1);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) K_[r * 3 + c] = frameK(KF1.mK, r, c);
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    probability_ = probability;
+    minInliers_ = minInliers;
+    maxIterations_ = maxIterations;
+    ran_ = false;
+    iterationsAsked_ = 0;
+  }
+
+  Mat find(std::vector<bool>& vbInliers12, int& nInliers) {
+    bool bFlag;
+    return iterate(maxIterations_, bFlag, vbInliers12, nInliers);
+  }
+
+  Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    run();
+    iterationsAsked_ += nIterations > 0 ? nIterations : 0;
+    bNoMore = false;
+    vbInliers.assign(n_[0], false);
+    nInliers = 0;
+    if (res_.status & (ORBX_SIM3_FEW_POINTS | ORBX_SIM3_BAD_INPUT | ORBX_SIM3_NONFINITE)) {
+      bNoMore = true;
+      return Mat();
+    }
+    if (res_.found_it >= 0 && res_.found_it < iterationsAsked_) {
+      nInliers = res_.n_inliers;
+      for (size_t i = 0; i < n_[0]; i++) vbInliers[i] = inl_[i] != 0;
+      return answer();
+    }
+    if (res_.found_it < 0 && iterationsAsked_ >= res_.its_run) bNoMore = true;
+    return Mat();
+  }
+
+  // R12 (row-major), t12 and s12 of the result; zeros without one
+  const float* GetEstimatedRotation() { return result().R12; }
+  const float* GetEstimatedTranslation() { return result().t12; }
+  float GetEstimatedScale() { return result().s12; }
+  // the row LoopClosing builds from vbInliers: vnMatches12 on the result's inliers, -1 elsewhere
+  const std::vector<int32_t>& inlierMatches() {
+    run();
+    return row_;
+  }
+  const orbx_sim3_result& result() {
+    run();
+    return res_;
+  }
+
+ private:
+  template <class KeyFrameT, class Point3>
+  void side(const KeyFrameT& KF, const std::vector<Point3>& vP3D, const std::vector<bool>& vbHasPoint, const PoseT& Tcw, int k) {
+    const size_t n = KF.mvKeysUn.size();
+    if (vP3D.size() != n || vbHasPoint.size() != n)
+      throw orbx::Error(ORBX_E_BADARG, "Sim3Solver: vP3D and vbHasPoint must have one entry per keypoint of their keyframe");
+    n_[k] = n;
+    keys_[k].resize(n ? n : 1);
+    p3d_[k].assign(3 * (n ? n : 1), 0.f);
+    has_[k].assign(n ? n : 1, 0);
+    if (n) std::memcpy(keys_[k].data(), KF.mvKeysUn.data(), n * sizeof(orbx_keypoint));
+    for (size_t i = 0; i < n; i++) {
+      p3d_[k][3 * i] = vP3D[i].x;
+      p3d_[k][3 * i + 1] = vP3D[i].y;
+      p3d_[k][3 * i + 2] = vP3D[i].z;
+      has_[k][i] = vbHasPoint[i] ? 1 : 0;
+    }
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) pose_[k][r * 3 + c] = (float)Tcw(r, c);
+      pose_[k][9 + r] = (float)Tcw(r, 3);
+    }
+  }
+
+  void run() {
+    if (ran_) return;
+    std::vector<int32_t> draws(3 * (size_t)(maxIterations_ > 0 ? maxIterations_ : 1));
+    for (size_t i = 0; i < draws.size(); i++) draws[i] = rand();
+    inl_.assign(n_[0] ? n_[0] : 1, 0);
+    row_.assign(n_[0] ? n_[0] : 1, -1);
+    const int r = orbx_sim3_solve(ext_->context(), keys_[0].data(), (int)n_[0], p3d_[0].data(), has_[0].data(), pose_[0], keys_[1].data(),
+                                  (int)n_[1], p3d_[1].data(), has_[1].data(), pose_[1], match_.data(), K_, nullptr, fixScale_ ? 1 : 0,
+                                  probability_, minInliers_, maxIterations_, 9.210f, (int)(draws.size() / 3), draws.data(), &res_, sim_,
+                                  row_.data(), inl_.data());
+    if (r != ORBX_OK) throw orbx::Error(r, r == ORBX_E_BADARG ? "Sim3Solver: a RANSAC parameter out of range" : orbx_last_error(ext_->context()));
+    row_.resize(n_[0]);
+    ran_ = true;
+  }
+
+  Mat answer() const {
+#ifdef ORBX_WITH_OPENCV
+    Mat T(4, 4, CV_32F);
+    for (int r = 0; r < 4; r++) {
+      float* row = reinterpret_cast<float*>(T.data + (size_t)r * T.step);
+      for (int c = 0; c < 4; c++) row[c] = r == 3 ? (c == 3 ? 1.f : 0.f) : (c == 3 ? res_.t12[r] : res_.s12 * res_.R12[r * 3 + c]);
+    }
+#else
+    Mat T;
+    T.has = true;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) T.m[r * 4 + c] = res_.s12 * res_.R12[r * 3 + c];
+      T.m[r * 4 + 3] = res_.t12[r];
+    }
+#endif
+    return T;
+  }
+
+  ORBextractor* ext_;
+  bool fixScale_;
+  size_t n_[2] = {0, 0};
+  std::vector<orbx_keypoint> keys_[2];
+  std::vector<float> p3d_[2];
+  std::vector<uint8_t> has_[2], inl_;
+  std::vector<int32_t> match_, row_;
+  float pose_[2][12], K_[9], sim_[13];
+  double probability_ = 0.99;
+  int minInliers_ = 6, maxIterations_ = 300;
+  bool ran_ = false;
+  int iterationsAsked_ = 0;
+  orbx_sim3_result res_ = {};
 };
 
 template <class Point3>

@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
-           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
+           "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "Sim3Result", "SIM3_RESULT_DTYPE", "SIM3_BAD_INPUT", "SIM3_NONFINITE", "SIM3_FEW_POINTS", "SIM3_BAD_DRAWS", "SIM3_NO_RESULT", "Sim3Solver", "sample_sim3_draws", "MatchSim3Result", "MSIM3_RESULT_DTYPE", "MSIM3_BAD_INPUT", "MSIM3_NONFINITE", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
@@ -177,6 +177,38 @@ def sample_pnp_draws(rand, n_iter: int) -> np.ndarray:
     return out
 
 
+SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT = 2, 4, 8, 16, 32
+_SIM3_INTS = ("status", "n_correspondences", "max_its", "its_run", "found_it", "best_it", "n_inliers", "n_best_inliers", "n_degenerate")
+
+
+class Sim3Result(ctypes.Structure):
+    """orbx_sim3_result: Sim3Solver's outcome for one keyframe pair (found_it tells which iterate() turn would have returned it)."""
+    _fields_ = [(n, ctypes.c_int32) for n in _SIM3_INTS] + [("reserved", ctypes.c_int32 * 2), ("s12", ctypes.c_float),
+                                                           ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n in _SIM3_INTS}
+        d["s12"], d["R12"] = float(self.s12), np.array(self.R12[:], np.float32).reshape(3, 3)
+        d["t12"] = np.array(self.t12[:], np.float32)
+        return d
+
+
+SIM3_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _SIM3_INTS] + [("reserved", "<i4", 2), ("s12", "<f4"), ("R12", "<f4", (3, 3)),
+                                                                 ("t12", "<f4", 3)])
+assert SIM3_RESULT_DTYPE.itemsize == ctypes.sizeof(Sim3Result) == 96
+
+
+def sample_sim3_draws(rand, n_iter: int) -> np.ndarray:
+    """The draws of n_iter Sim3 RANSAC hypotheses, int32 [n_iter, 3]: the next 3 * n_iter values of `rand`, as sample_pnp_draws
+    takes them, in the order Sim3Solver::iterate would draw them."""
+    n_iter = int(n_iter)
+    out = np.zeros((n_iter, 3), np.int32)
+    for it in range(n_iter):
+        for j in range(3):
+            out[it, j] = int(rand())
+    return out
+
+
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
 PROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_in_image", "n_with_candidates", "n_displaced", "n_rot_removed", "rounds")
 
@@ -226,6 +258,24 @@ class KfProjResult(ctypes.Structure):
 
 KFPROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in KFPROJ_RESULT_FIELDS])
 assert KFPROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(KfProjResult) == 52
+
+
+MSIM3_BAD_INPUT, MSIM3_NONFINITE = 2, 4
+MSIM3_RESULT_FIELDS = ("status", "n_found", "n_points_12", "n_behind_12", "n_out_image_12", "n_out_distance_12", "n_with_candidates_12",
+                       "n_over_dist_12", "n_points_21", "n_behind_21", "n_out_image_21", "n_out_distance_21", "n_with_candidates_21",
+                       "n_over_dist_21", "n_one_sided", "reserved")
+
+
+class MatchSim3Result(ctypes.Structure):
+    """orbx_msim3_result: the counters of ORBmatcher::SearchBySim3 for one (KF1, KF2) pair, per direction."""
+    _fields_ = [(n, ctypes.c_int32) for n in MSIM3_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+MSIM3_RESULT_DTYPE = np.dtype([(n, "<i4") for n in MSIM3_RESULT_FIELDS])
+assert MSIM3_RESULT_DTYPE.itemsize == ctypes.sizeof(MatchSim3Result) == 64
 
 
 TRI_BAD_INPUT, TRI_NONFINITE, TRI_LOW_BASELINE, TRI_ZERO_BASELINE = 2, 4, 8, 16
@@ -390,6 +440,15 @@ def lib() -> ctypes.CDLL:
     L.orbx_pnp_solve_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, f64, i32, i32, f32, f32, i32,
                                               vp, vp, vp, vp, vp]
     L.orbx_pnp_solve.argtypes = [vp, vp, i32, vp, vp, vp, vp, f64, i32, i32, f32, f32, i32, vp, ctypes.POINTER(PnpResult), vp]
+    L.orbx_sim3_ransac_table.argtypes = [f64, i32, i32, i32, vp]
+    L.orbx_sim3_solve_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, f64, i32, i32,
+                                               f32, i32, vp, vp, vp, vp, vp]
+    L.orbx_match_sim3_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                               ctypes.POINTER(_Bounds), f32, i32, vp, vp]
+    L.orbx_match_sim3.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds),
+                                  f32, i32, vp, ctypes.POINTER(MatchSim3Result)]
+    L.orbx_sim3_solve.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, f32, i32, vp,
+                                  ctypes.POINTER(Sim3Result), vp, vp, vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1044,6 +1103,93 @@ class ORBextractor:
                                                    int(bool(checkOri)), _ptr(mc), _ptr(out), ctypes.byref(res))
         self._check(r, "orbx_match_keyframe_projection")
         return mc[:len(ck)].copy(), res
+
+    # -- ORBmatcher::SearchBySim3 (include/orbx.h, "loop closing: matching under a similarity") ---------------------
+    def match_sim3_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, set1: np.ndarray, set2: np.ndarray, d_kps_un,
+                                d_desc, d_n, n_point_sets: int, d_points, d_point_mask, d_point_dist, d_pose, d_sim3, K,
+                                bounds: Tuple[int, int, int, int], d_matches, d_res, th: float = 7.5, ORBdist: int = 100,
+                                d_point_desc=None, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::SearchBySim3 for pairs (KF1 kf1[p] with point set set1[p], KF2 kf2[p] with set2[p]; host index arrays):
+        the point sets of sim3_solve_batch_device plus d_point_dist float32 [n_point_sets, capacity, 2] (mfMinDistance,
+        mfMaxDistance) and optionally d_point_desc uint8 [n_point_sets, capacity, 32]; d_pose float32 [n_frames, 12] and d_sim3
+        float32 [n_pairs, 13] as the solver takes and writes them.  d_matches int32 [n_pairs, capacity] is read and written (the
+        solver's d_match_inliers): KF1's feature -> KF2's feature, or -1.  d_res [n_pairs] MSIM3_RESULT_DTYPE records (64 bytes).
+        Stream-ordered on the context's stream."""
+        cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
+        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
+        set1, set2 = self._tri_pairs(set1, set2, ns)
+        P = len(kf1)
+        if len(set1) != P:
+            raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the point array", d_points, ns * cap * 12)
+        _need("the point distance array", d_point_dist, ns * cap * 8)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, ns * cap)
+        if d_point_desc is not None:
+            _need("the point descriptor array", d_point_desc, ns * cap * 32)
+        _need("the pose array", d_pose, nf * 48)
+        _need("the similarity array", d_sim3, P * 52)
+        _need("matches", d_matches, P * cap * 4)
+        _need("the result array", d_res, P * MSIM3_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_point_dist, d_pose, d_sim3, d_matches, d_res)
+        r = self._L.orbx_match_sim3_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2), _ptr(d_kps_un), _ptr(d_desc),
+                                                 _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask), _ptr(d_point_desc),
+                                                 _ptr(d_point_dist), _ptr(d_pose), _ptr(d_sim3), _ptr(Kf), ctypes.byref(b), float(th),
+                                                 int(ORBdist), _ptr(d_matches), _ptr(d_res))
+        self._check(r, "orbx_match_sim3_batch_device")
+
+    def compute_sim3_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets: int, d_points,
+                                  d_point_mask, d_point_dist, d_pose, K, bounds: Tuple[int, int, int, int], d_draws, d_sim3_res, d_sim3,
+                                  d_matches, d_msim3_res, d_point_desc=None, fix_scale: bool = False, th: float = 7.5, ORBdist: int = 100,
+                                  capacity: Optional[int] = None, **ransac) -> None:
+        """The geometry of LoopClosing::ComputeSim3 for pairs: sim3_solve_batch_device, then match_sim3_pairs_device on the
+        similarity and the row of inlier matches it wrote (d_matches), queued one behind the other on the context's stream with
+        no copy and no wait between them.  A pair without a similarity has zeros in d_sim3: the matcher flags it
+        (MSIM3_NONFINITE: s12 <= 0) and leaves its all -1 row."""
+        self.sim3_solve_batch_device(n_frames, kf1, kf2, set1, set2, d_kps_un, d_n, d_match, n_point_sets, d_points, d_point_mask, d_pose,
+                                     K, d_draws, d_sim3_res, d_sim3, d_matches, None, fix_scale=fix_scale, capacity=capacity, **ransac)
+        self.match_sim3_pairs_device(n_frames, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, n_point_sets, d_points, d_point_mask,
+                                     d_point_dist, d_pose, d_sim3, K, bounds, d_matches, d_msim3_res, th, ORBdist, d_point_desc, capacity)
+
+    def match_sim3(self, keys_un1, desc1, points1, mask1, point_dist1, Tcw1, keys_un2, desc2, points2, mask2, point_dist2, Tcw2, sim3,
+                   K, bounds: Tuple[int, int, int, int], matches12=None, th: float = 7.5, ORBdist: int = 100, point_desc1=None,
+                   point_desc2=None):
+        """SearchBySim3 for one pair in host memory (orbx_match_sim3) -> (matches12 int32 [n1], MatchSim3Result).  sim3 [13]: R12
+        row-major, t12, s12; matches12 (default all -1): the matches the pair already has.  Synchronous."""
+        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        p1, p2 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3), np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
+        q1, q2 = np.ascontiguousarray(point_dist1, np.float32).reshape(-1, 2), np.ascontiguousarray(point_dist2, np.float32).reshape(-1, 2)
+        if not (len(k1) == len(d1) == len(p1) == len(q1)) or not (len(k2) == len(d2) == len(p2) == len(q2)):
+            raise OrbxError(E_BADARG, "keypoints / descriptors / points / distances differ in length")
+        if (mask1 is None) != (mask2 is None) or (point_desc1 is None) != (point_desc2 is None):
+            raise OrbxError(E_BADARG, "the masks, and the point descriptors, are given together or not at all")
+        opt = lambda a, n, w: None if a is None else np.ascontiguousarray(a, np.uint8).reshape(n, *w)  # noqa: E731
+        m1, m2 = (None if m is None else np.ascontiguousarray(np.asarray(m) != 0, np.uint8).reshape(-1) for m in (mask1, mask2))
+        if m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2)):
+            raise OrbxError(E_BADARG, "a mask needs one entry per feature of its keyframe")
+        pd1, pd2 = opt(point_desc1, len(k1), (32,)), opt(point_desc2, len(k2), (32,))
+        row = np.full(max(len(k1), 1), -1, np.int32)
+        if matches12 is not None:
+            given = np.asarray(matches12, np.int32).reshape(-1)
+            if len(given) != len(k1):
+                raise OrbxError(E_BADARG, "matches12 needs one entry per feature of KF1")
+            row[:len(k1)] = given
+        T1, T2 = _pose12(Tcw1), _pose12(Tcw2)
+        sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        res = MatchSim3Result()
+        r = self._L.orbx_match_sim3(self._h, _ptr(k1), _ptr(d1), len(k1), _ptr(p1), _ptr(m1), _ptr(pd1), _ptr(q1), _ptr(T1), _ptr(k2),
+                                    _ptr(d2), len(k2), _ptr(p2), _ptr(m2), _ptr(pd2), _ptr(q2), _ptr(T2), _ptr(sim), _ptr(Kf),
+                                    ctypes.byref(b), float(th), int(ORBdist), _ptr(row), ctypes.byref(res))
+        self._check(r, "orbx_match_sim3")
+        return row[:len(k1)].copy(), res
 
     def _tri_pairs(self, kf1, kf2, n_frames: int):
         kf1 = np.ascontiguousarray(kf1, np.int32).reshape(-1)
@@ -1723,6 +1869,84 @@ class ORBextractor:
                                                         _ptr(d_res), _ptr(d_pose), _ptr(d_match_inliers), _ptr(d_inliers)),
                     "orbx_pnp_solve_batch_device")
 
+    # -- Sim3Solver of loop closing (include/orbx.h, "loop closing: Sim3 RANSAC") ----------------------------------
+    def sim3_solve(self, keys_un1, points1, mask1, pose1, keys_un2, points2, mask2, pose2, match12, K, draws, sigma2=None,
+                   fix_scale: bool = False, probability: float = 0.99, min_inliers: int = 20, max_iterations: int = 300,
+                   th2: float = 9.210):
+        """One keyframe pair from host memory: each keyframe's mvKeysUn, one map point per feature (points [n, 3], mask [n]; both
+        masks None = every feature has one), its pose Tcw (12 floats: R row-major, then t), the row match12 [n1] (KF2's feature
+        matched to KF1's, or -1), K and the draws int32 [n_iter, 3] (sample_sim3_draws).  One call is the solver's whole life.
+        Returns (Sim3Result, sim3 [13] float32 = R12, t12, s12, the inlier row [n1] int32, vbInliers [n1] bool)."""
+        k1 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        p1 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
+        if (mask1 is None) != (mask2 is None):
+            raise OrbxError(E_BADARG, "the two masks are given together or not at all")
+        m1 = None if mask1 is None else np.ascontiguousarray(np.asarray(mask1) != 0, np.uint8).reshape(-1)
+        m2 = None if mask2 is None else np.ascontiguousarray(np.asarray(mask2) != 0, np.uint8).reshape(-1)
+        row = np.ascontiguousarray(match12, np.int32).reshape(-1)
+        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1) or (m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2))):
+            raise OrbxError(E_BADARG, "points, mask and match12 must have one entry per keypoint of their keyframe")
+        T1, T2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (pose1, pose2))
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1, 3)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        res, sim = Sim3Result(), np.zeros(13, np.float32)
+        out_row, out = np.full(max(len(k1), 1), -1, np.int32), np.zeros(max(len(k1), 1), np.uint8)
+        self._check(self._L.orbx_sim3_solve(self._h, _ptr(k1), len(k1), _ptr(p1), _ptr(m1), _ptr(T1), _ptr(k2), len(k2), _ptr(p2),
+                                            _ptr(m2), _ptr(T2), _ptr(row), _ptr(Kf), _ptr(sig), int(bool(fix_scale)),
+                                            float(probability), int(min_inliers), int(max_iterations), float(th2), len(d), _ptr(d),
+                                            ctypes.byref(res), _ptr(sim), _ptr(out_row), _ptr(out)), "orbx_sim3_solve")
+        return res, sim, out_row[:len(k1)], out[:len(k1)].astype(bool)
+
+    def sim3_solve_batch_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, set1: np.ndarray, set2: np.ndarray, d_kps_un,
+                                d_n, d_match, n_point_sets: int, d_points, d_point_mask, d_pose, K, d_draws, d_res, d_sim3,
+                                d_match_inliers, d_inliers=None, sigma2=None, fix_scale: bool = False, probability: float = 0.99,
+                                min_inliers: int = 20, max_iterations: int = 300, th2: float = 9.210, n_iter: Optional[int] = None,
+                                capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: problem p finds the similarity between keyframe kf1[p] (the current one; its points are
+        set set1[p]) and keyframe kf2[p] (the candidate; set set2[p]).  d_match int32 [n_problems, capacity]: KF2's feature
+        matched to KF1's, or -1 (match_bow_pairs_device's row with KF1 on the frame side); d_pose float32 [n_frames, 12]; d_draws
+        int32 [n_problems, n_iter, 3] (n_iter: default from its size).  Outputs: d_res [n_problems] SIM3_RESULT_DTYPE records (96
+        bytes), d_sim3 float32 [n_problems, 13] (R12, t12, s12), d_match_inliers int32 [n_problems, capacity], d_inliers uint8
+        [n_problems, capacity] or None.  Stream-ordered: the outputs are valid after a device synchronisation."""
+        kf1, kf2 = np.ascontiguousarray(kf1, np.int32), np.ascontiguousarray(kf2, np.int32)
+        set1, set2 = np.ascontiguousarray(set1, np.int32), np.ascontiguousarray(set2, np.int32)
+        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
+        if len(kf2) != P or len(set1) != P or len(set2) != P:
+            raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
+        if n_iter is None:
+            nbytes = _nbytes(d_draws)
+            n_iter = nbytes // (12 * P) if P and nbytes is not None else 0
+        n_iter = int(n_iter)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        _need("the match array", d_match, P * cap * 4)
+        _need("the point array", d_points, n_point_sets * cap * 12)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, n_point_sets * cap)
+        _need("the pose array", d_pose, n_frames * 48)
+        _need("the draws", d_draws, P * max(n_iter, 0) * 12)
+        _need("the result array", d_res, P * SIM3_RESULT_DTYPE.itemsize)
+        _need("the similarity array", d_sim3, P * 52)
+        _need("the inlier match array", d_match_inliers, P * cap * 4)
+        if d_inliers is not None:
+            _need("the inlier flags", d_inliers, P * cap)
+        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_pose, d_draws, d_res, d_sim3, d_match_inliers, d_inliers)
+        self._check(self._L.orbx_sim3_solve_batch_device(self._h, n_frames, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2),
+                                                         _ptr(d_kps_un), _ptr(d_n), cap, _ptr(d_match), n_point_sets, _ptr(d_points),
+                                                         _ptr(d_point_mask), _ptr(d_pose), _ptr(Kf), _ptr(sig), int(bool(fix_scale)),
+                                                         float(probability), int(min_inliers), int(max_iterations), float(th2),
+                                                         n_iter, _ptr(d_draws), _ptr(d_res), _ptr(d_sim3), _ptr(d_match_inliers),
+                                                         _ptr(d_inliers)), "orbx_sim3_solve_batch_device")
+
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:
         w, h = ctypes.c_int(0), ctypes.c_int(0)
@@ -2326,6 +2550,26 @@ class ORBmatcher:
         return int(res.nmatches), m, res
 
 
+    def SearchBySim3(self, KF1: Frame, KF2: Frame, map1, map2, matches12, s12: float, R12, t12, th: float = 7.5, K=None,
+                     bounds=None, ORBdist: int = 100):
+        """ORB-SLAM2's SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (include/orbx.h, "loop closing: matching under a
+        similarity") -> (nFound, matches12, MatchSim3Result).  map1 / map2: (points [N, 3], mask [N] or None, point_dist [N, 2],
+        Tcw, point_desc [N, 32] or None) of each keyframe; matches12 int32 [N1]: KF2's feature per feature of KF1, or -1."""
+        ext = self._ext or KF1.mpORBextractor or KF2.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(KF1, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchBySim3 needs K (the keyframe carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        (p1, m1, q1, T1, pd1), (p2, m2, q2, T2, pd2) = map1, map2
+        sim = np.r_[np.asarray(R12, np.float32).reshape(9), np.asarray(t12, np.float32).reshape(3), np.float32(s12)].astype(np.float32)
+        m, res = ext.match_sim3(KF1.mvKeysUn, KF1.mDescriptors, p1, m1, q1, T1, KF2.mvKeysUn, KF2.mDescriptors, p2, m2, q2, T2, sim, K,
+                                bounds if bounds is not None else KF1.bounds, matches12, th, ORBdist, pd1, pd2)
+        return int(res.n_found), m, res
+
+
 class PnPsolver:
     """ORB-SLAM2's PnPsolver for one frame and one candidate's map points (include/orbx.h, "behind SearchByBoW: PnP RANSAC"):
     PnPsolver(frame, points, mask_or_match, K), SetRansacParameters, then iterate(nIterations) or find().  mask_or_match: bool /
@@ -2412,6 +2656,87 @@ class PnPsolver:
             return None, np.zeros(len(self._keys), bool), 0, res
         T, inl, n = self._answer()
         return T, inl, n, res
+
+
+class Sim3Solver:
+    """ORB-SLAM2's Sim3Solver for one keyframe pair (include/orbx.h, "loop closing: Sim3 RANSAC"), in the shape of PnPsolver:
+    Sim3Solver(kf1, kf2, match12, K, bFixScale), SetRansacParameters, then iterate(nIterations) or find().  kf1 / kf2: (mvKeysUn,
+    points [n, 3], mask [n] or None, Tcw 3x4 / 4x4 / 12 floats) of the current keyframe and of the candidate; match12 int32 [n1]:
+    KF2's feature matched to KF1's, or -1 (vpMatched12 with GetIndexInKeyFrame taken as the identity).  The device runs a
+    solver's whole life in one call: the first iterate() or find() runs every iteration on `rand`'s draws, and iterate(n) answers
+    as the reference's n-at-a-time turns would."""
+
+    def __init__(self, kf1, kf2, match12, K, bFixScale: bool = False, extractor: Optional[ORBextractor] = None, rand=None):
+        if extractor is None:
+            raise OrbxError(E_BADARG, "Sim3Solver needs an ORBextractor (device context); pass extractor=")
+        self._ext, self._kf1, self._kf2 = extractor, tuple(kf1), tuple(kf2)
+        self._match = np.ascontiguousarray(match12, np.int32).reshape(-1)
+        self._K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self._fix = bool(bFixScale)
+        if rand is None:
+            libc = ctypes.CDLL(None)
+            libc.rand.restype = ctypes.c_int
+            rand = libc.rand
+        self._rand = rand
+        self._params = dict(probability=0.99, min_inliers=6, max_iterations=300, th2=9.210)  # the constructor's own
+        self._turns = 0
+        self._result = None
+
+    def SetRansacParameters(self, probability: float = 0.99, minInliers: int = 6, maxIterations: int = 300) -> None:
+        self._params = dict(self._params, probability=probability, min_inliers=minInliers, max_iterations=maxIterations)
+        self._result, self._turns = None, 0
+
+    @staticmethod
+    def _pose12(T):
+        T = np.asarray(T, np.float32)
+        if T.size == 12 and T.ndim == 1:
+            return T
+        return np.r_[T[:3, :3].reshape(9), T[:3, 3]].astype(np.float32)
+
+    def _run(self):
+        if self._result is None:
+            draws = sample_sim3_draws(self._rand, int(self._params["max_iterations"]))
+            (k1, p1, m1, T1), (k2, p2, m2, T2) = self._kf1, self._kf2
+            self._result = self._ext.sim3_solve(k1, p1, m1, self._pose12(T1), k2, p2, m2, self._pose12(T2), self._match, self._K,
+                                                draws, fix_scale=self._fix, **self._params)
+        return self._result
+
+    def _answer(self):
+        res, sim, _, inl = self._run()
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3], T[:3, 3] = np.float32(sim[12]) * sim[:9].reshape(3, 3), sim[9:12]
+        return T, inl, int(res.n_inliers)
+
+    def iterate(self, nIterations: int):
+        """-> (T12 4x4 float32 = [s12 R12 | t12] or None, bNoMore, vbInliers [n1] bool, nInliers, the Sim3Result): what the
+        reference's iterate returns in this turn of nIterations iterations."""
+        res = self._run()[0]
+        self._turns += max(int(nIterations), 0)  # (the iterations asked for so far, as the shim counts them)
+        done = self._turns
+        none = np.zeros(len(self._match), bool)
+        if res.status & (SIM3_FEW_POINTS | SIM3_BAD_INPUT | SIM3_NONFINITE):
+            return None, True, none, 0, res
+        if res.found_it >= 0 and res.found_it < done:
+            T, inl, n = self._answer()
+            return T, False, inl, n, res
+        return None, res.found_it < 0 and done >= res.its_run, none, 0, res
+
+    def find(self):
+        """-> (T12 4x4 float32 or None, vbInliers [n1] bool, nInliers, the Sim3Result): iterate until a result or bNoMore."""
+        res = self._run()[0]
+        if res.status & SIM3_NO_RESULT:
+            return None, np.zeros(len(self._match), bool), 0, res
+        T, inl, n = self._answer()
+        return T, inl, n, res
+
+    def GetEstimatedRotation(self) -> np.ndarray:
+        return self._run()[1][:9].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self) -> np.ndarray:
+        return self._run()[1][9:12].copy()
+
+    def GetEstimatedScale(self) -> float:
+        return float(self._run()[1][12])
 
 
 class Optimizer:

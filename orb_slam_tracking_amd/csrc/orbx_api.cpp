@@ -175,6 +175,7 @@ struct orbx_ctx {
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
   PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
   PnpScratch pnp;                 // orbx_pnp_solve* (orbx_pose.cpp)
+  Sim3Scratch sim3;               // orbx_sim3_solve* (orbx_pose.cpp)
   TriScratch tri;                 // orbx_match_triangulation*, orbx_triangulate_matches* (orbx_match_bow.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
@@ -2514,6 +2515,7 @@ MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
 PoseScratch* ctxPose(orbx_ctx* c) { return &c->pose; }
 PnpScratch* ctxPnp(orbx_ctx* c) { return &c->pnp; }
+Sim3Scratch* ctxSim3(orbx_ctx* c) { return &c->sim3; }
 TriScratch* ctxTri(orbx_ctx* c) { return &c->tri; }
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;

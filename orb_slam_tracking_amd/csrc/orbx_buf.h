@@ -181,6 +181,8 @@ struct MatchBowScratch {
   DeviceBuf<uint8_t> dLocalIo;   // staging of orbx_match_local_map
   HeldArray<int32_t> kfProjPairs;  // the lists [3][n_pairs] (keyframe, current, point set) of the last orbx_match_keyframe_projection* call
   DeviceBuf<uint8_t> dKfProjIo;  // staging of orbx_match_keyframe_projection
+  HeldArray<int32_t> sim3Pairs;  // the lists [4][n_pairs] (KF1, KF2, set 1, set 2) of the last orbx_match_sim3* call
+  DeviceBuf<uint8_t> dSim3Io;    // staging of orbx_match_sim3
 };
 
 // What a context keeps for orbx_match_triangulation* and orbx_triangulate_matches* (orbx_match_bow.cpp).
@@ -215,6 +217,18 @@ struct PnpScratch {
   int keyMinInliers = 0, keyMaxIterations = 0;
   DeviceBuf<uint8_t> dWork;     // the correspondences, the hypotheses and the per-problem values of a call
   DeviceBuf<uint8_t> dIo;       // staging of orbx_pnp_solve
+};
+
+// What a context keeps for orbx_sim3_solve* (orbx_pose.cpp).
+struct Sim3Scratch {
+  HeldArray<int32_t> problems;  // the lists [4][n_problems] (KF1, KF2, set 1, set 2) of the last call
+  HeldArray<float> sigma2;      // sigma2 of the last call
+  HeldArray<int32_t> table;     // N -> mRansacMaxIts for N in [0, capacity] of the last call
+  std::vector<int32_t> hTable;  // ... as computed on the host for `key`: the parameters it was computed from
+  double keyProbability = 0;
+  int keyMinInliers = 0, keyMaxIterations = 0;
+  DeviceBuf<uint8_t> dWork;     // the correspondences, the hypotheses and the per-problem values of a call
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_sim3_solve
 };
 
 }  // namespace orbx

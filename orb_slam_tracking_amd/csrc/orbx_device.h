@@ -523,6 +523,24 @@ struct MatchKfProjArgs {
   orbx_kfproj_result* res;    // [nPairs]
 };
 
+// ---- ORBmatcher::SearchBySim3 (orbx_match_sim3_kernel.hip): one workgroup of MP_THREADS per (KF1, KF2) pair ----
+struct MatchSim3Args {
+  const orbx_keypoint* kps;   // [nFrames][cap] undistorted
+  const uint8_t* desc;        // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;           // [nFrames] (clamped to [0, cap])
+  const float* points;        // [nSets][cap][3] a keyframe's map points, per feature
+  const uint8_t* pointMask;   // nullable [nSets][cap]
+  const uint8_t* pointDesc;   // nullable [nSets][cap][32], 16-byte aligned
+  const float* pointDist;     // [nSets][cap][2] mfMinDistance, mfMaxDistance
+  const float* pose;          // [nFrames][12] Tcw per frame
+  const float* sim3;          // [nPairs][13] R12 row-major, t12, s12
+  const int32_t* pairs;       // [4][nPairs] KF1s, KF2s, KF1s' point sets, KF2s' point sets
+  int32_t cap, nPairs, orbDist;
+  MatchCamArgs cam;
+  int32_t* matches;           // [nPairs][cap] in and out, indexed by KF1's feature
+  orbx_msim3_result* res;     // [nPairs]
+};
+
 // ---- LocalMapping::CreateNewMapPoints (orbx_match_tri_kernel.hip): SearchForTriangulation, one workgroup of MB_THREADS per
 // (KF1, KF2) pair as k_match_bow; then the triangulation, TT_THREADS features of a pair per workgroup ----
 constexpr int TT_THREADS = 256;
@@ -729,5 +747,34 @@ struct PnpArgs {
   double fu, fv, uc, vc;
   float th2;
   int32_t nProblems, cap, nLevels, nIter;
+};
+
+// k_sim3_*: Sim3Solver (include/orbx.h, "loop closing: Sim3 RANSAC"): prep and resolve a wave per problem, the hypotheses a lane
+// per (problem, iteration)
+constexpr int SIM3_CORR_BYTES = 56;  // orbx_sim3::Corr
+constexpr int SIM3_HYP_BYTES = 64;   // orbx_sim3::Hyp
+constexpr int SIM3_MAX_CAPACITY = 16384;  // ORBX_BOW_MAX_FEATURES
+constexpr long long SIM3_MAX_HYPOTHESES = 2147483647LL - 63;  // n_problems * n_iter: (lanes + 63) / 64 workgroups of one wave
+struct Sim3Args {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const int32_t* nKps;        // [frames]
+  const int32_t* problems;    // [4][nProblems] KF1s, KF2s, KF1s' point sets, KF2s' point sets
+  const int32_t* match;       // [nProblems][cap]: the feature of KF2 matched to KF1's feature, or -1
+  const float* points;        // [sets][cap][3]
+  const uint8_t* mask;        // nullable [sets][cap]
+  const float* pose;          // [frames][12] Tcw
+  const float* sigma2;        // [nLevels] (device)
+  const int32_t* table;       // [cap + 1] (device): mRansacMaxIts of N
+  const int32_t* draws;       // [nProblems][nIter][3]
+  orbx_sim3_result* res;      // [nProblems]
+  float* sim3;                // [nProblems][13]
+  int32_t* matchInliers;      // [nProblems][cap]
+  uint8_t* inliers;           // nullable [nProblems][cap]
+  uint8_t* corr;              // workspace [nProblems][cap] Corr: the correspondences, ascending feature of KF1
+  int32_t* corrOf;            // workspace [nProblems][cap]: feature i1's correspondence, or -1
+  int32_t* meta;              // workspace [nProblems][4]: orbx_sim3::Meta
+  uint8_t* hyp;               // workspace [nProblems][nIter] Hyp
+  float fx, fy, cx, cy, th2;
+  int32_t nProblems, cap, nLevels, nIter, minInliers, fixScale;
 };
 }  // namespace orbx

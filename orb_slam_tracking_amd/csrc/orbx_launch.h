@@ -97,4 +97,12 @@ hipError_t launch_pnp_prep(hipStream_t st, const PnpArgs& a);
 hipError_t launch_pnp_hypotheses(hipStream_t st, const PnpArgs& a);
 hipError_t launch_pnp_refine(hipStream_t st, const PnpArgs& a);
 
+// orbx_sim3_kernel.hip
+hipError_t launch_sim3_prep(hipStream_t st, const Sim3Args& a);
+hipError_t launch_sim3_hypotheses(hipStream_t st, const Sim3Args& a);
+hipError_t launch_sim3_resolve(hipStream_t st, const Sim3Args& a);
+
+// orbx_match_sim3_kernel.hip
+hipError_t launch_match_sim3(hipStream_t st, const MatchSim3Args& a);
+
 }  // namespace orbx

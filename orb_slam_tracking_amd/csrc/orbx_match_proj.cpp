@@ -410,4 +410,128 @@ int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un
   return ORBX_OK;
 }
 
+// ---- ORBmatcher::SearchBySim3 (include/orbx.h, "loop closing: matching under a similarity"; orbx_match_sim3_kernel.hip)
+int orbx_match_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
+                                 const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const uint8_t* d_desc32,
+                                 const int32_t* d_n, int capacity, int n_point_sets, const float* d_points,
+                                 const uint8_t* d_point_mask, const uint8_t* d_point_desc32, const float* d_point_dist,
+                                 const float* d_pose, const float* d_sim3, const float* K, const orbx_bounds* bounds, float th,
+                                 int orb_dist, int32_t* d_matches, orbx_msim3_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || n_point_sets < 0 || capacity < 1 || (n_pairs > 0 && (!h_kf1 || !h_kf2 || !h_set1 || !h_set2)) ||
+      !d_kps_un || !d_desc32 || !d_n || !d_points || !d_point_dist || !d_pose || !d_sim3 || !K || !bounds || !d_matches || !d_res)
+    return ORBX_E_BADARG;
+  const bool listsOk = pairsInRange(h_kf1, h_kf2, n_pairs, n_frames) && pairsInRange(h_set1, h_set2, n_pairs, n_point_sets);
+  int r = refused(ctx, "match sim3", th, orb_dist < 0 || orb_dist > 256 ? "orb_dist outside [0, 256]" : nullptr, bounds,
+                  listsOk ? nullptr : "keyframe outside [0, n_frames) or point set outside [0, n_point_sets)",
+                  capacity > ORBX_BOW_MAX_FEATURES ? "capacity above ORBX_BOW_MAX_FEATURES" : nullptr);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  r = holdLists(ctx, st, s->sim3Pairs, {h_kf1, h_kf2, h_set1, h_set2}, n_pairs);
+  if (r != ORBX_OK) return r;
+  MatchSim3Args a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.points = d_points;
+  a.pointMask = d_point_mask;
+  a.pointDesc = d_point_desc32;
+  a.pointDist = d_point_dist;
+  a.pose = d_pose;
+  a.sim3 = d_sim3;
+  a.pairs = s->sim3Pairs;
+  a.cap = capacity;
+  a.nPairs = n_pairs;
+  a.orbDist = orb_dist;
+  a.cam = camArgs(ctx, K, bounds, th);
+  a.matches = d_matches;
+  a.res = d_res;
+  HIPCHK(launch_match_sim3(st, a));
+  return ORBX_OK;
+}
+
+int orbx_match_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* desc1, int n1, const float* points1,
+                    const uint8_t* mask1, const uint8_t* point_desc1, const float* point_dist1, const float* pose1,
+                    const orbx_keypoint* kps_un2, const uint8_t* desc2, int n2, const float* points2, const uint8_t* mask2,
+                    const uint8_t* point_desc2, const float* point_dist2, const float* pose2, const float* sim3, const float* K,
+                    const orbx_bounds* bounds, float th, int orb_dist, int32_t* matches12, orbx_msim3_result* res) {
+  if (n1 < 0 || n2 < 0 || !pose1 || !pose2 || !sim3 || !K || !bounds || !res ||
+      (n1 > 0 && (!kps_un1 || !desc1 || !points1 || !point_dist1 || !matches12)) ||
+      (n2 > 0 && (!kps_un2 || !desc2 || !points2 || !point_dist2)) || (mask1 == nullptr) != (mask2 == nullptr) ||
+      (point_desc1 == nullptr) != (point_desc2 == nullptr))
+    return ORBX_E_BADARG;
+  int r = refused(ctx, "match sim3", th, orb_dist < 0 || orb_dist > 256 ? "orb_dist outside [0, 256]" : nullptr, bounds, nullptr, nullptr);
+  if (r != ORBX_OK) return r;
+  const int cap = std::max(std::max(n1, n2), 1);
+  if (cap > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match sim3: more than ORBX_BOW_MAX_FEATURES features");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t *dD, *dPD, *dMask;
+  float *dP, *dDist, *dPose, *dSim;
+  int32_t *dN, *dM;
+  orbx_msim3_result* dR;
+  auto staging = [&](Layout L) {  // the two keyframes and their point sets in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dD = L.take<uint8_t>((size_t)2 * cap * 32);
+    dP = L.take<float>((size_t)2 * cap * 3);
+    dDist = L.take<float>((size_t)2 * cap * 2);
+    dPD = L.take<uint8_t>((size_t)2 * cap * 32);
+    dMask = L.take<uint8_t>((size_t)2 * cap);
+    dPose = L.take<float>(24);
+    dSim = L.take<float>(13);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dR = L.take<orbx_msim3_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dSim3Io.grow(bytes, st));
+  staging(Layout(s->dSim3Io));
+  HIPCHK(hipMemsetAsync(s->dSim3Io, 0, bytes, st));
+  const size_t c = (size_t)cap;
+  HIPCHK(up(dK, kps_un1, n1, st));
+  HIPCHK(up(dK + c, kps_un2, n2, st));
+  HIPCHK(up(dD, desc1, (size_t)n1 * 32, st));
+  HIPCHK(up(dD + c * 32, desc2, (size_t)n2 * 32, st));
+  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
+  HIPCHK(up(dP + c * 3, points2, (size_t)n2 * 3, st));
+  HIPCHK(up(dDist, point_dist1, (size_t)n1 * 2, st));
+  HIPCHK(up(dDist + c * 2, point_dist2, (size_t)n2 * 2, st));
+  if (point_desc1) {
+    HIPCHK(up(dPD, point_desc1, (size_t)n1 * 32, st));
+    HIPCHK(up(dPD + c * 32, point_desc2, (size_t)n2 * 32, st));
+  }
+  if (mask1) {
+    HIPCHK(up(dMask, mask1, n1, st));
+    HIPCHK(up(dMask + c, mask2, n2, st));
+  }
+  HIPCHK(up(dPose, pose1, 12, st));
+  HIPCHK(up(dPose + 12, pose2, 12, st));
+  HIPCHK(up(dSim, sim3, 13, st));
+  HIPCHK(up(dM, matches12, n1, st));
+  const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
+  HIPCHK(up(dN, hn, 2, st));
+  r = orbx_match_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dD, dN, cap, 2, dP, mask1 ? dMask : nullptr,
+                                   point_desc1 ? dPD : nullptr, dDist, dPose, dSim, K, bounds, th, orb_dist, dM, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(matches12, dM, n1, st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
 }  // extern "C"

@@ -63,16 +63,17 @@ ORBX_PNP_INL bool finite64(double x) { return (x - x) == 0.0; }
 ORBX_PNP_INL bool finite32(float x) { return (x - x) == 0.0f; }
 
 // ---- sampling: DUtils::Random::RandomInt(0, size - 1) on the caller's rand() values, and vAvailableIndices' swap-and-pop --------
-// Four draws change at most four entries of the list 0 .. N-1, so the changes are remembered instead of the list.  N >= 4.
-// Returns false (and picks nothing) when a draw lies outside [0, RAND_MAX].
-ORBX_PNP_INL bool sampleFour(const int32_t* draws, int N, int* sel) {
-  int pos[4], val[4];
+// K draws change at most K entries of the list 0 .. N-1, so the changes are remembered instead of the list.  N >= K.
+// Returns false (and picks nothing) when a draw lies outside [0, RAND_MAX].  (K = 4 here; 3 for orbx_sim3_math.inc.)
+template <int K>
+ORBX_PNP_INL bool sampleDraws(const int32_t* draws, int N, int* sel) {
+  int pos[K], val[K];
   bool ok = true;
 ORBX_PNP_UNROLL
-  for (int i = 0; i < 4; i++) ok = ok && draws[i] >= 0;  // (an int32 cannot exceed RAND_MAX)
+  for (int i = 0; i < K; i++) ok = ok && draws[i] >= 0;  // (an int32 cannot exceed RAND_MAX)
   if (!ok) return false;
 ORBX_PNP_UNROLL
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < K; i++) {
     const int size = N - i;
     const int randi = (int)(((double)draws[i] / ((double)PNP_RAND_MAX + 1.0)) * (double)size);
     int idx = randi, last = size - 1;
@@ -87,6 +88,7 @@ ORBX_PNP_UNROLL
   }
   return true;
 }
+ORBX_PNP_INL bool sampleFour(const int32_t* draws, int N, int* sel) { return sampleDraws<4>(draws, N, sel); }
 
 // ---- CheckInliers, one point: the reference's mixed types -----------------------------------------------------------------------
 ORBX_PNP_INL bool isInlier(const double* R, const double* t, const Corr& c, const Cam& K) {

@@ -1,7 +1,8 @@
 // orbx_pose.cpp — host side of what runs behind SearchByBoW: Optimizer::PoseOptimization (include/orbx.h, "behind SearchByBoW:
 // pose optimisation"; the kernel is in orbx_pose_kernel.hip) and, below it, PnPsolver, which gives a lost frame the start pose
-// ("behind SearchByBoW: PnP RANSAC"; orbx_pnp_kernel.hip).  For each: the argument checks, the problem list, the held tables and
-// the C entry points.
+// ("behind SearchByBoW: PnP RANSAC"; orbx_pnp_kernel.hip), and Sim3Solver, PnPsolver's 3D-3D sibling of loop closing ("loop
+// closing: Sim3 RANSAC"; orbx_sim3_kernel.hip).  For each: the argument checks, the problem list, the held tables and the C
+// entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -296,6 +297,206 @@ int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const floa
   }
   HIPCHK(down(res, dR, 1, st));
   HIPCHK(down(inliers, dI, n, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- Sim3Solver: SetRansacParameters' table, the workspace of the three launches and the C entry points -------------------------
+namespace {
+
+bool sim3ParamsOk(double probability, int minInliers, int maxIterations, float th2, int fixScale) {
+  return probability > 0.0 && probability < 1.0 && minInliers >= 3 && maxIterations >= 1 && th2 > 0.f && std::isfinite(th2) &&
+         (fixScale == 0 || fixScale == 1);
+}
+
+// SetRansacParameters for one N, with the design's expression types (include/orbx.h, rule 2)
+int32_t sim3RansacEntry(int N, double mRansacProb, int minInliers, int maxIterations) {
+  if (N < minInliers) return maxIterations;  // (the design takes log of a negative number; such a solver is bNoMore at once)
+  const float epsilon = (float)minInliers / N;
+  int nIterations;
+  if (minInliers == N) {
+    nIterations = 1;
+  } else {
+    const double it = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)epsilon, 3)));
+    nIterations = (it >= 1.0 && it < 2147483647.0) ? (int)it : (it < 1.0 ? 1 : maxIterations);
+  }
+  return std::max(1, std::min(nIterations, maxIterations));
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_sim3_ransac_table(double probability, int min_inliers, int max_iterations, int n_max, int32_t* out) {
+  if (!sim3ParamsOk(probability, min_inliers, max_iterations, 1.f, 0) || n_max < 0 || !out) return ORBX_E_BADARG;
+  for (int N = 0; N <= n_max; N++) out[N] = sim3RansacEntry(N, probability, min_inliers, max_iterations);
+  return ORBX_OK;
+}
+
+int orbx_sim3_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_kf1, const int32_t* h_kf2,
+                                 const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const int32_t* d_n,
+                                 int capacity, const int32_t* d_match, int n_point_sets, const float* d_points,
+                                 const uint8_t* d_point_mask, const float* d_pose, const float* K, const float* sigma2, int fix_scale,
+                                 double probability, int min_inliers, int max_iterations, float th2, int n_iter,
+                                 const int32_t* d_draws, orbx_sim3_result* d_res, float* d_sim3, int32_t* d_match_inliers,
+                                 uint8_t* d_inliers) {
+  if (n_frames < 0 || n_problems < 0 || n_point_sets < 0 || capacity < 1 || n_iter < 1 ||
+      (n_problems > 0 && (!h_kf1 || !h_kf2 || !h_set1 || !h_set2)) || !d_kps_un || !d_n || !d_match || !d_points || !d_pose || !K ||
+      !d_draws || !d_res || !d_sim3 || !d_match_inliers || !sim3ParamsOk(probability, min_inliers, max_iterations, th2, fix_scale))
+    return ORBX_E_BADARG;
+  if (!pairsInRange(h_kf1, h_kf2, n_problems, n_frames) || !pairsInRange(h_set1, h_set2, n_problems, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "sim3 solve: keyframe outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
+  if (capacity > SIM3_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "sim3 solve: capacity above ORBX_BOW_MAX_FEATURES");
+    return ORBX_E_CAPACITY;
+  }
+  if ((long long)n_problems * n_iter > SIM3_MAX_HYPOTHESES) {  // (a lane each: the launch's grid)
+    if (ctx) ctxSetError(ctx, "sim3 solve: n_problems * n_iter above 2^31 - 64");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_problems == 0) return ORBX_OK;
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  Sim3Scratch* s = ctxSim3(ctx);
+  hipStream_t st = ctxStream(ctx);
+  int nLevels = 0;
+  const float* own = ctxSigma2(ctx, &nLevels);
+  const float* sig = sigma2 ? sigma2 : own;
+  // the table of these parameters up to this capacity (computed again only when they change)
+  const size_t tableLen = (size_t)capacity + 1;
+  if (s->hTable.size() != tableLen || s->keyProbability != probability || s->keyMinInliers != min_inliers ||
+      s->keyMaxIterations != max_iterations) {
+    s->hTable.resize(tableLen);
+    (void)orbx_sim3_ransac_table(probability, min_inliers, max_iterations, capacity, s->hTable.data());
+    s->keyProbability = probability;
+    s->keyMinInliers = min_inliers;
+    s->keyMaxIterations = max_iterations;
+  }
+  // the workspace of the three launches
+  Sim3Args a{};
+  auto workspace = [&](Layout L) {
+    a.corr = L.take<uint8_t>((size_t)n_problems * capacity * SIM3_CORR_BYTES);
+    a.corrOf = L.take<int32_t>((size_t)n_problems * capacity);
+    a.meta = L.take<int32_t>((size_t)n_problems * 4);
+    a.hyp = L.take<uint8_t>((size_t)n_problems * n_iter * SIM3_HYP_BYTES);
+    return L.size();
+  };
+  const size_t bytes = workspace(Layout());
+  // the lists and the tables go up only when they differ from the last call's; such a call first waits for the context stream,
+  // as orbx_pnp_solve_batch_device does (include/orbx.h)
+  std::vector<int32_t> lists;
+  lists.reserve((size_t)4 * n_problems);
+  for (const int32_t* c : {h_kf1, h_kf2, h_set1, h_set2}) lists.insert(lists.end(), c, c + n_problems);
+  const bool sameList = s->problems.holds(lists.data(), lists.size()), sameSigma = s->sigma2.holds(sig, nLevels),
+             sameTable = s->table.holds(s->hTable.data(), tableLen);
+  if (!sameList || !sameSigma || !sameTable) HIPCHK(hipStreamSynchronize(st));
+  if (!sameList) HIPCHK(s->problems.replace(st, lists.data(), lists.size()));
+  if (!sameSigma) HIPCHK(s->sigma2.replace(st, sig, nLevels));
+  if (!sameTable) HIPCHK(s->table.replace(st, s->hTable.data(), tableLen));
+  HIPCHK(s->dWork.grow(bytes, st));
+  workspace(Layout(s->dWork));
+  a.kps = d_kps_un;
+  a.nKps = d_n;
+  a.problems = s->problems;
+  a.match = d_match;
+  a.points = d_points;
+  a.mask = d_point_mask;
+  a.pose = d_pose;
+  a.sigma2 = s->sigma2;
+  a.table = s->table;
+  a.draws = d_draws;
+  a.res = d_res;
+  a.sim3 = d_sim3;
+  a.matchInliers = d_match_inliers;
+  a.inliers = d_inliers;
+  a.fx = K[0];
+  a.fy = K[4];
+  a.cx = K[2];
+  a.cy = K[5];
+  a.th2 = th2;
+  a.nProblems = n_problems;
+  a.cap = capacity;
+  a.nLevels = nLevels;
+  a.nIter = n_iter;
+  a.minInliers = min_inliers;
+  a.fixScale = fix_scale;
+  HIPCHK(launch_sim3_prep(st, a));
+  HIPCHK(launch_sim3_hypotheses(st, a));
+  HIPCHK(launch_sim3_resolve(st, a));
+  return ORBX_OK;
+}
+
+int orbx_sim3_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* points1, const uint8_t* mask1,
+                    const float* pose1, const orbx_keypoint* kps_un2, int n2, const float* points2, const uint8_t* mask2,
+                    const float* pose2, const int32_t* match12, const float* K, const float* sigma2, int fix_scale,
+                    double probability, int min_inliers, int max_iterations, float th2, int n_iter, const int32_t* draws,
+                    orbx_sim3_result* res, float* sim3, int32_t* match_inliers, uint8_t* inliers) {
+  if (n1 < 0 || n2 < 0 || n_iter < 1 || !pose1 || !pose2 || !K || !draws || !res || !sim3 ||
+      (n1 > 0 && (!kps_un1 || !points1 || !match12 || !match_inliers)) || (n2 > 0 && (!kps_un2 || !points2)) ||
+      (mask1 == nullptr) != (mask2 == nullptr) || !sim3ParamsOk(probability, min_inliers, max_iterations, th2, fix_scale))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(n1, n2), 1);
+  if (cap > SIM3_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "sim3 solve: more than ORBX_BOW_MAX_FEATURES keypoints");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  Sim3Scratch* s = ctxSim3(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  int32_t *dN, *dMatch, *dDraws, *dRow;
+  float *dP, *dPose, *dSim;
+  uint8_t *dM, *dI;
+  orbx_sim3_result* dR;
+  auto staging = [&](Layout L) {  // two frames and two point sets in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dN = L.take<int32_t>(2);
+    dP = L.take<float>((size_t)2 * cap * 3);
+    dM = L.take<uint8_t>((size_t)2 * cap);
+    dPose = L.take<float>(24);
+    dMatch = L.take<int32_t>(cap);
+    dDraws = L.take<int32_t>((size_t)n_iter * 3);
+    dSim = L.take<float>(13);
+    dRow = L.take<int32_t>(cap);
+    dI = L.take<uint8_t>(cap);
+    dR = L.take<orbx_sim3_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dIo.grow(bytes, st));
+  staging(Layout(s->dIo));
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
+  HIPCHK(up(dK, kps_un1, n1, st));
+  HIPCHK(up(dK + cap, kps_un2, n2, st));
+  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
+  HIPCHK(up(dP + (size_t)cap * 3, points2, (size_t)n2 * 3, st));
+  if (mask1) {
+    HIPCHK(up(dM, mask1, n1, st));
+    HIPCHK(up(dM + cap, mask2, n2, st));
+  }
+  HIPCHK(up(dN, hn, 2, st));
+  HIPCHK(up(dPose, pose1, 12, st));
+  HIPCHK(up(dPose + 12, pose2, 12, st));
+  HIPCHK(up(dMatch, match12, n1, st));
+  HIPCHK(up(dDraws, draws, (size_t)n_iter * 3, st));
+  r = orbx_sim3_solve_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dN, cap, dMatch, 2, dP, mask1 ? dM : nullptr, dPose, K, sigma2,
+                                   fix_scale, probability, min_inliers, max_iterations, th2, n_iter, dDraws, dR, dSim, dRow, dI);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(down(sim3, dSim, 13, st));
+  HIPCHK(down(match_inliers, dRow, n1, st));
+  if (inliers) HIPCHK(down(inliers, dI, n1, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
