@@ -14,6 +14,8 @@ import tempfile
 
 import numpy as np
 
+from pose_ref_lib import K_ANISO, MOTION_2, NLEVELS_2, ROLL, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "ba_ref.cpp")
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -33,14 +35,12 @@ NLEVELS = 8
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="ba_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libba_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("ba_ref.cpp does not compile:\n" + p.stdout)
@@ -52,8 +52,14 @@ def lib() -> ctypes.CDLL:
     L.bar_sincos.argtypes = [f64, ctypes.POINTER(f64), ctypes.POINTER(f64)]
     L.bar_sincos.restype = None
     L.bar_huber_delta.restype = f64
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -210,7 +216,8 @@ def rotvec(w):
 
 
 def make_pair(n, seed=0, cap=None, noise=0.5, outliers=0, twist=(0.004, -0.003, 0.002, 0.01, -0.008, 0.006), point_noise=0.02,
-              pose_scale=1.0, mirrored=False, extra=5, nlevels=NLEVELS, motion=((0.02, -0.05, 0.01), (-0.3, 0.02, 0.05))):
+              pose_scale=1.0, mirrored=False, extra=5, nlevels=NLEVELS, motion=((0.02, -0.05, 0.01), (-0.3, 0.02, 0.05)), K=K0,
+              scale_factor=1.2):
     """A general scene of n triangulated matches seen from two frames: the true (R, t) and points, pixel noise (in units of the
     keypoint's level sigma), `outliers` gross mismatches, input points off by point_noise, and the input pose = the true one moved by
     the twist, its translation then multiplied by pose_scale.  Frame 1 holds `extra` keypoints without a match and `extra` matched but
@@ -218,9 +225,9 @@ def make_pair(n, seed=0, cap=None, noise=0.5, outliers=0, twist=(0.004, -0.003, 
     rng = np.random.default_rng(1000 + seed)
     Rt, tt = rotvec(motion[0]), np.array(motion[1], np.float64)
     X = np.c_[rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4, 8, n)]
-    Kd = K0.astype(np.float64)
+    Kd = np.asarray(K, np.float64).reshape(3, 3)
     octs = rng.integers(0, nlevels, (n, 2))
-    sigma = 1.2 ** octs
+    sigma = scale_factor ** octs
 
     def proj(P):
         return np.c_[P[:, 0] / P[:, 2] * Kd[0, 0] + Kd[0, 2], P[:, 1] / P[:, 2] * Kd[1, 1] + Kd[1, 2]]
@@ -254,7 +261,7 @@ def make_pair(n, seed=0, cap=None, noise=0.5, outliers=0, twist=(0.004, -0.003, 
     init = np.zeros(1, INIT_RESULT_DTYPE)
     init["model"], init["R21"][0], init["t21"][0] = 1, Rin, sign * tin
     truth = dict(R=Rt, t=sign * tt, X=sign * X, slots1=slots1, obs1=o1, obs2=o2, octs=octs)
-    return Pair(k1, n1, k2, n2, m12, init, p3d, tri, K0.reshape(9).copy(), truth)
+    return Pair(k1, n1, k2, n2, m12, init, p3d, tri, np.asarray(K, np.float32).reshape(9).copy(), truth)
 
 
 def skipped(pair: Pair, status=16) -> Pair:
@@ -307,16 +314,35 @@ def one_level_table(level=3):
     return t
 
 
+def inv_sigma2_of(setting_name: str):
+    """The inv_sigma2 table of a setting's pyramid: None (the default table) for the first."""
+    return None if setting_name == "first" else inv_sigma2_table(NLEVELS_2, SCALE_FACTOR_2)
+
+
+# frame 2 rolled by 89 degrees against frame 1 (pose_ref_lib.ROLL), the baseline as in the first setting
+MOTION_ROLL = (ROLL, (-0.3, 0.02, 0.05))
+# the named pairs that exist under the second setting as well (world(name, "second")): smaller, with seeds of their own
+SECOND_WORLDS = {"general": lambda: make_pair(120, 101, motion=MOTION_ROLL, **SECOND),
+                 "huber": lambda: make_pair(110, 103, outliers=8, motion=MOTION_ROLL, **SECOND),
+                 "few": lambda: make_pair(40, 105, motion=MOTION_ROLL, **SECOND),
+                 "truth": lambda: make_pair(150, 111, noise=0.2, twist=(0.02, -0.015, 0.01, 0.05, -0.04, 0.03), motion=MOTION_ROLL, **SECOND)}
 _worlds = {}
 
 
-def world(name: str) -> Pair:
-    """Named pairs, made once.  general: converges; rejecting: the input translation 30 times too long and gross
+def world(name: str, setting_name: str = "first") -> Pair:
+    """Named pairs, made once.  setting_name "second": the pair of that name in SECOND_WORLDS (K_ANISO, 5 levels of 1.37, frame 2
+    rolled by 89 degrees), for the table inv_sigma2_of("second").
+
+    general: converges; rejecting: the input translation 30 times too long and gross
     mismatches (rejected trials); huber:
     gross mismatches; converged: general's result fed back (the small-theta branch); mirrored: negative depths; few: 40 points; truth: little pixel noise, an input pose
     1.5 degrees and 11 degrees (translation direction) off; no_weight: general with every keypoint at the last level, for
     top_level_off_table() -- every edge weighs nothing, as under a table of zeros, in a call whose other pairs keep their weights
     (a call has one table)."""
+    if setting_name != "first":
+        if (name, setting_name) not in _worlds:
+            _worlds[name, setting_name] = SECOND_WORLDS[name]()
+        return _worlds[name, setting_name]
     if name not in _worlds:
         if name == "general":
             w = make_pair(300, 1)

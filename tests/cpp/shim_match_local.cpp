@@ -20,7 +20,7 @@ struct Frame {
   std::vector<uint8_t> mDescriptors;
   int N = 0;
   ORBextractor* mpORBextractor = nullptr;
-  float mK[9] = {520.f, 0.f, 320.f, 0.f, 520.f, 240.f, 0.f, 0.f, 1.f};
+  float mK[9] = {517.25f, 0.f, 318.75f, 0.f, 388.5f, 255.5f, 0.f, 0.f, 1.f};
   static int mnMinX, mnMaxX, mnMinY, mnMaxY;
 };
 int Frame::mnMinX = 0, Frame::mnMaxX = 640, Frame::mnMinY = 0, Frame::mnMaxY = 480;
@@ -46,7 +46,7 @@ int main(int argc, char** argv) {
   std::vector<int> entry, truth;  // per feature: the point it has on entry (-1 none), the point it shows
   for (int i = 0; i < n; i++) {
     const double z = uniform(3, 15) * (i % 11 == 3 ? -1 : 1), u = uniform(-150, 790), v = uniform(-100, 580);
-    const double Y[3] = {(u - 320) / 520 * z, (v - 240) / 520 * z, z};
+    const double Y[3] = {(u - 318.75) / 517.25 * z, (v - 255.5) / 388.5 * z, z};
     double X[3], PO[3], d = 0;  // X = R^T (Y - t)
     for (int c = 0; c < 3; c++) X[c] = R[0][c] * (Y[0] - t[0]) + R[1][c] * (Y[1] - t[1]) + R[2][c] * (Y[2] - t[2]);
     for (int c = 0; c < 3; c++) { PO[c] = X[c] - Ow[c]; d += PO[c] * PO[c]; }

@@ -18,7 +18,7 @@ using namespace ORB_SLAM_Tracking;
 struct Frame {
   std::vector<KeyPointT> mvKeysUn;
   ORBextractor* mpORBextractor = nullptr;
-  float mK[9] = {520.f, 0.f, 320.f, 0.f, 520.f, 240.f, 0.f, 0.f, 1.f};
+  float mK[9] = {517.25f, 0.f, 318.75f, 0.f, 388.5f, 255.5f, 0.f, 0.f, 1.f};
 };
 
 static double uniform(double lo, double hi) { return lo + (hi - lo) * (rand() / (double)RAND_MAX); }
@@ -41,8 +41,8 @@ int main(int argc, char** argv) {
     KeyPointT& k = F.mvKeysUn[i];
     k.octave = rand() % 8;
     const double s = std::pow(1.2, k.octave), off = i < planted ? 30 * s : 0;  // (the first features are gross mismatches)
-    k.pt.x = (float)(520 * Y[0] / Y[2] + 320 + uniform(-0.5, 0.5) * s + off);
-    k.pt.y = (float)(520 * Y[1] / Y[2] + 240 + uniform(-0.5, 0.5) * s - off);
+    k.pt.x = (float)(517.25 * Y[0] / Y[2] + 318.75 + uniform(-0.5, 0.5) * s + off);
+    k.pt.y = (float)(388.5 * Y[1] / Y[2] + 255.5 + uniform(-0.5, 0.5) * s - off);
     vP3D[i].x = (float)X[0];
     vP3D[i].y = (float)X[1];
     vP3D[i].z = (float)X[2];

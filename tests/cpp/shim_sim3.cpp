@@ -21,7 +21,7 @@ using namespace ORB_SLAM_Tracking;
 struct KeyFrame {
   std::vector<KeyPointT> mvKeysUn;
   ORBextractor* mpORBextractor = nullptr;
-  float mK[9] = {520.f, 0.f, 320.f, 0.f, 520.f, 240.f, 0.f, 0.f, 1.f};
+  float mK[9] = {517.25f, 0.f, 318.75f, 0.f, 388.5f, 255.5f, 0.f, 0.f, 1.f};
 };
 
 static double uniform(double lo, double hi) { return lo + (hi - lo) * (rand() / (double)RAND_MAX); }
@@ -63,10 +63,10 @@ int main(int argc, char** argv) {
     vP3D2[j].z = (float)(Y2[2] + uniform(-0.002, 0.002));
     const int level = rand() % 8;
     KF1.mvKeysUn[i].octave = KF2.mvKeysUn[j].octave = level;
-    KF1.mvKeysUn[i].pt.x = (float)(520 * Y1[0] / Y1[2] + 320);
-    KF1.mvKeysUn[i].pt.y = (float)(520 * Y1[1] / Y1[2] + 240);
-    KF2.mvKeysUn[j].pt.x = (float)(520 * Y2[0] / Y2[2] + 320);
-    KF2.mvKeysUn[j].pt.y = (float)(520 * Y2[1] / Y2[2] + 240);
+    KF1.mvKeysUn[i].pt.x = (float)(517.25 * Y1[0] / Y1[2] + 318.75);
+    KF1.mvKeysUn[i].pt.y = (float)(388.5 * Y1[1] / Y1[2] + 255.5);
+    KF2.mvKeysUn[j].pt.x = (float)(517.25 * Y2[0] / Y2[2] + 318.75);
+    KF2.mvKeysUn[j].pt.y = (float)(388.5 * Y2[1] / Y2[2] + 255.5);
     std::memcpy(&desc2[(size_t)j * 32], &desc1[(size_t)i * 32], 32);
     const double d1 = std::sqrt(Y1[0] * Y1[0] + Y1[1] * Y1[1] + Y1[2] * Y1[2]), d2 = std::sqrt(Y2[0] * Y2[0] + Y2[1] * Y2[1] + Y2[2] * Y2[2]);
     dist1[2 * i] = (float)(0.3 * d2);

@@ -20,7 +20,7 @@ static double uniform(double lo, double hi) { return lo + (hi - lo) * (rand() / 
 int main(int argc, char** argv) {
   srand(argc > 1 ? atoi(argv[1]) : 0);
   const int n = 300;
-  const float K[9] = {520.f, 0.f, 320.f, 0.f, 520.f, 240.f, 0.f, 0.f, 1.f};
+  const float K[9] = {517.25f, 0.f, 318.75f, 0.f, 388.5f, 255.5f, 0.f, 0.f, 1.f};
   ORBextractor extractor(1000, 1.2f, 8, 20, 7);
   // KF1 at the origin; KF2 turned by a about y, its centre at C
   const double a = 0.05, R[3][3] = {{std::cos(a), 0, std::sin(a)}, {0, 1, 0}, {-std::sin(a), 0, std::cos(a)}}, C[3] = {0.7, 0.05, 0.1};
@@ -39,8 +39,8 @@ int main(int argc, char** argv) {
   std::vector<int> level;
   for (int i = 0; i < n; i++) {
     const double z = uniform(3, 9), u = uniform(20, 620), v = uniform(20, 460);
-    pts.push_back((u - 320) / 520 * z);
-    pts.push_back((v - 240) / 520 * z);
+    pts.push_back((u - 318.75) / 517.25 * z);
+    pts.push_back((v - 255.5) / 388.5 * z);
     pts.push_back(z);
     level.push_back(rand() % 4);
     KeyPointT k;
@@ -57,7 +57,7 @@ int main(int argc, char** argv) {
     const int i = order[q];
     double Y[3];
     for (int r = 0; r < 3; r++) Y[r] = R[r][0] * (pts[3 * i] - C[0]) + R[r][1] * (pts[3 * i + 1] - C[1]) + R[r][2] * (pts[3 * i + 2] - C[2]);
-    const double u = 520 * Y[0] / Y[2] + 320, v = 520 * Y[1] / Y[2] + 240;
+    const double u = 517.25 * Y[0] / Y[2] + 318.75, v = 388.5 * Y[1] / Y[2] + 255.5;
     if (Y[2] < 0.5 || u < 2 || u > 638 || v < 2 || v > 478) continue;  // (KF2 does not see it)
     KeyPointT k;
     k.pt.x = (float)u;

@@ -18,6 +18,7 @@ import tempfile
 import numpy as np
 
 import match_proj_ref_lib as M
+from pose_ref_lib import K_ANISO, NLEVELS_2, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "match_kfproj_ref.cpp")
@@ -32,14 +33,12 @@ f32 = np.float32
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="match_kfproj_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libmatch_kfproj_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("match_kfproj_ref.cpp does not compile:\n" + p.stdout)
@@ -49,8 +48,14 @@ def lib() -> ctypes.CDLL:
     L.kpr_search_by_projection.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, fl, i32, i32, vp, vp, vp, vp, vp,
                                            vp, vp]
     L.kpr_search_by_projection.restype = None
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -226,20 +231,20 @@ def _none_frame():
     return np.zeros(0, KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8)
 
 
-def _distances(pts, pose, level, rng=None):
-    """(min, max) distances such that the table PredictScale gives `level` (an entry NLEVELS is beyond the table: clamped)."""
-    scale = scale_table()
+def _distances(pts, pose, level, rng=None, scale_factor=1.2, nlevels=NLEVELS):
+    """(min, max) distances such that the table PredictScale gives `level` (an entry nlevels is beyond the table: clamped)."""
+    scale = scale_table(nlevels, scale_factor)
     R, t = pose[:9].reshape(3, 3).astype(np.float64), pose[9:].astype(np.float64)
     dist = np.linalg.norm(pts.astype(np.float64) - (-R.T @ t), axis=1)
     level = np.broadcast_to(np.asarray(level), dist.shape)
     jitter = 0.93 if rng is None else rng.uniform(0.86, 0.99, len(dist))
-    maxd = dist * np.where(level == 0, 1.0, scale[np.minimum(level, NLEVELS - 1)].astype(np.float64)) * jitter
-    maxd = np.where(level == NLEVELS, dist * float(scale[-1]) * 1.3, maxd)
+    maxd = dist * np.where(level == 0, 1.0, scale[np.minimum(level, nlevels - 1)].astype(np.float64)) * jitter
+    maxd = np.where(level == nlevels, dist * float(scale[-1]) * 1.3, maxd)
     return dist, np.stack([maxd / float(scale[-1]), maxd], 1)
 
 
 def make_world(n_k, seed, bounds=BOUNDS, th=10.0, orb_dist=100, ori=True, n_extra=None, edge_cases=True, have=0.3, with_point_desc=False,
-               with_outlier=True):
+               with_outlier=True, K=None, scale_factor=1.2, nlevels=NLEVELS, roll_deg=0.0):
     """A keyframe of n_k features with map points: projections all over the bounds and a margin that leaves about a fifth outside,
     8% behind the camera (they project inside all the same), every level of the table, a tenth nearer than 0.8 times the minimal
     or farther than 1.2 times the maximal distance, 90% of the mask set, 12% twins of an earlier point (the same position, a
@@ -249,15 +254,16 @@ def make_world(n_k, seed, bounds=BOUNDS, th=10.0, orb_dist=100, ori=True, n_extr
     that bins lose; unrelated features; features outside the grid.  The frame already has a share `have` of the points its
     features show, and a few for unrelated features; 15% of these entries are outliers."""
     rng = np.random.default_rng(seed)
-    K, pose = camera(bounds), pose_of(seed + 1)
-    kk = _keypoints(n_k, rng)
+    K, pose = camera(bounds) if K is None else np.asarray(K, np.float32).reshape(9), pose_of(seed + 1, roll_deg)
+    scale = scale_table(nlevels, scale_factor)
+    kk = _keypoints(n_k, rng, nlevels=nlevels)
     dk = rng.integers(0, 256, (n_k, 32), dtype=np.uint8)
     w_, h_ = bounds[1] - bounds[0], bounds[3] - bounds[2]
     uv = np.stack([rng.uniform(bounds[0] - 0.06 * w_, bounds[1] + 0.06 * w_, n_k), rng.uniform(bounds[2] - 0.06 * h_, bounds[3] + 0.06 * h_, n_k)], 1)
     depth = rng.uniform(2.0, 10.0, n_k)
     depth[rng.random(n_k) < 0.08] *= -1.0
     pts = points_seen_at(pose, K, uv, depth)
-    dist, dists = _distances(pts, pose, rng.integers(0, NLEVELS + 1, n_k), rng)
+    dist, dists = _distances(pts, pose, rng.integers(0, nlevels + 1, n_k), rng, scale_factor, nlevels)
     far = rng.random(n_k)
     dists[:, 0] = np.where(far < 0.05, dist * 1.3, dists[:, 0])
     dists[:, 1] = np.where((far >= 0.05) & (far < 0.10), dist / 1.3, dists[:, 1])
@@ -269,7 +275,7 @@ def make_world(n_k, seed, bounds=BOUNDS, th=10.0, orb_dist=100, ori=True, n_extr
     pdesc = np.stack([_flip(d, rng.integers(0, 9), rng) for d in dk]) if with_point_desc and n_k else None
     src_desc = dk if pdesc is None else pdesc
     none_k, none_d = _none_frame()
-    proj = search_by_projection(World(kk, dk, none_k, none_d, pts, dists, None, pose, K, bounds, th, orb_dist, ori))["proj"]
+    proj = search_by_projection(World(kk, dk, none_k, none_d, pts, dists, None, pose, K, bounds, th, orb_dist, ori, scale=scale))["proj"]
     feats, descs, shows = [], [], []
 
     def feature(x, y, octave, desc, shown, angle):
@@ -303,9 +309,9 @@ def make_world(n_k, seed, bounds=BOUNDS, th=10.0, orb_dist=100, ori=True, n_extr
                 feature(x, v, int(proj[i, 3]), _flip(src_desc[i], 20 + len(edge) % 7, rng), -1, f32((float(kk["angle"][i]) - 40.0) % 360.0))
                 edge.append((int(i), len(feats) - 1, inside))
     n_extra = n_k // 8 if n_extra is None else n_extra
-    extra = _keypoints(n_extra, rng)
+    extra = _keypoints(n_extra, rng, nlevels=nlevels)
     extra["x"], extra["y"] = rng.uniform(bounds[0], bounds[1], n_extra), rng.uniform(bounds[2], bounds[3], n_extra)
-    outside = _keypoints(6, rng)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
+    outside = _keypoints(6, rng, nlevels=nlevels)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
     outside["x"] = np.array([bounds[0] - 40.0, bounds[1] + 40.0, 100.0, 200.0, np.nan, bounds[1] + 4.0], np.float32)
     outside["y"] = np.array([100.0, 100.0, bounds[2] - 40.0, bounds[3] + 40.0, 50.0, bounds[3] + 4.0], np.float32)
     kc = np.concatenate(feats + [extra, outside])
@@ -321,7 +327,7 @@ def make_world(n_k, seed, bounds=BOUNDS, th=10.0, orb_dist=100, ori=True, n_extr
     inv = np.empty_like(perm)
     inv[perm] = np.arange(len(perm))
     w = World(kk, dk, kc[perm], dc[perm], pts, dists, mask, pose, K, bounds, th, orb_dist, ori, pdesc, matches[perm],
-              None if outlier is None else outlier[perm])
+              None if outlier is None else outlier[perm], scale=scale)
     w.edge = [(i, int(inv[j]), inside) for i, j, inside in edge]
     w.shows = shows[perm]  # per feature: the point it was built around, or -1
     return w
@@ -388,11 +394,16 @@ def order_world():
     return World(kk, dk, kc, np.stack([A, B]), pts, dists, None, EYE, K, th=15.0)
 
 
+# the second setting: K_ANISO, 5 levels of 1.37, the pose rolled by 89 degrees; 150 features, and 310 under the offset bounds
+WORLDS_2 = ("w150@2", "w310_bounds@2")
+TWO = dict(roll_deg=89.0, **SECOND)
 WORLDS = ("main", "main_th3", "bounds", "pdesc", "w700", "contention", "order", "empty_frame", "empty_keyframe")
 _worlds = {}
 
 
 def world(name: str) -> World:
+    if name not in _worlds and name in WORLDS_2:
+        _worlds[name] = make_world(150, 101, **TWO) if name == "w150@2" else make_world(310, 104, bounds=(-12, 655, -9, 490), **TWO)
     if name not in _worlds:
         none_k, none_d = _none_frame()
         if name == "main":

@@ -16,6 +16,7 @@ import tempfile
 import numpy as np
 
 import match_proj_ref_lib as M
+from pose_ref_lib import K_ANISO, NLEVELS_2, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "match_local_ref.cpp")
@@ -32,14 +33,12 @@ f32 = np.float32
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="match_local_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libmatch_local_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("match_local_ref.cpp does not compile:\n" + p.stdout)
@@ -50,8 +49,14 @@ def lib() -> ctypes.CDLL:
     L.mlr_predict_scale.restype = None
     L.mlr_search_local_points.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, fl, fl, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mlr_search_local_points.restype = None
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -222,13 +227,13 @@ def _none_frame():
     return np.zeros(0, KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8)
 
 
-def make_map(n, seed, pose, K, bounds=BOUNDS, in_view=0.6):
+def make_map(n, seed, pose, K, bounds=BOUNDS, in_view=0.6, scale_factor=1.2, nlevels=NLEVELS):
     """n map points: projections all over the bounds and a margin that leaves about a fifth outside, 8% behind the camera; the
     normal the viewing direction turned by 0 to 3 degrees (viewCos > 0.998), 10 to 55 degrees or, for a seventh, 65 to 120
     degrees; the maximal distance such that every level of the table comes out, a tenth of the points nearer than 0.8 times the
     minimal or farther than 1.2 times the maximal distance; 90% of the mask set."""
     rng = np.random.default_rng(seed)
-    scale = scale_table()
+    scale = scale_table(nlevels, scale_factor)
     w_, h_ = bounds[1] - bounds[0], bounds[3] - bounds[2]
     m = 0.5 * (1.0 / math.sqrt(in_view + 0.2) - 1.0)
     uv = np.stack([rng.uniform(bounds[0] - m * w_, bounds[1] + m * w_, n), rng.uniform(bounds[2] - m * h_, bounds[3] + m * h_, n)], 1)
@@ -244,9 +249,9 @@ def make_map(n, seed, pose, K, bounds=BOUNDS, in_view=0.6):
     perp = np.cross(dirs, rng.normal(size=(n, 3)))
     perp /= np.linalg.norm(perp, axis=1)[:, None]
     normals = np.cos(ang)[:, None] * dirs + np.sin(ang)[:, None] * perp
-    level = rng.integers(0, NLEVELS + 1, n)  # (the last one is beyond the table: clamped)
-    maxd = dist * np.where(level == 0, 1.0, scale[np.minimum(level, NLEVELS - 1)].astype(np.float64)) * rng.uniform(0.86, 0.99, n)
-    maxd[level == NLEVELS] = dist[level == NLEVELS] * float(scale[-1]) * 1.3
+    level = rng.integers(0, nlevels + 1, n)  # (the last one is beyond the table: clamped)
+    maxd = dist * np.where(level == 0, 1.0, scale[np.minimum(level, nlevels - 1)].astype(np.float64)) * rng.uniform(0.86, 0.99, n)
+    maxd[level == nlevels] = dist[level == nlevels] * float(scale[-1]) * 1.3
     mind = maxd / float(scale[-1])
     far = rng.random(n)
     mind = np.where(far < 0.05, dist * 1.3, mind)
@@ -256,17 +261,19 @@ def make_map(n, seed, pose, K, bounds=BOUNDS, in_view=0.6):
     return pts, normals.astype(np.float32), np.stack([mind, maxd], 1).astype(np.float32), mdesc, mask
 
 
-def make_world(n_m, seed, bounds=BOUNDS, th=1.0, nnratio=0.8, n_extra=None, edge_cases=True, in_view=0.6, have=0.3):
+def make_world(n_m, seed, bounds=BOUNDS, th=1.0, nnratio=0.8, n_extra=None, edge_cases=True, in_view=0.6, have=0.3,
+               K=None, scale_factor=1.2, nlevels=NLEVELS, roll_deg=0.0):
     """A map of n_m points (make_map) and a frame built around the projections of those in view: for three quarters of them a
     feature within 0.2, 0.9 or 1.5 window radii, its octave the predicted level or off by one or two, its descriptor the point's
     with 0 to 60 bits flipped (a tenth: 105 to 140, beyond TH_HIGH); for a quarter of those a second feature of the same octave
     with a descriptor as near (what the ratio test rejects); unrelated features; features outside the grid.  The frame already
     has a share `have` of the points its features show, and a few it has no window for; 15% of these entries are outliers."""
     rng = np.random.default_rng(seed)
-    K, pose = camera(bounds), pose_of(seed + 1)
-    pts, normals, dists, mdesc, mask = make_map(n_m, seed + 2, pose, K, bounds, in_view)
+    K, pose = camera(bounds) if K is None else np.asarray(K, np.float32).reshape(9), pose_of(seed + 1, roll_deg)
+    scale = scale_table(nlevels, scale_factor)
+    pts, normals, dists, mdesc, mask = make_map(n_m, seed + 2, pose, K, bounds, in_view, scale_factor, nlevels)
     none_k, none_d = _none_frame()
-    proj = search_local_points(World(none_k, none_d, pts, normals, dists, mdesc, None, pose, K, bounds, th, nnratio))["proj"]
+    proj = search_local_points(World(none_k, none_d, pts, normals, dists, mdesc, None, pose, K, bounds, th, nnratio, scale=scale))["proj"]
     feats, descs, shows = [], [], []
 
     def feature(x, y, octave, desc, shown):
@@ -302,9 +309,9 @@ def make_world(n_m, seed, bounds=BOUNDS, th=1.0, nnratio=0.8, n_extra=None, edge
                 feature(x, v, int(proj[i, 3]), _flip(mdesc[i], 20 + len(edge) % 7, rng), -1)
                 edge.append((int(i), len(feats) - 1, inside))
     n_extra = n_m // 8 if n_extra is None else n_extra
-    extra = _keypoints(n_extra, rng)
+    extra = _keypoints(n_extra, rng, nlevels=nlevels)
     extra["x"], extra["y"] = rng.uniform(bounds[0], bounds[1], n_extra), rng.uniform(bounds[2], bounds[3], n_extra)
-    far = _keypoints(6, rng)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
+    far = _keypoints(6, rng, nlevels=nlevels)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
     far["x"] = np.array([bounds[0] - 40.0, bounds[1] + 40.0, 100.0, 200.0, np.nan, bounds[1] + 4.0], np.float32)
     far["y"] = np.array([100.0, 100.0, bounds[2] - 40.0, bounds[3] + 40.0, 50.0, bounds[3] + 4.0], np.float32)
     kf = np.concatenate(feats + [extra, far])
@@ -319,7 +326,8 @@ def make_world(n_m, seed, bounds=BOUNDS, th=1.0, nnratio=0.8, n_extra=None, edge
     perm = rng.permutation(len(kf))
     inv = np.empty_like(perm)
     inv[perm] = np.arange(len(perm))
-    w = World(kf[perm], df[perm], pts, normals, dists, mdesc, mask, pose, K, bounds, th, nnratio, matches[perm], outlier[perm])
+    w = World(kf[perm], df[perm], pts, normals, dists, mdesc, mask, pose, K, bounds, th, nnratio, matches[perm], outlier[perm],
+              scale=scale)
     w.edge = [(i, int(inv[j]), inside) for i, j, inside in edge]
     w.shows = shows[perm]  # per feature: the point it was built around, or -1
     return w
@@ -405,11 +413,16 @@ def order_world():
     return World(kf, np.stack([A, B]), pts, normals, dists, md, None, EYE, K)
 
 
+# the second setting: K_ANISO, 5 levels of 1.37, the pose rolled by 89 degrees; 150 features, and 310 under the offset bounds
+WORLDS_2 = ("w150@2", "w310_bounds@2")
+TWO = dict(roll_deg=89.0, **SECOND)
 WORLDS = ("main", "main_th5", "bounds", "w700", "w3000", "contention", "order", "empty_frame", "empty_map")
 _worlds = {}
 
 
 def world(name: str) -> World:
+    if name not in _worlds and name in WORLDS_2:
+        _worlds[name] = make_world(150, 101, **TWO) if name == "w150@2" else make_world(310, 104, bounds=(-12, 655, -9, 490), **TWO)
     if name not in _worlds:
         none_k, none_d = _none_frame()
         if name == "main":

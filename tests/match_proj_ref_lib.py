@@ -15,6 +15,8 @@ import tempfile
 
 import numpy as np
 
+from pose_ref_lib import K_ANISO, NLEVELS_2, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "match_proj_ref.cpp")
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -29,14 +31,12 @@ f32 = np.float32
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="match_proj_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libmatch_proj_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("match_proj_ref.cpp does not compile:\n" + p.stdout)
@@ -45,8 +45,14 @@ def lib() -> ctypes.CDLL:
     L.mpr_features_in_area.argtypes = [vp, i32, vp, fl, fl, fl, i32, i32, vp]
     L.mpr_search_by_projection.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, fl, i32, vp, vp, vp, vp, vp, vp]
     L.mpr_search_by_projection.restype = None
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -218,8 +224,9 @@ def camera(bounds=BOUNDS):
     return np.array([500.0, 0, (bounds[0] + bounds[1]) / 2.0, 0, 500.0, (bounds[2] + bounds[3]) / 2.0, 0, 0, 1], np.float32)
 
 
-def pose_of(seed):
-    """A small motion: a rotation of a few degrees about a random axis (f64 Rodrigues, stored f32) and a translation."""
+def pose_of(seed, roll_deg=0.0):
+    """A small motion: a rotation of a few degrees about a random axis (f64 Rodrigues, stored f32) and a translation.  roll_deg:
+    that rotation applied behind a roll about the optical axis (the second setting: 89 degrees)."""
     rng = np.random.default_rng(seed)
     wv = rng.normal(size=3)
     wv *= np.deg2rad(rng.uniform(1.0, 4.0)) / np.linalg.norm(wv)
@@ -227,6 +234,9 @@ def pose_of(seed):
     k = wv / th
     Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
     R = np.eye(3) + math.sin(th) * Kx + (1 - math.cos(th)) * Kx @ Kx
+    if roll_deg:
+        c, s = math.cos(math.radians(roll_deg)), math.sin(math.radians(roll_deg))
+        R = R @ np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
     return np.r_[R.reshape(9), rng.uniform(-0.2, 0.2, 3)].astype(np.float32)
 
 
@@ -237,11 +247,11 @@ def points_seen_at(pose, K, uv, depth):
     return ((xc - t) @ R).astype(np.float32)  # R^T (xc - t)
 
 
-def _keypoints(n, rng, octave=None):
+def _keypoints(n, rng, octave=None, nlevels=NLEVELS):
     k = np.zeros(n, KEYPOINT_DTYPE)
     k["x"], k["y"] = rng.uniform(0, 640, n), rng.uniform(0, 480, n)
     k["angle"] = rng.uniform(0.0, 360.0, n).astype(np.float32)
-    k["octave"] = rng.integers(0, NLEVELS, n) if octave is None else octave
+    k["octave"] = rng.integers(0, nlevels, n) if octave is None else octave
     k["size"], k["class_id"] = 31.0, -1
     return k
 
@@ -253,17 +263,18 @@ def _flip(desc, nbits, rng):
     return d
 
 
-def make_world(n, seed, bounds=BOUNDS, th=15.0, ori=True, n_extra=None, with_point_desc=False, with_outlier=True, edge_cases=True):
+def make_world(n, seed, bounds=BOUNDS, th=15.0, ori=True, n_extra=None, with_point_desc=False, with_outlier=True, edge_cases=True,
+               K=None, scale_factor=1.2, nlevels=NLEVELS, roll_deg=0.0):
     """n features in the last frame.  Their map points project all over the bounds and a margin around them, a tenth behind the
     camera; the current frame holds, in random order, for three quarters of the points a feature near the projection (0 to 3.5
     window radii away per axis, the octave off by 0, 1 or, rarely, 2; the descriptor the point's with 0 to 60 bits flipped; the
     angle the last frame's minus 40 degrees plus noise wide enough that bins lose), n_extra unrelated features, and features
     outside the grid.  With edge_cases a few features sit a hair inside and a hair outside the radius of a projection."""
     rng = np.random.default_rng(seed)
-    K, pose = camera(bounds), pose_of(seed + 1)
-    kl = _keypoints(n, rng)
+    K, pose = camera(bounds) if K is None else np.asarray(K, np.float32).reshape(9), pose_of(seed + 1, roll_deg)
+    kl = _keypoints(n, rng, nlevels=nlevels)
     if n >= 2:
-        kl["octave"][0], kl["octave"][1] = 0, NLEVELS - 1
+        kl["octave"][0], kl["octave"][1] = 0, nlevels - 1
     dl = rng.integers(0, 256, (n, 32), dtype=np.uint8)
     w_, h_ = bounds[1] - bounds[0], bounds[3] - bounds[2]
     uv = np.stack([rng.uniform(bounds[0] - 0.06 * w_, bounds[1] + 0.06 * w_, n), rng.uniform(bounds[2] - 0.06 * h_, bounds[3] + 0.06 * h_, n)], 1)
@@ -273,10 +284,10 @@ def make_world(n, seed, bounds=BOUNDS, th=15.0, ori=True, n_extra=None, with_poi
     mask = (rng.random(n) < 0.85).astype(np.uint8)
     outlier = (rng.random(n) < 0.05).astype(np.uint8) if with_outlier else None
     pdesc = np.stack([_flip(d, rng.integers(0, 9), rng) for d in dl]) if with_point_desc and n else None
-    scale = scale_table()
+    scale = scale_table(nlevels, scale_factor)
     # where the restatement projects them (the current frame plays no part in steps 2 and 3)
     none_k, none_d = np.zeros(0, KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8)
-    proj = search_by_projection(World(kl, dl, none_k, none_d, pts, None, pose, K, bounds, th, ori))["proj"]
+    proj = search_by_projection(World(kl, dl, none_k, none_d, pts, None, pose, K, bounds, th, ori, scale=scale))["proj"]
     feats, descs, truth = [], [], []
     src = dl if pdesc is None else pdesc
     for i in range(n):
@@ -310,9 +321,9 @@ def make_world(n, seed, bounds=BOUNDS, th=15.0, ori=True, n_extra=None, with_poi
                 truth.append(-1)
                 edge.append((int(i), len(feats) - 1, inside))
     n_extra = n // 4 if n_extra is None else n_extra
-    extra = _keypoints(n_extra, rng)
+    extra = _keypoints(n_extra, rng, nlevels=nlevels)
     extra["x"], extra["y"] = rng.uniform(bounds[0], bounds[1], n_extra), rng.uniform(bounds[2], bounds[3], n_extra)
-    far = _keypoints(min(6, n), rng)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
+    far = _keypoints(min(6, n), rng, nlevels=nlevels)  # outside the grid: beyond the bounds by more than a cell, and one that is no number
     far["x"] = np.array([bounds[0] - 40.0, bounds[1] + 40.0, 100.0, 200.0, np.nan, bounds[1] + 4.0], np.float32)[:len(far)]
     far["y"] = np.array([100.0, 100.0, bounds[2] - 40.0, bounds[3] + 40.0, 50.0, bounds[3] + 4.0], np.float32)[:len(far)]
     kc = np.concatenate(feats + [extra, far]) if feats or n_extra or len(far) else np.zeros(0, KEYPOINT_DTYPE)
@@ -407,6 +418,9 @@ def contention_world(n_clusters=40, seed=21):
     return World(kl, dl, kc[perm], np.array(dc, np.uint8)[perm], pts, None, pose, K, ori=False)
 
 
+# the second setting: K_ANISO, 5 levels of 1.37, the pose rolled by 89 degrees; 150 features, and 310 under the offset bounds
+WORLDS_2 = ("w150@2", "w310_bounds@2")
+TWO = dict(roll_deg=89.0, **SECOND)
 WORLDS = ("w300", "w300_noori", "w300_pdesc", "w310_bounds", "w1500", "w40_th30", "truth", "order", "contention", "empty_l", "empty_c")
 _worlds = {}
 
@@ -416,6 +430,10 @@ def world(name: str) -> World:
         none_k, none_d = np.zeros(0, KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8)
         if name == "w300":
             w = make_world(300, 1)
+        elif name == "w150@2":
+            w = make_world(150, 101, **TWO)
+        elif name == "w310_bounds@2":
+            w = make_world(310, 104, bounds=(-12, 655, -9, 490), **TWO)
         elif name == "w300_noori":
             w = make_world(300, 2, ori=False)
         elif name == "w300_pdesc":

@@ -411,12 +411,13 @@ def check_rt(R21, t21, K, k1, k2, matches12, inliers, th2=4.0):
     return int(n), good[:len(k1)].astype(bool), p3d[:len(k1)], np.float32(par.value)
 
 
-def two_view_case(seed=0, n=500, outliers=0.2, noise=0.5):
+def two_view_case(seed=0, n=500, outliers=0.2, noise=0.5, K=None):
     """Synthetic two-view geometry for CheckRT: 3-D points in front of camera 1, camera 2 = (R, t), pixel noise, a share of
     wrong matches, matches12 with holes.  Returns K, R, t (float64 truth), k1, k2, matches12 and the four (R, t) candidates
-    an essential-matrix decomposition yields (the true one first)."""
+    an essential-matrix decomposition yields (the true one first).  K: another camera than the default one, whose focal lengths
+    differ by 1e-4 only."""
     rng = np.random.default_rng(seed)
-    K = np.array([[609.2855, 0, 351.4274], [0, 609.3422, 237.7324], [0, 0, 1.0]])
+    K = np.array([[609.2855, 0, 351.4274], [0, 609.3422, 237.7324], [0, 0, 1.0]]) if K is None else np.asarray(K, np.float64).reshape(3, 3)
     ang = np.deg2rad(rng.uniform(2, 8, 3)) * rng.choice([-1, 1], 3)
     cx, sx, cy, sy, cz, sz = np.cos(ang[0]), np.sin(ang[0]), np.cos(ang[1]), np.sin(ang[1]), np.cos(ang[2]), np.sin(ang[2])
     R = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])

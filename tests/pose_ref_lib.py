@@ -30,14 +30,12 @@ NLEVELS = 8
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="pose_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libpose_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("pose_ref.cpp does not compile:\n" + p.stdout)
@@ -47,8 +45,14 @@ def lib() -> ctypes.CDLL:
     L.por_pose_optimize.restype = None
     L.por_first_step.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.por_huber_delta.restype = ctypes.c_double
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -220,10 +224,25 @@ def quat_to_matrix(q):
 # ---- the worlds the host and the GPU test share ----
 
 K0 = np.array([[520.0, 0, 320.0], [0, 520.0, 240.0], [0, 0, 1]], np.float32)
+SCALE_FACTOR = 1.2
+
+# The second setting of the back-end worlds (this library's and those of ba_, pnp_, sim3_, tri_, match_proj_, match_local_ and
+# match_kfproj_ref_lib, which import it).  Under the first one -- fx == fy, a pyramid of 8 levels of 1.2, motions of a few degrees
+# -- a v-projection that reads fx, a table length or a scale factor taken from a constant, and an x row written where a y row
+# belongs all leave every comparison unchanged.  K_ANISO: focal lengths a third apart and a principal point off the centre, all
+# four exact in f32.  The pyramid: 5 levels of 1.37, as the front-end tests use.  The motion: a roll of 89 degrees about the
+# optical axis with some 3 degrees about the other two (a rotation vector), so that the camera's x and y axes change roles.
+K_ANISO = np.array([[517.25, 0, 318.75], [0, 388.5, 255.5], [0, 0, 1]], np.float32)
+SCALE_FACTOR_2, NLEVELS_2 = 1.37, 5
+ROLL = (0.06, -0.05, 1.55)
+MOTION_2 = (ROLL, (0.4, -0.1, 0.3))
+SECOND = dict(K=K_ANISO, scale_factor=SCALE_FACTOR_2, nlevels=NLEVELS_2)
+SETTINGS = ("first", "second")
 
 
 def make_world(n, seed=0, cap=None, noise=0.5, outliers=0, angle_deg=2.0, scale=1.05, extra=5, matched=False, use_mask=True,
-               nlevels=NLEVELS, motion=((0.03, -0.06, 0.02), (0.4, -0.1, 0.3)), identity_start=False):
+               nlevels=NLEVELS, motion=((0.03, -0.06, 0.02), (0.4, -0.1, 0.3)), identity_start=False, K=K0,
+               scale_factor=SCALE_FACTOR):
     """A frame of n correspondences: map points 4 to 20 units deep seen from the true pose (R, t) = motion, pixel noise (in units
     of the keypoint's level sigma), mixed octaves, `outliers` gross mismatches more than 20 px off, and a start pose `angle_deg`
     off in rotation with its translation multiplied by `scale`.  The frame holds `extra` more features without a map point in
@@ -232,15 +251,15 @@ def make_world(n, seed=0, cap=None, noise=0.5, outliers=0, angle_deg=2.0, scale=
     identity_start: the start pose is the identity rotation with the true translation."""
     rng = np.random.default_rng(5000 + seed)
     Rt, tt = rotvec(motion[0]), np.array(motion[1], np.float64)
-    Kd = K0.astype(np.float64)
+    Kd = np.asarray(K, np.float64).reshape(3, 3)
     z = rng.uniform(4, 20, n)
     Y = np.c_[rng.uniform(-0.55, 0.55, n) * z, rng.uniform(-0.4, 0.4, n) * z, z]  # in the camera's frame, inside the image
     X = (Y - tt) @ Rt  # Rt^T (Y - t)
     octs = rng.integers(0, nlevels, n)
     obs = np.c_[Y[:, 0] / Y[:, 2] * Kd[0, 0] + Kd[0, 2], Y[:, 1] / Y[:, 2] * Kd[1, 1] + Kd[1, 2]]
-    obs = obs + rng.normal(0, 1, (n, 2)) * noise * (1.2 ** octs)[:, None]
+    obs = obs + rng.normal(0, 1, (n, 2)) * noise * (scale_factor ** octs)[:, None]
     bad = np.sort(rng.choice(n, outliers, replace=False)) if outliers else np.zeros(0, np.int64)
-    obs[bad] += rng.choice([-1.0, 1.0], (len(bad), 2)) * rng.uniform(20, 40, (len(bad), 2)) * (1.2 ** octs[bad])[:, None]
+    obs[bad] += rng.choice([-1.0, 1.0], (len(bad), 2)) * rng.uniform(20, 40, (len(bad), 2)) * (scale_factor ** octs[bad])[:, None]
     nf = n + extra if n else 0
     cap = int(cap or max(nf, 1))
     assert cap >= nf
@@ -274,7 +293,7 @@ def make_world(n, seed=0, cap=None, noise=0.5, outliers=0, angle_deg=2.0, scale=
         R0, t0 = dR @ Rt, (dR @ tt) * scale
     pose0 = np.r_[R0.reshape(9), t0].astype(np.float32)
     truth = dict(R=Rt, t=tt, slots=slots, bad=slots[bad], clean=np.setdiff1d(slots, slots[bad]))
-    return World(kps, nf, match, points, mask, pose0, K0.reshape(9).copy(), truth)
+    return World(kps, nf, match, points, mask, pose0, np.asarray(K, np.float32).reshape(9).copy(), truth)
 
 
 def feed_back(w: World, res) -> World:
@@ -367,11 +386,25 @@ def table_of(name):
     return TABLES[name]() if name in TABLES else None
 
 
+def inv_sigma2_of(setting_name: str):
+    """The inv_sigma2 table of a setting's pyramid: None (the default table) for the first."""
+    return None if setting_name == "first" else inv_sigma2_table(NLEVELS_2, SCALE_FACTOR_2)
+
+
+# the named worlds that exist under the second setting as well (world(name, "second")): smaller, with seeds of their own
+SECOND_WORLDS = {"clean": lambda: make_world(100, 101, outliers=10, motion=MOTION_2, **SECOND),
+                 "matched": lambda: make_world(80, 102, outliers=8, matched=True, motion=MOTION_2, **SECOND),
+                 "far": lambda: make_world(90, 103, outliers=30, angle_deg=25.0, scale=1.6, motion=MOTION_2, **SECOND),
+                 "noisy": lambda: make_world(120, 104, outliers=20, noise=1.2, angle_deg=4.0, motion=MOTION_2, **SECOND),
+                 "truth": lambda: make_world(150, 108, noise=0.2, outliers=15, motion=MOTION_2, **SECOND)}
 _worlds = {}
 
 
-def world(name: str) -> World:
-    """Named worlds, made once.  clean: 200 correspondences, 20 mismatches; matched: the same kind through a match row; far: a
+def world(name: str, setting_name: str = "first") -> World:
+    """Named worlds, made once.  setting_name "second": the world of that name in SECOND_WORLDS (K_ANISO, 5 levels of 1.37, the
+    true pose rolled by 89 degrees), for the table inv_sigma2_of("second").
+
+    clean: 200 correspondences, 20 mismatches; matched: the same kind through a match row; far: a
     start 25 degrees and 60 % off with a third mismatches (rejected trials); noisy: 1.2 sigma of pixel noise (features that
     change sides between rounds); converged: clean's result fed back; nine: 9 correspondences (one round); three: 3; two: 2
     (FEW_POINTS); truth: little noise.
@@ -388,6 +421,10 @@ def world(name: str) -> World:
     0: every solve fails); no_weight_big: the same with 700 correspondences; weight_lost (weight_lost_world: 100 gross mismatches
     at level 0, 20 exact correspondences at level 1) and weight_lost_big (420 and 40): failures behind accepted trials, with flags
     set."""
+    if setting_name != "first":
+        if (name, setting_name) not in _worlds:
+            _worlds[name, setting_name] = SECOND_WORLDS[name]()
+        return _worlds[name, setting_name]
     if name not in _worlds:
         if name == "clean":
             w = make_world(200, 1, outliers=20)

@@ -17,6 +17,7 @@ import numpy as np
 
 import pose_ref_lib as P
 from pnp_ref_lib import sigma2_table
+from pose_ref_lib import K_ANISO, MOTION_2, NLEVELS_2, ROLL, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "sim3_ref.cpp")
@@ -35,18 +36,16 @@ PARAMS = dict(probability=0.99, min_inliers=20, max_iterations=300, th2=9.210, f
 _L = None
 
 
-def compile_command(out, extra=()):
-    return ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", *extra, SRC, "-o", out]
+def compile_command(out, extra=(), src=SRC):
+    return ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", *extra, src, "-o", out]
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="sim3_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libsim3_ref.so")
-    p = subprocess.run(compile_command(so, ("-fPIC", "-shared")), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    p = subprocess.run(compile_command(so, ("-fPIC", "-shared"), src), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("sim3_ref.cpp does not compile:\n" + p.stdout)
     L = ctypes.CDLL(so)
@@ -61,8 +60,14 @@ def lib() -> ctypes.CDLL:
     L.s3r_horn.restype = None
     L.s3r_eig_top.argtypes = [vp, vp]
     L.s3r_eig_top.restype = ctypes.c_double
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -161,7 +166,7 @@ class World:
 
 
 def make_world(n, seed=0, cap=None, noise=0.0, outliers=0, extra=5, s=1.3, rot=(0.05, -0.08, 0.03), t=(0.3, -0.2, 0.4),
-               use_mask=True, nlevels=NLEVELS, same_depth=None):
+               use_mask=True, nlevels=NLEVELS, same_depth=None, K=K0, scale_factor=1.2):
     """Two keyframes with n correspondences.  The points lie 4 to 20 units in front of camera 2 (Y2); camera 1 sees them at Y1 =
     s R Y2 + t, the true similarity between the camera frames (s != 1: a monocular map that drifted in scale; s = 1 for a
     fix_scale world).  Each keyframe stores its points in a world frame of its own pose.  noise: standard deviation of the error
@@ -170,12 +175,12 @@ def make_world(n, seed=0, cap=None, noise=0.0, outliers=0, extra=5, s=1.3, rot=(
     point but no match, and matched to an entry that is no point."""
     rng = np.random.default_rng(15000 + seed)
     Rt, tt, st = P.rotvec(rot), np.array(t, np.float64), float(s)
-    Kd = K0.astype(np.float64)
+    Kd = np.asarray(K, np.float64).reshape(3, 3)
     z = rng.uniform(4, 20, n) if same_depth is None else np.full(n, float(same_depth))
     Y2 = np.c_[rng.uniform(-0.45, 0.45, n) * z, rng.uniform(-0.32, 0.32, n) * z, z]
     Y1 = st * Y2 @ Rt.T + tt
     oct1, oct2 = rng.integers(0, nlevels, n), rng.integers(0, nlevels, n)
-    Y2n = Y2 + rng.normal(0, 1, (n, 3)) * (noise * (1.2 ** oct2) * z / Kd[0, 0])[:, None]
+    Y2n = Y2 + rng.normal(0, 1, (n, 3)) * (noise * (scale_factor ** oct2) * z / Kd[0, 0])[:, None]
     bad = np.sort(rng.choice(n, outliers, replace=False)) if outliers else np.zeros(0, np.int64)
     Y2n[bad] += rng.choice([-1.0, 1.0], (len(bad), 3)) * rng.uniform(1.0, 3.0, (len(bad), 3))
     R1, t1 = P.rotvec((0.2, -0.1, 0.05)), np.array([0.5, -1.0, 2.0])
@@ -210,7 +215,7 @@ def make_world(n, seed=0, cap=None, noise=0.0, outliers=0, extra=5, s=1.3, rot=(
         mask1 = mask2 = None
     pose1, pose2 = np.r_[R1.reshape(9), t1].astype(np.float32), np.r_[R2.reshape(9), t2].astype(np.float32)
     truth = dict(s=st, R=Rt, t=tt, slots1=slots1, slots2=slots2, bad=bad, Y1=Y1, Y2=Y2)
-    return World(kps1, nf, kps2, nf, match, points1, mask1, points2, mask2, pose1, pose2, K0.reshape(9).copy(), truth)
+    return World(kps1, nf, kps2, nf, match, points1, mask1, points2, mask2, pose1, pose2, np.asarray(K, np.float32).reshape(9).copy(), truth)
 
 
 # ---- the restatement ----
@@ -353,6 +358,7 @@ class MWorld:
         self.pdesc = [z(32, dt=np.uint8), z(32, dt=np.uint8)] if pdesc else None
         self.pose, self.sim, self.match = [IDENTITY.copy(), IDENTITY.copy()], IDENTITY_SIM.copy(), np.full(cap, -1, np.int32)
         self.truth = {}
+        self.scale = None  # (mvScaleFactor when it is not the default table)
 
     def copy(self):
         import copy
@@ -378,7 +384,9 @@ class MWorld:
 def search_by_sim3(w: MWorld, th=7.5, orb_dist=100, scale=None):
     """The restatement for one pair -> dict(matches [cap], res (MSIM3_RESULT_DTYPE record), vn1, vn2 [cap], proj1, proj2 [cap,
     5] = u, v, radius, level, stage).  Counts outside [0, cap] are clamped and flagged here, as the device does."""
-    sc = np.ascontiguousarray(scale_table() if scale is None else scale, np.float32)
+    if scale is None:
+        scale = scale_table() if w.scale is None else w.scale
+    sc = np.ascontiguousarray(scale, np.float32)
     n = [max(0, min(int(v), w.cap)) for v in w.n]
     m, res = w.match.copy(), np.zeros(1, MSIM3_RESULT_DTYPE)
     vn1, vn2 = np.full(w.cap, -1, np.int32), np.full(w.cap, -1, np.int32)
@@ -418,7 +426,7 @@ def project(K, Y):
 
 
 def make_match_world(n, seed=0, cap=None, extra=20, matched=0.4, s=1.3, rot=(0.03, -0.05, 0.02), t=(0.2, -0.1, 0.3), pdesc=False,
-                     noise_bits=0):
+                     noise_bits=0, K=None, scale_factor=1.2, nlevels=NLEVELS):
     """A truth world: n physical points seen by both keyframes, Y1 = s R Y2 + t between the camera frames; each keyframe has a
     feature at the point's projection (exact descriptor copies, `noise_bits` flipped in KF2's) and the point in its own map;
     the distances are set so that PredictScale returns the features' octave.  A fraction `matched` of the pairs is already in
@@ -430,20 +438,22 @@ def make_match_world(n, seed=0, cap=None, extra=20, matched=0.4, s=1.3, rot=(0.0
     Y1 = st * Y2 @ Rt.T + tt
     nf = n + extra
     cap = int(cap or nf)
-    w = MWorld(cap, pdesc=pdesc)
+    w = MWorld(cap, K=K, pdesc=pdesc)
+    if (scale_factor, nlevels) != (1.2, NLEVELS):
+        w.scale = scale_table(nlevels, scale_factor)
     R1, t1 = P.rotvec((0.2, -0.1, 0.05)), np.array([0.5, -1.0, 2.0])
     R2, t2 = P.rotvec((-0.1, 0.3, 0.1)), np.array([-1.5, 0.4, 1.0])
     w.pose = [np.r_[R1.reshape(9), t1].astype(np.float32), np.r_[R2.reshape(9), t2].astype(np.float32)]
     w.sim = np.r_[Rt.reshape(9), tt, st].astype(np.float32)
     X = [(Y1 - t1) @ R1, (Y2 - t2) @ R2]
     uv = [project(w.K, Y1), project(w.K, Y2)]
-    lev = rng.integers(0, NLEVELS, n)
+    lev = rng.integers(0, nlevels, n)
     desc = rng.integers(0, 256, (n, 32)).astype(np.uint8)
     slots = [np.sort(rng.permutation(nf)[:n]), rng.permutation(nf)[:n]]
-    sc = scale_table().astype(np.float64)
+    sc = scale_table(nlevels, scale_factor).astype(np.float64)
     for side, other_depth in ((0, np.linalg.norm(Y2, axis=1)), (1, np.linalg.norm(Y1, axis=1))):
         k = w.kps[side]
-        k["x"][:nf], k["y"][:nf], k["octave"][:nf] = rng.uniform(0, 640, nf), rng.uniform(0, 480, nf), rng.integers(0, NLEVELS, nf)
+        k["x"][:nf], k["y"][:nf], k["octave"][:nf] = rng.uniform(0, 640, nf), rng.uniform(0, 480, nf), rng.integers(0, nlevels, nf)
         w.desc[side][:nf] = rng.integers(0, 256, (nf, 32))
         sl = slots[side]
         k["x"][sl], k["y"][sl], k["octave"][sl] = uv[side][:, 0], uv[side][:, 1], lev

@@ -191,6 +191,38 @@ def test_host_form_equals_the_batch(orbx, ext, sized):
         assert p1.tobytes() == pts[0, :w.n1].tobytes()
 
 
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37, frame 2 rolled by 89 degrees ----
+
+CAP_2 = 268  # just above the larger frame (257 matches + 10 other keypoints)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, B.SCALE_FACTOR_2, B.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, ext2):
+    """Two pairs (65 and 257 points) under K_ANISO: once with the context's own table, once with the same table given
+    explicitly; then the host form on the smaller one."""
+    pairs = [B.make_pair(n, 120 + k, cap=CAP_2, outliers=n // 16, motion=B.MOTION_ROLL, **B.SECOND) for k, n in enumerate((65, 257))]
+    table = B.inv_sigma2_of("second")
+    assert ext2.GetInverseScaleSigmaSquares().tobytes() == table.tobytes() and len(table) == B.NLEVELS_2
+    res, pts = run_batch(orbx, ext2, pairs, min_points=60)  # (the context's table)
+    for p, w in enumerate(pairs):
+        r, rp, _ = B.bundle_adjust(w, min_points=60, inv_sigma2=table)
+        same(res[p], pts[p], r, rp, "context's table, pair %d" % p)
+    res2 = check(orbx, ext2, pairs, min_points=60, inv_sigma2=table)
+    assert res2.tobytes() == res.tobytes()
+    for p, n in enumerate((65, 257)):  # not trivial: every point in the graph, iterations that gain
+        assert res[p]["status"] == 0 and res[p]["n_points"] == n and res[p]["iterations"] > 1
+        assert res[p]["chi2_final"] < 0.5 * res[p]["chi2_initial"]
+    w = pairs[0]
+    one, p1 = ext2.bundle_adjust(w.k1[:w.n1], w.k2[:w.n2], w.m12[:w.n1], w.init, w.p3d[:w.n1], w.tri[:w.n1], w.K, min_points=60)
+    assert bytes(one) == res[0].tobytes() and p1.tobytes() == pts[0, :w.n1].tobytes()
+
+
 def test_chained_behind_the_initializer(orbx, ext):
     """Initializer -> bundle adjustment on the device, the second stage reading what the first left there (its results, vP3D,
     vbTriangulated), for three pairs: two two-view scenes with depth that the Initializer accepts and, between them, a scene it

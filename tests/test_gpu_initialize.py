@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import init_ref_lib as R
+from pose_ref_lib import K_ANISO
 
 pytestmark = pytest.mark.gpu
 
@@ -63,8 +64,8 @@ def test_init_images_equal_the_restatement(orbx, ext, oracle, golden, seed):
     _same(res.as_dict(), p3d, tri, ref, rp3d, rtri)
 
 
-def test_general_scene_recovers_the_motion(orbx, ext, oracle):
-    K, Rm, t, k1, k2, m12, _ = oracle.two_view_case(seed=2, outliers=0.1, noise=0.3)
+def test_general_scene_recovers_the_motion(orbx, ext, oracle, camera=None, seed=2):
+    K, Rm, t, k1, k2, m12, _ = oracle.two_view_case(seed=seed, outliers=0.1, noise=0.3, K=camera)
     sets = _sets(orbx, m12, 0)
     res, p3d, tri = ext.initialize(k1, k2, m12, sets, K)
     ref, rp3d, rtri = R.initialize(k1, k2, m12, sets, K)
@@ -75,7 +76,12 @@ def test_general_scene_recovers_the_motion(orbx, ext, oracle):
     assert np.degrees(np.arccos(np.clip((np.trace(Re.T @ Rm) - 1) / 2, -1, 1))) < 0.5
     tt = d["t21"] / np.linalg.norm(d["t21"])
     assert np.degrees(np.arccos(min(1.0, abs(float(tt @ (t / np.linalg.norm(t))))))) < 1.0
-    assert tri.sum() >= 0.9 * d["n_inliers_f"]
+    assert tri.sum() >= 0.9 * d["n_inliers_f"] and d["n_inliers_f"] > 300 and d["n_solutions"] == 4
+
+
+def test_general_scene_under_an_anisotropic_camera(orbx, ext, oracle):
+    """K_ANISO: fx and fy a third apart (the seed: tests/test_initializer_host.py, test_restated_initialize_on_a_general_scene)."""
+    test_general_scene_recovers_the_motion(orbx, ext, oracle, K_ANISO, 17)
 
 
 def test_pure_rotation_is_low_parallax(orbx, ext, oracle):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import init_ref_lib as R
+from pose_ref_lib import K_ANISO
 
 pytestmark = pytest.mark.gpu
 
@@ -96,10 +97,14 @@ def test_init_images_equal_the_restatement(orbx, ext, oracle, golden, seed):
     assert np.array_equal(inl, rinl)
 
 
-def test_model_choice_on_a_general_scene(orbx, ext, oracle):
-    K, Rm, t, k1, k2, m12, _ = oracle.two_view_case(seed=2, outliers=0.1, noise=0.3)
-    res, inl = ext.find_models(k1, k2, m12, _sets(orbx, m12, 0))
-    assert res.status == 0 and res.model == 1 and res.rh < 0.5
+def test_model_choice_on_a_general_scene(orbx, ext, oracle, camera=None, seed=2):
+    K, Rm, t, k1, k2, m12, _ = oracle.two_view_case(seed=seed, outliers=0.1, noise=0.3, K=camera)
+    sets = _sets(orbx, m12, 0)
+    res, inl = ext.find_models(k1, k2, m12, sets)
+    rres, rinl, _, _ = R.find_models(k1, k2, m12, sets)
+    _same_result(res.as_dict(), rres)
+    assert np.array_equal(inl, rinl)
+    assert res.status == 0 and res.model == 1 and res.rh < 0.5 and res.n_inliers_f > 300
     # the kept F agrees with the true epipolar geometry on the true matches
     Ki = np.linalg.inv(K)
     tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
@@ -107,6 +112,11 @@ def test_model_choice_on_a_general_scene(orbx, ext, oracle):
     F = np.array(res.F21[:], np.float64).reshape(3, 3)
     Ft, F = Ft / np.linalg.norm(Ft), F / np.linalg.norm(F)
     assert min(np.abs(F - Ft).max(), np.abs(F + Ft).max()) < 0.05
+
+
+def test_model_choice_under_an_anisotropic_camera(orbx, ext, oracle):
+    """K_ANISO: fx and fy a third apart, pixel geometry that is not a scaled copy of the normalised one."""
+    test_model_choice_on_a_general_scene(orbx, ext, oracle, K_ANISO, 17)
 
 
 def test_batch_equals_single_calls(orbx, ext):

@@ -171,6 +171,47 @@ def test_batch_with_shared_frames(torch, ext):
         assert m1[0].tobytes() == m[p].tobytes() and r1[0, :NF - 1].tobytes() == r[p, :NF - 1].tobytes(), p
 
 
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37 (the matcher reads the context's scale
+# table), the pose rolled by 89 degrees ----
+
+BOUNDS_2 = (-12, 655, -9, 490)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, L.SCALE_FACTOR_2, L.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2, device=0)
+    assert np.asarray(e.GetScaleFactors(), np.float32).tobytes() == L.scale_table(L.NLEVELS_2, L.SCALE_FACTOR_2).tobytes()
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, torch, ext2):
+    """The keyframes of 150 and 310 features under K_ANISO in one batch at the capacity of the largest count, under the offset
+    bounds (a call has one set of bounds: the smaller scene's restatement runs under them too); then the smaller scene alone
+    at its own largest count under the usual bounds, through the batch and the host form."""
+    a, b = L.world("w150@2"), L.world("w310_bounds@2")
+    assert a.n_k == 150 and b.n_k == 310 and b.bounds == BOUNDS_2 and len(a.scale) == L.NLEVELS_2
+    a_off = a.variant(bounds=BOUNDS_2)
+    frames = [(a.kps_k, a.desc_k), (a.kps_c, a.desc_c), (b.kps_k, b.desc_k), (b.kps_c, b.desc_c)]
+    sets = [(a.points, a.dists, a.mask, None), (b.points, b.dists, b.mask, None)]
+    pairs = [(0, 1, 0, a.pose, a.matches, a.outlier), (2, 3, 1, b.pose, b.matches, b.outlier)]
+    cap = max(b.n_k, b.n_c)
+    m, r = Batch(torch, frames, sets, pairs, cap).run(torch, ext2, b.K, BOUNDS_2, b.th, b.orb_dist, b.ori)
+    for p, w in enumerate((a_off, b)):
+        res = check_pair(m[p], r[p], w, "pair %d" % p)
+        # not trivial: matches found, points rejected outside the image and by distance, windows with candidates
+        assert res["status"] == 0 and res["nmatches"] > 20 and res["n_out_image"] > 10 and res["n_out_distance"] > 10
+        assert res["n_with_candidates"] > 30
+    m1, r1 = run_world(torch, ext2, a, max(a.n_k, a.n_c))
+    check_pair(m1[0], r1[0], a, "alone")
+    e = a.expected()
+    T = np.c_[a.pose[:9].reshape(3, 3), a.pose[9:]]
+    mh, rh = ext2.match_keyframe_projection(a.kps_k, a.desc_k, a.kps_c, a.desc_c, a.points, a.mask, a.dists, T, a.K, a.bounds, a.matches,
+                                            a.th, a.orb_dist, a.ori, a.point_desc, a.outlier)
+    assert mh.tobytes() == e["matches"].tobytes()
+    assert {f: x for f, x in rh.as_dict().items() if f != "rounds"} == {f: e["res"][f] for f in L.COMPARED_FIELDS}
+
+
 def test_host_form_and_classes(orbx, torch, ext):
     for name in ("main", "main_th3", "pdesc", "order", "empty_frame", "empty_keyframe"):
         w = L.world(name)

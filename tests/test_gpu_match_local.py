@@ -228,6 +228,46 @@ def test_batch_with_shared_frames_and_maps(torch, ext):
         assert m1[0].tobytes() == m[p].tobytes() and v1[0].tobytes() == v[p].tobytes() and r1[0, :NF - 1].tobytes() == r[p, :NF - 1].tobytes(), p
 
 
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37 (the matcher reads the context's scale
+# table), the pose rolled by 89 degrees ----
+
+BOUNDS_2 = (-12, 655, -9, 490)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, L.SCALE_FACTOR_2, L.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2, device=0)
+    assert np.asarray(e.GetScaleFactors(), np.float32).tobytes() == L.scale_table(L.NLEVELS_2, L.SCALE_FACTOR_2).tobytes()
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, torch, ext2):
+    """The maps of 150 and 310 points under K_ANISO in one batch at the capacities of the largest counts, under the offset
+    bounds (a call has one set of bounds: the smaller scene's restatement runs under them too); then the smaller scene alone
+    at its own counts under the usual bounds, through the batch and the host form."""
+    a, b = L.world("w150@2"), L.world("w310_bounds@2")
+    assert a.n_m == 150 and b.n_m == 310 and b.bounds == BOUNDS_2 and len(a.scale) == L.NLEVELS_2
+    a_off = a.variant(bounds=BOUNDS_2)
+    fa, sa, _ = parts(a)
+    fb, sb, _ = parts(b)
+    pairs = [(0, 0, a.pose, a.matches, a.outlier), (1, 1, b.pose, b.matches, b.outlier)]
+    m, v, r = Batch(torch, [fa, fb], [sa, sb], pairs, max(a.n_f, b.n_f), 310).run(torch, ext2, b.K, BOUNDS_2, b.th, b.nnratio)
+    for p, w in enumerate((a_off, b)):
+        res = check_pair(m[p], v[p], r[p], w, "pair %d" % p)
+        # not trivial: matches found, points rejected outside the image, by distance and by angle, and by the ratio test
+        assert res["status"] == 0 and res["nmatches"] >= 8 and res["n_out_image"] > 10 and res["n_out_distance"] > 10
+        assert res["n_out_angle"] > 5 and res["n_in_view"] > 30 and res["n_ratio_rejected"] > 0
+    m1, v1, r1 = batch_of(torch, a, a.n_f, a.n_m).run(torch, ext2, a.K, a.bounds, a.th, a.nnratio)
+    check_pair(m1[0], v1[0], r1[0], a, "alone")
+    e = a.expected()
+    T = np.c_[a.pose[:9].reshape(3, 3), a.pose[9:]]
+    mh, vh, rh = ext2.match_local_map(a.kps, a.desc, a.points, a.normals, a.dists, a.map_desc, a.mask, T, a.K, a.bounds, a.matches, a.th,
+                                      a.nnratio, a.outlier)
+    assert mh.tobytes() == e["matches"].tobytes() and vh.tobytes() == e["view"].tobytes()
+    assert {f: x for f, x in rh.as_dict().items() if f != "rounds"} == {f: e["res"][f] for f in L.COMPARED_FIELDS}
+
+
 def test_host_form_and_classes(orbx, torch, ext):
     for name in ("main", "main_th5", "order", "empty_frame", "empty_map"):
         w = L.world(name)

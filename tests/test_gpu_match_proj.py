@@ -134,6 +134,45 @@ def test_capacity_and_counts(torch, orbx, ext, cap):
     assert res["nmatches"] > 30
 
 
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37 (the matcher reads the context's scale
+# table), the pose rolled by 89 degrees ----
+
+BOUNDS_2 = (-12, 655, -9, 490)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, M.SCALE_FACTOR_2, M.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2, device=0)
+    assert np.asarray(e.GetScaleFactors(), np.float32).tobytes() == M.scale_table(M.NLEVELS_2, M.SCALE_FACTOR_2).tobytes()
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, torch, ext2):
+    """The scenes of 150 and 310 features under K_ANISO in one batch at the capacity of the largest count, under the offset
+    bounds (a call has one set of bounds: the smaller scene's restatement runs under them too); then the smaller scene alone
+    at its own largest count under the usual bounds, through the batch and the host form."""
+    a, b = M.world("w150@2"), M.world("w310_bounds@2")
+    assert a.n_l == 150 and b.n_l == 310 and b.bounds == BOUNDS_2 and len(a.scale) == M.NLEVELS_2
+    a_off = a.variant(bounds=BOUNDS_2)
+    cap = max(b.n_l, b.n_c)
+    frames = [(a.kps_l, a.desc_l), (a.kps_c, a.desc_c), (b.kps_l, b.desc_l), (b.kps_c, b.desc_c)]
+    sets = [(a.points, a.mask, None), (b.points, b.mask, None)]
+    pairs = [(0, 1, 0, a.pose, a.outlier), (2, 3, 1, b.pose, b.outlier)]
+    m, r = Batch(torch, frames, sets, pairs, cap).run(torch, ext2, b.K, BOUNDS_2, b.th, b.ori)
+    for p, w in enumerate((a_off, b)):
+        res = check_pair(m[p], r[p], w, "pair %d" % p)
+        # not trivial: matches found, points that project outside the image (or lie behind the camera), windows with candidates
+        assert res["status"] == 0 and res["nmatches"] > 30 and res["n_points"] - res["n_in_image"] > 20 and res["n_with_candidates"] > 50
+    m1, r1 = batch_of(torch, a, max(a.n_l, a.n_c)).run(torch, ext2, a.K, a.bounds, a.th, a.ori)
+    check_pair(m1[0], r1[0], a, "alone")
+    e = a.expected()
+    T = np.c_[a.pose[:9].reshape(3, 3), a.pose[9:]]
+    mh, rh = ext2.match_projection(a.kps_l, a.desc_l, a.kps_c, a.desc_c, a.points, a.mask, T, a.K, a.bounds, a.th, a.ori, last_outlier=a.outlier)
+    assert mh.tobytes() == e["matches"].tobytes()
+    assert {f: v for f, v in rh.as_dict().items() if f != "rounds"} == {f: e["res"][f] for f in M.COMPARED_FIELDS}
+
+
 def test_batch_with_shared_frames(torch, ext):
     """One call: frame 1 is the current frame of pairs 0 and 1 (two poses, so two answers) and the last frame of pair 2, whose
     current frame is frame 0; pair 3 has an empty last frame, pair 4 an empty current frame; pair 1 brings outlier flags, the

@@ -135,13 +135,18 @@ def test_partial_and_full_waves_of_hypotheses(orbx, ext, n_iter):
         assert one[0].tobytes() == res[0].tobytes()
 
 
-def test_each_branch_world(orbx, ext, branch):
+def test_each_branch_world(orbx, ext, ext2, branch):
+    """The host test's worlds, grouped by what a batch shares; those of the second setting (named @2) on its context, under its
+    table."""
     by_len = {}
     for name, (w, d) in branch.items():
-        by_len.setdefault(len(d), []).append((name, with_match(w), d))
+        by_len.setdefault((len(d), name.endswith("@2")), []).append((name, with_match(w), d))
     seen = {}
-    for n_iter, group in by_len.items():
-        res = check(orbx, ext, [(w, d) for _, w, d in group])
+    for (n_iter, second), group in by_len.items():
+        if second:
+            res = check(orbx, ext2, [(w, d) for _, w, d in group], sigma2=Q.sigma2_table(Q.NLEVELS_2, Q.SCALE_FACTOR_2))
+        else:
+            res = check(orbx, ext, [(w, d) for _, w, d in group])
         seen.update({name: res[k] for k, (name, _, _) in enumerate(group)})
     assert seen["unrefined"]["refined"] == 0 and seen["unrefined"]["found_it"] == -1 and seen["unrefined"]["n_inliers"] == 10
     assert seen["second_try"]["n_refines"] >= 2 and seen["second_try"]["refined"] == 1
@@ -264,6 +269,49 @@ def test_host_form_equals_a_batch_of_one(orbx, ext, sized):
         assert np.array_equal(inl, got[3][0][:w.n] != 0)
         r = Q.solve(w, d, 0)
         assert bytes(res) == r[0].tobytes()
+
+
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37, a true pose rolled by 89 degrees ----
+
+CAP_2 = 263  # just above the larger frame (257 correspondences + 5 other features)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, Q.SCALE_FACTOR_2, Q.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, ext2):
+    """Two problems (65 and 257 correspondences, a fifth gross mismatches, 0.5 sigma of noise) under K_ANISO: once with the
+    context's own table, once with the same table given explicitly; then the host form and PnPsolver on the smaller one."""
+    pairs = [(Q.make_world(n, 440 + k, cap=CAP_2, outliers=n // 5, noise=0.5, motion=Q.MOTION_2, **Q.SECOND), Q.make_draws(35, 440 + k))
+             for k, n in enumerate((65, 257))]
+    table = Q.sigma2_table(Q.NLEVELS_2, Q.SCALE_FACTOR_2)
+    assert ext2.GetScaleSigmaSquares().tobytes() == table.tobytes() and len(table) == Q.NLEVELS_2
+    worlds, draws = [w for w, _ in pairs], np.stack([d for _, d in pairs])
+    res, pose, row, flags = run_batch(orbx, ext2, worlds, draws)  # (the context's table)
+    for p, (w, d) in enumerate(pairs):
+        same((res[p], pose[p], row[p], flags[p]), Q.solve(w, d, 0, sigma2=table), "context's table, problem %d" % p)
+    res2 = check(orbx, ext2, pairs, sigma2=table)
+    assert res2.tobytes() == res.tobytes()
+    for p, n in enumerate((65, 257)):  # not trivial: refined over more inliers than the minimum, no planted mismatch among them
+        assert res[p]["status"] == 0 and res[p]["refined"] == 1 and res[p]["n_correspondences"] == n
+        assert res[p]["n_inliers"] > res[p]["min_inliers"] and res[p]["n_inliers"] >= (n - n // 5) * 3 // 4
+        assert not flags[p][worlds[p].truth["bad"]].any()
+    w, d = pairs[0]
+    one, inl = ext2.pnp_solve(w.kps[:w.n], w.points[:w.n], w.mask[:w.n], w.K, d)
+    assert bytes(one) == res[0].tobytes() and np.array_equal(inl, flags[0][:w.n] != 0)
+    it = iter(d.reshape(-1).tolist() + [0] * (4 * 300))
+    s = orbx.PnPsolver(_Frame(w, ext2), w.points[:w.n], w.mask[:w.n], w.K.reshape(3, 3), rand=lambda: next(it))
+    s.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)
+    d300 = np.zeros((300, 4), np.int32)
+    d300[:35] = d
+    ref = Q.solve(w, d300, 0, sigma2=table)
+    T, inl, n, r = s.find()
+    assert bytes(r) == ref[0].tobytes() and n == ref[0]["n_inliers"] and np.array_equal(inl, ref[3][:w.n] != 0)
+    assert T[:3, :3].astype(np.float32).tobytes() == ref[1][:9].tobytes() and T[:3, 3].tobytes() == ref[1][9:].tobytes()
 
 
 class _Frame:

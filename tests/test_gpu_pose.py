@@ -244,6 +244,45 @@ def test_host_form_equals_a_batch_of_one(orbx, ext, sized):
     assert n == ref["n_inliers"] and T[:3, :3].tobytes() == ref["R"].tobytes() and T[:3, 3].tobytes() == ref["tcw"].tobytes()
 
 
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37, a true pose rolled by 89 degrees ----
+
+CAP_2 = 263  # just above the larger frame (257 correspondences + 5 other features)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, P.SCALE_FACTOR_2, P.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(orbx, ext2):
+    """Two problems (65 and 257 correspondences) under K_ANISO: once with the context's own table, once with the same table
+    given explicitly; then the host form and the Python class on the smaller one.  A v-projection that read fx, or a table of
+    the usual 8 levels of 1.2, would change every chi2 here."""
+    worlds = [P.make_world(n, 140 + k, cap=CAP_2, outliers=n // 8, motion=P.MOTION_2, **P.SECOND) for k, n in enumerate((65, 257))]
+    table = P.inv_sigma2_of("second")
+    assert ext2.GetInverseScaleSigmaSquares().tobytes() == table.tobytes() and len(table) == P.NLEVELS_2
+    res, flags = run_batch(orbx, ext2, worlds)  # (the context's table)
+    for p, w in enumerate(worlds):
+        r, rf, _, _ = P.pose_optimize(w, inv_sigma2=table)
+        same(res[p], flags[p], r, rf, "context's table, problem %d" % p)
+    res2 = check(orbx, ext2, worlds, inv_sigma2=table)
+    assert res2.tobytes() == res.tobytes()
+    for p, n in enumerate((65, 257)):  # not trivial: four rounds, the planted mismatches flagged, the rest inliers
+        assert res[p]["status"] == 0 and res[p]["rounds"] == 4 and res[p]["n_correspondences"] == n
+        assert res[p]["n_bad"] == n // 8 and res[p]["n_inliers"] == n - n // 8 and res[p]["chi2_final"] < res[p]["chi2_initial"]
+        assert np.array_equal(np.flatnonzero(flags[p]), worlds[p].truth["bad"])
+    w = worlds[0]
+    T = np.c_[w.pose0[:9].reshape(3, 3), w.pose0[9:]]
+    one, out = ext2.pose_optimize(w.kps[:w.n], w.points[:w.n], w.mask[:w.n], T, w.K)
+    assert bytes(one) == res[0].tobytes() and np.array_equal(out, flags[0, :w.n] != 0)
+    frame = orbx.Frame.from_arrays(w.kps[:w.n], np.zeros((w.n, 32), np.uint8), (0, 640, 0, 480))
+    n, T2, out2, _ = orbx.Optimizer.PoseOptimization(frame, w.points[:w.n], w.mask[:w.n], T, K=w.K, extractor=ext2)
+    assert n == res[0]["n_inliers"] and T2[:3, :3].tobytes() == res[0]["R"].tobytes() and T2[:3, 3].tobytes() == res[0]["tcw"].tobytes()
+    assert np.array_equal(np.asarray(out2, bool), out)
+
+
 # ---- behind the LDS cache: a lane's edges from the seventh on are read from the problem's rows, their flags from its outlier row
 # (tests/test_pose_host.py, test_the_cache_worlds_leave_the_cache, shows which worlds hold what there).  Capacity 1024, in a
 # context of their own ----

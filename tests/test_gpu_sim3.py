@@ -140,17 +140,19 @@ def test_found_at_the_first_in_the_middle_at_the_last_iteration_and_never(orbx, 
     assert list(res["status"]) == [0, 0, 0, S.NO_RESULT]
 
 
-def test_each_branch_world(orbx, ext):
-    """The host test's worlds (degenerate triples, the last of equals, fix_scale, no mask ...), grouped by what a batch shares."""
+def test_each_branch_world(orbx, ext, ext2):
+    """The host test's worlds (degenerate triples, the last of equals, fix_scale, no mask ...), grouped by what a batch shares;
+    those of the second setting (solved under a sigma2 table of their own) on its context."""
     groups = {}
     for name, (w, d, prm) in _worlds().items():
         if w.mask1 is None:
             continue
-        groups.setdefault((len(d), tuple(sorted(prm.items()))), []).append((name, padded(w, CAP), d))
+        rest = tuple(sorted((k, v) for k, v in prm.items() if k != "sigma2"))
+        groups.setdefault((len(d), rest, "sigma2" in prm), []).append((name, padded(w, CAP), d, prm.get("sigma2")))
     seen = {}
-    for (_, prm), group in groups.items():
-        res = check(orbx, ext, [(w, d) for _, w, d in group], **dict(prm))
-        seen.update({name: res[k] for k, (name, _, _) in enumerate(group)})
+    for (_, prm, second), group in groups.items():
+        res = check(orbx, ext2 if second else ext, [(w, d) for _, w, d, _ in group], sigma2=group[0][3], **dict(prm))
+        seen.update({name: res[k] for k, (name, _, _, _) in enumerate(group)})
     assert seen["coincident"]["n_degenerate"] >= 1 and seen["coincident"]["found_it"] > 0
     assert seen["equals"]["found_it"] == -1 and seen["equals"]["n_best_inliers"] == 20 and seen["equals_19"]["found_it"] >= 0
     assert seen["fix_scale"]["s12"] == 1.0 and seen["truth"]["status"] == 0 and seen["exactly_min"]["its_run"] == 1
@@ -277,6 +279,79 @@ def test_host_form_equals_a_batch_of_one(orbx, ext, sized):
         assert bytes(res) == got[0][0].tobytes() and sim.tobytes() == got[1][0].tobytes()
         assert np.array_equal(row, got[2][0][:w.n1]) and np.array_equal(inl, got[3][0][:w.n1] != 0)
         assert bytes(res) == S.solve(w, d, 0)[0].tobytes()
+
+
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37, camera 1 rolled by 89 degrees ----
+
+CAP_2 = 263  # just above the larger keyframe (257 correspondences + 5 other features)
+BOUNDS_2 = (-12, 655, -9, 490)
+
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, S.SCALE_FACTOR_2, S.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2)
+    yield e
+    e.close()
+
+
+def test_second_setting_solver_anisotropic_camera_and_five_levels(orbx, ext2):
+    """Two problems (65 and 257 correspondences, a fifth gross mismatches, half a sigma of noise) under K_ANISO: once with the
+    context's own table, once with the same table given explicitly; then the host form and Sim3Solver on the smaller one."""
+    pairs = [(S.make_world(n, 440 + k, cap=CAP_2, outliers=n // 5, noise=0.5, rot=S.ROLL, **S.SECOND), S.make_draws(35, 440 + k))
+             for k, n in enumerate((65, 257))]
+    table = S.sigma2_table(S.NLEVELS_2, S.SCALE_FACTOR_2)
+    assert ext2.GetScaleSigmaSquares().tobytes() == table.tobytes() and len(table) == S.NLEVELS_2
+    worlds, draws = [w for w, _ in pairs], np.stack([d for _, d in pairs])
+    res, sim, row, flags = run_batch(orbx, ext2, worlds, draws)  # (the context's table)
+    for p, (w, d) in enumerate(pairs):
+        same((res[p], sim[p], row[p], flags[p]), S.solve(w, d, 0, sigma2=table), "context's table, problem %d" % p)
+    res2 = check(orbx, ext2, pairs, sigma2=table)
+    assert res2.tobytes() == res.tobytes()
+    for p, n in enumerate((65, 257)):  # not trivial: found, more inliers than the minimum, no planted mismatch among them
+        assert res[p]["status"] == 0 and res[p]["found_it"] >= 0 and res[p]["n_correspondences"] == n and res[p]["n_inliers"] > 20
+        i1, _ = worlds[p].edges()
+        assert not flags[p][i1[worlds[p].truth["bad"]]].any()
+    w, d = pairs[0]
+    one, sim1, row1, inl = ext2.sim3_solve(w.kps1[:w.n1], w.points1[:w.n1], w.mask1[:w.n1], w.pose1, w.kps2[:w.n2], w.points2[:w.n2],
+                                           w.mask2[:w.n2], w.pose2, w.match[:w.n1], w.K, d)
+    assert bytes(one) == res[0].tobytes() and sim1.tobytes() == sim[0].tobytes()
+    assert np.array_equal(row1, row[0][:w.n1]) and np.array_equal(inl, flags[0][:w.n1] != 0)
+    it = iter(d.reshape(-1).tolist() + [0] * (3 * 300))
+    kf1 = (w.kps1[:w.n1], w.points1[:w.n1], w.mask1[:w.n1], w.pose1)
+    kf2 = (w.kps2[:w.n2], w.points2[:w.n2], w.mask2[:w.n2], w.pose2)
+    s = orbx.Sim3Solver(kf1, kf2, w.match[:w.n1], w.K, False, extractor=ext2, rand=lambda: next(it))
+    s.SetRansacParameters(0.99, 20, 300)
+    d300 = np.zeros((300, 3), np.int32)
+    d300[:35] = d
+    ref = S.solve(w, d300, 0, sigma2=table)
+    _, inl, n, r = s.find()
+    assert bytes(r) == ref[0].tobytes() and n == ref[0]["n_inliers"] and np.array_equal(inl, ref[3][:w.n1] != 0)
+    assert s.GetEstimatedRotation().tobytes() == ref[1][:9].tobytes() and s.GetEstimatedScale() == ref[1][12]
+
+
+def test_second_setting_matcher_anisotropic_camera_and_five_levels(orbx, ext2):
+    """SearchBySim3 on two truth worlds of 150 and 310 features per keyframe in one batch at the capacity of the larger, under
+    the offset bounds; then the smaller one alone through the host form, at its own count and under the usual bounds.  The
+    context's scale table (5 levels of 1.37) is the worlds'."""
+    assert np.asarray(ext2.GetScaleFactors(), np.float32).tobytes() == S.scale_table(S.NLEVELS_2, S.SCALE_FACTOR_2).tobytes()
+    small = S.make_match_world(130, 140, noise_bits=10, rot=S.ROLL, **S.SECOND)
+    ws = [padded_m(small, 310), S.make_match_world(290, 141, noise_bits=20, s=0.7, rot=S.ROLL, t=(-3.0, 1.5, 0.6), **S.SECOND)]
+    for w in ws:
+        w.bounds, w.scale = BOUNDS_2, small.scale
+    assert ws[1].cap == 310 == ws[1].n[0] and ws[0].n == [150, 150]
+    rows, res = run_match_batch(orbx, ext2, ws)
+    for p, w in enumerate(ws):
+        same_match(rows[p], res[p], S.search_by_sim3(w), "pair %d" % p)
+        assert res[p]["status"] == 0 and res[p]["n_found"] > 0.5 * (~w.truth["have"]).sum()  # not trivial: most partners found
+    assert res[1]["n_out_image_21"] > 10  # (the larger world's baseline takes some of KF2's points out of image 1)
+    w = small
+    n1, n2 = w.n
+    T = lambda p: np.c_[p[:9].reshape(3, 3), p[9:]]  # noqa: E731
+    m, r = ext2.match_sim3(w.kps[0][:n1], w.desc[0][:n1], w.points[0][:n1], w.mask[0][:n1], w.dist[0][:n1], T(w.pose[0]),
+                           w.kps[1][:n2], w.desc[1][:n2], w.points[1][:n2], w.mask[1][:n2], w.dist[1][:n2], T(w.pose[1]), w.sim, w.K,
+                           w.bounds, w.match[:n1], 7.5, 100)
+    ref = S.search_by_sim3(w)
+    assert bytes(r) == ref["res"].tobytes() and np.array_equal(m, ref["matches"][:n1]) and ref["res"]["n_found"] > 30
 
 
 def test_python_sim3solver(orbx, ext, sized):
@@ -508,11 +583,12 @@ def padded_m(w, cap):
     return q
 
 
-def test_match_sim3_host_worlds(orbx, ext):
-    """Every world of the host test, each alone at its own capacity (capacity = count for the truth worlds)."""
+def test_match_sim3_host_worlds(orbx, ext, ext2):
+    """Every world of the host test, each alone at its own capacity (capacity = count for the truth worlds); those of the second
+    setting on its context, whose scale table is theirs."""
     from test_sim3_host import _match_worlds
     for name, (w, th, od) in _match_worlds().items():
-        row, res = run_match_batch(orbx, ext, [w], th, od)
+        row, res = run_match_batch(orbx, ext2 if name.endswith("@2") else ext, [w], th, od)
         same_match(row[0], res[0], S.search_by_sim3(w, th, od), name)
     assert _match_worlds()["w1500"][0].n == [1500, 1500] == [_match_worlds()["w1500"][0].cap] * 2
 

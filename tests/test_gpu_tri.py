@@ -41,7 +41,8 @@ class Batch:
     """Keyframes and pairs in the device layout.  frames: [KeyFrame]; pairs: [(kf1, kf2)]; n / fv_n: the counts the device is told
     (default the true ones); median: [n_frames] or None."""
 
-    def __init__(self, torch, frames, pairs, cap, n=None, fv_n=None, median=None):
+    def __init__(self, torch, frames, pairs, cap, n=None, fv_n=None, median=None, scale_factor=L.SCALE_FACTOR, nlevels=L.NLEVELS):
+        self.scale_factor, self.nlevels = scale_factor, nlevels  # (the pyramid of the context the batch runs on: the restatement's tables)
         self.torch, self.frames, self.pairs, self.cap, self.F, self.P = torch, frames, pairs, cap, len(frames), len(pairs)
         F, P = self.F, self.P
         kps, desc = np.zeros((F, cap), KPD), np.zeros((F, cap, 32), np.uint8)
@@ -110,7 +111,8 @@ class Batch:
 
     def world_of(self, p, K, ori=True):
         f1, f2 = self.pairs[p]
-        return L.World(self.frames[f1], self.frames[f2], K, ori=ori, median=None if self.median is None else float(self.median[f2]))
+        return L.World(self.frames[f1], self.frames[f2], K, ori=ori, median=None if self.median is None else float(self.median[f2]),
+                       scale_factor=self.scale_factor, nlevels=self.nlevels)
 
     def expect_match(self, p, K, ori=True):
         f1, f2 = self.pairs[p]
@@ -145,6 +147,59 @@ def check_tri(b, got, K, rows, what=""):
         assert np.isfinite(got["points"][p]).all() and np.isfinite(got["normal"][p]).all() and np.isfinite(got["dist"][p]).all()
         out.append(e)
     return out
+
+
+# ---- the second setting (pose_ref_lib.SECOND): fx != fy, a context of 5 levels of 1.37 (both calls read the context's tables),
+# KF2 rolled by 89 degrees ----
+
+@pytest.fixture(scope="module")
+def ext2(orbx):
+    e = orbx.ORBextractor(1000, L.SCALE_FACTOR_2, L.NLEVELS_2, 20, 7, max_width=640, max_height=480, max_batch=2, device=0)
+    assert np.asarray(e.GetScaleFactors(), np.float32).tobytes() == L.scale_table(L.NLEVELS_2, L.SCALE_FACTOR_2).tobytes()
+    assert np.asarray(e.GetScaleSigmaSquares(), np.float32).tobytes() == L.sigma2_table(L.NLEVELS_2, L.SCALE_FACTOR_2).tobytes()
+    yield e
+    e.close()
+
+
+def second_setting_worlds():
+    """Two pairs whose first keyframes hold 150 and 310 features: a quiet one, and one with near points, pixel noise of a level's
+    scale and octaves up to four levels apart (every gate of the triangulation rejects some)."""
+    two = dict(rot2=L.ROLL_2, **L.SECOND)
+    return [L.make_world(211, n_points=120, n_random=30, n_distract=15, **two),
+            L.make_world(212, n_points=280, n_random=30, n_distract=30, noise=1.0, depth=(1.5, 6.0), octave_jitter=0.5, octave_spread=4,
+                         centre2=(0.5, 0.1, 0.3), **two)]
+
+
+def test_second_setting_anisotropic_camera_and_five_levels(torch, ext2):
+    """SearchForTriangulation and the triangulation on both pairs in one batch at the capacity of the largest count, each call
+    alone and chained; then both host forms on the smaller pair."""
+    ws = second_setting_worlds()
+    K = ws[0].K
+    assert ws[0].kf1.n == 150 and ws[1].kf1.n == 310 and K.tobytes() == L.K_ANISO.reshape(9).tobytes()
+    cap = max(k.n for w in ws for k in (w.kf1, w.kf2))
+    b = Batch(torch, [ws[0].kf1, ws[0].kf2, ws[1].kf1, ws[1].kf2], [(0, 1), (2, 3)], cap, scale_factor=L.SCALE_FACTOR_2, nlevels=L.NLEVELS_2)
+    got = b.match(ext2, K)
+    e = check_match(b, got, K, True, "second setting")
+    tri = b.triangulate(ext2, K)
+    t = check_tri(b, tri, K, got[0], "second setting")
+    (rows2, res2), tri2 = b.chain(ext2, K)
+    assert rows2.tobytes() == got[0].tobytes() and res2.tobytes() == got[1].tobytes()
+    for f in tri:
+        assert tri2[f].tobytes() == tri[f].tobytes(), f
+    for p, w in enumerate(ws):  # not trivial: matches found, candidates rejected by the epipolar line, points kept
+        assert e[p]["matches12"][:w.kf1.n].tobytes() == w.expected()["match"]["matches12"][:w.kf1.n].tobytes()
+        assert got[1][p]["status"] == 0 and got[1][p]["nmatches"] > 0.7 * len(w.truth) and got[1][p]["n_epiline_rejected"] > 5
+        assert tri["res"][p]["status"] == 0 and tri["res"][p]["n_points"] > 0.6 * len(w.truth)
+    assert tri["res"][1]["n_matches"] - tri["res"][1]["n_points"] > 5  # (the second pair's gates reject)
+    w, x = ws[0], ws[0].expected()
+    T1, T2 = np.c_[w.kf1.pose[:9].reshape(3, 3), w.kf1.pose[9:]], np.c_[w.kf2.pose[:9].reshape(3, 3), w.kf2.pose[9:]]
+    m12, res = ext2.match_triangulation(w.kf1.kps, w.kf1.desc, w.kf1.fv_node, w.kf1.fv_feat, T1, w.kf2.kps, w.kf2.desc, w.kf2.fv_node,
+                                        w.kf2.fv_feat, T2, w.K)
+    assert m12.tobytes() == x["match"]["matches12"][:w.kf1.n].tobytes() and bytes(res) == x["match"]["res"].tobytes()
+    pts, msk, nrm, dst, tres = ext2.triangulate_matches(w.kf1.kps, T1, w.kf2.kps, T2, w.K, m12)
+    tt, n1 = x["tri"], w.kf1.n
+    assert bytes(tres) == tt["res"].tobytes() and msk.tobytes() == tt["mask"][:n1].tobytes() and pts.tobytes() == tt["points"][:n1].tobytes()
+    assert nrm.tobytes() == tt["normal"][:n1].tobytes() and dst.tobytes() == tt["dist"][:n1].tobytes()
 
 
 def batch_of(torch, w, cap):

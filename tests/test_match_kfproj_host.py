@@ -65,7 +65,7 @@ def test_pinned_worlds_cover_the_window_edges(ref):
         assert inside >= 10 and outside >= 10
 
 
-@pytest.mark.parametrize("name", L.WORLDS)
+@pytest.mark.parametrize("name", L.WORLDS + L.WORLDS_2)
 def test_restatement_equals_the_numpy_statement(name):
     """The streaming `dist < bestDist` over a grid walk that skips what is taken equals "rank every candidate by (distance, window
     position), take the first untaken" over a filter of all features."""

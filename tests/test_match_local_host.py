@@ -64,7 +64,7 @@ def test_pinned_worlds_cover_the_window_edges(ref):
         assert inside >= 10 and outside >= 10
 
 
-@pytest.mark.parametrize("name", L.WORLDS)
+@pytest.mark.parametrize("name", L.WORLDS + L.WORLDS_2)
 def test_restatement_equals_the_numpy_statement(name):
     """The streaming update of bestDist / bestDist2 over a grid walk equals "the two smallest under (distance, window position)"
     over a filter of all features."""

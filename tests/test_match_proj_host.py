@@ -57,7 +57,7 @@ def test_pinned_worlds_cover_the_window_edges(ref):
         assert inside >= 10 and outside >= 10
 
 
-@pytest.mark.parametrize("name", M.WORLDS)
+@pytest.mark.parametrize("name", M.WORLDS + M.WORLDS_2)
 def test_restatement_equals_the_numpy_statement(name):
     w = M.world(name)
     e = w.expected()

@@ -62,7 +62,26 @@ def _worlds():
     d = Q.make_draws(35, 8)
     d[1] = draws_for([0, 1, 2, 3], len(jj))
     W["collinear"] = (w, d)
+    # the second setting (pose_ref_lib: K_ANISO, 5 levels of 1.37, a true pose rolled by 89 degrees), solved under SIGMA2_2
+    two = dict(motion=Q.MOTION_2, **Q.SECOND)
+    W["clean@2"] = (Q.make_world(90, 401, outliers=18, noise=0.0, **two), Q.make_draws(35, 1))
+    W["clean_matched@2"] = (Q.make_world(70, 402, outliers=14, noise=0.0, matched=True, **two), Q.make_draws(35, 2))
+    W["noisy@2"] = (Q.make_world(100, 403, outliers=20, noise=0.5, **two), Q.make_draws(35, 1))
+    for seed in range(410, 413):
+        W["mixed%d@2" % seed] = (Q.make_world(50, seed, outliers=10, noise=0.5, **two), Q.make_draws(35, seed - 410))
     return W
+
+
+SIGMA2_2 = Q.sigma2_table(Q.NLEVELS_2, Q.SCALE_FACTOR_2)
+
+
+def _sigma2(name):
+    """The sigma2 table a world is solved under: the second setting's for the names that end in @2."""
+    return SIGMA2_2 if name.endswith("@2") else None
+
+
+def _of(setting, names):
+    return names if setting == "first" else tuple(n + "@2" for n in names)
 
 
 @pytest.fixture(scope="module")
@@ -73,7 +92,7 @@ def worlds():
 @pytest.fixture(scope="module")
 def results(worlds):
     """name -> (literal loop's outputs, prefix resolution's outputs)"""
-    return {name: (Q.solve(w, d, 0), Q.solve(w, d, 1)) for name, (w, d) in worlds.items()}
+    return {name: (Q.solve(w, d, 0, _sigma2(name)), Q.solve(w, d, 1, _sigma2(name))) for name, (w, d) in worlds.items()}
 
 
 # ---- ABI ----
@@ -184,17 +203,17 @@ def test_sampler_against_a_literal_swap_and_pop():
 
 # ---- against truth ----
 
-def test_noise_free_worlds_return_exactly_the_clean_set(worlds, results):
-    for name in ("clean", "clean_matched"):
+def test_noise_free_worlds_return_exactly_the_clean_set(worlds, results, setting="first"):
+    for name in _of(setting, ("clean", "clean_matched")):
         w, _ = worlds[name]
         r, pose, row, inl = results[name][0]
         assert r["status"] == 0 and r["refined"] == 1 and r["found_it"] >= 0
         assert np.array_equal(np.flatnonzero(inl), w.truth["clean"]), name
         assert r["n_inliers"] == len(w.truth["clean"])
         j, e2 = Q.error2(w, r["R"], r["t"], w.truth["clean"])
-        assert (e2 < Q.max_error(w, j)).all()
+        assert (e2 < Q.max_error(w, j, sigma2=_sigma2(name))).all()
         jb, eb = Q.error2(w, r["R"], r["t"], w.truth["bad"])
-        assert (eb > Q.max_error(w, jb)).all()
+        assert (eb > Q.max_error(w, jb, sigma2=_sigma2(name))).all()
         # the row is the pose call's d_match for the inliers
         jj, ii = w.edges()
         want = np.full(w.cap, -1, np.int32)
@@ -204,20 +223,22 @@ def test_noise_free_worlds_return_exactly_the_clean_set(worlds, results):
         assert pose.tobytes() == r["Tcw"].tobytes() == np.r_[r["R"].reshape(9), r["t"]].astype(np.float32).tobytes()
 
 
-def test_every_returned_inlier_passes_when_recomputed(worlds, results):
+def test_every_returned_inlier_passes_when_recomputed(worlds, results, setting="first"):
     """On worlds with 0.5 sigma of noise: error2 < maxError in numpy at the returned pose, but for points within 1e-4 relative of
     the threshold (at most 2 %)."""
-    for name in ("noisy", "noisy_b", "second_try", "mixed300", "mixed303"):
+    first = ("noisy", "noisy_b", "second_try", "mixed300", "mixed303")
+    for name in (first if setting == "first" else ("noisy@2", "mixed410@2", "mixed411@2", "mixed412@2")):
         w, _ = worlds[name]
         r, _, _, inl = results[name][0]
         assert r["status"] == 0 and r["n_inliers"] == inl.sum() > 0
         j, e2 = Q.error2(w, r["R"], r["t"], np.flatnonzero(inl))
-        th = Q.max_error(w, j).astype(np.float64)
+        th = Q.max_error(w, j, sigma2=_sigma2(name)).astype(np.float64)
         near = np.abs(e2 - th) <= 1e-4 * th
+        print(name, "inliers", len(j), "within 1e-4 of the threshold", int(near.sum()))
         assert near.mean() <= 0.02, name
         assert (e2[~near] < th[~near]).all(), name
         jo, eo = Q.error2(w, r["R"], r["t"], np.setdiff1d(w.edges()[0], np.flatnonzero(inl)))
-        tho = Q.max_error(w, jo).astype(np.float64)
+        tho = Q.max_error(w, jo, sigma2=_sigma2(name)).astype(np.float64)
         far = np.abs(eo - tho) > 1e-4 * tho
         assert (eo[far] >= tho[far]).all(), name
 
@@ -225,22 +246,33 @@ def test_every_returned_inlier_passes_when_recomputed(worlds, results):
 # ---- against the numpy statement ----
 
 NUMPY_WORLDS = ("clean", "clean_matched", "noisy", "noisy_b", "mixed300", "mixed301", "mixed302", "mixed303", "mixed304", "mixed305")
+NUMPY_WORLDS_2 = ("clean@2", "clean_matched@2", "noisy@2", "mixed410@2", "mixed411@2", "mixed412@2")
 
-def test_refine_agrees_with_the_numpy_statement(worlds, results):
+
+def test_refine_agrees_with_the_numpy_statement(worlds, results, setting="first"):
     """compute_pose over the returned inlier set against epnp_numpy over the same set, under the control points' signs that
     come closest (with noise EPnP depends on them beyond rounding, and they are the eigen-solver's to choose)."""
     worst = [0.0, 0.0]
-    for name in NUMPY_WORLDS:
+    for name in (NUMPY_WORLDS if setting == "first" else NUMPY_WORLDS_2):
         w, _ = worlds[name]
         inl = results[name][0][3]
         assert inl.sum() >= 20
-        c, R, t = Q.epnp(w, inl)
+        c, R, t = Q.epnp(w, inl, _sigma2(name))
         assert c in (1, 2, 3)
         da, dt = Q.closest_numpy(w, inl, R, t)
         print(name, "angle", da, "translation", dt)
         worst = [max(worst[0], da), max(worst[1], dt)]
     print("largest: angle %.3g rad, relative translation %.3g" % tuple(worst))
-    assert worst[0] <= Q.NUMPY_ANGLE_LIMIT and worst[1] <= Q.NUMPY_TRANS_LIMIT
+    limit = (Q.NUMPY_ANGLE_LIMIT, Q.NUMPY_TRANS_LIMIT) if setting == "first" else (Q.NUMPY_ANGLE_LIMIT_2, Q.NUMPY_TRANS_LIMIT_2)
+    assert worst[0] <= limit[0] and worst[1] <= limit[1]
+
+
+def test_the_second_setting_against_the_truth_and_numpy(worlds, results):
+    """The clean set, the recomputed inliers and Refine against epnp_numpy under the second setting (the worlds named @2: K_ANISO,
+    5 levels of 1.37, a true pose rolled by 89 degrees)."""
+    test_noise_free_worlds_return_exactly_the_clean_set(worlds, results, "second")
+    test_every_returned_inlier_passes_when_recomputed(worlds, results, "second")
+    test_refine_agrees_with_the_numpy_statement(worlds, results, "second")
 
 
 # ---- the prefix resolution ----

@@ -33,6 +33,12 @@ GN_MEASURED = 1.4e-11
 # The same measurement over CACHE_STEP_WORLDS (cache_full, 700 edges: 1.95e-11; cache_skewed, 24 edges: 1.7e-11), likewise
 # against the numpy statement; their first steps stay below STEP_MEASURED (cache_full 2.3e-6, cache_skewed 6.1e-7).
 GN_MEASURED_CACHE = 2.0e-11
+# The same two measurements over the worlds of the second setting (pose_ref_lib.SECOND_WORLDS: K_ANISO, 5 levels of 1.37, a true
+# pose rolled by 89 degrees), each under this file's margin of 100: the first step (the largest: matched, 1.05e-5) and the
+# Gauss-Newton pose (the largest: noisy, 1.54e-10).
+STEP_MEASURED_2 = 1.06e-5
+GN_MEASURED_2 = 1.6e-10
+SECOND_STEP_WORLDS = tuple(P.SECOND_WORLDS)
 
 
 @pytest.fixture(scope="module")
@@ -46,6 +52,12 @@ def results():
 
 
 @pytest.fixture(scope="module")
+def results2():
+    """{world: (result, flags, flags per round, counters)} under the second setting (10 iterations), computed once."""
+    return {name: P.pose_optimize(P.world(name, "second"), 10, P.inv_sigma2_of("second")) for name in SECOND_STEP_WORLDS}
+
+
+@pytest.fixture(scope="module")
 def failing():
     """{world: (result, flags, flags per round, counters)} of the worlds whose solves fail, each under its table."""
     return {name: P.pose_optimize(P.world(name), 10, P.table_of(name)) for name in FAILING_WORLDS}
@@ -55,29 +67,30 @@ def _rel(a, b):
     return float(np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(np.asarray(b)).max())
 
 
-def test_first_step_agrees_with_the_numpy_statement():
+def test_first_step_agrees_with_the_numpy_statement(setting="first"):
     """The pose Jacobian, Huber's weights, the 6x6 system, lambda and the solve against numerically differentiated residuals
     and numpy.linalg.solve of the damped normal equations."""
-    worst = 0.0
-    for name in STEP_WORLDS + CACHE_STEP_WORLDS:
-        w = P.world(name)
-        a, b = P.first_step(w), P.first_step_numpy(w)
+    worst, sig = 0.0, P.inv_sigma2_of(setting)
+    for name in (STEP_WORLDS + CACHE_STEP_WORLDS if setting == "first" else SECOND_STEP_WORLDS):
+        w = P.world(name, setting)
+        a, b = P.first_step(w, sig), P.first_step_numpy(w, sig)
         assert a is not None and a["n"] == len(w.edges()[0]), name
         d = max(_rel(a["xp"], b["xp"]), _rel([a["chi2_initial"]], [b["chi2_initial"]]), _rel([a["lam"]], [b["lam"]]))
         print(name, "largest relative difference:", d)
         worst = max(worst, d)
-    assert worst <= 100 * STEP_MEASURED
+    assert worst <= 100 * (STEP_MEASURED if setting == "first" else STEP_MEASURED_2)
 
 
-def test_round_three_ends_where_gauss_newton_converges(results):
+def test_round_three_ends_where_gauss_newton_converges(results, results2):
     """Round 3 has no Huber: its pose against an independent Gauss-Newton over the same edges."""
-    for worlds, measured in ((STEP_WORLDS, GN_MEASURED), (CACHE_STEP_WORLDS, GN_MEASURED_CACHE)):
+    for worlds, measured in ((STEP_WORLDS, GN_MEASURED), (CACHE_STEP_WORLDS, GN_MEASURED_CACHE), (SECOND_STEP_WORLDS, GN_MEASURED_2)):
         worst = 0.0
+        second = worlds is SECOND_STEP_WORLDS
         for name in worlds:
-            w = P.world(name)
-            r, _, per_round, _ = results[name, 10]
+            w = P.world(name, "second" if second else "first")
+            r, _, per_round, _ = results2[name] if second else results[name, 10]
             assert r["rounds"] == 4 and r["iterations"][3] > 0
-            R, t = P.gauss_newton_numpy(w, per_round[2] == 0)
+            R, t = P.gauss_newton_numpy(w, per_round[2] == 0, P.inv_sigma2_of("second" if second else "first"))
             d = max(_rel(P.quat_to_matrix(r["q"]), R), _rel(r["t"], t))
             print(name, "largest relative difference:", d)
             worst = max(worst, d)
@@ -99,10 +112,11 @@ def test_properties_without_a_tolerance(results):
         assert all(0 <= i <= it for i in r["iterations"]), name
 
 
-def test_planted_mismatches_are_flagged_and_nothing_else(results):
-    for name in ("clean", "matched", "far", "truth", "converged", "nine", "cache_edge", "cache_skewed", "cache_holes"):
-        w = P.world(name)
-        _, flags, _, _ = results[name, 10]
+def test_planted_mismatches_are_flagged_and_nothing_else(results, results2=None, setting="first"):
+    first = ("clean", "matched", "far", "truth", "converged", "nine", "cache_edge", "cache_skewed", "cache_holes")
+    for name in (first if setting == "first" else ("clean", "matched", "far", "truth")):
+        w = P.world(name, setting)
+        _, flags, _, _ = results[name, 10] if setting == "first" else results2[name]
         assert flags[w.truth["bad"]].all(), name
         assert not flags[w.truth["clean"]].any(), name
 
@@ -111,15 +125,23 @@ def _angle(Ra, Rb):
     return float(np.degrees(np.arccos(np.clip((np.trace(Ra.T @ Rb) - 1) / 2, -1.0, 1.0))))
 
 
-def test_the_pose_moves_towards_the_truth(results):
-    for name in ("clean", "matched", "far", "truth") + CACHE_WORLDS:
-        w = P.world(name)
-        r = results[name, 10][0]
+def test_the_pose_moves_towards_the_truth(results, results2=None, setting="first"):
+    for name in ("clean", "matched", "far", "truth") + (CACHE_WORLDS if setting == "first" else ()):
+        w = P.world(name, setting)
+        r = (results[name, 10] if setting == "first" else results2[name])[0]
         R0, t0 = w.pose0[:9].reshape(3, 3).astype(np.float64), w.pose0[9:].astype(np.float64)
         assert _angle(r["R"].astype(np.float64), w.truth["R"]) < _angle(R0, w.truth["R"]), name
         assert np.linalg.norm(r["tcw"] - w.truth["t"]) < np.linalg.norm(t0 - w.truth["t"]), name
-    r = results["truth", 10][0]
-    assert _angle(r["R"].astype(np.float64), P.world("truth").truth["R"]) < 0.05
+    r = (results["truth", 10] if setting == "first" else results2["truth"])[0]
+    assert _angle(r["R"].astype(np.float64), P.world("truth", setting).truth["R"]) < 0.05
+
+
+def test_the_second_setting_against_numpy_and_the_truth(results2):
+    """The three tests above under the second setting (pose_ref_lib.SECOND_WORLDS: K_ANISO, 5 levels of 1.37, a true pose
+    rolled by 89 degrees)."""
+    test_first_step_agrees_with_the_numpy_statement("second")
+    test_planted_mismatches_are_flagged_and_nothing_else(None, results2, "second")
+    test_the_pose_moves_towards_the_truth(None, results2, "second")
 
 
 def _returned_as_given(r, flags, w, status):

@@ -97,7 +97,16 @@ def _worlds():
     W["below_min"] = (S.make_world(19, 11), S.make_draws(30, 11), {})
     W["three"] = (S.make_world(3, 12), S.make_draws(30, 12), dict(min_inliers=3))
     W["empty"] = (S.make_world(0, 13, cap=8), S.make_draws(30, 13), {})
+    # the second setting (pose_ref_lib: K_ANISO, 5 levels of 1.37), camera 1 rolled by 89 degrees against camera 2
+    two = dict(rot=S.ROLL, **S.SECOND)
+    W["truth@2"] = (S.make_world(80, 102, **two), S.make_draws(40, 2), dict(sigma2=SIGMA2_2))
+    W["clean@2"] = (S.make_world(120, 101, outliers=24, noise=0.5, **two), S.make_draws(300, 1), dict(sigma2=SIGMA2_2))
+    W["fix_scale_noisy@2"] = (S.make_world(100, 105, s=1.0, outliers=20, noise=0.5, **two), S.make_draws(300, 5),
+                              dict(fix_scale=1, sigma2=SIGMA2_2))
     return W
+
+
+SIGMA2_2 = S.sigma2_table(S.NLEVELS_2, S.SCALE_FACTOR_2)
 
 
 @pytest.fixture(scope="module")
@@ -218,7 +227,7 @@ def test_sampler_against_a_literal_swap_and_pop():
 
 # ---- ground truth ----
 
-@pytest.mark.parametrize("name", ["truth", "truth_far", "fix_scale", "identity"])
+@pytest.mark.parametrize("name", ["truth", "truth_far", "fix_scale", "identity", "truth@2"])
 def test_noise_free_worlds_return_the_clean_set_and_the_true_similarity(worlds, name):
     """A noise-free world solved from a well-spread triple: every correspondence is an inlier, and s12, R12, t12 equal the truth
     to a tolerance DERIVED from the f32 inputs (not tuned against the code):
@@ -259,7 +268,7 @@ def test_noise_free_worlds_return_the_clean_set_and_the_true_similarity(worlds, 
 
 
 def test_noisy_worlds_keep_the_clean_and_drop_the_gross(worlds, results):
-    for name in ("clean", "fix_scale_noisy", "hard", "no_mask"):
+    for name in ("clean", "fix_scale_noisy", "hard", "no_mask", "clean@2", "fix_scale_noisy@2"):
         w = worlds[name][0]
         res, sim, row, inl = results[name][0]
         assert res["status"] == 0 and res["found_it"] >= 0 and res["n_inliers"] > 20, name
@@ -281,7 +290,8 @@ BAND = 1e-3  # relative half-width of the excluded band around a bound.  The f32
 # px); the bounds are at d = 3 px and more, so err = d^2 is off by at most 2 * 4e-4 / 3 = 3e-4 relative.
 
 
-@pytest.mark.parametrize("name", ["clean", "truth", "fix_scale_noisy", "hard", "no_mask", "identity", "collinear"])
+@pytest.mark.parametrize("name", ["clean", "truth", "fix_scale_noisy", "hard", "no_mask", "identity", "collinear", "truth@2", "clean@2",
+                                  "fix_scale_noisy@2"])
 def test_inlier_decisions_agree_with_the_numpy_statement(worlds, results, name):
     """The winning hypothesis again in numpy f64 from the raw inputs: the sampler as a list, Horn through eigh, the two
     reprojections.  Every inlier decision agrees away from the thresholds; the band excludes at most 1 % of the world's
@@ -294,7 +304,7 @@ def test_inlier_decisions_agree_with_the_numpy_statement(worlds, results, name):
     s, R, t = S.horn_numpy(Y1[tr], Y2[tr], bool(prm.get("fix_scale")))
     rot, scale, trans = S.sim_difference(sim[12], sim[:9].reshape(3, 3), sim[9:12], s, R, t)
     e1, e2 = S.errors_numpy(Y1, Y2, s, R, t, w.K)
-    sig = S.sigma2_table().astype(np.float64)
+    sig = (S.sigma2_table() if prm.get("sigma2") is None else prm["sigma2"]).astype(np.float64)
     b1, b2 = 9.210 * sig[w.kps1["octave"][i1]], 9.210 * sig[w.kps2["octave"][i2]]
     near = (np.abs(e1 / b1 - 1) < BAND) | (np.abs(e2 / b2 - 1) < BAND)
     assert near.sum() <= 0.01 * len(i1), (name, int(near.sum()))
@@ -340,7 +350,7 @@ def test_every_result_is_consistent_with_its_hypotheses(worlds, results):
         if res["status"] & (S.FEW_POINTS | S.BAD_INPUT | S.NONFINITE):
             assert res["its_run"] == 0 and res["found_it"] == -1 and res["best_it"] == -1
             continue
-        N, counts, flags, sims = S.hypotheses(w, d, fix_scale=prm.get("fix_scale", 0))
+        N, counts, flags, sims = S.hypotheses(w, d, sigma2=prm.get("sigma2"), fix_scale=prm.get("fix_scale", 0))
         assert N == res["n_correspondences"]
         best, best_count, found = -1, 0, -1
         n_its = min(len(d), res["max_its"])
@@ -460,7 +470,7 @@ def test_every_returned_inlier_passes_when_recomputed(worlds, results):
         res, sim, row, inl = results[name][0]
         if res["found_it"] < 0:
             continue
-        e = S.errors(w, sim)
+        e = S.errors(w, sim, sigma2=prm.get("sigma2"))
         assert np.array_equal(e["inlier"], inl[e["i1"]] != 0), name
         ok = (e["err"][:, 0] < e["err"][:, 2]) & (e["err"][:, 1] < e["err"][:, 3])
         assert np.array_equal(ok, e["inlier"]) and ok.sum() == res["n_inliers"], name
@@ -604,6 +614,9 @@ def _match_worlds():
     W["w1500"] = (S.make_match_world(1300, 5, extra=200, noise_bits=20), 7.5, 100)
     W["empty1"] = (_emptied(S.make_match_world(100, 6), 0), 7.5, 100)
     W["empty2"] = (_emptied(S.make_match_world(100, 6), 1), 7.5, 100)
+    # the second setting: K_ANISO, 5 levels of 1.37 (the world carries its scale table), KF1 rolled by 89 degrees against KF2
+    W["truth@2"] = (S.make_match_world(150, 101, rot=S.ROLL, **S.SECOND), 7.5, 100)
+    W["truth_noisy@2"] = (S.make_match_world(120, 102, noise_bits=30, s=0.7, rot=S.ROLL, t=(-0.3, 0.2, 0.6), **S.SECOND), 7.5, 100)
     W["disagree"] = (_disagree_world(), 7.5, 100)
     W["two_on_one"] = (_two_on_one_world(), 7.5, 100)
     W["behind_and_out"] = (_behind_world(), 7.5, 100)
@@ -703,7 +716,7 @@ def test_msim3_refusals_without_a_context(orbx):
     assert host(n1=16385) == orbx.E_CAPACITY
 
 
-@pytest.mark.parametrize("name", ["truth", "truth_noisy", "truth_pdesc", "w1500"])
+@pytest.mark.parametrize("name", ["truth", "truth_noisy", "truth_pdesc", "w1500", "truth@2", "truth_noisy@2"])
 def test_truth_worlds_give_every_unmatched_point_its_partner(name):
     w, th, od = _match_worlds()[name]
     e = S.search_by_sim3(w, th, od)

@@ -24,7 +24,7 @@ K2 = L.K_POW2
 
 # ---- 1. two statements, the same worlds ----
 
-@pytest.mark.parametrize("name", L.WORLDS)
+@pytest.mark.parametrize("name", L.WORLDS + L.WORLDS_2)
 def test_restatement_equals_numpy_statement(name):
     w = L.world(name)
     e = w.expected()
@@ -64,8 +64,8 @@ def test_restatement_equals_numpy_statement(name):
     assert not t["points"][off].any() and not t["normal"][off].any() and not t["dist"][off].any()
 
 
-def test_noise_free_world_recovers_ground_truth():
-    w = L.world("noise_free")
+def test_noise_free_world_recovers_ground_truth(name="noise_free"):
+    w = L.world(name)
     e = w.expected()
     m, t = e["match"]["matches12"], e["tri"]
     right = [i for i, (j, _) in w.truth.items() if m[i] == j and t["outcome"][i] == L.KEPT]
@@ -76,6 +76,10 @@ def test_noise_free_world_recovers_ground_truth():
     assert rel.max() <= REL_BOUND
     # and no wrong match survives both calls on exact projections
     assert all(m[i] == w.truth[i][0] for i in np.flatnonzero(t["outcome"][:w.kf1.n] == L.KEPT) if i in w.truth)
+
+
+def test_noise_free_world_of_the_second_setting_recovers_ground_truth():
+    test_noise_free_world_recovers_ground_truth("noise_free@2")
 
 
 def test_worlds_reach_every_path():

@@ -17,6 +17,7 @@ import tempfile
 import numpy as np
 
 import match_proj_ref_lib as M
+from pose_ref_lib import K_ANISO, NLEVELS_2, SCALE_FACTOR_2, SECOND, SETTINGS  # noqa: F401 (the second setting)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "tri_ref.cpp")
@@ -44,14 +45,12 @@ f32 = np.float32
 _L = None
 
 
-def lib() -> ctypes.CDLL:
-    global _L
-    if _L is not None:
-        return _L
+def build(src=SRC) -> ctypes.CDLL:
+    """Compiles a restatement source (lib(): the committed one; tests/test_camera_mutants_host.py: an altered copy) and binds it."""
     d = tempfile.mkdtemp(prefix="tri_ref_")
     atexit.register(shutil.rmtree, d, True)
     so = os.path.join(d, "libtri_ref.so")
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", so]
+    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", src, "-o", so]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("tri_ref.cpp does not compile:\n" + p.stdout)
@@ -63,8 +62,14 @@ def lib() -> ctypes.CDLL:
     L.trr_triangulate_matches.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, fl, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.trr_triangulate_matches.restype = None
     L.trr_triangulate_one.argtypes = [vp, vp, vp, vp, vp, vp, vp, fl, fl, fl, fl, fl, fl, vp]
-    _L = L
     return L
+
+
+def lib() -> ctypes.CDLL:
+    global _L
+    if _L is None:
+        _L = build()
+    return _L
 
 
 def _p(a):
@@ -399,10 +404,10 @@ K_POW2 = np.array([512.0, 0, 256.0, 0, 512.0, 256.0, 0, 0, 1], np.float32)  # (c
 WIDTH, HEIGHT = 640, 480
 
 
-def keypoints(x, y, octave, angle):
+def keypoints(x, y, octave, angle, nlevels=NLEVELS, scale_factor=SCALE_FACTOR):
     k = np.zeros(len(x), KEYPOINT_DTYPE)
     k["x"], k["y"], k["octave"], k["angle"] = x, y, octave, angle
-    k["size"] = 31.0 * scale_table()[np.clip(octave, 0, NLEVELS - 1)]
+    k["size"] = 31.0 * scale_table(nlevels, scale_factor)[np.clip(octave, 0, nlevels - 1)]
     k["response"], k["class_id"] = 1.0, -1
     return k
 
@@ -416,15 +421,16 @@ def flip(desc, rng, n_bits):
 
 
 def make_world(seed, n_points=220, n_nodes=48, noise=0.35, n_distract=40, n_random=30, centre2=(0.6, 0.05, 0.1), rot2=((0.1, 1.0, 0.2), 4.0),
-               depth=(4.0, 12.0), ori=True, masked=0.0, median=None, big_node=0, octave_jitter=0.1, octave_spread=1, K=K_DEFAULT, angle_outliers=0.08):
+               depth=(4.0, 12.0), ori=True, masked=0.0, median=None, big_node=0, octave_jitter=0.1, octave_spread=1, K=K_DEFAULT, angle_outliers=0.08,
+               scale_factor=SCALE_FACTOR, nlevels=NLEVELS, rot1=((0.3, -0.2, 1.0), 1.5)):
     """Two keyframes that see n_points 3D points (KF2's copies carry pixel noise of `noise` * the level's scale and a few flipped
     descriptor bits), n_distract KF2 features that copy a KF1 feature's descriptor at a random place of its node, n_random
     features of their own in each keyframe; every feature in a random order.  big_node > 0 puts that many of the points under one
     node.  masked: the share of features of either keyframe that already have a map point."""
     rng = np.random.default_rng(seed)
-    sc = scale_table().astype(np.float64)
+    sc = scale_table(nlevels, scale_factor).astype(np.float64)
     Kd = np.asarray(K, np.float64).reshape(3, 3)
-    R1, C1 = rot((0.3, -0.2, 1.0), 1.5), np.array([0.02, -0.01, 0.03])
+    R1, C1 = rot(*rot1), np.array([0.02, -0.01, 0.03])
     R2, C2 = rot(*rot2), np.asarray(centre2, np.float64)
     pose1, pose2 = pose12(R1, C1), pose12(R2, C2)
     f1, f2 = [], []  # (x, y, octave, angle, desc, node, point id or -1)
@@ -441,8 +447,8 @@ def make_world(seed, n_points=220, n_nodes=48, noise=0.35, n_distract=40, n_rand
         u2, v2 = p2[0] / p2[2], p2[1] / p2[2]
         if not (10 < u2 < WIDTH - 10 and 10 < v2 < HEIGHT - 10):
             continue
-        o1 = int(min(NLEVELS - 1, rng.geometric(0.35) - 1))
-        o2 = int(np.clip(o1 + (rng.integers(-octave_spread, octave_spread + 1) if rng.random() < octave_jitter else 0), 0, NLEVELS - 1))
+        o1 = int(min(nlevels - 1, rng.geometric(0.35) - 1))
+        o2 = int(np.clip(o1 + (rng.integers(-octave_spread, octave_spread + 1) if rng.random() < octave_jitter else 0), 0, nlevels - 1))
         ang = rng.uniform(0, 360)
         ang2 = rng.uniform(0, 360) if rng.random() < angle_outliers else (ang - 12.0 + rng.normal(0, 2.0)) % 360.0
         d = rng.integers(0, 256, 32, dtype=np.uint8)
@@ -457,32 +463,50 @@ def make_world(seed, n_points=220, n_nodes=48, noise=0.35, n_distract=40, n_rand
                    flip(src[4], rng, int(rng.integers(20, 45))), src[5], -1, None))
     for f in (f1, f2):
         for _ in range(n_random):
-            f.append((rng.uniform(10, WIDTH - 10), rng.uniform(10, HEIGHT - 10), int(rng.integers(0, NLEVELS)), rng.uniform(0, 360),
+            f.append((rng.uniform(10, WIDTH - 10), rng.uniform(10, HEIGHT - 10), int(rng.integers(0, nlevels)), rng.uniform(0, 360),
                       rng.integers(0, 256, 32, dtype=np.uint8), 1000 + 7 * int(rng.integers(0, n_nodes + 6)), -1, None))
     kfs, index = [], []
     for f, pose in ((f1, pose1), (f2, pose2)):
         order = rng.permutation(len(f))
         f = [f[k] for k in order]
         kps = keypoints(np.array([e[0] for e in f], f32), np.array([e[1] for e in f], f32), np.array([e[2] for e in f], np.int32),
-                        np.array([e[3] for e in f], f32))
+                        np.array([e[3] for e in f], f32), nlevels, scale_factor)
         mask = (rng.random(len(f)) < masked).astype(np.uint8) if masked > 0 else None
         kfs.append(KeyFrame.from_nodes(kps, np.stack([e[4] for e in f]), [e[5] for e in f], pose, mask))
         index.append({e[6]: (k, e[7]) for k, e in enumerate(f) if e[6] >= 0})
     truth = {i: (index[1][p][0], X) for p, (i, X) in index[0].items()}
-    return World(kfs[0], kfs[1], K, ori=ori, median=median, truth=truth)
+    return World(kfs[0], kfs[1], K, ori=ori, median=median, truth=truth, scale_factor=scale_factor, nlevels=nlevels)
 
 
 _WORLDS = {}
 WORLDS = ("small_nodes", "big_node", "forward", "masked", "noise_free", "dense", "mixed")
 
 
+# the second setting: K_ANISO, 5 levels of 1.37, KF2 rolled by 89 degrees against KF1; the same seven kinds, smaller
+WORLDS_2 = tuple(n + "@2" for n in WORLDS)
+ROLL_2 = ((0.04, -0.03, 1.0), 89.0)
+
+
 def world(name):
-    """The committed worlds, built once.  small_nodes: 48 nodes of a handful of features (more nodes than the kernel has waves);
+    """The committed worlds, built once.  name@2: the world of that kind under the second setting (WORLDS_2).  small_nodes: 48 nodes of a handful of features (more nodes than the kernel has waves);
     big_node: one node of some 100 KF2 features (the chunked path) among the small ones; forward: KF2 ahead of KF1, the epipole
     inside the image; masked: a third of either keyframe's features already have map points; noise_free: exact projections
     (the ground-truth world); dense: 600 points, more than 256 matches per pair; mixed: near points, pixel noise of a level's scale
     and octaves up to five levels apart between the views, so that the line test, the reprojection gates and the scale gate all
     reject some."""
+    if name not in _WORLDS and name.endswith("@2"):
+        two = dict(rot2=ROLL_2, **SECOND)
+        _WORLDS[name] = {
+            "small_nodes@2": lambda: make_world(111, n_points=120, n_nodes=70, n_distract=20, n_random=15, **two),
+            "big_node@2": lambda: make_world(112, n_points=150, big_node=90, n_distract=20, n_random=15, **two),
+            "forward@2": lambda: make_world(113, n_points=120, n_distract=20, n_random=15, centre2=(0.03, -0.02, 1.2), depth=(4.0, 10.0), **two),
+            "masked@2": lambda: make_world(114, n_points=120, n_distract=20, n_random=15, masked=0.33, **two),
+            "noise_free@2": lambda: make_world(115, n_points=120, noise=0.0, n_distract=10, n_random=15, octave_jitter=0.0, depth=(2.0, 4.0),
+                                               centre2=(1.0, 0.1, 0.1), **two),
+            "dense@2": lambda: make_world(116, n_points=330, n_nodes=90, n_distract=30, **two),
+            "mixed@2": lambda: make_world(124, n_points=150, n_distract=20, n_random=15, noise=1.0, depth=(1.5, 6.0), octave_jitter=0.5,
+                                          octave_spread=4, centre2=(0.5, 0.1, 0.3), **two),
+        }[name]()
     if name not in _WORLDS:
         _WORLDS[name] = {
             "small_nodes": lambda: make_world(11),
