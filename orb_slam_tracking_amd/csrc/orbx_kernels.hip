@@ -740,15 +740,16 @@ __device__ __forceinline__ void fwStoreB8(const uint32_t addr, const uint32_t va
                : "s"(m), "v"(addr), "v"(val)
                : "memory");
 }
-// ballots of the sign bits of a packed pair of 16-bit values: one compare each
-__device__ __forceinline__ unsigned long long fwNegLo(const uint32_t x) {
+// ballots of "half > threshold" of a packed pair of signed 16-bit values against a scalar: one compare each.  The low half against
+// the scalar's low 16 bits; the high half as the whole dword against th << 16 | 0xffff
+__device__ __forceinline__ unsigned long long fwGtLo(const uint32_t x, const uint32_t thLo) {
   unsigned long long m;
-  asm("v_cmp_gt_i16_e64 %0, 0, %1" : "=s"(m) : "v"(x));
+  asm("v_cmp_lt_i16_e64 %0, %1, %2" : "=s"(m) : "s"(thLo), "v"(x));
   return m;
 }
-__device__ __forceinline__ unsigned long long fwNegHi(const uint32_t x) {
+__device__ __forceinline__ unsigned long long fwGtHi(const uint32_t x, const uint32_t thHi) {
   unsigned long long m;
-  asm("v_cmp_gt_i32_e64 %0, 0, %1" : "=s"(m) : "v"(x));
+  asm("v_cmp_lt_i32_e64 %0, %1, %2" : "=s"(m) : "s"(thHi), "v"(x));
   return m;
 }
 
@@ -895,17 +896,19 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   int nOut = 0;
   for (int pass = 0; pass < 2; pass++) {
     const int th = pass == 0 ? g.iniTh : g.minTh;
-    const uint32_t th2 = (uint32_t)th * 0x00010001u;
+    // the quick reject's compare operands: a u16 pair's low half against th, its high half (the pair read as one i32) against
+    // th << 16 | 0xffff -- the low half, whatever it holds, cannot lift an equal high half above that
+    const uint32_t thLo = (uint32_t)th, thHi = ((uint32_t)th << 16) | 0xffffu;
     const int thB = th + (int)FAST_PK_BIAS;
     int nList = 0, nCorn = 0;  // wave-uniform (SGPRs)
     // A cell without a survivor at iniThFAST is swept again at minThFAST (cpp:1117-1123) -- on real images that is every second
     // cell, and in a flat region the second sweep lists nothing either.  While the first sweep has not listed a pixel yet (`flat`,
-    // wave-uniform), it also keeps the minimum of its two test values e = (v + th) - max side and (min side + th) - v: a pixel
-    // passes the quick reject at minThFAST iff e < iniTh - minTh, so a cell whose sweep ends `flat` with every minimum at or above
-    // that difference could not list a single pixel at minThFAST and is not swept again.  Pixels beyond a row's end and idle lanes
-    // are not masked out of the minimum: a false "some pixel passes" only costs the second sweep, which then decides as before.
+    // wave-uniform), it also keeps the maximum of its test value d = max(max side - v, v - min side): a pixel passes the quick
+    // reject at a threshold iff d is above it, so a cell whose sweep ends `flat` with every maximum at or below minThFAST
+    // could not list a single pixel at minThFAST and is not swept again.  Pixels beyond a row's end and idle lanes
+    // are not masked out of the maximum: a false "some pixel passes" only costs the second sweep, which then decides as before.
     bool flat = pass == 0;
-    short2v looseMin = {0x7fff, 0x7fff};
+    short2v looseMax = {-0x8000, -0x8000};
     // evaluates the `cnt` newest entries of the survivor stack (64, or what is left at the end): exact strength; corners
     // (s > th) enter the strength map and the corner list
     auto flush = [&](const int cnt) {
@@ -946,8 +949,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
         // v_cndmask on the vector port, which is the port this kernel is bound by)
         const fw_lds_u32* const pr = fwLds32(a + rOff4);
         const uint32_t rlo = pr[3 * (TS / 4) + 1], rhi = pr[3 * (TS / 4) + 2];
-        uint32_t fl[2];
-        short2v em[2];
+        short2v d[2];
 #pragma unroll
         for (int hp = 0; hp < 2; hp++) {  // pixels (0, 1) and (2, 3) of the quad as u16 pairs
           const uint32_t V = __builtin_amdgcn_perm(c1, c0, hp ? selC1 : selC0);
@@ -958,17 +960,18 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
           // corner needs (max(T, B) > hi and max(L, R) > hi) or (min(T, B) < lo and min(L, R) < lo)
           const ushort2v mx = __builtin_elementwise_min(__builtin_elementwise_max(vT, vB), __builtin_elementwise_max(vL, vR));
           const ushort2v mn = __builtin_elementwise_max(__builtin_elementwise_min(vT, vB), __builtin_elementwise_min(vL, vR));
-          const ushort2v hi = vV + __builtin_bit_cast(ushort2v, th2);
-          const short2v e1 = __builtin_bit_cast(short2v, hi) - __builtin_bit_cast(short2v, mx);                      // < 0: mx > hi
-          const short2v e2 = __builtin_bit_cast(short2v, mn) + __builtin_bit_cast(short2v, th2) - __builtin_bit_cast(short2v, vV);  // < 0: mn < lo
-          fl[hp] = __builtin_bit_cast(uint32_t, e1) | __builtin_bit_cast(uint32_t, e2);  // sign bits: the two pixels' verdicts
-          em[hp] = __builtin_elementwise_min(e1, e2);
+          // (round 11) both test values from one maximum: min((v + th) - mx, (mn + th) - v) = th - max(mx - v, v - mn) = th - d, every
+          // value within +-511.  A pixel passes (mx > hi or mn < lo) iff th - d < 0 iff d > th: the verdicts are compares of d with
+          // the threshold in an SGPR, and th - d itself is never formed
+          d[hp] = __builtin_elementwise_max(__builtin_bit_cast(short2v, mx) - __builtin_bit_cast(short2v, vV),
+                                            __builtin_bit_cast(short2v, vV) - __builtin_bit_cast(short2v, mn));
         }
-        if (flat) {  // (uniform; the empty asm keeps it a branch -- as a select it would cost every step of every cell five instructions)
+        const uint32_t dm = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(d[0], d[1]));  // the quad's largest d, per half
+        if (flat) {  // (uniform; the empty asm keeps it a branch -- as a select it would cost every step of every cell two instructions)
           asm volatile("" ::: "memory");
-          looseMin = __builtin_elementwise_min(looseMin, __builtin_elementwise_min(em[0], em[1]));
+          looseMax = __builtin_elementwise_max(looseMax, __builtin_bit_cast(short2v, dm));
         }
-        if (__ballot(((fl[0] | fl[1]) & 0x80008000u) != 0u) != 0ull) {  // (wave-uniform) a step without any survivor appends nothing
+        if ((fwGtLo(dm, thLo) | fwGtHi(dm, thHi)) != 0ull) {  // (wave-uniform) a step without any survivor appends nothing
           flat = false;
           // what the ballots must not count: pixels beyond the row's end (the last quad of a row holds nvLast pixels of it) and the
           // idle lanes of the last step
@@ -978,7 +981,8 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
           const uint32_t q0 = a + (uint32_t)(sh + 1);  // the quad's first pixel as a stack entry
 #pragma unroll
           for (int j = 0; j < 4; j++) {
-            unsigned long long m = ((j & 1) ? fwNegHi(fl[j >> 1]) : fwNegLo(fl[j >> 1])) & live;
+            const uint32_t dj = __builtin_bit_cast(uint32_t, d[j >> 1]);
+            unsigned long long m = ((j & 1) ? fwGtHi(dj, thHi) : fwGtLo(dj, thLo)) & live;
             if (j >= nvLast) m &= keepEnd;
             if (m != 0ull) {  // (wave-uniform)
               fwStoreB16((ringAddr + 2u * (uint32_t)nList) + 2u * (uint32_t)fwMbcnt(m), q0 + (uint32_t)j, m);
@@ -1036,8 +1040,8 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
     // cpp:1109-1123: the cell is retried at minThFAST only if it yielded nothing at iniThFAST
     if (nOut > 0 || pass == 1 || g.minTh >= g.iniTh) break;
     {  // no pixel was listed and none passes the quick reject at minThFAST either
-      const short2v dth = {(short)(g.iniTh - g.minTh), (short)(g.iniTh - g.minTh)};
-      if (flat && __ballot((__builtin_bit_cast(uint32_t, looseMin - dth) & 0x80008000u) != 0u) == 0ull) break;
+      const uint32_t lm = __builtin_bit_cast(uint32_t, looseMax);
+      if (flat && (fwGtLo(lm, (uint32_t)g.minTh) | fwGtHi(lm, ((uint32_t)g.minTh << 16) | 0xffffu)) == 0ull) break;
     }
   }
   if (lane == 0) *myCount = min(nOut, segCap);  // nOut <= segCap: NMS survivors are never 8-neighbours
@@ -1215,6 +1219,8 @@ constexpr int descWaves(const int kpw) { return kpw == 2 ? DESC_PAIR_WAVES : DES
 // H = 256 hi + u is split into two int8 operands, hi = (signed) byte 1 and lo = u - 128 (so (W - 128) G_s = 256 hi + lo; the 128 in
 // the accumulator is what keeps hi inside int8 for both tap sets), and with S = the taps' sum
 //   Out = 256 (V hi) + (V lo) + 128 S S + 32768.
+// (Round 11: the sum is never formed; V lo + 128 S S + 32768, shifted right by 8, is the accumulator of V hi, and the blurred byte is
+// bits 8..15 of that product -- blurRangesOk below.)
 // The instruction sums over all (lane group q, byte j) slots of its two operands, so WHICH k a slot holds is ours to choose as
 // long as both operands agree.  Both products use  k(q, j) = 16 (j >> 2) + 4 q + (j & 3):  that is how a 16x16 accumulator tile
 // lies in the registers (lane = column + 16 q, register b = row 4 q + b), so the three row tiles of one column of H, packed to
@@ -1272,6 +1278,41 @@ constexpr bool blurFragsOk() {
   return true;
 }
 static_assert(blurFragsOk<0>() && blurFragsOk<1>(), "tap fragments of the matrix-core blur");
+// Round 11: the two chains of the vertical product are not added as (Hi << 8) + Lo.  With Hi = V hi and Lo = V lo + CLO,
+//   floor((256 Hi + Lo) / 65536) == floor((Hi + floor(Lo / 256)) / 256)        (integers; floor(Lo / 256) is Lo >> 8, arithmetic),
+// so the lo product runs first, its four results shifted right by 8 are the ACCUMULATOR of the hi product, and the blurred byte is
+// byte 1 of that product's result Out' = Hi + (Lo >> 8) = floor(Out / 256).  Value ranges, from the taps (S = their sum):
+//   H   = (W - 128) G_s + 128  in [-128 S + 128, 127 S + 128]: inside int16, so hi = its signed byte 1 is an int8 and lo = u - 128 too
+//   Lo  = V lo + CLO           in [CLO - 128 S, CLO + 127 S]:  CLO = 128 S S + 32768 keeps it non-negative (Lo >> 8 in 32768 .. 33023
+//                                                              for S = 256 -- 33022 is the largest that occurs, those taps are
+//                                                              all even and so is H's low byte -- and 33024 .. 33279 for S = 257)
+//   Out = 256 Hi + Lo = V (W G_s) + 32768  in [32768, 255 S S + 32768], so
+//   Out'                       in [128, 65408] (S = 256: below 2^16) or [128, 65918] (S = 257: below 2^17 before the min with 0xffff,
+//                                                              which saturates exactly where min(Out, 0xffffff) did)
+template <int GV>
+constexpr int blurCLO() {
+  int S = 0;
+  for (int j = 0; j < 7; j++) S += blurTap<GV>(j);
+  return 128 * S * S + 32768;
+}
+template <int GV>
+constexpr bool blurRangesOk() {
+  int S = 0;
+  for (int j = 0; j < 7; j++) S += blurTap<GV>(j);
+  const int CLO = blurCLO<GV>();
+  if (S != (GV ? 257 : 256)) return false;
+  if (-128 * S + 128 < -32768 || 127 * S + 128 > 32767) return false;  // H is an int16: hi and lo are int8
+  const int loMin = CLO - 128 * S, loMax = CLO + 127 * S;               // Lo over every lo in -128 .. 127
+  if (loMin < 0 || (loMin >> 8) != (GV ? 33024 : 32768) || (loMax >> 8) != (GV ? 33279 : 33023)) return false;
+  const long long outMin = 32768, outMax = 255ll * S * S + 32768;       // Out over every window of bytes
+  if (outMin >> 8 != 128 || outMax >> 8 >= (GV ? 1 << 17 : 1 << 16)) return false;
+  // the saturating case exists only for the taps that sum to 257, and it starts where the old form's did: Out >= 2^24 <=> Out' >= 2^16
+  if ((outMax >= (1 << 24)) != (GV != 0)) return false;
+  // (the never sampled padding rows and columns may hold anything: both operands are int8 whatever H was, 32 products of two int8
+  // and Lo >> 8 stay far inside int32, and an arithmetic shift is defined for either sign)
+  return true;
+}
+static_assert(blurRangesOk<0>() && blurRangesOk<1>(), "value ranges of the blur's two chains (lo chain's result >> 8 = hi chain's accumulator)");
 __device__ const BlurFrags d_blurFrags0 = makeBlurFrags<0>();
 __device__ const BlurFrags d_blurFrags1 = makeBlurFrags<1>();
 // the corner tile (rows 32.., columns 32..) of the blurred patch holds no point of the sampling disc and is not computed
@@ -1554,7 +1595,7 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
     {
-      constexpr int S = GV ? 257 : 256, CLO = 128 * S * S + 32768;
+      constexpr int CLO = blurCLO<GV>();
       const int col = lane & 15, q4 = lane >> 4;
 #pragma unroll
       for (int tn = 0; tn < 3; tn++) {
@@ -1580,21 +1621,25 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
           if (t == 2) { h12[1] = hi; l12[1] = (int)(lo ^ 0x80808080u); }
         }
         // Out, rows 16 to .. + 15 of these columns; the four rows a lane holds are one dword of the column-major blurred patch
+        // (round 11) the lo chain first, all row tiles of the column block together; Lo >> 8 is then the hi chain's accumulator
+        // (blurRangesOk has the identity and the ranges), so no hi product waits for one lo product alone
+        const int nto = tn == 2 ? 2 : 3;  // (the corner tile is not computed)
+        v4i_t ol[3];
 #pragma unroll
-        for (int to = 0; to < 3; to++) {
-          if (tn == 2 && to == 2) continue;
-          const v2i_t av = to == 2 ? fvX : fvP;
-          const v4i_t oh = blurMfma(av, to == 0 ? h01 : h12, v4i_t{0, 0, 0, 0});
-          const v4i_t ol = blurMfma(av, to == 0 ? l01 : l12, v4i_t{CLO, CLO, CLO, CLO});
+        for (int to = 0; to < nto; to++)
+          ol[to] = blurMfma(to == 2 ? fvX : fvP, to == 0 ? l01 : l12, v4i_t{CLO, CLO, CLO, CLO});
+#pragma unroll
+        for (int to = 0; to < nto; to++) {
+          const v4i_t oh = blurMfma(to == 2 ? fvX : fvP, to == 0 ? h01 : h12, ol[to] >> 8);
           uint32_t o[4];
 #pragma unroll
           for (int b = 0; b < 4; b++) {
-            o[b] = (uint32_t)((oh[b] << 8) + ol[b]);
-            if (GV) o[b] = min(o[b], 0xffffffu);  // taps that sum to 257: saturate_cast<uchar>
+            o[b] = (uint32_t)oh[b];
+            if (GV) o[b] = min(o[b], 0xffffu);  // taps that sum to 257: saturate_cast<uchar>
           }
-          // each sum is < 2^24: its blurred byte is bits 16..23; v_perm_b32 gathers byte 2 of four sums into one dword
+          // each sum is < 2^16: its blurred byte is bits 8..15; v_perm_b32 gathers byte 1 of four sums into one dword
           bl32[(16 * tn + col) * (BL_STRIDE / 4) + 4 * to + q4] =
-              __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0602u) | __builtin_amdgcn_perm(o[3], o[2], 0x06020c0cu);
+              __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0501u) | __builtin_amdgcn_perm(o[3], o[2], 0x05010c0cu);
         }
       }
     }
@@ -1648,33 +1693,71 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
       words[h][wq] = __ballot(t0 < t1);
     }
   }
-  // lane 0 stores keypoint A's descriptor and record, lane 1 (pair form) keypoint B's: the words are SGPR pairs, a lane's 32 bytes
-  // are eight moves (and eight selects between A and B) and two 16-byte stores (8-byte aligned, as the u64 stores before them)
+  // One lane per keypoint stores its descriptor and its record: the words are SGPR pairs, a lane's 32 bytes are eight moves and two
+  // 16-byte stores (8-byte aligned, as the u64 stores before them).
   const long long o = (long long)f * capacity + i;
-  const int nLive = KPW == 2 && liveB ? 2 : 1;
-  if (lane < nLive) {
-    const bool hb = KPW == 2 && lane != 0;
-    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+  typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+  if constexpr (KPW == 2) {
+    // Pair form (round 11): lanes 0 and 32, the first lane of each half -- it already holds its keypoint's angle.  What differs
+    // between the halves and lives in SGPRs (the descriptor words, the packed position, level and response, the level's scale and
+    // patch size, read through scalar loads) reaches the two lanes as a move of A's value and a v_writelane_b32 of B's into lane 32:
+    // no select, no second copy, no vector load behind the BRIEF loop, and both store addresses are a uniform base and the lane's
+    // 32-bit offset.
+    const uint32_t xyS[2] = {(uint32_t)kx[0] | ((uint32_t)ky[0] << 16), (uint32_t)kx[1] | ((uint32_t)ky[1] << 16)};
+    const uint32_t lrS[2] = {(uint32_t)level[0] | ((uint32_t)k[0].response << 8), (uint32_t)level[1] | ((uint32_t)k[1].response << 8)};
+    const float scS[2] = {Lg[0]->scale, Lg[1]->scale};
+    const int psS[2] = {Lg[0]->patchSize, Lg[1]->patchSize};
+    if (rl == 0 && (hl == 0 || liveB)) {
+      // four values at once: a[j] in every lane, b[j] in lane 32.  The lane is a constant, so there is no lane-select hazard; the
+      // b[j] may have been written by a vector compare (the descriptor words are ballots), and a vector instruction inside an
+      // asm is not covered by the compiler's wait states for an SGPR that a vector instruction wrote: the s_nop provides them
+      auto halves = [](uint32_t (&v)[4], const uint32_t b0, const uint32_t b1, const uint32_t b2, const uint32_t b3) {
+        asm("s_nop 1\n\tv_writelane_b32 %0, %4, 32\n\tv_writelane_b32 %1, %5, 32\n\tv_writelane_b32 %2, %6, 32\n\tv_writelane_b32 %3, %7, 32"
+            : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])
+            : "s"(b0), "s"(b1), "s"(b2), "s"(b3));
+      };
+#pragma unroll
+      for (int p = 0; p < 2; p++) {  // words 2 p and 2 p + 1: one 16-byte store
+        uint32_t d[4] = {(uint32_t)words[0][2 * p], (uint32_t)(words[0][2 * p] >> 32), (uint32_t)words[0][2 * p + 1], (uint32_t)(words[0][2 * p + 1] >> 32)};
+        halves(d, (uint32_t)words[1][2 * p], (uint32_t)(words[1][2 * p] >> 32), (uint32_t)words[1][2 * p + 1], (uint32_t)(words[1][2 * p + 1] >> 32));
+        reinterpret_cast<u32x4_a8*>(desc + o * 32 + (uint32_t)lane)[p] = u32x4_a8{d[0], d[1], d[2], d[3]};  // (lane = 32 x half)
+      }
+      uint32_t r[4] = {xyS[0], lrS[0], __float_as_uint(scS[0]), (uint32_t)psS[0]};
+      halves(r, xyS[1], lrS[1], __float_as_uint(scS[1]), (uint32_t)psS[1]);
+      const uint32_t xy = r[0], lr = r[1];
+      const float scale = __uint_as_float(r[2]);
+      const int lv = (int)(lr & 0xffu);
+      orbx_keypoint kp;
+      // cpp:1631-1634: pt *= scale for level != 0 (scale[0] == 1 exactly)
+      kp.x = lv ? (float)(xy & 0xffffu) * scale : (float)(xy & 0xffffu);
+      kp.y = lv ? (float)(xy >> 16) * scale : (float)(xy >> 16);
+      kp.size = (float)(int)r[3];
+      kp.angle = angleL;
+      kp.response = (float)((lr >> 8) & 0xffu);
+      kp.octave = lv;
+      kp.class_id = -1;
+      *reinterpret_cast<orbx_keypoint*>(reinterpret_cast<uint8_t*>(kps + o) + (uint32_t)(hl * (int)sizeof(orbx_keypoint))) = kp;
+    }
+  } else if (lane == 0) {
     u32x4_a8 dq[2];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const unsigned long long wd = hb ? words[KPW - 1][j] : words[0][j];
-      dq[j >> 1][2 * (j & 1)] = (uint32_t)wd; dq[j >> 1][2 * (j & 1) + 1] = (uint32_t)(wd >> 32);
+      dq[j >> 1][2 * (j & 1)] = (uint32_t)words[0][j]; dq[j >> 1][2 * (j & 1) + 1] = (uint32_t)(words[0][j] >> 32);
     }
-    u32x4_a8* dp = reinterpret_cast<u32x4_a8*>(desc + (o + lane) * 32);
+    u32x4_a8* dp = reinterpret_cast<u32x4_a8*>(desc + o * 32);
     dp[0] = dq[0]; dp[1] = dq[1];
-    const int lv = hb ? level[KPW - 1] : level[0], kxl = hb ? kx[KPW - 1] : kx[0], kyl = hb ? ky[KPW - 1] : ky[0];
-    const float scale = hb ? Lg[KPW - 1]->scale : Lg[0]->scale;
+    const int lv = level[0];
+    const float scale = Lg[0]->scale;
     orbx_keypoint kp;
     // cpp:1631-1634: pt *= scale for level != 0 (scale[0] == 1 exactly)
-    kp.x = lv ? (float)kxl * scale : (float)kxl;
-    kp.y = lv ? (float)kyl * scale : (float)kyl;
-    kp.size = (float)(hb ? Lg[KPW - 1]->patchSize : Lg[0]->patchSize);
-    kp.angle = hb ? angle[KPW - 1] : angle[0];
-    kp.response = (float)(hb ? k[KPW - 1].response : k[0].response);
+    kp.x = lv ? (float)kx[0] * scale : (float)kx[0];
+    kp.y = lv ? (float)ky[0] * scale : (float)ky[0];
+    kp.size = (float)Lg[0]->patchSize;
+    kp.angle = angle[0];
+    kp.response = (float)k[0].response;
     kp.octave = lv;
     kp.class_id = -1;
-    kps[o + lane] = kp;
+    kps[o] = kp;
   }
 }
 
