@@ -267,6 +267,9 @@ __device__ __forceinline__ uint32_t dot2u16(uint32_t a, uint32_t b, uint32_t c) 
 //     product); the row offsets and wy << 8 come ready-made from the host table PyrYRow
 //   * the four sums of a group are rounded, shifted and packed two at a time; no clamp: with tap pairs summing to 2048
 //     (checked on the host, else the per-level kernels run) the result is <= 255
+//   * rows: a thread keeps its column(s) and walks ONE contiguous run of the band's rows, two adjacent rows per step; the
+//     horizontal interpolation of a source row is computed once per thread -- shared between the step's two rows and carried
+//     to the next step (one-group instances) -- and lanes without a row stay out of the loop (round 12; at the row loop)
 __device__ __forceinline__ uint32_t mulHiU24(uint32_t a, uint32_t b) {  // v_mul_hi_u32_u24: bits 47:32 of the 24 x 24 bit product
   return (uint32_t)(((unsigned long long)(a & 0xffffffu) * (unsigned long long)(b & 0xffffffu)) >> 32);
 }
@@ -349,12 +352,22 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     // caller's last frame nothing is known to follow, so frames f >= pb.safeFrom take level 1 with clamped single dwords.
     // Round 5: a step's two rows are ADJACENT output rows dy, dy + 1.  At the pyramid's scale 1.2 the lower source row of dy is
     // the upper source row of dy + 1 for five row pairs of six (same byte offset in PyrYRow): that row is loaded once and its
-    // horizontal interpolation (perms, dot2, mask: 14 of a group's 50 instructions) is computed once for both outputs -- three
-    // loads and three interpolations per row pair and group instead of four.  A pair that does not share (every pair at scale 2)
-    // takes the fourth behind one wave-uniform test; values are those of the separate evaluation either way (same source bytes,
-    // same column constants).  (Before: rows dy and dy + rpp, four of each; a timing-only build with a fifth less pyramid work
-    // gave the step +3 %.)
+    // horizontal interpolation (perms, dot2, mask: 14 of a group's 50 instructions) is computed once for both outputs.
+    // Round 12: a thread-row owns ONE contiguous run of the band's rows, Lr = ceil(n / rpp) rounded up to even, thread-row rsub
+    // rows [r0 + rsub Lr, min(r1, r0 + (rsub + 1) Lr)) -- as many steps as with rows dy0 = r0 + 2 rsub + 2 rpp k before.  The lower
+    // source row of a step's second output row is then the upper source row of the NEXT step's first one for the same five of six,
+    // so its interpolation (t[4]) and its offset are carried from step to step (invalid at the start of a run and of a level: new
+    // column constants, new source).  A step always interpolates the lower rows of dy and dy + 1; the upper row of dy only when some
+    // lane of the wave has ty0.x != the carried offset, the upper row of dy + 1 only when some lane has ty1.x != ty0.y (two
+    // wave-uniform branches).  Where a branch is taken every lane takes the fresh values without a select: equal offsets mean the
+    // same bytes under the same column constants, hence the same values.  Rows clamped at the bottom edge (.y == .x) are just
+    // another offset comparison.  At scale 1.2 that is 1.2 - 1.3 interpolations per output row (1.6 - 1.8 before); at scale 2
+    // four per step as before.  Lanes without a row (rsub >= rpp, or a run beyond r1) do not enter the loop, and a wave of such
+    // lanes goes straight to the barrier (before: the loop bound ignored C.lanes; 110 of 512 threads at level 1 of 640x480).
+    // PYR_CARRY = false in the two-group instances (with the carried registers they take 85 / 87 VGPRs and lose a wave per SIMD;
+    // without, 77 / 79): runs and idle lanes as above, three interpolations per step plus the fourth behind its test as in round 5.
     static_assert(PYR_R == 2, "the row loop pairs adjacent rows");
+    constexpr bool PYR_CARRY = GMAX == 1;
     auto rows = [&](auto safeTag) {
     constexpr bool SAFE = decltype(safeTag)::value;
     auto load3 = [&](const uint32_t rowOff, const int j) -> PyrU3 {
@@ -381,34 +394,50 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
 #pragma unroll
       for (int i = 0; i < 4; i++) t[i] = dot2u16(p[i], C.cf[j][i], 0u) & ~0xffu;
     };
-    for (int dy0 = r0 + 2 * C.rsub; dy0 < r1; dy0 += 2 * rpp) {  // two adjacent rows per step: their loads are in flight together
-      const bool live0 = C.lanes && dy0 < r1, live1 = C.lanes && dy0 + 1 < r1;
-      const uint4 ty0 = yr[live0 ? dy0 - r0 : 0], ty1 = yr[live1 ? dy0 + 1 - r0 : 0];
-      const bool shared = ty1.x == ty0.y;                               // the rows' common source row
-      const bool fourth = __ballot(live1 && !shared) != 0ull;           // (wave-uniform) some lane's pair does not share one
+    const int Lr = ((r1 - r0 + rpp - 1) / rpp + 1) & ~1;
+    const int run0 = r0 + C.rsub * Lr, run1 = C.lanes ? min(r1, run0 + Lr) : run0;
+    uint32_t car[GMAX][4] = {}, carOff = ~0u;   // the interpolated lower source row of the run's last output row, and its offset
+    const unsigned col0 = (unsigned)((C.gOff + C.col * G) * 4);
+    // (for a lane without a run, run0 may lie beyond the band, the level and yrows: out and ty are only formed there, never
+    // dereferenced -- such a lane does not enter the loop)
+    uint8_t* out = dst + ((unsigned)(run0 * dstride) + col0);
+    const uint4* ty = yr + (run0 - r0);
+    for (int dy0 = run0; dy0 < run1; dy0 += 2, out += 2 * dstride, ty += 2) {  // two adjacent rows per step: their loads are in flight together
+      const bool live1 = dy0 + 1 < run1;
+      const uint4 ty0 = ty[0], ty1 = ty[live1 ? 1 : 0];
+      // (wave-uniform) some lane's upper source rows are not the ones it already has
+      const bool upper0 = !PYR_CARRY || __ballot(ty0.x != carOff) != 0ull;
+      const bool upper1 = __ballot(live1 && ty1.x != ty0.y) != 0ull;
       PyrU3 ra0[GMAX], rb0[GMAX], ra1[GMAX], rb1[GMAX];
 #pragma unroll
       for (int j = 0; j < GMAX; j++)
         if (j < G) {
-          ra0[j] = load3(ty0.x, j);
+          if (upper0) ra0[j] = load3(ty0.x, j);
           rb0[j] = load3(ty0.y, j);
+          if (upper1) ra1[j] = load3(ty1.x, j);
           rb1[j] = load3(ty1.y, j);
-          if (fourth) ra1[j] = load3(ty1.x, j);
         }
 #pragma unroll
       for (int j = 0; j < GMAX; j++) {
         if (j >= G) continue;
         uint32_t ta0[4], tb0[4], ta1[4], tb1[4];
-        hrow(ra0[j], j, ta0);
         hrow(rb0[j], j, tb0);
         hrow(rb1[j], j, tb1);
-        if (fourth) {
-          hrow(ra1[j], j, ta1);
+        if (upper0) {
+          hrow(ra0[j], j, ta0);
+        } else {
 #pragma unroll
-          for (int i = 0; i < 4; i++) ta1[i] = shared ? tb0[i] : ta1[i];
+          for (int i = 0; i < 4; i++) ta0[i] = car[j][i];
+        }
+        if (upper1) {
+          hrow(ra1[j], j, ta1);
         } else {
 #pragma unroll
           for (int i = 0; i < 4; i++) ta1[i] = tb0[i];
+        }
+        if (PYR_CARRY) {
+#pragma unroll
+          for (int i = 0; i < 4; i++) car[j][i] = tb1[i];
         }
         uint32_t u[4], v[4];
 #pragma unroll
@@ -419,10 +448,10 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
         // (u + 2) >> 2 on two 16-bit fields at a time; bytes 0 and 2 of each pair are the pixels
         const uint32_t s01 = ((u[0] | (u[1] << 16)) + 0x00020002u) >> 2, s23 = ((u[2] | (u[3] << 16)) + 0x00020002u) >> 2;
         const uint32_t q01 = ((v[0] | (v[1] << 16)) + 0x00020002u) >> 2, q23 = ((v[2] | (v[3] << 16)) + 0x00020002u) >> 2;
-        const unsigned col = (unsigned)((C.gOff + C.col * G + j) * 4);
-        if (live0 && C.haveG[j]) *reinterpret_cast<uint32_t*>(dst + ((unsigned)(dy0 * dstride) + col)) = __builtin_amdgcn_perm(s23, s01, 0x06040200u);
-        if (live1 && C.haveG[j]) *reinterpret_cast<uint32_t*>(dst + ((unsigned)((dy0 + 1) * dstride) + col)) = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
+        if (C.haveG[j]) *reinterpret_cast<uint32_t*>(out + 4 * j) = __builtin_amdgcn_perm(s23, s01, 0x06040200u);
+        if (live1 && C.haveG[j]) *reinterpret_cast<uint32_t*>(out + (dstride + 4 * j)) = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
       }
+      carOff = ty1.y;
     }
     };
     if (l == 1 && f >= pb.safeFrom) rows(std::true_type{});
