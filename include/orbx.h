@@ -755,7 +755,7 @@ int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const floa
  * no Sim3Solver: the rules below restate ORB-SLAM2's Sim3Solver.cc [from-knowledge], PARITY UNPINNED, as the PnP section above.
  * The device equals the CPU restatement tests/cpp/sim3_ref.cpp bit for bit.  (The guided matcher ORBmatcher::SearchBySim3 that
  * follows it in ComputeSim3 is the section "loop closing: matching under a similarity" below and reads the row and the similarity
- * written here as they are; OptimizeSim3 is not offered yet.)
+ * written here as they are; Optimizer::OptimizeSim3 behind that is the section "loop closing: Sim3 optimisation".)
  *
  * Rules.
  *  1. Constructor.  For feature i1 of KF1 in ascending i1: a correspondence exists when i2 = d_match[p][i1] >= 0 and the point
@@ -869,6 +869,116 @@ int orbx_sim3_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const f
                     const float* pose2, const int32_t* match12, const float* K, const float* sigma2, int fix_scale,
                     double probability, int min_inliers, int max_iterations, float th2, int n_iter, const int32_t* draws,
                     orbx_sim3_result* res, float* sim3, int32_t* match_inliers, uint8_t* inliers);
+
+/* ---- loop closing: Sim3 optimisation (Optimizer::OptimizeSim3, the call that decides whether a candidate closes the loop) -------
+ * Behind Sim3Solver and SearchBySim3, LoopClosing::ComputeSim3 refines the similarity over the widened match row and counts the
+ * correspondences that survive: `nInliers = Optimizer::OptimizeSim3(mpCurrentKF, pKF, vpMapPointMatches, gScm, 10, mbFixScale)`,
+ * accepted when nInliers >= 20.  The reference vendors the g2o types (types/sim3.h, types/types_seven_dof_expmap.h), the
+ * Levenberg solver and LinearSolverDense, but has no Optimizer: the rules below restate ORB-SLAM2's Optimizer::OptimizeSim3
+ * [from-knowledge], PARITY UNPINNED, as the pose section above.  The device equals the CPU restatement
+ * tests/cpp/sim3opt_ref.cpp bit for bit.
+ *
+ * Graph.  One VertexSim3Expmap with _fix_scale = fix_scale; its start is Sim3(Matrix3d R12, Vector3d t12, double s12) of the f32
+ * d_sim3 row (R12 row-major, t12, s12): Quaterniond(R) by Eigen's four-branch rule, with no sign flip and no normalisation
+ * (types/sim3.h:64-67 does neither, unlike SE3Quat).  Both cameras' fx fy cx cy come from K.  A correspondence exists for feature
+ * i1 of KF1, ascending, when i2 = row[i1] >= 0, i2 < KF2's count, and the point mask of KF1's set at i1 and of KF2's set at i2
+ * are set.  Its two fixed points are the camera-frame points of the Sim3 RANSAC section's rule 1 (Rcw * Xw + tcw in f32, each
+ * row's products added left to right, then the translation), taken to f64 afterwards: P1c of KF1's point, P2c of KF2's.  Two
+ * edges per correspondence, e12 before e21 wherever order matters:
+ *   e12  EdgeSim3ProjectXYZ (types_seven_dof_expmap.h:130-149): error = obs1 - cam_map1(project(S12.map(P2c))), obs1 =
+ *        kp1[i1].pt, information = inv_sigma2[octave(kp1[i1])] * I
+ *   e21  EdgeInverseSim3ProjectXYZ (:152-171): error = obs2 - cam_map2(project(S12.inverse().map(P1c))), obs2 = kp2[i2].pt,
+ *        information = inv_sigma2[octave(kp2[i2])] * I; inverse() is sim3.h:233-236
+ * both with a RobustKernelHuber of delta = (float)sqrt(th2) (`const float deltaHuber = sqrt(th2)`).  map is s * (r * xyz) + t
+ * (sim3.h:144-146), project is (x / z, y / z), cam_map is (v0 * fx + cx, v1 * fy + cy) (:74-88).
+ *
+ * Jacobians are numeric: both edges have linearizeOplus commented out (:147, :169), so BaseBinaryEdge::linearizeOplus
+ * (core/base_binary_edge.hpp:131-200) runs.  The point vertex is fixed, so only the seven columns of the Sim3 vertex exist.
+ * Column d = (1.0 / (2 * 1e-9)) * (error(oplus(+1e-9 e_d)) - error(oplus(-1e-9 e_d))), the subtraction first (:181-196).  oplus
+ * is Sim3(update) * estimate (types_seven_dof_expmap.h:60-69, sim3.h:266-272): the quaternion product is not normalised, and
+ * update[6] is forced to 0 under fix_scale, so column 6 is exactly zero there.  Sim3(const Vector7d&) is sim3.h:70-142 with all
+ * four branches on fabs(sigma) < 1e-5 and theta < 1e-5; the small-theta R = I + Omega + Omega * Omega is kept, without the 1/2,
+ * and Quaterniond(R) is taken of that matrix as it stands.  sin / cos are those of the bundle adjustment above; exp(sigma) is a
+ * restated fdlibm e_exp.c on [-700, 700] (NaN outside): reduction by ln2 in two parts, the polynomial, an exact scaling by 2^k.
+ *
+ * Optimisation.  initializeOptimization(); optimize(n_iterations) (the design passes 5): the loop of the pose section's rule c,
+ * steps 1 to 7, on the 7-dof vertex: computeLambdaInit over seven diagonal entries, computeScale over seven terms.
+ * First classification.  For every correspondence `e12->chi2() > th2 || e21->chi2() > th2` removes it: chi2 = e . (information
+ * e), unrobustified, f64, against the f32 th2 promoted to f64.  Its row entry becomes -1, both edges leave the graph, nBad counts
+ * them.  The stale-error rule of the pose section applies as it stands: an edge's _error is that of the round's last
+ * computeActiveErrors, i.e. of the last TRIAL, accepted or not (linearizeOplus restores _error at :200).
+ * Second round.  nMoreIterations = nBad > 0 ? 10 : 5.  `if (nCorrespondences - nBad < 10) return 0`: the similarity is NOT
+ * recovered (the output equals the input), the row keeps the first classification's removals, n_inliers is 0.  Otherwise
+ * initializeOptimization(); optimize(nMoreIterations): it continues FROM THE CURRENT ESTIMATE (no reset, unlike
+ * PoseOptimization), the robust kernel is still on, lambda, _ni and _nBad start again at iteration 0.  Then the second
+ * classification by the same test: a failing entry becomes -1, the rest count in nIn, the return value.  The result is the
+ * vertex' estimate: q, t, s in f64; s12, R12, t12 in f32, R12 = toRotationMatrix of the quaternion as it is.
+ *
+ * Documented deviations:
+ *  1. Sums: the pose section's deviation 1 (feature i1 belongs to lane i1 % 64; the 64 lanes folded + 32, + 16, ... + 1), with a
+ *     correspondence's e12 term added before its e21 term.  g2o adds edge by edge, all e12 / e21 pairs in insertion order.
+ *  2. The small dense algebra, sin / cos / exp and the 7x7 solve through the shared csrc/orbx_sim3opt_math.inc.  The solve is the
+ *     project's unblocked lower Cholesky where g2o's LinearSolverDense is an Eigen::LDLT; a pivot <= 0 or non-finite, or a
+ *     non-finite solution, is a failed solve and applies a zero step.  The fourteen perturbed estimates of a linearisation and
+ *     their inverses are computed once per linearisation, not once per edge: they depend on the estimate alone, and the bits
+ *     are those g2o computes per edge (tests/test_sim3opt_host.py compares both forms).
+ *  3. Arrays plus masks stand for KeyFrame / MapPoint; GetIndexInKeyFrame is the row.
+ *  4. Garbage is flagged and never followed.  ORBX_SIM3OPT_BAD_INPUT: a count outside [0, capacity], a row entry >= KF2's count,
+ *     an octave outside the table on a feature of a correspondence.  ORBX_SIM3OPT_NONFINITE: a non-finite pose, similarity,
+ *     point, keypoint or result, or s12 <= 0.  Such a problem returns its inputs: the row untouched, d_sim3 copied through,
+ *     every other number of the result 0.
+ *  5. n_iterations is two arguments (5 and 10): n_more_iterations is the count behind nBad > 0; behind nBad == 0 the second
+ *     round runs the first round's n_iterations.  0 is accepted and only classifies, at the estimate it was given.
+ *  6. n_correspondences == 0 runs nothing: rounds = 0, n_inliers = 0, the similarity copied through. */
+#define ORBX_SIM3OPT_BAD_INPUT 2 /* a count outside [0, capacity], a row entry >= KF2's count, an octave outside [0, nlevels) */
+#define ORBX_SIM3OPT_NONFINITE 4 /* a non-finite pose, similarity, point, keypoint or result, or s12 <= 0 */
+typedef struct orbx_sim3opt_result {
+  int32_t status;            /* 0, or a bitmask of ORBX_SIM3OPT_*; every field is written for every problem */
+  int32_t n_correspondences; /* nCorrespondences (0 with a status) */
+  int32_t n_bad;             /* removed by the first classification */
+  int32_t n_inliers;         /* nIn, the design's return value: 0 when the second round did not run */
+  int32_t rounds;            /* 2; 1 when nCorrespondences - nBad < 10; 0 when nothing ran */
+  int32_t iterations[2];     /* solve() calls of each round */
+  int32_t lm_trials;         /* over both rounds: the sum of qmax */
+  int32_t rejected_trials;
+  int32_t solver_failures;
+  int32_t stop_reason[2];    /* per round: 0 = all iterations ran, 1 = qmax == 10 || rho == 0, 2 = _nBad >= 3 */
+  int32_t small_theta;       /* LM steps (lm_trials - solver_failures of them ran) whose Sim3(update) had theta < 1e-5, */
+  int32_t small_sigma;       /* ... |sigma| < 1e-5 (every step under fix_scale), */
+  int32_t small_both;        /* ... both: with the two above, how often each of the four branches ran */
+  int32_t reserved;
+  double chi2_initial;       /* activeRobustChi2 at the given similarity */
+  double chi2_final, lambda; /* of the last round that ran an iteration */
+  double q[4], t[3], s;      /* the estimate as g2o holds it (quaternion x, y, z, w); the start estimate when rounds == 1 */
+  float s12, R12[9], t12[3]; /* as Converter::toCvMat would store it (row-major); d_sim3's bits when nothing was recovered */
+  float reserved_f;
+} orbx_sim3opt_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  The problem lists, d_kps_un, d_n, d_points, d_point_mask and
+ * d_pose mean what they mean in orbx_sim3_solve_batch_device.  d_matches int32 [n_problems][capacity], in and out: vpMatches1 as
+ * orbx_match_sim3_batch_device leaves it; a removed entry becomes -1, every other entry stays.  d_sim3 float [n_problems][13]:
+ * R12 row-major, t12, s12, as the solver writes it.  K row-major 3x3 (host, f32); inv_sigma2: host, the context's nlevels floats,
+ * NULL = the context's own table; fix_scale 0 or 1; th2 > 0 (the design passes 10); n_iterations, n_more_iterations >= 0 (5,
+ * 10).  Outputs: d_res [n_problems]; d_sim3_out float [n_problems][13], which may equal d_sim3.  One wave of 64 lanes runs a
+ * problem's whole optimisation, four problems per workgroup, in one launch, without a workspace.  The call returns once queued,
+ * with the pose call's exception: when the lists or the table differ from the previous call's on this context, it first waits
+ * for the context stream.  ORBX_E_BADARG: null required pointers, negative counts, capacity < 1, fix_scale not 0 or 1, th2 not a
+ * finite number > 0, a keyframe index outside [0, n_frames), a point set outside [0, n_point_sets); ORBX_E_CAPACITY: capacity >
+ * ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments -- all checked before anything touches a
+ * device.  n_problems == 0 is ORBX_OK. */
+int orbx_optimize_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_kf1, const int32_t* h_kf2,
+                                    const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const int32_t* d_n,
+                                    int capacity, int32_t* d_matches, int n_point_sets, const float* d_points,
+                                    const uint8_t* d_point_mask, const float* d_pose, const float* d_sim3, const float* K,
+                                    const float* inv_sigma2, int fix_scale, float th2, int n_iterations, int n_more_iterations,
+                                    orbx_sim3opt_result* d_res, float* d_sim3_out);
+/* The same for one pair in host memory: KF1 (n1 features, points1 [n1][3], mask1 [n1] nullable, pose1 [12]), then KF2; matches12
+ * [n1] in and out; sim3 [13] in; sim3_out [13] (may equal sim3).  mask1 and mask2 are given together or not at all.  Run through
+ * the batched path as a batch of one.  Synchronous. */
+int orbx_optimize_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* points1, const uint8_t* mask1,
+                       const float* pose1, const orbx_keypoint* kps_un2, int n2, const float* points2, const uint8_t* mask2,
+                       const float* pose2, int32_t* matches12, const float* sim3, const float* K, const float* inv_sigma2,
+                       int fix_scale, float th2, int n_iterations, int n_more_iterations, orbx_sim3opt_result* res, float* sim3_out);
 
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,

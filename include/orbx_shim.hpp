@@ -749,6 +749,38 @@ class Optimizer {
     if (result) *result = res;
     return res.n_inliers;
   }
+
+  // OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale): ORB-SLAM2's Optimizer::OptimizeSim3 (include/orbx.h, "loop
+  // closing: Sim3 optimisation"), what LoopClosing::ComputeSim3 runs behind SearchBySim3.  The keyframes as KeyFrameViews with
+  // their map points (mWorldPos, mbGood) and poses (mTcw); vpMatches1 holds KF2's feature per feature of KF1, or -1
+  // (GetIndexInKeyFrame taken as the identity): a correspondence the optimisation removes becomes -1.  g2oS12 is (s12, R12 [9]
+  // row-major, t12 [3]), replaced by the refined similarity unless fewer than 10 correspondences survive the first
+  // classification (then 0 is returned and it stays as given).  K [9]; ext: the device context.  Returns nIn.  Argument / HIP
+  // errors throw orbx::Error.
+  static int OptimizeSim3(ORBextractor* ext, const KeyFrameView& KF1, const KeyFrameView& KF2, std::vector<int>& vpMatches1, float& s12,
+                          float* R12, float* t12, const float th2, const bool bFixScale, const float* K,
+                          orbx_sim3opt_result* result = nullptr) {
+    if (!ext) throw orbx::Error(ORBX_E_BADARG, "Optimizer: no ORBextractor (device context)");
+    if (!KF1.mTcw || !KF2.mTcw) throw orbx::Error(ORBX_E_BADARG, "Optimizer::OptimizeSim3: a keyframe has no pose (mTcw)");
+    if (vpMatches1.size() != (size_t)KF1.N) throw orbx::Error(ORBX_E_BADARG, "Optimizer::OptimizeSim3: vpMatches1 needs KF1.N entries");
+    float sim[13], out[13];
+    for (int k = 0; k < 9; k++) sim[k] = R12[k];
+    for (int k = 0; k < 3; k++) sim[9 + k] = t12[k];
+    sim[12] = s12;
+    std::vector<int32_t> row(vpMatches1.begin(), vpMatches1.end());
+    if (row.empty()) row.push_back(-1);
+    orbx_sim3opt_result res;
+    const int r = orbx_optimize_sim3(ext->context(), reinterpret_cast<const orbx_keypoint*>(KF1.mvKeysUn), KF1.N, KF1.mWorldPos,
+                                     KF1.mbGood, KF1.mTcw, reinterpret_cast<const orbx_keypoint*>(KF2.mvKeysUn), KF2.N, KF2.mWorldPos,
+                                     KF2.mbGood, KF2.mTcw, row.data(), sim, K, nullptr, bFixScale ? 1 : 0, th2, 5, 10, &res, out);
+    if (r != ORBX_OK) throw orbx::Error(r, r == ORBX_E_BADARG ? "Optimizer::OptimizeSim3: an argument out of range" : orbx_last_error(ext->context()));
+    for (int i = 0; i < KF1.N; i++) vpMatches1[(size_t)i] = row[(size_t)i];
+    for (int k = 0; k < 9; k++) R12[k] = out[k];
+    for (int k = 0; k < 3; k++) t12[k] = out[9 + k];
+    s12 = out[12];
+    if (result) *result = res;
+    return res.n_inliers;
+  }
 };
 
 // ---- PnPsolver (ORB-SLAM2's PnPsolver.h; include/orbx.h, "behind SearchByBoW: PnP RANSAC") ---------------------------------------

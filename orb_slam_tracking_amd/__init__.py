@@ -23,7 +23,8 @@ import numpy as np
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
            "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "Sim3Result", "SIM3_RESULT_DTYPE", "SIM3_BAD_INPUT", "SIM3_NONFINITE", "SIM3_FEW_POINTS", "SIM3_BAD_DRAWS", "SIM3_NO_RESULT", "Sim3Solver", "sample_sim3_draws", "MatchSim3Result", "MSIM3_RESULT_DTYPE", "MSIM3_BAD_INPUT", "MSIM3_NONFINITE", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
-           "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL"]
+           "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL",
+           "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -196,6 +197,37 @@ class Sim3Result(ctypes.Structure):
 SIM3_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _SIM3_INTS] + [("reserved", "<i4", 2), ("s12", "<f4"), ("R12", "<f4", (3, 3)),
                                                                  ("t12", "<f4", 3)])
 assert SIM3_RESULT_DTYPE.itemsize == ctypes.sizeof(Sim3Result) == 96
+
+SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
+_SIM3OPT_INTS = ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")
+_SIM3OPT_INTS2 = ("lm_trials", "rejected_trials", "solver_failures")
+_SIM3OPT_INTS3 = ("small_theta", "small_sigma", "small_both", "reserved")
+_SIM3OPT_F64 = ("chi2_initial", "chi2_final", "lambda_")
+
+
+class Sim3OptResult(ctypes.Structure):
+    """orbx_sim3opt_result: Optimizer::OptimizeSim3's outcome for one keyframe pair (n_inliers is the design's return value)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in _SIM3OPT_INTS] + [("iterations", ctypes.c_int32 * 2)] +
+                [(n, ctypes.c_int32) for n in _SIM3OPT_INTS2] + [("stop_reason", ctypes.c_int32 * 2)] +
+                [(n, ctypes.c_int32) for n in _SIM3OPT_INTS3] + [(n, ctypes.c_double) for n in _SIM3OPT_F64] +
+                [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("s", ctypes.c_double), ("s12", ctypes.c_float),
+                 ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("reserved_f", ctypes.c_float)])
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n in _SIM3OPT_INTS + _SIM3OPT_INTS2 + _SIM3OPT_INTS3[:3]}
+        d["iterations"], d["stop_reason"] = list(self.iterations), list(self.stop_reason)
+        d.update(chi2_initial=float(self.chi2_initial), chi2_final=float(self.chi2_final), **{"lambda": float(self.lambda_)})
+        d.update(q=np.array(self.q[:]), t=np.array(self.t[:]), s=float(self.s), s12=float(self.s12),
+                 R12=np.array(self.R12[:], np.float32).reshape(3, 3), t12=np.array(self.t12[:], np.float32))
+        return d
+
+
+SIM3OPT_RESULT_DTYPE = np.dtype(
+    [(n, "<i4") for n in _SIM3OPT_INTS] + [("iterations", "<i4", 2)] + [(n, "<i4") for n in _SIM3OPT_INTS2] +
+    [("stop_reason", "<i4", 2)] + [(n, "<i4") for n in _SIM3OPT_INTS3] +
+    [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] + [("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8")] +
+    [("s12", "<f4"), ("R12", "<f4", (3, 3)), ("t12", "<f4", 3), ("reserved_f", "<f4")])
+assert SIM3OPT_RESULT_DTYPE.itemsize == ctypes.sizeof(Sim3OptResult) == 208
 
 
 def sample_sim3_draws(rand, n_iter: int) -> np.ndarray:
@@ -449,6 +481,10 @@ def lib() -> ctypes.CDLL:
                                   f32, i32, vp, ctypes.POINTER(MatchSim3Result)]
     L.orbx_sim3_solve.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, f32, i32, vp,
                                   ctypes.POINTER(Sim3Result), vp, vp, vp]
+    L.orbx_optimize_sim3_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, f32,
+                                                  i32, i32, vp, vp]
+    L.orbx_optimize_sim3.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32,
+                                     ctypes.POINTER(Sim3OptResult), vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1947,6 +1983,95 @@ class ORBextractor:
                                                          n_iter, _ptr(d_draws), _ptr(d_res), _ptr(d_sim3), _ptr(d_match_inliers),
                                                          _ptr(d_inliers)), "orbx_sim3_solve_batch_device")
 
+    # -- Optimizer::OptimizeSim3 of loop closing (include/orbx.h, "loop closing: Sim3 optimisation") ----------------
+    def optimize_sim3(self, keys_un1, points1, mask1, pose1, keys_un2, points2, mask2, pose2, matches12, sim3, K, inv_sigma2=None,
+                      fix_scale: bool = False, th2: float = 10.0, n_iterations: int = 5, n_more_iterations: int = 10):
+        """One keyframe pair from host memory, in sim3_solve's layout: each keyframe's mvKeysUn, one map point per feature (points
+        [n, 3], mask [n]; both masks None = every feature has one), its pose Tcw (12 floats), the row matches12 [n1] (KF2's
+        feature matched to KF1's, or -1: vpMatches1), the start similarity sim3 [13] (R12, t12, s12) and K.  Returns
+        (Sim3OptResult, sim3 [13] float32, the edited row [n1] int32: removed entries are -1)."""
+        k1 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        p1 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
+        if (mask1 is None) != (mask2 is None):
+            raise OrbxError(E_BADARG, "the two masks are given together or not at all")
+        m1 = None if mask1 is None else np.ascontiguousarray(np.asarray(mask1) != 0, np.uint8).reshape(-1)
+        m2 = None if mask2 is None else np.ascontiguousarray(np.asarray(mask2) != 0, np.uint8).reshape(-1)
+        row = np.array(matches12, np.int32).reshape(-1)  # (a copy: edited in place)
+        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1) or (m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2))):
+            raise OrbxError(E_BADARG, "points, mask and matches12 must have one entry per keypoint of their keyframe")
+        T1, T2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (pose1, pose2))
+        sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        res, out = Sim3OptResult(), np.zeros(13, np.float32)
+        if len(row) == 0:
+            row = np.full(1, -1, np.int32)
+        self._check(self._L.orbx_optimize_sim3(self._h, _ptr(k1), len(k1), _ptr(p1), _ptr(m1), _ptr(T1), _ptr(k2), len(k2), _ptr(p2),
+                                               _ptr(m2), _ptr(T2), _ptr(row), _ptr(sim), _ptr(Kf), _ptr(sig), int(bool(fix_scale)),
+                                               float(th2), int(n_iterations), int(n_more_iterations), ctypes.byref(res), _ptr(out)),
+                    "orbx_optimize_sim3")
+        return res, out, row[:len(k1)]
+
+    def optimize_sim3_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_n, d_matches, n_point_sets: int, d_points,
+                                   d_point_mask, d_pose, d_sim3, K, d_res, d_sim3_out=None, inv_sigma2=None, fix_scale: bool = False,
+                                   th2: float = 10.0, n_iterations: int = 5, n_more_iterations: int = 10,
+                                   capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: problem p refines the similarity d_sim3[p] (float32 [n_problems, 13]: R12, t12, s12, as
+        sim3_solve_batch_device writes it) between keyframe kf1[p] (point set set1[p]) and keyframe kf2[p] (set2[p]) over the
+        row d_matches[p] (int32 [n_problems, capacity], as match_sim3_pairs_device leaves it), which is edited in place: a removed
+        correspondence becomes -1.  Outputs: d_res [n_problems] SIM3OPT_RESULT_DTYPE records (208 bytes); d_sim3_out float32
+        [n_problems, 13], default d_sim3 itself.  Stream-ordered: valid after a device synchronisation."""
+        kf1, kf2 = np.ascontiguousarray(kf1, np.int32), np.ascontiguousarray(kf2, np.int32)
+        set1, set2 = np.ascontiguousarray(set1, np.int32), np.ascontiguousarray(set2, np.int32)
+        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
+        if len(kf2) != P or len(set1) != P or len(set2) != P:
+            raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
+        if d_sim3_out is None:
+            d_sim3_out = d_sim3
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if sig is not None and len(sig) != self.nlevels:
+            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
+        _need("the count array", d_n, n_frames * 4)
+        _need("the match array", d_matches, P * cap * 4)
+        _need("the point array", d_points, n_point_sets * cap * 12)
+        if d_point_mask is not None:
+            _need("the point mask", d_point_mask, n_point_sets * cap)
+        _need("the pose array", d_pose, n_frames * 48)
+        _need("the similarity array", d_sim3, P * 52)
+        _need("the result array", d_res, P * SIM3OPT_RESULT_DTYPE.itemsize)
+        _need("the output similarity array", d_sim3_out, P * 52)
+        self._order_torch(d_kps_un, d_n, d_matches, d_points, d_point_mask, d_pose, d_sim3, d_res, d_sim3_out)
+        self._check(self._L.orbx_optimize_sim3_batch_device(self._h, n_frames, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2),
+                                                            _ptr(d_kps_un), _ptr(d_n), cap, _ptr(d_matches), n_point_sets,
+                                                            _ptr(d_points), _ptr(d_point_mask), _ptr(d_pose), _ptr(d_sim3), _ptr(Kf),
+                                                            _ptr(sig), int(bool(fix_scale)), float(th2), int(n_iterations),
+                                                            int(n_more_iterations), _ptr(d_res), _ptr(d_sim3_out)),
+                    "orbx_optimize_sim3_batch_device")
+
+    def compute_sim3_optimized_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets: int,
+                                            d_points, d_point_mask, d_point_dist, d_pose, K, bounds: Tuple[int, int, int, int], d_draws,
+                                            d_sim3_res, d_sim3, d_matches, d_msim3_res, d_opt_res, d_point_desc=None,
+                                            fix_scale: bool = False, th: float = 7.5, ORBdist: int = 100, opt_th2: float = 10.0,
+                                            n_iterations: int = 5, n_more_iterations: int = 10, inv_sigma2=None,
+                                            capacity: Optional[int] = None, **ransac) -> None:
+        """LoopClosing::ComputeSim3 for pairs up to the number that decides whether a candidate closes the loop: the two calls
+        of compute_sim3_pairs_device, then optimize_sim3_pairs_device on the similarity and the widened row they leave, all
+        three queued on the context's stream with no copy and no wait between them.  d_sim3 is refined in place, d_matches loses
+        the correspondences the optimisation removes, d_opt_res[p].n_inliers is nInliers (a loop needs >= 20).  A pair without a
+        similarity has zeros in d_sim3: the optimiser flags it (SIM3OPT_NONFINITE: s12 <= 0) and returns its inputs."""
+        self.compute_sim3_pairs_device(n_frames, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets, d_points,
+                                       d_point_mask, d_point_dist, d_pose, K, bounds, d_draws, d_sim3_res, d_sim3, d_matches, d_msim3_res,
+                                       d_point_desc, fix_scale, th, ORBdist, capacity, **ransac)
+        self.optimize_sim3_pairs_device(n_frames, kf1, kf2, set1, set2, d_kps_un, d_n, d_matches, n_point_sets, d_points, d_point_mask,
+                                        d_pose, d_sim3, K, d_opt_res, None, inv_sigma2, fix_scale, opt_th2, n_iterations,
+                                        n_more_iterations, capacity)
+
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:
         w, h = ctypes.c_int(0), ctypes.c_int(0)
@@ -2759,3 +2884,24 @@ class Optimizer:
         T = np.eye(4, dtype=np.float32)
         T[:3, :3], T[:3, 3] = np.array(res.R[:], np.float32).reshape(3, 3), np.array(res.tcw[:], np.float32)
         return int(res.n_inliers), T, outlier, res
+
+    @staticmethod
+    def OptimizeSim3(kf1: Frame, kf2: Frame, map1, map2, matches12, s12: float, R12, t12, th2: float = 10.0, bFixScale: bool = False,
+                     K=None, extractor: Optional[ORBextractor] = None, n_iterations: int = 5, n_more_iterations: int = 10):
+        """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (include/orbx.h, "loop closing: Sim3
+        optimisation").  map1 / map2: (points [N, 3], mask [N] or None, Tcw 3x4 or 4x4) of each keyframe; matches12 int32 [N1]:
+        KF2's feature per feature of KF1, or -1.  Returns (nIn, the edited matches12, (s12, R12 3x3, t12), the Sim3OptResult): the similarity is
+        the one given when nIn is 0 because fewer than 10 correspondences survived the first classification."""
+        ext = extractor or kf1.mpORBextractor or kf2.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "Optimizer needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(kf1, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "Optimizer.OptimizeSim3 needs K (the keyframe carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        (p1, m1, T1), (p2, m2, T2) = map1, map2
+        sim = np.r_[np.asarray(R12, np.float32).reshape(9), np.asarray(t12, np.float32).reshape(3), np.float32(s12)].astype(np.float32)
+        res, out, row = ext.optimize_sim3(kf1.mvKeysUn, p1, m1, _pose12(T1), kf2.mvKeysUn, p2, m2, _pose12(T2), matches12, sim, K, None, bFixScale, th2,
+                                          n_iterations, n_more_iterations)
+        return int(res.n_inliers), row, (float(out[12]), out[:9].reshape(3, 3).copy(), out[9:12].copy()), res

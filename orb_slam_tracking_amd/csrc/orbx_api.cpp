@@ -176,6 +176,7 @@ struct orbx_ctx {
   PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
   PnpScratch pnp;                 // orbx_pnp_solve* (orbx_pose.cpp)
   Sim3Scratch sim3;               // orbx_sim3_solve* (orbx_pose.cpp)
+  Sim3OptScratch sim3Opt;         // orbx_optimize_sim3* (orbx_pose.cpp)
   TriScratch tri;                 // orbx_match_triangulation*, orbx_triangulate_matches* (orbx_match_bow.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
@@ -2516,6 +2517,7 @@ BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }
 PoseScratch* ctxPose(orbx_ctx* c) { return &c->pose; }
 PnpScratch* ctxPnp(orbx_ctx* c) { return &c->pnp; }
 Sim3Scratch* ctxSim3(orbx_ctx* c) { return &c->sim3; }
+Sim3OptScratch* ctxSim3Opt(orbx_ctx* c) { return &c->sim3Opt; }
 TriScratch* ctxTri(orbx_ctx* c) { return &c->tri; }
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;

@@ -231,4 +231,11 @@ struct Sim3Scratch {
   DeviceBuf<uint8_t> dIo;       // staging of orbx_sim3_solve
 };
 
+// What a context keeps for orbx_optimize_sim3* (orbx_pose.cpp).
+struct Sim3OptScratch {
+  HeldArray<int32_t> problems;  // the lists [4][n_problems] (KF1, KF2, set 1, set 2) of the last call
+  HeldArray<float> sigma;       // inv_sigma2 of the last call
+  DeviceBuf<uint8_t> dIo;       // staging of orbx_optimize_sim3
+};
+
 }  // namespace orbx

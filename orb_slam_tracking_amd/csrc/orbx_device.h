@@ -777,4 +777,24 @@ struct Sim3Args {
   float fx, fy, cx, cy, th2;
   int32_t nProblems, cap, nLevels, nIter, minInliers, fixScale;
 };
+
+// k_sim3_optimize: Optimizer::OptimizeSim3 (include/orbx.h, "loop closing: Sim3 optimisation"), a wave per problem
+constexpr int SIM3OPT_WAVES = 4;  // problems per workgroup; the waves share nothing
+constexpr int SIM3OPT_THREADS = 64 * SIM3OPT_WAVES;
+constexpr int SIM3OPT_MAX_CAPACITY = 16384;  // ORBX_BOW_MAX_FEATURES
+struct Sim3OptArgs {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const int32_t* nKps;        // [frames]
+  const int32_t* problems;    // [4][nProblems] KF1s, KF2s, KF1s' point sets, KF2s' point sets
+  int32_t* row;               // [nProblems][cap] in and out: the feature of KF2 matched to KF1's feature, or -1
+  const float* points;        // [sets][cap][3]
+  const uint8_t* mask;        // nullable [sets][cap]
+  const float* pose;          // [frames][12] Tcw
+  const float* sim3;          // [nProblems][13] R12 row-major, t12, s12
+  const float* invSigma2;     // [nLevels] (device)
+  orbx_sim3opt_result* res;   // [nProblems]
+  float* sim3Out;             // [nProblems][13], may be sim3
+  double fx, fy, cx, cy, delta, th2;
+  int32_t nProblems, cap, nLevels, nIterations, nMoreIterations, fixScale;
+};
 }  // namespace orbx

@@ -26,6 +26,7 @@ BaScratch* ctxBa(orbx_ctx* c);
 PoseScratch* ctxPose(orbx_ctx* c);
 PnpScratch* ctxPnp(orbx_ctx* c);
 Sim3Scratch* ctxSim3(orbx_ctx* c);
+Sim3OptScratch* ctxSim3Opt(orbx_ctx* c);
 TriScratch* ctxTri(orbx_ctx* c);
 
 // ... and of a vocabulary (orbx_vocabulary is private to orbx_bow.cpp): the context it was made on, and the descent alone over

@@ -1,7 +1,8 @@
 // orbx_pose.cpp — host side of what runs behind SearchByBoW: Optimizer::PoseOptimization (include/orbx.h, "behind SearchByBoW:
 // pose optimisation"; the kernel is in orbx_pose_kernel.hip) and, below it, PnPsolver, which gives a lost frame the start pose
 // ("behind SearchByBoW: PnP RANSAC"; orbx_pnp_kernel.hip), and Sim3Solver, PnPsolver's 3D-3D sibling of loop closing ("loop
-// closing: Sim3 RANSAC"; orbx_sim3_kernel.hip).  For each: the argument checks, the problem list, the held tables and the C
+// closing: Sim3 RANSAC"; orbx_sim3_kernel.hip), and at the end Optimizer::OptimizeSim3 ("loop closing: Sim3 optimisation";
+// orbx_sim3opt_kernel.hip).  For each: the argument checks, the problem list, the held tables and the C
 // entry points.
 #include <hip/hip_runtime.h>
 
@@ -497,6 +498,146 @@ int orbx_sim3_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const f
   HIPCHK(down(sim3, dSim, 13, st));
   HIPCHK(down(match_inliers, dRow, n1, st));
   if (inliers) HIPCHK(down(inliers, dI, n1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- Optimizer::OptimizeSim3 (include/orbx.h, "loop closing: Sim3 optimisation"; orbx_sim3opt_kernel.hip) ------------------------
+namespace {
+
+bool sim3OptParamsOk(int fixScale, float th2, int nIterations, int nMoreIterations) {
+  return (fixScale == 0 || fixScale == 1) && th2 > 0.f && std::isfinite(th2) && nIterations >= 0 && nMoreIterations >= 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_optimize_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_kf1, const int32_t* h_kf2,
+                                    const int32_t* h_set1, const int32_t* h_set2, const orbx_keypoint* d_kps_un, const int32_t* d_n,
+                                    int capacity, int32_t* d_matches, int n_point_sets, const float* d_points,
+                                    const uint8_t* d_point_mask, const float* d_pose, const float* d_sim3, const float* K,
+                                    const float* inv_sigma2, int fix_scale, float th2, int n_iterations, int n_more_iterations,
+                                    orbx_sim3opt_result* d_res, float* d_sim3_out) {
+  if (n_frames < 0 || n_problems < 0 || n_point_sets < 0 || capacity < 1 ||
+      (n_problems > 0 && (!h_kf1 || !h_kf2 || !h_set1 || !h_set2)) || !d_kps_un || !d_n || !d_matches || !d_points || !d_pose ||
+      !d_sim3 || !K || !d_res || !d_sim3_out || !sim3OptParamsOk(fix_scale, th2, n_iterations, n_more_iterations))
+    return ORBX_E_BADARG;
+  if (!pairsInRange(h_kf1, h_kf2, n_problems, n_frames) || !pairsInRange(h_set1, h_set2, n_problems, n_point_sets)) {
+    if (ctx) ctxSetError(ctx, "optimize sim3: keyframe outside [0, n_frames) or point set outside [0, n_point_sets)");
+    return ORBX_E_BADARG;
+  }
+  if (capacity > SIM3OPT_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "optimize sim3: capacity above ORBX_BOW_MAX_FEATURES");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_problems == 0) return ORBX_OK;
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  Sim3OptScratch* s = ctxSim3Opt(ctx);
+  hipStream_t st = ctxStream(ctx);
+  int nLevels = 0;
+  const float* table = ctxInvSigma2(ctx, &nLevels);
+  const float* sig = inv_sigma2 ? inv_sigma2 : table;
+  // the lists and the table go up only when they differ from the last call's; such a call first waits for the context stream, as
+  // orbx_pose_optimize_batch_device does (include/orbx.h)
+  std::vector<int32_t> lists;
+  lists.reserve((size_t)4 * n_problems);
+  for (const int32_t* c : {h_kf1, h_kf2, h_set1, h_set2}) lists.insert(lists.end(), c, c + n_problems);
+  const bool sameList = s->problems.holds(lists.data(), lists.size()), sameSigma = s->sigma.holds(sig, nLevels);
+  if (!sameList || !sameSigma) HIPCHK(hipStreamSynchronize(st));
+  if (!sameList) HIPCHK(s->problems.replace(st, lists.data(), lists.size()));
+  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
+  Sim3OptArgs a{};
+  a.kps = d_kps_un;
+  a.nKps = d_n;
+  a.problems = s->problems;
+  a.row = d_matches;
+  a.points = d_points;
+  a.mask = d_point_mask;
+  a.pose = d_pose;
+  a.sim3 = d_sim3;
+  a.invSigma2 = s->sigma;
+  a.res = d_res;
+  a.sim3Out = d_sim3_out;
+  intrinsics(K, &a.fx, &a.fy, &a.cx, &a.cy);
+  a.delta = (double)(float)std::sqrt((double)th2);  // `const float deltaHuber = sqrt(th2)` of the ORB-SLAM2 design
+  a.th2 = (double)th2;
+  a.nProblems = n_problems;
+  a.cap = capacity;
+  a.nLevels = nLevels;
+  a.nIterations = n_iterations;
+  a.nMoreIterations = n_more_iterations;
+  a.fixScale = fix_scale;
+  HIPCHK(launch_sim3_optimize(st, a));
+  return ORBX_OK;
+}
+
+int orbx_optimize_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* points1, const uint8_t* mask1,
+                       const float* pose1, const orbx_keypoint* kps_un2, int n2, const float* points2, const uint8_t* mask2,
+                       const float* pose2, int32_t* matches12, const float* sim3, const float* K, const float* inv_sigma2,
+                       int fix_scale, float th2, int n_iterations, int n_more_iterations, orbx_sim3opt_result* res, float* sim3_out) {
+  if (n1 < 0 || n2 < 0 || !pose1 || !pose2 || !sim3 || !K || !res || !sim3_out || (n1 > 0 && (!kps_un1 || !points1 || !matches12)) ||
+      (n2 > 0 && (!kps_un2 || !points2)) || (mask1 == nullptr) != (mask2 == nullptr) ||
+      !sim3OptParamsOk(fix_scale, th2, n_iterations, n_more_iterations))
+    return ORBX_E_BADARG;
+  const int cap = std::max(std::max(n1, n2), 1);
+  if (cap > SIM3OPT_MAX_CAPACITY) {
+    if (ctx) ctxSetError(ctx, "optimize sim3: more than ORBX_BOW_MAX_FEATURES keypoints");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  Sim3OptScratch* s = ctxSim3Opt(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  int32_t *dN, *dRow;
+  float *dP, *dPose, *dSim, *dSimOut;
+  uint8_t* dM;
+  orbx_sim3opt_result* dR;
+  auto staging = [&](Layout L) {  // two frames and two point sets in the batch layout, then the results
+    dK = L.take<orbx_keypoint>((size_t)2 * cap);
+    dN = L.take<int32_t>(2);
+    dP = L.take<float>((size_t)2 * cap * 3);
+    dM = L.take<uint8_t>((size_t)2 * cap);
+    dPose = L.take<float>(24);
+    dRow = L.take<int32_t>(cap);
+    dSim = L.take<float>(13);
+    dSimOut = L.take<float>(13);
+    dR = L.take<orbx_sim3opt_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dIo.grow(bytes, st));
+  staging(Layout(s->dIo));
+  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
+  HIPCHK(up(dK, kps_un1, n1, st));
+  HIPCHK(up(dK + cap, kps_un2, n2, st));
+  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
+  HIPCHK(up(dP + (size_t)cap * 3, points2, (size_t)n2 * 3, st));
+  if (mask1) {
+    HIPCHK(up(dM, mask1, n1, st));
+    HIPCHK(up(dM + cap, mask2, n2, st));
+  }
+  HIPCHK(up(dN, hn, 2, st));
+  HIPCHK(up(dPose, pose1, 12, st));
+  HIPCHK(up(dPose + 12, pose2, 12, st));
+  HIPCHK(up(dRow, matches12, n1, st));
+  HIPCHK(up(dSim, sim3, 13, st));
+  r = orbx_optimize_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dN, cap, dRow, 2, dP, mask1 ? dM : nullptr, dPose, dSim, K,
+                                      inv_sigma2, fix_scale, th2, n_iterations, n_more_iterations, dR, dSimOut);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(down(sim3_out, dSimOut, 13, st));
+  HIPCHK(down(matches12, dRow, n1, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }
