@@ -980,6 +980,126 @@ int orbx_optimize_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, cons
                        const float* pose2, int32_t* matches12, const float* sim3, const float* K, const float* inv_sigma2,
                        int fix_scale, float th2, int n_iterations, int n_more_iterations, orbx_sim3opt_result* res, float* sim3_out);
 
+/* ---- loop closing: matching the loop's points under Scw (ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)) ------
+ * The tail of LoopClosing::ComputeSim3: once OptimizeSim3 accepts a candidate (nInliers >= 20) it composes mScw = Scm * Smw,
+ * projects the map points of the loop keyframe and its covisible neighbours (mvpLoopMapPoints) into the current keyframe with th =
+ * 10, and accepts the loop when nTotalMatches >= 40; the row it leaves is mvpCurrentMatchedPoints, which CorrectLoop starts from.
+ * The reference ships no such function: this is ORB-SLAM2's code, [from-knowledge], PARITY UNPINNED, bit-identical to a CPU
+ * restatement of the rules below (tests/cpp/match_scw_ref.cpp).  The window search alone is pinned: it is the reference's
+ * Frame::GetFeaturesInArea (SlamTypes/Frame.cpp:163-206), and the tests compare it with the reference's own compiled code.
+ *
+ * Pair p: current keyframe C = h_kf[p] (n_C features), map set s = h_map_set[p] (n_s = d_map_n[s] points, the arrays of matching
+ * the local map by projection), the similarity d_scw[p] (12 floats: the top three rows of mScw as a CV_32F matrix, sR row-major,
+ * then t), the row d_matches[p] (C's feature j -> an index into set s, or a negative value; read and written).  f32 without
+ * contraction unless stated.
+ *   1. the decomposition: scw = (float)sqrt((double)((sR00*sR00 + sR01*sR01) + sR02*sR02)), the dot product in f32; Rcw = sR /
+ *      scw and tcw = t / scw element-wise, correctly rounded; Ow_k = -((Rcw[0][k]*tcw0 + Rcw[1][k]*tcw1) + Rcw[2][k]*tcw2).
+ *   2. what C already has (vpMatched[j] != NULL: feature j is taken; the set of those points is spAlreadyFound, and such a point
+ *      is not searched).  Without d_kf2_to_map an entry i >= 0 is an index into set s.  With d_kf2_to_map [n_pairs][capacity]
+ *      the entry row holds the MATCHED keyframe's feature indices as orbx_optimize_sim3_batch_device leaves them, and the table
+ *      maps such a feature to an index in set s, or to a negative value: each entry i2 >= 0 is translated through the table and
+ *      the translated value is written back.  An entry that translates to a negative value becomes ORBX_SCW_TAKEN_UNMAPPED: the
+ *      feature stays taken, no point is marked found, and the entry counts in n_unmapped; an entry that holds
+ *      ORBX_SCW_TAKEN_UNMAPPED on entry is treated, and counted, likewise.  Any other negative entry is free.  An entry >= n_s,
+ *      with the table an entry i2 >= capacity, and a translated value >= n_s are never followed: the entry stays as it is, its
+ *      feature counts as taken and ORBX_SCW_BAD_INPUT is set.  There is no outlier input.
+ *   3. the points searched: points i of the set in ascending order whose mask byte is set and that are not found.  Pc = Rcw*P +
+ *      tcw as xc = ((R0*X + R1*Y) + R2*Z) + t0, yc and zc likewise.  zc < 0.0f: skipped (n_behind); zc == 0 goes on and fails the
+ *      image test.  invz = 1.0f / zc correctly rounded; u = fx*(xc*invz) + cx, v = fy*(yc*invz) + cy.  KeyFrame::IsInImage: the
+ *      point stays iff u >= min_x && u < max_x && v >= min_y && v < max_y -- half-open above; a value that is no number fails.
+ *   4. PO = P - Ow; dist = (float)sqrt(((double)POx*POx + (double)POy*POy) + (double)POz*POz), the products and sums in f64 in
+ *      that order (cv::norm of a CV_32F vector); dist < 0.8f*minDist || dist > 1.2f*maxDist: skipped (d_map_dist holds the raw
+ *      mfMinDistance, mfMaxDistance).
+ *   5. the viewing angle: with dot = ((double)POx*Nx + (double)POy*Ny) + (double)POz*Nz, products and sums in f64 in that order,
+ *      the point is skipped when dot < 0.5 * (double)dist -- a comparison in f64 (PO.dot(Pn) < 0.5*dist).
+ *   6. level = PredictScale in table form on ratio = maxDist / dist (correctly rounded): the number of n in [0, nlevels - 1)
+ *      with ratio > scale[n].  r = th * scale[level]; the candidates are GetFeaturesInArea(u, v, r) over C's undistorted
+ *      keypoints, the reference's function without level bounds (PosInGrid's rounding, the clamped cell range, the strict
+ *      fabs(d) < r in both coordinates), in the order cell x outer, cell y inner, ascending index inside a cell; of them only
+ *      those with octave in [level - 1, level] stay.  None stays: the point is skipped (n_with_candidates counts the others).
+ *   7. over the candidates that are not taken, neither on entry nor by an earlier point of this call, in that order, with d =
+ *      popcount(d_map_desc32[s][i] ^ desc_C[j]): the first smallest wins (dist < bestDist, starting from 256).  bestDist <=
+ *      th_low: d_matches[p][bestIdx] = i, bestIdx is taken and nmatches counts it.  No ratio test, no orientation histogram.
+ *   8. n_total = the entries of the row that are not free on exit: the entry's matches, unmapped and unfollowed ones included,
+ *      plus the new ones.  This is ComputeSim3's nTotalMatches (a loop needs >= 40).
+ * Documented deviations from ORB-SLAM2:
+ *   1. PredictScale in table form (deviation 1 of matching the local map by projection).
+ *   2. Map points are arrays plus a mask (0 = NULL or isBad()), matches are indices into the pair's map set; a matched point
+ *      that is not in the set keeps its feature through ORBX_SCW_TAKEN_UNMAPPED.
+ *   3. th_low is an argument (ORBmatcher::TH_LOW is 50), accepted in [0, 256]: 0 accepts only an identical descriptor; 255 and
+ *      256 accept every candidate but one at distance 256, which `dist < bestDist` never picks.
+ *   4. Garbage is flagged and never followed.  Counts outside [0, capacity] / [0, map_capacity] are clamped and set
+ *      ORBX_SCW_BAD_INPUT, as do the entries of rule 2.  A similarity with a non-finite value, scw that is not a finite number > 0
+ *      or a quotient of rule 1 that is not finite sets ORBX_SCW_NONFINITE, drops every point of rule 3 and leaves the row as
+ *      rule 2 left it; a point of rule 3 whose position, normal or two distances hold a non-finite value sets it and is
+ *      dropped, as is one whose ratio is no number.  A keypoint whose cell is no number is in no cell; window cells are clamped
+ *      as floats.
+ * Worst case: points whose windows all share candidates within th_low resolve one per round (see the kernel). */
+#define ORBX_SCW_BAD_INPUT 2        /* a count outside its capacity, an entry of rule 2 that is never followed */
+#define ORBX_SCW_NONFINITE 4        /* a similarity rule 1 cannot decompose, a non-finite point / normal / distance or ratio */
+#define ORBX_SCW_TAKEN_UNMAPPED (-2) /* d_matches: the feature has a map point that is not in the pair's map set */
+typedef struct orbx_scw_result {
+  int32_t status;             /* 0, or a bitmask of ORBX_SCW_*; every field is written for every pair */
+  int32_t nmatches;           /* new matches (rule 7) */
+  int32_t n_total;            /* rule 8: nTotalMatches */
+  int32_t n_points;           /* points that reach rule 3: mask set, not found */
+  int32_t n_found;            /* points some entry of the row names (whatever their mask) */
+  int32_t n_unmapped;         /* entries that are ORBX_SCW_TAKEN_UNMAPPED behind rule 2 */
+  int32_t n_behind;           /* rule 3: zc < 0 */
+  int32_t n_out_image;        /* ... outside [min, max) or no number */
+  int32_t n_out_distance;     /* rule 4 */
+  int32_t n_out_angle;        /* rule 5 */
+  int32_t n_with_candidates;  /* searched points whose window holds a feature of their octaves (rule 6) */
+  int32_t n_over_dist;        /* ... whose bestDist is above th_low (256 when every candidate is taken) */
+  int32_t n_displaced;        /* searched points whose pick (the feature, or none) differs from what they would get with only
+                                 the entry's matches taken */
+  int32_t rounds;             /* the device's rounds of claims; a sequential statement reports 0 */
+} orbx_scw_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  d_kps_un / d_desc32 (16-byte aligned) / d_n: the keyframes, in
+ * the layout of the extract and undistort calls ([n_frames][capacity]).  Map set s of [n_map_sets][map_capacity], exactly the
+ * arrays of orbx_match_local_map_batch_device: d_map_n int32 [n_map_sets], d_map_points float [3], d_map_normals float [3],
+ * d_map_dist float [2], d_map_desc32 uint8 [32] (16-byte aligned), d_map_mask uint8 (NULL = every entry is a point); several
+ * pairs may share a keyframe or a map set.  d_scw float [n_pairs][12], as orbx_sim3_compose_scw_batch_device writes it.  K
+ * row-major 3x3 (host, f32), bounds = the keyframes' image bounds, th > 0 (ComputeSim3 passes 10), th_low in [0, 256] (TH_LOW =
+ * 50).  d_matches int32 [n_pairs][capacity], in and out and required; entries at and beyond C's count are not touched.
+ * d_kf2_to_map int32 [n_pairs][capacity] or NULL (rule 2).  d_res [n_pairs].
+ * One workgroup per pair, one launch.  The call returns once queued, with the exception orbx_match_bow_batch_device has: when the
+ * pair lists differ from the previous call's on this context, the call first waits for the context stream before it uploads
+ * them.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity or map_capacity < 1, th not finite or <= 0, th_low outside
+ * [0, 256], bounds with max <= min, a keyframe outside [0, n_frames), a map set outside [0, n_map_sets) -- all checked before
+ * anything touches a device; ORBX_E_CAPACITY: capacity or map_capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with
+ * otherwise well-formed arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_match_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                                const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                int n_map_sets, int map_capacity, const int32_t* d_map_n, const float* d_map_points,
+                                const float* d_map_normals, const float* d_map_dist, const uint8_t* d_map_desc32,
+                                const uint8_t* d_map_mask, const float* d_scw, const float* K, const orbx_bounds* bounds, float th,
+                                int th_low, int32_t* d_matches, const int32_t* d_kf2_to_map, orbx_scw_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: the keyframe (n features), the map (map_n
+ * points; map_mask nullable), scw [12]; matches [n] in and out; kf2_to_map [n_table] nullable (an entry >= n_table is an entry
+ * beyond the table: never followed).  More than ORBX_BOW_MAX_FEATURES features, points or table entries: ORBX_E_CAPACITY.
+ * Synchronous. */
+int orbx_match_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+                   const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+                   const float* scw, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches,
+                   const int32_t* kf2_to_map, int n_table, orbx_scw_result* res);
+
+/* The similarity in front of it: d_scw[p] = S12 * Tmw from d_sim3[p] (13 floats: R12 row-major, t12, s12; keyframe 1 is the
+ * current one, as orbx_optimize_sim3_batch_device writes it) and the matched keyframe's pose d_pose[h_kf2[p]] (12 floats: Rmw
+ * row-major, then tmw).  In f64 from the f32 inputs: R = R12 * Rmw, each element (a + b) + c; q = R12 * tmw likewise; t = s12*q +
+ * t12; the output is (float)(s12 * R) row-major followed by (float)t.
+ * Documented deviation: g2o multiplies two Sim3 through unit quaternions and Converter::toCvMat converts back.  Here the matrices
+ * are multiplied directly, which differs from g2o's result only by rounding and needs no quaternion normalisation on either side.
+ * A non-finite input or s12 that is not > 0 writes twelve zeros, which the matcher flags as ORBX_SCW_NONFINITE.
+ * A lane per pair, one launch; stream-ordered, with the list exception above.  ORBX_E_BADARG: null required pointers, negative
+ * counts, a keyframe outside [0, n_frames); ORBX_E_HIP: ctx == NULL otherwise.  n_pairs == 0 is ORBX_OK. */
+int orbx_sim3_compose_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf2, const float* d_pose,
+                                       const float* d_sim3, float* d_scw);
+/* The same for one pair in host memory: pose2 [12], sim3 [13] -> scw [12].  Synchronous. */
+int orbx_sim3_compose_scw(orbx_ctx* ctx, const float* pose2, const float* sim3, float* scw);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

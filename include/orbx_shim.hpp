@@ -452,6 +452,18 @@ class ORBmatcher {
   int SearchByProjection(FrameT& CurrentFrame, const KeyFrameView& KF, std::vector<int>& vnMatches, float th, int ORBdist,
                          const PoseT& Tcw, const std::vector<bool>* vbOutlier = nullptr, orbx_kfproj_result* result = nullptr);
 
+  // ORB-SLAM2's loop-closing overload SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+  // vector<MapPoint*>& vpMatched, int th) (orbx.h, "loop closing: matching the loop's points under Scw", with its documented
+  // deviations): the loop's map points `map` are projected into the current keyframe KF under the similarity Scw (the 4x4 mScw:
+  // sR and t in its top three rows) and matched within TH_LOW.  vpMatched[j] = the index into `map` of feature j's map point,
+  // ORBX_SCW_TAKEN_UNMAPPED, or -1 -- in and out: on entry what ComputeSim3 has (any other size than KF.N stands for none), on
+  // exit those plus the new ones (mvpCurrentMatchedPoints).  Returns the number of new matches; result->n_total is
+  // nTotalMatches.  K: 9 floats, row-major; bounds: the keyframe's image bounds (KeyFrameView carries neither).
+  int SearchByProjection(const KeyFrameView& KF, const PoseT& Scw, const MapView& map, std::vector<int>& vpMatched, float th,
+                         const float* K, const orbx_bounds& bounds, int thLow = 50, orbx_scw_result* result = nullptr) {
+    return searchScw(ext_, KF, Scw, map, vpMatched, th, K, bounds, thLow, result);
+  }
+
   // ORB-SLAM2's SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
   // const bool bOnlyStereo = false), monocular (orbx.h, "growing the map", with its documented deviations; the orientation check
   // is this matcher's): the features of KF1 without a map point are matched along their epipolar lines against KF2's features
@@ -517,6 +529,8 @@ class ORBmatcher {
   inline int searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,
                             int ORBdist, const PoseT& Tcw, const float* K, const std::vector<bool>* vbOutlier,
                             orbx_kfproj_result* result);  // (defined behind PoseT)
+  inline int searchScw(ORBextractor* e, const KeyFrameView& KF, const PoseT& Scw, const MapView& map, std::vector<int>& vpMatched,
+                       float th, const float* K, const orbx_bounds& bounds, int thLow, orbx_scw_result* result);  // (defined behind PoseT)
   inline int searchForTriangulation(ORBextractor* e, const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
                                     std::vector<std::pair<size_t, size_t> >& vMatchedPairs, float medianDepth2,
                                     orbx_tri_match_result* result);  // (defined behind DBoW2::FeatureVector)
@@ -1121,6 +1135,28 @@ int ORBmatcher::SearchByProjection(FrameT& F, const MapView& map, float th, cons
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) K[r * 3 + c] = frameK(F.mK, r, c);
   return searchLocalMap(ext_ ? ext_ : F.mpORBextractor, frameView(F), map, th, Tcw, K, vnMatches, vbOutlier, pointView, result);
+}
+
+inline int ORBmatcher::searchScw(ORBextractor* e, const KeyFrameView& KF, const PoseT& Scw, const MapView& map, std::vector<int>& vpMatched,
+                                 float th, const float* K, const orbx_bounds& bounds, int thLow, orbx_scw_result* result) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): none was set");
+  const size_t n = (size_t)(KF.N > 0 ? KF.N : 0);
+  float scw[12];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) scw[r * 3 + c] = (float)Scw(r, c);
+    scw[9 + r] = (float)Scw(r, 3);
+  }
+  if (vpMatched.size() != n) vpMatched.assign(n, -1);
+  std::vector<int32_t> row(vpMatched.begin(), vpMatched.end());
+  if (row.empty()) row.push_back(-1);
+  orbx_scw_result res;
+  const int r = orbx_match_scw(e->context(), reinterpret_cast<const orbx_keypoint*>(KF.mvKeysUn), KF.mDescriptors, KF.N, map.N,
+                               map.mWorldPos, map.mNormalVector, map.mfMinMaxDistance, map.mDescriptors, map.mbGood, scw, K, &bounds, th,
+                               thLow, row.data(), nullptr, 0, &res);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  vpMatched.assign(row.begin(), row.begin() + n);
+  if (result) *result = res;
+  return res.nmatches;
 }
 
 inline int ORBmatcher::searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,

@@ -24,7 +24,8 @@ import numpy as np
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame", "lib", "lib_path",
            "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "Sim3Result", "SIM3_RESULT_DTYPE", "SIM3_BAD_INPUT", "SIM3_NONFINITE", "SIM3_FEW_POINTS", "SIM3_BAD_DRAWS", "SIM3_NO_RESULT", "Sim3Solver", "sample_sim3_draws", "MatchSim3Result", "MSIM3_RESULT_DTYPE", "MSIM3_BAD_INPUT", "MSIM3_NONFINITE", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL",
-           "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE"]
+           "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE",
+           "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted"]
 
 # mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
@@ -274,6 +275,38 @@ LOCAL_RESULT_DTYPE = np.dtype([(n, "<i4") for n in LOCAL_RESULT_FIELDS])
 assert LOCAL_RESULT_DTYPE.itemsize == ctypes.sizeof(LocalResult) == 60
 
 
+SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
+SCW_RESULT_FIELDS = ("status", "nmatches", "n_total", "n_points", "n_found", "n_unmapped", "n_behind", "n_out_image", "n_out_distance",
+                     "n_out_angle", "n_with_candidates", "n_over_dist", "n_displaced", "rounds")
+
+
+class MatchScwResult(ctypes.Structure):
+    """orbx_scw_result: the counters of the loop-closing SearchByProjection under Scw for one (keyframe, map set) pair (rounds is
+    the device's own count; n_total is ComputeSim3's nTotalMatches)."""
+    _fields_ = [(n, ctypes.c_int32) for n in SCW_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+SCW_RESULT_DTYPE = np.dtype([(n, "<i4") for n in SCW_RESULT_FIELDS])
+assert SCW_RESULT_DTYPE.itemsize == ctypes.sizeof(MatchScwResult) == 56
+
+
+def loop_accepted(opt_res, scw_res, min_inliers: int = 20, min_total: int = 40) -> np.ndarray:
+    """LoopClosing::ComputeSim3's two gates over HOST record arrays (SIM3OPT_RESULT_DTYPE and SCW_RESULT_DTYPE, or their bytes):
+    accepted[p] = opt_res[p].n_inliers >= 20 and scw_res[p].n_total >= 40.  It orders nothing: device arrays go through
+    ORBextractor.loop_accepted, which reads them back behind the context's work; given one, this function refuses."""
+    def host(a, dtype):
+        if not isinstance(a, np.ndarray):
+            raise OrbxError(E_BADARG, "loop_accepted takes host record arrays; device arrays go through ORBextractor.loop_accepted")
+        return a.reshape(-1) if a.dtype == dtype else np.ascontiguousarray(a).reshape(-1).view(np.uint8).view(dtype)
+    o, m = host(opt_res, SIM3OPT_RESULT_DTYPE), host(scw_res, SCW_RESULT_DTYPE)
+    if len(o) != len(m):
+        raise OrbxError(E_BADARG, "the two result arrays must have one record per pair")
+    return (o["n_inliers"] >= int(min_inliers)) & (m["n_total"] >= int(min_total))
+
+
 KFPROJ_BAD_INPUT, KFPROJ_NONFINITE = 2, 4
 KFPROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_found", "n_behind_kept", "n_out_image", "n_out_distance", "n_with_candidates",
                         "n_over_dist", "n_displaced", "n_rot_removed", "n_outliers_cleared", "rounds")
@@ -485,6 +518,12 @@ def lib() -> ctypes.CDLL:
                                                   i32, i32, vp, vp]
     L.orbx_optimize_sim3.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32,
                                      ctypes.POINTER(Sim3OptResult), vp]
+    L.orbx_match_scw_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp]
+    L.orbx_match_scw.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp, vp, i32,
+                                 ctypes.POINTER(MatchScwResult)]
+    L.orbx_sim3_compose_scw_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.orbx_sim3_compose_scw.argtypes = [vp, vp, vp, vp]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -651,6 +690,13 @@ def _pose12(Tcw) -> np.ndarray:
     """Tcw (3x4 or 4x4) as the C ABI's pose: row-major R [9], then t [3]."""
     T = np.asarray(Tcw, np.float32)
     return np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
+
+
+def _scw12(Scw) -> np.ndarray:
+    """Scw (or a pose) as the C ABI takes it: 12 floats (the 3x3 row-major, then t) as they are, a 3x4 or 4x4 matrix through
+    _pose12."""
+    S = np.asarray(Scw, np.float32)
+    return np.ascontiguousarray(S.reshape(12)) if S.ndim == 1 else _pose12(S)
 
 
 def _need_batch(imgs, n_frames, width, height, stride, frame_stride, kps, desc, n, capacity, first=None, second=None, matches12=None,
@@ -2072,6 +2118,134 @@ class ORBextractor:
                                         d_pose, d_sim3, K, d_opt_res, None, inv_sigma2, fix_scale, opt_th2, n_iterations,
                                         n_more_iterations, capacity)
 
+    # -- the Scw SearchByProjection of loop closing (include/orbx.h, "loop closing: matching the loop's points under Scw") ------
+    def sim3_compose_scw_pairs_device(self, n_frames: int, kf2, d_pose, d_sim3, d_scw) -> None:
+        """d_scw[p] (float32 [n_pairs, 12]: sR row-major, then t) = S12 * Tmw from d_sim3[p] (float32 [n_pairs, 13]: R12, t12,
+        s12, keyframe 1 the current one) and the matched keyframe's pose d_pose[kf2[p]] (float32 [n_frames, 12]).  A pair without
+        a similarity gets twelve zeros.  Stream-ordered on the context's stream."""
+        kf2 = np.ascontiguousarray(kf2, np.int32).reshape(-1)
+        P, n_frames = len(kf2), int(n_frames)
+        _need("the pose array", d_pose, n_frames * 48)
+        _need("the similarity array", d_sim3, P * 52)
+        _need("the Scw array", d_scw, P * 48)
+        self._order_torch(d_pose, d_sim3, d_scw)
+        self._check(self._L.orbx_sim3_compose_scw_batch_device(self._h, n_frames, P, _ptr(kf2), _ptr(d_pose), _ptr(d_sim3), _ptr(d_scw)),
+                    "orbx_sim3_compose_scw_batch_device")
+
+    def sim3_compose_scw(self, pose2, sim3) -> np.ndarray:
+        """One pair from host memory: pose2 (Tmw, 12 floats or 3x4 / 4x4), sim3 [13] -> Scw [12] float32.  Synchronous."""
+        T2 = _scw12(pose2)  # (12 floats as they are, a matrix as R [9] then t [3])
+        sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
+        out = np.zeros(12, np.float32)
+        self._check(self._L.orbx_sim3_compose_scw(self._h, _ptr(T2), _ptr(sim), _ptr(out)), "orbx_sim3_compose_scw")
+        return out
+
+    def match_scw_pairs_device(self, n_frames: int, kf: np.ndarray, map_set: np.ndarray, d_kps_un, d_desc, d_n, n_map_sets: int,
+                               map_capacity: int, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_scw, K,
+                               bounds: Tuple[int, int, int, int], d_matches, d_res, th: float = 10.0, th_low: int = 50,
+                               d_kf2_to_map=None, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) of LoopClosing::ComputeSim3 for pairs (current
+        keyframe kf[p], map set map_set[p]; host index arrays): the map sets are match_local_map_pairs_device's arrays, d_scw
+        float32 [n_pairs, 12] is what sim3_compose_scw_pairs_device writes.  d_matches int32 [n_pairs, capacity] is read and
+        written: feature j's index into the pair's map set, SCW_TAKEN_UNMAPPED, or another negative value (free).  With
+        d_kf2_to_map int32 [n_pairs, capacity] the row holds the matched keyframe's feature indices on entry (the optimiser's
+        row) and is translated through the table.  d_res [n_pairs] SCW_RESULT_DTYPE records (56 bytes); n_total is
+        nTotalMatches.  Stream-ordered on the context's stream."""
+        cap, mcap, nf, ns = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets)
+        kf, map_set = _pair_lists(("kf", "map_set"), (kf, map_set), nf, ns, "map set")
+        P = len(kf)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        _need("the keypoint array", d_kps_un, nf * cap * 28)
+        _need("the descriptor array", d_desc, nf * cap * 32)
+        _need("the count array", d_n, nf * 4)
+        _need("the map count array", d_map_n, ns * 4)
+        _need("the map point array", d_map_points, ns * mcap * 12)
+        _need("the map normal array", d_map_normals, ns * mcap * 12)
+        _need("the map distance array", d_map_dist, ns * mcap * 8)
+        _need("the map descriptor array", d_map_desc, ns * mcap * 32)
+        if d_map_mask is not None:
+            _need("the map mask", d_map_mask, ns * mcap)
+        if d_kf2_to_map is not None:
+            _need("the table from the matched keyframe's features to the map set", d_kf2_to_map, P * cap * 4)
+        _need("the Scw array", d_scw, P * 48)
+        _need("matches", d_matches, P * cap * 4)
+        _need("the result array", d_res, P * SCW_RESULT_DTYPE.itemsize)
+        self._order_torch(d_kps_un, d_desc, d_n, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_scw,
+                          d_kf2_to_map, d_matches, d_res)
+        r = self._L.orbx_match_scw_batch_device(self._h, nf, P, _ptr(kf), _ptr(map_set), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n), cap, ns,
+                                                mcap, _ptr(d_map_n), _ptr(d_map_points), _ptr(d_map_normals), _ptr(d_map_dist),
+                                                _ptr(d_map_desc), _ptr(d_map_mask), _ptr(d_scw), _ptr(Kf), ctypes.byref(b), float(th),
+                                                int(th_low), _ptr(d_matches), _ptr(d_kf2_to_map), _ptr(d_res))
+        self._check(r, "orbx_match_scw_batch_device")
+
+    def match_scw(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K,
+                  bounds: Tuple[int, int, int, int], matches=None, th: float = 10.0, th_low: int = 50, kf2_to_map=None):
+        """The same for one keyframe and one map set in host memory (orbx_match_scw) -> (matches int32 [len(keys_un)],
+        MatchScwResult).  Scw: 12 floats (sR row-major, then t) or a 3x4 / 4x4 matrix; matches (default all -1): vpMatched as
+        indices into the map arrays, or with kf2_to_map as the matched keyframe's feature indices.  Synchronous."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        mp = np.ascontiguousarray(map_points, np.float32).reshape(-1, 3)
+        mn = np.ascontiguousarray(map_normals, np.float32).reshape(-1, 3)
+        md = np.ascontiguousarray(map_dist, np.float32).reshape(-1, 2)
+        mdesc = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, 32)
+        if len(k) != len(d) or not (len(mp) == len(mn) == len(md) == len(mdesc)):
+            raise OrbxError(E_BADARG, "keypoints / descriptors or the map arrays differ in length")
+        mm = None if map_mask is None else np.ascontiguousarray(np.asarray(map_mask) != 0, np.uint8).reshape(-1)
+        if mm is not None and len(mm) != len(mp):
+            raise OrbxError(E_BADARG, "the map mask needs one entry per map point")
+        m = np.full(max(len(k), 1), -1, np.int32)
+        if matches is not None:
+            given = np.asarray(matches, np.int32).reshape(-1)
+            if len(given) != len(k):
+                raise OrbxError(E_BADARG, "matches needs one entry per feature")
+            m[:len(k)] = given
+        tab = None if kf2_to_map is None else np.ascontiguousarray(kf2_to_map, np.int32).reshape(-1)
+        S = _scw12(Scw)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        b = _Bounds(*[int(v) for v in bounds])
+        res = MatchScwResult()
+        r = self._L.orbx_match_scw(self._h, _ptr(k), _ptr(d), len(k), len(mp), _ptr(mp), _ptr(mn), _ptr(md), _ptr(mdesc), _ptr(mm),
+                                   _ptr(S), _ptr(Kf), ctypes.byref(b), float(th), int(th_low), _ptr(m), _ptr(tab),
+                                   0 if tab is None else len(tab), ctypes.byref(res))
+        self._check(r, "orbx_match_scw")
+        return m[:len(k)].copy(), res
+
+    def compute_sim3_loop_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets: int,
+                                       d_points, d_point_mask, d_point_dist, d_pose, K, bounds: Tuple[int, int, int, int], d_draws,
+                                       d_sim3_res, d_sim3, d_matches, d_msim3_res, d_opt_res, map_set, n_map_sets: int,
+                                       map_capacity: int, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask,
+                                       d_kf2_to_map, d_scw, d_scw_res, loop_th: float = 10.0, th_low: int = 50,
+                                       capacity: Optional[int] = None, **sim3_args) -> None:
+        """LoopClosing::ComputeSim3 for pairs up to its decision: compute_sim3_optimized_pairs_device (its arguments, and its
+        keyword arguments through **sim3_args), then mScw = Scm * Smw (sim3_compose_scw_pairs_device into d_scw), then the Scw
+        SearchByProjection of map set map_set[p] into keyframe kf1[p] on the row the optimiser leaves, translated through
+        d_kf2_to_map -- all queued on the context's stream with no copy and no wait between them.  d_matches ends as
+        mvpCurrentMatchedPoints (indices into the map set), d_scw_res[p].n_total is nTotalMatches; self.loop_accepted(d_opt_res,
+        d_scw_res) reads the two arrays back behind these calls and applies the two gates."""
+        self.compute_sim3_optimized_pairs_device(n_frames, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets,
+                                                 d_points, d_point_mask, d_point_dist, d_pose, K, bounds, d_draws, d_sim3_res, d_sim3,
+                                                 d_matches, d_msim3_res, d_opt_res, capacity=capacity, **sim3_args)
+        self.sim3_compose_scw_pairs_device(n_frames, kf2, d_pose, d_sim3, d_scw)
+        self.match_scw_pairs_device(n_frames, kf1, map_set, d_kps_un, d_desc, d_n, n_map_sets, map_capacity, d_map_n, d_map_points,
+                                    d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_scw, K, bounds, d_matches, d_scw_res, loop_th,
+                                    th_low, d_kf2_to_map, capacity)
+
+    def loop_accepted(self, d_opt_res, d_scw_res, min_inliers: int = 20, min_total: int = 40) -> np.ndarray:
+        """ComputeSim3's decision from the two result arrays compute_sim3_loop_pairs_device filled (torch device tensors, or host
+        record arrays) -> accepted [n_pairs] bool: n_inliers >= 20 and n_total >= 40.  Ordered: a device tensor is read back on
+        torch's current stream of its device, which this call first places behind everything issued on the context so far
+        (order_before), and the copy to the host waits for that stream -- no device-wide synchronisation is needed, or made,
+        between the chain and this call.  Work issued on the context AFTER this call is not waited for."""
+        def host(a):
+            if isinstance(a, np.ndarray):
+                return a
+            import torch
+            self.order_before(torch.cuda.current_stream(a.device).cuda_stream)
+            return a.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy()
+        return loop_accepted(host(d_opt_res), host(d_scw_res), min_inliers, min_total)
+
     # -- mvImagePyramid (hpp:111) ----------------------------------------------------------------
     def level_size(self, level: int) -> Tuple[int, int]:
         w, h = ctypes.c_int(0), ctypes.c_int(0)
@@ -2652,6 +2826,24 @@ class ORBmatcher:
         m, view, res = ext.match_local_map(F.mvKeysUn, F.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
                                            F.bounds, matches, th, self.mfNNratio, outlier)
         return int(res.nmatches), m, view, res
+
+    def SearchByProjectionScw(self, KF: Frame, Scw, map_points, map_normals, map_dist, map_desc, map_mask, matched=None,
+                              th: float = 10.0, K=None, th_low: int = 50, kf2_to_map=None):
+        """ORB-SLAM2's loop-closing overload SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (include/orbx.h, "loop closing:
+        matching the loop's points under Scw") -> (nmatches, matched, MatchScwResult).  Scw: 12 floats (sR row-major, then t) or
+        a 3x4 / 4x4 matrix; the map arrays are SearchLocalPoints'; matched (optional): vpMatched as indices into the map arrays
+        (with kf2_to_map: as the matched keyframe's feature indices); K: 3x3, default KF's camera."""
+        ext = self._ext or KF.mpORBextractor
+        if ext is None:
+            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        if K is None:
+            cam = getattr(KF, "camera", None)
+            if cam is None:
+                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjectionScw needs K (the keyframe carries no camera)")
+            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        m, res = ext.match_scw(KF.mvKeysUn, KF.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K, KF.bounds,
+                               matched, th, th_low, kf2_to_map)
+        return int(res.nmatches), m, res
 
     def SearchByProjectionKeyFrame(self, CurrentFrame: Frame, KF: Frame, points, mask, point_dist, Tcw, th: float = 10.0, ORBdist: int = 100,
                                    K=None, matches=None, outlier=None, point_desc=None):

@@ -183,6 +183,10 @@ struct MatchBowScratch {
   DeviceBuf<uint8_t> dKfProjIo;  // staging of orbx_match_keyframe_projection
   HeldArray<int32_t> sim3Pairs;  // the lists [4][n_pairs] (KF1, KF2, set 1, set 2) of the last orbx_match_sim3* call
   DeviceBuf<uint8_t> dSim3Io;    // staging of orbx_match_sim3
+  HeldArray<int32_t> scwPairs;   // the lists [2][n_pairs] (current keyframe, map set) of the last orbx_match_scw* call
+  DeviceBuf<uint8_t> dScwIo;     // staging of orbx_match_scw
+  HeldArray<int32_t> composeKf2; // the list [n_pairs] (matched keyframe) of the last orbx_sim3_compose_scw* call
+  DeviceBuf<uint8_t> dComposeIo; // staging of orbx_sim3_compose_scw
 };
 
 // What a context keeps for orbx_match_triangulation* and orbx_triangulate_matches* (orbx_match_bow.cpp).

@@ -523,6 +523,34 @@ struct MatchKfProjArgs {
   orbx_kfproj_result* res;    // [nPairs]
 };
 
+// ---- ORBmatcher::SearchByProjection(KeyFrame, Scw, loop map points, vpMatched, th) (orbx_match_scw_kernel.hip): one workgroup
+// of MP_THREADS per (current keyframe, map set) pair; and the composition Scw = S12 * Tmw in front of it, a lane per pair ----
+struct MatchScwArgs {
+  const orbx_keypoint* kps;   // [nFrames][cap] undistorted
+  const uint8_t* desc;        // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;           // [nFrames] (clamped to [0, cap])
+  const int32_t* mapN;        // [nSets] (clamped to [0, mapCap])
+  const float* mapPoints;     // [nSets][mapCap][3]
+  const float* mapNormals;    // [nSets][mapCap][3]
+  const float* mapDist;       // [nSets][mapCap][2] mfMinDistance, mfMaxDistance
+  const uint8_t* mapDesc;     // [nSets][mapCap][32], 16-byte aligned
+  const uint8_t* mapMask;     // nullable [nSets][mapCap]
+  const float* scw;           // [nPairs][12] sR row-major, then t
+  const int32_t* kf2ToMap;    // nullable [nPairs][cap]: the matched keyframe's feature -> an index into the map set, or negative
+  const int32_t* pairs;       // [2][nPairs] current keyframes, map sets
+  int32_t cap, mapCap, nPairs, thLow;
+  MatchCamArgs cam;
+  int32_t* matches;           // [nPairs][cap] in and out
+  orbx_scw_result* res;       // [nPairs]
+};
+struct Sim3ComposeArgs {
+  const float* pose;          // [nFrames][12] Tcw per frame
+  const float* sim3;          // [nPairs][13] R12 row-major, t12, s12
+  const int32_t* kf2;         // [nPairs] the matched keyframes
+  int32_t nPairs;
+  float* scw;                 // [nPairs][12]
+};
+
 // ---- ORBmatcher::SearchBySim3 (orbx_match_sim3_kernel.hip): one workgroup of MP_THREADS per (KF1, KF2) pair ----
 struct MatchSim3Args {
   const orbx_keypoint* kps;   // [nFrames][cap] undistorted

@@ -105,6 +105,10 @@ hipError_t launch_sim3_resolve(hipStream_t st, const Sim3Args& a);
 // orbx_match_sim3_kernel.hip
 hipError_t launch_match_sim3(hipStream_t st, const MatchSim3Args& a);
 
+// orbx_match_scw_kernel.hip
+hipError_t launch_match_scw(hipStream_t st, const MatchScwArgs& a);
+hipError_t launch_sim3_compose_scw(hipStream_t st, const Sim3ComposeArgs& a);
+
 // orbx_sim3opt_kernel.hip
 hipError_t launch_sim3_optimize(hipStream_t st, const Sim3OptArgs& a);
 

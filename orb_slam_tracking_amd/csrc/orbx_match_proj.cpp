@@ -1,11 +1,14 @@
 // orbx_match_proj.cpp — host side of the matchers by projection: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame)
 // (include/orbx.h, "matching by projection"), Tracking::SearchLocalPoints ("matching the local map by projection") and the
 // relocalisation overload ("matching a keyframe's points by projection"): the argument checks, the index lists and the C entry
-// points.  The kernels are in orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip and orbx_match_kfproj_kernel.hip.
+// points; behind them SearchBySim3 and the loop-closing overload under Scw with its composition.  The kernels are in
+// orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip, orbx_match_kfproj_kernel.hip, orbx_match_sim3_kernel.hip and
+// orbx_match_scw_kernel.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <initializer_list>
 #include <vector>
 
@@ -530,6 +533,183 @@ int orbx_match_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* 
   }
   HIPCHK(down(matches12, dM, n1, st));
   HIPCHK(down(res, dR, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+// ---- ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and the composition of Scw (include/orbx.h, "loop closing:
+// matching the loop's points under Scw"; orbx_match_scw_kernel.hip)
+int orbx_match_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                                const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                int n_map_sets, int map_capacity, const int32_t* d_map_n, const float* d_map_points,
+                                const float* d_map_normals, const float* d_map_dist, const uint8_t* d_map_desc32,
+                                const uint8_t* d_map_mask, const float* d_scw, const float* K, const orbx_bounds* bounds, float th,
+                                int th_low, int32_t* d_matches, const int32_t* d_kf2_to_map, orbx_scw_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || n_map_sets < 0 || capacity < 1 || map_capacity < 1 || (n_pairs > 0 && (!h_kf || !h_map_set)) ||
+      !d_kps_un || !d_desc32 || !d_n || !d_map_n || !d_map_points || !d_map_normals || !d_map_dist || !d_map_desc32 || !d_scw || !K ||
+      !bounds || !d_matches || !d_res)
+    return ORBX_E_BADARG;
+  int r = refused(ctx, "match scw", th, th_low < 0 || th_low > 256 ? "th_low outside [0, 256]" : nullptr, bounds,
+                  pairsInRange(h_kf, h_map_set, n_pairs, n_frames, n_map_sets)
+                      ? nullptr
+                      : "keyframe outside [0, n_frames) or map set outside [0, n_map_sets)",
+                  capacity > ORBX_BOW_MAX_FEATURES || map_capacity > ORBX_BOW_MAX_FEATURES
+                      ? "capacity or map_capacity above ORBX_BOW_MAX_FEATURES"
+                      : nullptr);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  r = holdLists(ctx, st, s->scwPairs, {h_kf, h_map_set}, n_pairs);
+  if (r != ORBX_OK) return r;
+  MatchScwArgs a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.mapN = d_map_n;
+  a.mapPoints = d_map_points;
+  a.mapNormals = d_map_normals;
+  a.mapDist = d_map_dist;
+  a.mapDesc = d_map_desc32;
+  a.mapMask = d_map_mask;
+  a.scw = d_scw;
+  a.kf2ToMap = d_kf2_to_map;
+  a.pairs = s->scwPairs;
+  a.cap = capacity;
+  a.mapCap = map_capacity;
+  a.nPairs = n_pairs;
+  a.thLow = th_low;
+  a.cam = camArgs(ctx, K, bounds, th);
+  a.matches = d_matches;
+  a.res = d_res;
+  HIPCHK(launch_match_scw(st, a));
+  return ORBX_OK;
+}
+
+int orbx_match_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+                   const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+                   const float* scw, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches,
+                   const int32_t* kf2_to_map, int n_table, orbx_scw_result* res) {
+  if (n < 0 || map_n < 0 || n_table < 0 || !scw || !K || !bounds || !res || (n > 0 && (!kps_un || !desc32 || !matches)) ||
+      (map_n > 0 && (!map_points || !map_normals || !map_dist || !map_desc32)))
+    return ORBX_E_BADARG;
+  if (!kf2_to_map) n_table = 0;
+  const int cap = std::max(std::max(n, n_table), 1), mapCap = std::max(map_n, 1);
+  if (cap > ORBX_BOW_MAX_FEATURES || mapCap > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "match scw: more than ORBX_BOW_MAX_FEATURES features, points or table entries");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  orbx_keypoint* dK;
+  uint8_t *dD, *dMD, *dMask;
+  float *dP, *dNrm, *dDist, *dScw;
+  int32_t *dN, *dM, *dTab;
+  orbx_scw_result* dR;
+  auto staging = [&](Layout L) {  // one keyframe and one map set in the batch layout, then the results
+    dK = L.take<orbx_keypoint>(cap);
+    dD = L.take<uint8_t>((size_t)cap * 32);
+    dMD = L.take<uint8_t>((size_t)mapCap * 32);
+    dP = L.take<float>((size_t)mapCap * 3);
+    dNrm = L.take<float>((size_t)mapCap * 3);
+    dDist = L.take<float>((size_t)mapCap * 2);
+    dMask = L.take<uint8_t>(mapCap);
+    dScw = L.take<float>(12);
+    dN = L.take<int32_t>(2);
+    dM = L.take<int32_t>(cap);
+    dTab = L.take<int32_t>(cap);
+    dR = L.take<orbx_scw_result>(1);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dScwIo.grow(bytes, st));
+  staging(Layout(s->dScwIo));
+  HIPCHK(hipMemsetAsync(s->dScwIo, 0, bytes, st));
+  // (the table's tail, beyond n_table, names no point of the set: such an entry is never followed)
+  std::vector<int32_t> table(kf2_to_map ? cap : 0, INT32_MAX);
+  if (kf2_to_map) std::copy(kf2_to_map, kf2_to_map + n_table, table.begin());
+  HIPCHK(up(dK, kps_un, n, st));
+  HIPCHK(up(dD, desc32, (size_t)n * 32, st));
+  HIPCHK(up(dM, matches, n, st));
+  HIPCHK(up(dMD, map_desc32, (size_t)map_n * 32, st));
+  HIPCHK(up(dP, map_points, (size_t)map_n * 3, st));
+  HIPCHK(up(dNrm, map_normals, (size_t)map_n * 3, st));
+  HIPCHK(up(dDist, map_dist, (size_t)map_n * 2, st));
+  if (map_mask) HIPCHK(up(dMask, map_mask, map_n, st));
+  if (kf2_to_map) HIPCHK(up(dTab, table.data(), table.size(), st));
+  HIPCHK(up(dScw, scw, 12, st));
+  const int32_t hn[2] = {n, map_n};
+  HIPCHK(up(dN, hn, 2, st));
+  const int32_t frame = 0, set = 0;
+  r = orbx_match_scw_batch_device(ctx, 1, 1, &frame, &set, dK, dD, dN, cap, 1, mapCap, dN + 1, dP, dNrm, dDist, dMD,
+                                  map_mask ? dMask : nullptr, dScw, K, bounds, th, th_low, dM, kf2_to_map ? dTab : nullptr, dR);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
+    return r;
+  }
+  HIPCHK(down(matches, dM, n, st));
+  HIPCHK(down(res, dR, 1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ORBX_OK;
+}
+
+int orbx_sim3_compose_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf2, const float* d_pose,
+                                       const float* d_sim3, float* d_scw) {
+  if (n_frames < 0 || n_pairs < 0 || (n_pairs > 0 && !h_kf2) || !d_pose || !d_sim3 || !d_scw) return ORBX_E_BADARG;
+  if (!pairsInRange(h_kf2, h_kf2, n_pairs, n_frames)) {
+    if (ctx) ctxSetError(ctx, "sim3 compose scw: keyframe outside [0, n_frames)");
+    return ORBX_E_BADARG;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  r = holdLists(ctx, st, s->composeKf2, {h_kf2}, n_pairs);
+  if (r != ORBX_OK) return r;
+  Sim3ComposeArgs a{};
+  a.pose = d_pose;
+  a.sim3 = d_sim3;
+  a.kf2 = s->composeKf2;
+  a.nPairs = n_pairs;
+  a.scw = d_scw;
+  HIPCHK(launch_sim3_compose_scw(st, a));
+  return ORBX_OK;
+}
+
+int orbx_sim3_compose_scw(orbx_ctx* ctx, const float* pose2, const float* sim3, float* scw) {
+  if (!pose2 || !sim3 || !scw) return ORBX_E_BADARG;
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  MatchBowScratch* s = ctxMatchBow(ctx);
+  hipStream_t st = ctxStream(ctx);
+  float *dPose, *dSim, *dScw;
+  auto staging = [&](Layout L) {
+    dPose = L.take<float>(12);
+    dSim = L.take<float>(13);
+    dScw = L.take<float>(12);
+    return L.size();
+  };
+  const size_t bytes = staging(Layout());
+  HIPCHK(s->dComposeIo.grow(bytes, st));
+  staging(Layout(s->dComposeIo));
+  HIPCHK(up(dPose, pose2, 12, st));
+  HIPCHK(up(dSim, sim3, 13, st));
+  const int32_t kf2 = 0;
+  r = orbx_sim3_compose_scw_batch_device(ctx, 1, 1, &kf2, dPose, dSim, dScw);
+  if (r != ORBX_OK) {
+    (void)hipStreamSynchronize(st);  // (the uploads queued above read this call's arguments)
+    return r;
+  }
+  HIPCHK(down(scw, dScw, 12, st));
   HIPCHK(hipStreamSynchronize(st));
   return ORBX_OK;
 }

@@ -1,14 +1,14 @@
-// orbx_match_rounds.h — what the three SearchByProjection kernels share on top of the grid (orbx_match_grid.h): the pose, the
-// camera, bit sets, the window walk and the launcher for all of them (orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip,
-// orbx_match_kfproj_kernel.hip), and for the two kernels that keep a list of points (local, kfproj) the key, the LDS layout, the
-// entry pass, the ordered append, a round's head and the counter flush.  Each kernel keeps its own phases A and B, its decision
-// and its counters: those are what differs, and what a reader compares with the reference's rule.  Device code apart from the
-// launcher; every function with a barrier in it is called by all MP_THREADS threads of a workgroup.
+// orbx_match_rounds.h — what the SearchByProjection kernels share on top of the grid (orbx_match_grid.h): the pose, the camera,
+// bit sets, the window walk and the launcher for all of them (orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip,
+// orbx_match_kfproj_kernel.hip, orbx_match_scw_kernel.hip), and for the kernels that keep a list of points (local, kfproj, scw)
+// the key, the LDS layout, the entry pass, the ordered append, a round's head and the counter flush.  Each kernel keeps its own
+// phases A and B, its decision and its counters: those are what differs, and what a reader compares with the reference's rule.
+// Device code apart from the launcher; every function with a barrier in it is called by all MP_THREADS threads of a workgroup.
 //
-// The sequential rule in claim rounds (k_match_local, k_match_kfproj; k_match_proj's pick-then-claim rounds and their argument
-// are in its own file).  The points of the list are visited by the reference in ascending position p.  Point p's outcome (its
-// match, or none, and why) is a function of U(p), the candidates of its window that nobody has taken when its turn comes.  Each
-// kernel names a claim set C(p), a subset of the untaken candidates of p's window chosen by a test on (p, j) alone, with ONE
+// The sequential rule in claim rounds (k_match_local, k_match_kfproj, k_match_scw; k_match_proj's pick-then-claim rounds and
+// their argument are in its own file).  The points of the list are visited by the reference in ascending position p.  Point
+// p's outcome (its match, or none, and why) is a function of U(p), the candidates of its window that nobody has taken when its
+// turn comes.  Each kernel names a claim set C(p), a subset of the untaken candidates of p's window chosen by a test on (p, j) alone, with ONE
 // property: every untaken candidate that can still become part of p's outcome -- that p's decision reads, now or once others
 // are taken -- is in C(p); a candidate outside it can be struck from U(p) without changing the outcome.  In particular a
 // point's match is always in its claim set.  A round:
@@ -119,7 +119,7 @@ hipError_t mrLaunch(void (*kernel)(A), int nPairs, size_t lds, hipStream_t st, c
   return hipGetLastError();
 }
 
-// ======== for the kernels with a list of points (k_match_local, k_match_kfproj) ========
+// ======== for the kernels with a list of points (k_match_local, k_match_kfproj, k_match_scw) ========
 
 constexpr int MR_FREE = 0x3fffffff;       // claim[j]: nobody claims j
 constexpr int MR_MATCHED = 0x40000000;    // claim[j]: ... | this bit: the claimant is final on j (a new match)
@@ -174,11 +174,36 @@ struct MrLds {
 // The entry pass over the match row of the nF features: a feature that names a point (of nPts) marks it in L.had and keeps it
 // ("taken"), unless it is an outlier: then its entry is cleared (counted in *cleared).  An entry >= nPts: the feature is taken
 // and *status |= badInput.  Ends without a barrier.
+// With `xlate` (k_match_scw; the other callers pass none and are as they were) an entry i >= 0 is an index into xlate [nXlate],
+// which holds the point or a negative value: the point is written back to the row; a negative one writes `unmappedMark` there,
+// keeps the feature taken, marks no point and counts in *unmapped, as does an entry that holds the mark already (a mark of 0
+// is none).  An entry >= nXlate or a translated value >= nPts stays as it is: the feature is taken and *status |= badInput.
 __device__ __forceinline__ void mrEntryPass(const MrLds& L, int* row, int nF, int nPts, const uint8_t* outl, int badInput, int* status,
-                                            int* cleared) {
+                                            int* cleared, const int32_t* xlate = nullptr, int nXlate = 0, int unmappedMark = 0,
+                                            int* unmapped = nullptr) {
   for (int j = threadIdx.x; j < nF; j += MP_THREADS) {
-    const int i = row[j];
+    int i = row[j];
+    if (unmappedMark != 0 && i == unmappedMark) {
+      mrSetBit(L.taken, j);
+      (*unmapped)++;
+      continue;
+    }
     if (i < 0) continue;
+    if (xlate) {
+      if (i >= nXlate) {
+        *status |= badInput;
+        mrSetBit(L.taken, j);
+        continue;
+      }
+      i = xlate[i];
+      if (i < 0) {
+        row[j] = unmappedMark;
+        mrSetBit(L.taken, j);
+        (*unmapped)++;
+        continue;
+      }
+      if (i < nPts) row[j] = i;
+    }
     if (i >= nPts) {
       *status |= badInput;
       mrSetBit(L.taken, j);
