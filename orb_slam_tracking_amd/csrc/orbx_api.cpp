@@ -169,8 +169,9 @@ struct orbx_ctx {
   PinnedBuf<int> hMo;  // mapped [mCap + 8]: n/a[2], nmatches, stats[3], pad[2], matches12[mCap]
   DeviceBuf<int> dMi;  // n[2] + matches12[cap] + nmatches + stats[3]  (device ints of orbx_undistort_keypoints)
   size_t mCap = 0;
+  DeviceBuf<uint8_t> io;          // the one staging block of the single-problem calls of the modules below (Staged, orbx_host.h)
   InitScratch init;               // the Initializer (orbx_init.cpp)
-  DeviceBuf<uint8_t> dColor;      // staging of orbx_to_gray (host API): colour frame followed by its gray image
+  DeviceBuf<uint8_t> dColor;     // staging of orbx_to_gray (host API): colour frame followed by its gray image
   MatchBowScratch matchBow;       // orbx_match_bow* (orbx_match_bow.cpp), the matchers by projection (orbx_match_proj.cpp)
   BaScratch ba;                   // orbx_bundle_adjust* (orbx_ba.cpp)
   PoseScratch pose;               // orbx_pose_optimize* (orbx_pose.cpp)
@@ -1220,11 +1221,11 @@ int settleMatch(orbx_ctx* ctx, int parity) {
 int waitAll(orbx_ctx* ctx);
 int uploadPairs(orbx_ctx* ctx, int nPairs, const int32_t* hFirst, const int32_t* hSecond, bool* copied = nullptr) {
   if (copied) *copied = false;
-  if (ctx->pairs.holds(hFirst, nPairs, hSecond, nPairs)) return ORBX_OK;
+  if (ctx->pairs.holds({hFirst, hSecond}, nPairs)) return ORBX_OK;
   const int r = waitAll(ctx);
   if (r != ORBX_OK) return r;
   if (copied) *copied = true;
-  HIPCHK(ctx->pairs.replace(ctx->st, hFirst, nPairs, hSecond, nPairs));
+  HIPCHK(ctx->pairs.replace(ctx->st, {hFirst, hSecond}, nPairs));
   return ORBX_OK;
 }
 
@@ -2511,6 +2512,7 @@ int ctxDrain(orbx_ctx* c) {
   return waitAll(c);
 }
 void ctxSetError(orbx_ctx* c, const char* msg) { c->err = msg; }
+DeviceBuf<uint8_t>& ctxIo(orbx_ctx* c) { return c->io; }
 InitScratch* ctxInit(orbx_ctx* c) { return &c->init; }
 MatchBowScratch* ctxMatchBow(orbx_ctx* c) { return &c->matchBow; }
 BaScratch* ctxBa(orbx_ctx* c) { return &c->ba; }

@@ -41,14 +41,9 @@ int orbx_bundle_adjust_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, co
   hipStream_t st = ctxStream(ctx);
   int nLevels = 0;
   const float* table = ctxInvSigma2(ctx, &nLevels);
-  // the pair list and the table go up only when they differ from the last call's.  Such a call first waits for the context stream
-  // -- the host copies an earlier upload may still be reading are replaced -- and is the documented exception to "returns once
-  // queued" (include/orbx.h); a pipeline that adjusts the same pairs of every batch uploads once
-  const float* sig = inv_sigma2 ? inv_sigma2 : table;
-  const bool samePairs = s->pairs.holds(h_first, n_pairs, h_second, n_pairs), sameSigma = s->sigma.holds(sig, nLevels);
-  if (!samePairs || !sameSigma) HIPCHK(hipStreamSynchronize(st));
-  if (!samePairs) HIPCHK(s->pairs.replace(st, h_first, n_pairs, h_second, n_pairs));
-  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
+  HeldUploads hold(st);
+  HIPCHK(hold(s->pairs, {h_first, h_second}, n_pairs));
+  HIPCHK(hold(s->sigma, {inv_sigma2 ? inv_sigma2 : table}, nLevels));
   BaArgs a{};
   const size_t points = (size_t)n_pairs * (size_t)capacity;
   auto work = [&](Layout L) {
@@ -96,47 +91,23 @@ int orbx_bundle_adjust(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orb
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  BaScratch* s = ctxBa(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  int32_t *dN, *dM;
-  orbx_init_result* dIR;
-  orbx_ba_result* dR;
-  float* dP;
-  uint8_t* dT;
-  auto staging = [&](Layout L) {  // the two frames (0 and 1) in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dIR = L.take<orbx_init_result>(1);
-    dR = L.take<orbx_ba_result>(1);
-    dP = L.take<float>((size_t)cap * 3);
-    dT = L.take<uint8_t>(cap);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));  // (entries beyond n1: no match, not triangulated)
+  const size_t c = (size_t)cap;
   const int32_t hn[2] = {n1, n2};
-  HIPCHK(up(dK, k1, n1, st));
-  HIPCHK(up(dM, matches12, n1, st));
-  HIPCHK(up(dP, p3d, (size_t)n1 * 3, st));
-  HIPCHK(up(dT, triangulated, n1, st));
-  HIPCHK(up(dK + cap, k2, n2, st));
-  HIPCHK(up(dN, hn, 2, st));
-  HIPCHK(up(dIR, init_res, 1, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two frames (0 and 1) in the batch layout, then the results
+  auto dK = io.in(k1, n1, 2 * c);
+  io.in(dK, c, k2, n2);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.in(matches12, n1, c);
+  auto dIR = io.in(init_res, 1, 1);
+  auto dR = io.out(res, 1, 1);
+  auto dP = io.in(p3d, (size_t)n1 * 3, c * 3);  // (adjusted in place)
+  io.out(dP, 0, p3d_out, (size_t)n1 * 3);
+  auto dT = io.in(triangulated, n1, c);
+  HIPCHK(io.open(Staged::Zeroed));  // (entries beyond n1: no match, not triangulated)
   const int32_t f0 = 0, f1 = 1;
-  r = orbx_bundle_adjust_batch_device(ctx, 2, 1, &f0, &f1, dK, dN, cap, dM, dIR, dP, dT, K, inv_sigma2, n_iterations, min_points,
-                                      normalize, dR, dP);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(down(p3d_out, dP, (size_t)n1 * 3, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_bundle_adjust_batch_device(ctx, 2, 1, &f0, &f1, io[dK], io[dN], cap, io[dM], io[dIR], io[dP], io[dT], K, inv_sigma2,
+                                      n_iterations, min_points, normalize, io[dR], io[dP]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"

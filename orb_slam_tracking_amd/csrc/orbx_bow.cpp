@@ -412,42 +412,33 @@ int orbx_bow_transform(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint8_t*
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
   const int cap = n > 0 ? n : 1;
-  hipStream_t st = ctxStream(ctx);
-  uint8_t* dD;
-  int32_t* dN;
-  uint32_t *dW, *dFn, *dFf, *dFw;
-  double* dV;
-  auto staging = [&](Layout L) {
-    dD = L.take<uint8_t>((size_t)cap * 32);  // descriptors
-    dN = L.take<int32_t>(4);                 // counts: n, bow_n, fv_n
-    dW = L.take<uint32_t>(cap);              // bow words
-    dFn = L.take<uint32_t>(cap);             // fv nodes
-    dFf = L.take<uint32_t>(cap);             // fv features
-    dFw = L.take<uint32_t>(cap);             // feat words
-    dV = L.take<double>(cap);                // bow values
-    return L.size();
-  };
-  HIPCHK(v->dIo.grow(staging(Layout())));
-  staging(Layout(v->dIo));
-  HIPCHK(up(dD, desc32, (size_t)n * 32, st));
-  HIPCHK(up(dN, &n, 1, st));
-  r = transformIssue(ctx, v, 1, dD, dN, cap, levelsup, dW, dV, dN + 1, fv ? dFn : nullptr, fv ? dFf : nullptr, fv ? dN + 2 : nullptr,
-                     feat_word ? dFw : nullptr);
-  if (r != ORBX_OK) return r;
+  const size_t c = (size_t)cap;
+  const int32_t hn = n;
   int32_t counts[3] = {0, 0, 0};
-  HIPCHK(down(counts, dN, 3, st));
-  HIPCHK(hipStreamSynchronize(st));
+  Staged io(v->dIo, ctxStream(ctx));
+  auto dD = io.in(desc32, (size_t)n * 32, c * 32);  // descriptors
+  auto dN = io.in(&hn, 1, 4);                        // counts: n, bow_n, fv_n
+  io.out(dN, 0, counts, 3);
+  auto dW = io.room<uint32_t>(c);                    // bow words
+  auto dFn = io.room<uint32_t>(c);                   // fv nodes
+  auto dFf = io.room<uint32_t>(c);                   // fv features
+  auto dFw = io.optOut(feat_word, n, c);             // feat words
+  auto dV = io.room<double>(c);                      // bow values
+  HIPCHK(io.open());
+  r = transformIssue(ctx, v, 1, io[dD], io[dN], cap, levelsup, io[dW], io[dV], io[dN] + 1, fv ? io[dFn] : nullptr, fv ? io[dFf] : nullptr,
+                     fv ? io[dN] + 2 : nullptr, io[dFw]);
+  r = io.close(ctx, r);
+  if (r != ORBX_OK) return r;
+  // what the counts, now here, say there is of each
   *bow_n = counts[1];
-  HIPCHK(down(bow_word, dW, counts[1], st));
-  HIPCHK(down(bow_value, dV, counts[1], st));
+  io.out(dW, 0, bow_word, counts[1]);
+  io.out(dV, 0, bow_value, counts[1]);
   if (fv) {
     *fv_n = counts[2];
-    HIPCHK(down(fv_node, dFn, counts[2], st));
-    HIPCHK(down(fv_feat, dFf, counts[2], st));
+    io.out(dFn, 0, fv_node, counts[2]);
+    io.out(dFf, 0, fv_feat, counts[2]);
   }
-  if (feat_word) HIPCHK(down(feat_word, dFw, n, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  return io.close(ctx, ORBX_OK);
 }
 
 int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n_frames, int n_pairs, const int32_t* h_first,
@@ -471,12 +462,7 @@ int orbx_bow_score_batch_device(orbx_ctx* ctx, const orbx_vocabulary* voc, int n
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
   hipStream_t st = ctxStream(ctx);
-  // the pair list goes up only when it differs from the last call's.  Such a call first waits for the context stream -- the host
-  // copy an earlier upload may still be reading is replaced -- and is the documented exception to "returns once queued"
-  if (!v->pairs.holds(h_first, n_pairs, h_second, n_pairs)) {
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(v->pairs.replace(st, h_first, n_pairs, h_second, n_pairs));
-  }
+  HIPCHK(HeldUploads(st)(v->pairs, {h_first, h_second}, n_pairs));
   BowScoreArgs s{};
   s.word = d_bow_word;
   s.value = d_bow_value;
@@ -499,31 +485,19 @@ int orbx_bow_score(orbx_ctx* ctx, const orbx_vocabulary* voc, const uint32_t* w1
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
   orbx_vocabulary* v = const_cast<orbx_vocabulary*>(voc);
-  hipStream_t st = ctxStream(ctx);
-  uint32_t* dW;
-  double *dV, *dS;
-  int32_t* dN;
-  auto staging = [&](Layout L) {  // the two frames' words and values, their counts, the score
-    dW = L.take<uint32_t>((size_t)2 * cap);
-    dV = L.take<double>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dS = L.take<double>(1);
-    return L.size();
-  };
-  HIPCHK(v->dIo.grow(staging(Layout())));
-  staging(Layout(v->dIo));
+  const size_t c = (size_t)cap;
   const int32_t hn[2] = {n1, n2};
-  HIPCHK(up(dW, w1, n1, st));
-  HIPCHK(up(dW + cap, w2, n2, st));
-  HIPCHK(up(dV, v1, n1, st));
-  HIPCHK(up(dV + cap, v2, n2, st));
-  HIPCHK(up(dN, hn, 2, st));
+  Staged io(v->dIo, ctxStream(ctx));  // the two frames' words and values, their counts, the score
+  auto dW = io.in(w1, n1, 2 * c);
+  io.in(dW, c, w2, n2);
+  auto dV = io.in(v1, n1, 2 * c);
+  io.in(dV, c, v2, n2);
+  auto dN = io.in(hn, 2, 2);
+  auto dS = io.out(score, 1, 1);
+  HIPCHK(io.open());
   const int32_t f0 = 0, f1 = 1;
-  r = orbx_bow_score_batch_device(ctx, voc, 2, 1, &f0, &f1, dW, dV, dN, cap, dS);
-  if (r != ORBX_OK) return r;
-  HIPCHK(down(score, dS, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_bow_score_batch_device(ctx, voc, 2, 1, &f0, &f1, io[dW], io[dV], io[dN], cap, io[dS]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"

@@ -1,13 +1,15 @@
-// orbx_buf.h — owners of the library's device and page-locked host memory, and the one description of a staging block.
-// Every host .cpp of the library except orbx_multi.cpp (orbx_api, orbx_init, orbx_bow, orbx_db, orbx_voc_train, orbx_match_bow,
-// orbx_ba, orbx_pose) allocates and frees through these types only.  The scratch structs at the end are what a context keeps for
-// the modules that live in their own .cpp; orbx_host.h declares the accessors.
+// orbx_buf.h — owners of the library's device and page-locked host memory, and the one description of a block's layout.
+// Every host .cpp of the library except orbx_multi.cpp allocates and frees through these types only.  The scratch structs at the
+// end are what a context keeps across calls for the modules that live in their own .cpp: held arrays and work areas.  The
+// staging of the single-problem calls is no part of them: a context has one block for all of it (ctxIo() in orbx_host.h, which
+// declares the accessors and Staged, the helper that lays a call's staging out).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -112,8 +114,8 @@ class PinnedBuf {
   size_t bytes_ = 0;
 };
 
-// A staging block's arrays in order, each starting 256-byte aligned.  A block is described once, as code that takes its arrays
-// from a Layout: run over a Layout without a base it only counts (size()), run over the block's base it hands out the pointers.
+// A block's arrays in order, each starting 256-byte aligned.  A block is described once, as code that takes its arrays from a
+// Layout: run over a Layout without a base it only counts (size()), run over the block's base it hands out the pointers.
 class Layout {
  public:
   Layout() = default;
@@ -134,24 +136,29 @@ class Layout {
 // A device array and the host copy its last upload read.  The copy command reads the host copy when it runs, which may be after
 // the call that queued it has returned, so the copy stays put until the next replace(); and an array that holds() the values a
 // call brings is not uploaded again.  Between "holds() says no" and replace() the caller drains whatever may still read either
-// copy.  Reads as a T* (the device array) wherever one is expected.
+// copy (HeldUploads in orbx_host.h is that step).  A call brings its values as columns of n entries each, held one after the
+// other: a pair list is its two columns, a table is one.  Reads as a T* (the device array) wherever one is expected.
 template <class T>
 class HeldArray {
  public:
+  using Columns = std::initializer_list<const T*>;
   operator T*() const { return dev_; }
-  // exactly a[0, na) followed by b[0, nb)?  (A pair list is its two columns, one after the other.)
-  bool holds(const T* a, size_t na, const T* b = nullptr, size_t nb = 0) const {
-    return host_.size() == na + nb && (na == 0 || std::memcmp(host_.data(), a, na * sizeof(T)) == 0) &&
-           (nb == 0 || std::memcmp(host_.data() + na, b, nb * sizeof(T)) == 0);
+  bool holds(Columns columns, size_t n) const {
+    if (host_.size() != columns.size() * n) return false;
+    const T* held = host_.data();
+    for (const T* c : columns) {
+      if (n && std::memcmp(held, c, n * sizeof(T)) != 0) return false;
+      held += n;
+    }
+    return true;
   }
   // From the first step to the queued copy the array holds nothing, and again after a copy command that failed: no later call
   // skips an upload the device never received.
-  hipError_t replace(hipStream_t st, const T* a, size_t na, const T* b = nullptr, size_t nb = 0) {
+  hipError_t replace(hipStream_t st, Columns columns, size_t n) {
     host_.clear();
-    hipError_t e = dev_.grow((na + nb) * sizeof(T));
+    hipError_t e = dev_.grow(columns.size() * n * sizeof(T));
     if (e != hipSuccess) return e;
-    host_.assign(a, a + na);
-    host_.insert(host_.end(), b, b + nb);
+    for (const T* c : columns) host_.insert(host_.end(), c, c + n);
     e = hipMemcpyAsync(dev_, host_.data(), host_.size() * sizeof(T), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) host_.clear();
     return e;
@@ -165,34 +172,25 @@ class HeldArray {
 
 // What a context keeps for the Initializer (orbx_init.cpp).
 struct InitScratch {
-  DeviceBuf<uint8_t> dScore;  // staging of orbx_check_homography / _fundamental / orbx_check_rt
-  DeviceBuf<uint8_t> dInit;   // arena of orbx_find_models* / orbx_initialize*
-  HeldArray<int32_t> pairs;   // their pair list [2][n_pairs]
+  DeviceBuf<uint8_t> dInit;  // arena of orbx_find_models* / orbx_initialize*: the work area, a single pair's staging behind it
+  HeldArray<int32_t> pairs;  // their pair list [2][n_pairs]
 };
 
-// What a context keeps for orbx_match_bow*, orbx_match_projection*, orbx_match_local_map* and orbx_match_keyframe_projection*
-// (orbx_match_bow.cpp, orbx_match_proj.cpp).
+// What a context keeps for orbx_match_bow* (orbx_match_bow.cpp) and the matchers by projection (orbx_match_proj.cpp): the index
+// lists of the last call of each.
 struct MatchBowScratch {
-  HeldArray<int32_t> pairs;      // the pair list [2][n_pairs] of the last orbx_match_bow* call
-  DeviceBuf<uint8_t> dIo;        // staging of orbx_match_bow
-  HeldArray<int32_t> projPairs;  // the lists [3][n_pairs] (last, current, point set) of the last orbx_match_projection* call
-  DeviceBuf<uint8_t> dProjIo;    // staging of orbx_match_projection
-  HeldArray<int32_t> localPairs; // the lists [2][n_pairs] (frame, map set) of the last orbx_match_local_map* call
-  DeviceBuf<uint8_t> dLocalIo;   // staging of orbx_match_local_map
-  HeldArray<int32_t> kfProjPairs;  // the lists [3][n_pairs] (keyframe, current, point set) of the last orbx_match_keyframe_projection* call
-  DeviceBuf<uint8_t> dKfProjIo;  // staging of orbx_match_keyframe_projection
-  HeldArray<int32_t> sim3Pairs;  // the lists [4][n_pairs] (KF1, KF2, set 1, set 2) of the last orbx_match_sim3* call
-  DeviceBuf<uint8_t> dSim3Io;    // staging of orbx_match_sim3
-  HeldArray<int32_t> scwPairs;   // the lists [2][n_pairs] (current keyframe, map set) of the last orbx_match_scw* call
-  DeviceBuf<uint8_t> dScwIo;     // staging of orbx_match_scw
-  HeldArray<int32_t> composeKf2; // the list [n_pairs] (matched keyframe) of the last orbx_sim3_compose_scw* call
-  DeviceBuf<uint8_t> dComposeIo; // staging of orbx_sim3_compose_scw
+  HeldArray<int32_t> pairs;        // [2][n_pairs] of orbx_match_bow*
+  HeldArray<int32_t> projPairs;    // [3][n_pairs] (last, current, point set) of orbx_match_projection*
+  HeldArray<int32_t> localPairs;   // [2][n_pairs] (frame, map set) of orbx_match_local_map*
+  HeldArray<int32_t> kfProjPairs;  // [3][n_pairs] (keyframe, current, point set) of orbx_match_keyframe_projection*
+  HeldArray<int32_t> sim3Pairs;    // [4][n_pairs] (KF1, KF2, set 1, set 2) of orbx_match_sim3*
+  HeldArray<int32_t> scwPairs;     // [2][n_pairs] (current keyframe, map set) of orbx_match_scw*
+  HeldArray<int32_t> composeKf2;   // [n_pairs] (matched keyframe) of orbx_sim3_compose_scw*
 };
 
 // What a context keeps for orbx_match_triangulation* and orbx_triangulate_matches* (orbx_match_bow.cpp).
 struct TriScratch {
   HeldArray<int32_t> pairs;  // the pair list [2][n_pairs] (KF1s, KF2s) of the last call of either: the chain uploads it once
-  DeviceBuf<uint8_t> dIo;    // staging of orbx_match_triangulation / orbx_triangulate_matches
 };
 
 // What a context keeps for orbx_bundle_adjust* (orbx_ba.cpp).
@@ -200,14 +198,12 @@ struct BaScratch {
   DeviceBuf<uint8_t> dWork;  // the per-point blocks of every pair: sized from n_pairs x capacity
   HeldArray<int32_t> pairs;  // the pair list [2][n_pairs] of the last call
   HeldArray<float> sigma;    // inv_sigma2 of the last call
-  DeviceBuf<uint8_t> dIo;    // staging of orbx_bundle_adjust
 };
 
 // What a context keeps for orbx_pose_optimize* (orbx_pose.cpp).
 struct PoseScratch {
   HeldArray<int32_t> problems;  // the problem list [2][n_problems] of the last call
   HeldArray<float> sigma;       // inv_sigma2 of the last call
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_pose_optimize
 };
 
 // What a context keeps for orbx_pnp_solve* (orbx_pose.cpp).
@@ -220,7 +216,6 @@ struct PnpScratch {
   float keyEpsilon = 0;
   int keyMinInliers = 0, keyMaxIterations = 0;
   DeviceBuf<uint8_t> dWork;     // the correspondences, the hypotheses and the per-problem values of a call
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_pnp_solve
 };
 
 // What a context keeps for orbx_sim3_solve* (orbx_pose.cpp).
@@ -232,14 +227,12 @@ struct Sim3Scratch {
   double keyProbability = 0;
   int keyMinInliers = 0, keyMaxIterations = 0;
   DeviceBuf<uint8_t> dWork;     // the correspondences, the hypotheses and the per-problem values of a call
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_sim3_solve
 };
 
 // What a context keeps for orbx_optimize_sim3* (orbx_pose.cpp).
 struct Sim3OptScratch {
   HeldArray<int32_t> problems;  // the lists [4][n_problems] (KF1, KF2, set 1, set 2) of the last call
   HeldArray<float> sigma;       // inv_sigma2 of the last call
-  DeviceBuf<uint8_t> dIo;       // staging of orbx_optimize_sim3
 };
 
 }  // namespace orbx

@@ -307,27 +307,15 @@ int orbx_database_add(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, co
   if (r != ORBX_OK) return r;
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  hipStream_t st = ctxStream(ctx);
   const int cap = std::max(n, 1);
-  uint32_t* dW;
-  double* dV;
-  int32_t* dN;
-  auto staging = [&](Layout L) {  // the vector's words and values, its count
-    dW = L.take<uint32_t>(cap);
-    dV = L.take<double>(cap);
-    dN = L.take<int32_t>(1);
-    return L.size();
-  };
-  HIPCHK(db->dIo.grow(staging(Layout()), st));
-  staging(Layout(db->dIo));
   const int32_t hn = n;
-  HIPCHK(up(dW, word, n, st));
-  HIPCHK(up(dV, value, n, st));
-  HIPCHK(up(dN, &hn, 1, st));
-  r = orbx_database_add_batch_device(ctx, db, 1, dW, dV, dN, cap, entry_id);
-  if (r != ORBX_OK) return r;
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(db->dIo, ctxStream(ctx));  // the vector's words and values, its count
+  auto dW = io.in(word, n, cap);
+  auto dV = io.in(value, n, cap);
+  auto dN = io.in(&hn, 1, 1);
+  HIPCHK(io.open());
+  r = orbx_database_add_batch_device(ctx, db, 1, io[dW], io[dV], io[dN], cap, entry_id);
+  return io.close(ctx, r);
 }
 
 int orbx_database_query(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, const double* value, int n, int max_results,
@@ -342,37 +330,25 @@ int orbx_database_query(orbx_ctx* ctx, orbx_database* db, const uint32_t* word, 
   }
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  hipStream_t st = ctxStream(ctx);
   const int cap = std::max(n, 1);
-  uint32_t* dW;
-  double *dV, *dS;
-  int32_t *dN, *dE;
-  auto staging = [&](Layout L) {  // the vector's words and values, its count and the result count, the results
-    dW = L.take<uint32_t>(cap);
-    dV = L.take<double>(cap);
-    dN = L.take<int32_t>(2);
-    dE = L.take<int32_t>(max_results);
-    dS = L.take<double>(max_results);
-    return L.size();
-  };
-  HIPCHK(db->dIo.grow(staging(Layout()), st));
-  staging(Layout(db->dIo));
   const int32_t hn = n;
-  HIPCHK(up(dW, word, n, st));
-  HIPCHK(up(dV, value, n, st));
-  HIPCHK(up(dN, &hn, 1, st));
-  r = orbx_database_query_batch_device(ctx, db, 1, dW, dV, dN, cap, max_results, max_id, dE, dS, dN + 1);
-  if (r != ORBX_OK) return r;
   int32_t got = 0;
-  HIPCHK(down(&got, dN + 1, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
+  Staged io(db->dIo, ctxStream(ctx));  // the vector's words and values, its count and the result count, the results
+  auto dW = io.in(word, n, cap);
+  auto dV = io.in(value, n, cap);
+  auto dN = io.in(&hn, 1, 2);
+  io.out(dN, 1, &got, 1);
+  auto dE = io.room<int32_t>(max_results);
+  auto dS = io.room<double>(max_results);
+  HIPCHK(io.open());
+  r = orbx_database_query_batch_device(ctx, db, 1, io[dW], io[dV], io[dN], cap, max_results, max_id, io[dE], io[dS], io[dN] + 1);
+  r = io.close(ctx, r);
+  if (r != ORBX_OK) return r;
   *res_n = got;
-  if (got) {
-    HIPCHK(down(res_entry, dE, got, st));
-    HIPCHK(down(res_score, dS, got, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return ORBX_OK;
+  if (!got) return ORBX_OK;
+  io.out(dE, 0, res_entry, got);
+  io.out(dS, 0, res_score, got);
+  return io.close(ctx, ORBX_OK);
 }
 
 int64_t orbx_database_get_inverted_file(orbx_database* db, uint32_t* row_start, uint32_t* post_entry, double* post_value,

@@ -42,38 +42,27 @@ int checkModels(orbx_ctx* ctx, int kind, int n_models, const float* M21, const f
   if (hipSetDevice(ctxDevice(ctx)) != hipSuccess) return ORBX_E_HIP;
   // the batched form with one pair (frames {0, 0} of k1 / k2: the staged keypoint arrays) and the call's models as its
   // hypotheses; one staging block: models | keypoints | matches | pair table | scores | inliers
-  ScoreArgs a{};
-  int32_t* table;
-  auto staging = [&](Layout L) {
-    a.M21 = L.take<float>((size_t)n_models * 9);
-    a.M12 = L.take<float>((size_t)n_models * 9);
-    a.k1 = L.take<orbx_keypoint>(n1);
-    a.k2 = L.take<orbx_keypoint>(n2);
-    a.first = L.take<int32_t>(N);
-    a.second = L.take<int32_t>(N);
-    table = L.take<int32_t>(3);  // pairN[1], frames[2]
-    a.scores = L.take<float>(n_models);
-    a.inliers = L.take<uint8_t>((size_t)n_models * N);
-    return L.size();
-  };
-  InitScratch* s = ctxInit(ctx);
-  hipStream_t st = ctxStream(ctx);
-  HIPCHK(s->dScore.grow(staging(Layout())));
-  staging(Layout(s->dScore));
   const int32_t hTable[3] = {N, 0, 0};
-  a.pairN = table; a.frames = table + 1; a.perPair = n_models; a.stride = N; a.nPairs = 1; a.kind = kind;
+  const size_t models = (size_t)n_models * 9;
+  hipStream_t st = ctxStream(ctx);
+  Staged io(ctxIo(ctx), st);
+  auto dM21 = io.in(M21, models, models);
+  auto dM12 = io.in(kind == 0 ? M12 : nullptr, models, models);
+  auto dK1 = io.in(k1, n1, n1);
+  auto dK2 = io.in(k2, n2, n2);
+  auto dFirst = io.in(fs.data(), N, N);
+  auto dSecond = io.in(sc.data(), N, N);
+  auto dTable = io.in(hTable, 3, 3);  // pairN[1], frames[2]
+  auto dScores = io.out(scores, n_models, n_models);
+  auto dInliers = io.out(inliers, (size_t)n_models * N, (size_t)n_models * N);
+  HIPCHK(io.open());
+  ScoreArgs a{};
+  a.M21 = io[dM21]; a.M12 = io[dM12]; a.k1 = io[dK1]; a.k2 = io[dK2]; a.first = io[dFirst]; a.second = io[dSecond];
+  a.scores = io[dScores]; a.inliers = io[dInliers];
+  a.pairN = io[dTable]; a.frames = io[dTable] + 1; a.perPair = n_models; a.stride = N; a.nPairs = 1; a.kind = kind;
   a.invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // `const float invSigmaSquare = 1.0 / (sigma * sigma)`
-  HIPCHK(up(a.M21, M21, (size_t)n_models * 9, st));
-  if (kind == 0) HIPCHK(up(a.M12, M12, (size_t)n_models * 9, st));
-  HIPCHK(up(a.k1, k1, n1, st));
-  HIPCHK(up(a.k2, k2, n2, st));
-  HIPCHK(up(a.first, fs.data(), N, st));
-  HIPCHK(up(a.second, sc.data(), N, st));
-  HIPCHK(up(table, hTable, 3, st));
-  HIPCHK(launch_check_model(st, n_models, a));
-  HIPCHK(down(scores, a.scores, n_models, st));
-  HIPCHK(down(inliers, a.inliers, (size_t)n_models * N, st));
-  HIPCHK(hipStreamSynchronize(st));
+  const int r = io.close(ctx, HIPRC(launch_check_model(st, n_models, a)));
+  if (r != ORBX_OK) return r;
   if (best) {  // `if (currentScore > score)` with score starting at 0, Initializer.cpp:205-209 / 259-263
     float sc = 0;
     for (int m = 0; m < n_models; m++)
@@ -120,41 +109,28 @@ int orbx_check_rt(orbx_ctx* ctx, int n_models, const float* R21, const float* t2
   const int nInl = (int)book.size();
   if (hipSetDevice(ctxDevice(ctx)) != hipSuccess) return ORBX_E_HIP;
   // the batched form with one pair whose n_models candidates are all solutions (stride n1 >= nInl)
-  CheckRtArgs a{};
-  int32_t* table;
-  auto staging = [&](Layout L) {
-    a.R21 = L.take<float>((size_t)n_models * 9);
-    a.t21 = L.take<float>((size_t)n_models * 3);
-    a.pts = L.take<float>((size_t)nInl * 4);
-    a.book = L.take<int32_t>(nInl);
-    table = L.take<int32_t>(2);  // pairNInl[1], pairNSol[1]
-    a.good = L.take<uint8_t>((size_t)n_models * n1);
-    a.p3d = L.take<float>((size_t)n_models * n1 * 3);
-    a.cosBuf = L.take<float>((size_t)n_models * n1);
-    a.nGood = L.take<int32_t>(n_models);
-    a.parallax = L.take<float>(n_models);
-    return L.size();
-  };
-  InitScratch* s = ctxInit(ctx);
-  hipStream_t st = ctxStream(ctx);
-  HIPCHK(s->dScore.grow(staging(Layout())));
-  staging(Layout(s->dScore));
   const int32_t hTable[2] = {nInl, n_models};
+  const size_t M = (size_t)n_models, all = M * n1;
+  hipStream_t st = ctxStream(ctx);
+  Staged io(ctxIo(ctx), st);
+  auto dR21 = io.in(R21, M * 9, M * 9);
+  auto dT21 = io.in(t21, M * 3, M * 3);
+  auto dPts = io.in(pts.data(), (size_t)nInl * 4, (size_t)nInl * 4);
+  auto dBook = io.in(book.data(), nInl, nInl);
+  auto dTable = io.in(hTable, 2, 2);  // pairNInl[1], pairNSol[1]
+  auto dGood = io.out(tri_good, all, all);
+  auto dP3d = io.out(p3d, all * 3, all * 3);
+  auto dCos = io.room<float>(all);
+  auto dNGood = io.out(n_good, M, M);
+  auto dParallax = io.out(parallax, M, M);
+  HIPCHK(io.open());
+  CheckRtArgs a{};
+  a.R21 = io[dR21]; a.t21 = io[dT21]; a.pts = io[dPts]; a.book = io[dBook]; a.good = io[dGood]; a.p3d = io[dP3d];
+  a.cosBuf = io[dCos]; a.nGood = io[dNGood]; a.parallax = io[dParallax];
   for (int i = 0; i < 9; i++) a.K[i] = K[i];
   a.th2 = th2;
-  a.pairNInl = table; a.pairNSol = table + 1; a.perPair = n_models; a.stride = n1;
-  HIPCHK(up(a.R21, R21, (size_t)n_models * 9, st));
-  HIPCHK(up(a.t21, t21, (size_t)n_models * 3, st));
-  HIPCHK(up(a.pts, pts.data(), (size_t)nInl * 4, st));
-  HIPCHK(up(a.book, book.data(), nInl, st));
-  HIPCHK(up(table, hTable, 2, st));
-  HIPCHK(launch_check_rt(st, n_models, a));
-  HIPCHK(down(n_good, a.nGood, n_models, st));
-  HIPCHK(down(parallax, a.parallax, n_models, st));
-  HIPCHK(down(tri_good, a.good, (size_t)n_models * n1, st));
-  HIPCHK(down(p3d, a.p3d, (size_t)n_models * n1 * 3, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  a.pairNInl = io[dTable]; a.pairNSol = io[dTable] + 1; a.perPair = n_models; a.stride = n1;
+  return io.close(ctx, HIPRC(launch_check_rt(st, n_models, a)));
 }
 
 // ---- the RANSAC stage of Initializer::Initialize (Initialization/Initializer.cpp:19-111) ----------------------------------
@@ -215,10 +191,7 @@ int findModels(orbx_ctx* ctx, uint8_t* work, int n_pairs, const int32_t* h_first
   hipStream_t st = ctxStream(ctx);
   const size_t H = (size_t)n_pairs * n_iter;
   HeldArray<int32_t>& pairs = ctxInit(ctx)->pairs;
-  if (!pairs.holds(h_first, n_pairs, h_second, n_pairs)) {  // (the copy an earlier upload may still be reading is replaced)
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(pairs.replace(st, h_first, n_pairs, h_second, n_pairs));
-  }
+  HIPCHK(HeldUploads(st)(pairs, {h_first, h_second}, n_pairs));
   InitArgs a{};
   ScoreArgs sH{}, sF{};
   CheckRtArgs c{};
@@ -316,59 +289,34 @@ int singlePair(orbx_ctx* ctx, const orbx_keypoint* k1, int n1, const orbx_keypoi
   if (r != ORBX_OK) return r;
   const int cap = std::max(std::max(n1, n2), 1);
   const size_t work = initWorkSize(1, n_iter, cap, ires != nullptr);
-  orbx_keypoint* dK;  // [2][cap]
-  int32_t *dN, *dM, *dS;
-  orbx_hf_result* dR;
-  orbx_init_result* dIR;
-  uint8_t *dI, *dT;
-  float *dMo, *dSo, *dP;
-  auto staging = [&](Layout L) {  // behind the work area
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dS = L.take<int32_t>((size_t)n_iter * 8);
-    dR = L.take<orbx_hf_result>(1);
-    dIR = L.take<orbx_init_result>(1);
-    dI = L.take<uint8_t>((size_t)2 * cap);
-    dMo = L.take<float>((size_t)3 * n_iter * 9);
-    dSo = L.take<float>((size_t)2 * n_iter);
-    dP = L.take<float>((size_t)cap * 3);
-    dT = L.take<uint8_t>(cap);
-    return L.size();
-  };
-  DeviceBuf<uint8_t>& dInit = ctxInit(ctx)->dInit;
-  hipStream_t st = ctxStream(ctx);
-  HIPCHK(dInit.grow(work + staging(Layout()), st));
-  staging(Layout(dInit + work));
+  const size_t c = (size_t)cap, it = (size_t)n_iter;
   const int32_t hn[2] = {n1, n2};
-  HIPCHK(up(dK, k1, n1, st));
-  HIPCHK(up(dK + cap, k2, n2, st));
-  HIPCHK(up(dN, hn, 2, st));
-  HIPCHK(up(dM, matches12, n1, st));
-  HIPCHK(up(dS, sets, (size_t)n_iter * 8, st));
+  DeviceBuf<uint8_t>& dInit = ctxInit(ctx)->dInit;
+  // behind the work area; of the results, the caller asks for the H/F stage's (hres ...) or the reconstruction's (ires ...): the
+  // others are null here and stay on the device
+  Staged io(dInit, ctxStream(ctx), work);
+  auto dK = io.in(k1, n1, 2 * c);
+  io.in(dK, c, k2, n2);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.in(matches12, n1, c);
+  auto dS = io.in(sets, it * 8, it * 8);
+  auto dR = io.out(hres, 1, 1);
+  auto dIR = io.out(ires, 1, 1);
+  auto dI = io.out(inliers, n1, 2 * c);  // [2][n1] from [2][cap]
+  io.out(dI, c, inliers ? inliers + n1 : nullptr, n1);
+  auto dMo = io.out(models, 3 * it * 9, 3 * it * 9);
+  auto dSo = io.out(scores, 2 * it, 2 * it);
+  auto dP = io.out(p3d, (size_t)n1 * 3, c * 3);
+  auto dT = io.out(tri, n1, c);
+  HIPCHK(io.open());
   const int32_t f0 = 0, f1 = 1;
   if (ires) {
-    const ReconParams rc{K, min_parallax, min_triangulated, dIR, dP, dT};
-    r = findModels(ctx, dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, nullptr, nullptr, nullptr, nullptr, &rc);
+    const ReconParams rc{K, min_parallax, min_triangulated, io[dIR], io[dP], io[dT]};
+    r = findModels(ctx, dInit, 1, &f0, &f1, io[dK], io[dN], cap, io[dM], n_iter, io[dS], sigma, nullptr, nullptr, nullptr, nullptr, &rc);
   } else {
-    r = findModels(ctx, dInit, 1, &f0, &f1, dK, dN, cap, dM, n_iter, dS, sigma, dR, dI, dMo, dSo, nullptr);
+    r = findModels(ctx, dInit, 1, &f0, &f1, io[dK], io[dN], cap, io[dM], n_iter, io[dS], sigma, io[dR], io[dI], io[dMo], io[dSo], nullptr);
   }
-  if (r != ORBX_OK) return r;
-  if (ires) {
-    HIPCHK(down(ires, dIR, 1, st));
-    if (p3d) HIPCHK(down(p3d, dP, (size_t)n1 * 3, st));
-    if (tri) HIPCHK(down(tri, dT, n1, st));
-  } else {
-    HIPCHK(down(hres, dR, 1, st));
-    if (inliers) {  // [2][n1] from [2][cap]
-      HIPCHK(down(inliers, dI, n1, st));
-      HIPCHK(down(inliers + n1, dI + cap, n1, st));
-    }
-    if (models) HIPCHK(down(models, dMo, (size_t)3 * n_iter * 9, st));
-    if (scores) HIPCHK(down(scores, dSo, (size_t)2 * n_iter, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  return io.close(ctx, r);
 }
 }  // namespace
 

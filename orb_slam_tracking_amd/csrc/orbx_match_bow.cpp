@@ -57,16 +57,6 @@ TriCamArgs triCam(const orbx_ctx* ctx, const float* K) {
   return c;
 }
 
-// the pair list [2][n_pairs] of the two calls, which take the same one: uploaded only when it differs from the last call's.  Such a
-// call first waits for the context stream -- the host copy an earlier upload may still be reading is replaced
-int triPairs(orbx_ctx* ctx, hipStream_t st, TriScratch* s, const int32_t* h_kf1, const int32_t* h_kf2, int n_pairs) {
-  if (!s->pairs.holds(h_kf1, n_pairs, h_kf2, n_pairs)) {
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(s->pairs.replace(st, h_kf1, n_pairs, h_kf2, n_pairs));
-  }
-  return ORBX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -92,12 +82,7 @@ int orbx_match_bow_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   if (r != ORBX_OK) return r;
   MatchBowScratch* s = ctxMatchBow(ctx);
   hipStream_t st = ctxStream(ctx);
-  // the pair list goes up only when it differs from the last call's.  Such a call first waits for the context stream -- the host
-  // copy an earlier upload may still be reading is replaced -- and is the documented exception to "returns once queued"
-  if (!s->pairs.holds(h_kf, n_pairs, h_f, n_pairs)) {
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(s->pairs.replace(st, h_kf, n_pairs, h_f, n_pairs));
-  }
+  HIPCHK(HeldUploads(st)(s->pairs, {h_kf, h_f}, n_pairs));
   MatchBowArgs a{};
   a.kps = d_kps;
   a.desc = d_desc32;
@@ -137,44 +122,26 @@ int orbx_match_bow(orbx_ctx* ctx, const orbx_keypoint* kf_kps, const uint8_t* kf
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dMask;
-  uint32_t *dNode, *dFeat;
-  int32_t *dN, *dM;
-  auto staging = [&](Layout L) {  // the two frames (keyframe 0, frame 1) in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dNode = L.take<uint32_t>((size_t)2 * cap);
-    dFeat = L.take<uint32_t>((size_t)2 * cap);
-    dMask = L.take<uint8_t>((size_t)2 * cap);
-    dN = L.take<int32_t>(5);  // n[2], fv_n[2], nmatches
-    dM = L.take<int32_t>(cap);
-    return L.size();
-  };
-  HIPCHK(s->dIo.grow(staging(Layout()), st));
-  staging(Layout(s->dIo));
   const size_t c = (size_t)cap;
-  HIPCHK(up(dK, kf_kps, kf_n, st));
-  HIPCHK(up(dD, kf_desc32, (size_t)kf_n * 32, st));
-  if (kf_mask) HIPCHK(up(dMask, kf_mask, kf_n, st));
-  HIPCHK(up(dK + c, f_kps, f_n, st));
-  HIPCHK(up(dD + c * 32, f_desc32, (size_t)f_n * 32, st));
-  HIPCHK(up(dNode, kf_fv_node, kf_fv_n, st));
-  HIPCHK(up(dFeat, kf_fv_feat, kf_fv_n, st));
-  HIPCHK(up(dNode + c, f_fv_node, f_fv_n, st));
-  HIPCHK(up(dFeat + c, f_fv_feat, f_fv_n, st));
   const int32_t hn[4] = {kf_n, f_n, kf_fv_n, f_fv_n};
-  HIPCHK(up(dN, hn, 4, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two frames (keyframe 0, frame 1) in the batch layout, then the results
+  auto dK = io.in(kf_kps, kf_n, 2 * c);
+  io.in(dK, c, f_kps, f_n);
+  auto dD = io.in(kf_desc32, (size_t)kf_n * 32, 2 * c * 32);
+  io.in(dD, c * 32, f_desc32, (size_t)f_n * 32);
+  auto dNode = io.in(kf_fv_node, kf_fv_n, 2 * c);
+  io.in(dNode, c, f_fv_node, f_fv_n);
+  auto dFeat = io.in(kf_fv_feat, kf_fv_n, 2 * c);
+  io.in(dFeat, c, f_fv_feat, f_fv_n);
+  auto dMask = io.optIn(kf_mask, kf_n, 2 * c);
+  auto dN = io.in(hn, 4, 5);  // n[2], fv_n[2], nmatches
+  io.out(dN, 4, nmatches, 1);
+  auto dM = io.out(matches_f, f_n, c);
+  HIPCHK(io.open());
   const int32_t kf = 0, f = 1;
-  r = orbx_match_bow_batch_device(ctx, 2, 1, &kf, &f, dK, dD, dN, cap, dNode, dFeat, dN + 2, kf_mask ? dMask : nullptr, nnratio,
-                                  check_orientation, dM, dN + 4);
-  if (r != ORBX_OK) return r;
-  HIPCHK(down(matches_f, dM, f_n, st));
-  HIPCHK(down(nmatches, dN + 4, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_match_bow_batch_device(ctx, 2, 1, &kf, &f, io[dK], io[dD], io[dN], cap, io[dNode], io[dFeat], io[dN] + 2, io[dMask], nnratio,
+                                  check_orientation, io[dM], io[dN] + 4);
+  return io.close(ctx, r);
 }
 
 int orbx_match_triangulation_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf1, const int32_t* h_kf2,
@@ -193,8 +160,7 @@ int orbx_match_triangulation_batch_device(orbx_ctx* ctx, int n_frames, int n_pai
   if (r != ORBX_OK) return r;
   TriScratch* s = ctxTri(ctx);
   hipStream_t st = ctxStream(ctx);
-  r = triPairs(ctx, st, s, h_kf1, h_kf2, n_pairs);
-  if (r != ORBX_OK) return r;
+  HIPCHK(HeldUploads(st)(s->pairs, {h_kf1, h_kf2}, n_pairs));  // (the two calls take the same list: the chain uploads it once)
   MatchTriArgs a{};
   a.kps = d_kps_un;
   a.desc = d_desc32;
@@ -231,8 +197,7 @@ int orbx_triangulate_matches_batch_device(orbx_ctx* ctx, int n_frames, int n_pai
   if (r != ORBX_OK) return r;
   TriScratch* s = ctxTri(ctx);
   hipStream_t st = ctxStream(ctx);
-  r = triPairs(ctx, st, s, h_kf1, h_kf2, n_pairs);
-  if (r != ORBX_OK) return r;
+  HIPCHK(HeldUploads(st)(s->pairs, {h_kf1, h_kf2}, n_pairs));  // (the two calls take the same list: the chain uploads it once)
   TriangulateArgs a{};
   a.kps = d_kps_un;
   a.n = d_n;
@@ -270,59 +235,32 @@ int orbx_match_triangulation(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const 
   if (!ctx) return ORBX_E_HIP;
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  TriScratch* s = ctxTri(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dMask;
-  uint32_t *dNode, *dFeat;
-  float *dPose, *dMed;
-  int32_t *dN, *dM;
-  orbx_tri_match_result* dR;
-  auto staging = [&](Layout L) {  // the two keyframes (KF1 0, KF2 1) in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dNode = L.take<uint32_t>((size_t)2 * cap);
-    dFeat = L.take<uint32_t>((size_t)2 * cap);
-    dMask = L.take<uint8_t>((size_t)2 * cap);
-    dPose = L.take<float>(24);
-    dMed = L.take<float>(2);
-    dN = L.take<int32_t>(4);  // n[2], fv_n[2]
-    dM = L.take<int32_t>(cap);
-    dR = L.take<orbx_tri_match_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));  // (the mask of a keyframe that brings none)
   const size_t c = (size_t)cap;
-  HIPCHK(up(dK, kps_un1, n1, st));
-  HIPCHK(up(dD, desc1, (size_t)n1 * 32, st));
-  HIPCHK(up(dK + c, kps_un2, n2, st));
-  HIPCHK(up(dD + c * 32, desc2, (size_t)n2 * 32, st));
-  HIPCHK(up(dNode, fv_node1, fv_n1, st));
-  HIPCHK(up(dFeat, fv_feat1, fv_n1, st));
-  HIPCHK(up(dNode + c, fv_node2, fv_n2, st));
-  HIPCHK(up(dFeat + c, fv_feat2, fv_n2, st));
-  if (mask1) HIPCHK(up(dMask, mask1, n1, st));
-  if (mask2) HIPCHK(up(dMask + c, mask2, n2, st));
-  HIPCHK(up(dPose, pose1, 12, st));
-  HIPCHK(up(dPose + 12, pose2, 12, st));
   const bool gate = median_depth2 > 0.0f;
   const float hMed[2] = {0.0f, median_depth2};
-  if (gate) HIPCHK(up(dMed, hMed, 2, st));
   const int32_t hn[4] = {n1, n2, fv_n1, fv_n2};
-  HIPCHK(up(dN, hn, 4, st));
-  r = orbx_match_triangulation_batch_device(ctx, 2, 1, &kf1, &kf2, dK, dD, dN, cap, dNode, dFeat, dN + 2,
-                                            mask1 || mask2 ? dMask : nullptr, dPose, K, gate ? dMed : nullptr, check_orientation, dM, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches12, dM, n1, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two keyframes (KF1 0, KF2 1) in the batch layout, then the results
+  auto dK = io.in(kps_un1, n1, 2 * c);
+  io.in(dK, c, kps_un2, n2);
+  auto dD = io.in(desc1, (size_t)n1 * 32, 2 * c * 32);
+  io.in(dD, c * 32, desc2, (size_t)n2 * 32);
+  auto dNode = io.in(fv_node1, fv_n1, 2 * c);
+  io.in(dNode, c, fv_node2, fv_n2);
+  auto dFeat = io.in(fv_feat1, fv_n1, 2 * c);
+  io.in(dFeat, c, fv_feat2, fv_n2);
+  auto dMask = io.optIn(mask1, n1, 2 * c);
+  io.in(dMask, c, mask2, n2);
+  dMask.absent = !mask1 && !mask2;  // (either keyframe may bring one alone: the other's stays zero)
+  auto dPose = io.in(pose1, 12, 24);
+  io.in(dPose, 12, pose2, 12);
+  auto dMed = io.optIn(gate ? hMed : nullptr, 2, 2);
+  auto dN = io.in(hn, 4, 4);  // n[2], fv_n[2]
+  auto dM = io.out(matches12, n1, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_match_triangulation_batch_device(ctx, 2, 1, &kf1, &kf2, io[dK], io[dD], io[dN], cap, io[dNode], io[dFeat], io[dN] + 2,
+                                            io[dMask], io[dPose], K, io[dMed], check_orientation, io[dM], io[dR]);
+  return io.close(ctx, r);
 }
 
 int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const float* pose1, const orbx_keypoint* kps_un2,
@@ -338,48 +276,25 @@ int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1
   if (!ctx) return ORBX_E_HIP;
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  TriScratch* s = ctxTri(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t* dMask;
-  float *dPose, *dP, *dNrm, *dDist;
-  int32_t *dN, *dM;
-  orbx_tri_result* dR;
-  auto staging = [&](Layout L) {  // the two keyframes in the batch layout, the matches, then the point set and the record
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dPose = L.take<float>(24);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dP = L.take<float>((size_t)cap * 3);
-    dMask = L.take<uint8_t>(cap);
-    dNrm = L.take<float>((size_t)cap * 3);
-    dDist = L.take<float>((size_t)cap * 2);
-    dR = L.take<orbx_tri_result>(1);
-    return L.size();
-  };
-  HIPCHK(s->dIo.grow(staging(Layout()), st));
-  staging(Layout(s->dIo));
   const size_t c = (size_t)cap;
-  HIPCHK(hipMemsetAsync(dM, 0xff, c * sizeof(int32_t), st));  // (entries at and beyond n1: no match)
-  HIPCHK(up(dK, kps_un1, n1, st));
-  HIPCHK(up(dK + c, kps_un2, n2, st));
-  HIPCHK(up(dPose, pose1, 12, st));
-  HIPCHK(up(dPose + 12, pose2, 12, st));
-  HIPCHK(up(dM, matches12, n1, st));
   const int32_t hn[2] = {n1, n2};
-  HIPCHK(up(dN, hn, 2, st));
-  r = orbx_triangulate_matches_batch_device(ctx, 2, 1, &kf1, &kf2, dK, dN, cap, dPose, K, dM, dP, dMask, dNrm, dDist, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);
-    return r;
-  }
-  HIPCHK(down(points, dP, (size_t)n1 * 3, st));
-  HIPCHK(down(point_mask, dMask, n1, st));
-  HIPCHK(down(point_normal, dNrm, (size_t)n1 * 3, st));
-  HIPCHK(down(point_dist, dDist, (size_t)n1 * 2, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two keyframes in the batch layout, the matches, then the point set and the record
+  auto dK = io.in(kps_un1, n1, 2 * c);
+  io.in(dK, c, kps_un2, n2);
+  auto dPose = io.in(pose1, 12, 24);
+  io.in(dPose, 12, pose2, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.in(matches12, n1, c);
+  io.fill(dM, 0xff, c);  // (entries at and beyond n1: no match)
+  auto dP = io.out(points, (size_t)n1 * 3, c * 3);
+  auto dMask = io.out(point_mask, n1, c);
+  auto dNrm = io.out(point_normal, (size_t)n1 * 3, c * 3);
+  auto dDist = io.out(point_dist, (size_t)n1 * 2, c * 2);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open());
+  r = orbx_triangulate_matches_batch_device(ctx, 2, 1, &kf1, &kf2, io[dK], io[dN], cap, io[dPose], K, io[dM], io[dP], io[dMask],
+                                            io[dNrm], io[dDist], io[dR]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"

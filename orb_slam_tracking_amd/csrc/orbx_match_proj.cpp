@@ -38,17 +38,14 @@ int refused(orbx_ctx* ctx, const char* name, float th, const char* own, const or
   return why ? ORBX_E_BADARG : ORBX_E_CAPACITY;
 }
 
-// A call's index lists, each of n_pairs entries, as one array [k][n_pairs] in `held`: uploaded only when they differ from the last
-// call's.  Such a call first waits for the context stream -- the host copy an earlier upload may still be reading is replaced --
-// and is the documented exception to "returns once queued".
-int holdLists(orbx_ctx* ctx, hipStream_t st, HeldArray<int32_t>& held, std::initializer_list<const int32_t*> columns, int nPairs) {
-  std::vector<int32_t> lists;
-  lists.reserve(columns.size() * nPairs);
-  for (const int32_t* c : columns) lists.insert(lists.end(), c, c + nPairs);
-  if (!held.holds(lists.data(), lists.size())) {
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(held.replace(st, lists.data(), lists.size()));
-  }
+// What every batch call here does once its arguments stand and there are pairs: the batches issued with the _async calls waited
+// for, and the call's index lists, each of n_pairs entries, as one array [k][n_pairs] in `held` (HeldUploads) -> *st, the stream
+// to launch on.
+int listsHeld(orbx_ctx* ctx, HeldArray<int32_t>& held, HeldArray<int32_t>::Columns columns, int nPairs, hipStream_t* st) {
+  const int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  *st = ctxStream(ctx);
+  HIPCHK(HeldUploads(*st)(held, columns, nPairs));
   return ORBX_OK;
 }
 
@@ -86,11 +83,9 @@ int orbx_match_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs,
   if (r != ORBX_OK) return r;
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->projPairs, {h_last, h_cur, h_point_set}, n_pairs);
+  HeldArray<int32_t>& pairs = ctxMatchBow(ctx)->projPairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_last, h_cur, h_point_set}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   MatchProjArgs a{};
   a.kps = d_kps_un;
@@ -101,7 +96,7 @@ int orbx_match_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs,
   a.pointDesc = d_point_desc32;
   a.lastOutlier = d_last_outlier;
   a.pose = d_pose_cur;
-  a.pairs = s->projPairs;
+  a.pairs = pairs;
   a.cap = capacity;
   a.nPairs = n_pairs;
   a.checkOri = check_orientation != 0;
@@ -128,54 +123,26 @@ int orbx_match_projection(orbx_ctx* ctx, const orbx_keypoint* last_kps_un, const
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dPD, *dMask, *dOut;
-  float *dP, *dPose;
-  int32_t *dN, *dM;
-  orbx_proj_result* dR;
-  auto staging = [&](Layout L) {  // the two frames (last 0, current 1) and one point set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dP = L.take<float>((size_t)cap * 3);
-    dPD = L.take<uint8_t>((size_t)cap * 32);
-    dMask = L.take<uint8_t>(cap);
-    dOut = L.take<uint8_t>(cap);
-    dPose = L.take<float>(12);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dR = L.take<orbx_proj_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dProjIo.grow(bytes, st));
-  staging(Layout(s->dProjIo));
-  HIPCHK(hipMemsetAsync(s->dProjIo, 0, bytes, st));
   const size_t c = (size_t)cap;
-  HIPCHK(up(dK, last_kps_un, last_n, st));
-  HIPCHK(up(dD, last_desc32, (size_t)last_n * 32, st));
-  HIPCHK(up(dK + c, cur_kps_un, cur_n, st));
-  HIPCHK(up(dD + c * 32, cur_desc32, (size_t)cur_n * 32, st));
-  HIPCHK(up(dP, points, (size_t)last_n * 3, st));
-  if (point_desc32) HIPCHK(up(dPD, point_desc32, (size_t)last_n * 32, st));
-  if (mask) HIPCHK(up(dMask, mask, last_n, st));
-  if (last_outlier) HIPCHK(up(dOut, last_outlier, last_n, st));
-  HIPCHK(up(dPose, pose_cur, 12, st));
   const int32_t hn[2] = {last_n, cur_n};
-  HIPCHK(up(dN, hn, 2, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two frames (last 0, current 1) and one point set in the batch layout, then the results
+  auto dK = io.in(last_kps_un, last_n, 2 * c);
+  io.in(dK, c, cur_kps_un, cur_n);
+  auto dD = io.in(last_desc32, (size_t)last_n * 32, 2 * c * 32);
+  io.in(dD, c * 32, cur_desc32, (size_t)cur_n * 32);
+  auto dP = io.in(points, (size_t)last_n * 3, c * 3);
+  auto dPD = io.optIn(point_desc32, (size_t)last_n * 32, c * 32);
+  auto dMask = io.optIn(mask, last_n, c);
+  auto dOut = io.optIn(last_outlier, last_n, c);
+  auto dPose = io.in(pose_cur, 12, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.out(matches_cur, cur_n, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
   const int32_t last = 0, cur = 1, set = 0;
-  r = orbx_match_projection_batch_device(ctx, 2, 1, &last, &cur, &set, dK, dD, dN, cap, 1, dP, mask ? dMask : nullptr,
-                                         point_desc32 ? dPD : nullptr, last_outlier ? dOut : nullptr, dPose, K, bounds, th,
-                                         check_orientation, dM, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches_cur, dM, cur_n, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_match_projection_batch_device(ctx, 2, 1, &last, &cur, &set, io[dK], io[dD], io[dN], cap, 1, io[dP], io[dMask], io[dPD],
+                                         io[dOut], io[dPose], K, bounds, th, check_orientation, io[dM], io[dR]);
+  return io.close(ctx, r);
 }
 
 int orbx_match_local_map_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_frame, const int32_t* h_map_set,
@@ -199,11 +166,9 @@ int orbx_match_local_map_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, 
   if (r != ORBX_OK) return r;
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->localPairs, {h_frame, h_map_set}, n_pairs);
+  HeldArray<int32_t>& pairs = ctxMatchBow(ctx)->localPairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_frame, h_map_set}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   MatchLocalArgs a{};
   a.kps = d_kps_un;
@@ -217,7 +182,7 @@ int orbx_match_local_map_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, 
   a.mapMask = d_map_mask;
   a.outlier = d_outlier;
   a.pose = d_pose;
-  a.pairs = s->localPairs;
+  a.pairs = pairs;
   a.cap = capacity;
   a.mapCap = map_capacity;
   a.nPairs = n_pairs;
@@ -245,58 +210,28 @@ int orbx_match_local_map(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dMD, *dMask, *dOut, *dView;
-  float *dP, *dNrm, *dDist, *dPose;
-  int32_t *dN, *dM;
-  orbx_local_result* dR;
-  auto staging = [&](Layout L) {  // one frame and one map set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>(cap);
-    dD = L.take<uint8_t>((size_t)cap * 32);
-    dMD = L.take<uint8_t>((size_t)mapCap * 32);
-    dP = L.take<float>((size_t)mapCap * 3);
-    dNrm = L.take<float>((size_t)mapCap * 3);
-    dDist = L.take<float>((size_t)mapCap * 2);
-    dMask = L.take<uint8_t>(mapCap);
-    dOut = L.take<uint8_t>(cap);
-    dView = L.take<uint8_t>(mapCap);
-    dPose = L.take<float>(12);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dR = L.take<orbx_local_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dLocalIo.grow(bytes, st));
-  staging(Layout(s->dLocalIo));
-  HIPCHK(hipMemsetAsync(s->dLocalIo, 0, bytes, st));
-  HIPCHK(up(dK, kps_un, n, st));
-  HIPCHK(up(dD, desc32, (size_t)n * 32, st));
-  HIPCHK(up(dM, matches, n, st));
-  HIPCHK(up(dMD, map_desc32, (size_t)map_n * 32, st));
-  HIPCHK(up(dP, map_points, (size_t)map_n * 3, st));
-  HIPCHK(up(dNrm, map_normals, (size_t)map_n * 3, st));
-  HIPCHK(up(dDist, map_dist, (size_t)map_n * 2, st));
-  if (map_mask) HIPCHK(up(dMask, map_mask, map_n, st));
-  if (outlier) HIPCHK(up(dOut, outlier, n, st));
-  HIPCHK(up(dPose, pose, 12, st));
+  const size_t c = (size_t)cap, mc = (size_t)mapCap;
   const int32_t hn[2] = {n, map_n};
-  HIPCHK(up(dN, hn, 2, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // one frame and one map set in the batch layout, then the results
+  auto dK = io.in(kps_un, n, c);
+  auto dD = io.in(desc32, (size_t)n * 32, c * 32);
+  auto dMD = io.in(map_desc32, (size_t)map_n * 32, mc * 32);
+  auto dP = io.in(map_points, (size_t)map_n * 3, mc * 3);
+  auto dNrm = io.in(map_normals, (size_t)map_n * 3, mc * 3);
+  auto dDist = io.in(map_dist, (size_t)map_n * 2, mc * 2);
+  auto dMask = io.optIn(map_mask, map_n, mc);
+  auto dOut = io.optIn(outlier, n, c);
+  auto dView = io.optOut(point_view, map_n, mc);
+  auto dPose = io.in(pose, 12, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.inout(matches, n, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
   const int32_t frame = 0, set = 0;
-  r = orbx_match_local_map_batch_device(ctx, 1, 1, &frame, &set, dK, dD, dN, cap, 1, mapCap, dN + 1, dP, dNrm, dDist, dMD,
-                                        map_mask ? dMask : nullptr, dPose, K, bounds, th, nnratio, dM, outlier ? dOut : nullptr,
-                                        point_view ? dView : nullptr, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches, dM, n, st));
-  if (point_view) HIPCHK(down(point_view, dView, map_n, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_match_local_map_batch_device(ctx, 1, 1, &frame, &set, io[dK], io[dD], io[dN], cap, 1, mapCap, io[dN] + 1, io[dP], io[dNrm],
+                                        io[dDist], io[dMD], io[dMask], io[dPose], K, bounds, th, nnratio, io[dM], io[dOut], io[dView],
+                                        io[dR]);
+  return io.close(ctx, r);
 }
 
 int orbx_match_keyframe_projection_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_cur,
@@ -316,11 +251,9 @@ int orbx_match_keyframe_projection_batch_device(orbx_ctx* ctx, int n_frames, int
   if (r != ORBX_OK) return r;
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->kfProjPairs, {h_kf, h_cur, h_point_set}, n_pairs);
+  HeldArray<int32_t>& pairs = ctxMatchBow(ctx)->kfProjPairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_kf, h_cur, h_point_set}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   MatchKfProjArgs a{};
   a.kps = d_kps_un;
@@ -332,7 +265,7 @@ int orbx_match_keyframe_projection_batch_device(orbx_ctx* ctx, int n_frames, int
   a.pointDist = d_point_dist;
   a.outlier = d_outlier;
   a.pose = d_pose;
-  a.pairs = s->kfProjPairs;
+  a.pairs = pairs;
   a.cap = capacity;
   a.nPairs = n_pairs;
   a.orbDist = orb_dist;
@@ -360,57 +293,28 @@ int orbx_match_keyframe_projection(orbx_ctx* ctx, const orbx_keypoint* kf_kps_un
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dPD, *dMask, *dOut;
-  float *dP, *dDist, *dPose;
-  int32_t *dN, *dM;
-  orbx_kfproj_result* dR;
-  auto staging = [&](Layout L) {  // the two frames (keyframe 0, current 1) and one point set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dP = L.take<float>((size_t)cap * 3);
-    dDist = L.take<float>((size_t)cap * 2);
-    dPD = L.take<uint8_t>((size_t)cap * 32);
-    dMask = L.take<uint8_t>(cap);
-    dOut = L.take<uint8_t>(cap);
-    dPose = L.take<float>(12);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dR = L.take<orbx_kfproj_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dKfProjIo.grow(bytes, st));
-  staging(Layout(s->dKfProjIo));
-  HIPCHK(hipMemsetAsync(s->dKfProjIo, 0, bytes, st));
   const size_t c = (size_t)cap;
-  HIPCHK(up(dK, kf_kps_un, kf_n, st));
-  HIPCHK(up(dD, kf_desc32, (size_t)kf_n * 32, st));
-  HIPCHK(up(dK + c, cur_kps_un, cur_n, st));
-  HIPCHK(up(dD + c * 32, cur_desc32, (size_t)cur_n * 32, st));
-  HIPCHK(up(dP, points, (size_t)kf_n * 3, st));
-  HIPCHK(up(dDist, point_dist, (size_t)kf_n * 2, st));
-  if (point_desc32) HIPCHK(up(dPD, point_desc32, (size_t)kf_n * 32, st));
-  if (mask) HIPCHK(up(dMask, mask, kf_n, st));
-  if (outlier) HIPCHK(up(dOut, outlier, cur_n, st));
-  HIPCHK(up(dM, matches, cur_n, st));
-  HIPCHK(up(dPose, pose, 12, st));
   const int32_t hn[2] = {kf_n, cur_n};
-  HIPCHK(up(dN, hn, 2, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two frames (keyframe 0, current 1) and one point set in the batch layout, then the results
+  auto dK = io.in(kf_kps_un, kf_n, 2 * c);
+  io.in(dK, c, cur_kps_un, cur_n);
+  auto dD = io.in(kf_desc32, (size_t)kf_n * 32, 2 * c * 32);
+  io.in(dD, c * 32, cur_desc32, (size_t)cur_n * 32);
+  auto dP = io.in(points, (size_t)kf_n * 3, c * 3);
+  auto dDist = io.in(point_dist, (size_t)kf_n * 2, c * 2);
+  auto dPD = io.optIn(point_desc32, (size_t)kf_n * 32, c * 32);
+  auto dMask = io.optIn(mask, kf_n, c);
+  auto dOut = io.optIn(outlier, cur_n, c);
+  auto dPose = io.in(pose, 12, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.inout(matches, cur_n, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
   const int32_t kf = 0, cur = 1, set = 0;
-  r = orbx_match_keyframe_projection_batch_device(ctx, 2, 1, &kf, &cur, &set, dK, dD, dN, cap, 1, dP, mask ? dMask : nullptr,
-                                                  point_desc32 ? dPD : nullptr, dDist, dPose, K, bounds, th, orb_dist,
-                                                  check_orientation, dM, outlier ? dOut : nullptr, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches, dM, cur_n, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_match_keyframe_projection_batch_device(ctx, 2, 1, &kf, &cur, &set, io[dK], io[dD], io[dN], cap, 1, io[dP], io[dMask], io[dPD],
+                                                  io[dDist], io[dPose], K, bounds, th, orb_dist, check_orientation, io[dM], io[dOut],
+                                                  io[dR]);
+  return io.close(ctx, r);
 }
 
 // ---- ORBmatcher::SearchBySim3 (include/orbx.h, "loop closing: matching under a similarity"; orbx_match_sim3_kernel.hip)
@@ -430,11 +334,9 @@ int orbx_match_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const
   if (r != ORBX_OK) return r;
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->sim3Pairs, {h_kf1, h_kf2, h_set1, h_set2}, n_pairs);
+  HeldArray<int32_t>& pairs = ctxMatchBow(ctx)->sim3Pairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_kf1, h_kf2, h_set1, h_set2}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   MatchSim3Args a{};
   a.kps = d_kps_un;
@@ -446,7 +348,7 @@ int orbx_match_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const
   a.pointDist = d_point_dist;
   a.pose = d_pose;
   a.sim3 = d_sim3;
-  a.pairs = s->sim3Pairs;
+  a.pairs = pairs;
   a.cap = capacity;
   a.nPairs = n_pairs;
   a.orbDist = orb_dist;
@@ -477,64 +379,31 @@ int orbx_match_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, const uint8_t* 
   if (!ctx) return ORBX_E_HIP;
   r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dPD, *dMask;
-  float *dP, *dDist, *dPose, *dSim;
-  int32_t *dN, *dM;
-  orbx_msim3_result* dR;
-  auto staging = [&](Layout L) {  // the two keyframes and their point sets in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dP = L.take<float>((size_t)2 * cap * 3);
-    dDist = L.take<float>((size_t)2 * cap * 2);
-    dPD = L.take<uint8_t>((size_t)2 * cap * 32);
-    dMask = L.take<uint8_t>((size_t)2 * cap);
-    dPose = L.take<float>(24);
-    dSim = L.take<float>(13);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dR = L.take<orbx_msim3_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dSim3Io.grow(bytes, st));
-  staging(Layout(s->dSim3Io));
-  HIPCHK(hipMemsetAsync(s->dSim3Io, 0, bytes, st));
   const size_t c = (size_t)cap;
-  HIPCHK(up(dK, kps_un1, n1, st));
-  HIPCHK(up(dK + c, kps_un2, n2, st));
-  HIPCHK(up(dD, desc1, (size_t)n1 * 32, st));
-  HIPCHK(up(dD + c * 32, desc2, (size_t)n2 * 32, st));
-  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
-  HIPCHK(up(dP + c * 3, points2, (size_t)n2 * 3, st));
-  HIPCHK(up(dDist, point_dist1, (size_t)n1 * 2, st));
-  HIPCHK(up(dDist + c * 2, point_dist2, (size_t)n2 * 2, st));
-  if (point_desc1) {
-    HIPCHK(up(dPD, point_desc1, (size_t)n1 * 32, st));
-    HIPCHK(up(dPD + c * 32, point_desc2, (size_t)n2 * 32, st));
-  }
-  if (mask1) {
-    HIPCHK(up(dMask, mask1, n1, st));
-    HIPCHK(up(dMask + c, mask2, n2, st));
-  }
-  HIPCHK(up(dPose, pose1, 12, st));
-  HIPCHK(up(dPose + 12, pose2, 12, st));
-  HIPCHK(up(dSim, sim3, 13, st));
-  HIPCHK(up(dM, matches12, n1, st));
   const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
-  HIPCHK(up(dN, hn, 2, st));
-  r = orbx_match_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dD, dN, cap, 2, dP, mask1 ? dMask : nullptr,
-                                   point_desc1 ? dPD : nullptr, dDist, dPose, dSim, K, bounds, th, orb_dist, dM, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches12, dM, n1, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // the two keyframes and their point sets in the batch layout, then the results
+  auto dK = io.in(kps_un1, n1, 2 * c);
+  io.in(dK, c, kps_un2, n2);
+  auto dD = io.in(desc1, (size_t)n1 * 32, 2 * c * 32);
+  io.in(dD, c * 32, desc2, (size_t)n2 * 32);
+  auto dP = io.in(points1, (size_t)n1 * 3, 2 * c * 3);
+  io.in(dP, c * 3, points2, (size_t)n2 * 3);
+  auto dDist = io.in(point_dist1, (size_t)n1 * 2, 2 * c * 2);
+  io.in(dDist, c * 2, point_dist2, (size_t)n2 * 2);
+  auto dPD = io.optIn(point_desc1, (size_t)n1 * 32, 2 * c * 32);  // (both keyframes bring theirs, or neither does)
+  io.in(dPD, c * 32, point_desc2, (size_t)n2 * 32);
+  auto dMask = io.optIn(mask1, n1, 2 * c);
+  io.in(dMask, c, mask2, n2);
+  auto dPose = io.in(pose1, 12, 24);
+  io.in(dPose, 12, pose2, 12);
+  auto dSim = io.in(sim3, 13, 13);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.inout(matches12, n1, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_match_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, io[dK], io[dD], io[dN], cap, 2, io[dP], io[dMask], io[dPD],
+                                   io[dDist], io[dPose], io[dSim], K, bounds, th, orb_dist, io[dM], io[dR]);
+  return io.close(ctx, r);
 }
 
 // ---- ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and the composition of Scw (include/orbx.h, "loop closing:
@@ -559,11 +428,9 @@ int orbx_match_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   if (r != ORBX_OK) return r;
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->scwPairs, {h_kf, h_map_set}, n_pairs);
+  HeldArray<int32_t>& pairs = ctxMatchBow(ctx)->scwPairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_kf, h_map_set}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   MatchScwArgs a{};
   a.kps = d_kps_un;
@@ -577,7 +444,7 @@ int orbx_match_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const 
   a.mapMask = d_map_mask;
   a.scw = d_scw;
   a.kf2ToMap = d_kf2_to_map;
-  a.pairs = s->scwPairs;
+  a.pairs = pairs;
   a.cap = capacity;
   a.mapCap = map_capacity;
   a.nPairs = n_pairs;
@@ -605,58 +472,29 @@ int orbx_match_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* de
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  uint8_t *dD, *dMD, *dMask;
-  float *dP, *dNrm, *dDist, *dScw;
-  int32_t *dN, *dM, *dTab;
-  orbx_scw_result* dR;
-  auto staging = [&](Layout L) {  // one keyframe and one map set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>(cap);
-    dD = L.take<uint8_t>((size_t)cap * 32);
-    dMD = L.take<uint8_t>((size_t)mapCap * 32);
-    dP = L.take<float>((size_t)mapCap * 3);
-    dNrm = L.take<float>((size_t)mapCap * 3);
-    dDist = L.take<float>((size_t)mapCap * 2);
-    dMask = L.take<uint8_t>(mapCap);
-    dScw = L.take<float>(12);
-    dN = L.take<int32_t>(2);
-    dM = L.take<int32_t>(cap);
-    dTab = L.take<int32_t>(cap);
-    dR = L.take<orbx_scw_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dScwIo.grow(bytes, st));
-  staging(Layout(s->dScwIo));
-  HIPCHK(hipMemsetAsync(s->dScwIo, 0, bytes, st));
   // (the table's tail, beyond n_table, names no point of the set: such an entry is never followed)
   std::vector<int32_t> table(kf2_to_map ? cap : 0, INT32_MAX);
   if (kf2_to_map) std::copy(kf2_to_map, kf2_to_map + n_table, table.begin());
-  HIPCHK(up(dK, kps_un, n, st));
-  HIPCHK(up(dD, desc32, (size_t)n * 32, st));
-  HIPCHK(up(dM, matches, n, st));
-  HIPCHK(up(dMD, map_desc32, (size_t)map_n * 32, st));
-  HIPCHK(up(dP, map_points, (size_t)map_n * 3, st));
-  HIPCHK(up(dNrm, map_normals, (size_t)map_n * 3, st));
-  HIPCHK(up(dDist, map_dist, (size_t)map_n * 2, st));
-  if (map_mask) HIPCHK(up(dMask, map_mask, map_n, st));
-  if (kf2_to_map) HIPCHK(up(dTab, table.data(), table.size(), st));
-  HIPCHK(up(dScw, scw, 12, st));
+  const size_t c = (size_t)cap, mc = (size_t)mapCap;
   const int32_t hn[2] = {n, map_n};
-  HIPCHK(up(dN, hn, 2, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // one keyframe and one map set in the batch layout, then the results
+  auto dK = io.in(kps_un, n, c);
+  auto dD = io.in(desc32, (size_t)n * 32, c * 32);
+  auto dMD = io.in(map_desc32, (size_t)map_n * 32, mc * 32);
+  auto dP = io.in(map_points, (size_t)map_n * 3, mc * 3);
+  auto dNrm = io.in(map_normals, (size_t)map_n * 3, mc * 3);
+  auto dDist = io.in(map_dist, (size_t)map_n * 2, mc * 2);
+  auto dMask = io.optIn(map_mask, map_n, mc);
+  auto dScw = io.in(scw, 12, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.inout(matches, n, c);
+  auto dTab = io.optIn(kf2_to_map ? table.data() : nullptr, table.size(), c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
   const int32_t frame = 0, set = 0;
-  r = orbx_match_scw_batch_device(ctx, 1, 1, &frame, &set, dK, dD, dN, cap, 1, mapCap, dN + 1, dP, dNrm, dDist, dMD,
-                                  map_mask ? dMask : nullptr, dScw, K, bounds, th, th_low, dM, kf2_to_map ? dTab : nullptr, dR);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(matches, dM, n, st));
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_match_scw_batch_device(ctx, 1, 1, &frame, &set, io[dK], io[dD], io[dN], cap, 1, mapCap, io[dN] + 1, io[dP], io[dNrm], io[dDist],
+                                  io[dMD], io[dMask], io[dScw], K, bounds, th, th_low, io[dM], io[dTab], io[dR]);
+  return io.close(ctx, r);
 }
 
 int orbx_sim3_compose_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf2, const float* d_pose,
@@ -668,16 +506,14 @@ int orbx_sim3_compose_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs,
   }
   if (!ctx) return ORBX_E_HIP;  // no device context
   if (n_pairs == 0) return ORBX_OK;
-  int r = ctxDrain(ctx);
-  if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  r = holdLists(ctx, st, s->composeKf2, {h_kf2}, n_pairs);
+  HeldArray<int32_t>& kf2 = ctxMatchBow(ctx)->composeKf2;
+  hipStream_t st;
+  const int r = listsHeld(ctx, kf2, {h_kf2}, n_pairs, &st);
   if (r != ORBX_OK) return r;
   Sim3ComposeArgs a{};
   a.pose = d_pose;
   a.sim3 = d_sim3;
-  a.kf2 = s->composeKf2;
+  a.kf2 = kf2;
   a.nPairs = n_pairs;
   a.scw = d_scw;
   HIPCHK(launch_sim3_compose_scw(st, a));
@@ -689,29 +525,14 @@ int orbx_sim3_compose_scw(orbx_ctx* ctx, const float* pose2, const float* sim3, 
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  MatchBowScratch* s = ctxMatchBow(ctx);
-  hipStream_t st = ctxStream(ctx);
-  float *dPose, *dSim, *dScw;
-  auto staging = [&](Layout L) {
-    dPose = L.take<float>(12);
-    dSim = L.take<float>(13);
-    dScw = L.take<float>(12);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dComposeIo.grow(bytes, st));
-  staging(Layout(s->dComposeIo));
-  HIPCHK(up(dPose, pose2, 12, st));
-  HIPCHK(up(dSim, sim3, 13, st));
+  Staged io(ctxIo(ctx), ctxStream(ctx));
+  auto dPose = io.in(pose2, 12, 12);
+  auto dSim = io.in(sim3, 13, 13);
+  auto dScw = io.out(scw, 12, 12);
+  HIPCHK(io.open());
   const int32_t kf2 = 0;
-  r = orbx_sim3_compose_scw_batch_device(ctx, 1, 1, &kf2, dPose, dSim, dScw);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this call's arguments)
-    return r;
-  }
-  HIPCHK(down(scw, dScw, 12, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  r = orbx_sim3_compose_scw_batch_device(ctx, 1, 1, &kf2, io[dPose], io[dSim], io[dScw]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"

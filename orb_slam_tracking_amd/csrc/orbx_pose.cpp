@@ -45,14 +45,9 @@ int orbx_pose_optimize_batch_device(orbx_ctx* ctx, int n_frames, int n_problems,
   hipStream_t st = ctxStream(ctx);
   int nLevels = 0;
   const float* table = ctxInvSigma2(ctx, &nLevels);
-  // the problem list and the table go up only when they differ from the last call's.  Such a call first waits for the context
-  // stream -- the host copies an earlier upload may still be reading are replaced -- and is the documented exception to "returns
-  // once queued" (include/orbx.h)
-  const float* sig = inv_sigma2 ? inv_sigma2 : table;
-  const bool sameList = s->problems.holds(h_frame, n_problems, h_point_set, n_problems), sameSigma = s->sigma.holds(sig, nLevels);
-  if (!sameList || !sameSigma) HIPCHK(hipStreamSynchronize(st));
-  if (!sameList) HIPCHK(s->problems.replace(st, h_frame, n_problems, h_point_set, n_problems));
-  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
+  HeldUploads hold(st);
+  HIPCHK(hold(s->problems, {h_frame, h_point_set}, n_problems));
+  HIPCHK(hold(s->sigma, {inv_sigma2 ? inv_sigma2 : table}, nLevels));
   PoseArgs a{};
   a.kps = d_kps_un;
   a.nKps = d_n;
@@ -86,43 +81,20 @@ int orbx_pose_optimize(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const 
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  PoseScratch* s = ctxPose(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  int32_t* dN;
-  float *dP, *dPose;
-  uint8_t *dM, *dO;
-  orbx_pose_result* dR;
-  auto staging = [&](Layout L) {  // one frame and one point set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>(cap);
-    dN = L.take<int32_t>(1);
-    dP = L.take<float>((size_t)cap * 3);
-    dPose = L.take<float>(12);
-    dM = L.take<uint8_t>(cap);
-    dO = L.take<uint8_t>(cap);
-    dR = L.take<orbx_pose_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
   const int32_t hn = n, zero = 0;
-  HIPCHK(up(dK, kps_un, n, st));
-  HIPCHK(up(dP, points, (size_t)n * 3, st));
-  if (mask) HIPCHK(up(dM, mask, n, st));
-  HIPCHK(up(dN, &hn, 1, st));
-  HIPCHK(up(dPose, pose0, 12, st));
-  r = orbx_pose_optimize_batch_device(ctx, 1, 1, &zero, &zero, dK, dN, cap, nullptr, 1, dP, mask ? dM : nullptr, dPose, K, inv_sigma2,
-                                      n_iterations, dR, dO);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(down(outlier, dO, n, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // one frame and one point set in the batch layout, then the results
+  auto dK = io.in(kps_un, n, c);
+  auto dN = io.in(&hn, 1, 1);
+  auto dP = io.in(points, (size_t)n * 3, c * 3);
+  auto dPose = io.in(pose0, 12, 12);
+  auto dM = io.optIn(mask, n, c);
+  auto dO = io.out(outlier, n, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_pose_optimize_batch_device(ctx, 1, 1, &zero, &zero, io[dK], io[dN], cap, nullptr, 1, io[dP], io[dM], io[dPose], K, inv_sigma2,
+                                      n_iterations, io[dR], io[dO]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"
@@ -212,14 +184,10 @@ int orbx_pnp_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, con
     return L.size();
   };
   const size_t bytes = workspace(Layout());
-  // the lists and the tables go up only when they differ from the last call's; such a call first waits for the context stream,
-  // as orbx_pose_optimize_batch_device does (include/orbx.h)
-  const bool sameList = s->problems.holds(h_frame, n_problems, h_point_set, n_problems), sameSigma = s->sigma2.holds(sig, nLevels),
-             sameTable = s->table.holds(s->hTable.data(), tableLen);
-  if (!sameList || !sameSigma || !sameTable) HIPCHK(hipStreamSynchronize(st));
-  if (!sameList) HIPCHK(s->problems.replace(st, h_frame, n_problems, h_point_set, n_problems));
-  if (!sameSigma) HIPCHK(s->sigma2.replace(st, sig, nLevels));
-  if (!sameTable) HIPCHK(s->table.replace(st, s->hTable.data(), tableLen));
+  HeldUploads hold(st);
+  HIPCHK(hold(s->problems, {h_frame, h_point_set}, n_problems));
+  HIPCHK(hold(s->sigma2, {sig}, nLevels));
+  HIPCHK(hold(s->table, {s->hTable.data()}, tableLen));
   HIPCHK(s->dWork.grow(bytes, st));
   workspace(Layout(s->dWork));
   a.kps = d_kps_un;
@@ -261,45 +229,22 @@ int orbx_pnp_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un, int n, const floa
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  PnpScratch* s = ctxPnp(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  int32_t *dN, *dDraws, *dRow;
-  float *dP, *dPose;
-  uint8_t *dM, *dI;
-  orbx_pnp_result* dR;
-  auto staging = [&](Layout L) {  // one frame and one point set in the batch layout, then the results
-    dK = L.take<orbx_keypoint>(cap);
-    dN = L.take<int32_t>(1);
-    dP = L.take<float>((size_t)cap * 3);
-    dM = L.take<uint8_t>(cap);
-    dDraws = L.take<int32_t>((size_t)n_iter * 4);
-    dPose = L.take<float>(12);
-    dRow = L.take<int32_t>(cap);
-    dI = L.take<uint8_t>(cap);
-    dR = L.take<orbx_pnp_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
   const int32_t hn = n, zero = 0;
-  HIPCHK(up(dK, kps_un, n, st));
-  HIPCHK(up(dP, points, (size_t)n * 3, st));
-  if (mask) HIPCHK(up(dM, mask, n, st));
-  HIPCHK(up(dN, &hn, 1, st));
-  HIPCHK(up(dDraws, draws, (size_t)n_iter * 4, st));
-  r = orbx_pnp_solve_batch_device(ctx, 1, 1, &zero, &zero, dK, dN, cap, nullptr, 1, dP, mask ? dM : nullptr, K, sigma2, probability,
-                                  min_inliers, max_iterations, epsilon, th2, n_iter, dDraws, dR, dPose, dRow, dI);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(down(inliers, dI, n, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // one frame and one point set in the batch layout, then the results
+  auto dK = io.in(kps_un, n, c);
+  auto dN = io.in(&hn, 1, 1);
+  auto dP = io.in(points, (size_t)n * 3, c * 3);
+  auto dM = io.optIn(mask, n, c);
+  auto dDraws = io.in(draws, (size_t)n_iter * 4, (size_t)n_iter * 4);
+  auto dPose = io.room<float>(12);
+  auto dRow = io.room<int32_t>(c);
+  auto dI = io.out(inliers, n, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_pnp_solve_batch_device(ctx, 1, 1, &zero, &zero, io[dK], io[dN], cap, nullptr, 1, io[dP], io[dM], K, sigma2, probability,
+                                  min_inliers, max_iterations, epsilon, th2, n_iter, io[dDraws], io[dR], io[dPose], io[dRow], io[dI]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"
@@ -388,17 +333,10 @@ int orbx_sim3_solve_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, co
     return L.size();
   };
   const size_t bytes = workspace(Layout());
-  // the lists and the tables go up only when they differ from the last call's; such a call first waits for the context stream,
-  // as orbx_pnp_solve_batch_device does (include/orbx.h)
-  std::vector<int32_t> lists;
-  lists.reserve((size_t)4 * n_problems);
-  for (const int32_t* c : {h_kf1, h_kf2, h_set1, h_set2}) lists.insert(lists.end(), c, c + n_problems);
-  const bool sameList = s->problems.holds(lists.data(), lists.size()), sameSigma = s->sigma2.holds(sig, nLevels),
-             sameTable = s->table.holds(s->hTable.data(), tableLen);
-  if (!sameList || !sameSigma || !sameTable) HIPCHK(hipStreamSynchronize(st));
-  if (!sameList) HIPCHK(s->problems.replace(st, lists.data(), lists.size()));
-  if (!sameSigma) HIPCHK(s->sigma2.replace(st, sig, nLevels));
-  if (!sameTable) HIPCHK(s->table.replace(st, s->hTable.data(), tableLen));
+  HeldUploads hold(st);
+  HIPCHK(hold(s->problems, {h_kf1, h_kf2, h_set1, h_set2}, n_problems));
+  HIPCHK(hold(s->sigma2, {sig}, nLevels));
+  HIPCHK(hold(s->table, {s->hTable.data()}, tableLen));
   HIPCHK(s->dWork.grow(bytes, st));
   workspace(Layout(s->dWork));
   a.kps = d_kps_un;
@@ -449,57 +387,29 @@ int orbx_sim3_solve(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, const f
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  Sim3Scratch* s = ctxSim3(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  int32_t *dN, *dMatch, *dDraws, *dRow;
-  float *dP, *dPose, *dSim;
-  uint8_t *dM, *dI;
-  orbx_sim3_result* dR;
-  auto staging = [&](Layout L) {  // two frames and two point sets in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dP = L.take<float>((size_t)2 * cap * 3);
-    dM = L.take<uint8_t>((size_t)2 * cap);
-    dPose = L.take<float>(24);
-    dMatch = L.take<int32_t>(cap);
-    dDraws = L.take<int32_t>((size_t)n_iter * 3);
-    dSim = L.take<float>(13);
-    dRow = L.take<int32_t>(cap);
-    dI = L.take<uint8_t>(cap);
-    dR = L.take<orbx_sim3_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
   const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
-  HIPCHK(up(dK, kps_un1, n1, st));
-  HIPCHK(up(dK + cap, kps_un2, n2, st));
-  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
-  HIPCHK(up(dP + (size_t)cap * 3, points2, (size_t)n2 * 3, st));
-  if (mask1) {
-    HIPCHK(up(dM, mask1, n1, st));
-    HIPCHK(up(dM + cap, mask2, n2, st));
-  }
-  HIPCHK(up(dN, hn, 2, st));
-  HIPCHK(up(dPose, pose1, 12, st));
-  HIPCHK(up(dPose + 12, pose2, 12, st));
-  HIPCHK(up(dMatch, match12, n1, st));
-  HIPCHK(up(dDraws, draws, (size_t)n_iter * 3, st));
-  r = orbx_sim3_solve_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dN, cap, dMatch, 2, dP, mask1 ? dM : nullptr, dPose, K, sigma2,
-                                   fix_scale, probability, min_inliers, max_iterations, th2, n_iter, dDraws, dR, dSim, dRow, dI);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(down(sim3, dSim, 13, st));
-  HIPCHK(down(match_inliers, dRow, n1, st));
-  if (inliers) HIPCHK(down(inliers, dI, n1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // two frames and two point sets in the batch layout, then the results
+  auto dK = io.in(kps_un1, n1, 2 * c);
+  io.in(dK, c, kps_un2, n2);
+  auto dN = io.in(hn, 2, 2);
+  auto dP = io.in(points1, (size_t)n1 * 3, 2 * c * 3);
+  io.in(dP, c * 3, points2, (size_t)n2 * 3);
+  auto dM = io.optIn(mask1, n1, 2 * c);  // (both frames bring a mask, or neither does)
+  io.in(dM, c, mask2, n2);
+  auto dPose = io.in(pose1, 12, 24);
+  io.in(dPose, 12, pose2, 12);
+  auto dMatch = io.in(match12, n1, c);
+  auto dDraws = io.in(draws, (size_t)n_iter * 3, (size_t)n_iter * 3);
+  auto dSim = io.out(sim3, 13, 13);
+  auto dRow = io.out(match_inliers, n1, c);
+  auto dI = io.out(inliers, n1, c);  // (the kernel writes them whether the caller takes them or not)
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_sim3_solve_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, io[dK], io[dN], cap, io[dMatch], 2, io[dP], io[dM], io[dPose], K,
+                                   sigma2, fix_scale, probability, min_inliers, max_iterations, th2, n_iter, io[dDraws], io[dR], io[dSim],
+                                   io[dRow], io[dI]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"
@@ -541,16 +451,9 @@ int orbx_optimize_sim3_batch_device(orbx_ctx* ctx, int n_frames, int n_problems,
   hipStream_t st = ctxStream(ctx);
   int nLevels = 0;
   const float* table = ctxInvSigma2(ctx, &nLevels);
-  const float* sig = inv_sigma2 ? inv_sigma2 : table;
-  // the lists and the table go up only when they differ from the last call's; such a call first waits for the context stream, as
-  // orbx_pose_optimize_batch_device does (include/orbx.h)
-  std::vector<int32_t> lists;
-  lists.reserve((size_t)4 * n_problems);
-  for (const int32_t* c : {h_kf1, h_kf2, h_set1, h_set2}) lists.insert(lists.end(), c, c + n_problems);
-  const bool sameList = s->problems.holds(lists.data(), lists.size()), sameSigma = s->sigma.holds(sig, nLevels);
-  if (!sameList || !sameSigma) HIPCHK(hipStreamSynchronize(st));
-  if (!sameList) HIPCHK(s->problems.replace(st, lists.data(), lists.size()));
-  if (!sameSigma) HIPCHK(s->sigma.replace(st, sig, nLevels));
+  HeldUploads hold(st);
+  HIPCHK(hold(s->problems, {h_kf1, h_kf2, h_set1, h_set2}, n_problems));
+  HIPCHK(hold(s->sigma, {inv_sigma2 ? inv_sigma2 : table}, nLevels));
   Sim3OptArgs a{};
   a.kps = d_kps_un;
   a.nKps = d_n;
@@ -592,54 +495,26 @@ int orbx_optimize_sim3(orbx_ctx* ctx, const orbx_keypoint* kps_un1, int n1, cons
   if (!ctx) return ORBX_E_HIP;
   int r = ctxDrain(ctx);
   if (r != ORBX_OK) return r;
-  Sim3OptScratch* s = ctxSim3Opt(ctx);
-  hipStream_t st = ctxStream(ctx);
-  orbx_keypoint* dK;
-  int32_t *dN, *dRow;
-  float *dP, *dPose, *dSim, *dSimOut;
-  uint8_t* dM;
-  orbx_sim3opt_result* dR;
-  auto staging = [&](Layout L) {  // two frames and two point sets in the batch layout, then the results
-    dK = L.take<orbx_keypoint>((size_t)2 * cap);
-    dN = L.take<int32_t>(2);
-    dP = L.take<float>((size_t)2 * cap * 3);
-    dM = L.take<uint8_t>((size_t)2 * cap);
-    dPose = L.take<float>(24);
-    dRow = L.take<int32_t>(cap);
-    dSim = L.take<float>(13);
-    dSimOut = L.take<float>(13);
-    dR = L.take<orbx_sim3opt_result>(1);
-    return L.size();
-  };
-  const size_t bytes = staging(Layout());
-  HIPCHK(s->dIo.grow(bytes, st));
-  staging(Layout(s->dIo));
-  HIPCHK(hipMemsetAsync(s->dIo, 0, bytes, st));
+  const size_t c = (size_t)cap;
   const int32_t hn[2] = {n1, n2}, zero = 0, one = 1;
-  HIPCHK(up(dK, kps_un1, n1, st));
-  HIPCHK(up(dK + cap, kps_un2, n2, st));
-  HIPCHK(up(dP, points1, (size_t)n1 * 3, st));
-  HIPCHK(up(dP + (size_t)cap * 3, points2, (size_t)n2 * 3, st));
-  if (mask1) {
-    HIPCHK(up(dM, mask1, n1, st));
-    HIPCHK(up(dM + cap, mask2, n2, st));
-  }
-  HIPCHK(up(dN, hn, 2, st));
-  HIPCHK(up(dPose, pose1, 12, st));
-  HIPCHK(up(dPose + 12, pose2, 12, st));
-  HIPCHK(up(dRow, matches12, n1, st));
-  HIPCHK(up(dSim, sim3, 13, st));
-  r = orbx_optimize_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, dK, dN, cap, dRow, 2, dP, mask1 ? dM : nullptr, dPose, dSim, K,
-                                      inv_sigma2, fix_scale, th2, n_iterations, n_more_iterations, dR, dSimOut);
-  if (r != ORBX_OK) {
-    (void)hipStreamSynchronize(st);  // (the uploads queued above read this frame's variables)
-    return r;
-  }
-  HIPCHK(down(res, dR, 1, st));
-  HIPCHK(down(sim3_out, dSimOut, 13, st));
-  HIPCHK(down(matches12, dRow, n1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return ORBX_OK;
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // two frames and two point sets in the batch layout, then the results
+  auto dK = io.in(kps_un1, n1, 2 * c);
+  io.in(dK, c, kps_un2, n2);
+  auto dN = io.in(hn, 2, 2);
+  auto dP = io.in(points1, (size_t)n1 * 3, 2 * c * 3);
+  io.in(dP, c * 3, points2, (size_t)n2 * 3);
+  auto dM = io.optIn(mask1, n1, 2 * c);  // (both frames bring a mask, or neither does)
+  io.in(dM, c, mask2, n2);
+  auto dPose = io.in(pose1, 12, 24);
+  io.in(dPose, 12, pose2, 12);
+  auto dRow = io.inout(matches12, n1, c);
+  auto dSim = io.in(sim3, 13, 13);
+  auto dSimOut = io.out(sim3_out, 13, 13);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = orbx_optimize_sim3_batch_device(ctx, 2, 1, &zero, &one, &zero, &one, io[dK], io[dN], cap, io[dRow], 2, io[dP], io[dM], io[dPose],
+                                      io[dSim], K, inv_sigma2, fix_scale, th2, n_iterations, n_more_iterations, io[dR], io[dSimOut]);
+  return io.close(ctx, r);
 }
 
 }  // extern "C"
