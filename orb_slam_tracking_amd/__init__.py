@@ -27,10 +27,13 @@ __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame",
            "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE",
            "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted"]
 
-# mirrors cv::KeyPoint / orbx_keypoint (28 bytes)
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                           ("octave", "<i4"), ("class_id", "<i4")])
-assert KEYPOINT_DTYPE.itemsize == 28
+from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResult, HF_RESULT_DTYPE, InitResult,  # noqa: F401
+                       INIT_RESULT_DTYPE, BAResult, BA_RESULT_DTYPE, PoseResult, POSE_RESULT_DTYPE, PnpResult, PNP_RESULT_DTYPE,
+                       Sim3Result, SIM3_RESULT_DTYPE, Sim3OptResult, SIM3OPT_RESULT_DTYPE, ProjResult, PROJ_RESULT_DTYPE,
+                       PROJ_RESULT_FIELDS, LocalResult, LOCAL_RESULT_DTYPE, LOCAL_RESULT_FIELDS, MatchScwResult, SCW_RESULT_DTYPE,
+                       SCW_RESULT_FIELDS, KfProjResult, KFPROJ_RESULT_DTYPE, KFPROJ_RESULT_FIELDS, MatchSim3Result,
+                       MSIM3_RESULT_DTYPE, MSIM3_RESULT_FIELDS, TriMatchResult, TRI_MATCH_RESULT_DTYPE, TRI_MATCH_COUNTERS,
+                       TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS)
 
 E_EMPTY, E_BADARG, E_TOOSMALL, E_HIP, E_CAPACITY, E_RCCL = -1, -2, -3, -4, -5, -6
 _ERRNAMES = {-1: "ORBX_E_EMPTY", -2: "ORBX_E_BADARG", -3: "ORBX_E_TOOSMALL", -4: "ORBX_E_HIP", -5: "ORBX_E_CAPACITY", -6: "ORBX_E_RCCL"}
@@ -43,254 +46,50 @@ class OrbxError(RuntimeError):
         super().__init__("%s (%d)%s" % (_ERRNAMES.get(code, "ORBX_E_?"), code, (": " + what) if what else ""))
 
 
-class _Params(ctypes.Structure):
-    _fields_ = [("nfeatures", ctypes.c_int32), ("scale_factor", ctypes.c_float), ("nlevels", ctypes.c_int32),
-                ("ini_th_fast", ctypes.c_int32), ("min_th_fast", ctypes.c_int32)]
-
-
-class _Bounds(ctypes.Structure):
-    _fields_ = [("min_x", ctypes.c_int32), ("max_x", ctypes.c_int32), ("min_y", ctypes.c_int32), ("max_y", ctypes.c_int32)]
-
-
-class _Camera(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
-
-
-class HFResult(ctypes.Structure):
-    """orbx_hf_result: what Initializer::Initialize knows after its two RANSAC loops (Initializer.cpp:78-111)."""
-    _fields_ = [(n, ctypes.c_int32) for n in ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h",
-                                              "n_inliers_f", "reserved")] + \
-               [(n, ctypes.c_float) for n in ("score_h", "score_f", "rh")] + \
-               [(n, ctypes.c_float * 9) for n in ("H21", "H12", "F21")]
-
-    def as_dict(self) -> dict:
-        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
-        for n in ("H21", "H12", "F21"):
-            d[n] = np.array(d[n][:], np.float32).reshape(3, 3)
-        return d
-
-
-assert ctypes.sizeof(HFResult) == 4 * (8 + 3 + 27)
-HF_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h",
-                                                 "n_inliers_f", "reserved")] +
-                           [(n, "<f4") for n in ("score_h", "score_f", "rh")] + [(n, "<f4", (3, 3)) for n in ("H21", "H12", "F21")])
-assert HF_RESULT_DTYPE.itemsize == ctypes.sizeof(HFResult)
+# the status bits of the records (_records.py), as include/orbx.h names them
 INIT_TOO_FEW_MATCHES, INIT_BAD_SETS, INIT_NO_SCORE, INIT_BAD_MATCHES = 1, 2, 4, 128
 INIT_AMBIGUOUS, INIT_LOW_PARALLAX, INIT_FEW_TRIANGULATED, INIT_FEW_INLIERS = 8, 16, 32, 64
-_INIT_INTS = ("status", "model", "n_matches", "best_it_h", "best_it_f", "n_inliers_h", "n_inliers_f", "n_solutions", "best_solution",
-              "best_good", "second_good", "reserved")
-
-
-class InitResult(ctypes.Structure):
-    """orbx_init_result: Initializer::Initialize's outcome (status 0 = reconstructed) and the chosen (R21, t21)."""
-    _fields_ = [(n, ctypes.c_int32) for n in _INIT_INTS] + [(n, ctypes.c_float) for n in ("score_h", "score_f", "rh", "parallax")] + \
-               [("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3), ("H21", ctypes.c_float * 9), ("F21", ctypes.c_float * 9)]
-
-    def as_dict(self) -> dict:
-        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
-        for n in ("R21", "H21", "F21"):
-            d[n] = np.array(d[n][:], np.float32).reshape(3, 3)
-        d["t21"] = np.array(d["t21"][:], np.float32)
-        return d
-
-
-INIT_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _INIT_INTS] + [(n, "<f4") for n in ("score_h", "score_f", "rh", "parallax")] +
-                             [("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3))])
-assert INIT_RESULT_DTYPE.itemsize == ctypes.sizeof(InitResult) == 184
 BA_SKIPPED, BA_BAD_INPUT, BA_NONFINITE, BA_FEW_POINTS, BA_NEGATIVE_DEPTH = 1, 2, 4, 8, 16
-_BA_INTS = ("status", "n_points", "iterations", "lm_trials", "rejected_trials", "solver_failures", "stop_reason", "reserved")
-
-
-class BAResult(ctypes.Structure):
-    """orbx_ba_result: the two-view bundle adjustment's outcome for one pair (status 0 = a usable initial map)."""
-    _fields_ = [(n, ctypes.c_int32) for n in _BA_INTS] + [(n, ctypes.c_double) for n in ("chi2_initial", "chi2_final", "lambda_")] + \
-               [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
-                ("median_depth", ctypes.c_float), ("reserved2", ctypes.c_float)]
-
-    def as_dict(self) -> dict:
-        d = {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
-        d["lambda"] = d.pop("lambda_")
-        d["q"], d["t"] = np.array(d["q"][:], np.float64), np.array(d["t"][:], np.float64)
-        d["R21"], d["t21"] = np.array(d["R21"][:], np.float32).reshape(3, 3), np.array(d["t21"][:], np.float32)
-        return d
-
-
-BA_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _BA_INTS] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
-                           [("q", "<f8", 4), ("t", "<f8", 3), ("R21", "<f4", (3, 3)), ("t21", "<f4", 3), ("median_depth", "<f4"),
-                            ("reserved2", "<f4")])
-assert BA_RESULT_DTYPE.itemsize == ctypes.sizeof(BAResult) == 168
 POSE_BAD_INPUT, POSE_NONFINITE, POSE_FEW_POINTS = 2, 4, 8
-
-
-class PoseResult(ctypes.Structure):
-    """orbx_pose_result: Optimizer::PoseOptimization's outcome for one problem (n_inliers is the reference design's return value)."""
-    _fields_ = [(n, ctypes.c_int32) for n in ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")] + \
-               [("iterations", ctypes.c_int32 * 4)] + [(n, ctypes.c_int32) for n in ("lm_trials", "rejected_trials", "solver_failures")] + \
-               [("stop_reason", ctypes.c_int32 * 4)] + [(n, ctypes.c_double) for n in ("chi2_initial", "chi2_final", "lambda_")] + \
-               [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("R", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3)]
-
-    def as_dict(self) -> dict:
-        d = {n: getattr(self, n) for n, _ in self._fields_}
-        d["lambda"] = d.pop("lambda_")
-        d["iterations"], d["stop_reason"] = np.array(d["iterations"][:], np.int32), np.array(d["stop_reason"][:], np.int32)
-        d["q"], d["t"] = np.array(d["q"][:], np.float64), np.array(d["t"][:], np.float64)
-        d["R"], d["tcw"] = np.array(d["R"][:], np.float32).reshape(3, 3), np.array(d["tcw"][:], np.float32)
-        return d
-
-
-POSE_RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")] +
-                             [("iterations", "<i4", 4)] + [(n, "<i4") for n in ("lm_trials", "rejected_trials", "solver_failures")] +
-                             [("stop_reason", "<i4", 4)] + [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] +
-                             [("q", "<f8", 4), ("t", "<f8", 3), ("R", "<f4", (3, 3)), ("tcw", "<f4", 3)])
-assert POSE_RESULT_DTYPE.itemsize == ctypes.sizeof(PoseResult) == 192
-
-
 PNP_BAD_INPUT, PNP_NONFINITE, PNP_FEW_POINTS, PNP_BAD_DRAWS, PNP_NO_POSE = 2, 4, 8, 16, 32
 PNP_RAND_MAX = 2147483647
-_PNP_INTS = ("status", "n_correspondences", "min_inliers", "max_its", "its_run", "found_it", "best_it", "refined", "n_inliers",
-             "n_best_inliers", "n_refines", "n_degenerate", "beta_choice", "reserved")
+SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT = 2, 4, 8, 16, 32
+SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
+PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
+LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
+SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
+KFPROJ_BAD_INPUT, KFPROJ_NONFINITE = 2, 4
+MSIM3_BAD_INPUT, MSIM3_NONFINITE = 2, 4
+TRI_BAD_INPUT, TRI_NONFINITE, TRI_LOW_BASELINE, TRI_ZERO_BASELINE = 2, 4, 8, 16
 
 
-class PnpResult(ctypes.Structure):
-    """orbx_pnp_result: PnPsolver's outcome for one problem (found_it tells which iterate() turn would have returned it)."""
-    _fields_ = [(n, ctypes.c_int32) for n in _PNP_INTS] + [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3),
-                                                          ("Tcw", ctypes.c_float * 12)]
-
-    def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n in _PNP_INTS if n != "reserved"}
-        d["R"], d["t"] = np.array(self.R[:], np.float64).reshape(3, 3), np.array(self.t[:], np.float64)
-        d["Tcw"] = np.array(self.Tcw[:], np.float32)
-        return d
-
-
-PNP_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _PNP_INTS] + [("R", "<f8", (3, 3)), ("t", "<f8", 3), ("Tcw", "<f4", 12)])
-assert PNP_RESULT_DTYPE.itemsize == ctypes.sizeof(PnpResult) == 200
+def _sample_draws(rand, n_iter: int, width: int) -> np.ndarray:
+    out = np.zeros((int(n_iter), width), np.int32)
+    for row in out:
+        for j in range(width):
+            row[j] = int(rand())
+    return out
 
 
 def sample_pnp_draws(rand, n_iter: int) -> np.ndarray:
     """The draws of n_iter PnP RANSAC hypotheses, int32 [n_iter, 4]: the next 4 * n_iter values of `rand`, a callable returning
     the host's next rand() value (as sample_sets takes it), in the order PnPsolver::iterate would draw them.  The device turns
     them into indices itself (DUtils::Random::RandomInt and the swap-and-pop), so the caller need not know N."""
-    n_iter = int(n_iter)
-    out = np.zeros((n_iter, 4), np.int32)
-    for it in range(n_iter):
-        for j in range(4):
-            out[it, j] = int(rand())
-    return out
-
-
-SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT = 2, 4, 8, 16, 32
-_SIM3_INTS = ("status", "n_correspondences", "max_its", "its_run", "found_it", "best_it", "n_inliers", "n_best_inliers", "n_degenerate")
-
-
-class Sim3Result(ctypes.Structure):
-    """orbx_sim3_result: Sim3Solver's outcome for one keyframe pair (found_it tells which iterate() turn would have returned it)."""
-    _fields_ = [(n, ctypes.c_int32) for n in _SIM3_INTS] + [("reserved", ctypes.c_int32 * 2), ("s12", ctypes.c_float),
-                                                           ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3)]
-
-    def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n in _SIM3_INTS}
-        d["s12"], d["R12"] = float(self.s12), np.array(self.R12[:], np.float32).reshape(3, 3)
-        d["t12"] = np.array(self.t12[:], np.float32)
-        return d
-
-
-SIM3_RESULT_DTYPE = np.dtype([(n, "<i4") for n in _SIM3_INTS] + [("reserved", "<i4", 2), ("s12", "<f4"), ("R12", "<f4", (3, 3)),
-                                                                 ("t12", "<f4", 3)])
-assert SIM3_RESULT_DTYPE.itemsize == ctypes.sizeof(Sim3Result) == 96
-
-SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
-_SIM3OPT_INTS = ("status", "n_correspondences", "n_bad", "n_inliers", "rounds")
-_SIM3OPT_INTS2 = ("lm_trials", "rejected_trials", "solver_failures")
-_SIM3OPT_INTS3 = ("small_theta", "small_sigma", "small_both", "reserved")
-_SIM3OPT_F64 = ("chi2_initial", "chi2_final", "lambda_")
-
-
-class Sim3OptResult(ctypes.Structure):
-    """orbx_sim3opt_result: Optimizer::OptimizeSim3's outcome for one keyframe pair (n_inliers is the design's return value)."""
-    _fields_ = ([(n, ctypes.c_int32) for n in _SIM3OPT_INTS] + [("iterations", ctypes.c_int32 * 2)] +
-                [(n, ctypes.c_int32) for n in _SIM3OPT_INTS2] + [("stop_reason", ctypes.c_int32 * 2)] +
-                [(n, ctypes.c_int32) for n in _SIM3OPT_INTS3] + [(n, ctypes.c_double) for n in _SIM3OPT_F64] +
-                [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("s", ctypes.c_double), ("s12", ctypes.c_float),
-                 ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("reserved_f", ctypes.c_float)])
-
-    def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n in _SIM3OPT_INTS + _SIM3OPT_INTS2 + _SIM3OPT_INTS3[:3]}
-        d["iterations"], d["stop_reason"] = list(self.iterations), list(self.stop_reason)
-        d.update(chi2_initial=float(self.chi2_initial), chi2_final=float(self.chi2_final), **{"lambda": float(self.lambda_)})
-        d.update(q=np.array(self.q[:]), t=np.array(self.t[:]), s=float(self.s), s12=float(self.s12),
-                 R12=np.array(self.R12[:], np.float32).reshape(3, 3), t12=np.array(self.t12[:], np.float32))
-        return d
-
-
-SIM3OPT_RESULT_DTYPE = np.dtype(
-    [(n, "<i4") for n in _SIM3OPT_INTS] + [("iterations", "<i4", 2)] + [(n, "<i4") for n in _SIM3OPT_INTS2] +
-    [("stop_reason", "<i4", 2)] + [(n, "<i4") for n in _SIM3OPT_INTS3] +
-    [(n, "<f8") for n in ("chi2_initial", "chi2_final", "lambda")] + [("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8")] +
-    [("s12", "<f4"), ("R12", "<f4", (3, 3)), ("t12", "<f4", 3), ("reserved_f", "<f4")])
-assert SIM3OPT_RESULT_DTYPE.itemsize == ctypes.sizeof(Sim3OptResult) == 208
+    return _sample_draws(rand, n_iter, 4)
 
 
 def sample_sim3_draws(rand, n_iter: int) -> np.ndarray:
     """The draws of n_iter Sim3 RANSAC hypotheses, int32 [n_iter, 3]: the next 3 * n_iter values of `rand`, as sample_pnp_draws
     takes them, in the order Sim3Solver::iterate would draw them."""
-    n_iter = int(n_iter)
-    out = np.zeros((n_iter, 3), np.int32)
-    for it in range(n_iter):
-        for j in range(3):
-            out[it, j] = int(rand())
-    return out
+    return _sample_draws(rand, n_iter, 3)
 
 
-PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
-PROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_in_image", "n_with_candidates", "n_displaced", "n_rot_removed", "rounds")
+def _libc_rand():
+    """glibc's rand(), the default random stream of PnPsolver and Sim3Solver (the reference's)."""
+    libc = ctypes.CDLL(None)
+    libc.rand.restype = ctypes.c_int
+    return libc.rand
 
-
-class ProjResult(ctypes.Structure):
-    """orbx_proj_result: ORBmatcher::SearchByProjection's counters for one pair (rounds is the device's own count)."""
-    _fields_ = [(n, ctypes.c_int32) for n in PROJ_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-PROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in PROJ_RESULT_FIELDS])
-assert PROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(ProjResult) == 32
-
-
-LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
-LOCAL_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_seen", "n_behind", "n_out_image", "n_out_distance", "n_out_angle", "n_in_view",
-                       "n_with_candidates", "n_over_th", "n_ratio_rejected", "n_displaced", "n_outliers_cleared", "rounds")
-
-
-class LocalResult(ctypes.Structure):
-    """orbx_local_result: SearchLocalPoints' counters for one (frame, map set) pair (rounds is the device's own count)."""
-    _fields_ = [(n, ctypes.c_int32) for n in LOCAL_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-LOCAL_RESULT_DTYPE = np.dtype([(n, "<i4") for n in LOCAL_RESULT_FIELDS])
-assert LOCAL_RESULT_DTYPE.itemsize == ctypes.sizeof(LocalResult) == 60
-
-
-SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
-SCW_RESULT_FIELDS = ("status", "nmatches", "n_total", "n_points", "n_found", "n_unmapped", "n_behind", "n_out_image", "n_out_distance",
-                     "n_out_angle", "n_with_candidates", "n_over_dist", "n_displaced", "rounds")
-
-
-class MatchScwResult(ctypes.Structure):
-    """orbx_scw_result: the counters of the loop-closing SearchByProjection under Scw for one (keyframe, map set) pair (rounds is
-    the device's own count; n_total is ComputeSim3's nTotalMatches)."""
-    _fields_ = [(n, ctypes.c_int32) for n in SCW_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-SCW_RESULT_DTYPE = np.dtype([(n, "<i4") for n in SCW_RESULT_FIELDS])
-assert SCW_RESULT_DTYPE.itemsize == ctypes.sizeof(MatchScwResult) == 56
 
 
 def loop_accepted(opt_res, scw_res, min_inliers: int = 20, min_total: int = 40) -> np.ndarray:
@@ -305,76 +104,6 @@ def loop_accepted(opt_res, scw_res, min_inliers: int = 20, min_total: int = 40) 
     if len(o) != len(m):
         raise OrbxError(E_BADARG, "the two result arrays must have one record per pair")
     return (o["n_inliers"] >= int(min_inliers)) & (m["n_total"] >= int(min_total))
-
-
-KFPROJ_BAD_INPUT, KFPROJ_NONFINITE = 2, 4
-KFPROJ_RESULT_FIELDS = ("status", "nmatches", "n_points", "n_found", "n_behind_kept", "n_out_image", "n_out_distance", "n_with_candidates",
-                        "n_over_dist", "n_displaced", "n_rot_removed", "n_outliers_cleared", "rounds")
-
-
-class KfProjResult(ctypes.Structure):
-    """orbx_kfproj_result: the counters of the relocalisation SearchByProjection for one (keyframe, frame) pair (rounds is the
-    device's own count)."""
-    _fields_ = [(n, ctypes.c_int32) for n in KFPROJ_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-KFPROJ_RESULT_DTYPE = np.dtype([(n, "<i4") for n in KFPROJ_RESULT_FIELDS])
-assert KFPROJ_RESULT_DTYPE.itemsize == ctypes.sizeof(KfProjResult) == 52
-
-
-MSIM3_BAD_INPUT, MSIM3_NONFINITE = 2, 4
-MSIM3_RESULT_FIELDS = ("status", "n_found", "n_points_12", "n_behind_12", "n_out_image_12", "n_out_distance_12", "n_with_candidates_12",
-                       "n_over_dist_12", "n_points_21", "n_behind_21", "n_out_image_21", "n_out_distance_21", "n_with_candidates_21",
-                       "n_over_dist_21", "n_one_sided", "reserved")
-
-
-class MatchSim3Result(ctypes.Structure):
-    """orbx_msim3_result: the counters of ORBmatcher::SearchBySim3 for one (KF1, KF2) pair, per direction."""
-    _fields_ = [(n, ctypes.c_int32) for n in MSIM3_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
-
-
-MSIM3_RESULT_DTYPE = np.dtype([(n, "<i4") for n in MSIM3_RESULT_FIELDS])
-assert MSIM3_RESULT_DTYPE.itemsize == ctypes.sizeof(MatchSim3Result) == 64
-
-
-TRI_BAD_INPUT, TRI_NONFINITE, TRI_LOW_BASELINE, TRI_ZERO_BASELINE = 2, 4, 8, 16
-TRI_MATCH_COUNTERS = ("status", "nmatches", "n_queries", "n_with_candidates", "n_epipole_rejected", "n_epiline_rejected", "n_rot_removed")
-TRI_RESULT_FIELDS = ("status", "n_matches", "n_points", "n_low_parallax", "n_w_zero", "n_behind_1", "n_behind_2", "n_reproj_1", "n_reproj_2",
-                     "n_zero_dist", "n_scale")
-
-
-class TriMatchResult(ctypes.Structure):
-    """orbx_tri_match_result: SearchForTriangulation's counters and the pair's geometry (baseline, epipole, F12 row-major)."""
-    _fields_ = [(n, ctypes.c_int32) for n in TRI_MATCH_COUNTERS] + [("baseline", ctypes.c_float), ("ex", ctypes.c_float),
-                                                                    ("ey", ctypes.c_float), ("F12", ctypes.c_float * 9)]
-
-    def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n in TRI_MATCH_COUNTERS}
-        d.update(baseline=float(self.baseline), ex=float(self.ex), ey=float(self.ey), F12=np.array(list(self.F12), np.float32).reshape(3, 3))
-        return d
-
-
-TRI_MATCH_RESULT_DTYPE = np.dtype([(n, "<i4") for n in TRI_MATCH_COUNTERS] + [("baseline", "<f4"), ("ex", "<f4"), ("ey", "<f4"),
-                                                                               ("F12", "<f4", (9,))])
-assert TRI_MATCH_RESULT_DTYPE.itemsize == ctypes.sizeof(TriMatchResult) == 76
-
-
-class TriResult(ctypes.Structure):
-    """orbx_tri_result: CreateNewMapPoints' counters for one (KF1, KF2) pair, one per gate."""
-    _fields_ = [(n, ctypes.c_int32) for n in TRI_RESULT_FIELDS]
-
-    def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-TRI_RESULT_DTYPE = np.dtype([(n, "<i4") for n in TRI_RESULT_FIELDS])
-assert TRI_RESULT_DTYPE.itemsize == ctypes.sizeof(TriResult) == 44
 
 
 def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
@@ -394,11 +123,6 @@ def sample_sets(n_matches: int, n_iter: int, rand) -> np.ndarray:
             avail[randi] = avail[-1]
             avail.pop()
     return out
-
-
-class _Stats(ctypes.Structure):
-    _fields_ = [("invalid_by_distance", ctypes.c_int32), ("invalid_by_ratio", ctypes.c_int32),
-                ("invalid_by_orientation", ctypes.c_int32)]
 
 
 def lib_path() -> str:
@@ -665,38 +389,97 @@ def _need(what: str, a, nbytes: int) -> None:
         raise ValueError("%s holds %d bytes, the call needs %d" % (what, have, nbytes))
 
 
-def _pair_lists(names, lists, n_frames: int, n_sets: int, set_what: str) -> np.ndarray:
-    """The host index lists of a match_*_pairs_device call as the rows of one int32 array [len(lists), n_pairs]: of one length, the
-    last one (the sets: `set_what` in the message) below n_sets, the others (frames) below n_frames."""
-    try:
-        m = np.ascontiguousarray(lists, np.int32)
-    except ValueError:  # (not of one shape)
-        m = None
-    if m is None or m.ndim != 2:  # each list flattened on its own: they may still be of one length
-        flat = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in lists]
-        if any(len(a) != len(flat[0]) for a in flat):
+def _pair_lists(names, lists, n_frames: Optional[int] = None, n_sets: Optional[int] = None, set_what: str = "") -> list:
+    """The host index lists of a device-resident call, each as a flat int32 array.  Of one length, else OrbxError.  With n_frames
+    the lists (but the last one when n_sets is given) must lie below it, and with n_sets the last list (the sets: `set_what` in
+    the message) below that, else ValueError; None leaves the range to the C side, which answers ORBX_E_BADARG (each method
+    keeps the check it always made)."""
+    rows = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in lists]
+    n = len(rows[0])
+    for r in rows:
+        if len(r) != n:
             raise OrbxError(E_BADARG, "%s and %s must have the same length" % (", ".join(names[:-1]), names[-1]))
-        m = np.stack(flat)
-    if m.shape[1]:
-        u = m.view(np.uint32)  # (as unsigned, a negative index is a huge one)
-        if int(u[:-1].max()) >= n_frames:
+    if n and (n_frames is not None or n_sets is not None):
+        top = [int(r.view(np.uint32).max()) for r in rows]  # (as unsigned, a negative index is a huge one)
+        if n_frames is not None and max(top if n_sets is None else top[:-1]) >= n_frames:
             raise ValueError("a pair names a frame outside the batch of %d" % n_frames)
-        if int(u[-1].max()) >= n_sets:
+        if n_sets is not None and top[-1] >= n_sets:
             raise ValueError("a pair names a %s outside the %d given" % (set_what, n_sets))
-    return m
+    return rows
+
+
+# -- the conversions of the single-problem calls: what the caller holds -> what the C ABI reads ----------------------------
+def _k9(K) -> np.ndarray:
+    return np.ascontiguousarray(K, np.float32).reshape(9)
+
+
+def _bounds(bounds) -> _Bounds:
+    return _Bounds(*[int(v) for v in bounds])
+
+
+def _keys(keys) -> np.ndarray:
+    return np.ascontiguousarray(keys, KEYPOINT_DTYPE).reshape(-1)
+
+
+def _desc(desc, n: Optional[int] = None, message: str = "") -> Optional[np.ndarray]:
+    """Descriptor rows uint8 [., 32].  With n: an optional array (None passes through) that must hold n rows."""
+    if desc is None and n is not None:
+        return None
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    if n is not None and len(d) != n:
+        raise OrbxError(E_BADARG, message)
+    return d
+
+
+def _points(points, width: int = 3) -> np.ndarray:
+    return np.ascontiguousarray(points, np.float32).reshape(-1, width)
+
+
+def _flags(flags, n: int, message: str) -> Optional[np.ndarray]:
+    """A row of n flags as uint8 (!= 0 -> 1); None passes through; another length is OrbxError(E_BADARG, message)."""
+    if flags is None:
+        return None
+    f = np.ascontiguousarray(np.asarray(flags) != 0, np.uint8).reshape(-1)
+    if len(f) != n:
+        raise OrbxError(E_BADARG, message)
+    return f
+
+
+def _row(row, n: int, message: str) -> np.ndarray:
+    """An int32 row of n entries (at least one is allocated), all -1 unless `row` gives them: then it must hold n."""
+    out = np.full(max(n, 1), -1, np.int32)
+    if row is not None:
+        given = np.asarray(row, np.int32).reshape(-1)
+        if len(given) != n:
+            raise OrbxError(E_BADARG, message)
+        out[:n] = given
+    return out
+
+
+def _per_level(table, nlevels: int, name: str) -> Optional[np.ndarray]:
+    """A float32 table with one entry per pyramid level (inv_sigma2 / sigma2); None passes through."""
+    t = None if table is None else np.ascontiguousarray(table, np.float32)
+    if t is not None and len(t) != nlevels:
+        raise OrbxError(E_BADARG, "%s must have one entry per pyramid level" % name)
+    return t
 
 
 def _pose12(Tcw) -> np.ndarray:
-    """Tcw (3x4 or 4x4) as the C ABI's pose: row-major R [9], then t [3]."""
+    """A pose (or Scw) as the C ABI takes it, row-major R [9] then t [3]: 12 floats as they are, a 3x4 or 4x4 matrix converted."""
     T = np.asarray(Tcw, np.float32)
+    if T.ndim == 1:
+        return np.ascontiguousarray(T.reshape(12))
     return np.ascontiguousarray(np.r_[T[:3, :3].reshape(9), T[:3, 3]], np.float32)
 
 
-def _scw12(Scw) -> np.ndarray:
-    """Scw (or a pose) as the C ABI takes it: 12 floats (the 3x3 row-major, then t) as they are, a 3x4 or 4x4 matrix through
-    _pose12."""
-    S = np.asarray(Scw, np.float32)
-    return np.ascontiguousarray(S.reshape(12)) if S.ndim == 1 else _pose12(S)
+def _camera_K(K, holder, who: str, what: str = "frame") -> np.ndarray:
+    """K as given, or the 3x3 of the camera `holder` (a Frame) carries; neither: OrbxError naming the caller."""
+    if K is not None:
+        return K
+    cam = getattr(holder, "camera", None)
+    if cam is None:
+        raise OrbxError(E_BADARG, "%s needs K (the %s carries no camera)" % (who, what))
+    return np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
 
 
 def _need_batch(imgs, n_frames, width, height, stride, frame_stride, kps, desc, n, capacity, first=None, second=None, matches12=None,
@@ -814,6 +597,19 @@ class ORBextractor:
             raise OrbxError(r, (self._L.orbx_last_error(self._h) or b"").decode() or what)
         return r
 
+    def _device_call(self, fn: str, *args) -> int:
+        """One device-resident C call, fn(ctx, *args), with every argument named once in the C order.  A device array (device
+        pointer or torch tensor; None where the C side takes null) goes in as (what, array, bytes the call reads or writes): each
+        one given is checked against its size (_need), the context is ordered behind torch for exactly these arrays, and the call
+        gets their pointers.  Host arrays (numpy, or None) become pointers too; everything else is passed as it is."""
+        given = [a for a in args if type(a) is tuple and a[1] is not None]
+        for a in given:
+            _need(*a)
+        self._order_torch(*[a[1] for a in given])
+        r = getattr(self._L, fn)(self._h, *[_ptr(a[1]) if type(a) is tuple else _ptr(a) if a is None or type(a) is np.ndarray else a
+                                            for a in args])
+        return self._check(r, fn)
+
     # -- getters (hpp:87-108) --------------------------------------------------------------------
     def GetLevels(self) -> int:
         return self._L.orbx_get_levels(self._h)
@@ -897,7 +693,7 @@ class ORBextractor:
                            checkOri: bool = True, capacity: Optional[int] = None) -> None:
         first = np.ascontiguousarray(first, np.int32)
         second = np.ascontiguousarray(second, np.int32)
-        b = _Bounds(*[int(v) for v in bounds])
+        b = _bounds(bounds)
         if len(first):
             nfr = int(max(first.max(), second.max())) + 1
             _need_batch(None, nfr, 0, 0, 0, 0, d_kps, d_desc, d_n, int(capacity or self.capacity), first, second, d_matches12, d_nmatches, d_stats)
@@ -915,41 +711,25 @@ class ORBextractor:
         and Vocabulary.transform_batch_device filled (same capacity): d_matches_f int32 [n_pairs, capacity] (row p: the keyframe
         feature matched to each of frame f[p]'s features, or -1), d_nmatches int32 [n_pairs]; d_kf_mask (optional) uint8
         [n_frames, capacity], 0 = the keyframe's feature has no map point.  Stream-ordered on the context's stream."""
-        kf = np.ascontiguousarray(kf, np.int32).reshape(-1)
-        f = np.ascontiguousarray(f, np.int32).reshape(-1)
-        if len(kf) != len(f):
-            raise OrbxError(E_BADARG, "kf and f must have the same length")
+        kf, f = _pair_lists(("kf", "f"), (kf, f))
         cap, nf, P = int(capacity or self.capacity), int(n_frames), len(kf)
-        _need("the keypoint array", d_kps, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
-        _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
-        _need("the FeatureVector count array", d_fv_n, nf * 4)
-        if d_kf_mask is not None:
-            _need("the keyframe mask", d_kf_mask, nf * cap)
-        _need("matches_f", d_matches_f, P * cap * 4)
-        _need("nmatches", d_nmatches, P * 4)
-        self._order_torch(d_kps, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n, d_kf_mask, d_matches_f, d_nmatches)
-        r = self._L.orbx_match_bow_batch_device(self._h, nf, P, _ptr(kf), _ptr(f), _ptr(d_kps), _ptr(d_desc), _ptr(d_n), cap,
-                                                _ptr(d_fv_node), _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_kf_mask), float(nnratio),
-                                                int(bool(checkOri)), _ptr(d_matches_f), _ptr(d_nmatches))
-        self._check(r, "orbx_match_bow_batch_device")
+        self._device_call("orbx_match_bow_batch_device", nf, P, kf, f, ("the keypoint array", d_kps, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap,
+                          ("the FeatureVector node array", d_fv_node, nf * cap * 4),
+                          ("the FeatureVector feature array", d_fv_feat, nf * cap * 4), ("the FeatureVector count array", d_fv_n, nf * 4),
+                          ("the keyframe mask", d_kf_mask, nf * cap), float(nnratio), int(bool(checkOri)),
+                          ("matches_f", d_matches_f, P * cap * 4), ("nmatches", d_nmatches, P * 4))
 
     def match_bow(self, kf_keys, kf_desc, kf_fv_node, kf_fv_feat, f_keys, f_desc, f_fv_node, f_fv_feat, kf_mask=None,
                   nnratio: float = 0.6, checkOri: bool = True):
         """SearchByBoW for one pair in host memory (orbx_match_bow) -> (matches_f int32 [len(f_keys)], nmatches).  Synchronous."""
-        kk, fk = np.ascontiguousarray(kf_keys, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(f_keys, KEYPOINT_DTYPE).reshape(-1)
-        kd, fd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(f_desc, np.uint8).reshape(-1, 32)
+        kk, fk = _keys(kf_keys), _keys(f_keys)
+        kd, fd = _desc(kf_desc), _desc(f_desc)
         kn, kft = np.ascontiguousarray(kf_fv_node, np.uint32).reshape(-1), np.ascontiguousarray(kf_fv_feat, np.uint32).reshape(-1)
         fn, fft = np.ascontiguousarray(f_fv_node, np.uint32).reshape(-1), np.ascontiguousarray(f_fv_feat, np.uint32).reshape(-1)
         if len(kk) != len(kd) or len(fk) != len(fd) or len(kn) != len(kft) or len(fn) != len(fft):
             raise OrbxError(E_BADARG, "keypoints / descriptors or FeatureVector nodes / features differ in length")
-        mask = None
-        if kf_mask is not None:
-            mask = np.ascontiguousarray(np.asarray(kf_mask) != 0, np.uint8).reshape(-1)
-            if len(mask) != len(kk):
-                raise OrbxError(E_BADARG, "the mask needs one entry per keyframe feature")
+        mask = _flags(kf_mask, len(kk), "the mask needs one entry per keyframe feature")
         m = np.full(max(len(fk), 1), -1, np.int32)
         nm = ctypes.c_int32(0)
         r = self._L.orbx_match_bow(self._h, _ptr(kk), _ptr(kd), len(kk), _ptr(kn), _ptr(kft), len(kn), _ptr(fk), _ptr(fd), len(fk),
@@ -973,52 +753,29 @@ class ORBextractor:
         cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
         last, cur, point_set = _pair_lists(("last", "cur", "point_set"), (last, cur, point_set), nf, ns, "point set")
         P = len(last)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the point array", d_points, ns * cap * 12)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, ns * cap)
-        if d_point_desc is not None:
-            _need("the point descriptor array", d_point_desc, ns * cap * 32)
-        if d_last_outlier is not None:
-            _need("the outlier array", d_last_outlier, P * cap)
-        _need("the pose array", d_pose_cur, P * 48)
-        _need("matches_cur", d_matches_cur, P * cap * 4)
-        _need("the result array", d_res, P * PROJ_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_last_outlier, d_pose_cur, d_matches_cur, d_res)
-        r = self._L.orbx_match_projection_batch_device(self._h, nf, P, _ptr(last), _ptr(cur), _ptr(point_set), _ptr(d_kps_un),
-                                                       _ptr(d_desc), _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask),
-                                                       _ptr(d_point_desc), _ptr(d_last_outlier), _ptr(d_pose_cur), _ptr(Kf),
-                                                       ctypes.byref(b), float(th), int(bool(checkOri)), _ptr(d_matches_cur), _ptr(d_res))
-        self._check(r, "orbx_match_projection_batch_device")
+        self._device_call("orbx_match_projection_batch_device", nf, P, last, cur, point_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap),
+                          ("the point descriptor array", d_point_desc, ns * cap * 32), ("the outlier array", d_last_outlier, P * cap),
+                          ("the pose array", d_pose_cur, P * 48), _k9(K), ctypes.byref(_bounds(bounds)), float(th), int(bool(checkOri)),
+                          ("matches_cur", d_matches_cur, P * cap * 4), ("the result array", d_res, P * PROJ_RESULT_DTYPE.itemsize))
 
     def match_projection(self, last_keys_un, last_desc, cur_keys_un, cur_desc, points, mask, Tcw, K, bounds: Tuple[int, int, int, int],
                          th: float = 15.0, checkOri: bool = True, point_desc=None, last_outlier=None):
         """SearchByProjection for one pair in host memory (orbx_match_projection) -> (matches_cur int32 [len(cur_keys_un)],
         ProjResult).  points [n_last, 3] and mask [n_last] (or None) are the last frame's map points, Tcw (3x4 or 4x4) the
         current frame's predicted pose.  Synchronous."""
-        lk, ck = np.ascontiguousarray(last_keys_un, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(cur_keys_un, KEYPOINT_DTYPE).reshape(-1)
-        ld, cd = np.ascontiguousarray(last_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, 32)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        lk, ck = _keys(last_keys_un), _keys(cur_keys_un)
+        ld, cd = _desc(last_desc), _desc(cur_desc)
+        pts = _points(points)
         if len(lk) != len(ld) or len(ck) != len(cd) or len(pts) != len(lk):
             raise OrbxError(E_BADARG, "keypoints / descriptors / points differ in length")
-
-        def per_feature(a, what, width=None):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, np.uint8).reshape(-1) if width is None else np.ascontiguousarray(a, np.uint8).reshape(-1, width)
-            if len(a) != len(lk):
-                raise OrbxError(E_BADARG, "%s needs one entry per feature of the last frame" % what)
-            return a
-        m = per_feature(None if mask is None else np.asarray(mask) != 0, "the mask")
-        out = per_feature(None if last_outlier is None else np.asarray(last_outlier) != 0, "last_outlier")
-        pd = per_feature(point_desc, "point_desc", 32)
+        m = _flags(mask, len(lk), "the mask needs one entry per feature of the last frame")
+        out = _flags(last_outlier, len(lk), "last_outlier needs one entry per feature of the last frame")
+        pd = _desc(point_desc, len(lk), "point_desc needs one entry per feature of the last frame")
         pose = _pose12(Tcw)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
+        Kf = _k9(K)
+        b = _bounds(bounds)
         mc = np.full(max(len(ck), 1), -1, np.int32)
         res = ProjResult()
         r = self._L.orbx_match_projection(self._h, _ptr(lk), _ptr(ld), len(lk), _ptr(ck), _ptr(cd), len(ck), _ptr(pts), _ptr(m), _ptr(pd),
@@ -1043,62 +800,34 @@ class ORBextractor:
         cap, mcap, nf, ns = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets)
         frame, map_set = _pair_lists(("frame", "map_set"), (frame, map_set), nf, ns, "map set")
         P = len(frame)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the map count array", d_map_n, ns * 4)
-        _need("the map point array", d_map_points, ns * mcap * 12)
-        _need("the map normal array", d_map_normals, ns * mcap * 12)
-        _need("the map distance array", d_map_dist, ns * mcap * 8)
-        _need("the map descriptor array", d_map_desc, ns * mcap * 32)
-        if d_map_mask is not None:
-            _need("the map mask", d_map_mask, ns * mcap)
-        if d_outlier is not None:
-            _need("the outlier array", d_outlier, P * cap)
-        if d_point_view is not None:
-            _need("point_view", d_point_view, P * mcap)
-        _need("the pose array", d_pose, P * 48)
-        _need("matches", d_matches, P * cap * 4)
-        _need("the result array", d_res, P * LOCAL_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_outlier,
-                          d_point_view, d_pose, d_matches, d_res)
-        r = self._L.orbx_match_local_map_batch_device(self._h, nf, P, _ptr(frame), _ptr(map_set), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n),
-                                                      cap, ns, mcap, _ptr(d_map_n), _ptr(d_map_points), _ptr(d_map_normals),
-                                                      _ptr(d_map_dist), _ptr(d_map_desc), _ptr(d_map_mask), _ptr(d_pose), _ptr(Kf),
-                                                      ctypes.byref(b), float(th), float(nnratio), _ptr(d_matches), _ptr(d_outlier),
-                                                      _ptr(d_point_view), _ptr(d_res))
-        self._check(r, "orbx_match_local_map_batch_device")
+        self._device_call("orbx_match_local_map_batch_device", nf, P, frame, map_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, ns, mcap,
+                          ("the map count array", d_map_n, ns * 4), ("the map point array", d_map_points, ns * mcap * 12),
+                          ("the map normal array", d_map_normals, ns * mcap * 12), ("the map distance array", d_map_dist, ns * mcap * 8),
+                          ("the map descriptor array", d_map_desc, ns * mcap * 32), ("the map mask", d_map_mask, ns * mcap),
+                          ("the pose array", d_pose, P * 48), _k9(K), ctypes.byref(_bounds(bounds)), float(th), float(nnratio),
+                          ("matches", d_matches, P * cap * 4), ("the outlier array", d_outlier, P * cap),
+                          ("point_view", d_point_view, P * mcap), ("the result array", d_res, P * LOCAL_RESULT_DTYPE.itemsize))
 
     def match_local_map(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
                         bounds: Tuple[int, int, int, int], matches=None, th: float = 1.0, nnratio: float = 0.8, outlier=None):
         """SearchLocalPoints for one frame and one local map in host memory (orbx_match_local_map) -> (matches int32
         [len(keys_un)], point_view uint8 [n_map], LocalResult).  matches (default all -1) holds the map points the frame already
         has, as indices into the map arrays; Tcw is 3x4 or 4x4.  Synchronous."""
-        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
-        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        mp = np.ascontiguousarray(map_points, np.float32).reshape(-1, 3)
-        mn = np.ascontiguousarray(map_normals, np.float32).reshape(-1, 3)
-        md = np.ascontiguousarray(map_dist, np.float32).reshape(-1, 2)
-        mdesc = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, 32)
+        k = _keys(keys_un)
+        d = _desc(desc)
+        mp = _points(map_points)
+        mn = _points(map_normals)
+        md = _points(map_dist, 2)
+        mdesc = _desc(map_desc)
         if len(k) != len(d) or not (len(mp) == len(mn) == len(md) == len(mdesc)):
             raise OrbxError(E_BADARG, "keypoints / descriptors or the map arrays differ in length")
-        mm = None if map_mask is None else np.ascontiguousarray(np.asarray(map_mask) != 0, np.uint8).reshape(-1)
-        if mm is not None and len(mm) != len(mp):
-            raise OrbxError(E_BADARG, "the map mask needs one entry per map point")
-        out = None if outlier is None else np.ascontiguousarray(np.asarray(outlier) != 0, np.uint8).reshape(-1)
-        if out is not None and len(out) != len(k):
-            raise OrbxError(E_BADARG, "outlier needs one entry per feature")
-        m = np.full(max(len(k), 1), -1, np.int32)
-        if matches is not None:
-            given = np.asarray(matches, np.int32).reshape(-1)
-            if len(given) != len(k):
-                raise OrbxError(E_BADARG, "matches needs one entry per feature")
-            m[:len(k)] = given
+        mm = _flags(map_mask, len(mp), "the map mask needs one entry per map point")
+        out = _flags(outlier, len(k), "outlier needs one entry per feature")
+        m = _row(matches, len(k), "matches needs one entry per feature")
         pose = _pose12(Tcw)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
+        Kf = _k9(K)
+        b = _bounds(bounds)
         view = np.zeros(max(len(mp), 1), np.uint8)
         res = LocalResult()
         r = self._L.orbx_match_local_map(self._h, _ptr(k), _ptr(d), len(k), len(mp), _ptr(mp), _ptr(mn), _ptr(md), _ptr(mdesc), _ptr(mm),
@@ -1124,29 +853,13 @@ class ORBextractor:
         cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
         kf, cur, point_set = _pair_lists(("kf", "cur", "point_set"), (kf, cur, point_set), nf, ns, "point set")
         P = len(kf)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the point array", d_points, ns * cap * 12)
-        _need("the point distance array", d_point_dist, ns * cap * 8)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, ns * cap)
-        if d_point_desc is not None:
-            _need("the point descriptor array", d_point_desc, ns * cap * 32)
-        if d_outlier is not None:
-            _need("the outlier array", d_outlier, P * cap)
-        _need("the pose array", d_pose, P * 48)
-        _need("matches", d_matches, P * cap * 4)
-        _need("the result array", d_res, P * KFPROJ_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_point_dist, d_outlier, d_pose, d_matches, d_res)
-        r = self._L.orbx_match_keyframe_projection_batch_device(self._h, nf, P, _ptr(kf), _ptr(cur), _ptr(point_set), _ptr(d_kps_un),
-                                                                _ptr(d_desc), _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask),
-                                                                _ptr(d_point_desc), _ptr(d_point_dist), _ptr(d_pose), _ptr(Kf),
-                                                                ctypes.byref(b), float(th), int(ORBdist), int(bool(checkOri)),
-                                                                _ptr(d_matches), _ptr(d_outlier), _ptr(d_res))
-        self._check(r, "orbx_match_keyframe_projection_batch_device")
+        self._device_call("orbx_match_keyframe_projection_batch_device", nf, P, kf, cur, point_set,
+                          ("the keypoint array", d_kps_un, nf * cap * 28), ("the descriptor array", d_desc, nf * cap * 32),
+                          ("the count array", d_n, nf * 4), cap, ns, ("the point array", d_points, ns * cap * 12),
+                          ("the point mask", d_point_mask, ns * cap), ("the point descriptor array", d_point_desc, ns * cap * 32),
+                          ("the point distance array", d_point_dist, ns * cap * 8), ("the pose array", d_pose, P * 48), _k9(K),
+                          ctypes.byref(_bounds(bounds)), float(th), int(ORBdist), int(bool(checkOri)), ("matches", d_matches, P * cap * 4),
+                          ("the outlier array", d_outlier, P * cap), ("the result array", d_res, P * KFPROJ_RESULT_DTYPE.itemsize))
 
     def match_keyframe_projection(self, kf_keys_un, kf_desc, cur_keys_un, cur_desc, points, mask, point_dist, Tcw, K,
                                   bounds: Tuple[int, int, int, int], matches=None, th: float = 10.0, ORBdist: int = 100,
@@ -1155,30 +868,19 @@ class ORBextractor:
         [len(cur_keys_un)], KfProjResult).  points [n_kf, 3], mask [n_kf] (or None) and point_dist [n_kf, 2] are the keyframe's
         map points; matches (default all -1) holds the points the current frame already has, as indices into them; Tcw (3x4 or
         4x4) is the current frame's pose.  Synchronous."""
-        kk, ck = np.ascontiguousarray(kf_keys_un, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(cur_keys_un, KEYPOINT_DTYPE).reshape(-1)
-        kd, cd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, 32)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        dst = np.ascontiguousarray(point_dist, np.float32).reshape(-1, 2)
+        kk, ck = _keys(kf_keys_un), _keys(cur_keys_un)
+        kd, cd = _desc(kf_desc), _desc(cur_desc)
+        pts = _points(points)
+        dst = _points(point_dist, 2)
         if len(kk) != len(kd) or len(ck) != len(cd) or len(pts) != len(kk) or len(dst) != len(kk):
             raise OrbxError(E_BADARG, "keypoints / descriptors / points / distances differ in length")
-        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
-        if m is not None and len(m) != len(kk):
-            raise OrbxError(E_BADARG, "the mask needs one entry per feature of the keyframe")
-        pd = None if point_desc is None else np.ascontiguousarray(point_desc, np.uint8).reshape(-1, 32)
-        if pd is not None and len(pd) != len(kk):
-            raise OrbxError(E_BADARG, "point_desc needs one entry per feature of the keyframe")
-        out = None if outlier is None else np.ascontiguousarray(np.asarray(outlier) != 0, np.uint8).reshape(-1)
-        if out is not None and len(out) != len(ck):
-            raise OrbxError(E_BADARG, "outlier needs one entry per feature of the current frame")
-        mc = np.full(max(len(ck), 1), -1, np.int32)
-        if matches is not None:
-            given = np.asarray(matches, np.int32).reshape(-1)
-            if len(given) != len(ck):
-                raise OrbxError(E_BADARG, "matches needs one entry per feature of the current frame")
-            mc[:len(ck)] = given
+        m = _flags(mask, len(kk), "the mask needs one entry per feature of the keyframe")
+        pd = _desc(point_desc, len(kk), "point_desc needs one entry per feature of the keyframe")
+        out = _flags(outlier, len(ck), "outlier needs one entry per feature of the current frame")
+        mc = _row(matches, len(ck), "matches needs one entry per feature of the current frame")
         pose = _pose12(Tcw)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
+        Kf = _k9(K)
+        b = _bounds(bounds)
         res = KfProjResult()
         r = self._L.orbx_match_keyframe_projection(self._h, _ptr(kk), _ptr(kd), len(kk), _ptr(ck), _ptr(cd), len(ck), _ptr(pts), _ptr(m),
                                                    _ptr(pd), _ptr(dst), _ptr(pose), _ptr(Kf), ctypes.byref(b), float(th), int(ORBdist),
@@ -1198,32 +900,18 @@ class ORBextractor:
         solver's d_match_inliers): KF1's feature -> KF2's feature, or -1.  d_res [n_pairs] MSIM3_RESULT_DTYPE records (64 bytes).
         Stream-ordered on the context's stream."""
         cap, nf, ns = int(capacity or self.capacity), int(n_frames), int(n_point_sets)
-        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
-        set1, set2 = self._tri_pairs(set1, set2, ns)
+        kf1, kf2 = _pair_lists(("kf1", "kf2"), (kf1, kf2), nf)  # (two lists at a time, as this method always checked them)
+        set1, set2 = _pair_lists(("set1", "set2"), (set1, set2), ns)
         P = len(kf1)
         if len(set1) != P:
             raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the point array", d_points, ns * cap * 12)
-        _need("the point distance array", d_point_dist, ns * cap * 8)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, ns * cap)
-        if d_point_desc is not None:
-            _need("the point descriptor array", d_point_desc, ns * cap * 32)
-        _need("the pose array", d_pose, nf * 48)
-        _need("the similarity array", d_sim3, P * 52)
-        _need("matches", d_matches, P * cap * 4)
-        _need("the result array", d_res, P * MSIM3_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_points, d_point_mask, d_point_desc, d_point_dist, d_pose, d_sim3, d_matches, d_res)
-        r = self._L.orbx_match_sim3_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2), _ptr(d_kps_un), _ptr(d_desc),
-                                                 _ptr(d_n), cap, ns, _ptr(d_points), _ptr(d_point_mask), _ptr(d_point_desc),
-                                                 _ptr(d_point_dist), _ptr(d_pose), _ptr(d_sim3), _ptr(Kf), ctypes.byref(b), float(th),
-                                                 int(ORBdist), _ptr(d_matches), _ptr(d_res))
-        self._check(r, "orbx_match_sim3_batch_device")
+        self._device_call("orbx_match_sim3_batch_device", nf, P, kf1, kf2, set1, set2, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap),
+                          ("the point descriptor array", d_point_desc, ns * cap * 32),
+                          ("the point distance array", d_point_dist, ns * cap * 8), ("the pose array", d_pose, nf * 48),
+                          ("the similarity array", d_sim3, P * 52), _k9(K), ctypes.byref(_bounds(bounds)), float(th), int(ORBdist),
+                          ("matches", d_matches, P * cap * 4), ("the result array", d_res, P * MSIM3_RESULT_DTYPE.itemsize))
 
     def compute_sim3_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets: int, d_points,
                                   d_point_mask, d_point_dist, d_pose, K, bounds: Tuple[int, int, int, int], d_draws, d_sim3_res, d_sim3,
@@ -1243,44 +931,28 @@ class ORBextractor:
                    point_desc2=None):
         """SearchBySim3 for one pair in host memory (orbx_match_sim3) -> (matches12 int32 [n1], MatchSim3Result).  sim3 [13]: R12
         row-major, t12, s12; matches12 (default all -1): the matches the pair already has.  Synchronous."""
-        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
-        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
-        p1, p2 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3), np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
-        q1, q2 = np.ascontiguousarray(point_dist1, np.float32).reshape(-1, 2), np.ascontiguousarray(point_dist2, np.float32).reshape(-1, 2)
+        k1, k2 = _keys(keys_un1), _keys(keys_un2)
+        d1, d2 = _desc(desc1), _desc(desc2)
+        p1, p2 = _points(points1), _points(points2)
+        q1, q2 = _points(point_dist1, 2), _points(point_dist2, 2)
         if not (len(k1) == len(d1) == len(p1) == len(q1)) or not (len(k2) == len(d2) == len(p2) == len(q2)):
             raise OrbxError(E_BADARG, "keypoints / descriptors / points / distances differ in length")
         if (mask1 is None) != (mask2 is None) or (point_desc1 is None) != (point_desc2 is None):
             raise OrbxError(E_BADARG, "the masks, and the point descriptors, are given together or not at all")
         opt = lambda a, n, w: None if a is None else np.ascontiguousarray(a, np.uint8).reshape(n, *w)  # noqa: E731
-        m1, m2 = (None if m is None else np.ascontiguousarray(np.asarray(m) != 0, np.uint8).reshape(-1) for m in (mask1, mask2))
-        if m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2)):
-            raise OrbxError(E_BADARG, "a mask needs one entry per feature of its keyframe")
+        m1, m2 = (_flags(m, len(k), "a mask needs one entry per feature of its keyframe") for m, k in ((mask1, k1), (mask2, k2)))
         pd1, pd2 = opt(point_desc1, len(k1), (32,)), opt(point_desc2, len(k2), (32,))
-        row = np.full(max(len(k1), 1), -1, np.int32)
-        if matches12 is not None:
-            given = np.asarray(matches12, np.int32).reshape(-1)
-            if len(given) != len(k1):
-                raise OrbxError(E_BADARG, "matches12 needs one entry per feature of KF1")
-            row[:len(k1)] = given
+        row = _row(matches12, len(k1), "matches12 needs one entry per feature of KF1")
         T1, T2 = _pose12(Tcw1), _pose12(Tcw2)
         sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
+        Kf = _k9(K)
+        b = _bounds(bounds)
         res = MatchSim3Result()
         r = self._L.orbx_match_sim3(self._h, _ptr(k1), _ptr(d1), len(k1), _ptr(p1), _ptr(m1), _ptr(pd1), _ptr(q1), _ptr(T1), _ptr(k2),
                                     _ptr(d2), len(k2), _ptr(p2), _ptr(m2), _ptr(pd2), _ptr(q2), _ptr(T2), _ptr(sim), _ptr(Kf),
                                     ctypes.byref(b), float(th), int(ORBdist), _ptr(row), ctypes.byref(res))
         self._check(r, "orbx_match_sim3")
         return row[:len(k1)].copy(), res
-
-    def _tri_pairs(self, kf1, kf2, n_frames: int):
-        kf1 = np.ascontiguousarray(kf1, np.int32).reshape(-1)
-        kf2 = np.ascontiguousarray(kf2, np.int32).reshape(-1)
-        if len(kf1) != len(kf2):
-            raise OrbxError(E_BADARG, "kf1 and kf2 must have the same length")
-        if len(kf1) and int(np.maximum(kf1.view(np.uint32), kf2.view(np.uint32)).max()) >= n_frames:
-            raise ValueError("a pair names a frame outside the batch of %d" % n_frames)
-        return kf1, kf2
 
     def match_triangulation_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_desc, d_n, d_fv_node,
                                          d_fv_feat, d_fv_n, d_pose, K, d_matches12, d_res, d_mask=None, d_median_depth=None,
@@ -1292,28 +964,15 @@ class ORBextractor:
         bytes).  Optional: d_mask uint8 [n_frames, capacity] (!= 0 = the feature already has a map point), d_median_depth float32
         [n_frames] (the baseline gate).  Stream-ordered on the context's stream."""
         cap, nf = int(capacity or self.capacity), int(n_frames)
-        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
+        kf1, kf2 = _pair_lists(("kf1", "kf2"), (kf1, kf2), nf)
         P = len(kf1)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
-        _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
-        _need("the FeatureVector count array", d_fv_n, nf * 4)
-        _need("the pose array", d_pose, nf * 48)
-        if d_mask is not None:
-            _need("the mask", d_mask, nf * cap)
-        if d_median_depth is not None:
-            _need("the median depth array", d_median_depth, nf * 4)
-        _need("matches12", d_matches12, P * cap * 4)
-        _need("the result array", d_res, P * TRI_MATCH_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_fv_node, d_fv_feat, d_fv_n, d_pose, d_mask, d_median_depth, d_matches12, d_res)
-        r = self._L.orbx_match_triangulation_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n),
-                                                          cap, _ptr(d_fv_node), _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_mask), _ptr(d_pose),
-                                                          _ptr(Kf), _ptr(d_median_depth), int(bool(checkOri)), _ptr(d_matches12),
-                                                          _ptr(d_res))
-        self._check(r, "orbx_match_triangulation_batch_device")
+        self._device_call("orbx_match_triangulation_batch_device", nf, P, kf1, kf2, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap,
+                          ("the FeatureVector node array", d_fv_node, nf * cap * 4),
+                          ("the FeatureVector feature array", d_fv_feat, nf * cap * 4), ("the FeatureVector count array", d_fv_n, nf * 4),
+                          ("the mask", d_mask, nf * cap), ("the pose array", d_pose, nf * 48), _k9(K),
+                          ("the median depth array", d_median_depth, nf * 4), int(bool(checkOri)), ("matches12", d_matches12, P * cap * 4),
+                          ("the result array", d_res, P * TRI_MATCH_RESULT_DTYPE.itemsize))
 
     def triangulate_matches_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_n, d_pose, K, d_matches12,
                                          d_points, d_point_mask, d_point_normal, d_point_dist, d_res,
@@ -1324,23 +983,13 @@ class ORBextractor:
         (mfMinDistance, mfMaxDistance) is a point set indexed by kf1's feature, as match_keyframe_projection_pairs_device and
         pose_optimize_batch_device read one.  d_res [n_pairs] TRI_RESULT_DTYPE records (44 bytes).  Stream-ordered."""
         cap, nf = int(capacity or self.capacity), int(n_frames)
-        kf1, kf2 = self._tri_pairs(kf1, kf2, nf)
+        kf1, kf2 = _pair_lists(("kf1", "kf2"), (kf1, kf2), nf)
         P = len(kf1)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the count array", d_n, nf * 4)
-        _need("the pose array", d_pose, nf * 48)
-        _need("matches12", d_matches12, P * cap * 4)
-        _need("the point array", d_points, P * cap * 12)
-        _need("the point mask", d_point_mask, P * cap)
-        _need("the point normal array", d_point_normal, P * cap * 12)
-        _need("the point distance array", d_point_dist, P * cap * 8)
-        _need("the result array", d_res, P * TRI_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_n, d_pose, d_matches12, d_points, d_point_mask, d_point_normal, d_point_dist, d_res)
-        r = self._L.orbx_triangulate_matches_batch_device(self._h, nf, P, _ptr(kf1), _ptr(kf2), _ptr(d_kps_un), _ptr(d_n), cap,
-                                                          _ptr(d_pose), _ptr(Kf), _ptr(d_matches12), _ptr(d_points), _ptr(d_point_mask),
-                                                          _ptr(d_point_normal), _ptr(d_point_dist), _ptr(d_res))
-        self._check(r, "orbx_triangulate_matches_batch_device")
+        self._device_call("orbx_triangulate_matches_batch_device", nf, P, kf1, kf2, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("the pose array", d_pose, nf * 48), _k9(K),
+                          ("matches12", d_matches12, P * cap * 4), ("the point array", d_points, P * cap * 12),
+                          ("the point mask", d_point_mask, P * cap), ("the point normal array", d_point_normal, P * cap * 12),
+                          ("the point distance array", d_point_dist, P * cap * 8), ("the result array", d_res, P * TRI_RESULT_DTYPE.itemsize))
 
     def create_new_map_points_pairs_device(self, n_frames: int, kf1: np.ndarray, kf2: np.ndarray, d_kps_un, d_desc, d_n, d_fv_node,
                                            d_fv_feat, d_fv_n, d_pose, K, d_matches12, d_match_res, d_points, d_point_mask,
@@ -1358,20 +1007,15 @@ class ORBextractor:
                             mask2=None, median_depth2: float = 0.0, checkOri: bool = True):
         """SearchForTriangulation for one pair in host memory (orbx_match_triangulation) -> (matches12 int32 [len(keys_un1)],
         TriMatchResult).  Synchronous."""
-        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
-        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        k1, k2 = _keys(keys_un1), _keys(keys_un2)
+        d1, d2 = _desc(desc1), _desc(desc2)
         n1, t1 = np.ascontiguousarray(fv_node1, np.uint32).reshape(-1), np.ascontiguousarray(fv_feat1, np.uint32).reshape(-1)
         n2, t2 = np.ascontiguousarray(fv_node2, np.uint32).reshape(-1), np.ascontiguousarray(fv_feat2, np.uint32).reshape(-1)
         if len(k1) != len(d1) or len(k2) != len(d2) or len(n1) != len(t1) or len(n2) != len(t2):
             raise OrbxError(E_BADARG, "keypoints / descriptors or FeatureVector nodes / features differ in length")
-        masks = []
-        for mk, k in ((mask1, k1), (mask2, k2)):
-            m = None if mk is None else np.ascontiguousarray(np.asarray(mk) != 0, np.uint8).reshape(-1)
-            if m is not None and len(m) != len(k):
-                raise OrbxError(E_BADARG, "a mask needs one entry per feature of its keyframe")
-            masks.append(m)
+        masks = [_flags(m, len(k), "a mask needs one entry per feature of its keyframe") for m, k in ((mask1, k1), (mask2, k2))]
         p1, p2 = _pose12(Tcw1), _pose12(Tcw2)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        Kf = _k9(K)
         m12 = np.full(max(len(k1), 1), -1, np.int32)
         res = TriMatchResult()
         r = self._L.orbx_match_triangulation(self._h, _ptr(k1), _ptr(d1), len(k1), _ptr(n1), _ptr(t1), len(n1), _ptr(masks[0]), _ptr(p1),
@@ -1383,14 +1027,14 @@ class ORBextractor:
     def triangulate_matches(self, keys_un1, Tcw1, keys_un2, Tcw2, K, matches12):
         """CreateNewMapPoints' triangulation for one pair in host memory (orbx_triangulate_matches) -> (points [n1, 3], mask [n1],
         normals [n1, 3], dist [n1, 2], TriResult).  Synchronous."""
-        k1, k2 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1), np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
+        k1, k2 = _keys(keys_un1), _keys(keys_un2)
         m12 = np.ascontiguousarray(matches12, np.int32).reshape(-1)
         if len(m12) != len(k1):
             raise OrbxError(E_BADARG, "matches12 needs one entry per feature of the first keyframe")
         n = max(len(k1), 1)
         pts, msk, nrm, dst = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
         p1, p2 = _pose12(Tcw1), _pose12(Tcw2)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        Kf = _k9(K)
         res = TriResult()
         r = self._L.orbx_triangulate_matches(self._h, _ptr(k1), len(k1), _ptr(p1), _ptr(k2), len(k2), _ptr(p2), _ptr(Kf), _ptr(m12),
                                              _ptr(pts), _ptr(msk), _ptr(nrm), _ptr(dst), ctypes.byref(res))
@@ -1413,10 +1057,8 @@ class ORBextractor:
         entries cleared as Relocalization clears them.  -> (stage int32 [n_pairs] the last stage the pair ran, nGood int32
         [n_pairs], d_pose float32 [n_pairs, 12], d_matches)."""
         import torch
-        kf, cur, point_set = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (kf, cur, point_set))
+        kf, cur, point_set = _pair_lists(("kf", "cur", "point_set"), (kf, cur, point_set))
         cap, P = int(capacity or self.capacity), len(kf)
-        if len(cur) != P or len(point_set) != P:
-            raise OrbxError(E_BADARG, "kf, cur and point_set must have the same length")
         _need("the pose array", d_pose0, P * 48)
         _need("matches", d_matches, P * cap * 4)
         dev = d_matches.device
@@ -1573,15 +1215,18 @@ class ORBextractor:
 
     def to_gray_batch_device(self, d_src, n_frames: int, width: int, height: int, stride: int, frame_stride: int, channels: int,
                              bRGB: bool, d_gray, gray_stride: int, gray_frame_stride: int) -> None:
-        self._order_torch(d_src, d_gray)
-        self._check(self._L.orbx_to_gray_batch_device(self._h, int(n_frames), _ptr(d_src), int(width), int(height), int(stride),
-                                                      int(frame_stride), int(channels), int(bool(bRGB)), _ptr(d_gray),
-                                                      int(gray_stride), int(gray_frame_stride)), "orbx_to_gray_batch_device")
+        nf, w, h, ch = int(n_frames), int(width), int(height), int(channels)
+        some = nf > 0 and h > 0  # (the last frame's last row ends the bytes the call touches)
+        self._device_call("orbx_to_gray_batch_device", nf,
+                          ("the source frames", d_src, (nf - 1) * int(frame_stride) + (h - 1) * int(stride) + w * ch if some else 0), w, h,
+                          int(stride), int(frame_stride), ch, int(bool(bRGB)),
+                          ("the gray frames", d_gray, (nf - 1) * int(gray_frame_stride) + (h - 1) * int(gray_stride) + w if some else 0),
+                          int(gray_stride), int(gray_frame_stride))
 
     # -- Frame::UndistortKeyPoints / ComputeImageBounds (SlamTypes/Frame.cpp:101-161) ----------------
     def undistort_keypoints(self, kps: np.ndarray, camera: Sequence[float]) -> np.ndarray:
         """mvKeysUn from mvKeys; camera = (fx, fy, cx, cy, k1, k2, p1, p2)."""
-        kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+        kps = _keys(kps)
         out = np.zeros(len(kps), KEYPOINT_DTYPE)
         cam = _Camera(*[float(v) for v in camera])
         self._check(self._L.orbx_undistort_keypoints(self._h, _ptr(kps), len(kps), ctypes.byref(cam), _ptr(out)),
@@ -1590,11 +1235,9 @@ class ORBextractor:
 
     def undistort_batch_device(self, n_frames: int, d_kps, d_n, camera: Sequence[float], d_kps_un,
                                capacity: Optional[int] = None) -> None:
-        cam = _Camera(*[float(v) for v in camera])
-        self._order_torch(d_kps, d_n, d_kps_un)
-        self._check(self._L.orbx_undistort_batch_device(self._h, int(n_frames), _ptr(d_kps), _ptr(d_n),
-                                                        int(capacity or self.capacity), ctypes.byref(cam), _ptr(d_kps_un)),
-                    "orbx_undistort_batch_device")
+        cap, nf = int(capacity or self.capacity), int(n_frames)
+        self._device_call("orbx_undistort_batch_device", nf, ("the keypoint array", d_kps, nf * cap * 28), ("the count array", d_n, nf * 4),
+                          cap, ctypes.byref(_Camera(*[float(v) for v in camera])), ("the undistorted keypoint array", d_kps_un, nf * cap * 28))
 
     def image_bounds(self, camera: Sequence[float], width: int, height: int) -> Tuple[int, int, int, int]:
         cam = _Camera(*[float(v) for v in camera])
@@ -1606,8 +1249,8 @@ class ORBextractor:
     # -- Initializer::CheckHomography / CheckFundamental (Initialization/Initializer.cpp:268-438) ------
     def _check_models(self, kind: int, M21, M12, keys1, keys2, matches12, sigma: float):
         M21 = np.ascontiguousarray(M21, np.float32).reshape(-1, 3, 3)
-        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        k1 = _keys(keys1)
+        k2 = _keys(keys2)
         m12 = np.ascontiguousarray(matches12, np.int32)
         if len(m12) != len(k1):
             raise OrbxError(E_BADARG, "matches12 must have one entry per keypoint of frame 1")
@@ -1639,10 +1282,10 @@ class ORBextractor:
         """Initializer::CheckRT (Initializer.cpp:569-713) for a stack of (R21, t21) hypotheses ->
         (nGood[m], vbTriGood[m, n1], vP3D[m, n1, 3], parallax[m])."""
         R21 = np.ascontiguousarray(R21, np.float32).reshape(-1, 3, 3)
-        t21 = np.ascontiguousarray(t21, np.float32).reshape(-1, 3)
+        t21 = _points(t21)
         K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
-        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        k1 = _keys(keys1)
+        k2 = _keys(keys2)
         m12 = np.ascontiguousarray(matches12, np.int32)
         inl = np.ascontiguousarray(matches_inliers, np.uint8)
         nm = len(R21)
@@ -1661,8 +1304,8 @@ class ORBextractor:
         """One pair from host memory: mvKeys1 / mvKeys2 (mvKeysUn), vnMatches12 (one entry per keypoint of frame 1), mvSets
         [n_iter, 8] (sample_sets).  Returns (HFResult, inliers [2, N] bool: the kept H's, then F's, vbMatchesInliers); with
         debug=True also every hypothesis (models [3, n_iter, 3, 3] = H21, H12, F21) and its score (scores [2, n_iter])."""
-        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        k1 = _keys(keys1)
+        k2 = _keys(keys2)
         m12 = np.ascontiguousarray(matches12, np.int32)
         sets = np.ascontiguousarray(sets, np.int32)
         if len(m12) != len(k1):
@@ -1690,30 +1333,14 @@ class ORBextractor:
         d_inliers uint8 [n_pairs, 2, capacity], d_models float32 [3, n_pairs, n_iter, 9], d_scores float32 [2, n_pairs, n_iter]
         are optional.  n_iter: from d_sets' shape when it is a [n_pairs, n_iter, 8] tensor, else required.  Stream-ordered on the
         context's stream: the outputs are valid after a device synchronisation (torch.cuda.synchronize())."""
-        first = np.ascontiguousarray(first, np.int32)
-        second = np.ascontiguousarray(second, np.int32)
-        cap = int(capacity or self.capacity)
-        P = len(first)
-        if len(second) != P:
-            raise OrbxError(E_BADARG, "first and second must have the same length")
+        first, second = _pair_lists(("first", "second"), (first, second))
+        cap, nf, P = int(capacity or self.capacity), int(n_frames), len(first)
         n_iter = self._n_iter(d_sets, P, n_iter)
-        n_frames = int(n_frames)
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        _need("matches12", d_matches12, P * cap * 4)
-        _need("the sets", d_sets, P * n_iter * 32)
-        _need("the result array", d_res, P * HF_RESULT_DTYPE.itemsize)
-        if d_inliers is not None:
-            _need("the inlier array", d_inliers, P * 2 * cap)
-        if d_models is not None:
-            _need("the model array", d_models, 3 * P * n_iter * 36)
-        if d_scores is not None:
-            _need("the score array", d_scores, 2 * P * n_iter * 4)
-        self._order_torch(d_kps_un, d_n, d_matches12, d_sets, d_res, d_inliers, d_models, d_scores)
-        self._check(self._L.orbx_find_models_batch_device(self._h, n_frames, P, _ptr(first), _ptr(second), _ptr(d_kps_un), _ptr(d_n), cap,
-                                                          _ptr(d_matches12), n_iter, _ptr(d_sets), float(sigma), _ptr(d_res),
-                                                          _ptr(d_inliers), _ptr(d_models), _ptr(d_scores)),
-                    "orbx_find_models_batch_device")
+        self._device_call("orbx_find_models_batch_device", nf, P, first, second, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("matches12", d_matches12, P * cap * 4), n_iter,
+                          ("the sets", d_sets, P * n_iter * 32), float(sigma), ("the result array", d_res, P * HF_RESULT_DTYPE.itemsize),
+                          ("the inlier array", d_inliers, P * 2 * cap), ("the model array", d_models, 3 * P * n_iter * 36),
+                          ("the score array", d_scores, 2 * P * n_iter * 4))
 
     @staticmethod
     def _n_iter(d_sets, n_pairs: int, n_iter: Optional[int]) -> int:
@@ -1730,11 +1357,11 @@ class ORBextractor:
     def initialize(self, keys1, keys2, matches12, sets, K, sigma: float = 1.0, min_parallax: float = 1.0, min_triangulated: int = 50):
         """One pair from host memory: mvKeys1 / mvKeys2 (mvKeysUn), vnMatches12, mvSets [n_iter, 8] (sample_sets), K 3x3.  Returns
         (InitResult, vP3D [n1, 3] float32, vbTriangulated [n1] bool); result.status == 0 is Initialize's `true`."""
-        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        k1 = _keys(keys1)
+        k2 = _keys(keys2)
         m12 = np.ascontiguousarray(matches12, np.int32)
         sets = np.ascontiguousarray(sets, np.int32)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        Kf = _k9(K)
         if len(m12) != len(k1):
             raise OrbxError(E_BADARG, "matches12 must have one entry per keypoint of frame 1")
         if sets.ndim != 2 or sets.shape[1] != 8:
@@ -1753,50 +1380,33 @@ class ORBextractor:
         """Batched and device-resident (device pointers or torch tensors), the layout of find_models_batch_device; d_res
         [n_pairs] INIT_RESULT_DTYPE records (184 bytes), d_p3d float32 [n_pairs, capacity, 3] and d_triangulated uint8
         [n_pairs, capacity] optional.  Stream-ordered: the outputs are valid after a device synchronisation."""
-        first = np.ascontiguousarray(first, np.int32)
-        second = np.ascontiguousarray(second, np.int32)
-        cap = int(capacity or self.capacity)
-        P = len(first)
-        if len(second) != P:
-            raise OrbxError(E_BADARG, "first and second must have the same length")
+        first, second = _pair_lists(("first", "second"), (first, second))
+        cap, nf, P = int(capacity or self.capacity), int(n_frames), len(first)
         n_iter = self._n_iter(d_sets, P, n_iter)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        n_frames = int(n_frames)
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        _need("matches12", d_matches12, P * cap * 4)
-        _need("the sets", d_sets, P * n_iter * 32)
-        _need("the result array", d_res, P * INIT_RESULT_DTYPE.itemsize)
-        if d_p3d is not None:
-            _need("the point array", d_p3d, P * cap * 12)
-        if d_triangulated is not None:
-            _need("the triangulated array", d_triangulated, P * cap)
-        self._order_torch(d_kps_un, d_n, d_matches12, d_sets, d_res, d_p3d, d_triangulated)
-        self._check(self._L.orbx_initialize_batch_device(self._h, n_frames, P, _ptr(first), _ptr(second), _ptr(d_kps_un), _ptr(d_n), cap,
-                                                         _ptr(d_matches12), n_iter, _ptr(d_sets), _ptr(Kf), float(sigma),
-                                                         float(min_parallax), int(min_triangulated), _ptr(d_res), _ptr(d_p3d),
-                                                         _ptr(d_triangulated)), "orbx_initialize_batch_device")
+        self._device_call("orbx_initialize_batch_device", nf, P, first, second, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("matches12", d_matches12, P * cap * 4), n_iter,
+                          ("the sets", d_sets, P * n_iter * 32), _k9(K), float(sigma), float(min_parallax), int(min_triangulated),
+                          ("the result array", d_res, P * INIT_RESULT_DTYPE.itemsize), ("the point array", d_p3d, P * cap * 12),
+                          ("the triangulated array", d_triangulated, P * cap))
 
     # -- two-view bundle adjustment behind the Initializer (include/orbx.h) ------------------------------
     def bundle_adjust(self, keys1, keys2, matches12, init_res, p3d, triangulated, K, inv_sigma2=None, n_iterations: int = 20,
                       min_points: int = 100, normalize: bool = True):
         """One pair from host memory: what initialize() took and returned (its InitResult, vP3D, vbTriangulated).  Returns
         (BAResult, refined vP3D [n1, 3] float32); result.status == 0 is an accepted initial map."""
-        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+        k1 = _keys(keys1)
+        k2 = _keys(keys2)
         m12 = np.ascontiguousarray(matches12, np.int32)
-        pts = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+        pts = _points(p3d)
         tri = np.ascontiguousarray(np.asarray(triangulated) != 0, np.uint8)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        Kf = _k9(K)
         if len(m12) != len(k1) or len(pts) != len(k1) or len(tri) != len(k1):
             raise OrbxError(E_BADARG, "matches12, p3d and triangulated must have one entry per keypoint of frame 1")
         if isinstance(init_res, InitResult):
             ir = init_res
         else:
             ir = InitResult.from_buffer_copy(np.ascontiguousarray(init_res, INIT_RESULT_DTYPE).tobytes())
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
         res = BAResult()
         out = np.zeros((max(len(k1), 1), 3), np.float32)
         self._check(self._L.orbx_bundle_adjust(self._h, _ptr(k1), len(k1), _ptr(k2), len(k2), _ptr(m12), ctypes.byref(ir), _ptr(pts),
@@ -1817,10 +1427,8 @@ class ORBextractor:
             raise OrbxError(E_BADARG, "first and second must have the same length")
         if d_p3d_out is None:
             d_p3d_out = d_p3d
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        Kf = _k9(K)
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
         n_frames = int(n_frames)
         _need_batch(None, n_frames, 0, 0, 0, 0, d_kps_un, None, d_n, cap, first, second, d_matches12, None, None, init_res=d_init_res,
                     p3d=d_p3d, triangulated=d_triangulated, ba_res=d_res, p3d_out=d_p3d_out)
@@ -1836,16 +1444,14 @@ class ORBextractor:
         """One problem from host memory: the frame's mvKeysUn, one map point per feature (points [n, 3], mask [n] or None = every
         feature has one), the start pose Tcw (3x4 or 4x4) and K.  Returns (PoseResult, vbOutlier [n] bool); result.n_inliers is
         the reference design's return value."""
-        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
-        if len(pts) != len(k) or (m is not None and len(m) != len(k)):
+        k = _keys(keys_un)
+        pts = _points(points)
+        m = _flags(mask, len(k), "points and mask must have one entry per keypoint of the frame")
+        if len(pts) != len(k):
             raise OrbxError(E_BADARG, "points and mask must have one entry per keypoint of the frame")
         pose0 = _pose12(Tcw)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        Kf = _k9(K)
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
         res = PoseResult()
         out = np.zeros(max(len(k), 1), np.uint8)
         self._check(self._L.orbx_pose_optimize(self._h, _ptr(k), len(k), _ptr(pts), _ptr(m), _ptr(pose0), _ptr(Kf), _ptr(sig),
@@ -1860,30 +1466,14 @@ class ORBextractor:
         d_match int32 [n_problems, capacity] is match_bow_batch_device's d_matches_f (the point sets are then the keyframes' map
         points), or None = feature j's point is entry j.  d_res [n_problems] POSE_RESULT_DTYPE records (192 bytes), d_outlier
         uint8 [n_problems, capacity].  Stream-ordered: the outputs are valid after a device synchronisation."""
-        frame = np.ascontiguousarray(frame, np.int32)
-        point_set = np.ascontiguousarray(point_set, np.int32)
-        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
-        if len(point_set) != P:
-            raise OrbxError(E_BADARG, "frame and point_set must have the same length")
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        if d_match is not None:
-            _need("the match array", d_match, P * cap * 4)
-        _need("the point array", d_points, n_point_sets * cap * 12)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, n_point_sets * cap)
-        _need("the pose array", d_pose0, P * 48)
-        _need("the result array", d_res, P * POSE_RESULT_DTYPE.itemsize)
-        _need("the outlier array", d_outlier, P * cap)
-        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_pose0, d_res, d_outlier)
-        self._check(self._L.orbx_pose_optimize_batch_device(self._h, n_frames, P, _ptr(frame), _ptr(point_set), _ptr(d_kps_un), _ptr(d_n),
-                                                            cap, _ptr(d_match), n_point_sets, _ptr(d_points), _ptr(d_point_mask),
-                                                            _ptr(d_pose0), _ptr(Kf), _ptr(sig), int(n_iterations), _ptr(d_res),
-                                                            _ptr(d_outlier)), "orbx_pose_optimize_batch_device")
+        frame, point_set = _pair_lists(("frame", "point_set"), (frame, point_set))
+        cap, P, nf, ns = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
+        self._device_call("orbx_pose_optimize_batch_device", nf, P, frame, point_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("the match array", d_match, P * cap * 4), ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap),
+                          ("the pose array", d_pose0, P * 48), _k9(K), sig, int(n_iterations),
+                          ("the result array", d_res, P * POSE_RESULT_DTYPE.itemsize), ("the outlier array", d_outlier, P * cap))
 
     # -- PnPsolver behind SearchByBoW (include/orbx.h, "behind SearchByBoW: PnP RANSAC") ------------------------
     def pnp_solve(self, keys_un, points, mask, K, draws, sigma2=None, probability: float = 0.99, min_inliers: int = 10,
@@ -1891,16 +1481,14 @@ class ORBextractor:
         """One problem from host memory: the frame's mvKeysUn, one map point per feature (points [n, 3], mask [n] or None = every
         feature has one), K and the draws int32 [n_iter, 4] (sample_pnp_draws).  One call is the solver's whole life: up to
         min(n_iter, mRansacMaxIts) iterations.  Returns (PnpResult, vbInliers [n] bool)."""
-        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
-        if len(pts) != len(k) or (m is not None and len(m) != len(k)):
+        k = _keys(keys_un)
+        pts = _points(points)
+        m = _flags(mask, len(k), "points and mask must have one entry per keypoint of the frame")
+        if len(pts) != len(k):
             raise OrbxError(E_BADARG, "points and mask must have one entry per keypoint of the frame")
         d = np.ascontiguousarray(draws, np.int32).reshape(-1, 4)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        Kf = _k9(K)
+        sig = _per_level(sigma2, self.nlevels, "sigma2")
         res = PnpResult()
         out = np.zeros(max(len(k), 1), np.uint8)
         self._check(self._L.orbx_pnp_solve(self._h, _ptr(k), len(k), _ptr(pts), _ptr(m), _ptr(Kf), _ptr(sig), float(probability),
@@ -1917,39 +1505,25 @@ class ORBextractor:
         Outputs: d_res [n_problems] PNP_RESULT_DTYPE records (200 bytes), d_pose float32 [n_problems, 12] and d_match_inliers int32
         [n_problems, capacity] -- pose_optimize_batch_device's d_pose0 and d_match for the same lists --, d_inliers uint8
         [n_problems, capacity] or None.  Stream-ordered: the outputs are valid after a device synchronisation."""
-        frame = np.ascontiguousarray(frame, np.int32)
-        point_set = np.ascontiguousarray(point_set, np.int32)
-        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
-        if len(point_set) != P:
-            raise OrbxError(E_BADARG, "frame and point_set must have the same length")
+        frame, point_set = _pair_lists(("frame", "point_set"), (frame, point_set))
+        cap, P, nf, ns = int(capacity or self.capacity), len(frame), int(n_frames), int(n_point_sets)
+        n_iter = self._draws_n_iter(d_draws, P, 4, n_iter)
+        sig = _per_level(sigma2, self.nlevels, "sigma2")
+        self._device_call("orbx_pnp_solve_batch_device", nf, P, frame, point_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("the match array", d_match, P * cap * 4), ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap), _k9(K), sig,
+                          float(probability), int(min_inliers), int(max_iterations), float(epsilon), float(th2), n_iter,
+                          ("the draws", d_draws, P * max(n_iter, 0) * 16), ("the result array", d_res, P * PNP_RESULT_DTYPE.itemsize),
+                          ("the pose array", d_pose, P * 48), ("the inlier match array", d_match_inliers, P * cap * 4),
+                          ("the inlier flags", d_inliers, P * cap))
+
+    @staticmethod
+    def _draws_n_iter(d_draws, n_problems: int, width: int, n_iter: Optional[int]) -> int:
+        """n_iter as given, or from the size of d_draws int32 [n_problems, n_iter, width] (0 for a raw pointer)."""
         if n_iter is None:
             nbytes = _nbytes(d_draws)
-            n_iter = nbytes // (16 * P) if P and nbytes is not None else 0
-        n_iter = int(n_iter)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        if d_match is not None:
-            _need("the match array", d_match, P * cap * 4)
-        _need("the point array", d_points, n_point_sets * cap * 12)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, n_point_sets * cap)
-        _need("the draws", d_draws, P * max(n_iter, 0) * 16)
-        _need("the result array", d_res, P * PNP_RESULT_DTYPE.itemsize)
-        _need("the pose array", d_pose, P * 48)
-        _need("the inlier match array", d_match_inliers, P * cap * 4)
-        if d_inliers is not None:
-            _need("the inlier flags", d_inliers, P * cap)
-        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_draws, d_res, d_pose, d_match_inliers, d_inliers)
-        self._check(self._L.orbx_pnp_solve_batch_device(self._h, n_frames, P, _ptr(frame), _ptr(point_set), _ptr(d_kps_un), _ptr(d_n),
-                                                        cap, _ptr(d_match), n_point_sets, _ptr(d_points), _ptr(d_point_mask),
-                                                        _ptr(Kf), _ptr(sig), float(probability), int(min_inliers),
-                                                        int(max_iterations), float(epsilon), float(th2), n_iter, _ptr(d_draws),
-                                                        _ptr(d_res), _ptr(d_pose), _ptr(d_match_inliers), _ptr(d_inliers)),
-                    "orbx_pnp_solve_batch_device")
+            n_iter = nbytes // (4 * width * n_problems) if n_problems and nbytes is not None else 0
+        return int(n_iter)
 
     # -- Sim3Solver of loop closing (include/orbx.h, "loop closing: Sim3 RANSAC") ----------------------------------
     def sim3_solve(self, keys_un1, points1, mask1, pose1, keys_un2, points2, mask2, pose2, match12, K, draws, sigma2=None,
@@ -1959,23 +1533,21 @@ class ORBextractor:
         masks None = every feature has one), its pose Tcw (12 floats: R row-major, then t), the row match12 [n1] (KF2's feature
         matched to KF1's, or -1), K and the draws int32 [n_iter, 3] (sample_sim3_draws).  One call is the solver's whole life.
         Returns (Sim3Result, sim3 [13] float32 = R12, t12, s12, the inlier row [n1] int32, vbInliers [n1] bool)."""
-        k1 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1)
-        k2 = np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
-        p1 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3)
-        p2 = np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
+        k1 = _keys(keys_un1)
+        k2 = _keys(keys_un2)
+        p1 = _points(points1)
+        p2 = _points(points2)
         if (mask1 is None) != (mask2 is None):
             raise OrbxError(E_BADARG, "the two masks are given together or not at all")
-        m1 = None if mask1 is None else np.ascontiguousarray(np.asarray(mask1) != 0, np.uint8).reshape(-1)
-        m2 = None if mask2 is None else np.ascontiguousarray(np.asarray(mask2) != 0, np.uint8).reshape(-1)
+        message = "points, mask and match12 must have one entry per keypoint of their keyframe"
+        m1, m2 = _flags(mask1, len(k1), message), _flags(mask2, len(k2), message)
         row = np.ascontiguousarray(match12, np.int32).reshape(-1)
-        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1) or (m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2))):
-            raise OrbxError(E_BADARG, "points, mask and match12 must have one entry per keypoint of their keyframe")
+        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1):
+            raise OrbxError(E_BADARG, message)
         T1, T2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (pose1, pose2))
         d = np.ascontiguousarray(draws, np.int32).reshape(-1, 3)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
+        Kf = _k9(K)
+        sig = _per_level(sigma2, self.nlevels, "sigma2")
         res, sim = Sim3Result(), np.zeros(13, np.float32)
         out_row, out = np.full(max(len(k1), 1), -1, np.int32), np.zeros(max(len(k1), 1), np.uint8)
         self._check(self._L.orbx_sim3_solve(self._h, _ptr(k1), len(k1), _ptr(p1), _ptr(m1), _ptr(T1), _ptr(k2), len(k2), _ptr(p2),
@@ -1995,39 +1567,17 @@ class ORBextractor:
         int32 [n_problems, n_iter, 3] (n_iter: default from its size).  Outputs: d_res [n_problems] SIM3_RESULT_DTYPE records (96
         bytes), d_sim3 float32 [n_problems, 13] (R12, t12, s12), d_match_inliers int32 [n_problems, capacity], d_inliers uint8
         [n_problems, capacity] or None.  Stream-ordered: the outputs are valid after a device synchronisation."""
-        kf1, kf2 = np.ascontiguousarray(kf1, np.int32), np.ascontiguousarray(kf2, np.int32)
-        set1, set2 = np.ascontiguousarray(set1, np.int32), np.ascontiguousarray(set2, np.int32)
-        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
-        if len(kf2) != P or len(set1) != P or len(set2) != P:
-            raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
-        if n_iter is None:
-            nbytes = _nbytes(d_draws)
-            n_iter = nbytes // (12 * P) if P and nbytes is not None else 0
-        n_iter = int(n_iter)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if sigma2 is None else np.ascontiguousarray(sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "sigma2 must have one entry per pyramid level")
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        _need("the match array", d_match, P * cap * 4)
-        _need("the point array", d_points, n_point_sets * cap * 12)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, n_point_sets * cap)
-        _need("the pose array", d_pose, n_frames * 48)
-        _need("the draws", d_draws, P * max(n_iter, 0) * 12)
-        _need("the result array", d_res, P * SIM3_RESULT_DTYPE.itemsize)
-        _need("the similarity array", d_sim3, P * 52)
-        _need("the inlier match array", d_match_inliers, P * cap * 4)
-        if d_inliers is not None:
-            _need("the inlier flags", d_inliers, P * cap)
-        self._order_torch(d_kps_un, d_n, d_match, d_points, d_point_mask, d_pose, d_draws, d_res, d_sim3, d_match_inliers, d_inliers)
-        self._check(self._L.orbx_sim3_solve_batch_device(self._h, n_frames, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2),
-                                                         _ptr(d_kps_un), _ptr(d_n), cap, _ptr(d_match), n_point_sets, _ptr(d_points),
-                                                         _ptr(d_point_mask), _ptr(d_pose), _ptr(Kf), _ptr(sig), int(bool(fix_scale)),
-                                                         float(probability), int(min_inliers), int(max_iterations), float(th2),
-                                                         n_iter, _ptr(d_draws), _ptr(d_res), _ptr(d_sim3), _ptr(d_match_inliers),
-                                                         _ptr(d_inliers)), "orbx_sim3_solve_batch_device")
+        kf1, kf2, set1, set2 = _pair_lists(("kf1", "kf2", "set1", "set2"), (kf1, kf2, set1, set2))
+        cap, P, nf, ns = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
+        n_iter = self._draws_n_iter(d_draws, P, 3, n_iter)
+        sig = _per_level(sigma2, self.nlevels, "sigma2")
+        self._device_call("orbx_sim3_solve_batch_device", nf, P, kf1, kf2, set1, set2, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("the match array", d_match, P * cap * 4), ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap),
+                          ("the pose array", d_pose, nf * 48), _k9(K), sig, int(bool(fix_scale)), float(probability), int(min_inliers),
+                          int(max_iterations), float(th2), n_iter, ("the draws", d_draws, P * max(n_iter, 0) * 12),
+                          ("the result array", d_res, P * SIM3_RESULT_DTYPE.itemsize), ("the similarity array", d_sim3, P * 52),
+                          ("the inlier match array", d_match_inliers, P * cap * 4), ("the inlier flags", d_inliers, P * cap))
 
     # -- Optimizer::OptimizeSim3 of loop closing (include/orbx.h, "loop closing: Sim3 optimisation") ----------------
     def optimize_sim3(self, keys_un1, points1, mask1, pose1, keys_un2, points2, mask2, pose2, matches12, sim3, K, inv_sigma2=None,
@@ -2036,23 +1586,21 @@ class ORBextractor:
         [n, 3], mask [n]; both masks None = every feature has one), its pose Tcw (12 floats), the row matches12 [n1] (KF2's
         feature matched to KF1's, or -1: vpMatches1), the start similarity sim3 [13] (R12, t12, s12) and K.  Returns
         (Sim3OptResult, sim3 [13] float32, the edited row [n1] int32: removed entries are -1)."""
-        k1 = np.ascontiguousarray(keys_un1, KEYPOINT_DTYPE).reshape(-1)
-        k2 = np.ascontiguousarray(keys_un2, KEYPOINT_DTYPE).reshape(-1)
-        p1 = np.ascontiguousarray(points1, np.float32).reshape(-1, 3)
-        p2 = np.ascontiguousarray(points2, np.float32).reshape(-1, 3)
+        k1 = _keys(keys_un1)
+        k2 = _keys(keys_un2)
+        p1 = _points(points1)
+        p2 = _points(points2)
         if (mask1 is None) != (mask2 is None):
             raise OrbxError(E_BADARG, "the two masks are given together or not at all")
-        m1 = None if mask1 is None else np.ascontiguousarray(np.asarray(mask1) != 0, np.uint8).reshape(-1)
-        m2 = None if mask2 is None else np.ascontiguousarray(np.asarray(mask2) != 0, np.uint8).reshape(-1)
+        message = "points, mask and matches12 must have one entry per keypoint of their keyframe"
+        m1, m2 = _flags(mask1, len(k1), message), _flags(mask2, len(k2), message)
         row = np.array(matches12, np.int32).reshape(-1)  # (a copy: edited in place)
-        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1) or (m1 is not None and (len(m1) != len(k1) or len(m2) != len(k2))):
-            raise OrbxError(E_BADARG, "points, mask and matches12 must have one entry per keypoint of their keyframe")
+        if len(p1) != len(k1) or len(p2) != len(k2) or len(row) != len(k1):
+            raise OrbxError(E_BADARG, message)
         T1, T2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (pose1, pose2))
         sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
+        Kf = _k9(K)
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
         res, out = Sim3OptResult(), np.zeros(13, np.float32)
         if len(row) == 0:
             row = np.full(1, -1, np.int32)
@@ -2071,34 +1619,16 @@ class ORBextractor:
         row d_matches[p] (int32 [n_problems, capacity], as match_sim3_pairs_device leaves it), which is edited in place: a removed
         correspondence becomes -1.  Outputs: d_res [n_problems] SIM3OPT_RESULT_DTYPE records (208 bytes); d_sim3_out float32
         [n_problems, 13], default d_sim3 itself.  Stream-ordered: valid after a device synchronisation."""
-        kf1, kf2 = np.ascontiguousarray(kf1, np.int32), np.ascontiguousarray(kf2, np.int32)
-        set1, set2 = np.ascontiguousarray(set1, np.int32), np.ascontiguousarray(set2, np.int32)
-        cap, P, n_frames, n_point_sets = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
-        if len(kf2) != P or len(set1) != P or len(set2) != P:
-            raise OrbxError(E_BADARG, "kf1, kf2, set1 and set2 must have the same length")
-        if d_sim3_out is None:
-            d_sim3_out = d_sim3
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        sig = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
-        if sig is not None and len(sig) != self.nlevels:
-            raise OrbxError(E_BADARG, "inv_sigma2 must have one entry per pyramid level")
-        _need("the keypoint array", d_kps_un, n_frames * cap * 28)
-        _need("the count array", d_n, n_frames * 4)
-        _need("the match array", d_matches, P * cap * 4)
-        _need("the point array", d_points, n_point_sets * cap * 12)
-        if d_point_mask is not None:
-            _need("the point mask", d_point_mask, n_point_sets * cap)
-        _need("the pose array", d_pose, n_frames * 48)
-        _need("the similarity array", d_sim3, P * 52)
-        _need("the result array", d_res, P * SIM3OPT_RESULT_DTYPE.itemsize)
-        _need("the output similarity array", d_sim3_out, P * 52)
-        self._order_torch(d_kps_un, d_n, d_matches, d_points, d_point_mask, d_pose, d_sim3, d_res, d_sim3_out)
-        self._check(self._L.orbx_optimize_sim3_batch_device(self._h, n_frames, P, _ptr(kf1), _ptr(kf2), _ptr(set1), _ptr(set2),
-                                                            _ptr(d_kps_un), _ptr(d_n), cap, _ptr(d_matches), n_point_sets,
-                                                            _ptr(d_points), _ptr(d_point_mask), _ptr(d_pose), _ptr(d_sim3), _ptr(Kf),
-                                                            _ptr(sig), int(bool(fix_scale)), float(th2), int(n_iterations),
-                                                            int(n_more_iterations), _ptr(d_res), _ptr(d_sim3_out)),
-                    "orbx_optimize_sim3_batch_device")
+        kf1, kf2, set1, set2 = _pair_lists(("kf1", "kf2", "set1", "set2"), (kf1, kf2, set1, set2))
+        cap, P, nf, ns = int(capacity or self.capacity), len(kf1), int(n_frames), int(n_point_sets)
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
+        self._device_call("orbx_optimize_sim3_batch_device", nf, P, kf1, kf2, set1, set2, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the count array", d_n, nf * 4), cap, ("the match array", d_matches, P * cap * 4), ns,
+                          ("the point array", d_points, ns * cap * 12), ("the point mask", d_point_mask, ns * cap),
+                          ("the pose array", d_pose, nf * 48), ("the similarity array", d_sim3, P * 52), _k9(K), sig,
+                          int(bool(fix_scale)), float(th2), int(n_iterations), int(n_more_iterations),
+                          ("the result array", d_res, P * SIM3OPT_RESULT_DTYPE.itemsize),
+                          ("the output similarity array", d_sim3 if d_sim3_out is None else d_sim3_out, P * 52))
 
     def compute_sim3_optimized_pairs_device(self, n_frames: int, kf1, kf2, set1, set2, d_kps_un, d_desc, d_n, d_match, n_point_sets: int,
                                             d_points, d_point_mask, d_point_dist, d_pose, K, bounds: Tuple[int, int, int, int], d_draws,
@@ -2124,17 +1654,13 @@ class ORBextractor:
         s12, keyframe 1 the current one) and the matched keyframe's pose d_pose[kf2[p]] (float32 [n_frames, 12]).  A pair without
         a similarity gets twelve zeros.  Stream-ordered on the context's stream."""
         kf2 = np.ascontiguousarray(kf2, np.int32).reshape(-1)
-        P, n_frames = len(kf2), int(n_frames)
-        _need("the pose array", d_pose, n_frames * 48)
-        _need("the similarity array", d_sim3, P * 52)
-        _need("the Scw array", d_scw, P * 48)
-        self._order_torch(d_pose, d_sim3, d_scw)
-        self._check(self._L.orbx_sim3_compose_scw_batch_device(self._h, n_frames, P, _ptr(kf2), _ptr(d_pose), _ptr(d_sim3), _ptr(d_scw)),
-                    "orbx_sim3_compose_scw_batch_device")
+        P, nf = len(kf2), int(n_frames)
+        self._device_call("orbx_sim3_compose_scw_batch_device", nf, P, kf2, ("the pose array", d_pose, nf * 48),
+                          ("the similarity array", d_sim3, P * 52), ("the Scw array", d_scw, P * 48))
 
     def sim3_compose_scw(self, pose2, sim3) -> np.ndarray:
         """One pair from host memory: pose2 (Tmw, 12 floats or 3x4 / 4x4), sim3 [13] -> Scw [12] float32.  Synchronous."""
-        T2 = _scw12(pose2)  # (12 floats as they are, a matrix as R [9] then t [3])
+        T2 = _pose12(pose2)  # (12 floats as they are, a matrix as R [9] then t [3])
         sim = np.ascontiguousarray(sim3, np.float32).reshape(13)
         out = np.zeros(12, np.float32)
         self._check(self._L.orbx_sim3_compose_scw(self._h, _ptr(T2), _ptr(sim), _ptr(out)), "orbx_sim3_compose_scw")
@@ -2154,57 +1680,35 @@ class ORBextractor:
         cap, mcap, nf, ns = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets)
         kf, map_set = _pair_lists(("kf", "map_set"), (kf, map_set), nf, ns, "map set")
         P = len(kf)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
-        _need("the keypoint array", d_kps_un, nf * cap * 28)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the map count array", d_map_n, ns * 4)
-        _need("the map point array", d_map_points, ns * mcap * 12)
-        _need("the map normal array", d_map_normals, ns * mcap * 12)
-        _need("the map distance array", d_map_dist, ns * mcap * 8)
-        _need("the map descriptor array", d_map_desc, ns * mcap * 32)
-        if d_map_mask is not None:
-            _need("the map mask", d_map_mask, ns * mcap)
-        if d_kf2_to_map is not None:
-            _need("the table from the matched keyframe's features to the map set", d_kf2_to_map, P * cap * 4)
-        _need("the Scw array", d_scw, P * 48)
-        _need("matches", d_matches, P * cap * 4)
-        _need("the result array", d_res, P * SCW_RESULT_DTYPE.itemsize)
-        self._order_torch(d_kps_un, d_desc, d_n, d_map_n, d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_scw,
-                          d_kf2_to_map, d_matches, d_res)
-        r = self._L.orbx_match_scw_batch_device(self._h, nf, P, _ptr(kf), _ptr(map_set), _ptr(d_kps_un), _ptr(d_desc), _ptr(d_n), cap, ns,
-                                                mcap, _ptr(d_map_n), _ptr(d_map_points), _ptr(d_map_normals), _ptr(d_map_dist),
-                                                _ptr(d_map_desc), _ptr(d_map_mask), _ptr(d_scw), _ptr(Kf), ctypes.byref(b), float(th),
-                                                int(th_low), _ptr(d_matches), _ptr(d_kf2_to_map), _ptr(d_res))
-        self._check(r, "orbx_match_scw_batch_device")
+        self._device_call("orbx_match_scw_batch_device", nf, P, kf, map_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, ns, mcap,
+                          ("the map count array", d_map_n, ns * 4), ("the map point array", d_map_points, ns * mcap * 12),
+                          ("the map normal array", d_map_normals, ns * mcap * 12), ("the map distance array", d_map_dist, ns * mcap * 8),
+                          ("the map descriptor array", d_map_desc, ns * mcap * 32), ("the map mask", d_map_mask, ns * mcap),
+                          ("the Scw array", d_scw, P * 48), _k9(K), ctypes.byref(_bounds(bounds)), float(th), int(th_low),
+                          ("matches", d_matches, P * cap * 4),
+                          ("the table from the matched keyframe's features to the map set", d_kf2_to_map, P * cap * 4),
+                          ("the result array", d_res, P * SCW_RESULT_DTYPE.itemsize))
 
     def match_scw(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K,
                   bounds: Tuple[int, int, int, int], matches=None, th: float = 10.0, th_low: int = 50, kf2_to_map=None):
         """The same for one keyframe and one map set in host memory (orbx_match_scw) -> (matches int32 [len(keys_un)],
         MatchScwResult).  Scw: 12 floats (sR row-major, then t) or a 3x4 / 4x4 matrix; matches (default all -1): vpMatched as
         indices into the map arrays, or with kf2_to_map as the matched keyframe's feature indices.  Synchronous."""
-        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE).reshape(-1)
-        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        mp = np.ascontiguousarray(map_points, np.float32).reshape(-1, 3)
-        mn = np.ascontiguousarray(map_normals, np.float32).reshape(-1, 3)
-        md = np.ascontiguousarray(map_dist, np.float32).reshape(-1, 2)
-        mdesc = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, 32)
+        k = _keys(keys_un)
+        d = _desc(desc)
+        mp = _points(map_points)
+        mn = _points(map_normals)
+        md = _points(map_dist, 2)
+        mdesc = _desc(map_desc)
         if len(k) != len(d) or not (len(mp) == len(mn) == len(md) == len(mdesc)):
             raise OrbxError(E_BADARG, "keypoints / descriptors or the map arrays differ in length")
-        mm = None if map_mask is None else np.ascontiguousarray(np.asarray(map_mask) != 0, np.uint8).reshape(-1)
-        if mm is not None and len(mm) != len(mp):
-            raise OrbxError(E_BADARG, "the map mask needs one entry per map point")
-        m = np.full(max(len(k), 1), -1, np.int32)
-        if matches is not None:
-            given = np.asarray(matches, np.int32).reshape(-1)
-            if len(given) != len(k):
-                raise OrbxError(E_BADARG, "matches needs one entry per feature")
-            m[:len(k)] = given
+        mm = _flags(map_mask, len(mp), "the map mask needs one entry per map point")
+        m = _row(matches, len(k), "matches needs one entry per feature")
         tab = None if kf2_to_map is None else np.ascontiguousarray(kf2_to_map, np.int32).reshape(-1)
-        S = _scw12(Scw)
-        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
-        b = _Bounds(*[int(v) for v in bounds])
+        S = _pose12(Scw)
+        Kf = _k9(K)
+        b = _bounds(bounds)
         res = MatchScwResult()
         r = self._L.orbx_match_scw(self._h, _ptr(k), _ptr(d), len(k), len(mp), _ptr(mp), _ptr(mn), _ptr(md), _ptr(mdesc), _ptr(mm),
                                    _ptr(S), _ptr(Kf), ctypes.byref(b), float(th), int(th_low), _ptr(m), _ptr(tab),
@@ -2281,7 +1785,7 @@ class ORBextractor:
     def debug_distribute_device(self, xyr: np.ndarray, min_x: int, max_x: int, min_y: int, max_y: int, n_features: int,
                                 variant: int = 0) -> np.ndarray:
         """The device selection kernels on caller-supplied, row-major ordered candidates (test hook)."""
-        xyr = np.ascontiguousarray(xyr, np.float32).reshape(-1, 3)
+        xyr = _points(xyr)
         out = np.zeros((max(n_features, 1), 3), np.float32)
         r = self._check(self._L.orbx_debug_distribute_device(self._h, _ptr(xyr), len(xyr), min_x, max_x, min_y, max_y,
                                                              n_features, variant, _ptr(out), len(out)))
@@ -2388,7 +1892,7 @@ class Vocabulary:
         parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
         n = len(parent)
         is_leaf = np.ascontiguousarray(is_leaf, np.int32).reshape(-1)
-        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        desc = _desc(desc)
         weight = np.ascontiguousarray(weight, np.float64).reshape(-1)
         if len(is_leaf) != n or len(desc) != n or len(weight) != n:
             raise OrbxError(E_BADARG, "parent, is_leaf, desc and weight must describe the same nodes")
@@ -2417,7 +1921,7 @@ class Vocabulary:
         if docs is not None:
             if d_desc is not None or d_n is not None:
                 raise OrbxError(E_BADARG, "either docs or d_desc / d_n")
-            arrs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
+            arrs = [_desc(d) for d in docs]
             doc_n = np.array([len(a) for a in arrs], np.int32)
             cat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 32), np.uint8))
             fw = np.zeros(max(len(cat), 1), np.uint32) if feat_word else None
@@ -2430,14 +1934,9 @@ class Vocabulary:
             if d_desc is None or d_n is None or n_docs is None:
                 raise OrbxError(E_BADARG, "the device form needs d_desc, d_n and n_docs")
             cap, nd = int(capacity or extractor.capacity), int(n_docs)
-            _need("the descriptor array", d_desc, nd * cap * 32)
-            _need("the count array", d_n, nd * 4)
-            if d_feat_word is not None:
-                _need("the feature word array", d_feat_word, nd * cap * 4)
-            extractor._order_torch(d_desc, d_n, d_feat_word)
-            extractor._check(extractor._L.orbx_vocabulary_train_device(extractor._h, int(k), int(L), int(scoring), int(weighting), int(seed),
-                                                                       int(max_rounds), nd, _ptr(d_desc), _ptr(d_n), cap, ctypes.byref(h),
-                                                                       _ptr(stats), _ptr(d_feat_word)), "orbx_vocabulary_train_device")
+            extractor._device_call("orbx_vocabulary_train_device", int(k), int(L), int(scoring), int(weighting), int(seed), int(max_rounds),
+                                   nd, ("the descriptor array", d_desc, nd * cap * 32), ("the count array", d_n, nd * 4), cap,
+                                   ctypes.byref(h), stats, ("the feature word array", d_feat_word, nd * cap * 4))
         v = cls(extractor, h)
         v.train_stats = dict(zip(cls.TRAIN_STATS, (int(x) for x in stats)))
         v.train_feat_word = fw
@@ -2476,7 +1975,7 @@ class Vocabulary:
     def transform(self, descriptors, levelsup: int = 4, feature_vector: bool = True, feat_word: bool = False) -> BowResult:
         """transform(features, BowVector&, FeatureVector&, levelsup) of one frame's descriptors [n, 32] from host memory
         (feature_vector=False: the two-argument transform, fv_* None).  Synchronous."""
-        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        d = _desc(descriptors)
         n = len(d)
         m = max(n, 1)
         bw, bv, fn, ff, fw = np.zeros(m, np.uint32), np.zeros(m, np.float64), np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint32)
@@ -2506,42 +2005,24 @@ class Vocabulary:
         uint32 / d_feat_word uint32, all [n_frames, capacity], d_bow_n / d_fv_n int32 [n_frames]; d_fv_* (all three or none) and
         d_feat_word optional.  Stream-ordered on the context's stream: the outputs are valid after a device synchronisation."""
         cap, nf = int(capacity or self._ext.capacity), int(n_frames)
-        _need("the descriptor array", d_desc, nf * cap * 32)
-        _need("the count array", d_n, nf * 4)
-        _need("the word array", d_bow_word, nf * cap * 4)
-        _need("the value array", d_bow_value, nf * cap * 8)
-        _need("the BowVector count array", d_bow_n, nf * 4)
         if (d_fv_node is None) != (d_fv_feat is None) or (d_fv_node is None) != (d_fv_n is None):
             raise OrbxError(E_BADARG, "d_fv_node, d_fv_feat and d_fv_n go together")
-        if d_fv_node is not None:
-            _need("the FeatureVector node array", d_fv_node, nf * cap * 4)
-            _need("the FeatureVector feature array", d_fv_feat, nf * cap * 4)
-            _need("the FeatureVector count array", d_fv_n, nf * 4)
-        if d_feat_word is not None:
-            _need("the feature word array", d_feat_word, nf * cap * 4)
-        self._ext._order_torch(d_desc, d_n, d_bow_word, d_bow_value, d_bow_n, d_fv_node, d_fv_feat, d_fv_n, d_feat_word)
-        self._ext._check(self._L.orbx_bow_transform_batch_device(self._ext._h, self._h, nf, _ptr(d_desc), _ptr(d_n), cap, int(levelsup),
-                                                                 _ptr(d_bow_word), _ptr(d_bow_value), _ptr(d_bow_n), _ptr(d_fv_node),
-                                                                 _ptr(d_fv_feat), _ptr(d_fv_n), _ptr(d_feat_word)),
-                         "orbx_bow_transform_batch_device")
+        self._ext._device_call("orbx_bow_transform_batch_device", self._h, nf, ("the descriptor array", d_desc, nf * cap * 32),
+                               ("the count array", d_n, nf * 4), cap, int(levelsup), ("the word array", d_bow_word, nf * cap * 4),
+                               ("the value array", d_bow_value, nf * cap * 8), ("the BowVector count array", d_bow_n, nf * 4),
+                               ("the FeatureVector node array", d_fv_node, nf * cap * 4),
+                               ("the FeatureVector feature array", d_fv_feat, nf * cap * 4),
+                               ("the FeatureVector count array", d_fv_n, nf * 4), ("the feature word array", d_feat_word, nf * cap * 4))
 
     def score_pairs_device(self, n_frames: int, first, second, d_bow_word, d_bow_value, d_bow_n, d_score,
                            capacity: Optional[int] = None) -> None:
         """L1Scoring::score of frame first[p] vs second[p] (host index arrays) of transform_batch_device's BowVectors (same
         capacity) into d_score float64 [n_pairs].  Stream-ordered like the transform."""
-        first = np.ascontiguousarray(first, np.int32).reshape(-1)
-        second = np.ascontiguousarray(second, np.int32).reshape(-1)
-        if len(first) != len(second):
-            raise OrbxError(E_BADARG, "first and second must have the same length")
+        first, second = _pair_lists(("first", "second"), (first, second))
         cap, nf, P = int(capacity or self._ext.capacity), int(n_frames), len(first)
-        _need("the word array", d_bow_word, nf * cap * 4)
-        _need("the value array", d_bow_value, nf * cap * 8)
-        _need("the BowVector count array", d_bow_n, nf * 4)
-        _need("the score array", d_score, P * 8)
-        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n, d_score)
-        self._ext._check(self._L.orbx_bow_score_batch_device(self._ext._h, self._h, nf, P, _ptr(first), _ptr(second), _ptr(d_bow_word),
-                                                             _ptr(d_bow_value), _ptr(d_bow_n), cap, _ptr(d_score)),
-                         "orbx_bow_score_batch_device")
+        self._ext._device_call("orbx_bow_score_batch_device", self._h, nf, P, first, second, ("the word array", d_bow_word, nf * cap * 4),
+                               ("the value array", d_bow_value, nf * cap * 8), ("the BowVector count array", d_bow_n, nf * 4), cap,
+                               ("the score array", d_score, P * 8))
 
 
 DB_MAX_RESULTS = 256  # ORBX_DB_MAX_RESULTS: the longest result list of a database query
@@ -2618,14 +2099,10 @@ class Database:
         uint32 / d_bow_value float64 [n_frames, capacity], d_bow_n int32 [n_frames] -> the first frame's entry id (frame f is
         entry first + f).  Stream-ordered on the context's stream."""
         cap, nf = int(capacity or self._ext.capacity), int(n_frames)
-        _need("the word array", d_bow_word, nf * cap * 4)
-        _need("the value array", d_bow_value, nf * cap * 8)
-        _need("the BowVector count array", d_bow_n, nf * 4)
-        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n)
         first = ctypes.c_int32(0)
-        self._ext._check(self._L.orbx_database_add_batch_device(self._ext._h, self._h, nf, _ptr(d_bow_word), _ptr(d_bow_value),
-                                                                _ptr(d_bow_n), cap, ctypes.byref(first)),
-                         "orbx_database_add_batch_device")
+        self._ext._device_call("orbx_database_add_batch_device", self._h, nf, ("the word array", d_bow_word, nf * cap * 4),
+                               ("the value array", d_bow_value, nf * cap * 8), ("the BowVector count array", d_bow_n, nf * 4), cap,
+                               ctypes.byref(first))
         return first.value
 
     def query_batch_device(self, n_queries: int, d_bow_word, d_bow_value, d_bow_n, d_res_entry, d_res_score, d_res_n,
@@ -2634,17 +2111,10 @@ class Database:
         [n_queries, max_results] best first, d_res_n int32 [n_queries] the entries written for each query; nothing beyond them is
         written.  Stream-ordered on the context's stream: the results are valid after a device synchronisation."""
         cap, nq, m = int(capacity or self._ext.capacity), int(n_queries), max(int(max_results), 0)
-        _need("the word array", d_bow_word, nq * cap * 4)
-        _need("the value array", d_bow_value, nq * cap * 8)
-        _need("the BowVector count array", d_bow_n, nq * 4)
-        _need("the result entry array", d_res_entry, nq * m * 4)
-        _need("the result score array", d_res_score, nq * m * 8)
-        _need("the result count array", d_res_n, nq * 4)
-        self._ext._order_torch(d_bow_word, d_bow_value, d_bow_n, d_res_entry, d_res_score, d_res_n)
-        self._ext._check(self._L.orbx_database_query_batch_device(self._ext._h, self._h, nq, _ptr(d_bow_word), _ptr(d_bow_value),
-                                                                  _ptr(d_bow_n), cap, int(max_results), int(max_id), _ptr(d_res_entry),
-                                                                  _ptr(d_res_score), _ptr(d_res_n)),
-                         "orbx_database_query_batch_device")
+        self._ext._device_call("orbx_database_query_batch_device", self._h, nq, ("the word array", d_bow_word, nq * cap * 4),
+                               ("the value array", d_bow_value, nq * cap * 8), ("the BowVector count array", d_bow_n, nq * 4), cap,
+                               int(max_results), int(max_id), ("the result entry array", d_res_entry, nq * m * 4),
+                               ("the result score array", d_res_score, nq * m * 8), ("the result count array", d_res_n, nq * 4))
 
     def inverted_file(self):
         """Diagnostic readback (orbx_database_get_inverted_file): (row_start uint32 [words + 1], post_entry uint32, post_value
@@ -2687,8 +2157,8 @@ class Frame:
         f = cls.__new__(cls)
         f.mTimestamp, f.mpORBextractor = 0.0, None
         f.mpORBvocabulary, f.mBowVec, f.mFeatVec = voc, {}, {}
-        f.mvKeys = f.mvKeysUn = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
-        f.mDescriptors = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        f.mvKeys = f.mvKeysUn = _keys(keys)
+        f.mDescriptors = _desc(descriptors)
         f.N = len(f.mvKeysUn)
         f.bounds = tuple(int(v) for v in bounds)
         return f
@@ -2709,6 +2179,13 @@ class Frame:
         self._bow_computed = True  # (both vectors may be empty: ORBmatcher.SearchByBoW asks whether this has run)
 
 
+def _flat_feature_vector(fv):
+    """mFeatVec {node id: [feature indices]} as the two parallel uint32 arrays of the C ABI, in ascending node order."""
+    node = [n for n in sorted(fv) for _ in fv[n]]
+    feat = [j for n in sorted(fv) for j in fv[n]]
+    return np.asarray(node, np.uint32), np.asarray(feat, np.uint32)
+
+
 class ORBmatcher:
     """Features/ORBmatcher.hpp:13-61."""
 
@@ -2720,18 +2197,22 @@ class ORBmatcher:
         self._ext = extractor
         self.last_stats = None
 
-    def SearchForInitialization(self, F1: Frame, F2: Frame, windowSize: int = 100):
-        """Returns (nmatches, vnMatches12).  nmatches keeps the reference's double-decrement quirk (cpp:95-98,130-138)."""
-        ext = self._ext or F1.mpORBextractor or F2.mpORBextractor
+    def _extractor(self, *frames) -> ORBextractor:
+        ext = self._ext or next((f.mpORBextractor for f in frames if f.mpORBextractor is not None), None)
         if ext is None:
             raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        k1 = np.ascontiguousarray(F1.mvKeysUn, KEYPOINT_DTYPE)
-        k2 = np.ascontiguousarray(F2.mvKeysUn, KEYPOINT_DTYPE)
+        return ext
+
+    def SearchForInitialization(self, F1: Frame, F2: Frame, windowSize: int = 100):
+        """Returns (nmatches, vnMatches12).  nmatches keeps the reference's double-decrement quirk (cpp:95-98,130-138)."""
+        ext = self._extractor(F1, F2)
+        k1 = _keys(F1.mvKeysUn)
+        k2 = _keys(F2.mvKeysUn)
         d1 = np.ascontiguousarray(F1.mDescriptors, np.uint8)
         d2 = np.ascontiguousarray(F2.mDescriptors, np.uint8)
         m12 = np.full(max(len(k1), 1), -1, np.int32)
         st = _Stats()
-        b = _Bounds(*[int(v) for v in F2.bounds])
+        b = _bounds(F2.bounds)
         nm = ctypes.c_int32(0)
         r = ext._L.orbx_match_init(ext._h, _ptr(k1), _ptr(d1), len(k1), _ptr(k2), _ptr(d2), len(k2), ctypes.byref(b),
                                    int(windowSize), self.mfNNratio, int(self.mbCheckOrientation), _ptr(m12), ctypes.byref(nm),
@@ -2744,19 +2225,12 @@ class ORBmatcher:
         """ORB-SLAM2's SearchByBoW(KeyFrame*, Frame&, ...) over the frames' mFeatVec (include/orbx.h, "matching through the
         FeatureVector") -> (matches_f, nmatches): matches_f[j] = the KF feature matched to F's feature j, or -1.  mask
         (optional): one entry per KF feature, false = it has no map point.  Both frames' ComputeBoW must have run."""
-        ext = self._ext or KF.mpORBextractor or F.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        ext = self._extractor(KF, F)
         for name, fr in (("KF", KF), ("F", F)):
             if not (getattr(fr, "_bow_computed", False) or fr.mBowVec or fr.mFeatVec):
                 raise OrbxError(E_BADARG, "ORBmatcher.SearchByBoW: %s has no FeatureVector; call its ComputeBoW() first" % name)
-
-        def flat(fv):
-            node = [n for n in sorted(fv) for _ in fv[n]]
-            feat = [j for n in sorted(fv) for j in fv[n]]
-            return np.asarray(node, np.uint32), np.asarray(feat, np.uint32)
-        kn, kf = flat(KF.mFeatVec)
-        fn, ff = flat(F.mFeatVec)
+        kn, kf = _flat_feature_vector(KF.mFeatVec)
+        fn, ff = _flat_feature_vector(F.mFeatVec)
         return ext.match_bow(KF.mvKeysUn, KF.mDescriptors, kn, kf, F.mvKeysUn, F.mDescriptors, fn, ff, mask, self.mfNNratio,
                              self.mbCheckOrientation)
 
@@ -2766,24 +2240,13 @@ class ORBmatcher:
         (KF1 feature, KF2 feature) in ascending KF1 index, as ORB-SLAM2 builds it.  F12 is computed from the two poses Tcw (3x4 or
         4x4) and K (3x3, default KF1's camera); mask1 / mask2 (optional): true = the feature already has a map point.  Both
         keyframes' ComputeBoW must have run."""
-        ext = self._ext or KF1.mpORBextractor or KF2.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
+        ext = self._extractor(KF1, KF2)
         for name, fr in (("KF1", KF1), ("KF2", KF2)):
             if not (getattr(fr, "_bow_computed", False) or fr.mBowVec or fr.mFeatVec):
                 raise OrbxError(E_BADARG, "ORBmatcher.SearchForTriangulation: %s has no FeatureVector; call its ComputeBoW() first" % name)
-        if K is None:
-            cam = getattr(KF1, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchForTriangulation needs K (the keyframe carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
-
-        def flat(fv):
-            node = [n for n in sorted(fv) for _ in fv[n]]
-            feat = [j for n in sorted(fv) for j in fv[n]]
-            return np.asarray(node, np.uint32), np.asarray(feat, np.uint32)
-        n1, f1 = flat(KF1.mFeatVec)
-        n2, f2 = flat(KF2.mFeatVec)
+        K = _camera_K(K, KF1, "ORBmatcher.SearchForTriangulation", "keyframe")
+        n1, f1 = _flat_feature_vector(KF1.mFeatVec)
+        n2, f2 = _flat_feature_vector(KF2.mFeatVec)
         m12, res = ext.match_triangulation(KF1.mvKeysUn, KF1.mDescriptors, n1, f1, Tcw1, KF2.mvKeysUn, KF2.mDescriptors, n2, f2, Tcw2, K,
                                            mask1, mask2, median_depth2, self.mbCheckOrientation)
         i = np.flatnonzero(m12 >= 0)
@@ -2796,14 +2259,8 @@ class ORBmatcher:
         got, or -1.  points [N_last, 3] / mask [N_last]: LastFrame's map points (mvpMapPoints); Tcw (3x4 or 4x4):
         CurrentFrame's predicted pose; K: 3x3, default CurrentFrame's camera; point_desc (optional): the map points' own
         descriptors; last_outlier (optional): LastFrame.mvbOutlier."""
-        ext = self._ext or CurrentFrame.mpORBextractor or LastFrame.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(CurrentFrame, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjection needs K (the frame carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        ext = self._extractor(CurrentFrame, LastFrame)
+        K = _camera_K(K, CurrentFrame, "ORBmatcher.SearchByProjection", "frame")
         m, res = ext.match_projection(LastFrame.mvKeysUn, LastFrame.mDescriptors, CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors,
                                       points, mask, Tcw, K, CurrentFrame.bounds, th, self.mbCheckOrientation, point_desc, last_outlier)
         return int(res.nmatches), m, res
@@ -2815,14 +2272,8 @@ class ORBmatcher:
         projection"): isInFrustum, PredictScale and ORB-SLAM2's SearchByProjection(F, vpMapPoints, th) with this matcher's
         nnratio -> (nmatches, matches, point_view, LocalResult).  matches (optional): the map points F already has, as indices
         into the map arrays (F.mvpMapPoints); outlier (optional): F.mvbOutlier; K: 3x3, default F's camera."""
-        ext = self._ext or F.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(F, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchLocalPoints needs K (the frame carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        ext = self._extractor(F)
+        K = _camera_K(K, F, "ORBmatcher.SearchLocalPoints", "frame")
         m, view, res = ext.match_local_map(F.mvKeysUn, F.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Tcw, K,
                                            F.bounds, matches, th, self.mfNNratio, outlier)
         return int(res.nmatches), m, view, res
@@ -2833,14 +2284,8 @@ class ORBmatcher:
         matching the loop's points under Scw") -> (nmatches, matched, MatchScwResult).  Scw: 12 floats (sR row-major, then t) or
         a 3x4 / 4x4 matrix; the map arrays are SearchLocalPoints'; matched (optional): vpMatched as indices into the map arrays
         (with kf2_to_map: as the matched keyframe's feature indices); K: 3x3, default KF's camera."""
-        ext = self._ext or KF.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(KF, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjectionScw needs K (the keyframe carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        ext = self._extractor(KF)
+        K = _camera_K(K, KF, "ORBmatcher.SearchByProjectionScw", "keyframe")
         m, res = ext.match_scw(KF.mvKeysUn, KF.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K, KF.bounds,
                                matched, th, th_low, kf2_to_map)
         return int(res.nmatches), m, res
@@ -2853,14 +2298,8 @@ class ORBmatcher:
         CurrentFrame's pose; matches (optional): the points CurrentFrame already has (mvpMapPoints = sAlreadyFound), as indices
         into the keyframe's features; outlier (optional): CurrentFrame.mvbOutlier; point_desc (optional): the map points' own
         descriptors; K: 3x3, default CurrentFrame's camera."""
-        ext = self._ext or CurrentFrame.mpORBextractor or KF.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(CurrentFrame, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchByProjectionKeyFrame needs K (the frame carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        ext = self._extractor(CurrentFrame, KF)
+        K = _camera_K(K, CurrentFrame, "ORBmatcher.SearchByProjectionKeyFrame", "frame")
         m, res = ext.match_keyframe_projection(KF.mvKeysUn, KF.mDescriptors, CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors, points, mask,
                                                point_dist, Tcw, K, CurrentFrame.bounds, matches, th, ORBdist, self.mbCheckOrientation,
                                                point_desc, outlier)
@@ -2872,14 +2311,8 @@ class ORBmatcher:
         """ORB-SLAM2's SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (include/orbx.h, "loop closing: matching under a
         similarity") -> (nFound, matches12, MatchSim3Result).  map1 / map2: (points [N, 3], mask [N] or None, point_dist [N, 2],
         Tcw, point_desc [N, 32] or None) of each keyframe; matches12 int32 [N1]: KF2's feature per feature of KF1, or -1."""
-        ext = self._ext or KF1.mpORBextractor or KF2.mpORBextractor
-        if ext is None:
-            raise OrbxError(E_BADARG, "ORBmatcher needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(KF1, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "ORBmatcher.SearchBySim3 needs K (the keyframe carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        ext = self._extractor(KF1, KF2)
+        K = _camera_K(K, KF1, "ORBmatcher.SearchBySim3", "keyframe")
         (p1, m1, q1, T1, pd1), (p2, m2, q2, T2, pd2) = map1, map2
         sim = np.r_[np.asarray(R12, np.float32).reshape(9), np.asarray(t12, np.float32).reshape(3), np.float32(s12)].astype(np.float32)
         m, res = ext.match_sim3(KF1.mvKeysUn, KF1.mDescriptors, p1, m1, q1, T1, KF2.mvKeysUn, KF2.mDescriptors, p2, m2, q2, T2, sim, K,
@@ -2898,15 +2331,11 @@ class PnPsolver:
         self._ext = extractor or frame.mpORBextractor
         if self._ext is None:
             raise OrbxError(E_BADARG, "PnPsolver needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(frame, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "PnPsolver needs K (the frame carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        K = _camera_K(K, frame, "PnPsolver", "frame")
         self._K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
-        self._keys = np.ascontiguousarray(frame.mvKeysUn, KEYPOINT_DTYPE).reshape(-1)
+        self._keys = _keys(frame.mvKeysUn)
         n = len(self._keys)
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        pts = _points(points)
         mm = np.asarray(mask_or_match).reshape(-1)
         if len(mm) != n:
             raise OrbxError(E_BADARG, "mask_or_match must have one entry per keypoint of the frame")
@@ -2919,11 +2348,7 @@ class PnPsolver:
             if len(pts) != n:
                 raise OrbxError(E_BADARG, "points must have one entry per keypoint of the frame")
             self._points, self._mask = pts, (mm != 0).astype(np.uint8)
-        if rand is None:
-            libc = ctypes.CDLL(None)
-            libc.rand.restype = ctypes.c_int
-            rand = libc.rand
-        self._rand = rand
+        self._rand = rand or _libc_rand()
         self._params = dict(probability=0.99, min_inliers=8, max_iterations=300, epsilon=0.4, th2=5.991)  # the constructor's own
         self._turns = 0
         self._result = None
@@ -2990,11 +2415,7 @@ class Sim3Solver:
         self._match = np.ascontiguousarray(match12, np.int32).reshape(-1)
         self._K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
         self._fix = bool(bFixScale)
-        if rand is None:
-            libc = ctypes.CDLL(None)
-            libc.rand.restype = ctypes.c_int
-            rand = libc.rand
-        self._rand = rand
+        self._rand = rand or _libc_rand()
         self._params = dict(probability=0.99, min_inliers=6, max_iterations=300, th2=9.210)  # the constructor's own
         self._turns = 0
         self._result = None
@@ -3003,18 +2424,11 @@ class Sim3Solver:
         self._params = dict(self._params, probability=probability, min_inliers=minInliers, max_iterations=maxIterations)
         self._result, self._turns = None, 0
 
-    @staticmethod
-    def _pose12(T):
-        T = np.asarray(T, np.float32)
-        if T.size == 12 and T.ndim == 1:
-            return T
-        return np.r_[T[:3, :3].reshape(9), T[:3, 3]].astype(np.float32)
-
     def _run(self):
         if self._result is None:
             draws = sample_sim3_draws(self._rand, int(self._params["max_iterations"]))
             (k1, p1, m1, T1), (k2, p2, m2, T2) = self._kf1, self._kf2
-            self._result = self._ext.sim3_solve(k1, p1, m1, self._pose12(T1), k2, p2, m2, self._pose12(T2), self._match, self._K,
+            self._result = self._ext.sim3_solve(k1, p1, m1, _pose12(T1), k2, p2, m2, _pose12(T2), self._match, self._K,
                                                 draws, fix_scale=self._fix, **self._params)
         return self._result
 
@@ -3067,11 +2481,7 @@ class Optimizer:
         ext = extractor or frame.mpORBextractor
         if ext is None:
             raise OrbxError(E_BADARG, "Optimizer needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(frame, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "Optimizer.PoseOptimization needs K (the frame carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        K = _camera_K(K, frame, "Optimizer.PoseOptimization", "frame")
         res, outlier = ext.pose_optimize(frame.mvKeysUn, points, mask, Tcw, K, None, n_iterations)
         T = np.eye(4, dtype=np.float32)
         T[:3, :3], T[:3, 3] = np.array(res.R[:], np.float32).reshape(3, 3), np.array(res.tcw[:], np.float32)
@@ -3087,11 +2497,7 @@ class Optimizer:
         ext = extractor or kf1.mpORBextractor or kf2.mpORBextractor
         if ext is None:
             raise OrbxError(E_BADARG, "Optimizer needs an ORBextractor (device context); pass extractor=")
-        if K is None:
-            cam = getattr(kf1, "camera", None)
-            if cam is None:
-                raise OrbxError(E_BADARG, "Optimizer.OptimizeSim3 needs K (the keyframe carries no camera)")
-            K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
+        K = _camera_K(K, kf1, "Optimizer.OptimizeSim3", "keyframe")
         (p1, m1, T1), (p2, m2, T2) = map1, map2
         sim = np.r_[np.asarray(R12, np.float32).reshape(9), np.asarray(t12, np.float32).reshape(3), np.float32(s12)].astype(np.float32)
         res, out, row = ext.optimize_sim3(kf1.mvKeysUn, p1, m1, _pose12(T1), kf2.mvKeysUn, p2, m2, _pose12(T2), matches12, sim, K, None, bFixScale, th2,
