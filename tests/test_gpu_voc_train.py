@@ -1,6 +1,8 @@
 """DBoW2's TemplatedVocabulary::create on the device (orbx_vocabulary_train): every case equals the recursive CPU restatement
 (tests/cpp/voc_train_ref.cpp) byte for byte -- parents, leaf flags, descriptors, the bytes of every weight, the statistics and each
 training feature's word -- and the reference's compiled DBoW2 loads and transforms with what the device trained."""
+import contextlib
+import functools
 import os
 import subprocess
 
@@ -89,6 +91,123 @@ def test_larger_nodes_take_the_chunked_paths(orbx, ext):
     v = orbx.Vocabulary.train(ext, docs, 6, 2, 0, 0, 3, feat_word=True)
     _same(v, T.train(docs, 6, 2, 0, 3))
     v.close()
+
+
+@contextlib.contextmanager
+def _seed_grid_min(orbx, value):
+    """Inside the block, nodes above `value` features are seeded grid-wide (None: the default).  The switch is process-wide."""
+    if value is None:
+        yield
+        return
+    orbx.lib().orbx_debug_voc_train_seed_grid_min(value)
+    try:
+        yield
+    finally:
+        orbx.lib().orbx_debug_voc_train_seed_grid_min(-1)
+
+
+@pytest.mark.parametrize("name", T.SIZE_CASES)
+def test_size_case_equals_the_restatement(orbx, ext, name, tmp_path):
+    """The inputs at which the kernels change paths (voc_train_ref_lib.size_case; tests/test_voc_train_host.py asserts that each
+    reaches its path).  root_above_65536 also runs in the device form, and the reference's compiled transform of its training
+    features through the saved file gives the device's words."""
+    for c, tr in zip(T.size_case(name), T.size_trained(name)):
+        with _seed_grid_min(orbx, c.grid_min):
+            v = orbx.Vocabulary.train(ext, c.docs, c.k, c.L, c.weighting, 0, c.seed, feat_word=True)
+        _same(v, tr, "%s %s" % (name, c.label))
+        if name == "root_above_65536":
+            import torch
+            desc, n = np.stack(c.docs), np.full(len(c.docs), T.MAX_DOC, np.int32)
+            assert desc.shape == (5, T.MAX_DOC, 32)
+            d_desc, d_n = torch.from_numpy(desc).cuda(), torch.from_numpy(n).cuda()
+            d_fw = torch.zeros((len(c.docs), T.MAX_DOC), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            d = orbx.Vocabulary.train(ext, None, c.k, c.L, c.weighting, 0, c.seed, d_desc=d_desc, d_n=d_n, n_docs=len(c.docs),
+                                      capacity=T.MAX_DOC, d_feat_word=d_fw)
+            _same(d, tr, "device form")
+            assert np.array_equal(d_fw.cpu().numpy().view(np.uint32).reshape(-1), tr.feat_word)
+            d.close()
+            path = str(tmp_path / "device.txt")
+            v.save_text(path, exact=True)
+            text = open(path).read()
+            assert text.endswith("\n")
+            open(path, "w").write(text[:-1])  # (as in test_device_against_the_reference)
+            rv = ref_lib.Vocabulary(path)
+            off = 0
+            for doc in c.docs:
+                assert np.array_equal(rv.transform(doc, 4, feature_vector=False)["feat_word"], v.train_feat_word[off:off + len(doc)])
+                off += len(doc)
+            rv.close()
+        v.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _seed_input(which):
+    """(docs, k, L, seed, grid_min) of test_seeds_equal_the_numpy_statement."""
+    if which in ("300", "300_grid_wide"):
+        rng = np.random.default_rng(300)
+        base = rng.integers(0, 256, (12, 32), dtype=np.uint8)
+        return [R._flip(rng, base[rng.integers(0, 12, 300)], 3)], 5, 1, 17, 0 if which == "300_grid_wide" else None
+    name, label, L = {"4097": ("edges_of_4096", "4097", 1), "65537": ("edge_of_65536", "65537", 1),
+                      "81920": ("root_above_65536", "81920", 1), "short": ("short_seeding_large", "5000", 1), "two_levels": ("root_above_65536", "81920", 2)}[which]
+    c = [x for x in T.size_case(name) if x.label == label][0]
+    return c.docs, c.k, L, c.seed, c.grid_min
+
+
+@pytest.mark.parametrize("which", ["300", "300_grid_wide", "4097", "65537", "81920", "short", "two_levels"])
+def test_seeds_equal_the_numpy_statement(orbx, ext, which):
+    """A training stopped after its first round leaves the seeds as the children's descriptors.  They equal, in count and bytes,
+    what voc_train_ref_lib.seeds_numpy -- written from the text of include/orbx.h, not from the restatement -- picks: by one
+    workgroup (300), grid-wide (300 under the switch, 4097), with one and with two block sums per thread of k_vt_seed_pick (65537,
+    81920), stopping short grid-wide (three distinct descriptors), and on the second level under every node's own key."""
+    docs, k, L, seed, grid_min = _seed_input(which)
+    feats = T.case_feats(docs)
+    parent, desc = T.seeded_tree_numpy(feats, k, L, seed)
+    with _seed_grid_min(orbx, grid_min):
+        v = orbx.Vocabulary.train(ext, docs, k, L, 0, 0, seed, max_rounds=1)
+    mine = v.nodes()
+    assert v.n_nodes == len(parent) and np.array_equal(mine[0], parent) and np.array_equal(mine[2], desc)
+    assert v.train_stats["capped_runs"] == v.train_stats["kmeans_runs"] >= 1 and v.train_stats["max_rounds_seen"] == 1
+    if which == "short":
+        assert len(parent) == 3 and v.train_stats["short_seedings"] == 1
+    if which == "two_levels":
+        assert len(parent) == k + k * k
+    v.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_trained(i):
+    docs, k, L, seed = T.sweep_case(i)
+    return T.train(docs, k, L, i % 4, seed)
+
+
+@pytest.mark.parametrize("grid_min", [0, 16])
+def test_edge_sweep_under_grid_wide_seeding(orbx, ext, grid_min):
+    """The edge sweep with every k-means node (0), or every one above 16 features (a mixed level), seeded by the grid-wide
+    kernels: down to n = k + 1, and with the seedings that stop short in k_vt_seed_pick."""
+    short = 0
+    with _seed_grid_min(orbx, grid_min):
+        for i in range(T.SWEEP):
+            docs, k, L, seed = T.sweep_case(i)
+            v = orbx.Vocabulary.train(ext, docs, k, L, i % 4, i % 6, seed, feat_word=True)
+            _same(v, _sweep_trained(i), "set %d" % i)
+            short += _sweep_trained(i).stats["short_seedings"]
+            v.close()
+    assert short >= 1
+
+
+def test_round_limit_in_a_chunked_node(orbx, ext):
+    """5,000 features in one node (two count chunks, global counters): stopped after 1, 2 and 3 rounds."""
+    rng = np.random.default_rng(12)
+    base = rng.integers(0, 256, (20, 32), dtype=np.uint8)
+    docs = [R._flip(rng, base[rng.integers(0, 20, 5000)], 3)]
+    assert len(docs[0]) > T.VT_CHUNK and T.train(docs, 6, 1, 0, 7).stats["max_rounds_seen"] > 3
+    for max_rounds in (1, 2, 3):
+        tr = T.train(docs, 6, 1, 0, 7, max_rounds)
+        assert tr.stats["capped_runs"] == 1
+        v = orbx.Vocabulary.train(ext, docs, 6, 1, 0, 0, 7, max_rounds=max_rounds, feat_word=True)
+        _same(v, tr, "max_rounds %d" % max_rounds)
+        v.close()
 
 
 def test_trained_vocabulary_transforms_like_its_nodes(orbx, ext, golden):

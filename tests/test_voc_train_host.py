@@ -1,9 +1,13 @@
 """Vocabulary training (orbx_vocabulary_train, include/orbx.h "training") without a device: the ABI's refusals, and the CPU
 restatement the GPU tests compare against (tests/cpp/voc_train_ref.cpp) checked on its own -- against the reference's compiled
-DBoW2 as far as oracle/_ref/libref.so reaches (its loader, its transform), and against the fixed-point property of k-means stated
-in numpy.  (save_text needs a vocabulary, which needs a device: its round trip is in tests/test_gpu_voc_train.py.)"""
+DBoW2 as far as oracle/_ref/libref.so reaches (its loader, its transform), against the fixed-point property of k-means stated
+in numpy, and its k-means++ seeding against a numpy statement written from the header's text; and that the inputs of the size
+edges (voc_train_ref_lib.size_case) reach the paths they are there for.  (save_text needs a vocabulary, which needs a device: its round trip is in
+tests/test_gpu_voc_train.py.)"""
 import ctypes
 import math
+import os
+import re
 
 import numpy as np
 import pytest
@@ -42,20 +46,6 @@ def test_abi_refusals_without_a_device(orbx):
     assert L.orbx_vocabulary_save_text(None, b"/nonexistent/x", 1) == orbx.E_BADARG
 
 
-def _groups(tr, n_feat):
-    """node id -> ascending features of its training group, from every feature's final node and the parents."""
-    groups = {}
-    par = np.concatenate([[0], tr.parent])  # parent of node id (root: itself)
-    for f in range(n_feat):
-        node = int(tr.feat_node[f])
-        while True:
-            groups.setdefault(node, []).append(f)
-            if node == 0:
-                break
-            node = int(par[node])
-    return groups
-
-
 def _check_fixed_point(tr, docs, k, L):
     """For every node that was split and not stopped by the round limit: each child's descriptor is meanValue of its group (the
     trivial case: the feature itself, in order), and every feature's nearest child, the first among equals, is its group's."""
@@ -64,9 +54,7 @@ def _check_fixed_point(tr, docs, k, L):
         assert len(tr.parent) == 0
         return
     assert tr.stats["capped_runs"] == 0  # (no input of these tests runs into the limit of 100 rounds)
-    children, groups = T.children_of(tr.parent), _groups(tr, len(feats))
-    bits = np.unpackbits(feats, axis=1).astype(np.int32)
-    nbits = np.unpackbits(tr.desc, axis=1).astype(np.int32)
+    children, groups = T.children_of(tr.parent), T.groups_of(tr, len(feats))
     seen_kmeans = seen_trivial = 0
     for node, ch in enumerate(children):
         if not ch:
@@ -78,7 +66,7 @@ def _check_fixed_point(tr, docs, k, L):
             assert all(groups[c] == [int(f)] for c, f in zip(ch, g))
             continue
         seen_kmeans += 1
-        dist = (bits[g][:, None, :] != nbits[np.array(ch) - 1][None, :, :]).sum(axis=2)
+        dist = T.POPCOUNT[feats[g][:, None, :] ^ tr.desc[np.array(ch) - 1][None, :, :]].sum(axis=2)  # (per byte, not per bit)
         nearest = np.array(ch)[np.argmin(dist, axis=1)]  # argmin: the first minimum
         for c in ch:
             mine = g[nearest == c]
@@ -159,3 +147,115 @@ def test_round_limit_and_seed():
     assert not (np.array_equal(a.parent, b.parent) and np.array_equal(a.desc, b.desc))  # the seed matters
     c = T.train(docs, k, L, 0, seed, max_rounds=2)
     assert c.stats["capped_runs"] >= 1 and c.stats["max_rounds_seen"] == 2
+
+
+# ---- the seeding against its numpy statement (voc_train_ref_lib.seeds_numpy, written from include/orbx.h) -------------------------
+
+
+def _check_seeds(tr, feats, k, seed, what):
+    """Of a training stopped after one round: every split node's children are, in count and bytes, the seeds the numpy statement
+    picks from the node's group under the node's key (a node of at most k features: its features).  Returns the seedings that
+    stopped short, counted from the statement's own output."""
+    short = 0
+    for s in T.splits_of(tr, len(feats)):
+        f = feats[s.group]
+        picks = list(range(len(f))) if len(f) <= k else T.seeds_numpy(f, k, seed, s.key)
+        short += len(f) > k and len(picks) < k
+        assert len(s.children) == len(picks), (what, s.node, s.key)
+        assert np.array_equal(tr.desc[np.array(s.children) - 1], f[picks]), (what, s.node, s.key)
+    return short
+
+
+def test_seeding_equals_the_numpy_statement():
+    ran = short = 0
+    for i in range(T.SWEEP):
+        docs, k, L, seed = T.sweep_case(i)
+        feats = T.case_feats(docs)
+        if len(feats) <= k:
+            continue  # (the trivial root: nothing is seeded)
+        tr = T.train(docs, k, 1, 0, seed, max_rounds=1)
+        picks = T.seeds_numpy(feats, k, seed, 0)
+        assert len(tr.parent) == len(picks) and np.array_equal(tr.desc, feats[picks]), "set %d" % i
+        assert tr.stats["short_seedings"] == (len(picks) < k), "set %d" % i
+        ran += 1
+        short += len(picks) < k
+    deeper = 0
+    for i, L in [(j, 2) for j in range(14)] + [(20, 3), (22, 3), (24, 3)]:
+        docs, k, _, seed = T.sweep_case(i)
+        feats = T.case_feats(docs)
+        if len(feats) <= k:
+            continue
+        tr = T.train(docs, k, L, 0, seed, max_rounds=1)
+        short_here = _check_seeds(tr, feats, k, seed, "set %d, L %d" % (i, L))
+        assert short_here == tr.stats["short_seedings"]
+        parent, desc = T.seeded_tree_numpy(feats, k, L, seed)
+        assert np.array_equal(parent, tr.parent) and np.array_equal(desc, tr.desc), "set %d, L %d" % (i, L)
+        deeper += 1
+    print("seeding: %d of %d sweep sets with n > k, %d of them stop short; %d sets with L 2 or 3" % (ran, T.SWEEP, short, deeper))
+    assert ran >= T.SWEEP - 1 and short >= 1 and deeper >= 12
+
+
+def test_size_constants_equal_the_device_header():
+    text = open(os.path.join(T.ROOT, "orb_slam_tracking_amd", "csrc", "orbx_device.h")).read()
+    for name in ("VT_THREADS", "VT_CHUNK", "VT_SEED_LDS", "VT_KMAX"):
+        m = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert len(m) == 1 and int(m[0]) == getattr(T, name), name
+    m = re.findall(r"#define\s+ORBX_BOW_MAX_FEATURES\s+(\d+)", open(os.path.join(T.ROOT, "include", "orbx.h")).read())
+    assert len(m) == 1 and int(m[0]) == T.MAX_DOC
+
+
+def _levels(tr, n_feat):
+    """level -> the sizes of the groups that were split there (level 1: the root's), from the restatement's tree."""
+    out = {}
+    for s in T.splits_of(tr, n_feat):
+        out.setdefault(s.level, []).append(len(s.group))
+    return out
+
+
+@pytest.mark.parametrize("name", T.SIZE_CASES)
+def test_size_cases_reach_their_paths(name):
+    """Each named input of voc_train_ref_lib.size_case meets, in the restatement's tree alone, the condition it exists for (the
+    device's path at that size is in the comment), and is a fixed point of k-means."""
+    cases, trained = T.size_case(name), T.size_trained(name)
+    B, C, S = T.VT_THREADS, T.VT_CHUNK, T.VT_SEED_LDS
+    for c, tr in zip(cases, trained):
+        n = sum(len(d) for d in c.docs)
+        lv = _levels(tr, n)
+        kmeans = {level: [m for m in sizes if m > c.k] for level, sizes in lv.items()}
+        print(name, c.label, "n %d k %d L %d" % (n, c.k, c.L), tr.stats, "k-means nodes per level",
+              {level: len(v) for level, v in kmeans.items()})
+        assert all(len(d) <= T.MAX_DOC for d in c.docs)
+        assert tr.stats["capped_runs"] == 0
+        if name == "root_above_65536":
+            assert n > B * B  # k_vt_seed_pick: more than VT_THREADS blocks, two block sums per thread
+            assert len([m for m in lv[2] if m > max(C, S)]) >= 2  # grid-wide seeding and global counters, several nodes at once
+            assert max(len(d) for d in c.docs) == T.MAX_DOC and c.weighting == T.IDF  # k_vt_docfreq at the largest capacity
+        elif name == "edges_of_4096":
+            assert (C, S) == (4096, 4096) and n == int(c.label) and len(c.docs) == 1 and lv[1] == [n] and n > c.k
+        elif name == "edges_of_256":
+            assert B == 256 and n == int(c.label) and lv[1] == [n] and c.grid_min < B - 1 and c.L == 2
+            assert any(m > c.grid_min for m in lv.get(2, []))  # a grid-seeded node that does not start at a block's edge
+        elif name == "edge_of_65536":
+            assert n == int(c.label) and lv[1] == [n] and n - B * B in (0, 1)
+        elif name == "emptied_in_chunks":
+            assert c.L == 1 and n > C and tr.stats["emptied_clusters"] >= 1  # vtMean's size == 0 from k_vt_centre_final
+        elif name == "short_seeding_large":
+            assert n > S and c.grid_min is None and tr.stats["short_seedings"] >= 1
+            assert len(T.children_of(tr.parent)[0]) < c.k  # the root itself, above VT_SEED_LDS, was seeded short
+        elif name == "wide_level":
+            assert max(len(v) for v in kmeans.values()) > B  # k_vt_round's second workgroup
+            assert [len(lv[level]) for level in (1, 2, 3, 4)] == [1, 10, 100, 1000]
+        elif name == "k20":
+            assert c.k == T.VT_KMAX and len(T.children_of(tr.parent)[0]) == T.VT_KMAX and any(m > c.k for m in lv[2])
+        elif name == "deep":
+            assert c.L == 10 and max(lv) == 10 and any(m > c.k for m in lv[10])  # keys up to 21^9 and beyond
+        elif name == "many_documents":
+            lens = [len(d) for d in c.docs]
+            assert len(lens) >= 700 and lens.count(0) >= 10 and 32 < max(lens) <= 64  # k_vt_docfreq sorts 64 keys a document
+            assert c.weighting in (T.IDF, T.TF_IDF)
+            w = tr.weight[tr.is_leaf == 1]
+            assert w.min() < math.log(len(lens) / 100.0) and len(np.unique(w)) > 20  # a word in more than 100 documents
+        _check_fixed_point(tr, c.docs, c.k, c.L)
+    assert {c.label for c in cases} == {"root_above_65536": {"81920"}, "edges_of_4096": {"4095", "4096", "4097"},
+                                        "edges_of_256": {"255", "256", "257", "512", "513"}, "edge_of_65536": {"65536", "65537"},
+                                        "many_documents": {"idf", "tf_idf"}}.get(name, {cases[0].label})
