@@ -1100,6 +1100,147 @@ int orbx_sim3_compose_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs,
 /* The same for one pair in host memory: pose2 [12], sim3 [13] -> scw [12].  Synchronous. */
 int orbx_sim3_compose_scw(orbx_ctx* ctx, const float* pose2, const float* sim3, float* scw);
 
+/* ---- fusing map points into a keyframe (ORBmatcher::Fuse, both overloads) ----------------------------------------------------
+ * LocalMapping::SearchInNeighbors runs Fuse(pKF, vpMapPoints, th = 3) behind CreateNewMapPoints, the new keyframe's points into
+ * every neighbour and the neighbours' points into the new keyframe; LoopClosing::SearchAndFuse runs Fuse(pKF, Scw, vpPoints, th
+ * = 4, vpReplacePoint) over the map set the Scw matcher above has read.  The reference ships no Fuse: the rules are ORB-SLAM2's,
+ * [from-knowledge], PARITY UNPINNED, bit-identical to a CPU restatement (tests/cpp/fuse_ref.cpp).  The window search alone is
+ * pinned: the reference's Frame::GetFeaturesInArea, compared with its compiled code by the tests.
+ *
+ * Pair p: keyframe h_kf[p] (n_C features), map set s = h_map_set[p] (n_s points), d_pose[p] or d_scw[p] (12 floats), the row
+ * d_matches[p] (mvpMapPoints: feature j -> an index into set s, ORBX_FUSE_OCCUPIED_UNMAPPED for a point that is not in the set,
+ * any other negative value: free; read and written).  f32 without contraction unless stated.
+ * Search, pose form, for every point i in ascending order:
+ *   1. the entry: a row entry e with 0 <= e < n_s names point e, which is IsInKeyFrame and not searched, whatever its mask
+ *      (n_in_kf counts the points named).  An entry >= n_s is never followed: ORBX_FUSE_BAD_INPUT, and its feature holds a bad
+ *      point.  The points searched are those with their mask byte set (d_map_mask NULL: all) that the row does not name
+ *      (n_points).
+ *   2. Pc = Rcw*P + tcw as xc = ((R0*X + R1*Y) + R2*Z) + t0, yc and zc likewise.  zc < 0.0f: skipped (n_behind); zc == 0 goes on
+ *      and fails the image test.  invz = 1.0f / zc correctly rounded; u = fx*(xc*invz) + cx, v = fy*(yc*invz) + cy.
+ *      KeyFrame::IsInImage: the point stays iff u >= min_x && u < max_x && v >= min_y && v < max_y; no number fails
+ *      (n_out_image).
+ *   3. Ow_k = -((R[0][k]*t0 + R[1][k]*t1) + R[2][k]*t2); PO = P - Ow; dist, its two bounds (n_out_distance) and the viewing angle
+ *      (n_out_angle) are rules 4 and 5 of "loop closing: matching the loop's points under Scw", verbatim.
+ *   4. level = PredictScale in table form on ratio = maxDist / dist: the number of n in [0, nlevels - 1) with ratio > scale[n].
+ *      r = th * scale[level]; the candidates are GetFeaturesInArea(u, v, r) without level bounds, in the grid's order (cell x
+ *      outer, cell y inner, ascending index inside a cell); n_with_candidates counts the points with at least one.  A
+ *      candidate whose octave is outside [level - 1, level] is dropped.
+ *   5. the chi-square gate (this form only): ex = u - kp.x, ey = v - kp.y, e2 = ex*ex + ey*ey; the candidate is dropped when
+ *      (double)(e2 * invLevelSigma2[octave]) > 5.99, the product in f32; invLevelSigma2 is the context's table.  An octave < 0
+ *      is outside the table: dropped.
+ *   6. d = popcount(d_map_desc32[s][i] ^ desc_C[j]); bestDist starts at 256 and `d < bestDist` takes the candidate: the first
+ *      smallest in the order wins.  The pick stands when bestDist <= th_low; a point with candidates whose pick does not stand
+ *      counts in n_over_dist.  A point's pick depends on nothing another point does: there is no "taken" rule.
+ * Search, Scw form: rule 1 of the Scw matcher decomposes d_scw[p] (scw from the first row, twelve divisions, Ow = -Rcw^T tcw);
+ * rules 1 to 4 above; no chi-square gate; bestDist starts at INT_MAX, so with th_low = 256 a candidate at distance 256 fuses
+ * here and never in the pose form.
+ * Resolution, per feature f over the points that picked it, in ascending i (each counts in n_fused); obs_i = d_map_obs[s][i]:
+ *   R1. f is free: ORBX_FUSE_ADD, row[f] = i, d_fuse_other[i] = -1; the modelled count of f's occupant becomes obs_i + 1.
+ *   R2. the occupant is bad (a set entry with mask 0; ORBX_FUSE_OCCUPIED_UNMAPPED with d_occ_obs[f] < 0; an entry >= n_s):
+ *       ORBX_FUSE_BAD_OCCUPANT, nothing changes, also for later points; d_fuse_other[i] is the entry.
+ *   R3. pose form, a good occupant with count c (d_map_obs of the entry, d_occ_obs[f] of an unmapped one, or the modelled count
+ *       when this call has decided on f before): c > obs_i gives ORBX_FUSE_KEEP_OCCUPANT (pMP->Replace(pMPinKF)); otherwise,
+ *       equality included, ORBX_FUSE_REPLACE_OCCUPANT (pMPinKF->Replace(pMP)) and row[f] = i; either way c becomes c + obs_i.
+ *       d_fuse_other[i] is the occupant met.
+ *   R4. Scw form, a good occupant: ORBX_FUSE_KEEP_OCCUPANT and d_fuse_other[i] = vpReplacePoint[i], the occupant; the row
+ *       changes only by ORBX_FUSE_ADD, and a later point on a feature an earlier one was added to gets that earlier point.
+ *   n_chained counts the decisions that are not the first on their feature and do not meet a bad occupant: those read a count
+ *   (or an occupant) this call has changed.
+ * Documented deviations from ORB-SLAM2:
+ *   1. PredictScale in table form (deviation 1 of matching the local map by projection).
+ *   2. Map points are arrays plus a mask (0 = NULL or isBad()), with indices; the points of one set are distinct.
+ *   3. No stereo branch.
+ *   4. The count model of R1 / R3.  ORB-SLAM2's Replace hands over only the observations in keyframes that do not already see
+ *      the survivor; the sum is that number when the two points share no keyframe.  A modelled count is read only where a
+ *      feature is picked a second time in one call: n_chained counts exactly those decisions, and d_fuse_idx / d_fuse_act /
+ *      d_fuse_other let a caller replay them with the map's own counts.  The Scw form reads no counts and is exact.
+ *   5. The pairs of one call are independent.  ORB-SLAM2's loop over neighbours sees the earlier neighbours' fusions: a caller
+ *      who needs that issues the neighbours call by call.
+ *   6. Replace, AddObservation, ComputeDistinctiveDescriptors and UpdateNormalAndDepth stay the caller's.
+ *   7. th_low is an argument (ORBmatcher::TH_LOW is 50), accepted in [0, 256].
+ *   8. Garbage is flagged and never followed.  Counts outside [0, capacity] / [0, map_capacity] are clamped and set
+ *      ORBX_FUSE_BAD_INPUT, as do a row entry >= n_s and, in the pose form without d_occ_obs, an ORBX_FUSE_OCCUPIED_UNMAPPED
+ *      entry (handled as a bad occupant).  The pose form reads obs_i of every point whose pick stands and the count of every
+ *      good occupant a first decision meets: a value outside [0, 65535] is clamped into it and sets ORBX_FUSE_BAD_INPUT, so no
+ *      sum overflows.  A pose with a non-finite value, a similarity rule 1 of the Scw matcher cannot decompose: ORBX_FUSE_NONFINITE,
+ *      every point of rule 1 dropped, the row untouched; a point whose position, normal or two distances hold a non-finite
+ *      value sets it and is dropped, as is one whose ratio is no number.
+ * Worst case: every point of the set on one feature resolves one point per round (see the kernel). */
+#define ORBX_FUSE_BAD_INPUT 2 /* a count outside its range, a row entry that is never followed */
+#define ORBX_FUSE_NONFINITE 4 /* a pose or similarity that cannot be used, a non-finite point / normal / distance or ratio */
+#define ORBX_FUSE_OCCUPIED_UNMAPPED (-2) /* d_matches: the feature has a map point that is not in the pair's map set */
+#define ORBX_FUSE_NONE 0
+#define ORBX_FUSE_ADD 1
+#define ORBX_FUSE_KEEP_OCCUPANT 2
+#define ORBX_FUSE_REPLACE_OCCUPANT 3
+#define ORBX_FUSE_BAD_OCCUPANT 4
+typedef struct orbx_fuse_result {
+  int32_t status;              /* 0, or a bitmask of ORBX_FUSE_*; every field is written for every pair */
+  int32_t n_fused;             /* nFused, the design's return value: the points whose pick stands */
+  int32_t n_points;            /* points that reach rule 2: mask set, not in the keyframe */
+  int32_t n_in_kf;             /* points some entry of the row names (whatever their mask) */
+  int32_t n_behind;            /* rule 2: zc < 0 */
+  int32_t n_out_image;         /* ... outside [min, max) or no number */
+  int32_t n_out_distance;      /* rule 3 */
+  int32_t n_out_angle;         /* rule 3 */
+  int32_t n_with_candidates;   /* searched points whose window holds a feature (rule 4) */
+  int32_t n_over_dist;         /* ... whose pick does not stand (rules 4 to 6) */
+  int32_t n_added;             /* R1 */
+  int32_t n_kept_occupant;     /* R3 / R4 */
+  int32_t n_replaced_occupant; /* R3 */
+  int32_t n_bad_occupant;      /* R2 */
+  int32_t n_chained;           /* decisions behind an earlier one on the same feature (deviation 4) */
+  int32_t rounds;              /* the device's rounds: the longest list of points on one feature; a sequential statement: 0 */
+} orbx_fuse_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  The keyframes and the map sets are exactly the arrays of
+ * orbx_match_scw_batch_device, with the same sharing: several pairs may name one keyframe or one set.  d_map_obs int32
+ * [n_map_sets][map_capacity]: Observations() of each point (required).  d_pose float [n_pairs][12]: Rcw row-major, then tcw.  K
+ * row-major 3x3 (host, f32), bounds = the keyframes' image bounds, th finite and > 0 (SearchInNeighbors passes 3), th_low in [0,
+ * 256].  d_matches int32 [n_pairs][capacity], in and out and required; entries at and beyond the keyframe's count are not
+ * touched.  d_occ_obs int32 [n_pairs][capacity] or NULL: for an ORBX_FUSE_OCCUPIED_UNMAPPED entry the occupant's
+ * Observations(), negative when that occupant isBad().  Outputs per pair and map point i < n_s (entries at and beyond n_s are
+ * not touched): d_fuse_idx int32 [n_pairs][map_capacity], the feature picked or -1; d_fuse_act uint8 [n_pairs][map_capacity],
+ * ORBX_FUSE_NONE .. ORBX_FUSE_BAD_OCCUPANT; d_fuse_other int32 [n_pairs][map_capacity], the occupant the decision met (a set
+ * index, ORBX_FUSE_OCCUPIED_UNMAPPED, an entry >= n_s as it stands) or -1.  d_res [n_pairs].
+ * One workgroup per pair, one launch.  The call returns once queued, with the exception orbx_match_bow_batch_device has: when the
+ * pair lists differ from the previous call's on this context, the call first waits for the context stream before it uploads
+ * them.
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity or map_capacity < 1, th not finite or <= 0, th_low outside
+ * [0, 256], bounds with max <= min, a keyframe outside [0, n_frames), a map set outside [0, n_map_sets) -- all checked before
+ * anything touches a device; ORBX_E_CAPACITY: capacity or map_capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with
+ * otherwise well-formed arguments.  n_pairs == 0 is ORBX_OK. */
+int orbx_fuse_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                           const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity, int n_map_sets,
+                           int map_capacity, const int32_t* d_map_n, const float* d_map_points, const float* d_map_normals,
+                           const float* d_map_dist, const uint8_t* d_map_desc32, const uint8_t* d_map_mask, const int32_t* d_map_obs,
+                           const float* d_pose, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* d_matches,
+                           const int32_t* d_occ_obs, int32_t* d_fuse_idx, uint8_t* d_fuse_act, int32_t* d_fuse_other,
+                           orbx_fuse_result* d_res);
+/* The Scw form: d_scw float [n_pairs][12] as orbx_sim3_compose_scw_batch_device writes it in place of d_pose, no d_map_obs;
+ * d_occ_obs is read for its sign only, and with NULL an unmapped occupant is good (SearchAndFuse passes th = 4).  d_fuse_other
+ * is vpReplacePoint.  Everything else, the refusals included, as above. */
+int orbx_fuse_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                               const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                               int n_map_sets, int map_capacity, const int32_t* d_map_n, const float* d_map_points,
+                               const float* d_map_normals, const float* d_map_dist, const uint8_t* d_map_desc32,
+                               const uint8_t* d_map_mask, const float* d_scw, const float* K, const orbx_bounds* bounds, float th,
+                               int th_low, int32_t* d_matches, const int32_t* d_occ_obs, int32_t* d_fuse_idx, uint8_t* d_fuse_act,
+                               int32_t* d_fuse_other, orbx_fuse_result* d_res);
+/* The same for one pair in host memory, through the batched path as a batch of one: the keyframe (n features), the map (map_n
+ * points; map_mask nullable; map_obs [map_n], required with points in the pose form), pose / scw [12]; matches [n] in and out;
+ * occ_obs [n] nullable; fuse_idx, fuse_act, fuse_other [map_n].  More than ORBX_BOW_MAX_FEATURES features or points:
+ * ORBX_E_CAPACITY.  Synchronous. */
+int orbx_fuse(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+              const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+              const int32_t* map_obs, const float* pose, const float* K, const orbx_bounds* bounds, float th, int th_low,
+              int32_t* matches, const int32_t* occ_obs, int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other,
+              orbx_fuse_result* res);
+int orbx_fuse_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+                  const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+                  const float* scw, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches,
+                  const int32_t* occ_obs, int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other, orbx_fuse_result* res);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

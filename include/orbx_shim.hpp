@@ -330,6 +330,16 @@ struct MapView {
   const float* mfMinMaxDistance = nullptr;  // [N][2]
   const uint8_t* mDescriptors = nullptr;  // [N][32]
   const uint8_t* mbGood = nullptr;        // [N] or null
+  const int32_t* mnObs = nullptr;         // [N] or null: Observations(), what ORBmatcher::Fuse(KF, Tcw, map, ...) compares
+};
+
+// What ORBmatcher::Fuse decides (orbx.h, "fusing map points into a keyframe"): per map point the feature it picked (or -1), the
+// action (ORBX_FUSE_NONE .. ORBX_FUSE_BAD_OCCUPANT) and the occupant it met (or -1), and the counters.  Replace / AddObservation
+// stay the caller's.
+struct FuseOutcome {
+  std::vector<int> vnFeature, vnOccupant;
+  std::vector<uint8_t> vnAction;
+  orbx_fuse_result result;
 };
 
 // A candidate keyframe as the relocalisation overload ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th,
@@ -464,6 +474,26 @@ class ORBmatcher {
     return searchScw(ext_, KF, Scw, map, vpMatched, th, K, bounds, thLow, result);
   }
 
+  // ORB-SLAM2's Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th) (orbx.h, "fusing map points into a
+  // keyframe", with its documented deviations): the points of `map` (with mnObs) are projected into KF under its pose Tcw.
+  // vpMapPoints[j] = the index into `map` of feature j's map point, ORBX_FUSE_OCCUPIED_UNMAPPED (with its Observations() in
+  // vnOccObs[j], when given) or -1 -- KF's mvpMapPoints, in and out (any other size than KF.N stands for none).  Returns nFused.
+  int Fuse(const KeyFrameView& KF, const PoseT& Tcw, const MapView& map, float th, const float* K, const orbx_bounds& bounds,
+           FuseOutcome& out, std::vector<int>* vpMapPoints = nullptr, const std::vector<int>* vnOccObs = nullptr, int thLow = 50) {
+    return fuse(ext_, false, KF, Tcw, map, th, K, bounds, out, vpMapPoints, vnOccObs, thLow);
+  }
+  // ORB-SLAM2's Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint)
+  // of LoopClosing::SearchAndFuse: vpReplacePoint[i] = the index of the point of KF that map point i is to replace, or -1.
+  int Fuse(const KeyFrameView& KF, const PoseT& Scw, const MapView& map, float th, std::vector<int>& vpReplacePoint, const float* K,
+           const orbx_bounds& bounds, FuseOutcome& out, std::vector<int>* vpMapPoints = nullptr,
+           const std::vector<int>* vnOccObs = nullptr, int thLow = 50) {
+    const int n = fuse(ext_, true, KF, Scw, map, th, K, bounds, out, vpMapPoints, vnOccObs, thLow);
+    vpReplacePoint = out.vnOccupant;
+    for (size_t i = 0; i < vpReplacePoint.size(); i++)
+      if (out.vnAction[i] != ORBX_FUSE_KEEP_OCCUPANT) vpReplacePoint[i] = -1;
+    return n;
+  }
+
   // ORB-SLAM2's SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
   // const bool bOnlyStereo = false), monocular (orbx.h, "growing the map", with its documented deviations; the orientation check
   // is this matcher's): the features of KF1 without a map point are matched along their epipolar lines against KF2's features
@@ -531,6 +561,8 @@ class ORBmatcher {
                             orbx_kfproj_result* result);  // (defined behind PoseT)
   inline int searchScw(ORBextractor* e, const KeyFrameView& KF, const PoseT& Scw, const MapView& map, std::vector<int>& vpMatched,
                        float th, const float* K, const orbx_bounds& bounds, int thLow, orbx_scw_result* result);  // (defined behind PoseT)
+  inline int fuse(ORBextractor* e, bool scwForm, const KeyFrameView& KF, const PoseT& T, const MapView& map, float th, const float* K,
+                  const orbx_bounds& bounds, FuseOutcome& out, std::vector<int>* vpMapPoints, const std::vector<int>* vnOccObs, int thLow);
   inline int searchForTriangulation(ORBextractor* e, const KeyFrameView& KF1, const KeyFrameView& KF2, const float* K,
                                     std::vector<std::pair<size_t, size_t> >& vMatchedPairs, float medianDepth2,
                                     orbx_tri_match_result* result);  // (defined behind DBoW2::FeatureVector)
@@ -1157,6 +1189,38 @@ inline int ORBmatcher::searchScw(ORBextractor* e, const KeyFrameView& KF, const 
   vpMatched.assign(row.begin(), row.begin() + n);
   if (result) *result = res;
   return res.nmatches;
+}
+
+inline int ORBmatcher::fuse(ORBextractor* e, bool scwForm, const KeyFrameView& KF, const PoseT& T, const MapView& map, float th,
+                            const float* K, const orbx_bounds& bounds, FuseOutcome& out, std::vector<int>* vpMapPoints,
+                            const std::vector<int>* vnOccObs, int thLow) {
+  if (!e) throw orbx::Error(ORBX_E_BADARG, "ORBmatcher: no ORBextractor (device context): none was set");
+  const size_t n = (size_t)(KF.N > 0 ? KF.N : 0), m = (size_t)(map.N > 0 ? map.N : 0);
+  float t12[12];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) t12[r * 3 + c] = (float)T(r, c);
+    t12[9 + r] = (float)T(r, 3);
+  }
+  std::vector<int32_t> row(n, -1), occ, idx(m ? m : 1, -1), other(m ? m : 1, -1);
+  if (vpMapPoints && vpMapPoints->size() == n) row.assign(vpMapPoints->begin(), vpMapPoints->end());
+  if (row.empty()) row.push_back(-1);
+  if (vnOccObs && vnOccObs->size() == n) occ.assign(vnOccObs->begin(), vnOccObs->end());
+  if (vnOccObs && occ.empty()) occ.push_back(-1);
+  std::vector<uint8_t> act(m ? m : 1, 0);
+  const orbx_keypoint* kps = reinterpret_cast<const orbx_keypoint*>(KF.mvKeysUn);
+  const int32_t* occP = vnOccObs ? occ.data() : nullptr;
+  const int r = scwForm ? orbx_fuse_scw(e->context(), kps, KF.mDescriptors, KF.N, map.N, map.mWorldPos, map.mNormalVector,
+                                        map.mfMinMaxDistance, map.mDescriptors, map.mbGood, t12, K, &bounds, th, thLow, row.data(), occP,
+                                        idx.data(), act.data(), other.data(), &out.result)
+                        : orbx_fuse(e->context(), kps, KF.mDescriptors, KF.N, map.N, map.mWorldPos, map.mNormalVector,
+                                    map.mfMinMaxDistance, map.mDescriptors, map.mbGood, map.mnObs, t12, K, &bounds, th, thLow, row.data(),
+                                    occP, idx.data(), act.data(), other.data(), &out.result);
+  if (r != ORBX_OK) throw orbx::Error(r, orbx_last_error(e->context()));
+  if (vpMapPoints) vpMapPoints->assign(row.begin(), row.begin() + n);
+  out.vnFeature.assign(idx.begin(), idx.begin() + m);
+  out.vnOccupant.assign(other.begin(), other.begin() + m);
+  out.vnAction.assign(act.begin(), act.begin() + m);
+  return out.result.n_fused;
 }
 
 inline int ORBmatcher::searchKeyFrame(ORBextractor* e, const FrameView& C, const KeyFrameView& KF, std::vector<int>& vnMatches, float th,

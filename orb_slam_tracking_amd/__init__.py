@@ -25,7 +25,9 @@ __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame",
            "HFResult", "HF_RESULT_DTYPE", "Vocabulary", "BowResult", "BOW_MAX_FEATURES", "Database", "DB_MAX_RESULTS", "debug_database_shape", "InitResult", "INIT_RESULT_DTYPE", "BAResult", "BA_RESULT_DTYPE", "BA_SKIPPED", "BA_BAD_INPUT", "BA_NONFINITE", "BA_FEW_POINTS", "BA_NEGATIVE_DEPTH", "PoseResult", "POSE_RESULT_DTYPE", "POSE_BAD_INPUT", "POSE_NONFINITE", "POSE_FEW_POINTS", "PnpResult", "PNP_RESULT_DTYPE", "PNP_BAD_INPUT", "PNP_NONFINITE", "PNP_FEW_POINTS", "PNP_BAD_DRAWS", "PNP_NO_POSE", "PNP_RAND_MAX", "PnPsolver", "sample_pnp_draws", "Sim3Result", "SIM3_RESULT_DTYPE", "SIM3_BAD_INPUT", "SIM3_NONFINITE", "SIM3_FEW_POINTS", "SIM3_BAD_DRAWS", "SIM3_NO_RESULT", "Sim3Solver", "sample_sim3_draws", "MatchSim3Result", "MSIM3_RESULT_DTYPE", "MSIM3_BAD_INPUT", "MSIM3_NONFINITE", "ProjResult", "PROJ_RESULT_DTYPE", "PROJ_BAD_INPUT", "PROJ_NONFINITE", "LocalResult", "LOCAL_RESULT_DTYPE", "LOCAL_BAD_INPUT", "LOCAL_NONFINITE", "LOCAL_NOT_IN_VIEW", "LOCAL_SEEN", "KfProjResult", "KFPROJ_RESULT_DTYPE", "KFPROJ_BAD_INPUT", "KFPROJ_NONFINITE", "TriMatchResult", "TRI_MATCH_RESULT_DTYPE", "TriResult", "TRI_RESULT_DTYPE", "TRI_BAD_INPUT", "TRI_NONFINITE", "TRI_LOW_BASELINE", "TRI_ZERO_BASELINE", "Optimizer", "sample_sets", "INIT_TOO_FEW_MATCHES", "INIT_BAD_SETS", "INIT_NO_SCORE", "INIT_BAD_MATCHES",
            "STAGES", "E_EMPTY", "E_BADARG", "E_TOOSMALL", "E_HIP", "E_CAPACITY", "E_RCCL",
            "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE",
-           "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted"]
+           "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted",
+           "MapFuser", "FuseResult", "FUSE_RESULT_DTYPE", "FUSE_BAD_INPUT", "FUSE_NONFINITE", "FUSE_OCCUPIED_UNMAPPED", "FUSE_NONE",
+           "FUSE_ADD", "FUSE_KEEP_OCCUPANT", "FUSE_REPLACE_OCCUPANT", "FUSE_BAD_OCCUPANT"]
 
 from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResult, HF_RESULT_DTYPE, InitResult,  # noqa: F401
                        INIT_RESULT_DTYPE, BAResult, BA_RESULT_DTYPE, PoseResult, POSE_RESULT_DTYPE, PnpResult, PNP_RESULT_DTYPE,
@@ -33,7 +35,7 @@ from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResu
                        PROJ_RESULT_FIELDS, LocalResult, LOCAL_RESULT_DTYPE, LOCAL_RESULT_FIELDS, MatchScwResult, SCW_RESULT_DTYPE,
                        SCW_RESULT_FIELDS, KfProjResult, KFPROJ_RESULT_DTYPE, KFPROJ_RESULT_FIELDS, MatchSim3Result,
                        MSIM3_RESULT_DTYPE, MSIM3_RESULT_FIELDS, TriMatchResult, TRI_MATCH_RESULT_DTYPE, TRI_MATCH_COUNTERS,
-                       TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS)
+                       TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS, FuseResult, FUSE_RESULT_DTYPE, FUSE_RESULT_FIELDS)
 
 E_EMPTY, E_BADARG, E_TOOSMALL, E_HIP, E_CAPACITY, E_RCCL = -1, -2, -3, -4, -5, -6
 _ERRNAMES = {-1: "ORBX_E_EMPTY", -2: "ORBX_E_BADARG", -3: "ORBX_E_TOOSMALL", -4: "ORBX_E_HIP", -5: "ORBX_E_CAPACITY", -6: "ORBX_E_RCCL"}
@@ -58,6 +60,8 @@ SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
 LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
 SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
+FUSE_BAD_INPUT, FUSE_NONFINITE, FUSE_OCCUPIED_UNMAPPED = 2, 4, -2
+FUSE_NONE, FUSE_ADD, FUSE_KEEP_OCCUPANT, FUSE_REPLACE_OCCUPANT, FUSE_BAD_OCCUPANT = 0, 1, 2, 3, 4
 KFPROJ_BAD_INPUT, KFPROJ_NONFINITE = 2, 4
 MSIM3_BAD_INPUT, MSIM3_NONFINITE = 2, 4
 TRI_BAD_INPUT, TRI_NONFINITE, TRI_LOW_BASELINE, TRI_ZERO_BASELINE = 2, 4, 8, 16
@@ -248,6 +252,14 @@ def lib() -> ctypes.CDLL:
                                  ctypes.POINTER(MatchScwResult)]
     L.orbx_sim3_compose_scw_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     L.orbx_sim3_compose_scw.argtypes = [vp, vp, vp, vp]
+    L.orbx_fuse_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_fuse_scw_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_fuse.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp, vp, vp,
+                            ctypes.POINTER(FuseResult)]
+    L.orbx_fuse_scw.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp, vp, vp,
+                                ctypes.POINTER(FuseResult)]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -2127,6 +2139,105 @@ class Database:
         return rs, pe[:n], pv[:n]
 
 
+class MapFuser:
+    """ORBmatcher::Fuse, both overloads, on the device of an extractor's context (include/orbx.h, "fusing map points into a
+    keyframe", with its documented deviations): MapFuser(extractor).  The keyframes and the map sets are the arrays of
+    ORBextractor.match_scw_pairs_device; the fuser keeps its extractor alive."""
+
+    def __init__(self, extractor: ORBextractor):
+        self._ext, self._L = extractor, extractor._L
+
+    def _pairs_device(self, fn, n_frames, kf, map_set, d_kps_un, d_desc, d_n, n_map_sets, map_capacity, d_map_n, d_map_points,
+                      d_map_normals, d_map_dist, d_map_desc, d_map_mask, obs, d_pose, K, bounds, d_matches, d_occ_obs, d_fuse_idx,
+                      d_fuse_act, d_fuse_other, d_res, th, th_low, capacity):
+        cap, mcap, nf, ns = int(capacity or self._ext.capacity), int(map_capacity), int(n_frames), int(n_map_sets)
+        kf, map_set = _pair_lists(("kf", "map_set"), (kf, map_set), nf, ns, "map set")
+        P = len(kf)
+        self._ext._device_call(fn, nf, P, kf, map_set, ("the keypoint array", d_kps_un, nf * cap * 28),
+                               ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, ns, mcap,
+                               ("the map count array", d_map_n, ns * 4), ("the map point array", d_map_points, ns * mcap * 12),
+                               ("the map normal array", d_map_normals, ns * mcap * 12), ("the map distance array", d_map_dist, ns * mcap * 8),
+                               ("the map descriptor array", d_map_desc, ns * mcap * 32), ("the map mask", d_map_mask, ns * mcap), *obs,
+                               d_pose + (P * 48,), _k9(K), ctypes.byref(_bounds(bounds)), float(th), int(th_low),
+                               ("matches", d_matches, P * cap * 4), ("the occupants' observation counts", d_occ_obs, P * cap * 4),
+                               ("the picked-feature array", d_fuse_idx, P * mcap * 4), ("the action array", d_fuse_act, P * mcap),
+                               ("the occupant array", d_fuse_other, P * mcap * 4),
+                               ("the result array", d_res, P * FUSE_RESULT_DTYPE.itemsize))
+
+    def fuse_pairs_device(self, n_frames: int, kf, map_set, d_kps_un, d_desc, d_n, n_map_sets: int, map_capacity: int, d_map_n,
+                          d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_map_obs, d_pose, K,
+                          bounds: Tuple[int, int, int, int], d_matches, d_occ_obs, d_fuse_idx, d_fuse_act, d_fuse_other, d_res,
+                          th: float = 3.0, th_low: int = 50, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) of LocalMapping::SearchInNeighbors for pairs (keyframe kf[p], map set
+        map_set[p]; host index arrays).  d_map_obs int32 [n_map_sets, map_capacity]: Observations(); d_pose float32 [n_pairs, 12]
+        (Rcw row-major, then tcw).  d_matches int32 [n_pairs, capacity] is read and written: mvpMapPoints as indices into the
+        pair's set, FUSE_OCCUPIED_UNMAPPED, or another negative value (free); d_occ_obs int32 [n_pairs, capacity] or None: the
+        unmapped occupants' Observations(), negative = isBad().  Per map point: d_fuse_idx int32 / d_fuse_act uint8 /
+        d_fuse_other int32 [n_pairs, map_capacity]; d_res [n_pairs] FUSE_RESULT_DTYPE records (64 bytes).  Stream-ordered on the
+        context's stream."""
+        self._pairs_device("orbx_fuse_batch_device", n_frames, kf, map_set, d_kps_un, d_desc, d_n, n_map_sets, map_capacity, d_map_n,
+                           d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask,
+                           [("the map observation array", d_map_obs, int(n_map_sets) * int(map_capacity) * 4)],
+                           ("the pose array", d_pose), K, bounds, d_matches, d_occ_obs, d_fuse_idx,
+                           d_fuse_act, d_fuse_other, d_res, th, th_low, capacity)
+
+    def fuse_scw_pairs_device(self, n_frames: int, kf, map_set, d_kps_un, d_desc, d_n, n_map_sets: int, map_capacity: int, d_map_n,
+                              d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, d_scw, K,
+                              bounds: Tuple[int, int, int, int], d_matches, d_occ_obs, d_fuse_idx, d_fuse_act, d_fuse_other, d_res,
+                              th: float = 4.0, th_low: int = 50, capacity: Optional[int] = None) -> None:
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse for pairs: as
+        fuse_pairs_device with d_scw float32 [n_pairs, 12] (what sim3_compose_scw_pairs_device writes) in place of the pose and
+        without observation counts; d_occ_obs is read for its sign only.  d_fuse_other is vpReplacePoint."""
+        self._pairs_device("orbx_fuse_scw_batch_device", n_frames, kf, map_set, d_kps_un, d_desc, d_n, n_map_sets, map_capacity, d_map_n,
+                           d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, [],
+                           ("the Scw array", d_scw), K, bounds, d_matches, d_occ_obs, d_fuse_idx,
+                           d_fuse_act, d_fuse_other, d_res, th, th_low, capacity)
+
+    def _one(self, scw_form, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, T, K, bounds, matches,
+             occ_obs, th, th_low):
+        k = _keys(keys_un)
+        d = _desc(desc)
+        mp = _points(map_points)
+        mn = _points(map_normals)
+        md = _points(map_dist, 2)
+        mdesc = _desc(map_desc)
+        if len(k) != len(d) or not (len(mp) == len(mn) == len(md) == len(mdesc)):
+            raise OrbxError(E_BADARG, "keypoints / descriptors or the map arrays differ in length")
+        mm = _flags(map_mask, len(mp), "the map mask needs one entry per map point")
+        m = _row(matches, len(k), "matches needs one entry per feature")
+        occ = None if occ_obs is None else _row(occ_obs, len(k), "occ_obs needs one entry per feature")
+        nm = max(len(mp), 1)
+        idx, act, other = np.full(nm, -1, np.int32), np.zeros(nm, np.uint8), np.full(nm, -1, np.int32)
+        S, Kf, b, res = _pose12(T), _k9(K), _bounds(bounds), FuseResult()
+        head = (self._ext._h, _ptr(k), _ptr(d), len(k), len(mp), _ptr(mp), _ptr(mn), _ptr(md), _ptr(mdesc), _ptr(mm))
+        tail = (_ptr(S), _ptr(Kf), ctypes.byref(b), float(th), int(th_low), _ptr(m), _ptr(occ), _ptr(idx), _ptr(act), _ptr(other),
+                ctypes.byref(res))
+        if scw_form:
+            r, fn = self._L.orbx_fuse_scw(*head, *tail), "orbx_fuse_scw"
+        else:
+            if map_obs is None:
+                raise OrbxError(E_BADARG, "MapFuser.fuse needs map_obs, the Observations() of every map point")
+            obs = _row(map_obs, len(mp), "map_obs needs one entry per map point")
+            r, fn = self._L.orbx_fuse(*head, _ptr(obs), *tail), "orbx_fuse"
+        self._ext._check(r, fn)
+        return m[:len(k)].copy(), idx[:len(mp)].copy(), act[:len(mp)].copy(), other[:len(mp)].copy(), res
+
+    def fuse(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, Tcw, K,
+             bounds: Tuple[int, int, int, int], matches=None, occ_obs=None, th: float = 3.0, th_low: int = 50):
+        """One keyframe and one map set in host memory (orbx_fuse) -> (row int32 [len(keys_un)], idx, act, other [n points],
+        FuseResult).  Tcw: 12 floats (Rcw row-major, then tcw) or a 3x4 / 4x4 matrix; matches (default all -1): mvpMapPoints as
+        indices into the map arrays.  Synchronous."""
+        return self._one(False, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, Tcw, K, bounds, matches,
+                         occ_obs, th, th_low)
+
+    def fuse_scw(self, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K,
+                 bounds: Tuple[int, int, int, int], matches=None, occ_obs=None, th: float = 4.0, th_low: int = 50):
+        """The Scw form for one keyframe and one map set in host memory (orbx_fuse_scw) -> (row, idx, act, other, FuseResult);
+        other is vpReplacePoint.  Synchronous."""
+        return self._one(True, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, None, Scw, K, bounds, matches,
+                         occ_obs, th, th_low)
+
+
 class Frame:
     """The slice of SlamTypes/Frame.{hpp,cpp} on this path: runs the extractor (Frame.cpp:58-60), undistorts the
     keypoints (Frame.cpp:136-161) and keeps mvKeys / mvKeysUn / mDescriptors / N and the image bounds
@@ -2289,6 +2400,29 @@ class ORBmatcher:
         m, res = ext.match_scw(KF.mvKeysUn, KF.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask, Scw, K, KF.bounds,
                                matched, th, th_low, kf2_to_map)
         return int(res.nmatches), m, res
+
+    def Fuse(self, KF: Frame, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, Tcw, th: float = 3.0, K=None,
+             matches=None, occ_obs=None, th_low: int = 50):
+        """ORB-SLAM2's Fuse(pKF, vpMapPoints, th) (include/orbx.h, "fusing map points into a keyframe") -> (nFused, row, idx, act,
+        other, FuseResult).  The map arrays are SearchLocalPoints' plus map_obs, the points' Observations(); Tcw: KF's pose;
+        matches (optional): KF's mvpMapPoints as indices into the map arrays (FUSE_OCCUPIED_UNMAPPED: a point that is not among
+        them, with its Observations() in occ_obs); K: 3x3, default KF's camera.  The caller applies the decisions (Replace,
+        AddObservation) from idx / act / other."""
+        ext = self._extractor(KF)
+        K = _camera_K(K, KF, "ORBmatcher.Fuse", "keyframe")
+        row, idx, act, other, res = MapFuser(ext).fuse(KF.mvKeysUn, KF.mDescriptors, map_points, map_normals, map_dist, map_desc, map_mask,
+                                                       map_obs, Tcw, K, KF.bounds, matches, occ_obs, th, th_low)
+        return int(res.n_fused), row, idx, act, other, res
+
+    def FuseScw(self, KF: Frame, Scw, map_points, map_normals, map_dist, map_desc, map_mask, th: float = 4.0, K=None, matches=None,
+                occ_obs=None, th_low: int = 50):
+        """ORB-SLAM2's Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse -> (nFused, row, idx, act,
+        vpReplacePoint, FuseResult): vpReplacePoint[i] is the point of KF that map point i is to replace, or -1."""
+        ext = self._extractor(KF)
+        K = _camera_K(K, KF, "ORBmatcher.FuseScw", "keyframe")
+        row, idx, act, other, res = MapFuser(ext).fuse_scw(KF.mvKeysUn, KF.mDescriptors, map_points, map_normals, map_dist, map_desc,
+                                                           map_mask, Scw, K, KF.bounds, matches, occ_obs, th, th_low)
+        return int(res.n_fused), row, idx, act, other, res
 
     def SearchByProjectionKeyFrame(self, CurrentFrame: Frame, KF: Frame, points, mask, point_dist, Tcw, th: float = 10.0, ORBdist: int = 100,
                                    K=None, matches=None, outlier=None, point_desc=None):

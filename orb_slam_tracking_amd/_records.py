@@ -1,6 +1,8 @@
 """The records of ``include/orbx.h`` the package exchanges with liborbx.so, each described ONCE: a field list in the header's
 order, from which ``_record`` makes the ``ctypes.Structure`` subclass, the numpy dtype and ``as_dict``.  RECORDS keeps every
-pair under its C struct's name; tests/test_abi_host.py compiles a probe against the header and compares sizes and offsets."""
+pair under its C struct's name; tests/test_abi_host.py compiles a probe against the header and compares sizes and offsets.
+RECORDS_FUSE is a second table of the same form for the records of "fusing map points into a keyframe"
+(tests/test_fuse_abi_host.py probes it the same way)."""
 from __future__ import annotations
 
 import ctypes
@@ -10,6 +12,7 @@ import numpy as np
 
 _CTYPES = {"i4": ctypes.c_int32, "f4": ctypes.c_float, "f8": ctypes.c_double}
 RECORDS = {}  # C struct name -> (ctypes.Structure subclass or None, numpy dtype)
+RECORDS_FUSE = {}  # the same for orbx_fuse_result
 
 
 def _as_dict(self) -> dict:
@@ -26,11 +29,11 @@ def _as_dict(self) -> dict:
     return d
 
 
-def _record(c_name: str, py_name: str, fields, doc: str = None):
+def _record(c_name: str, py_name: str, fields, doc: str = None, table: dict = None):
     """(ctypes.Structure subclass, numpy dtype) of one C struct.  A field is (name, kind[, shape[, form]]): kind "i4" / "f4" /
     "f8"; shape None for a scalar, an int or a tuple for an array; form how as_dict returns an array when not as a numpy array of
     `shape` -- another shape, or `list`.  A name that is a Python keyword (lambda) gets a trailing underscore as the ctypes
-    attribute and keeps its own name in the dtype and in as_dict."""
+    attribute and keeps its own name in the dtype and in as_dict.  The pair is kept in `table` (default RECORDS)."""
     norm = []
     for f in fields:
         name, kind, shape, form = (tuple(f) + (None, None))[:4]
@@ -43,7 +46,7 @@ def _record(c_name: str, py_name: str, fields, doc: str = None):
                                               "__doc__": doc, "__module__": __package__})
     dtype = np.dtype([(n, "<" + k) if s is None else (n, "<" + k, s) for n, k, s, _ in norm])
     assert dtype.itemsize == ctypes.sizeof(cls), c_name
-    RECORDS[c_name] = (cls, dtype)
+    (RECORDS if table is None else table)[c_name] = (cls, dtype)
     return cls, dtype
 
 
@@ -174,3 +177,12 @@ TriResult, TRI_RESULT_DTYPE = _record(
     "orbx_tri_result", "TriResult", _ints(*TRI_RESULT_FIELDS),
     "orbx_tri_result: CreateNewMapPoints' counters for one (KF1, KF2) pair, one per gate.")
 assert TRI_RESULT_DTYPE.itemsize == 44
+
+FUSE_RESULT_FIELDS = ("status", "n_fused", "n_points", "n_in_kf", "n_behind", "n_out_image", "n_out_distance", "n_out_angle",
+                      "n_with_candidates", "n_over_dist", "n_added", "n_kept_occupant", "n_replaced_occupant", "n_bad_occupant", "n_chained",
+                      "rounds")
+FuseResult, FUSE_RESULT_DTYPE = _record(
+    "orbx_fuse_result", "FuseResult", _ints(*FUSE_RESULT_FIELDS),
+    """orbx_fuse_result: ORBmatcher::Fuse's counters for one (keyframe, map set) pair, either overload (n_fused is the design's
+    return value; rounds is the device's own count).""", table=RECORDS_FUSE)
+assert FUSE_RESULT_DTYPE.itemsize == 64

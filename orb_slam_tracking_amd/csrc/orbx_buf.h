@@ -186,6 +186,8 @@ struct MatchBowScratch {
   HeldArray<int32_t> sim3Pairs;    // [4][n_pairs] (KF1, KF2, set 1, set 2) of orbx_match_sim3*
   HeldArray<int32_t> scwPairs;     // [2][n_pairs] (current keyframe, map set) of orbx_match_scw*
   HeldArray<int32_t> composeKf2;   // [n_pairs] (matched keyframe) of orbx_sim3_compose_scw*
+  HeldArray<int32_t> fusePairs;    // [2][n_pairs] (keyframe, map set) of orbx_fuse*
+  HeldArray<int32_t> fuseScwPairs; // [2][n_pairs] (keyframe, map set) of orbx_fuse_scw*
 };
 
 // What a context keeps for orbx_match_triangulation* and orbx_triangulate_matches* (orbx_match_bow.cpp).

@@ -551,6 +551,31 @@ struct Sim3ComposeArgs {
   float* scw;                 // [nPairs][12]
 };
 
+// ---- ORBmatcher::Fuse, both overloads (orbx_match_fuse_kernel.hip): one workgroup of MP_THREADS per (keyframe, map set) pair ----
+struct MatchFuseArgs {
+  const orbx_keypoint* kps;   // [nFrames][cap] undistorted
+  const uint8_t* desc;        // [nFrames][cap][32], 16-byte aligned
+  const int32_t* n;           // [nFrames] (clamped to [0, cap])
+  const int32_t* mapN;        // [nSets] (clamped to [0, mapCap])
+  const float* mapPoints;     // [nSets][mapCap][3]
+  const float* mapNormals;    // [nSets][mapCap][3]
+  const float* mapDist;       // [nSets][mapCap][2] mfMinDistance, mfMaxDistance
+  const uint8_t* mapDesc;     // [nSets][mapCap][32], 16-byte aligned
+  const uint8_t* mapMask;     // nullable [nSets][mapCap]
+  const int32_t* mapObs;      // [nSets][mapCap] Observations(); the pose form only (null in the Scw form)
+  const float* pose;          // [nPairs][12]: Rcw row-major, then tcw (pose form); sR row-major, then t (Scw form)
+  const int32_t* pairs;       // [2][nPairs] keyframes, map sets
+  int32_t cap, mapCap, nPairs, thLow;
+  MatchCamArgs cam;
+  float invSigma2[ORBX_MAX_LEVELS];  // the context's mvInvLevelSigma2 (the pose form's chi-square gate)
+  int32_t* matches;           // [nPairs][cap] in and out
+  const int32_t* occObs;      // nullable [nPairs][cap]
+  int32_t* fuseIdx;           // [nPairs][mapCap]
+  uint8_t* fuseAct;           // [nPairs][mapCap]
+  int32_t* fuseOther;         // [nPairs][mapCap]
+  orbx_fuse_result* res;      // [nPairs]
+};
+
 // ---- ORBmatcher::SearchBySim3 (orbx_match_sim3_kernel.hip): one workgroup of MP_THREADS per (KF1, KF2) pair ----
 struct MatchSim3Args {
   const orbx_keypoint* kps;   // [nFrames][cap] undistorted

@@ -108,6 +108,8 @@ hipError_t launch_match_sim3(hipStream_t st, const MatchSim3Args& a);
 // orbx_match_scw_kernel.hip
 hipError_t launch_match_scw(hipStream_t st, const MatchScwArgs& a);
 hipError_t launch_sim3_compose_scw(hipStream_t st, const Sim3ComposeArgs& a);
+// orbx_match_fuse_kernel.hip (scwForm: a.pose holds similarities and there is no chi-square gate)
+hipError_t launch_match_fuse(hipStream_t st, const MatchFuseArgs& a, bool scwForm);
 
 // orbx_sim3opt_kernel.hip
 hipError_t launch_sim3_optimize(hipStream_t st, const Sim3OptArgs& a);

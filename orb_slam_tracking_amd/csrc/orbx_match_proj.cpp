@@ -1,9 +1,9 @@
 // orbx_match_proj.cpp — host side of the matchers by projection: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame)
 // (include/orbx.h, "matching by projection"), Tracking::SearchLocalPoints ("matching the local map by projection") and the
 // relocalisation overload ("matching a keyframe's points by projection"): the argument checks, the index lists and the C entry
-// points; behind them SearchBySim3 and the loop-closing overload under Scw with its composition.  The kernels are in
-// orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip, orbx_match_kfproj_kernel.hip, orbx_match_sim3_kernel.hip and
-// orbx_match_scw_kernel.hip.
+// points; behind them SearchBySim3, the loop-closing overload under Scw with its composition, and both overloads of Fuse.  The
+// kernels are in orbx_match_proj_kernel.hip, orbx_match_local_kernel.hip, orbx_match_kfproj_kernel.hip,
+// orbx_match_sim3_kernel.hip, orbx_match_scw_kernel.hip and orbx_match_fuse_kernel.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -533,6 +533,158 @@ int orbx_sim3_compose_scw(orbx_ctx* ctx, const float* pose2, const float* sim3, 
   const int32_t kf2 = 0;
   r = orbx_sim3_compose_scw_batch_device(ctx, 1, 1, &kf2, io[dPose], io[dSim], io[dScw]);
   return io.close(ctx, r);
+}
+
+}  // extern "C"
+
+// ---- ORBmatcher::Fuse, both overloads (include/orbx.h, "fusing map points into a keyframe"; orbx_match_fuse_kernel.hip)
+namespace {
+
+// Both batch calls: d_pose holds poses (d_map_obs required) or, with scwForm, similarities (d_map_obs null).
+int fuseBatch(orbx_ctx* ctx, bool scwForm, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+              const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity, int n_map_sets, int map_capacity,
+              const int32_t* d_map_n, const float* d_map_points, const float* d_map_normals, const float* d_map_dist,
+              const uint8_t* d_map_desc32, const uint8_t* d_map_mask, const int32_t* d_map_obs, const float* d_pose, const float* K,
+              const orbx_bounds* bounds, float th, int th_low, int32_t* d_matches, const int32_t* d_occ_obs, int32_t* d_fuse_idx,
+              uint8_t* d_fuse_act, int32_t* d_fuse_other, orbx_fuse_result* d_res) {
+  if (n_frames < 0 || n_pairs < 0 || n_map_sets < 0 || capacity < 1 || map_capacity < 1 || (n_pairs > 0 && (!h_kf || !h_map_set)) ||
+      !d_kps_un || !d_desc32 || !d_n || !d_map_n || !d_map_points || !d_map_normals || !d_map_dist || !d_map_desc32 ||
+      (!scwForm && !d_map_obs) || !d_pose || !K || !bounds || !d_matches || !d_fuse_idx || !d_fuse_act || !d_fuse_other || !d_res)
+    return ORBX_E_BADARG;
+  const char* name = scwForm ? "fuse scw" : "fuse";
+  int r = refused(ctx, name, th, th_low < 0 || th_low > 256 ? "th_low outside [0, 256]" : nullptr, bounds,
+                  pairsInRange(h_kf, h_map_set, n_pairs, n_frames, n_map_sets)
+                      ? nullptr
+                      : "keyframe outside [0, n_frames) or map set outside [0, n_map_sets)",
+                  capacity > ORBX_BOW_MAX_FEATURES || map_capacity > ORBX_BOW_MAX_FEATURES
+                      ? "capacity or map_capacity above ORBX_BOW_MAX_FEATURES"
+                      : nullptr);
+  if (r != ORBX_OK) return r;
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_pairs == 0) return ORBX_OK;
+  HeldArray<int32_t>& pairs = scwForm ? ctxMatchBow(ctx)->fuseScwPairs : ctxMatchBow(ctx)->fusePairs;
+  hipStream_t st;
+  r = listsHeld(ctx, pairs, {h_kf, h_map_set}, n_pairs, &st);
+  if (r != ORBX_OK) return r;
+  MatchFuseArgs a{};
+  a.kps = d_kps_un;
+  a.desc = d_desc32;
+  a.n = d_n;
+  a.mapN = d_map_n;
+  a.mapPoints = d_map_points;
+  a.mapNormals = d_map_normals;
+  a.mapDist = d_map_dist;
+  a.mapDesc = d_map_desc32;
+  a.mapMask = d_map_mask;
+  a.mapObs = d_map_obs;
+  a.pose = d_pose;
+  a.pairs = pairs;
+  a.cap = capacity;
+  a.mapCap = map_capacity;
+  a.nPairs = n_pairs;
+  a.thLow = th_low;
+  a.cam = camArgs(ctx, K, bounds, th);
+  int nLevels = 0;
+  const float* inv = ctxInvSigma2(ctx, &nLevels);
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) a.invSigma2[l] = l < nLevels ? inv[l] : 0.0f;
+  a.matches = d_matches;
+  a.occObs = d_occ_obs;
+  a.fuseIdx = d_fuse_idx;
+  a.fuseAct = d_fuse_act;
+  a.fuseOther = d_fuse_other;
+  a.res = d_res;
+  HIPCHK(launch_match_fuse(st, a, scwForm));
+  return ORBX_OK;
+}
+
+// Both host forms: one keyframe and one map set in the context's staging block, through fuseBatch as a batch of one.
+int fuseOne(orbx_ctx* ctx, bool scwForm, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+            const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask, const int32_t* map_obs,
+            const float* pose, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches, const int32_t* occ_obs,
+            int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other, orbx_fuse_result* res) {
+  if (n < 0 || map_n < 0 || !pose || !K || !bounds || !res || (n > 0 && (!kps_un || !desc32 || !matches)) ||
+      (map_n > 0 && (!map_points || !map_normals || !map_dist || !map_desc32 || (!scwForm && !map_obs) || !fuse_idx || !fuse_act ||
+                     !fuse_other)))
+    return ORBX_E_BADARG;
+  const int cap = std::max(n, 1), mapCap = std::max(map_n, 1);
+  if (cap > ORBX_BOW_MAX_FEATURES || mapCap > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctxSetError(ctx, "fuse: more than ORBX_BOW_MAX_FEATURES features or points");
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  int r = ctxDrain(ctx);
+  if (r != ORBX_OK) return r;
+  const size_t c = (size_t)cap, mc = (size_t)mapCap;
+  const int32_t hn[2] = {n, map_n};
+  Staged io(ctxIo(ctx), ctxStream(ctx));  // one keyframe and one map set in the batch layout, then the results
+  auto dK = io.in(kps_un, n, c);
+  auto dD = io.in(desc32, (size_t)n * 32, c * 32);
+  auto dMD = io.in(map_desc32, (size_t)map_n * 32, mc * 32);
+  auto dP = io.in(map_points, (size_t)map_n * 3, mc * 3);
+  auto dNrm = io.in(map_normals, (size_t)map_n * 3, mc * 3);
+  auto dDist = io.in(map_dist, (size_t)map_n * 2, mc * 2);
+  auto dObs = io.in(map_obs, (size_t)map_n, mc);  // (the Scw form brings none and reads none)
+  auto dMask = io.optIn(map_mask, map_n, mc);
+  auto dOcc = io.optIn(occ_obs, n, c);
+  auto dPose = io.in(pose, 12, 12);
+  auto dN = io.in(hn, 2, 2);
+  auto dM = io.inout(matches, n, c);
+  auto dIdx = io.out(fuse_idx, map_n, mc);
+  auto dAct = io.out(fuse_act, map_n, mc);
+  auto dOther = io.out(fuse_other, map_n, mc);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  const int32_t frame = 0, set = 0;
+  r = fuseBatch(ctx, scwForm, 1, 1, &frame, &set, io[dK], io[dD], io[dN], cap, 1, mapCap, io[dN] + 1, io[dP], io[dNrm], io[dDist], io[dMD],
+                io[dMask], scwForm ? nullptr : io[dObs], io[dPose], K, bounds, th, th_low, io[dM], io[dOcc], io[dIdx], io[dAct],
+                io[dOther], io[dR]);
+  return io.close(ctx, r);
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_fuse_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                           const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity, int n_map_sets,
+                           int map_capacity, const int32_t* d_map_n, const float* d_map_points, const float* d_map_normals,
+                           const float* d_map_dist, const uint8_t* d_map_desc32, const uint8_t* d_map_mask, const int32_t* d_map_obs,
+                           const float* d_pose, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* d_matches,
+                           const int32_t* d_occ_obs, int32_t* d_fuse_idx, uint8_t* d_fuse_act, int32_t* d_fuse_other,
+                           orbx_fuse_result* d_res) {
+  if (!d_map_obs) return ORBX_E_BADARG;
+  return fuseBatch(ctx, false, n_frames, n_pairs, h_kf, h_map_set, d_kps_un, d_desc32, d_n, capacity, n_map_sets, map_capacity, d_map_n,
+                   d_map_points, d_map_normals, d_map_dist, d_map_desc32, d_map_mask, d_map_obs, d_pose, K, bounds, th, th_low, d_matches,
+                   d_occ_obs, d_fuse_idx, d_fuse_act, d_fuse_other, d_res);
+}
+
+int orbx_fuse_scw_batch_device(orbx_ctx* ctx, int n_frames, int n_pairs, const int32_t* h_kf, const int32_t* h_map_set,
+                               const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                               int n_map_sets, int map_capacity, const int32_t* d_map_n, const float* d_map_points,
+                               const float* d_map_normals, const float* d_map_dist, const uint8_t* d_map_desc32,
+                               const uint8_t* d_map_mask, const float* d_scw, const float* K, const orbx_bounds* bounds, float th,
+                               int th_low, int32_t* d_matches, const int32_t* d_occ_obs, int32_t* d_fuse_idx, uint8_t* d_fuse_act,
+                               int32_t* d_fuse_other, orbx_fuse_result* d_res) {
+  return fuseBatch(ctx, true, n_frames, n_pairs, h_kf, h_map_set, d_kps_un, d_desc32, d_n, capacity, n_map_sets, map_capacity, d_map_n,
+                   d_map_points, d_map_normals, d_map_dist, d_map_desc32, d_map_mask, nullptr, d_scw, K, bounds, th, th_low, d_matches,
+                   d_occ_obs, d_fuse_idx, d_fuse_act, d_fuse_other, d_res);
+}
+
+int orbx_fuse(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+              const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+              const int32_t* map_obs, const float* pose, const float* K, const orbx_bounds* bounds, float th, int th_low,
+              int32_t* matches, const int32_t* occ_obs, int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other,
+              orbx_fuse_result* res) {
+  return fuseOne(ctx, false, kps_un, desc32, n, map_n, map_points, map_normals, map_dist, map_desc32, map_mask, map_obs, pose, K, bounds,
+                 th, th_low, matches, occ_obs, fuse_idx, fuse_act, fuse_other, res);
+}
+
+int orbx_fuse_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* desc32, int n, int map_n, const float* map_points,
+                  const float* map_normals, const float* map_dist, const uint8_t* map_desc32, const uint8_t* map_mask,
+                  const float* scw, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches,
+                  const int32_t* occ_obs, int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other, orbx_fuse_result* res) {
+  return fuseOne(ctx, true, kps_un, desc32, n, map_n, map_points, map_normals, map_dist, map_desc32, map_mask, nullptr, scw, K, bounds,
+                 th, th_low, matches, occ_obs, fuse_idx, fuse_act, fuse_other, res);
 }
 
 }  // extern "C"
