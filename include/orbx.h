@@ -1241,6 +1241,133 @@ int orbx_fuse_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* des
                   const float* scw, const float* K, const orbx_bounds* bounds, float th, int th_low, int32_t* matches,
                   const int32_t* occ_obs, int32_t* fuse_idx, uint8_t* fuse_act, int32_t* fuse_other, orbx_fuse_result* res);
 
+/* ---- local mapping: local bundle adjustment (Optimizer::LocalBundleAdjustment) ------------------------------------------------
+ * What LocalMapping calls behind SearchInNeighbors: the keyframes of the local window (free), the keyframes outside it that see
+ * the window's points (fixed) and those points are made consistent with each other, for a batch of independent problems, on
+ * the rows orbx_match_local_map* / orbx_match_scw* / orbx_fuse* leave and the points orbx_triangulate_matches* writes.  The
+ * reference vendors g2o but no Optimizer: the rules restate the monocular Optimizer::LocalBundleAdjustment(pKF, pbStopFlag,
+ * pMap) of the ORB-SLAM2 design [from-knowledge] over the vendored g2o sources -- types/types_six_dof_expmap.h:40-102 and
+ * .cpp:98-134 (VertexSE3Expmap, EdgeSE3ProjectXYZ), core/block_solver.hpp:354-486 (the Schur complement),
+ * core/optimization_algorithm_levenberg.cpp:61-189, core/sparse_optimizer.cpp:376-414, core/robust_kernel_impl.cpp:78-91,
+ * solvers/linear_solver_eigen.h (the reduced system's solver, replaced: deviation 1) -- PARITY UNPINNED, as the two-view bundle
+ * adjustment above, whose arithmetic (csrc/orbx_ba_math.inc) this shares.  The device equals the CPU restatement
+ * tests/cpp/lba_ref.cpp bit for bit.
+ *
+ * A problem is a run of entries in a flat entry list and one map set.  Entry e names a frame (its row of d_kps_un / d_n /
+ * d_pose float [n_frames][12], Rcw row-major then tcw) and owns row e of d_rows int32 [n_entries][capacity]: the keyframe's
+ * mvpMapPoints as indices into the problem's map set (d_map_n, d_map_points float [n_map_sets][map_capacity][3], d_map_mask
+ * uint8, NULL = every point), entries below 0 (-2 for an unmapped point included) being no observation.  The first n_free
+ * entries of a problem are lLocalKeyFrames, the rest lFixedCameras; the caller puts keyframe 0 of the map among the fixed ones.
+ *
+ * Rules:
+ *  1. Graph.  One VertexSE3Expmap per entry, SE3Quat(R, t) of its f32 pose, the free ones first in list order.  One marginalised
+ *     VertexSBAPointXYZ per map point below map_n whose mask byte is set and that a free entry observes, ascending index, f32 ->
+ *     f64.  One EdgeSE3ProjectXYZ per (entry, feature) whose row names such a point: measurement = the undistorted keypoint,
+ *     information = inv_sigma2[octave] * I, RobustKernelHuber with delta = (float)sqrt(5.991) (`const float thHuberMono`).
+ *  2. Round 1: optimize(n_iterations) (5): Levenberg-Marquardt exactly as rules 1-7 of the two-view section --
+ *     computeLambdaInit over the diagonals of every active free pose and point, up to 10 trials, the _nBad rule -- with
+ *     BlockSolver_6_3's Schur complement over all free poses: Hschur = Hpp + lambda I - sum Hpl (Hll + lambda I)^-1 Hpl^T, bschur
+ *     = bp - sum Hpl (Hll + lambda I)^-1 bl, xl = (Hll + lambda I)^-1 (bl - Hpl^T xp).  An edge to a fixed keyframe adds to Hll,
+ *     bl and chi2 only.
+ *  3. Between the rounds every edge with chi2() > 5.991 || !isDepthPositive() goes to level 1 and every edge loses its robust
+ *     kernel.  chi2() is e . (information e) of the error as LAST COMPUTED: g2o's stale errors are kept as in
+ *     orbx_pose_optimize* (the errors are those of the round's last trial, accepted or not; a trial whose solve failed computes
+ *     none).  isDepthPositive uses the current estimates.
+ *  4. Round 2: initializeOptimization(0), optimize(n_more_iterations) (10): a fresh run (lambda initialised again, _ni = 2,
+ *     _nBad = 0) over the level-0 edges without kernel (rho = (chi2, 1)).  A vertex without an active edge is not part of the
+ *     round: its estimate keeps its bits, it adds nothing to the system, to computeLambdaInit or to computeScale.  (The same
+ *     holds in round 1 for a free keyframe that observes nothing.)
+ *  5. Behind round 2 the test of rule 3, over ALL edges, fills d_obs_outlier (vToErase).  Free poses go out as f32 Tcw: the
+ *     rotation matrix of the quaternion, as orbx_bundle_adjust* writes R21; points go out as f32.
+ * UpdateNormalAndDepth, the SetWorldPos / SetPose bookkeeping and the erasures themselves (EraseMapPointMatch /
+ * EraseObservation for every set byte of d_obs_outlier) stay with the caller.
+ *
+ * Documented deviations:
+ *  1. Linear solver.  The reduced system of the active free poses (6 x their count, in entry order) is dense and solved by an
+ *     unpivoted Cholesky factorisation: column by column, every element receiving its terms in ascending column; L y = b in
+ *     ascending and L^T x = y in descending column order.  A pivot that is not > 0 or not finite, or a non-finite solution, is a
+ *     failed solve: no step is applied, tempChi is DBL_MAX, the trial is rejected (two-view section, deviation 2).  g2o uses
+ *     Eigen's sparse LDLT with a block ordering.
+ *  2. Sums.  Every floating-point sum is f64 in an order that depends on the input only (csrc/orbx_lba_math.inc states each):
+ *     a problem has 256 lanes; vertex j belongs to lane j % 256.  Hll and bl of a vertex: its owner, over its edges in ascending
+ *     entry.  chi2, the points' part of computeScale: a lane adds its vertices' terms in ascending j (a vertex's edges in
+ *     ascending entry), then the lanes are folded as a tree: lane l += lane l + 128, then + 64, ... + 1.  Hpp and bp of a free
+ *     pose: lane l of 64 adds the terms of the keyframe's features l, l + 64, ...; lane l += lane l + 32, + 16, ... + 1.  Each row
+ *     of each 6x6 block (a, c), a <= c, of sum Hpl Dinv Hpl^T, and each row of sum Hpl Dinv bl: one owner, over the vertices in
+ *     ascending index whose active observer word has both bits.  computeScale: the poses' terms in order, + the points' sum, +
+ *     1e-3.  No floating-point atomic is used.
+ *  3. A point's observations are ordered by entry (the reference's std::map<KeyFrame*, size_t> by address).
+ *  4. There is no pbStopFlag and there are no Map / KeyFrame / MapPoint types.
+ *  5. The errors of a round's active edges are computed once when the round starts, so a round with 0 iterations classifies at
+ *     the estimates it was given (g2o would read errors never computed).
+ *  6. Garbage is flagged and never followed.  ORBX_LBA_BAD_INPUT: a count outside its capacity (d_n of an entry's frame, d_map_n),
+ *     a row entry >= map_n, an octave outside the table on a feature that names a masked point, two features of one keyframe
+ *     naming one point vertex, a frame used twice in one problem.  ORBX_LBA_NONFINITE: a non-finite pose of an entry or point
+ *     vertex, or a non-finite result.  A flagged problem copies its inputs through: every d_pose_out row is the input's bits,
+ *     no point is written, every outlier byte of its entries is 0, every number of the result but status and n_free is 0 (a non-finite RESULT keeps
+ *     its counters).
+ *  7. n_free == 0 or a problem without an edge runs nothing: status 0, the inputs copied through.
+ *  8. Problems are independent: two problems may share a map set as long as no point is a vertex of both (and, in place, none
+ *     is a vertex of one and read by the other); the entry runs of two problems do not overlap. */
+#define ORBX_LBA_MAX_FREE 64     /* free keyframes per problem: one 64-bit word of free observers per point */
+#define ORBX_LBA_BAD_INPUT 2
+#define ORBX_LBA_NONFINITE 4
+typedef struct orbx_lba_result {
+  int32_t status;             /* 0, or a bitmask of ORBX_LBA_*; every field is written for every problem */
+  int32_t n_points, n_edges;  /* point vertices, edges (to free and fixed entries) */
+  int32_t n_free;
+  int32_t iterations[2];      /* per round: solve() calls */
+  int32_t lm_trials[2];       /* the sum of qmax */
+  int32_t rejected_trials[2];
+  int32_t solver_failures[2];
+  int32_t stop_reason[2];     /* 0 = all iterations ran, 1 = qmax == 10 || rho == 0, 2 = _nBad >= 3 */
+  int32_t n_active_points[2]; /* point vertices / free poses with an active edge in the round */
+  int32_t n_active_free[2];
+  int32_t n_level1;           /* edges set aside between the rounds */
+  int32_t n_erased;           /* set bytes of d_obs_outlier (vToErase) */
+  double chi2_initial[2], chi2_final[2], lambda[2];
+} orbx_lba_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  Host arrays [n_problems]: h_first / h_count (the problem's
+ * run in the entry list), h_n_free, h_map_set; h_entry_frame [n_entries].  K row-major 3x3 (host, f32); inv_sigma2: host,
+ * nlevels floats, NULL = the context's table; n_iterations, n_more_iterations >= 0 (5, 10).  Outputs: d_pose_out float
+ * [n_entries][12] (free: the optimised pose; fixed: a copy of its input); d_map_points_out [n_map_sets][map_capacity][3], which
+ * may equal d_map_points (otherwise the call first copies d_map_points to it: points outside a problem or without an
+ * observation come through bit for bit); d_obs_outlier uint8 [n_entries][capacity], every byte of a problem's entries written;
+ * d_res [n_problems].  One workgroup per problem runs both rounds in one launch.  Workspace: per problem the bytes
+ * csrc/orbx_lba_math.inc layout() counts (DESIGN.md 4s has the formula), grown in the context; a call whose workspace cannot be
+ * allocated returns ORBX_E_HIP and runs nothing.  The call returns once queued, with the exception
+ * orbx_bundle_adjust_batch_device has (a list or table that differs from the previous call's is uploaded behind a wait).
+ * ORBX_E_BADARG: null required pointers, negative counts, capacity or map_capacity < 1, a run outside [0, n_entries], n_free
+ * outside [0, count] or above ORBX_LBA_MAX_FREE, a map set outside [0, n_map_sets), a frame outside [0, n_frames);
+ * ORBX_E_CAPACITY: capacity or map_capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed
+ * arguments -- all checked before anything touches a device; ORBX_E_CAPACITY also for a batch whose workspace would exceed
+ * 512 GiB.  n_problems == 0 is ORBX_OK.  The workspace is a block of the context's own (not the staging block of the
+ * single-problem calls, which the host form fills while this call runs); it only grows and is freed with the context: a
+ * context that once ran 640 local windows keeps their 2.7 GB.  A problem with at most 29 free keyframes keeps the reduced
+ * system's packed factor in LDS: the launch asks for the largest such factor of the batch as dynamic LDS, up to 120,408 bytes
+ * beside the kernel's 36 KB, and a launch that asks for more than about 45 KB has one workgroup per CU instead of two. */
+int orbx_local_ba_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_first, const int32_t* h_count,
+                               const int32_t* h_n_free, const int32_t* h_map_set, int n_entries, const int32_t* h_entry_frame,
+                               const orbx_keypoint* d_kps_un, const int32_t* d_n, int capacity, const float* d_pose,
+                               const int32_t* d_rows, int n_map_sets, int map_capacity, const int32_t* d_map_n,
+                               const float* d_map_points, const uint8_t* d_map_mask, const float* K, const float* inv_sigma2,
+                               int n_iterations, int n_more_iterations, float* d_pose_out, float* d_map_points_out,
+                               uint8_t* d_obs_outlier, orbx_lba_result* d_res);
+/* One problem in host memory, run through the batched path as a batch of one: entry e is keyframe e (kps_un
+ * [n_entries][capacity], n [n_entries], pose [n_entries][12], rows [n_entries][capacity]), the first n_free free; map_points
+ * [map_n][3], map_mask [map_n] nullable; pose_out [n_entries][12], map_points_out [map_n][3] (may equal map_points),
+ * obs_outlier [n_entries][capacity].  Synchronous. */
+int orbx_local_ba(orbx_ctx* ctx, int n_entries, int n_free, const orbx_keypoint* kps_un, const int32_t* n, int capacity,
+                  const float* pose, const int32_t* rows, int map_n, const float* map_points, const uint8_t* map_mask,
+                  const float* K, const float* inv_sigma2, int n_iterations, int n_more_iterations, float* pose_out,
+                  float* map_points_out, uint8_t* obs_outlier, orbx_lba_result* res);
+
+/* Measurement aid: problems with at most max_free free keyframes keep the reduced system's packed factor in LDS (default and
+ * largest value 29: 120,408 bytes beside the kernel's 36 KB); 0 = every problem keeps it in the workspace, -1 restores the
+ * default.  Every value gives the same bytes.  Process-wide.  ORBX_E_BADARG outside [-1, 29]. */
+int orbx_debug_local_ba_lds_max_free(int max_free);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

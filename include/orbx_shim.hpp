@@ -827,6 +827,54 @@ class Optimizer {
     if (result) *result = res;
     return res.n_inliers;
   }
+
+  // LocalBundleAdjustment(pKF, pbStopFlag, pMap): ORB-SLAM2's Optimizer::LocalBundleAdjustment (include/orbx.h, "local mapping:
+  // local bundle adjustment").  vKeyFrames: lLocalKeyFrames (the first nFree) then lFixedCameras as KeyFrameViews (mvKeysUn, N
+  // and mTcw are read); vRows[k]: keyframe k's mvpMapPoints as indices into the map (negative: none), KF.N entries; map:
+  // mWorldPos and mbGood are read.  vTcw [keyframes][12] receives the poses (a fixed keyframe's as given), vWorldPos [map.N][3]
+  // the points, vToErase the (keyframe, feature) pairs of the edges to erase: SetPose / SetWorldPos / UpdateNormalAndDepth /
+  // EraseMapPointMatch / EraseObservation stay the caller's.  K [9]; ext: the device context.  Returns vToErase.size().
+  // Argument / HIP errors throw orbx::Error.
+  static int LocalBundleAdjustment(ORBextractor* ext, const std::vector<KeyFrameView>& vKeyFrames, int nFree,
+                                   const std::vector<std::vector<int>>& vRows, const MapView& map, const float* K,
+                                   std::vector<float>& vTcw, std::vector<float>& vWorldPos, std::vector<std::pair<int, int>>& vToErase,
+                                   orbx_lba_result* result = nullptr) {
+    if (!ext) throw orbx::Error(ORBX_E_BADARG, "Optimizer: no ORBextractor (device context)");
+    const size_t nE = vKeyFrames.size();
+    if (vRows.size() != nE) throw orbx::Error(ORBX_E_BADARG, "Optimizer::LocalBundleAdjustment: vRows needs one row per keyframe");
+    size_t cap = 1;
+    for (const KeyFrameView& kf : vKeyFrames) cap = kf.N > (int)cap ? (size_t)kf.N : cap;
+    std::vector<orbx_keypoint> keys((nE ? nE : 1) * cap);
+    std::vector<int32_t> n(nE ? nE : 1, 0), rows((nE ? nE : 1) * cap, -1);
+    std::vector<float> pose((nE ? nE : 1) * 12, 0.f);
+    for (size_t k = 0; k < nE; k++) {
+      const KeyFrameView& kf = vKeyFrames[k];
+      if (!kf.mTcw) throw orbx::Error(ORBX_E_BADARG, "Optimizer::LocalBundleAdjustment: a keyframe has no pose (mTcw)");
+      if (vRows[k].size() != (size_t)kf.N) throw orbx::Error(ORBX_E_BADARG, "Optimizer::LocalBundleAdjustment: a row needs KF.N entries");
+      n[k] = kf.N;
+      for (int i = 0; i < kf.N; i++) {
+        std::memcpy(&keys[k * cap + (size_t)i], &kf.mvKeysUn[i], sizeof(orbx_keypoint));
+        rows[k * cap + (size_t)i] = vRows[k][(size_t)i];
+      }
+      for (int i = 0; i < 12; i++) pose[k * 12 + (size_t)i] = kf.mTcw[i];
+    }
+    vTcw.assign((nE ? nE : 1) * 12, 0.f);
+    vWorldPos.assign(3 * (size_t)(map.N ? map.N : 1), 0.f);
+    std::vector<uint8_t> outlier((nE ? nE : 1) * cap, 0);
+    orbx_lba_result res;
+    const int r = orbx_local_ba(ext->context(), (int)nE, nFree, keys.data(), n.data(), (int)cap, pose.data(), rows.data(), map.N,
+                                map.mWorldPos, map.mbGood, K, nullptr, 5, 10, vTcw.data(), vWorldPos.data(), outlier.data(), &res);
+    if (r != ORBX_OK)
+      throw orbx::Error(r, r == ORBX_E_BADARG ? "Optimizer::LocalBundleAdjustment: an argument out of range" : orbx_last_error(ext->context()));
+    vTcw.resize(nE * 12);
+    vWorldPos.resize(3 * (size_t)map.N);
+    vToErase.clear();
+    for (size_t k = 0; k < nE; k++)
+      for (int i = 0; i < vKeyFrames[k].N; i++)
+        if (outlier[k * cap + (size_t)i]) vToErase.push_back(std::make_pair((int)k, i));
+    if (result) *result = res;
+    return (int)vToErase.size();
+  }
 };
 
 // ---- PnPsolver (ORB-SLAM2's PnPsolver.h; include/orbx.h, "behind SearchByBoW: PnP RANSAC") ---------------------------------------

@@ -27,7 +27,8 @@ __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame",
            "Sim3OptResult", "SIM3OPT_RESULT_DTYPE", "SIM3OPT_BAD_INPUT", "SIM3OPT_NONFINITE",
            "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted",
            "MapFuser", "FuseResult", "FUSE_RESULT_DTYPE", "FUSE_BAD_INPUT", "FUSE_NONFINITE", "FUSE_OCCUPIED_UNMAPPED", "FUSE_NONE",
-           "FUSE_ADD", "FUSE_KEEP_OCCUPANT", "FUSE_REPLACE_OCCUPANT", "FUSE_BAD_OCCUPANT"]
+           "FUSE_ADD", "FUSE_KEEP_OCCUPANT", "FUSE_REPLACE_OCCUPANT", "FUSE_BAD_OCCUPANT",
+           "LbaResult", "LBA_RESULT_DTYPE", "LBA_BAD_INPUT", "LBA_NONFINITE", "LBA_MAX_FREE"]
 
 from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResult, HF_RESULT_DTYPE, InitResult,  # noqa: F401
                        INIT_RESULT_DTYPE, BAResult, BA_RESULT_DTYPE, PoseResult, POSE_RESULT_DTYPE, PnpResult, PNP_RESULT_DTYPE,
@@ -35,7 +36,8 @@ from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResu
                        PROJ_RESULT_FIELDS, LocalResult, LOCAL_RESULT_DTYPE, LOCAL_RESULT_FIELDS, MatchScwResult, SCW_RESULT_DTYPE,
                        SCW_RESULT_FIELDS, KfProjResult, KFPROJ_RESULT_DTYPE, KFPROJ_RESULT_FIELDS, MatchSim3Result,
                        MSIM3_RESULT_DTYPE, MSIM3_RESULT_FIELDS, TriMatchResult, TRI_MATCH_RESULT_DTYPE, TRI_MATCH_COUNTERS,
-                       TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS, FuseResult, FUSE_RESULT_DTYPE, FUSE_RESULT_FIELDS)
+                       TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS, FuseResult, FUSE_RESULT_DTYPE, FUSE_RESULT_FIELDS,
+                       LbaResult, LBA_RESULT_DTYPE)
 
 E_EMPTY, E_BADARG, E_TOOSMALL, E_HIP, E_CAPACITY, E_RCCL = -1, -2, -3, -4, -5, -6
 _ERRNAMES = {-1: "ORBX_E_EMPTY", -2: "ORBX_E_BADARG", -3: "ORBX_E_TOOSMALL", -4: "ORBX_E_HIP", -5: "ORBX_E_CAPACITY", -6: "ORBX_E_RCCL"}
@@ -57,6 +59,7 @@ PNP_BAD_INPUT, PNP_NONFINITE, PNP_FEW_POINTS, PNP_BAD_DRAWS, PNP_NO_POSE = 2, 4,
 PNP_RAND_MAX = 2147483647
 SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT = 2, 4, 8, 16, 32
 SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
+LBA_BAD_INPUT, LBA_NONFINITE, LBA_MAX_FREE = 2, 4, 64
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
 LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
 SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
@@ -260,6 +263,10 @@ def lib() -> ctypes.CDLL:
                             ctypes.POINTER(FuseResult)]
     L.orbx_fuse_scw.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_Bounds), f32, i32, vp, vp, vp, vp, vp,
                                 ctypes.POINTER(FuseResult)]
+    L.orbx_local_ba_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
+                                             vp, vp, vp, vp]
+    L.orbx_local_ba.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, ctypes.POINTER(LbaResult)]
+    L.orbx_debug_local_ba_lds_max_free.argtypes = [i32]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1487,6 +1494,57 @@ class ORBextractor:
                           ("the pose array", d_pose0, P * 48), _k9(K), sig, int(n_iterations),
                           ("the result array", d_res, P * POSE_RESULT_DTYPE.itemsize), ("the outlier array", d_outlier, P * cap))
 
+    # -- Optimizer::LocalBundleAdjustment behind Fuse (include/orbx.h, "local mapping: local bundle adjustment") -----------
+    def local_ba_problems_device(self, n_frames: int, first, count, n_free, map_set, entry_frame, d_kps_un, d_n, d_pose, d_rows,
+                                 n_map_sets: int, map_capacity: int, d_map_n, d_map_points, d_map_mask, K, d_pose_out, d_obs_outlier,
+                                 d_res, d_map_points_out=None, inv_sigma2=None, n_iterations: int = 5, n_more_iterations: int = 10,
+                                 capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: problem p adjusts the entries first[p] .. first[p] + count[p] - 1 of the entry list (the
+        first n_free[p] free, the rest fixed; entry e is frame entry_frame[e] of d_kps_un / d_n / d_pose float32 [n_frames, 12])
+        against map set map_set[p].  d_rows int32 [n_entries, capacity]: the keyframes' mvpMapPoints as indices into the
+        problem's set, what match_local_map_pairs_device, match_scw_pairs_device and MapFuser.fuse_pairs_device leave in their
+        match arrays.  d_pose_out float32 [n_entries, 12], d_obs_outlier uint8 [n_entries, capacity], d_res [n_problems]
+        LBA_RESULT_DTYPE records (128 bytes); d_map_points_out None = in place.  Stream-ordered."""
+        first, count, n_free, map_set = _pair_lists(("first", "count", "n_free", "map_set"), (first, count, n_free, map_set))
+        entry_frame = np.ascontiguousarray(entry_frame, np.int32).reshape(-1)
+        cap, mcap, nf, ns, P, E = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets), len(first), len(entry_frame)
+        if d_map_points_out is None:
+            d_map_points_out = d_map_points
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
+        self._device_call("orbx_local_ba_batch_device", nf, P, first, count, n_free, map_set, E, entry_frame,
+                          ("the keypoint array", d_kps_un, nf * cap * 28), ("the count array", d_n, nf * 4), cap,
+                          ("the pose array", d_pose, nf * 48), ("the row array", d_rows, E * cap * 4), ns, mcap,
+                          ("the map count array", d_map_n, ns * 4), ("the map point array", d_map_points, ns * mcap * 12),
+                          ("the map mask", d_map_mask, ns * mcap), _k9(K), sig, int(n_iterations), int(n_more_iterations),
+                          ("the pose output array", d_pose_out, E * 48), ("the map point output array", d_map_points_out, ns * mcap * 12),
+                          ("the outlier array", d_obs_outlier, E * cap), ("the result array", d_res, P * LBA_RESULT_DTYPE.itemsize))
+
+    def local_ba(self, keys_un, n, poses, rows, n_free: int, map_points, map_mask, K, inv_sigma2=None, n_iterations: int = 5,
+                 n_more_iterations: int = 10):
+        """One problem from host memory: keys_un [n_entries, capacity] keypoints (n [n_entries] of them valid per keyframe), poses
+        [n_entries, 12], rows int32 [n_entries, capacity], the first n_free keyframes free; map_points [map_n, 3], map_mask [map_n]
+        or None.  Returns (LbaResult, poses [n_entries, 12] float32, map points [map_n, 3] float32, vToErase as uint8 [n_entries,
+        capacity])."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+        if k.ndim != 2:
+            raise OrbxError(E_BADARG, "keys_un must be [n_entries, capacity]")
+        E, cap = k.shape
+        cnt = np.ascontiguousarray(n, np.int32).reshape(-1)
+        pose = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        r = np.ascontiguousarray(rows, np.int32).reshape(-1, cap) if E else np.zeros((0, cap), np.int32)
+        pts = _points(map_points)
+        if len(cnt) != E or len(pose) != E or len(r) != E:
+            raise OrbxError(E_BADARG, "n, poses and rows must have one entry per keyframe")
+        m = _flags(map_mask, len(pts), "the map mask needs one entry per map point")
+        sig = _per_level(inv_sigma2, self.nlevels, "inv_sigma2")
+        res = LbaResult()
+        pose_out, pts_out = np.zeros((max(E, 1), 12), np.float32), np.zeros((max(len(pts), 1), 3), np.float32)
+        outlier = np.zeros((max(E, 1), max(cap, 1)), np.uint8)
+        self._check(self._L.orbx_local_ba(self._h, E, int(n_free), _ptr(k), _ptr(cnt), max(cap, 1), _ptr(pose), _ptr(r), len(pts), _ptr(pts),
+                                          _ptr(m), _ptr(_k9(K)), _ptr(sig), int(n_iterations), int(n_more_iterations), _ptr(pose_out),
+                                          _ptr(pts_out), _ptr(outlier), ctypes.byref(res)), "orbx_local_ba")
+        return res, pose_out[:E], pts_out[:len(pts)], outlier[:E]
+
     # -- PnPsolver behind SearchByBoW (include/orbx.h, "behind SearchByBoW: PnP RANSAC") ------------------------
     def pnp_solve(self, keys_un, points, mask, K, draws, sigma2=None, probability: float = 0.99, min_inliers: int = 10,
                   max_iterations: int = 300, epsilon: float = 0.5, th2: float = 5.991):
@@ -2037,6 +2095,14 @@ class Vocabulary:
                                ("the score array", d_score, P * 8))
 
 
+def debug_local_ba_lds_max_free(max_free: int = -1) -> None:
+    """Measurement aid (orbx_debug_local_ba_lds_max_free): local bundle adjustments with at most max_free free keyframes keep the
+    reduced system's factor in LDS; 0 = none does, -1 = the default (29).  Same results either way."""
+    r = lib().orbx_debug_local_ba_lds_max_free(int(max_free))
+    if r < 0:
+        raise OrbxError(r, "orbx_debug_local_ba_lds_max_free")
+
+
 DB_MAX_RESULTS = 256  # ORBX_DB_MAX_RESULTS: the longest result list of a database query
 DB_ENTRIES_PER_SLICE, DB_LISTS_PER_MERGE = 2048, 8  # the defaults of orbx_debug_database_shape
 
@@ -2192,6 +2258,17 @@ class MapFuser:
                            d_map_points, d_map_normals, d_map_dist, d_map_desc, d_map_mask, [],
                            ("the Scw array", d_scw), K, bounds, d_matches, d_occ_obs, d_fuse_idx,
                            d_fuse_act, d_fuse_other, d_res, th, th_low, capacity)
+
+    def fuse_local_ba_device(self, create: dict, fuse: dict, local_ba: dict) -> None:
+        """LocalMapping's chain behind a new keyframe, queued on the context's stream with no copy and no wait in between:
+        ORBextractor.create_new_map_points_pairs_device(**create), fuse_pairs_device(**fuse), then
+        ORBextractor.local_ba_problems_device(**local_ba).  The dictionaries hold the three calls' own arguments by name; the
+        chain is in what they share: the point arrays `create` writes are map sets of `fuse` (map_capacity = capacity), and
+        `fuse`'s d_matches is `local_ba`'s d_rows with the fuse pairs as the entry list (entry_frame = kf), each problem a run of
+        pairs that name one map set."""
+        self._ext.create_new_map_points_pairs_device(**create)
+        self.fuse_pairs_device(**fuse)
+        self._ext.local_ba_problems_device(**local_ba)
 
     def _one(self, scw_form, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, T, K, bounds, matches,
              occ_obs, th, th_low):
@@ -2637,3 +2714,27 @@ class Optimizer:
         res, out, row = ext.optimize_sim3(kf1.mvKeysUn, p1, m1, _pose12(T1), kf2.mvKeysUn, p2, m2, _pose12(T2), matches12, sim, K, None, bFixScale, th2,
                                           n_iterations, n_more_iterations)
         return int(res.n_inliers), row, (float(out[12]), out[:9].reshape(3, 3).copy(), out[9:12].copy()), res
+
+    @staticmethod
+    def LocalBundleAdjustment(keyframes, n_free: int, rows, map_points, map_mask=None, K=None, extractor: Optional[ORBextractor] = None,
+                              n_iterations: int = 5, n_more_iterations: int = 10):
+        """Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (include/orbx.h, "local mapping: local bundle adjustment").
+        keyframes: a list of (Frame, Tcw 3x4 / 4x4 / 12 floats), lLocalKeyFrames (the first n_free) then lFixedCameras; rows: per
+        keyframe its mvpMapPoints as indices into map_points [N, 3] (negative: none).  Returns (the poses [n, 4, 4] float32, the
+        points [N, 3] float32, vToErase as a list of (keyframe, feature), the LbaResult); the erasures stay with the caller."""
+        frames = [kf for kf, _ in keyframes]
+        ext = extractor or next((f.mpORBextractor for f in frames if f.mpORBextractor is not None), None)
+        if ext is None:
+            raise OrbxError(E_BADARG, "Optimizer needs an ORBextractor (device context); pass extractor=")
+        K = _camera_K(K, frames[0] if frames else None, "Optimizer.LocalBundleAdjustment", "keyframe")
+        cap = max([len(f.mvKeysUn) for f in frames] + [1])
+        keys, r = np.zeros((len(frames), cap), KEYPOINT_DTYPE), np.full((len(frames), cap), -1, np.int32)
+        for e, f in enumerate(frames):
+            keys[e, :len(f.mvKeysUn)] = _keys(f.mvKeysUn)
+            r[e, :len(f.mvKeysUn)] = _row(rows[e], len(f.mvKeysUn), "rows needs one entry per feature of its keyframe")[:len(f.mvKeysUn)]
+        poses = np.stack([_pose12(T) for _, T in keyframes]) if frames else np.zeros((0, 12), np.float32)
+        res, pose_out, pts, outlier = ext.local_ba(keys, [len(f.mvKeysUn) for f in frames], poses, r, n_free, map_points, map_mask, K, None,
+                                                   n_iterations, n_more_iterations)
+        T = np.tile(np.eye(4, dtype=np.float32), (len(frames), 1, 1))
+        T[:, :3, :3], T[:, :3, 3] = pose_out[:, :9].reshape(-1, 3, 3), pose_out[:, 9:]
+        return T, pts, [(int(e), int(f)) for e, f in zip(*np.nonzero(outlier))], res

@@ -2,7 +2,8 @@
 order, from which ``_record`` makes the ``ctypes.Structure`` subclass, the numpy dtype and ``as_dict``.  RECORDS keeps every
 pair under its C struct's name; tests/test_abi_host.py compiles a probe against the header and compares sizes and offsets.
 RECORDS_FUSE is a second table of the same form for the records of "fusing map points into a keyframe"
-(tests/test_fuse_abi_host.py probes it the same way)."""
+(tests/test_fuse_abi_host.py probes it the same way), RECORDS_LBA a third for the record of "local mapping: local bundle
+adjustment" (tests/test_lba_abi_host.py)."""
 from __future__ import annotations
 
 import ctypes
@@ -13,6 +14,7 @@ import numpy as np
 _CTYPES = {"i4": ctypes.c_int32, "f4": ctypes.c_float, "f8": ctypes.c_double}
 RECORDS = {}  # C struct name -> (ctypes.Structure subclass or None, numpy dtype)
 RECORDS_FUSE = {}  # the same for orbx_fuse_result
+RECORDS_LBA = {}  # the same for orbx_lba_result
 
 
 def _as_dict(self) -> dict:
@@ -186,3 +188,13 @@ FuseResult, FUSE_RESULT_DTYPE = _record(
     """orbx_fuse_result: ORBmatcher::Fuse's counters for one (keyframe, map set) pair, either overload (n_fused is the design's
     return value; rounds is the device's own count).""", table=RECORDS_FUSE)
 assert FUSE_RESULT_DTYPE.itemsize == 64
+
+# (the per-round fields are plain lists of two in as_dict)
+LBA_ROUND_FIELDS = ("iterations", "lm_trials", "rejected_trials", "solver_failures", "stop_reason", "n_active_points", "n_active_free")
+LbaResult, LBA_RESULT_DTYPE = _record(
+    "orbx_lba_result", "LbaResult",
+    _ints("status", "n_points", "n_edges", "n_free") + [(n, "i4", 2, list) for n in LBA_ROUND_FIELDS] + _ints("n_level1", "n_erased") +
+    [("chi2_initial", "f8", 2, list), ("chi2_final", "f8", 2, list), ("lambda", "f8", 2, list)],
+    """orbx_lba_result: Optimizer::LocalBundleAdjustment's outcome for one problem, per round where a field has two entries
+    (n_erased is the size of vToErase).""", table=RECORDS_LBA)
+assert LBA_RESULT_DTYPE.itemsize == 128

@@ -237,4 +237,12 @@ struct Sim3OptScratch {
   HeldArray<float> sigma;       // inv_sigma2 of the last call
 };
 
+// What a context keeps for orbx_local_ba* (orbx_ba.cpp).
+struct LbaScratch {
+  HeldArray<int32_t> problems;  // [5][n_problems] (first entry, entries, free entries, map set, workspace offset / 256) of the last call
+  HeldArray<int32_t> entries;   // the entry list [n_entries] (frames) of the last call
+  HeldArray<float> sigma;       // inv_sigma2 of the last call
+  DeviceBuf<uint8_t> dWork;     // the problems' workspaces: graph, per-vertex and per-edge blocks, poses, reduced systems
+};
+
 }  // namespace orbx

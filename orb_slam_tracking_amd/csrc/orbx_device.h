@@ -850,4 +850,27 @@ struct Sim3OptArgs {
   double fx, fy, cx, cy, delta, th2;
   int32_t nProblems, cap, nLevels, nIterations, nMoreIterations, fixScale;
 };
+// k_lba: Optimizer::LocalBundleAdjustment (include/orbx.h, "local mapping: local bundle adjustment"), a workgroup per problem
+constexpr int LBA_THREADS = 256;
+struct LbaArgs {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const int32_t* nKps;        // [frames]
+  const float* pose;          // [frames][12]
+  const int32_t* rows;        // [nEntries][cap]
+  const int32_t* problems;    // [5][nProblems]: first entry, entries, free entries, map set, workspace offset / 256
+  const int32_t* entryFrame;  // [nEntries]
+  const int32_t* mapN;        // [mapSets]
+  const float* mapPts;        // [mapSets][mapCap][3]
+  const uint8_t* mapMask;     // [mapSets][mapCap] or null
+  const float* invSigma2;     // [nLevels] (device)
+  float* poseOut;             // [nEntries][12]
+  float* mapOut;              // [mapSets][mapCap][3], may be mapPts
+  uint8_t* outlier;           // [nEntries][cap]
+  orbx_lba_result* res;       // [nProblems]
+  uint8_t* ws;                // the problems' workspaces
+  double fx, fy, cx, cy, delta;
+  int32_t nProblems, cap, mapCap, nLevels, nIterations, nMoreIterations;
+  int32_t ldsMaxFree;         // problems with at most this many free keyframes keep the packed factor in LDS
+  uint32_t ldsBytes;          // dynamic LDS of the launch: the largest such factor
+};
 }  // namespace orbx

@@ -114,4 +114,7 @@ hipError_t launch_match_fuse(hipStream_t st, const MatchFuseArgs& a, bool scwFor
 // orbx_sim3opt_kernel.hip
 hipError_t launch_sim3_optimize(hipStream_t st, const Sim3OptArgs& a);
 
+// orbx_lba_kernel.hip
+hipError_t launch_lba(hipStream_t st, const LbaArgs& a);
+
 }  // namespace orbx
