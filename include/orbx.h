@@ -1280,7 +1280,8 @@ int orbx_fuse_scw(orbx_ctx* ctx, const orbx_keypoint* kps_un, const uint8_t* des
  *  5. Behind round 2 the test of rule 3, over ALL edges, fills d_obs_outlier (vToErase).  Free poses go out as f32 Tcw: the
  *     rotation matrix of the quaternion, as orbx_bundle_adjust* writes R21; points go out as f32.
  * UpdateNormalAndDepth, the SetWorldPos / SetPose bookkeeping and the erasures themselves (EraseMapPointMatch /
- * EraseObservation for every set byte of d_obs_outlier) stay with the caller.
+ * EraseObservation for every set byte of d_obs_outlier) stay with the caller, who may hand the erasures, UpdateNormalAndDepth
+ * and ComputeDistinctiveDescriptors to orbx_map_update* ("local mapping: updating the map points", below).
  *
  * Documented deviations:
  *  1. Linear solver.  The reduced system of the active free poses (6 x their count, in entry order) is dense and solved by an
@@ -1367,6 +1368,121 @@ int orbx_local_ba(orbx_ctx* ctx, int n_entries, int n_free, const orbx_keypoint*
  * largest value 29: 120,408 bytes beside the kernel's 36 KB); 0 = every problem keeps it in the workspace, -1 restores the
  * default.  Every value gives the same bytes.  Process-wide.  ORBX_E_BADARG outside [-1, 29]. */
 int orbx_debug_local_ba_lds_max_free(int max_free);
+
+/* ---- local mapping: updating the map points (MapPoint::Observations, UpdateNormalAndDepth, ComputeDistinctiveDescriptors) ----
+ * What LocalMapping does with the result of the local bundle adjustment before the tracker matches against the map again:
+ * vToErase is applied (KeyFrame::EraseMapPointMatch / MapPoint::EraseObservation with its nObs <= 2 rule), and every adjusted
+ * point gets its observation count, its mean viewing direction and scale-invariance distances and its representative
+ * descriptor -- the four arrays per map set that orbx_match_local_map*, orbx_match_scw*, orbx_fuse* and
+ * orbx_match_keyframe_projection* read (d_map_normals, d_map_dist, d_map_desc32, d_map_obs), written on the device, for a batch
+ * of independent problems, in the layout orbx_local_ba_batch_device uses.  The reference ships no MapPoint: the rules restate
+ * MapPoint::EraseObservation, Observations, UpdateNormalAndDepth and ComputeDistinctiveDescriptors of the ORB-SLAM2 design
+ * [from-knowledge], PARITY UNPINNED, as Fuse and the local bundle adjustment above.  The device equals the CPU restatement
+ * tests/cpp/map_update_ref.cpp bit for bit, which shares csrc/orbx_map_math.inc with it and is itself tested against an
+ * independently written numpy statement.
+ *
+ * A problem is exactly a problem of orbx_local_ba_batch_device: a run of entries in a flat entry list, the first n_free of
+ * them free, and one map set.  Entry e names a frame (its row of d_kps_un / d_desc32 / d_n), has its pose in row e of
+ * d_entry_pose float [n_entries][12] (orbx_local_ba_batch_device's d_pose_out as it is) and owns row e of d_rows.  Features at
+ * or beyond the frame's d_n are not read.  All arithmetic is f32 without contraction unless said otherwise.
+ *
+ * Rules:
+ *  1. Points updated.  The points updated ("vertices") are the local bundle adjustment's: i < map_n, mask byte set (d_map_mask
+ *     NULL = every point), named by the row of at least one FREE entry on entry.  With n_free == count that is every point any
+ *     entry names: the form for use behind orbx_fuse* / orbx_triangulate_matches*.  A point that is not a vertex is not touched
+ *     in any output.
+ *  2. Erasures.  With d_obs_outlier, every (entry, feature) whose byte is set and whose row entry names a vertex gets row entry
+ *     -1 (n_erased).  A set byte anywhere else is ignored.
+ *  3. Observation counts.  obs_i = the number of entries whose row still names vertex i -> d_map_obs.  A vertex that lost at
+ *     least one observation in rule 2 and has obs_i <= 2 is bad (EraseObservation -> SetBadFlag): its d_map_mask_out byte is 0,
+ *     every row entry of the problem that names it becomes -1 (n_cleared), its d_map_obs is 0 and nothing else is written for
+ *     it (n_bad_points).  A vertex that lost nothing keeps its mask byte whatever its count: a freshly triangulated point has
+ *     two observations.
+ *  4. The reference keyframe.  The observers of a point are ordered by ascending entry.  The reference keyframe (mpRefKF) is
+ *     the observer whose frame is d_map_ref[i]; where there is none -- a negative value, d_map_ref NULL, or the keyframe erased
+ *     in rule 2 or no observer -- it is the first observer, and d_map_ref[i] is set to its frame (n_ref_moved counts the
+ *     non-negative values that changed).
+ *  5. ORBX_MAP_NORMALS: UpdateNormalAndDepth.  Ow_e = -Rcw^T tcw of the entry's pose (gemm: f64 products and sum, one rounding).
+ *     Per observer in order: d = P - Ow_e, len = cv::norm(d) (f64 inside, rounded to f32), normal_k += d_k / len, starting
+ *     from +0.0f; then normal_k / (float)obs_i -> d_map_normals.  dist = cv::norm(P - Ow_ref); max = dist * scale[octave of the
+ *     reference's feature]; min = max / scale[nlevels - 1]; d_map_dist[i] = (min, max).  The scale table is the context's.  For
+ *     a point with two observers, KF1 the reference, these are the bits rule 6 of orbx_triangulate_matches* writes (one source:
+ *     csrc/orbx_tri_math.inc).
+ *  6. ORBX_MAP_DESCRIPTORS: ComputeDistinctiveDescriptors.  Over the observers' descriptors D_0 .. D_{N-1} in order:
+ *     dist[a][b] = popcount(D_a ^ D_b); median_a = the element at index (N - 1) / 2 (integer division: `0.5 * (N - 1)`
+ *     truncated) of row a sorted ascending, the zero on the diagonal included; the first a with the smallest median wins
+ *     (`median < BestMedian` from INT_MAX); d_map_desc32[i] = D_a.
+ *  7. Garbage is flagged and never followed.  ORBX_MAP_BAD_INPUT: a count outside its capacity (d_n of an entry's frame,
+ *     d_map_n), a row entry >= map_n, two features of one entry naming one vertex (an erased one included), a frame twice in
+ *     one problem, the octave of a reference keyframe's feature outside the table.  ORBX_MAP_NONFINITE: a non-finite pose of an
+ *     entry, a non-finite vertex position, a len that is 0 or no number.  The checks do not depend on `what`.  A flagged
+ *     problem changes NOTHING: rows, mask, reference frames and every output keep their bits, every field of the record but
+ *     status is 0.
+ *
+ * Documented deviations:
+ *  1. The entry run is assumed to hold every keyframe that observes a vertex, which is how LocalBundleAdjustment builds its
+ *     fixed cameras: an observer outside the run is not counted, summed or compared.
+ *  2. A point's observations are ordered by entry (the design's std::map<KeyFrame*, size_t> by address): the local bundle
+ *     adjustment's deviation 3.
+ *  3. There is no KeyFrame::isBad(): a culled keyframe is simply not an entry.
+ *  4. max_observers is taken over every vertex, the bad ones with the count that made them bad.
+ *  5. Problems are independent as under the local bundle adjustment's deviation 8: two problems may share a map set as long as
+ *     no point is a vertex of both (and, with d_map_mask_out == d_map_mask, none is a vertex of one and named by the other);
+ *     the entry runs of two problems do not overlap.
+ * Out of scope: MapPoint::Replace and replaying orbx_fuse*'s d_fuse_act decisions across keyframes, KeyFrame::UpdateConnections,
+ * culling (MapPointCulling / KeyFrameCulling), stereo. */
+#define ORBX_MAP_NORMALS 1
+#define ORBX_MAP_DESCRIPTORS 2
+#define ORBX_MAP_BAD_INPUT 2
+#define ORBX_MAP_NONFINITE 4
+typedef struct orbx_map_result {
+  int32_t status;          /* 0, or a bitmask of ORBX_MAP_BAD_INPUT / ORBX_MAP_NONFINITE; every field is written for every problem */
+  int32_t n_points;        /* vertices */
+  int32_t n_observations;  /* the sum of obs_i over the vertices that are not bad */
+  int32_t n_erased;        /* rule 2 */
+  int32_t n_bad_points;    /* rule 3 */
+  int32_t n_cleared;       /* rule 3 */
+  int32_t n_ref_moved;     /* rule 4 */
+  int32_t max_observers;   /* the largest obs_i */
+  int32_t n_free;          /* as given */
+  int32_t reserved[7];     /* zero */
+} orbx_map_result;
+
+/* Batched, device-resident, stream-ordered on the context stream.  Host arrays [n_problems]: h_first / h_count (the problem's
+ * run in the entry list), h_n_free, h_map_set; h_entry_frame [n_entries].  d_desc32 uint8 [n_frames][capacity][32] (read with
+ * ORBX_MAP_DESCRIPTORS only; 4-byte aligned); d_rows int32 [n_entries][capacity], in and out; d_obs_outlier uint8
+ * [n_entries][capacity] or NULL: orbx_local_ba*'s vToErase.  d_map_mask uint8 [n_map_sets][map_capacity] (NULL = every point);
+ * d_map_mask_out required, may equal d_map_mask; d_map_ref int32 [n_map_sets][map_capacity] or NULL: mpRefKF as a FRAME index,
+ * < 0 = none yet, in and out.  what: a bitmask of ORBX_MAP_NORMALS / ORBX_MAP_DESCRIPTORS (0 = rows, mask, counts and
+ * reference frames only).  Outputs, vertices only: d_map_normals float [..][3], d_map_dist float [..][2], d_map_desc32 uint8
+ * [..][32], d_map_obs int32 [..]; d_res [n_problems].  Two launches: one workgroup per problem checks the problem, builds the
+ * inverse of the rows and writes rows, mask, counts and reference frames; then (what != 0) a grid over (problem, 64 points), a
+ * wave per point, writes the rest.  Workspace: per problem 256-byte aligned arrays of 12 map_capacity + 8 map_capacity *
+ * count + 12 count + 4 bytes (MapWork of csrc/orbx_device.h), a block of the context's own that only grows and is
+ * freed with the context: a context that once ran 640 local windows of 20 keyframes and 2000 points keeps their 220 MB.  The
+ * call returns once queued, with the exception orbx_bundle_adjust_batch_device has.  ORBX_E_BADARG: null required pointers
+ * (d_map_obs and d_map_mask_out always; d_map_normals and d_map_dist, d_desc32 and d_map_desc32 when `what` names them),
+ * negative counts, capacity or map_capacity < 1, what outside [0, 3], a frame outside [0, n_frames), a run outside [0,
+ * n_entries], n_free outside [0, count] (no other bound), a map set outside [0, n_map_sets); ORBX_E_CAPACITY: capacity or
+ * map_capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise well-formed arguments -- all checked before
+ * anything touches a device; ORBX_E_CAPACITY also for a batch whose workspace would exceed 512 GiB.  n_problems == 0 is
+ * ORBX_OK. */
+int orbx_map_update_batch_device(orbx_ctx* ctx, int n_frames, int n_problems, const int32_t* h_first, const int32_t* h_count,
+                                 const int32_t* h_n_free, const int32_t* h_map_set, int n_entries, const int32_t* h_entry_frame,
+                                 const orbx_keypoint* d_kps_un, const uint8_t* d_desc32, const int32_t* d_n, int capacity,
+                                 const float* d_entry_pose, int32_t* d_rows, const uint8_t* d_obs_outlier, int n_map_sets,
+                                 int map_capacity, const int32_t* d_map_n, const float* d_map_points, const uint8_t* d_map_mask,
+                                 uint8_t* d_map_mask_out, int32_t* d_map_ref, int what, float* d_map_normals, float* d_map_dist,
+                                 uint8_t* d_map_desc32, int32_t* d_map_obs, orbx_map_result* d_res);
+/* One problem in host memory, run through the batched path as a batch of one: entry e is keyframe e (kps_un
+ * [n_entries][capacity], desc32 [n_entries][capacity][32], n [n_entries], pose [n_entries][12], rows [n_entries][capacity] in
+ * and out, obs_outlier [n_entries][capacity] or NULL), the first n_free free; map_points [map_n][3], map_mask [map_n] nullable,
+ * map_mask_out [map_n] (may equal map_mask), map_ref [map_n] nullable, in and out; map_normals, map_dist, map_desc32, map_obs
+ * [map_n] rows in and out: what the call does not write comes back as it went in.  Synchronous. */
+int orbx_map_update(orbx_ctx* ctx, int n_entries, int n_free, const orbx_keypoint* kps_un, const uint8_t* desc32, const int32_t* n,
+                    int capacity, const float* pose, int32_t* rows, const uint8_t* obs_outlier, int map_n, const float* map_points,
+                    const uint8_t* map_mask, uint8_t* map_mask_out, int32_t* map_ref, int what, float* map_normals, float* map_dist,
+                    uint8_t* map_desc32, int32_t* map_obs, orbx_map_result* res);
 
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,

@@ -877,6 +877,85 @@ class Optimizer {
   }
 };
 
+// ---- behind Optimizer::LocalBundleAdjustment (include/orbx.h, "local mapping: updating the map points") ---------------------------
+// The map points as the update leaves them: per point of the map mnObs (MapPoint::Observations()), mNormalVector and
+// mfMinMaxDistance (MapPoint::UpdateNormalAndDepth), mDescriptor (MapPoint::ComputeDistinctiveDescriptors), mbGood (0 behind
+// MapPoint::SetBadFlag) and mnRefKF (mpRefKF as an index into vKeyFrames, -1 = none).  Rows of points the call does not update keep
+// what they held.
+struct MapPointsUpdate {
+  std::vector<int32_t> mnObs, mnRefKF;
+  std::vector<float> mNormalVector, mfMinMaxDistance;  // [N][3], [N][2]
+  std::vector<uint8_t> mDescriptor, mbGood;            // [N][32], [N]
+  orbx_map_result result;
+};
+
+class LocalMapping {
+ public:
+  // What LocalMapping does with Optimizer::LocalBundleAdjustment's result: for every (keyframe, feature) of vToErase
+  // KeyFrame::EraseMapPointMatch and MapPoint::EraseObservation (a point left with two observations or fewer: SetBadFlag, its
+  // remaining matches erased too), then for every adjusted point MapPoint::Observations, MapPoint::UpdateNormalAndDepth and
+  // MapPoint::ComputeDistinctiveDescriptors.  vKeyFrames as LocalBundleAdjustment takes them (mvKeysUn, mDescriptors and N are
+  // read), vTcw [keyframes][12] the adjusted poses it returned; vRows: in and out; map: mWorldPos (the adjusted points) and mbGood
+  // are read; up: in and out, sized [map.N] rows by the caller or empty (then zeros, mnRefKF -1, mbGood from the map).  Returns
+  // the number of points updated.  Argument / HIP errors throw orbx::Error.
+  static int UpdateMapPoints(ORBextractor* ext, const std::vector<KeyFrameView>& vKeyFrames, int nFree, const std::vector<float>& vTcw,
+                             std::vector<std::vector<int>>& vRows, const std::vector<std::pair<int, int>>& vToErase, const MapView& map,
+                             MapPointsUpdate& up, int what = ORBX_MAP_NORMALS | ORBX_MAP_DESCRIPTORS) {
+    if (!ext) throw orbx::Error(ORBX_E_BADARG, "LocalMapping: no ORBextractor (device context)");
+    const size_t nE = vKeyFrames.size(), nP = (size_t)(map.N > 0 ? map.N : 0), np1 = nP ? nP : 1;
+    if (vRows.size() != nE || vTcw.size() != nE * 12)
+      throw orbx::Error(ORBX_E_BADARG, "LocalMapping::UpdateMapPoints: vRows and vTcw need one row per keyframe");
+    size_t cap = 1;
+    for (const KeyFrameView& kf : vKeyFrames) cap = kf.N > (int)cap ? (size_t)kf.N : cap;
+    const size_t ne1 = nE ? nE : 1;
+    std::vector<orbx_keypoint> keys(ne1 * cap);
+    std::vector<uint8_t> desc(ne1 * cap * 32, 0), outlier(ne1 * cap, 0);
+    std::vector<int32_t> n(ne1, 0), rows(ne1 * cap, -1);
+    for (size_t k = 0; k < nE; k++) {
+      const KeyFrameView& kf = vKeyFrames[k];
+      if (vRows[k].size() != (size_t)kf.N) throw orbx::Error(ORBX_E_BADARG, "LocalMapping::UpdateMapPoints: a row needs KF.N entries");
+      if ((what & ORBX_MAP_DESCRIPTORS) && kf.N > 0 && !kf.mDescriptors)
+        throw orbx::Error(ORBX_E_BADARG, "LocalMapping::UpdateMapPoints: a keyframe has no descriptors");
+      n[k] = kf.N;
+      for (int i = 0; i < kf.N; i++) {
+        std::memcpy(&keys[k * cap + (size_t)i], &kf.mvKeysUn[i], sizeof(orbx_keypoint));
+        rows[k * cap + (size_t)i] = vRows[k][(size_t)i];
+      }
+      if (kf.mDescriptors) std::memcpy(&desc[k * cap * 32], kf.mDescriptors, (size_t)kf.N * 32);
+    }
+    for (const std::pair<int, int>& kf_i : vToErase) {
+      if (kf_i.first < 0 || (size_t)kf_i.first >= nE || kf_i.second < 0 || kf_i.second >= vKeyFrames[(size_t)kf_i.first].N)
+        throw orbx::Error(ORBX_E_BADARG, "LocalMapping::UpdateMapPoints: vToErase names no feature");
+      outlier[(size_t)kf_i.first * cap + (size_t)kf_i.second] = 1;
+    }
+    if (up.mbGood.size() != nP) {
+      up.mbGood.assign(np1, 1);
+      if (map.mbGood) std::memcpy(up.mbGood.data(), map.mbGood, nP);
+    }
+    if (up.mnRefKF.size() != nP) up.mnRefKF.assign(np1, -1);
+    up.mnObs.resize(np1, 0);
+    up.mNormalVector.resize(np1 * 3, 0.f);
+    up.mfMinMaxDistance.resize(np1 * 2, 0.f);
+    up.mDescriptor.resize(np1 * 32, 0);
+    up.mbGood.resize(np1, 0);
+    up.mnRefKF.resize(np1, -1);
+    const int r = orbx_map_update(ext->context(), (int)nE, nFree, keys.data(), desc.data(), n.data(), (int)cap, vTcw.data(), rows.data(),
+                                  outlier.data(), (int)nP, map.mWorldPos, map.mbGood, up.mbGood.data(), up.mnRefKF.data(), what,
+                                  up.mNormalVector.data(), up.mfMinMaxDistance.data(), up.mDescriptor.data(), up.mnObs.data(), &up.result);
+    if (r != ORBX_OK)
+      throw orbx::Error(r, r == ORBX_E_BADARG ? "LocalMapping::UpdateMapPoints: an argument out of range" : orbx_last_error(ext->context()));
+    up.mnObs.resize(nP);
+    up.mnRefKF.resize(nP);
+    up.mNormalVector.resize(nP * 3);
+    up.mfMinMaxDistance.resize(nP * 2);
+    up.mDescriptor.resize(nP * 32);
+    up.mbGood.resize(nP);
+    for (size_t k = 0; k < nE; k++)
+      for (int i = 0; i < vKeyFrames[k].N; i++) vRows[k][(size_t)i] = rows[k * cap + (size_t)i];
+    return up.result.n_points;
+  }
+};
+
 // ---- PnPsolver (ORB-SLAM2's PnPsolver.h; include/orbx.h, "behind SearchByBoW: PnP RANSAC") ---------------------------------------
 // The design's constructor takes the frame and vpMapPointMatches; here the map points are coordinates plus a has-point flag per
 // feature, like PoseOptimization above.  SetRansacParameters, iterate and find keep their signatures; the pose comes back as the

@@ -28,7 +28,8 @@ __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame",
            "MatchScwResult", "SCW_RESULT_DTYPE", "SCW_BAD_INPUT", "SCW_NONFINITE", "SCW_TAKEN_UNMAPPED", "loop_accepted",
            "MapFuser", "FuseResult", "FUSE_RESULT_DTYPE", "FUSE_BAD_INPUT", "FUSE_NONFINITE", "FUSE_OCCUPIED_UNMAPPED", "FUSE_NONE",
            "FUSE_ADD", "FUSE_KEEP_OCCUPANT", "FUSE_REPLACE_OCCUPANT", "FUSE_BAD_OCCUPANT",
-           "LbaResult", "LBA_RESULT_DTYPE", "LBA_BAD_INPUT", "LBA_NONFINITE", "LBA_MAX_FREE"]
+           "LbaResult", "LBA_RESULT_DTYPE", "LBA_BAD_INPUT", "LBA_NONFINITE", "LBA_MAX_FREE",
+           "MapResult", "MAP_RESULT_DTYPE", "MAP_RESULT_FIELDS", "MAP_NORMALS", "MAP_DESCRIPTORS", "MAP_BAD_INPUT", "MAP_NONFINITE"]
 
 from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResult, HF_RESULT_DTYPE, InitResult,  # noqa: F401
                        INIT_RESULT_DTYPE, BAResult, BA_RESULT_DTYPE, PoseResult, POSE_RESULT_DTYPE, PnpResult, PNP_RESULT_DTYPE,
@@ -37,7 +38,7 @@ from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResu
                        SCW_RESULT_FIELDS, KfProjResult, KFPROJ_RESULT_DTYPE, KFPROJ_RESULT_FIELDS, MatchSim3Result,
                        MSIM3_RESULT_DTYPE, MSIM3_RESULT_FIELDS, TriMatchResult, TRI_MATCH_RESULT_DTYPE, TRI_MATCH_COUNTERS,
                        TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS, FuseResult, FUSE_RESULT_DTYPE, FUSE_RESULT_FIELDS,
-                       LbaResult, LBA_RESULT_DTYPE)
+                       LbaResult, LBA_RESULT_DTYPE, MapResult, MAP_RESULT_DTYPE, MAP_RESULT_FIELDS)
 
 E_EMPTY, E_BADARG, E_TOOSMALL, E_HIP, E_CAPACITY, E_RCCL = -1, -2, -3, -4, -5, -6
 _ERRNAMES = {-1: "ORBX_E_EMPTY", -2: "ORBX_E_BADARG", -3: "ORBX_E_TOOSMALL", -4: "ORBX_E_HIP", -5: "ORBX_E_CAPACITY", -6: "ORBX_E_RCCL"}
@@ -60,6 +61,7 @@ PNP_RAND_MAX = 2147483647
 SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT = 2, 4, 8, 16, 32
 SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
 LBA_BAD_INPUT, LBA_NONFINITE, LBA_MAX_FREE = 2, 4, 64
+MAP_NORMALS, MAP_DESCRIPTORS, MAP_BAD_INPUT, MAP_NONFINITE = 1, 2, 2, 4
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
 LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
 SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
@@ -267,6 +269,9 @@ def lib() -> ctypes.CDLL:
                                              vp, vp, vp, vp]
     L.orbx_local_ba.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, ctypes.POINTER(LbaResult)]
     L.orbx_debug_local_ba_lds_max_free.argtypes = [i32]
+    L.orbx_map_update_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                               i32, vp, vp, vp, vp, vp]
+    L.orbx_map_update.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, ctypes.POINTER(MapResult)]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1545,6 +1550,77 @@ class ORBextractor:
                                           _ptr(pts_out), _ptr(outlier), ctypes.byref(res)), "orbx_local_ba")
         return res, pose_out[:E], pts_out[:len(pts)], outlier[:E]
 
+    # -- behind the local bundle adjustment (include/orbx.h, "local mapping: updating the map points") ---------------------
+    def map_update_problems_device(self, n_frames: int, first, count, n_free, map_set, entry_frame, d_kps_un, d_desc, d_n, d_entry_pose,
+                                   d_rows, d_obs_outlier, n_map_sets: int, map_capacity: int, d_map_n, d_map_points, d_map_mask,
+                                   d_map_obs, d_res, d_map_normals=None, d_map_dist=None, d_map_desc=None, d_map_ref=None,
+                                   d_map_mask_out=None, what: int = MAP_NORMALS | MAP_DESCRIPTORS, capacity: Optional[int] = None) -> None:
+        """Batched and device-resident: the problems are those of local_ba_problems_device (d_entry_pose float32 [n_entries, 12] is
+        its d_pose_out, d_obs_outlier its vToErase bytes or None, d_rows int32 [n_entries, capacity] is rewritten: erased and
+        cleared observations become -1).  For every adjusted point: d_map_obs int32 [n_map_sets, map_capacity] (Observations()),
+        with MAP_NORMALS d_map_normals float32 [.., 3] and d_map_dist float32 [.., 2] (UpdateNormalAndDepth), with
+        MAP_DESCRIPTORS d_map_desc uint8 [.., 32] (ComputeDistinctiveDescriptors); d_map_mask_out None = in place (d_map_mask
+        must then be given); d_map_ref int32 [.., map_capacity] or None: the reference keyframes as frame indices, in and out;
+        d_res [n_problems] MAP_RESULT_DTYPE records (64 bytes).  Stream-ordered."""
+        first, count, n_free, map_set = _pair_lists(("first", "count", "n_free", "map_set"), (first, count, n_free, map_set))
+        entry_frame = np.ascontiguousarray(entry_frame, np.int32).reshape(-1)
+        cap, mcap, nf, ns, P, E = int(capacity or self.capacity), int(map_capacity), int(n_frames), int(n_map_sets), len(first), len(entry_frame)
+        if d_map_mask_out is None:
+            d_map_mask_out = d_map_mask
+        self._device_call("orbx_map_update_batch_device", nf, P, first, count, n_free, map_set, E, entry_frame,
+                          ("the keypoint array", d_kps_un, nf * cap * 28), ("the descriptor array", d_desc, nf * cap * 32),
+                          ("the count array", d_n, nf * 4), cap, ("the entry pose array", d_entry_pose, E * 48),
+                          ("the row array", d_rows, E * cap * 4), ("the outlier array", d_obs_outlier, E * cap), ns, mcap,
+                          ("the map count array", d_map_n, ns * 4), ("the map point array", d_map_points, ns * mcap * 12),
+                          ("the map mask", d_map_mask, ns * mcap), ("the map mask output", d_map_mask_out, ns * mcap),
+                          ("the reference keyframe array", d_map_ref, ns * mcap * 4), int(what),
+                          ("the map normal array", d_map_normals, ns * mcap * 12), ("the map distance array", d_map_dist, ns * mcap * 8),
+                          ("the map descriptor array", d_map_desc, ns * mcap * 32), ("the map observation array", d_map_obs, ns * mcap * 4),
+                          ("the result array", d_res, P * MAP_RESULT_DTYPE.itemsize))
+
+    def map_update(self, keys_un, desc, n, poses, rows, n_free: int, map_points, map_mask=None, obs_outlier=None, map_ref=None,
+                   map_normals=None, map_dist=None, map_desc=None, map_obs=None, what: int = MAP_NORMALS | MAP_DESCRIPTORS):
+        """One problem from host memory: keys_un [n_entries, capacity], desc [n_entries, capacity, 32], n [n_entries], poses
+        [n_entries, 12] (the adjusted ones), rows int32 [n_entries, capacity], the first n_free keyframes free; obs_outlier
+        [n_entries, capacity] or None; map_points [map_n, 3]; map_mask, map_ref (frame = keyframe index, -1 = none) [map_n] or
+        None; map_normals / map_dist / map_desc / map_obs: the arrays as they stand (None = zeros), of which the call rewrites
+        the adjusted points' rows.  Returns (MapResult, dict(rows, mask, ref, obs, normals, dist, desc))."""
+        k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+        if k.ndim != 2:
+            raise OrbxError(E_BADARG, "keys_un must be [n_entries, capacity]")
+        E, cap = k.shape
+        cnt = np.ascontiguousarray(n, np.int32).reshape(-1)
+        pose = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        r = np.array(rows, np.int32).reshape(-1, cap) if E else np.zeros((0, cap), np.int32)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, cap, 32) if E else np.zeros((0, cap, 32), np.uint8)
+        pts = _points(map_points)
+        N = len(pts)
+        if len(cnt) != E or len(pose) != E or len(r) != E or len(d) != E:
+            raise OrbxError(E_BADARG, "desc, n, poses and rows must have one entry per keyframe")
+        m = _flags(map_mask, N, "the map mask needs one entry per map point")
+        ol = None if obs_outlier is None else np.ascontiguousarray(np.asarray(obs_outlier) != 0, np.uint8).reshape(-1, cap)
+        if ol is not None and len(ol) != E:
+            raise OrbxError(E_BADARG, "obs_outlier needs one row per keyframe")
+
+        def have(a, dtype, width, what_):
+            out = np.zeros((max(N, 1),) + width, dtype)
+            if a is not None:
+                given = np.asarray(a, dtype).reshape((-1,) + width)
+                if len(given) != N:
+                    raise OrbxError(E_BADARG, "%s needs one row per map point" % what_)
+                out[:N] = given
+            return out
+        mask_out = have(np.ones(N, np.uint8) if m is None else m, np.uint8, (), "the map mask")
+        ref = None if map_ref is None else have(map_ref, np.int32, (), "map_ref")
+        nrm, dst = have(map_normals, np.float32, (3,), "map_normals"), have(map_dist, np.float32, (2,), "map_dist")
+        dsc, obs = have(map_desc, np.uint8, (32,), "map_desc"), have(map_obs, np.int32, (), "map_obs")
+        res = MapResult()
+        self._check(self._L.orbx_map_update(self._h, E, int(n_free), _ptr(k), _ptr(d), _ptr(cnt), max(cap, 1), _ptr(pose), _ptr(r), _ptr(ol), N,
+                                            _ptr(pts), _ptr(m), _ptr(mask_out), _ptr(ref), int(what), _ptr(nrm), _ptr(dst), _ptr(dsc),
+                                            _ptr(obs), ctypes.byref(res)), "orbx_map_update")
+        return res, dict(rows=r, mask=mask_out[:N], ref=None if ref is None else ref[:N], obs=obs[:N], normals=nrm[:N], dist=dst[:N],
+                         desc=dsc[:N])
+
     # -- PnPsolver behind SearchByBoW (include/orbx.h, "behind SearchByBoW: PnP RANSAC") ------------------------
     def pnp_solve(self, keys_un, points, mask, K, draws, sigma2=None, probability: float = 0.99, min_inliers: int = 10,
                   max_iterations: int = 300, epsilon: float = 0.5, th2: float = 5.991):
@@ -2269,6 +2345,14 @@ class MapFuser:
         self._ext.create_new_map_points_pairs_device(**create)
         self.fuse_pairs_device(**fuse)
         self._ext.local_ba_problems_device(**local_ba)
+
+    def fuse_local_ba_update_device(self, create: dict, fuse: dict, local_ba: dict, update: dict) -> None:
+        """fuse_local_ba_device(create, fuse, local_ba), then ORBextractor.map_update_problems_device(**update) on the same
+        stream, again with no copy and no wait: `update` names `local_ba`'s problems, its d_pose_out as d_entry_pose, its
+        d_obs_outlier and d_rows, and as outputs the arrays the next match_local_map_pairs_device reads (`fuse`'s d_map_normals,
+        d_map_dist, d_map_desc, d_map_obs; d_map_mask in place or a d_map_mask_out)."""
+        self.fuse_local_ba_device(create, fuse, local_ba)
+        self._ext.map_update_problems_device(**update)
 
     def _one(self, scw_form, keys_un, desc, map_points, map_normals, map_dist, map_desc, map_mask, map_obs, T, K, bounds, matches,
              occ_obs, th, th_low):

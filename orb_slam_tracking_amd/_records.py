@@ -3,7 +3,8 @@ order, from which ``_record`` makes the ``ctypes.Structure`` subclass, the numpy
 pair under its C struct's name; tests/test_abi_host.py compiles a probe against the header and compares sizes and offsets.
 RECORDS_FUSE is a second table of the same form for the records of "fusing map points into a keyframe"
 (tests/test_fuse_abi_host.py probes it the same way), RECORDS_LBA a third for the record of "local mapping: local bundle
-adjustment" (tests/test_lba_abi_host.py)."""
+adjustment" (tests/test_lba_abi_host.py), RECORDS_MAP a fourth for the record of "local mapping: updating the map points"
+(tests/test_map_update_abi_host.py)."""
 from __future__ import annotations
 
 import ctypes
@@ -15,6 +16,7 @@ _CTYPES = {"i4": ctypes.c_int32, "f4": ctypes.c_float, "f8": ctypes.c_double}
 RECORDS = {}  # C struct name -> (ctypes.Structure subclass or None, numpy dtype)
 RECORDS_FUSE = {}  # the same for orbx_fuse_result
 RECORDS_LBA = {}  # the same for orbx_lba_result
+RECORDS_MAP = {}  # the same for orbx_map_result
 
 
 def _as_dict(self) -> dict:
@@ -198,3 +200,11 @@ LbaResult, LBA_RESULT_DTYPE = _record(
     """orbx_lba_result: Optimizer::LocalBundleAdjustment's outcome for one problem, per round where a field has two entries
     (n_erased is the size of vToErase).""", table=RECORDS_LBA)
 assert LBA_RESULT_DTYPE.itemsize == 128
+
+MAP_RESULT_FIELDS = ("status", "n_points", "n_observations", "n_erased", "n_bad_points", "n_cleared", "n_ref_moved", "max_observers",
+                     "n_free")
+MapResult, MAP_RESULT_DTYPE = _record(
+    "orbx_map_result", "MapResult", _ints(*MAP_RESULT_FIELDS) + [("reserved", "i4", 7, list)],
+    """orbx_map_result: what the update of the map points behind a local bundle adjustment did for one problem (n_erased:
+    vToErase applied; n_bad_points: EraseObservation's SetBadFlag).""", table=RECORDS_MAP)
+assert MAP_RESULT_DTYPE.itemsize == 64

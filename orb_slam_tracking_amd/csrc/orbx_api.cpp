@@ -179,6 +179,7 @@ struct orbx_ctx {
   Sim3Scratch sim3;               // orbx_sim3_solve* (orbx_pose.cpp)
   Sim3OptScratch sim3Opt;         // orbx_optimize_sim3* (orbx_pose.cpp)
   LbaScratch lba;                 // orbx_local_ba* (orbx_ba.cpp)
+  MapScratch map;                 // orbx_map_update* (orbx_ba.cpp)
   TriScratch tri;                 // orbx_match_triangulation*, orbx_triangulate_matches* (orbx_match_bow.cpp)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
@@ -2522,6 +2523,7 @@ PnpScratch* ctxPnp(orbx_ctx* c) { return &c->pnp; }
 Sim3Scratch* ctxSim3(orbx_ctx* c) { return &c->sim3; }
 Sim3OptScratch* ctxSim3Opt(orbx_ctx* c) { return &c->sim3Opt; }
 LbaScratch* ctxLba(orbx_ctx* c) { return &c->lba; }
+MapScratch* ctxMap(orbx_ctx* c) { return &c->map; }
 TriScratch* ctxTri(orbx_ctx* c) { return &c->tri; }
 const float* ctxInvSigma2(const orbx_ctx* c, int* nlevels) {
   *nlevels = c->p.nlevels;

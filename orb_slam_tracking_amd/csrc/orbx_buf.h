@@ -245,4 +245,12 @@ struct LbaScratch {
   DeviceBuf<uint8_t> dWork;     // the problems' workspaces: graph, per-vertex and per-edge blocks, poses, reduced systems
 };
 
+// What a context keeps for orbx_map_update* (orbx_ba.cpp).
+struct MapScratch {
+  HeldArray<int32_t> problems;  // [5][n_problems] (first entry, entries, free entries, map set, workspace offset / 256) of the last call
+  HeldArray<int32_t> entries;   // the entry list [n_entries] (frames) of the last call
+  HeldArray<float> scale;       // mvScaleFactor
+  DeviceBuf<uint8_t> dWork;     // the problems' workspaces: MapWork of orbx_device.h
+};
+
 }  // namespace orbx

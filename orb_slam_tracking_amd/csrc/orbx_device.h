@@ -873,4 +873,60 @@ struct LbaArgs {
   int32_t ldsMaxFree;         // problems with at most this many free keyframes keep the packed factor in LDS
   uint32_t ldsBytes;          // dynamic LDS of the launch: the largest such factor
 };
+// k_map_build, k_map_points: the map points behind a local bundle adjustment (include/orbx.h, "local mapping: updating the map
+// points")
+constexpr int MAP_THREADS = 512;  // k_map_build: one workgroup per problem
+constexpr int MAP_WAVES = 4;      // k_map_points: waves per workgroup, one point per wave at a time
+constexpr int MAP_CHUNK = 64;     // k_map_points: points per workgroup
+// A problem's part of the workspace, every array 256-byte aligned: the one description the host sizes it by and the kernels
+// find their arrays by (base 0 only counts).
+struct MapWork {
+  int32_t* state;   // [mapCap] PT_VERTEX | PT_LOST | PT_BAD (csrc/orbx_map_math.inc)
+  int32_t* cnt;     // [mapCap] observers left behind the erasures
+  int32_t* refEnt;  // [mapCap] the reference keyframe's entry
+  int32_t* slot;    // [mapCap][nE] the inverse of the rows: the feature of entry e that names the point, or -1
+  int32_t* list;    // [mapCap][nE] the point's observers (entries), ascending, cnt of them
+  float* ow;        // [nE][3] the entries' camera centres
+  int32_t* flag;    // [1] the problem's status, for k_map_points
+};
+ORBX_HD inline size_t mapWorkLayout(int mapCap, int nE, uintptr_t base, MapWork* w) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const uintptr_t p = base + off;
+    off += (bytes + 255) / 256 * 256;
+    return p;
+  };
+  const size_t mc = (size_t)mapCap, ne = (size_t)nE;
+  w->state = (int32_t*)take(mc * 4);
+  w->cnt = (int32_t*)take(mc * 4);
+  w->refEnt = (int32_t*)take(mc * 4);
+  w->slot = (int32_t*)take(mc * ne * 4);
+  w->list = (int32_t*)take(mc * ne * 4);
+  w->ow = (float*)take(ne * 12);
+  w->flag = (int32_t*)take(4);
+  return off;
+}
+struct MapArgs {
+  const orbx_keypoint* kps;   // [frames][cap] mvKeysUn
+  const uint8_t* desc;        // [frames][cap][32]
+  const int32_t* nKps;        // [frames]
+  const float* entryPose;     // [nEntries][12]
+  int32_t* rows;              // [nEntries][cap], in and out
+  const uint8_t* outlier;     // [nEntries][cap] or null
+  const int32_t* problems;    // [5][nProblems]: first entry, entries, free entries, map set, workspace offset / 256
+  const int32_t* entryFrame;  // [nEntries]
+  const int32_t* mapN;        // [mapSets]
+  const float* mapPts;        // [mapSets][mapCap][3]
+  const uint8_t* mapMask;     // [mapSets][mapCap] or null
+  uint8_t* mapMaskOut;       // [mapSets][mapCap]
+  int32_t* mapRef;            // [mapSets][mapCap] or null
+  const float* scale;         // [nLevels] (device) mvScaleFactor
+  float* mapNormals;          // [mapSets][mapCap][3]
+  float* mapDist;             // [mapSets][mapCap][2]
+  uint8_t* mapDesc;           // [mapSets][mapCap][32]
+  int32_t* mapObs;            // [mapSets][mapCap]
+  orbx_map_result* res;       // [nProblems]
+  uint8_t* ws;                // the problems' workspaces
+  int32_t nProblems, cap, mapCap, nLevels, what;
+};
 }  // namespace orbx

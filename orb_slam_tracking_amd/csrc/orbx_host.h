@@ -32,6 +32,7 @@ Sim3Scratch* ctxSim3(orbx_ctx* c);
 Sim3OptScratch* ctxSim3Opt(orbx_ctx* c);
 TriScratch* ctxTri(orbx_ctx* c);
 LbaScratch* ctxLba(orbx_ctx* c);
+MapScratch* ctxMap(orbx_ctx* c);
 
 // ... and of a vocabulary (orbx_vocabulary is private to orbx_bow.cpp): the context it was made on, and the descent alone over
 // a batch; *nodes the vocabulary's breadth-first nodes, *fin [n_frames][capacity] the breadth-first index each feature ends at

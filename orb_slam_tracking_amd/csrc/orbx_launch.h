@@ -117,4 +117,7 @@ hipError_t launch_sim3_optimize(hipStream_t st, const Sim3OptArgs& a);
 // orbx_lba_kernel.hip
 hipError_t launch_lba(hipStream_t st, const LbaArgs& a);
 
+// orbx_map_kernel.hip: k_map_build, then (what != 0) k_map_points
+hipError_t launch_map_update(hipStream_t st, const MapArgs& a);
+
 }  // namespace orbx
