@@ -2364,6 +2364,11 @@ int orbx_debug_sincos(orbx_ctx* ctx, const float* angle_deg, int n, float* cos_o
  * bit 2: the descriptor kernel ran its pair form, two keypoints per wave (the launches on k_sel_compact's list); [5] frames per kernel launch; [6] 1 = the wide matcher kernels went with the batch; [7] lane the batch
  * went to (1-based; 0 = the context itself) }. */
 int orbx_debug_last_launch(const orbx_ctx* ctx, int32_t* info8);
+/* Host only, no device needed: how k_pyramid_bands' 512 threads split over a row of `groups` (1 .. 1024) groups of four output
+ * pixels, as the host hands it to the kernel with every launch -- info5 = { [0] groups per thread G (2 only when two_groups != 0,
+ * i.e. in a launch of the two-group instances), [1] thread-columns ngt, [2] thread-rows per pass rpp, [3] ceil(2^19 / ngt),
+ * [4] ceil(2^19 / rpp) }: the kernel computes x / d as (x * ceil(2^19 / d)) >> 19 and divides nothing. */
+int orbx_debug_pyr_cols(int groups, int two_groups, uint32_t* info5);
 /* Which matcher kernels did the work (cumulative since orbx_create, for the context itself -- a lane has its own): info4 = { [0] blocks
  * of 256 queries whose candidate lists k_match_bf_mfma built on the matrix cores (a brute-force block of a launch with at least 256
  * such blocks; everything else is listed by k_match_wide_lists on the vector ALU), [1..3] reserved (0) }.  Waits for the context's

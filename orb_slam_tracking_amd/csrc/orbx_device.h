@@ -262,13 +262,39 @@ struct PyrBands {
   int32_t safeFrom;                                      // frames >= safeFrom (batch index): nothing is known to follow their level 0
   int32_t maxRows;                                       // most rows any band has on any level (<= 256)
   int32_t xoff[ORBX_MAX_LEVELS], yoff[ORBX_MAX_LEVELS];  // the level's PyrXGroup / PyrYRow tables, in uint4 units from the table base
-  int16_t r0[ORBX_PYR_BANDS_MAX][ORBX_MAX_LEVELS], r1[ORBX_PYR_BANDS_MAX][ORBX_MAX_LEVELS];
+  // r0 | r1 << 16 (both below 32768): one dword, so that the kernel fetches the pair with a scalar load (16-bit fields of a
+  // kernel argument under a runtime index are fetched by the vector unit, and what is computed from them stays there)
+  uint32_t rows[ORBX_PYR_BANDS_MAX][ORBX_MAX_LEVELS];
   // column strips (round 5: few large frames -- four 3840x2160 frames are 128 workgroups of 32 bands, half the chip's CUs with one
   // workgroup each): strip s of a band produces the 4-pixel groups [g0, g1) of level l, its own share of the row plus the groups
   // its share of level l + 1 reads; workgroup = (band, strip).  One strip = the whole row (every 640x480 batch).
   int32_t nStrips;
-  int16_t g0[ORBX_PYR_STRIPS_MAX][ORBX_MAX_LEVELS], g1[ORBX_PYR_STRIPS_MAX][ORBX_MAX_LEVELS];
+  uint32_t grp[ORBX_PYR_STRIPS_MAX][ORBX_MAX_LEVELS];   // g0 | g1 << 16
+  // round 13: how the workgroup's 512 threads split into thread-columns and thread-rows on level l of strip s depends on the launch
+  // alone, so the host works it out (pyrColsOf) and the kernel divides nothing:
+  //   cols[s][l][0] = ceil(2^19 / ngt) | (ngt - 1) << 20 | (G - 1) << 31      cols[s][l][1] = ceil(2^19 / rpp) | (rpp - 1) << 20
+  // G groups per thread, ngt thread-columns, rpp thread-rows per pass (1 .. 512 each).  x / d == (x * ceil(2^19 / d)) >> 19 for
+  // d <= 512 and x < 1024: the error term x (d ceil(2^19 / d) - 2^19) / (d 2^19) stays below 1 / d while x (d - 1) < 2^19, and
+  // x * 2^19 < 2^32 (the kernel divides tid < 512 by ngt, and a band's rows + rpp - 1 < 768 by rpp)
+  int32_t twoGroups;                                     // the two-group instances (GMAX = 2) take this launch
+  uint32_t cols[ORBX_PYR_STRIPS_MAX][ORBX_MAX_LEVELS][2];
 };
+#define ORBX_PYR_INV_SHIFT 19
+#define ORBX_PYR_THREADS 512   // threads per workgroup of k_pyramid_bands (PYR_T)
+// groups per thread G, thread-columns ngt and thread-rows per pass rpp of a row of ng groups of 4 pixels: G (1 or 2) = whichever
+// fills more of the workgroup's threads with whole rows; two only in the two-group instances
+static inline void pyrColsOf(int ng, int twoGroups, uint32_t out[2]) {
+  const int nThreads = ORBX_PYR_THREADS;
+  ng = ng < 1 ? 1 : ng;
+  const int ngt2 = (ng + 1) >> 1;
+  const int use1 = ng <= nThreads ? ng * (nThreads / ng) : 0, use2 = ngt2 * (nThreads / ngt2);
+  const int G = twoGroups && use2 > use1 ? 2 : 1;
+  const int ngt = G == 2 ? ngt2 : ng;
+  const int rpp = nThreads / ngt > 1 ? nThreads / ngt : 1;
+  const uint32_t one = 1u << ORBX_PYR_INV_SHIFT;
+  out[0] = (one + (uint32_t)ngt - 1u) / (uint32_t)ngt | (uint32_t)(ngt - 1) << 20 | (uint32_t)(G - 1) << 31;
+  out[1] = (one + (uint32_t)rpp - 1u) / (uint32_t)rpp | (uint32_t)(rpp - 1) << 20;
+}
 // column constants of one group of 4 output pixels (host: appendPyrTables).  The group's taps lie in the 12 bytes of three
 // dwords at byte offsets o[0] = (first tap & ~3), o[1], o[2] of a source row (o[1], o[2]: + 4, + 8, but never beyond the
 // row's last dword, which can then only supply bytes of weight 0).

@@ -269,11 +269,21 @@ __device__ __forceinline__ uint32_t dot2u16(uint32_t a, uint32_t b, uint32_t c) 
 //     (checked on the host, else the per-level kernels run) the result is <= 255
 //   * rows: a thread keeps its column(s) and walks ONE contiguous run of the band's rows, two adjacent rows per step; the
 //     horizontal interpolation of a source row is computed once per thread -- shared between the step's two rows and carried
-//     to the next step (one-group instances) -- and lanes without a row stay out of the loop (round 12; at the row loop)
-__device__ __forceinline__ uint32_t mulHiU24(uint32_t a, uint32_t b) {  // v_mul_hi_u32_u24: bits 47:32 of the 24 x 24 bit product
-  return (uint32_t)(((unsigned long long)(a & 0xffffffu) * (unsigned long long)(b & 0xffffffu)) >> 32);
+//     to the next step (one-group instances) -- and lanes without a row stay out of the loop (round 12; at the row loop)// v_mul_hi_u32_u24: bits 47:32 of the product of the operands' low 24 bits.  Round 13: the instruction itself, on the operands as
+// they are.  Written as (a & 0xffffff) * (b & 0xffffff) >> 32 the compiler selects the same instruction but folds hrow's & ~0xff
+// into a & 0xffff00 of its own ONCE PER USE (a row interpolated once and used by two output rows was masked twice) and masks
+// the weights as well (20 v_and_b32 per step where 8 are needed).  Both operands are below 2^24 by the tables' construction:
+//   b = 16 t & ~0xff, 16 t = dot2(two bytes, Q11 pair << 4) <= 255 * 2048 * 16 (the pair sums to 2048: checked on the host)
+//   a = wy << 8 <= 2048 << 8 = 2^19 (PyrYRow)
+// The operands come from v_and_b32 (hrow: an ordinary VALU result, no wait states towards a VALU reader) and from ds_read_b128
+// (the compiler's own load, waited for before the statement); the result feeds ordinary VALU adds.
+static_assert(255ull * 2048 * 16 < (1ull << 24) && (2048ull << 8) <= (1ull << 19), "mulHiU24's operands fit 24 bits unmasked");
+__device__ __forceinline__ uint32_t mulHiU24(uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_mul_hi_u32_u24_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
 }
-#define PYR_T 512   // threads per workgroup: 512 fill their lanes with whole rows better than 256 (level 1 of 640x480: 469 of 512
+#define PYR_T ORBX_PYR_THREADS   // threads per workgroup: 512 fill their lanes with whole rows better than 256 (level 1 of 640x480: 469 of 512
                     // against 201 of 256) and take three fat bands per frame (3.5 % shared rows instead of 11 % with seven)
 #define PYR_R 2   // output rows in flight per thread and step
 // GMAX = groups of 4 pixels a thread may own: 2 in general; 1 (round 5) when no level (strip) is wider than PYR_T groups -- every
@@ -284,36 +294,47 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
                                                        const uint4* __restrict__ ptab, const PyrBands pb) {
   // the band's PyrYRow entries of the current level (and, filled meanwhile, of the next one): a step's row constants then
   // cost an LDS read instead of a global load in front of the source loads that depend on them
-  extern __shared__ uint4 yrows[];  // [2][pb.maxRows]
+  // Round 13: each half ends with one padding entry, a copy of the band's last row, so that a step reads the constants of its
+  // second row unconditionally (an odd run's last step has no second row: it then computes the last row twice and stores it once)
+  extern __shared__ uint4 yrows[];  // [2][pb.maxRows + 1]
   const int f = blockIdx.y + g.frame0, strip = (int)blockIdx.x / pb.nBands, band = (int)blockIdx.x - strip * pb.nBands, tid = threadIdx.x;
   const int nl = g.nlevels;
-  // column constants of this thread for level l
+  const int yhalf = pb.maxRows + 1;
+  // the band's n rows of level l from row q0, plus the padding entry: what thread tid stages (n == 0: nothing)
+  auto yrowOf = [&](int l, int q0, int n) { return (ptab + pb.yoff[l])[q0 + min(tid, n - 1)]; };
+  // column constants and row run of this thread for level l
   struct Cols {
     uint32_t o[GMAX], sel[GMAX][6], cf[GMAX][4];
-    int G, rpp, rsub, col, gOff;
-    bool lanes, haveG[GMAX];
+    int G, run0, run1, col, gOff;
+    bool haveG[GMAX];
   };
   auto loadCols = [&](int l, Cols& c) {
-    c.gOff = pb.g0[strip][l];
-    const int ng = max(pb.g1[strip][l] - c.gOff, 1);   // groups of 4 output pixels per row of this workgroup's strip
+    const uint32_t gr = pb.grp[strip][l], rw = pb.rows[band][l];
+    c.gOff = (int)(gr & 0xffffu);
     // A thread keeps its column(s): it owns G adjacent groups (8 or 4 output pixels) of one thread-column and walks down the
     // band's rows, so the column constants of its pixels are loaded ONCE per level and stay in registers.  rpp rows are
-    // covered per pass; G (1 or 2) = whichever fills more of the 256 lanes with whole rows (134 groups: 67 thread-columns
-    // x 3 rows = 201 of 256 lanes).  (The host takes this kernel only when every level >= 1 is at most 4096 pixels wide,
-    // i.e. at most PYR_T = 512 thread-columns of two groups: 3840x2160 frames qualify.)
-    const int ngt2 = (ng + 1) >> 1;
-    const int use1 = ng <= PYR_T ? ng * (PYR_T / ng) : 0, use2 = ngt2 * (PYR_T / ngt2);
-    c.G = GMAX == 2 && use2 > use1 ? 2 : 1;
-    const int ngt = c.G == 2 ? ngt2 : ng;
-    c.rpp = max(PYR_T / ngt, 1);
-    c.rsub = tid / ngt;
-    c.col = tid - c.rsub * ngt;
-    c.lanes = c.rsub < c.rpp;
+    // covered per pass; G (1 or 2) = whichever fills more of the 512 lanes with whole rows.  (The host takes this kernel only
+    // when every level >= 1 is at most 4096 pixels wide, i.e. at most PYR_T = 512 thread-columns of two groups: 3840x2160
+    // frames qualify.)  Round 13: G, the ngt thread-columns, rpp and the reciprocals of both come from the host (PyrBands::cols,
+    // pyrColsOf): what used to be two runtime divisions per thread and two per wave is two 24-bit multiplies and shifts.
+    const uint32_t k0 = pb.cols[strip][l][0], k1 = pb.cols[strip][l][1];
+    c.G = GMAX == 2 ? 1 + (int)(k0 >> 31) : 1;
+    const int ngt = (int)(k0 >> 20 & 0x1ffu) + 1, rpp = (int)(k1 >> 20 & 0x1ffu) + 1;
+    const int rsub = (int)(((uint32_t)tid * (k0 & 0xfffffu)) >> ORBX_PYR_INV_SHIFT);   // tid / ngt
+    c.col = tid - rsub * ngt;
+    // the thread-row's run of the band's rows (round 12; at the row loop): Lr = ceil(n / rpp) rounded up to even
+    const int r0 = (int)(rw & 0xffffu), r1 = (int)(rw >> 16);
+    const int Lr = ((int)(((uint32_t)(r1 - r0 + rpp - 1) * (k1 & 0xfffffu)) >> ORBX_PYR_INV_SHIFT) + 1) & ~1;
+    c.run0 = r0 + rsub * Lr;
+    c.run1 = rsub < rpp ? min(r1, c.run0 + Lr) : c.run0;
+    const bool rowsHere = c.run0 < c.run1;
+    // a wave none of whose lanes has a row on this level keeps the constants it has: nothing will read them
+    if (__ballot(rowsHere) == 0ull) return;
     const uint4* xg = ptab + pb.xoff[l];
 #pragma unroll
     for (int j = 0; j < GMAX; j++) {
       const int gx = c.col * c.G + j;
-      c.haveG[j] = c.lanes && j < c.G && gx < pb.g1[strip][l] - c.gOff;
+      c.haveG[j] = rowsHere && j < c.G && gx < (int)(gr >> 16) - c.gOff;
       const uint4* e = xg + (unsigned)(c.haveG[j] ? c.gOff + gx : 0) * 4u;
       const uint4 X0 = e[0], X1 = e[1], X2 = e[2];
       const uint32_t X3 = e[3].x;
@@ -325,8 +346,8 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
   Cols C;
   loadCols(1, C);
   {
-    const int r0 = pb.r0[band][1], n = pb.r1[band][1] - r0;
-    if (tid < n) yrows[pb.maxRows + tid] = (ptab + pb.yoff[1])[r0 + tid];
+    const int r0 = (int)(pb.rows[band][1] & 0xffffu), n = (int)(pb.rows[band][1] >> 16) - r0;
+    if (n > 0 && tid <= n) yrows[yhalf + tid] = yrowOf(1, r0, n);
   }
   __syncthreads();
   for (int l = 1; l < nl; l++) {
@@ -334,18 +355,18 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     const LevelGeom& D = g.L[l];
     const uint8_t* src = l == 1 ? img0 + (long long)f * img0FrameStride : pyr + S.imgOff + (long long)f * S.frameStride;
     uint8_t* dst = pyr + D.imgOff + (long long)f * D.frameStride;
-    const uint4* yr = yrows + (l & 1) * pb.maxRows;
-    const int r0 = pb.r0[band][l], r1 = pb.r1[band][l];
+    const uint4* yr = yrows + (l & 1) * yhalf;
+    const int r0 = (int)(pb.rows[band][l] & 0xffffu);
     const int dstride = D.stride;
     // the next level's row constants are fetched now and used after the barrier: their latency runs under this level's rows
     uint4 nextY = make_uint4(0, 0, 0, 0);
-    int nextN = 0;
+    int nextN = 0;   // entries to stage: the band's rows and the padding entry
     if (l + 1 < nl) {
-      const int q0 = pb.r0[band][l + 1];
-      nextN = pb.r1[band][l + 1] - q0;
-      if (tid < nextN) nextY = (ptab + pb.yoff[l + 1])[q0 + tid];
+      const int q0 = (int)(pb.rows[band][l + 1] & 0xffffu), n = (int)(pb.rows[band][l + 1] >> 16) - q0;
+      nextN = n > 0 ? n + 1 : 0;
+      if (tid < nextN) nextY = yrowOf(l + 1, q0, n);
     }
-    const int G = C.G, rpp = C.rpp;
+    const int G = C.G;
     // The three dwords of a group come as ONE 12-byte load (the addresser's cost is per instruction and lane: 18 cycles, against
     // 3 x 12 for single dwords at this pitch).  At the end of a row that reads up to 11 bytes beyond the last pixel: the next
     // row, the next level, the next frame, or the slack the pyramid buffer ends with; only behind the last row of the
@@ -394,8 +415,12 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
 #pragma unroll
       for (int i = 0; i < 4; i++) t[i] = dot2u16(p[i], C.cf[j][i], 0u) & ~0xffu;
     };
-    const int Lr = ((r1 - r0 + rpp - 1) / rpp + 1) & ~1;
-    const int run0 = r0 + C.rsub * Lr, run1 = C.lanes ? min(r1, run0 + Lr) : run0;
+    // the two weighted rows of an output row: mulHiU24 on the masked 16 t as they are, no second mask (round 13)
+    auto vrow = [&](const uint4 w, const uint32_t (&ta)[4], const uint32_t (&tb)[4], uint32_t (&u)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) u[i] = mulHiU24(w.z, ta[i]) + mulHiU24(w.w, tb[i]);
+    };
+    const int run0 = C.run0, run1 = C.run1;   // (loadCols: the host's thread split, no division here)
     uint32_t car[GMAX][4] = {}, carOff = ~0u;   // the interpolated lower source row of the run's last output row, and its offset
     const unsigned col0 = (unsigned)((C.gOff + C.col * G) * 4);
     // (for a lane without a run, run0 may lie beyond the band, the level and yrows: out and ty are only formed there, never
@@ -404,10 +429,12 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     const uint4* ty = yr + (run0 - r0);
     for (int dy0 = run0; dy0 < run1; dy0 += 2, out += 2 * dstride, ty += 2) {  // two adjacent rows per step: their loads are in flight together
       const bool live1 = dy0 + 1 < run1;
-      const uint4 ty0 = ty[0], ty1 = ty[live1 ? 1 : 0];
-      // (wave-uniform) some lane's upper source rows are not the ones it already has
+      // ty[1] of an odd run's last step is the row after the run: run0 + Lr is even, so the run ends at r1 there and this is the
+      // half's padding entry, a copy of ty[0] -- valid offsets for the loads below, and nothing of it is stored (live1)
+      const uint4 ty0 = ty[0], ty1 = ty[1];
+      // (wave-uniform) some lane's upper source rows are not the ones it already has; the two lane masks meet as scalars
       const bool upper0 = !PYR_CARRY || __ballot(ty0.x != carOff) != 0ull;
-      const bool upper1 = __ballot(live1 && ty1.x != ty0.y) != 0ull;
+      const bool upper1 = (__ballot(ty1.x != ty0.y) & __ballot(live1)) != 0ull;
       PyrU3 ra0[GMAX], rb0[GMAX], ra1[GMAX], rb1[GMAX];
 #pragma unroll
       for (int j = 0; j < GMAX; j++)
@@ -420,30 +447,28 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
 #pragma unroll
       for (int j = 0; j < GMAX; j++) {
         if (j >= G) continue;
-        uint32_t ta0[4], tb0[4], ta1[4], tb1[4];
+        // Round 13: the vertical step is written once per outcome of each test, reading the row it needs where that row lies
+        // (the fresh one, the carried one, or the first output row's lower one): no row is selected or copied into another's registers
+        uint32_t tb0[4], tb1[4], u[4], v[4];
         hrow(rb0[j], j, tb0);
         hrow(rb1[j], j, tb1);
         if (upper0) {
+          uint32_t ta0[4];
           hrow(ra0[j], j, ta0);
+          vrow(ty0, ta0, tb0, u);
         } else {
-#pragma unroll
-          for (int i = 0; i < 4; i++) ta0[i] = car[j][i];
+          vrow(ty0, car[j], tb0, u);
         }
         if (upper1) {
+          uint32_t ta1[4];
           hrow(ra1[j], j, ta1);
+          vrow(ty1, ta1, tb1, v);
         } else {
-#pragma unroll
-          for (int i = 0; i < 4; i++) ta1[i] = tb0[i];
+          vrow(ty1, tb0, tb1, v);
         }
         if (PYR_CARRY) {
 #pragma unroll
           for (int i = 0; i < 4; i++) car[j][i] = tb1[i];
-        }
-        uint32_t u[4], v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          u[i] = mulHiU24(ty0.z, ta0[i]) + mulHiU24(ty0.w, tb0[i]);
-          v[i] = mulHiU24(ty1.z, ta1[i]) + mulHiU24(ty1.w, tb1[i]);
         }
         // (u + 2) >> 2 on two 16-bit fields at a time; bytes 0 and 2 of each pair are the pixels
         const uint32_t s01 = ((u[0] | (u[1] << 16)) + 0x00020002u) >> 2, s23 = ((u[2] | (u[3] << 16)) + 0x00020002u) >> 2;
@@ -456,7 +481,7 @@ __global__ __launch_bounds__(PYR_T) void k_pyramid_bands(const uint8_t* __restri
     };
     if (l == 1 && f >= pb.safeFrom) rows(std::true_type{});
     else rows(std::false_type{});
-    if (tid < nextN) yrows[((l + 1) & 1) * pb.maxRows + tid] = nextY;
+    if (tid < nextN) yrows[((l + 1) & 1) * yhalf + tid] = nextY;
     if (l + 1 < nl) loadCols(l + 1, C);
     // this band of level l is the source of the band of level l + 1 in the same workgroup: the barrier's workgroup-scope
     // release/acquire is all that is needed (the CU's vector L1 is coherent for its own workgroup; an agent-scope
@@ -3449,16 +3474,10 @@ hipError_t launch_pyramid_bands(hipStream_t st, int nFrames, const uint8_t* img0
   if (nFrames <= 0 || g.nlevels <= 1) return hipSuccess;
   dim3 block(PYR_T, 1, 1), grid(pb.nBands * pb.nStrips, nFrames, 1);
   if (pb.maxRows > 256 || pb.maxRows < 1 || pb.nStrips < 1 || pb.nStrips > ORBX_PYR_STRIPS_MAX) return hipErrorInvalidValue;  // (the host picks the band count accordingly)
-  // one group per thread when no level's strip is wider than PYR_T groups (GMAX = 1: fewer registers)
-  bool one = true;
-  for (int l = 1; l < g.nlevels; l++)
-    for (int s2 = 0; s2 < pb.nStrips; s2++) one = one && pb.g1[s2][l] - pb.g0[s2][l] <= PYR_T;
-  // ... and when rows of at most 256 groups leave 512 threads at least two rows per pass: with one row of 270 .. 400 groups per
-  // pass (1920x1080: levels 1 .. 3) two groups per thread fill the lanes so much better that they win (config 3: pyramid 0.242
-  // against 0.285 ms per batch; 640x480 and the strips of 3840x2160 the other way round: 425.2 k against 416.8 k frames/s,
-  // 0.206 against 0.243 ms)
-  one = one && g.nlevels > 1 && pb.g1[0][1] - pb.g0[0][1] <= PYR_T / 2;
-  const size_t lds = 2 * (size_t)pb.maxRows * sizeof(uint4);
+  // one group per thread (GMAX = 1) or two: the host decided with the thread split it put into pb.cols (computePyrBands)
+  const bool one = !pb.twoGroups;
+  // (one padding entry per half: a step reads its second row's constants unconditionally)
+  const size_t lds = 2 * ((size_t)pb.maxRows + 1) * sizeof(uint4);
   const uint4* tab4 = reinterpret_cast<const uint4*>(tab);
   if (pb.dual2 && one) hipLaunchKernelGGL((k_pyramid_bands<1, 1>), grid, block, lds, st, img0, img0FrameStride, pyr, g, tab4, pb);
   else if (pb.dual2) hipLaunchKernelGGL((k_pyramid_bands<1, 2>), grid, block, lds, st, img0, img0FrameStride, pyr, g, tab4, pb);

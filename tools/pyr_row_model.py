@@ -36,6 +36,13 @@ STRIPS_MAX = 8   # ORBX_PYR_STRIPS_MAX
 STEP_INSTS = 70  # vector instructions of a step outside hrow (instance <0,1>)
 HROW_INSTS = 14
 LEVEL_INSTS = 71  # vector instructions of a wave per level outside the loop (round 12's listing of <0,1>)
+# Round 13's listing of <0,1> (one mask per interpolated row, no row copies, thread split from the host): a step without upper rows is
+# 78 vector instructions = 50 + 2 x 14, and an upper row adds its interpolation and the address of its load, 15:
+#   vector instructions per frame ~ 48 wave-steps + 15 interpolations + 40 busy wave-levels + 24 idle wave-levels
+STEP_INSTS_R13 = 48
+HROW_INSTS_R13 = 15
+LEVEL_INSTS_R13 = 40       # a wave with a row on the level: column record, run bounds, the next level's row table
+LEVEL_IDLE_INSTS_R13 = 24  # a wave without one: it skips the column record and the loop's set-up
 
 f32 = np.float32
 
@@ -176,6 +183,24 @@ def level_runs(rows, r0, r1, ng, gmax):
     return steps, interps
 
 
+def wave_level_counts(w, h, scale_factor, nlevels, K, S):
+    """(busy, idle) wave-levels per frame under round 12's map: waves with and without a row on a level, over the frame's workgroups."""
+    levels = geometry(w, h, scale_factor, nlevels)
+    r, g = bands(levels, K, S)
+    gmax = 2 if two_groups(levels, g) else 1
+    busy = idle = 0
+    for l in range(1, nlevels):
+        for b in range(len(r)):
+            for s in range(len(g)):
+                _, ngt, rpp = columns(g[s][l][1] - g[s][l][0], gmax)
+                r0, r1 = r[b][l]
+                Lr = ((r1 - r0 + rpp - 1) // rpp + 1) & ~1
+                for w0 in range(0, PYR_T, WAVE):
+                    rows = any(rs < rpp and r0 + rs * Lr < r1 for rs in {t // ngt for t in range(w0, w0 + WAVE)})
+                    busy, idle = busy + rows, idle + (not rows)
+    return busy, idle
+
+
 def model(w, h, scale_factor, nlevels, K, S, level_fn):
     """Per level >= 1: (wave-steps, interpolations) per frame, summed over the frame's workgroups."""
     levels = geometry(w, h, scale_factor, nlevels)
@@ -221,6 +246,11 @@ def main():
     wave_levels = (PYR_T // WAVE) * min(a.bands, BANDS_MAX) * len(bands(levels, a.bands, a.strips)[1]) * (a.levels - 1)
     print("runs, with %d vector instructions per wave and level outside the loop (%d wave-levels): %.1f k" %
           (LEVEL_INSTS, wave_levels, (STEP_INSTS * st + HROW_INSTS * it + LEVEL_INSTS * wave_levels) / 1e3))
+    busy, idle = wave_level_counts(*args)
+    print("round 13's weights, %d x + %d x + %d x %d busy + %d x %d idle wave-levels: %.1f k%s" %
+          (STEP_INSTS_R13, HROW_INSTS_R13, LEVEL_INSTS_R13, busy, LEVEL_IDLE_INSTS_R13, idle,
+           (STEP_INSTS_R13 * st + HROW_INSTS_R13 * it + LEVEL_INSTS_R13 * busy + LEVEL_IDLE_INSTS_R13 * idle) / 1e3,
+           "" if gmax == 1 else " (one-group weights: indicative only)"))
 
 
 if __name__ == "__main__":
