@@ -2369,6 +2369,14 @@ int orbx_debug_last_launch(const orbx_ctx* ctx, int32_t* info8);
  * i.e. in a launch of the two-group instances), [1] thread-columns ngt, [2] thread-rows per pass rpp, [3] ceil(2^19 / ngt),
  * [4] ceil(2^19 / rpp) }: the kernel computes x / d as (x * ceil(2^19 / d)) >> 19 and divides nothing. */
 int orbx_debug_pyr_cols(int groups, int two_groups, uint32_t* info5);
+/* Host only, no device needed: the cell records k_fast_wave reads (one 64-byte record of sixteen dwords per FAST cell, in the
+ * order (level, cell row, cell column); csrc/orbx_device.h, FastCell) as a context with these parameters and `max_batch` frames
+ * builds them for frames of width x height pixels whose level-0 rows lie `stride0` bytes apart.  records (nullable) receives
+ * min(cells, cap) records of 16 dwords; info4 = { [0] cells of a frame over all levels, [1] which instance takes the geometry:
+ * 0 = none (k_fast runs, and the records are zero), 1 = tile rows of 64 bytes, 2 = of 48 bytes, [2] bytes of the tile in the
+ * kernel's dynamic LDS, [3] bytes of that LDS in all }. */
+int orbx_debug_fast_cells(const orbx_params* params, int width, int height, int stride0, int max_batch, uint32_t* records, int cap,
+                          int32_t* info4);
 /* Which matcher kernels did the work (cumulative since orbx_create, for the context itself -- a lane has its own): info4 = { [0] blocks
  * of 256 queries whose candidate lists k_match_bf_mfma built on the matrix cores (a brute-force block of a launch with at least 256
  * such blocks; everything else is listed by k_match_wide_lists on the vector ALU), [1..3] reserved (0) }.  Waits for the context's

@@ -343,6 +343,7 @@ def lib() -> ctypes.CDLL:
     L.orbx_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     L.orbx_debug_last_launch.argtypes = [vp, vp]
     L.orbx_debug_pyr_cols.argtypes = [ctypes.c_int, ctypes.c_int, vp]
+    L.orbx_debug_fast_cells.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp]
     L.orbx_debug_match_counters.argtypes = [vp, vp]
     L.orbx_debug_selection_units.argtypes = [vp, i32, vp, vp]
     L.orbx_debug_path_codes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]

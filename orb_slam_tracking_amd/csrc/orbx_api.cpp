@@ -95,18 +95,26 @@ struct PairBlock {
   }
 };
 
-struct orbx_ctx {
+// What the ORBextractor tables (computeTables) and a frame size's geometry (buildGeometry, buildFastCells) are computed from and
+// into: host arithmetic only, no device, no buffer.  A context is one of these plus everything that lives on a device;
+// orbx_debug_fast_cells makes one on its own.
+struct ExtractorSetup {
   orbx_params p{};
-  int device = 0;
-  hipStream_t st = nullptr;
-  bool ownStream = false;
-  int maxW = 0, maxH = 0, maxB = 0;
+  int maxB = 0;
   std::vector<float> scale, invScale, sigma2, invSigma2;
   std::vector<int> quota;
   int umax[16]{};
-  int gaussVariant = 0, grayVariant = 0;  // orbx_set_opencv_variant
   int libmVariant = ORBX_LIBM_DEFAULT;    // orbx_set_libm_variant
   int selCap = 0;  // sum of the per-level quotas
+  std::string err;
+};
+
+struct orbx_ctx : ExtractorSetup {
+  int device = 0;
+  hipStream_t st = nullptr;
+  bool ownStream = false;
+  int maxW = 0, maxH = 0;
+  int gaussVariant = 0, grayVariant = 0;  // orbx_set_opencv_variant
 
   // geometry of the current frame size
   int curW = 0, curH = 0, curStride0 = 0;
@@ -215,14 +223,12 @@ struct orbx_ctx {
   int parity = 0;          // of the batch being issued
   double ms[ORBX_STAGE_COUNT]{};
   int64_t launches[ORBX_STAGE_COUNT]{};
-
-  std::string err;
 };
 
 namespace {
 
 // ORBextractor ctor arithmetic, Features/ORBextractor.cpp:508-594
-void computeTables(orbx_ctx* c) {
+void computeTables(ExtractorSetup* c) {
   const int nl = c->p.nlevels;
   const double scaleFactor = (double)c->p.scale_factor;  // the member is a double (hpp:142)
   c->scale.assign(nl, 1.f);
@@ -264,7 +270,7 @@ void computeTables(orbx_ctx* c) {
   }
 }
 
-void levelSize(const orbx_ctx* c, int w, int h, int l, int* lw, int* lh) {  // cpp:1662-1663
+void levelSize(const ExtractorSetup* c, int w, int h, int l, int* lw, int* lh) {  // cpp:1662-1663
   *lw = cvRoundF(w * c->invScale[l]);
   *lh = cvRoundF(h * c->invScale[l]);
 }
@@ -329,7 +335,7 @@ void appendPyrTables(const Geom& g, std::vector<ResizeTab>* tab, PyrTabInfo* inf
   }
 }
 
-int buildGeometry(orbx_ctx* c, int w, int h, int stride0, Geom* out, std::vector<ResizeTab>* tab, PyrTabInfo* pyrInfo = nullptr) {
+int buildGeometry(ExtractorSetup* c, int w, int h, int stride0, Geom* out, std::vector<ResizeTab>* tab, PyrTabInfo* pyrInfo = nullptr) {
   Geom g{};
   g.nlevels = c->p.nlevels;
   g.iniTh = std::min(std::max(c->p.ini_th_fast, 0), 255);
@@ -441,35 +447,76 @@ int buildGeometry(orbx_ctx* c, int w, int h, int stride0, Geom* out, std::vector
 // k_fast_wave's cell records (FastCell): the cell rectangles of ComputeKeyPointsOctTree (cpp:1078-1103) for every level,
 // with everything a wave would otherwise derive from its cell index.  Returns whether every cell fits the kernel's tile.
 // 0 = some cell does not fit (k_fast runs), 1 = tiles of 16 dwords x 64 rows, 2 = every cell image is at most 12 dwords wide.
+// The first walk over the cells decides the tile stride (which every LDS-relative field depends on), the second fills the records.
+// A geometry the kernel cannot take (return 0) leaves the records zero: rows == 0, and nothing reads them.
 int buildFastCells(const Geom& g, std::vector<FastCell>* out) {
   out->assign((size_t)g.nCellsTotal, FastCell{});
+  struct Rect {
+    int iniX, iniY, cw, ch;  // ch == 0: the cell detects nothing
+  };
+  auto rectOf = [](const LevelGeom& L, int ci, int cj) {
+    Rect r{ORBX_MIN_BORDER + cj * L.wCell, ORBX_MIN_BORDER + ci * L.hCell, 0, 0};
+    if (r.iniY >= L.maxBY - 3 || r.iniX >= L.maxBX - 6) return r;  // cpp:1088, 1101
+    const int maxY = std::min(r.iniY + L.hCell + 6, L.maxBY), maxX = std::min(r.iniX + L.wCell + 6, L.maxBX);
+    if (maxX - r.iniX < 7 || maxY - r.iniY < 7) return r;  // cv::FAST finds nothing in an image this small
+    r.cw = maxX - r.iniX;
+    r.ch = maxY - r.iniY;
+    return r;
+  };
   bool ok = true, narrow = true;
+  for (int l = 0; l < g.nlevels; l++) {
+    const LevelGeom& L = g.L[l];
+    // (widths of the packed fields; a level's frames lie less than 2^32 bytes apart, level 0's stride comes with the launch)
+    if (L.segCap >= 2048 || L.candCap >= (1 << 30) || (l > 0 && (L.frameStride <= 0 || L.frameStride >= (int64_t)1 << 32))) ok = false;
+    for (int ci = 0; ci < L.nRows; ci++)
+      for (int cj = 0; cj < L.nCols; cj++) {
+        const Rect r = rectOf(L, ci, cj);
+        if (r.ch == 0) continue;
+        const int nw = (r.iniX + r.cw - (r.iniX & ~3) + 3) >> 2;
+        if (nw > 16 || r.ch > 64) ok = false;
+        if (nw > 12) narrow = false;
+      }
+  }
+  if (!ok) return 0;
+  const int TS = narrow ? 48 : 64;
+  const FastWaveLds lds = fastWaveLds(g, TS);
+  const uint32_t tileAddr = 16u;
   for (int l = 0; l < g.nlevels; l++) {
     const LevelGeom& L = g.L[l];
     for (int ci = 0; ci < L.nRows; ci++)
       for (int cj = 0; cj < L.nCols; cj++) {
+        const Rect r = rectOf(L, ci, cj);
+        if (r.ch == 0) continue;
         const int local = ci * L.nCols + cj;
         FastCell& c = (*out)[(size_t)L.cellBase + local];
-        c.xoff_level = (uint32_t)l << 16;
+        const int ax0 = r.iniX & ~3, xoff = r.iniX - ax0, iw = r.cw - 6, ih = r.ch - 6;
+        c.img = (uint64_t)(l == 0 ? 0 : L.imgOff) + (uint64_t)r.iniY * (uint64_t)L.stride + (uint64_t)ax0;
+        c.frameStride = l == 0 ? 0u : (uint32_t)L.frameStride;
         c.stride = (uint32_t)L.stride;
-        c.segOff = (uint32_t)local * (uint32_t)L.segCap;
-        c.segCap = (uint32_t)L.segCap;
-        const int iniY = ORBX_MIN_BORDER + ci * L.hCell, iniX = ORBX_MIN_BORDER + cj * L.wCell;
-        if (iniY >= L.maxBY - 3 || iniX >= L.maxBX - 6) continue;  // cpp:1088, 1101 (rows stay 0)
-        const int maxY = std::min(iniY + L.hCell + 6, L.maxBY), maxX = std::min(iniX + L.wCell + 6, L.maxBX);
-        const int cw = maxX - iniX, ch = maxY - iniY;
-        if (cw < 7 || ch < 7) continue;  // cv::FAST finds nothing in an image this small
-        const int ax0 = iniX & ~3, xoff = iniX - ax0, nw = (maxX - ax0 + 3) >> 2;
-        if (nw > 16 || ch > 64) ok = false;
-        if (nw > 12) narrow = false;
-        c.imgOff = (uint32_t)(iniY * L.stride + ax0);
-        c.nw_ch = (uint32_t)nw | ((uint32_t)ch << 16);
-        c.iw_ih = (uint32_t)(cw - 6) | ((uint32_t)(ch - 6) << 16);
-        c.xoff_level |= (uint32_t)xoff;
-        c.ox_oy = ((uint32_t)(cj * L.wCell - xoff) & 0xffffu) | ((uint32_t)(ci * L.hCell) << 16);
+        c.cand = 4u * ((uint64_t)L.candOff + (uint64_t)local * (uint64_t)L.segCap);
+        c.candCap = 4u * (uint32_t)L.candCap;
+        c.oxy = (uint32_t)(cj * L.wCell - xoff) + ((uint32_t)(ci * L.hCell) << 12);
+        // the sweep over quads of four pixels: item = (quad column, row), a lane's next item is 64 further (k_fast_wave)
+        const int nqc = (iw + 3) >> 2, sh = (xoff + 3) & 3;
+        const uint32_t inv = ((1u << 20) + (uint32_t)nqc - 1u) / (uint32_t)nqc;
+        const int dqy = (int)((64u * inv) >> 20), dqc = 64 - dqy * nqc;
+        c.dPos = ((uint32_t)dqc << 16) | (uint32_t)(dqy * TS + 4 * dqc);
+        c.wrapK = (uint32_t)(TS - 4 * nqc) - ((uint32_t)nqc << 16);
+        c.selC0 = 0x0c000c00u + (uint32_t)sh * 0x00010001u + 0x00010000u;
+        c.selR0 = 0x0c000c00u + (uint32_t)(sh <= 1 ? sh + 3 : sh - 1) * 0x00010001u + 0x00010000u;
+        c.lastThr = (uint32_t)(nqc - 1) << 16;
+        const uint32_t aLast = tileAddr + (uint32_t)((ih - 1) * TS + xoff + 3 - sh + 4 * (nqc - 1) - 4);
+        const uint32_t kN = (uint32_t)lds.tileBytes - (uint32_t)xoff;
+        c.aLast_kN = aLast | (kN << 16);
+        const int nvLast = iw - 4 * (nqc - 1);  // 1 .. 4, stored as the three bits (nvLast > j), j = 1 .. 3
+        const uint32_t inside = (uint32_t)(nvLast > 1) | ((uint32_t)(nvLast > 2) << 1) | ((uint32_t)(nvLast > 3) << 2);
+        c.quad = inv | ((uint32_t)nqc << 21) | (inside << 25) | ((uint32_t)(sh >= 2) << 28) | ((uint32_t)(sh + 1) << 29);
+        const int nItems = nqc * ih, nFull = (nItems - 1) >> 6, nTail = nItems - 64 * nFull;  // nTail: 1 .. 64
+        c.counts = (uint32_t)nFull | ((uint32_t)(64 - nTail) << 4) | ((uint32_t)L.segCap << 10) | ((uint32_t)r.ch << 21) |
+                   ((uint32_t)xoff << 28);
       }
   }
-  return ok ? (narrow ? 2 : 1) : 0;
+  return narrow ? 2 : 1;
 }
 
 struct Sizes {
@@ -2474,6 +2521,32 @@ int orbx_debug_pyr_cols(int groups, int two_groups, uint32_t* info5) {
   info5[2] = (c[1] >> 20 & 0x1ffu) + 1;
   info5[3] = c[0] & 0xfffffu;
   info5[4] = c[1] & 0xfffffu;
+  return ORBX_OK;
+}
+
+int orbx_debug_fast_cells(const orbx_params* params, int width, int height, int stride0, int max_batch, uint32_t* records, int cap,
+                          int32_t* info4) {
+  if (!params || !info4 || cap < 0 || (cap > 0 && !records) || params->nlevels < 1 || params->nlevels > ORBX_MAX_LEVELS ||
+      params->nfeatures < 1 || !(params->scale_factor >= 1.0f) || (params->scale_factor == 1.0f && params->nlevels > 1) || width < 1 ||
+      height < 1 || stride0 < width || max_batch < 1)
+    return ORBX_E_BADARG;  // (as orbx_create asks)
+  ExtractorSetup tmp;  // (no device behind it: the ORBextractor tables and the geometry are host arithmetic)
+  tmp.p = *params;
+  tmp.maxB = max_batch;
+  computeTables(&tmp);
+  Geom g;
+  const int r = buildGeometry(&tmp, width, height, stride0, &g, nullptr);
+  if (r != ORBX_OK) return r;
+  std::vector<FastCell> cells;
+  const int ok = buildFastCells(g, &cells);
+  const FastWaveLds lds = fastWaveLds(g, ok == 2 ? 48 : 64);
+  info4[0] = g.nCellsTotal;
+  info4[1] = ok;
+  info4[2] = ok ? lds.tileBytes : 0;
+  info4[3] = ok ? lds.total : 0;
+  static_assert(sizeof(FastCell) == 16 * sizeof(uint32_t), "a record is sixteen dwords");
+  const size_t n = std::min((size_t)cap, cells.size());
+  if (n) memcpy(records, cells.data(), n * sizeof(FastCell));
   return ORBX_OK;
 }
 

@@ -45,18 +45,45 @@ struct Geom {
 };
 
 // k_fast_wave: what one wave needs to know about its FAST cell, precomputed on the host (buildFastCells) so that the kernel's
-// prologue is one scalar load instead of a level search and a dozen divisions / multiplications per wave
-struct FastCell {          // 32 bytes, eight dwords (16-bit fields are packed by hand: scalar loads come in dwords)
-  uint32_t imgOff;         // byte offset, inside the frame's level image, of the first staged dword (row iniY, column iniX & ~3)
-  uint32_t segOff;         // entry offset of the cell's candidate segment inside the frame's level area (local cell * segCap)
+// prologue is one scalar load instead of a level search and a dozen divisions / multiplications per wave.  Round 14: the record
+// carries everything the wave used to derive from the cell, its level (LevelGeom, a second scalar load behind the first) and the
+// tile stride TS (48 / 64) -- none of it changes between the calls of a context.  LDS addresses are relative to the start of the
+// kernel's dynamic LDS, whose layout (fastWaveLds) is fixed by the geometry.  Whole dwords are what the kernel uses as they come;
+// every packed field costs the wave one scalar instruction.
+struct FastCell {          // 64 bytes, sixteen dwords
+  uint64_t img;            // byte offset of the first staged dword (row iniY, column iniX & ~3) from frame 0's image: inside the
+                           // caller's image (level 0) or inside the pyramid buffer (LevelGeom::imgOff folded in)
+  uint32_t frameStride;    // bytes between the level's frames in the pyramid buffer (below 2^32, buildFastCells checks); 0 = level 0: the launch's own base / stride
   uint32_t stride;         // row stride of the level image in bytes
-  uint32_t nw_ch;          // staged dwords per row (<= 16) | rows (<= 64) << 16; rows == 0: the cell detects nothing (cpp:1088,1101)
-  uint32_t iw_ih;          // detection area = cell image minus the 3-px FAST border: width | height << 16
-  uint32_t xoff_level;     // iniX & 3 | pyramid level << 16
-  uint32_t ox_oy;          // candidate (x, y) = (tile column + ox, tile row + oy), relative to minBorder: (uint16)ox | oy << 16
-  uint32_t segCap;         // entries of the segment
+  uint64_t cand;           // byte offset of the cell's candidate segment of frame 0: 4 (LevelGeom::candOff + local cell * segCap)
+  uint32_t candCap;        // bytes between the level's frames in the candidate area: 4 LevelGeom::candCap
+  uint32_t oxy;            // candidate = (tile column | tile row << 12 | score << 24) + oxy: ox + (oy << 12) mod 2^32, relative to minBorder
+  uint32_t dPos;           // sweep: a lane's step to its next quad, quad columns << 16 | LDS bytes
+  uint32_t wrapK;          // ... and what a column at or beyond the row's end adds to get into the next tile row
+  uint32_t selC0, selR0;   // v_perm_b32 selectors of the byte phase sh: centre / top / bottom pixels (0, 1); right compass pixels (0, 1)
+  uint32_t lastThr;        // positions at or above: the row's last quad, (nqc - 1) << 16
+  uint32_t aLast_kN;       // LDS address of the sweep's last item | (strength map - tile - xoff) << 16
+  uint32_t quad;           // ceil(2^20 / nqc) | nqc << 21 | (nvLast > 1, > 2, > 3: one bit each) << 25 | (right compass pair one dword
+                           // further: sh >= 2) << 28 | (sh + 1) << 29; nqc = quads per row (<= 15), nvLast = the last one's pixels inside
+  uint32_t counts;         // full steps of 64 items (<= 13) | (64 - items of the last step) << 4 | segCap (< 2048) << 10 | rows ch
+                           // (<= 64) << 21 | xoff << 28; ch == 0: the cell detects nothing (cpp:1088,1101), the whole record is zero
 };
-static_assert(sizeof(FastCell) == 32, "FastCell is loaded with one s_load_dwordx8");
+static_assert(sizeof(FastCell) == 64, "FastCell is loaded with one s_load_dwordx16");
+// k_fast_wave's dynamic LDS for a geometry: 16 bytes | tile[tileBytes] | strength map[smapBytes] | survivor stack | corner list
+#define ORBX_FW_RING 192   // survivor stack, entries (u16 LDS addresses)
+#define ORBX_FW_CORN 256   // corner list, entries
+struct FastWaveLds {
+  int32_t tileBytes, smapBytes, total;
+};
+static inline FastWaveLds fastWaveLds(const Geom& g, int ts) {
+  int ch = 7;  // tallest cell image of this geometry (cell + 6 px overlap, cpp:1094-1103)
+  for (int l = 0; l < g.nlevels; l++) ch = std::max(ch, std::min(g.L[l].hCell + 6, ORBX_CELL_MAX));
+  FastWaveLds r;
+  r.tileBytes = ch * ts + 16;  // (+ 16: the quick reject's dword reads reach a few bytes beyond the last tile row)
+  r.smapBytes = (ch - 6 + 2) * ts;
+  r.total = 16 + r.tileBytes + r.smapBytes + ORBX_FW_RING * 2 + ORBX_FW_CORN * 2;
+  return r;
+}
 
 // candidate entry written by the FAST kernel: x | y<<12 | score<<24, x/y relative to minBorder
 #if defined(__HIPCC__)

@@ -744,7 +744,9 @@ __global__ __launch_bounds__(FAST_T) void k_fast(const uint8_t* __restrict__ img
 // per vector instruction (r01 counters) -- and its 147,712 workgroups per 256 frames arrive at the dispatcher's limit
 // (~400 workgroups per microsecond chip-wide), which is why nothing done inside that kernel ever moved its 0.34 ms.
 // Here a wave owns the cell:
-//   * prologue = one s_load_dwordx8 of the cell record the host precomputed (FastCell);
+//   * prologue = one s_load_dwordx16 of the cell record the host precomputed (FastCell) and no load behind it: round 14 moved what
+//     a wave derived from its cell, its level and the tile stride into the record (the kernel executed as many scalar as vector
+//     instructions, 364 and 374 per cell, and a third of the scalar ones rebuilt per wave what is constant per geometry);
 //   * the cell image (<= 64 rows x 16 dwords) is staged lane = tile row, three 16-byte loads per lane in flight;
 //   * the quick reject works on quads of four horizontally adjacent pixels per lane (dword LDS reads, packed 16-bit
 //     arithmetic); its survivors go onto a stack in LDS (ballot + mbcnt compaction, no atomics) and are evaluated 64 at a
@@ -757,10 +759,10 @@ __global__ __launch_bounds__(FAST_T) void k_fast(const uint8_t* __restrict__ img
 // Same arithmetic and the same outputs (a cell's survivors in another order, which the selection stage does not see).
 // Preconditions (launch_fast): 4-byte aligned level-0 rows, every cell image <= 61 x 64 pixels; otherwise k_fast runs.
 // -------------------------------------------------------------------------------------------------
-#define FW_RING 192   // survivor stack, entries (u16 LDS addresses): fewer than 64 waiting + at most 128 new ones per half step
+#define FW_RING ORBX_FW_RING  // survivor stack, entries (u16 LDS addresses): fewer than 64 waiting + at most 128 new ones per half step
                       // (LDS is granted in pieces of 1280 bytes on gfx950: at 640x480 the kernel's 6208 bytes are five of them, 25
                       // waves per CU; with a stack of 320 entries it took six and ran 21)
-#define FW_CORN 256   // corner list, entries
+#define FW_CORN ORBX_FW_CORN  // corner list, entries
 #define FW_CPW 1      // consecutive cells per wave (measured per 256 frames: 1: 0.275 ms, 2: 0.288, 4: 0.316, 8: 0.361: the tail grows)
 #define FW_XK 16      // groups of FW_CPW cells per run of the XCD-aware order (8 .. 64 measured equal)
 
@@ -779,19 +781,16 @@ __device__ __forceinline__ const fw_lds_u8* fwLds8(const uint32_t a) { return re
 __device__ __forceinline__ const fw_lds_u16* fwLds16(const uint32_t a) { return reinterpret_cast<const fw_lds_u16*>((size_t)a); }
 __device__ __forceinline__ const fw_lds_u32* fwLds32(const uint32_t a) { return reinterpret_cast<const fw_lds_u32*>((size_t)a); }
 // store by the lanes of a SCALAR mask (a ballot, cut down by scalar masks): exec = m around one DS write -- no vector
-// instruction selects an address or rebuilds the lane's own bit (all 64 lanes are active where these are used)
+// instruction selects an address or rebuilds the lane's own bit.  ALL 64 LANES ARE ACTIVE where these are used (wave-uniform
+// control flow of a 64-thread workgroup), so exec is restored with the constant: two scalar instructions per store, not three
 __device__ __forceinline__ void fwStoreB16(const uint32_t addr, const uint32_t val, const unsigned long long m) {
-  unsigned long long saved;
-  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b16 %2, %3\n\ts_mov_b64 exec, %0"
-               : "=&s"(saved)
-               : "s"(m), "v"(addr), "v"(val)
-               : "memory");
+  asm volatile("s_mov_b64 exec, %0\n\tds_write_b16 %1, %2\n\ts_mov_b64 exec, -1" : : "s"(m), "v"(addr), "v"(val) : "memory");
 }
+template <int OFF>  // (the byte at the immediate offset OFF from addr)
 __device__ __forceinline__ void fwStoreB8(const uint32_t addr, const uint32_t val, const unsigned long long m) {
-  unsigned long long saved;
-  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b8 %2, %3\n\ts_mov_b64 exec, %0"
-               : "=&s"(saved)
-               : "s"(m), "v"(addr), "v"(val)
+  asm volatile("s_mov_b64 exec, %0\n\tds_write_b8 %1, %2 offset:%3\n\ts_mov_b64 exec, -1"
+               :
+               : "s"(m), "v"(addr), "v"(val), "n"(OFF)
                : "memory");
 }
 // ballots of "half > threshold" of a packed pair of signed 16-bit values against a scalar: one compare each.  The low half against
@@ -858,7 +857,6 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   const uint32_t ldsBase = (uint32_t)(size_t)(fw_lds_u8*)fwLds;
   const uint32_t tileAddr = ldsBase + 16u, smapAddr = tileAddr + (uint32_t)tileBytes;
   const uint32_t ringAddr = smapAddr + (uint32_t)smapBytes, cornAddr = ringAddr + 2u * FW_RING;
-  const uint32_t ringLane = ringAddr + 2u * (uint32_t)lane;
   // XCD-aware group order.  Workgroups go round-robin to the 8 XCDs (the grid's x size is a multiple of 8 * FW_XK), so the
   // workgroups with equal (blockIdx.x & 7) share an L2.  Each XCD takes every eighth RUN of FW_XK consecutive groups (16
   // cells, about one cell row of the lowest level): horizontally adjacent cells, which overlap by 6 px and share cache lines,
@@ -873,19 +871,30 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
   // (a frame's groups from the LAST one down: the cells of the small top levels hold about twice the corners of a level-0 cell, and
   // the workgroups dispatched last are the launch's tail -- with the light level-0 cells there, 0.202 - 0.203 against 0.206 - 0.207 ms
   // alone per 256 frames, round 6)
+  const uint32_t fu = (uint32_t)f;  // (never negative: the 64-bit products below are unsigned)
   const int cid0 = (nGroups - 1 - grp) * FW_CPW, cid1 = min(cid0 + FW_CPW, g.nCellsTotal);
   for (int cid = cid0; cid < cid1; cid++) {
-  const FastCell c = cells[cid];  // wave-uniform: one s_load_dwordx8
-  int* const myCount = cellCount + (long long)f * g.nCellsTotal + cid;
-  const int ch = (int)(c.nw_ch >> 16);
+  // wave-uniform: one s_load_dwordx16, and no scalar load behind it -- everything below is arithmetic on the record and on
+  // kernel arguments (round 14; before, LevelGeom was fetched behind the record and ~130 scalar instructions rebuilt per wave
+  // what the host knows per geometry)
+  // (written out: left to itself the compiler fetched the record in four pieces, each where it was first used and waited for there)
+  FastCell c;
+  {
+    typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    u32x16 r;
+    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(cells + cid) : "memory");
+    c = __builtin_bit_cast(FastCell, r);
+  }
+  // (where it is stored through, so that its address arithmetic is not part of every cell's prologue)
+  auto myCount = [&]() { return cellCount + (long long)((uint64_t)fu * (uint32_t)g.nCellsTotal + (uint32_t)cid); };
+  const int ch = (int)((c.counts >> 21) & 0x7fu);
   if (ch == 0) {  // every cell writes its counter (also 0), so the counters need no clearing between batches
-    if (lane == 0) *myCount = 0;
+    if (lane == 0) *myCount() = 0;
     continue;
   }
-  const int level = (int)(c.xoff_level >> 16);
-  const LevelGeom& L = g.L[level];
-  const uint8_t* const base =
-      (level == 0 ? img0 + (long long)f * img0FrameStride : pyr + L.imgOff + (long long)f * L.frameStride) + c.imgOff;
+  const bool level0 = c.frameStride == 0u;
+  const uint8_t* const base = (level0 ? img0 : pyr) + (long long)fu * (level0 ? img0FrameStride : (long long)c.frameStride) +
+                              (long long)c.img;
   // ---- stage the cell image: LANE = TILE ROW (a cell image has at most 64 rows), the row's TS bytes as TS / 16 16-byte loads
   //      (4-byte aligned global_load_dwordx4) and as many ds_write_b128 -- 3 + 3 instructions per cell instead of 9 + 9 with
   //      lane = (row mod 5, dword) (round 5: the CU's vector-memory path charges per instruction and lane, k_describe_patch).
@@ -905,48 +914,59 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
       for (int j = 0; j < NQ; j++) dst[j] = make_uint4(q[j].x, q[j].y, q[j].z, q[j].w);
     }
   }
-  const int iw = (int)(c.iw_ih & 0xffffu), ih = (int)(c.iw_ih >> 16), xoff = (int)(c.xoff_level & 0xffffu);
-  const int ox = (int)(int16_t)(c.ox_oy & 0xffffu), oy = (int)(c.ox_oy >> 16);
-  {  // strength map rows 0 .. ih + 1
+  {  // strength map rows 0 .. ih + 1 (ih = ch - 6)
     uint4* const s128 = reinterpret_cast<uint4*>(smap);
-    for (int i = lane; i < (ih + 2) * (TS / 16); i += 64) s128[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = lane; i < (ch - 4) * (TS / 16); i += 64) s128[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   __builtin_amdgcn_wave_barrier();  // (LDS operations of one wave execute in order; this only pins the compiler's order)
 
   constexpr int RS = TS;
   // a pixel's tile offset is o = (py + 3) * TS + xoff + px + 3; it is carried as e = tileAddr + o - (3 * TS + 3), the LDS address
-  // of the top-left byte of its 7 x 7 block; its strength-map byte is at smap + (py + 1) * TS + px + 1 = LDS address e + kS, the
+  // of the top-left byte of its 7 x 7 block; its strength-map byte is at smap + (py + 1) * TS + px + 1 = LDS address e + kN + TS + 1, the
   // 3 x 3 block around that at e + kN + {0, 1, 2} + {0, TS, 2 TS}
-  const uint32_t kN = smapAddr - tileAddr - (uint32_t)xoff, kS = kN + (uint32_t)(TS + 1);
-  const uint32_t eIdle = tileAddr + (uint32_t)xoff;  // the first pixel: what idle lanes evaluate
+  // (kN as the host has it: smapAddr - tileAddr - xoff; the strength-map byte itself is the immediate offset TS + 1 from e + kN)
+  const uint32_t kN = c.aLast_kN >> 16;
+  const uint32_t eIdle = tileAddr + ((c.counts >> 28) & 3u);  // tileAddr + xoff, the first pixel: what idle lanes evaluate
   // The quick reject works on QUADS of four horizontally adjacent pixels per lane: the quad's rows come from LDS as dwords
   // (8 reads per 4 pixels instead of 20 byte reads) and the test runs on packed 16-bit pairs.  Item = (quad column, row);
-  // idx += 64  <=>  (qc, qy) += (dqc, dqy) with one wrap at most.
-  const int nqc = (iw + 3) >> 2, nItems = nqc * ih;
-  const uint32_t inv = c_inv20.v[nqc];  // nqc <= 15
+  // idx += 64  <=>  (qc, qy) += (dqc, dqy) with one wrap at most.  nqc = quad columns of a row (<= 15), nItems = nqc * ih >= 1:
+  // nFull steps of 64 items and a last one of 64 - tailShift (1 .. 64).
+  const int nqc = (int)((c.quad >> 21) & 15u);
+  const int nFull = (int)(c.counts & 15u);
+  const uint32_t tailShift = (c.counts >> 4) & 63u;
+  const uint32_t inv = c.quad & 0x1fffffu;  // ceil(2^20 / nqc)
   const int qy0 = (int)(((uint32_t)lane * inv) >> 20), qc0 = lane - qy0 * nqc;
-  const int dqy = (int)((64u * inv) >> 20), dqc = 64 - dqy * nqc;  // dqc = 64 mod nqc < nqc
-  const int sh = (xoff + 3) & 3;  // byte phase of a quad's first pixel inside its dword (wave-uniform)
+  // sh = (xoff + 3) & 3: byte phase of a quad's first pixel inside its dword (wave-uniform)
+  const uint32_t sh1 = c.quad >> 29;  // sh + 1
   // a lane's position: quad column << 16 | LDS address a of the dword in front of the quad's first dword, three tile rows up (the
   // reads below are a[1], a[2] (top), a[3 TS / 4 .. + 2] (centre row) and a[6 TS / 4 + 1, + 2] (bottom); the quad's first pixel is
   // at a + 3 TS + 4 + sh).  Next item: += dPos; a column at or beyond nqc wraps into the next row: += wrapK -- for a column that
   // has not passed the row's end that sum underflows into a huge value, so the unsigned minimum of the two keeps the right one.
-  const uint32_t pos0 = ((uint32_t)qc0 << 16) | (tileAddr + (uint32_t)(qy0 * TS + xoff + 3 - sh + 4 * qc0 - 4));
-  const uint32_t dPos = ((uint32_t)dqc << 16) | (uint32_t)(dqy * TS + 4 * dqc);
-  const uint32_t wrapK = (uint32_t)(TS - 4 * nqc) - ((uint32_t)nqc << 16);
-  const uint32_t lastThr = (uint32_t)(nqc - 1) << 16;          // positions at or above: the row's last quad
-  const int nvLast = iw - 4 * (nqc - 1);                        // pixels of a row's last quad that lie inside the row (1 .. 4)
-  const uint32_t aLast = tileAddr + (uint32_t)((ih - 1) * TS + xoff + 3 - sh + 4 * (nqc - 1) - 4);  // the last item's address
+  // (the scalar part: tileAddr + xoff + 3 - sh - 4 = eIdle - (sh + 1); the sum stays below 2^16, so + is |)
+  const uint32_t pos0 = ((uint32_t)qc0 << 16) + ((eIdle - sh1) + (uint32_t)(qy0 * TS + 4 * qc0));
+  const uint32_t dPos = c.dPos;      // dqc << 16 | dqy * TS + 4 * dqc, with dqy = 64 / nqc and dqc = 64 mod nqc
+  const uint32_t wrapK = c.wrapK;    // (TS - 4 * nqc) - (nqc << 16)
+  const uint32_t lastThr = c.lastThr;                           // positions at or above: the row's last quad
+  // nvLast = pixels of a row's last quad that lie inside the row (1 .. 4), as bit 24 + j of the record's dword for j = 1 .. 3:
+  // pixel j of that quad is inside (j < nvLast).  keepJ[j] = that bit on all 64 lanes: one s_bfe_i64 (width 1) each
+  const unsigned long long quad64 = (unsigned long long)c.quad;
+  unsigned long long keepJ[4];
+  keepJ[0] = ~0ull;
+  asm("s_bfe_i64 %0, %1, 0x10019" : "=s"(keepJ[1]) : "s"(quad64) : "scc");
+  asm("s_bfe_i64 %0, %1, 0x1001a" : "=s"(keepJ[2]) : "s"(quad64) : "scc");
+  asm("s_bfe_i64 %0, %1, 0x1001b" : "=s"(keepJ[3]) : "s"(quad64) : "scc");
+  const bool endPartial = (c.quad & (1u << 27)) == 0u;         // nvLast < 4
+  const uint32_t aLast = ldsBase + (c.aLast_kN & 0xffffu);      // the last item's address
   // v_perm_b32 selectors (SGPRs): two tap bytes -> the halves of a u16 pair (0x0c = constant 0).  Centre / top / bottom bytes
   // sh + {0..3} of the dword pair at the quad; left compass bytes sh + 1 + {0..3} of the pair one dword to the left; right
   // compass bytes sh + 3 + {0..3} of the pair at the quad (sh <= 1) or sh - 1 + {0..3} of the pair one dword to the right
-  const uint32_t selC0 = 0x0c000c00u + (uint32_t)sh * 0x00010001u + 0x00010000u, selC1 = selC0 + 0x00020002u;
+  const uint32_t selC0 = c.selC0, selC1 = selC0 + 0x00020002u;
   const uint32_t selL0 = selC0 + 0x00010001u, selL1 = selL0 + 0x00020002u;
-  const bool rNear = sh <= 1;
-  const uint32_t rOff4 = rNear ? 0u : 4u;
-  const uint32_t selR0 = 0x0c000c00u + (uint32_t)(rNear ? sh + 3 : sh - 1) * 0x00010001u + 0x00010000u, selR1 = selR0 + 0x00020002u;
-  uint32_t* const dstc = cand + L.candOff + (long long)f * L.candCap + c.segOff;
-  const int segCap = (int)c.segCap;
+  const uint32_t rOff4 = (c.quad >> 26) & 4u;  // (bit 28: sh >= 2)
+  const uint32_t selR0 = c.selR0, selR1 = selR0 + 0x00020002u;
+  uint32_t* const dstc =
+      reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cand) + (long long)(c.cand + (uint64_t)fu * c.candCap));  // (bytes)
+  const int segCap = (int)((c.counts >> 10) & 0x7ffu);
   int nOut = 0;
   for (int pass = 0; pass < 2; pass++) {
     const int th = pass == 0 ? g.iniTh : g.minTh;
@@ -954,7 +974,10 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
     // th << 16 | 0xffff -- the low half, whatever it holds, cannot lift an equal high half above that
     const uint32_t thLo = (uint32_t)th, thHi = ((uint32_t)th << 16) | 0xffffu;
     const int thB = th + (int)FAST_PK_BIAS;
-    int nList = 0, nCorn = 0;  // wave-uniform (SGPRs)
+    // the survivor stack and the corner list are kept as the LDS address of their next free entry (wave-uniform, SGPRs): an append's
+    // address is one v_lshl_add_u32 from it, and "64 waiting" is one compare
+    uint32_t ringTop = ringAddr, cornTop = cornAddr;
+    const uint32_t ringFull = ringAddr + 2u * 64u, cornEnd = cornAddr + 2u * FW_CORN;
     // A cell without a survivor at iniThFAST is swept again at minThFAST (cpp:1117-1123) -- on real images that is every second
     // cell, and in a flat region the second sweep lists nothing either.  While the first sweep has not listed a pixel yet (`flat`,
     // wave-uniform), it also keeps the maximum of its test value d = max(max side - v, v - min side): a pixel passes the quick
@@ -965,36 +988,37 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
     short2v looseMax = {-0x8000, -0x8000};
     // evaluates the `cnt` newest entries of the survivor stack (64, or what is left at the end): exact strength; corners
     // (s > th) enter the strength map and the corner list
-    auto flush = [&](const int cnt) {
+    auto flush = [&](auto whole) {  // whole: the 64 newest entries; otherwise every entry (fewer than 64)
+      constexpr bool WHOLE = decltype(whole)::value;
       __builtin_amdgcn_wave_barrier();
-      const int keepN = nList - cnt;
-      uint32_t e = (uint32_t)fwLds16(ringLane)[keepN];
+      const uint32_t newTop = WHOLE ? ringTop - 2u * 64u : ringAddr;
+      uint32_t e = (uint32_t)fwLds16(newTop + 2u * (uint32_t)lane)[0];
       unsigned long long act = ~0ull;
-      if (cnt < 64) {  // (uniform)
-        asm volatile("" ::: "memory");
+      if (!WHOLE) {
+        const int cnt = (int)((ringTop - ringAddr) >> 1);
         act = (1ull << cnt) - 1ull;
         e = lane < cnt ? e : eIdle;
       }
       const uint32_t sv = fwStrength<TS>(e);  // B + strength
-      const unsigned long long mc = __ballot((int)sv > thB) & act;
+      unsigned long long mc = __ballot((int)sv > thB);
+      if (!WHOLE) mc &= act;
       if (mc != 0ull) {
-        fwStoreB8(e + kS, sv, mc);  // (the low byte: B's is 0 and a corner's strength is 1 .. 255)
-        const int nc = (int)__popcll(mc);
-        if (nCorn + nc <= FW_CORN) fwStoreB16((cornAddr + 2u * (uint32_t)nCorn) + 2u * (uint32_t)fwMbcnt(mc), e, mc);
-        nCorn += nc;
+        fwStoreB8<TS + 1>(e + kN, sv, mc);  // (the low byte: B's is 0 and a corner's strength is 1 .. 255)
+        const uint32_t top = cornTop + 2u * (uint32_t)__popcll(mc);
+        if (top <= cornEnd) fwStoreB16(cornTop + 2u * (uint32_t)fwMbcnt(mc), e, mc);
+        cornTop = top;  // (beyond cornEnd: more corners than the list holds; the strength map is scanned instead)
       }
-      nList = keepN;
+      ringTop = newTop;
     };
     // ---- quick reject on the 4 compass pixels (an arc of 9 holds two adjacent ones), survivors onto the stack ----
     {
       uint32_t pos = pos0;
-      for (int idx0 = 0; idx0 < nItems; idx0 += 64) {
+      // one step of 64 items.  The sweep's LAST step is peeled off (round 14): only there can lanes be idle -- they read the last
+      // item again and are taken out of the ballots by `live` -- so the full steps carry neither the clamp nor the mask
+      auto step = [&](auto lastStep) {
+        constexpr bool LAST = decltype(lastStep)::value;
         uint32_t a = pos & 0xffffu;
-        const bool tail = idx0 + 64 > nItems;  // (uniform) the step with idle lanes: they read the last item again, masked below
-        if (tail) {
-          asm volatile("" ::: "memory");
-          a = min(a, aLast);
-        }
+        if (LAST) a = min(a, aLast);
         const fw_lds_u32* const pa = fwLds32(a);
         const uint32_t t0 = pa[1], t1 = pa[2];
         const uint32_t cM = pa[3 * (TS / 4)], c0 = pa[3 * (TS / 4) + 1], c1 = pa[3 * (TS / 4) + 2];
@@ -1027,29 +1051,33 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
         }
         if ((fwGtLo(dm, thLo) | fwGtHi(dm, thHi)) != 0ull) {  // (wave-uniform) a step without any survivor appends nothing
           flat = false;
-          // what the ballots must not count: pixels beyond the row's end (the last quad of a row holds nvLast pixels of it) and the
-          // idle lanes of the last step
+          // what the ballots must not count: pixels beyond the row's end (the last quad of a row holds nvLast pixels of it: pixel j
+          // of every quad is kept by keepJ[j], and of every quad but a row's last by keepEnd) and the idle lanes of the last step
           unsigned long long keepEnd = ~0ull;
-          if (nvLast < 4) keepEnd = ~__ballot(pos >= lastThr);
-          const unsigned long long live = tail ? (1ull << (nItems - idx0)) - 1ull : ~0ull;
-          const uint32_t q0 = a + (uint32_t)(sh + 1);  // the quad's first pixel as a stack entry
+          if (endPartial) keepEnd = ~__ballot(pos >= lastThr);
+          const uint32_t q0 = a + sh1;  // the quad's first pixel as a stack entry
 #pragma unroll
           for (int j = 0; j < 4; j++) {
             const uint32_t dj = __builtin_bit_cast(uint32_t, d[j >> 1]);
-            unsigned long long m = ((j & 1) ? fwGtHi(dj, thHi) : fwGtLo(dj, thLo)) & live;
-            if (j >= nvLast) m &= keepEnd;
+            unsigned long long m = (j & 1) ? fwGtHi(dj, thHi) : fwGtLo(dj, thLo);
+            if (LAST) m &= ~0ull >> tailShift;
+            if (j > 0) m &= keepEnd | keepJ[j];
             if (m != 0ull) {  // (wave-uniform)
-              fwStoreB16((ringAddr + 2u * (uint32_t)nList) + 2u * (uint32_t)fwMbcnt(m), q0 + (uint32_t)j, m);
-              nList += (int)__popcll(m);
+              fwStoreB16(ringTop + 2u * (uint32_t)fwMbcnt(m), q0 + (uint32_t)j, m);
+              ringTop += 2u * (uint32_t)__popcll(m);
             }
             if (j & 1)
-              while (nList >= 64) flush(64);
+              while (ringTop >= ringFull) flush(std::true_type{});
           }
         }
-        pos += dPos;
-        pos = min(pos, pos + wrapK);
-      }
-      if (nList > 0) flush(nList);
+        if (!LAST) {
+          pos += dPos;
+          pos = min(pos, pos + wrapK);
+        }
+      };
+      for (int i = nFull; i > 0; i--) step(std::false_type{});
+      step(std::true_type{});
+      if (ringTop != ringAddr) flush(std::false_type{});
     }
     __builtin_amdgcn_wave_barrier();
     // ---- in-cell NMS on the strength map; survivors are the cell's keypoints ----
@@ -1064,18 +1092,28 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
       const unsigned long long mk = __ballot(keep);
       if (keep) {
         const int slot = nOut + fwMbcnt(mk);
-        // tile row = y - oy, tile column = x - ox; o / TS by multiply-shift (exact for o < 2^12)
+        // tile row = y - oy, tile column = x - ox; o / TS by multiply-shift (exact for o < 2^12).  x and y are below 4096, so
+        // packCand(column + ox, row + oy, score) is the sum of packCand(column, row, score) and the record's ox + (oy << 12)
         const int o = (int)(e - tileAddr) + 3 * TS + 3;
         const int row = TS == 64 ? (o >> 6) : (int)(((uint32_t)o * 43691u) >> 21);
         static_assert(TS == 64 || TS == 48, "row split of a tile offset");
-        if (slot < segCap) dstc[slot] = packCand(o - row * TS + ox, row + oy, sv - 1);
+        if (slot < segCap) dstc[slot] = packCand(o - row * TS, row, sv - 1) + c.oxy;
       }
       nOut += (int)__popcll(mk);
     };
-    if (nCorn <= FW_CORN) {
+    if (cornTop <= cornEnd) {
+      const int nCorn = (int)((cornTop - cornAddr) >> 1);
       for (int e0 = 0; e0 < nCorn; e0 += 64) nms((uint32_t)fwLds16(cornAddr)[min(e0 + lane, FW_CORN - 1)], e0 + lane < nCorn);
     } else {  // more corners than the list holds (noise at a low threshold): scan the strength map instead
-      const uint32_t invw = c_inv20.v[iw];
+      // (the empty asm keeps this path's arithmetic inside it: as plain arithmetic on the record it was hoisted into every cell's
+      // prologue, the division included)
+      uint32_t quadHere = c.quad;
+      int chHere = ch;
+      asm volatile("" : "+s"(quadHere), "+s"(chHere));
+      const int iw = 1 + (int)__popc((quadHere >> 25) & 7u) + 4 * (int)(((quadHere >> 21) & 15u) - 1u);  // nvLast + 4 (nqc - 1)
+      const int ih = chHere - 6;                                                                          // the detection area
+      // c_inv20.v[iw], divided out here: a table read would be a scalar load behind the record, and this path is rare
+      const uint32_t invw = ((1u << 20) + (uint32_t)iw - 1u) / (uint32_t)iw;
       const int py0 = (int)(((uint32_t)lane * invw) >> 20), px0 = lane - py0 * iw;
       const int dpy = (int)((64u * invw) >> 20), dpx = 64 - dpy * iw;
       int px = px0;
@@ -1083,7 +1121,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
       const int npix = iw * ih;
       for (int idx0 = 0; idx0 < npix; idx0 += 64) {
         const bool live = idx0 + lane < npix;
-        const int sv = live ? (int)fwLds8(e + kS)[0] : 0;
+        const int sv = live ? (int)fwLds8(e + kN)[TS + 1] : 0;
         const unsigned long long any = __ballot(sv > 0);
         if (any) nms(e, sv > 0);
         px += dpx;
@@ -1098,7 +1136,7 @@ __global__ __launch_bounds__(64) void k_fast_wave(const uint8_t* __restrict__ im
       if (flat && (fwGtLo(lm, (uint32_t)g.minTh) | fwGtHi(lm, ((uint32_t)g.minTh << 16) | 0xffffu)) == 0ull) break;
     }
   }
-  if (lane == 0) *myCount = min(nOut, segCap);  // nOut <= segCap: NMS survivors are never 8-neighbours
+  if (lane == 0) *myCount() = min(nOut, segCap);  // nOut <= segCap: NMS survivors are never 8-neighbours
   __builtin_amdgcn_wave_barrier();  // the next cell's staging stores come after this cell's last LDS reads
   }  // cells of this wave
 }
@@ -3504,15 +3542,13 @@ hipError_t launch_fast(hipStream_t st, int nFrames, const uint8_t* img0, long lo
     // one wave per workgroup, FW_CPW cells per wave; x size padded to whole rounds of 8 runs (XCD-aware order)
     const int groups = ((g.nCellsTotal + FW_CPW - 1) / FW_CPW + 8 * FW_XK - 1) / (8 * FW_XK) * (8 * FW_XK);
     const int ts = waveOk == 2 ? 48 : 64;  // tile / strength-map row stride: 48 when every cell image is <= 12 dwords wide
-    // (+ 16: the quick reject's dword reads reach a few bytes beyond the last tile row)
-    const int tileBytes = ch * ts + 16, smapBytes = (ch - 6 + 2) * ts;
-    const size_t lds = (size_t)(16 + tileBytes + smapBytes + FW_RING * 2 + FW_CORN * 2);  // k_fast_wave's layout
+    const FastWaveLds lds = fastWaveLds(g, ts);  // (the cell records hold addresses inside this layout: buildFastCells)
     if (ts == 48)
-      hipLaunchKernelGGL(k_fast_wave<48>, dim3(groups, nFrames, 1), dim3(64, 1, 1), lds, st, img0, img0FrameStride, pyr, g, cells,
-                         cand, cellCount, tileBytes, smapBytes);
+      hipLaunchKernelGGL(k_fast_wave<48>, dim3(groups, nFrames, 1), dim3(64, 1, 1), (size_t)lds.total, st, img0, img0FrameStride, pyr, g,
+                         cells, cand, cellCount, lds.tileBytes, lds.smapBytes);
     else
-      hipLaunchKernelGGL(k_fast_wave<64>, dim3(groups, nFrames, 1), dim3(64, 1, 1), lds, st, img0, img0FrameStride, pyr, g, cells,
-                         cand, cellCount, tileBytes, smapBytes);
+      hipLaunchKernelGGL(k_fast_wave<64>, dim3(groups, nFrames, 1), dim3(64, 1, 1), (size_t)lds.total, st, img0, img0FrameStride, pyr, g,
+                         cells, cand, cellCount, lds.tileBytes, lds.smapBytes);
     return hipGetLastError();
   }
   dim3 block(FAST_T, 1, 1), grid(g.nCellsTotal, nFrames, 1);
