@@ -1261,7 +1261,8 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 #define BL_STRIDE 48   // the blurred bytes are stored column-major: byte (column c, row r) at c * 48 + r, three 16-row tiles
 #define BL_COLS 48     // 37 blurred columns padded to three 16-column tiles
 #define PW_RAW_WORDS (PW_ROWS_PAD * PW_WORDS)
-#define PW_WAVE_WORDS (PW_RAW_WORDS + 4)  // the blurred bytes reuse the raw window's space; + 2 moment sums
+#define PW_WAVE_WORDS (PW_RAW_WORDS + 4)  // the blurred bytes reuse the raw window's space; + 4 words that held IC_Angle's moment sums
+                                          // until round 15 (kept: the slices' places and the LDS per workgroup stand)
 
 // IC_Angle disc as dot4 weights: row |v| of the 31x31 disc covers u = -umax[|v|] .. umax[|v|]; the row's 32 bytes
 // u = -15 .. 16 are 8 dwords j, and for each the weights are w1 = (1 per valid byte) and wu = (u + 15 per valid byte), so
@@ -1449,7 +1450,7 @@ __device__ __forceinline__ float fast_atan2_deg_sel(float y, float x) {
 // launches on k_sel_compact's list): wave-item j owns keypoints 2 j and 2 j + 1 of the frame's level-major list, each with its own
 // LDS slice and its own scalars (level, position, byte shift, geometry, image base -- the two may lie on different levels).  What is
 // per WAVE is then paid once per PAIR: the work-item map and the table loads, IC_Angle (lanes 0..30 = disc rows of keypoint A, lanes
-// 32..62 of keypoint B: the same 9 LDS reads, 8 v_alignbyte, 16 v_dot4, 2 atomics), fastAtan2 and cos / sin (lane = keypoint, the
+// 32..62 of keypoint B: the same 9 LDS reads, 8 v_alignbyte, 16 v_dot4, 8 DPP adds), fastAtan2 and cos / sin (lane = keypoint, the
 // per-lane forms; the three values per keypoint go to SGPRs by v_readlane), the pattern loads and the stores.  Staging, the blur and
 // the steered-BRIEF loop run one after the other, A then B, on the same registers.  Nothing is handed over between waves.
 template <int GV, bool STAGED = false, int KPW = 1>
@@ -1472,7 +1473,11 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
   // XCDs stay balanced.
   const int grp = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   // (the wave's index as a scalar: the keypoint record then comes through a scalar load, beside the count's)
-  const int i = (grp * WPG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * KPW;  // the wave's first keypoint
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int i = (grp * WPG + wv) * KPW;  // the wave's first keypoint
+  // the workgroup's LDS as bytes, and where this wave's first slice starts in it (a scalar)
+  uint8_t* const ldsB = reinterpret_cast<uint8_t*>(&ldsAll[0][0][0]);
+  const uint32_t wvBase = (uint32_t)wv * (uint32_t)(KPW * PW_WAVE_WORDS * 4);
   // (the keypoint record is fetched together with the frame's count, not behind it: count, record and window were three
   // dependent global loads and, by the cycle stamps of docs/history.md, 63 % of a wave's lifetime)
   SelKp k[KPW];
@@ -1525,10 +1530,9 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
   // a keypoint's slice (half h of the wave at lds + h * PW_WAVE_WORDS):
   //   raw   [48][13] dwords (rows 43..47: padding of the third row tile, never written)
   //   bl32  [48][12] dwords = blurred bytes, column-major, in the raw window's place (raw is dead by then)
-  //   msum  [2] moment sums of IC_Angle, behind them
+  //   four unused words behind them (IC_Angle's moment sums until round 15: they are reduced in registers now)
   static_assert(BL_COLS * (BL_STRIDE / 4) <= PW_RAW_WORDS, "blurred bytes must fit in the raw window");
   static_assert((PW_ROWS_PAD - 1) * PW_WORDS + 8 + 3 < PW_RAW_WORDS, "the padded row tiles stay inside the keypoint's own slice");
-  int* const msumL = reinterpret_cast<int*>(lds + hl * PW_WAVE_WORDS + PW_RAW_WORDS);  // the moment sums of this lane's half
   // a keypoint is wave-uniform: keep its fields in SGPRs so that the level geometry comes through scalar loads
   int level[KPW], kx[KPW], ky[KPW], s[KPW];
   const LevelGeom* Lg[KPW];
@@ -1547,7 +1551,6 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
   //      zero taps (blurred columns 37..39, the padding of the last group of four, are never sampled) and is left as it is.
   //      Pair form: both windows' loads are issued before either is stored -- six 16-byte loads in flight. ----
   {
-    if (rl == 0) { msumL[0] = 0; msumL[1] = 0; }
     typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
     const uint8_t* img[KPW];
     bool aligned[KPW], rowsInside[KPW];
@@ -1568,8 +1571,12 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
       q[0] = *reinterpret_cast<const u32x4_a4*>(p); q[1] = *reinterpret_cast<const u32x4_a4*>(p + 16);
       q[2] = *reinterpret_cast<const u32x4_a4*>(p + 32);
     };
+    // (slice B's row is one address register behind slice A's and the stores' immediate offsets: a ds_write2_b32 offset counts
+    // dwords in 8 bits, the compiler cannot reach slice B from A's register and made an address per store otherwise)
     auto rowStore = [&](const int h, const u32x4_a4* q) {
-      uint32_t* dst = lds + h * PW_WAVE_WORDS + lane * PW_WORDS;
+      uint32_t db = wvBase + (uint32_t)(lane * (PW_WORDS * 4)) + (uint32_t)(h * PW_WAVE_WORDS * 4);
+      if (h) asm("" : "+v"(db));
+      uint32_t* dst = reinterpret_cast<uint32_t*>(ldsB + db);
       dst[0] = q[0].x; dst[1] = q[0].y; dst[2] = q[0].z; dst[3] = q[0].w; dst[4] = q[1].x; dst[5] = q[1].y; dst[6] = q[1].z; dst[7] = q[1].w;
       dst[8] = q[2].x; dst[9] = q[2].y; dst[10] = q[2].z; dst[11] = q[2].w;
     };
@@ -1632,6 +1639,7 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
   // ---- IC_Angle (cpp:103-159) on the un-blurred window: pixel (u, v) is row 21+v, byte s+21+u.  Lane = disc row v (pair form:
   //      lanes 0..30 keypoint A, lanes 32..62 keypoint B, each half on its own slice and its own two sums); the row's bytes
   //      u = -15..16 are 8 dwords, each weighted with v_dot4_u32_u8 (tables d_ic) ----
+  int pm10 = 0, pm01 = 0;
   if (rl < 31) {
     const int v = rl - 15;
     const uint32_t w1[8] = {w1a.x, w1a.y, w1a.z, w1a.w, w1b.x, w1b.y, w1b.z, w1b.w};
@@ -1649,13 +1657,29 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
       sumI = __builtin_amdgcn_udot4(B, w1[j], sumI, false);
       sumU = __builtin_amdgcn_udot4(B, wu[j], sumU, false);
     }
-    atomicAdd(&msumL[0], (int)sumU - 15 * (int)sumI);  // m10 = sum u*I
-    atomicAdd(&msumL[1], v * (int)sumI);                // m01 = sum v*I
+    pm10 = (int)sumU - 15 * (int)sumI;  // this row's part of m10 = sum u*I
+    pm01 = v * (int)sumI;               // and of m01 = sum v*I
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  // (pair form: every lane of a half reads its half's sums; lanes 0 and 32 are the ones read back)
-  const int m10 = msumL[0], m01 = msumL[1];
+  // Round 15: the disc rows' parts are summed in registers -- over each row of 16 lanes by four DPP adds (integer sums: any
+  // order is exact; lanes 31 and 63, and lanes 31 .. 63 of the one-keypoint form, add zeros), the four row sums go to SGPRs, a
+  // half's sum is two of them.  Until then each half added into two LDS words with ds_add_u32: 31 lanes on one address, about 62
+  // of the kernel's 216 LDS-active cycles per keypoint, all of them counted as bank conflicts (docs/history.md).
+  auto rowSum = [](int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, true);   // quad_perm [2, 3, 0, 1]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);  // row_half_mirror
+    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);  // row_mirror
+    return x;
+  };
+  const int r10 = rowSum(pm10), r01 = rowSum(pm01);
+  const int m10A = __builtin_amdgcn_readlane(r10, 0) + __builtin_amdgcn_readlane(r10, 16);
+  const int m01A = __builtin_amdgcn_readlane(r01, 0) + __builtin_amdgcn_readlane(r01, 16);
+  int m10 = m10A, m01 = m01A;
+  if constexpr (KPW == 2) {
+    const int m10B = __builtin_amdgcn_readlane(r10, 32) + __builtin_amdgcn_readlane(r10, 48);
+    const int m01B = __builtin_amdgcn_readlane(r01, 32) + __builtin_amdgcn_readlane(r01, 48);
+    m10 = hl ? m10B : m10A; m01 = hl ? m01B : m01A;
+  }
   const float angleL = KPW == 2 ? fast_atan2_deg_sel((float)m01, (float)m10) : fast_atan2_deg((float)m01, (float)m10);
   // ---- 7x7 Gaussian on the matrix cores (the comment at BlurFrags has the arithmetic and the k order), one keypoint after the
   //      other on the same registers.
@@ -1766,22 +1790,36 @@ __global__ __launch_bounds__(64 * descWaves(KPW), 7) void k_describe_patch(const
     }
   }
   unsigned long long words[KPW][4];
+  // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + c) * 48 + 18 + r (column-major) in one go:
+  // v + 1.5 * 2^23 rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits.  The low
+  // 24 bits of ic (0x400000 + c) are what v_mad_u32_u24 multiplies by the stride, ir is its full-dword addend, and the constants
+  // are taken off, mod 2^32, by one add of a per-wave scalar that also holds the wave's slice base; keypoint B's slice is the
+  // read's immediate offset.  (Round 15: written as the instruction -- from the expression (ic & 0xffffff) * 48 + ir - OFF the
+  // compiler made v_mul_u32_u24, v_add_u32 of the slice base and v_add3_u32.)
+  constexpr float MAGIC = 12582912.f;
+  constexpr uint32_t OFF = (uint32_t)BL_STRIDE * 0x400000u + 0x4B400000u - (18u * BL_STRIDE + 18u);
+  static_assert(0x400000u + 18u < (1u << 24), "0x400000 + c, |c| <= 18, is the low 24 bits of ic");
+  static_assert((unsigned long long)(0x400000u + 18u) * BL_STRIDE + 0x4B400000u + 18u < (1ull << 32) &&
+                (0x400000u - 18u) * (uint32_t)BL_STRIDE + (0x4B400000u - 18u) - OFF == 0u &&
+                (0x400000u + 18u) * (uint32_t)BL_STRIDE + (0x4B400000u + 18u) - OFF == 36u * BL_STRIDE + 36u &&
+                36u * BL_STRIDE + 36u < BL_COLS * BL_STRIDE,
+                "the mad does not wrap; minus OFF it is the byte (18 + c) * 48 + 18 + r of the blurred patch");
+  auto briefAddr = [](const uint32_t ic, const uint32_t ir) {
+    uint32_t t;
+    asm("v_mad_u32_u24 %0, %1, %3, %2" : "=v"(t) : "v"(ic), "v"(ir), "n"(BL_STRIDE));
+    return t;
+  };
+  const uint32_t blBase = wvBase - OFF;
 #pragma unroll
   for (int h = 0; h < KPW; h++) {
-    const uint8_t* bl = reinterpret_cast<const uint8_t*>(lds + h * PW_WAVE_WORDS);
 #pragma unroll
     for (int wq = 0; wq < 4; wq++) {
       const float4 pt = pat[wq];
       const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
-      // cvRound of the rotated coordinates (cpp:184-188) and the byte address (18 + c) * 48 + 18 + r (column-major) in one go:
-      // v + 1.5 * 2^23 rounds to nearest-even at integer granularity and leaves 0x4B400000 + rint(v) in the float's bits; the low
-      // 24 bits (0x400000 + c) go through v_mad_u32_u24, the constants are taken off at the end
-      constexpr float MAGIC = 12582912.f;
-      constexpr uint32_t OFF = (uint32_t)BL_STRIDE * 0x400000u + 0x4B400000u - (18u * BL_STRIDE + 18u);
       const uint32_t ir0 = __float_as_uint((x0 * sn[h] + y0 * cs[h]) + MAGIC), ic0 = __float_as_uint((x0 * cs[h] - y0 * sn[h]) + MAGIC);
       const uint32_t ir1 = __float_as_uint((x1 * sn[h] + y1 * cs[h]) + MAGIC), ic1 = __float_as_uint((x1 * cs[h] - y1 * sn[h]) + MAGIC);
-      const int t0 = bl[(ic0 & 0xffffffu) * (uint32_t)BL_STRIDE + ir0 - OFF];
-      const int t1 = bl[(ic1 & 0xffffffu) * (uint32_t)BL_STRIDE + ir1 - OFF];
+      const int t0 = ldsB[(briefAddr(ic0, ir0) + blBase) + h * (PW_WAVE_WORDS * 4)];
+      const int t1 = ldsB[(briefAddr(ic1, ir1) + blBase) + h * (PW_WAVE_WORDS * 4)];
       words[h][wq] = __ballot(t0 < t1);
     }
   }
