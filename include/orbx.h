@@ -1484,6 +1484,111 @@ int orbx_map_update(orbx_ctx* ctx, int n_entries, int n_free, const orbx_keypoin
                     const uint8_t* map_mask, uint8_t* map_mask_out, int32_t* map_ref, int what, float* map_normals, float* map_dist,
                     uint8_t* map_desc32, int32_t* map_obs, orbx_map_result* res);
 
+/* ---- stereo: matching left and right ------------------------------------------------------------------------------------------
+ * Frame::ComputeStereoMatches (and, as an optional tail, Frame::UnprojectStereo) of ORB-SLAM2's stereo Frame constructor, for
+ * batches of rigs.  The reference ships no stereo: this is ORB-SLAM2's code, [from-knowledge], PARITY UNPINNED, as the sections
+ * above.  The device equals the CPU restatement tests/cpp/stereo_ref.cpp bit for bit, which shares csrc/orbx_stereo_math.inc
+ * with it and is itself tested against an independently written numpy statement and against ground truth.
+ *
+ * A rig p is a (left frame, right frame) pair of ONE extract batch: L = h_left[p] and R = h_right[p] are frame indices of the
+ * context's LAST EXTRACT CALL, whose pyramid is still resident (level 0: the caller's frames, read in place, so they must still
+ * be there; levels 1..: the context's own).  The keypoints are the raw mvKeys (stereo input is rectified), bf is mbf, b is mb,
+ * scale[] / inv_scale[] are the context's tables (orbx_get_tables), cols_l / rows_l the level sizes (orbx_level_size).  All
+ * arithmetic is f32 without contraction unless said otherwise.
+ *
+ * Rules:
+ *  1. Every u_right[i] = -1.0f, depth[i] = -1.0f, match_right[i] = -1, sad[i] = -1 (i < d_n[L]; rows beyond it are not touched).
+ *  2. Row bands.  Right keypoint iR: r = 2.0f * scale[oct_R], maxr = (int)ceilf(y_R + r), minr = (int)floorf(y_R - r) (f32
+ *     sums).  It is a candidate of row y for minr <= y <= maxr, clipped to [0, rows_0).
+ *  3. Limits.  minD = 0, maxD = bf / b (f32 division), thOrbDist = (100 + 50) / 2 = 75.
+ *  4. Left keypoint iL: row = (int)y_L (truncation); minU = x_L - maxD, maxU = x_L.  Skipped when maxU < 0.
+ *  5. Candidates are the right keypoints that pass all three tests: the band holds `row`; oct_L - 1 <= oct_R <= oct_L + 1;
+ *     minU <= x_R <= maxU (both ends inclusive).
+ *  6. Descriptor search.  d = popcount(desc_L ^ desc_R); best = the smallest d, among equal d the LOWEST iR (the design's
+ *     ascending row lists with a strict <).  bestDist starts at 100 (TH_HIGH), so d >= 100 never matches.  The search continues
+ *     only when best < 75.
+ *  7. Coordinates at the keypoint's level o = oct_L: su = roundf(x_L * inv_scale[o]), sv = roundf(y_L * inv_scale[o]),
+ *     su0 = roundf(x_R(best) * inv_scale[o]): f32 products, rounded half away from zero.
+ *  8. Window test.  With w = 5, L = 5: refused (`continue`) when su0 + L - w < 0 || su0 + L + w + 1 >= cols_o.  The test is the
+ *     design's as written; it is weaker than what it reads.  That is the design's quirk; see deviation 1.
+ *  9. SAD over the shifts.  For inc = -5 .. +5 in ascending order, SAD(inc) = the sum over the 11 x 11 window of
+ *     | (IL(sv+dy, su+dx) - IL(sv, su)) - (IR(sv+dy, su0+inc+dx) - IR(sv, su0+inc)) |, both sides read from level o of L and of
+ *     R.  Integer arithmetic (at most 121 * 510 = 61 710); it equals the design's convertTo(CV_32F), centre subtraction and
+ *     cv::norm(NORM_L1) exactly.  The best is the first inc with the smallest SAD (strict <).  Refused when it is -5 or +5.
+ * 10. Parabola.  d1, d2, d3 = SAD at best-1, best, best+1 as f32; delta = (d1 - d3) / (2.0f * ((d1 + d3) - 2.0f * d2)).
+ *     Refused when delta < -1 || delta > 1.
+ * 11. Disparity.  bestuR = scale[o] * ((su0 + (float)inc) + delta); disp = x_L - bestuR.  Kept when disp >= 0 && disp < maxD.
+ *     When disp <= 0: disp = 0.01f and bestuR = (float)((double)x_L - 0.01).  depth[iL] = bf / disp, u_right[iL] = bestuR,
+ *     match_right[iL] = best iR, sad[iL] = SAD(best).
+ * 12. Median filter.  With M kept matches and M > 0: median = the element of rank M / 2 (0-based) of the kept SADs in ascending
+ *     order; thDist = (1.5f * 1.4f) * (float)median; every kept match with (float)sad >= thDist goes back to -1 / -1.0f in all
+ *     four arrays.  A median of 0 therefore removes EVERY match: the design's quirk, kept.
+ * 13. Optional tail, Frame::UnprojectStereo, when d_points is given.  For depth[i] > 0: z = depth; x = ((u - cx) * z) * invfx,
+ *     y = ((v - cy) * z) * invfy with invfx = 1.0f / fx; (u, v) from d_kps_un when given, else from d_kps.  Without d_pose_wc
+ *     the point is in camera coordinates; with it (12 floats per rig: Rwc row-major, then Ow) it is
+ *     ((R0*x + R1*y) + R2*z) + t0 and so on.  Any other i < d_n[L] gets (0, 0, 0).  d_point_mask[i] = depth[i] > 0.  The row
+ *     is a point set that orbx_match_projection* and orbx_pose_optimize* take as it is.
+ *
+ * Documented deviations:
+ *  1. A window or strip that would leave its level is refused and counted (n_out_of_level), never read: sv +- 5 rows and
+ *     su +- 5 columns on the left, su0 - 10 .. su0 + 10 columns on the right.  OpenCV would throw.  For the extractor's own
+ *     keypoints it cannot happen at scale factors up to 1.5: a keypoint of level l lies at least 16 pixels of ITS level from
+ *     that level's edges (EDGE_THRESHOLD - 3), which covers the left window, and a match is at most one octave away, so at
+ *     level o the right keypoint lies at least 16 / 1.5 > 10.5 pixels inside, which covers the strip.  (At a factor of 2 a
+ *     right keypoint one octave below can come as close as 8 pixels: then the deviation is reached and counted.)  Rule 8 alone
+ *     asks su0 >= 0 only, so a hand-made keypoint reaches it at any factor.
+ *  2. M == 0: nothing to filter (median_sad 0, th_dist 0).  The design indexes an empty vector.
+ *  3. Garbage is flagged and never followed: ORBX_STEREO_BAD_INPUT for an octave outside [0, nlevels), a `row` outside
+ *     [0, rows_0), or a count outside [0, capacity] (clamped); ORBX_STEREO_NONFINITE for a non-finite coordinate.  Such a
+ *     keypoint is skipped, on either side; the rest of the rig is unaffected.
+ *  4. Results are arrays and indices.
+ * Out of scope: the stereo edges of the optimisers, the mvuRight tests of the matchers, StereoInitialization. */
+#define ORBX_STEREO_BAD_INPUT 2
+#define ORBX_STEREO_NONFINITE 4
+typedef struct orbx_stereo_result {
+  int32_t status;               /* 0, or a bitmask of ORBX_STEREO_BAD_INPUT / ORBX_STEREO_NONFINITE; every field is written for every rig */
+  int32_t n_matches;            /* after rule 12 */
+  int32_t n_with_candidates;    /* left keypoints with at least one candidate (rule 5) */
+  int32_t n_orb_matched;        /* rule 6: best < 75 */
+  int32_t n_window_refused;     /* rule 8 */
+  int32_t n_out_of_level;       /* deviation 1 */
+  int32_t n_edge;               /* rule 9: the best shift is -5 or +5 */
+  int32_t n_delta_refused;      /* rule 10 */
+  int32_t n_disparity_refused;  /* rule 11 */
+  int32_t n_clamped;            /* rule 11: disp <= 0 */
+  int32_t n_before_median;      /* M */
+  int32_t median_sad;
+  float th_dist;
+  int32_t n_removed_by_median;
+  int32_t reserved[2];          /* zero */
+} orbx_stereo_result;
+
+/* Batched, device-resident, stream-ordered on the context stream; returns once queued (with the exception
+ * orbx_bundle_adjust_batch_device has).  Host arrays h_left / h_right [n_rigs].  d_kps [n_frames][capacity], d_desc32 uint8
+ * [n_frames][capacity][32] (16-byte aligned), d_n [n_frames]: what the last extract call wrote.  Outputs, rows
+ * [n_rigs][capacity]: d_u_right, d_depth float; d_match_right, d_sad int32, nullable; d_points float [..][3] and d_point_mask
+ * uint8, nullable (rule 13: K is the host 3x3, required with d_points; d_kps_un [n_frames][capacity] nullable; d_pose_wc float
+ * [n_rigs][12] nullable); d_res [n_rigs].  Two launches: k_stereo_match over (rig, blocks of 32 left keypoints), k_stereo_filter
+ * with a workgroup per rig.  ORBX_E_BADARG, judged before anything touches a device: null required pointers, negative counts,
+ * capacity < 1, bf or b not finite or <= 0, a frame index outside [0, n_frames), h_left[p] == h_right[p], d_points without K,
+ * d_desc32 not 16-byte aligned; ORBX_E_CAPACITY: capacity > ORBX_BOW_MAX_FEATURES; ORBX_E_HIP: ctx == NULL with otherwise
+ * well-formed arguments.  n_rigs == 0 is ORBX_OK.  With a context, ORBX_E_BADARG and a message in orbx_last_error when n_frames
+ * differs from the last extract call's frame count, when there was no extract call, and while batches are in flight on lanes
+ * (orbx_set_pipeline_depth > 0 with work pending). */
+int orbx_stereo_match_batch_device(orbx_ctx* ctx, int n_frames, int n_rigs, const int32_t* h_left, const int32_t* h_right,
+                                   const orbx_keypoint* d_kps, const uint8_t* d_desc32, const int32_t* d_n, int capacity, float bf,
+                                   float b, float* d_u_right, float* d_depth, int32_t* d_match_right, int32_t* d_sad,
+                                   const orbx_keypoint* d_kps_un, const float* K, const float* d_pose_wc, float* d_points,
+                                   uint8_t* d_point_mask, orbx_stereo_result* d_res);
+/* The stereo Frame constructor for one rig in host memory: both images (width x height, row stride `stride`) go through the
+ * batched path as a batch of two, then comes the call above.  kpsL / kpsR, descL / descR hold `capacity` entries (at least the
+ * context's feature budget, as orbx_extract_batch asks), u_right / depth `capacity` floats of which the first *nL are written.
+ * Synchronous.  The call's pyramid is not kept for later calls (its level 0 lies in the context's staging block): a following
+ * orbx_stereo_match_batch_device or orbx_download_pyramid needs an extract call of its own. */
+int orbx_extract_stereo(orbx_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int stride, float bf,
+                        float b, orbx_keypoint* kpsL, uint8_t* descL, int32_t* nL, orbx_keypoint* kpsR, uint8_t* descR, int32_t* nR,
+                        int capacity, float* u_right, float* depth, orbx_stereo_result* res);
+
 /* ---- bag of words: DBoW2 TemplatedVocabulary<FORB>::transform and L1Scoring::score ---------------------------------------
  * (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1078-1270, src/BowVector.cpp:36-86, src/FeatureVector.cpp:31-45,
  * include/DBoW2/ScoringObject.h:72-88, src/ScoringObject.cpp:23-66; what Frame::mBowVec / mFeatVec hold, SlamTypes/Frame.hpp:79-81.)

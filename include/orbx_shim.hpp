@@ -956,6 +956,63 @@ class LocalMapping {
   }
 };
 
+// ---- the stereo Frame (ORB-SLAM2's Frame(imLeft, imRight, ...); include/orbx.h, "stereo: matching left and right") ----------------
+// The constructor's work on the two rectified images: ORB on both (one batch of two on the device), then
+// Frame::ComputeStereoMatches.  mvKeys / mDescriptors are the left image's, mvKeysRight / mDescriptorsRight the right one's;
+// mvuRight and mvDepth hold N entries, -1 where a keypoint has no stereo match.  UnprojectStereo is the design's, in camera
+// coordinates or through Twc (Rwc row-major, then Ow).  Argument / HIP errors throw orbx::Error.
+struct StereoFrame {
+  std::vector<KeyPointT> mvKeys, mvKeysRight;
+  std::vector<uint8_t> mDescriptors, mDescriptorsRight;  // [N][32]
+  std::vector<float> mvuRight, mvDepth;
+  int N = 0;
+  float mbf = 0.f, mb = 0.f;
+  orbx_stereo_result result{};
+
+  StereoFrame(const uint8_t* imLeft, const uint8_t* imRight, int width, int height, int stride, ORBextractor* ext, float bf, float b)
+      : mbf(bf), mb(b) {
+    if (!ext) throw orbx::Error(ORBX_E_BADARG, "StereoFrame: no ORBextractor (device context)");
+    size_t cap = 0;
+    for (int q : ext->GetNumFeaturesPerLevel()) cap += (size_t)q;
+    cap = cap ? cap : 1;
+    static_assert(sizeof(KeyPointT) == sizeof(orbx_keypoint), "KeyPoint layout");
+    mvKeys.resize(cap);
+    mvKeysRight.resize(cap);
+    mDescriptors.resize(cap * 32);
+    mDescriptorsRight.resize(cap * 32);
+    mvuRight.assign(cap, -1.f);
+    mvDepth.assign(cap, -1.f);
+    int32_t nL = 0, nR = 0;
+    const int r = orbx_extract_stereo(ext->context(), imLeft, imRight, width, height, stride, bf, b,
+                                      reinterpret_cast<orbx_keypoint*>(mvKeys.data()), mDescriptors.data(), &nL,
+                                      reinterpret_cast<orbx_keypoint*>(mvKeysRight.data()), mDescriptorsRight.data(), &nR, (int)cap,
+                                      mvuRight.data(), mvDepth.data(), &result);
+    if (r != ORBX_OK) throw orbx::Error(r, r == ORBX_E_BADARG ? "StereoFrame: an argument out of range" : orbx_last_error(ext->context()));
+    N = nL;
+    mvKeys.resize((size_t)nL);
+    mDescriptors.resize((size_t)nL * 32);
+    mvuRight.resize((size_t)nL);
+    mvDepth.resize((size_t)nL);
+    mvKeysRight.resize((size_t)nR);
+    mDescriptorsRight.resize((size_t)nR * 32);
+  }
+
+  // Frame::UnprojectStereo: false where feature i has no depth.  K row-major 3x3; Twc 12 floats or null.
+  bool UnprojectStereo(int i, const float* K, const float* Twc, float* x3D) const {
+    if (i < 0 || i >= N || !K || !x3D || !(mvDepth[(size_t)i] > 0.f)) return false;
+    const float z = mvDepth[(size_t)i], invfx = 1.0f / K[0], invfy = 1.0f / K[4];
+    const float x = ((mvKeys[(size_t)i].pt.x - K[2]) * z) * invfx, y = ((mvKeys[(size_t)i].pt.y - K[5]) * z) * invfy;
+    if (!Twc) {
+      x3D[0] = x;
+      x3D[1] = y;
+      x3D[2] = z;
+      return true;
+    }
+    for (int k = 0; k < 3; k++) x3D[k] = ((Twc[3 * k] * x + Twc[3 * k + 1] * y) + Twc[3 * k + 2] * z) + Twc[9 + k];
+    return true;
+  }
+};
+
 // ---- PnPsolver (ORB-SLAM2's PnPsolver.h; include/orbx.h, "behind SearchByBoW: PnP RANSAC") ---------------------------------------
 // The design's constructor takes the frame and vpMapPointMatches; here the map points are coordinates plus a has-point flag per
 // feature, like PoseOptimization above.  SetRansacParameters, iterate and find keep their signatures; the pose comes back as the

@@ -29,7 +29,8 @@ __all__ = ["KEYPOINT_DTYPE", "OrbxError", "ORBextractor", "ORBmatcher", "Frame",
            "MapFuser", "FuseResult", "FUSE_RESULT_DTYPE", "FUSE_BAD_INPUT", "FUSE_NONFINITE", "FUSE_OCCUPIED_UNMAPPED", "FUSE_NONE",
            "FUSE_ADD", "FUSE_KEEP_OCCUPANT", "FUSE_REPLACE_OCCUPANT", "FUSE_BAD_OCCUPANT",
            "LbaResult", "LBA_RESULT_DTYPE", "LBA_BAD_INPUT", "LBA_NONFINITE", "LBA_MAX_FREE",
-           "MapResult", "MAP_RESULT_DTYPE", "MAP_RESULT_FIELDS", "MAP_NORMALS", "MAP_DESCRIPTORS", "MAP_BAD_INPUT", "MAP_NONFINITE"]
+           "MapResult", "MAP_RESULT_DTYPE", "MAP_RESULT_FIELDS", "MAP_NORMALS", "MAP_DESCRIPTORS", "MAP_BAD_INPUT", "MAP_NONFINITE",
+           "StereoResult", "STEREO_RESULT_DTYPE", "STEREO_RESULT_FIELDS", "STEREO_BAD_INPUT", "STEREO_NONFINITE"]
 
 from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResult, HF_RESULT_DTYPE, InitResult,  # noqa: F401
                        INIT_RESULT_DTYPE, BAResult, BA_RESULT_DTYPE, PoseResult, POSE_RESULT_DTYPE, PnpResult, PNP_RESULT_DTYPE,
@@ -38,7 +39,8 @@ from ._records import (KEYPOINT_DTYPE, _Params, _Bounds, _Camera, _Stats, HFResu
                        SCW_RESULT_FIELDS, KfProjResult, KFPROJ_RESULT_DTYPE, KFPROJ_RESULT_FIELDS, MatchSim3Result,
                        MSIM3_RESULT_DTYPE, MSIM3_RESULT_FIELDS, TriMatchResult, TRI_MATCH_RESULT_DTYPE, TRI_MATCH_COUNTERS,
                        TriResult, TRI_RESULT_DTYPE, TRI_RESULT_FIELDS, FuseResult, FUSE_RESULT_DTYPE, FUSE_RESULT_FIELDS,
-                       LbaResult, LBA_RESULT_DTYPE, MapResult, MAP_RESULT_DTYPE, MAP_RESULT_FIELDS)
+                       LbaResult, LBA_RESULT_DTYPE, MapResult, MAP_RESULT_DTYPE, MAP_RESULT_FIELDS, StereoResult,
+                       STEREO_RESULT_DTYPE, STEREO_RESULT_FIELDS)
 
 E_EMPTY, E_BADARG, E_TOOSMALL, E_HIP, E_CAPACITY, E_RCCL = -1, -2, -3, -4, -5, -6
 _ERRNAMES = {-1: "ORBX_E_EMPTY", -2: "ORBX_E_BADARG", -3: "ORBX_E_TOOSMALL", -4: "ORBX_E_HIP", -5: "ORBX_E_CAPACITY", -6: "ORBX_E_RCCL"}
@@ -62,6 +64,7 @@ SIM3_BAD_INPUT, SIM3_NONFINITE, SIM3_FEW_POINTS, SIM3_BAD_DRAWS, SIM3_NO_RESULT 
 SIM3OPT_BAD_INPUT, SIM3OPT_NONFINITE = 2, 4
 LBA_BAD_INPUT, LBA_NONFINITE, LBA_MAX_FREE = 2, 4, 64
 MAP_NORMALS, MAP_DESCRIPTORS, MAP_BAD_INPUT, MAP_NONFINITE = 1, 2, 2, 4
+STEREO_BAD_INPUT, STEREO_NONFINITE = 2, 4
 PROJ_BAD_INPUT, PROJ_NONFINITE = 2, 4
 LOCAL_BAD_INPUT, LOCAL_NONFINITE, LOCAL_NOT_IN_VIEW, LOCAL_SEEN = 2, 4, 0xFF, 0xFE
 SCW_BAD_INPUT, SCW_NONFINITE, SCW_TAKEN_UNMAPPED = 2, 4, -2
@@ -272,6 +275,10 @@ def lib() -> ctypes.CDLL:
     L.orbx_map_update_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp,
                                                i32, vp, vp, vp, vp, vp]
     L.orbx_map_update.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, ctypes.POINTER(MapResult)]
+    L.orbx_stereo_match_batch_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp,
+                                                 vp, vp, vp]
+    L.orbx_extract_stereo.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp, vp, i32, vp, vp,
+                                      ctypes.POINTER(StereoResult)]
     L.orbx_vocabulary_parse_text.argtypes = [ctypes.c_char_p, vp, vp, vp, vp, vp, vp, i32]
     L.orbx_vocabulary_create.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.orbx_vocabulary_load_text.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -1623,6 +1630,47 @@ class ORBextractor:
         return res, dict(rows=r, mask=mask_out[:N], ref=None if ref is None else ref[:N], obs=obs[:N], normals=nrm[:N], dist=dst[:N],
                          desc=dsc[:N])
 
+    # -- the stereo Frame (include/orbx.h, "stereo: matching left and right") -------------------------------------------------
+    def stereo_match_rigs_device(self, n_frames: int, left, right, d_kps, d_desc, d_n, bf: float, b: float, d_u_right, d_depth, d_res,
+                                 d_match_right=None, d_sad=None, d_kps_un=None, K=None, d_pose_wc=None, d_points=None,
+                                 d_point_mask=None, capacity: Optional[int] = None) -> None:
+        """Frame::ComputeStereoMatches for rigs (left frame left[p], right frame right[p]; host index arrays) of the LAST
+        extract_batch_device call, whose pyramid is still resident (its d_imgs must still be there: level 0 is read in place).
+        d_kps / d_desc / d_n are that call's outputs (raw mvKeys).  Rows [n_rigs, capacity]: d_u_right, d_depth float32 (mvuRight,
+        mvDepth; -1 = none), optional d_match_right, d_sad int32; with d_points float32 [n_rigs, capacity, 3] (and K) the
+        matches are unprojected as Frame::UnprojectStereo does, (u, v) from d_kps_un when given, through d_pose_wc float32
+        [n_rigs, 12] (Rwc row-major, then Ow) when given, d_point_mask uint8 [n_rigs, capacity] = depth > 0: a point set for
+        match_projection_pairs_device / pose_optimize_batch_device.  d_res [n_rigs] STEREO_RESULT_DTYPE records (64 bytes).
+        Stream-ordered."""
+        left, right = _pair_lists(("left", "right"), (left, right))
+        cap, nf, P = int(capacity or self.capacity), int(n_frames), len(left)
+        self._device_call("orbx_stereo_match_batch_device", nf, P, left, right, ("the keypoint array", d_kps, nf * cap * 28),
+                          ("the descriptor array", d_desc, nf * cap * 32), ("the count array", d_n, nf * 4), cap, float(bf), float(b),
+                          ("the u_right array", d_u_right, P * cap * 4), ("the depth array", d_depth, P * cap * 4),
+                          ("the right-match array", d_match_right, P * cap * 4), ("the SAD array", d_sad, P * cap * 4),
+                          ("the undistorted keypoint array", d_kps_un, nf * cap * 28), None if K is None else _k9(K),
+                          ("the pose array", d_pose_wc, P * 48), ("the point array", d_points, P * cap * 12),
+                          ("the point mask", d_point_mask, P * cap), ("the result array", d_res, P * STEREO_RESULT_DTYPE.itemsize))
+
+    def extract_stereo(self, left: np.ndarray, right: np.ndarray, bf: float, b: float):
+        """The stereo Frame constructor for one rig in host memory (orbx_extract_stereo): both images through the extractor as a
+        batch of two, then Frame::ComputeStereoMatches.  Returns ((keysL, descL), (keysR, descR), mvuRight, mvDepth,
+        StereoResult), mvuRight / mvDepth float32 [len(keysL)] with -1 where there is no match.  Synchronous."""
+        imgs = [np.ascontiguousarray(im) for im in (left, right)]
+        if any(im.dtype != np.uint8 or im.ndim != 2 for im in imgs) or imgs[0].shape != imgs[1].shape:
+            raise OrbxError(E_BADARG, "left and right must be 2-D uint8 arrays of one shape")
+        h, w = imgs[0].shape
+        cap = self.capacity
+        kps, desc = np.zeros((2, cap), KEYPOINT_DTYPE), np.zeros((2, cap, 32), np.uint8)
+        n = np.zeros(2, np.int32)
+        ur, z = np.full(cap, -1, np.float32), np.full(cap, -1, np.float32)
+        res = StereoResult()
+        self._check(self._L.orbx_extract_stereo(self._h, _ptr(imgs[0]), _ptr(imgs[1]), w, h, w, float(bf), float(b), _ptr(kps[0]), _ptr(desc[0]),
+                                                _ptr(n[0:1]), _ptr(kps[1]), _ptr(desc[1]), _ptr(n[1:2]), cap, _ptr(ur), _ptr(z),
+                                                ctypes.byref(res)), "orbx_extract_stereo")
+        nl, nr = int(n[0]), int(n[1])
+        return (kps[0, :nl].copy(), desc[0, :nl].copy()), (kps[1, :nr].copy(), desc[1, :nr].copy()), ur[:nl].copy(), z[:nl].copy(), res
+
     # -- PnPsolver behind SearchByBoW (include/orbx.h, "behind SearchByBoW: PnP RANSAC") ------------------------
     def pnp_solve(self, keys_un, points, mask, K, draws, sigma2=None, probability: float = 0.99, min_inliers: int = 10,
                   max_iterations: int = 300, epsilon: float = 0.5, th2: float = 5.991):
@@ -2418,6 +2466,7 @@ class Frame:
             self.bounds = extractor.image_bounds(self.camera, w, h)  # Frame.cpp:44
         else:
             self.bounds = (0, w, 0, h)  # mnMinX, mnMaxX, mnMinY, mnMaxY (Frame.cpp:127-131)
+        self._image = im  # (ComputeStereoMatches correlates on the images)
         _, self.mvKeys, self.mDescriptors = extractor(im, None, (0, 0))
         if self.camera is not None and len(self.mvKeys):
             self.mvKeysUn = extractor.undistort_keypoints(self.mvKeys, self.camera)  # Frame.cpp:64
@@ -2436,6 +2485,38 @@ class Frame:
         f.N = len(f.mvKeysUn)
         f.bounds = tuple(int(v) for v in bounds)
         return f
+
+    def ComputeStereoMatches(self, right_frame: "Frame", bf: float, b: float):
+        """Frame::ComputeStereoMatches against the right image's frame (include/orbx.h, "stereo: matching left and right"): sets
+        mvuRight / mvDepth (float32 [N], -1 = no match), mbf and mb, and returns the StereoResult.  Both frames must come from
+        images of one size; they are extracted again as a batch of two, which is what leaves their pyramids side by side on the
+        device (the keypoints are the same bytes)."""
+        ext = self.mpORBextractor or right_frame.mpORBextractor
+        if ext is None or getattr(self, "_image", None) is None or getattr(right_frame, "_image", None) is None:
+            raise OrbxError(E_BADARG, "Frame.ComputeStereoMatches needs two frames made from images (Frame(im, ...))")
+        (kl, _), _, self.mvuRight, self.mvDepth, res = ext.extract_stereo(self._image, right_frame._image, bf, b)
+        if kl.tobytes() != _keys(self.mvKeys).tobytes():
+            raise OrbxError(E_BADARG, "Frame.ComputeStereoMatches: the frame's keypoints are not its image's")
+        self.mbf, self.mb = float(bf), float(b)
+        return res
+
+    def UnprojectStereo(self, i: int, Twc=None):
+        """Frame::UnprojectStereo: the 3-D point of feature i from mvDepth (float32 [3]; in camera coordinates unless Twc, 12
+        floats or a 3x4 / 4x4 matrix, is given), or None where the feature has no depth.  The arithmetic is rule 13's."""
+        z = np.float32(self.mvDepth[i])
+        if not z > 0:
+            return None
+        cam = self.camera if self.camera is not None else getattr(self, "stereo_camera", None)
+        if cam is None:
+            raise OrbxError(E_BADARG, "Frame.UnprojectStereo needs a camera (Frame(..., K=, distCoef=) or frame.stereo_camera = (fx, fy, cx, cy))")
+        f32 = np.float32
+        fx, fy, cx, cy = (f32(v) for v in cam[:4])
+        u, v = f32(self.mvKeysUn["x"][i]), f32(self.mvKeysUn["y"][i])
+        x, y = f32(f32(f32(u - cx) * z) * f32(f32(1) / fx)), f32(f32(f32(v - cy) * z) * f32(f32(1) / fy))
+        if Twc is None:
+            return np.array([x, y, z], f32)
+        T = _pose12(Twc)
+        return np.array([f32(f32(f32(f32(T[3 * k] * x) + f32(T[3 * k + 1] * y)) + f32(T[3 * k + 2] * z)) + T[9 + k]) for k in range(3)], f32)
 
     def ComputeBoW(self, levelsup: int = 4) -> None:
         """Frame::ComputeBoW: once, mBowVec {word id: value} and mFeatVec {node id: [feature indices]}, both in ascending key

@@ -4,7 +4,8 @@ pair under its C struct's name; tests/test_abi_host.py compiles a probe against 
 RECORDS_FUSE is a second table of the same form for the records of "fusing map points into a keyframe"
 (tests/test_fuse_abi_host.py probes it the same way), RECORDS_LBA a third for the record of "local mapping: local bundle
 adjustment" (tests/test_lba_abi_host.py), RECORDS_MAP a fourth for the record of "local mapping: updating the map points"
-(tests/test_map_update_abi_host.py)."""
+(tests/test_map_update_abi_host.py), RECORDS_STEREO a fifth for the record of "stereo: matching left and right"
+(tests/test_stereo_abi_host.py)."""
 from __future__ import annotations
 
 import ctypes
@@ -17,6 +18,7 @@ RECORDS = {}  # C struct name -> (ctypes.Structure subclass or None, numpy dtype
 RECORDS_FUSE = {}  # the same for orbx_fuse_result
 RECORDS_LBA = {}  # the same for orbx_lba_result
 RECORDS_MAP = {}  # the same for orbx_map_result
+RECORDS_STEREO = {}  # the same for orbx_stereo_result
 
 
 def _as_dict(self) -> dict:
@@ -208,3 +210,13 @@ MapResult, MAP_RESULT_DTYPE = _record(
     """orbx_map_result: what the update of the map points behind a local bundle adjustment did for one problem (n_erased:
     vToErase applied; n_bad_points: EraseObservation's SetBadFlag).""", table=RECORDS_MAP)
 assert MAP_RESULT_DTYPE.itemsize == 64
+
+STEREO_RESULT_FIELDS = ("status", "n_matches", "n_with_candidates", "n_orb_matched", "n_window_refused", "n_out_of_level", "n_edge",
+                        "n_delta_refused", "n_disparity_refused", "n_clamped", "n_before_median", "median_sad", "th_dist",
+                        "n_removed_by_median")
+StereoResult, STEREO_RESULT_DTYPE = _record(
+    "orbx_stereo_result", "StereoResult",
+    [(n, "f4" if n == "th_dist" else "i4") for n in STEREO_RESULT_FIELDS] + [("reserved", "i4", 2, list)],
+    """orbx_stereo_result: what Frame::ComputeStereoMatches did for one rig, a counter per place a left keypoint can end in
+    (n_before_median: the matches rule 11 kept; n_matches: those the median filter left).""", table=RECORDS_STEREO)
+assert STEREO_RESULT_DTYPE.itemsize == 64

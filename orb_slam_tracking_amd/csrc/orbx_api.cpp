@@ -189,6 +189,7 @@ struct orbx_ctx : ExtractorSetup {
   LbaScratch lba;                 // orbx_local_ba* (orbx_ba.cpp)
   MapScratch map;                 // orbx_map_update* (orbx_ba.cpp)
   TriScratch tri;                 // orbx_match_triangulation*, orbx_triangulate_matches* (orbx_match_bow.cpp)
+  StereoScratch stereo;           // orbx_stereo_match* (this file)
 
   // last extract call (for orbx_download_pyramid / debug hooks)
   const uint8_t* lastImg0 = nullptr;
@@ -2595,6 +2596,152 @@ int orbx_debug_std_sort(orbx_ctx* ctx, int32_t* triples, int n) {
   HIPCHK(hipMemcpyAsync(triples, d, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
   return ORBX_OK;
+}
+
+// ---- stereo: matching left and right (include/orbx.h; kernels in orbx_stereo_kernel.hip).  The host side lives here because it
+// reads what only this file knows: the last extract call's frames, its geometry and the pyramid buffer. ----
+
+int orbx_stereo_match_batch_device(orbx_ctx* ctx, int n_frames, int n_rigs, const int32_t* h_left, const int32_t* h_right,
+                                   const orbx_keypoint* d_kps, const uint8_t* d_desc32, const int32_t* d_n, int capacity, float bf,
+                                   float b, float* d_u_right, float* d_depth, int32_t* d_match_right, int32_t* d_sad,
+                                   const orbx_keypoint* d_kps_un, const float* K, const float* d_pose_wc, float* d_points,
+                                   uint8_t* d_point_mask, orbx_stereo_result* d_res) {
+  if (n_frames < 0 || n_rigs < 0 || capacity < 1 || (n_rigs > 0 && (!h_left || !h_right)) || !d_kps || !d_desc32 || !d_n || !d_u_right ||
+      !d_depth || !d_res || !std::isfinite(bf) || !std::isfinite(b) || !(bf > 0.0f) || !(b > 0.0f) || (d_points && !K) ||
+      ((uintptr_t)d_desc32 & 15) != 0)
+    return ORBX_E_BADARG;
+  for (int p = 0; p < n_rigs; p++)
+    if (h_left[p] < 0 || h_left[p] >= n_frames || h_right[p] < 0 || h_right[p] >= n_frames || h_left[p] == h_right[p]) {
+      if (ctx) ctx->err = "stereo: a rig names a frame outside [0, n_frames), or one frame twice";
+      return ORBX_E_BADARG;
+    }
+  if (capacity > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctx->err = "stereo: capacity above ORBX_BOW_MAX_FEATURES";
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;  // no device context
+  if (n_rigs == 0) return ORBX_OK;
+  if (ctx->laneDone != ctx->laneIssue) {
+    ctx->err = "stereo: batches are in flight on the pipeline's lanes; wait for them first";
+    return ORBX_E_BADARG;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
+  {
+    const int r = waitAll(ctx);  // (a stream-ordered extract call may still be writing the pyramid on the second stream)
+    if (r != ORBX_OK) return r;
+  }
+  if (ctx->lastB == 0 || !ctx->lastImg0) {
+    ctx->err = "stereo: no extract call has run on this context: there is no pyramid to correlate on";
+    return ORBX_E_BADARG;
+  }
+  if (n_frames != ctx->lastB) {
+    ctx->err = "stereo: n_frames differs from the frame count of the last extract call";
+    return ORBX_E_BADARG;
+  }
+  const int nl = ctx->p.nlevels;
+  StereoLevel lev[ORBX_MAX_LEVELS]{};
+  for (int l = 0; l < nl; l++) {
+    const LevelGeom& L = ctx->g.L[l];
+    lev[l].imgOff = l == 0 ? 0 : L.imgOff;
+    lev[l].frameStride = l == 0 ? ctx->lastFrameStride0 : L.frameStride;
+    lev[l].cols = L.w;
+    lev[l].rows = L.h;
+    lev[l].stride = L.stride;
+    lev[l].scale = ctx->scale[l];
+    lev[l].invScale = ctx->invScale[l];
+  }
+  if (lev[0].rows > 32767) {
+    ctx->err = "stereo: frames of more than 32767 rows";
+    return ORBX_E_CAPACITY;
+  }
+  StereoScratch* s = &ctx->stereo;
+  hipStream_t st = ctx->st;
+  HeldUploads hold(st);
+  HIPCHK(hold(s->rigs, {h_left, h_right}, (size_t)n_rigs));
+  HIPCHK(hold(s->levels, {(const uint8_t*)lev}, (size_t)nl * sizeof(StereoLevel)));
+  HIPCHK(s->dWs.grow((size_t)n_rigs * STEREO_WS * sizeof(int32_t), st));
+  if (!d_sad) HIPCHK(s->dSad.grow((size_t)n_rigs * capacity * sizeof(int32_t), st));
+  StereoArgs a{};
+  a.kps = d_kps;
+  a.desc = d_desc32;
+  a.nKps = d_n;
+  a.rigs = s->rigs;
+  a.img0 = ctx->lastImg0;
+  a.pyr = ctx->bufs.dPyr;
+  a.lev = (const StereoLevel*)(const uint8_t*)s->levels;
+  a.uRight = d_u_right;
+  a.depth = d_depth;
+  a.matchRight = d_match_right;
+  a.sad = d_sad ? d_sad : (int32_t*)s->dSad;
+  a.ws = s->dWs;
+  a.kpsUn = d_kps_un;
+  a.poseWc = d_pose_wc;
+  a.points = d_points;
+  a.pointMask = d_point_mask;
+  a.res = d_res;
+  a.bf = bf;
+  a.maxD = bf / b;
+  if (K) {
+    a.cx = K[2];
+    a.cy = K[5];
+    a.invfx = 1.0f / K[0];
+    a.invfy = 1.0f / K[4];
+  }
+  a.nRigs = n_rigs;
+  a.cap = capacity;
+  a.nLevels = nl;
+  HIPCHK(launch_stereo(st, a));
+  return ORBX_OK;
+}
+
+int orbx_extract_stereo(orbx_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int stride, float bf,
+                        float b, orbx_keypoint* kpsL, uint8_t* descL, int32_t* nL, orbx_keypoint* kpsR, uint8_t* descR, int32_t* nR,
+                        int capacity, float* u_right, float* depth, orbx_stereo_result* res) {
+  if (!left || !right || width < 1 || height < 1 || stride < width || capacity < 1 || !kpsL || !descL || !nL || !kpsR || !descR || !nR ||
+      !u_right || !depth || !res || !std::isfinite(bf) || !std::isfinite(b) || !(bf > 0.0f) || !(b > 0.0f))
+    return ORBX_E_BADARG;
+  if (capacity > ORBX_BOW_MAX_FEATURES) {
+    if (ctx) ctx->err = "stereo: capacity above ORBX_BOW_MAX_FEATURES";
+    return ORBX_E_CAPACITY;
+  }
+  if (!ctx) return ORBX_E_HIP;
+  if (hipSetDevice(ctx->device) != hipSuccess) return ORBX_E_HIP;
+  int r = waitAll(ctx);
+  if (r != ORBX_OK) return r;
+  // the two frames as a batch of two in the staging block, with the caller's stride: level 0 is read there
+  const size_t c = (size_t)capacity, rowBytes = (size_t)stride * (height - 1) + width, fs = alignUp((size_t)stride * height, (size_t)256);
+  int32_t n2[2] = {0, 0};
+  Staged io(ctx->io, ctx->st);
+  auto dImg = io.room<uint8_t>(2 * fs);
+  io.in(dImg, 0, left, rowBytes);
+  io.in(dImg, fs, right, rowBytes);
+  auto dK = io.room<orbx_keypoint>(2 * c);
+  io.out(dK, 0, kpsL, c);
+  io.out(dK, c, kpsR, c);
+  auto dD = io.room<uint8_t>(2 * c * 32);
+  io.out(dD, 0, descL, c * 32);
+  io.out(dD, c * 32, descR, c * 32);
+  auto dN = io.out(n2, 2, 2);
+  auto dU = io.out(u_right, c, c);
+  auto dZ = io.out(depth, c, c);
+  auto dR = io.out(res, 1, 1);
+  HIPCHK(io.open(Staged::Zeroed));
+  r = extractCore(ctx, 2, io[dImg], width, height, stride, (long long)fs, io[dK], io[dD], capacity, io[dN], nullptr);
+  if (r == ORBX_OK) {
+    static const int32_t leftFrame = 0, rightFrame = 1;
+    r = orbx_stereo_match_batch_device(ctx, 2, 1, &leftFrame, &rightFrame, io[dK], io[dD], io[dN], capacity, bf, b, io[dU], io[dZ], nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, io[dR]);
+  }
+  r = io.close(ctx, r);
+  // level 0 of this batch lies in the staging block, which the next single-problem call may overwrite or move: no later call may
+  // take it for a resident pyramid
+  ctx->lastImg0 = nullptr;
+  ctx->lastB = 0;
+  if (r == ORBX_OK) {
+    *nL = n2[0];
+    *nR = n2[1];
+  }
+  return r;
 }
 
 }  // extern "C"

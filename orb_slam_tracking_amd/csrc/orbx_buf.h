@@ -253,4 +253,12 @@ struct MapScratch {
   DeviceBuf<uint8_t> dWork;     // the problems' workspaces: MapWork of orbx_device.h
 };
 
+// What a context keeps for orbx_stereo_match* (orbx_api.cpp).
+struct StereoScratch {
+  HeldArray<int32_t> rigs;  // [2][n_rigs] (left frame, right frame) of the last call
+  HeldArray<uint8_t> levels;  // the last extract call's levels, StereoLevel of orbx_device.h [nlevels]
+  DeviceBuf<int32_t> dWs;   // [n_rigs][STEREO_WS] the rigs' counters
+  DeviceBuf<int32_t> dSad;  // [n_rigs][capacity] the kept SADs when the caller takes none
+};
+
 }  // namespace orbx

@@ -982,4 +982,39 @@ struct MapArgs {
   uint8_t* ws;                // the problems' workspaces
   int32_t nProblems, cap, mapCap, nLevels, what;
 };
+// k_stereo_match, k_stereo_filter: Frame::ComputeStereoMatches for rigs of one extract batch (include/orbx.h, "stereo: matching left
+// and right")
+constexpr int STEREO_THREADS = 256;                            // both kernels
+constexpr int STEREO_WAVES = STEREO_THREADS / 64;              // k_stereo_match: one left keypoint per wave at a time
+constexpr int STEREO_PER_WAVE = 8;                             // ... and this many one after the other
+constexpr int STEREO_BLOCK = STEREO_WAVES * STEREO_PER_WAVE;   // left keypoints per workgroup
+constexpr int STEREO_CHUNK = 2048;                             // right keypoints whose records are in LDS at a time
+constexpr int STEREO_WS = 16;                                  // int32 words of a rig's counters (orbx_stereo_math.inc's Counter)
+struct StereoLevel {  // a pyramid level as the correlation reads it (40 bytes, no padding: held by memcmp)
+  int64_t imgOff;       // levels >= 1: byte offset of frame 0's image inside the pyramid buffer; level 0: 0
+  int64_t frameStride;  // bytes between consecutive frames (level 0: the caller's)
+  int32_t cols, rows, stride, pad;
+  float scale, invScale;
+};
+struct StereoArgs {
+  const orbx_keypoint* kps;  // [frames][cap] mvKeys
+  const uint8_t* desc;       // [frames][cap][32], 16-byte aligned
+  const int32_t* nKps;       // [frames]
+  const int32_t* rigs;       // [2][nRigs]: left frame, right frame
+  const uint8_t* img0;       // level 0 of frame 0: the last extract call's frames, read in place
+  const uint8_t* pyr;        // levels >= 1
+  const StereoLevel* lev;    // [nLevels] (device)
+  float* uRight;             // [nRigs][cap]
+  float* depth;              // [nRigs][cap]
+  int32_t* matchRight;       // [nRigs][cap] or null
+  int32_t* sad;              // [nRigs][cap]: the caller's, or the context's own
+  int32_t* ws;               // [nRigs][STEREO_WS], zero before k_stereo_match
+  const orbx_keypoint* kpsUn;  // [frames][cap] or null: k_stereo_filter's (u, v)
+  const float* poseWc;       // [nRigs][12] or null
+  float* points;             // [nRigs][cap][3] or null
+  uint8_t* pointMask;        // [nRigs][cap] or null
+  orbx_stereo_result* res;   // [nRigs]
+  float bf, maxD, cx, cy, invfx, invfy;
+  int32_t nRigs, cap, nLevels;
+};
 }  // namespace orbx

@@ -120,4 +120,7 @@ hipError_t launch_lba(hipStream_t st, const LbaArgs& a);
 // orbx_map_kernel.hip: k_map_build, then (what != 0) k_map_points
 hipError_t launch_map_update(hipStream_t st, const MapArgs& a);
 
+// orbx_stereo_kernel.hip: a.ws zeroed, k_stereo_match, k_stereo_filter
+hipError_t launch_stereo(hipStream_t st, const StereoArgs& a);
+
 }  // namespace orbx
